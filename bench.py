@@ -13,7 +13,13 @@ steps.  Inputs are resident in HBM when the timed region starts.
 
 One process per GPU.  Scenes are independent units, so N ranks run N scene streams with no data-path collective (weak
 scaling); the only collectives are the timing barrier and the max-over-ranks of the elapsed time.  Rank 0 prints ONE JSON line.
-Per-kernel figures come from event pairs the product path records on its launch stream while the timed steps run
+
+A plain run sets up, warms up, times the K steps and prints the headline (scenes/s, ms_per_step, per-step percentiles).
+``--dump-outputs DIR`` writes the detections of the last timed step as DIR/<name>.npy (float32); inputs and weights are seeded, so two
+builds given the same arguments can be compared output for output.  ``--full`` adds everything else the benchmark measures:
+the per-kernel event spans and stage times of the timed steps, the HBM copy ceiling, the rooflines, the two-scenes-in-flight loop, the
+interleaved bf16x3 comparison, the CPU baseline and the training-step probe.
+Per-kernel figures (``--full``) come from event pairs the product path records on its launch stream while the timed steps run
 (nerfdet_amd/trace.py): `roofline` = the dominant hand-written kernel of the step (the convolution instantiation with the largest
 share) against the matrix-core peak of its arithmetic; `roofline_all_convolutions` aggregates every convolution launch;
 `roofline_memory_bound_convolutions` prices the launches whose arithmetic intensity lies below the machine's ridge point (the
@@ -162,6 +168,17 @@ def to_device(batch, device):
     for k, v in batch.items():
         out[k] = v.to(device) if isinstance(v, torch.Tensor) else v
     return out
+
+
+def dump_outputs(directory, res, rank):
+    """What a caller of ``forward_test`` receives for the step's one scene -- boxes (K, 7), scores (K,), labels (K,) -- as
+    DIR/{boxes_3d,scores_3d,labels_3d}.npy in float32 (class ids are exact in fp32); ranks r > 0 add ``_rank<r>`` to the names."""
+    import numpy as np
+    (scene,) = res
+    os.makedirs(directory, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, t in (("boxes_3d", scene["boxes_3d"].tensor), ("scores_3d", scene["scores_3d"]), ("labels_3d", scene["labels_3d"])):
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), t.detach().to("cpu", torch.float32).numpy())
 
 
 def cpu_baseline(w, det_cpu, batch, scenes=5, warmups=2):
@@ -327,11 +344,14 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train-probe", action="store_true", help="skip the cfg3 training-step figure (tools/bench_train.py in a child process after the "
-                    "timed region; BENCH records then carry a driver-run training number: key train_cfg3_step)")
-    ap.add_argument("--no-serving", action="store_true", help="skip the extra two-scenes-in-flight loop after the timed region (profiling runs: its "
-                    "overlapped launches would enter the per-kernel averages)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-kernel spans and stage times of the timed steps, HBM copy ceiling, "
+                    "rooflines, two-scenes-in-flight loop, bf16x3 comparison, CPU baseline, training-step probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the detections of the last timed step to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-train-probe", action="store_true", help="with --full: skip the cfg3 training-step figure (tools/bench_train.py in a child "
+                    "process after the timed region; BENCH records then carry a driver-run training number: key train_cfg3_step)")
+    ap.add_argument("--no-serving", action="store_true", help="with --full: skip the extra two-scenes-in-flight loop after the timed region (profiling "
+                    "runs: its overlapped launches would enter the per-kernel averages)")
     ap.add_argument("--graph", action="store_true",
                     help="replay the static part of the step from hipGraphs (nerfdet_amd/graphed.py); measured equal to eager "
                          "launches within 1 %% on MI355X: the step is GPU-bound, launch-ahead already hides the gaps")
@@ -374,8 +394,10 @@ def main():
 
     state = {"step": 0}
     # ~150 conv launches per step: their event pairs cost ~2 % of the step, so they are sampled on every SPAN_EVERY-th timed step (see the constant); the two
-    # gather kernels and the five stage marks are recorded on every step
-    rec = trace.Recorder(sample=lambda name: (not name.startswith(("k_conv", "k_bottleneck", "k_point_mlp", "f32:", "bf16x3:", "f16x2:", "bf16:"))) or state["step"] % SPAN_EVERY == 0)
+    # gather kernels and the five stage marks are recorded on every step.  A plain run records none of them (trace.recorder stays None).
+    rec = None
+    if args.full:
+        rec = trace.Recorder(sample=lambda name: (not name.startswith(("k_conv", "k_bottleneck", "k_point_mlp", "f32:", "bf16x3:", "f16x2:", "bf16:"))) or state["step"] % SPAN_EVERY == 0)
 
     if args.graph:
         from nerfdet_amd.graphed import GraphedForwardTest
@@ -417,6 +439,45 @@ def main():
     dt = max_over_ranks(dt, device)
     per_step = sorted((b - a) * 1e3 for a, b in zip(ticks, ticks[1:]))
     pct = lambda q: per_step[min(len(per_step) - 1, int(round(q * (len(per_step) - 1))))]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rank)
+
+    def headline():
+        return {
+            "metric": f"scenes/sec ({w['n_views']}-view {w['img_hw'][0]}x{w['img_hw'][1]}, {'x'.join(map(str, w['n_voxels']))} voxels)",
+            "value": world * args.steps / dt,
+            "unit": "scenes/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "median_ms": pct(0.5), "p10_ms": pct(0.1), "p90_ms": pct(0.9),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": {"f32": "f32", "f16x2": "f32 (convolutions: fp32 operands as hi + lo fp16 pairs of the power-of-two pre-scaled tensors, three products per "
+                               "multiply on the fp16 MFMA, fp32 accumulate; error against fp64 at or below the six-product bf16x3 form's; a device-side range "
+                               "guard repeats a scene on bf16x3 when part of a tensor falls outside the pair's window: range_guard_trips)",
+                      "bf16x3": "f32 (convolutions: fp32 operands as exact 3-term bf16 sums on the bf16 MFMA, fp32 accumulate)",
+                      "bf16": "bf16 (convolution operands rounded to bf16 on the MFMA, fp32 accumulate; activations, projection, aggregation, "
+                              "NMS fp32 -- SURVEY.md 0.1)"}[C3.ARITHMETIC],
+            "data": "synthetic",
+            "config": {"workload": f"{args.workload}: nerfdet_res{w['depth']}_2x_low_res forward_test, {w['n_views']} views "
+                                   f"{w['img_hw'][0]}x{w['img_hw'][1]}, {'x'.join(map(str, w['n_voxels']))} voxels, "
+                                   f"{'bf16 convolutions' if C3.ARITHMETIC == 'bf16' else 'fp32'}, 1 scene/step/GPU, random-init weights",
+                       "scenes_per_step": world, "parallelism": f"scene replicas x{world} (no data-path collective)"},
+            "collectives": (f"{torch.distributed.get_backend()} (timing barrier + max-over-ranks only)" if grouped else "none (bare single process)"),
+            "execution": "hipGraph replay (2 graphs) + eager K1 + eager post-processing" if args.graph else "eager launches",
+            "detections_last_step": int(len(res[0]["scores_3d"])),
+            "range_guard_trips": C3.guard_trips,      # scenes repeated on bf16x3 because a fp16-pair launch reported a visible absolute error floor (expected: 0)
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()))
+        if grouped:
+            torch.distributed.destroy_process_group()
+        return
 
     n_conv_steps = len([i for i in range(args.steps) if i % SPAN_EVERY == 0])
     if args.graph:  # per-kernel breakdown from a few eager steps outside the timed region (events cannot sit inside a graph)
@@ -542,29 +603,8 @@ def main():
                     "algorithmic_bytes": abytes, "avg_launch_ms": avg, "median_launch_ms": ms[len(ms) // 2], "launches": len(ms)}
 
         out = {
-            "metric": f"scenes/sec ({w['n_views']}-view {w['img_hw'][0]}x{w['img_hw'][1]}, {'x'.join(map(str, w['n_voxels']))} voxels)",
-            "value": world * args.steps / dt,
-            "unit": "scenes/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "median_ms": pct(0.5), "p10_ms": pct(0.1), "p90_ms": pct(0.9),
+            **headline(),
             "hbm_copy_ceiling_gbs": copy["best"], "hbm_copy_ceiling": copy,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": {"f32": "f32", "f16x2": "f32 (convolutions: fp32 operands as hi + lo fp16 pairs of the power-of-two pre-scaled tensors, three products per "
-                               "multiply on the fp16 MFMA, fp32 accumulate; error against fp64 at or below the six-product bf16x3 form's; a device-side range "
-                               "guard repeats a scene on bf16x3 when part of a tensor falls outside the pair's window: range_guard_trips)",
-                      "bf16x3": "f32 (convolutions: fp32 operands as exact 3-term bf16 sums on the bf16 MFMA, fp32 accumulate)",
-                      "bf16": "bf16 (convolution operands rounded to bf16 on the MFMA, fp32 accumulate; activations, projection, aggregation, "
-                              "NMS fp32 -- SURVEY.md 0.1)"}[C3.ARITHMETIC],
-            "data": "synthetic",
-            "config": {"workload": f"{args.workload}: nerfdet_res{w['depth']}_2x_low_res forward_test, {w['n_views']} views "
-                                   f"{w['img_hw'][0]}x{w['img_hw'][1]}, {'x'.join(map(str, w['n_voxels']))} voxels, "
-                                   f"{'bf16 convolutions' if C3.ARITHMETIC == 'bf16' else 'fp32'}, 1 scene/step/GPU, random-init weights",
-                       "scenes_per_step": world, "parallelism": f"scene replicas x{world} (no data-path collective)"},
             "roofline": {"kernel": f"{dom_name} (the convolution kernel with the largest share of the step, tile instantiations {sorted(dom_members)} "
                                    f"together; event spans include the split-K reduce launch where a layer splits K; traffic: {dom_big})",
                          "bound": "mfma", "achieved": dom_tflops, "peak": dom_peak, "unit": "TFLOP/s",
@@ -596,11 +636,7 @@ def main():
                                             k1_algorithmic_bytes(w)),
             "roofline_density_features": hbm_line("k_density_features", "k_density_features (K2: mapped features + RGB -> per-voxel mean / exp(-var) rows)",
                                                   k2_algorithmic_bytes(w)),
-            "collectives": (f"{torch.distributed.get_backend()} (timing barrier + max-over-ranks only)" if grouped else "none (bare single process)"),
-            "execution": "hipGraph replay (2 graphs) + eager K1 + eager post-processing" if args.graph else "eager launches",
             "stages_ms": stages,
-            "detections_last_step": int(len(res[0]["scores_3d"])),
-            "range_guard_trips": C3.guard_trips,      # scenes repeated on bf16x3 because a fp16-pair launch reported a visible absolute error floor (expected: 0)
         }
         if serving is not None:
             out["serving_two_scenes_in_flight"] = {

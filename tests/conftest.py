@@ -34,6 +34,25 @@ def golden_meta(g):
         ori_shape=tuple(int(v) for v in g["ori_shape"]), img_shape=tuple(int(v) for v in g["img_shape"]))
 
 
+def reference_config_names():
+    """File names of the reference's configs/nerfdet/*.py, as stored in golden/nerfdet_configs.json."""
+    import json
+    with open(os.path.join(GOLDEN, "nerfdet_configs.json")) as f:
+        return sorted(json.load(f))
+
+
+def reference_config(directory, name):
+    """Path of a flat config file that ``Config.fromfile`` reads as the reference's configs/nerfdet/<name>: the values stored in
+    golden/nerfdet_configs.json (make_golden_configs.py) written out as one ``key = literal`` line each."""
+    import json
+    with open(os.path.join(GOLDEN, "nerfdet_configs.json")) as f:
+        cfg = json.load(f, object_hook=lambda d: tuple(d["__tuple__"]) if set(d) == {"__tuple__"} else d)[name]
+    path = os.path.join(str(directory), name)
+    with open(path, "w") as f:
+        f.writelines(f"{k} = {v!r}\n" for k, v in cfg.items())
+    return path
+
+
 def sub_state(g, prefix):
     return {k[len(prefix):]: torch.as_tensor(v) for k, v in g.items() if k.startswith(prefix)}
 

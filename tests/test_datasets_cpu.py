@@ -5,10 +5,10 @@ import os
 import pickle
 
 import numpy as np
-import pytest
 import torch
 
-REF_CFG = "/root/reference/configs/nerfdet"
+from conftest import reference_config
+
 CLASSES = None
 
 
@@ -56,13 +56,12 @@ def _data_cfg(root, ann, hw=(48, 64), n_images=5, targets=2, train=True):
     return dict(type="RepeatDataset", times=3, dataset=ds) if train else ds
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference configs only exist in the build container")
-def test_reference_cfg_data_builds_unmodified():
+def test_reference_cfg_data_builds_unmodified(tmp_path):
     from nerfdet_amd.config import Config
     from nerfdet_amd.datasets import MultiViewPipeline, RandomShiftOrigin, RepeatDataset, ScanNetMultiViewDataset
     from nerfdet_amd.registry import build_dataset
     for f in ("nerfdet_res50_2x_low_res.py", "nerfdet_res101_2x_low_res_depth_sp.py"):
-        cfg = Config.fromfile(os.path.join(REF_CFG, f))
+        cfg = Config.fromfile(reference_config(tmp_path, f))
         train = build_dataset(cfg.data.train)
         assert isinstance(train, RepeatDataset) and train.times == 6 and isinstance(train.dataset, ScanNetMultiViewDataset)
         steps = train.dataset.pipeline.transforms

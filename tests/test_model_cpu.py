@@ -1,12 +1,8 @@
 """CPU checks of the registry/config surface: the reference's config files load unmodified and
 build the mirrored detector with the reference's state-dict surface."""
-import glob
-import os
-
-import pytest
 import torch
 
-REF_CFG = "/root/reference/configs/nerfdet"
+from conftest import reference_config, reference_config_names
 
 
 def test_preset_builds_with_reference_state_dict_surface():
@@ -42,18 +38,17 @@ def test_preset_builds_with_reference_state_dict_surface():
     assert abs(float(m.bbox_head.cls_conv.bias[0]) + 4.59512) < 1e-4
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference configs only exist in the build container")
-def test_reference_configs_load_unmodified_and_build():
+def test_reference_configs_load_unmodified_and_build(tmp_path):
     from nerfdet_amd.config import Config
     from nerfdet_amd.presets import nerfdet_cfg
     from nerfdet_amd.registry import build_detector
-    files = sorted(glob.glob(os.path.join(REF_CFG, "*.py")))
+    files = [reference_config(tmp_path, n) for n in reference_config_names()]
     assert len(files) == 5
     for f in files:
         cfg = Config.fromfile(f)
         assert cfg.model.type == "nerfdet" and cfg.test_cfg.nms_pre == 1000 and cfg.data.samples_per_gpu == 1
         assert "denorm_images" in cfg.test_collect_keys
-    cfg = Config.fromfile(os.path.join(REF_CFG, "nerfdet_res50_2x_low_res.py"))
+    cfg = Config.fromfile(reference_config(tmp_path, "nerfdet_res50_2x_low_res.py"))
     ours = nerfdet_cfg(50)
     for k, v in ours["model"].items():
         if k != "pretrained":
@@ -62,7 +57,7 @@ def test_reference_configs_load_unmodified_and_build():
     cfg.model.pretrained = None  # torchvision:// is a network fetch
     det = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)
     assert det.N_samples == 64 and det.N_rand == 2048 and det.bbox_head.test_cfg.score_thr == 0.01
-    cfg101 = Config.fromfile(os.path.join(REF_CFG, "nerfdet_res101_2x_low_res_depth_sp.py"))
+    cfg101 = Config.fromfile(reference_config(tmp_path, "nerfdet_res101_2x_low_res_depth_sp.py"))
     assert cfg101.model.backbone.depth == 101 and cfg101.model.depth_supervise is True
 
 

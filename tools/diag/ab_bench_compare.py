@@ -1,4 +1,4 @@
-"""Same-box comparison of two checkouts' bench.py lines (event-timed spans, no profiler): python tools/diag/ab_bench_compare.py A.json B.json"""
+"""Same-box comparison of two checkouts' ``bench.py --full`` lines (event-timed spans, no profiler): python tools/diag/ab_bench_compare.py A.json B.json"""
 import json
 import sys
 
