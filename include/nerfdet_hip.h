@@ -171,7 +171,7 @@ int ndet_gather_detections(const int64_t* keep, int n_keep, const float* boxes, 
  * greedy NMS (core/post_processing/box3d_nms.py:91-138) over the candidates ndet_select_candidates compacted -- their count is read
  * on the device from counts[n_levels] -- and the picks packed for ONE device-to-host copy: out_packed = {n_keep, n_candidates,
  * status, range guard} followed by up to k_cap rows [x, y, z_bottom, dx, dy, dz, 0, score, label]; range_guard (may be null): the scene's guard word
- * of ndet_conv_ndhwc_guarded, whose bit 0 is copied into the header so that it reaches the host with the picks.  status != 0 (more than n_cap <= 4096
+ * of ndet_conv_split / ndet_conv_chain (NdetConvArgs::guard), whose bit 0 is copied into the header so that it reaches the host with the picks.  status != 0 (more than n_cap <= 4096
  * candidates, a level with more than nms_pre survivors, more picks than rows): the caller repeats the scene on the synchronous
  * path.  workspace: ndet_nms_workspace_bytes(n_cap). */
 int ndet_nms_pack_detections(const float* cand_boxes, const float* cand_scores, const int64_t* cand_labels, const int* counts,
@@ -256,7 +256,7 @@ int ndet_conv_ndhwc(const float* in, const float* w_packed, float* out, int D, i
 
 /* Packed fp32 weights (taps, Cout, Cin) -> three bf16 planes tiled per 32-channel K step, (taps, Cin/32, 3, Cout, 32), with
  * w = p0 + p1 + p2 exactly (p0 = bf16(w), p1 = bf16(w - p0), p2 = bf16(w - p0 - p1), round-to-nearest-even).  Prepares the
- * weights of ndet_conv_ndhwc_split (the conv weights of necks/imvoxelnet.py:36-67, dense_heads/imvoxel_head_v2.py:45-49). */
+ * weights of ndet_conv_split with arith 0 / 2 (the conv weights of necks/imvoxelnet.py:36-67, dense_heads/imvoxel_head_v2.py:45-49). */
 int ndet_split_weights_bf16x3(const float* w_packed, int taps, int Cout, int Cin, uint16_t* planes, void* stream);
 
 /* The same planes straight from a torch-layout weight (Cout, Cin, taps) -- training re-packs every step.  adjoint = 0: the layer's
@@ -264,46 +264,6 @@ int ndet_split_weights_bf16x3(const float* w_packed, int taps, int Cout, int Cin
  * convolutions of mmdet3d/models/necks/imvoxelnet.py:22-67,233-260), W'[t][ci][co] = W[co][ci][taps-1-t], planes
  * (taps, ceil32(Cout)/32, 3, Cin, 32) with the padded input channels zero. */
 int ndet_split_weights_bf16x3_torch(const float* w_torch, int taps, int Cout, int Cin, int adjoint, uint16_t* planes, void* stream);
-
-/* Same contract as ndet_conv_ndhwc / the transposed form of ndet_conv3d_ndhwc, computed on the bf16 matrix cores:
- * weights as tiled bf16 planes (taps, Cin/32, 3, Cout, 32) from ndet_split_weights_bf16x3, activations split on the fly; the six
- * products of order <= 2 are accumulated in fp32 (error at the level of an fp32 FMA chain).  transposed = 1: k2 s2
- * ConvTranspose3d (kernel/stride must be 2, pad 0; 8 taps).  tile (rows x output channels of a workgroup's tile): 0 auto; 64 (64 x 64), 128
- * (128 x 128), 12864 (128 x 64): the unified tiles, LDS-staged epilogue; 100064 / 100128 / 112864: the same tiles storing straight from the
- * accumulators (splits == 1, not transposed, Cout % 32 == 0, output < 4 GB; plain and nearest-x2 residual); 128256: wave-specialised 128 x 256;
- * 129256 / 129257 (eight consumer waves) / 129064 (64-row tiles): its persistent form (plain convolutions, Cout % 16 == 0, <= 32 taps);
- * 3128 / 3256 / 3257 / 3258: halo-stationary 128-voxel patch x 128 / 256 channels (stride 1, odd kernel, same padding, more than one tap;
- * 3257: two consumer waves per SIMD, 3258: eight producer waves).  The staged and direct forms of a unified tile, and the one-shot and persistent
- * forms of the wave-specialised tile, give bit-identical results (tests/test_conv3d_gpu.py).
- * Replaces the same reference modules as ndet_conv3d_ndhwc (necks/imvoxelnet.py:36-67,233-260,
- * dense_heads/imvoxel_head_v2.py:45-49) and the mmdet ResNet/FPN convolutions behind nerfdet.py:140. */
-int ndet_conv_ndhwc_split(const float* in, const uint16_t* w_planes, float* out, int D, int H, int W, int Cin, int Cout,
-                          const int* kernel, const int* stride, const int* pad, int transposed, const float* scale,
-                          const float* shift, const float* residual, int residual_up2, int relu, int splits, int tile,
-                          void* workspace, void* stream);
-
-/* The same convolution with both operands rounded to bf16 and ONE MFMA product per multiply (fp32 accumulate, fp32 activations in
- * HBM): the "bf16" arithmetic BASELINE.json's configs 3 and 5 name -- what torch.autocast(bfloat16) would run nn.Conv3d / nn.Conv2d
- * of mmdet3d/models/necks/imvoxelnet.py:22-67,233-260 and the ResNet/FPN layers in.  Same arguments and weight planes as
- * ndet_conv_ndhwc_split (only the first plane is multiplied). */
-int ndet_conv_ndhwc_bf16(const float* in, const uint16_t* w_planes, float* out, int D, int H, int W, int Cin, int Cout,
-                         const int* kernel, const int* stride, const int* pad, int transposed, const float* scale,
-                         const float* shift, const float* residual, int residual_up2, int relu, int splits, int tile,
-                         void* workspace, void* stream);
-
-/* Convolution + chained 1x1 convolution in one launch: out = act3(bn3(W3 . relu(bn1(conv(in)))) + residual), the intermediate (Cmid = 64 or
- * 128 channels, ALL of them in one 128-row tile) never leaves the CU.  Replaces the conv2 -> bn2 -> relu -> conv3 -> bn3 -> (+identity) ->
- * relu tail of the ResNet bottlenecks the detector runs as `self.backbone(img)` in mmdet3d/models/detectors/nerfdet.py:140 (mmdet's
- * resnet.py Bottleneck.forward; third-party, restated): in stages 1 / 2 the intermediate is 61 / 31 MB per block at 50 views 240x320.
- * in (D,H,W,Cin) fp32 channels-last (2D: D = batch, kernel[0] = 1); w_planes / w3_planes: bf16 planes of ndet_split_weights_bf16x3 for
- * the (taps, Cmid, Cin) and (1, Cout, Cmid) packed weights; scale1/shift1, scale3/shift3: folded BatchNorm (null = identity); residual
- * (M, Cout) or null; relu3: 0 none, 1 after the residual add, 2 before it; max_order 2: six products (fp32-class), 0: one (bf16).
- * Cin % 32 == 0, Cout % 64 == 0.  Same arithmetic as the two ndet_conv_ndhwc_split launches it replaces except that the intermediate is
- * not rounded through memory (it is the same fp32 value). */
-int ndet_conv_chain_split(const float* in, const uint16_t* w_planes, int D, int H, int W, int Cin, int Cmid, const int* kernel,
-                          const int* stride, const int* pad, const float* scale1, const float* shift1, const uint16_t* w3_planes,
-                          int Cout, const float* scale3, const float* shift3, const float* residual, int relu3, float* out,
-                          int max_order, void* stream);
 
 /* A6 fused: [posenc(points) | global_feat] -> 4 x (Linear 256 + ReLU) -> sigma layer over [h | input] -> alpha = 1 - exp(-relu(sigma)), one launch,
  * the 256-wide activations never leave the CU.  Replaces VanillaNeRFRadianceField.query_density (mmdet3d/models/model_utils/nerf_mlp.py:224-227;
@@ -327,7 +287,7 @@ int ndet_point_mlp_alpha(const float* points, const float* global_feat, int N, i
  * instead of six; tests/test_conv3d_gpu.py).  Weights: ndet_split_weights_f16x2 builds the planes (taps, Cin/32, 2, Cout, 32) of
  * w * scale once per model (scale = a power of two, chosen by the caller from max |w|); activations: the kernels derive their scale on
  * the device from `in_amax` (max |in|, written by the previous layer's epilogue through its `out_amax`, or by ndet_amax_f32) and undo both
- * scales in the epilogue -- nothing is synchronised with the host.  Same reference modules as ndet_conv_ndhwc_split
+ * scales in the epilogue -- nothing is synchronised with the host.  Same reference modules as ndet_conv_split
  * (mmdet3d/models/necks/imvoxelnet.py:36-67,233-260). */
 int ndet_split_weights_f16x2(const float* w_packed, int taps, int Cout, int Cin, float scale, uint16_t* planes, void* stream);
 
@@ -345,75 +305,118 @@ int ndet_amax_slot_floats(void);
  * (default 32 MiB); "order2": 1 / 0 = deal the column tiles of a row tile to one XCD or keep grid order (neither changes a result bit);
  * "deterministic_scatter": 1 = the backward kernels' gradient scatter on 64-bit fixed-point integer atomics (the caller then passes zeroed int64
  * buffers in place of the float ones: order-independent sums, for reproducibility tests; nerfdet_amd/autograd.py::set_deterministic);
- * "wgrad_wide": 0 = ndet_wgrad_split_f16x2 keeps its 128 x 128 tile where it would take 128 x 256 (same sums in another association);
+ * "wgrad_wide": 0 = ndet_wgrad_split (arith 1) keeps its 128 x 128 tile where it would take 128 x 256 (same sums in another association);
  * "wgrad_xcd": 0 = the weight-gradient kernel's workgroups in grid order instead of one K split per XCD at a time (no result bit changes).
  * HOST string.  No reference counterpart (the reference's harness, tools/benchmark.py:63-89, times the model only). */
 int ndet_measurement_knob(const char* name_host, int64_t value);
 
-/* ndet_conv_ndhwc_split / ndet_conv_ndhwc_bf16 (necks/imvoxelnet.py:36-67,233-260, imvoxel_head_v2.py:45-49, the backbone behind
- * nerfdet.py:140) with the arithmetic as an argument: arith 0 = bf16x3 (six products), 1 = fp16 pair (three
- * products; w_planes from ndet_split_weights_f16x2, `in_amax` required, w_inv_scale = 1 / that call's scale), 2 = bf16 (one product).
- * out_amax (any arith, may be null): max |out| is maxed into *out_amax (zeroed by the caller) -- the next layer's in_amax. */
-int ndet_conv_ndhwc_arith(const float* in, const uint16_t* w_planes, float* out, int D, int H, int W, int Cin, int Cout,
-                          const int* kernel, const int* stride, const int* pad, int transposed, const float* scale,
-                          const float* shift, const float* residual, int residual_up2, int relu, int splits, int tile, int arith,
-                          const float* in_amax, float w_inv_scale, float* out_amax, void* workspace, void* stream);
+/* The split-family convolutions on the bf16 / fp16 matrix cores (csrc/conv_split_kernels.hip), every argument in one block: the same contract
+ * as ndet_conv_ndhwc / the transposed form of ndet_conv3d_ndhwc, replacing the same reference modules -- nn.Conv3d / nn.ConvTranspose3d +
+ * BatchNorm3d + ReLU (+ residual) of mmdet3d/models/necks/imvoxelnet.py:36-67,233-260, dense_heads/imvoxel_head_v2.py:45-49 and the mmdet
+ * ResNet/FPN convolutions behind detectors/nerfdet.py:140.  `a` is a HOST pointer, read during the call only; a zero / null field switches its
+ * feature off.
+ *   size          sizeof(NdetConvArgs), set by the caller; any other value is rejected (NDET_E_INVALID): the caller's layout differs from this one.
+ *   in, out       (D,H,W,Cin) fp32 channels-last (2D: D = batch, kernel[0] = 1) -> (OD,OH,OW,Cout) [transposed: (2D,2H,2W,Cout)]; `in` 16-byte aligned.
+ *   w_planes      the packed (taps, Cout, Cin) weight as tiled planes (taps, Cin/32, P, Cout, 32), 16-byte aligned: ndet_split_weights_bf16x3
+ *                 (arith 0 / 2, P = 3), ndet_split_weights_f16x2 or ndet_split_weights_train (arith 1, P = 2).  Cin % 32 == 0.
+ *   kernel, stride, pad   per axis (D, H, W).  transposed = 1: k2 s2 ConvTranspose3d (kernel / stride 2, pad 0; 8 taps).
+ *   scale, shift  (Cout) folded BatchNorm / bias, both or neither.  relu: 0 none, 1 after the residual add, 2 before it.
+ *   residual      (OD,OH,OW,Cout); residual_up2 = 1: a (OD, ceil(OH/2), ceil(OW/2), Cout) map added at (d, h/2, w/2) -- the FPN's nearest x2
+ *                 upsample-add (not with split-K).
+ *   splits        split-K over blockIdx.z into `workspace` (splits * M * Cout floats), reduced in a fixed order.
+ *   tile          rows x output channels of a workgroup's tile: 0 auto; 64 (64 x 64), 128 (128 x 128), 12864 (128 x 64): the unified tiles,
+ *                 LDS-staged epilogue; 100064 / 100128 / 112864: the same tiles storing straight from the accumulators (splits == 1, not transposed,
+ *                 Cout % 32 == 0, output < 4 GB); 128256: wave-specialised 128 x 256; 129256 / 129257 (eight consumer waves) / 129064 (64-row
+ *                 tiles): its persistent form (plain convolutions, Cout % 16 == 0, <= 32 taps); 3128 / 3256 / 3257 / 3258: halo-stationary
+ *                 128-voxel patch x 128 / 256 channels (stride 1, odd kernel, same padding, more than one tap; 3257: two consumer waves per SIMD,
+ *                 3258: eight producer waves).  The staged and direct forms of a unified tile, and the one-shot and persistent forms of the
+ *                 wave-specialised tile, give bit-identical results (tests/test_conv3d_gpu.py).
+ *   arith         0 = bf16x3: every fp32 operand as the exact sum of three bf16 terms, the six products of order <= 2 accumulated in fp32 (error at
+ *                 the level of an fp32 FMA chain).  1 = fp16 pair (three products; see ndet_split_weights_f16x2).  2 = bf16: both operands rounded
+ *                 to bf16, one product, fp32 accumulate and fp32 activations in HBM -- the "bf16" arithmetic BASELINE.json's configs 3 and 5
+ *                 name (what torch.autocast(bfloat16) would run the layers in).
+ *   in_amax       arith 1 only, and required there: the input's amax slot (ndet_amax_f32, or the out_amax of the launch that wrote it).
+ *   w_inv_scale   arith 1 without w_amax: 1 / the scale ndet_split_weights_f16x2 was given (> 0).  Ignored otherwise.
+ *   w_amax        the TRAINING form (arith 1, not transposed, no residual_up2; forward and data gradient of the convolutions above and of
+ *                 dense_heads/imvoxel_head_v2.py:444-449, detectors/nerfdet.py:140-142): the weight planes were scaled ON THE DEVICE by the
+ *                 power of two of this slot -- by ndet_split_weights_train (the optimizer moves the weights every step), or, for the
+ *                 weight-gradient GEMM over ndet_wgrad_rows' tap copies, dy's planes from ndet_wgrad_dy_planes_f16x2 -- so 1 / scale is read
+ *                 from the same slot and w_inv_scale is ignored; guard_l1 is then the contraction length taps * Cin (||w||_1 <= K max|w|).
+ *   out_amax      any arith: max |out| is maxed into this zeroed slot -- the next layer's in_amax.
+ *   guard         the RANGE GUARD of arith 1 (ignored otherwise; with it guard_l1 >= 0 and guard_tol > 0).  The activation scale of that arithmetic
+ *                 is per tensor, so beside its fp32-class relative error an output carries an absolute floor of at most
+ *                     2^-39 max|in| * guard_l1,    guard_l1 = max_j |scale_j| (sum_k |w_jk| + max|w| #{k: 0 < |w_jk| < 2^-16 max|w|})    (host, per pack)
+ *                 whatever the distribution inside the tensor (csrc/conv_common.hpp::conv_guard_check).  max|in| is known on the device at kernel
+ *                 entry, and so is the smallest maximum any workgroup tile of the input committed (word 1 of the amax sub-slots): when the floor
+ *                 exceeds guard_tol AND that tile minimum lies below 2^-16 of max|in| (a part of the tensor really is outside the fp16-pair window;
+ *                 a uniformly large tensor is not), the launch ORs 1 into *guard (device word, zeroed by the caller per scene).  The caller reads
+ *                 the word with the detections (ndet_nms_pack_detections) and repeats such a scene on bf16x3.  The tensor that first needed it:
+ *                 the sigma-MLP rows of detectors/nerfdet.py:236-243.
+ *   keep_partials 1 (weight-gradient GEMMs; no affine / residual / ReLU / out_amax, not transposed): a split-K launch leaves its partial sums in
+ *                 the workspace for ndet_wgrad_to_torch instead of running the reduction pass; `out` is then not written.
+ *   map_w, map_b, map_out   a chained 32-channel projection of every output row in the same launch: map_out (M, 32) = out_row . map_w + map_b,
+ *                 map_w (Cout, 32) and map_b (32) with the convolution's own affine folded in by the caller (map_w[c][j] = scale_c Wm[j][c],
+ *                 map_b[j] = sum_c shift_c Wm[j][c] + bm[j]); fp32 FMAs; all three 16-byte aligned.  The detector's feature mapping
+ *                 (detectors/nerfdet.py:194-197: self.mapping on every FPN level-0 pixel) behind the FPN output convolution: the 276 MB feature
+ *                 map is not read back by a launch of its own.  Only the 256-column halo tiles own whole rows: tile 3256 / 3257 / 3258,
+ *                 Cout = 256, no split-K, residual, ReLU or transposition. */
+typedef struct NdetConvArgs {
+    int32_t size;
+    const float* in;
+    const uint16_t* w_planes;
+    float* out;
+    int D, H, W, Cin, Cout;
+    int kernel[3], stride[3], pad[3];
+    int transposed;
+    const float* scale;
+    const float* shift;
+    const float* residual;
+    int residual_up2, relu, splits, tile, arith;
+    const float* in_amax;
+    float w_inv_scale;
+    const float* w_amax;
+    float* out_amax;
+    void* workspace;
+    unsigned* guard;
+    float guard_l1, guard_tol;
+    int keep_partials;
+    const float* map_w;
+    const float* map_b;
+    float* map_out;
+} NdetConvArgs;
+int ndet_conv_split(const NdetConvArgs* a, void* stream);
 
-/* ndet_conv_ndhwc_arith with the RANGE GUARD of the fp16-pair arithmetic (arith 1; ignored otherwise).  The activation scale of that arithmetic
- * is per tensor, so beside its fp32-class relative error an output carries an absolute floor of at most
- *     2^-39 max|in| * guard_l1,      guard_l1 = max_j |scale_j| (sum_k |w_jk| + max|w| #{k: 0 < |w_jk| < 2^-16 max|w|})      (host, once per pack)
- * whatever the distribution inside the tensor (csrc/conv_common.hpp::conv_guard_check).  max|in| is known on the device at kernel entry, and so is
- * the smallest maximum any workgroup tile of the input committed (word 1 of the amax sub-slots): when the floor exceeds guard_tol AND that tile
- * minimum lies below 2^-16 of max|in| (a part of the tensor really is outside the fp16-pair window; a uniformly large tensor is not), the launch ORs
- * 1 into *guard (device word, zeroed by the caller per scene).  The caller reads the word with the
- * detections (ndet_nms_pack_detections) and repeats such a scene on the six-product bf16x3 arithmetic.  Same reference modules as
- * ndet_conv_ndhwc_split (mmdet3d/models/necks/imvoxelnet.py:36-67,233-260, dense_heads/imvoxel_head_v2.py:45-49, the backbone behind
- * detectors/nerfdet.py:140); the tensor that first needed it: the sigma-MLP rows of nerfdet.py:236-243. */
-int ndet_conv_ndhwc_guarded(const float* in, const uint16_t* w_planes, float* out, int D, int H, int W, int Cin, int Cout,
-                            const int* kernel, const int* stride, const int* pad, int transposed, const float* scale,
-                            const float* shift, const float* residual, int residual_up2, int relu, int splits, int tile, int arith,
-                            const float* in_amax, float w_inv_scale, float* out_amax, void* workspace, float guard_l1, float guard_tol,
-                            unsigned* guard, void* stream);
-
-/* ndet_conv_ndhwc_guarded (plain stride-1 same-padded convolution, no residual / ReLU / split-K) with a chained 32-channel projection of every output
- * row in the same launch: map_out (M, 32) = out_row . map_w + map_b, map_w (Cout, 32) and map_b (32) with the convolution's own affine folded in by
- * the caller (map_w[c][j] = scale_c Wm[j][c], map_b[j] = sum_c shift_c Wm[j][c] + bm[j]); fp32 FMAs.  The detector's feature mapping
- * (mmdet3d/models/detectors/nerfdet.py:194-197: self.mapping on every FPN level-0 pixel) behind the FPN output convolution (nerfdet.py:140-142): the
- * 276 MB feature map is not read back by a launch of its own.  Only the 256-column halo tiles own whole rows: tile 3256 / 3257 / 3258, Cout = 256. */
-int ndet_conv_ndhwc_mapped(const float* in, const uint16_t* w_planes, float* out, int D, int H, int W, int Cin, int Cout, const int* kernel,
-                           const int* stride, const int* pad, const float* scale, const float* shift, int tile, int arith, const float* in_amax,
-                           float w_inv_scale, float* out_amax, float guard_l1, float guard_tol, unsigned* guard, const float* map_w,
-                           const float* map_b, float* map_out, void* stream);
-
-/* ndet_conv_chain_arith with the range guard (see ndet_conv_ndhwc_guarded): guard_l1 belongs to w_planes and max|in|, guard_l1_3 to w3_planes and
- * the chained product (reserved: its operand is scaled by each workgroup's own maximum, which needs no check).  The bottleneck tail of the backbone called at mmdet3d/models/detectors/nerfdet.py:140. */
-int ndet_conv_chain_guarded(const float* in, const uint16_t* w_planes, int D, int H, int W, int Cin, int Cmid, const int* kernel,
-                            const int* stride, const int* pad, const float* scale1, const float* shift1, const uint16_t* w3_planes,
-                            int Cout, const float* scale3, const float* shift3, const float* residual, int relu3, float* out,
-                            int arith, const float* in_amax, float w1_inv_scale, float w3_inv_scale, float* out_amax, float guard_l1,
-                            float guard_l1_3, float guard_tol, unsigned* guard, void* stream);
+/* Convolution + chained 1x1 convolution in one launch: out = act3(bn3(W3 . relu(bn1(conv(in)))) + residual), the intermediate (Cmid = 64 or
+ * 128 channels, ALL of them in one 128-row tile) never leaves the CU.  Replaces the conv2 -> bn2 -> relu -> conv3 -> bn3 -> (+identity) ->
+ * relu tail of the ResNet bottlenecks the detector runs as `self.backbone(img)` in mmdet3d/models/detectors/nerfdet.py:140 (mmdet's
+ * resnet.py Bottleneck.forward; third-party, restated): in stages 1 / 2 the intermediate is 61 / 31 MB per block at 50 views 240x320.
+ * in (D,H,W,Cin) fp32 channels-last (2D: D = batch, kernel[0] = 1); w_planes / w3_planes: the planes of the (taps, Cmid, Cin) and (1, Cout, Cmid)
+ * packed weights for `arith` (numbered as NdetConvArgs::arith; w1_inv_scale / w3_inv_scale belong to w_planes / w3_planes, 1 for arith 0 / 2);
+ * scale1/shift1, scale3/shift3: folded BatchNorm (null = identity); residual (M, Cout) or null; relu3: 0 none, 1 after the residual add, 2
+ * before it; in_amax / out_amax as in NdetConvArgs.  Cin % 32 == 0, Cout % 64 == 0.  The bf16x3 form is the same arithmetic as the two
+ * ndet_conv_split launches it replaces except that the intermediate is not rounded through memory (it is the same fp32 value); in the
+ * fp16-pair arithmetic the intermediate's scale is the workgroup's own maximum: it never exists as a whole tensor.  guard (arith 1, may be
+ * null): the range guard of NdetConvArgs -- guard_l1 belongs to w_planes and max|in|, guard_l1_3 to w3_planes and the chained product
+ * (reserved: its operand is scaled by each workgroup's own maximum, which needs no check). */
+int ndet_conv_chain(const float* in, const uint16_t* w_planes, int D, int H, int W, int Cin, int Cmid, const int* kernel,
+                    const int* stride, const int* pad, const float* scale1, const float* shift1, const uint16_t* w3_planes,
+                    int Cout, const float* scale3, const float* shift3, const float* residual, int relu3, float* out,
+                    int arith, const float* in_amax, float w1_inv_scale, float w3_inv_scale, float* out_amax, float guard_l1,
+                    float guard_l1_3, float guard_tol, unsigned* guard, void* stream);
 
 /* A whole ResNet bottleneck of stage 1 in one launch, fp16-pair arithmetic: out = relu(bn3(W3 . relu(bn2(conv3x3(relu(bn1(W1 . x)))))) + identity),
  * identity = x (Cin == Cout) or, with wd_planes, bnD(WD . x) (the first block of the stage; Cin = 64) -- mmdet's Bottleneck.forward (style 'pytorch',
  * stride 1) behind mmdet3d/models/detectors/nerfdet.py:140.  x (N, H, W, Cin) channels-last, out (N, H, W, Cout); the intermediate has 64 channels
  * (w1 (1, Cin/32, 2, 64, 32), w2 (9, 2, 2, 64, 32), w3 (1, 2, 2, Cout, 32), wd (1, Cin/32, 2, Cout, 32): ndet_split_weights_f16x2 planes with their
  * inverse scales; scale* / shift*: folded eval-mode BatchNorm).  A workgroup owns a 4 x 16 patch of one map from x to out: conv1 is evaluated on
- * the patch plus its one-pixel halo into LDS, conv2's taps multiply out of that image, conv3 follows as in ndet_conv_chain_arith; the scales of
+ * the patch plus its one-pixel halo into LDS, conv2's taps multiply out of that image, conv3 follows as in ndet_conv_chain; the scales of
  * the two intermediates are the workgroup's own maxima.  in_amax: x's slot; out_amax (may be null): max |out|.  guard (may be null): the range
- * guard word (see ndet_conv_ndhwc_guarded), guard_l1_host = 4 HOST floats (w1, w2, w3, wd). */
+ * guard word (see NdetConvArgs::guard), guard_l1_host = 4 HOST floats (w1, w2, w3, wd). */
 int ndet_bottleneck_f16x2(const float* x, int N, int H, int W, int Cin, int Cout, const uint16_t* w1_planes, float w1_inv_scale, const float* scale1,
                           const float* shift1, const uint16_t* w2_planes, float w2_inv_scale, const float* scale2, const float* shift2,
                           const uint16_t* w3_planes, float w3_inv_scale, const float* scale3, const float* shift3, const uint16_t* wd_planes,
                           float wd_inv_scale, const float* scale_d, const float* shift_d, const float* in_amax, float* out_amax, float* out,
                           const float* guard_l1_host, float guard_tol, unsigned* guard, void* stream);
-
-/* ndet_conv_chain_split with the arithmetic as an argument (as above; w1_inv_scale / w3_inv_scale belong to w_planes / w3_planes).  In the
- * fp16-pair arithmetic the intermediate's scale is the workgroup's own maximum: it never exists as a whole tensor.  Same reference code
- * as ndet_conv_chain_split: the bottleneck tail of the backbone called at mmdet3d/models/detectors/nerfdet.py:140. */
-int ndet_conv_chain_arith(const float* in, const uint16_t* w_planes, int D, int H, int W, int Cin, int Cmid, const int* kernel,
-                          const int* stride, const int* pad, const float* scale1, const float* shift1, const uint16_t* w3_planes,
-                          int Cout, const float* scale3, const float* shift3, const float* residual, int relu3, float* out,
-                          int arith, const float* in_amax, float w1_inv_scale, float w3_inv_scale, float* out_amax, void* stream);
 
 /* ResNet stem tail in one pass: BatchNorm(eval) as per-channel scale/shift + ReLU + MaxPool(3, stride 2, pad 1) on the
  * channels-last stem output x (N,H,W,C), C % 4 == 0 -> out (N, (H-1)/2+1, (W-1)/2+1, C).  Third-party mmdet ResNet stem
@@ -425,7 +428,7 @@ int ndet_bn_relu_maxpool_nhwc(const float* x, const float* scale, const float* s
  * MaxPool(3, stride 2, pad 1) -- conv1 / bn1 / relu / maxpool of the third-party mmdet ResNet called at
  * mmdet3d/models/detectors/nerfdet.py:140.  images: N views of 3 x H x W fp32 with the given ELEMENT strides (NCHW or channels-last);
  * w_planes: ndet_stem_pack_weights of the (64,3,7,7) weight; out (N, PH, PW, 64) channels-last, PH = ((H-1)/2+1 - 1)/2 + 1.
- * Arithmetic of ndet_conv_ndhwc_split (fp32 operands as exact sums of three bf16 terms, six MFMA products). */
+ * Arithmetic of ndet_conv_split with arith 0 (fp32 operands as exact sums of three bf16 terms, six MFMA products). */
 int ndet_stem_pack_weights(const float* w_64x3x7x7, uint16_t* planes /* (3, 64, 176) */, void* stream);
 /* ... and its fp16-pair form (two fp16 planes of w * scale, scale a power of two chosen by the caller from max |w|): ndet_stem_conv_bn_relu_maxpool
  * with w_inv_scale = 1 / scale then issues three fp16 MFMA products per multiply, the image patch scaled by the power of two of its own maximum
@@ -463,7 +466,7 @@ int ndet_target_rays(const uint8_t* frames_bgr, const int* target_ids, int n_tar
  * out[t - t0][c][j] = x[stride * o(j) + tap(t) - pad][c] over the flattened OUTPUT grid of the (kernel, stride, pad) convolution, taps
  * t0 .. t0+n_taps-1; every element of out (n_taps, C, lrow) is written (zeros where the tap reads padding and for j past the grid;
  * lrow >= OD*OH*OW).  With these rows (and dY staged by the same call with a 1x1x1 kernel) the weight gradient is one GEMM over j on
- * ndet_conv_ndhwc_split, for any stride (nerfdet_amd/conv_train.py). */
+ * ndet_conv_split, for any stride (nerfdet_amd/conv_train.py). */
 int ndet_wgrad_rows(const float* x_ndhwc, int D, int H, int W, int C, const int* kernel, const int* stride, const int* pad, int t0,
                     int n_taps, int lrow, float* out, void* stream);
 
@@ -472,25 +475,25 @@ int ndet_wgrad_rows(const float* x_ndhwc, int D, int H, int W, int C, const int*
  * x[stride * o(j) + tap(t) - pad][ci] * dy[j][co].  x (D,H,W,Cin) channels-last fp32 is read in place (transposed on its way into
  * LDS); dy arrives as the bf16 planes of its channel-major rows: ndet_wgrad_rows(dy, 1x1x1) -> (Cout, lrow), then
  * ndet_split_weights_bf16x3 on that (1, Cout, lrow) "weight".  dw_rows (taps * Cin, Cout) row-major; Cin % 64 == 0, lrow % 32 == 0;
- * splits > 1: workspace of splits * taps * Cin * Cout floats, reduced in a fixed order.  max_order 2: six products, 0: one (bf16). */
+ * splits > 1: workspace of splits * taps * Cin * Cout floats, reduced in a fixed order (keep_partials = 1: left there for ndet_wgrad_to_torch,
+ * dw_rows not written).  arith as NdetConvArgs::arith: 0 six products, 2 one (bf16); 1 fp16 pairs -- dy_planes from ndet_wgrad_dy_planes_f16x2
+ * (two planes per K step, scaled by the slot dy_amax), x split in the kernel under the scale of the slot x_amax, three products, the sums
+ * multiplied by the inverse of both scales; the two slots are required with arith 1 and null otherwise. */
 int ndet_wgrad_split(const float* x_ndhwc, int D, int H, int W, int Cin, const int* kernel, const int* stride, const int* pad,
-                     const uint16_t* dy_planes, int Cout, int lrow, int splits, int max_order, void* workspace, float* dw_rows,
-                     void* stream);
+                     const uint16_t* dy_planes, int Cout, int lrow, int splits, int arith, const float* x_amax, const float* dy_amax,
+                     void* workspace, float* dw_rows, int keep_partials, void* stream);
 
 /* dY of a convolution (L output voxels x Cout, channels-last fp32) -> the bf16 planes of its channel-major rows in the layout of
  * ndet_split_weights_bf16x3 for a (1, Cout, lrow) "weight": (lrow/32, 3, Cout, 32), zeros past L -- the "weight" operand of the
- * weight-gradient GEMMs (ndet_wgrad_split, or ndet_conv_ndhwc_split on ndet_wgrad_rows' tap copies) in one pass; autograd of nn.Conv3d /
+ * weight-gradient GEMMs (ndet_wgrad_split, or ndet_conv_split on ndet_wgrad_rows' tap copies) in one pass; autograd of nn.Conv3d /
  * nn.Conv2d in mmdet3d/models/necks/imvoxelnet.py:22-67,233-260 and of the ResNet / FPN layers. */
 int ndet_wgrad_dy_planes(const float* dy_rows_by_voxel, int L, int Cout, int lrow, uint16_t* planes, void* stream);
 
-/* fp16-pair forms of the two calls above (the training step on the three-product arithmetic): dy's planes are (lrow/32, 2, Cout, 32), two fp16
- * halves of dy * 2^k with 2^k taken ON THE DEVICE from dy's amax slot (ndet_amax_f32; largest magnitude in [2^14, 2^15)); ndet_wgrad_split_f16x2
- * splits x the same way under x_amax and multiplies the sums by the inverse of both scales, read from the same slots.  Same reference as
- * ndet_wgrad_split: autograd of nn.Conv3d / nn.Conv2d in mmdet3d/models/necks/imvoxelnet.py:22-67,233-260 and of the ResNet / FPN layers. */
+/* fp16-pair form of the call above (the training step on the three-product arithmetic): dy's planes are (lrow/32, 2, Cout, 32), two fp16
+ * halves of dy * 2^k with 2^k taken ON THE DEVICE from dy's amax slot (ndet_amax_f32; largest magnitude in [2^14, 2^15)) -- the operand of
+ * ndet_wgrad_split with arith 1.  Same reference: autograd of nn.Conv3d / nn.Conv2d in mmdet3d/models/necks/imvoxelnet.py:22-67,233-260 and of
+ * the ResNet / FPN layers. */
 int ndet_wgrad_dy_planes_f16x2(const float* dy_rows_by_voxel, int L, int Cout, int lrow, const float* dy_amax, uint16_t* planes, void* stream);
-int ndet_wgrad_split_f16x2(const float* x_ndhwc, int D, int H, int W, int Cin, const int* kernel, const int* stride, const int* pad,
-                           const uint16_t* dy_planes, int Cout, int lrow, int splits, const float* x_amax, const float* dy_amax, void* workspace,
-                           float* dw_rows, int keep_partials, void* stream);
 
 /* Both weight packs of one training step in ONE pass over a torch-layout weight (Cout, Cin, taps <= 27): planes = the layer's own
  * (taps, Cin/32, P, Cout, 32), planes_adjoint (may be null) = its data gradient's (taps, ceil32(Cout)/32, P, Cin, 32), W'[t][ci][co] = W[co][ci][taps-1-t]
@@ -516,24 +519,12 @@ int ndet_bn_train_backward(const float* dy, const float* x, const float* y, int6
                            const float* save_invstd, int relu, float* dx, float* d_residual, float* dgamma, float* dbeta, float* dx_amax,
                            float* workspace, void* stream);
 
-/* The weight gradient in torch's layout: dw_rows ((tap, ci) rows x Cout floats, what ndet_wgrad_split* and the staged GEMM write) ->
+/* The weight gradient in torch's layout: dw_rows ((tap, ci) rows x Cout floats, what ndet_wgrad_split and the staged GEMM write) ->
  * dw_torch (Cout, Cin, taps), the layout autograd hands to the optimizer for nn.Conv3d / nn.Conv2d.weight
  * (mmdet3d/models/necks/imvoxelnet.py:22-67,233-260).  32 x 32 x taps blocks through LDS, coalesced on both sides; taps <= 27, Cin % 32 == 0.
- * splits > 1: dw_rows is the split-K WORKSPACE of a launch made with keep_partials = 1 (ndet_conv_ndhwc_train, ndet_wgrad_split_f16x2) -- `splits`
+ * splits > 1: dw_rows is the split-K WORKSPACE of a launch made with keep_partials = 1 (ndet_conv_split, ndet_wgrad_split) -- `splits`
  * partial sums taps * Cin * Cout floats apart, added here in index order (what the separate reduction pass would have done, bit for bit). */
 int ndet_wgrad_to_torch(const float* dw_rows, int splits, int taps, int Cout, int Cin, float* dw_torch, void* stream);
-
-/* The fp16-pair convolution launch of the training step (forward and data gradient of the convolutions of
- * mmdet3d/models/necks/imvoxelnet.py:22-67,233-260, dense_heads/imvoxel_head_v2.py:45-58,444-449 and the trainable ResNet / FPN layers behind
- * detectors/nerfdet.py:140-142): ndet_conv_ndhwc_guarded with arith = 1 whose weight planes were scaled on the device -- by ndet_split_weights_train,
- * or, for the weight-gradient GEMM over ndet_wgrad_rows' tap copies, dy's planes from ndet_wgrad_dy_planes_f16x2 -- so 1 / (weight scale) is taken
- * from the slot w_amax instead of a host float.  guard (may be null): the range guard with ||w||_1 bounded by guard_k * max|w|, guard_k = taps * Cin.
- * keep_partials = 1 (weight-gradient GEMMs; no affine / residual / ReLU / out_amax): a split-K launch leaves its partial sums in the workspace for
- * ndet_wgrad_to_torch instead of running the reduction pass; `out` is then not written. */
-int ndet_conv_ndhwc_train(const float* in, const uint16_t* w_planes, float* out, int D, int H, int W, int Cin, int Cout, const int* kernel,
-                          const int* stride, const int* pad, const float* scale, const float* shift, const float* residual, int relu, int splits,
-                          int tile, const float* in_amax, const float* w_amax, float* out_amax, void* workspace, float guard_k, float guard_tol,
-                          unsigned* guard, int keep_partials, void* stream);
 
 /* Backward of the fused epilogue y = relu(conv * scale + shift (+ identity)) -- convolution + frozen eval-mode BatchNorm + ReLU (+ the
  * bottleneck's identity) of the trainable ResNet stages (mmdet Bottleneck.forward behind mmdet3d/models/detectors/nerfdet.py:140;

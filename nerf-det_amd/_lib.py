@@ -18,6 +18,15 @@ NDET_LAYOUT_NC = 1
 _P = c_void_p
 _F3 = ctypes.POINTER(c_float)
 
+
+class NdetConvArgs(ctypes.Structure):    # ndet_conv_split's block: include/nerfdet_hip.h::NdetConvArgs (C's `in` is `in_`), size = sizeof(NdetConvArgs)
+    _fields_ = ([("size", ctypes.c_int32), ("in_", _P), ("w_planes", _P), ("out", _P)] + [(f, c_int) for f in ("D", "H", "W", "Cin", "Cout")]
+                + [(f, c_int * 3) for f in ("kernel", "stride", "pad")] + [("transposed", c_int), ("scale", _P), ("shift", _P), ("residual", _P)]
+                + [(f, c_int) for f in ("residual_up2", "relu", "splits", "tile", "arith")] + [("in_amax", _P), ("w_inv_scale", c_float)]
+                + [(f, _P) for f in ("w_amax", "out_amax", "workspace", "guard")] + [("guard_l1", c_float), ("guard_tol", c_float), ("keep_partials", c_int)]
+                + [(f, _P) for f in ("map_w", "map_b", "map_out")])
+
+
 # name -> argtypes; kept in one table so tests can check the .so exports exactly this surface
 SIGNATURES = {
     "ndet_version": ([], c_int),
@@ -55,22 +64,15 @@ SIGNATURES = {
     "ndet_composite_bwd": ([_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P], c_int),
     "ndet_split_weights_bf16x3": ([_P, c_int, c_int, c_int, _P, _P], c_int),
     "ndet_split_weights_f16x2": ([_P, c_int, c_int, c_int, c_float, _P, _P], c_int),
-    "ndet_conv_ndhwc_arith": ([_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_float, _P, _P, _P], c_int),
-    "ndet_conv_ndhwc_guarded": ([_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_float, _P, _P,
-                                 c_float, c_float, _P, _P], c_int),
-    "ndet_conv_chain_guarded": ([_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_int, _P, c_int, _P, c_float, c_float, _P,
-                                 c_float, c_float, c_float, _P, _P], c_int),
+    "ndet_conv_split": ([ctypes.POINTER(NdetConvArgs), _P], c_int),
+    "ndet_conv_chain": ([_P, _P] + [c_int] * 5 + [_P] * 6 + [c_int, _P, _P, _P, c_int, _P, c_int, _P, c_float, c_float, _P, c_float, c_float, c_float, _P, _P], c_int),
     "ndet_bottleneck_f16x2": ([_P, c_int, c_int, c_int, c_int, c_int, _P, c_float, _P, _P, _P, c_float, _P, _P, _P, c_float, _P, _P, _P, c_float, _P, _P, _P, _P, _P,
                                _P, c_float, _P, _P], c_int),
     "ndet_amax_f32": ([_P, ctypes.c_int64, _P, _P], c_int),
     "ndet_amax_slot_floats": ([], c_int),
     "ndet_point_mlp_alpha": ([_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P], c_int),
     "ndet_measurement_knob": ([c_char_p, c_int64], c_int),
-    "ndet_conv_chain_arith": ([_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_int, _P, c_int, _P, c_float, c_float, _P, _P], c_int),
     "ndet_split_weights_bf16x3_torch": ([_P, c_int, c_int, c_int, c_int, _P, _P], c_int),
-    "ndet_conv_ndhwc_split": ([_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P], c_int),
-    "ndet_conv_chain_split": ([_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_int, _P, c_int, _P], c_int),
-    "ndet_conv_ndhwc_bf16": ([_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P], c_int),
     "ndet_level_valid": ([_P, c_int, c_int, c_int, c_int, _P, _P], c_int),
     "ndet_select_candidates": ([c_int, _P, _P, _P, _P, c_float, _P, _P, _P, _P, _P], c_int),
     "ndet_select_candidates_topk": ([c_int, _P, _P, _P, _P, c_float, c_int, _P, _P, _P, _P, _P], c_int),
@@ -83,17 +85,14 @@ SIGNATURES = {
     "ndet_stem_pack_weights_f16x2": ([_P, c_float, _P, _P], c_int),
     "ndet_wgrad_dy_planes": ([_P, c_int, c_int, c_int, _P, _P], c_int),
     "ndet_wgrad_dy_planes_f16x2": ([_P, c_int, c_int, c_int, _P, _P, _P], c_int),
-    "ndet_wgrad_split_f16x2": ([_P] + [c_int] * 4 + [_P, _P, _P, _P] + [c_int] * 3 + [_P, _P, _P, _P, c_int, _P], c_int),
     "ndet_bn_workspace_floats": ([c_int64, c_int], c_int64),
     "ndet_bn_train_forward": ([_P, c_int64, c_int, _P, _P, _P, _P, c_float, c_float, _P, c_int, _P, _P, _P, _P, _P, _P], c_int),
     "ndet_bn_train_backward": ([_P, _P, _P, c_int64, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P], c_int),
     "ndet_wgrad_to_torch": ([_P, c_int, c_int, c_int, c_int, _P, _P], c_int),
     "ndet_split_weights_train": ([_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P], c_int),
-    "ndet_conv_ndhwc_mapped": ([_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, _P, c_float, _P, c_float, c_float, _P, _P, _P, _P, _P], c_int),
-    "ndet_conv_ndhwc_train": ([_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_float, c_float, _P, c_int, _P], c_int),
     "ndet_relu_affine_bwd": ([_P, _P, _P, c_int64, c_int, c_int, _P, _P, _P], c_int),
     "ndet_relu_affine_bwd_amax": ([_P, _P, _P, c_int64, c_int, c_int, _P, _P, _P, _P], c_int),
-    "ndet_wgrad_split": ([_P] + [c_int] * 4 + [_P, _P, _P, _P] + [c_int] * 4 + [_P, _P, _P], c_int),
+    "ndet_wgrad_split": ([_P] + [c_int] * 4 + [_P, _P, _P, _P] + [c_int] * 4 + [_P, _P, _P, _P, c_int, _P], c_int),
     "ndet_wgrad_rows": ([_P] + [c_int] * 4 + [_P, _P, _P] + [c_int] * 3 + [_P, _P], c_int),
     "ndet_bn_relu_maxpool_nhwc": ([_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P], c_int),
     "ndet_conv3d_workspace_bytes": ([c_int] * 8, c_int64),

@@ -33,6 +33,7 @@ from ._lib import raw_stream
 ARITHMETIC = "f16x2"
 F16_MIN_KSTEPS = 4
 SPLIT_FAMILY = ("bf16x3", "bf16", "f16x2")    # the arithmetics of csrc/conv_split_kernels.hip
+ARITH_ID = {"bf16x3": 0, "f16x2": 1, "bf16": 2}   # ... as the library numbers them (NdetConvArgs::arith)
 
 
 def set_arithmetic(mode: str) -> str:
@@ -241,10 +242,10 @@ KERNEL_NAMES.update({("bf16", t): n for (a, t), n in list(KERNEL_NAMES.items()) 
 KERNEL_NAMES.update({("f16x2", t): n + "/f16x2" for (a, t), n in list(KERNEL_NAMES.items()) if a == "bf16x3"})
 
 
-def _launch(flops, thunk, arith="f32", tile=0, nbytes=0):
+def _launch(flops, thunk, arith="f32", tile=0, nbytes=0, name=None):
     """Every MFMA-convolution launch goes through here: ``nbytes`` = algorithmic traffic (input + weights + output + residual, each
-    touched once), ``flops`` = algorithmic multiply-adds x 2."""
-    name = KERNEL_NAMES.get((arith, tile), f"{arith}:{tile}")
+    touched once), ``flops`` = algorithmic multiply-adds x 2; ``name`` = the kernel's, when (arith, tile) does not say it."""
+    name = name or KERNEL_NAMES.get((arith, tile), f"{arith}:{tile}")
     if launch_hook is not None:
         return launch_hook(flops, thunk, name)
     return trace.span(name, thunk, flops=flops, bytes=nbytes, kind="conv")
@@ -372,11 +373,9 @@ def _conv_split(x, pk, out, dims, kernel, stride, pad, transposed, residual, res
         tile = 128256                                        # the persistent form takes plain convolutions with Cout % 16 == 0
     # unified tiles that write final values: the epilogue straight from the MFMA's C layout (no LDS staging, no barriers)
     base = {100064: 64, 100128: 128, 112864: 12864}.get(tile, tile)
-    direct_ok = (splits == 1 and not transposed and pk["cout"] % 32 == 0 and (m + 128) * pk["cout"] * 4 < (1 << 32)
-                 and (not residual_up2 or _lib.load().ndet_version() >= 105))     # (the upsampled residual in the direct epilogue: ABI 105)
+    direct_ok = splits == 1 and not transposed and pk["cout"] % 32 == 0 and (m + 128) * pk["cout"] * 4 < (1 << 32)
     tile = {64: 100064, 128: 100128, 12864: 112864}[base] if (base in (64, 128, 12864) and direct_ok and DIRECT_EPILOGUE) else base
     ws = torch.empty((m * pk["cout"] * splits * 4,), dtype=torch.uint8, device=x.device) if splits > 1 else None
-    i3 = lambda v: (ctypes.c_int * 3)(*v)
     st = c_void_p(raw_stream(x.device))
     lib = _lib.load()
     d, h, w = dims
@@ -387,61 +386,48 @@ def _conv_split(x, pk, out, dims, kernel, stride, pad, transposed, residual, res
         want_amax = want_amax and bool(pk.get("keep_amax"))    # (otherwise a reader in the fp16-pair arithmetic takes its own pass, amax_of)
     if NO_AMAX_COMMIT:
         want_amax = False
+    # one argument block (csrc: NdetConvArgs); the branches below only fill in the fields of the arithmetic, the guard and the projection
+    a = _lib.NdetConvArgs(size=ctypes.sizeof(_lib.NdetConvArgs), in_=x.data_ptr(), out=out.data_ptr(), D=d, H=h, W=w, Cin=pk["cin"], Cout=pk["cout"],
+                          kernel=kernel, stride=stride, pad=pad, transposed=int(transposed), scale=_addr(pk["scale"]), shift=_addr(pk["shift"]),
+                          residual=_addr(residual), residual_up2=int(residual_up2), relu=relu, splits=splits, tile=tile, arith=ARITH_ID[arith],
+                          workspace=_addr(ws))
+    keep, mapped = False, None
     if ARITHMETIC != "f16x2":
-        planes = split_planes(pk)
-        fn = lib.ndet_conv_ndhwc_bf16 if arith == "bf16" else lib.ndet_conv_ndhwc_split
-        _launch(flops, lambda: check(fn(_ptr(x), _ptr(planes), _ptr(out), d, h, w, pk["cin"], pk["cout"], i3(kernel), i3(stride), i3(pad), int(transposed),
-                                        _ptr(pk["scale"]), _ptr(pk["shift"]), _ptr(residual), int(residual_up2), relu, splits, tile, _ptr(ws), st),
-                                     "conv_ndhwc_split"), arith, tile, nbytes)
-        return out
-    # fp16-pair mode: every launch leaves max |out| behind; the fp16-pair launches read their input's
-    if arith == "f16x2" and pk.get("w_amax") is not None:
+        # bf16x3 / bf16 modes: no amax slots, no guard
+        a.w_planes = split_planes(pk).data_ptr()
+        want_amax = False
+    elif arith == "f16x2" and pk.get("w_amax") is not None:
         # training packs (conv_train.py): planes scaled on the device by the slot pk["w_amax"]; plain convolutions only
         assert not transposed and not residual_up2
-        planes, in_amax = pk["w_f16"][0], amax_of(x)
         keep = bool(pk.get("keep_partials"))       # weight-gradient GEMMs: a split-K launch leaves its partials for ndet_wgrad_to_torch (no reduction pass)
         want_amax = want_amax and not keep
-        out_amax = AMAX.take(x.device) if want_amax else None
+        a.w_planes, a.in_amax, a.w_amax, a.keep_partials = pk["w_f16"][0].data_ptr(), amax_of(x).data_ptr(), pk["w_amax"].data_ptr(), int(keep)
         gw = guard_word(x.device) if pk.get("guard", True) else None
-        _launch(flops, lambda: check(lib.ndet_conv_ndhwc_train(_ptr(x), _ptr(planes), _ptr(out), d, h, w, pk["cin"], pk["cout"], i3(kernel), i3(stride), i3(pad),
-                                                               _ptr(pk["scale"]), _ptr(pk["shift"]), _ptr(residual), relu, splits, tile, _ptr(in_amax),
-                                                               _ptr(pk["w_amax"]), _ptr(out_amax), _ptr(ws), float(kernel[0] * kernel[1] * kernel[2] * pk["cin"]),
-                                                               GUARD_TOL, _ptr(gw), int(keep), st),
-                                     "conv_ndhwc_train"), arith, tile, nbytes)
-        if keep:
-            pk["_partials"] = (ws.view(torch.float32), splits) if splits > 1 else None     # (splits == 1: the launch wrote `out` as usual)
-        if want_amax:
-            _tag_amax(out, out_amax)
-        return out
-    if arith == "f16x2":
-        planes, winv = split_planes_f16(pk)
-        in_amax = amax_of(x)
+        a.guard, a.guard_l1, a.guard_tol = _addr(gw), float(kernel[0] * kernel[1] * kernel[2] * pk["cin"]), GUARD_TOL    # (l1 bound: K max|w|)
     else:
-        planes, winv, in_amax = split_planes(pk), 1.0, None
-    out_amax = AMAX.take(x.device) if want_amax else None
-    gw = guard_word(x.device) if arith == "f16x2" else None
-    gl1 = guard_l1(pk) if gw is not None else 0.0
-    if chain is not None:
-        # the chained 32-channel projection of the output rows in the same launch (csrc: conv_map_rows): the 256-column halo tiles only
-        mapped = None
-        if tile in (3256, 3257, 3258) and splits == 1 and residual is None and relu == 0 and not transposed and pk["cout"] == 256 and arith in ("f16x2", "bf16x3"):
+        # fp16-pair mode: every launch leaves max |out| behind; the fp16-pair launches read their input's
+        if arith == "f16x2":
+            planes, a.w_inv_scale = split_planes_f16(pk)
+            a.in_amax = amax_of(x).data_ptr()
+            gw = guard_word(x.device)
+        else:
+            planes, gw = split_planes(pk), None
+        a.w_planes, a.guard, a.guard_l1, a.guard_tol = planes.data_ptr(), _addr(gw), (guard_l1(pk) if gw is not None else 0.0), GUARD_TOL
+        # the chained 32-channel projection of the output rows in the same launch (csrc: conv_map_rows): the 256-column halo tiles only; with another
+        # tile / arithmetic the caller projects in a launch of its own
+        if (chain is not None and tile in (3256, 3257, 3258) and splits == 1 and residual is None and relu == 0 and not transposed and pk["cout"] == 256
+                and arith in ("f16x2", "bf16x3")):
             mapped = torch.empty((m, 32), dtype=torch.float32, device=x.device)
-            _launch(flops, lambda: check(lib.ndet_conv_ndhwc_mapped(_ptr(x), _ptr(planes), _ptr(out), d, h, w, pk["cin"], pk["cout"], i3(kernel), i3(stride), i3(pad),
-                                                                    _ptr(pk["scale"]), _ptr(pk["shift"]), tile, 1 if arith == "f16x2" else 0, _ptr(in_amax), winv,
-                                                                    _ptr(out_amax), gl1, GUARD_TOL, _ptr(gw), _ptr(chain[0]), _ptr(chain[1]), _ptr(mapped), st),
-                                         "conv_ndhwc_mapped"), arith, tile, nbytes + 4 * mapped.numel())
-            if want_amax:
-                _tag_amax(out, out_amax)
-            return out, mapped
-        chain = None      # another tile / arithmetic took the layer: the caller projects in a launch of its own
-    _launch(flops, lambda: check(lib.ndet_conv_ndhwc_guarded(_ptr(x), _ptr(planes), _ptr(out), d, h, w, pk["cin"], pk["cout"], i3(kernel), i3(stride), i3(pad),
-                                                             int(transposed), _ptr(pk["scale"]), _ptr(pk["shift"]), _ptr(residual), int(residual_up2), relu,
-                                                             splits, tile, 1 if arith == "f16x2" else 0, _ptr(in_amax), winv, _ptr(out_amax), _ptr(ws),
-                                                             gl1, GUARD_TOL, _ptr(gw), st),
-                                 "conv_ndhwc_guarded"), arith, tile, nbytes)
+            a.map_w, a.map_b, a.map_out = chain[0].data_ptr(), chain[1].data_ptr(), mapped.data_ptr()
+            nbytes += 4 * mapped.numel()
+    out_amax = AMAX.take(x.device) if want_amax else None
+    a.out_amax = _addr(out_amax)
+    _launch(flops, lambda: check(lib.ndet_conv_split(a, st), "conv_split"), arith, tile, nbytes)
+    if keep:
+        pk["_partials"] = (ws.view(torch.float32), splits) if splits > 1 else None     # (splits == 1: the launch wrote `out` as usual)
     if want_amax:
         _tag_amax(out, out_amax)
-    return out
+    return out if mapped is None else (out, mapped)
 
 
 def projection_ok() -> bool:
@@ -451,6 +437,10 @@ def projection_ok() -> bool:
 
 def _ptr(t):
     return c_void_p(0 if t is None else t.data_ptr())
+
+
+def _addr(t):
+    return None if t is None else t.data_ptr()
 
 
 def pack_weight(w: torch.Tensor, transposed: bool = False) -> torch.Tensor:
@@ -659,28 +649,22 @@ def conv2d_chain_nhwc(x: torch.Tensor, pk: dict, pk3: dict, residual: Optional[t
     lib = _lib.load()
     flops = 2 * m * mid * (cin * kh * kw + cout)
     nbytes = 4 * (x.numel() + pk["w"].numel() + pk3["w"].numel() + out.numel() + (0 if residual is None else residual.numel()))
-    name = f"k_conv_split_chain<{mid}>"
     if ARITHMETIC == "f16x2":
         (p1, w1inv), (p3, w3inv) = split_planes_f16(pk), split_planes_f16(pk3)
         in_amax, out_amax = amax_of(x), (None if NO_AMAX_COMMIT else AMAX.take(x.device))
-        name += "/f16x2"
         gw = guard_word(x.device)
         gl1, gl3 = (guard_l1(pk), guard_l1(pk3)) if gw is not None else (0.0, 0.0)
-        thunk = lambda: check(lib.ndet_conv_chain_guarded(_ptr(x), _ptr(p1), n, h, w, cin, mid, i3(1, kh, kw), i3(1, sh, sw), i3(0, ph, pw), _ptr(pk["scale"]),
-                                                          _ptr(pk["shift"]), _ptr(p3), cout, _ptr(pk3["scale"]), _ptr(pk3["shift"]), _ptr(residual), relu,
-                                                          _ptr(out), 1, _ptr(in_amax), w1inv, w3inv, _ptr(out_amax), gl1, gl3, GUARD_TOL, _ptr(gw), st),
-                              "conv_chain_guarded")
-        if out_amax is not None:
-            _tag_amax(out, out_amax)
+        tol = GUARD_TOL
     else:
-        p1, p3 = split_planes(pk), split_planes(pk3)
-        thunk = lambda: check(lib.ndet_conv_chain_split(_ptr(x), _ptr(p1), n, h, w, cin, mid, i3(1, kh, kw), i3(1, sh, sw), i3(0, ph, pw), _ptr(pk["scale"]),
-                                                        _ptr(pk["shift"]), _ptr(p3), cout, _ptr(pk3["scale"]), _ptr(pk3["shift"]), _ptr(residual), relu,
-                                                        _ptr(out), 0 if ARITHMETIC == "bf16" else 2, st), "conv_chain_split")
-    if launch_hook is not None:
-        launch_hook(flops, thunk, name)
-    else:
-        trace.span(name, thunk, flops=flops, bytes=nbytes, kind="conv")
+        (p1, w1inv), (p3, w3inv) = (split_planes(pk), 1.0), (split_planes(pk3), 1.0)
+        in_amax = out_amax = gw = None
+        gl1 = gl3 = tol = 0.0
+    _launch(flops, lambda: check(lib.ndet_conv_chain(_ptr(x), _ptr(p1), n, h, w, cin, mid, i3(1, kh, kw), i3(1, sh, sw), i3(0, ph, pw), _ptr(pk["scale"]),
+                                                     _ptr(pk["shift"]), _ptr(p3), cout, _ptr(pk3["scale"]), _ptr(pk3["shift"]), _ptr(residual), relu, _ptr(out),
+                                                     ARITH_ID[ARITHMETIC], _ptr(in_amax), w1inv, w3inv, _ptr(out_amax), gl1, gl3, tol, _ptr(gw), st), "conv_chain"),
+            nbytes=nbytes, name=f"k_conv_split_chain<{mid}>" + ("/f16x2" if ARITHMETIC == "f16x2" else ""))
+    if out_amax is not None:
+        _tag_amax(out, out_amax)
     return out
 
 

@@ -1,7 +1,7 @@
 """Training-time convolutions on the hand-written MFMA kernels (SURVEY.md 8a rows A13/A14 in ``forward_train``).
 
 Forward, data gradient and weight gradient of the same-padded convolutions -- the convolutions of ``FastIndoorImVoxelNeck``
-(mmdet3d/models/necks/imvoxelnet.py:22-67,233-260) and of the trainable ResNet stages / FPN -- run on ``ndet_conv_ndhwc_split``
+(mmdet3d/models/necks/imvoxelnet.py:22-67,233-260) and of the trainable ResNet stages / FPN -- run on ``ndet_conv_split``
 (csrc/conv_split_kernels.hip):
 
   forward   y = conv(x, W)                                         the inference kernel, no epilogue (any stride)
@@ -257,7 +257,7 @@ def weight_grad(x: Tensor, g: Tensor, kernel: Sequence[int], stride: int = 1, pa
         from . import _lib
         planes = pk["w_f16"][0] if f16 else C.split_planes(pk)
         bm = 128 if cin % 128 == 0 else 64
-        bn = 256 if (f16 and bm == 128 and cout % 256 == 0 and taps * (cin // 128) >= 32) else (128 if cout > 64 else 64)      # (the library's own choice: ndet_wgrad_split*)
+        bn = 256 if (f16 and bm == 128 and cout % 256 == 0 and taps * (cin // 128) >= 32) else (128 if cout > 64 else 64)      # (the library's own choice: ndet_wgrad_split)
         tiles = (taps * cin // bm) * ((cout + bn - 1) // bn)
         ksteps = lrow // 32
         # ~1 000 workgroups of the 128 x 128 tile (768 left the FPN's 36-tile layer at 24 splits: 1 505 us against 1 260 at 32), ~800 of the 128 x 256
@@ -271,16 +271,11 @@ def weight_grad(x: Tensor, g: Tensor, kernel: Sequence[int], stride: int = 1, pa
         dw = None if keep else torch.empty((m, cout), dtype=torch.float32, device=x.device)
         i3 = lambda v: (ctypes.c_int * 3)(*v)
         st = c_void_p(raw_stream(x.device))
-        if f16:
-            _lib.check(_lib.load().ndet_wgrad_split_f16x2(c_void_p(x.data_ptr()), d, h, w, cin, i3(k3), i3(s3), i3(pads), c_void_p(planes.data_ptr()), cout, lrow,
-                                                          splits, c_void_p(x_slot.data_ptr()), c_void_p(dy_slot.data_ptr()), c_void_p(0 if ws is None else ws.data_ptr()),
-                                                          c_void_p(ws.data_ptr() if keep else dw.data_ptr()), int(keep), st), "wgrad_split_f16x2")
-            if keep:
-                return _to_torch_layout(ws, taps, cin, cout, kernel, splits)
-        else:
-            _lib.check(_lib.load().ndet_wgrad_split(c_void_p(x.data_ptr()), d, h, w, cin, i3(k3), i3(s3), i3(pads), c_void_p(planes.data_ptr()), cout, lrow,
-                                                    splits, 0 if arith == "bf16" else 2, c_void_p(0 if ws is None else ws.data_ptr()),
-                                                    c_void_p(dw.data_ptr()), st), "wgrad_split")
+        _lib.check(_lib.load().ndet_wgrad_split(c_void_p(x.data_ptr()), d, h, w, cin, i3(k3), i3(s3), i3(pads), c_void_p(planes.data_ptr()), cout, lrow,
+                                                splits, C.ARITH_ID[arith], C._ptr(x_slot), C._ptr(dy_slot), C._ptr(ws), C._ptr(ws if keep else dw), int(keep), st),
+                   "wgrad_split")
+        if keep:
+            return _to_torch_layout(ws, taps, cin, cout, kernel, splits)
         return _to_torch_layout(dw, taps, cin, cout, kernel)
     per = max(1, min(taps, (1 << 30) // (cin * lrow * 4)))  # the kernel addresses its operand with 32-bit byte offsets: <= 1 GiB per launch
     if f16 and per >= taps and taps <= 27 and cin % 32 == 0:

@@ -157,7 +157,7 @@ __device__ __forceinline__ void conv_guard_check(const Conv3dParams& p, float am
 
 // internal launchers (one per kernel family) and the shared split-K reduction
 int conv_f32_launch(Conv3dParams& p, int tile, hipStream_t st, const char* fn);
-int conv_split_launch(Conv3dParams& p, int tile, hipStream_t st, const char* fn);
+int conv_split_launch(Conv3dParams& p, int tile, bool keep_partials, hipStream_t st, const char* fn);
 int conv_splitk_reduce_launch(const Conv3dParams& p, hipStream_t st, const char* fn);
 
 // Logical (row tile, column tile, split / tap) of this workgroup under p.order; gx = gridDim.x row tiles, gy column tiles, gz splits.

@@ -25,10 +25,6 @@
 
 #include "spl_common.hpp"
 
-// set per call by the weight-gradient entry points (ndet_conv_ndhwc_train, ndet_wgrad_split*): the split-K partials stay in the workspace and
-// ndet_wgrad_to_torch adds them up (same fixed order) on its way to torch's layout -- one launch and one pass over dW fewer per layer
-static thread_local int g_keep_partials = 0;
-
 // K walk of the unified tiles: fills acc (per-wave 32x32 MFMA tiles) for GEMM rows m0.. and channels n0..; returns the transposed-conv tap
 // (blockIdx.z) in ztap.  Ends behind a barrier: the LDS operand planes are free for the epilogue.
 template <int BM, int BN, int WGM, int WGN, int SCH>
@@ -1753,7 +1749,9 @@ extern "C" int ndet_measurement_knob(const char* name, int64_t value) {
 }
 extern "C" int ndet_amax_slot_floats(void) { return NDET_AMAX_SUB * NDET_AMAX_STRIDE; }
 
-int conv_split_launch(Conv3dParams& p, int tile, hipStream_t st, const char* fn) {
+// keep_partials (weight-gradient GEMMs): a split-K launch leaves its partial sums in the workspace and ndet_wgrad_to_torch adds them up (same fixed
+// order) on its way to torch's layout -- one launch and one pass over dW fewer per layer
+int conv_split_launch(Conv3dParams& p, int tile, bool keep_partials, hipStream_t st, const char* fn) {
     p.direct = 0;
     p.nt = (p.splits <= 1 || p.transposed) && (int64_t)p.M * p.Cout * 4 * (p.transposed ? 8 : 1) >= conv_nt_bytes() ? 1 : 0;
     if (tile >= 100000 && (tile - 100000 == 64 || tile - 100000 == 128 || tile - 100000 == 12864)) {   // 100064 / 100128 / 112864: direct epilogue
@@ -1780,7 +1778,7 @@ int conv_split_launch(Conv3dParams& p, int tile, hipStream_t st, const char* fn)
         }
     }
     int rc;
-    switch (tile) {
+    switch (tile) {     // the tile ids of NdetConvArgs::tile (with the direct forms above): any other is rejected here, before a launch
         case 64: rc = split_launch_tile<64, 64, 2, 2>(p, st, fn); break;
         case 128: rc = split_launch_tile<128, 128, 2, 2>(p, st, fn); break;
         case 12864: rc = split_launch_tile<128, 64, 2, 2>(p, st, fn); break;
@@ -1799,7 +1797,7 @@ int conv_split_launch(Conv3dParams& p, int tile, hipStream_t st, const char* fn)
     }
     if (rc != NDET_OK) return rc;
     NDET_CHECK_LAUNCH(fn);
-    if (g_keep_partials && p.splits > 1) return NDET_OK;
+    if (keep_partials && p.splits > 1) return NDET_OK;
     return conv_splitk_reduce_launch(p, st, fn);
 }
 
@@ -1903,7 +1901,7 @@ extern "C" int ndet_split_weights_bf16x3_torch(const float* w_torch, int taps, i
 
 // Both packs of a TRAINING step's weight in one pass over it: the layer's own planes (taps, Cin/32, WPL, Cout, 32) and the planes of its data gradient
 // W'[t][ci][co] = W[co][ci][taps - 1 - t], (taps, ceil(Cout/32), WPL, Cin, 32) (Cout zero-padded) -- SCH 0: three bf16 planes; SCH 1: two fp16 planes of
-// w * conv_xscale(amax slot), the scale never leaving the device (ndet_conv_ndhwc_train reads its inverse from the same slot).  k_split_weights_torch
+// w * conv_xscale(amax slot), the scale never leaving the device (ndet_conv_split with w_amax reads its inverse from the same slot).  k_split_weights_torch
 // reads the torch layout (Cout, Cin, taps) with a stride of `taps` floats between neighbouring lanes (a 1024 x 1024 x 27 weight: 559 us, 0.2 TB/s of
 // reads) and runs once per pack; here a workgroup takes a 32 x 32 (co, ci) block with all its taps -- 32 contiguous runs of 32 taps floats -- through
 // LDS, and every (tap, plane) of either pack leaves as one contiguous 2 KB piece.
@@ -2028,96 +2026,6 @@ extern "C" int ndet_split_weights_train(const float* w_torch, int taps, int Cout
     return NDET_OK;
 }
 
-static int conv_split_entry(const char* fn, int max_order, const float* in_amax, float w_inv_scale, float* out_amax, const float* in, const uint16_t* w_planes,
-                            float* out, int D, int H, int W, int Cin, int Cout, const int* kernel, const int* stride, const int* pad, int transposed,
-                            const float* scale, const float* shift, const float* residual, int residual_up2, int relu, int splits, int tile,
-                            void* workspace, void* stream);
-
-extern "C" int ndet_conv_ndhwc_split(const float* in, const uint16_t* w_planes, float* out, int D, int H, int W, int Cin, int Cout,
-                                     const int* kernel, const int* stride, const int* pad, int transposed, const float* scale,
-                                     const float* shift, const float* residual, int residual_up2, int relu, int splits, int tile,
-                                     void* workspace, void* stream) {
-    return conv_split_entry("ndet_conv_ndhwc_split", 2, nullptr, 1.0f, nullptr, in, w_planes, out, D, H, W, Cin, Cout, kernel, stride, pad, transposed, scale, shift, residual,
-                            residual_up2, relu, splits, tile, workspace, stream);
-}
-
-extern "C" int ndet_conv_ndhwc_bf16(const float* in, const uint16_t* w_planes, float* out, int D, int H, int W, int Cin, int Cout,
-                                    const int* kernel, const int* stride, const int* pad, int transposed, const float* scale,
-                                    const float* shift, const float* residual, int residual_up2, int relu, int splits, int tile,
-                                    void* workspace, void* stream) {
-    return conv_split_entry("ndet_conv_ndhwc_bf16", 0, nullptr, 1.0f, nullptr, in, w_planes, out, D, H, W, Cin, Cout, kernel, stride, pad, transposed, scale, shift, residual,
-                            residual_up2, relu, splits, tile, workspace, stream);
-}
-
-struct ConvGuard { unsigned* flag; float l1, l1_3, tol; const float* w_amax; const float* map_w; const float* map_b; float* map_out; };
-static thread_local ConvGuard g_guard = {nullptr, 0.0f, 0.0f, 0.0f, nullptr, nullptr, nullptr, nullptr};     // handed from the *_guarded / *_train entry points to the shared argument checks below (per call)
-
-extern "C" int ndet_conv_ndhwc_guarded(const float* in, const uint16_t* w_planes, float* out, int D, int H, int W, int Cin, int Cout,
-                                       const int* kernel, const int* stride, const int* pad, int transposed, const float* scale,
-                                       const float* shift, const float* residual, int residual_up2, int relu, int splits, int tile, int arith,
-                                       const float* in_amax, float w_inv_scale, float* out_amax, void* workspace, float guard_l1, float guard_tol,
-                                       unsigned* guard, void* stream) {
-    NDET_REQUIRE(!guard || (guard_l1 >= 0.0f && guard_tol > 0.0f), NDET_E_INVALID, "ndet_conv_ndhwc_guarded: the guard needs guard_l1 >= 0 and guard_tol > 0");
-    g_guard = ConvGuard{arith == 1 ? guard : nullptr, guard_l1, 0.0f, guard_tol, nullptr};
-    const int rc = ndet_conv_ndhwc_arith(in, w_planes, out, D, H, W, Cin, Cout, kernel, stride, pad, transposed, scale, shift, residual, residual_up2, relu, splits,
-                                         tile, arith, in_amax, w_inv_scale, out_amax, workspace, stream);
-    g_guard = ConvGuard{nullptr, 0.0f, 0.0f, 0.0f, nullptr};
-    return rc;
-}
-
-// ndet_conv_ndhwc_guarded with a chained 32-channel projection of the output rows in the same launch (see Conv3dParams::map_out): only the
-// halo-stationary tiles that own all Cout = 256 channels of their rows take it (tile 3256 / 3257 / 3258), without split-K, residual or ReLU.
-extern "C" int ndet_conv_ndhwc_mapped(const float* in, const uint16_t* w_planes, float* out, int D, int H, int W, int Cin, int Cout,
-                                      const int* kernel, const int* stride, const int* pad, const float* scale, const float* shift, int tile, int arith,
-                                      const float* in_amax, float w_inv_scale, float* out_amax, float guard_l1, float guard_tol, unsigned* guard,
-                                      const float* map_w, const float* map_b, float* map_out, void* stream) {
-    const char* fn = "ndet_conv_ndhwc_mapped";
-    NDET_REQUIRE(map_w && map_b && map_out, NDET_E_INVALID, "%s: null projection pointers", fn);
-    NDET_REQUIRE((((uintptr_t)map_w | (uintptr_t)map_b | (uintptr_t)map_out) & 15) == 0, NDET_E_UNSUPPORTED, "%s: projection pointers must be 16-byte aligned", fn);
-    NDET_REQUIRE(tile == 3256 || tile == 3257 || tile == 3258, NDET_E_UNSUPPORTED, "%s: tile %d does not own whole rows (3256 / 3257 / 3258 do)", fn, tile);
-    NDET_REQUIRE(Cout == 256, NDET_E_UNSUPPORTED, "%s: Cout=%d, the 256-column tiles own whole rows of 256 channels only", fn, Cout);
-    NDET_REQUIRE(!guard || (guard_l1 >= 0.0f && guard_tol > 0.0f), NDET_E_INVALID, "%s: the guard needs guard_l1 >= 0 and guard_tol > 0", fn);
-    g_guard = ConvGuard{arith == 1 ? guard : nullptr, guard_l1, 0.0f, guard_tol, nullptr, map_w, map_b, map_out};
-    const int rc = ndet_conv_ndhwc_arith(in, w_planes, out, D, H, W, Cin, Cout, kernel, stride, pad, 0, scale, shift, nullptr, 0, 0, 1, tile, arith, in_amax, w_inv_scale,
-                                         out_amax, nullptr, stream);
-    g_guard = ConvGuard{nullptr, 0.0f, 0.0f, 0.0f, nullptr, nullptr, nullptr, nullptr};
-    return rc;
-}
-
-// The fp16-pair launch of the training step: the weight planes were scaled ON THE DEVICE by conv_xscale of the slot `w_amax` (ndet_split_weights_train:
-// the optimizer moves the weights every step; ndet_wgrad_dy_planes_f16x2: the weight gradient's "weight" operand is dy), so the kernels take 1 / scale
-// from the same slot.  `guard_k` = the contraction length (taps x Cin): the range guard bounds ||w||_1 by guard_k max|w|; guard null = no check.
-extern "C" int ndet_conv_ndhwc_train(const float* in, const uint16_t* w_planes, float* out, int D, int H, int W, int Cin, int Cout,
-                                     const int* kernel, const int* stride, const int* pad, const float* scale, const float* shift, const float* residual,
-                                     int relu, int splits, int tile, const float* in_amax, const float* w_amax, float* out_amax, void* workspace,
-                                     float guard_k, float guard_tol, unsigned* guard, int keep_partials, void* stream) {
-    NDET_REQUIRE(w_amax != nullptr, NDET_E_INVALID, "ndet_conv_ndhwc_train: the weight planes' amax slot is required");
-    NDET_REQUIRE(!keep_partials || (!scale && !residual && !relu && !out_amax), NDET_E_INVALID, "ndet_conv_ndhwc_train: keep_partials leaves the epilogue to ndet_wgrad_to_torch (no affine / residual / ReLU / amax)");
-    NDET_REQUIRE(!guard || (guard_k >= 0.0f && guard_tol > 0.0f), NDET_E_INVALID, "ndet_conv_ndhwc_train: the guard needs guard_k >= 0 and guard_tol > 0");
-    g_guard = ConvGuard{guard, guard_k, 0.0f, guard_tol, w_amax};
-    g_keep_partials = keep_partials ? 1 : 0;
-    const int rc = ndet_conv_ndhwc_arith(in, w_planes, out, D, H, W, Cin, Cout, kernel, stride, pad, 0, scale, shift, residual, 0, relu, splits, tile, 1, in_amax, 1.0f,
-                                         out_amax, workspace, stream);
-    g_keep_partials = 0;
-    g_guard = ConvGuard{nullptr, 0.0f, 0.0f, 0.0f, nullptr};
-    return rc;
-}
-
-extern "C" int ndet_conv_ndhwc_arith(const float* in, const uint16_t* w_planes, float* out, int D, int H, int W, int Cin, int Cout,
-                                     const int* kernel, const int* stride, const int* pad, int transposed, const float* scale,
-                                     const float* shift, const float* residual, int residual_up2, int relu, int splits, int tile, int arith,
-                                     const float* in_amax, float w_inv_scale, float* out_amax, void* workspace, void* stream) {
-    const char* fn = "ndet_conv_ndhwc_arith";
-    NDET_REQUIRE(arith >= 0 && arith <= 2, NDET_E_INVALID, "%s: arith must be 0 (bf16x3), 1 (fp16 pair) or 2 (bf16)", fn);
-    if (arith == 1) {
-        NDET_REQUIRE(in_amax != nullptr && w_inv_scale > 0.0f, NDET_E_INVALID, "%s: the fp16-pair arithmetic needs the input's amax slot and the weight planes' inverse scale", fn);
-    } else {
-        NDET_REQUIRE(in_amax == nullptr, NDET_E_INVALID, "%s: in_amax belongs to the fp16-pair arithmetic only", fn);
-    }
-    return conv_split_entry(fn, arith == 0 ? 2 : (arith == 1 ? 1 : 0), in_amax, arith == 1 ? w_inv_scale : 1.0f, out_amax, in, w_planes, out, D, H, W, Cin, Cout,
-                            kernel, stride, pad, transposed, scale, shift, residual, residual_up2, relu, splits, tile, workspace, stream);
-}
-
 // max |x| of a tensor into a zeroed slot: the amax_in of a fp16-pair convolution whose input was not written by one of the convolution kernels
 __global__ __launch_bounds__(256) void k_amax(const float* __restrict__ x, int64_t n4, int64_t n, float* __restrict__ slot) {
     // every workgroup takes ONE contiguous range of the tensor: its maximum is the maximum of a region (a few rows / voxels), which is what the range
@@ -2147,37 +2055,9 @@ extern "C" int ndet_amax_f32(const float* x, int64_t n, float* slot, void* strea
     return NDET_OK;
 }
 
-static int conv_split_entry(const char* fn, int max_order, const float* in_amax, float w_inv_scale, float* out_amax, const float* in, const uint16_t* w_planes,
-                            float* out, int D, int H, int W, int Cin, int Cout, const int* kernel, const int* stride, const int* pad, int transposed,
-                            const float* scale, const float* shift, const float* residual, int residual_up2, int relu, int splits, int tile,
-                            void* workspace, void* stream) {
-    NDET_REQUIRE(in && w_planes && out && kernel && stride && pad, NDET_E_INVALID, "%s: null pointer", fn);
-    NDET_REQUIRE(D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
-    NDET_REQUIRE((scale == nullptr) == (shift == nullptr), NDET_E_INVALID, "%s: scale and shift go together", fn);
-    NDET_REQUIRE(relu >= 0 && relu <= 2 && (tile == 0 || tile == 64 || tile == 128 || tile == 12864 || tile == 128256 || tile == 129256 || tile == 129257 || tile == 129064 || tile == 3128 || tile == 3256 || tile == 3257 || tile == 3258 ||
-                                          tile == 100064 || tile == 100128 || tile == 112864), NDET_E_INVALID, "%s: bad relu mode / tile", fn);
-    NDET_REQUIRE(Cin % CBK == 0, NDET_E_UNSUPPORTED, "%s: Cin=%d must be a multiple of %d", fn, Cin, CBK);
-    NDET_REQUIRE((((uintptr_t)in | (uintptr_t)w_planes) & 15) == 0, NDET_E_UNSUPPORTED, "%s: in / weights must be 16-byte aligned", fn);
-    Conv3dParams p;
-    p.in = in; p.w = reinterpret_cast<const float*>(w_planes); p.out = out; p.scale = scale; p.shift = shift; p.res = residual;
-    p.partial = (float*)workspace;
-    p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.relu = relu;
-    p.max_order = max_order;
-    p.amax_in = in_amax; p.winv = w_inv_scale; p.amax_out = out_amax;
-    p.guard = g_guard.flag; p.guard_l1 = g_guard.l1; p.guard_tol = g_guard.tol; p.w_amax = g_guard.w_amax;
-    p.map_w = g_guard.map_w; p.map_b = g_guard.map_b; p.map_out = g_guard.map_out;
-    if (transposed) {
-        for (int a = 0; a < 3; ++a)
-            NDET_REQUIRE(kernel[a] == 2 && stride[a] == 2 && pad[a] == 0, NDET_E_UNSUPPORTED, "%s: transposed conv supports kernel 2 stride 2 pad 0 only", fn);
-        p.transposed = 1;
-        p.kd = p.kh = p.kw = 2; p.sd = p.sh = p.sw = 2; p.pd = p.ph = p.pw = 0;
-        p.OD = 2 * D; p.OH = 2 * H; p.OW = 2 * W;
-        NDET_REQUIRE((int64_t)p.OD * p.OH * p.OW < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: tensor too large", fn);
-        p.M = D * H * W;
-        p.splits = 1; p.partial = nullptr;
-        p.res_up2 = 0; p.RH = p.RW = 0;
-        return conv_split_launch(p, tile, (hipStream_t)stream, fn);
-    }
+// Checks kernel / stride / pad of a plain (not transposed) convolution over p.D x p.H x p.W x p.Cin and fills p's taps, strides, pads,
+// output extents and GEMM rows M.
+static int conv_geometry(Conv3dParams& p, const int* kernel, const int* stride, const int* pad, const char* fn) {
     for (int a = 0; a < 3; ++a)
         NDET_REQUIRE(kernel[a] >= 1 && kernel[a] <= 7 && stride[a] >= 1 && stride[a] <= 4 && pad[a] >= 0 && pad[a] < kernel[a], NDET_E_UNSUPPORTED,
                      "%s: kernel/stride/pad out of range on axis %d", fn, a);
@@ -2185,20 +2065,82 @@ static int conv_split_entry(const char* fn, int max_order, const float* in_amax,
     p.kd = kernel[0]; p.kh = kernel[1]; p.kw = kernel[2];
     p.sd = stride[0]; p.sh = stride[1]; p.sw = stride[2];
     p.pd = pad[0]; p.ph = pad[1]; p.pw = pad[2];
-    p.OD = (D + 2 * p.pd - p.kd) / p.sd + 1;
-    p.OH = (H + 2 * p.ph - p.kh) / p.sh + 1;
-    p.OW = (W + 2 * p.pw - p.kw) / p.sw + 1;
+    p.OD = (p.D + 2 * p.pd - p.kd) / p.sd + 1;
+    p.OH = (p.H + 2 * p.ph - p.kh) / p.sh + 1;
+    p.OW = (p.W + 2 * p.pw - p.kw) / p.sw + 1;
     NDET_REQUIRE(p.OD > 0 && p.OH > 0 && p.OW > 0, NDET_E_INVALID, "%s: empty output", fn);
-    NDET_REQUIRE((int64_t)p.OD * p.OH * p.OW < ((int64_t)1 << 31) && (int64_t)D * H * W * Cin < ((int64_t)1 << 40), NDET_E_UNSUPPORTED, "%s: tensor too large", fn);
+    NDET_REQUIRE((int64_t)p.OD * p.OH * p.OW < ((int64_t)1 << 31) && (int64_t)p.D * p.H * p.W * p.Cin < ((int64_t)1 << 40), NDET_E_UNSUPPORTED,
+                 "%s: tensor too large", fn);
     p.M = p.OD * p.OH * p.OW;
-    p.splits = splits < 1 ? 1 : splits;
-    p.res_up2 = (residual && residual_up2) ? 1 : 0;
+    return NDET_OK;
+}
+
+// arith (0 bf16x3, 1 fp16 pair, 2 bf16) -> Conv3dParams::max_order; the kernels' SCH template argument is numbered as arith (conv_scheme)
+static int max_order_of(int arith) { return arith == 0 ? 2 : (arith == 1 ? 1 : 0); }
+
+extern "C" int ndet_conv_split(const NdetConvArgs* a, void* stream) {
+    const char* fn = "ndet_conv_split";
+    NDET_REQUIRE(a && a->size == (int32_t)sizeof(NdetConvArgs), NDET_E_INVALID, "%s: the argument block must be set up with size = %d", fn,
+                 (int)sizeof(NdetConvArgs));
+    NDET_REQUIRE(a->arith >= 0 && a->arith <= 2, NDET_E_INVALID, "%s: arith must be 0 (bf16x3), 1 (fp16 pair) or 2 (bf16)", fn);
+    const bool f16 = a->arith == 1, train = a->w_amax != nullptr;
+    NDET_REQUIRE(!train || (f16 && !a->transposed && !a->residual_up2), NDET_E_INVALID,
+                 "%s: w_amax (the training form) needs arith 1, no transposition and no upsampled residual", fn);
+    if (f16) {
+        NDET_REQUIRE(a->in_amax && (train || a->w_inv_scale > 0.0f), NDET_E_INVALID,
+                     "%s: the fp16-pair arithmetic needs the input's amax slot and the weight planes' inverse scale (or w_amax)", fn);
+        NDET_REQUIRE(!a->guard || (a->guard_l1 >= 0.0f && a->guard_tol > 0.0f), NDET_E_INVALID, "%s: the guard needs guard_l1 >= 0 and guard_tol > 0", fn);
+    } else {
+        NDET_REQUIRE(!a->in_amax, NDET_E_INVALID, "%s: in_amax belongs to the fp16-pair arithmetic only", fn);
+    }
+    NDET_REQUIRE(!a->keep_partials || (!a->scale && !a->residual && !a->relu && !a->out_amax && !a->transposed), NDET_E_INVALID,
+                 "%s: keep_partials leaves the epilogue to ndet_wgrad_to_torch (no affine / residual / ReLU / amax, no transposition)", fn);
+    if (a->map_w || a->map_b || a->map_out) {
+        NDET_REQUIRE(a->map_w && a->map_b && a->map_out, NDET_E_INVALID, "%s: null projection pointers", fn);
+        NDET_REQUIRE((((uintptr_t)a->map_w | (uintptr_t)a->map_b | (uintptr_t)a->map_out) & 15) == 0, NDET_E_UNSUPPORTED,
+                     "%s: projection pointers must be 16-byte aligned", fn);
+        NDET_REQUIRE(a->tile == 3256 || a->tile == 3257 || a->tile == 3258, NDET_E_UNSUPPORTED, "%s: tile %d does not own whole rows (3256 / 3257 / 3258 do)",
+                     fn, a->tile);
+        NDET_REQUIRE(a->Cout == 256, NDET_E_UNSUPPORTED, "%s: Cout=%d, the 256-column tiles own whole rows of 256 channels only", fn, a->Cout);
+        NDET_REQUIRE(a->splits <= 1 && !a->residual && !a->relu && !a->transposed, NDET_E_UNSUPPORTED,
+                     "%s: the chained projection takes no split-K, residual, ReLU or transposition", fn);
+    }
+    NDET_REQUIRE(a->in && a->w_planes && a->out, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(a->D > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
+    NDET_REQUIRE((a->scale == nullptr) == (a->shift == nullptr), NDET_E_INVALID, "%s: scale and shift go together", fn);
+    NDET_REQUIRE(a->relu >= 0 && a->relu <= 2, NDET_E_INVALID, "%s: bad relu mode", fn);
+    NDET_REQUIRE(a->Cin % CBK == 0, NDET_E_UNSUPPORTED, "%s: Cin=%d must be a multiple of %d", fn, a->Cin, CBK);
+    NDET_REQUIRE((((uintptr_t)a->in | (uintptr_t)a->w_planes) & 15) == 0, NDET_E_UNSUPPORTED, "%s: in / weights must be 16-byte aligned", fn);
+    Conv3dParams p;
+    p.in = a->in; p.w = reinterpret_cast<const float*>(a->w_planes); p.out = a->out; p.scale = a->scale; p.shift = a->shift; p.res = a->residual;
+    p.partial = (float*)a->workspace;
+    p.D = a->D; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.relu = a->relu;
+    p.max_order = max_order_of(a->arith);
+    p.amax_in = a->in_amax; p.winv = f16 && !train ? a->w_inv_scale : 1.0f; p.w_amax = a->w_amax; p.amax_out = a->out_amax;
+    p.guard = f16 ? a->guard : nullptr; p.guard_l1 = a->guard_l1; p.guard_tol = a->guard_tol;
+    p.map_w = a->map_w; p.map_b = a->map_b; p.map_out = a->map_out;
+    if (a->transposed) {
+        for (int i = 0; i < 3; ++i)
+            NDET_REQUIRE(a->kernel[i] == 2 && a->stride[i] == 2 && a->pad[i] == 0, NDET_E_UNSUPPORTED, "%s: transposed conv supports kernel 2 stride 2 pad 0 only", fn);
+        p.transposed = 1;
+        p.kd = p.kh = p.kw = 2; p.sd = p.sh = p.sw = 2; p.pd = p.ph = p.pw = 0;
+        p.OD = 2 * p.D; p.OH = 2 * p.H; p.OW = 2 * p.W;
+        NDET_REQUIRE((int64_t)p.OD * p.OH * p.OW < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: tensor too large", fn);
+        p.M = p.D * p.H * p.W;
+        p.splits = 1; p.partial = nullptr;
+        p.res_up2 = 0; p.RH = p.RW = 0;
+        return conv_split_launch(p, a->tile, false, (hipStream_t)stream, fn);
+    }
+    const int rc = conv_geometry(p, a->kernel, a->stride, a->pad, fn);
+    if (rc != NDET_OK) return rc;
+    p.splits = a->splits < 1 ? 1 : a->splits;
+    p.res_up2 = (a->residual && a->residual_up2) ? 1 : 0;
     p.RH = (p.OH + 1) / 2; p.RW = (p.OW + 1) / 2;
     NDET_REQUIRE(!(p.res_up2 && p.splits > 1), NDET_E_UNSUPPORTED, "%s: upsampled residual cannot be combined with split-K", fn);
-    const int iters = p.kd * p.kh * p.kw * (Cin / CBK);
+    const int iters = p.kd * p.kh * p.kw * (p.Cin / CBK);
     NDET_REQUIRE(p.splits <= iters, NDET_E_INVALID, "%s: splits=%d exceeds the %d K steps", fn, p.splits, iters);
-    NDET_REQUIRE(p.splits == 1 || workspace != nullptr, NDET_E_INVALID, "%s: split-K needs a workspace", fn);
-    return conv_split_launch(p, tile, (hipStream_t)stream, fn);
+    NDET_REQUIRE(p.splits == 1 || a->workspace != nullptr, NDET_E_INVALID, "%s: split-K needs a workspace", fn);
+    return conv_split_launch(p, a->tile, a->keep_partials != 0, (hipStream_t)stream, fn);
 }
 
 template <int MID, int SCH>
@@ -2219,42 +2161,16 @@ static int chain_launch(const Conv3dParams& p, const ConvChain& c, hipStream_t s
     return NDET_OK;
 }
 
-extern "C" int ndet_conv_chain_arith(const float* in, const uint16_t* w_planes, int D, int H, int W, int Cin, int Cmid, const int* kernel,
-                                     const int* stride, const int* pad, const float* scale1, const float* shift1, const uint16_t* w3_planes,
-                                     int Cout, const float* scale3, const float* shift3, const float* residual, int relu3, float* out,
-                                     int arith, const float* in_amax, float w1_inv_scale, float w3_inv_scale, float* out_amax, void* stream);
-
-extern "C" int ndet_conv_chain_guarded(const float* in, const uint16_t* w_planes, int D, int H, int W, int Cin, int Cmid, const int* kernel,
-                                       const int* stride, const int* pad, const float* scale1, const float* shift1, const uint16_t* w3_planes,
-                                       int Cout, const float* scale3, const float* shift3, const float* residual, int relu3, float* out,
-                                       int arith, const float* in_amax, float w1_inv_scale, float w3_inv_scale, float* out_amax, float guard_l1,
-                                       float guard_l1_3, float guard_tol, unsigned* guard, void* stream) {
-    NDET_REQUIRE(!guard || (guard_l1 >= 0.0f && guard_l1_3 >= 0.0f && guard_tol > 0.0f), NDET_E_INVALID, "ndet_conv_chain_guarded: the guard needs l1 >= 0 and tol > 0");
-    g_guard = ConvGuard{arith == 1 ? guard : nullptr, guard_l1, guard_l1_3, guard_tol};
-    const int rc = ndet_conv_chain_arith(in, w_planes, D, H, W, Cin, Cmid, kernel, stride, pad, scale1, shift1, w3_planes, Cout, scale3, shift3, residual, relu3, out,
-                                         arith, in_amax, w1_inv_scale, w3_inv_scale, out_amax, stream);
-    g_guard = ConvGuard{nullptr, 0.0f, 0.0f, 0.0f};
-    return rc;
-}
-
-extern "C" int ndet_conv_chain_split(const float* in, const uint16_t* w_planes, int D, int H, int W, int Cin, int Cmid, const int* kernel,
-                                     const int* stride, const int* pad, const float* scale1, const float* shift1, const uint16_t* w3_planes,
-                                     int Cout, const float* scale3, const float* shift3, const float* residual, int relu3, float* out,
-                                     int max_order, void* stream) {
-    NDET_REQUIRE(max_order == 0 || max_order == 2, NDET_E_INVALID, "ndet_conv_chain_split: bad arithmetic");
-    return ndet_conv_chain_arith(in, w_planes, D, H, W, Cin, Cmid, kernel, stride, pad, scale1, shift1, w3_planes, Cout, scale3, shift3, residual, relu3, out,
-                                 max_order == 0 ? 2 : 0, nullptr, 1.0f, 1.0f, nullptr, stream);
-}
-
-extern "C" int ndet_conv_chain_arith(const float* in, const uint16_t* w_planes, int D, int H, int W, int Cin, int Cmid, const int* kernel,
-                                     const int* stride, const int* pad, const float* scale1, const float* shift1, const uint16_t* w3_planes,
-                                     int Cout, const float* scale3, const float* shift3, const float* residual, int relu3, float* out,
-                                     int arith, const float* in_amax, float w1_inv_scale, float w3_inv_scale, float* out_amax, void* stream) {
-    const char* fn = "ndet_conv_chain_arith";
+extern "C" int ndet_conv_chain(const float* in, const uint16_t* w_planes, int D, int H, int W, int Cin, int Cmid, const int* kernel,
+                               const int* stride, const int* pad, const float* scale1, const float* shift1, const uint16_t* w3_planes,
+                               int Cout, const float* scale3, const float* shift3, const float* residual, int relu3, float* out,
+                               int arith, const float* in_amax, float w1_inv_scale, float w3_inv_scale, float* out_amax, float guard_l1,
+                               float guard_l1_3, float guard_tol, unsigned* guard, void* stream) {
+    const char* fn = "ndet_conv_chain";
     NDET_REQUIRE(arith >= 0 && arith <= 2, NDET_E_INVALID, "%s: arith must be 0 (bf16x3), 1 (fp16 pair) or 2 (bf16)", fn);
     NDET_REQUIRE((arith == 1) == (in_amax != nullptr), NDET_E_INVALID, "%s: in_amax goes with the fp16-pair arithmetic", fn);
     NDET_REQUIRE(arith != 1 || (w1_inv_scale > 0.0f && w3_inv_scale > 0.0f), NDET_E_INVALID, "%s: the fp16-pair arithmetic needs the weight planes' inverse scales", fn);
-    const int max_order = arith == 0 ? 2 : (arith == 1 ? 1 : 0);
+    NDET_REQUIRE(arith != 1 || !guard || (guard_l1 >= 0.0f && guard_l1_3 >= 0.0f && guard_tol > 0.0f), NDET_E_INVALID, "%s: the guard needs l1 >= 0 and tol > 0", fn);
     NDET_REQUIRE(in && w_planes && w3_planes && out && kernel && stride && pad, NDET_E_INVALID, "%s: null pointer", fn);
     NDET_REQUIRE(D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
     NDET_REQUIRE((scale1 == nullptr) == (shift1 == nullptr) && (scale3 == nullptr) == (shift3 == nullptr), NDET_E_INVALID, "%s: scale and shift go together", fn);
@@ -2264,27 +2180,16 @@ extern "C" int ndet_conv_chain_arith(const float* in, const uint16_t* w_planes, 
     NDET_REQUIRE((((uintptr_t)in | (uintptr_t)w_planes | (uintptr_t)w3_planes) & 15) == 0, NDET_E_UNSUPPORTED, "%s: in / weights must be 16-byte aligned", fn);
     Conv3dParams p;
     p.in = in; p.w = reinterpret_cast<const float*>(w_planes); p.out = nullptr; p.scale = scale1; p.shift = shift1; p.res = nullptr; p.partial = nullptr;
-    p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cmid; p.relu = 1; p.max_order = max_order;
+    p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cmid; p.relu = 1; p.max_order = max_order_of(arith);
     p.amax_in = in_amax; p.winv = w1_inv_scale;
-    p.guard = g_guard.flag; p.guard_l1 = g_guard.l1; p.guard_tol = g_guard.tol;
-    for (int a = 0; a < 3; ++a)
-        NDET_REQUIRE(kernel[a] >= 1 && kernel[a] <= 7 && stride[a] >= 1 && stride[a] <= 4 && pad[a] >= 0 && pad[a] < kernel[a], NDET_E_UNSUPPORTED,
-                     "%s: kernel/stride/pad out of range on axis %d", fn, a);
-    p.transposed = 0;
-    p.kd = kernel[0]; p.kh = kernel[1]; p.kw = kernel[2];
-    p.sd = stride[0]; p.sh = stride[1]; p.sw = stride[2];
-    p.pd = pad[0]; p.ph = pad[1]; p.pw = pad[2];
-    p.OD = (D + 2 * p.pd - p.kd) / p.sd + 1;
-    p.OH = (H + 2 * p.ph - p.kh) / p.sh + 1;
-    p.OW = (W + 2 * p.pw - p.kw) / p.sw + 1;
-    NDET_REQUIRE(p.OD > 0 && p.OH > 0 && p.OW > 0, NDET_E_INVALID, "%s: empty output", fn);
-    NDET_REQUIRE((int64_t)p.OD * p.OH * p.OW < ((int64_t)1 << 31) && (int64_t)D * H * W * Cin < ((int64_t)1 << 40), NDET_E_UNSUPPORTED, "%s: tensor too large", fn);
-    p.M = p.OD * p.OH * p.OW;
+    p.guard = arith == 1 ? guard : nullptr; p.guard_l1 = guard_l1; p.guard_tol = guard_tol;
+    const int rc0 = conv_geometry(p, kernel, stride, pad, fn);
+    if (rc0 != NDET_OK) return rc0;
     NDET_REQUIRE(((int64_t)p.M + 128) * Cout * 4 < ((int64_t)1 << 32), NDET_E_UNSUPPORTED, "%s: the output is addressed with 32-bit byte offsets (< 4 GB)", fn);
     p.splits = 1; p.res_up2 = 0; p.RH = p.RW = 0;
     ConvChain c;
     c.w3 = w3_planes; c.scale3 = scale3; c.shift3 = shift3; c.res = residual; c.out = out; c.Cout3 = Cout; c.relu3 = relu3;
-    c.w3inv = arith == 1 ? w3_inv_scale : 1.0f; c.amax_out = out_amax; c.guard_l1 = g_guard.l1_3;
+    c.w3inv = arith == 1 ? w3_inv_scale : 1.0f; c.amax_out = out_amax; c.guard_l1 = guard_l1_3;
     p.nt = (int64_t)p.M * Cout * 4 >= conv_nt_bytes() ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
     int rc;
@@ -2305,42 +2210,41 @@ static int wgrad_launch(const WgradParams& g, const Conv3dParams& p, const uint1
     return NDET_OK;
 }
 
-static int wgrad_split_entry(const char* fn, const float* x_ndhwc, int D, int H, int W, int Cin, const int* kernel, const int* stride, const int* pad,
-                             const uint16_t* dy_planes, int Cout, int lrow, int splits, int max_order, const float* x_amax, const float* dy_amax, void* workspace,
-                             float* dw_rows, int keep_partials, void* stream) {
+extern "C" int ndet_wgrad_split(const float* x_ndhwc, int D, int H, int W, int Cin, const int* kernel, const int* stride, const int* pad,
+                                const uint16_t* dy_planes, int Cout, int lrow, int splits, int arith, const float* x_amax, const float* dy_amax,
+                                void* workspace, float* dw_rows, int keep_partials, void* stream) {
+    const char* fn = "ndet_wgrad_split";
     NDET_REQUIRE(x_ndhwc && kernel && stride && pad && dy_planes && dw_rows, NDET_E_INVALID, "%s: null pointer", fn);
     NDET_REQUIRE(D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && lrow > 0 && lrow % CBK == 0, NDET_E_INVALID, "%s: bad sizes", fn);
     NDET_REQUIRE(Cin % 64 == 0, NDET_E_UNSUPPORTED, "%s: Cin=%d must be a multiple of 64", fn, Cin);
-    NDET_REQUIRE(max_order == 0 || max_order == 1 || max_order == 2, NDET_E_INVALID, "%s: bad arithmetic", fn);
-    NDET_REQUIRE((max_order == 1) == (x_amax != nullptr && dy_amax != nullptr), NDET_E_INVALID, "%s: the fp16-pair arithmetic needs both amax slots (the others none)", fn);
+    NDET_REQUIRE(arith >= 0 && arith <= 2, NDET_E_INVALID, "%s: arith must be 0 (bf16x3), 1 (fp16 pair) or 2 (bf16)", fn);
+    NDET_REQUIRE(arith == 1 ? (x_amax && dy_amax) : (!x_amax && !dy_amax), NDET_E_INVALID, "%s: the fp16-pair arithmetic needs both amax slots (the others none)", fn);
     NDET_REQUIRE((((uintptr_t)x_ndhwc | (uintptr_t)dy_planes | (uintptr_t)dw_rows) & 15) == 0, NDET_E_UNSUPPORTED, "%s: pointers must be 16-byte aligned", fn);
+    Conv3dParams geo;
+    geo.D = D; geo.H = H; geo.W = W; geo.Cin = Cin;
+    const int rc0 = conv_geometry(geo, kernel, stride, pad, fn);
+    if (rc0 != NDET_OK) return rc0;
+    NDET_REQUIRE(geo.M <= lrow, NDET_E_INVALID, "%s: dy rows (%d) shorter than the output grid", fn, lrow);
     WgradParams g;
     g.x = x_ndhwc; g.D = D; g.H = H; g.W = W; g.Cin = Cin; g.x_amax = x_amax; g.dy_amax = dy_amax;
-    for (int a = 0; a < 3; ++a)
-        NDET_REQUIRE(kernel[a] >= 1 && kernel[a] <= 7 && stride[a] >= 1 && stride[a] <= 4 && pad[a] >= 0 && pad[a] < kernel[a], NDET_E_UNSUPPORTED,
-                     "%s: kernel/stride/pad out of range on axis %d", fn, a);
-    g.kh = kernel[1]; g.kw = kernel[2];
-    g.pd = pad[0]; g.ph = pad[1]; g.pw = pad[2]; g.sd = stride[0]; g.sh = stride[1]; g.sw = stride[2];
-    g.OD = (D + 2 * pad[0] - kernel[0]) / stride[0] + 1;
-    g.OH = (H + 2 * pad[1] - kernel[1]) / stride[1] + 1;
-    g.OW = (W + 2 * pad[2] - kernel[2]) / stride[2] + 1;
-    NDET_REQUIRE(g.OD > 0 && g.OH > 0 && g.OW > 0 && (int64_t)g.OD * g.OH * g.OW <= lrow && (int64_t)D * H * W * Cin < ((int64_t)1 << 40),
-                 NDET_E_INVALID, "%s: dy rows (%d) shorter than the output grid", fn, lrow);
-    g.L = g.OD * g.OH * g.OW;
+    g.kh = geo.kh; g.kw = geo.kw;
+    g.pd = geo.pd; g.ph = geo.ph; g.pw = geo.pw; g.sd = geo.sd; g.sh = geo.sh; g.sw = geo.sw;
+    g.OD = geo.OD; g.OH = geo.OH; g.OW = geo.OW;
+    g.L = geo.M;
     g.ksteps = lrow / CBK;
     const int taps = kernel[0] * kernel[1] * kernel[2];
     Conv3dParams p;
     p.in = nullptr; p.w = nullptr; p.out = dw_rows; p.scale = nullptr; p.shift = nullptr; p.res = nullptr; p.partial = (float*)workspace;
     p.D = p.H = p.W = 1; p.Cin = lrow; p.Cout = Cout; p.OD = p.OH = 1; p.OW = taps * Cin;
     p.kd = p.kh = p.kw = 1; p.sd = p.sh = p.sw = 1; p.pd = p.ph = p.pw = 0;
-    p.relu = 0; p.transposed = 0; p.M = taps * Cin; p.res_up2 = 0; p.RH = p.RW = 0; p.max_order = max_order;
+    p.relu = 0; p.transposed = 0; p.M = taps * Cin; p.res_up2 = 0; p.RH = p.RW = 0; p.max_order = max_order_of(arith);
     p.splits = splits < 1 ? 1 : splits;
     NDET_REQUIRE(p.splits <= g.ksteps, NDET_E_INVALID, "%s: splits=%d exceeds the %d K steps", fn, p.splits, g.ksteps);
     NDET_REQUIRE(p.splits == 1 || workspace != nullptr, NDET_E_INVALID, "%s: split-K needs a workspace", fn);
     g.xcd_order = (g_wgrad_xcd && p.splits >= 8 && p.splits % 8 == 0) ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
     const bool wide = Cout > 64, big = Cin % 128 == 0;
-    const int sch = max_order == 0 ? 2 : (max_order == 1 ? 1 : 0);
+    const int sch = arith;       // (= conv_scheme(p))
     int rc;
 #define NDET_WGRAD_TILE(BM, BN) (sch == 2 ? wgrad_launch<BM, BN, 2>(g, p, dy_planes, st) : (sch == 1 ? wgrad_launch<BM, BN, 1>(g, p, dy_planes, st) : wgrad_launch<BM, BN, 0>(g, p, dy_planes, st)))
     // 256 output channels per workgroup where the layer has them (fp16 pairs; the 3-plane arithmetic's LDS tiles would not leave room for two
@@ -2369,20 +2273,3 @@ static int wgrad_split_entry(const char* fn, const float* x_ndhwc, int D, int H,
     if (keep_partials && p.splits > 1) return NDET_OK;
     return conv_splitk_reduce_launch(p, st, fn);
 }
-
-extern "C" int ndet_wgrad_split(const float* x_ndhwc, int D, int H, int W, int Cin, const int* kernel, const int* stride, const int* pad,
-                                const uint16_t* dy_planes, int Cout, int lrow, int splits, int max_order, void* workspace, float* dw_rows,
-                                void* stream) {
-    NDET_REQUIRE(max_order == 0 || max_order == 2, NDET_E_INVALID, "ndet_wgrad_split: max_order 0 (bf16) or 2 (bf16x3); the fp16-pair form is ndet_wgrad_split_f16x2");
-    return wgrad_split_entry("ndet_wgrad_split", x_ndhwc, D, H, W, Cin, kernel, stride, pad, dy_planes, Cout, lrow, splits, max_order, nullptr, nullptr, workspace, dw_rows, 0, stream);
-}
-
-// The same implicit GEMM in the fp16-pair arithmetic: dy_planes from ndet_wgrad_dy_planes_f16x2 (two planes per K step, scaled by its slot), x split in
-// the kernel under the scale of x_amax, three products.
-extern "C" int ndet_wgrad_split_f16x2(const float* x_ndhwc, int D, int H, int W, int Cin, const int* kernel, const int* stride, const int* pad,
-                                      const uint16_t* dy_planes, int Cout, int lrow, int splits, const float* x_amax, const float* dy_amax, void* workspace,
-                                      float* dw_rows, int keep_partials, void* stream) {
-    return wgrad_split_entry("ndet_wgrad_split_f16x2", x_ndhwc, D, H, W, Cin, kernel, stride, pad, dy_planes, Cout, lrow, splits, 1, x_amax, dy_amax, workspace, dw_rows,
-                             keep_partials, stream);
-}
-

@@ -57,6 +57,24 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     # pitch smaller than a row
     assert lib.ndet_backproject_aggregate(fake, 2, 8, 4, 4, 128, 16, fake, 16, fake, None, fake, 1, fake, None) == -1
     assert lib.ndet_density_features(fake, 2, 62, 4, 4, 992, 248, fake, fake, 16, 16, 768, 256, 16, fake, 16, fake, fake, fake, None) == -2
+    # the convolution's argument block: each bad field is rejected before any HIP call (a valid block would launch)
+    def conv(**bad):
+        fields = dict(size=ctypes.sizeof(_lib.NdetConvArgs), in_=0x1000, w_planes=0x1000, out=0x1000, D=4, H=4, W=4, Cin=32, Cout=256, kernel=(1, 3, 3),
+                      stride=(1, 1, 1), pad=(0, 1, 1), tile=3256)
+        fields.update(bad)
+        return lib.ndet_conv_split(_lib.NdetConvArgs(**fields), None)
+    assert conv(size=ctypes.sizeof(_lib.NdetConvArgs) - 8) == -1
+    assert conv(in_=None) == -1
+    assert conv(tile=77) == -1
+    assert conv(arith=0, in_amax=0x1000) == -1
+    assert conv(arith=0, w_amax=0x1000) == -1
+    proj = dict(map_w=0x1000, map_b=0x1000, map_out=0x1000)
+    assert conv(tile=128, **proj) == -2
+    assert conv(Cout=128, **proj) == -2
+    assert conv(keep_partials=1, relu=1) == -1
+    i3 = lambda *v: (ctypes.c_int * 3)(*v)
+    assert lib.ndet_conv_chain(fake, fake, 1, 4, 4, 32, 96, i3(1, 3, 3), i3(1, 1, 1), i3(0, 1, 1), None, None, fake, 64, None, None, None, 1, fake,
+                               0, None, 1.0, 1.0, None, 0.0, 0.0, 0.0, None, None) == -2
     with pytest.raises(AssertionError):
         _lib.check(-1, "x")
     with pytest.raises(ValueError):

@@ -24,12 +24,22 @@ if os.environ.get("F16_MIN_KSTEPS"):
     from nerfdet_amd import conv3d
     conv3d.F16_MIN_KSTEPS = int(os.environ["F16_MIN_KSTEPS"])
 if os.environ.get("TIMING_NO_AMAX_OUT"):      # timing probe only (results are garbage): no launch commits its maximum, readers find zeroed slots
-    from ctypes import c_void_p
+    import re
     from nerfdet_amd import _lib
     _l = _lib.load()
-    _f, _g = _l.ndet_conv_ndhwc_guarded, _l.ndet_conv_chain_guarded
-    _l.ndet_conv_ndhwc_guarded = lambda *a: _f(*a[:22], c_void_p(0), *a[23:])
-    _l.ndet_conv_chain_guarded = lambda *a: _g(*a[:23], c_void_p(0), *a[24:])
+    _f, _g = _l.ndet_conv_split, _l.ndet_conv_chain
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "nerfdet_hip.h")).read()
+    _k = [p.split()[-1] for p in re.search(r"int ndet_conv_chain\((.*?)\);", hdr, re.S).group(1).split(",")].index("out_amax")
+
+    def _conv(a, st):
+        a.out_amax = None
+        return _f(a, st)
+
+    def _chain(*a):
+        a = list(a)
+        a[_k] = None
+        return _g(*a)
+    _l.ndet_conv_split, _l.ndet_conv_chain = _conv, _chain
 dev = torch.device("cuda")
 det = bench.build_model(w).to(dev)
 batch = bench.to_device(bench.synth_batch(w, 0), dev)

@@ -14,15 +14,16 @@ out = torch.empty(60, 80, 50, 256, device=dev)
 planes = C3.split_planes(pk)
 ws = torch.zeros(128, dtype=torch.int64, device=dev)
 lib = _lib.load()
-i3 = lambda *v: (ctypes.c_int * 3)(*v)
-P = lambda t: c_void_p(t.data_ptr())
 st = c_void_p(torch.cuda.current_stream().cuda_stream)
 TILE = int(sys.argv[1]) if len(sys.argv) > 1 else 128
+args = _lib.NdetConvArgs(size=ctypes.sizeof(_lib.NdetConvArgs), in_=x.data_ptr(), w_planes=planes.data_ptr(), out=out.data_ptr(), D=60, H=80, W=50,
+                         Cin=256, Cout=256, kernel=(3, 3, 3), stride=(1, 1, 1), pad=(1, 1, 1), scale=pk["scale"].data_ptr(), shift=pk["shift"].data_ptr(),
+                         relu=1, splits=1, tile=TILE, arith=0, workspace=ws.data_ptr())
 ts = []
 for i in range(6):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    rc = lib.ndet_conv_ndhwc_split(P(x), P(planes), P(out), 60, 80, 50, 256, 256, i3(3,3,3), i3(1,1,1), i3(1,1,1), 0, P(pk["scale"]), P(pk["shift"]), None, 0, 1, 1, TILE, P(ws), st)
+    rc = lib.ndet_conv_split(args, st)
     e1.record(); torch.cuda.synchronize(); assert rc == 0
     ts.append(e0.elapsed_time(e1))
 print("TILE", TILE, "ms", sorted(ts)[2], "TF", 2*240000*256*6912/sorted(ts)[2]/1e9, flush=True)
