@@ -98,6 +98,75 @@ int ndet_density_features_packed(const float* mapped_nhwc, int n_views, int cm, 
                                  const float* points, int N, const float* projection,
                                  const float* rgb_projection, float* global_feat, void* stream);
 
+/* ---- depth-gated backprojection (RGB-D scenes): nerfdet.py:404-411 ----
+ * With a per-view depth map D, the reference's backproject() counts view v as seeing voxel n only where the ordinary test holds
+ * (pixel in bounds after round(), z > 0) AND  D'[v,y,x] - voxel_size[2] < z < D'[v,y,x] + voxel_size[2]  (both strict), with
+ * z = the third row of P.[p;1] (the `d` of every projection here) and D' = F.interpolate(D, (h, w), bilinear, align_corners=False)
+ * resized to the map the projection indexes.  The arithmetic follows PyTorch's promotion: dtype 0 (float32 D): D' - band in
+ * float32 with band rounded to float32; dtype 1 (float64 D): in float64, z widened exactly.  Everything downstream of the
+ * validity (counts, means, the bias fill of unseen views, variance, gradients) is the ungated statement over the gated mask.
+ *
+ * NdetDepthGate, one block per call (same style as NdetConvArgs):
+ *   size            sizeof(NdetDepthGate); any other value is rejected (NDET_E_INVALID).
+ *   dtype           0 = float32, 1 = float64 (element type of depth_f / depth_r).
+ *   n_views         views of both maps; must equal the call's n_views.
+ *   depth_f, h, w   D resized to the projection's map (the feature map, or the image for ndet_backproject_gated on images);
+ *                   element (v,y,x) at v*f_view_pitch + y*f_row_pitch + x (elements); h, w must equal the call's.
+ *   depth_r, H, W   D resized to the full-resolution image (the stride-1 projection of the density features); read by
+ *                   ndet_density_features*_gated only, NULL / 0 elsewhere.
+ *   band            voxel_size[2]: finite, > 0.
+ */
+typedef struct NdetDepthGate {
+    int32_t size;
+    int32_t dtype;
+    int32_t n_views;
+    int32_t h, w;
+    int32_t H, W;
+    const void* depth_f;
+    int64_t f_view_pitch, f_row_pitch;
+    const void* depth_r;
+    int64_t r_view_pitch, r_row_pitch;
+    double band;
+} NdetDepthGate;
+
+/* D' of nerfdet.py:405 for one scene in one launch: depth (n_views, Hd, Wd), element (v,y,x) at v*sv + y*sy + x, of `dtype`
+ * (0 float32, 1 float64) -> out_f (n_views, h, w) and, when out_r != NULL, out_r (n_views, H, W), both contiguous, same dtype.
+ * F.interpolate(mode="bilinear", align_corners=False) in the map's dtype: src = max((dst + 0.5) * (in / out) - 0.5, 0),
+ * i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1, out = ly0 (lx0 v00 + lx1 v01) + ly1 (lx0 v10 + lx1 v11) for an
+ * output with H + W > 128, ((ly0 lx0) v00 + (ly0 lx1) v01 + (ly1 lx0) v10) + (ly1 lx1) v11 (left to right) for a smaller one -- the two
+ * paths of PyTorch's CPU kernel, bit-equal to it at integer ratios; at other ratios within a few ulp. */
+int ndet_depth_resize(const void* depth, int dtype, int n_views, int Hd, int Wd, int64_t sv, int64_t sy,
+                      void* out_f, int h, int w, void* out_r, int H, int W, void* stream);
+
+/* ndet_backproject with the depth gate of nerfdet.py:404-411 (gate->depth_f at the features' h x w). */
+int ndet_backproject_gated(const float* features, int n_views, int C, int h, int w,
+                           int64_t sv, int64_t sc, int64_t sy, int64_t sx,
+                           const float* points, int N, const float* projection,
+                           float* volume, uint8_t* valid, const NdetDepthGate* gate, void* stream);
+
+/* ndet_backproject_aggregate with the depth gate of nerfdet.py:404-411 (gate->depth_f at the features' h x w): gated-out views
+ * are dropped before the row gather. */
+int ndet_backproject_aggregate_gated(const float* features_nhwc, int n_views, int C, int h, int w,
+                                     int64_t view_pitch, int64_t row_pitch,
+                                     const float* points, int N, const float* projection,
+                                     const float* alpha, float* out, int out_layout, int64_t* count,
+                                     const NdetDepthGate* gate, void* stream);
+
+/* ndet_density_features with the depth gate of nerfdet.py:404-411 on both projections: the stride-4 one against gate->depth_f
+ * (h x w), the stride-1 one against gate->depth_r (H x W), as the reference's two backproject() calls (nerfdet.py:164-169, 204-210). */
+int ndet_density_features_gated(const float* mapped_nhwc, int n_views, int cm, int h, int w,
+                                int64_t mview_pitch, int64_t mrow_pitch, const float* bias,
+                                const float* rgb, int H, int W, int64_t rsv, int64_t rsc, int64_t rsy,
+                                const float* points, int N, const float* projection, const float* rgb_projection,
+                                float* global_feat, const NdetDepthGate* gate, void* stream);
+
+/* ndet_density_features_packed with the depth gate of nerfdet.py:404-411, maps as in ndet_density_features_gated. */
+int ndet_density_features_packed_gated(const float* mapped_nhwc, int n_views, int cm, int h, int w,
+                                       int64_t mview_pitch, int64_t mrow_pitch, const float* bias,
+                                       const float* rgb, int H, int W, int64_t rsv, int64_t rsc, int64_t rsy,
+                                       const float* points, int N, const float* projection,
+                                       const float* rgb_projection, float* global_feat, const NdetDepthGate* gate, void* stream);
+
 /* A6 (gating only, unfused form). volume = (1-exp(-density)) * mean, 0 where count==0; nerfdet.py:257-261.
  * mean/out in `layout` with C channels. */
 int ndet_alpha_gate(const float* mean, const float* density, const int64_t* count, float* out,
@@ -552,6 +621,18 @@ int ndet_backproject_aggregate_bwd(const float* grad_mean, int grad_layout, int 
 int ndet_density_features_bwd(const float* grad_global_feat, const float* mapped_nhwc, int n_views, int cm, int h, int w,
                               int64_t mview_pitch, int64_t mrow_pitch, const float* bias, const float* points, int N,
                               const float* projection, float* grad_mapped_nhwc, float* grad_bias, void* stream);
+
+/* ndet_backproject_aggregate_bwd over the depth-gated validity of nerfdet.py:404-411 (gate->depth_f at h x w). */
+int ndet_backproject_aggregate_bwd_gated(const float* grad_mean, int grad_layout, int n_views, int C, int h, int w,
+                                         int64_t view_pitch, int64_t row_pitch, const float* points, int N,
+                                         const float* projection, float* grad_features_nhwc, const NdetDepthGate* gate,
+                                         void* stream);
+
+/* ndet_density_features_bwd over the depth-gated stride-4 validity of nerfdet.py:404-411 (gate->depth_f at h x w). */
+int ndet_density_features_bwd_gated(const float* grad_global_feat, const float* mapped_nhwc, int n_views, int cm, int h, int w,
+                                    int64_t mview_pitch, int64_t mrow_pitch, const float* bias, const float* points, int N,
+                                    const float* projection, float* grad_mapped_nhwc, float* grad_bias,
+                                    const NdetDepthGate* gate, void* stream);
 
 /* d(mapped features) of ndet_ray_view_stats: F.grid_sample backward (projection.py:127) through the masked statistics of
  * render_ray.py:83-88.  Sample points and images carry no gradient. */

@@ -27,6 +27,14 @@ class NdetConvArgs(ctypes.Structure):    # ndet_conv_split's block: include/nerf
                 + [(f, _P) for f in ("map_w", "map_b", "map_out")])
 
 
+class NdetDepthGate(ctypes.Structure):   # the depth gate of the *_gated entry points: include/nerfdet_hip.h::NdetDepthGate, size = sizeof(NdetDepthGate)
+    _fields_ = [(f, ctypes.c_int32) for f in ("size", "dtype", "n_views", "h", "w", "H", "W")] + [
+        ("depth_f", _P), ("f_view_pitch", c_int64), ("f_row_pitch", c_int64),
+        ("depth_r", _P), ("r_view_pitch", c_int64), ("r_row_pitch", c_int64), ("band", ctypes.c_double)]
+
+
+_G = ctypes.POINTER(NdetDepthGate)
+
 # name -> argtypes; kept in one table so tests can check the .so exports exactly this surface
 SIGNATURES = {
     "ndet_version": ([], c_int),
@@ -40,6 +48,15 @@ SIGNATURES = {
                                c_int64, _P, c_int, _P, _P, _P, _P], c_int),
     "ndet_density_features_packed": ([_P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, _P, c_int, c_int, c_int64, c_int64,
                                       c_int64, _P, c_int, _P, _P, _P, _P], c_int),
+    "ndet_depth_resize": ([_P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, c_int, c_int, _P, c_int, c_int, _P], c_int),
+    "ndet_backproject_gated": ([_P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, _P, c_int, _P, _P, _P, _G, _P], c_int),
+    "ndet_backproject_aggregate_gated": ([_P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, c_int, _P, _P, _P, c_int, _P, _G, _P], c_int),
+    "ndet_density_features_gated": ([_P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, _P, c_int, c_int, c_int64, c_int64,
+                                     c_int64, _P, c_int, _P, _P, _P, _G, _P], c_int),
+    "ndet_density_features_packed_gated": ([_P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, _P, c_int, c_int, c_int64, c_int64,
+                                            c_int64, _P, c_int, _P, _P, _P, _G, _P], c_int),
+    "ndet_backproject_aggregate_bwd_gated": ([_P, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, c_int, _P, _P, _G, _P], c_int),
+    "ndet_density_features_bwd_gated": ([_P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, _P, c_int, _P, _P, _P, _G, _P], c_int),
     "ndet_alpha_gate": ([_P, _P, _P, _P, c_int, c_int, c_int, _P], c_int),
     "ndet_sigma_to_alpha": ([_P, _P, c_int, _P], c_int),
     "ndet_posenc_concat": ([_P, _P, c_int, c_int, c_int, _P, _P], c_int),

@@ -67,13 +67,15 @@ def _grad_result(buf):
 
 
 class BackprojectMean(torch.autograd.Function):
-    """features (n_v,C,h,w) -> (mean (C,X,Y,Z), count (1,X,Y,Z)); nerfdet.py:164-176."""
+    """features (n_v,C,h,w) -> (mean (C,X,Y,Z), count (1,X,Y,Z)); nerfdet.py:164-176.  ``depth_gate``: None or an ops.DepthGate
+    (nerfdet.py:404-411), applied in the forward and the backward alike."""
 
     @staticmethod
-    def forward(ctx, features, points, projection, channels_last_out):
+    def forward(ctx, features, points, projection, channels_last_out, depth_gate=None):
         f = ops.to_channels_last(features.detach())
-        out, cnt = ops.backproject_aggregate(f, points, projection, None, channels_last_out)
+        out, cnt = ops.backproject_aggregate(f, points, projection, None, channels_last_out, depth_gate=depth_gate)
         ctx.save_for_backward(points, projection)
+        ctx.depth_gate = depth_gate
         ctx.fshape, ctx.fstrides = tuple(f.shape), (f.stride(0), f.stride(2))
         ctx.mark_non_differentiable(cnt)
         return out, cnt
@@ -92,19 +94,27 @@ class BackprojectMean(torch.autograd.Function):
         dfeat = _grad_buffer((n_v, h, w, c), g.device)
         pts = points.float().contiguous()
         pj = projection.float().contiguous()
-        check(_lib.load().ndet_backproject_aggregate_bwd(_ptr(g), layout, n_v, c, h, w, dfeat.stride(0), dfeat.stride(1), _ptr(pts), n,
-                                                         _ptr(pj), _ptr(dfeat), _stream(g)), "backproject_aggregate_bwd")
-        return _grad_result(dfeat).permute(0, 3, 1, 2), None, None, None
+        lib = _lib.load()
+        if ctx.depth_gate is None:
+            check(lib.ndet_backproject_aggregate_bwd(_ptr(g), layout, n_v, c, h, w, dfeat.stride(0), dfeat.stride(1), _ptr(pts), n,
+                                                     _ptr(pj), _ptr(dfeat), _stream(g)), "backproject_aggregate_bwd")
+        else:
+            check(lib.ndet_backproject_aggregate_bwd_gated(_ptr(g), layout, n_v, c, h, w, dfeat.stride(0), dfeat.stride(1), _ptr(pts), n,
+                                                           _ptr(pj), _ptr(dfeat), ops._gate_arg(ctx.depth_gate, n_v, (h, w)), _stream(g)),
+                  "backproject_aggregate_bwd_gated")
+        return _grad_result(dfeat).permute(0, 3, 1, 2), None, None, None, None
 
 
 class DensityFeatures(torch.autograd.Function):
-    """(mapped (n_v,cm,h,w), bias (cm)) -> global_feat (N, 2*(3+cm)); nerfdet.py:234-253."""
+    """(mapped (n_v,cm,h,w), bias (cm)) -> global_feat (N, 2*(3+cm)); nerfdet.py:234-253.  ``depth_gate``: None or an ops.DepthGate
+    (nerfdet.py:404-411) with maps at the features' and the images' sizes."""
 
     @staticmethod
-    def forward(ctx, mapped, bias, denorm_images, points, projection, rgb_projection):
+    def forward(ctx, mapped, bias, denorm_images, points, projection, rgb_projection, depth_gate=None):
         m = _dense_nhwc(mapped.detach())
-        out = ops.density_features(m, bias.detach(), denorm_images, points, projection, rgb_projection)
+        out = ops.density_features(m, bias.detach(), denorm_images, points, projection, rgb_projection, depth_gate=depth_gate)
         ctx.save_for_backward(m, bias.detach(), points, projection)
+        ctx.depth_gate = depth_gate
         return out
 
     @staticmethod
@@ -116,10 +126,14 @@ class DensityFeatures(torch.autograd.Function):
         dm = _grad_buffer((n_v, h, w, cm), g.device)
         assert (m.stride(0), m.stride(2)) == (dm.stride(0), dm.stride(1)), "saved input and gradient buffer must share their pitches"
         db = _grad_buffer((cm,), g.device)
-        check(_lib.load().ndet_density_features_bwd(_ptr(g), _ptr(m), n_v, cm, h, w, m.stride(0), m.stride(2), _ptr(bias.float().contiguous()),
-                                                    _ptr(points.float().contiguous()), n, _ptr(projection.float().contiguous()), _ptr(dm),
-                                                    _ptr(db), _stream(g)), "density_features_bwd")
-        return _grad_result(dm).permute(0, 3, 1, 2), _grad_result(db), None, None, None, None
+        args = (_ptr(g), _ptr(m), n_v, cm, h, w, m.stride(0), m.stride(2), _ptr(bias.float().contiguous()), _ptr(points.float().contiguous()), n,
+                _ptr(projection.float().contiguous()), _ptr(dm), _ptr(db))
+        lib = _lib.load()
+        if ctx.depth_gate is None:
+            check(lib.ndet_density_features_bwd(*args, _stream(g)), "density_features_bwd")
+        else:
+            check(lib.ndet_density_features_bwd_gated(*args, ops._gate_arg(ctx.depth_gate, n_v, (h, w)), _stream(g)), "density_features_bwd_gated")
+        return _grad_result(dm).permute(0, 3, 1, 2), _grad_result(db), None, None, None, None, None
 
 
 class RayViewStats(torch.autograd.Function):

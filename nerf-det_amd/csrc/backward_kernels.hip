@@ -13,10 +13,11 @@
 //   => d feat[v,y,x,:] += g[n,:] / (cnt_n + 1e-8)      for every valid (n, v);   nothing flows where cnt == 0
 // Same wave-per-voxel / lanes-over-channels / ballot walk as the forward kernel.
 // ------------------------------------------------------------------------------------------------
-template <int LAYOUT>
+template <int LAYOUT, bool DG>
 __global__ __launch_bounds__(256) void k_backproject_aggregate_bwd(const float* __restrict__ g, int n_views, int C, int h, int w,
                                                                    int64_t view_pitch, int row_pitch, const float* __restrict__ points, int N,
-                                                                   const float* __restrict__ proj, float* __restrict__ dfeat, int n_tiles, int det) {
+                                                                   const float* __restrict__ proj, float* __restrict__ dfeat, int n_tiles, int det,
+                                                                   NdetGateMap dgate) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tile = ndet_xcd_remap(blockIdx.x, n_tiles);
     for (int j = 0; j < BVOX_PER_TILE / 4; ++j) {
@@ -28,7 +29,9 @@ __global__ __launch_bounds__(256) void k_backproject_aggregate_bwd(const float* 
         for (int r0 = 0; r0 < n_views; r0 += 64) {
             const int v = r0 + lane;
             int xi, yi;
-            const bool ok = v < n_views && ndet_project(proj + v * 12, px, py, pz, w, h, xi, yi);
+            float z;
+            bool ok = v < n_views && ndet_project_z(proj + v * 12, px, py, pz, w, h, xi, yi, z);
+            if (DG) ok = ok && ndet_depth_band(dgate, v, xi, yi, z);     // nerfdet.py:404-411
             cnt += __popcll(__ballot(ok));
         }
         if (cnt == 0) continue;
@@ -43,7 +46,9 @@ __global__ __launch_bounds__(256) void k_backproject_aggregate_bwd(const float* 
         for (int r0 = 0; r0 < n_views; r0 += 64) {
             const int v = r0 + lane;
             int xi = 0, yi = 0;
-            const bool ok = v < n_views && ndet_project(proj + v * 12, px, py, pz, w, h, xi, yi);
+            float z;
+            bool ok = v < n_views && ndet_project_z(proj + v * 12, px, py, pz, w, h, xi, yi, z);
+            if (DG) ok = ok && ndet_depth_band(dgate, v, xi, yi, z);
             const int off = yi * row_pitch + xi * C;
             unsigned long long m = __ballot(ok);
             while (m) {
@@ -61,23 +66,47 @@ __global__ __launch_bounds__(256) void k_backproject_aggregate_bwd(const float* 
     }
 }
 
-extern "C" int ndet_backproject_aggregate_bwd(const float* grad_mean, int grad_layout, int n_views, int C, int h, int w,
-                                              int64_t view_pitch, int64_t row_pitch, const float* points, int N, const float* projection,
-                                              float* grad_features_nhwc, void* stream) {
-    const char* fn = "ndet_backproject_aggregate_bwd";
+static int backproject_aggregate_bwd_impl(const char* fn, const float* grad_mean, int grad_layout, int n_views, int C, int h, int w,
+                                          int64_t view_pitch, int64_t row_pitch, const float* points, int N, const float* projection,
+                                          float* grad_features_nhwc, const NdetDepthGate* dgate, void* stream) {
     NDET_REQUIRE(grad_mean && points && projection && grad_features_nhwc, NDET_E_INVALID, "%s: null pointer", fn);
     NDET_REQUIRE(n_views > 0 && C > 0 && h > 0 && w > 0 && N > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
     NDET_REQUIRE(grad_layout == NDET_LAYOUT_CN || grad_layout == NDET_LAYOUT_NC, NDET_E_INVALID, "%s: bad layout", fn);
     NDET_REQUIRE((int64_t)h * row_pitch < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: one view exceeds 2^31 floats", fn);
+    NdetGateMap gm = {};
+    if (dgate) {
+        const int rc = ndet_gate_prepare(dgate, fn, n_views, h, w, 0, 0, false, &gm, nullptr);
+        if (rc != NDET_OK) return rc;
+    }
     const int n_tiles = (N + BVOX_PER_TILE - 1) / BVOX_PER_TILE;
-    if (grad_layout == NDET_LAYOUT_NC)
-        hipLaunchKernelGGL(k_backproject_aggregate_bwd<NDET_LAYOUT_NC>, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, grad_mean, n_views, C, h, w,
-                           view_pitch, (int)row_pitch, points, N, projection, grad_features_nhwc, n_tiles, g_ndet_deterministic_scatter);
-    else
-        hipLaunchKernelGGL(k_backproject_aggregate_bwd<NDET_LAYOUT_CN>, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, grad_mean, n_views, C, h, w,
-                           view_pitch, (int)row_pitch, points, N, projection, grad_features_nhwc, n_tiles, g_ndet_deterministic_scatter);
+#define K1B_LAUNCH(L, DG)                                                                                                                          \
+    hipLaunchKernelGGL((k_backproject_aggregate_bwd<L, DG>), dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, grad_mean, n_views, C, h, w,      \
+                       view_pitch, (int)row_pitch, points, N, projection, grad_features_nhwc, n_tiles, g_ndet_deterministic_scatter, gm)
+    if (dgate) {
+        if (grad_layout == NDET_LAYOUT_NC) K1B_LAUNCH(NDET_LAYOUT_NC, true);
+        else K1B_LAUNCH(NDET_LAYOUT_CN, true);
+    } else {
+        if (grad_layout == NDET_LAYOUT_NC) K1B_LAUNCH(NDET_LAYOUT_NC, false);
+        else K1B_LAUNCH(NDET_LAYOUT_CN, false);
+    }
+#undef K1B_LAUNCH
     NDET_CHECK_LAUNCH(fn);
     return NDET_OK;
+}
+
+extern "C" int ndet_backproject_aggregate_bwd(const float* grad_mean, int grad_layout, int n_views, int C, int h, int w,
+                                              int64_t view_pitch, int64_t row_pitch, const float* points, int N, const float* projection,
+                                              float* grad_features_nhwc, void* stream) {
+    return backproject_aggregate_bwd_impl("ndet_backproject_aggregate_bwd", grad_mean, grad_layout, n_views, C, h, w, view_pitch, row_pitch, points, N,
+                                          projection, grad_features_nhwc, nullptr, stream);
+}
+
+extern "C" int ndet_backproject_aggregate_bwd_gated(const float* grad_mean, int grad_layout, int n_views, int C, int h, int w,
+                                                    int64_t view_pitch, int64_t row_pitch, const float* points, int N, const float* projection,
+                                                    float* grad_features_nhwc, const NdetDepthGate* gate, void* stream) {
+    NDET_REQUIRE(gate, NDET_E_INVALID, "ndet_backproject_aggregate_bwd_gated: null depth gate");
+    return backproject_aggregate_bwd_impl("ndet_backproject_aggregate_bwd_gated", grad_mean, grad_layout, n_views, C, h, w, view_pitch, row_pitch,
+                                          points, N, projection, grad_features_nhwc, gate, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -87,10 +116,12 @@ extern "C" int ndet_backproject_aggregate_bwd(const float* grad_mean, int grad_l
 //   dL/dval_v = gm/den + (-gc*cov/den) * ( 2 (val_v - mean) - 2 (S - n_v*mean)/den )        (cov term 0 when cnt == 0)
 // RGB channels carry no gradient (images are inputs).  Lanes over the cm mapped channels.
 // ------------------------------------------------------------------------------------------------
+template <bool DG>
 __global__ __launch_bounds__(256) void k_density_features_bwd(const float* __restrict__ gout, const float* __restrict__ mapped, int n_views, int cm,
                                                               int h, int w, int64_t mview_pitch, int mrow_pitch, const float* __restrict__ bias,
                                                               const float* __restrict__ points, int N, const float* __restrict__ proj,
-                                                              float* __restrict__ dmapped, float* __restrict__ dbias, int n_tiles, int det) {
+                                                              float* __restrict__ dmapped, float* __restrict__ dbias, int n_tiles, int det,
+                                                              NdetGateMap dgate) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tile = ndet_xcd_remap(blockIdx.x, n_tiles);
     const int F = 2 * (3 + cm);
@@ -111,7 +142,9 @@ __global__ __launch_bounds__(256) void k_density_features_bwd(const float* __res
             for (int r0 = 0; r0 < n_views; r0 += 64) {
                 const int v = r0 + lane;
                 int xi = 0, yi = 0;
-                const bool ok = v < n_views && ndet_project(proj + v * 12, px, py, pz, w, h, xi, yi);
+                float z;
+                bool ok = v < n_views && ndet_project_z(proj + v * 12, px, py, pz, w, h, xi, yi, z);
+                if (DG) ok = ok && ndet_depth_band(dgate, v, xi, yi, z);     // nerfdet.py:404-411
                 const int off = yi * mrow_pitch + xi * cm;
                 unsigned long long m = __ballot(ok);
                 c_here += __popcll(m);
@@ -149,18 +182,44 @@ __global__ __launch_bounds__(256) void k_density_features_bwd(const float* __res
     if (active && dbias_acc != 0.0f) ndet_scatter_add(dbias, lane, dbias_acc, det);
 }
 
-extern "C" int ndet_density_features_bwd(const float* grad_global_feat, const float* mapped_nhwc, int n_views, int cm, int h, int w,
-                                         int64_t mview_pitch, int64_t mrow_pitch, const float* bias, const float* points, int N,
-                                         const float* projection, float* grad_mapped_nhwc, float* grad_bias, void* stream) {
-    const char* fn = "ndet_density_features_bwd";
+static int density_features_bwd_impl(const char* fn, const float* grad_global_feat, const float* mapped_nhwc, int n_views, int cm, int h, int w,
+                                     int64_t mview_pitch, int64_t mrow_pitch, const float* bias, const float* points, int N,
+                                     const float* projection, float* grad_mapped_nhwc, float* grad_bias, const NdetDepthGate* dgate, void* stream) {
     NDET_REQUIRE(grad_global_feat && mapped_nhwc && bias && points && projection && grad_mapped_nhwc && grad_bias, NDET_E_INVALID, "%s: null pointer", fn);
     NDET_REQUIRE(n_views > 0 && cm > 0 && cm <= 61 && h > 0 && w > 0 && N > 0, NDET_E_INVALID, "%s: bad sizes", fn);
     NDET_REQUIRE((int64_t)h * mrow_pitch < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: one view exceeds 2^31 floats", fn);
+    NdetGateMap gm = {};
+    if (dgate) {
+        const int rc = ndet_gate_prepare(dgate, fn, n_views, h, w, 0, 0, false, &gm, nullptr);
+        if (rc != NDET_OK) return rc;
+    }
     const int n_tiles = (N + BVOX_PER_TILE - 1) / BVOX_PER_TILE;
-    hipLaunchKernelGGL(k_density_features_bwd, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, grad_global_feat, mapped_nhwc, n_views, cm, h, w,
-                       mview_pitch, (int)mrow_pitch, bias, points, N, projection, grad_mapped_nhwc, grad_bias, n_tiles, g_ndet_deterministic_scatter);
+    if (dgate)
+        hipLaunchKernelGGL(k_density_features_bwd<true>, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, grad_global_feat, mapped_nhwc, n_views, cm, h,
+                           w, mview_pitch, (int)mrow_pitch, bias, points, N, projection, grad_mapped_nhwc, grad_bias, n_tiles,
+                           g_ndet_deterministic_scatter, gm);
+    else
+        hipLaunchKernelGGL(k_density_features_bwd<false>, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, grad_global_feat, mapped_nhwc, n_views, cm, h,
+                           w, mview_pitch, (int)mrow_pitch, bias, points, N, projection, grad_mapped_nhwc, grad_bias, n_tiles,
+                           g_ndet_deterministic_scatter, gm);
     NDET_CHECK_LAUNCH(fn);
     return NDET_OK;
+}
+
+extern "C" int ndet_density_features_bwd(const float* grad_global_feat, const float* mapped_nhwc, int n_views, int cm, int h, int w,
+                                         int64_t mview_pitch, int64_t mrow_pitch, const float* bias, const float* points, int N,
+                                         const float* projection, float* grad_mapped_nhwc, float* grad_bias, void* stream) {
+    return density_features_bwd_impl("ndet_density_features_bwd", grad_global_feat, mapped_nhwc, n_views, cm, h, w, mview_pitch, mrow_pitch, bias,
+                                     points, N, projection, grad_mapped_nhwc, grad_bias, nullptr, stream);
+}
+
+extern "C" int ndet_density_features_bwd_gated(const float* grad_global_feat, const float* mapped_nhwc, int n_views, int cm, int h, int w,
+                                               int64_t mview_pitch, int64_t mrow_pitch, const float* bias, const float* points, int N,
+                                               const float* projection, float* grad_mapped_nhwc, float* grad_bias, const NdetDepthGate* gate,
+                                               void* stream) {
+    NDET_REQUIRE(gate, NDET_E_INVALID, "ndet_density_features_bwd_gated: null depth gate");
+    return density_features_bwd_impl("ndet_density_features_bwd_gated", grad_global_feat, mapped_nhwc, n_views, cm, h, w, mview_pitch, mrow_pitch,
+                                     bias, points, N, projection, grad_mapped_nhwc, grad_bias, gate, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -21,13 +21,13 @@
 // (3.6 waves per SIMD, all resident at once).  The groups share the pivot (the fill value: the Linear's bias / 0), so their partial
 // sums add; they meet in LDS.  With pivot = fill the views that do not see the voxel drop out of the shifted sums:
 //     sum_all (v - mean)^2 = sum_seen (v - fill)^2 - 2 (mean - fill) sum_seen (v - fill) + n_views (mean - fill)^2.
-template <int DUMMY>
+template <int DUMMY, bool DG>
 __global__ __launch_bounds__(256) void k_density_features_packed(const float* __restrict__ mapped, int n_views, int cm, int h, int w,
                                                                  int mview_pitch, int mrow_pitch, const float* __restrict__ bias,
                                                                  const float* __restrict__ rgb, int H, int W, int rsv, int rsc, int rsy,
                                                                  const float* __restrict__ points, int N, const float* __restrict__ proj,
                                                                  const float* __restrict__ rgb_proj, float* __restrict__ out, int n_blocks,
-                                                                 int nvp) {
+                                                                 int nvp, NdetGateMap gf, NdetGateMap gr) {
     extern __shared__ int2 s_off[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lps = (cm >> 2) + 1;
@@ -53,8 +53,13 @@ __global__ __launch_bounds__(256) void k_density_features_packed(const float* __
                 bool okf = false, okr = false;
                 if (v < n_views) {
                     int xf, yf, xr, yr;
-                    okf = ndet_project(proj + v * 12, px, py, pz, w, h, xf, yf);
-                    okr = ndet_project(rgb_proj + v * 12, px, py, pz, W, H, xr, yr);
+                    float zf, zr;
+                    okf = ndet_project_z(proj + v * 12, px, py, pz, w, h, xf, yf, zf);
+                    okr = ndet_project_z(rgb_proj + v * 12, px, py, pz, W, H, xr, yr, zr);
+                    if (DG) {   // depth gate of both backproject() calls (nerfdet.py:404-411)
+                        okf = okf && ndet_depth_band(gf, v, xf, yf, zf);
+                        okr = okr && ndet_depth_band(gr, v, xr, yr, zr);
+                    }
                     rec[v] = make_int2(v * mview_pitch + yf * mrow_pitch + xf * cm, v * rsv + yr * rsy + xr);
                 }
                 mf[r] = __ballot(okf);
@@ -156,11 +161,10 @@ __global__ __launch_bounds__(256) void k_density_features_packed(const float* __
     if (!is_rgb) *reinterpret_cast<float2*>(row + 6) = make_float2(mean.w, cov.w);
 }
 
-extern "C" int ndet_density_features_packed(const float* mapped_nhwc, int n_views, int cm, int h, int w, int64_t mview_pitch,
-                                            int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv,
-                                            int64_t rsc, int64_t rsy, const float* points, int N, const float* projection,
-                                            const float* rgb_projection, float* global_feat, void* stream) {
-    const char* fn = "ndet_density_features_packed";
+static int density_features_packed_impl(const char* fn, const float* mapped_nhwc, int n_views, int cm, int h, int w, int64_t mview_pitch,
+                                        int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv,
+                                        int64_t rsc, int64_t rsy, const float* points, int N, const float* projection,
+                                        const float* rgb_projection, float* global_feat, const NdetDepthGate* dgate, void* stream) {
     NDET_REQUIRE(mapped_nhwc && bias && rgb && points && projection && rgb_projection && global_feat, NDET_E_INVALID, "%s: null pointer", fn);
     NDET_REQUIRE(n_views > 0 && cm > 0 && h > 0 && w > 0 && H > 0 && W > 0 && N > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
     NDET_REQUIRE(cm % 4 == 0 && cm <= 128, NDET_E_UNSUPPORTED, "%s: cm=%d must be a multiple of 4, at most 128 (use ndet_density_features)", fn, cm);
@@ -176,9 +180,36 @@ extern "C" int ndet_density_features_packed(const float* mapped_nhwc, int n_view
     const int lds = 4 * nvp * (int)sizeof(int2) + 4 * 64 * 3 * (int)sizeof(float4);
     const int64_t blocks = ((int64_t)N + 3) / 4;               // one voxel per wavefront
     NDET_REQUIRE(blocks < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
-    hipLaunchKernelGGL(k_density_features_packed<0>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, mapped_nhwc, n_views, cm, h, w,
-                       (int)mview_pitch, (int)mrow_pitch, bias, rgb, H, W, (int)rsv, (int)rsc, (int)rsy, points, N, projection, rgb_projection,
-                       global_feat, (int)blocks, nvp);
+    NdetGateMap gf = {}, gr = {};
+    if (dgate) {
+        const int rc = ndet_gate_prepare(dgate, fn, n_views, h, w, H, W, true, &gf, &gr);
+        if (rc != NDET_OK) return rc;
+    }
+    if (dgate)
+        hipLaunchKernelGGL((k_density_features_packed<0, true>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, mapped_nhwc, n_views, cm,
+                           h, w, (int)mview_pitch, (int)mrow_pitch, bias, rgb, H, W, (int)rsv, (int)rsc, (int)rsy, points, N, projection,
+                           rgb_projection, global_feat, (int)blocks, nvp, gf, gr);
+    else
+        hipLaunchKernelGGL((k_density_features_packed<0, false>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, mapped_nhwc, n_views, cm,
+                           h, w, (int)mview_pitch, (int)mrow_pitch, bias, rgb, H, W, (int)rsv, (int)rsc, (int)rsy, points, N, projection,
+                           rgb_projection, global_feat, (int)blocks, nvp, gf, gr);
     NDET_CHECK_LAUNCH(fn);
     return NDET_OK;
+}
+
+extern "C" int ndet_density_features_packed(const float* mapped_nhwc, int n_views, int cm, int h, int w, int64_t mview_pitch,
+                                            int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv,
+                                            int64_t rsc, int64_t rsy, const float* points, int N, const float* projection,
+                                            const float* rgb_projection, float* global_feat, void* stream) {
+    return density_features_packed_impl("ndet_density_features_packed", mapped_nhwc, n_views, cm, h, w, mview_pitch, mrow_pitch, bias, rgb, H, W,
+                                        rsv, rsc, rsy, points, N, projection, rgb_projection, global_feat, nullptr, stream);
+}
+
+extern "C" int ndet_density_features_packed_gated(const float* mapped_nhwc, int n_views, int cm, int h, int w, int64_t mview_pitch,
+                                                  int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv,
+                                                  int64_t rsc, int64_t rsy, const float* points, int N, const float* projection,
+                                                  const float* rgb_projection, float* global_feat, const NdetDepthGate* gate, void* stream) {
+    NDET_REQUIRE(gate, NDET_E_INVALID, "ndet_density_features_packed_gated: null depth gate");
+    return density_features_packed_impl("ndet_density_features_packed_gated", mapped_nhwc, n_views, cm, h, w, mview_pitch, mrow_pitch, bias, rgb,
+                                        H, W, rsv, rsc, rsy, points, N, projection, rgb_projection, global_feat, gate, stream);
 }

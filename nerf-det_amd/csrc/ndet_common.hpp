@@ -49,8 +49,8 @@ __device__ __forceinline__ int ndet_xcd_remap(int b, int n) {
 //   Validity is evaluated on the rounded *float* coordinate: equivalent to the reference's
 //   int64 cast + compare for every finite value, and NaN / inf / |x| >= 2^63 come out invalid
 //   on both sides (x86 cvttss2si yields INT64_MIN there).
-__device__ __forceinline__ bool ndet_project(const float* __restrict__ P, float px, float py, float pz,
-                                             int w, int h, int& xi, int& yi) {
+__device__ __forceinline__ bool ndet_project_z(const float* __restrict__ P, float px, float py, float pz,
+                                               int w, int h, int& xi, int& yi, float& z) {
     float u = P[0] * px;
     u = fmaf(P[1], py, u);
     u = fmaf(P[2], pz, u);
@@ -68,8 +68,45 @@ __device__ __forceinline__ bool ndet_project(const float* __restrict__ P, float 
     const bool ok = (fx >= 0.0f) && (fy >= 0.0f) && (fx < (float)w) && (fy < (float)h) && (d > 0.0f);
     xi = ok ? (int)fx : 0;
     yi = ok ? (int)fy : 0;
+    z = d;
     return ok;
 }
+
+__device__ __forceinline__ bool ndet_project(const float* __restrict__ P, float px, float py, float pz,
+                                             int w, int h, int& xi, int& yi) {
+    float z;
+    return ndet_project_z(P, px, py, pz, w, h, xi, yi, z);
+}
+
+// Depth gate of nerfdet.py:404-411 (include/nerfdet_hip.h, NdetDepthGate): one resized map, kernel-argument form.  The kernels
+// take it under a compile-time flag; their ungated instantiations never read it.
+struct NdetGateMap {
+    const void* map;      // (n_views, h, w) float or double, element (v,y,x) at v*view_pitch + y*row_pitch + x
+    int64_t view_pitch;
+    int row_pitch;
+    int f64;              // 0: float32 map, 1: float64 map
+    double band;          // voxel_size[2]
+};
+
+// View v sees the voxel at pixel (xi, yi) with camera depth z iff  D'[v,y,x] - band < z < D'[v,y,x] + band  (strict), evaluated
+// as PyTorch evaluates `z > depth - voxel_size[-1]` on the reference's tensors: in float32 with band rounded to float32 for a
+// float32 map, in float64 (z widened exactly) for a float64 one.  Call only where ndet_project accepted the pixel.
+__device__ __forceinline__ bool ndet_depth_band(const NdetGateMap& g, int v, int xi, int yi, float z) {
+    const int64_t o = (int64_t)v * g.view_pitch + (int64_t)yi * g.row_pitch + xi;
+    if (g.f64) {
+        const double dv = static_cast<const double*>(g.map)[o];
+        const double zz = (double)z;
+        return (zz > dv - g.band) && (zz < dv + g.band);
+    }
+    const float dv = static_cast<const float*>(g.map)[o];
+    const float b = (float)g.band;
+    return (z > dv - b) && (z < dv + b);
+}
+
+// Host side: validate a caller's NdetDepthGate against the call (n_views, the projection's map h x w, and when need_r the image's
+// H x W) and turn its maps into kernel arguments.  Returns NDET_OK or the error code (message set).
+int ndet_gate_prepare(const NdetDepthGate* g, const char* fn, int n_views, int h, int w, int H, int W, bool need_r,
+                      NdetGateMap* gf, NdetGateMap* gr);
 
 // Gradient scatter of the backward kernels.  Default: float atomics (global_atomic_add_f32) -- fast, but the ORDER of the adds, and with it the last
 // bits of every sum, changes from run to run.  Deterministic mode (tests: ndet_measurement_knob("deterministic_scatter", 1); the caller then hands

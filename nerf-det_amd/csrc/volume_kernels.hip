@@ -19,7 +19,7 @@ void ndet_set_error(const char* fmt, ...) {
 }
 
 int g_ndet_deterministic_scatter = 0;      // ndet_common.hpp::ndet_scatter_add
-extern "C" int ndet_version(void) { return 108; }
+extern "C" int ndet_version(void) { return 109; }
 extern "C" const char* ndet_last_error(void) { return g_err; }
 
 #define VOX_PER_TILE 16  // one workgroup = 4 waves x 4 voxels = 16 consecutive voxels (one z column at Z=16)
@@ -125,18 +125,113 @@ extern "C" int ndet_hbm_copy(const float* src, float* dst, int64_t n_floats, voi
 }
 
 // ------------------------------------------------------------------------------------------
+// Depth gate (nerfdet.py:404-411): argument checks and the resize of the depth maps
+// ------------------------------------------------------------------------------------------
+int ndet_gate_prepare(const NdetDepthGate* g, const char* fn, int n_views, int h, int w, int H, int W, bool need_r,
+                      NdetGateMap* gf, NdetGateMap* gr) {
+    NDET_REQUIRE(g, NDET_E_INVALID, "%s: null depth gate", fn);
+    NDET_REQUIRE(g->size == (int32_t)sizeof(NdetDepthGate), NDET_E_INVALID, "%s: NdetDepthGate.size %d != %d (caller built against another layout)",
+                 fn, g->size, (int)sizeof(NdetDepthGate));
+    NDET_REQUIRE(g->dtype == 0 || g->dtype == 1, NDET_E_INVALID, "%s: depth dtype %d (0 = float32, 1 = float64)", fn, g->dtype);
+    NDET_REQUIRE(g->band > 0.0 && g->band < 1e300, NDET_E_INVALID, "%s: band %g must be finite and > 0", fn, g->band);
+    NDET_REQUIRE(g->n_views == n_views, NDET_E_INVALID, "%s: depth maps for %d views, call has %d", fn, g->n_views, n_views);
+    NDET_REQUIRE(g->depth_f && g->h == h && g->w == w, NDET_E_INVALID, "%s: depth_f must be a %dx%d map (got %p, %dx%d)", fn, h, w,
+                 g->depth_f, g->h, g->w);
+    NDET_REQUIRE(g->f_row_pitch >= w && g->f_view_pitch >= (int64_t)h * g->f_row_pitch && g->f_row_pitch < ((int64_t)1 << 31),
+                 NDET_E_INVALID, "%s: depth_f pitches smaller than the map", fn);
+    const size_t es = g->dtype ? sizeof(double) : sizeof(float);
+    NDET_REQUIRE(((uintptr_t)g->depth_f % es) == 0, NDET_E_INVALID, "%s: depth_f misaligned for its dtype", fn);
+    gf->map = g->depth_f; gf->view_pitch = g->f_view_pitch; gf->row_pitch = (int)g->f_row_pitch; gf->f64 = g->dtype; gf->band = g->band;
+    if (need_r) {
+        NDET_REQUIRE(g->depth_r && g->H == H && g->W == W, NDET_E_INVALID, "%s: depth_r must be a %dx%d map (got %p, %dx%d)", fn, H, W,
+                     g->depth_r, g->H, g->W);
+        NDET_REQUIRE(g->r_row_pitch >= W && g->r_view_pitch >= (int64_t)H * g->r_row_pitch && g->r_row_pitch < ((int64_t)1 << 31),
+                     NDET_E_INVALID, "%s: depth_r pitches smaller than the map", fn);
+        NDET_REQUIRE(((uintptr_t)g->depth_r % es) == 0, NDET_E_INVALID, "%s: depth_r misaligned for its dtype", fn);
+        gr->map = g->depth_r; gr->view_pitch = g->r_view_pitch; gr->row_pitch = (int)g->r_row_pitch; gr->f64 = g->dtype; gr->band = g->band;
+    } else if (gr) {
+        *gr = *gf;
+    }
+    return NDET_OK;
+}
+
+// F.interpolate(bilinear, align_corners=False) in T, PyTorch's CPU kernel's source-index form (bit-equal at integer ratios).
+// One thread per output pixel; the launch covers the feature-sized maps of all views, then the image-sized ones.
+template <typename T>
+__device__ __forceinline__ void resize_axis(int dst, int in, T scale, int& i0, int& i1, T& l0, T& l1) {
+    T src = ((T)dst + (T)0.5) * scale - (T)0.5;
+    if (src < (T)0) src = (T)0;
+    i0 = (int)src;
+    i1 = i0 + ((i0 < in - 1) ? 1 : 0);
+    l1 = src - (T)i0;
+    l0 = (T)1 - l1;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_depth_resize(const T* __restrict__ src, int n_views, int Hd, int Wd, int64_t sv, int64_t sy,
+                                                      T* __restrict__ out_f, int h, int w, T* __restrict__ out_r, int H, int W) {
+    const int64_t nf = (int64_t)n_views * h * w;
+    const int64_t nr = out_r ? (int64_t)n_views * H * W : 0;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nf + nr) return;
+    const bool f = i < nf;
+    const int64_t k = f ? i : i - nf;
+    const int oh = f ? h : H, ow = f ? w : W;
+    T* out = f ? out_f : out_r;
+    const int x = (int)(k % ow), y = (int)((k / ow) % oh), v = (int)(k / ((int64_t)ow * oh));
+    const T sh = (T)Hd / (T)oh, sw = (T)Wd / (T)ow;
+    int y0, y1, x0, x1;
+    T ly0, ly1, lx0, lx1;
+    resize_axis<T>(y, Hd, sh, y0, y1, ly0, ly1);
+    resize_axis<T>(x, Wd, sw, x0, x1, lx0, lx1);
+    const T* b = src + (int64_t)v * sv;
+    const T v00 = b[(int64_t)y0 * sy + x0], v01 = b[(int64_t)y0 * sy + x1];
+    const T v10 = b[(int64_t)y1 * sy + x0], v11 = b[(int64_t)y1 * sy + x1];
+    // PyTorch's CPU kernel takes one of two paths by the OUTPUT size (H + W <= 128: the per-tap weight products summed left to right;
+    // larger: the nested form); each is followed here so that both the small test scenes and the shipped sizes come out bit-equal
+    if (oh + ow <= 128)
+        out[k] = (((ly0 * lx0) * v00 + (ly0 * lx1) * v01) + (ly1 * lx0) * v10) + (ly1 * lx1) * v11;
+    else
+        out[k] = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
+}
+
+extern "C" int ndet_depth_resize(const void* depth, int dtype, int n_views, int Hd, int Wd, int64_t sv, int64_t sy,
+                                 void* out_f, int h, int w, void* out_r, int H, int W, void* stream) {
+    const char* fn = "ndet_depth_resize";
+    NDET_REQUIRE(depth && out_f, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(dtype == 0 || dtype == 1, NDET_E_INVALID, "%s: dtype %d (0 = float32, 1 = float64)", fn, dtype);
+    NDET_REQUIRE(n_views > 0 && Hd > 0 && Wd > 0 && h > 0 && w > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
+    NDET_REQUIRE(!out_r || (H > 0 && W > 0), NDET_E_INVALID, "%s: image-sized map of %dx%d", fn, H, W);
+    NDET_REQUIRE(sy >= Wd && sv >= (int64_t)Hd * sy, NDET_E_INVALID, "%s: pitches smaller than the depth map", fn);
+    const int64_t total = (int64_t)n_views * h * w + (out_r ? (int64_t)n_views * H * W : 0);
+    const int64_t blocks = (total + 255) / 256;
+    NDET_REQUIRE(blocks < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many pixels", fn);
+    if (dtype == 0)
+        hipLaunchKernelGGL(k_depth_resize<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)depth, n_views, Hd, Wd,
+                           sv, sy, (float*)out_f, h, w, (float*)out_r, H, W);
+    else
+        hipLaunchKernelGGL(k_depth_resize<double>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const double*)depth, n_views, Hd,
+                           Wd, sv, sy, (double*)out_f, h, w, (double*)out_r, H, W);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // A3  backproject, materialising form (exact reference API; not the hot path)
 // ------------------------------------------------------------------------------------------
+template <bool DG>
 __global__ __launch_bounds__(256) void k_backproject(const float* __restrict__ feat, int C, int h, int w,
                                                      int64_t sv, int64_t sc, int64_t sy, int64_t sx,
                                                      const float* __restrict__ points, int N,
                                                      const float* __restrict__ proj, float* __restrict__ volume,
-                                                     uint8_t* __restrict__ valid) {
+                                                     uint8_t* __restrict__ valid, NdetGateMap gate) {
     const int v = blockIdx.y;
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
     int xi, yi;
-    const bool ok = ndet_project(proj + v * 12, points[n], points[N + n], points[2 * N + n], w, h, xi, yi);
+    float z;
+    bool ok = ndet_project_z(proj + v * 12, points[n], points[N + n], points[2 * N + n], w, h, xi, yi, z);
+    if (DG) ok = ok && ndet_depth_band(gate, v, xi, yi, z);
     valid[(int64_t)v * N + n] = ok ? 1 : 0;
     const float* src = feat + v * sv + yi * sy + xi * sx;
     float* dst = volume + (int64_t)v * C * N + n;
@@ -157,17 +252,41 @@ __global__ __launch_bounds__(256) void k_backproject(const float* __restrict__ f
     for (; c < C; ++c) dst[(int64_t)c * N] = ok ? src[c * sc] : 0.f;
 }
 
+static int backproject_impl(const char* fn, const float* features, int n_views, int C, int h, int w, int64_t sv, int64_t sc,
+                            int64_t sy, int64_t sx, const float* points, int N, const float* projection,
+                            float* volume, uint8_t* valid, const NdetDepthGate* gate, void* stream) {
+    NDET_REQUIRE(features && points && projection && volume && valid, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(n_views > 0 && C > 0 && h > 0 && w > 0 && N > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
+    NDET_REQUIRE(n_views <= 65535, NDET_E_UNSUPPORTED, "%s: more than 65535 views", fn);
+    NdetGateMap gm = {};
+    if (gate) {
+        const int rc = ndet_gate_prepare(gate, fn, n_views, h, w, 0, 0, false, &gm, nullptr);
+        if (rc != NDET_OK) return rc;
+    }
+    dim3 grid((N + 255) / 256, n_views);
+    if (gate)
+        hipLaunchKernelGGL(k_backproject<true>, grid, dim3(256), 0, (hipStream_t)stream, features, C, h, w, sv, sc, sy, sx, points,
+                           N, projection, volume, valid, gm);
+    else
+        hipLaunchKernelGGL(k_backproject<false>, grid, dim3(256), 0, (hipStream_t)stream, features, C, h, w, sv, sc, sy, sx, points,
+                           N, projection, volume, valid, gm);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
 extern "C" int ndet_backproject(const float* features, int n_views, int C, int h, int w, int64_t sv, int64_t sc,
                                 int64_t sy, int64_t sx, const float* points, int N, const float* projection,
                                 float* volume, uint8_t* valid, void* stream) {
-    NDET_REQUIRE(features && points && projection && volume && valid, NDET_E_INVALID, "ndet_backproject: null pointer");
-    NDET_REQUIRE(n_views > 0 && C > 0 && h > 0 && w > 0 && N > 0, NDET_E_INVALID, "ndet_backproject: sizes must be positive");
-    NDET_REQUIRE(n_views <= 65535, NDET_E_UNSUPPORTED, "ndet_backproject: more than 65535 views");
-    dim3 grid((N + 255) / 256, n_views);
-    hipLaunchKernelGGL(k_backproject, grid, dim3(256), 0, (hipStream_t)stream, features, C, h, w, sv, sc, sy, sx, points,
-                       N, projection, volume, valid);
-    NDET_CHECK_LAUNCH("ndet_backproject");
-    return NDET_OK;
+    return backproject_impl("ndet_backproject", features, n_views, C, h, w, sv, sc, sy, sx, points, N, projection, volume, valid,
+                            nullptr, stream);
+}
+
+extern "C" int ndet_backproject_gated(const float* features, int n_views, int C, int h, int w, int64_t sv, int64_t sc,
+                                      int64_t sy, int64_t sx, const float* points, int N, const float* projection,
+                                      float* volume, uint8_t* valid, const NdetDepthGate* gate, void* stream) {
+    NDET_REQUIRE(gate, NDET_E_INVALID, "ndet_backproject_gated: null depth gate");
+    return backproject_impl("ndet_backproject_gated", features, n_views, C, h, w, sv, sc, sy, sx, points, N, projection, volume, valid,
+                            gate, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -183,11 +302,13 @@ extern "C" int ndet_backproject(const float* features, int n_views, int C, int h
 // Nothing of size (n_views, C, N) is ever written: reads = feature rows actually hit,
 // writes = (C + 2) * N * 4 bytes.
 // ------------------------------------------------------------------------------------------
-template <int NCHUNK, bool GATE, int LAYOUT>
-__global__ __launch_bounds__(256, K1_MIN_WAVES) void k_backproject_aggregate(
+// The depth-gated instantiations (DG) hold the gate's map, pitches and band on top: at K1_MIN_WAVES they spill, one wave fewer per SIMD
+// leaves them spill-free.
+template <int NCHUNK, bool GATE, int LAYOUT, bool DG>
+__global__ __launch_bounds__(256, DG ? K1_MIN_WAVES - 1 : K1_MIN_WAVES) void k_backproject_aggregate(
     const float* __restrict__ feat, int n_views, int C, int h, int w, int64_t view_pitch, int row_pitch,
     const float* __restrict__ points, int N, const float* __restrict__ proj, const float* __restrict__ alpha,
-    float* __restrict__ out, int64_t* __restrict__ count, int n_tiles) {
+    float* __restrict__ out, int64_t* __restrict__ count, int n_tiles, NdetGateMap dgate) {
     extern __shared__ __attribute__((aligned(16))) float smem[];  // LAYOUT_CN only: [16][C + 4]
     constexpr int VPW = VOX_PER_TILE / 4;  // voxels per wave, processed together
     const int lane = threadIdx.x & 63;
@@ -235,7 +356,10 @@ __global__ __launch_bounds__(256, K1_MIN_WAVES) void k_backproject_aggregate(
 #pragma unroll
         for (int j = 0; j < VPW; ++j) {
             int xi = 0, yi = 0;
-            const bool ok = (v < n_views) && live[j] && ndet_project(P, px[j], py[j], pz[j], w, h, xi, yi);
+            float z;
+            bool ok = (v < n_views) && live[j] && ndet_project_z(P, px[j], py[j], pz[j], w, h, xi, yi, z);
+            // depth gate: the lane's own view's depth value, before the ballot -- a gated-out view never costs a row gather
+            if (DG) ok = ok && ndet_depth_band(dgate, v, xi, yi, z);
             off[j] = yi * row_pitch + xi * C;  // floats inside one view (< 2^31, checked on the host)
             mask[j] = __ballot(ok);
             cnt[j] += __popcll(mask[j]);
@@ -321,13 +445,13 @@ __global__ __launch_bounds__(256, K1_MIN_WAVES) void k_backproject_aggregate(
     }
 }
 
-template <int NCHUNK>
+template <int NCHUNK, bool DG>
 static void launch_k1(bool gate, int layout, dim3 grid, size_t lds, hipStream_t st, const float* feat, int n_views, int C,
                       int h, int w, int64_t view_pitch, int row_pitch, const float* points, int N, const float* proj,
-                      const float* alpha, float* out, int64_t* count, int n_tiles) {
-#define K1_LAUNCH(G, L)                                                                                              \
-    hipLaunchKernelGGL((k_backproject_aggregate<NCHUNK, G, L>), grid, dim3(256), lds, st, feat, n_views, C, h, w,    \
-                       view_pitch, row_pitch, points, N, proj, alpha, out, count, n_tiles)
+                      const float* alpha, float* out, int64_t* count, int n_tiles, const NdetGateMap& dgate) {
+#define K1_LAUNCH(G, L)                                                                                                  \
+    hipLaunchKernelGGL((k_backproject_aggregate<NCHUNK, G, L, DG>), grid, dim3(256), lds, st, feat, n_views, C, h, w,    \
+                       view_pitch, row_pitch, points, N, proj, alpha, out, count, n_tiles, dgate)
     if (gate) {
         if (layout == NDET_LAYOUT_NC) K1_LAUNCH(true, NDET_LAYOUT_NC);
         else K1_LAUNCH(true, NDET_LAYOUT_CN);
@@ -338,11 +462,10 @@ static void launch_k1(bool gate, int layout, dim3 grid, size_t lds, hipStream_t 
 #undef K1_LAUNCH
 }
 
-extern "C" int ndet_backproject_aggregate(const float* features_nhwc, int n_views, int C, int h, int w,
-                                          int64_t view_pitch, int64_t row_pitch, const float* points, int N,
-                                          const float* projection, const float* alpha, float* out, int out_layout,
-                                          int64_t* count, void* stream) {
-    const char* fn = "ndet_backproject_aggregate";
+static int backproject_aggregate_impl(const char* fn, const float* features_nhwc, int n_views, int C, int h, int w,
+                                      int64_t view_pitch, int64_t row_pitch, const float* points, int N,
+                                      const float* projection, const float* alpha, float* out, int out_layout,
+                                      int64_t* count, const NdetDepthGate* dgate, void* stream) {
     NDET_REQUIRE(features_nhwc && points && projection && out && count, NDET_E_INVALID, "%s: null pointer", fn);
     NDET_REQUIRE(n_views > 0 && C > 0 && h > 0 && w > 0 && N > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
     NDET_REQUIRE(out_layout == NDET_LAYOUT_CN || out_layout == NDET_LAYOUT_NC, NDET_E_INVALID, "%s: bad layout %d", fn, out_layout);
@@ -352,19 +475,51 @@ extern "C" int ndet_backproject_aggregate(const float* features_nhwc, int n_view
                  "%s: feature rows must be 16-byte aligned", fn);
     NDET_REQUIRE((int64_t)h * row_pitch < (int64_t)1 << 31, NDET_E_UNSUPPORTED, "%s: one view exceeds 2^31 floats", fn);
     if (out_layout == NDET_LAYOUT_NC) NDET_REQUIRE(((uintptr_t)out & 15) == 0, NDET_E_UNSUPPORTED, "%s: out must be 16-byte aligned", fn);
+    NdetGateMap gm = {};
+    if (dgate) {
+        const int rc = ndet_gate_prepare(dgate, fn, n_views, h, w, 0, 0, false, &gm, nullptr);
+        if (rc != NDET_OK) return rc;
+    }
     const int n_tiles = (N + VOX_PER_TILE - 1) / VOX_PER_TILE;
     const size_t lds = out_layout == NDET_LAYOUT_CN ? (size_t)VOX_PER_TILE * (C + 4) * sizeof(float) : 0;
     const dim3 grid(n_tiles);
     hipStream_t st = (hipStream_t)stream;
     const bool gate = alpha != nullptr;
-    if (C <= 256)
-        launch_k1<1>(gate, out_layout, grid, lds, st, features_nhwc, n_views, C, h, w, view_pitch, (int)row_pitch, points, N, projection, alpha, out, count, n_tiles);
-    else if (C <= 512)
-        launch_k1<2>(gate, out_layout, grid, lds, st, features_nhwc, n_views, C, h, w, view_pitch, (int)row_pitch, points, N, projection, alpha, out, count, n_tiles);
-    else
-        launch_k1<4>(gate, out_layout, grid, lds, st, features_nhwc, n_views, C, h, w, view_pitch, (int)row_pitch, points, N, projection, alpha, out, count, n_tiles);
+#define K1_CHUNKS(DG)                                                                                                                                \
+    if (C <= 256)                                                                                                                                    \
+        launch_k1<1, DG>(gate, out_layout, grid, lds, st, features_nhwc, n_views, C, h, w, view_pitch, (int)row_pitch, points, N, projection, alpha, \
+                         out, count, n_tiles, gm);                                                                                                   \
+    else if (C <= 512)                                                                                                                               \
+        launch_k1<2, DG>(gate, out_layout, grid, lds, st, features_nhwc, n_views, C, h, w, view_pitch, (int)row_pitch, points, N, projection, alpha, \
+                         out, count, n_tiles, gm);                                                                                                   \
+    else                                                                                                                                             \
+        launch_k1<4, DG>(gate, out_layout, grid, lds, st, features_nhwc, n_views, C, h, w, view_pitch, (int)row_pitch, points, N, projection, alpha, \
+                         out, count, n_tiles, gm)
+    if (dgate) {
+        K1_CHUNKS(true);
+    } else {
+        K1_CHUNKS(false);
+    }
+#undef K1_CHUNKS
     NDET_CHECK_LAUNCH(fn);
     return NDET_OK;
+}
+
+extern "C" int ndet_backproject_aggregate(const float* features_nhwc, int n_views, int C, int h, int w,
+                                          int64_t view_pitch, int64_t row_pitch, const float* points, int N,
+                                          const float* projection, const float* alpha, float* out, int out_layout,
+                                          int64_t* count, void* stream) {
+    return backproject_aggregate_impl("ndet_backproject_aggregate", features_nhwc, n_views, C, h, w, view_pitch, row_pitch, points, N,
+                                      projection, alpha, out, out_layout, count, nullptr, stream);
+}
+
+extern "C" int ndet_backproject_aggregate_gated(const float* features_nhwc, int n_views, int C, int h, int w,
+                                                int64_t view_pitch, int64_t row_pitch, const float* points, int N,
+                                                const float* projection, const float* alpha, float* out, int out_layout,
+                                                int64_t* count, const NdetDepthGate* gate, void* stream) {
+    NDET_REQUIRE(gate, NDET_E_INVALID, "ndet_backproject_aggregate_gated: null depth gate");
+    return backproject_aggregate_impl("ndet_backproject_aggregate_gated", features_nhwc, n_views, C, h, w, view_pitch, row_pitch, points, N,
+                                      projection, alpha, out, out_layout, count, gate, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -385,14 +540,21 @@ struct DensityRound {
     unsigned boff_f, boff_r;    // the same as byte offsets from the tensor base, view included (buffer-load path)
 };
 
+template <bool DG>
 __device__ __forceinline__ DensityRound density_project(int v, int n_views, const float* __restrict__ proj, const float* __restrict__ rgb_proj,
                                                         float px, float py, float pz, int w, int h, int W, int H, int mrow_pitch, int cm,
-                                                        int rsy, int64_t mview_pitch = 0, int64_t rsv = 0) {
+                                                        int rsy, int64_t mview_pitch, int64_t rsv, const NdetGateMap& gf, const NdetGateMap& gr) {
     int xf = 0, yf = 0, xr = 0, yr = 0;
     bool okf = false, okr = false;
     if (v < n_views) {
-        okf = ndet_project(proj + v * 12, px, py, pz, w, h, xf, yf);
-        okr = ndet_project(rgb_proj + v * 12, px, py, pz, W, H, xr, yr);
+        if (DG) {   // depth gate of both backproject() calls (nerfdet.py:164-169 / 204-210 -> 404-411)
+            float zf, zr;
+            okf = ndet_project_z(proj + v * 12, px, py, pz, w, h, xf, yf, zf) && ndet_depth_band(gf, v, xf, yf, zf);
+            okr = ndet_project_z(rgb_proj + v * 12, px, py, pz, W, H, xr, yr, zr) && ndet_depth_band(gr, v, xr, yr, zr);
+        } else {
+            okf = ndet_project(proj + v * 12, px, py, pz, w, h, xf, yf);
+            okr = ndet_project(rgb_proj + v * 12, px, py, pz, W, H, xr, yr);
+        }
     }
     DensityRound r;
     r.off_f = yf * mrow_pitch + xf * cm;
@@ -491,13 +653,13 @@ __device__ __forceinline__ float density_round_pass_buf(const DensityRound& d, _
     return acc;
 }
 
-template <bool BUF>
+template <bool BUF, bool DG>
 __global__ __launch_bounds__(256) void k_density_features(const float* __restrict__ mapped, int n_views, int cm, int h, int w,
                                                           int64_t mview_pitch, int mrow_pitch, const float* __restrict__ bias,
                                                           const float* __restrict__ rgb, int H, int W, int64_t rsv, int64_t rsc,
                                                           int rsy, const float* __restrict__ points, int N,
                                                           const float* __restrict__ proj, const float* __restrict__ rgb_proj,
-                                                          float* __restrict__ out, int n_tiles) {
+                                                          float* __restrict__ out, int n_tiles, NdetGateMap gf, NdetGateMap gr) {
     constexpr int VPW = VOX_PER_TILE / 4;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -524,7 +686,7 @@ __global__ __launch_bounds__(256) void k_density_features(const float* __restric
     // the wave's 4 voxels are projected back to back (lanes over views) before any gather is issued
     DensityRound first[VPW];
 #pragma unroll
-    for (int j = 0; j < VPW; ++j) first[j] = density_project(lane, n_views, proj, rgb_proj, px[j], py[j], pz[j], w, h, W, H, mrow_pitch, cm, rsy, mview_pitch, rsv);
+    for (int j = 0; j < VPW; ++j) first[j] = density_project<DG>(lane, n_views, proj, rgb_proj, px[j], py[j], pz[j], w, h, W, H, mrow_pitch, cm, rsy, mview_pitch, rsv, gf, gr);
 
 #pragma unroll
     for (int j = 0; j < VPW; ++j) {
@@ -534,7 +696,7 @@ __global__ __launch_bounds__(256) void k_density_features(const float* __restric
         int cnt = 0, n_union = 0;
         for (int r0 = 0; r0 < n_views; r0 += 64) {
             const DensityRound d = (r0 == 0) ? first[j]
-                                             : density_project(r0 + lane, n_views, proj, rgb_proj, px[j], py[j], pz[j], w, h, W, H, mrow_pitch, cm, rsy, mview_pitch, rsv);
+                                             : density_project<DG>(r0 + lane, n_views, proj, rgb_proj, px[j], py[j], pz[j], w, h, W, H, mrow_pitch, cm, rsy, mview_pitch, rsv, gf, gr);
             cnt += __popcll(d.mf);
             n_union += __popcll(d.mf | d.mr);
             sum = BUF ? density_round_pass_buf<0>(d, mres, rres, fvoff, rvoff, is_rgb, fill, 0.0f, sum)
@@ -547,7 +709,7 @@ __global__ __launch_bounds__(256) void k_density_features(const float* __restric
         float ss = 0.0f;
         for (int r0 = 0; r0 < n_views; r0 += 64) {
             const DensityRound d = (r0 == 0 || single_round) ? first[j]
-                                                             : density_project(r0 + lane, n_views, proj, rgb_proj, px[j], py[j], pz[j], w, h, W, H, mrow_pitch, cm, rsy, mview_pitch, rsv);
+                                                             : density_project<DG>(r0 + lane, n_views, proj, rgb_proj, px[j], py[j], pz[j], w, h, W, H, mrow_pitch, cm, rsy, mview_pitch, rsv, gf, gr);
             ss = BUF ? density_round_pass_buf<1>(d, mres, rres, fvoff, rvoff, is_rgb, fill, mean, ss)
                      : density_round_pass<1>(d, r0, mapped, mview_pitch, rgb, rsv, rsc, lane, cm, fill, mean, ss);
         }
@@ -560,31 +722,56 @@ __global__ __launch_bounds__(256) void k_density_features(const float* __restric
     }
 }
 
-extern "C" int ndet_density_features(const float* mapped_nhwc, int n_views, int cm, int h, int w, int64_t mview_pitch,
-                                     int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv,
-                                     int64_t rsc, int64_t rsy, const float* points, int N, const float* projection,
-                                     const float* rgb_projection, float* global_feat, void* stream) {
-    const char* fn = "ndet_density_features";
+static int density_features_impl(const char* fn, const float* mapped_nhwc, int n_views, int cm, int h, int w, int64_t mview_pitch,
+                                 int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv,
+                                 int64_t rsc, int64_t rsy, const float* points, int N, const float* projection,
+                                 const float* rgb_projection, float* global_feat, const NdetDepthGate* dgate, void* stream) {
     NDET_REQUIRE(mapped_nhwc && bias && rgb && points && projection && rgb_projection && global_feat, NDET_E_INVALID, "%s: null pointer", fn);
     NDET_REQUIRE(n_views > 0 && cm > 0 && h > 0 && w > 0 && H > 0 && W > 0 && N > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
     NDET_REQUIRE(cm <= 61, NDET_E_UNSUPPORTED, "%s: cm=%d mapped channels do not fit one wavefront (max 61)", fn, cm);
     NDET_REQUIRE((int64_t)h * mrow_pitch < (int64_t)1 << 31 && (int64_t)H * rsy < (int64_t)1 << 31, NDET_E_UNSUPPORTED,
                  "%s: one view exceeds 2^31 floats", fn);
     NDET_REQUIRE(((uintptr_t)global_feat & 7) == 0, NDET_E_UNSUPPORTED, "%s: global_feat must be 8-byte aligned", fn);
+    NdetGateMap gf = {}, gr = {};
+    if (dgate) {
+        const int rc = ndet_gate_prepare(dgate, fn, n_views, h, w, H, W, true, &gf, &gr);
+        if (rc != NDET_OK) return rc;
+    }
     const int n_tiles = (N + VOX_PER_TILE - 1) / VOX_PER_TILE;
     // both tensors within 2 GB: gathers as buffer loads with the view offset in the scalar register
     const bool buf = (int64_t)n_views * mview_pitch * 4 < ((int64_t)1 << 31) && (int64_t)n_views * rsv * 4 < ((int64_t)1 << 31) &&
                      mview_pitch >= 0 && rsv >= 0 && rsc >= 0;
-    if (buf)
-        hipLaunchKernelGGL(k_density_features<true>, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, mapped_nhwc, n_views, cm, h, w,
-                           mview_pitch, (int)mrow_pitch, bias, rgb, H, W, rsv, rsc, (int)rsy, points, N, projection, rgb_projection,
-                           global_feat, n_tiles);
-    else
-        hipLaunchKernelGGL(k_density_features<false>, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, mapped_nhwc, n_views, cm, h, w,
-                           mview_pitch, (int)mrow_pitch, bias, rgb, H, W, rsv, rsc, (int)rsy, points, N, projection, rgb_projection,
-                           global_feat, n_tiles);
+#define K2_LAUNCH(B, DG)                                                                                                                    \
+    hipLaunchKernelGGL((k_density_features<B, DG>), dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, mapped_nhwc, n_views, cm, h, w,     \
+                       mview_pitch, (int)mrow_pitch, bias, rgb, H, W, rsv, rsc, (int)rsy, points, N, projection, rgb_projection,            \
+                       global_feat, n_tiles, gf, gr)
+    if (dgate) {
+        if (buf) K2_LAUNCH(true, true);
+        else K2_LAUNCH(false, true);
+    } else {
+        if (buf) K2_LAUNCH(true, false);
+        else K2_LAUNCH(false, false);
+    }
+#undef K2_LAUNCH
     NDET_CHECK_LAUNCH(fn);
     return NDET_OK;
+}
+
+extern "C" int ndet_density_features(const float* mapped_nhwc, int n_views, int cm, int h, int w, int64_t mview_pitch,
+                                     int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv,
+                                     int64_t rsc, int64_t rsy, const float* points, int N, const float* projection,
+                                     const float* rgb_projection, float* global_feat, void* stream) {
+    return density_features_impl("ndet_density_features", mapped_nhwc, n_views, cm, h, w, mview_pitch, mrow_pitch, bias, rgb, H, W, rsv, rsc,
+                                 rsy, points, N, projection, rgb_projection, global_feat, nullptr, stream);
+}
+
+extern "C" int ndet_density_features_gated(const float* mapped_nhwc, int n_views, int cm, int h, int w, int64_t mview_pitch,
+                                           int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv,
+                                           int64_t rsc, int64_t rsy, const float* points, int N, const float* projection,
+                                           const float* rgb_projection, float* global_feat, const NdetDepthGate* gate, void* stream) {
+    NDET_REQUIRE(gate, NDET_E_INVALID, "ndet_density_features_gated: null depth gate");
+    return density_features_impl("ndet_density_features_gated", mapped_nhwc, n_views, cm, h, w, mview_pitch, mrow_pitch, bias, rgb, H, W, rsv,
+                                 rsc, rsy, points, N, projection, rgb_projection, global_feat, gate, stream);
 }
 
 // ------------------------------------------------------------------------------------------

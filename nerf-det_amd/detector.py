@@ -113,8 +113,12 @@ class nerfdet(BaseDetector):
         return x, b, int(stride)
 
     def extract_feat(self, img, img_metas, mode, depth=None, ray_batch=None):
-        """Same contract as nerfdet.py:133-269: returns (neck_3d outputs, valids, features_2d, rgb_preds, densitys)."""
-        assert depth is None, "depth is never forwarded to extract_feat by the reference (SURVEY.md 0.1)"
+        """Same contract as nerfdet.py:133-269: returns (neck_3d outputs, valids, features_2d, rgb_preds, densitys).
+        ``depth`` (B, n_v, Hd, Wd) float32 / float64, in metres (the loader's ``depth`` key): every backprojection is depth-gated
+        (nerfdet.py:136-139, 164-169, 204-210, 404-411)."""
+        if depth is not None:
+            assert depth.shape[0] == img.shape[0], "depth and img must hold the same scenes (nerfdet.py:137)"
+            depth = depth.reshape([-1] + list(depth.shape)[2:])
         assert ray_batch is not None and self.nerf_density and self.nerf_mode == "image", \
             "effective contract of the reference: use_ray=True, nerf_density=True, nerf_mode='image' (SURVEY.md 0.2)"
         trace.mark("begin")
@@ -144,10 +148,12 @@ class nerfdet(BaseDetector):
             dn = denorm.reshape([-1] + list(denorm.shape)[2:])
             # channels-last volume straight into the MFMA convolutions of the 3D neck (inference and training alike)
             hf, wf = img_meta["img_shape"][0] // stride, img_meta["img_shape"][1] // stride
+            # the keyword only when there is depth: callers that stand in for extract_volume keep the ungated signature
+            gated = {} if depth is None else dict(depth=depth[b * n_v:(b + 1) * n_v])
             out = extract_volume(feat, dn, img_meta, self.n_voxels, self.voxel_size, self.mapping, self.nerf_mlp,
                                  stride=stride, channels_last_out=True,
                                  feature_2d=None if (f2d is None or torch.is_grad_enabled()) else f2d[b * n_v:(b + 1) * n_v, :, :hf, :wf],
-                                 geometry=None if geoms is None else geoms[b])
+                                 geometry=None if geoms is None else geoms[b], **gated)
             if mode == "train" or self.render_testing:
                 from .rays import render_rays
                 rgb_preds.append(render_rays(ray_batch, None, None, out["feature_2d"], dn, self.aabb, self.near_far_range,

@@ -2,12 +2,15 @@
 bodies routed to libnerfdet_hip.so through the C ABI.  PyTorch is used for device memory and
 streams only; every function here requires CUDA(HIP) tensors and raises otherwise.
 
-Reference signatures kept: ``get_points``, ``backproject`` (mmdet3d/models/detectors/nerfdet.py:380-420).
+Reference signatures kept: ``get_points``, ``backproject`` (mmdet3d/models/detectors/nerfdet.py:380-420, with or without the depth
+gate of :405-411).
 Fused forms that have no single reference counterpart (``backproject_aggregate``, ``density_features``)
 document the reference lines they replace.
 """
 from __future__ import annotations
 
+import ctypes
+import math
 from ctypes import c_void_p
 from typing import Optional, Sequence, Tuple
 
@@ -16,7 +19,7 @@ import torch
 
 from . import _lib, trace
 from .hostmath import matmul_fma_chain
-from ._lib import NDET_LAYOUT_CN, NDET_LAYOUT_NC, check, float3
+from ._lib import NDET_LAYOUT_CN, NDET_LAYOUT_NC, NdetDepthGate, check, float3
 from ._lib import raw_stream
 
 Tensor = torch.Tensor
@@ -118,15 +121,96 @@ def to_channels_last(x: Tensor) -> Tensor:
 
 
 # --------------------------------------------------------------------------------------------
+# depth gate (RGB-D scenes): nerfdet.py:404-411
+# --------------------------------------------------------------------------------------------
+_DEPTH_DTYPES = {torch.float32: 0, torch.float64: 1}
+
+
+def depth_resize(depth: Tensor, feat_hw, img_hw=None) -> Tuple[Tensor, Optional[Tensor]]:
+    """``F.interpolate(depth.unsqueeze(1), size, mode="bilinear")`` (nerfdet.py:405) to the feature map's ``feat_hw`` and, with
+    ``img_hw``, to the image's as well -- both in one launch, in the depth map's own dtype (float32 or float64).
+    ``depth`` (n_v, Hd, Wd) on the GPU.  Returns ``(D_f (n_v,h,w), D_r (n_v,H,W) or None)``, contiguous."""
+    _need_gpu(depth)
+    assert depth.dim() == 3, f"depth must be (n_views, H, W), got {tuple(depth.shape)}"
+    if depth.dtype not in _DEPTH_DTYPES:
+        raise ValueError(f"depth maps are float32 or float64, got {depth.dtype}")
+    if depth.stride(2) != 1:
+        depth = depth.contiguous()
+    n_v, hd, wd = depth.shape
+    h, w = int(feat_hw[0]), int(feat_hw[1])
+    out_f = torch.empty((n_v, h, w), dtype=depth.dtype, device=depth.device)
+    out_r = None
+    hh = ww = 0
+    if img_hw is not None:
+        hh, ww = int(img_hw[0]), int(img_hw[1])
+        out_r = torch.empty((n_v, hh, ww), dtype=depth.dtype, device=depth.device)
+    trace.span("k_depth_resize", lambda: check(
+        _lib.load().ndet_depth_resize(_ptr(depth), _DEPTH_DTYPES[depth.dtype], n_v, hd, wd, depth.stride(0), depth.stride(1), _ptr(out_f), h, w,
+                                      _ptr(out_r), hh, ww, _stream(depth)), "depth_resize"),
+        bytes=depth.element_size() * (n_v * hd * wd + out_f.numel() + (0 if out_r is None else out_r.numel())), kind="hbm")
+    return out_f, out_r
+
+
+class DepthGate:
+    """One scene's depth gate (nerfdet.py:404-411): the depth map resized to the feature map (``depth_f``) and, for the density features'
+    stride-1 projection, to the image (``depth_r``), plus ``band`` = voxel_size[2].  A view sees a voxel only where its camera depth z
+    satisfies ``D' - band < z < D' + band``.  Built by :func:`depth_gate`; passed to the ``depth_gate=`` argument of the ops."""
+
+    def __init__(self, depth_f: Tensor, depth_r: Optional[Tensor], band: float):
+        assert math.isfinite(band) and band > 0, f"the depth band (voxel_size[2]) must be finite and > 0, got {band}"
+        self.depth_f, self.depth_r, self.band = depth_f, depth_r, float(band)
+
+    @property
+    def n_views(self) -> int:
+        return self.depth_f.shape[0]
+
+    def block(self) -> NdetDepthGate:
+        """The C ABI's NdetDepthGate for this gate (the tensors stay owned by ``self``)."""
+        f, r = self.depth_f, self.depth_r
+        g = NdetDepthGate()
+        g.size = ctypes.sizeof(NdetDepthGate)
+        g.dtype = _DEPTH_DTYPES[f.dtype]
+        g.n_views, g.h, g.w = f.shape[0], f.shape[1], f.shape[2]
+        g.depth_f, g.f_view_pitch, g.f_row_pitch = f.data_ptr(), f.stride(0), f.stride(1)
+        if r is not None:
+            g.H, g.W = r.shape[1], r.shape[2]
+            g.depth_r, g.r_view_pitch, g.r_row_pitch = r.data_ptr(), r.stride(0), r.stride(1)
+        g.band = self.band
+        return g
+
+
+def depth_gate(depth: Tensor, voxel_size, feat_hw, img_hw=None) -> DepthGate:
+    """The :class:`DepthGate` of ``depth`` (n_v, Hd, Wd) for a (h, w) feature map [and an (H, W) image]: one resize launch."""
+    assert voxel_size is not None, "the depth gate needs voxel_size (its band is voxel_size[2], nerfdet.py:408)"
+    vs = voxel_size.tolist() if isinstance(voxel_size, Tensor) else list(voxel_size)
+    d_f, d_r = depth_resize(depth, feat_hw, img_hw)
+    return DepthGate(d_f, d_r, float(vs[-1]))
+
+
+def _gate_arg(gate: Optional[DepthGate], n_v: int, hw, img_hw=None):
+    if gate is None:
+        return None
+    assert gate.n_views == n_v and tuple(gate.depth_f.shape[1:]) == tuple(hw), \
+        f"depth gate for {tuple(gate.depth_f.shape)}, map is {(n_v,) + tuple(hw)}"
+    if img_hw is not None:
+        assert gate.depth_r is not None and tuple(gate.depth_r.shape[1:]) == tuple(img_hw), "depth gate has no map at the image's size"
+    return ctypes.byref(gate.block())
+
+
+# --------------------------------------------------------------------------------------------
 # A3 exact form
 # --------------------------------------------------------------------------------------------
 def backproject(features: Tensor, points: Tensor, projection: Tensor, depth=None, voxel_size=None) -> Tuple[Tensor, Tensor]:
     """Reference API: (n_v,C,h,w),(3,X,Y,Z),(n_v,3,4) -> volume (n_v,C,X,Y,Z), valid (n_v,1,X,Y,Z) bool.
     nerfdet.py:393-420.  Materialises the per-view volume exactly like the reference; the inference
-    path uses :func:`backproject_aggregate` instead.  ``depth`` gating is dead code under every shipped
-    config and is rejected."""
-    assert depth is None, "depth-gated backproject (nerfdet.py:405-411) is not reachable from the nerfdet configs"
-    _need_gpu(features, points, projection)
+    path uses :func:`backproject_aggregate` instead.  With ``depth`` (n_v,Hd,Wd) float32/float64 and ``voxel_size``, a view
+    sees a voxel only within voxel_size[2] of the observed surface (nerfdet.py:404-411): the map is resized to (h, w) in its
+    own dtype and the band test runs in that dtype, as PyTorch evaluates the reference's expression."""
+    if depth is not None:
+        assert isinstance(depth, Tensor) and depth.dim() == 3 and depth.shape[0] == features.shape[0], \
+            "depth must be (n_views, H, W) (nerfdet.py:405)"
+        assert voxel_size is not None, "depth-gated backproject needs voxel_size (nerfdet.py:408)"
+    _need_gpu(features, points, projection, depth)
     if features.dtype != torch.float32:
         features = features.float()
     n_v, c, h, w = features.shape
@@ -138,8 +222,13 @@ def backproject(features: Tensor, points: Tensor, projection: Tensor, depth=None
     volume = torch.empty((n_v, c, gx, gy, gz), dtype=torch.float32, device=features.device)
     valid = torch.empty((n_v, 1, gx, gy, gz), dtype=torch.bool, device=features.device)
     sv, sc, sy, sx = features.stride()
-    check(_lib.load().ndet_backproject(_ptr(features), n_v, c, h, w, sv, sc, sy, sx, _ptr(points), n, _ptr(projection),
-                                       _ptr(volume), _ptr(valid), _stream(features)), "backproject")
+    if depth is None:
+        check(_lib.load().ndet_backproject(_ptr(features), n_v, c, h, w, sv, sc, sy, sx, _ptr(points), n, _ptr(projection),
+                                           _ptr(volume), _ptr(valid), _stream(features)), "backproject")
+    else:
+        gate = depth_gate(depth, voxel_size, (h, w))
+        check(_lib.load().ndet_backproject_gated(_ptr(features), n_v, c, h, w, sv, sc, sy, sx, _ptr(points), n, _ptr(projection),
+                                                 _ptr(volume), _ptr(valid), _gate_arg(gate, n_v, (h, w)), _stream(features)), "backproject_gated")
     return volume, valid
 
 
@@ -147,9 +236,11 @@ def backproject(features: Tensor, points: Tensor, projection: Tensor, depth=None
 # K1: A3 + A4 (+ A6 gating)
 # --------------------------------------------------------------------------------------------
 def backproject_aggregate(features: Tensor, points: Tensor, projection: Tensor, alpha: Optional[Tensor] = None,
-                          channels_last_out: bool = True, out: Optional[Tuple[Tensor, Tensor]] = None) -> Tuple[Tensor, Tensor]:
+                          channels_last_out: bool = True, out: Optional[Tuple[Tensor, Tensor]] = None,
+                          depth_gate: Optional[DepthGate] = None) -> Tuple[Tensor, Tensor]:
     """Fused ``backproject`` + view mean/count of nerfdet.py:164-176 (and, with ``alpha``, the gating of
-    nerfdet.py:259-261): returns ``(volume (C,X,Y,Z), count (1,X,Y,Z) int64)``.
+    nerfdet.py:259-261): returns ``(volume (C,X,Y,Z), count (1,X,Y,Z) int64)``.  With ``depth_gate`` (:func:`depth_gate` at the
+    features' h x w) only views whose observed depth lies within the band count (nerfdet.py:404-411).
 
     ``features`` is the logical (n_v,C,h,w) map, ideally channels-last in memory.  With
     ``channels_last_out`` the result's memory is (X,Y,Z,C) -- what a channels-last 3D conv wants -- while
@@ -182,10 +273,16 @@ def backproject_aggregate(features: Tensor, points: Tensor, projection: Tensor, 
             buf = torch.empty((c, gx, gy, gz), dtype=torch.float32, device=f.device)
             out, layout = buf, NDET_LAYOUT_CN
     # algorithmic bytes: every feature row once + (C fp32 + int64 count) per voxel
-    trace.span("k_backproject_aggregate", lambda: check(
-        _lib.load().ndet_backproject_aggregate(_ptr(f), n_v, c, h, w, f.stride(0), f.stride(2), _ptr(points), n, _ptr(projection), _ptr(alpha),
-                                               _ptr(buf), layout, _ptr(count), _stream(f)), "backproject_aggregate"),
-        bytes=4 * n_v * c * h * w + (4 * c + 8) * n, kind="hbm")
+    lib = _lib.load()
+    if depth_gate is None:
+        launch = lambda: check(lib.ndet_backproject_aggregate(_ptr(f), n_v, c, h, w, f.stride(0), f.stride(2), _ptr(points), n, _ptr(projection),
+                                                              _ptr(alpha), _ptr(buf), layout, _ptr(count), _stream(f)), "backproject_aggregate")
+    else:
+        g = _gate_arg(depth_gate, n_v, (h, w))
+        launch = lambda: check(lib.ndet_backproject_aggregate_gated(_ptr(f), n_v, c, h, w, f.stride(0), f.stride(2), _ptr(points), n,
+                                                                    _ptr(projection), _ptr(alpha), _ptr(buf), layout, _ptr(count), g, _stream(f)),
+                               "backproject_aggregate_gated")
+    trace.span("k_backproject_aggregate", launch, bytes=4 * n_v * c * h * w + (4 * c + 8) * n, kind="hbm")
     return out, count
 
 
@@ -202,8 +299,9 @@ def density_packed_ok(n_views: int, cm: int, mapped: Optional[Tensor] = None, bi
 
 
 def density_features(mapped: Tensor, bias: Tensor, denorm_images: Tensor, points: Tensor, projection: Tensor,
-                     rgb_projection: Tensor) -> Tensor:
+                     rgb_projection: Tensor, depth_gate: Optional[DepthGate] = None) -> Tensor:
     """(N, 2*(3+cm)) NeRF conditioning rows for the voxel grid; replaces nerfdet.py:234-253.
+    With ``depth_gate`` (maps at the features' h x w and the images' H x W) both projections are depth-gated (nerfdet.py:404-411).
 
     ``mapped``: logical (n_v,cm,h,w) = Linear(C->cm) of the feature map (``feature_2d`` of nerfdet.py:194-197),
     ``bias`` its bias (contributed by views that do not see a voxel), ``denorm_images`` (n_v,3,H,W)."""
@@ -220,12 +318,17 @@ def density_features(mapped: Tensor, bias: Tensor, denorm_images: Tensor, points
     out = torch.empty((n, 2 * (3 + cm)), dtype=torch.float32, device=m.device)
     # algorithmic bytes: images + mapped map read once, 2*(3+cm) floats written per voxel
     lib = _lib.load()
-    fn = lib.ndet_density_features_packed if density_packed_ok(n_v, cm, m, bias) else lib.ndet_density_features
-    trace.span("k_density_features", lambda: check(
-        fn(_ptr(m), n_v, cm, h, w, m.stride(0), m.stride(2), _ptr(bias), _ptr(rgb), hh, ww, rgb.stride(0),
-                                          rgb.stride(1), rgb.stride(2), _ptr(points), n, _ptr(projection), _ptr(rgb_projection), _ptr(out),
-                                          _stream(m)), "density_features"),
-        bytes=4 * (n_v * 3 * hh * ww + n_v * cm * h * w + 2 * (3 + cm) * n), kind="hbm")
+    packed = density_packed_ok(n_v, cm, m, bias)
+    args = (_ptr(m), n_v, cm, h, w, m.stride(0), m.stride(2), _ptr(bias), _ptr(rgb), hh, ww, rgb.stride(0), rgb.stride(1), rgb.stride(2),
+            _ptr(points), n, _ptr(projection), _ptr(rgb_projection), _ptr(out))
+    if depth_gate is None:
+        fn = lib.ndet_density_features_packed if packed else lib.ndet_density_features
+        launch = lambda: check(fn(*args, _stream(m)), "density_features")
+    else:
+        fn = lib.ndet_density_features_packed_gated if packed else lib.ndet_density_features_gated
+        g = _gate_arg(depth_gate, n_v, (h, w), (hh, ww))
+        launch = lambda: check(fn(*args, g, _stream(m)), "density_features_gated")
+    trace.span("k_density_features", launch, bytes=4 * (n_v * 3 * hh * ww + n_v * cm * h * w + 2 * (3 + cm) * n), kind="hbm")
     return out
 
 

@@ -11,6 +11,10 @@ five times; here nothing larger than the inputs and the outputs ever exists:
 
 The order differs from the reference (density first, aggregation last) so that the alpha gating
 costs no extra pass over the (C, N) volume; the arithmetic per element is the reference's.
+
+With a per-view depth map (RGB-D scenes, ``depth=``) one more launch resizes it to the feature map and to
+the image (ops.depth_gate), and K2 and K1 count a view only where the voxel lies within voxel_size[2] of the
+observed surface (nerfdet.py:404-411); everything downstream follows from that validity.
 """
 from __future__ import annotations
 
@@ -54,9 +58,11 @@ def scene_geometry(img_meta: dict, n_voxels, voxel_size, stride: int, device) ->
 
 
 def density_alpha(features: Tensor, denorm_images: Tensor, img_meta: dict, n_voxels, voxel_size, mapping: torch.nn.Module, nerf_mlp,
-                  stride: int = 4, feature_2d: Optional[Tensor] = None, geometry: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+                  stride: int = 4, feature_2d: Optional[Tensor] = None, geometry: Optional[Dict[str, Tensor]] = None,
+                  depth: Optional[Tensor] = None) -> Dict[str, Tensor]:
     """First half of the inference path: mapping GEMM -> K2 -> sigma-MLP -> per-voxel alpha (nerfdet.py:190-197,232-257).
-    Returns everything the aggregation kernel needs (``feat``, ``points``, ``projection``, ``alpha``)."""
+    Returns everything the aggregation kernel needs (``feat``, ``points``, ``projection``, ``alpha``, ``depth_gate``).
+    ``depth``: None, or the scene's (n_v, Hd, Wd) depth maps (float32 / float64, any resolution) that gate every projection."""
     dev = features.device
     h = img_meta["img_shape"][0] // stride
     w = img_meta["img_shape"][1] // stride
@@ -72,10 +78,14 @@ def density_alpha(features: Tensor, denorm_images: Tensor, img_meta: dict, n_vox
         else:
             feature_2d = map_features_2d(feat, lin.weight, lin.bias)
     rgb = denorm_images[:, :, :img_meta["img_shape"][0], :img_meta["img_shape"][1]]
-    out = dict(feat=feat, feature_2d=feature_2d, points=pts, projection=proj, rgb_projection=rgb_proj, rgb=rgb, lin=lin)
+    gate = None
+    if depth is not None:
+        assert depth.dim() == 3 and depth.shape[0] == feat.shape[0], "depth must be the scene's (n_views, H, W) maps (nerfdet.py:136-139)"
+        gate = ops.depth_gate(depth.to(dev, non_blocking=True), voxel_size, (h, w), tuple(img_meta["img_shape"][:2]))
+    out = dict(feat=feat, feature_2d=feature_2d, points=pts, projection=proj, rgb_projection=rgb_proj, rgb=rgb, lin=lin, depth_gate=gate)
     if training:
         return out  # the caller continues under autograd
-    glob = ops.density_features(feature_2d, lin.bias, rgb, pts, proj, rgb_proj)
+    glob = ops.density_features(feature_2d, lin.bias, rgb, pts, proj, rgb_proj, depth_gate=gate)
     if hasattr(nerf_mlp, "hip_trunk_ok") and nerf_mlp.hip_trunk_ok():
         out.update(global_feat=glob, raw_sigma=None, alpha=nerf_mlp.alpha_from_points(pts, glob))
     else:  # other MLP shapes: library GEMMs
@@ -86,28 +96,31 @@ def density_alpha(features: Tensor, denorm_images: Tensor, img_meta: dict, n_vox
 
 def extract_volume(features: Tensor, denorm_images: Tensor, img_meta: dict, n_voxels, voxel_size,
                    mapping: torch.nn.Module, nerf_mlp, stride: int = 4, channels_last_out: bool = True,
-                   feature_2d: Optional[Tensor] = None, geometry: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+                   feature_2d: Optional[Tensor] = None, geometry: Optional[Dict[str, Tensor]] = None,
+                   depth: Optional[Tensor] = None) -> Dict[str, Tensor]:
     """One scene.  ``features`` (n_v,C,Hf,Wf) FPN level 0 (channels-last preferred), ``denorm_images``
     (n_v,3,H,W).  Returns ``volume`` (C,X,Y,Z) = alpha * mean (zero where unseen), ``valid`` (1,X,Y,Z) int64
-    view count, plus ``feature_2d`` (the mapped map, reused by the ray branch) and ``density``."""
-    d = density_alpha(features, denorm_images, img_meta, n_voxels, voxel_size, mapping, nerf_mlp, stride, feature_2d, geometry)
+    view count, plus ``feature_2d`` (the mapped map, reused by the ray branch) and ``density``.
+    ``depth`` (n_v,Hd,Wd), float32 or float64: the depth-gated backprojection of RGB-D scenes (nerfdet.py:404-411)."""
+    d = density_alpha(features, denorm_images, img_meta, n_voxels, voxel_size, mapping, nerf_mlp, stride, feature_2d, geometry, depth)
     if "alpha" not in d:
         return _extract_volume_train(d["feat"], d["rgb"], d["points"], d["projection"], d["rgb_projection"], d["lin"], nerf_mlp,
-                                     d["feature_2d"], channels_last_out)
-    volume, count = ops.backproject_aggregate(d["feat"], d["points"], d["projection"], alpha=d["alpha"], channels_last_out=channels_last_out)
+                                     d["feature_2d"], channels_last_out, d["depth_gate"])
+    volume, count = ops.backproject_aggregate(d["feat"], d["points"], d["projection"], alpha=d["alpha"], channels_last_out=channels_last_out,
+                                              depth_gate=d["depth_gate"])
     return dict(volume=volume, valid=count, feature_2d=d["feature_2d"], global_feat=d["global_feat"], raw_sigma=d["raw_sigma"],
                 alpha=d["alpha"], points=d["points"], projection=d["projection"], rgb_projection=d["rgb_projection"])
 
 
-def _extract_volume_train(feat, rgb, pts, proj, rgb_proj, lin, nerf_mlp, feature_2d, channels_last_out):
+def _extract_volume_train(feat, rgb, pts, proj, rgb_proj, lin, nerf_mlp, feature_2d, channels_last_out, depth_gate=None):
     """Training form: the same kernels under autograd (nerf_det_amd.autograd); gating stays a differentiable
     tensor product so that d(alpha) and d(mean) come out separately (nerfdet.py:257-261)."""
     from .autograd import BackprojectMean, DensityFeatures
-    glob = DensityFeatures.apply(feature_2d, lin.bias, rgb, pts, proj, rgb_proj)
+    glob = DensityFeatures.apply(feature_2d, lin.bias, rgb, pts, proj, rgb_proj, depth_gate)
     rows = torch.cat([ops.posenc_concat(pts, None), glob], dim=1)
     raw_sigma = nerf_mlp.raw_sigma_from_rows(rows)
     alpha = 1 - torch.exp(-F.relu(raw_sigma))
-    mean, count = BackprojectMean.apply(feat, pts, proj, channels_last_out)
+    mean, count = BackprojectMean.apply(feat, pts, proj, channels_last_out, depth_gate)
     volume = alpha.view(1, *mean.shape[1:]) * mean
     volume = torch.where((count == 0), torch.zeros_like(volume), volume)
     return dict(volume=volume, valid=count, feature_2d=feature_2d, global_feat=glob, raw_sigma=raw_sigma, alpha=alpha.reshape(-1),
