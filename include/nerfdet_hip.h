@@ -167,6 +167,53 @@ int ndet_density_features_packed_gated(const float* mapped_nhwc, int n_views, in
                                        const float* points, int N, const float* projection,
                                        const float* rgb_projection, float* global_feat, const NdetDepthGate* gate, void* stream);
 
+/* Streaming scenes: one scene's views arrive in chunks (nerf-det_amd/streaming.py).  The state holds what K1 and K2 keep of the views
+ * seen so far; the finishes turn it into K2's conditioning rows and K1's gated volume at any time and leave it unchanged.
+ *
+ * NdetSceneAccum, one block per call (same style as NdetConvArgs / NdetDepthGate):
+ *   size          sizeof(NdetSceneAccum); any other value is rejected (NDET_E_INVALID).
+ *   N, C, cm      voxels, feature channels (multiple of 4, <= 1024), mapped channels (multiple of 4, <= 128).
+ *   n_views       views accumulated so far (the scene's total); read by the finishes only.
+ *   k1_sum        (N, k1_pitch) fp32: per voxel the running sum of the C-float feature rows of the views that see it, in ascending
+ *                 view order; k1_pitch >= C, a multiple of 4, 16-byte aligned rows.
+ *   k1_count      (N) int32: views that see the voxel (the stride-4 projection, depth-gated when the chunks were).
+ *   k2_sum        (N, k2_pitch) fp32, k2_pitch >= 3 (cm + 4), a multiple of 4: three segments of cm + 4 floats, each laid out
+ *                 [r, g, b, 0, mapped channel 0 .. cm-1]: sum_seen v, sum_seen (v - fill)^2, sum_seen (v - fill), where fill is the
+ *                 Linear's bias (mapped channels) or 0 (colour) and "seen" is the stride-4 map for mapped channels, the image for colour.
+ *   k2_count      (N, 2) int32: views that see the voxel in the stride-4 map / in the stride-1 image.
+ * A zeroed state is an empty scene.  Pitches must fit int32. */
+typedef struct NdetSceneAccum {
+    int32_t size;
+    int32_t N, C, cm;
+    int32_t n_views;
+    float* k1_sum;
+    int64_t k1_pitch;
+    int32_t* k1_count;
+    float* k2_sum;
+    int64_t k2_pitch;
+    int32_t* k2_count;
+} NdetSceneAccum;
+
+/* Add one chunk of n_views views (any number; K2 runs in launches of at most 128) to the state: K1's running sums and count of
+ * nerfdet.py:164-176 without the division, K2's shifted sums and counts of nerfdet.py:234-253 without the finish.  Inputs as in
+ * ndet_backproject_aggregate (features, h x w, pitches) and ndet_density_features_packed (mapped map at the same h x w, bias, rgb,
+ * projections) for the chunk's views; points (3, N).  gate: NULL, or the depth gate of nerfdet.py:404-411 for the chunk's views
+ * (maps at h x w and H x W).  Feeding a scene's views in any chunking leaves the same K1 sums and the same counts as one chunk. */
+int ndet_scene_accumulate(const NdetSceneAccum* s, const float* features_nhwc, int n_views, int h, int w,
+                          int64_t view_pitch, int64_t row_pitch, const float* mapped_nhwc, int64_t mview_pitch,
+                          int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv, int64_t rsc,
+                          int64_t rsy, const float* points, const float* projection, const float* rgb_projection,
+                          const NdetDepthGate* gate, void* stream);
+
+/* K2's finish over the state's s->n_views views (nerfdet.py:234-253): global_feat (N, 2 (3 + cm)) rows [mean_c, cov_c] with the packed
+ * kernel's expressions (mean not zeroed at cnt 0, variance 1e6 at cnt 0, cov = exp(-var)).  bias: the Linear's bias, the state's pivot.
+ * For a state filled by one chunk of <= 128 views the rows equal ndet_density_features_packed's bit for bit. */
+int ndet_scene_density_finish(const NdetSceneAccum* s, const float* bias, float* global_feat, void* stream);
+
+/* K1's epilogue over the state (nerfdet.py:175-176, 259-261): out (N, C) channels-last = alpha * sum / (count + 1e-8), 0 where count
+ * is 0 (alpha NULL: no gating), count (N) int64.  Equals ndet_backproject_aggregate over all the state's views bit for bit. */
+int ndet_scene_volume_finish(const NdetSceneAccum* s, const float* alpha, float* out, int64_t* count, void* stream);
+
 /* A6 (gating only, unfused form). volume = (1-exp(-density)) * mean, 0 where count==0; nerfdet.py:257-261.
  * mean/out in `layout` with C channels. */
 int ndet_alpha_gate(const float* mean, const float* density, const int64_t* count, float* out,

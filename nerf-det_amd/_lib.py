@@ -33,7 +33,13 @@ class NdetDepthGate(ctypes.Structure):   # the depth gate of the *_gated entry p
         ("depth_r", _P), ("r_view_pitch", c_int64), ("r_row_pitch", c_int64), ("band", ctypes.c_double)]
 
 
+class NdetSceneAccum(ctypes.Structure):  # a streaming scene's state: include/nerfdet_hip.h::NdetSceneAccum, size = sizeof(NdetSceneAccum)
+    _fields_ = [(f, ctypes.c_int32) for f in ("size", "N", "C", "cm", "n_views")] + [
+        ("k1_sum", _P), ("k1_pitch", c_int64), ("k1_count", _P), ("k2_sum", _P), ("k2_pitch", c_int64), ("k2_count", _P)]
+
+
 _G = ctypes.POINTER(NdetDepthGate)
+_S = ctypes.POINTER(NdetSceneAccum)
 
 # name -> argtypes; kept in one table so tests can check the .so exports exactly this surface
 SIGNATURES = {
@@ -57,6 +63,10 @@ SIGNATURES = {
                                             c_int64, _P, c_int, _P, _P, _P, _G, _P], c_int),
     "ndet_backproject_aggregate_bwd_gated": ([_P, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, c_int, _P, _P, _G, _P], c_int),
     "ndet_density_features_bwd_gated": ([_P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, _P, c_int, _P, _P, _P, _G, _P], c_int),
+    "ndet_scene_accumulate": ([_S, _P, c_int, c_int, c_int, c_int64, c_int64, _P, c_int64, c_int64, _P, _P, c_int, c_int, c_int64, c_int64, c_int64,
+                               _P, _P, _P, _G, _P], c_int),
+    "ndet_scene_density_finish": ([_S, _P, _P, _P], c_int),
+    "ndet_scene_volume_finish": ([_S, _P, _P, _P, _P], c_int),
     "ndet_alpha_gate": ([_P, _P, _P, _P, c_int, c_int, c_int, _P], c_int),
     "ndet_sigma_to_alpha": ([_P, _P, c_int, _P], c_int),
     "ndet_posenc_concat": ([_P, _P, c_int, c_int, c_int, _P, _P], c_int),

@@ -213,3 +213,213 @@ extern "C" int ndet_density_features_packed_gated(const float* mapped_nhwc, int 
     return density_features_packed_impl("ndet_density_features_packed_gated", mapped_nhwc, n_views, cm, h, w, mview_pitch, mrow_pitch, bias, rgb,
                                         H, W, rsv, rsc, rsy, points, N, projection, rgb_projection, global_feat, gate, stream);
 }
+
+// ------------------------------------------------------------------------------------------
+// Streaming scenes (include/nerfdet_hip.h, NdetSceneAccum): the packed kernel split at its finish.
+//
+// K2-accumulate adds a launch's (<= 128 views) group-reduced sums and counts to the scene's state: the walk's three sums per channel
+// (sum_seen v for the mean, the shifted sums about the fill for the variance) and the two counts the finish needs.  Views that do not see a
+// voxel add nothing; they enter only through n_views in the finish.  K2-finish is the packed kernel's finish over the state, expression for
+// expression: a state filled by one launch gives its rows bit for bit (0 + x = x).  The state is only read.
+// ------------------------------------------------------------------------------------------
+// What a finishing lane (group 0) of a packed K2 wave holds after the walk over the launch's views and the groups' meeting in LDS.
+struct K2Sums {
+    float4 acc, q, s1, fill;   // sum_seen v, sum_seen (v - fill)^2, sum_seen (v - fill); the fill of the lane's channels
+    int cnt, n_mine;           // views seeing the voxel in the stride-4 map / in the lane's own map
+    bool is_rgb;
+    int fq, n;                 // channel quad (-1: the colour lane), voxel
+};
+
+// Phases 1 and 2 of k_density_features_packed below, for its streaming form k_density_accumulate_packed.  Returns false on the lanes that
+// do not finish a voxel (after the workgroup's last barrier).  The one-shot kernel keeps its own copy: inlined through this helper it
+// compiles to another register allocation.
+template <bool DG>
+__device__ __forceinline__ bool k2_packed_sums(int2* s_off, const float* __restrict__ mapped, int n_views, int cm, int h, int w,
+                                               int mview_pitch, int mrow_pitch, const float* __restrict__ bias,
+                                               const float* __restrict__ rgb, int H, int W, int rsv, int rsc, int rsy,
+                                               const float* __restrict__ points, int N, const float* __restrict__ proj,
+                                               const float* __restrict__ rgb_proj, int n_blocks, int nvp, const NdetGateMap& gf,
+                                               const NdetGateMap& gr, K2Sums& res) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lps = (cm >> 2) + 1;
+    const int SPLIT = 64 / lps;
+    const int grp = lane / lps, sub = lane - grp * lps;
+    const int blk = ndet_xcd_remap(blockIdx.x, n_blocks);      // neighbouring voxel blocks hit the same pixels: keep them on one XCD's L2
+    const int n = blk * 4 + wave;                              // this wave's voxel
+    int2* rec = s_off + (size_t)wave * nvp;
+    float4* part = reinterpret_cast<float4*>(s_off + (size_t)4 * nvp) + (size_t)wave * 64 * 3;   // [lane][acc, q, s1]
+    const int rounds = (n_views + 63) >> 6;
+    const bool live = n < N;
+
+    // ---- phase 1: lanes over views, both projections of every (voxel, view) pair once ----
+    unsigned long long mf[DK_ROUNDS], mr[DK_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < DK_ROUNDS; ++r) { mf[r] = 0ull; mr[r] = 0ull; }
+    if (live) {
+        const float px = points[n], py = points[N + n], pz = points[2 * N + n];
+#pragma unroll
+        for (int r = 0; r < DK_ROUNDS; ++r) {
+            if (r < rounds) {
+                const int v = r * 64 + lane;
+                bool okf = false, okr = false;
+                if (v < n_views) {
+                    int xf, yf, xr, yr;
+                    float zf, zr;
+                    okf = ndet_project_z(proj + v * 12, px, py, pz, w, h, xf, yf, zf);
+                    okr = ndet_project_z(rgb_proj + v * 12, px, py, pz, W, H, xr, yr, zr);
+                    if (DG) {   // depth gate of both backproject() calls (nerfdet.py:404-411)
+                        okf = okf && ndet_depth_band(gf, v, xf, yf, zf);
+                        okr = okr && ndet_depth_band(gr, v, xr, yr, zr);
+                    }
+                    rec[v] = make_int2(v * mview_pitch + yf * mrow_pitch + xf * cm, v * rsv + yr * rsy + xr);
+                }
+                mf[r] = __ballot(okf);
+                mr[r] = __ballot(okr);
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 2: lanes over (view group, channel quad) ----
+    const bool on = live && grp < SPLIT;
+    const bool is_rgb = sub == 0;
+    const int fq = sub - 1;
+    float4 fill = make_float4(0.f, 0.f, 0.f, 0.f);            // what a view that does not see the voxel contributes (nerfdet.py:233)
+    if (!is_rgb && on) fill = *reinterpret_cast<const float4*>(bias + 4 * fq);
+    const float* fbase = mapped + 4 * max(fq, 0);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), q = acc, s1 = acc;
+    auto fetch = [&](int idx) -> float4 {
+        const int2 o = rec[idx];
+        if (is_rgb) {
+            const float* p = rgb + o.y;
+            return make_float4(p[0], p[rsc], p[2 * rsc], 0.0f);
+        }
+        return *reinterpret_cast<const float4*>(fbase + o.x);
+    };
+    auto take = [&](const float4& v) {
+        acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z; acc.w = acc.w + v.w;
+        const float dx = v.x - fill.x, dy = v.y - fill.y, dz = v.z - fill.z, dw = v.w - fill.w;
+        q.x = q.x + dx * dx; q.y = q.y + dy * dy; q.z = q.z + dz * dz; q.w = q.w + dw * dw;
+        s1.x = s1.x + dx; s1.y = s1.y + dy; s1.z = s1.z + dz; s1.w = s1.w + dw;
+    };
+    // the views of group g: bits g, g + SPLIT, g + 2 SPLIT, ... of the round's mask
+    unsigned long long stripe = 0ull;
+    for (int b = grp; b < 64; b += SPLIT) stripe |= 1ull << b;
+#pragma unroll
+    for (int r = 0; r < DK_ROUNDS; ++r) {
+        if (r >= rounds) break;
+        unsigned long long m = on ? ((is_rgb ? mr[r] : mf[r]) & stripe) : 0ull;
+        while (__ballot(m != 0ull) != 0ull) {
+            bool hh[8];
+            int bb[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                hh[k] = m != 0ull;
+                bb[k] = hh[k] ? __builtin_ctzll(m) : 0;
+                m = hh[k] ? (m & (m - 1ull)) : 0ull;
+            }
+            float4 vv[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                vv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (hh[k]) vv[k] = fetch(r * 64 + bb[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (hh[k]) take(vv[k]);
+        }
+    }
+    // ---- the groups' partial sums meet in LDS; group 0 finishes the voxel ----
+    part[lane * 3 + 0] = acc;
+    part[lane * 3 + 1] = q;
+    part[lane * 3 + 2] = s1;
+    __syncthreads();
+    if (!(on && grp == 0)) return false;
+    for (int g2 = 1; g2 < SPLIT; ++g2) {
+        const float4 a2 = part[(g2 * lps + sub) * 3 + 0], q2 = part[(g2 * lps + sub) * 3 + 1], s2 = part[(g2 * lps + sub) * 3 + 2];
+        acc.x += a2.x; acc.y += a2.y; acc.z += a2.z; acc.w += a2.w;
+        q.x += q2.x; q.y += q2.y; q.z += q2.z; q.w += q2.w;
+        s1.x += s2.x; s1.y += s2.y; s1.z += s2.z; s1.w += s2.w;
+    }
+    int cnt = 0, n_mine = 0;
+#pragma unroll
+    for (int r = 0; r < DK_ROUNDS; ++r) {
+        cnt += __popcll(mf[r]);
+        n_mine += __popcll(is_rgb ? mr[r] : mf[r]);
+    }
+    res.acc = acc; res.q = q; res.s1 = s1; res.fill = fill;
+    res.cnt = cnt; res.n_mine = n_mine; res.is_rgb = is_rgb; res.fq = fq; res.n = n;
+    return true;
+}
+
+template <bool DG>
+__global__ __launch_bounds__(256) void k_density_accumulate_packed(const float* __restrict__ mapped, int n_views, int cm, int h, int w,
+                                                                   int mview_pitch, int mrow_pitch, const float* __restrict__ bias,
+                                                                   const float* __restrict__ rgb, int H, int W, int rsv, int rsc, int rsy,
+                                                                   const float* __restrict__ points, int N, const float* __restrict__ proj,
+                                                                   const float* __restrict__ rgb_proj, float* __restrict__ sum, int pitch,
+                                                                   int* __restrict__ count, int n_blocks, int nvp, NdetGateMap gf, NdetGateMap gr) {
+    extern __shared__ int2 s_off[];
+    K2Sums r;
+    if (!k2_packed_sums<DG>(s_off, mapped, n_views, cm, h, w, mview_pitch, mrow_pitch, bias, rgb, H, W, rsv, rsc, rsy, points, N, proj, rgb_proj,
+                            n_blocks, nvp, gf, gr, r))
+        return;
+    const int seg = cm + 4;   // [r g b 0 | cm mapped channels] per sum
+    float4* row = reinterpret_cast<float4*>(sum + (int64_t)r.n * pitch + (r.is_rgb ? 0 : 4 + 4 * r.fq));
+    row[0] = ndet_add4(row[0], r.acc);
+    row[seg / 4] = ndet_add4(row[seg / 4], r.q);
+    row[2 * seg / 4] = ndet_add4(row[2 * seg / 4], r.s1);
+    if (r.is_rgb) {
+        int2* c = reinterpret_cast<int2*>(count) + r.n;
+        const int2 c0 = *c;
+        *c = make_int2(c0.x + r.cnt, c0.y + r.n_mine);
+    }
+}
+
+// One thread per (voxel, channel): k_density_features_packed's finish over the state.
+__global__ __launch_bounds__(256) void k_density_finish(const float* __restrict__ sum, int pitch, const int* __restrict__ count,
+                                                        const float* __restrict__ bias, int cm, int N, int n_views, float* __restrict__ out) {
+    const int nc = 3 + cm;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)N * nc) return;
+    const int n = (int)(i / nc), c = (int)(i % nc);
+    const bool is_rgb = c < 3;
+    const int k = is_rgb ? c : c + 1;          // column inside a segment
+    const int seg = cm + 4;
+    const float* row = sum + (int64_t)n * pitch;
+    const float a = row[k], qq = row[seg + k], ss = row[2 * seg + k];
+    const float fl = is_rgb ? 0.0f : bias[c - 3];
+    const int cnt = count[2 * n], n_mine = is_rgb ? count[2 * n + 1] : cnt;
+    const float denom = (float)cnt + 1e-8f;
+    const float nu = (float)(n_views - n_mine), nv = (float)n_views;
+    const float sm = a + nu * fl;
+    const float mean = sm / denom;                        // NOT zeroed at cnt == 0 (nerfdet.py:241)
+    const float dm = mean - fl;
+    float s = qq - 2.0f * dm * ss + nv * (dm * dm);
+    s = fmaxf(s, 0.0f);                                   // a sum of squares: rounding may leave -1 ulp
+    float var = s / denom;
+    if (cnt == 0) var = 1e6f;                             // nerfdet.py:249
+    *reinterpret_cast<float2*>(out + (int64_t)n * 2 * nc + 2 * c) = make_float2(mean, expf(-var));
+}
+
+void ndet_scene_k2_accumulate_launch(const NdetSceneAccum* s, const float* mapped, int n_views, int h, int w, int mview_pitch, int mrow_pitch,
+                                     const float* bias, const float* rgb, int H, int W, int rsv, int rsc, int rsy, const float* points,
+                                     const float* proj, const float* rgb_proj, bool gated, const NdetGateMap& gf, const NdetGateMap& gr,
+                                     hipStream_t stream) {
+    const int nvp = ((n_views + 63) / 64) * 64;
+    const int lds = 4 * nvp * (int)sizeof(int2) + 4 * 64 * 3 * (int)sizeof(float4);
+    const int blocks = (s->N + 3) / 4;
+#define K2A_LAUNCH(DG)                                                                                                                       \
+    hipLaunchKernelGGL((k_density_accumulate_packed<DG>), dim3((unsigned)blocks), dim3(256), lds, stream, mapped, n_views, s->cm, h, w,     \
+                       mview_pitch, mrow_pitch, bias, rgb, H, W, rsv, rsc, rsy, points, s->N, proj, rgb_proj, s->k2_sum, (int)s->k2_pitch, \
+                       s->k2_count, blocks, nvp, gf, gr)
+    if (gated) K2A_LAUNCH(true);
+    else K2A_LAUNCH(false);
+#undef K2A_LAUNCH
+}
+
+void ndet_scene_k2_finish_launch(const NdetSceneAccum* s, const float* bias, float* global_feat, hipStream_t stream) {
+    const int64_t total = (int64_t)s->N * (3 + s->cm);
+    hipLaunchKernelGGL(k_density_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, s->k2_sum, (int)s->k2_pitch, s->k2_count,
+                       bias, s->cm, s->N, s->n_views, global_feat);
+}

@@ -108,6 +108,14 @@ __device__ __forceinline__ bool ndet_depth_band(const NdetGateMap& g, int v, int
 int ndet_gate_prepare(const NdetDepthGate* g, const char* fn, int n_views, int h, int w, int H, int W, bool need_r,
                       NdetGateMap* gf, NdetGateMap* gr);
 
+// Streaming scenes (include/nerfdet_hip.h, NdetSceneAccum): launchers of K2's accumulate (<= 128 views) and finish kernels
+// (density_kernels.hip), called by the entry points in volume_kernels.hip once every argument has been checked.
+void ndet_scene_k2_accumulate_launch(const NdetSceneAccum* s, const float* mapped, int n_views, int h, int w, int mview_pitch, int mrow_pitch,
+                                     const float* bias, const float* rgb, int H, int W, int rsv, int rsc, int rsy, const float* points,
+                                     const float* proj, const float* rgb_proj, bool gated, const NdetGateMap& gf, const NdetGateMap& gr,
+                                     hipStream_t stream);
+void ndet_scene_k2_finish_launch(const NdetSceneAccum* s, const float* bias, float* global_feat, hipStream_t stream);
+
 // Gradient scatter of the backward kernels.  Default: float atomics (global_atomic_add_f32) -- fast, but the ORDER of the adds, and with it the last
 // bits of every sum, changes from run to run.  Deterministic mode (tests: ndet_measurement_knob("deterministic_scatter", 1); the caller then hands
 // a zeroed buffer of int64 in place of the float buffer): every contribution is rounded to a multiple of 2^-40 and added as a 64-bit INTEGER --

@@ -19,7 +19,7 @@ void ndet_set_error(const char* fmt, ...) {
 }
 
 int g_ndet_deterministic_scatter = 0;      // ndet_common.hpp::ndet_scatter_add
-extern "C" int ndet_version(void) { return 109; }
+extern "C" int ndet_version(void) { return 110; }
 extern "C" const char* ndet_last_error(void) { return g_err; }
 
 #define VOX_PER_TILE 16  // one workgroup = 4 waves x 4 voxels = 16 consecutive voxels (one z column at Z=16)
@@ -302,6 +302,78 @@ extern "C" int ndet_backproject_gated(const float* features, int n_views, int C,
 // Nothing of size (n_views, C, N) is ever written: reads = feature rows actually hit,
 // writes = (C + 2) * N * 4 bytes.
 // ------------------------------------------------------------------------------------------
+// K1's view walk for the wave's voxels, phases A and B of k_backproject_aggregate below: adds the feature row of every view that sees a voxel
+// to acc, in ascending view order, and the number of those views to cnt.  Used by the streaming accumulate kernel (k_backproject_accumulate),
+// which starts from the scene's running sums instead of zero.  The one-shot kernel keeps its own copy of the walk: inlined through this
+// helper it compiles to other register allocations (more spills at NCHUNK = 2).
+constexpr int K1_VPW = VOX_PER_TILE / 4;  // voxels per wave, processed together
+template <int NCHUNK, bool DG>
+__device__ __forceinline__ void k1_walk(const float* __restrict__ feat, int n_views, int C, int h, int w, int64_t view_pitch, int row_pitch,
+                                        const float* __restrict__ proj, const float (&px)[K1_VPW], const float (&py)[K1_VPW],
+                                        const float (&pz)[K1_VPW], const bool (&live)[K1_VPW], float4 (&acc)[K1_VPW][NCHUNK],
+                                        int (&cnt)[K1_VPW], const NdetGateMap& dgate, int lane) {
+    constexpr int VPW = K1_VPW;
+    const int c4 = C >> 2;
+    for (int r0 = 0; r0 < n_views; r0 += 64) {
+        // phase A: lanes over views, one camera matrix per lane, all voxels of the wave projected back to back
+        const int v = r0 + lane;
+        float P[12];
+        {
+            const float4* pm = reinterpret_cast<const float4*>(proj + (v < n_views ? v : 0) * 12);
+            const float4 a = pm[0], b = pm[1], c = pm[2];
+            P[0] = a.x; P[1] = a.y; P[2] = a.z; P[3] = a.w;
+            P[4] = b.x; P[5] = b.y; P[6] = b.z; P[7] = b.w;
+            P[8] = c.x; P[9] = c.y; P[10] = c.z; P[11] = c.w;
+        }
+        int off[VPW];
+        unsigned long long mask[VPW];
+#pragma unroll
+        for (int j = 0; j < VPW; ++j) {
+            int xi = 0, yi = 0;
+            float z;
+            bool ok = (v < n_views) && live[j] && ndet_project_z(P, px[j], py[j], pz[j], w, h, xi, yi, z);
+            // depth gate: the lane's own view's depth value, before the ballot -- a gated-out view never costs a row gather
+            if (DG) ok = ok && ndet_depth_band(dgate, v, xi, yi, z);
+            off[j] = yi * row_pitch + xi * C;  // floats inside one view (< 2^31, checked on the host)
+            mask[j] = __ballot(ok);
+            cnt[j] += __popcll(mask[j]);
+        }
+        // phase B: walk the set bits; GATHER_BATCH independent row loads in flight
+        const float* vbase = feat + (int64_t)r0 * view_pitch;
+#pragma unroll
+        for (int j = 0; j < VPW; ++j) {
+            unsigned long long m = mask[j];
+            int b = 0;
+            while (m) {
+                float4 t[GATHER_BATCH][NCHUNK];
+                bool has[GATHER_BATCH];
+#pragma unroll
+                for (int k = 0; k < GATHER_BATCH; ++k) {
+                    has[k] = (m != 0ull);
+                    if (has[k]) {
+                        b = __builtin_ctzll(m);
+                        m &= (m - 1ull);
+                    }  // else: re-read the previous row (L1 hit), discarded below
+                    const int o = __builtin_amdgcn_readlane(off[j], b);
+                    const float4* p = reinterpret_cast<const float4*>(vbase + (int64_t)b * view_pitch + o);
+#pragma unroll
+                    for (int q = 0; q < NCHUNK; ++q) {
+                        const int ci = lane + q * 64;
+                        t[k][q] = (ci < c4) ? p[ci] : make_float4(0.f, 0.f, 0.f, 0.f);
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < GATHER_BATCH; ++k) {
+                    if (has[k]) {
+#pragma unroll
+                        for (int q = 0; q < NCHUNK; ++q) acc[j][q] = ndet_add4(acc[j][q], t[k][q]);
+                    }
+                }
+            }
+        }
+    }
+}
+
 // The depth-gated instantiations (DG) hold the gate's map, pitches and band on top: at K1_MIN_WAVES they spill, one wave fewer per SIMD
 // leaves them spill-free.
 template <int NCHUNK, bool GATE, int LAYOUT, bool DG>
@@ -520,6 +592,192 @@ extern "C" int ndet_backproject_aggregate_gated(const float* features_nhwc, int 
     NDET_REQUIRE(gate, NDET_E_INVALID, "ndet_backproject_aggregate_gated: null depth gate");
     return backproject_aggregate_impl("ndet_backproject_aggregate_gated", features_nhwc, n_views, C, h, w, view_pitch, row_pitch, points, N,
                                       projection, alpha, out, out_layout, count, gate, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// Streaming scenes (include/nerfdet_hip.h, NdetSceneAccum): K1 split at its division.
+//
+// K1-accumulate is k_backproject_aggregate's walk started from the scene's running sums (channels-last fp32) and count instead of zero,
+// stored back without the division.  The walk adds rows in ascending view order, so a scene fed in chunks holds the very sums one launch
+// over all its views forms.  K1-finish is K1's epilogue over the state; the state is only read.
+// ------------------------------------------------------------------------------------------
+template <int NCHUNK, bool DG>
+__global__ __launch_bounds__(256, DG ? K1_MIN_WAVES - 1 : K1_MIN_WAVES) void k_backproject_accumulate(
+    const float* __restrict__ feat, int n_views, int C, int h, int w, int64_t view_pitch, int row_pitch,
+    const float* __restrict__ points, int N, const float* __restrict__ proj, float* __restrict__ sum, int pitch,
+    int* __restrict__ count, int n_tiles, NdetGateMap dgate) {
+    constexpr int VPW = K1_VPW;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int tile = ndet_xcd_remap(blockIdx.x, n_tiles);
+    const int n0 = tile * VOX_PER_TILE;
+    const int c4 = C >> 2;
+    float px[VPW], py[VPW], pz[VPW];
+    bool live[VPW];
+    float4 acc[VPW][NCHUNK];
+    int cnt[VPW];
+#pragma unroll
+    for (int j = 0; j < VPW; ++j) {
+        const int n = n0 + j * 4 + wave;
+        live[j] = n < N;  // wave-uniform
+        const int nn = live[j] ? n : 0;
+        px[j] = points[nn];
+        py[j] = points[N + nn];
+        pz[j] = points[2 * N + nn];
+        cnt[j] = live[j] ? count[nn] : 0;
+#pragma unroll
+        for (int q = 0; q < NCHUNK; ++q) {
+            const int ci = lane + q * 64;
+            acc[j][q] = (live[j] && ci < c4) ? *reinterpret_cast<const float4*>(sum + (int64_t)nn * pitch + ci * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    k1_walk<NCHUNK, DG>(feat, n_views, C, h, w, view_pitch, row_pitch, proj, px, py, pz, live, acc, cnt, dgate, lane);
+#pragma unroll
+    for (int j = 0; j < VPW; ++j) {
+        if (!live[j]) continue;
+        const int n = n0 + j * 4 + wave;
+#pragma unroll
+        for (int q = 0; q < NCHUNK; ++q) {
+            const int ci = lane + q * 64;
+            if (ci < c4) *reinterpret_cast<float4*>(sum + (int64_t)n * pitch + ci * 4) = acc[j][q];
+        }
+        if (lane == 0) count[n] = cnt[j];
+    }
+}
+
+// One thread per (voxel, channel quad): K1's epilogue, expression for expression (k_backproject_aggregate above).
+__global__ __launch_bounds__(256) void k_volume_finish(const float* __restrict__ sum, int pitch, const int* __restrict__ count,
+                                                       const float* __restrict__ alpha, int C, int N, float* __restrict__ out,
+                                                       int64_t* __restrict__ out_count) {
+    const int c4 = C >> 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)N * c4) return;
+    const int n = (int)(i / c4), q = (int)(i % c4);
+    const int cnt = count[n];
+    const float denom = (float)cnt + 1e-8f;
+    const float4 s = *reinterpret_cast<const float4*>(sum + (int64_t)n * pitch + q * 4);
+    float4 mean;
+    mean.x = s.x / denom;
+    mean.y = s.y / denom;
+    mean.z = s.z / denom;
+    mean.w = s.w / denom;
+    if (alpha) {
+        const float a = alpha[n];
+        mean.x = a * mean.x;
+        mean.y = a * mean.y;
+        mean.z = a * mean.z;
+        mean.w = a * mean.w;
+    }
+    if (cnt == 0) mean = make_float4(0.f, 0.f, 0.f, 0.f);
+    *reinterpret_cast<float4*>(out + (int64_t)n * C + q * 4) = mean;
+    if (q == 0) out_count[n] = (int64_t)cnt;
+}
+
+// The block's own fields (pointers, sizes, pitches, alignment), checked before any launch.
+static int scene_check(const NdetSceneAccum* s, const char* fn) {
+    NDET_REQUIRE(s, NDET_E_INVALID, "%s: null scene state", fn);
+    NDET_REQUIRE(s->size == (int32_t)sizeof(NdetSceneAccum), NDET_E_INVALID, "%s: NdetSceneAccum.size %d != %d (caller built against another layout)",
+                 fn, s->size, (int)sizeof(NdetSceneAccum));
+    NDET_REQUIRE(s->k1_sum && s->k1_count && s->k2_sum && s->k2_count, NDET_E_INVALID, "%s: null pointer in the scene state", fn);
+    NDET_REQUIRE(s->N > 0 && s->C > 0 && s->cm > 0 && s->n_views >= 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
+    NDET_REQUIRE(s->C % 4 == 0 && s->C <= 1024, NDET_E_UNSUPPORTED, "%s: C=%d must be a multiple of 4 and <= 1024", fn, s->C);
+    NDET_REQUIRE(s->cm % 4 == 0 && s->cm <= 128, NDET_E_UNSUPPORTED, "%s: cm=%d must be a multiple of 4 and <= 128", fn, s->cm);
+    NDET_REQUIRE(s->k1_pitch >= s->C && s->k2_pitch >= 3 * (s->cm + 4), NDET_E_INVALID, "%s: state pitches smaller than a row", fn);
+    NDET_REQUIRE(s->k1_pitch < ((int64_t)1 << 31) && s->k2_pitch < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: state pitches exceed int32", fn);
+    NDET_REQUIRE(s->k1_pitch % 4 == 0 && s->k2_pitch % 4 == 0 && (((uintptr_t)s->k1_sum | (uintptr_t)s->k2_sum) & 15) == 0 &&
+                     (((uintptr_t)s->k1_count & 3) | ((uintptr_t)s->k2_count & 7)) == 0,
+                 NDET_E_UNSUPPORTED, "%s: state rows must be 16-byte aligned", fn);
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_accumulate(const NdetSceneAccum* s, const float* features_nhwc, int n_views, int h, int w,
+                                     int64_t view_pitch, int64_t row_pitch, const float* mapped_nhwc, int64_t mview_pitch,
+                                     int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv, int64_t rsc,
+                                     int64_t rsy, const float* points, const float* projection, const float* rgb_projection,
+                                     const NdetDepthGate* gate, void* stream) {
+    const char* fn = "ndet_scene_accumulate";
+    int rc = scene_check(s, fn);
+    if (rc != NDET_OK) return rc;
+    const int N = s->N, C = s->C, cm = s->cm;
+    NDET_REQUIRE(features_nhwc && mapped_nhwc && bias && rgb && points && projection && rgb_projection, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(n_views > 0 && h > 0 && w > 0 && H > 0 && W > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
+    NDET_REQUIRE(s->n_views <= 0x7fffffff - n_views, NDET_E_UNSUPPORTED, "%s: view count overflows int32", fn);
+    // K1's inputs (backproject_aggregate_impl)
+    NDET_REQUIRE(row_pitch >= (int64_t)w * C && view_pitch >= (int64_t)h * row_pitch, NDET_E_INVALID, "%s: feature pitches smaller than the map", fn);
+    NDET_REQUIRE(row_pitch % 4 == 0 && view_pitch % 4 == 0 && ((uintptr_t)features_nhwc & 15) == 0, NDET_E_UNSUPPORTED,
+                 "%s: feature rows must be 16-byte aligned", fn);
+    NDET_REQUIRE((int64_t)h * row_pitch < (int64_t)1 << 31, NDET_E_UNSUPPORTED, "%s: one view exceeds 2^31 floats", fn);
+    // K2's inputs (density_features_packed_impl), per launch of at most 128 views
+    const int per = n_views < 128 ? n_views : 128;
+    NDET_REQUIRE(mrow_pitch >= (int64_t)w * cm && mview_pitch >= (int64_t)h * mrow_pitch && rsy >= W && rsc >= 0 && rsv >= 0, NDET_E_INVALID,
+                 "%s: mapped / image pitches smaller than the maps", fn);
+    NDET_REQUIRE((int64_t)per * mview_pitch < ((int64_t)1 << 31) && (int64_t)per * rsv + 3 * rsc < ((int64_t)1 << 31), NDET_E_UNSUPPORTED,
+                 "%s: a launch's source tensor exceeds 2^31 floats", fn);
+    NDET_REQUIRE(mview_pitch % 4 == 0 && mrow_pitch % 4 == 0 && (((uintptr_t)mapped_nhwc | (uintptr_t)bias) & 15) == 0, NDET_E_UNSUPPORTED,
+                 "%s: mapped features / bias must keep channel quads 16-byte aligned", fn);
+    NdetGateMap gf = {}, gr = {};
+    if (gate) {
+        rc = ndet_gate_prepare(gate, fn, n_views, h, w, H, W, true, &gf, &gr);
+        if (rc != NDET_OK) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int n_tiles = (N + VOX_PER_TILE - 1) / VOX_PER_TILE;
+    const int rp = (int)row_pitch, k1p = (int)s->k1_pitch;
+#define K1A_LAUNCH(NC, DG)                                                                                                                \
+    hipLaunchKernelGGL((k_backproject_accumulate<NC, DG>), dim3(n_tiles), dim3(256), 0, st, features_nhwc, n_views, C, h, w, view_pitch, rp, \
+                       points, N, projection, s->k1_sum, k1p, s->k1_count, n_tiles, gf)
+#define K1A_CHUNKS(DG)                \
+    if (C <= 256) K1A_LAUNCH(1, DG);  \
+    else if (C <= 512) K1A_LAUNCH(2, DG); \
+    else K1A_LAUNCH(4, DG)
+    if (gate) {
+        K1A_CHUNKS(true);
+    } else {
+        K1A_CHUNKS(false);
+    }
+#undef K1A_CHUNKS
+#undef K1A_LAUNCH
+    NDET_CHECK_LAUNCH(fn);
+    for (int v0 = 0; v0 < n_views; v0 += 128) {
+        const int nv = n_views - v0 < 128 ? n_views - v0 : 128;
+        NdetGateMap gf1 = gf, gr1 = gr;
+        if (gate) {
+            const size_t es = gf.f64 ? sizeof(double) : sizeof(float);
+            gf1.map = (const char*)gf.map + (size_t)v0 * gf.view_pitch * es;
+            gr1.map = (const char*)gr.map + (size_t)v0 * gr.view_pitch * es;
+        }
+        ndet_scene_k2_accumulate_launch(s, mapped_nhwc + (int64_t)v0 * mview_pitch, nv, h, w, (int)mview_pitch, (int)mrow_pitch, bias,
+                                        rgb + (int64_t)v0 * rsv, H, W, (int)rsv, (int)rsc, (int)rsy, points, projection + (int64_t)v0 * 12,
+                                        rgb_projection + (int64_t)v0 * 12, gate != nullptr, gf1, gr1, st);
+        NDET_CHECK_LAUNCH(fn);
+    }
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_density_finish(const NdetSceneAccum* s, const float* bias, float* global_feat, void* stream) {
+    const char* fn = "ndet_scene_density_finish";
+    const int rc = scene_check(s, fn);
+    if (rc != NDET_OK) return rc;
+    NDET_REQUIRE(bias && global_feat, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(((uintptr_t)global_feat & 7) == 0, NDET_E_UNSUPPORTED, "%s: global_feat must be 8-byte aligned", fn);
+    NDET_REQUIRE(((int64_t)s->N * (s->cm + 3) + 255) / 256 < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
+    ndet_scene_k2_finish_launch(s, bias, global_feat, (hipStream_t)stream);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_volume_finish(const NdetSceneAccum* s, const float* alpha, float* out, int64_t* count, void* stream) {
+    const char* fn = "ndet_scene_volume_finish";
+    const int rc = scene_check(s, fn);
+    if (rc != NDET_OK) return rc;
+    NDET_REQUIRE(out && count, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(((uintptr_t)out & 15) == 0, NDET_E_UNSUPPORTED, "%s: out must be 16-byte aligned", fn);
+    const int64_t blocks = ((int64_t)s->N * (s->C / 4) + 255) / 256;
+    NDET_REQUIRE(blocks < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
+    hipLaunchKernelGGL(k_volume_finish, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, s->k1_sum, (int)s->k1_pitch, s->k1_count,
+                       alpha, s->C, s->N, out, count);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
 }
 
 // ------------------------------------------------------------------------------------------

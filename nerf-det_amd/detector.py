@@ -234,6 +234,13 @@ class nerfdet(BaseDetector):
             from .rays import rendering_metrics
             assert rgb_preds and rgb_preds[-1] is not None, "evaluate_nerf needs render_testing=True (render_ray.py:452-517)"
             self.render_metrics = rendering_metrics(rgb_preds[-1])
+        return self._detect_tail(x, valids, img_metas, defer, guarded, img.device,
+                                 lambda: self._repeat_exact(img, img_metas, depth, ray_batch, evaluate_nerf))
+
+    def _detect_tail(self, x, valids, img_metas, defer, guarded, device, repeat):
+        """neck_3d outputs -> detections (nerfdet.py:292-311), shared by simple_test and streaming.SceneStream.detect: the fused head with its
+        single device-to-host copy where it applies.  ``guarded``: a set range-guard word calls ``repeat()`` for the answer instead."""
+        from . import conv3d
         for m in img_metas:
             m.setdefault("box_type_3d", DepthInstance3DBoxes)
         if hasattr(self.bbox_head, "can_fuse") and self.bbox_head.can_fuse(x) and len(img_metas) == 1:
@@ -249,14 +256,20 @@ class nerfdet(BaseDetector):
             def finish():
                 got = pending()
                 if guarded and getattr(got, "range_guard", False):
-                    return self._repeat_exact(img, img_metas, depth, ray_batch, evaluate_nerf)
+                    return repeat()
                 return [bbox3d2result(b, s, l) for b, s, l in got]
             return finish
-        if guarded and (getattr(bbox_list, "range_guard", False) or (not hasattr(bbox_list, "range_guard") and conv3d.guard_tripped(img.device))):
-            return self._repeat_exact(img, img_metas, depth, ray_batch, evaluate_nerf)
+        if guarded and (getattr(bbox_list, "range_guard", False) or (not hasattr(bbox_list, "range_guard") and conv3d.guard_tripped(device))):
+            return repeat()
         res = [bbox3d2result(b, s, l) for b, s, l in bbox_list]
         trace.mark("head_nms")
         return res
+
+    def begin_scene(self, img_meta):
+        """A :class:`~nerfdet_amd.streaming.SceneStream` for one scene whose views arrive in chunks: ``add_views`` runs the backbone on a
+        chunk and folds it into the scene's running sums, ``detect`` returns what :meth:`simple_test` returns for the views so far."""
+        from .streaming import SceneStream
+        return SceneStream(self, img_meta)
 
     def forward_test_async(self, img, img_metas, **kwargs):
         """Serving form of :meth:`forward_test`: every launch of the scene is queued on the current stream and a ``finish()`` callable is

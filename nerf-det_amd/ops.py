@@ -19,7 +19,7 @@ import torch
 
 from . import _lib, trace
 from .hostmath import matmul_fma_chain
-from ._lib import NDET_LAYOUT_CN, NDET_LAYOUT_NC, NdetDepthGate, check, float3
+from ._lib import NDET_LAYOUT_CN, NDET_LAYOUT_NC, NdetDepthGate, NdetSceneAccum, check, float3
 from ._lib import raw_stream
 
 Tensor = torch.Tensor
@@ -330,6 +330,106 @@ def density_features(mapped: Tensor, bias: Tensor, denorm_images: Tensor, points
         launch = lambda: check(fn(*args, g, _stream(m)), "density_features_gated")
     trace.span("k_density_features", launch, bytes=4 * (n_v * 3 * hh * ww + n_v * cm * h * w + 2 * (3 + cm) * n), kind="hbm")
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# Streaming scenes: K1 and K2 split into accumulate / finish (include/nerfdet_hip.h, NdetSceneAccum)
+# --------------------------------------------------------------------------------------------
+class SceneState:
+    """One scene's running sums on the device, views added chunk by chunk (:func:`scene_accumulate`) and finished at any time
+    (:func:`density_finish`, :func:`volume_finish`).  Per voxel: K1's C-float feature-row sum and view count, K2's three sums of the 3 + cm
+    channels (sum v, sum (v - fill)^2, sum (v - fill), quad-padded rows) and its two view counts -- 4 C + 12 (cm + 4) + 12 bytes."""
+
+    def __init__(self, n_voxels, c: int, cm: int, device):
+        self.grid = tuple(int(v) for v in n_voxels)
+        n = self.grid[0] * self.grid[1] * self.grid[2]
+        assert c % 4 == 0 and cm % 4 == 0, f"streaming needs C and cm in multiples of 4 (got {c}, {cm})"
+        self.c, self.cm, self.n_views = int(c), int(cm), 0
+        self.k1_sum = torch.zeros((n, c), dtype=torch.float32, device=device)
+        self.k1_count = torch.zeros((n,), dtype=torch.int32, device=device)
+        self.k2_sum = torch.zeros((n, 3 * (cm + 4)), dtype=torch.float32, device=device)
+        self.k2_count = torch.zeros((n, 2), dtype=torch.int32, device=device)
+
+    @property
+    def n_voxels(self) -> int:
+        return self.k1_sum.shape[0]
+
+    def reset(self) -> None:
+        for t in (self.k1_sum, self.k1_count, self.k2_sum, self.k2_count):
+            t.zero_()
+        self.n_views = 0
+
+    def block(self) -> NdetSceneAccum:
+        """The C ABI's NdetSceneAccum for this state (the tensors stay owned by ``self``)."""
+        b = NdetSceneAccum()
+        b.size = ctypes.sizeof(NdetSceneAccum)
+        b.N, b.C, b.cm, b.n_views = self.n_voxels, self.c, self.cm, self.n_views
+        b.k1_sum, b.k1_pitch, b.k1_count = self.k1_sum.data_ptr(), self.k1_sum.stride(0), self.k1_count.data_ptr()
+        b.k2_sum, b.k2_pitch, b.k2_count = self.k2_sum.data_ptr(), self.k2_sum.stride(0), self.k2_count.data_ptr()
+        return b
+
+
+def scene_accumulate(state: SceneState, features: Tensor, mapped: Tensor, bias: Tensor, denorm_images: Tensor, points: Tensor,
+                     projection: Tensor, rgb_projection: Tensor, depth_gate: Optional[DepthGate] = None) -> None:
+    """Add one chunk of k views to ``state``: K1's view sum and count of nerfdet.py:164-176 and K2's sums of nerfdet.py:234-253, both without
+    their finish.  Arguments as :func:`backproject_aggregate` (``features`` (k,C,h,w)) and :func:`density_features` (``mapped`` (k,cm,h,w),
+    ``bias``, ``denorm_images`` (k,3,H,W)) for the chunk's views; ``depth_gate`` for the chunk's views (nerfdet.py:404-411).  K1's sums hold
+    the same bits whatever the chunking; K2 runs in launches of at most 128 views."""
+    _need_gpu(features, mapped, bias, denorm_images, points, projection, rgb_projection)
+    f = to_channels_last(features)
+    m = to_channels_last(mapped)
+    n_v, c, h, w = f.shape
+    assert m.shape[0] == n_v and m.shape[2:] == f.shape[2:], f"mapped map {tuple(m.shape)} for features {tuple(f.shape)}"
+    assert (c, m.shape[1]) == (state.c, state.cm), f"state for C={state.c}, cm={state.cm}; chunk has {c}, {m.shape[1]}"
+    if not density_packed_ok(0, state.cm, m):       # the packed walk's channel quads need 16-byte aligned rows
+        m = to_channels_last(m.contiguous())
+    rgb = denorm_images if denorm_images.dtype == torch.float32 else denorm_images.float()
+    assert rgb.shape[0] == n_v and rgb.shape[1] == 3
+    if rgb.stride(3) != 1:
+        rgb = rgb.contiguous()
+    hh, ww = rgb.shape[2:]
+    assert points.shape[-3:] == state.grid, f"points {tuple(points.shape)} for a {state.grid} state"
+    points, projection, rgb_projection, bias = _f32c(points), _f32c(projection), _f32c(rgb_projection), _f32c(bias)
+    assert projection.shape == (n_v, 3, 4) and rgb_projection.shape == (n_v, 3, 4)
+    g = None if depth_gate is None else _gate_arg(depth_gate, n_v, (h, w), (hh, ww))
+    blk = state.block()
+    trace.span("k_scene_accumulate", lambda: check(_lib.load().ndet_scene_accumulate(
+        ctypes.byref(blk), _ptr(f), n_v, h, w, f.stride(0), f.stride(2), _ptr(m), m.stride(0), m.stride(2), _ptr(bias), _ptr(rgb), hh, ww,
+        rgb.stride(0), rgb.stride(1), rgb.stride(2), _ptr(points), _ptr(projection), _ptr(rgb_projection), g, _stream(f)), "scene_accumulate"),
+        bytes=4 * (n_v * (c * h * w + state.cm * h * w + 3 * hh * ww)) + 2 * (state.k1_sum.numel() + state.k2_sum.numel()) * 4, kind="hbm")
+    state.n_views += n_v
+
+
+def density_finish(state: SceneState, bias: Tensor) -> Tensor:
+    """(N, 2*(3+cm)) conditioning rows over every view in ``state`` (nerfdet.py:234-253), the packed K2's finish; ``state`` is not changed.
+    A state filled by one chunk of at most 128 views gives :func:`density_features`'s rows bit for bit."""
+    _need_gpu(bias)
+    assert state.n_views > 0, "the scene has no views yet"
+    bias = _f32c(bias)
+    assert bias.numel() == state.cm
+    out = torch.empty((state.n_voxels, 2 * (3 + state.cm)), dtype=torch.float32, device=state.k1_sum.device)
+    blk = state.block()
+    trace.span("k_density_finish", lambda: check(_lib.load().ndet_scene_density_finish(ctypes.byref(blk), _ptr(bias), _ptr(out), _stream(out)),
+                                                 "scene_density_finish"), bytes=4 * (state.k2_sum.numel() + out.numel()), kind="hbm")
+    return out
+
+
+def volume_finish(state: SceneState, alpha: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """K1's epilogue over ``state`` (nerfdet.py:175-176 and, with ``alpha``, 259-261): ``(volume (C,X,Y,Z) with (X,Y,Z,C) memory, count
+    (1,X,Y,Z) int64)``, bit for bit what :func:`backproject_aggregate` returns over all the state's views; ``state`` is not changed."""
+    _need_gpu(alpha)
+    dev = state.k1_sum.device
+    if alpha is not None:
+        alpha = _f32c(alpha).reshape(-1)
+        assert alpha.numel() == state.n_voxels
+    gx, gy, gz = state.grid
+    buf = torch.empty((gx, gy, gz, state.c), dtype=torch.float32, device=dev)
+    count = torch.empty((1, gx, gy, gz), dtype=torch.int64, device=dev)
+    blk = state.block()
+    trace.span("k_volume_finish", lambda: check(_lib.load().ndet_scene_volume_finish(ctypes.byref(blk), _ptr(alpha), _ptr(buf), _ptr(count),
+                                                                                     _stream(buf)), "scene_volume_finish"),
+               bytes=8 * state.k1_sum.numel() + 12 * state.n_voxels, kind="hbm")
+    return buf.permute(3, 0, 1, 2), count
 
 
 # --------------------------------------------------------------------------------------------

@@ -1,0 +1,150 @@
+"""Streaming scene inference: a scene's views arrive in chunks, detections are available after any of them.
+
+``nerfdet.begin_scene(img_meta)`` returns a :class:`SceneStream`.  ``add_views`` runs the backbone and FPN on a chunk of views (the FPN's
+output convolution producing the mapped map on the way, as ``extract_feat`` does) and folds the chunk into the scene's running sums
+(ops.scene_accumulate); the chunk's feature maps are dropped right after.  ``detect`` finishes the sums into the reference's conditioning
+rows and gated volume (nerfdet.py:164-176, 234-261) and runs neck_3d and the head, exactly as ``simple_test``'s tail does.  The backbone
+runs once per view, when the view arrives, and memory is the state's (ops.SceneState), whatever the number of views.
+
+K1's sums and every count are the same bits whatever the chunking; K2's sums add per chunk, so its rows differ from the one-shot kernel's by
+rounding only.  A single chunk reproduces ``simple_test`` bit for bit.  Inference only: no training / autograd, no ray branch
+(render_testing needs every view's map), no hipGraph replay, one scene per stream, views cannot be removed.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import conv3d, ops
+from .volume import map_features_2d, map_features_2d_hip
+
+Tensor = torch.Tensor
+
+
+class SceneStream:
+    """One scene of a :class:`~nerfdet_amd.detector.nerfdet` detector, filled chunk by chunk (:meth:`add_views`) and detected at any time
+    (:meth:`detect`).  ``img_meta`` fixes the scene: ``lidar2img.intrinsic``, ``lidar2img.origin``, ``img_shape`` and ``ori_shape``; its
+    extrinsics are not used (each chunk brings its own)."""
+
+    def __init__(self, det, img_meta: dict):
+        if det.training:
+            raise RuntimeError("SceneStream is inference only: call det.eval() first")
+        if det.render_testing:
+            raise NotImplementedError("SceneStream does not render rays (render_testing needs every view's feature map)")
+        self.det = det
+        self.meta = img_meta
+        self.device = next(det.parameters()).device
+        lin = det.mapping[0]
+        self._lin = lin
+        self.state = ops.SceneState(det.n_voxels, lin.in_features, lin.out_features, self.device)
+        self.points = ops.get_points(det.n_voxels, det.voxel_size, img_meta["lidar2img"]["origin"], self.device)
+
+    @property
+    def n_views(self) -> int:
+        return self.state.n_views
+
+    def reset(self) -> None:
+        """Forget every view: the scene starts empty again."""
+        self.state.reset()
+
+    def _check_meta(self, img_meta: dict, k: int) -> None:
+        a, b = self.meta, img_meta
+        for key in ("intrinsic", "origin"):
+            if not np.array_equal(np.asarray(a["lidar2img"][key], dtype=np.float64), np.asarray(b["lidar2img"][key], dtype=np.float64)):
+                raise ValueError(f"add_views: the chunk's lidar2img.{key} differs from the scene's")
+        for key in ("img_shape", "ori_shape"):
+            if tuple(a[key]) != tuple(b[key]):
+                raise ValueError(f"add_views: the chunk's {key} {tuple(b[key])} differs from the scene's {tuple(a[key])}")
+        if len(b["lidar2img"]["extrinsic"]) != k:
+            raise ValueError(f"add_views: {len(b['lidar2img']['extrinsic'])} extrinsics for {k} views")
+
+    def _features(self, img: Tensor):
+        x, _, stride = self.det.extract_2d(img)
+        return x, getattr(x, "_ndet_feature_2d", None), stride
+
+    def add_views(self, img: Tensor, denorm_images: Tensor, img_meta: dict, depth: Optional[Tensor] = None) -> None:
+        """Fold k >= 1 views into the scene.  ``img``, ``denorm_images`` (1, k, 3, H, W); ``img_meta`` the chunk's (its ``extrinsic`` list has
+        k entries; the rest must equal the scene's, else ValueError); ``depth`` None or (1, k, Hd, Wd) float32 / float64: the chunk's views are
+        depth-gated as by ``simple_test(depth=)`` (nerfdet.py:404-411).
+
+        Range guard of the fp16-pair arithmetic: the guard word is cleared before the chunk's backbone and read back before the chunk enters
+        the state -- one 4-byte device-to-host read (a synchronisation) per chunk.  A tripped chunk is redone on bf16x3 first
+        (``conv3d.guard_trips`` counts it), so no tripped chunk reaches the state."""
+        if img.dim() != 5 or img.shape[0] != 1:
+            raise ValueError(f"add_views takes one scene's chunk, (1, k, 3, H, W); got {tuple(img.shape)}")
+        k = img.shape[1]
+        if k < 1 or denorm_images.shape[:2] != img.shape[:2]:
+            raise ValueError(f"add_views: img {tuple(img.shape)} and denorm_images {tuple(denorm_images.shape)} must hold the same k >= 1 views")
+        if depth is not None and (depth.dim() != 4 or depth.shape[:2] != img.shape[:2]):
+            raise ValueError(f"add_views: depth must be (1, k, Hd, Wd), got {tuple(depth.shape)}")
+        self._check_meta(img_meta, k)
+        if self.det.training:
+            raise RuntimeError("SceneStream is inference only: call det.eval() first")
+        with torch.no_grad():
+            guarded = conv3d.ARITHMETIC == "f16x2" and img.is_cuda
+            if guarded:
+                conv3d.guard_begin(img.device)
+            x, f2d, stride = self._features(img)
+            if guarded and conv3d.guard_tripped(img.device):
+                conv3d.guard_trips += 1
+                prev = conv3d.set_arithmetic("bf16x3")
+                try:
+                    x, f2d, stride = self._features(img)
+                finally:
+                    conv3d.set_arithmetic(prev)
+            hh, ww = self.meta["img_shape"][0], self.meta["img_shape"][1]
+            h, w = hh // stride, ww // stride
+            feat = ops.to_channels_last(x)[:, :, :h, :w]
+            lin = self._lin
+            if f2d is not None:
+                mapped = f2d[:, :, :h, :w]
+            elif lin.in_features % 32 == 0:
+                mapped = map_features_2d_hip(feat, lin)
+            else:
+                mapped = map_features_2d(feat, lin.weight, lin.bias)
+            rgb = denorm_images[0][:, :, :hh, :ww]
+            gate = None
+            if depth is not None:
+                gate = ops.depth_gate(depth[0].to(self.device, non_blocking=True), self.det.voxel_size, (h, w), (hh, ww))
+            proj = ops.compute_projection(img_meta, stride, self.device)
+            rgb_proj = ops.compute_projection(img_meta, 1, self.device)
+            ops.scene_accumulate(self.state, feat, mapped, lin.bias, rgb, self.points, proj, rgb_proj, depth_gate=gate)
+
+    def volume(self):
+        """``(volume (C,X,Y,Z), valid (1,X,Y,Z) int64)`` of the views so far: K2-finish -> sigma-MLP -> K1-finish, what ``extract_volume``
+        returns for them (channels-last memory)."""
+        if self.state.n_views == 0:
+            raise RuntimeError("the scene has no views yet: call add_views first")
+        with torch.no_grad():
+            glob = ops.density_finish(self.state, self._lin.bias)
+            mlp = self.det.nerf_mlp
+            if hasattr(mlp, "hip_trunk_ok") and mlp.hip_trunk_ok():
+                alpha = mlp.alpha_from_points(self.points, glob)
+            else:
+                alpha = ops.sigma_to_alpha(mlp.raw_sigma_from_rows(ops.posenc_concat(self.points, glob)))
+            return ops.volume_finish(self.state, alpha)
+
+    def detect(self, defer: bool = False):
+        """Detections over the views so far: what ``simple_test`` returns, ``[dict(boxes_3d, scores_3d, labels_3d)]``; with ``defer`` a
+        ``finish()`` callable that returns it (one device-to-host copy).  The state is not changed: more views may follow.  When a fp16-pair
+        launch of neck_3d or the head trips the range guard, those two are repeated on bf16x3 from the finished volume."""
+        vol, valid = self.volume()
+        metas = [dict(self.meta)]
+        with torch.no_grad():
+            guarded = conv3d.ARITHMETIC == "f16x2" and vol.is_cuda
+            if guarded:
+                conv3d.guard_begin(vol.device)
+            x = self.det.neck_3d(vol.unsqueeze(0))
+            return self.det._detect_tail(x, valid.unsqueeze(0), metas, defer, guarded, vol.device, lambda: self._repeat_tail(vol, valid, metas))
+
+    def _repeat_tail(self, vol: Tensor, valid: Tensor, metas):
+        conv3d.guard_trips += 1
+        prev = conv3d.set_arithmetic("bf16x3")
+        try:
+            with torch.no_grad():
+                x = self.det.neck_3d(vol.unsqueeze(0))
+                return self.det._detect_tail(x, valid.unsqueeze(0), metas, False, False, vol.device, None)
+        finally:
+            conv3d.set_arithmetic(prev)
