@@ -420,7 +420,8 @@ int ndet_amax_slot_floats(void);
  * a production process cannot pick them up by accident.  "nt_bytes": outputs of at least this many bytes are written with non-temporal stores
  * (default 32 MiB); "order2": 1 / 0 = deal the column tiles of a row tile to one XCD or keep grid order (neither changes a result bit);
  * "deterministic_scatter": 1 = the backward kernels' gradient scatter on 64-bit fixed-point integer atomics (the caller then passes zeroed int64
- * buffers in place of the float ones: order-independent sums, for reproducibility tests; nerfdet_amd/autograd.py::set_deterministic);
+ * buffers in place of the float ones: order-independent sums, for reproducibility tests; nerfdet_amd/autograd.py::set_deterministic; the
+ * grad_bias of ndet_density_features_bwd[_gated] is then 2 * cm int64: units of 2^-40 in [0, cm), units of 2^-8 in [cm, 2 cm));
  * "wgrad_wide": 0 = ndet_wgrad_split (arith 1) keeps its 128 x 128 tile where it would take 128 x 256 (same sums in another association);
  * "wgrad_xcd": 0 = the weight-gradient kernel's workgroups in grid order instead of one K split per XCD at a time (no result bit changes).
  * HOST string.  No reference counterpart (the reference's harness, tools/benchmark.py:63-89, times the model only). */

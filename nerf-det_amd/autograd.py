@@ -125,7 +125,9 @@ class DensityFeatures(torch.autograd.Function):
         g = g.float().contiguous()
         dm = _grad_buffer((n_v, h, w, cm), g.device)
         assert (m.stride(0), m.stride(2)) == (dm.stride(0), dm.stride(1)), "saved input and gradient buffer must share their pitches"
-        db = _grad_buffer((cm,), g.device)
+        # deterministic mode: the bias gradient in two fixed-point words (csrc/backward_kernels.hip, k_density_features_bwd): an unseen voxel's
+        # mean is n_v b / 1e-8, so its share of d bias exceeds the 2^-40 format's range
+        db = _grad_buffer((2 * cm,) if DETERMINISTIC else (cm,), g.device)
         args = (_ptr(g), _ptr(m), n_v, cm, h, w, m.stride(0), m.stride(2), _ptr(bias.float().contiguous()), _ptr(points.float().contiguous()), n,
                 _ptr(projection.float().contiguous()), _ptr(dm), _ptr(db))
         lib = _lib.load()
@@ -133,7 +135,9 @@ class DensityFeatures(torch.autograd.Function):
             check(lib.ndet_density_features_bwd(*args, _stream(g)), "density_features_bwd")
         else:
             check(lib.ndet_density_features_bwd_gated(*args, ops._gate_arg(ctx.depth_gate, n_v, (h, w)), _stream(g)), "density_features_bwd_gated")
-        return _grad_result(dm).permute(0, 3, 1, 2), _grad_result(db), None, None, None, None, None
+        if db.dtype == torch.int64:
+            db = (db[:cm].double() * _FIX + db[cm:].double() * 2.0 ** -8).float()
+        return _grad_result(dm).permute(0, 3, 1, 2), db, None, None, None, None, None
 
 
 class RayViewStats(torch.autograd.Function):
@@ -142,6 +146,12 @@ class RayViewStats(torch.autograd.Function):
     @staticmethod
     def forward(ctx, featmaps, xyz, train_imgs, train_cameras):
         from . import rays
+        n_v, d = featmaps.shape[:2]
+        # the packed forward samples up to 128 channels, the backward kernels take d <= 64 (packed) or d <= 61 (generic): refuse here
+        # rather than after the forward, inside backward()
+        if ctx.needs_input_grad[0] and d > 61 and not rays.packed_ok(n_v, d, backward=True):
+            raise ValueError(f"RayViewStats: no backward kernel for d={d} feature channels with {n_v} views "
+                             "(packed: d % 4 == 0, d <= 64, at most 128 views; generic: d <= 61)")
         f = _dense_nhwc(featmaps.detach())
         glob, pm, vc = rays.ray_view_stats(xyz, train_imgs, train_cameras, f)
         cams = train_cameras.squeeze(0) if train_cameras.dim() == 3 else train_cameras

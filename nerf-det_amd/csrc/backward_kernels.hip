@@ -179,7 +179,19 @@ __global__ __launch_bounds__(256) void k_density_features_bwd(const float* __res
             }
         }
     }
-    if (active && dbias_acc != 0.0f) ndet_scatter_add(dbias, lane, dbias_acc, det);
+    if (!active || dbias_acc == 0.0f) return;
+    if (!det) {
+        unsafeAtomicAdd(dbias + lane, dbias_acc);
+        return;
+    }
+    // Deterministic mode: a voxel no view sees has mean n_v b / 1e-8 (nerfdet.py:234-253), so a wave's bias partial reaches ~1e8 |g| n_v and
+    // would overflow the 2^-40 fixed point (|x| < 8.4e6).  The bias buffer then holds 2 cm int64: [cm + c] counts units of 2^-8 (range 3.6e16),
+    // [c] the remainder in units of 2^-40.  The split is exact: for |v| >= 2^16 v is a multiple of 2^-8; below, hi * 2^-8 is a float and
+    // v - hi * 2^-8 (|.| <= 2^-9) is exact.
+    const long long hi = llrintf(dbias_acc * 0x1p8f);
+    const float lo = dbias_acc - (float)hi * 0x1p-8f;
+    atomicAdd(reinterpret_cast<unsigned long long*>(dbias) + cm + lane, (unsigned long long)hi);
+    ndet_scatter_add(dbias, lane, lo, det);
 }
 
 static int density_features_bwd_impl(const char* fn, const float* grad_global_feat, const float* mapped_nhwc, int n_views, int cm, int h, int w,

@@ -1,0 +1,446 @@
+"""Backward kernels of the training step at cfg3 sizes against float64 autograd through the oracle.
+
+K1 backward (BackprojectMean), K2 backward (DensityFeatures), K4 backward (RayViewStats, packed and generic) and the compositing
+backward (rays.raw2outputs) run at the channel counts, view counts and ray batches of a cfg3 step: 40-101 views, C = 200-320,
+cm up to 61, d = 8-64, 2048 rays x 64 samples.  The reference is the oracle on the CPU under autograd with the DATA in float64
+(features, mapped maps, images, upstream gradients) and the GEOMETRY in float32 (points, projections, sample positions): the
+pixel each voxel or sample reads comes from the same float32 chain as in the kernels, so both sides read the same pixels and only
+the arithmetic differs.  Every gradient is held to
+
+  * max |got - ref| <= 2e-5 x scale (scale = max |ref|),
+  * |got - ref| <= 1e-4 |ref| + 1e-6 scale elementwise (a contribution missing from a small entry), and
+  * the same set of nonzero entries as the reference (a write to the wrong pixel, pitch or crop).
+
+The deterministic scatter (autograd.set_deterministic) is held to the same bounds plus what its fixed point promises: each
+contribution is rounded to a multiple of 2^-40, so an element that receives k contributions may be off by k x 2^-41 more, at
+upstream scales 1 and 1e-6 (about where training gradients sit)."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import nerfdet_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+HW = (240, 320)                                   # cfg3 image size; feature maps at stride 4: 60 x 80
+FHW = (HW[0] // 4, HW[1] // 4)
+GRID, VOXEL = (15, 11, 7), (0.36, 0.36, 0.36)      # 1155 voxels, not a multiple of the 16-voxel tile; ~200 seen by no view
+HALF_ULP = 2.0 ** -41                             # deterministic scatter: rounding of one contribution
+EPS32 = float(torch.finfo(torch.float32).eps)
+MODES = [("float", 1.0), ("det", 1.0), ("det", 1e-6)]
+MODE_IDS = ["float", "det", "det-1e-6"]
+
+
+def _check(got, ref, what, hits=None, tol=2e-5, etol=1e-4, atol=1e-6, floor=0.0):
+    """The three assertions of the module docstring.  ``hits``: contributions per element (deterministic mode) or None; ``floor``: least
+    scale (for a part of a gradient that may be zero)."""
+    got, ref = got.detach().cpu().double(), ref.detach().double()
+    assert got.shape == ref.shape, what
+    scale = max(float(ref.abs().max()), floor)
+    assert scale > 0, f"{what}: reference gradient is zero"
+    slack = torch.zeros_like(ref) if hits is None else hits.double() * HALF_ULP
+    err = (got - ref).abs()
+    assert float(err.max()) <= tol * scale + float(slack.max()), f"{what}: max err {float(err.max()):.3e} vs scale {scale:.3e}"
+    bound = etol * ref.abs() + atol * scale + slack
+    bad = err > bound
+    if bad.any():
+        i = int(torch.argmax((err - bound).flatten()))
+        pytest.fail(f"{what}: {int(bad.sum())} of {ref.numel()} elements out of bound; worst got {float(got.flatten()[i]):.6e} "
+                    f"ref {float(ref.flatten()[i]):.6e}")
+    # nonzero exactly where the reference is.  An entry below float32's resolution at the gradient's scale may come out 0 (1 - exp(-1e-12)
+    # is 0 in float32, exp(-var) of a view far from the mean underflows), and the fixed point rounds an entry below its own slack to 0
+    assert not (got[ref == 0] != 0).any(), f"{what}: {int((got[ref == 0] != 0).sum())} gradient entries where the reference has none"
+    lost = (got == 0) & (ref.abs() > slack + EPS32 * scale)
+    assert not lost.any(), f"{what}: {int(lost.sum())} entries the reference reaches are 0"
+
+
+@pytest.fixture
+def scatter_mode(request, device):
+    from nerfdet_amd import autograd as A
+    mode, gscale = request.param
+    prev = A.set_deterministic(mode == "det")
+    try:
+        yield mode == "det", gscale
+    finally:
+        A.set_deterministic(prev)
+
+
+@functools.lru_cache(maxsize=None)
+def _scene(n_v):
+    meta = O.ring_scene_meta(n_v, HW)
+    return meta, O.compute_projection(meta, 4), O.compute_projection(meta, 1), O.get_points(GRID, VOXEL, meta["lidar2img"]["origin"])
+
+
+def _pixels(points, projection, h, w):
+    """Pixel index (n_v, N) and validity of every voxel in every view, from the oracle's float32 projection chain."""
+    fu, fv, z = O.project_voxels(points, projection)
+    x, y = fu.round().long(), fv.round().long()
+    valid = (x >= 0) & (y >= 0) & (x < w) & (y < h) & (z > 0)
+    return x.clamp(0, w - 1), y.clamp(0, h - 1), z, valid
+
+
+def _backproject64(feat, points, projection, dmap=None, band=None):
+    """O.backproject as one differentiable gather; with ``dmap`` (n_v, h, w), the depth gate of nerfdet.py:404-411 against that
+    already resized map (the resize itself is tested in test_depth_gate_gpu.py: here the kernel's own map is used so that both
+    sides gate the same voxels).  Autograd through the oracle's per-view masked gather takes ~25 s at C = 320, 101 views on the
+    CPU; the forward is checked equal to the oracle's instead."""
+    n_v, c, h, w = feat.shape
+    x, y, z, valid = _pixels(points, projection, h, w)
+    if dmap is not None:
+        dv = torch.gather(dmap.reshape(n_v, -1), 1, y * w + x)
+        valid = valid & (z > dv - band) & (z < dv + band)
+    idx = torch.arange(n_v).view(n_v, 1) * (h * w) + y * w + x
+    rows = feat.permute(0, 2, 3, 1).reshape(n_v * h * w, c).index_select(0, idx.flatten()).view(n_v, -1, c)
+    vol = torch.where(valid.unsqueeze(-1), rows, torch.zeros((), dtype=feat.dtype)).permute(0, 2, 1)
+    vol, valid = vol.reshape(n_v, c, *points.shape[-3:]), valid.view(n_v, 1, *points.shape[-3:])
+    if dmap is None:
+        ov, ovalid = O.backproject(feat.detach(), points, projection)
+        assert torch.equal(ovalid, valid) and torch.equal(ov, vol.detach())
+    return vol, valid
+
+
+def _hits(valid, points, projection, h, w):
+    """Voxel-view pairs per feature pixel (n_v, h, w): the scatter contributions each gradient pixel of K1 / K2 receives."""
+    x, y, _, _ = _pixels(points, projection, h, w)
+    valid = valid.reshape(valid.shape[0], -1)
+    out = torch.zeros(valid.shape[0], h * w, dtype=torch.int64)
+    out.scatter_add_(1, (y * w + x), valid.long())
+    return out.view(-1, h, w)
+
+
+def _depth_gate(device, n_v, img_hw=None):
+    from depth_gate_ref import plane_depth
+    from nerfdet_amd import ops
+    meta = _scene(n_v)[0]
+    depth = plane_depth(meta, (120, 160), 0.3, noise=0.02, seed=5, missing=0.05)        # float64 RGB-D map, 5 % holes
+    return ops.depth_gate(depth.to(device), VOXEL, FHW, img_hw)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# K1 backward: d features of the view mean
+# ------------------------------------------------------------------------------------------------------------------------------
+K1_CASES = [  # (C, n_views, channels_last_out, kind)
+    (256, 40, True, "dense"),
+    (256, 64, False, "dense"),
+    (256, 65, True, "dense"),
+    (200, 101, False, "dense"),
+    (320, 65, True, "dense"),        # channels 256..319 through the tail loop, views 64.. through the second round
+    (320, 101, False, "dense"),
+    (256, 65, False, "crop"),        # [:h,:w] of a wider channels-last map: row pitch (w + 3) C
+    (256, 65, True, "gated"),
+]
+
+
+@functools.lru_cache(maxsize=None)
+def _k1_ref(c, n_v, gated_map_key):
+    meta, proj, _, pts = _scene(n_v)
+    gen = torch.Generator().manual_seed(1000 * n_v + c)
+    feat = torch.randn(n_v, c, *FHW, generator=gen)
+    g = torch.randn(c, *GRID, generator=gen)
+    f64 = feat.double().requires_grad_(True)
+    dmap = None if gated_map_key is None else _K1_MAPS[gated_map_key]
+    vol, valid = _backproject64(f64, pts, proj, dmap, VOXEL[2])
+    mean, cnt, _ = O.aggregate_views(vol, valid)
+    (grad,) = torch.autograd.grad(mean, f64, g.double())
+    return feat, g, grad, cnt, _hits(valid, pts, proj, *FHW)
+
+
+_K1_MAPS = {}
+
+
+@pytest.mark.parametrize("scatter_mode", MODES, ids=MODE_IDS, indirect=True)
+@pytest.mark.parametrize("c,n_v,cl_out,kind", K1_CASES)
+def test_k1_backward_vs_fp64(device, scatter_mode, c, n_v, cl_out, kind):
+    from nerfdet_amd.autograd import BackprojectMean
+    det, gscale = scatter_mode
+    _, proj, _, pts = _scene(n_v)
+    gate = None
+    if kind == "gated":
+        gate = _depth_gate(device, n_v)
+        _K1_MAPS.setdefault(n_v, gate.depth_f.cpu())
+    feat, g, ref, cnt, hits = _k1_ref(c, n_v, n_v if kind == "gated" else None)
+    assert (cnt == 0).any() and (n_v <= 64 or int(hits[64:].sum()) > 0)
+    h, w = FHW
+    if kind == "crop":
+        base = torch.zeros(n_v, h + 1, w + 3, c, device=device)
+        base[:, :h, :w] = feat.permute(0, 2, 3, 1).to(device)
+        base.requires_grad_(True)
+        fd = base.permute(0, 3, 1, 2)[:, :, :h, :w]
+        assert fd.stride(2) == (w + 3) * c
+    else:
+        fd = base = feat.to(device).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    out, count = BackprojectMean.apply(fd, pts.to(device), proj.to(device), cl_out, gate)
+    assert torch.equal(count.cpu(), cnt)
+    # the upstream gradient in the layout the output has, so both of K1 backward's gradient layouts run
+    gu = (g * gscale).to(device)
+    if cl_out:
+        gu = gu.permute(1, 2, 3, 0).contiguous().permute(3, 0, 1, 2)
+    torch.autograd.backward(out, gu)
+    got = base.grad
+    if kind == "crop":
+        assert float(got[:, h:].abs().max()) == 0 and float(got[:, :, w:].abs().max()) == 0, "gradient outside the crop"
+        got = got[:, :h, :w].permute(0, 3, 1, 2)
+    slack = hits.unsqueeze(1).expand(-1, c, -1, -1) if det else None
+    _check(got, ref * gscale, f"K1 d features C={c} n_v={n_v} {kind}", slack)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# K2 backward: d mapped map and d bias of the 70 (2 (3 + cm)) conditioning values
+# ------------------------------------------------------------------------------------------------------------------------------
+K2_CASES = [  # (cm, n_views, kind); "unseen": the voxels no view sees carry an upstream gradient too
+    (32, 40, "dense"),
+    (61, 64, "dense"),               # 61 mapped channels: the per-lane limit of the kernel
+    (5, 65, "dense"),
+    (32, 101, "dense"),
+    (61, 101, "dense"),
+    (32, 65, "unseen"),
+    (32, 65, "gated"),
+]
+_K2_MAPS = {}
+
+
+@functools.lru_cache(maxsize=None)
+def _k2_ref(cm, n_v, kind):
+    meta, proj, rgb_proj, pts = _scene(n_v)
+    gen = torch.Generator().manual_seed(7 * n_v + cm)
+    mapped = torch.randn(n_v, cm, *FHW, generator=gen)
+    bias = 0.5 * torch.randn(cm, generator=gen)
+    rgb = torch.rand(n_v, 3, *HW, generator=gen)
+    m64, b64 = mapped.double().requires_grad_(True), bias.double().requires_grad_(True)
+    dmf, dmr = _K2_MAPS[n_v] if kind == "gated" else (None, None)
+    vol, valid = _backproject64(m64, pts, proj, dmf, VOXEL[2])
+    # nerfdet.py:234-243 maps every voxel-view, so a view that misses the voxel contributes the bias; then identity mapping
+    vol = vol + (~valid) * b64.view(1, cm, 1, 1, 1)
+    rgb_vol, _ = _backproject64(rgb.double(), pts, rgb_proj, dmr, VOXEL[2])
+    cnt = valid.sum(dim=0)
+    glob = O.density_features(vol, rgb_vol, cnt, torch.eye(cm, dtype=torch.float64), torch.zeros(cm, dtype=torch.float64))
+    g = torch.randn(glob.shape, generator=gen)
+    if kind != "unseen":
+        g[cnt.flatten() == 0] = 0.0
+    dm, db = torch.autograd.grad(glob, (m64, b64), g.double())
+    return mapped, bias, rgb, g, glob.detach(), dm, db, cnt, _hits(valid, pts, proj, *FHW)
+
+
+@pytest.mark.parametrize("scatter_mode", MODES, ids=MODE_IDS, indirect=True)
+@pytest.mark.parametrize("cm,n_v,kind", K2_CASES)
+def test_k2_backward_vs_fp64(device, scatter_mode, cm, n_v, kind):
+    from nerfdet_amd.autograd import DensityFeatures
+    det, gscale = scatter_mode
+    _, proj, rgb_proj, pts = _scene(n_v)
+    gate = None
+    if kind == "gated":
+        gate = _depth_gate(device, n_v, HW)
+        _K2_MAPS.setdefault(n_v, (gate.depth_f.cpu(), gate.depth_r.cpu()))
+    mapped, bias, rgb, g, glob_ref, ref_dm, ref_db, cnt, hits = _k2_ref(cm, n_v, kind)
+    seen = cnt.flatten() > 0
+    assert (~seen).any()
+    md = mapped.to(device).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    bd = bias.to(device).requires_grad_(True)
+    glob = DensityFeatures.apply(md, bd, rgb.to(device), pts.to(device), proj.to(device), rgb_proj.to(device), gate)
+    s = float(glob_ref[seen].abs().max())
+    assert float((glob.detach().cpu().double()[seen] - glob_ref[seen]).abs().max()) <= 2e-5 * s, "K2 forward"
+    torch.autograd.backward(glob, (g * gscale).to(device))
+    slack = hits.unsqueeze(1).expand(-1, cm, -1, -1) if det else None
+    _check(md.grad, ref_dm * gscale, f"K2 d mapped cm={cm} n_v={n_v} {kind}", slack)
+    # d bias: one scatter per wave and channel (4 waves per 16-voxel tile)
+    n_waves = 4 * ((cnt.numel() + 15) // 16)
+    db_slack = torch.full((cm,), n_waves) if det else None
+    if kind == "unseen":
+        # an unseen voxel's mean is n_v b / 1e-8 (the reference does not zero it): its bias gradient n_v g / 1e-8 dominates, and the
+        # kernel's 1e-8f differs from 1e-8 by 6e-9 relative -- a relative bound on that sum
+        rel = (bd.grad.cpu().double() - ref_db * gscale).abs() / (ref_db * gscale).abs()
+        assert float(rel.max()) <= 1e-5, f"K2 d bias (unseen voxels): relative error {float(rel.max()):.3e}"
+    else:
+        _check(bd.grad, ref_db * gscale, f"K2 d bias cm={cm} n_v={n_v} {kind}", db_slack)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# K4 backward: d mapped map of the ray sampler's masked mean / exp(-variance) over the source views
+# ------------------------------------------------------------------------------------------------------------------------------
+K4_CASES = [  # (n_views, d, image h x w): packed or generic backward as rays.packed_ok decides
+    (40, 32, (240, 320), True),
+    (100, 32, (120, 160), True),
+    (20, 64, (240, 320), True),
+    (40, 8, (240, 320), False),       # LDS of the packed backward too small at d = 8: generic fallback
+    (150, 32, (120, 160), False),     # more than 128 views: generic only
+]
+R, S = 2048, 64
+SAMPLE_BUDGET = 8_000_000             # float64 (sample, view, channel) elements of the reference per tensor
+
+
+def _rays(device, gen, r):
+    from nerfdet_amd import rays
+    ang = torch.rand(r, generator=gen) * 2 * np.pi
+    ray_o = torch.stack([2.0 * torch.cos(ang), 2.0 * torch.sin(ang), 1.0 + 0.3 * torch.rand(r, generator=gen)], -1)
+    ray_d = -ray_o / ray_o.norm(dim=-1, keepdim=True) + 0.35 * torch.randn(r, 3, generator=gen)
+    pts, _ = rays.sample_along_camera_ray(ray_o.to(device), ray_d.to(device), [0.2, 8.0], S, det=True)
+    return pts
+
+
+def _k4_ref(pts, ke, img_hw, feat):
+    """projection.py:42-64 + 91-151 (bilinear sampling of the feature maps, zero padding, align_corners=True) and
+    render_ray.py:71-93 (O.compute_mask_points).  The sample's source coordinate is the float32 chain of the kernels (KE rows as
+    a k-ordered FMA chain: O.fma_chain_matmul); the bilinear weights and everything after are float64.  F.grid_sample itself
+    cannot be used: it takes the grid in the map's dtype and would recompute the coordinate in float64.
+    pts (n,3) float32, ke (n_v,3,4) float32, feat (n_v,d,hf,wf) float64 -> (mean (n,d), exp(-var) (n,d), mask (n,n_v), taps)."""
+    n_v, d, hf, wf = feat.shape
+    h, w = img_hw
+    hom = torch.cat([pts.t(), torch.ones(1, pts.shape[0])]).numpy()[None]
+    q = torch.from_numpy(O.fma_chain_matmul(ke.numpy(), hom))                    # (n_v, 3, n) float32
+    den = q[:, 2].clamp(min=1e-8)
+    px, py = (q[:, 0] / den).clamp(-1e6, 1e6), (q[:, 1] / den).clamp(-1e6, 1e6)
+    mask = (px <= w - 1.0) & (px >= 0) & (py <= h - 1.0) & (py >= 0) & (q[:, 2] > 0)
+    nx, ny = 2.0 * px / (w - 1.0) - 1.0, 2.0 * py / (h - 1.0) - 1.0
+    ix = (((nx + 1) / 2) * (wf - 1)).double()                                    # grid_sample's source coordinate, float32
+    iy = (((ny + 1) / 2) * (hf - 1)).double()
+    x0, y0 = ix.floor(), iy.floor()
+    flat = feat.permute(0, 2, 3, 1).reshape(-1, d)
+    view = torch.arange(n_v).view(n_v, 1)
+    val = torch.zeros(pts.shape[0], n_v, d, dtype=feat.dtype)
+    taps = []
+    for xt, yt, wt in ((x0, y0, (x0 + 1 - ix) * (y0 + 1 - iy)), (x0 + 1, y0, (ix - x0) * (y0 + 1 - iy)),
+                       (x0, y0 + 1, (x0 + 1 - ix) * (iy - y0)), (x0 + 1, y0 + 1, (ix - x0) * (iy - y0))):
+        inside = (xt >= 0) & (xt <= wf - 1) & (yt >= 0) & (yt <= hf - 1)
+        idx = view * hf * wf + yt.clamp(0, hf - 1).long() * wf + xt.clamp(0, wf - 1).long()
+        wt = torch.where(inside, wt, torch.zeros_like(wt))
+        val = val + flat[idx.t()] * wt.t().unsqueeze(-1)
+        taps.append((idx, wt))
+    mk = mask.t().double().unsqueeze(-1)                                          # (n, n_v, 1)
+    mean, ev = O.compute_mask_points(val.unsqueeze(1), mk.unsqueeze(1))
+    return mean.view(-1, d), ev.view(-1, d), mask.t(), taps
+
+
+@pytest.mark.parametrize("scatter_mode", MODES, ids=MODE_IDS, indirect=True)
+@pytest.mark.parametrize("n_v,d,img_hw,packed", K4_CASES)
+def test_k4_backward_vs_fp64(device, scatter_mode, n_v, d, img_hw, packed):
+    from nerfdet_amd import rays
+    from nerfdet_amd.autograd import RayViewStats
+    det, gscale = scatter_mode
+    assert rays.packed_ok(n_v, d, backward=True) == packed
+    gen = torch.Generator().manual_seed(n_v * 100 + d)
+    meta = O.ring_scene_meta(n_v, img_hw)
+    hf, wf = img_hw[0] // 4, img_hw[1] // 4
+    feat = torch.randn(n_v, d, hf, wf, generator=gen)
+    img = torch.rand(n_v, 3, *img_hw, generator=gen)
+    pts = _rays(device, gen, R)
+    cams = rays._compute_projection(meta)
+    nch = 3 + d
+    # a full-size launch; the reference covers the first `k` rays, the only ones with a nonzero upstream gradient
+    k = max(8, min(256, SAMPLE_BUDGET // (S * n_v * d)))
+    g = torch.zeros(R, S, 2 * nch)
+    g[:k] = torch.randn(k, S, 2 * nch, generator=gen)
+    fd = feat.to(device).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    glob, pm, vc = RayViewStats.apply(fd, pts, img.to(device), cams)
+    # samples no view sees (count 0) in a backward of their own: see below
+    unseen = (vc == 0).cpu().unsqueeze(-1)
+    got = {part: torch.autograd.grad(glob, fd, (g * gscale * sel).to(device), retain_graph=True)[0]
+           for part, sel in (("seen", ~unseen), ("unseen", unseen))}
+    # reference on the slice
+    ke, h, w = rays._camera_matrices(cams.squeeze(0))
+    p = pts[:k].reshape(-1, 3).cpu()
+    f64 = feat.double().requires_grad_(True)
+    mean, ev, mask, taps = _k4_ref(p, ke, (h, w), f64)
+    assert torch.equal(vc[:k].reshape(-1).cpu(), mask.sum(1).int()), "view counts differ from the reference's float32 chain"
+    assert 0 < int(mask.sum()) and (mask.sum(1) == 0).any()
+    gs = g[:k].reshape(-1, 2 * nch).double()
+    gl = glob.detach()[:k].reshape(-1, 2 * nch).cpu().double()
+    torch.testing.assert_close(gl[:, 3:nch], mean.detach(), rtol=0, atol=2e-5 * float(mean.detach().abs().max()))
+    torch.testing.assert_close(gl[:, nch + 3:], ev.detach(), rtol=0, atol=2e-5)
+    # the restated sampler against the oracle's own grid_sample path (float32, the cameras' bmm chain): pins the reference
+    rf, mk = O.projector_compute(pts[:k].cpu(), img.permute(0, 2, 3, 1).unsqueeze(0), cams, feat)
+    same = (mk[..., 0].reshape(-1, n_v) > 0) == mask
+    assert float(same.float().mean()) > 0.999
+    torch.testing.assert_close(rf[..., 3:].reshape(-1, n_v, d)[same.all(1)], _k4_val(f64.detach(), taps)[same.all(1)].float(),
+                               rtol=0, atol=1e-4)
+    un = unseen[:k].reshape(-1, 1).double()
+    kind = "packed" if packed else "generic"
+    for part, sel in (("seen", 1 - un), ("unseen", un)):
+        (ref,) = torch.autograd.grad((mean, ev), f64, (gs[:, 3:nch] * sel, gs[:, nch + 3:] * sel), retain_graph=True)
+        slack = None
+        if det:   # (sample, view, tap) contributions per feature pixel
+            cnt = torch.zeros(n_v * hf * wf, dtype=torch.int64)
+            for idx, wt in taps:
+                cnt.scatter_add_(0, idx.reshape(-1), ((wt != 0) & (sel.t() > 0)).long().reshape(-1))
+            slack = cnt.view(n_v, 1, hf, wf).expand(-1, d, -1, -1)
+        if part == "seen":
+            _check(got[part], ref * gscale, f"K4 d features n_v={n_v} d={d} {kind}", slack)
+            seen_scale = float(ref.abs().max()) * gscale
+        else:
+            # A sample no source image contains has mean 0 and variance sum(val^2) / 1e-8 over the views whose taps reach a map, so its
+            # gradient 2 ge exp(-var) val / 1e-8 moves by |1 - 2 var| x the relative error of val.  The kernel's val is a float32 blend
+            # of up to four taps whose terms may nearly cancel: measured 4e-6 relative in val (2.3e-4 from terms of 0.04) and 4e-5
+            # in the gradient, with the kernel equal to a float32 evaluation of the same expression.  These are held to 1e-3.  Where
+            # every such view is far from the mean, exp(-var) underflows (1e-70 in float64): no scale below float32's at the launch's.
+            _check(got[part], ref * gscale, f"K4 d features n_v={n_v} d={d} {kind}, unseen samples", slack, tol=1e-3, etol=1e-3, atol=1e-5,
+                   floor=EPS32 * seen_scale)
+
+
+def _k4_val(feat, taps):
+    n_v, d, hf, wf = feat.shape
+    flat = feat.permute(0, 2, 3, 1).reshape(-1, d)
+    val = 0
+    for idx, wt in taps:
+        val = val + flat[idx.t()] * wt.t().unsqueeze(-1)
+    return val
+
+
+def test_k4_backward_refuses_feature_widths_without_a_kernel(device):
+    """The packed forward samples up to d = 128 channels, the backward kernels take d <= 64 (packed) and d <= 61 (generic): with a
+    gradient wanted, a wider map is refused before the forward runs instead of failing inside backward()."""
+    from nerfdet_amd import rays
+    from nerfdet_amd.autograd import RayViewStats
+    n_v, d, img_hw = 8, 96, (64, 96)
+    assert rays.packed_ok(n_v, d) and not rays.packed_ok(n_v, d, backward=True)
+    gen = torch.Generator().manual_seed(3)
+    meta = O.ring_scene_meta(n_v, img_hw)
+    feat = torch.randn(n_v, d, img_hw[0] // 4, img_hw[1] // 4, generator=gen).to(device).contiguous(memory_format=torch.channels_last)
+    img = torch.rand(n_v, 3, *img_hw, generator=gen).to(device)
+    pts = _rays(device, gen, 16)
+    cams = rays._compute_projection(meta)
+    with pytest.raises(ValueError, match="no backward kernel"):
+        RayViewStats.apply(feat.detach().requires_grad_(True), pts, img, cams)
+    glob, _, _ = RayViewStats.apply(feat, pts, img, cams)      # no gradient wanted: the forward is still served
+    assert glob.shape == (16, S, 2 * (3 + d)) and torch.isfinite(glob).all()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# compositing backward
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("white", [False, True])
+@pytest.mark.parametrize("zsign", [1.0, -1.0])
+def test_composite_backward_vs_fp64(device, white, zsign):
+    """2048 rays x 64 samples.  Transparent rays (sigma 0 or 1e-12) have a weight sum far below the 1e-8 of the depth's denominator:
+    their depth falls outside the z range and is clamped (zero slope) -- at the lower end for positive z, at the upper end for
+    negative z.  Opaque samples (sigma 40: 1 - alpha rounds to 0 in float32 and float64 alike) leave a transmittance of 1e-10 or
+    1e-30 behind them.  sigma stays below 16 or at 40: in between, 1 - alpha is 0 in float32 but not in float64, and the
+    transmittance after the sample differs by orders of magnitude between the two arithmetics, not because of the kernel."""
+    from nerfdet_amd import rays
+    gen = torch.Generator().manual_seed(11 + int(white) + int(zsign > 0))
+    r, s = R, S
+    raw = torch.cat([torch.rand(r, s, 3, generator=gen), 3 * torch.rand(r, s, 1, generator=gen) ** 3], -1)
+    raw[:64, :, 3] = 0.0                       # transparent: depth 0, clamped
+    raw[64:128, :, 3] = 1e-12
+    raw[128:256, 20, 3] = 40.0                 # one opaque sample: T = 1e-10 behind it
+    raw[256:320, 10:13, 3] = 40.0              # three: T = 1e-30
+    z = torch.sort(torch.rand(r, s, generator=gen) * 7.8 + 0.2, dim=1)[0]
+    if zsign < 0:
+        z = -z.flip(1)
+    pmask = torch.rand(r, s, generator=gen) < 0.2
+    w_rgb, w_dep = torch.randn(r, 3, generator=gen), torch.randn(r, generator=gen)
+    a = raw.double().requires_grad_(True)
+    o = O.raw2outputs(a, z.double(), pmask, white_bkgd=white)
+    ref_rgb, ref_depth = o["rgb"].detach(), o["depth"].detach()
+    (ref,) = torch.autograd.grad((o["rgb"], o["depth"]), a, (w_rgb.double(), w_dep.double()))
+    lo, hi = float(z.min()), float(z.max())
+    clamped = (ref_depth <= lo) | (ref_depth >= hi)
+    assert int(clamped.sum()) >= 64 and float(ref[clamped, :, 3].abs().max()) > 0      # clamped rays still get d sigma via rgb
+    b = raw.to(device).requires_grad_(True)
+    p = rays.raw2outputs(b, z.to(device), pmask.to(device), white_bkgd=white)
+    assert torch.equal(p["mask"].cpu(), o["mask"])
+    torch.testing.assert_close(p["rgb"].detach().cpu().double(), ref_rgb, rtol=0, atol=2e-5)
+    torch.autograd.backward((p["rgb"], p["depth"]), (w_rgb.to(device), w_dep.to(device)))
+    tag = f"white={white} z{'+' if zsign > 0 else '-'}"
+    _check(b.grad[..., :3], ref[..., :3], f"composite d rgb {tag}")
+    _check(b.grad[..., 3:], ref[..., 3:], f"composite d sigma {tag}")
