@@ -441,13 +441,12 @@ int ndet_measurement_knob(const char* name_host, int64_t value);
  *   residual      (OD,OH,OW,Cout); residual_up2 = 1: a (OD, ceil(OH/2), ceil(OW/2), Cout) map added at (d, h/2, w/2) -- the FPN's nearest x2
  *                 upsample-add (not with split-K).
  *   splits        split-K over blockIdx.z into `workspace` (splits * M * Cout floats), reduced in a fixed order.
- *   tile          rows x output channels of a workgroup's tile: 0 auto; 64 (64 x 64), 128 (128 x 128), 12864 (128 x 64): the unified tiles,
- *                 LDS-staged epilogue; 100064 / 100128 / 112864: the same tiles storing straight from the accumulators (splits == 1, not transposed,
- *                 Cout % 32 == 0, output < 4 GB); 128256: wave-specialised 128 x 256; 129256 / 129257 (eight consumer waves) / 129064 (64-row
- *                 tiles): its persistent form (plain convolutions, Cout % 16 == 0, <= 32 taps); 3128 / 3256 / 3257 / 3258: halo-stationary
- *                 128-voxel patch x 128 / 256 channels (stride 1, odd kernel, same padding, more than one tap; 3257: two consumer waves per SIMD,
- *                 3258: eight producer waves).  The staged and direct forms of a unified tile, and the one-shot and persistent forms of the
- *                 wave-specialised tile, give bit-identical results (tests/test_conv3d_gpu.py).
+ *   tile          a workgroup's tile: 0 auto, or an id of the table CONV_TILES (csrc/conv_split_kernels.hip; read it with ndet_conv_tile_info).  Four
+ *                 families: the unified tiles, LDS-staged epilogue or -- NDET_TILE_DIRECT -- storing straight from the accumulators (splits == 1, not
+ *                 transposed, Cout % 32 == 0, output < 4 GB); the wave-specialised 128 x 256 tile; its persistent forms (plain convolutions,
+ *                 Cout % 16 == 0, <= 32 taps); the halo-stationary 128-voxel patches (stride 1, odd kernel, same padding, more than one tap).  The
+ *                 staged and direct forms of a unified tile, and the one-shot and persistent forms of the wave-specialised tile, give bit-identical
+ *                 results (tests/test_conv3d_gpu.py).
  *   arith         0 = bf16x3: every fp32 operand as the exact sum of three bf16 terms, the six products of order <= 2 accumulated in fp32 (error at
  *                 the level of an fp32 FMA chain).  1 = fp16 pair (three products; see ndet_split_weights_f16x2).  2 = bf16: both operands rounded
  *                 to bf16, one product, fp32 accumulate and fp32 activations in HBM -- the "bf16" arithmetic BASELINE.json's configs 3 and 5
@@ -475,7 +474,7 @@ int ndet_measurement_knob(const char* name_host, int64_t value);
  *                 map_w (Cout, 32) and map_b (32) with the convolution's own affine folded in by the caller (map_w[c][j] = scale_c Wm[j][c],
  *                 map_b[j] = sum_c shift_c Wm[j][c] + bm[j]); fp32 FMAs; all three 16-byte aligned.  The detector's feature mapping
  *                 (detectors/nerfdet.py:194-197: self.mapping on every FPN level-0 pixel) behind the FPN output convolution: the 276 MB feature
- *                 map is not read back by a launch of its own.  Only the 256-column halo tiles own whole rows: tile 3256 / 3257 / 3258,
+ *                 map is not read back by a launch of its own.  Only the tiles flagged NDET_TILE_OWNS_ROWS (the 256-column halo tiles) take it:
  *                 Cout = 256, no split-K, residual, ReLU or transposition. */
 typedef struct NdetConvArgs {
     int32_t size;
@@ -502,6 +501,14 @@ typedef struct NdetConvArgs {
     float* map_out;
 } NdetConvArgs;
 int ndet_conv_split(const NdetConvArgs* a, void* stream);
+
+#define NDET_TILE_DIRECT 1    /* epilogue straight from the accumulators: final values only */
+#define NDET_TILE_OWNS_ROWS 2 /* one tile holds all 256 channels of its rows: the chained projection (map_out) is allowed */
+#define NDET_TILE_ORDER2 4    /* may be dealt in the activation-stationary workgroup order */
+/* One row of the tile table behind NdetConvArgs::tile: rows x output channels of a workgroup's tile and its NDET_TILE_* flags; NDET_E_INVALID for an
+ * id the table does not hold (0 = auto included).  No HIP call.  For the host's copy of the table (nerfdet_amd/conv_tiles.py), which tests hold
+ * against this one; part of the launcher of the convolutions of mmdet3d/models/necks/imvoxelnet.py:36-67, the reference has no counterpart. */
+int ndet_conv_tile_info(int tile, int* rows, int* cols, int* flags);
 
 /* Convolution + chained 1x1 convolution in one launch: out = act3(bn3(W3 . relu(bn1(conv(in)))) + residual), the intermediate (Cmid = 64 or
  * 128 channels, ALL of them in one 128-row tile) never leaves the CU.  Replaces the conv2 -> bn2 -> relu -> conv3 -> bn3 -> (+identity) ->

@@ -14,7 +14,7 @@ from typing import Optional, Sequence
 import torch
 from torch import nn
 
-from . import _lib, trace
+from . import _lib, conv_tiles, trace
 from ._lib import check
 from .conv_tuning import TUNED, TUNED_BF16, TUNED_F16, TUNED_SPLIT
 from ._lib import raw_stream
@@ -234,12 +234,9 @@ def guard_l1(pk: dict) -> float:
 
 launch_hook = None  # bench.py: callable(flops, thunk, kernel_name) wrapping every MFMA-conv launch (event timing); None = direct
 
-KERNEL_NAMES = {("bf16x3", 64): "k_conv_split<64,64,2,2>", ("bf16x3", 128): "k_conv_split<128,128,2,2>", ("bf16x3", 12864): "k_conv_split<128,64,2,2>",
-                ("bf16x3", 128256): "k_conv_split_ws", ("bf16x3", 129256): "k_conv_split_wsp<128>", ("bf16x3", 129257): "k_conv_split_wsp<128,8>", ("bf16x3", 129064): "k_conv_split_wsp<64>", ("bf16x3", 3128): "k_conv_split_halo<4,2>", ("bf16x3", 3256): "k_conv_split_halo<8,2>", ("bf16x3", 3257): "k_conv_split_halo<4,4>", ("bf16x3", 3258): "k_conv_split_halo<4,4,p8>",
-                ("f32", 64): "k_conv3d_igemm<64,64,2,2>", ("f32", 128): "k_conv3d_igemm<128,128,4,2>"}
-KERNEL_NAMES.update({("bf16x3", 100000 + t if t != 12864 else 112864): KERNEL_NAMES[("bf16x3", t)] for t in (64, 128, 12864)})   # direct-epilogue forms
-KERNEL_NAMES.update({("bf16", t): n for (a, t), n in list(KERNEL_NAMES.items()) if a == "bf16x3"})
-KERNEL_NAMES.update({("f16x2", t): n + "/f16x2" for (a, t), n in list(KERNEL_NAMES.items()) if a == "bf16x3"})
+KERNEL_NAMES = {("f32", 64): "k_conv3d_igemm<64,64,2,2>", ("f32", 128): "k_conv3d_igemm<128,128,4,2>"}
+for _t, _row in conv_tiles.TILES.items():
+    KERNEL_NAMES.update({("bf16x3", _t): _row.name, ("bf16", _t): _row.name, ("f16x2", _t): _row.name + "/f16x2"})
 
 
 def _launch(flops, thunk, arith="f32", tile=0, nbytes=0, name=None):
@@ -298,9 +295,9 @@ def choose_tiling_split(m: int, cout: int, k_iters: int, tile: int = 0, splits: 
         else:
             tile = 64
     if splits == 0:
-        if transposed or tile in (100064, 100128, 112864):     # (the direct-epilogue forms of the unified tiles write final values: no split-K)
+        if transposed or conv_tiles.is_direct(tile):     # (the direct-epilogue forms of the unified tiles write final values: no split-K)
             return tile, 1
-        tm, tn = {12864: (128, 64), 128256: (128, 256), 129256: (128, 256), 129257: (128, 256), 129064: (64, 256), 3128: (128, 128), 3256: (128, 256), 3257: (128, 256), 3258: (128, 256)}.get(tile, (tile, tile))
+        tm, tn = conv_tiles.TILES[tile][:2] if tile in conv_tiles.TILES else (tile, tile)
         tiles = ((m + tm - 1) // tm) * ((cout + tn - 1) // tn)
         splits = 1
         while splits < 32 and k_iters // (splits + 1) >= 24 and tiles * (splits + 1) <= 768:
@@ -364,17 +361,8 @@ def _conv_split(x, pk, out, dims, kernel, stride, pad, transposed, residual, res
     halo_ok = (not transposed and all(s == 1 for s in stride) and all(k % 2 == 1 and q == k // 2 for k, q in zip(kernel, pad))
                and kernel[0] * kernel[1] * kernel[2] > 1)
     tile, splits = choose_tiling_split(m, pk["cout"], k_iters, tile, 1 if (transposed or residual_up2) else splits, transposed, halo_ok)
-    if tile in (3128, 3256, 3257, 3258):   # halo-stationary tiles: stride-1 same-padded multi-tap convolutions only, K split over the channel chunks
-        if not halo_ok:
-            tile = 128256 if pk["cout"] > 128 else 128
-        else:
-            splits = min(splits, pk["cin"] // 32)
-    if tile in (129256, 129257, 129064) and (transposed or pk["cout"] % 16 or kernel[0] * kernel[1] * kernel[2] > 32):
-        tile = 128256                                        # the persistent form takes plain convolutions with Cout % 16 == 0
-    # unified tiles that write final values: the epilogue straight from the MFMA's C layout (no LDS staging, no barriers)
-    base = {100064: 64, 100128: 128, 112864: 12864}.get(tile, tile)
-    direct_ok = splits == 1 and not transposed and pk["cout"] % 32 == 0 and (m + 128) * pk["cout"] * 4 < (1 << 32)
-    tile = {64: 100064, 128: 100128, 12864: 112864}[base] if (base in (64, 128, 12864) and direct_ok and DIRECT_EPILOGUE) else base
+    tile, splits = conv_tiles.resolve(tile, splits, m=m, cout=pk["cout"], cin=pk["cin"], taps=kernel[0] * kernel[1] * kernel[2], transposed=transposed,
+                                      halo_ok=halo_ok, direct_epilogue=DIRECT_EPILOGUE)
     ws = torch.empty((m * pk["cout"] * splits * 4,), dtype=torch.uint8, device=x.device) if splits > 1 else None
     st = c_void_p(raw_stream(x.device))
     lib = _lib.load()
@@ -415,7 +403,7 @@ def _conv_split(x, pk, out, dims, kernel, stride, pad, transposed, residual, res
         a.w_planes, a.guard, a.guard_l1, a.guard_tol = planes.data_ptr(), _addr(gw), (guard_l1(pk) if gw is not None else 0.0), GUARD_TOL
         # the chained 32-channel projection of the output rows in the same launch (csrc: conv_map_rows): the 256-column halo tiles only; with another
         # tile / arithmetic the caller projects in a launch of its own
-        if (chain is not None and tile in (3256, 3257, 3258) and splits == 1 and residual is None and relu == 0 and not transposed and pk["cout"] == 256
+        if (chain is not None and conv_tiles.owns_rows(tile) and splits == 1 and residual is None and relu == 0 and not transposed and pk["cout"] == 256
                 and arith in ("f16x2", "bf16x3")):
             mapped = torch.empty((m, 32), dtype=torch.float32, device=x.device)
             a.map_w, a.map_b, a.map_out = chain[0].data_ptr(), chain[1].data_ptr(), mapped.data_ptr()

@@ -467,19 +467,12 @@ extern "C" int ndet_bottleneck_f16x2(const float* x, int N, int H, int W, int Ci
     const int64_t blocks = (int64_t)N * p.tiles_x * p.tiles_y;
     NDET_REQUIRE(blocks < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many patches", fn);
     const size_t lds = (size_t)(2 * (BT_AROWS + BT_MID) * SPL_RS + 2 * BT_AROWS * BT_MID + (ds ? 2 * BT_OROWS * BT_MID : 0)) * sizeof(uint16_t);
-    const void* kfn = ds ? (const void*)k_bottleneck_f16x2<true, 2> : (Cin == 64 ? (const void*)k_bottleneck_f16x2<false, 2> : (const void*)k_bottleneck_f16x2<false, 8>);
-    const int variant = ds ? 0 : (Cin == 64 ? 1 : 2);
-    static int attr_state[16][3] = {{0}};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    if (lds > 64 * 1024 && attr_state[dev][variant] == 0) {
-        hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const auto kernel = ds ? k_bottleneck_f16x2<true, 2> : (Cin == 64 ? k_bottleneck_f16x2<false, 2> : k_bottleneck_f16x2<false, 8>);
+    if (lds > 64 * 1024) {
+        const hipError_t e = ndet_lds_limit((const void*)kernel, lds);
         NDET_REQUIRE(e == hipSuccess, NDET_E_LAUNCH, "%s: cannot raise the LDS limit to %zu bytes: %s", fn, lds, hipGetErrorString(e));
-        attr_state[dev][variant] = 1;
     }
-    if (ds) hipLaunchKernelGGL((k_bottleneck_f16x2<true, 2>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, p);
-    else if (Cin == 64) hipLaunchKernelGGL((k_bottleneck_f16x2<false, 2>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((k_bottleneck_f16x2<false, 8>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, p);
     NDET_CHECK_LAUNCH(fn);
     return NDET_OK;
 }

@@ -249,14 +249,7 @@ static int conv_launch_tile(const Conv3dParams& p, hipStream_t st, const char* f
     const int zdim = p.transposed ? 8 : p.splits;
     dim3 grid((p.M + BM - 1) / BM, (p.Cout + BN - 1) / BN, zdim);
     const size_t lds = (size_t)2 * (BM + BN) * LdsStride<BM>::value * sizeof(float);
-    if (lds > 64 * 1024) {  // above the default dynamic-LDS cap
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute((const void*)k_conv3d_igemm<BM, BN, WGM, WGN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            NDET_REQUIRE(e == hipSuccess, NDET_E_LAUNCH, "%s: cannot raise the LDS limit: %s", fn, hipGetErrorString(e));
-            attr_set = true;
-        }
-    }
+    if (lds > 64 * 1024) NDET_RAISE_LDS((k_conv3d_igemm<BM, BN, WGM, WGN>), lds);  // above the default dynamic-LDS cap
     hipLaunchKernelGGL((k_conv3d_igemm<BM, BN, WGM, WGN>), grid, dim3(64 * WGM * WGN), lds, st, p);
     return NDET_OK;
 }

@@ -25,6 +25,8 @@
 
 #include "spl_common.hpp"
 
+#include <type_traits>
+
 // K walk of the unified tiles: fills acc (per-wave 32x32 MFMA tiles) for GEMM rows m0.. and channels n0..; returns the transposed-conv tap
 // (blockIdx.z) in ztap.  Ends behind a barrier: the LDS operand planes are free for the epilogue.
 template <int BM, int BN, int WGM, int WGN, int SCH>
@@ -990,6 +992,12 @@ __global__ __launch_bounds__(512, 1) void k_conv_split_ws(const Conv3dParams p, 
 // arithmetic scheme of a launch (Spl): max_order 2 = bf16x3, 1 = fp16 pair, 0 = one bf16 product
 static inline int conv_scheme(const Conv3dParams& p) { return p.max_order == 0 ? 2 : (p.max_order == 1 ? 1 : 0); }
 
+// the one run-time -> compile-time step of the scheme: f(std::integral_constant<int, SCH>) for SCH = sch
+template <class F>
+static inline int with_scheme(int sch, F&& f) {
+    return sch == 2 ? f(std::integral_constant<int, 2>{}) : (sch == 1 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{}));
+}
+
 static int split_launch_ws(const Conv3dParams& p, hipStream_t st, const char* fn) {
     const int taps = p.transposed ? 1 : p.kd * p.kh * p.kw;
     NDET_REQUIRE(taps <= 32, NDET_E_UNSUPPORTED, "%s: the 128x256 tile supports at most 32 taps", fn);
@@ -1001,17 +1009,12 @@ static int split_launch_ws(const Conv3dParams& p, hipStream_t st, const char* fn
     size_t lds = (size_t)2 * (sch == 2 ? 1 : (sch == 1 ? 2 : 3)) * (WS_BM + WS_BN) * CBK * sizeof(uint16_t);
     const size_t cs = (size_t)64 * (WS_BN + 4) * sizeof(float);   // the epilogue's C staging
     if (cs > lds) lds = cs;
-    static bool attr_set[3] = {false, false, false};
-    const void* kfn = sch == 2 ? (const void*)k_conv_split_ws<2> : (sch == 1 ? (const void*)k_conv_split_ws<1> : (const void*)k_conv_split_ws<0>);
-    if (!attr_set[sch]) {
-        hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        NDET_REQUIRE(e == hipSuccess, NDET_E_LAUNCH, "%s: cannot raise the LDS limit: %s", fn, hipGetErrorString(e));
-        attr_set[sch] = true;
-    }
-    if (sch == 2) hipLaunchKernelGGL(k_conv_split_ws<2>, grid, dim3(512), lds, st, p, (const uint16_t*)p.w);
-    else if (sch == 1) hipLaunchKernelGGL(k_conv_split_ws<1>, grid, dim3(512), lds, st, p, (const uint16_t*)p.w);
-    else hipLaunchKernelGGL(k_conv_split_ws<0>, grid, dim3(512), lds, st, p, (const uint16_t*)p.w);
-    return NDET_OK;
+    return with_scheme(sch, [&](auto s) -> int {
+        const auto kernel = k_conv_split_ws<decltype(s)::value>;
+        NDET_RAISE_LDS(kernel, lds);
+        hipLaunchKernelGGL(kernel, grid, dim3(512), lds, st, p, (const uint16_t*)p.w);
+        return NDET_OK;
+    });
 }
 
 
@@ -1332,17 +1335,12 @@ static int split_launch_wsp(const Conv3dParams& p, hipStream_t st, const char* f
     const int grid = (int)(n_tiles < n_cu ? n_tiles : n_cu);
     const int sch = conv_scheme(p);
     const size_t lds = (size_t)2 * (sch == 2 ? 1 : (sch == 1 ? 2 : 3)) * (BM + WS_BN) * CBK * sizeof(uint16_t);
-    static bool attr_set[3] = {false, false, false};
-    const void* kfn = sch == 2 ? (const void*)k_conv_split_wsp<2, BM, NCONS> : (sch == 1 ? (const void*)k_conv_split_wsp<1, BM, NCONS> : (const void*)k_conv_split_wsp<0, BM, NCONS>);
-    if (!attr_set[sch]) {
-        hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        NDET_REQUIRE(e == hipSuccess, NDET_E_LAUNCH, "%s: cannot raise the LDS limit: %s", fn, hipGetErrorString(e));
-        attr_set[sch] = true;
-    }
-    if (sch == 2) hipLaunchKernelGGL((k_conv_split_wsp<2, BM, NCONS>), dim3(grid), dim3(64 * (NCONS + 4)), lds, st, p, (const uint16_t*)p.w, n_mt, n_nt);
-    else if (sch == 1) hipLaunchKernelGGL((k_conv_split_wsp<1, BM, NCONS>), dim3(grid), dim3(64 * (NCONS + 4)), lds, st, p, (const uint16_t*)p.w, n_mt, n_nt);
-    else hipLaunchKernelGGL((k_conv_split_wsp<0, BM, NCONS>), dim3(grid), dim3(64 * (NCONS + 4)), lds, st, p, (const uint16_t*)p.w, n_mt, n_nt);
-    return NDET_OK;
+    return with_scheme(sch, [&](auto s) -> int {
+        const auto kernel = k_conv_split_wsp<decltype(s)::value, BM, NCONS>;
+        NDET_RAISE_LDS(kernel, lds);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * (NCONS + 4)), lds, st, p, (const uint16_t*)p.w, n_mt, n_nt);
+        return NDET_OK;
+    });
 }
 
 
@@ -1678,12 +1676,7 @@ static int split_launch_halo(const Conv3dParams& p, hipStream_t st, const char* 
                      "%s: the chained projection needs a tile that owns all %d output channels of its rows, no split-K / residual / ReLU", fn, p.Cout);
         lds = lds_cap;
     }
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_conv_split_halo<NT16, WGN, SCH, NPROD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap);
-        NDET_REQUIRE(e == hipSuccess, NDET_E_LAUNCH, "%s: cannot raise the LDS limit: %s", fn, hipGetErrorString(e));
-        attr_set = true;
-    }
+    NDET_RAISE_LDS((k_conv_split_halo<NT16, WGN, SCH, NPROD>), lds_cap);
     hipLaunchKernelGGL((k_conv_split_halo<NT16, WGN, SCH, NPROD>), grid, dim3(64 * (2 * WGN + NPROD)), lds, st, p, (const uint16_t*)p.w, g);
     return NDET_OK;
 }
@@ -1695,32 +1688,24 @@ static int split_launch_tile_sch(const Conv3dParams& p, hipStream_t st, const ch
     size_t lds = (size_t)Spl<SCH>::NPL * (BM + BN) * SPL_RS * sizeof(uint16_t);
     const size_t cs = (size_t)(BM / WGM) * (BN + 4) * sizeof(float);
     if (cs > lds) lds = cs;
-    if (lds > 64 * 1024) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute((const void*)k_conv_split<BM, BN, WGM, WGN, SCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            NDET_REQUIRE(e == hipSuccess, NDET_E_LAUNCH, "%s: cannot raise the LDS limit: %s", fn, hipGetErrorString(e));
-            attr_set = true;
-        }
-    }
+    if (lds > 64 * 1024) NDET_RAISE_LDS((k_conv_split<BM, BN, WGM, WGN, SCH>), lds);
     hipLaunchKernelGGL((k_conv_split<BM, BN, WGM, WGN, SCH>), grid, dim3(64 * WGM * WGN), lds, st, p, (const uint16_t*)p.w);
     return NDET_OK;
 }
 template <int BM, int BN, int WGM, int WGN>
 static int split_launch_tile(const Conv3dParams& p, hipStream_t st, const char* fn) {
-    switch (conv_scheme(p)) {
-        case 1: return split_launch_tile_sch<BM, BN, WGM, WGN, 1>(p, st, fn);
-        case 2: return split_launch_tile_sch<BM, BN, WGM, WGN, 2>(p, st, fn);
-        default: return split_launch_tile_sch<BM, BN, WGM, WGN, 0>(p, st, fn);
-    }
+    return with_scheme(conv_scheme(p), [&](auto s) { return split_launch_tile_sch<BM, BN, WGM, WGN, decltype(s)::value>(p, st, fn); });
 }
-template <int NT16, int WGN, int NPROD = 4>
+template <int NT16, int WGN>
 static int split_launch_halo_any(const Conv3dParams& p, hipStream_t st, const char* fn) {
-    switch (conv_scheme(p)) {
-        case 1: return split_launch_halo<NT16, WGN, 1, NPROD>(p, st, fn);
-        case 2: return split_launch_halo<NT16, WGN, 2, NPROD>(p, st, fn);
-        default: return split_launch_halo<NT16, WGN, 0, NPROD>(p, st, fn);
-    }
+    return with_scheme(conv_scheme(p), [&](auto s) { return split_launch_halo<NT16, WGN, decltype(s)::value>(p, st, fn); });
+}
+// tile 3258: <4,4> with eight producer waves (16 waves: 128 registers each -- the three-plane form does not fit and keeps four)
+static int split_launch_halo_p8(const Conv3dParams& p, hipStream_t st, const char* fn) {
+    return with_scheme(conv_scheme(p), [&](auto s) {
+        constexpr int SCH = decltype(s)::value;
+        return split_launch_halo<4, 4, SCH, SCH == 0 ? 4 : 8>(p, st, fn);
+    });
 }
 
 #ifndef NDET_ORDER_DEFAULT
@@ -1749,21 +1734,60 @@ extern "C" int ndet_measurement_knob(const char* name, int64_t value) {
 }
 extern "C" int ndet_amax_slot_floats(void) { return NDET_AMAX_SUB * NDET_AMAX_STRIDE; }
 
+// Every tile id of NdetConvArgs::tile: what a workgroup of it covers, what it may be asked for (NDET_TILE_*) and its launcher.  The one place a
+// new tile is entered on this side; nerfdet_amd/conv_tiles.py holds the same rows for the host's decisions (tests/test_abi_cpu.py compares
+// the two through ndet_conv_tile_info).
+struct ConvTile {
+    int id, rows, cols, flags;
+    int (*launch)(const Conv3dParams&, hipStream_t, const char*);
+};
+static const ConvTile CONV_TILES[] = {
+    // the unified tiles: LDS-staged epilogue, and the same tiles storing straight from the accumulators
+    {64, 64, 64, NDET_TILE_ORDER2, split_launch_tile<64, 64, 2, 2>},
+    {128, 128, 128, NDET_TILE_ORDER2, split_launch_tile<128, 128, 2, 2>},
+    {12864, 128, 64, NDET_TILE_ORDER2, split_launch_tile<128, 64, 2, 2>},
+    {100064, 64, 64, NDET_TILE_ORDER2 | NDET_TILE_DIRECT, split_launch_tile<64, 64, 2, 2>},
+    {100128, 128, 128, NDET_TILE_ORDER2 | NDET_TILE_DIRECT, split_launch_tile<128, 128, 2, 2>},
+    {112864, 128, 64, NDET_TILE_ORDER2 | NDET_TILE_DIRECT, split_launch_tile<128, 64, 2, 2>},
+    // wave-specialised 128 x 256, and its persistent forms: eight consumer waves (two per SIMD, 64 x 64 each); 64-row tiles
+    {128256, 128, 256, NDET_TILE_ORDER2, split_launch_ws},
+    {129256, 128, 256, 0, split_launch_wsp<128, 4>},
+    {129257, 128, 256, 0, split_launch_wsp<128, 8>},
+    {129064, 64, 256, 0, split_launch_wsp<64, 4>},
+    // halo-stationary 128-voxel patch; the 256-column ones own whole rows of a 256-channel layer
+    {3128, 128, 128, 0, split_launch_halo_any<4, 2>},
+    {3256, 128, 256, NDET_TILE_OWNS_ROWS, split_launch_halo_any<8, 2>},
+    {3257, 128, 256, NDET_TILE_OWNS_ROWS, split_launch_halo_any<4, 4>},
+    {3258, 128, 256, NDET_TILE_OWNS_ROWS, split_launch_halo_p8},
+};
+static const ConvTile* conv_tile(int id) {
+    for (const ConvTile& t : CONV_TILES)
+        if (t.id == id) return &t;
+    return nullptr;
+}
+
+extern "C" int ndet_conv_tile_info(int tile, int* rows, int* cols, int* flags) {
+    const char* fn = "ndet_conv_tile_info";
+    NDET_REQUIRE(rows && cols && flags, NDET_E_INVALID, "%s: null pointer", fn);
+    const ConvTile* t = conv_tile(tile);
+    NDET_REQUIRE(t, NDET_E_INVALID, "%s: unknown tile %d", fn, tile);
+    *rows = t->rows; *cols = t->cols; *flags = t->flags;
+    return NDET_OK;
+}
+
 // keep_partials (weight-gradient GEMMs): a split-K launch leaves its partial sums in the workspace and ndet_wgrad_to_torch adds them up (same fixed
 // order) on its way to torch's layout -- one launch and one pass over dW fewer per layer
 int conv_split_launch(Conv3dParams& p, int tile, bool keep_partials, hipStream_t st, const char* fn) {
-    p.direct = 0;
     p.nt = (p.splits <= 1 || p.transposed) && (int64_t)p.M * p.Cout * 4 * (p.transposed ? 8 : 1) >= conv_nt_bytes() ? 1 : 0;
-    if (tile >= 100000 && (tile - 100000 == 64 || tile - 100000 == 128 || tile - 100000 == 12864)) {   // 100064 / 100128 / 112864: direct epilogue
-        tile -= 100000;
-        NDET_REQUIRE(!p.transposed && p.splits == 1 && p.Cout % 32 == 0 && ((int64_t)p.M + 128) * p.Cout * 4 < ((int64_t)1 << 32),
-                     NDET_E_UNSUPPORTED, "%s: the direct epilogue needs splits == 1, no transposition, Cout %% 32 == 0 and an output below 4 GB", fn);
-        p.direct = 1;
-    }
     const int64_t big_tiles = (int64_t)((p.M + 127) / 128) * ((p.Cout + 127) / 128);
     if (tile == 0) tile = (big_tiles >= 192 && p.Cout >= 128) ? 128 : 64;
+    const ConvTile* t = conv_tile(tile);
+    NDET_REQUIRE(t, NDET_E_INVALID, "%s: unknown tile %d", fn, tile);
+    p.direct = (t->flags & NDET_TILE_DIRECT) ? 1 : 0;
+    NDET_REQUIRE(!p.direct || (!p.transposed && p.splits == 1 && p.Cout % 32 == 0 && ((int64_t)p.M + 128) * p.Cout * 4 < ((int64_t)1 << 32)),
+                 NDET_E_UNSUPPORTED, "%s: the direct epilogue needs splits == 1, no transposition, Cout %% 32 == 0 and an output below 4 GB", fn);
     {   // which operand is worth keeping in one XCD's L2 (Conv3dParams::order): the bytes its re-reads would otherwise fetch again
-        const int tm = tile == 64 ? 64 : 128, tn = tile == 64 || tile == 12864 ? 64 : (tile == 128 || tile == 3128 ? 128 : 256);
+        const int tm = t->rows, tn = t->cols;
         const int64_t mt = (p.M + tm - 1) / tm, nt = (p.Cout + tn - 1) / tn;
         const int64_t taps = p.transposed ? 1 : (int64_t)p.kd * p.kh * p.kw;
         const int64_t w_bytes = taps * p.Cin * p.Cout * 6, a_bytes = (int64_t)p.M * p.Cin * 4 * (p.sd * p.sh * p.sw);
@@ -1774,27 +1798,10 @@ int conv_split_launch(Conv3dParams& p, int tile, bool keep_partials, hipStream_t
             if (!p.transposed && mt > 1 && nt * p.splits > 1 && save_w > save_a && w_bytes > (8 << 20)) p.order = 1;
             // the mirror case: weights small enough to sit in every L2 (1x1 layers), several column tiles, the rows re-read once per XCD otherwise
             if (g_order2 && p.order == 0 && !p.transposed && nt > 1 && mt >= 16 && w_bytes <= (2 << 20) && save_a >= (8 << 20) &&
-                (tile == 64 || tile == 128 || tile == 12864 || tile == 128256)) p.order = 2;
+                (t->flags & NDET_TILE_ORDER2)) p.order = 2;
         }
     }
-    int rc;
-    switch (tile) {     // the tile ids of NdetConvArgs::tile (with the direct forms above): any other is rejected here, before a launch
-        case 64: rc = split_launch_tile<64, 64, 2, 2>(p, st, fn); break;
-        case 128: rc = split_launch_tile<128, 128, 2, 2>(p, st, fn); break;
-        case 12864: rc = split_launch_tile<128, 64, 2, 2>(p, st, fn); break;
-        case 128256: rc = split_launch_ws(p, st, fn); break;
-        case 129256: rc = split_launch_wsp<128, 4>(p, st, fn); break;     // persistent form of 128256
-        case 129257: rc = split_launch_wsp<128, 8>(p, st, fn); break;     // ... with eight consumer waves (two per SIMD, 64 x 64 each)
-        case 129064: rc = split_launch_wsp<64, 4>(p, st, fn); break;      // ... with 64-row tiles
-        case 3128: rc = split_launch_halo_any<4, 2>(p, st, fn); break;
-        case 3256: rc = split_launch_halo_any<8, 2>(p, st, fn); break;
-        case 3257: rc = split_launch_halo_any<4, 4>(p, st, fn); break;
-        case 3258:                                                            // ... with eight producer waves (16 waves: 128 registers each --
-            rc = conv_scheme(p) == 1 ? split_launch_halo<4, 4, 1, 8>(p, st, fn)                  // the three-plane form does not fit and keeps four)
-                 : conv_scheme(p) == 2 ? split_launch_halo<4, 4, 2, 8>(p, st, fn) : split_launch_halo<4, 4, 0, 4>(p, st, fn);
-            break;
-        default: ndet_set_error("%s: unknown tile %d", fn, tile); return NDET_E_INVALID;
-    }
+    const int rc = t->launch(p, st, fn);
     if (rc != NDET_OK) return rc;
     NDET_CHECK_LAUNCH(fn);
     if (keep_partials && p.splits > 1) return NDET_OK;
@@ -1984,16 +1991,7 @@ extern "C" int ndet_wgrad_to_torch(const float* dw_rows, int splits, int taps, i
     NDET_REQUIRE(dw_rows && dw_torch && splits >= 1, NDET_E_INVALID, "%s: null pointer / splits < 1", fn);
     NDET_REQUIRE(taps > 0 && taps <= 27 && Cout > 0 && Cin > 0 && Cin % 32 == 0 && (Cout + 31) / 32 <= 65535, NDET_E_UNSUPPORTED, "%s: 1..27 taps, Cin %% 32 == 0", fn);
     const size_t lds = (size_t)32 * (32 * taps + 1) * sizeof(float);
-    if (lds > 48 * 1024) {
-        static bool attr_set[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)k_wgrad_to_torch, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * (32 * 27 + 1) * 4);
-            NDET_REQUIRE(e == hipSuccess, NDET_E_LAUNCH, "%s: cannot raise the LDS limit: %s", fn, hipGetErrorString(e));
-            if (dev >= 0 && dev < 64) attr_set[dev] = true;
-        }
-    }
+    if (lds > 48 * 1024) NDET_RAISE_LDS(k_wgrad_to_torch, 32 * (32 * 27 + 1) * 4);
     hipLaunchKernelGGL(k_wgrad_to_torch, dim3(Cin / 32, (Cout + 31) / 32), dim3(1024), lds, (hipStream_t)stream, dw_rows, splits, taps, Cout, Cin, dw_torch);
     NDET_CHECK_LAUNCH(fn);
     return NDET_OK;
@@ -2008,20 +2006,10 @@ extern "C" int ndet_split_weights_train(const float* w_torch, int taps, int Cout
     NDET_REQUIRE((arith == 1) == (w_amax != nullptr), NDET_E_INVALID, "%s: the amax slot belongs to the fp16-pair arithmetic", fn);
     NDET_REQUIRE(Cin % CBK == 0 && (Cout + CBK - 1) / CBK <= 65535, NDET_E_UNSUPPORTED, "%s: Cin=%d must be a multiple of %d", fn, Cin, CBK);
     const size_t lds = (size_t)32 * (32 * taps + 1) * sizeof(float);
-    const void* kfn = arith == 1 ? (const void*)k_split_weights_train<1> : (const void*)k_split_weights_train<0>;
-    if (lds > 48 * 1024) {                           // per device: a process may drive several (one rank per GPU is the rule, not a guarantee)
-        static bool attr_set[2][64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_set[arith][dev]) {
-            hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * (32 * 27 + 1) * 4);
-            NDET_REQUIRE(e == hipSuccess, NDET_E_LAUNCH, "%s: cannot raise the LDS limit: %s", fn, hipGetErrorString(e));
-            if (dev >= 0 && dev < 64) attr_set[arith][dev] = true;
-        }
-    }
-    const dim3 grid(Cin / CBK, (Cout + CBK - 1) / CBK);
-    if (arith == 1) hipLaunchKernelGGL(k_split_weights_train<1>, grid, dim3(1024), lds, (hipStream_t)stream, w_torch, taps, Cout, Cin, w_amax, planes, planes_adjoint);
-    else hipLaunchKernelGGL(k_split_weights_train<0>, grid, dim3(1024), lds, (hipStream_t)stream, w_torch, taps, Cout, Cin, w_amax, planes, planes_adjoint);
+    const auto kernel = arith == 1 ? k_split_weights_train<1> : k_split_weights_train<0>;
+    if (lds > 48 * 1024) NDET_RAISE_LDS(kernel, 32 * (32 * 27 + 1) * 4);
+    hipLaunchKernelGGL(kernel, dim3(Cin / CBK, (Cout + CBK - 1) / CBK), dim3(1024), lds, (hipStream_t)stream, w_torch, taps, Cout, Cin, w_amax, planes,
+                       planes_adjoint);
     NDET_CHECK_LAUNCH(fn);
     return NDET_OK;
 }
@@ -2099,8 +2087,8 @@ extern "C" int ndet_conv_split(const NdetConvArgs* a, void* stream) {
         NDET_REQUIRE(a->map_w && a->map_b && a->map_out, NDET_E_INVALID, "%s: null projection pointers", fn);
         NDET_REQUIRE((((uintptr_t)a->map_w | (uintptr_t)a->map_b | (uintptr_t)a->map_out) & 15) == 0, NDET_E_UNSUPPORTED,
                      "%s: projection pointers must be 16-byte aligned", fn);
-        NDET_REQUIRE(a->tile == 3256 || a->tile == 3257 || a->tile == 3258, NDET_E_UNSUPPORTED, "%s: tile %d does not own whole rows (3256 / 3257 / 3258 do)",
-                     fn, a->tile);
+        const ConvTile* t = conv_tile(a->tile);
+        NDET_REQUIRE(t && (t->flags & NDET_TILE_OWNS_ROWS), NDET_E_UNSUPPORTED, "%s: tile %d does not own whole rows (3256 / 3257 / 3258 do)", fn, a->tile);
         NDET_REQUIRE(a->Cout == 256, NDET_E_UNSUPPORTED, "%s: Cout=%d, the 256-column tiles own whole rows of 256 channels only", fn, a->Cout);
         NDET_REQUIRE(a->splits <= 1 && !a->residual && !a->relu && !a->transposed, NDET_E_UNSUPPORTED,
                      "%s: the chained projection takes no split-K, residual, ReLU or transposition", fn);
@@ -2149,14 +2137,7 @@ static int chain_launch(const Conv3dParams& p, const ConvChain& c, hipStream_t s
     size_t lds = (size_t)NPL * (128 + MID) * SPL_RS * sizeof(uint16_t);
     const size_t y = (size_t)NPL * (MID == 128 ? 64 : 128) * MID * sizeof(uint16_t);
     if (y > lds) lds = y;
-    if (lds > 64 * 1024) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute((const void*)k_conv_split_chain<MID, SCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            NDET_REQUIRE(e == hipSuccess, NDET_E_LAUNCH, "%s: cannot raise the LDS limit: %s", fn, hipGetErrorString(e));
-            attr_set = true;
-        }
-    }
+    if (lds > 64 * 1024) NDET_RAISE_LDS((k_conv_split_chain<MID, SCH>), lds);
     hipLaunchKernelGGL((k_conv_split_chain<MID, SCH>), dim3((p.M + 127) / 128), dim3(256), lds, st, p, (const uint16_t*)p.w, c);
     return NDET_OK;
 }
@@ -2192,9 +2173,10 @@ extern "C" int ndet_conv_chain(const float* in, const uint16_t* w_planes, int D,
     c.w3inv = arith == 1 ? w3_inv_scale : 1.0f; c.amax_out = out_amax; c.guard_l1 = guard_l1_3;
     p.nt = (int64_t)p.M * Cout * 4 >= conv_nt_bytes() ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (Cmid == 64) rc = arith == 2 ? chain_launch<64, 2>(p, c, st, fn) : (arith == 1 ? chain_launch<64, 1>(p, c, st, fn) : chain_launch<64, 0>(p, c, st, fn));
-    else rc = arith == 2 ? chain_launch<128, 2>(p, c, st, fn) : (arith == 1 ? chain_launch<128, 1>(p, c, st, fn) : chain_launch<128, 0>(p, c, st, fn));
+    const int rc = with_scheme(arith, [&](auto s) {
+        constexpr int SCH = decltype(s)::value;
+        return Cmid == 64 ? chain_launch<64, SCH>(p, c, st, fn) : chain_launch<128, SCH>(p, c, st, fn);
+    });
     if (rc != NDET_OK) return rc;
     NDET_CHECK_LAUNCH(fn);
     return NDET_OK;
@@ -2246,21 +2228,14 @@ extern "C" int ndet_wgrad_split(const float* x_ndhwc, int D, int H, int W, int C
     const bool wide = Cout > 64, big = Cin % 128 == 0;
     const int sch = arith;       // (= conv_scheme(p))
     int rc;
-#define NDET_WGRAD_TILE(BM, BN) (sch == 2 ? wgrad_launch<BM, BN, 2>(g, p, dy_planes, st) : (sch == 1 ? wgrad_launch<BM, BN, 1>(g, p, dy_planes, st) : wgrad_launch<BM, BN, 0>(g, p, dy_planes, st)))
+#define NDET_WGRAD_TILE(BM, BN) with_scheme(sch, [&](auto s) { return wgrad_launch<BM, BN, decltype(s)::value>(g, p, dy_planes, st); })
     // 256 output channels per workgroup where the layer has them (fp16 pairs; the 3-plane arithmetic's LDS tiles would not leave room for two
     // workgroups per CU): the kernel is bound by what it pulls through L2 -- every (tap, channel tile) re-reads dy, every column tile re-reads x;
     // measured on the neck's 27-tap 256 -> 256 layer at 128 x 128: 2.8 GB per launch, 6.2 TB/s -- and the wider tile halves the x side
     // (layers with fewer than 32 row tiles keep 128 x 128: the FPN's 9-tap 256 -> 256 layer over 192 000 pixels has 18, and with the K splits capped
     // at 32 the wide tile leaves it 576 workgroups -- measured 1 413 us against 1 247 us)
     if (big && sch == 1 && Cout % 256 == 0 && taps * (Cin / 128) >= 32 && g_wgrad_wide) {
-        static bool attr_set[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)k_wgrad_split<128, 256, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * (256 + 4) * 4);
-            NDET_REQUIRE(e == hipSuccess, NDET_E_LAUNCH, "%s: cannot raise the LDS limit: %s", fn, hipGetErrorString(e));
-            if (dev >= 0 && dev < 64) attr_set[dev] = true;
-        }
+        NDET_RAISE_LDS((k_wgrad_split<128, 256, 1>), 64 * (256 + 4) * 4);
         rc = wgrad_launch<128, 256, 1>(g, p, dy_planes, st);
     }
     else if (big && wide) rc = NDET_WGRAD_TILE(128, 128);

@@ -29,6 +29,18 @@ void ndet_set_error(const char* fmt, ...);
         }                                                                            \
     } while (0)
 
+// Raise `kernel`'s dynamic-LDS limit to `bytes`.  The limit is a per-device attribute of the kernel: the runtime is asked once per (kernel,
+// current device) -- again only for a larger size -- and its answer, a refusal included, is what every later call returns; a call that
+// finds its answer costs one hipGetDevice.  What a refusal means is the caller's business (volume_kernels.hip).
+hipError_t ndet_lds_limit(const void* kernel, size_t bytes);
+
+// ... for the launchers to which a refusal is an error (`fn` = the entry point's name, in scope)
+#define NDET_RAISE_LDS(kernel, bytes)                                                                                     \
+    do {                                                                                                                  \
+        const hipError_t e__ = ndet_lds_limit((const void*)(kernel), (bytes));                                            \
+        NDET_REQUIRE(e__ == hipSuccess, NDET_E_LAUNCH, "%s: cannot raise the LDS limit: %s", fn, hipGetErrorString(e__)); \
+    } while (0)
+
 // ---- device helpers ----------------------------------------------------------------------
 
 // Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share one).  Give each XCD a

@@ -307,14 +307,8 @@ extern "C" int ndet_point_mlp_alpha(const float* points, const float* global_fea
     NDET_REQUIRE(((uintptr_t)w_sigma & 15) == 0 && (!h_out || ((uintptr_t)h_out & 15) == 0), NDET_E_UNSUPPORTED, "%s: w_sigma / h_out must be 16-byte aligned", fn);
     p.wsig = w_sigma; p.bsig = b_sigma; p.raw = raw_sigma; p.alpha = alpha; p.h_out = h_out;
     const size_t lds = (size_t)2 * PM_BM * PM_LDW * sizeof(uint16_t) + (size_t)(4 * PM_BM + PM_BM + PM_BM + 4 * PM_BM) * sizeof(float);
-    static int attr_state[16] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    if (attr_state[dev] == 0) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_point_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        NDET_REQUIRE(e == hipSuccess, NDET_E_LAUNCH, "%s: cannot raise the LDS limit to %zu bytes: %s", fn, lds, hipGetErrorString(e));
-        attr_state[dev] = 1;
-    }
+    const hipError_t e = ndet_lds_limit((const void*)k_point_mlp, lds);
+    NDET_REQUIRE(e == hipSuccess, NDET_E_LAUNCH, "%s: cannot raise the LDS limit to %zu bytes: %s", fn, lds, hipGetErrorString(e));
     const int64_t blocks = ((int64_t)N + PM_BM - 1) / PM_BM;
     hipLaunchKernelGGL(k_point_mlp, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, p);
     NDET_CHECK_LAUNCH(fn);

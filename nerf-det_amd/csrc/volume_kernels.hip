@@ -6,6 +6,10 @@
 
 #include <stdarg.h>
 
+#include <map>
+#include <mutex>
+#include <utility>
+
 // ------------------------------------------------------------------------------------------
 // error plumbing (host)
 // ------------------------------------------------------------------------------------------
@@ -18,7 +22,21 @@ void ndet_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-int g_ndet_deterministic_scatter = 0;      // ndet_common.hpp::ndet_scatter_add
+hipError_t ndet_lds_limit(const void* kernel, size_t bytes) {
+    struct Raised { size_t bytes; hipError_t err; };
+    static std::mutex mu;
+    static std::map<std::pair<const void*, int>, Raised> seen;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    std::lock_guard<std::mutex> lock(mu);
+    const auto it = seen.find({kernel, dev});
+    if (it != seen.end() && it->second.bytes >= bytes) return it->second.err;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    seen[{kernel, dev}] = {bytes, e};
+    return e;
+}
+
+int g_ndet_deterministic_scatter = 0;     // ndet_common.hpp::ndet_scatter_add
 extern "C" int ndet_version(void) { return 110; }
 extern "C" const char* ndet_last_error(void) { return g_err; }
 

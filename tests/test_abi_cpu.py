@@ -81,6 +81,25 @@ def test_bad_arguments_are_rejected_without_a_gpu():
         _lib.check(-2, "x")
 
 
+def test_tile_table_of_the_library_matches_the_hosts():
+    """nerfdet_amd/conv_tiles.py and CONV_TILES of csrc/conv_split_kernels.hip hold the same rows: ids, rows x columns, flags."""
+    from nerfdet_amd import _lib, conv_tiles
+    lib = _lib.load()
+    rows, cols, flags = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    assert len(conv_tiles.TILES) == 14
+    for tile, row in conv_tiles.TILES.items():
+        assert lib.ndet_conv_tile_info(tile, ctypes.byref(rows), ctypes.byref(cols), ctypes.byref(flags)) == 0, tile
+        assert (rows.value, cols.value, flags.value) == (row.rows, row.cols, row.flags), tile
+        if row.partner is not None:     # staged <-> direct: the same tile, the DIRECT flag apart
+            other = conv_tiles.TILES[row.partner]
+            assert other.partner == tile and (other.rows, other.cols, other.family, other.name) == (row.rows, row.cols, row.family, row.name)
+            assert other.flags ^ row.flags == conv_tiles.DIRECT
+    for tile in (77, 100256, 103256, 0):
+        assert lib.ndet_conv_tile_info(tile, ctypes.byref(rows), ctypes.byref(cols), ctypes.byref(flags)) == -1 and tile not in conv_tiles.TILES
+        assert b"unknown tile" in lib.ndet_last_error()
+    assert lib.ndet_conv_tile_info(64, None, None, None) == -1
+
+
 def test_product_path_has_no_cpu_fallback():
     import torch
     import nerfdet_amd.ops as ops

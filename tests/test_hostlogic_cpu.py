@@ -6,16 +6,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_tiling_tables_and_heuristics_are_well_formed():
-    from nerfdet_amd import conv3d
-    from nerfdet_amd.conv_tuning import TUNED, TUNED_SPLIT
-    f32_tiles, split_tiles = {64, 128}, {64, 128, 12864, 128256, 129256, 129257, 129064, 3128, 3256, 3257}
-    for table, tiles in ((TUNED, f32_tiles), (TUNED_SPLIT, split_tiles)):
+    from nerfdet_amd import conv3d, conv_tiles
+    from nerfdet_amd.conv_tuning import TUNED, TUNED_BF16, TUNED_F16, TUNED_SPLIT
+    f32_tiles, split_tiles = set(conv_tiles.F32_IDS), set(conv_tiles.SPLIT_IDS)
+    halo, persistent = conv_tiles.ids("halo"), conv_tiles.ids("wsp")
+    assert {3258, 100064, 100128, 112864} <= split_tiles and set(halo) == {3128, 3256, 3257, 3258} and set(persistent) == {129256, 129257, 129064}
+    for table, tiles in ((TUNED, f32_tiles), (TUNED_SPLIT, split_tiles), (TUNED_F16, split_tiles), (TUNED_BF16, split_tiles)):
         assert len(table) >= 20
         for (m, cout, k_iters, tr), (tile, splits) in table.items():
             assert m > 0 and cout > 0 and k_iters > 0 and tr in (0, 1)
             assert tile in tiles and 1 <= splits <= 32 and splits <= k_iters
             assert not (tr and splits != 1), "transposed convolutions never split K"
-            assert not (tr and tile in (3128, 3256, 3257)), "halo tiles are for stride-1 same-padded layers only"
+            assert not (tr and tile in halo), f"halo tiles are for stride-1 same-padded layers only: {(m, cout, k_iters, tr)} -> {(tile, splits)}"
     # every (arithmetic, tile) the tables can select has a kernel name for the bench's per-kernel roofline
     for t in split_tiles:
         assert ("bf16x3", t) in conv3d.KERNEL_NAMES
@@ -28,9 +30,45 @@ def test_tiling_tables_and_heuristics_are_well_formed():
                 for halo_ok in (False, True):
                     tile, splits = conv3d.choose_tiling_split(m + 1, cout, k_iters, halo_ok=halo_ok)   # +1: never a table key
                     assert tile in split_tiles and 1 <= splits <= min(32, k_iters)
-                    assert halo_ok or tile not in (3128, 3256, 3257)
+                    assert halo_ok or tile not in halo
+                    # ... and what _conv_split makes of it, whatever the layer's geometry
+                    for h_ok in (False, True):
+                        for transposed in (False, True):
+                            for taps in (1, 9):
+                                if k_iters % taps:
+                                    continue
+                                geo = dict(m=m + 1, cout=cout, cin=32 * (k_iters // taps), taps=taps, transposed=transposed, halo_ok=h_ok, direct_epilogue=True)
+                                rt, rs = conv_tiles.resolve(tile, splits, **geo)
+                                assert rt in split_tiles and 1 <= rs <= splits
+                                assert h_ok or rt not in halo
+                                assert not (transposed and (rt in persistent or conv_tiles.is_direct(rt)))
+                                assert rs == 1 or not conv_tiles.is_direct(rt)
+                                assert conv_tiles.resolve(rt, rs, **geo) == (rt, rs)
                 tile, splits = conv3d.choose_tiling(m + 1, cout, k_iters)
                 assert tile in f32_tiles and 1 <= splits <= min(8, k_iters)
+
+
+def test_resolve_is_idempotent_for_every_tile():
+    """conv_tiles.resolve over every id of the table (the tuning tables and callers may name any of them for any layer): the outcome is an id of the
+    table that the layer's geometry admits, and resolving it again with the same geometry changes nothing."""
+    from nerfdet_amd import conv_tiles
+    halo, persistent = conv_tiles.ids("halo"), conv_tiles.ids("wsp")
+    for tile in conv_tiles.SPLIT_IDS:
+        for splits in (1, 2, 4, 32):
+            for m, cout, cin, taps in ((400, 25, 32, 1), (240000, 256, 256, 9), (25600, 128, 64, 27), (5_000_000, 256, 32, 1), (48000, 24, 96, 125)):
+                for transposed in (False, True):
+                    for halo_ok in (False, True):
+                        for direct in (False, True):
+                            geo = dict(m=m, cout=cout, cin=cin, taps=taps, transposed=transposed, halo_ok=halo_ok, direct_epilogue=direct)
+                            rt, rs = conv_tiles.resolve(tile, splits, **geo)
+                            assert rt in conv_tiles.TILES and 1 <= rs <= splits
+                            assert halo_ok or rt not in halo
+                            assert not (transposed and (rt in persistent or conv_tiles.is_direct(rt)))
+                            assert not (rt in persistent and (cout % 16 or taps > 32))
+                            assert not (conv_tiles.is_direct(rt) and (rs != 1 or not direct or cout % 32))
+                            assert conv_tiles.resolve(rt, rs, **geo) == (rt, rs)
+    for bad in (77, 100256, 103256, 0):
+        assert bad not in conv_tiles.TILES and conv_tiles.resolve(bad, 3, m=400, cout=64, cin=64, taps=1, transposed=False, halo_ok=False) == (bad, 3)
 
 
 def test_bench_bookkeeping():

@@ -5,7 +5,7 @@ import torch
 from torch import nn
 import torch.nn.functional as F
 import nerfdet_amd  # noqa: F401
-from nerfdet_amd import conv3d as C
+from nerfdet_amd import conv3d as C, conv_tiles
 
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
@@ -89,16 +89,16 @@ def run_chain(n, h, w, cin, mid, cout, res=True):
 if __name__ == "__main__":
     quick = len(sys.argv) > 1 and sys.argv[1] == "quick"
     # unified tiles (staged / direct epilogue), split-K
-    for tile in (64, 128, 12864):
+    for tile in conv_tiles.ids("unified"):
         run3d(64, 128, (6, 10, 12), 3, tile, 1)
         run3d(64, 128, (6, 10, 12), 3, tile, 3, res=True)
         run3d(128, 64, (6, 10, 12), 1, tile, 1, res=True)
     # wave-specialised one-shot and persistent tiles
-    for tile in (128256, 129256, 129257, 129064):
+    for tile in conv_tiles.ids("ws", "wsp"):
         run3d(256, 256, (6, 10, 12), 3, tile, 1, res=True)
         run3d(256, 512, (6, 10, 12), 1, tile, 2)
     # halo tiles
-    for tile in (3128, 3256, 3257, 3258):
+    for tile in conv_tiles.ids("halo"):
         run3d(256, 256, (8, 12, 12), 3, tile, 1, res=True)
         run3d(128, 256, (8, 12, 12), 3, tile, 2)
     # stride 2, magnitudes far from 1

@@ -33,13 +33,13 @@ def layers_for(gx, gy, gz):
 
 
 def main():
-    from nerfdet_amd import conv3d as C3
+    from nerfdet_amd import conv3d as C3, conv_tiles
     global LAYERS
     if len(sys.argv) > 1:
         C3.set_arithmetic(sys.argv[1])
     if len(sys.argv) > 4:          # tune_conv3d.py <arithmetic> <X> <Y> <Z>
         LAYERS = layers_for(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]))
-    tiles = (64, 128, 12864, 128256, 129256, 129257, 129064, 3128, 3256, 3257, 3258, 100064, 100128, 112864) if C3.ARITHMETIC in ("bf16x3", "bf16", "f16x2") else (64, 128)
+    tiles = conv_tiles.SPLIT_IDS if C3.ARITHMETIC in C3.SPLIT_FAMILY else conv_tiles.F32_IDS
     if os.environ.get("TUNE_TILES"):
         tiles = tuple(int(t) for t in os.environ["TUNE_TILES"].split(","))
     if os.environ.get("TUNE_LAYERS"):

@@ -15,10 +15,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def main():
-    from nerfdet_amd import conv3d as C3
+    from nerfdet_amd import conv3d as C3, conv_tiles
     C3.set_arithmetic(sys.argv[1])
     shapes = [tuple(int(v) for v in a.split(",")) for a in sys.argv[2:]]
-    tiles = (64, 128, 12864, 128256, 129256, 129064, 100064, 100128, 112864)
+    tiles = conv_tiles.ids("unified", "ws", "wsp", direct=True)     # (one tap: nothing for the halo tiles)
     dev = torch.device("cuda")
     for m, cout, ksteps in shapes:
         cin = 32 * ksteps
