@@ -172,6 +172,20 @@ def float3(vals):
     return (c_float * 3)(*[float(v) for v in vals])
 
 
+def _ptr(t):
+    """A tensor's device address as the C ABI takes it; None -> the null pointer."""
+    return c_void_p(0 if t is None else t.data_ptr())
+
+
+def i3(a, b, c):
+    return (c_int * 3)(a, b, c)
+
+
+def _stream(t):
+    """The current HIP stream of the tensor's device, as the C ABI takes it."""
+    return c_void_p(raw_stream(t.device))
+
+
 def raw_stream(device) -> int:
     """The current HIP stream of ``device`` as the raw handle the C ABI takes -- what ``torch.cuda.current_stream(device).cuda_stream`` returns,
     without building the Stream object on the way (measured: 4.6 us a call, ~360 calls per training step)."""

@@ -3,21 +3,10 @@
 autograd over its materialised tensors ("autograd must flow through A3-A11 in training")."""
 from __future__ import annotations
 
-from ctypes import c_void_p
-
 import torch
 
 from . import _lib, ops
-from ._lib import NDET_LAYOUT_CN, NDET_LAYOUT_NC, check
-from ._lib import raw_stream
-
-
-def _ptr(t):
-    return c_void_p(0 if t is None else t.data_ptr())
-
-
-def _stream(t):
-    return c_void_p(raw_stream(t.device))
+from ._lib import NDET_LAYOUT_CN, NDET_LAYOUT_NC, _ptr, _stream, check
 
 
 def _dense_nhwc(t):

@@ -218,13 +218,13 @@ def _chain_pack(pk: dict, lin: nn.Linear):
     convolution's own per-channel affine (bias / folded BatchNorm) is folded in, out = (acc * scale + shift) . Wm^T + bm.  Cached on the Linear."""
     store = lin.__dict__.setdefault("_ndet_chain", {})
     stamp = (lin.weight.data_ptr(), lin.weight._version, lin.bias.data_ptr(), lin.bias._version, id(pk),
-             None if pk["scale"] is None else (pk["scale"].data_ptr(), pk["scale"]._version), None if pk["shift"] is None else (pk["shift"].data_ptr(), pk["shift"]._version))
+             None if pk.scale is None else (pk.scale.data_ptr(), pk.scale._version), None if pk.shift is None else (pk.shift.data_ptr(), pk.shift._version))
     hit = store.get("pack")
     if hit is None or hit[0] != stamp:
         with torch.no_grad():
             wm, bm = lin.weight.detach().float(), lin.bias.detach().float()
-            scale = pk["scale"] if pk["scale"] is not None else torch.ones(pk["cout"], device=wm.device)
-            shift = pk["shift"] if pk["shift"] is not None else torch.zeros(pk["cout"], device=wm.device)
+            scale = pk.scale if pk.scale is not None else torch.ones(pk.cout, device=wm.device)
+            shift = pk.shift if pk.shift is not None else torch.zeros(pk.cout, device=wm.device)
             map_w = (wm * scale.view(1, -1)).t().contiguous()
             map_b = (wm @ shift + bm).contiguous()
         hit = (stamp, (map_w, map_b), pk)          # (pk kept alive: its id is part of the stamp)
@@ -281,7 +281,7 @@ class FPN(nn.Module):
                 continue
             pk = packed([self.fpn_convs[i].conv])
             lin = self.chain_linear if i == 0 else None
-            if lin is not None and lin.in_features == pk["cout"] == 256 and lin.out_features == 32 and lin.weight.is_cuda:
+            if lin is not None and lin.in_features == pk.cout == 256 and lin.out_features == 32 and lin.weight.is_cuda:
                 # the detector's 256 -> 32 feature mapping (nerfdet.py:194-197) rides in the level-0 output convolution's epilogue: the mapped map
                 # travels on the output tensor as ``_ndet_feature_2d`` (logical (N, 32, H, W), channels-last memory)
                 o, mapped = conv2d_nhwc(lat[i], pk, amax=False, chain=_chain_pack(pk, lin))

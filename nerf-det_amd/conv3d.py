@@ -9,15 +9,15 @@ from __future__ import annotations
 import ctypes
 import math
 from ctypes import c_void_p
+from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import torch
 from torch import nn
 
 from . import _lib, conv_tiles, trace
-from ._lib import check
+from ._lib import _ptr, check, i3, raw_stream
 from .conv_tuning import TUNED, TUNED_BF16, TUNED_F16, TUNED_SPLIT
-from ._lib import raw_stream
 
 # Arithmetic of the convolution kernels: "bf16x3" = fp32 operands split exactly into three bf16 terms, six bf16-MFMA
 # products accumulated in fp32 (csrc/conv_split_kernels.hip; fp32-level error, 16x the MFMA rate per product);
@@ -55,6 +55,44 @@ def train_arithmetic() -> str:
     if ARITHMETIC == "f16x2":
         return "f16x2" if TRAIN_F16X2 else "bf16x3"
     return ARITHMETIC
+
+
+@dataclass(slots=True, eq=False)
+class ConvPack:
+    """What the launchers below are told about one convolution: its geometry and epilogue, the arithmetic policy, and the weight's planes."""
+    # geometry and epilogue.  ``w``: the packed fp32 weight (taps, Cout, Cin) -- or, in the packs of conv_train.py whose planes are pre-built, the
+    # torch-layout weight / the dy planes they stand for (its numel() is the weight term of a launch's algorithmic bytes)
+    w: Optional[torch.Tensor]
+    cout: int
+    cin: int                                    # (the data-gradient packs: Cin of the layer and its Cout padded to 32, not w's shape)
+    kernel: tuple
+    strides: tuple
+    pads: tuple
+    transposed: bool = False
+    scale: Optional[torch.Tensor] = None
+    shift: Optional[torch.Tensor] = None
+    # policy (fp16-pair mode)
+    arith: Optional[str] = None                 # pinned arithmetic: training (the weights change every step) and the point MLPs (packed_linear)
+    keep_amax: bool = False                     # a pinned pack's launches leave max |out| behind (otherwise a fp16-pair reader takes its own pass, amax_of)
+    guard: bool = True                          # the fp16-pair launches of a ``w_amax`` pack raise the range guard
+    w_amax: Optional[torch.Tensor] = None       # the device slot ``planes_f16`` were scaled by (training: no scale ever reaches the host)
+    # planes: given to the constructor (training, weight gradients: never split again), else filled once by split_planes / split_planes_f16 / guard_l1
+    planes_bf16: Optional[torch.Tensor] = None
+    planes_f16: Optional[tuple] = None          # (planes, 1 / scale)
+    guard_l1: Optional[float] = None
+
+    @property
+    def ndim(self) -> int:
+        return len(self.kernel)
+
+    @property
+    def taps(self) -> int:
+        return math.prod(self.kernel)
+
+    @classmethod
+    def gemm(cls, w, cout: int, cin: int, **policy) -> "ConvPack":
+        """A bare GEMM over rows, (M, cin) -> (M, cout): the 1x1 convolution linear_rows / conv2d_nhwc take."""
+        return cls(w, cout, cin, (1, 1), (1, 1), (0, 0), **policy)
 
 
 class _AmaxSlots:
@@ -216,19 +254,19 @@ def guard_tripped(device) -> bool:
     return bool(w is not None and int(w.item()) & 1)
 
 
-def guard_l1(pk: dict) -> float:
+def guard_l1(pk: ConvPack) -> float:
     """max over output channels j of |scale_j| (sum_k |w_jk| + max|w| #{k: 0 < |w_jk| < 2^-16 max|w|}): what the launch multiplies 2^-39 max|in|
     by to bound its absolute error floor (the second term: weights so far below the weight maximum that THEIR error is absolute).  Once per pack."""
-    hit = pk.get("guard_l1")
+    hit = pk.guard_l1
     if hit is None:
-        w = pk["w"].abs()
+        w = pk.w.abs()
         wmax = w.max()
         tiny = ((w > 0) & (w < wmax * 2.0 ** -16)).sum(dim=(0, 2)).float()
         l1 = w.sum(dim=(0, 2)) + wmax * tiny
-        if pk.get("scale") is not None:
-            l1 = l1 * pk["scale"].abs()
+        if pk.scale is not None:
+            l1 = l1 * pk.scale.abs()
         v = float(l1.max())
-        hit = pk["guard_l1"] = v if math.isfinite(v) else float("inf")
+        hit = pk.guard_l1 = v if math.isfinite(v) else float("inf")
     return hit
 
 
@@ -308,19 +346,19 @@ def choose_tiling_split(m: int, cout: int, k_iters: int, tile: int = 0, splits: 
 DIRECT_EPILOGUE = True     # unified bf16x3 tiles store straight from the accumulators' layout whenever they write final values
 
 
-def split_planes(pk: dict) -> torch.Tensor:
+def split_planes(pk: ConvPack) -> torch.Tensor:
     """The packed weight (taps, Cout, Cin) as three bf16 planes tiled per 32-channel K step, (taps, Cin/32, 3, Cout, 32), with
     w = p0 + p1 + p2 exactly (built once per pack)."""
-    planes = pk.get("w_split")
+    planes = pk.planes_bf16
     if planes is None:
-        w = pk["w"]
+        w = pk.w
         taps, cout, cin = w.shape
         if cin % 32:
             raise ValueError(f"conv_ndhwc_split: Cin={cin} must be a multiple of 32")
         planes = torch.empty((taps, cin // 32, 3, cout, 32), dtype=torch.int16, device=w.device)
         st = c_void_p(raw_stream(w.device))
         check(_lib.load().ndet_split_weights_bf16x3(_ptr(w), taps, cout, cin, _ptr(planes), st), "split_weights_bf16x3")
-        pk["w_split"] = planes
+        pk.planes_bf16 = planes
     return planes
 
 
@@ -333,12 +371,12 @@ def f16_weight_scale(wmax: float) -> float:
     return math.ldexp(1.0, 15 - e)
 
 
-def split_planes_f16(pk: dict):
+def split_planes_f16(pk: ConvPack):
     """(planes, 1 / scale): the packed weight times a power of two that puts max |w| in [2^14, 2^15), as two fp16 planes tiled per 32-channel K
     step, (taps, Cin/32, 2, Cout, 32) (built once per pack; reading max |w| back is the one host synchronisation, at pack time)."""
-    hit = pk.get("w_f16")
+    hit = pk.planes_f16
     if hit is None:
-        w = pk["w"]
+        w = pk.w
         taps, cout, cin = w.shape
         if cin % 32:
             raise ValueError(f"conv_ndhwc_arith: Cin={cin} must be a multiple of 32")
@@ -346,7 +384,7 @@ def split_planes_f16(pk: dict):
         planes = torch.empty((taps, cin // 32, 2, cout, 32), dtype=torch.int16, device=w.device)
         st = c_void_p(raw_stream(w.device))
         check(_lib.load().ndet_split_weights_f16x2(_ptr(w), taps, cout, cin, scale, _ptr(planes), st), "split_weights_f16x2")
-        hit = pk["w_f16"] = (planes, 1.0 / scale)
+        hit = pk.planes_f16 = (planes, 1.0 / scale)
     return hit
 
 
@@ -357,26 +395,29 @@ def layer_arithmetic(k_iters: int) -> str:
     return ARITHMETIC
 
 
-def _conv_split(x, pk, out, dims, kernel, stride, pad, transposed, residual, residual_up2, relu, splits, tile, m, k_iters, flops, want_amax=True, chain=None):
+def _conv_split(x, pk, out, dims, kernel, stride, pad, transposed, residual, residual_up2, relu, splits, tile, m, k_iters, flops, want_amax=True, chain=None,
+                keep_partials=False):
+    """One ndet_conv_split launch.  ``keep_partials`` (the weight-gradient GEMM of conv_train.weight_grad): returns ``(out, partials)``, ``partials`` =
+    ``(workspace, splits)`` when the launch split K and left its partial sums for ndet_wgrad_to_torch to add (``out`` is then unwritten), else None."""
     halo_ok = (not transposed and all(s == 1 for s in stride) and all(k % 2 == 1 and q == k // 2 for k, q in zip(kernel, pad))
                and kernel[0] * kernel[1] * kernel[2] > 1)
-    tile, splits = choose_tiling_split(m, pk["cout"], k_iters, tile, 1 if (transposed or residual_up2) else splits, transposed, halo_ok)
-    tile, splits = conv_tiles.resolve(tile, splits, m=m, cout=pk["cout"], cin=pk["cin"], taps=kernel[0] * kernel[1] * kernel[2], transposed=transposed,
+    tile, splits = choose_tiling_split(m, pk.cout, k_iters, tile, 1 if (transposed or residual_up2) else splits, transposed, halo_ok)
+    tile, splits = conv_tiles.resolve(tile, splits, m=m, cout=pk.cout, cin=pk.cin, taps=kernel[0] * kernel[1] * kernel[2], transposed=transposed,
                                       halo_ok=halo_ok, direct_epilogue=DIRECT_EPILOGUE)
-    ws = torch.empty((m * pk["cout"] * splits * 4,), dtype=torch.uint8, device=x.device) if splits > 1 else None
+    ws = torch.empty((m * pk.cout * splits * 4,), dtype=torch.uint8, device=x.device) if splits > 1 else None
     st = c_void_p(raw_stream(x.device))
     lib = _lib.load()
     d, h, w = dims
-    nbytes = 4 * (x.numel() + pk["w"].numel() + out.numel() + (0 if residual is None else residual.numel()))
+    nbytes = 4 * (x.numel() + pk.w.numel() + out.numel() + (0 if residual is None else residual.numel()))
     arith = layer_arithmetic(k_iters)
-    if ARITHMETIC == "f16x2" and pk.get("arith"):
-        arith = pk["arith"]            # pinned packs: training (conv_train.py: the weights change every step) and the point MLPs (packed_linear)
-        want_amax = want_amax and bool(pk.get("keep_amax"))    # (otherwise a reader in the fp16-pair arithmetic takes its own pass, amax_of)
+    if ARITHMETIC == "f16x2" and pk.arith:
+        arith = pk.arith               # pinned packs: training (conv_train.py: the weights change every step) and the point MLPs (packed_linear)
+        want_amax = want_amax and pk.keep_amax    # (otherwise a reader in the fp16-pair arithmetic takes its own pass, amax_of)
     if NO_AMAX_COMMIT:
         want_amax = False
     # one argument block (csrc: NdetConvArgs); the branches below only fill in the fields of the arithmetic, the guard and the projection
-    a = _lib.NdetConvArgs(size=ctypes.sizeof(_lib.NdetConvArgs), in_=x.data_ptr(), out=out.data_ptr(), D=d, H=h, W=w, Cin=pk["cin"], Cout=pk["cout"],
-                          kernel=kernel, stride=stride, pad=pad, transposed=int(transposed), scale=_addr(pk["scale"]), shift=_addr(pk["shift"]),
+    a = _lib.NdetConvArgs(size=ctypes.sizeof(_lib.NdetConvArgs), in_=x.data_ptr(), out=out.data_ptr(), D=d, H=h, W=w, Cin=pk.cin, Cout=pk.cout,
+                          kernel=kernel, stride=stride, pad=pad, transposed=int(transposed), scale=_addr(pk.scale), shift=_addr(pk.shift),
                           residual=_addr(residual), residual_up2=int(residual_up2), relu=relu, splits=splits, tile=tile, arith=ARITH_ID[arith],
                           workspace=_addr(ws))
     keep, mapped = False, None
@@ -384,14 +425,14 @@ def _conv_split(x, pk, out, dims, kernel, stride, pad, transposed, residual, res
         # bf16x3 / bf16 modes: no amax slots, no guard
         a.w_planes = split_planes(pk).data_ptr()
         want_amax = False
-    elif arith == "f16x2" and pk.get("w_amax") is not None:
-        # training packs (conv_train.py): planes scaled on the device by the slot pk["w_amax"]; plain convolutions only
+    elif arith == "f16x2" and pk.w_amax is not None:
+        # training packs (conv_train.py): planes scaled on the device by the slot pk.w_amax; plain convolutions only
         assert not transposed and not residual_up2
-        keep = bool(pk.get("keep_partials"))       # weight-gradient GEMMs: a split-K launch leaves its partials for ndet_wgrad_to_torch (no reduction pass)
+        keep = keep_partials           # weight-gradient GEMMs: a split-K launch leaves its partials for ndet_wgrad_to_torch (no reduction pass)
         want_amax = want_amax and not keep
-        a.w_planes, a.in_amax, a.w_amax, a.keep_partials = pk["w_f16"][0].data_ptr(), amax_of(x).data_ptr(), pk["w_amax"].data_ptr(), int(keep)
-        gw = guard_word(x.device) if pk.get("guard", True) else None
-        a.guard, a.guard_l1, a.guard_tol = _addr(gw), float(kernel[0] * kernel[1] * kernel[2] * pk["cin"]), GUARD_TOL    # (l1 bound: K max|w|)
+        a.w_planes, a.in_amax, a.w_amax, a.keep_partials = pk.planes_f16[0].data_ptr(), amax_of(x).data_ptr(), pk.w_amax.data_ptr(), int(keep)
+        gw = guard_word(x.device) if pk.guard else None
+        a.guard, a.guard_l1, a.guard_tol = _addr(gw), float(kernel[0] * kernel[1] * kernel[2] * pk.cin), GUARD_TOL    # (l1 bound: K max|w|)
     else:
         # fp16-pair mode: every launch leaves max |out| behind; the fp16-pair launches read their input's
         if arith == "f16x2":
@@ -403,7 +444,7 @@ def _conv_split(x, pk, out, dims, kernel, stride, pad, transposed, residual, res
         a.w_planes, a.guard, a.guard_l1, a.guard_tol = planes.data_ptr(), _addr(gw), (guard_l1(pk) if gw is not None else 0.0), GUARD_TOL
         # the chained 32-channel projection of the output rows in the same launch (csrc: conv_map_rows): the 256-column halo tiles only; with another
         # tile / arithmetic the caller projects in a launch of its own
-        if (chain is not None and conv_tiles.owns_rows(tile) and splits == 1 and residual is None and relu == 0 and not transposed and pk["cout"] == 256
+        if (chain is not None and conv_tiles.owns_rows(tile) and splits == 1 and residual is None and relu == 0 and not transposed and pk.cout == 256
                 and arith in ("f16x2", "bf16x3")):
             mapped = torch.empty((m, 32), dtype=torch.float32, device=x.device)
             a.map_w, a.map_b, a.map_out = chain[0].data_ptr(), chain[1].data_ptr(), mapped.data_ptr()
@@ -411,20 +452,16 @@ def _conv_split(x, pk, out, dims, kernel, stride, pad, transposed, residual, res
     out_amax = AMAX.take(x.device) if want_amax else None
     a.out_amax = _addr(out_amax)
     _launch(flops, lambda: check(lib.ndet_conv_split(a, st), "conv_split"), arith, tile, nbytes)
-    if keep:
-        pk["_partials"] = (ws.view(torch.float32), splits) if splits > 1 else None     # (splits == 1: the launch wrote `out` as usual)
     if want_amax:
         _tag_amax(out, out_amax)
+    if keep_partials:
+        return out, ((ws.view(torch.float32), splits) if keep and splits > 1 else None)     # (splits == 1: the launch wrote `out` as usual)
     return out if mapped is None else (out, mapped)
 
 
 def projection_ok() -> bool:
     """Does the current arithmetic have the chained-projection epilogue (conv2d_nhwc(..., chain=...))?"""
     return ARITHMETIC == "f16x2"
-
-
-def _ptr(t):
-    return c_void_p(0 if t is None else t.data_ptr())
 
 
 def _addr(t):
@@ -468,7 +505,7 @@ def bn_affine(bn: nn.Module):
     return hit[1]
 
 
-def packed(convs: Sequence[nn.Module], bn: Optional[nn.BatchNorm3d] = None):
+def packed(convs: Sequence[nn.Module], bn: Optional[nn.BatchNorm3d] = None) -> ConvPack:
     """Pack (and cache) one conv, or several convs sharing an input concatenated along Cout.  The cache entry is
     rebuilt when any parameter was updated in place (optimizer step, load_state_dict)."""
     tensors = [t for c in convs for t in (c.weight, c.bias) if t is not None]
@@ -490,13 +527,12 @@ def packed(convs: Sequence[nn.Module], bn: Optional[nn.BatchNorm3d] = None):
                           for c in convs])
     scale, shift = fold_bn(bn, bias, cout, w.device)
     c0 = convs[0]
-    val = dict(w=w, scale=scale, shift=shift, cout=cout, cin=w.shape[2], ksize=c0.kernel_size[0], stride=c0.stride[0], transposed=tr,
-               kernel=tuple(c0.kernel_size), strides=tuple(c0.stride), pads=tuple(c0.padding), ndim=len(c0.kernel_size))
+    val = ConvPack(w, cout, w.shape[2], tuple(c0.kernel_size), tuple(c0.stride), tuple(c0.padding), tr, scale, shift)
     store[key] = (stamp, val, convs[1:], bn)  # keep the partner modules alive so their ids stay unique
     return val
 
 
-def packed_linear(lin: nn.Linear, pad_in_to: int = 0):
+def packed_linear(lin: nn.Linear, pad_in_to: int = 0) -> ConvPack:
     """nn.Linear as a 1x1 convolution for the MFMA kernel: weight (Cout, Cin) -> (1, Cout, Cin_padded), bias in the epilogue shift."""
     store = lin.__dict__.setdefault("_ndet_packed", {})
     stamp = (lin.weight.data_ptr(), lin.weight._version, None if lin.bias is None else (lin.bias.data_ptr(), lin.bias._version), pad_in_to)
@@ -514,20 +550,19 @@ def packed_linear(lin: nn.Linear, pad_in_to: int = 0):
     # arith: the point MLPs stay on bf16x3 under the fp16-pair mode.  Their inputs hold the reference's own garbage rows -- nerfdet.py:236-243 divides
     # by (count + 1e-8), so a voxel no view sees carries ~1e9 where the seen ones carry O(1) -- and the fp16-pair scheme is exact only to
     # 2^-40 of the TENSOR's maximum per element (its scale is per tensor): rows 2^-30 below the maximum would keep 10 bits.
-    val = dict(w=w.unsqueeze(0).contiguous(), scale=scale, shift=shift, cout=cout, cin=width, ksize=1, stride=1, transposed=False,
-               kernel=(1, 1), strides=(1, 1), pads=(0, 0), ndim=2, arith="bf16x3")
+    val = ConvPack.gemm(w.unsqueeze(0).contiguous(), cout, width, scale=scale, shift=shift, arith="bf16x3")
     store["linear"] = (stamp, val)
     return val
 
 
-def linear_rows(x: torch.Tensor, pk: dict, relu: int = 0) -> torch.Tensor:
+def linear_rows(x: torch.Tensor, pk: ConvPack, relu: int = 0) -> torch.Tensor:
     """(M, Cin) rows -> (M, Cout): a Linear (+ ReLU) as one launch of the MFMA kernel (bias and ReLU in the epilogue)."""
     assert x.dim() == 2 and x.is_contiguous()
     y = conv2d_nhwc(carry_amax(x, x.view(1, 1, x.shape[0], x.shape[1])), pk, relu=relu)
     return carry_amax(y, y.view(x.shape[0], -1))
 
 
-def conv3d_ndhwc(x: torch.Tensor, pk: dict, residual: Optional[torch.Tensor] = None, relu: int = 0, splits: int = 0, tile: int = 0,
+def conv3d_ndhwc(x: torch.Tensor, pk: ConvPack, residual: Optional[torch.Tensor] = None, relu: int = 0, splits: int = 0, tile: int = 0,
                  amax: bool = True):
     """x (D,H,W,Cin) contiguous fp32 on the GPU -> (OD,OH,OW,Cout).  relu: 0 none, 1 after the residual add, 2 before it.  amax (fp16-pair
     mode): leave max |out| behind for a following convolution -- False for outputs no convolution reads (identity branches, final heads)."""
@@ -535,12 +570,12 @@ def conv3d_ndhwc(x: torch.Tensor, pk: dict, residual: Optional[torch.Tensor] = N
         raise RuntimeError("nerfdet_amd.conv3d: tensors must live on the GPU (no CPU fallback)")
     assert x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32
     d, h, w, cin = x.shape
-    assert cin == pk["cin"], (cin, pk["cin"])
-    k, s, tr, cout = pk["ksize"], pk["stride"], pk["transposed"], pk["cout"]
+    assert cin == pk.cin, (cin, pk.cin)
+    k, s, tr, cout = pk.kernel[0], pk.strides[0], pk.transposed, pk.cout
     if tr:
         od, oh, ow = 2 * d, 2 * h, 2 * w
     else:
-        pad = int(pk["pads"][0]) if "pads" in pk else k // 2
+        pad = int(pk.pads[0])
         assert pad == k // 2 or ARITHMETIC in SPLIT_FAMILY, "the fp32-MFMA family pads by k // 2"
         od, oh, ow = ((v + 2 * pad - k) // s + 1 for v in (d, h, w))
     out = torch.empty((od, oh, ow, cout), dtype=torch.float32, device=x.device)
@@ -561,25 +596,26 @@ def conv3d_ndhwc(x: torch.Tensor, pk: dict, residual: Optional[torch.Tensor] = N
     if splits > 1:
         ws = torch.empty((int(lib.ndet_conv3d_workspace_bytes(d, h, w, cin, cout, k, s, splits)),), dtype=torch.uint8, device=x.device)
     st = c_void_p(raw_stream(x.device))
-    _launch(flops, lambda: check(lib.ndet_conv3d_ndhwc(_ptr(x), _ptr(pk["w"]), _ptr(out), d, h, w, cin, cout, k, s, int(tr), _ptr(pk["scale"]),
-                                                       _ptr(pk["shift"]), _ptr(residual), relu, splits, tile, _ptr(ws), st), "conv3d_ndhwc"), "f32", tile,
-            4 * (x.numel() + pk["w"].numel() + out.numel() + (0 if residual is None else residual.numel())))
+    _launch(flops, lambda: check(lib.ndet_conv3d_ndhwc(_ptr(x), _ptr(pk.w), _ptr(out), d, h, w, cin, cout, k, s, int(tr), _ptr(pk.scale),
+                                                       _ptr(pk.shift), _ptr(residual), relu, splits, tile, _ptr(ws), st), "conv3d_ndhwc"), "f32", tile,
+            4 * (x.numel() + pk.w.numel() + out.numel() + (0 if residual is None else residual.numel())))
     return out
 
 
-def conv2d_nhwc(x: torch.Tensor, pk: dict, residual: Optional[torch.Tensor] = None, relu: int = 0, splits: int = 0, tile: int = 0,
-                residual_up2: bool = False, amax: bool = True, chain=None):
+def conv2d_nhwc(x: torch.Tensor, pk: ConvPack, residual: Optional[torch.Tensor] = None, relu: int = 0, splits: int = 0, tile: int = 0,
+                residual_up2: bool = False, amax: bool = True, chain=None, keep_partials: bool = False):
     """Batch of 2D maps, x (N,H,W,Cin) contiguous fp32 -> (N,OH,OW,Cout): Conv2d (+ eval BatchNorm2d / bias) + ReLU +
     residual in one pass of the MFMA kernel (the batch is the kernel's depth axis with extent-1 taps).
 
     ``chain`` = (map_w (Cout, 32), map_b (32)) (fp16-pair mode, :func:`projection_ok`): returns ``(out, mapped)`` with ``mapped`` (N*OH*OW, 32) the
-    projection of every output row computed in the same launch -- or ``(out, None)`` when the layer's tile cannot take it."""
+    projection of every output row computed in the same launch -- or ``(out, None)`` when the layer's tile cannot take it.  ``keep_partials``
+    (split-family arithmetics, no ``chain``): returns ``(out, partials)`` as :func:`_conv_split` describes."""
     if not x.is_cuda:
         raise RuntimeError("nerfdet_amd.conv3d: tensors must live on the GPU (no CPU fallback)")
-    assert x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32 and pk["ndim"] == 2
+    assert x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32 and pk.ndim == 2
     n, h, w, cin = x.shape
-    assert cin == pk["cin"], (cin, pk["cin"])
-    (kh, kw), (sh, sw), (ph, pw), cout = pk["kernel"], pk["strides"], pk["pads"], pk["cout"]
+    assert cin == pk.cin, (cin, pk.cin)
+    (kh, kw), (sh, sw), (ph, pw), cout = pk.kernel, pk.strides, pk.pads, pk.cout
     oh, ow = (h + 2 * ph - kh) // sh + 1, (w + 2 * pw - kw) // sw + 1
     out = torch.empty((n, oh, ow, cout), dtype=torch.float32, device=x.device)
     if residual is not None:
@@ -593,50 +629,49 @@ def conv2d_nhwc(x: torch.Tensor, pk: dict, residual: Optional[torch.Tensor] = No
         if chain is not None and not projection_ok():
             chain = None
         r = _conv_split(x, pk, out, (n, h, w), (1, kh, kw), (1, sh, sw), (0, ph, pw), False, residual, residual_up2, relu, splits, tile, m,
-                        kh * kw * (cin // 32), 2 * m * cout * cin * kh * kw, amax, chain)
+                        kh * kw * (cin // 32), 2 * m * cout * cin * kh * kw, amax, chain, keep_partials)
         return r if (not pair or isinstance(r, tuple)) else (r, None)
+    assert not keep_partials
     tile, splits = choose_tiling(m, cout, kh * kw * (cin // 32), tile, splits)
     ws = torch.empty((m * cout * splits * 4,), dtype=torch.uint8, device=x.device) if splits > 1 else None
-    i3 = lambda a, b, c: (ctypes.c_int * 3)(a, b, c)
     st = c_void_p(raw_stream(x.device))
     lib = _lib.load()
     _launch(2 * m * cout * cin * kh * kw,
-            lambda: check(lib.ndet_conv_ndhwc(_ptr(x), _ptr(pk["w"]), _ptr(out), n, h, w, cin, cout, i3(1, kh, kw), i3(1, sh, sw), i3(0, ph, pw),
-                                              _ptr(pk["scale"]), _ptr(pk["shift"]), _ptr(residual), int(residual_up2), relu, splits, tile, _ptr(ws), st),
-                          "conv2d_nhwc"), "f32", tile, 4 * (x.numel() + pk["w"].numel() + out.numel() + (0 if residual is None else residual.numel())))
+            lambda: check(lib.ndet_conv_ndhwc(_ptr(x), _ptr(pk.w), _ptr(out), n, h, w, cin, cout, i3(1, kh, kw), i3(1, sh, sw), i3(0, ph, pw),
+                                              _ptr(pk.scale), _ptr(pk.shift), _ptr(residual), int(residual_up2), relu, splits, tile, _ptr(ws), st),
+                          "conv2d_nhwc"), "f32", tile, 4 * (x.numel() + pk.w.numel() + out.numel() + (0 if residual is None else residual.numel())))
     return (out, None) if pair else out
 
 
 CHAIN_BOTTLENECKS = True    # conv2 -> conv3 of the 64- / 128-channel bottlenecks in one launch (k_conv_split_chain)
 
 
-def chain_ok(pk: dict, pk3: dict) -> bool:
+def chain_ok(pk: ConvPack, pk3: ConvPack) -> bool:
     """The chained kernel holds ALL output channels of the first convolution in one 128 x 64 / 128 x 128 tile and multiplies them by a
     1x1 layer: a 2D convolution to 64 / 128 channels followed by a stride-1 1x1 layer to a multiple of 64, in the bf16 family."""
-    return (CHAIN_BOTTLENECKS and ARITHMETIC in SPLIT_FAMILY and pk["ndim"] == 2 and pk3["ndim"] == 2 and pk["cout"] in (64, 128)
-            and not pk["transposed"] and tuple(pk3["kernel"]) == (1, 1) and tuple(pk3["strides"]) == (1, 1) and pk3["cin"] == pk["cout"]
-            and pk3["cout"] % 64 == 0 and pk["cin"] % 32 == 0 and pk["scale"] is not None and pk3["scale"] is not None)
+    return (CHAIN_BOTTLENECKS and ARITHMETIC in SPLIT_FAMILY and pk.ndim == 2 and pk3.ndim == 2 and pk.cout in (64, 128)
+            and not pk.transposed and tuple(pk3.kernel) == (1, 1) and tuple(pk3.strides) == (1, 1) and pk3.cin == pk.cout
+            and pk3.cout % 64 == 0 and pk.cin % 32 == 0 and pk.scale is not None and pk3.scale is not None)
 
 
-def conv2d_chain_nhwc(x: torch.Tensor, pk: dict, pk3: dict, residual: Optional[torch.Tensor] = None, relu: int = 1) -> torch.Tensor:
+def conv2d_chain_nhwc(x: torch.Tensor, pk: ConvPack, pk3: ConvPack, residual: Optional[torch.Tensor] = None, relu: int = 1) -> torch.Tensor:
     """relu_mode(bn3(conv1x1(relu(bn(conv(x))))) + residual) in ONE launch (csrc/conv_split_kernels.hip::k_conv_split_chain): conv2 -> conv3 of a
     ResNet bottleneck without the intermediate's round trip through HBM.  x (N,H,W,Cin) contiguous fp32 -> (N,OH,OW,pk3 cout)."""
     if not x.is_cuda:
         raise RuntimeError("nerfdet_amd.conv3d: tensors must live on the GPU (no CPU fallback)")
     assert chain_ok(pk, pk3) and x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32
     n, h, w, cin = x.shape
-    assert cin == pk["cin"], (cin, pk["cin"])
-    (kh, kw), (sh, sw), (ph, pw), mid, cout = pk["kernel"], pk["strides"], pk["pads"], pk["cout"], pk3["cout"]
+    assert cin == pk.cin, (cin, pk.cin)
+    (kh, kw), (sh, sw), (ph, pw), mid, cout = pk.kernel, pk.strides, pk.pads, pk.cout, pk3.cout
     oh, ow = (h + 2 * ph - kh) // sh + 1, (w + 2 * pw - kw) // sw + 1
     out = torch.empty((n, oh, ow, cout), dtype=torch.float32, device=x.device)
     if residual is not None:
         assert tuple(residual.shape) == tuple(out.shape) and residual.is_contiguous(), (tuple(residual.shape), tuple(out.shape))
     m = n * oh * ow
-    i3 = lambda a, b, c: (ctypes.c_int * 3)(a, b, c)
     st = c_void_p(raw_stream(x.device))
     lib = _lib.load()
     flops = 2 * m * mid * (cin * kh * kw + cout)
-    nbytes = 4 * (x.numel() + pk["w"].numel() + pk3["w"].numel() + out.numel() + (0 if residual is None else residual.numel()))
+    nbytes = 4 * (x.numel() + pk.w.numel() + pk3.w.numel() + out.numel() + (0 if residual is None else residual.numel()))
     if ARITHMETIC == "f16x2":
         (p1, w1inv), (p3, w3inv) = split_planes_f16(pk), split_planes_f16(pk3)
         in_amax, out_amax = amax_of(x), (None if NO_AMAX_COMMIT else AMAX.take(x.device))
@@ -647,8 +682,8 @@ def conv2d_chain_nhwc(x: torch.Tensor, pk: dict, pk3: dict, residual: Optional[t
         (p1, w1inv), (p3, w3inv) = (split_planes(pk), 1.0), (split_planes(pk3), 1.0)
         in_amax = out_amax = gw = None
         gl1 = gl3 = tol = 0.0
-    _launch(flops, lambda: check(lib.ndet_conv_chain(_ptr(x), _ptr(p1), n, h, w, cin, mid, i3(1, kh, kw), i3(1, sh, sw), i3(0, ph, pw), _ptr(pk["scale"]),
-                                                     _ptr(pk["shift"]), _ptr(p3), cout, _ptr(pk3["scale"]), _ptr(pk3["shift"]), _ptr(residual), relu, _ptr(out),
+    _launch(flops, lambda: check(lib.ndet_conv_chain(_ptr(x), _ptr(p1), n, h, w, cin, mid, i3(1, kh, kw), i3(1, sh, sw), i3(0, ph, pw), _ptr(pk.scale),
+                                                     _ptr(pk.shift), _ptr(p3), cout, _ptr(pk3.scale), _ptr(pk3.shift), _ptr(residual), relu, _ptr(out),
                                                      ARITH_ID[ARITHMETIC], _ptr(in_amax), w1inv, w3inv, _ptr(out_amax), gl1, gl3, tol, _ptr(gw), st), "conv_chain"),
             nbytes=nbytes, name=f"k_conv_split_chain<{mid}>" + ("/f16x2" if ARITHMETIC == "f16x2" else ""))
     if out_amax is not None:
@@ -659,31 +694,31 @@ def conv2d_chain_nhwc(x: torch.Tensor, pk: dict, pk3: dict, residual: Optional[t
 FUSE_BOTTLENECKS = True     # the whole stage-1 bottleneck (conv1 -> conv2 -> conv3 + identity / downsample) in one launch (k_bottleneck_f16x2)
 
 
-def bottleneck_ok(x: torch.Tensor, pk1: dict, pk2: dict, pk3: dict, pkd: Optional[dict]) -> bool:
+def bottleneck_ok(x: torch.Tensor, pk1: ConvPack, pk2: ConvPack, pk3: ConvPack, pkd: Optional[ConvPack]) -> bool:
     """Shapes csrc/bottleneck_kernels.hip takes: fp16-pair arithmetic, a 64-channel 3x3 stride-1 middle convolution between two 1x1 layers, frozen
     BatchNorm on all of them, identity residual (Cin == Cout) or a stride-1 1x1 downsample of a 64-channel input."""
     def one(pk):
-        return pk["ndim"] == 2 and tuple(pk["kernel"]) == (1, 1) and tuple(pk["strides"]) == (1, 1) and not pk["transposed"] and pk["scale"] is not None
+        return pk.ndim == 2 and tuple(pk.kernel) == (1, 1) and tuple(pk.strides) == (1, 1) and not pk.transposed and pk.scale is not None
     if not (FUSE_BOTTLENECKS and ARITHMETIC == "f16x2" and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
         return False
-    if not (one(pk1) and one(pk3) and pk2["ndim"] == 2 and tuple(pk2["kernel"]) == (3, 3) and tuple(pk2["strides"]) == (1, 1) and tuple(pk2["pads"]) == (1, 1)
-            and pk2["scale"] is not None and pk1["cout"] == 64 and pk2["cin"] == 64 and pk2["cout"] == 64 and pk3["cin"] == 64 and pk3["cout"] % 32 == 0
-            and pk1["cin"] % 32 == 0 and pk1["cin"] == x.shape[3]):
+    if not (one(pk1) and one(pk3) and pk2.ndim == 2 and tuple(pk2.kernel) == (3, 3) and tuple(pk2.strides) == (1, 1) and tuple(pk2.pads) == (1, 1)
+            and pk2.scale is not None and pk1.cout == 64 and pk2.cin == 64 and pk2.cout == 64 and pk3.cin == 64 and pk3.cout % 32 == 0
+            and pk1.cin % 32 == 0 and pk1.cin == x.shape[3]):
         return False
     if pkd is not None:
-        if not (one(pkd) and pkd["cin"] == 64 and pk1["cin"] == 64 and pkd["cout"] == pk3["cout"]):
+        if not (one(pkd) and pkd.cin == 64 and pk1.cin == 64 and pkd.cout == pk3.cout):
             return False
-    elif pk1["cin"] != pk3["cout"]:
+    elif pk1.cin != pk3.cout:
         return False
-    return x.numel() // x.shape[3] * max(pk1["cin"], pk3["cout"]) * 4 < 0xfffffff0
+    return x.numel() // x.shape[3] * max(pk1.cin, pk3.cout) * 4 < 0xfffffff0
 
 
-def conv2d_bottleneck_nhwc(x: torch.Tensor, pk1: dict, pk2: dict, pk3: dict, pkd: Optional[dict] = None) -> torch.Tensor:
+def conv2d_bottleneck_nhwc(x: torch.Tensor, pk1: ConvPack, pk2: ConvPack, pk3: ConvPack, pkd: Optional[ConvPack] = None) -> torch.Tensor:
     """relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1(x)))))))) + identity) of a stage-1 ResNet bottleneck in ONE launch (csrc/bottleneck_kernels.hip);
     identity = x, or bnD(convD(x)) with ``pkd``.  x (N,H,W,Cin) contiguous fp32 -> (N,H,W,pk3 cout)."""
     assert bottleneck_ok(x, pk1, pk2, pk3, pkd)
     n, h, w, cin = x.shape
-    cout = pk3["cout"]
+    cout = pk3.cout
     out = torch.empty((n, h, w, cout), dtype=torch.float32, device=x.device)
     lib = _lib.load()
     st = c_void_p(raw_stream(x.device))
@@ -695,16 +730,12 @@ def conv2d_bottleneck_nhwc(x: torch.Tensor, pk1: dict, pk2: dict, pk3: dict, pkd
     gl = (ctypes.c_float * 4)(*([guard_l1(pk1), guard_l1(pk2), guard_l1(pk3), guard_l1(pkd) if pkd is not None else 0.0] if gw is not None else [0.0] * 4))
     m = n * h * w
     flops = 2 * m * 64 * (cin + 9 * 64 + cout) + (2 * m * cin * cout if pkd is not None else 0)
-    nbytes = 4 * (x.numel() + out.numel() + sum(pk["w"].numel() for pk in (pk1, pk2, pk3) + ((pkd,) if pkd is not None else ())))
-    name = "k_bottleneck/f16x2"
-    thunk = lambda: check(lib.ndet_bottleneck_f16x2(_ptr(x), n, h, w, cin, cout, _ptr(p1), i1, _ptr(pk1["scale"]), _ptr(pk1["shift"]), _ptr(p2), i2,
-                                                    _ptr(pk2["scale"]), _ptr(pk2["shift"]), _ptr(p3), i3, _ptr(pk3["scale"]), _ptr(pk3["shift"]), _ptr(pd), idd,
-                                                    _ptr(None if pkd is None else pkd["scale"]), _ptr(None if pkd is None else pkd["shift"]), _ptr(in_amax),
-                                                    _ptr(out_amax), _ptr(out), gl, GUARD_TOL, _ptr(gw), st), "bottleneck_f16x2")
-    if launch_hook is not None:
-        launch_hook(flops, thunk, name)
-    else:
-        trace.span(name, thunk, flops=flops, bytes=nbytes, kind="conv")
+    nbytes = 4 * (x.numel() + out.numel() + sum(pk.w.numel() for pk in (pk1, pk2, pk3) + ((pkd,) if pkd is not None else ())))
+    _launch(flops, lambda: check(lib.ndet_bottleneck_f16x2(_ptr(x), n, h, w, cin, cout, _ptr(p1), i1, _ptr(pk1.scale), _ptr(pk1.shift), _ptr(p2), i2,
+                                                           _ptr(pk2.scale), _ptr(pk2.shift), _ptr(p3), i3, _ptr(pk3.scale), _ptr(pk3.shift), _ptr(pd), idd,
+                                                           _ptr(None if pkd is None else pkd.scale), _ptr(None if pkd is None else pkd.shift), _ptr(in_amax),
+                                                           _ptr(out_amax), _ptr(out), gl, GUARD_TOL, _ptr(gw), st), "bottleneck_f16x2"),
+            nbytes=nbytes, name="k_bottleneck/f16x2")
     if out_amax is not None:
         _tag_amax(out, out_amax)
     return out

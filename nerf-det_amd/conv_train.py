@@ -16,28 +16,32 @@ Transposed convolutions stay on the vendor library.  BatchNorm in training mode 
 the same channels-last memory; nothing is copied between layouts."""
 from __future__ import annotations
 
-from typing import Sequence, Tuple
+import weakref
+from typing import Sequence
 
 import torch
 from torch import nn
 
-from . import conv3d as C
-from ._lib import raw_stream
+from . import _lib, conv3d as C
+from ._lib import _ptr, _stream, i3
+from .conv3d import ConvPack
 
 Tensor = torch.Tensor
 
 
-def _raw_pack(w_taps_co_ci: Tensor, kernel: Sequence[int], stride: int = 1, pads=None) -> dict:
-    """Pack dict of nerfdet_amd.conv3d for a bare weight already in (taps, Cout, Cin) order: no BatchNorm, no bias."""
+def _geometry(kernel: Sequence[int], stride: int, pads) -> tuple:
+    """(kernel, strides, pads) of a ConvPack for a uniform stride; same-padded unless ``pads`` says otherwise."""
     k = tuple(int(v) for v in kernel)
-    ndim = len(k)
-    return dict(w=w_taps_co_ci.contiguous().float(), scale=None, shift=None, cout=int(w_taps_co_ci.shape[1]), cin=int(w_taps_co_ci.shape[2]),
-                ksize=k[0], stride=stride, transposed=False, kernel=k, strides=(stride,) * ndim,
-                pads=tuple(v // 2 for v in k) if pads is None else tuple(pads), ndim=ndim, arith="bf16x3")
+    return k, (stride,) * len(k), tuple(v // 2 for v in k) if pads is None else tuple(pads)
+
+
+def _raw_pack(w_taps_co_ci: Tensor, kernel: Sequence[int], stride: int = 1, pads=None, scale=None, shift=None) -> ConvPack:
+    """Pack for a bare weight already in (taps, Cout, Cin) order (the fp32-MFMA family: no planes)."""
+    return ConvPack(w_taps_co_ci.contiguous().float(), int(w_taps_co_ci.shape[1]), int(w_taps_co_ci.shape[2]), *_geometry(kernel, stride, pads),
+                    scale=scale, shift=shift, arith="bf16x3")
 
 
 _STEP_SLOTS = {}      # (weight address, version) -> amax slot, filled by prepare_step for ONE step (cleared by the next call)
-import weakref
 
 _STEP_PARAMS = weakref.WeakKeyDictionary()     # model -> its convolution modules (the entry goes with the model: no model is kept alive by it)
 
@@ -85,42 +89,38 @@ def _split_both(w: Tensor, taps: int, arith: str, want_adjoint: bool):
     """(planes, adjoint planes or None, amax slot or None) of the torch-layout weight ``w``: ONE launch writes both packs
     (ndet_split_weights_train); the forward hands the adjoint planes to its backward through the autograd context, so a step splits each weight
     once.  fp16-pair: the scale comes from the weight's amax slot (one ndet_amax_f32 launch); nothing is read back to the host."""
-    from ctypes import c_void_p
-    from . import _lib
     cout, cin = int(w.shape[0]), int(w.shape[1])
     npl = 2 if arith == "f16x2" else 3
     planes = torch.empty((taps, cin // 32, npl, cout, 32), dtype=torch.int16, device=w.device)
     adj = torch.empty((taps, (cout + 31) // 32, npl, cin, 32), dtype=torch.int16, device=w.device) if want_adjoint else None
     wc = w.contiguous()
-    st = c_void_p(raw_stream(w.device))
+    st = _stream(w)
     slot = None
     if arith == "f16x2":
         slot = _step_slot(w)
         if slot is None:
             slot = C.AMAX.take(w.device)
-            _lib.check(_lib.load().ndet_amax_f32(c_void_p(wc.data_ptr()), wc.numel(), c_void_p(slot.data_ptr()), st), "amax_f32")
-    _lib.check(_lib.load().ndet_split_weights_train(c_void_p(wc.data_ptr()), taps, cout, cin, 1 if arith == "f16x2" else 0, c_void_p(0 if slot is None else slot.data_ptr()),
-                                                    c_void_p(planes.data_ptr()), c_void_p(0 if adj is None else adj.data_ptr()), st), "split_weights_train")
+            _lib.check(_lib.load().ndet_amax_f32(_ptr(wc), wc.numel(), _ptr(slot), st), "amax_f32")
+    _lib.check(_lib.load().ndet_split_weights_train(_ptr(wc), taps, cout, cin, 1 if arith == "f16x2" else 0, _ptr(slot), _ptr(planes), _ptr(adj), st),
+               "split_weights_train")
     return planes, adj, slot
 
 
-def _plane_pack(w: Tensor, planes: Tensor, slot, arith: str, kernel, adjoint: bool, stride: int = 1, pads=None) -> dict:
+def _plane_pack(w: Tensor, planes: Tensor, slot, arith: str, kernel, adjoint: bool, stride: int = 1, pads=None, scale=None, shift=None) -> ConvPack:
+    """Pack around pre-built planes of the torch-layout weight ``w`` (``adjoint``: its data gradient's); fp16-pair planes carry the slot they were scaled by."""
     cout, cin = int(w.shape[0]), int(w.shape[1])
     no, ki = (cin, (cout + 31) // 32 * 32) if adjoint else (cout, cin)
-    k = tuple(int(v) for v in kernel)
-    pk = dict(w=w, scale=None, shift=None, cout=no, cin=ki, ksize=k[0], stride=stride, transposed=False, kernel=k,
-              strides=(stride,) * len(k), pads=tuple(v // 2 for v in k) if pads is None else tuple(pads), ndim=len(k), arith="bf16x3")
     if arith == "f16x2":
-        pk.update(arith="f16x2", w_f16=(planes, 1.0), w_amax=slot, keep_amax=True)
+        policy = dict(arith="f16x2", planes_f16=(planes, 1.0), w_amax=slot, keep_amax=True)
     else:
-        pk["w_split"] = planes
-    return pk
+        policy = dict(arith="bf16x3", planes_bf16=planes)
+    return ConvPack(w, no, ki, *_geometry(kernel, stride, pads), scale=scale, shift=shift, **policy)
 
 
-def _train_pack(w: Tensor, kernel, adjoint: bool, stride: int = 1, pads=None, want_adjoint: bool = False) -> dict:
-    """Pack dict for the layer (or, ``adjoint``, for its data gradient) straight from the torch-layout weight.  Split-family kernels: one launch
-    writes the layer's planes and -- ``want_adjoint`` -- its data gradient's, returned under ``"_adjoint"`` for :func:`_adjoint_pack`; the
-    fp32-MFMA family goes through the generic packer."""
+def _train_pack(w: Tensor, kernel, adjoint: bool, stride: int = 1, pads=None, want_adjoint: bool = False, scale=None, shift=None):
+    """``(pack, handed)``: the pack for the layer (or, ``adjoint``, for its data gradient) straight from the torch-layout weight, ``scale`` / ``shift``
+    in its epilogue.  Split-family kernels: one launch writes the layer's planes and -- ``want_adjoint`` -- its data gradient's, which ``handed``
+    carries to :func:`_adjoint_pack` (None when not asked for); the fp32-MFMA family goes through the generic packer."""
     cout, cin = int(w.shape[0]), int(w.shape[1])
     taps = 1
     for v in kernel:
@@ -128,37 +128,33 @@ def _train_pack(w: Tensor, kernel, adjoint: bool, stride: int = 1, pads=None, wa
     arith = C.train_arithmetic()
     if arith not in ("bf16x3", "bf16", "f16x2"):
         if not adjoint:
-            return _raw_pack(C.pack_weight(w), kernel, stride, pads)
+            return _raw_pack(C.pack_weight(w), kernel, stride, pads, scale, shift), None
         flip = w.flip(tuple(range(2, w.dim()))).transpose(0, 1)
         if cout % 32:
             flip = torch.nn.functional.pad(flip, (0, 0) * (w.dim() - 2) + (0, 32 - cout % 32))
-        return _raw_pack(C.pack_weight(flip), kernel)
+        return _raw_pack(C.pack_weight(flip), kernel), None
     if taps <= 27:
         planes, adj, slot = _split_both(w, taps, arith, adjoint or want_adjoint)
-        pk = _plane_pack(w, adj if adjoint else planes, slot, arith, kernel, adjoint, stride, pads)
-        if want_adjoint and not adjoint:
-            pk["_adjoint"] = (adj, slot, arith)
-        return pk
+        pk = _plane_pack(w, adj if adjoint else planes, slot, arith, kernel, adjoint, stride, pads, scale, shift)
+        return pk, ((adj, slot, arith) if want_adjoint and not adjoint else None)
     # more taps than one workgroup's LDS block takes (none among the shipped models' trainable layers): one pack per launch, six-product arithmetic
-    from ctypes import c_void_p
-    from . import _lib
     no, ki = (cin, (cout + 31) // 32 * 32) if adjoint else (cout, cin)
     planes = torch.empty((taps, ki // 32, 3, no, 32), dtype=torch.int16, device=w.device)
     wc = w.contiguous()
-    _lib.check(_lib.load().ndet_split_weights_bf16x3_torch(c_void_p(wc.data_ptr()), taps, cout, cin, int(adjoint), c_void_p(planes.data_ptr()),
-                                                           c_void_p(raw_stream(w.device))), "split_weights_torch")
-    return _plane_pack(w, planes, None, "bf16x3", kernel, adjoint, stride, pads)
+    _lib.check(_lib.load().ndet_split_weights_bf16x3_torch(_ptr(wc), taps, cout, cin, int(adjoint), _ptr(planes), _stream(w)),
+               "split_weights_torch")
+    return _plane_pack(w, planes, None, "bf16x3", kernel, adjoint, stride, pads, scale, shift), None
 
 
-def _adjoint_pack(handed, w: Tensor, kernel) -> dict:
-    """The data gradient's pack: the planes the forward wrote alongside its own (``handed`` = its ``"_adjoint"`` entry), or a fresh split."""
+def _adjoint_pack(handed, w: Tensor, kernel) -> ConvPack:
+    """The data gradient's pack: the planes the forward wrote alongside its own (``handed`` by its :func:`_train_pack`), or a fresh split."""
     if handed is not None and handed[2] == C.train_arithmetic():
         return _plane_pack(w, handed[0], handed[1], handed[2], kernel, True)
-    return _train_pack(w, kernel, True)
+    return _train_pack(w, kernel, True)[0]
 
 
-def _conv(x: Tensor, pk: dict) -> Tensor:
-    return C.conv3d_ndhwc(x, pk) if pk["ndim"] == 3 else C.conv2d_nhwc(x, pk)
+def _conv(x: Tensor, pk: ConvPack, **kw) -> Tensor:
+    return (C.conv3d_ndhwc if pk.ndim == 3 else C.conv2d_nhwc)(x, pk, **kw)
 
 
 def eligible(conv: nn.Module, x: Tensor) -> bool:
@@ -182,14 +178,10 @@ IMPLICIT_MIN_TAPS = 9     # fewer taps: the staged form (its GEMM runs on the fa
 
 def _rows(x: Tensor, k3, stride3, pads, t0: int, n_taps: int, lrow: int) -> Tensor:
     """csrc/pipeline_kernels.hip::k_wgrad_rows: (D,H,W,C) -> (n_taps, C, lrow) channel-major rows over the convolution's output grid."""
-    import ctypes
-    from ctypes import c_void_p
-    from . import _lib
     d, h, w, c = x.shape
     out = torch.empty((n_taps, c, lrow), dtype=torch.float32, device=x.device)
-    i3 = lambda v: (ctypes.c_int * 3)(*v)
-    _lib.check(_lib.load().ndet_wgrad_rows(c_void_p(x.data_ptr()), d, h, w, c, i3(k3), i3(stride3), i3(pads), t0, n_taps, lrow,
-                                           c_void_p(out.data_ptr()), c_void_p(raw_stream(x.device))), "wgrad_rows")
+    _lib.check(_lib.load().ndet_wgrad_rows(_ptr(x), d, h, w, c, i3(*k3), i3(*stride3), i3(*pads), t0, n_taps, lrow, _ptr(out),
+                                           _stream(x)), "wgrad_rows")
     return out
 
 
@@ -199,11 +191,8 @@ def _to_torch_layout(dw_rows: Tensor, taps: int, cin: int, cout: int, kernel, sp
     if taps > 27 or cin % 32:
         assert splits == 1
         return dw_rows.view(taps, cin, cout).permute(2, 1, 0).reshape(cout, cin, *kernel)
-    from ctypes import c_void_p
-    from . import _lib
     out = torch.empty((cout, cin) + tuple(kernel), dtype=torch.float32, device=dw_rows.device)
-    _lib.check(_lib.load().ndet_wgrad_to_torch(c_void_p(dw_rows.data_ptr()), splits, taps, cout, cin, c_void_p(out.data_ptr()),
-                                               c_void_p(raw_stream(dw_rows.device))), "wgrad_to_torch")
+    _lib.check(_lib.load().ndet_wgrad_to_torch(_ptr(dw_rows), splits, taps, cout, cin, _ptr(out), _stream(dw_rows)), "wgrad_to_torch")
     return out
 
 
@@ -226,36 +215,26 @@ def weight_grad(x: Tensor, g: Tensor, kernel: Sequence[int], stride: int = 1, pa
     x_slot = dy_slot = None
     if f16:
         dy_slot, x_slot = C.amax_of(g), C.amax_of(x)          # device slots; the scales and their inverses never leave the device
+    st = _stream(x)
     if FUSED_DY_PLANES and arith in ("bf16x3", "bf16", "f16x2"):
-        from ctypes import c_void_p
-        from . import _lib
-        st = c_void_p(raw_stream(x.device))
         planes = torch.empty((1, lrow // 32, 2 if f16 else 3, cout, 32), dtype=torch.int16, device=x.device)     # one pass: transpose + split
         if f16:
-            _lib.check(_lib.load().ndet_wgrad_dy_planes_f16x2(c_void_p(g.data_ptr()), lo, cout, lrow, c_void_p(dy_slot.data_ptr()), c_void_p(planes.data_ptr()), st),
-                       "wgrad_dy_planes_f16x2")
+            _lib.check(_lib.load().ndet_wgrad_dy_planes_f16x2(_ptr(g), lo, cout, lrow, _ptr(dy_slot), _ptr(planes), st), "wgrad_dy_planes_f16x2")
             # (no range guard: its bound, 2^-39 max|x| L max|dy|, is an absolute floor on a SUM over L output voxels -- for a weight gradient
             # the error that matters is relative to that sum's own size, and the bound trips on every early layer)
-            pk = dict(w=planes, w_f16=(planes, 1.0), w_amax=dy_slot, guard=False, scale=None, shift=None, cout=cout, cin=lrow, ksize=1, stride=1, transposed=False,
-                      kernel=(1, 1), strides=(1, 1), pads=(0, 0), ndim=2, arith="f16x2")
+            pk = ConvPack.gemm(planes, cout, lrow, arith="f16x2", planes_f16=(planes, 1.0), w_amax=dy_slot, guard=False)
         else:
-            _lib.check(_lib.load().ndet_wgrad_dy_planes(c_void_p(g.data_ptr()), lo, cout, lrow, c_void_p(planes.data_ptr()), st), "wgrad_dy_planes")
-            pk = dict(w=planes, w_split=planes, scale=None, shift=None, cout=cout, cin=lrow, ksize=1, stride=1, transposed=False, kernel=(1, 1),
-                      strides=(1, 1), pads=(0, 0), ndim=2, arith="bf16x3")
+            _lib.check(_lib.load().ndet_wgrad_dy_planes(_ptr(g), lo, cout, lrow, _ptr(planes), st), "wgrad_dy_planes")
+            pk = ConvPack.gemm(planes, cout, lrow, arith="bf16x3", planes_bf16=planes)
     else:
-        grows = _rows(g, (1, 1, 1), (1, 1, 1), (0, 0, 0), 0, 1, lrow)
-        pk = dict(w=grows, scale=None, shift=None, cout=cout, cin=lrow, ksize=1, stride=1, transposed=False, kernel=(1, 1), strides=(1, 1),
-                  pads=(0, 0), ndim=2, arith="bf16x3")
+        pk = ConvPack.gemm(_rows(g, (1, 1, 1), (1, 1, 1), (0, 0, 0), 0, 1, lrow), cout, lrow, arith="bf16x3")
     if implicit is None:
         implicit = IMPLICIT_WGRAD and taps >= IMPLICIT_MIN_TAPS and lo >= 16384
     if implicit and arith in ("bf16x3", "bf16", "f16x2") and cin % 64 == 0:
         # multi-tap layers on large grids: x read in place (csrc/conv_split_kernels.hip::k_wgrad_split), no tap copies -- there the staged
         # form writes and re-reads taps x the input (707 MB for a 3x3x3 layer at 40x40x16x256); on small grids and 1x1 layers the staged
         # GEMM runs on the faster tiles and wins (tools/bench_wgrad.py)
-        import ctypes
-        from ctypes import c_void_p
-        from . import _lib
-        planes = pk["w_f16"][0] if f16 else C.split_planes(pk)
+        planes = pk.planes_f16[0] if f16 else C.split_planes(pk)
         bm = 128 if cin % 128 == 0 else 64
         bn = 256 if (f16 and bm == 128 and cout % 256 == 0 and taps * (cin // 128) >= 32) else (128 if cout > 64 else 64)      # (the library's own choice: ndet_wgrad_split)
         tiles = (taps * cin // bm) * ((cout + bn - 1) // bn)
@@ -269,26 +248,24 @@ def weight_grad(x: Tensor, g: Tensor, kernel: Sequence[int], stride: int = 1, pa
         ws = torch.empty((splits * m * cout,), dtype=torch.float32, device=x.device) if splits > 1 else None
         keep = f16 and splits > 1 and taps <= 27       # the partials go straight to ndet_wgrad_to_torch: no reduction pass, no (m, cout) intermediate
         dw = None if keep else torch.empty((m, cout), dtype=torch.float32, device=x.device)
-        i3 = lambda v: (ctypes.c_int * 3)(*v)
-        st = c_void_p(raw_stream(x.device))
-        _lib.check(_lib.load().ndet_wgrad_split(c_void_p(x.data_ptr()), d, h, w, cin, i3(k3), i3(s3), i3(pads), c_void_p(planes.data_ptr()), cout, lrow,
-                                                splits, C.ARITH_ID[arith], C._ptr(x_slot), C._ptr(dy_slot), C._ptr(ws), C._ptr(ws if keep else dw), int(keep), st),
-                   "wgrad_split")
+        _lib.check(_lib.load().ndet_wgrad_split(_ptr(x), d, h, w, cin, i3(*k3), i3(*s3), i3(*pads), _ptr(planes), cout, lrow, splits, C.ARITH_ID[arith],
+                                                _ptr(x_slot), _ptr(dy_slot), _ptr(ws), _ptr(ws if keep else dw), int(keep), st), "wgrad_split")
         if keep:
             return _to_torch_layout(ws, taps, cin, cout, kernel, splits)
         return _to_torch_layout(dw, taps, cin, cout, kernel)
     per = max(1, min(taps, (1 << 30) // (cin * lrow * 4)))  # the kernel addresses its operand with 32-bit byte offsets: <= 1 GiB per launch
-    if f16 and per >= taps and taps <= 27 and cin % 32 == 0:
-        pk["keep_partials"] = True                          # one GEMM: its split-K partials are added by ndet_wgrad_to_torch (no reduction pass)
+    keep = f16 and per >= taps and taps <= 27 and cin % 32 == 0      # one GEMM: its split-K partials are added by ndet_wgrad_to_torch (no reduction pass)
     parts = []
     for t0 in range(0, taps, per):
         a_all = _rows(x, k3, s3, pads, t0, min(per, taps - t0), lrow)          # rows (t, ci): x sampled at tap t of every output voxel
         if f16:
             C._tag_amax(a_all, x_slot)                                         # copies of x's elements and zeros: max |rows| <= max |x|
-        parts.append(C.linear_rows(C.carry_amax(a_all, a_all.view(-1, lrow)), pk))     # (taps*Cin, Cout): the sum over the output voxels
-    kept = pk.pop("_partials", None)
-    if kept is not None:
-        return _to_torch_layout(kept[0], taps, cin, cout, kernel, kept[1])
+        y = C.conv2d_nhwc(C.carry_amax(a_all, a_all.view(1, 1, -1, lrow)), pk, keep_partials=keep)    # (taps*Cin, Cout): the sum over the output voxels
+        if keep:
+            y, kept = y
+            if kept is not None:
+                return _to_torch_layout(kept[0], taps, cin, cout, kernel, kept[1])
+        parts.append(y.view(-1, cout))
     dw = parts[0] if len(parts) == 1 else torch.cat(parts)
     return _to_torch_layout(dw, taps, cin, cout, kernel)
 
@@ -325,6 +302,22 @@ def _dgrad_strided(g: Tensor, x: Tensor, w: Tensor, kernel, stride: int, handed=
     return _conv(up, _adjoint_pack(handed, w, kernel))
 
 
+def _conv_grads(ctx, x: Tensor, w: Tensor, g: Tensor):
+    """(dx, dw) of y = conv(x, w) from g = dL/dy, each None when autograd does not need it (ctx: kernel, stride, adjoint, needs_input_grad[0:2])."""
+    dx = dw = None
+    if ctx.needs_input_grad[0]:
+        if ctx.stride == 1:
+            # the adjoint convolution: W'[ci, co, t] = W[co, ci, flip(t)]; the kernel steps its input channels by 32, so dy (and W')
+            # are zero-padded when Cout is not a multiple
+            gd = g if g.shape[-1] % 32 == 0 else torch.nn.functional.pad(g, (0, 32 - g.shape[-1] % 32))
+            dx = _conv(gd, _adjoint_pack(ctx.adjoint, w, ctx.kernel))
+        else:
+            dx = _dgrad_strided(g, x, w, ctx.kernel, ctx.stride, ctx.adjoint)
+    if ctx.needs_input_grad[1]:
+        dw = weight_grad(x, g, ctx.kernel, ctx.stride)
+    return dx, dw
+
+
 class ConvS1(torch.autograd.Function):
     """y = conv(x, weight) for channels-last x (D,H,W,Cin) / (N,H,W,Cin) and a torch-layout weight; see the module docstring."""
 
@@ -335,26 +328,13 @@ class ConvS1(torch.autograd.Function):
         w = weight.detach()
         xc = C.carry_amax(x, x.detach().contiguous())           # the backward kernels index it densely
         ctx.save_for_backward(xc, w)
-        pk = _train_pack(w, kernel, False, int(stride), want_adjoint=ctx.needs_input_grad[0])
-        ctx.adjoint = pk.pop("_adjoint", None)
+        pk, ctx.adjoint = _train_pack(w, kernel, False, int(stride), want_adjoint=ctx.needs_input_grad[0])
         return _conv(xc, pk)
 
     @staticmethod
     def backward(ctx, g):
         x, w = ctx.saved_tensors
-        g = g.contiguous().float()
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            if ctx.stride == 1:
-                # the adjoint convolution: W'[ci, co, t] = W[co, ci, flip(t)]; the kernel steps its input channels by 32, so dy (and W')
-                # are zero-padded when Cout is not a multiple
-                gd = g if g.shape[-1] % 32 == 0 else torch.nn.functional.pad(g, (0, 32 - g.shape[-1] % 32))
-                dx = _conv(gd, _adjoint_pack(ctx.adjoint, w, ctx.kernel))
-            else:
-                dx = _dgrad_strided(g, x, w, ctx.kernel, ctx.stride, ctx.adjoint)
-        if ctx.needs_input_grad[1]:
-            dw = weight_grad(x, g, ctx.kernel, ctx.stride)
-        return dx, dw, None
+        return *_conv_grads(ctx, x, w, g.contiguous().float()), None
 
 
 class ConvAffineAct(torch.autograd.Function):
@@ -369,12 +349,10 @@ class ConvAffineAct(torch.autograd.Function):
     def forward(ctx, x, weight, scale, shift, residual, relu, stride):
         kernel = tuple(weight.shape[2:])
         w = weight.detach()
-        pk = _train_pack(w, kernel, False, int(stride), want_adjoint=ctx.needs_input_grad[0])
-        ctx.adjoint = pk.pop("_adjoint", None)
-        pk["scale"], pk["shift"] = scale, shift
+        pk, ctx.adjoint = _train_pack(w, kernel, False, int(stride), want_adjoint=ctx.needs_input_grad[0], scale=scale, shift=shift)
         res = None if residual is None else residual.detach().contiguous()
         xc = C.carry_amax(x, x.detach().contiguous())           # the backward kernels index it densely
-        y = (C.conv3d_ndhwc if pk["ndim"] == 3 else C.conv2d_nhwc)(xc, pk, residual=res, relu=1 if relu else 0)
+        y = _conv(xc, pk, residual=res, relu=1 if relu else 0)
         ctx.kernel, ctx.stride, ctx.relu, ctx.has_res = kernel, int(stride), bool(relu), residual is not None
         ctx.save_for_backward(xc, w, scale, y if relu else None)
         return y
@@ -384,30 +362,17 @@ class ConvAffineAct(torch.autograd.Function):
         x, w, scale, y = ctx.saved_tensors
         g = g.contiguous().float()
         want_res = ctx.has_res and ctx.needs_input_grad[4]
-        from ctypes import c_void_p
-        from . import _lib
         d_res = torch.empty_like(g) if want_res else None
         gs = torch.empty_like(g)
+        rows, st = g.numel() // g.shape[-1], _stream(g)
         if C.train_arithmetic() == "f16x2":      # the same pass leaves max |gs| for the fp16-pair data / weight gradients below
             slot = C.AMAX.take(g.device)
-            _lib.check(_lib.load().ndet_relu_affine_bwd_amax(c_void_p(g.data_ptr()), c_void_p(y.data_ptr() if ctx.relu else 0), c_void_p(scale.data_ptr()),
-                                                             g.numel() // g.shape[-1], g.shape[-1], int(ctx.relu), c_void_p(d_res.data_ptr() if want_res else 0),
-                                                             c_void_p(gs.data_ptr()), c_void_p(slot.data_ptr()),
-                                                             c_void_p(raw_stream(g.device))), "relu_affine_bwd_amax")
+            _lib.check(_lib.load().ndet_relu_affine_bwd_amax(_ptr(g), _ptr(y), _ptr(scale), rows, g.shape[-1], int(ctx.relu), _ptr(d_res), _ptr(gs), _ptr(slot), st),
+                       "relu_affine_bwd_amax")
             C._tag_amax(gs, slot)
         else:
-            _lib.check(_lib.load().ndet_relu_affine_bwd(c_void_p(g.data_ptr()), c_void_p(y.data_ptr() if ctx.relu else 0), c_void_p(scale.data_ptr()),
-                                                        g.numel() // g.shape[-1], g.shape[-1], int(ctx.relu), c_void_p(d_res.data_ptr() if want_res else 0),
-                                                        c_void_p(gs.data_ptr()), c_void_p(raw_stream(g.device))), "relu_affine_bwd")
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            if ctx.stride == 1:
-                gd = gs if gs.shape[-1] % 32 == 0 else torch.nn.functional.pad(gs, (0, 32 - gs.shape[-1] % 32))
-                dx = _conv(gd, _adjoint_pack(ctx.adjoint, w, ctx.kernel))
-            else:
-                dx = _dgrad_strided(gs, x, w, ctx.kernel, ctx.stride, ctx.adjoint)
-        if ctx.needs_input_grad[1]:
-            dw = weight_grad(x, gs, ctx.kernel, ctx.stride)
+            _lib.check(_lib.load().ndet_relu_affine_bwd(_ptr(g), _ptr(y), _ptr(scale), rows, g.shape[-1], int(ctx.relu), _ptr(d_res), _ptr(gs), st), "relu_affine_bwd")
+        dx, dw = _conv_grads(ctx, x, w, gs)
         return dx, dw, None, None, d_res, None, None
 
 
@@ -444,9 +409,7 @@ class ConvT2(torch.autograd.Function):
         w = weight.detach()
         xc = x.detach().contiguous()                            # the backward kernels index it densely
         ctx.save_for_backward(xc, w)
-        pk = dict(w=C.pack_weight(w, True), scale=None, shift=None, cout=int(w.shape[1]), cin=int(w.shape[0]), ksize=2, stride=2, transposed=True,
-                  kernel=(2, 2, 2), strides=(2, 2, 2), pads=(0, 0, 0), ndim=3, arith="bf16x3")
-        return C.conv3d_ndhwc(xc, pk)
+        return C.conv3d_ndhwc(xc, ConvPack(C.pack_weight(w, True), int(w.shape[1]), int(w.shape[0]), (2, 2, 2), (2, 2, 2), (0, 0, 0), True, arith="bf16x3"))
 
     @staticmethod
     def backward(ctx, g):
@@ -454,7 +417,7 @@ class ConvT2(torch.autograd.Function):
         g = g.contiguous().float()
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            dx = _conv(g, _train_pack(w, (2, 2, 2), False, 2, (0, 0, 0)))
+            dx = _conv(g, _train_pack(w, (2, 2, 2), False, 2, (0, 0, 0))[0])
         if ctx.needs_input_grad[1]:
             dw = weight_grad(g, x, (2, 2, 2), 2, (0, 0, 0))
         return dx, dw
@@ -472,26 +435,26 @@ def _scene(x: Tensor, b: int) -> Tensor:
     return x.squeeze(0) if x.shape[0] == 1 else x[b]
 
 
+def _per_scene(fn, x: Tensor, *args) -> Tensor:
+    """``fn(scene, *args)`` over the scenes of a logical (B,C,X,Y,Z) batch, each handed over channels-last (X,Y,Z,C) -- the kernel's depth axis is X --
+    and the results stacked back to (B,C',X',Y',Z')."""
+    outs = []
+    for b in range(x.shape[0]):
+        xb = C.carry_amax(x, _scene(x, b).permute(1, 2, 3, 0))      # (one scene of the batch: max |x[b]| <= max |x|, an upper bound is all the scale needs)
+        outs.append(fn(xb if xb.is_contiguous() else xb.contiguous(), *args).permute(3, 0, 1, 2))
+    return outs[0].unsqueeze(0) if len(outs) == 1 else torch.stack(outs)
+
+
 def conv_forward(conv: nn.Module, x: Tensor) -> Tensor:
     """``conv(x)`` for a logical (B,C,...) tensor: eligible layers run on the MFMA kernels under autograd (channels-last memory in,
     channels-last memory out, logical shape unchanged); everything else goes to the module itself."""
     if torch.is_grad_enabled() and eligible_transposed(conv, x):
-        outs = []
-        for b in range(x.shape[0]):
-            xb = C.carry_amax(x, _scene(x, b).permute(1, 2, 3, 0))      # (one scene of the batch: max |x[b]| <= max |x|, an upper bound is all the scale needs)
-            outs.append(ConvT2.apply(xb if xb.is_contiguous() else xb.contiguous(), conv.weight).permute(3, 0, 1, 2))
-        y = outs[0].unsqueeze(0) if len(outs) == 1 else torch.stack(outs)
+        y = _per_scene(ConvT2.apply, x, conv.weight)
         return y if conv.bias is None else y + conv.bias.view(1, -1, 1, 1, 1)
     if not (torch.is_grad_enabled() and eligible(conv, x)):
         return conv(x)
-    three_d = isinstance(conv, nn.Conv3d)
-    outs = []
-    if three_d:
-        for b in range(x.shape[0]):                                           # one scene at a time: the kernel's depth axis is X
-            xb = C.carry_amax(x, _scene(x, b).permute(1, 2, 3, 0))      # (one scene of the batch: max |x[b]| <= max |x|, an upper bound is all the scale needs)
-            y = ConvS1.apply(xb if xb.is_contiguous() else xb.contiguous(), conv.weight, conv.stride[0])
-            outs.append(y.permute(3, 0, 1, 2))
-        y = outs[0].unsqueeze(0) if len(outs) == 1 else torch.stack(outs)
+    if isinstance(conv, nn.Conv3d):
+        y = _per_scene(ConvS1.apply, x, conv.weight, conv.stride[0])
     else:
         xb = x.permute(0, 2, 3, 1)
         y = ConvS1.apply(xb if xb.is_contiguous() else xb.contiguous(), conv.weight, conv.stride[0]).permute(0, 3, 1, 2)
@@ -507,11 +470,7 @@ def conv_forward_shared(convs: Sequence[nn.Module], x: Tensor):
     if not (torch.is_grad_enabled() and all(eligible(c, x) and c.stride[0] == 1 for c in convs) and len({tuple(c.kernel_size) for c in convs}) == 1):
         return [c(x) for c in convs]
     w = torch.cat([c.weight for c in convs], dim=0)
-    outs = []
-    for b in range(x.shape[0]):
-        xb = C.carry_amax(x, _scene(x, b).permute(1, 2, 3, 0))      # (one scene of the batch: max |x[b]| <= max |x|, an upper bound is all the scale needs)
-        outs.append(ConvS1.apply(xb if xb.is_contiguous() else xb.contiguous(), w).permute(3, 0, 1, 2))
-    y = outs[0].unsqueeze(0) if len(outs) == 1 else torch.stack(outs)
+    y = _per_scene(ConvS1.apply, x, w)
     res, o = [], 0
     for c in convs:
         part = y[:, o:o + c.out_channels]
@@ -549,8 +508,6 @@ class BatchNormRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu, residual):
-        from ctypes import c_void_p
-        from . import _lib
         lib = _lib.load()
         xc = x.detach()
         n, c = xc.shape
@@ -559,9 +516,8 @@ class BatchNormRows(torch.autograd.Function):
         mean, invstd = torch.empty(c, dtype=torch.float32, device=x.device), torch.empty(c, dtype=torch.float32, device=x.device)
         ws = torch.empty(int(lib.ndet_bn_workspace_floats(n, c)), dtype=torch.float32, device=x.device)
         slot = C.AMAX.take(x.device) if C.train_arithmetic() == "f16x2" else None
-        p = lambda t: c_void_p(0 if t is None else t.data_ptr())
-        _lib.check(lib.ndet_bn_train_forward(p(xc), n, c, p(weight.detach()), p(bias.detach()), p(running_mean), p(running_var), float(momentum), float(eps), p(res),
-                                             int(bool(relu)), p(y), p(mean), p(invstd), p(slot), p(ws), c_void_p(raw_stream(x.device))),
+        _lib.check(lib.ndet_bn_train_forward(_ptr(xc), n, c, _ptr(weight.detach()), _ptr(bias.detach()), _ptr(running_mean), _ptr(running_var), float(momentum), float(eps), _ptr(res),
+                                             int(bool(relu)), _ptr(y), _ptr(mean), _ptr(invstd), _ptr(slot), _ptr(ws), _stream(x)),
                    "bn_train_forward")
         if slot is not None:
             C._tag_amax(y, slot)
@@ -573,8 +529,6 @@ class BatchNormRows(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from ctypes import c_void_p
-        from . import _lib
         lib = _lib.load()
         x, y, w, mean, invstd = ctx.saved_tensors
         g = g.contiguous()
@@ -584,9 +538,8 @@ class BatchNormRows(torch.autograd.Function):
         dgamma, dbeta = torch.empty(c, dtype=torch.float32, device=x.device), torch.empty(c, dtype=torch.float32, device=x.device)
         ws = torch.empty(int(lib.ndet_bn_workspace_floats(n, c)), dtype=torch.float32, device=x.device)
         slot = C.AMAX.take(x.device) if C.train_arithmetic() == "f16x2" else None
-        p = lambda t: c_void_p(0 if t is None else t.data_ptr())
-        _lib.check(lib.ndet_bn_train_backward(p(g), p(x), p(y), n, c, p(w), p(mean), p(invstd), int(ctx.relu), p(dx), p(dres), p(dgamma), p(dbeta), p(slot), p(ws),
-                                              c_void_p(raw_stream(x.device))), "bn_train_backward")
+        _lib.check(lib.ndet_bn_train_backward(_ptr(g), _ptr(x), _ptr(y), n, c, _ptr(w), _ptr(mean), _ptr(invstd), int(ctx.relu), _ptr(dx), _ptr(dres), _ptr(dgamma), _ptr(dbeta), _ptr(slot), _ptr(ws),
+                                              _stream(x)), "bn_train_backward")
         if slot is not None:
             C._tag_amax(dx, slot)
         return dx, dgamma, dbeta, None, None, None, None, None, dres

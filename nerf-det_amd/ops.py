@@ -11,7 +11,6 @@ from __future__ import annotations
 
 import ctypes
 import math
-from ctypes import c_void_p
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -19,18 +18,9 @@ import torch
 
 from . import _lib, trace
 from .hostmath import matmul_fma_chain
-from ._lib import NDET_LAYOUT_CN, NDET_LAYOUT_NC, NdetDepthGate, NdetSceneAccum, check, float3
-from ._lib import raw_stream
+from ._lib import NDET_LAYOUT_CN, NDET_LAYOUT_NC, NdetDepthGate, NdetSceneAccum, _ptr, _stream, check, float3
 
 Tensor = torch.Tensor
-
-
-def _ptr(t: Optional[Tensor]):
-    return c_void_p(0 if t is None else t.data_ptr())
-
-
-def _stream(t: Tensor):
-    return c_void_p(raw_stream(t.device))
 
 
 def _need_gpu(*ts: Tensor):

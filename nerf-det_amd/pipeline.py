@@ -17,14 +17,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import _ptr, check
 
 IMG_MEAN = (123.675, 116.28, 103.53)   # configs/nerfdet/*.py img_norm_cfg (RGB)
 IMG_STD = (58.395, 57.12, 57.375)
-
-
-def _ptr(t):
-    return c_void_p(t.data_ptr())
 
 
 def get_dtu_raydir(pixelcoords, intrinsic, rot, dir_norm=None):

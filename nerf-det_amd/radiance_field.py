@@ -163,7 +163,7 @@ class VanillaNeRFRadianceField(nn.Module):
         for i, lin in enumerate(self.mlp.base.hidden_layers):
             pk = packed_linear(lin, pad_in_to=width if i == 0 else 0)
             planes, winv = split_planes_f16(pk)
-            layers.append((planes, winv, pk["shift"]))
+            layers.append((planes, winv, pk.shift))
         return layers
 
     def forward_rows_hip(self, x, condition, features):

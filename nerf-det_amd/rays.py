@@ -12,15 +12,11 @@ import numpy as np
 import torch
 
 from . import _lib, ops, trace
-from ._lib import check
+from ._lib import _ptr, check
 from .hostmath import matmul_mul_add
 
 Tensor = torch.Tensor
 rng = np.random.RandomState(234)  # render_ray.py:20 -- module-global stream used for ray selection
-
-
-def _ptr(t):
-    return c_void_p(0 if t is None else t.data_ptr())
 
 
 def _stream(t):

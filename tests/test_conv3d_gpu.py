@@ -354,7 +354,7 @@ def test_split_planes_sum_exactly(device):
     from nerfdet_amd import conv3d
     torch.manual_seed(6)
     w = (torch.randn(3, 37, 64) * torch.logspace(-20, 20, 64)).to(device)
-    planes = conv3d.split_planes(dict(w=w)).view(torch.bfloat16).double()   # (taps, Cin/32, 3, Cout, 32)
+    planes = conv3d.split_planes(conv3d.ConvPack(w, 37, 64, (3, 1), (1, 1), (1, 0))).view(torch.bfloat16).double()   # (taps, Cin/32, 3, Cout, 32)
     back = planes.sum(2).permute(0, 2, 1, 3).reshape(3, 37, 64)
     assert torch.equal(back, w.double())
 

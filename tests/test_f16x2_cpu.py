@@ -53,7 +53,7 @@ def test_weight_scale_and_layer_rule():
     # the point MLPs are pinned (their inputs carry the reference's 1e9 rows, nerfdet.py:236-243)
     import torch
     pk = C.packed_linear(torch.nn.Linear(64, 32))
-    assert pk["arith"] == "bf16x3"
+    assert pk.arith == "bf16x3"
 
 
 def _split_f16(x, scale):

@@ -307,7 +307,7 @@ def test_range_guard_trips_exactly_when_the_floor_exceeds_the_tolerance(device):
     with torch.no_grad():
         pk = C.packed([conv.to(device)], bn.to(device))
         l1 = C.guard_l1(pk)
-        w = pk["w"].abs().cpu() * pk["scale"].abs().cpu()[None, :, None]
+        w = pk.w.abs().cpu() * pk.scale.abs().cpu()[None, :, None]
         assert abs(l1 - float(w.sum(dim=(0, 2)).max())) <= 1e-4 * l1          # no weight of this layer lies 2^-16 below the weight maximum
         C.guard_begin(device)
         y = _run(C, "f16x2", x, pk, None, 1, device)

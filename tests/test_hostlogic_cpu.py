@@ -137,7 +137,7 @@ def test_training_and_fusion_eligibility_rules():
     assert not conv_train.frozen_eval_bn(bn)                                       # training mode, trainable affine
     bn.eval(); bn.weight.requires_grad_(False); bn.bias.requires_grad_(False)
     assert conv_train.frozen_eval_bn(bn)
-    pk = lambda cin, cout, k, s: dict(ndim=2, cin=cin, cout=cout, kernel=(k, k), strides=(s, s), pads=(k // 2, k // 2), transposed=False, scale=1, shift=1)
+    pk = lambda cin, cout, k, s: conv3d.ConvPack(None, cout, cin, (k, k), (s, s), (k // 2, k // 2), scale=1, shift=1)
     assert conv3d.chain_ok(pk(64, 64, 3, 1), pk(64, 256, 1, 1)) and conv3d.chain_ok(pk(128, 128, 3, 2), pk(128, 512, 1, 1))
     assert not conv3d.chain_ok(pk(256, 256, 3, 1), pk(256, 1024, 1, 1))           # the 256-channel intermediate does not fit the tile
     assert not conv3d.chain_ok(pk(64, 64, 3, 1), pk(64, 256, 1, 2)) and not conv3d.chain_ok(pk(64, 64, 3, 1), pk(64, 100, 1, 1))
@@ -148,6 +148,52 @@ def test_training_and_fusion_eligibility_rules():
         conv3d.set_arithmetic(prev)
     assert conv3d.choose_tiling_split(240000, 256, 2, 100064, 0) == (100064, 1)   # direct-epilogue tiles never split K
     assert conv3d.choose_tiling_split(2304, 256, 375)[1] > 4 and conv3d.choose_tiling_split(2304, 256, 375)[0] in (128256, 129256)   # ... the 128 x 256 tile (code 128256, or its persistent form since the training sweep) does
+
+
+def test_conv_packs_are_typed_and_cached():
+    """conv3d.packed / packed_linear / ConvPack.gemm: what each constructor declares about its layer, and the per-module cache (the same
+    object until a parameter is written in place).  Packing is plain torch: CPU modules do."""
+    import torch
+    from torch import nn
+    from nerfdet_amd.conv3d import ConvPack, packed, packed_linear
+
+    def geometry(pk):
+        return (pk.cout, pk.cin, pk.kernel, pk.strides, pk.pads, pk.transposed, pk.ndim, pk.taps)
+    conv, bn = nn.Conv2d(64, 96, (3, 5), (2, 1), (1, 2), bias=False), nn.BatchNorm2d(96).eval()
+    pk = packed([conv], bn)
+    assert isinstance(pk, ConvPack) and geometry(pk) == (96, 64, (3, 5), (2, 1), (1, 2), False, 2, 15)
+    assert tuple(pk.w.shape) == (15, 96, 64) and tuple(pk.scale.shape) == tuple(pk.shift.shape) == (96,)
+    assert pk.arith is None and not pk.keep_amax and pk.guard and pk.w_amax is None
+    assert pk.planes_bf16 is None and pk.planes_f16 is None and pk.guard_l1 is None          # the lazy fillers have not run
+    two = packed([nn.Conv2d(32, 8, 1), nn.Conv2d(32, 24, 1, bias=False)])                    # convs sharing an input: concatenated along Cout
+    assert geometry(two) == (32, 32, (1, 1), (1, 1), (0, 0), False, 2, 1) and tuple(two.shift.shape) == (32,)
+    up = packed([nn.ConvTranspose3d(64, 32, 2, 2, bias=False)])
+    assert isinstance(up, ConvPack) and geometry(up) == (32, 64, (2, 2, 2), (2, 2, 2), (0, 0, 0), True, 3, 8)
+    assert tuple(up.w.shape) == (8, 32, 64) and up.scale is None and up.shift is None
+    lin = packed_linear(nn.Linear(64, 32))
+    assert isinstance(lin, ConvPack) and geometry(lin) == (32, 64, (1, 1), (1, 1), (0, 0), False, 2, 1)
+    assert lin.arith == "bf16x3" and tuple(lin.w.shape) == (1, 32, 64) and tuple(lin.shift.shape) == (32,)
+    assert packed_linear(nn.Linear(40, 32), pad_in_to=64).cin == 64
+    w = torch.zeros(1, 48, 96)
+    gemm = ConvPack.gemm(w, 48, 96, arith="f16x2", guard=False)
+    assert isinstance(gemm, ConvPack) and geometry(gemm) == (48, 96, (1, 1), (1, 1), (0, 0), False, 2, 1)
+    assert gemm.w is w and gemm.arith == "f16x2" and not gemm.guard and gemm.scale is None and gemm.shift is None
+    assert not hasattr(pk, "__dict__") and not hasattr(pk, "__getitem__")                    # slotted, and no dict protocol
+    # the cache: unchanged modules -> the same object; an in-place update of any parameter -> a new one
+    assert packed([conv], bn) is pk
+    with torch.no_grad():
+        conv.weight.mul_(2.0)
+    pk2 = packed([conv], bn)
+    assert pk2 is not pk and torch.equal(pk2.w, 2.0 * pk.w) and packed([conv], bn) is pk2
+    with torch.no_grad():
+        bn.running_var.add_(1.0)
+    assert packed([conv], bn) is not pk2
+    mlp = nn.Linear(64, 32)
+    first = packed_linear(mlp)
+    assert packed_linear(mlp) is first
+    with torch.no_grad():
+        mlp.bias.add_(1.0)
+    assert packed_linear(mlp) is not first
 
 
 def test_ssim_closed_form_cases():

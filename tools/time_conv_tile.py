@@ -18,7 +18,7 @@ st = c_void_p(torch.cuda.current_stream().cuda_stream)
 TILE = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 assert TILE in conv_tiles.TILES, f"tile: one of {conv_tiles.SPLIT_IDS}"
 args = _lib.NdetConvArgs(size=ctypes.sizeof(_lib.NdetConvArgs), in_=x.data_ptr(), w_planes=planes.data_ptr(), out=out.data_ptr(), D=60, H=80, W=50,
-                         Cin=256, Cout=256, kernel=(3, 3, 3), stride=(1, 1, 1), pad=(1, 1, 1), scale=pk["scale"].data_ptr(), shift=pk["shift"].data_ptr(),
+                         Cin=256, Cout=256, kernel=(3, 3, 3), stride=(1, 1, 1), pad=(1, 1, 1), scale=pk.scale.data_ptr(), shift=pk.shift.data_ptr(),
                          relu=1, splits=1, tile=TILE, arith=0, workspace=ws.data_ptr())
 ts = []
 for i in range(6):

@@ -23,7 +23,7 @@ def main():
     for m, cout, ksteps in shapes:
         cin = 32 * ksteps
         w = torch.randn(1, cout, cin, device=dev) / cin ** 0.5
-        pk = dict(w=w, scale=None, shift=None, cout=cout, cin=cin, ksize=1, stride=1, transposed=False, kernel=(1, 1), strides=(1, 1), pads=(0, 0), ndim=2)
+        pk = C3.ConvPack.gemm(w, cout, cin)
         x = torch.randn(1, 1, m, cin, device=dev)
 
         def run(**kw):
