@@ -214,6 +214,20 @@ int ndet_scene_density_finish(const NdetSceneAccum* s, const float* bias, float*
  * is 0 (alpha NULL: no gating), count (N) int64.  Equals ndet_backproject_aggregate over all the state's views bit for bit. */
 int ndet_scene_volume_finish(const NdetSceneAccum* s, const float* alpha, float* out, int64_t* count, void* stream);
 
+/* Sliding windows: one state per chunk, finished over several states at once, so that a chunk is forgotten by leaving its state out.
+ * segs: HOST array of n_segs blocks, oldest first, 1 <= n_segs <= NDET_RING_MAX; every block valid as above, all with the same N, C
+ * and cm; the blocks' n_views must add up to an int32.  Per voxel the segments' sums (fp32) and counts (int32) are added in array order,
+ * starting from the oldest segment's values (not from zero), and the total is finished with the single-state expressions: n_segs == 1
+ * gives the single-state function's output bit for bit.  A segment's row is not read where its own count for the voxel is 0 (a state
+ * filled by ndet_scene_accumulate holds an all-zero row there); the states are only read. */
+#define NDET_RING_MAX 64
+
+/* ndet_scene_density_finish over a ring of states (nerfdet.py:234-253): global_feat (N, 2 (3 + cm)), n_views the segments' total. */
+int ndet_scene_density_finish_ring(const NdetSceneAccum* segs, int n_segs, const float* bias, float* global_feat, void* stream);
+
+/* ndet_scene_volume_finish over a ring of states (nerfdet.py:175-176, 259-261): out (N, C) channels-last, count (N) int64. */
+int ndet_scene_volume_finish_ring(const NdetSceneAccum* segs, int n_segs, const float* alpha, float* out, int64_t* count, void* stream);
+
 /* A6 (gating only, unfused form). volume = (1-exp(-density)) * mean, 0 where count==0; nerfdet.py:257-261.
  * mean/out in `layout` with C channels. */
 int ndet_alpha_gate(const float* mean, const float* density, const int64_t* count, float* out,

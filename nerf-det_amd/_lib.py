@@ -67,6 +67,8 @@ SIGNATURES = {
                                _P, _P, _P, _G, _P], c_int),
     "ndet_scene_density_finish": ([_S, _P, _P, _P], c_int),
     "ndet_scene_volume_finish": ([_S, _P, _P, _P, _P], c_int),
+    "ndet_scene_density_finish_ring": ([_S, c_int, _P, _P, _P], c_int),
+    "ndet_scene_volume_finish_ring": ([_S, c_int, _P, _P, _P, _P], c_int),
     "ndet_alpha_gate": ([_P, _P, _P, _P, c_int, c_int, c_int, _P], c_int),
     "ndet_sigma_to_alpha": ([_P, _P, c_int, _P], c_int),
     "ndet_posenc_concat": ([_P, _P, c_int, c_int, c_int, _P, _P], c_int),

@@ -402,6 +402,90 @@ __global__ __launch_bounds__(256) void k_density_finish(const float* __restrict_
     *reinterpret_cast<float2*>(out + (int64_t)n * 2 * nc + 2 * c) = make_float2(mean, expf(-var));
 }
 
+// k_density_finish over a ring of states (include/nerfdet_hip.h, ndet_scene_density_finish_ring), its own copy of the finish: one thread
+// per (voxel, channel quad) -- quad 0 the colour lane [r g b 0], quads 1 .. cm / 4 the mapped channels -- with 16-byte loads of the three
+// sums.  The sums and counts start from the oldest segment's values and take the others in array order, NDET_RING_BATCH segments at a
+// time: counts first, then the rows of the segments that see the voxel in the quad's own map (the others hold zeros there), then the adds.
+// Every component then goes through k_density_finish's expressions, so one segment gives its rows bit for bit.
+__global__ __launch_bounds__(256) void k_density_finish_ring(NdetRingArgs r, int n_segs, const float* __restrict__ bias, int cm, int N,
+                                                             int n_views, float* __restrict__ out) {
+    constexpr int U = NDET_RING_BATCH;
+    const int nq = (cm >> 2) + 1;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)N * nq) return;
+    const int n = (int)(i / nq), qd = (int)(i % nq);
+    const bool is_rgb = qd == 0;
+    const int seg = cm + 4;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto counts = [&](int sj, int& c_f, int& c_mine) {
+        const int2 c = *reinterpret_cast<const int2*>(r.count[sj] + 2 * n);
+        c_f = c.x;
+        c_mine = is_rgb ? c.y : c.x;
+    };
+    int cnt, n_mine;
+    counts(0, cnt, n_mine);
+    float4 a = zero, qq = zero, ss = zero;
+    if (n_mine != 0) {
+        const float* row = r.sum[0] + (int64_t)n * r.pitch[0] + 4 * qd;
+        a = *reinterpret_cast<const float4*>(row);
+        qq = *reinterpret_cast<const float4*>(row + seg);
+        ss = *reinterpret_cast<const float4*>(row + 2 * seg);
+    }
+    for (int s0 = 1; s0 < n_segs; s0 += U) {
+        int cc[U], mm[U];
+        float4 va[U], vq[U], vs[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {      // unconditional loads (past the end: the last segment's counts again, dropped), so all U are in flight
+            const bool in = s0 + j < n_segs;
+            counts(min(s0 + j, n_segs - 1), cc[j], mm[j]);
+            cc[j] = in ? cc[j] : 0;
+            mm[j] = in ? mm[j] : 0;
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            va[j] = zero; vq[j] = zero; vs[j] = zero;
+            if (mm[j] != 0) {      // implies s0 + j < n_segs
+                const float* row = r.sum[s0 + j] + (int64_t)n * r.pitch[s0 + j] + 4 * qd;
+                va[j] = *reinterpret_cast<const float4*>(row);
+                vq[j] = *reinterpret_cast<const float4*>(row + seg);
+                vs[j] = *reinterpret_cast<const float4*>(row + 2 * seg);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            a = ndet_add4(a, va[j]);
+            qq = ndet_add4(qq, vq[j]);
+            ss = ndet_add4(ss, vs[j]);
+            cnt += cc[j];
+            n_mine += mm[j];
+        }
+    }
+    const float denom = (float)cnt + 1e-8f;
+    const float nu = (float)(n_views - n_mine), nv = (float)n_views;
+    auto finish = [&](float a1, float q1, float s1, float fl) -> float2 {
+        const float sm = a1 + nu * fl;
+        const float mean = sm / denom;                        // NOT zeroed at cnt == 0 (nerfdet.py:241)
+        const float dm = mean - fl;
+        float s = q1 - 2.0f * dm * s1 + nv * (dm * dm);
+        s = fmaxf(s, 0.0f);                                   // a sum of squares: rounding may leave -1 ulp
+        float var = s / denom;
+        if (cnt == 0) var = 1e6f;                             // nerfdet.py:249
+        return make_float2(mean, expf(-var));
+    };
+    float2* o = reinterpret_cast<float2*>(out + (int64_t)n * 2 * (3 + cm));
+    if (is_rgb) {
+        o[0] = finish(a.x, qq.x, ss.x, 0.0f);
+        o[1] = finish(a.y, qq.y, ss.y, 0.0f);
+        o[2] = finish(a.z, qq.z, ss.z, 0.0f);
+    } else {
+        const int c = 4 * (qd - 1);                           // first mapped channel of the quad
+        o[3 + c] = finish(a.x, qq.x, ss.x, bias[c]);
+        o[4 + c] = finish(a.y, qq.y, ss.y, bias[c + 1]);
+        o[5 + c] = finish(a.z, qq.z, ss.z, bias[c + 2]);
+        o[6 + c] = finish(a.w, qq.w, ss.w, bias[c + 3]);
+    }
+}
+
 void ndet_scene_k2_accumulate_launch(const NdetSceneAccum* s, const float* mapped, int n_views, int h, int w, int mview_pitch, int mrow_pitch,
                                      const float* bias, const float* rgb, int H, int W, int rsv, int rsc, int rsy, const float* points,
                                      const float* proj, const float* rgb_proj, bool gated, const NdetGateMap& gf, const NdetGateMap& gr,
@@ -422,4 +506,17 @@ void ndet_scene_k2_finish_launch(const NdetSceneAccum* s, const float* bias, flo
     const int64_t total = (int64_t)s->N * (3 + s->cm);
     hipLaunchKernelGGL(k_density_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, s->k2_sum, (int)s->k2_pitch, s->k2_count,
                        bias, s->cm, s->N, s->n_views, global_feat);
+}
+
+void ndet_scene_k2_finish_ring_launch(const NdetSceneAccum* segs, int n_segs, int n_views, const float* bias, float* global_feat,
+                                      hipStream_t stream) {
+    NdetRingArgs r = {};
+    for (int i = 0; i < n_segs; ++i) {
+        r.sum[i] = segs[i].k2_sum;
+        r.count[i] = segs[i].k2_count;
+        r.pitch[i] = (int)segs[i].k2_pitch;
+    }
+    const int64_t total = (int64_t)segs[0].N * (segs[0].cm / 4 + 1);
+    hipLaunchKernelGGL(k_density_finish_ring, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, r, n_segs, bias, segs[0].cm,
+                       segs[0].N, n_views, global_feat);
 }

@@ -128,6 +128,17 @@ void ndet_scene_k2_accumulate_launch(const NdetSceneAccum* s, const float* mappe
                                      hipStream_t stream);
 void ndet_scene_k2_finish_launch(const NdetSceneAccum* s, const float* bias, float* global_feat, hipStream_t stream);
 
+// Ring finishes (include/nerfdet_hip.h, ndet_scene_*_finish_ring): the segments' sum and count tensors of one kernel (K1's or K2's), oldest
+// first, riding in the kernel-argument block (1.25 KiB); entries beyond n_segs are null and never read.
+struct NdetRingArgs {
+    const float* sum[NDET_RING_MAX];
+    const int* count[NDET_RING_MAX];
+    int pitch[NDET_RING_MAX];
+};
+#define NDET_RING_BATCH 4   // segments whose loads a thread issues before it adds them (in array order)
+void ndet_scene_k2_finish_ring_launch(const NdetSceneAccum* segs, int n_segs, int n_views, const float* bias, float* global_feat,
+                                      hipStream_t stream);
+
 // Gradient scatter of the backward kernels.  Default: float atomics (global_atomic_add_f32) -- fast, but the ORDER of the adds, and with it the last
 // bits of every sum, changes from run to run.  Deterministic mode (tests: ndet_measurement_knob("deterministic_scatter", 1); the caller then hands
 // a zeroed buffer of int64 in place of the float buffer): every contribution is rounded to a multiple of 2^-40 and added as a 64-bit INTEGER --

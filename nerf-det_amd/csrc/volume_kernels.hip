@@ -799,6 +799,127 @@ extern "C" int ndet_scene_volume_finish(const NdetSceneAccum* s, const float* al
 }
 
 // ------------------------------------------------------------------------------------------
+// Sliding windows (include/nerfdet_hip.h, ndet_scene_*_finish_ring): one state per chunk, finished over a list of states.
+//
+// k_volume_finish_ring is k_volume_finish (its own copy) with the row sum and count formed over the segments first: the accumulator starts
+// from the oldest segment's values, the others are added in array order, NDET_RING_BATCH segments at a time -- their counts are loaded
+// first, then the rows of those that see the voxel (a segment that does not holds an all-zero row: adding +0 instead changes at most the
+// sign of a zero), then the adds.  With one segment the loop does not run and the expressions are k_volume_finish's.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_volume_finish_ring(NdetRingArgs r, int n_segs, const float* __restrict__ alpha, int C, int N,
+                                                            float* __restrict__ out, int64_t* __restrict__ out_count) {
+    constexpr int U = NDET_RING_BATCH;
+    const int c4 = C >> 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)N * c4) return;
+    const int n = (int)(i / c4), q = (int)(i % c4);
+    int cnt = r.count[0][n];
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (cnt != 0) s = *reinterpret_cast<const float4*>(r.sum[0] + (int64_t)n * r.pitch[0] + q * 4);
+    for (int s0 = 1; s0 < n_segs; s0 += U) {
+        int cc[U];
+        float4 vv[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int sj = min(s0 + j, n_segs - 1);     // past the end: the last segment's slot, not read (cc = 0)
+            cc[j] = (s0 + j < n_segs) ? r.count[sj][n] : 0;
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int sj = min(s0 + j, n_segs - 1);
+            vv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (cc[j] != 0) vv[j] = *reinterpret_cast<const float4*>(r.sum[sj] + (int64_t)n * r.pitch[sj] + q * 4);
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            s.x = s.x + vv[j].x;
+            s.y = s.y + vv[j].y;
+            s.z = s.z + vv[j].z;
+            s.w = s.w + vv[j].w;
+            cnt += cc[j];
+        }
+    }
+    const float denom = (float)cnt + 1e-8f;
+    float4 mean;
+    mean.x = s.x / denom;
+    mean.y = s.y / denom;
+    mean.z = s.z / denom;
+    mean.w = s.w / denom;
+    if (alpha) {
+        const float a = alpha[n];
+        mean.x = a * mean.x;
+        mean.y = a * mean.y;
+        mean.z = a * mean.z;
+        mean.w = a * mean.w;
+    }
+    if (cnt == 0) mean = make_float4(0.f, 0.f, 0.f, 0.f);
+    *reinterpret_cast<float4*>(out + (int64_t)n * C + q * 4) = mean;
+    if (q == 0) out_count[n] = (int64_t)cnt;
+}
+
+// The segment list of a ring finish, checked before any launch: every block as scene_check checks it (the message names the segment),
+// equal N / C / cm, a view total within int32.
+static int ring_check(const NdetSceneAccum* segs, int n_segs, const char* fn, int* total_views) {
+    NDET_REQUIRE(segs, NDET_E_INVALID, "%s: null segs", fn);
+    NDET_REQUIRE(n_segs >= 1 && n_segs <= NDET_RING_MAX, NDET_E_INVALID, "%s: n_segs=%d must be 1 .. %d", fn, n_segs, NDET_RING_MAX);
+    int64_t total = 0;
+    for (int i = 0; i < n_segs; ++i) {
+        const int rc = scene_check(&segs[i], fn);
+        if (rc != NDET_OK) {
+            char msg[400];
+            snprintf(msg, sizeof(msg), "%s", g_err);
+            ndet_set_error("%s (segs[%d])", msg, i);
+            return rc;
+        }
+        NDET_REQUIRE(segs[i].N == segs[0].N, NDET_E_INVALID, "%s: segs[%d].N=%d differs from segs[0].N=%d", fn, i, segs[i].N, segs[0].N);
+        NDET_REQUIRE(segs[i].C == segs[0].C, NDET_E_INVALID, "%s: segs[%d].C=%d differs from segs[0].C=%d", fn, i, segs[i].C, segs[0].C);
+        NDET_REQUIRE(segs[i].cm == segs[0].cm, NDET_E_INVALID, "%s: segs[%d].cm=%d differs from segs[0].cm=%d", fn, i, segs[i].cm, segs[0].cm);
+        total += segs[i].n_views;
+        NDET_REQUIRE(total <= 0x7fffffff, NDET_E_UNSUPPORTED, "%s: n_views of segs[0..%d] add up to more than int32 holds", fn, i);
+    }
+    *total_views = (int)total;
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_density_finish_ring(const NdetSceneAccum* segs, int n_segs, const float* bias, float* global_feat, void* stream) {
+    const char* fn = "ndet_scene_density_finish_ring";
+    int n_views = 0;
+    const int rc = ring_check(segs, n_segs, fn, &n_views);
+    if (rc != NDET_OK) return rc;
+    NDET_REQUIRE(bias, NDET_E_INVALID, "%s: null bias", fn);
+    NDET_REQUIRE(global_feat, NDET_E_INVALID, "%s: null global_feat", fn);
+    NDET_REQUIRE(((uintptr_t)global_feat & 7) == 0, NDET_E_UNSUPPORTED, "%s: global_feat must be 8-byte aligned", fn);
+    NDET_REQUIRE(((int64_t)segs[0].N * (segs[0].cm / 4 + 1) + 255) / 256 < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
+    ndet_scene_k2_finish_ring_launch(segs, n_segs, n_views, bias, global_feat, (hipStream_t)stream);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_volume_finish_ring(const NdetSceneAccum* segs, int n_segs, const float* alpha, float* out, int64_t* count,
+                                             void* stream) {
+    const char* fn = "ndet_scene_volume_finish_ring";
+    int n_views = 0;
+    const int rc = ring_check(segs, n_segs, fn, &n_views);
+    if (rc != NDET_OK) return rc;
+    NDET_REQUIRE(out, NDET_E_INVALID, "%s: null out", fn);
+    NDET_REQUIRE(count, NDET_E_INVALID, "%s: null count", fn);
+    NDET_REQUIRE(((uintptr_t)out & 15) == 0, NDET_E_UNSUPPORTED, "%s: out must be 16-byte aligned", fn);
+    NDET_REQUIRE(((uintptr_t)count & 7) == 0, NDET_E_UNSUPPORTED, "%s: count must be 8-byte aligned", fn);
+    const int64_t blocks = ((int64_t)segs[0].N * (segs[0].C / 4) + 255) / 256;
+    NDET_REQUIRE(blocks < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
+    NdetRingArgs r = {};
+    for (int i = 0; i < n_segs; ++i) {
+        r.sum[i] = segs[i].k1_sum;
+        r.count[i] = segs[i].k1_count;
+        r.pitch[i] = (int)segs[i].k1_pitch;
+    }
+    hipLaunchKernelGGL(k_volume_finish_ring, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, r, n_segs, alpha, segs[0].C, segs[0].N,
+                       out, count);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // K2  density conditioning features   A5
 //
 // One wavefront per voxel, lanes over the 3 + cm channels (35 of 64 lanes at cm = 32): lanes 0-2

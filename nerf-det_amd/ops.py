@@ -422,6 +422,64 @@ def volume_finish(state: SceneState, alpha: Optional[Tensor] = None) -> Tuple[Te
     return buf.permute(3, 0, 1, 2), count
 
 
+RING_MAX = 64   # segments one ring finish reads (include/nerfdet_hip.h)
+
+
+def _ring_blocks(states: Sequence[SceneState]):
+    """The host array of NdetSceneAccum blocks the ring finishes take, oldest first."""
+    states = list(states)
+    assert 1 <= len(states) <= RING_MAX, f"a ring holds 1 to {RING_MAX} states, got {len(states)}"
+    s0 = states[0]
+    for s in states[1:]:
+        assert (s.grid, s.c, s.cm) == (s0.grid, s0.c, s0.cm), "the ring's states must share grid, C and cm"
+        assert s.k1_sum.device == s0.k1_sum.device
+    assert sum(s.n_views for s in states) > 0, "the scene has no views yet"
+    arr = (NdetSceneAccum * len(states))()
+    for i, s in enumerate(states):
+        arr[i] = s.block()
+    return states, arr
+
+
+def density_finish_ring(states: Sequence[SceneState], bias: Tensor) -> Tensor:
+    """:func:`density_finish` over several states at once (oldest first, at most 64): per voxel the states' K2 sums and counts are added in
+    that order, then finished over the states' total view count.  One state gives :func:`density_finish`'s rows bit for bit; no state is
+    changed.  The span's bytes count every state in full: an upper bound, the kernel skips a state's row where its count is 0 (knowing
+    how many would cost a device-to-host read per call; tools/time_streaming.py --window counts them)."""
+    _need_gpu(bias)
+    states, arr = _ring_blocks(states)
+    s0 = states[0]
+    bias = _f32c(bias)
+    assert bias.numel() == s0.cm
+    out = torch.empty((s0.n_voxels, 2 * (3 + s0.cm)), dtype=torch.float32, device=s0.k1_sum.device)
+    read = sum(s.k2_sum.numel() + s.k2_count.numel() for s in states)
+    trace.span("k_density_finish_ring", lambda: check(_lib.load().ndet_scene_density_finish_ring(arr, len(states), _ptr(bias), _ptr(out),
+                                                                                                _stream(out)), "scene_density_finish_ring"),
+               bytes=4 * (read + out.numel()), kind="hbm")
+    return out
+
+
+def volume_finish_ring(states: Sequence[SceneState], alpha: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """:func:`volume_finish` over several states at once (oldest first, at most 64): per voxel the states' K1 sums and counts are added in
+    that order, then divided and gated.  One state gives :func:`volume_finish`'s outputs bit for bit; no state is changed.  The span's bytes count every
+    state in full, an upper bound as in :func:`density_finish_ring`."""
+    _need_gpu(alpha)
+    states, arr = _ring_blocks(states)
+    s0 = states[0]
+    dev = s0.k1_sum.device
+    if alpha is not None:
+        alpha = _f32c(alpha).reshape(-1)
+        assert alpha.numel() == s0.n_voxels
+    gx, gy, gz = s0.grid
+    buf = torch.empty((gx, gy, gz, s0.c), dtype=torch.float32, device=dev)
+    count = torch.empty((1, gx, gy, gz), dtype=torch.int64, device=dev)
+    read = sum(s.k1_sum.numel() + s.k1_count.numel() for s in states)
+    trace.span("k_volume_finish_ring", lambda: check(_lib.load().ndet_scene_volume_finish_ring(arr, len(states), _ptr(alpha), _ptr(buf),
+                                                                                              _ptr(count), _stream(buf)),
+                                                    "scene_volume_finish_ring"),
+               bytes=4 * (read + buf.numel()) + (12 if alpha is not None else 8) * s0.n_voxels, kind="hbm")
+    return buf.permute(3, 0, 1, 2), count
+
+
 # --------------------------------------------------------------------------------------------
 # A6 pieces
 # --------------------------------------------------------------------------------------------

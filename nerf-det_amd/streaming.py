@@ -7,12 +7,19 @@ rows and gated volume (nerfdet.py:164-176, 234-261) and runs neck_3d and the hea
 runs once per view, when the view arrives, and memory is the state's (ops.SceneState), whatever the number of views.
 
 K1's sums and every count are the same bits whatever the chunking; K2's sums add per chunk, so its rows differ from the one-shot kernel's by
-rounding only.  A single chunk reproduces ``simple_test`` bit for bit.  Inference only: no training / autograd, no ray branch
-(render_testing needs every view's map), no hipGraph replay, one scene per stream, views cannot be removed.
+rounding only.  A single chunk reproduces ``simple_test`` bit for bit.
+
+``begin_scene(img_meta, window=S)`` keeps the last S chunks only: every ``add_views`` call fills a state of its own, the oldest state is
+dropped when an (S+1)-th chunk arrives (or by ``drop_oldest``), and ``detect`` finishes over the states held, oldest first
+(ops.density_finish_ring / volume_finish_ring).  Nothing is subtracted, so a dropped chunk leaves no trace: the window's answer is the
+bits a fresh windowed stream gives when fed the same chunks.
+
+Inference only: no training / autograd, no ray branch (render_testing needs every view's map), no hipGraph replay, one scene per stream;
+whole chunks are dropped, not single views out of one.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -26,9 +33,12 @@ Tensor = torch.Tensor
 class SceneStream:
     """One scene of a :class:`~nerfdet_amd.detector.nerfdet` detector, filled chunk by chunk (:meth:`add_views`) and detected at any time
     (:meth:`detect`).  ``img_meta`` fixes the scene: ``lidar2img.intrinsic``, ``lidar2img.origin``, ``img_shape`` and ``ori_shape``; its
-    extrinsics are not used (each chunk brings its own)."""
+    extrinsics are not used (each chunk brings its own).  ``window``: None, or the number of chunks kept (1 .. ops.RING_MAX): the
+    stream then holds one state per ``add_views`` call and forgets the oldest when a chunk arrives at a full window."""
 
-    def __init__(self, det, img_meta: dict):
+    def __init__(self, det, img_meta: dict, window: Optional[int] = None):
+        if window is not None and (isinstance(window, bool) or not isinstance(window, int) or not 1 <= window <= ops.RING_MAX):
+            raise ValueError(f"window must be None or an int in 1 .. {ops.RING_MAX}, got {window!r}")
         if det.training:
             raise RuntimeError("SceneStream is inference only: call det.eval() first")
         if det.render_testing:
@@ -38,16 +48,65 @@ class SceneStream:
         self.device = next(det.parameters()).device
         lin = det.mapping[0]
         self._lin = lin
-        self.state = ops.SceneState(det.n_voxels, lin.in_features, lin.out_features, self.device)
+        self.window = window
+        # unwindowed: one state for the scene.  Windowed: one state per chunk held, oldest first, allocated when first needed; a
+        # dropped state is zeroed and kept for a chunk to come, so a sliding window allocates nothing once it has slid once.
+        self.state = ops.SceneState(det.n_voxels, lin.in_features, lin.out_features, self.device) if window is None else None
+        self._segs: List[ops.SceneState] = []
+        self._spare: List[ops.SceneState] = []
         self.points = ops.get_points(det.n_voxels, det.voxel_size, img_meta["lidar2img"]["origin"], self.device)
 
     @property
+    def chunk_views(self) -> List[int]:
+        """View counts of the chunks held, oldest first (an unwindowed stream holds its views as one)."""
+        if self.window is None:
+            return [self.state.n_views] if self.state.n_views else []
+        return [st.n_views for st in self._segs]
+
+    @property
+    def n_chunks(self) -> int:
+        return len(self.chunk_views)
+
+    @property
     def n_views(self) -> int:
-        return self.state.n_views
+        return sum(self.chunk_views)
 
     def reset(self) -> None:
         """Forget every view: the scene starts empty again."""
-        self.state.reset()
+        if self.window is None:
+            self.state.reset()
+        else:
+            self.drop_oldest(len(self._segs))
+
+    def drop_oldest(self, k: int = 1) -> None:
+        """Forget the k oldest chunks of a windowed stream (their states are zeroed and kept for the chunks to come)."""
+        if self.window is None:
+            raise ValueError("drop_oldest needs a windowed stream: begin_scene(img_meta, window=S)")
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= len(self._segs):
+            raise ValueError(f"drop_oldest: k={k!r} for {len(self._segs)} chunks held")
+        for st in self._segs[:k]:
+            st.reset()
+            self._spare.append(st)
+        del self._segs[:k]
+
+    def _accumulate(self, *chunk, depth_gate=None) -> None:
+        """Fold a chunk into the scene's state, or in a window into an empty state that joins the window once it is filled; only then does
+        the oldest chunk leave a full window.  A chunk that fails leaves the window as it was (its state goes back, zeroed)."""
+        if self.window is None:
+            ops.scene_accumulate(self.state, *chunk, depth_gate=depth_gate)
+            return
+        lin = self._lin
+        # a sliding window therefore owns S + 1 states: the chunk that leaves hands its (zeroed) state to the chunk after the next
+        st = self._spare.pop() if self._spare else ops.SceneState(self.det.n_voxels, lin.in_features, lin.out_features, self.device)
+        try:
+            ops.scene_accumulate(st, *chunk, depth_gate=depth_gate)
+        except BaseException:
+            st.reset()
+            self._spare.append(st)
+            raise
+        if len(self._segs) == self.window:
+            self.drop_oldest(1)
+        self._segs.append(st)
 
     def _check_meta(self, img_meta: dict, k: int) -> None:
         a, b = self.meta, img_meta
@@ -110,21 +169,22 @@ class SceneStream:
                 gate = ops.depth_gate(depth[0].to(self.device, non_blocking=True), self.det.voxel_size, (h, w), (hh, ww))
             proj = ops.compute_projection(img_meta, stride, self.device)
             rgb_proj = ops.compute_projection(img_meta, 1, self.device)
-            ops.scene_accumulate(self.state, feat, mapped, lin.bias, rgb, self.points, proj, rgb_proj, depth_gate=gate)
+            self._accumulate(feat, mapped, lin.bias, rgb, self.points, proj, rgb_proj, depth_gate=gate)
 
     def volume(self):
         """``(volume (C,X,Y,Z), valid (1,X,Y,Z) int64)`` of the views so far: K2-finish -> sigma-MLP -> K1-finish, what ``extract_volume``
         returns for them (channels-last memory)."""
-        if self.state.n_views == 0:
+        if self.n_views == 0:
             raise RuntimeError("the scene has no views yet: call add_views first")
+        ring = self.window is not None
         with torch.no_grad():
-            glob = ops.density_finish(self.state, self._lin.bias)
+            glob = ops.density_finish_ring(self._segs, self._lin.bias) if ring else ops.density_finish(self.state, self._lin.bias)
             mlp = self.det.nerf_mlp
             if hasattr(mlp, "hip_trunk_ok") and mlp.hip_trunk_ok():
                 alpha = mlp.alpha_from_points(self.points, glob)
             else:
                 alpha = ops.sigma_to_alpha(mlp.raw_sigma_from_rows(ops.posenc_concat(self.points, glob)))
-            return ops.volume_finish(self.state, alpha)
+            return ops.volume_finish_ring(self._segs, alpha) if ring else ops.volume_finish(self.state, alpha)
 
     def detect(self, defer: bool = False):
         """Detections over the views so far: what ``simple_test`` returns, ``[dict(boxes_3d, scores_3d, labels_3d)]``; with ``defer`` a

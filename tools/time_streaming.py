@@ -4,6 +4,11 @@
 against one simple_test on the same views, with the peak of torch.cuda.max_memory_allocated for both.  Medians of --reps event-timed
 calls after --warmup, one line per figure, then one JSON line.
     python tools/time_streaming.py [--reps 20 --warmup 3]
+With --window 1,4,8 it times sliding windows instead: for every S a window of S full chunks of 5 views -- detect() and the two ring
+finishes (ops.density_finish_ring / volume_finish_ring, with their achieved bytes/s next to the live copy ceiling of bench.py) -- next to
+detect() of an unwindowed stream holding the same views, the calls alternating inside one loop; and the peak allocation of filling the
+window and detecting once.
+    python tools/time_streaming.py --window 1,4,8 [--reps 20 --warmup 3]
 """
 import argparse
 import importlib.util
@@ -32,6 +37,70 @@ def timed(fn, reps, warmup):
     return statistics.median(ts)
 
 
+def timed_alternating(fns, reps, warmup):
+    """Medians (and [min, max]) of ``reps`` event-timed calls of every function in ``fns``, the functions taking turns inside one loop."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ts[k].append(a.elapsed_time(b))
+    return {k: statistics.median(v) for k, v in ts.items()}, {k: [min(v), max(v)] for k, v in ts.items()}
+
+
+def window_mode(bench, det, img, dn, meta, sizes, reps, warmup, dev):
+    from nerfdet_amd import ops
+    res = {"hbm_copy_ceiling_gbs": bench.hbm_copy_ceiling(dev)["best"]}
+    chunk = 5
+    for S in sizes:
+        assert 1 <= S and S * chunk <= img.shape[1], f"--window {S}: the workload has {img.shape[1]} views, chunks are of {chunk}"
+
+        def fill(stream):
+            for v0 in range(0, S * chunk, chunk):
+                stream.add_views(img[:, v0:v0 + chunk], dn[:, v0:v0 + chunk], chunk_meta(meta, v0, v0 + chunk))
+            return stream
+
+        def windowed_once():
+            return fill(det.begin_scene(dict(meta), window=S)).detect()
+
+        windowed_once()     # the first chunk of a shape allocates the convolutions' cached workspaces: not the window's memory
+        res[f"window_S{S}_peak_mb"] = peak_mb(windowed_once)
+        win, flat = fill(det.begin_scene(dict(meta), window=S)), fill(det.begin_scene(dict(meta)))
+        assert win.n_chunks == S and win.n_views == flat.n_views == S * chunk
+        bias = win._lin.bias
+        alpha = torch.rand(win._segs[0].n_voxels, device=dev)
+        fns = {"detect_ms": win.detect, "unwindowed_detect_ms": flat.detect,
+               "density_finish_ring_ms": lambda: ops.density_finish_ring(win._segs, bias),
+               "volume_finish_ring_ms": lambda: ops.volume_finish_ring(win._segs, alpha)}
+        med, span = timed_alternating(fns, reps, warmup)
+        n, c, cm = win._segs[0].n_voxels, win._segs[0].c, win._segs[0].cm
+        # bytes the kernels move: every segment's counts, the rows of the voxels a segment sees (the others are skipped), the outputs;
+        # "_full" counts every row instead, what ops reports to the trace
+        seen1 = sum(int((st.k1_count != 0).sum()) for st in win._segs)
+        seen_f = sum(int((st.k2_count[:, 0] != 0).sum()) for st in win._segs)
+        seen_r = sum(int((st.k2_count[:, 1] != 0).sum()) for st in win._segs)
+        out_d, out_v = n * 2 * (3 + cm) * 4, n * c * 4 + n * 12
+        nbytes = {"density_finish_ring": S * n * 8 + seen_f * 3 * cm * 4 + seen_r * 3 * 16 + out_d,
+                  "volume_finish_ring": S * n * 4 + seen1 * c * 4 + out_v,
+                  "density_finish_ring_full": S * (win._segs[0].k2_sum.numel() + 2 * n) * 4 + out_d,
+                  "volume_finish_ring_full": S * (n * c + n) * 4 + out_v}
+        res[f"window_S{S}_rows_read_fraction"] = seen1 / (S * n)
+        for k in fns:
+            res[f"window_S{S}_{k}"] = med[k]
+            res[f"window_S{S}_{k}_min_max"] = span[k]
+        for k, b in nbytes.items():
+            res[f"window_S{S}_{k}_gbs"] = b / (med[k.replace("_full", "") + "_ms"] * 1e-3) / 1e9
+        res[f"window_S{S}_state_mb"] = S * sum(t.numel() * t.element_size() for t in (
+            win._segs[0].k1_sum, win._segs[0].k1_count, win._segs[0].k2_sum, win._segs[0].k2_count)) / 2 ** 20
+    return res
+
+
 def peak_mb(fn):
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
@@ -51,6 +120,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--window", type=str, default=None, help="comma-separated window sizes in chunks of 5 views, e.g. 1,4,8")
     args = ap.parse_args()
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
@@ -63,6 +133,13 @@ def main():
     rb = det._ray_batch({k: v for k, v in batch.items() if k not in ("img", "img_metas")})
     n_v = img.shape[1]
     res = {}
+    if args.window:
+        with torch.no_grad():
+            res = window_mode(bench, det, img, dn, meta, [int(v) for v in args.window.split(",")], args.reps, args.warmup, dev)
+        for k, v in res.items():
+            print(f"{k:>44}: " + (f"{v:.3f}" if isinstance(v, float) else str(v)))
+        print(json.dumps(res))
+        return
     with torch.no_grad():
         s = det.begin_scene(dict(meta))
         for k in (1, 5, 10, 50):
