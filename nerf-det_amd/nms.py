@@ -16,7 +16,10 @@ NMS_MAX = 4096   # candidates one launch of the kernels takes (one 64-bit word o
 def _nms_in_windows(boxes, scores, classes, thresh):
     """More candidates than one launch takes (the reference has no cap: ``nms_pre <= 0`` hands it every voxel): greedy NMS is
     sequential in score order, so it can be run window by window -- the boxes kept so far (all of higher score, mutually
-    non-suppressing, hence kept again) go back in together with the next-best candidates that fit."""
+    non-suppressing, hence kept again) go back in together with the next-best candidates that fit.
+
+    A window is handed over in REVERSE global order: the launch visits equal scores from the higher position down, so only then does it
+    visit the window's candidates in the global order -- a box kept earlier stays ahead of a newcomer of the same score."""
     n = boxes.shape[0]
     # descending by (score, index), the order of k_nms_sort: stable sort of the index-reversed array
     rev = torch.arange(n - 1, -1, -1, device=boxes.device)
@@ -27,7 +30,7 @@ def _nms_in_windows(boxes, scores, classes, thresh):
         room = NMS_MAX - kept.numel()
         if room <= 0:
             raise ValueError(f"aligned_3d_nms: more than {NMS_MAX} boxes survive; raise score_thr or lower nms_pre")
-        cand = torch.cat([kept, order[pos:pos + room]])
+        cand = torch.cat([kept, order[pos:pos + room]]).flip(0)
         pos += room
         kept = cand[aligned_3d_nms(boxes[cand], scores[cand], classes[cand], thresh)]
     return kept
