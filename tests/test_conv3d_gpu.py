@@ -330,6 +330,17 @@ HALO_CASES = [
 
 @pytest.mark.parametrize("cin,cout,grid,kern,relu,use_res,splits,tile", HALO_CASES)
 def test_split_conv_halo_tile(device, cin, cout, grid, kern, relu, use_res, splits, tile):
+    """Pinned to the fp16-pair arithmetic (the default this test ran in while it took whatever the default was); the launch must also leave the exact
+    max |out| slot.  The same rows on the six-product kernels: test_split_conv_halo_tile_bf16x3."""
+    _halo_case(device, "f16x2", cin, cout, grid, kern, relu, use_res, splits, tile)
+
+
+@pytest.mark.parametrize("cin,cout,grid,kern,relu,use_res,splits,tile", HALO_CASES)
+def test_split_conv_halo_tile_bf16x3(device, cin, cout, grid, kern, relu, use_res, splits, tile):
+    _halo_case(device, "bf16x3", cin, cout, grid, kern, relu, use_res, splits, tile)
+
+
+def _halo_case(device, mode, cin, cout, grid, kern, relu, use_res, splits, tile):
     from nerfdet_amd import conv3d
     torch.manual_seed(cin + cout + sum(kern))
     conv = nn.Conv3d(cin, cout, kern, 1, tuple(k // 2 for k in kern), bias=False)
@@ -343,11 +354,17 @@ def test_split_conv_halo_tile(device, cin, cout, grid, kern, relu, use_res, spli
         ref = _ref(x, conv, bn, res, relu)
         pk = conv3d.packed([conv.to(device)], bn.to(device))
         out = torch.empty(ref.shape, device=device)
-        got = conv3d._conv_split(x.to(device), pk, out, grid, kern, (1, 1, 1), tuple(k // 2 for k in kern), False,
-                                 None if res is None else res.to(device), False, relu, splits, tile, ref.shape[0] * ref.shape[1] * ref.shape[2],
-                                 kern[0] * kern[1] * kern[2] * (cin // 32), 0)
+        prev = conv3d.set_arithmetic(mode)
+        try:
+            got = conv3d._conv_split(x.to(device), pk, out, grid, kern, (1, 1, 1), tuple(k // 2 for k in kern), False,
+                                     None if res is None else res.to(device), False, relu, splits, tile, ref.shape[0] * ref.shape[1] * ref.shape[2],
+                                     kern[0] * kern[1] * kern[2] * (cin // 32), 0)
+        finally:
+            conv3d.set_arithmetic(prev)
     scale = max(1.0, float(ref.abs().max()))
     assert float((got.cpu() - ref).abs().max()) <= 2e-5 * scale
+    if mode == "f16x2":
+        assert conv3d.amax_value(got._ndet_amax) == float(got.abs().max()), "the epilogue's max |out| is not the tensor's"
 
 
 def test_split_planes_sum_exactly(device):

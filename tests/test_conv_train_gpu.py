@@ -27,6 +27,7 @@ def _rel(a, b):
                                                    ((9, 8, 6), 64, 128, 3, 2), ((8, 6, 4), 64, 96, 1, 2),            # the neck's stride-2 3x3x3 / 1x1x1 downsample layers
                                                    ((3, 11, 14), 64, 64, (3, 3), 2), ((2, 9, 12), 128, 256, (1, 1), 2)])
 def test_conv_s1_forward_dgrad_wgrad_vs_torch_cpu(device, dims, cin, cout, k, stride):
+    from nerfdet_amd import autograd as A
     from nerfdet_amd.conv_train import ConvS1
     torch.manual_seed(sum(dims) + cin)
     two_d = isinstance(k, tuple)
@@ -40,12 +41,23 @@ def test_conv_s1_forward_dgrad_wgrad_vs_torch_cpu(device, dims, cin, cout, k, st
         ref = F.conv3d(xr.permute(3, 0, 1, 2).unsqueeze(0), wr, stride=stride, padding=k // 2)[0].permute(1, 2, 3, 0)
     gy = torch.randn(*ref.shape)
     (ref * gy).sum().backward()
-    xg, wg = x.to(device).requires_grad_(True), w.to(device).requires_grad_(True)
-    out = ConvS1.apply(xg, wg, stride)
-    (out * gy.to(device)).sum().backward()
-    assert _rel(out.detach().cpu(), ref.detach()) <= 2e-5
-    assert _rel(xg.grad.cpu(), xr.grad) <= 2e-5
-    assert _rel(wg.grad.cpu(), wr.grad) <= 5e-5      # a sum over every voxel, in another order
+
+    def check():
+        xg, wg = x.to(device).requires_grad_(True), w.to(device).requires_grad_(True)
+        out = ConvS1.apply(xg, wg, stride)
+        (out * gy.to(device)).sum().backward()
+        assert _rel(out.detach().cpu(), ref.detach()) <= 2e-5
+        assert _rel(xg.grad.cpu(), xr.grad) <= 2e-5
+        assert _rel(wg.grad.cpu(), wr.grad) <= 5e-5      # a sum over every voxel, in another order
+    check()
+    if stride == 2:
+        # the deterministic mode's stride-2 data gradient (conv_train._dgrad_strided: dy zero-upsampled to the input's extent, Cout padded to 32, then the
+        # stride-1 adjoint convolution on the MFMA kernels instead of the vendor library): the same bars
+        prev = A.set_deterministic(True)
+        try:
+            check()
+        finally:
+            A.set_deterministic(prev)
 
 
 def test_neck_training_step_matches_library_path(device):
@@ -233,7 +245,7 @@ def test_both_weight_packs_in_one_launch(device, train_arith, cout, cin, kernel)
 
 @pytest.mark.parametrize("n,c,relu,with_res", [(25600, 256, True, False), (3200, 512, True, True), (400, 1024, False, False), (777, 128, True, True), (50, 64, False, True),
                                                (100000, 32, True, False)])
-def test_batch_norm_rows_forward_backward_vs_fp64(device, n, c, relu, with_res):
+def test_batch_norm_rows_forward_backward_vs_fp64(device, train_arith, n, c, relu, with_res):
     """csrc/bn_kernels.hip (BatchNorm on batch statistics + ReLU + residual over channels-last rows, mmdet3d/models/necks/imvoxelnet.py:22-67,233-260)
     against an fp64 evaluation of relu(F.batch_norm(x) + residual): output, input / residual / affine gradients, running statistics; and not
     further from it than the library's fp32 path on the same tensors."""
@@ -265,6 +277,59 @@ def test_batch_norm_rows_forward_backward_vs_fp64(device, n, c, relu, with_res):
     for name, e, l, o in zip(names, exact, lib, ours):
         err_o, err_l = _rel(o, e), _rel(l, e)
         assert err_o <= max(3e-6, 2.0 * err_l), (name, err_o, err_l)
+    if train_arith != "f16x2":
+        return
+    # fp16-pair mode: the apply passes leave max |y| / max |dx| behind for the convolutions that read them (k_bn_apply, k_bn_backward).  A slot that is
+    # too small overflows fp16 silently in the next layer: both must be the tensors' exact maxima.  The library called as BatchNormRows calls it.
+    from nerfdet_amd import _lib, conv3d as C
+    lib, P = _lib.load(), _lib._ptr
+    xd, wd, bd, gd = (t.to(device) for t in (x, w, b, gy))
+    rd = None if res is None else res.to(device)
+    rm, rv = torch.zeros(c, device=device), torch.ones(c, device=device)
+    y, mean, invstd = torch.empty_like(xd), torch.empty(c, device=device), torch.empty(c, device=device)
+    ws = torch.empty(int(lib.ndet_bn_workspace_floats(n, c)), dtype=torch.float32, device=device)
+    st = _lib._stream(xd)
+    y_slot = C.AMAX.take(device)
+    _lib.check(lib.ndet_bn_train_forward(P(xd), n, c, P(wd), P(bd), P(rm), P(rv), mom, eps, P(rd), int(relu), P(y), P(mean), P(invstd), P(y_slot), P(ws), st),
+               "bn_train_forward")
+    assert torch.equal(y.double().cpu(), ours[0])            # (fixed-order partial sums: the very tensor checked above)
+    assert C.amax_value(y_slot) == float(y.abs().max())
+    dx, dres = torch.empty_like(xd), (None if rd is None else torch.empty_like(xd))
+    dgamma, dbeta = torch.empty(c, device=device), torch.empty(c, device=device)
+    dx_slot = C.AMAX.take(device)
+    _lib.check(lib.ndet_bn_train_backward(P(gd), P(xd), P(y if relu else None), n, c, P(wd), P(mean), P(invstd), int(relu), P(dx), P(dres), P(dgamma), P(dbeta),
+                                          P(dx_slot), P(ws), st), "bn_train_backward")
+    assert torch.equal(dx.double().cpu(), ours[1])
+    assert C.amax_value(dx_slot) == float(dx.abs().max())
+
+
+@pytest.mark.parametrize("rows,c,relu,identity", [(777, 128, True, True), (50, 64, False, False)])
+def test_relu_affine_bwd_amax_is_the_plain_pass_plus_the_slot(device, rows, c, relu, identity):
+    """ndet_relu_affine_bwd_amax (ConvAffineAct.backward in the fp16-pair mode: g' = dy [y > 0] * scale, the identity's gradient dy [y > 0]) against
+    ndet_relu_affine_bwd -- the same outputs bit for bit -- and against the definition; its slot holds max |g'|, the scale of the data and weight
+    gradient launches that read g'."""
+    from nerfdet_amd import _lib, conv3d as C
+    torch.manual_seed(rows + c)
+    lib, P = _lib.load(), _lib._ptr
+    g = torch.randn(rows, c, device=device) * torch.exp(torch.randn(rows, 1, device=device))
+    y = torch.relu(torch.randn(rows, c, device=device)) if relu else None
+    scale = (torch.rand(c, device=device) + 0.5) * (1 - 2 * (torch.arange(c, device=device) % 3 == 0).float())     # both signs
+    st = _lib._stream(g)
+    out = {}
+    for name in ("plain", "amax"):
+        d_conv, d_id = torch.full_like(g, float("nan")), (torch.full_like(g, float("nan")) if identity else None)
+        if name == "plain":
+            _lib.check(lib.ndet_relu_affine_bwd(P(g), P(y), P(scale), rows, c, int(relu), P(d_id), P(d_conv), st), "relu_affine_bwd")
+        else:
+            slot = C.AMAX.take(device)
+            _lib.check(lib.ndet_relu_affine_bwd_amax(P(g), P(y), P(scale), rows, c, int(relu), P(d_id), P(d_conv), P(slot), st), "relu_affine_bwd_amax")
+        out[name] = (d_conv, d_id)
+    assert torch.equal(out["amax"][0], out["plain"][0])
+    masked = g * (y > 0) if relu else g
+    torch.testing.assert_close(out["amax"][0].double(), masked.double() * scale.double(), rtol=1e-6, atol=0)
+    if identity:
+        assert torch.equal(out["amax"][1], out["plain"][1]) and torch.equal(out["amax"][1], masked)
+    assert C.amax_value(slot) == float(out["amax"][0].abs().max())
 
 
 def test_prepare_step_hands_every_convolution_weight_its_maximum(device, train_arith):
