@@ -343,6 +343,26 @@ int ndet_ray_view_stats_packed(const float* pts, int n_points, const float* KE, 
                                int64_t fview_pitch, int64_t frow_pitch, float* global_feat, uint8_t* pixel_mask, int* view_count,
                                void* stream);
 
+/* A view bank: the source views of a streamed scene (nerf-det_amd/streaming.py), kept per chunk in separate allocations.  One
+ * NdetBankView per source view, oldest first, in DEVICE memory:
+ *   feat   (hf, wf, d) mapped map of the view, dense, 16-byte aligned.
+ *   rgb4   (H, W, 4) image of the view as ndet_pack_rgb_nhwc4 writes it, 16-byte aligned.
+ *   ke     rows 0..2 of K(4x4) @ E(4x4) of the view (render_ray.py:48-69 cameras).
+ * The map and image sizes are the call's, the same for every view. */
+typedef struct NdetBankView {
+    const float* feat;
+    const float* rgb4;
+    float ke[12];
+} NdetBankView;
+
+/* A7+A8 fused over a view bank: the outputs of ndet_ray_view_stats_packed -- Projector.compute() (model_utils/projection.py:91-151) +
+ * compute_mask_points() (render_ray.py:71-93) + the concat / pixel mask of render_ray.py:299-303 -- for any number of views, each behind
+ * its own pointers.  d % 4 == 0, d <= 128; views_dev 8-byte aligned.  The views are taken in rounds of 64 in ascending order with the
+ * statistics carried from round to round; with more than one round a first pass counts the views seeing each sample (the masked mean's
+ * weight needs the count over all views).  For at most 128 views the outputs equal ndet_ray_view_stats_packed's bit for bit. */
+int ndet_ray_view_stats_bank(const float* pts, int n_points, const NdetBankView* views_dev, int n_views, float img_h, float img_w, int H,
+                             int W, int d, int hf, int wf, float* global_feat, uint8_t* pixel_mask, int* view_count, void* stream);
+
 /* A7 exact API form. Replaces Projector.compute(), projection.py:91-151: rgb_feat (P, n_views, 3+d) and
  * mask (P, n_views) fp32 0/1, materialised like the reference. Same inputs as ndet_ray_view_stats. */
 int ndet_project_sample(const float* pts, int n_points, const float* KE, int n_views, float img_h, float img_w,

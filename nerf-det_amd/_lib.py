@@ -38,6 +38,10 @@ class NdetSceneAccum(ctypes.Structure):  # a streaming scene's state: include/ne
         ("k1_sum", _P), ("k1_pitch", c_int64), ("k1_count", _P), ("k2_sum", _P), ("k2_pitch", c_int64), ("k2_count", _P)]
 
 
+class NdetBankView(ctypes.Structure):    # one source view of a view bank (a DEVICE table of these): include/nerfdet_hip.h::NdetBankView, 64 bytes
+    _fields_ = [("feat", _P), ("rgb4", _P), ("ke", c_float * 12)]
+
+
 _G = ctypes.POINTER(NdetDepthGate)
 _S = ctypes.POINTER(NdetSceneAccum)
 
@@ -83,6 +87,7 @@ SIGNATURES = {
     "ndet_pack_rgb_nhwc4": ([_P, c_int, c_int, c_int, c_int64, c_int64, c_int64, _P, _P], c_int),
     "ndet_ray_view_stats_packed": ([_P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int64, c_int64,
                                     _P, _P, _P, _P], c_int),
+    "ndet_ray_view_stats_bank": ([_P, c_int, _P, c_int, c_float, c_float, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P], c_int),
     "ndet_ray_view_stats_packed_bwd": ([_P, _P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, c_int, c_int64, c_int64, _P, _P], c_int),
     "ndet_project_sample": ([_P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, c_int64, c_int64, c_int64,
                              _P, c_int, c_int, c_int, c_int64, c_int64, _P, _P, _P], c_int),

@@ -14,6 +14,7 @@
 //   * the variance is accumulated in the same walk with the first gathered value as pivot:
 //         sum_near (v - mean)^2 = sum (v - c)^2 - 2 (mean - c) sum (v - c) + n_near (mean - c)^2,   + n_far mean^2
 //     (shifted-data form: conditioned like the two-pass sum when the pivot lies inside the data, no second gather).
+// k_ray_stats_bank (below) runs the same expressions over a view bank: any number of views, each behind its own pointers.
 // Compiled with -ffp-contract=off.
 #include "ndet_common.hpp"
 
@@ -371,6 +372,171 @@ extern "C" int ndet_ray_view_stats_packed(const float* pts, int n_points, const 
     hipLaunchKernelGGL(k_ray_stats_packed<false>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pts, n_points, KE, n_views, img_h,
                        img_w, rgb_nhwc4, H, W, feat_nhwc, d, hf, wf, (int)fview_pitch, (int)frow_pitch, global_feat, pixel_mask, view_count,
                        (const float*)nullptr, (float*)nullptr, nvp, 0);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// view bank: the packed forward kernel's expressions over any number of views, each behind its own pointers (NdetBankView).
+// Views go in rounds of 64, ascending; a round projects its views into the LDS record area and walks its near bits exactly as
+// k_ray_stats_packed does, RsAcc stays in registers from round to round.  The masked mean's weight needs the valid count over ALL
+// views before the first rs_take: with more than one round a count pass projects every view first and keeps the counts only.
+// The round's base pointers sit in LDS beside the records (one ds_read per view in the walk, no dependent global load).
+// LDS: 4 waves x G samples x 64 records + 128 pointers; G is the host's (at most 64 / lanes per sample, fewer where 64 KB ask for it).
+// ------------------------------------------------------------------------------------------------
+#define RB_VIEWS 64  // views per round
+
+template <bool STORE>
+__device__ __forceinline__ void rb_project_round(const float* __restrict__ pts, int n_points, int p_base, int G, int g, int lane,
+                                                 const NdetBankView* __restrict__ views, int v, int n_views, float img_h, float img_w, int H, int W,
+                                                 int hf, int wf, float2* rec, unsigned long long& my_valid, unsigned long long& my_near) {
+    float cam[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) cam[k] = v < n_views ? views[v].ke[k] : 0.0f;
+    my_valid = 0ull;
+    my_near = 0ull;
+    for (int gg = 0; gg < G; ++gg) {
+        const int p = p_base + gg;
+        if (p >= n_points) break;   // wave-uniform
+        const float x = pts[(int64_t)p * 3 + 0], y = pts[(int64_t)p * 3 + 1], z = pts[(int64_t)p * 3 + 2];
+        bool m = false, nr = false;
+        if (v < n_views) {
+            const RsHit hit = rs_project(cam, x, y, z, img_h, img_w);
+            m = hit.mask;
+            nr = rs_near(hit.nx, hit.ny, hf, wf) || rs_near(hit.nx, hit.ny, H, W);
+            if (STORE) rec[gg * RB_VIEWS + lane] = make_float2(hit.nx, hit.ny);
+        }
+        const unsigned long long vb = __ballot(m), nb = __ballot(nr);
+        if (g == gg) { my_valid = vb; my_near = nb; }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ray_stats_bank(const float* __restrict__ pts, int n_points, const NdetBankView* __restrict__ views,
+                                                        int n_views, float img_h, float img_w, int H, int W, int d, int hf, int wf, int G,
+                                                        float* __restrict__ glob, uint8_t* __restrict__ pixel_mask, int* __restrict__ view_count) {
+    extern __shared__ float2 s_bank[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lps = (d >> 2) + 1;                      // lanes per sample: [image quad | d/4 feature quads]
+    const int g = lane / lps, sub = lane - g * lps;
+    const int p_base = (blockIdx.x * 4 + wave) * G;
+    float2* rec = s_bank + (size_t)wave * G * RB_VIEWS;
+    const float** s_ptr = reinterpret_cast<const float**>(s_bank + (size_t)4 * G * RB_VIEWS);   // [0,64) feature maps, [64,128) images
+    const int rounds = (n_views + RB_VIEWS - 1) / RB_VIEWS;
+
+    // ---- count pass (more than one round): valid and near views of every sample over all the views ----
+    int cnt = 0, n_near = 0;
+    unsigned long long my_valid = 0ull, my_near = 0ull;
+    if (rounds > 1) {
+        for (int r = 0; r < rounds; ++r) {
+            rb_project_round<false>(pts, n_points, p_base, G, g, lane, views, r * RB_VIEWS + lane, n_views, img_h, img_w, H, W, hf, wf, rec,
+                                    my_valid, my_near);
+            cnt += __popcll(my_valid);
+            n_near += __popcll(my_near);
+        }
+    }
+
+    const int my_p = p_base + g;
+    const bool on = g < G && my_p < n_points;
+    const bool is_rgb = sub == 0;
+    const int fq = sub - 1;                                   // feature quad of this lane
+    const int Hs = is_rgb ? H : hf, Ws = is_rgb ? W : wf;
+    const int rpitch = is_rgb ? W * 4 : wf * d, pix = is_rgb ? 4 : d;
+    const int poff = is_rgb ? 0 : 4 * fq;
+    const float** my_ptr = s_ptr + (is_rgb ? RB_VIEWS : 0);
+    const float2* myrec = rec + (on ? g : 0) * RB_VIEWS;
+    float denom = (float)cnt + 1e-8f;
+    float wgt = 1.0f / denom;                                 // mask / (sum(mask) + 1e-8), render_ray.py:83
+    RsAcc a;
+    a.acc = a.q = a.s1 = a.piv = make_float4(0.f, 0.f, 0.f, 0.f);
+    a.have = false;
+
+    // ---- walk pass: round by round, lanes over views, then lanes over (sample, channel quad) ----
+    for (int r = 0; r < rounds; ++r) {
+        if (r > 0) __syncthreads();                           // the round before has read its records and pointers
+        const int v = r * RB_VIEWS + lane;
+        rb_project_round<true>(pts, n_points, p_base, G, g, lane, views, v, n_views, img_h, img_w, H, W, hf, wf, rec, my_valid, my_near);
+        if (wave < 2) s_ptr[wave * RB_VIEWS + lane] = v < n_views ? (wave == 0 ? views[v].feat : views[v].rgb4) : nullptr;
+        if (rounds == 1) {                                    // a single round: its own ballots are the counts
+            cnt = __popcll(my_valid);
+            n_near = __popcll(my_near);
+            denom = (float)cnt + 1e-8f;
+            wgt = 1.0f / denom;
+        }
+        __syncthreads();
+        unsigned long long m = on ? my_near : 0ull;
+        const unsigned long long vm = my_valid;
+        while (__ballot(m != 0ull) != 0ull) {                 // until every sample of the wave has walked its near views
+            const bool h0 = m != 0ull;
+            const int b0 = h0 ? __builtin_ctzll(m) : 0;
+            m = h0 ? (m & (m - 1ull)) : 0ull;
+            const bool h1 = m != 0ull;
+            const int b1 = h1 ? __builtin_ctzll(m) : 0;
+            m = h1 ? (m & (m - 1ull)) : 0ull;
+            const float2 r0 = h0 ? myrec[b0] : make_float2(0.f, 0.f);
+            const float2 r1 = h1 ? myrec[b1] : make_float2(0.f, 0.f);
+            const float* v0 = h0 ? my_ptr[b0] + poff : nullptr;
+            const float* v1 = h1 ? my_ptr[b1] + poff : nullptr;
+            const RsTaps t0 = rs_taps(r0.x, r0.y, Hs, Ws, rpitch, pix), t1 = rs_taps(r1.x, r1.y, Hs, Ws, rpitch, pix);
+            float4 a00 = make_float4(0.f, 0.f, 0.f, 0.f), a01 = a00, a10 = a00, a11 = a00, c00 = a00, c01 = a00, c10 = a00, c11 = a00;
+            if (h0) {
+                a00 = *reinterpret_cast<const float4*>(v0 + t0.o00);
+                a01 = *reinterpret_cast<const float4*>(v0 + t0.o01);
+                a10 = *reinterpret_cast<const float4*>(v0 + t0.o10);
+                a11 = *reinterpret_cast<const float4*>(v0 + t0.o11);
+            }
+            if (h1) {
+                c00 = *reinterpret_cast<const float4*>(v1 + t1.o00);
+                c01 = *reinterpret_cast<const float4*>(v1 + t1.o01);
+                c10 = *reinterpret_cast<const float4*>(v1 + t1.o10);
+                c11 = *reinterpret_cast<const float4*>(v1 + t1.o11);
+            }
+            if (h0) rs_take(a, rs_blend(a00, a01, a10, a11, t0), (vm >> b0) & 1ull, wgt);
+            if (h1) rs_take(a, rs_blend(c00, c01, c10, c11, t1), (vm >> b1) & 1ull, wgt);
+        }
+    }
+    if (!on) return;
+    const float nn = (float)n_near, nf = (float)(n_views - n_near);
+    const float4 mean = a.acc;
+    float4 ev;
+    ev.x = expf(-(rs_var_sum(a.q.x, a.s1.x, a.piv.x, mean.x, nn, nf) / denom));
+    ev.y = expf(-(rs_var_sum(a.q.y, a.s1.y, a.piv.y, mean.y, nn, nf) / denom));
+    ev.z = expf(-(rs_var_sum(a.q.z, a.s1.z, a.piv.z, mean.z, nn, nf) / denom));
+    ev.w = expf(-(rs_var_sum(a.q.w, a.s1.w, a.piv.w, mean.w, nn, nf) / denom));
+    const int nch = 3 + d;
+    float* row = glob + (int64_t)my_p * 2 * nch;              // cat([mean, exp(-var)], dim=-1), render_ray.py:303
+    if (is_rgb) {
+        row[0] = mean.x; row[1] = mean.y; row[2] = mean.z;
+        row[nch + 0] = ev.x; row[nch + 1] = ev.y; row[nch + 2] = ev.z;
+        pixel_mask[my_p] = cnt > 1 ? 1 : 0;                   // render_ray.py:301
+        if (view_count) view_count[my_p] = cnt;
+    } else {
+        const int c = 3 + 4 * fq;
+        row[c + 0] = mean.x; row[c + 1] = mean.y; row[c + 2] = mean.z; row[c + 3] = mean.w;
+        row[nch + c + 0] = ev.x; row[nch + c + 1] = ev.y; row[nch + c + 2] = ev.z; row[nch + c + 3] = ev.w;
+    }
+}
+
+extern "C" int ndet_ray_view_stats_bank(const float* pts, int n_points, const NdetBankView* views_dev, int n_views, float img_h, float img_w,
+                                        int H, int W, int d, int hf, int wf, float* global_feat, uint8_t* pixel_mask, int* view_count,
+                                        void* stream) {
+    const char* fn = "ndet_ray_view_stats_bank";
+    static_assert(sizeof(NdetBankView) == 64, "NdetBankView is 64 bytes");
+    NDET_REQUIRE(pts && views_dev && global_feat && pixel_mask, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(n_points > 0 && n_views > 0 && H > 1 && W > 1 && hf > 1 && wf > 1 && d > 0, NDET_E_INVALID, "%s: bad sizes", fn);
+    NDET_REQUIRE(d % 4 == 0 && d <= 128, NDET_E_UNSUPPORTED, "%s: d=%d must be a multiple of 4, at most 128", fn, d);
+    NDET_REQUIRE(((uintptr_t)views_dev & 7) == 0, NDET_E_UNSUPPORTED, "%s: the view table must be 8-byte aligned", fn);
+    NDET_REQUIRE(((uintptr_t)global_feat & 3) == 0, NDET_E_UNSUPPORTED, "%s: global_feat must be 4-byte aligned", fn);
+    NDET_REQUIRE((int64_t)hf * wf * d < ((int64_t)1 << 31) && (int64_t)H * W * 4 < ((int64_t)1 << 31), NDET_E_UNSUPPORTED,
+                 "%s: a source view exceeds 2^31 floats", fn);
+    const int lps = d / 4 + 1;
+    int G = 64 / lps;
+    const int ptr_bytes = 2 * RB_VIEWS * (int)sizeof(const float*);
+    while (G > 1 && 4 * G * RB_VIEWS * (int)sizeof(float2) + ptr_bytes > 64 * 1024) --G;
+    const int lds = 4 * G * RB_VIEWS * (int)sizeof(float2) + ptr_bytes;
+    const int64_t blocks = ((int64_t)n_points + 4 * G - 1) / (4 * G);
+    NDET_REQUIRE(blocks * 4 * G < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many points", fn);
+    hipLaunchKernelGGL(k_ray_stats_bank, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pts, n_points, views_dev, n_views, img_h,
+                       img_w, H, W, d, hf, wf, G, global_feat, pixel_mask, view_count);
     NDET_CHECK_LAUNCH(fn);
     return NDET_OK;
 }

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 from collections import OrderedDict
 from ctypes import c_void_p
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -130,6 +130,140 @@ def ray_view_stats(xyz: Tensor, train_imgs: Tensor, train_cameras: Tensor, featm
                                         rgb.stride(2), _ptr(f), d, hf, wf, f.stride(0), f.stride(2), _ptr(glob), _ptr(pm), _ptr(vc),
                                         _stream(xyz)), "ray_view_stats"),
         bytes=nbytes, kind="hbm")
+    return glob.view(*shape, -1), pm.view(*shape), vc.view(*shape)
+
+
+class BankSegment:
+    """One chunk of a :class:`ViewBank`: ``feat`` (k,hf,wf,d) dense mapped maps, ``rgb4`` (k,H,W,4) packed images (device), ``ke`` (k,3,4)
+    rows 0..2 of K @ E (host), ``img_hw`` the cameras' image size (render_ray.py:48-69: cameras[:, :2])."""
+    __slots__ = ("feat", "rgb4", "ke", "img_hw")
+
+    def __init__(self, feat: Tensor, rgb4: Tensor, ke: Tensor, img_hw: Tuple[float, float]):
+        self.feat, self.rgb4, self.ke, self.img_hw = feat, rgb4, ke, img_hw
+
+    @property
+    def n_views(self) -> int:
+        return self.feat.shape[0]
+
+
+class ViewBank:
+    """What the ray branch needs of a streamed scene's source views, kept chunk by chunk: ``segments``, oldest first, each with its own
+    allocations (mapped map + packed image + 12 camera floats per view).  :func:`ray_view_stats_bank` samples all of them through a device
+    table of per-view pointers (``NdetBankView``), built when first needed, uploaded through the pinned staging ring and kept until the
+    segment list changes.  The bank owns every tensor the table points to.
+
+    Renders and evictions must be issued on ONE stream: a dropped segment's memory goes back to the caching allocator, whose stream
+    order then keeps a later allocation on that stream behind the renders already queued; a render queued on another stream would
+    have no such protection."""
+
+    def __init__(self):
+        self.segments: List[BankSegment] = []
+        self._table = None                                     # (device table, n_views) of the current segment list
+
+    @property
+    def n_views(self) -> int:
+        return sum(s.n_views for s in self.segments)
+
+    def nbytes(self) -> int:
+        """Device bytes held: maps, images and the 64-byte table rows."""
+        return sum(4 * (s.feat.numel() + s.rgb4.numel()) + 64 * s.n_views for s in self.segments)
+
+    def append(self, mapped: Tensor, images: Tensor, img_meta: dict) -> None:
+        """Bank a chunk (:meth:`make_segment`, then :meth:`push`)."""
+        self.push(self.make_segment(mapped, images, img_meta))
+
+    def push(self, seg: BankSegment) -> None:
+        """A segment made by :meth:`make_segment` for this bank becomes its newest."""
+        self.segments.append(seg)
+        self._table = None
+
+    def make_segment(self, mapped: Tensor, images: Tensor, img_meta: dict) -> BankSegment:
+        """A chunk's segment, checked against the bank, which is not changed: ``mapped`` logical (k,d,hf,wf) (any crop of a channels-last map), ``images`` (k,3,H,W) as the reference hands them
+        to Projector.compute (uncropped: grid_sample normalises by their size), ``img_meta`` with the chunk's k extrinsics."""
+        if not mapped.is_cuda:
+            raise RuntimeError("nerfdet_amd.rays: tensors must live on the GPU (no CPU fallback)")
+        k, d = mapped.shape[0], mapped.shape[1]
+        if images.dim() != 4 or images.shape[0] != k or images.shape[1] != 3:
+            raise ValueError(f"ViewBank.append: images {tuple(images.shape)} for {k} mapped maps")
+        if d % 4 or d > 128:
+            raise ValueError(f"ViewBank.append: d={d} must be a multiple of 4, at most 128")
+        ke, h, w = _camera_matrices(_compute_projection(img_meta).squeeze(0))
+        if ke.shape[0] != k:
+            raise ValueError(f"ViewBank.append: {ke.shape[0]} extrinsics for {k} views")
+        if self.segments:
+            s0 = self.segments[0]
+            if tuple(mapped.shape[1:]) != (s0.feat.shape[3], s0.feat.shape[1], s0.feat.shape[2]) or tuple(images.shape[2:]) != tuple(s0.rgb4.shape[1:3]) \
+                    or (h, w) != s0.img_hw or mapped.device != s0.feat.device:
+                raise ValueError("ViewBank.append: the chunk's map, image or camera size differs from the bank's")
+        feat = mapped.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
+        if feat.data_ptr() == mapped.data_ptr():
+            feat = feat.clone()                                # a copy of its own: the producer may reuse the chunk's map
+        rgb = images.detach()
+        if rgb.dtype != torch.float32:
+            rgb = rgb.float()
+        if rgb.stride(3) != 1:
+            rgb = rgb.contiguous()
+        rgb = rgb.to(feat.device)
+        rgb4 = torch.empty((k, rgb.shape[2], rgb.shape[3], 4), dtype=torch.float32, device=feat.device)
+        check(_lib.load().ndet_pack_rgb_nhwc4(_ptr(rgb), k, rgb.shape[2], rgb.shape[3], rgb.stride(0), rgb.stride(1), rgb.stride(2), _ptr(rgb4),
+                                              _stream(feat)), "pack_rgb_nhwc4")
+        assert feat.data_ptr() % 16 == 0 and rgb4.data_ptr() % 16 == 0
+        return BankSegment(feat, rgb4, ke, (h, w))
+
+    def drop_oldest(self, k_segments: int = 1) -> None:
+        if isinstance(k_segments, bool) or not isinstance(k_segments, int) or not 0 <= k_segments <= len(self.segments):
+            raise ValueError(f"ViewBank.drop_oldest: k={k_segments!r} for {len(self.segments)} segments held")
+        if k_segments:
+            del self.segments[:k_segments]
+            self._table = None
+
+    def clear(self) -> None:
+        self.drop_oldest(len(self.segments))
+
+    def table(self) -> Tuple[Tensor, int]:
+        """``(device table (n_views, 64) uint8 of NdetBankView rows, n_views)`` for the segments held now."""
+        n = self.n_views
+        if n == 0:
+            raise RuntimeError("the view bank holds no views")
+        if self._table is not None:
+            return self._table
+        rows = (_lib.NdetBankView * n)()
+        i = 0
+        for s in self.segments:
+            fp, ip = s.feat.stride(0) * 4, s.rgb4.stride(0) * 4
+            ke = s.ke.reshape(-1, 12).tolist()
+            for j in range(s.n_views):
+                rows[i].feat, rows[i].rgb4 = s.feat.data_ptr() + j * fp, s.rgb4.data_ptr() + j * ip
+                rows[i].ke[:] = ke[j]
+                i += 1
+        host = torch.from_numpy(np.frombuffer(rows, dtype=np.uint8).reshape(n, 64).copy())
+        self._table = (_to_device(host, self.segments[0].feat.device), n)
+        return self._table
+
+
+def ray_view_stats_bank(xyz: Tensor, bank: ViewBank):
+    """:func:`ray_view_stats` over a :class:`ViewBank`: sample points (R,S,3) -> ``globalfeat`` (R,S,2*(3+d)), ``pixel_mask`` (R,S) bool,
+    ``view_count`` (R,S) int32 (projection.py:91-151 + render_ray.py:71-93, 299-303), for any number of views in any number of segments.
+    The bank is not changed.  At most 128 views give the packed sampler's bits over the concatenated segments."""
+    if not xyz.is_cuda:
+        raise RuntimeError("nerfdet_amd.rays: tensors must live on the GPU (no CPU fallback)")
+    table, n_v = bank.table()
+    s0 = bank.segments[0]
+    if xyz.device != s0.feat.device:
+        raise ValueError("ray_view_stats_bank: the points and the bank live on different devices")
+    _, hf, wf, d = s0.feat.shape
+    H, W = s0.rgb4.shape[1], s0.rgb4.shape[2]
+    h, w = s0.img_hw
+    shape = xyz.shape[:-1]
+    pts = xyz.to(torch.float32).reshape(-1, 3).contiguous()
+    n = pts.shape[0]
+    glob = torch.empty((n, 2 * (3 + d)), dtype=torch.float32, device=xyz.device)
+    pm = torch.empty((n,), dtype=torch.bool, device=xyz.device)
+    vc = torch.empty((n,), dtype=torch.int32, device=xyz.device)
+    nbytes = 4 * (n_v * 4 * H * W + n_v * d * hf * wf + 2 * (3 + d) * n)
+    trace.span("k_ray_stats_bank", lambda: check(
+        _lib.load().ndet_ray_view_stats_bank(_ptr(pts), n, _ptr(table), n_v, h, w, H, W, d, hf, wf, _ptr(glob), _ptr(pm), _ptr(vc), _stream(xyz)),
+        "ray_view_stats_bank"), bytes=nbytes, kind="hbm")
     return glob.view(*shape, -1), pm.view(*shape), vc.view(*shape)
 
 

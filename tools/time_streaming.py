@@ -9,6 +9,11 @@ finishes (ops.density_finish_ring / volume_finish_ring, with their achieved byte
 detect() of an unwindowed stream holding the same views, the calls alternating inside one loop; and the peak allocation of filling the
 window and detecting once.
     python tools/time_streaming.py --window 1,4,8 [--reps 20 --warmup 3]
+With --render it times rendering from a streamed scene (begin_scene(keep_views=True)): the view-bank sampler against the packed sampler on
+the scene's 50 views and 8192 x 64 sample points, for the bank held as 1, 10 and 50 segments; the bank sampler at 150 and 300 views against
+the generic sampler over a concatenated copy; scene.render of one target view next to rays.render_rays(render_testing=True) over the same
+maps; and the bank's bytes per view.  The calls of a comparison alternate inside one loop.
+    python tools/time_streaming.py --render [--reps 20 --warmup 3]
 """
 import argparse
 import importlib.util
@@ -101,6 +106,90 @@ def window_mode(bench, det, img, dn, meta, sizes, reps, warmup, dev):
     return res
 
 
+def render_mode(det, img, dn, meta, rb, reps, warmup, dev):
+    from nerfdet_amd import rays, synth
+    res = {}
+    n_v = img.shape[1]
+    # the workload's ray batch is a dummy of 4 rays: one target view of real rays (tools/bench_render_testing.py's, 220 x 300 at cfg2)
+    target = synth.batch_to(synth.train_scene(1, tuple(img.shape[-2:]), t_views=1, n_boxes=1, seed=1), dev)
+    rb = det._ray_batch({k: v for k, v in target.items() if k not in ("img", "img_metas")})
+    scene = det.begin_scene(dict(meta), keep_views=True)
+    for v0 in range(0, n_v, 5):
+        scene.add_views(img[:, v0:v0 + 5], dn[:, v0:v0 + 5], chunk_meta(meta, v0, v0 + 5))
+    bank = scene.bank
+    res["bank_bytes_per_view"] = bank.nbytes() / bank.n_views
+    res["bank_mb"] = bank.nbytes() / 2 ** 20
+    feat = torch.cat([s.feat for s in bank.segments])                      # (n_v, hf, wf, cm)
+    rgb4 = torch.cat([s.rgb4 for s in bank.segments])
+    rgb = rgb4[..., :3].permute(0, 3, 1, 2).contiguous()
+    cams = rays._compute_projection(meta)
+    ray_o, ray_d = rb["ray_o"].reshape(-1, 3)[:8192], rb["ray_d"].reshape(-1, 3)[:8192]
+    pts, _ = rays.sample_along_camera_ray(ray_o, ray_d, det.near_far_range, 64, det=True)
+
+    def regroup(sizes):
+        b, v = rays.ViewBank(), 0
+        for k in sizes:
+            b.append(feat[v:v + k].permute(0, 3, 1, 2), rgb[v:v + k], chunk_meta(meta, v, v + k))
+            v += k
+        return b
+
+    # 1. the bank sampler against the packed one: same 50 views, same points; 1, 10 and 50 segments
+    banks = {1: regroup([n_v]), 10: regroup([n_v // 10] * 10), n_v: regroup([1] * n_v)}
+    f_cl = feat.permute(0, 3, 1, 2)
+    assert rays.packed_ok(n_v, f_cl.shape[1])
+    fns = {"packed_ms": lambda: rays.ray_view_stats(pts, rgb, cams, f_cl)}
+    for k, b in banks.items():
+        fns[f"bank_{k}seg_ms"] = (lambda b=b: rays.ray_view_stats_bank(pts, b))
+    want = fns["packed_ms"]()
+    for k in banks:
+        got = fns[f"bank_{k}seg_ms"]()
+        assert all(torch.equal(a, c) for a, c in zip(got, want)), f"{k} segments: not the packed sampler's bits"
+    med, span = timed_alternating(fns, reps, warmup)
+    for k in fns:
+        res[f"stats_50v_{k}"], res[f"stats_50v_{k}_min_max"] = med[k], span[k]
+    for k in banks:
+        res[f"stats_50v_bank_{k}seg_over_packed"] = med[f"bank_{k}seg_ms"] / med["packed_ms"]
+
+    # 2. beyond the packed sampler's 128 views: against the generic sampler over one concatenated copy
+    hw = (rgb.shape[2], rgb.shape[3])
+    for n_big in (150, 300):
+        g = torch.Generator().manual_seed(n_big)
+        big_meta = synth.ring_scene_meta(n_big, hw)
+        big_meta["img_shape"], big_meta["ori_shape"] = meta["img_shape"], meta["ori_shape"]
+        big_meta["lidar2img"] = dict(big_meta["lidar2img"], intrinsic=meta["lidar2img"]["intrinsic"])
+        bf = torch.randn(n_big, feat.shape[3], feat.shape[1], feat.shape[2], generator=g).to(dev).contiguous(memory_format=torch.channels_last)
+        bi = torch.rand(n_big, 3, *hw, generator=g).to(dev)
+        big, v = rays.ViewBank(), 0
+        while v < n_big:
+            k = min(5, n_big - v)
+            big.append(bf[v:v + k], bi[v:v + k], chunk_meta(big_meta, v, v + k))
+            v += k
+        big_cams = rays._compute_projection(big_meta)
+        assert not rays.packed_ok(n_big, bf.shape[1])
+        fns = {"generic_ms": lambda: rays.ray_view_stats(pts, bi, big_cams, bf), "bank_ms": lambda: rays.ray_view_stats_bank(pts, big)}
+        a, b = fns["generic_ms"](), fns["bank_ms"]()
+        assert torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
+        res[f"stats_{n_big}v_max_abs_diff"] = float((a[0] - b[0]).abs().max())
+        med, span = timed_alternating(fns, reps, warmup)
+        for k in fns:
+            res[f"stats_{n_big}v_{k}"], res[f"stats_{n_big}v_{k}_min_max"] = med[k], span[k]
+        res[f"stats_{n_big}v_bank_over_generic"] = med["bank_ms"] / med["generic_ms"]
+        del big, bf, bi
+
+    # 3. one target view: scene.render against the one-shot render_testing walk over the same maps
+    one = rb
+    fns = {"scene_render_ms": lambda: scene.render(one),
+           "one_shot_render_ms": lambda: rays.render_rays(one, None, None, f_cl, rgb, det.aabb, det.near_far_range, det.N_samples, det.N_rand,
+                                                           det.nerf_mlp, meta, None, "image", is_train=False, render_testing=True)}
+    a, b = fns["scene_render_ms"](), fns["one_shot_render_ms"]()
+    assert torch.equal(a["outputs_coarse"]["rgb"], b["outputs_coarse"]["rgb"])
+    med, span = timed_alternating(fns, max(3, reps // 4), 1)
+    for k in fns:
+        res[f"render_1view_{k}"], res[f"render_1view_{k}_min_max"] = med[k], span[k]
+    res["render_1view_rays"] = int(one["ray_o"].reshape(-1, 3).shape[0])
+    return res
+
+
 def peak_mb(fn):
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
@@ -121,6 +210,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--window", type=str, default=None, help="comma-separated window sizes in chunks of 5 views, e.g. 1,4,8")
+    ap.add_argument("--render", action="store_true", help="time rendering from a streamed scene (the view-bank sampler)")
     args = ap.parse_args()
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
@@ -133,6 +223,13 @@ def main():
     rb = det._ray_batch({k: v for k, v in batch.items() if k not in ("img", "img_metas")})
     n_v = img.shape[1]
     res = {}
+    if args.render:
+        with torch.no_grad():
+            res = render_mode(det, img, dn, meta, rb, args.reps, args.warmup, dev)
+        for k, v in res.items():
+            print(f"{k:>44}: " + (f"{v:.3f}" if isinstance(v, float) else str(v)))
+        print(json.dumps(res))
+        return
     if args.window:
         with torch.no_grad():
             res = window_mode(bench, det, img, dn, meta, [int(v) for v in args.window.split(",")], args.reps, args.warmup, dev)
