@@ -228,6 +228,77 @@ int ndet_scene_density_finish_ring(const NdetSceneAccum* segs, int n_segs, const
 /* ndet_scene_volume_finish over a ring of states (nerfdet.py:175-176, 259-261): out (N, C) channels-last, count (N) int64. */
 int ndet_scene_volume_finish_ring(const NdetSceneAccum* segs, int n_segs, const float* alpha, float* out, int64_t* count, void* stream);
 
+/* Scene groups: many streamed scenes served by one call (nerf-det_amd/streaming.py, SceneGroup).  Every scene keeps a state of its own, laid
+ * out as an NdetSceneAccum's tensors; one accumulate folds one chunk of k views per listed scene into that scene's state, one finish
+ * finishes the listed scenes' states, with grid.y = listed scene.  Nothing a scene receives depends on the other scenes of the call:
+ *   - for the same feature rows, mapped rows, images, points, projections and gate, a scene's four state tensors after
+ *     ndet_scene_accumulate_group hold the bits ndet_scene_accumulate leaves in them for that scene alone (sums and counts), for any
+ *     number of scenes, any subset and any order of the listed scenes;
+ *   - the grouped finishes write, per listed scene, the single-state finishes' rows, volume and counts bit for bit.
+ *
+ * NdetSceneSlot: one 64-byte row per scene of the group, a table in DEVICE memory (built once per group; the host cannot read it, so
+ * the caller answers for its pointers: the alignments of NdetSceneAccum, allocations of N rows at the group's pitches, points (3, N)).
+ * NdetSceneGroup: what the group's scenes share, one HOST block per call (size = sizeof(NdetSceneGroup)): the table and its n_slots
+ *   (1 .. NDET_GROUP_MAX), N, C, cm and the two state pitches, under NdetSceneAccum's rules.
+ * NdetGroupSel: the scenes one call serves, a HOST block (size = sizeof(NdetGroupSel)) that rides by value in the kernel arguments:
+ *   n          listed scenes, 1 .. NDET_GROUP_MAX; grid.y of every launch.
+ *   slot[i]    table row of listed scene i: 0 <= slot[i] < n_slots, all distinct (two blocks never share a state).
+ *   n_views[i] the scene's view total: for the accumulate the views held before the call (n_views[i] + k must fit int32), for the
+ *              finishes the views held (>= 0; the divisor-side n_views of nerfdet.py:234-253).
+ * Entries beyond n are not read. */
+#define NDET_GROUP_MAX 64
+typedef struct NdetSceneSlot {
+    float* k1_sum;
+    int32_t* k1_count;
+    float* k2_sum;
+    int32_t* k2_count;
+    const float* points;
+    int64_t reserved[3];
+} NdetSceneSlot;
+
+typedef struct NdetSceneGroup {
+    int32_t size;
+    int32_t n_slots;
+    int32_t N, C, cm;
+    int32_t reserved;
+    int64_t k1_pitch, k2_pitch;
+    const NdetSceneSlot* table;
+} NdetSceneGroup;
+
+typedef struct NdetGroupSel {
+    int32_t size;
+    int32_t n;
+    int32_t slot[NDET_GROUP_MAX];
+    int32_t n_views[NDET_GROUP_MAX];
+} NdetGroupSel;
+
+/* The host-side checks every group entry point makes before it launches anything, on their own (nerfdet.py:164-176, 234-253 are what the
+ * blocks feed): the NdetSceneGroup's fields as ndet_scene_accumulate checks an NdetSceneAccum's, the selection as described above.
+ * k > 0: also the accumulate's check that n_views[i] + k fits int32; k = 0: the finishes' checks.  NDET_OK, NDET_E_INVALID or
+ * NDET_E_UNSUPPORTED (message set); nothing is launched and no device memory is read. */
+int ndet_scene_group_check(const NdetSceneGroup* g, const NdetGroupSel* sel, int k);
+
+/* ndet_scene_accumulate for sel->n scenes in two launches (K1's running sums and count of nerfdet.py:164-176, K2's shifted sums and
+ * counts of nerfdet.py:234-253): every listed scene brings k views, 1 <= k <= 128.  features / mapped / rgb / projection /
+ * rgb_projection and the gate's maps hold n * k views, scene-major in the listed order (listed scene i owns views i k .. (i + 1) k - 1),
+ * with the pitches and alignments of ndet_scene_accumulate; k views of the mapped map and of the images must each stay below 2^31
+ * floats.  gate: NULL, or one depth gate over the n * k views (gate->n_views = n * k): it gates every scene of the call.  The states and
+ * points come from the table rows sel->slot[i].  A scene's state ends up bit-equal to ndet_scene_accumulate on that scene alone. */
+int ndet_scene_accumulate_group(const NdetSceneGroup* g, const NdetGroupSel* sel, int k, const float* features_nhwc, int h, int w,
+                                int64_t view_pitch, int64_t row_pitch, const float* mapped_nhwc, int64_t mview_pitch,
+                                int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv, int64_t rsc,
+                                int64_t rsy, const float* projection, const float* rgb_projection, const NdetDepthGate* gate,
+                                void* stream);
+
+/* ndet_scene_density_finish for the listed scenes in one launch (nerfdet.py:234-253): global_feat (n N, 2 (3 + cm)), listed scene i's
+ * voxel v in row i N + v, finished over sel->n_views[i] views; bit for bit the single-state finish's rows.  The states are only read. */
+int ndet_scene_density_finish_group(const NdetSceneGroup* g, const NdetGroupSel* sel, const float* bias, float* global_feat, void* stream);
+
+/* ndet_scene_volume_finish for the listed scenes in one launch (nerfdet.py:175-176, 259-261): out (n, N, C) channels-last, count (n, N)
+ * int64, alpha NULL or (n N) indexed as global_feat's rows; bit for bit the single-state finish's outputs.  The states are only read. */
+int ndet_scene_volume_finish_group(const NdetSceneGroup* g, const NdetGroupSel* sel, const float* alpha, float* out, int64_t* count,
+                                   void* stream);
+
 /* A6 (gating only, unfused form). volume = (1-exp(-density)) * mean, 0 where count==0; nerfdet.py:257-261.
  * mean/out in `layout` with C channels. */
 int ndet_alpha_gate(const float* mean, const float* density, const int64_t* count, float* out,

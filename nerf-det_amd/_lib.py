@@ -42,8 +42,27 @@ class NdetBankView(ctypes.Structure):    # one source view of a view bank (a DEV
     _fields_ = [("feat", _P), ("rgb4", _P), ("ke", c_float * 12)]
 
 
+NDET_GROUP_MAX = 64
+
+
+class NdetSceneSlot(ctypes.Structure):   # one scene of a scene group (a DEVICE table of these): include/nerfdet_hip.h::NdetSceneSlot, 64 bytes
+    _fields_ = [(f, _P) for f in ("k1_sum", "k1_count", "k2_sum", "k2_count", "points")] + [("reserved", c_int64 * 3)]
+
+
+class NdetSceneGroup(ctypes.Structure):  # what a group's scenes share: include/nerfdet_hip.h::NdetSceneGroup, size = sizeof(NdetSceneGroup)
+    _fields_ = [(f, ctypes.c_int32) for f in ("size", "n_slots", "N", "C", "cm", "reserved")] + [
+        ("k1_pitch", c_int64), ("k2_pitch", c_int64), ("table", _P)]
+
+
+class NdetGroupSel(ctypes.Structure):    # the scenes one grouped call serves: include/nerfdet_hip.h::NdetGroupSel, size = sizeof(NdetGroupSel)
+    _fields_ = [("size", ctypes.c_int32), ("n", ctypes.c_int32), ("slot", ctypes.c_int32 * NDET_GROUP_MAX),
+                ("n_views", ctypes.c_int32 * NDET_GROUP_MAX)]
+
+
 _G = ctypes.POINTER(NdetDepthGate)
 _S = ctypes.POINTER(NdetSceneAccum)
+_SG = ctypes.POINTER(NdetSceneGroup)
+_GS = ctypes.POINTER(NdetGroupSel)
 
 # name -> argtypes; kept in one table so tests can check the .so exports exactly this surface
 SIGNATURES = {
@@ -73,6 +92,11 @@ SIGNATURES = {
     "ndet_scene_volume_finish": ([_S, _P, _P, _P, _P], c_int),
     "ndet_scene_density_finish_ring": ([_S, c_int, _P, _P, _P], c_int),
     "ndet_scene_volume_finish_ring": ([_S, c_int, _P, _P, _P, _P], c_int),
+    "ndet_scene_group_check": ([_SG, _GS, c_int], c_int),
+    "ndet_scene_accumulate_group": ([_SG, _GS, c_int, _P, c_int, c_int, c_int64, c_int64, _P, c_int64, c_int64, _P, _P, c_int, c_int, c_int64, c_int64,
+                                     c_int64, _P, _P, _G, _P], c_int),
+    "ndet_scene_density_finish_group": ([_SG, _GS, _P, _P, _P], c_int),
+    "ndet_scene_volume_finish_group": ([_SG, _GS, _P, _P, _P, _P], c_int),
     "ndet_alpha_gate": ([_P, _P, _P, _P, c_int, c_int, c_int, _P], c_int),
     "ndet_sigma_to_alpha": ([_P, _P, c_int, _P], c_int),
     "ndet_posenc_concat": ([_P, _P, c_int, c_int, c_int, _P, _P], c_int),

@@ -486,6 +486,105 @@ __global__ __launch_bounds__(256) void k_density_finish_ring(NdetRingArgs r, int
     }
 }
 
+// k_density_accumulate_packed for the listed scenes of a group (include/nerfdet_hip.h, ndet_scene_accumulate_group), grid.y = listed scene:
+// the block takes its scene's state and points from the device table, moves the mapped maps, images, projections and gate maps on by y * k
+// views and runs the packed walk over the scene's k views.  Its own copy of the parent's epilogue; the offsets the walk records stay inside
+// the scene's k views (k * mview_pitch and k * rsv below 2^31, checked on the host).
+template <bool DG>
+__global__ __launch_bounds__(256) void k_density_accumulate_group(const NdetSceneSlot* __restrict__ table, NdetGroupSel sel, int k,
+                                                                  const float* __restrict__ mapped_all, int cm, int h, int w, int mview_pitch,
+                                                                  int mrow_pitch, const float* __restrict__ bias, const float* __restrict__ rgb_all,
+                                                                  int H, int W, int rsv, int rsc, int rsy, int N,
+                                                                  const float* __restrict__ proj_all, const float* __restrict__ rgb_proj_all,
+                                                                  int pitch, int n_blocks, int nvp, NdetGateMap gf_all, NdetGateMap gr_all) {
+    extern __shared__ int2 s_off[];
+    const int y = blockIdx.y;
+    const NdetSceneSlot& sl = table[sel.slot[y]];
+    const float* __restrict__ points = sl.points;
+    float* __restrict__ sum = sl.k2_sum;
+    int* __restrict__ count = sl.k2_count;
+    const int64_t v0 = (int64_t)y * k;                         // the scene's first view of the call
+    const float* __restrict__ mapped = mapped_all + v0 * mview_pitch;
+    const float* __restrict__ rgb = rgb_all + v0 * rsv;
+    const float* __restrict__ proj = proj_all + v0 * 12;
+    const float* __restrict__ rgb_proj = rgb_proj_all + v0 * 12;
+    NdetGateMap gf = gf_all, gr = gr_all;
+    if (DG) {
+        const size_t es = gf_all.f64 ? sizeof(double) : sizeof(float);
+        gf.map = static_cast<const char*>(gf_all.map) + (size_t)v0 * gf_all.view_pitch * es;
+        gr.map = static_cast<const char*>(gr_all.map) + (size_t)v0 * gr_all.view_pitch * es;
+    }
+    K2Sums r;
+    if (!k2_packed_sums<DG>(s_off, mapped, k, cm, h, w, mview_pitch, mrow_pitch, bias, rgb, H, W, rsv, rsc, rsy, points, N, proj, rgb_proj,
+                            n_blocks, nvp, gf, gr, r))
+        return;
+    const int seg = cm + 4;   // [r g b 0 | cm mapped channels] per sum
+    float4* row = reinterpret_cast<float4*>(sum + (int64_t)r.n * pitch + (r.is_rgb ? 0 : 4 + 4 * r.fq));
+    row[0] = ndet_add4(row[0], r.acc);
+    row[seg / 4] = ndet_add4(row[seg / 4], r.q);
+    row[2 * seg / 4] = ndet_add4(row[2 * seg / 4], r.s1);
+    if (r.is_rgb) {
+        int2* c = reinterpret_cast<int2*>(count) + r.n;
+        const int2 c0 = *c;
+        *c = make_int2(c0.x + r.cnt, c0.y + r.n_mine);
+    }
+}
+
+// k_density_finish (its own copy, expression for expression) for the listed scenes of a group: output row y N + n, finished over the
+// scene's own view total.
+__global__ __launch_bounds__(256) void k_density_finish_group(const NdetSceneSlot* __restrict__ table, NdetGroupSel sel, int pitch,
+                                                              const float* __restrict__ bias, int cm, int N, float* __restrict__ out) {
+    const int nc = 3 + cm;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)N * nc) return;
+    const int y = blockIdx.y;
+    const NdetSceneSlot& sl = table[sel.slot[y]];
+    const float* __restrict__ sum = sl.k2_sum;
+    const int* __restrict__ count = sl.k2_count;
+    const int n_views = sel.n_views[y];
+    const int n = (int)(i / nc), c = (int)(i % nc);
+    const bool is_rgb = c < 3;
+    const int k = is_rgb ? c : c + 1;          // column inside a segment
+    const int seg = cm + 4;
+    const float* row = sum + (int64_t)n * pitch;
+    const float a = row[k], qq = row[seg + k], ss = row[2 * seg + k];
+    const float fl = is_rgb ? 0.0f : bias[c - 3];
+    const int cnt = count[2 * n], n_mine = is_rgb ? count[2 * n + 1] : cnt;
+    const float denom = (float)cnt + 1e-8f;
+    const float nu = (float)(n_views - n_mine), nv = (float)n_views;
+    const float sm = a + nu * fl;
+    const float mean = sm / denom;                        // NOT zeroed at cnt == 0 (nerfdet.py:241)
+    const float dm = mean - fl;
+    float s = qq - 2.0f * dm * ss + nv * (dm * dm);
+    s = fmaxf(s, 0.0f);                                   // a sum of squares: rounding may leave -1 ulp
+    float var = s / denom;
+    if (cnt == 0) var = 1e6f;                             // nerfdet.py:249
+    *reinterpret_cast<float2*>(out + ((int64_t)y * N + n) * 2 * nc + 2 * c) = make_float2(mean, expf(-var));
+}
+
+void ndet_scene_k2_accumulate_group_launch(const NdetSceneGroup* g, const NdetGroupSel* sel, int k, const float* mapped, int h, int w,
+                                           int mview_pitch, int mrow_pitch, const float* bias, const float* rgb, int H, int W, int rsv, int rsc,
+                                           int rsy, const float* proj, const float* rgb_proj, bool gated, const NdetGateMap& gf,
+                                           const NdetGateMap& gr, hipStream_t stream) {
+    const int nvp = ((k + 63) / 64) * 64;
+    const int lds = 4 * nvp * (int)sizeof(int2) + 4 * 64 * 3 * (int)sizeof(float4);
+    const int blocks = (g->N + 3) / 4;
+#define K2G_LAUNCH(DG)                                                                                                                          \
+    hipLaunchKernelGGL((k_density_accumulate_group<DG>), dim3((unsigned)blocks, sel->n), dim3(256), lds, stream, g->table, *sel, k, mapped,    \
+                       g->cm, h, w, mview_pitch, mrow_pitch, bias, rgb, H, W, rsv, rsc, rsy, g->N, proj, rgb_proj, (int)g->k2_pitch, blocks, \
+                       nvp, gf, gr)
+    if (gated) K2G_LAUNCH(true);
+    else K2G_LAUNCH(false);
+#undef K2G_LAUNCH
+}
+
+void ndet_scene_k2_finish_group_launch(const NdetSceneGroup* g, const NdetGroupSel* sel, const float* bias, float* global_feat,
+                                       hipStream_t stream) {
+    const int64_t total = (int64_t)g->N * (3 + g->cm);
+    hipLaunchKernelGGL(k_density_finish_group, dim3((unsigned)((total + 255) / 256), sel->n), dim3(256), 0, stream, g->table, *sel,
+                       (int)g->k2_pitch, bias, g->cm, g->N, global_feat);
+}
+
 void ndet_scene_k2_accumulate_launch(const NdetSceneAccum* s, const float* mapped, int n_views, int h, int w, int mview_pitch, int mrow_pitch,
                                      const float* bias, const float* rgb, int H, int W, int rsv, int rsc, int rsy, const float* points,
                                      const float* proj, const float* rgb_proj, bool gated, const NdetGateMap& gf, const NdetGateMap& gr,

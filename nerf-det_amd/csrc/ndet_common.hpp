@@ -139,6 +139,15 @@ struct NdetRingArgs {
 void ndet_scene_k2_finish_ring_launch(const NdetSceneAccum* segs, int n_segs, int n_views, const float* bias, float* global_feat,
                                       hipStream_t stream);
 
+// Scene groups (include/nerfdet_hip.h, ndet_scene_*_group): launchers of K2's grouped accumulate (k <= 128 views per scene, grid.y = listed
+// scene) and finish kernels (density_kernels.hip), called by the entry points in volume_kernels.hip once every argument has been checked.
+void ndet_scene_k2_accumulate_group_launch(const NdetSceneGroup* g, const NdetGroupSel* sel, int k, const float* mapped, int h, int w,
+                                           int mview_pitch, int mrow_pitch, const float* bias, const float* rgb, int H, int W, int rsv, int rsc,
+                                           int rsy, const float* proj, const float* rgb_proj, bool gated, const NdetGateMap& gf,
+                                           const NdetGateMap& gr, hipStream_t stream);
+void ndet_scene_k2_finish_group_launch(const NdetSceneGroup* g, const NdetGroupSel* sel, const float* bias, float* global_feat,
+                                       hipStream_t stream);
+
 // Gradient scatter of the backward kernels.  Default: float atomics (global_atomic_add_f32) -- fast, but the ORDER of the adds, and with it the last
 // bits of every sum, changes from run to run.  Deterministic mode (tests: ndet_measurement_knob("deterministic_scatter", 1); the caller then hands
 // a zeroed buffer of int64 in place of the float buffer): every contribution is rounded to a multiple of 2^-40 and added as a 64-bit INTEGER --

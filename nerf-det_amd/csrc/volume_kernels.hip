@@ -920,6 +920,218 @@ extern "C" int ndet_scene_volume_finish_ring(const NdetSceneAccum* segs, int n_s
 }
 
 // ------------------------------------------------------------------------------------------
+// Scene groups (include/nerfdet_hip.h, NdetSceneSlot / NdetSceneGroup / NdetGroupSel): many scenes' chunks in one launch, grid.y = listed
+// scene.  A block reads its scene's row of the device table, moves the view-indexed inputs on by y * k views -- as the host loop of
+// ndet_scene_accumulate moves them on per 128-view launch -- and runs the single-scene walk on that scene's state and points.  The kernels
+// are copies of their parents' bodies around the shared walks (k1_walk, k2_packed_sums); no block reads or writes another scene's state.
+// The XCD remap stays on blockIdx.x: a scene's neighbouring tiles still share an L2, which XCD a slab lands on differs from row to row
+// when the tile count is no multiple of 8 (locality only).
+// ------------------------------------------------------------------------------------------
+template <int NCHUNK, bool DG>
+__global__ __launch_bounds__(256, DG ? K1_MIN_WAVES - 1 : K1_MIN_WAVES) void k_backproject_accumulate_group(
+    const NdetSceneSlot* __restrict__ table, NdetGroupSel sel, int k, const float* __restrict__ feat_all, int C, int h, int w,
+    int64_t view_pitch, int row_pitch, int N, const float* __restrict__ proj_all, int pitch, int n_tiles, NdetGateMap dgate_all) {
+    constexpr int VPW = K1_VPW;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int y = blockIdx.y;                                  // listed scene: block-uniform, the row comes in through scalar loads
+    const NdetSceneSlot& sl = table[sel.slot[y]];
+    const float* __restrict__ points = sl.points;
+    float* __restrict__ sum = sl.k1_sum;
+    int* __restrict__ count = sl.k1_count;
+    const int64_t v0 = (int64_t)y * k;                         // the scene's first view of the call
+    const float* __restrict__ feat = feat_all + v0 * view_pitch;
+    const float* __restrict__ proj = proj_all + v0 * 12;
+    NdetGateMap dgate = dgate_all;
+    if (DG) dgate.map = static_cast<const char*>(dgate_all.map) + (size_t)v0 * dgate_all.view_pitch * (dgate_all.f64 ? sizeof(double) : sizeof(float));
+    const int tile = ndet_xcd_remap(blockIdx.x, n_tiles);
+    const int n0 = tile * VOX_PER_TILE;
+    const int c4 = C >> 2;
+    float px[VPW], py[VPW], pz[VPW];
+    bool live[VPW];
+    float4 acc[VPW][NCHUNK];
+    int cnt[VPW];
+#pragma unroll
+    for (int j = 0; j < VPW; ++j) {
+        const int n = n0 + j * 4 + wave;
+        live[j] = n < N;  // wave-uniform
+        const int nn = live[j] ? n : 0;
+        px[j] = points[nn];
+        py[j] = points[N + nn];
+        pz[j] = points[2 * N + nn];
+        cnt[j] = live[j] ? count[nn] : 0;
+#pragma unroll
+        for (int q = 0; q < NCHUNK; ++q) {
+            const int ci = lane + q * 64;
+            acc[j][q] = (live[j] && ci < c4) ? *reinterpret_cast<const float4*>(sum + (int64_t)nn * pitch + ci * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    k1_walk<NCHUNK, DG>(feat, k, C, h, w, view_pitch, row_pitch, proj, px, py, pz, live, acc, cnt, dgate, lane);
+#pragma unroll
+    for (int j = 0; j < VPW; ++j) {
+        if (!live[j]) continue;
+        const int n = n0 + j * 4 + wave;
+#pragma unroll
+        for (int q = 0; q < NCHUNK; ++q) {
+            const int ci = lane + q * 64;
+            if (ci < c4) *reinterpret_cast<float4*>(sum + (int64_t)n * pitch + ci * 4) = acc[j][q];
+        }
+        if (lane == 0) count[n] = cnt[j];
+    }
+}
+
+// k_volume_finish (its own copy, expression for expression) for the listed scenes: output row y N + n, alpha indexed the same way.
+__global__ __launch_bounds__(256) void k_volume_finish_group(const NdetSceneSlot* __restrict__ table, NdetGroupSel sel, int pitch,
+                                                             const float* __restrict__ alpha, int C, int N, float* __restrict__ out,
+                                                             int64_t* __restrict__ out_count) {
+    const int c4 = C >> 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)N * c4) return;
+    const int y = blockIdx.y;
+    const NdetSceneSlot& sl = table[sel.slot[y]];
+    const float* __restrict__ sum = sl.k1_sum;
+    const int* __restrict__ count = sl.k1_count;
+    const int n = (int)(i / c4), q = (int)(i % c4);
+    const int64_t row = (int64_t)y * N + n;
+    const int cnt = count[n];
+    const float denom = (float)cnt + 1e-8f;
+    const float4 s = *reinterpret_cast<const float4*>(sum + (int64_t)n * pitch + q * 4);
+    float4 mean;
+    mean.x = s.x / denom;
+    mean.y = s.y / denom;
+    mean.z = s.z / denom;
+    mean.w = s.w / denom;
+    if (alpha) {
+        const float a = alpha[row];
+        mean.x = a * mean.x;
+        mean.y = a * mean.y;
+        mean.z = a * mean.z;
+        mean.w = a * mean.w;
+    }
+    if (cnt == 0) mean = make_float4(0.f, 0.f, 0.f, 0.f);
+    *reinterpret_cast<float4*>(out + row * C + q * 4) = mean;
+    if (q == 0) out_count[row] = (int64_t)cnt;
+}
+
+// The group's block and a call's selection, checked before any launch (the table itself is device memory: its rows are the caller's).
+static int group_check(const NdetSceneGroup* g, const NdetGroupSel* sel, int k, const char* fn) {
+    NDET_REQUIRE(g, NDET_E_INVALID, "%s: null scene group", fn);
+    NDET_REQUIRE(g->size == (int32_t)sizeof(NdetSceneGroup), NDET_E_INVALID, "%s: NdetSceneGroup.size %d != %d (caller built against another layout)",
+                 fn, g->size, (int)sizeof(NdetSceneGroup));
+    NDET_REQUIRE(g->table, NDET_E_INVALID, "%s: null scene table", fn);
+    NDET_REQUIRE(((uintptr_t)g->table & 15) == 0, NDET_E_UNSUPPORTED, "%s: the scene table must be 16-byte aligned", fn);
+    NDET_REQUIRE(g->n_slots >= 1 && g->n_slots <= NDET_GROUP_MAX, NDET_E_INVALID, "%s: n_slots=%d must be 1 .. %d", fn, g->n_slots, NDET_GROUP_MAX);
+    NDET_REQUIRE(g->N > 0 && g->C > 0 && g->cm > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
+    NDET_REQUIRE(g->C % 4 == 0 && g->C <= 1024, NDET_E_UNSUPPORTED, "%s: C=%d must be a multiple of 4 and <= 1024", fn, g->C);
+    NDET_REQUIRE(g->cm % 4 == 0 && g->cm <= 128, NDET_E_UNSUPPORTED, "%s: cm=%d must be a multiple of 4 and <= 128", fn, g->cm);
+    NDET_REQUIRE(g->k1_pitch >= g->C && g->k2_pitch >= 3 * (g->cm + 4), NDET_E_INVALID, "%s: state pitches smaller than a row", fn);
+    NDET_REQUIRE(g->k1_pitch < ((int64_t)1 << 31) && g->k2_pitch < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: state pitches exceed int32", fn);
+    NDET_REQUIRE(g->k1_pitch % 4 == 0 && g->k2_pitch % 4 == 0, NDET_E_UNSUPPORTED, "%s: state rows must be 16-byte aligned", fn);
+    NDET_REQUIRE(sel, NDET_E_INVALID, "%s: null selection", fn);
+    NDET_REQUIRE(sel->size == (int32_t)sizeof(NdetGroupSel), NDET_E_INVALID, "%s: NdetGroupSel.size %d != %d (caller built against another layout)",
+                 fn, sel->size, (int)sizeof(NdetGroupSel));
+    NDET_REQUIRE(sel->n >= 1 && sel->n <= NDET_GROUP_MAX, NDET_E_INVALID, "%s: %d listed scenes, must be 1 .. %d", fn, sel->n, NDET_GROUP_MAX);
+    NDET_REQUIRE(k >= 0, NDET_E_INVALID, "%s: k=%d views", fn, k);
+    unsigned long long used = 0ull;
+    for (int i = 0; i < sel->n; ++i) {
+        const int s = sel->slot[i];
+        NDET_REQUIRE(s >= 0 && s < g->n_slots, NDET_E_INVALID, "%s: slot[%d]=%d outside the table's %d rows", fn, i, s, g->n_slots);
+        NDET_REQUIRE(!((used >> s) & 1ull), NDET_E_INVALID, "%s: slot[%d]=%d is listed twice", fn, i, s);
+        used |= 1ull << s;
+        NDET_REQUIRE(sel->n_views[i] >= 0, NDET_E_INVALID, "%s: n_views[%d]=%d", fn, i, sel->n_views[i]);
+        NDET_REQUIRE(sel->n_views[i] <= 0x7fffffff - k, NDET_E_UNSUPPORTED, "%s: view count of slot[%d] overflows int32", fn, i);
+    }
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_group_check(const NdetSceneGroup* g, const NdetGroupSel* sel, int k) {
+    return group_check(g, sel, k, "ndet_scene_group_check");
+}
+
+extern "C" int ndet_scene_accumulate_group(const NdetSceneGroup* g, const NdetGroupSel* sel, int k, const float* features_nhwc, int h, int w,
+                                           int64_t view_pitch, int64_t row_pitch, const float* mapped_nhwc, int64_t mview_pitch,
+                                           int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv, int64_t rsc,
+                                           int64_t rsy, const float* projection, const float* rgb_projection, const NdetDepthGate* gate,
+                                           void* stream) {
+    const char* fn = "ndet_scene_accumulate_group";
+    NDET_REQUIRE(k >= 1 && k <= 128, NDET_E_UNSUPPORTED, "%s: k=%d views per scene, must be 1 .. 128", fn, k);
+    int rc = group_check(g, sel, k, fn);
+    if (rc != NDET_OK) return rc;
+    const int N = g->N, C = g->C, cm = g->cm, n = sel->n;
+    NDET_REQUIRE(features_nhwc && mapped_nhwc && bias && rgb && projection && rgb_projection, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(h > 0 && w > 0 && H > 0 && W > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
+    // K1's inputs (ndet_scene_accumulate)
+    NDET_REQUIRE(row_pitch >= (int64_t)w * C && view_pitch >= (int64_t)h * row_pitch, NDET_E_INVALID, "%s: feature pitches smaller than the map", fn);
+    NDET_REQUIRE(row_pitch % 4 == 0 && view_pitch % 4 == 0 && ((uintptr_t)features_nhwc & 15) == 0, NDET_E_UNSUPPORTED,
+                 "%s: feature rows must be 16-byte aligned", fn);
+    NDET_REQUIRE((int64_t)h * row_pitch < (int64_t)1 << 31, NDET_E_UNSUPPORTED, "%s: one view exceeds 2^31 floats", fn);
+    // K2's inputs: a scene's k views are one packed launch's
+    NDET_REQUIRE(mrow_pitch >= (int64_t)w * cm && mview_pitch >= (int64_t)h * mrow_pitch && rsy >= W && rsc >= 0 && rsv >= 0, NDET_E_INVALID,
+                 "%s: mapped / image pitches smaller than the maps", fn);
+    NDET_REQUIRE((int64_t)k * mview_pitch < ((int64_t)1 << 31) && (int64_t)k * rsv + 3 * rsc < ((int64_t)1 << 31), NDET_E_UNSUPPORTED,
+                 "%s: a scene's source tensor exceeds 2^31 floats", fn);
+    NDET_REQUIRE(mview_pitch % 4 == 0 && mrow_pitch % 4 == 0 && (((uintptr_t)mapped_nhwc | (uintptr_t)bias) & 15) == 0, NDET_E_UNSUPPORTED,
+                 "%s: mapped features / bias must keep channel quads 16-byte aligned", fn);
+    NdetGateMap gf = {}, gr = {};
+    if (gate) {
+        rc = ndet_gate_prepare(gate, fn, n * k, h, w, H, W, true, &gf, &gr);
+        if (rc != NDET_OK) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int n_tiles = (N + VOX_PER_TILE - 1) / VOX_PER_TILE;
+    const int rp = (int)row_pitch, k1p = (int)g->k1_pitch;
+    const dim3 grid(n_tiles, n);
+#define K1G_LAUNCH(NC, DG)                                                                                                                  \
+    hipLaunchKernelGGL((k_backproject_accumulate_group<NC, DG>), grid, dim3(256), 0, st, g->table, *sel, k, features_nhwc, C, h, w, view_pitch, \
+                       rp, N, projection, k1p, n_tiles, gf)
+#define K1G_CHUNKS(DG)                \
+    if (C <= 256) K1G_LAUNCH(1, DG);  \
+    else if (C <= 512) K1G_LAUNCH(2, DG); \
+    else K1G_LAUNCH(4, DG)
+    if (gate) {
+        K1G_CHUNKS(true);
+    } else {
+        K1G_CHUNKS(false);
+    }
+#undef K1G_CHUNKS
+#undef K1G_LAUNCH
+    NDET_CHECK_LAUNCH(fn);
+    ndet_scene_k2_accumulate_group_launch(g, sel, k, mapped_nhwc, h, w, (int)mview_pitch, (int)mrow_pitch, bias, rgb, H, W, (int)rsv, (int)rsc,
+                                          (int)rsy, projection, rgb_projection, gate != nullptr, gf, gr, st);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_density_finish_group(const NdetSceneGroup* g, const NdetGroupSel* sel, const float* bias, float* global_feat,
+                                               void* stream) {
+    const char* fn = "ndet_scene_density_finish_group";
+    const int rc = group_check(g, sel, 0, fn);
+    if (rc != NDET_OK) return rc;
+    NDET_REQUIRE(bias && global_feat, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(((uintptr_t)global_feat & 7) == 0, NDET_E_UNSUPPORTED, "%s: global_feat must be 8-byte aligned", fn);
+    NDET_REQUIRE(((int64_t)g->N * (g->cm + 3) + 255) / 256 < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
+    ndet_scene_k2_finish_group_launch(g, sel, bias, global_feat, (hipStream_t)stream);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_volume_finish_group(const NdetSceneGroup* g, const NdetGroupSel* sel, const float* alpha, float* out, int64_t* count,
+                                              void* stream) {
+    const char* fn = "ndet_scene_volume_finish_group";
+    const int rc = group_check(g, sel, 0, fn);
+    if (rc != NDET_OK) return rc;
+    NDET_REQUIRE(out && count, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(((uintptr_t)out & 15) == 0, NDET_E_UNSUPPORTED, "%s: out must be 16-byte aligned", fn);
+    NDET_REQUIRE(((uintptr_t)count & 7) == 0, NDET_E_UNSUPPORTED, "%s: count must be 8-byte aligned", fn);
+    const int64_t blocks = ((int64_t)g->N * (g->C / 4) + 255) / 256;
+    NDET_REQUIRE(blocks < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
+    hipLaunchKernelGGL(k_volume_finish_group, dim3((unsigned)blocks, sel->n), dim3(256), 0, (hipStream_t)stream, g->table, *sel,
+                       (int)g->k1_pitch, alpha, g->C, g->N, out, count);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // K2  density conditioning features   A5
 //
 // One wavefront per voxel, lanes over the 3 + cm channels (35 of 64 lanes at cm = 32): lanes 0-2

@@ -481,6 +481,191 @@ def volume_finish_ring(states: Sequence[SceneState], alpha: Optional[Tensor] = N
 
 
 # --------------------------------------------------------------------------------------------
+# Scene groups: many scenes' states behind one device table, accumulated and finished by grouped launches
+# (include/nerfdet_hip.h, NdetSceneSlot / NdetSceneGroup / NdetGroupSel)
+# --------------------------------------------------------------------------------------------
+GROUP_MAX = 64        # scenes of one group (include/nerfdet_hip.h, NDET_GROUP_MAX)
+GROUP_VIEWS_MAX = 128  # views one scene brings to one grouped accumulate (one packed K2 launch)
+
+
+def listed_scenes(n_scenes: int, scenes) -> list:
+    """``scenes`` of a grouped call over ``n_scenes`` scenes -- None: all of them, in order -- as a list of distinct indices (else ValueError)."""
+    if scenes is None:
+        return list(range(n_scenes))
+    scenes = list(scenes)
+    if not scenes:
+        raise ValueError("a grouped call lists at least one scene")
+    for s in scenes:
+        if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= s < n_scenes:
+            raise ValueError(f"scene index {s!r} outside the group's {n_scenes} scenes")
+    if len(set(int(s) for s in scenes)) != len(scenes):
+        raise ValueError(f"scenes {scenes} lists a scene twice")
+    return [int(s) for s in scenes]
+
+
+def compute_projection_group(img_metas, strides, device=None) -> Tensor:
+    """:func:`compute_projection` for the chunk metas of several scenes and several strides at once: ``(len(strides), sum of views, 3, 4)``, the
+    rows in the metas' order -- the same host arithmetic element for element (hostmath.py), one product and one asynchronous upload for all."""
+    ks, exts = [], []
+    for stride in strides:
+        for m in img_metas:
+            k = torch.tensor(np.asarray(m["lidar2img"]["intrinsic"], dtype=np.float32)[:3, :3])
+            k[:2] /= m["ori_shape"][0] / (m["img_shape"][0] / stride)
+            ext = np.stack([np.asarray(e, dtype=np.float32)[:3] for e in m["lidar2img"]["extrinsic"]])
+            ks.append(np.broadcast_to(k.numpy()[None], (ext.shape[0], 3, 3)))
+            exts.append(ext)
+    proj = torch.from_numpy(matmul_fma_chain(np.concatenate(ks), np.concatenate(exts))).reshape(len(strides), -1, 3, 4)
+    if device is None:
+        return proj
+    return _upload_async(proj, device) if torch.device(device).type == "cuda" else proj.to(device)
+
+
+class SceneGroupState:
+    """The states of S scenes (1 .. 64) that share grid, C and cm, one :class:`SceneState` and one ``(3,X,Y,Z)`` point lattice per scene, and
+    the device table the grouped kernels find them through: one 64-byte NdetSceneSlot per scene, built on the host once and uploaded
+    asynchronously.  The group owns every tensor the table points to, for its whole life: states are zeroed in place, never replaced.
+    The upload is ordered on the stream that is current when the group is built (as a view bank's table is): use the group on that stream, or
+    make the other stream wait for it first."""
+
+    def __init__(self, n_voxels, c: int, cm: int, points: Sequence[Tensor], device):
+        points = list(points)
+        if not 1 <= len(points) <= GROUP_MAX:
+            raise ValueError(f"a scene group holds 1 to {GROUP_MAX} scenes, got {len(points)}")
+        self.states = [SceneState(n_voxels, c, cm, device) for _ in points]
+        s0 = self.states[0]
+        self.grid, self.c, self.cm = s0.grid, s0.c, s0.cm
+        self.points = []
+        for p in points:
+            _need_gpu(p)
+            assert tuple(p.shape[-3:]) == self.grid and p.shape[0] == 3, f"points {tuple(p.shape)} for a {self.grid} state"
+            self.points.append(_f32c(p))
+        rows = (_lib.NdetSceneSlot * len(points))()
+        for row, st, p in zip(rows, self.states, self.points):
+            assert (st.k1_sum.stride(0), st.k2_sum.stride(0)) == (s0.k1_sum.stride(0), s0.k2_sum.stride(0))
+            assert (st.k1_sum.data_ptr() | st.k2_sum.data_ptr()) % 16 == 0 and st.k1_count.data_ptr() % 4 == 0 and st.k2_count.data_ptr() % 8 == 0 \
+                and p.data_ptr() % 4 == 0, "state rows must be 16-byte aligned"
+            row.k1_sum, row.k1_count, row.k2_sum, row.k2_count = st.k1_sum.data_ptr(), st.k1_count.data_ptr(), st.k2_sum.data_ptr(), st.k2_count.data_ptr()
+            row.points = p.data_ptr()
+        host = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8)
+        dev = torch.device(device)
+        self.table = _upload_async(host, dev) if dev.type == "cuda" else host.clone()
+        self.device = dev
+
+    def __len__(self) -> int:
+        return len(self.states)
+
+    @property
+    def n_voxels(self) -> int:
+        return self.states[0].n_voxels
+
+    @property
+    def n_views(self):
+        return [st.n_views for st in self.states]
+
+    def listed(self, scenes) -> list:
+        """``scenes`` (None: every scene, in order) as a checked list of distinct scene indices."""
+        return listed_scenes(len(self.states), scenes)
+
+    def block(self) -> "_lib.NdetSceneGroup":
+        s0 = self.states[0]
+        g = _lib.NdetSceneGroup()
+        g.size = ctypes.sizeof(_lib.NdetSceneGroup)
+        g.n_slots, g.N, g.C, g.cm = len(self.states), s0.n_voxels, s0.c, s0.cm
+        g.k1_pitch, g.k2_pitch, g.table = s0.k1_sum.stride(0), s0.k2_sum.stride(0), self.table.data_ptr()
+        return g
+
+    def sel(self, scenes) -> "_lib.NdetGroupSel":
+        """The C ABI's selection block for the (checked) scene list, with the scenes' view totals."""
+        sel = _lib.NdetGroupSel()
+        sel.size = ctypes.sizeof(_lib.NdetGroupSel)
+        sel.n = len(scenes)
+        for i, s in enumerate(scenes):
+            sel.slot[i], sel.n_views[i] = s, self.states[s].n_views
+        return sel
+
+
+def scene_accumulate_group(group: SceneGroupState, scenes, features: Tensor, mapped: Tensor, bias: Tensor, denorm_images: Tensor,
+                           projection: Tensor, rgb_projection: Tensor, depth_gate: Optional[DepthGate] = None) -> None:
+    """:func:`scene_accumulate` for the listed scenes in two launches: every listed scene brings k views (1 .. 128), the view-indexed arguments
+    hold ``len(scenes) * k`` views, scene-major in the listed order (``features`` (n k,C,h,w), ``mapped`` (n k,cm,h,w), ``denorm_images``
+    (n k,3,H,W), the projections (n k,3,4), the gate's maps).  ``scenes``: None (all, in order) or distinct scene indices.  ``depth_gate``
+    gates every scene of the call.  Each scene's state ends up bit-equal to :func:`scene_accumulate` on that scene alone, whatever the
+    other scenes, the subset or its order."""
+    _need_gpu(features, mapped, bias, denorm_images, projection, rgb_projection)
+    scenes = group.listed(scenes)
+    n = len(scenes)
+    f = to_channels_last(features)
+    m = to_channels_last(mapped)
+    n_v, c, h, w = f.shape
+    if n_v % n or not 1 <= n_v // n <= GROUP_VIEWS_MAX:
+        raise ValueError(f"{n_v} views for {n} scenes: every listed scene brings the same 1 .. {GROUP_VIEWS_MAX} views")
+    k = n_v // n
+    assert m.shape[0] == n_v and m.shape[2:] == f.shape[2:], f"mapped map {tuple(m.shape)} for features {tuple(f.shape)}"
+    assert (c, m.shape[1]) == (group.c, group.cm), f"group for C={group.c}, cm={group.cm}; chunk has {c}, {m.shape[1]}"
+    if not density_packed_ok(0, group.cm, m):       # the packed walk's channel quads need 16-byte aligned rows
+        m = to_channels_last(m.contiguous())
+    rgb = denorm_images if denorm_images.dtype == torch.float32 else denorm_images.float()
+    assert rgb.shape[0] == n_v and rgb.shape[1] == 3
+    if rgb.stride(3) != 1:
+        rgb = rgb.contiguous()
+    hh, ww = rgb.shape[2:]
+    projection, rgb_projection, bias = _f32c(projection), _f32c(rgb_projection), _f32c(bias)
+    assert projection.shape == (n_v, 3, 4) and rgb_projection.shape == (n_v, 3, 4)
+    g = None if depth_gate is None else _gate_arg(depth_gate, n_v, (h, w), (hh, ww))
+    blk, sel = group.block(), group.sel(scenes)
+    s0 = group.states[0]
+    trace.span("k_scene_accumulate_group", lambda: check(_lib.load().ndet_scene_accumulate_group(
+        ctypes.byref(blk), ctypes.byref(sel), k, _ptr(f), h, w, f.stride(0), f.stride(2), _ptr(m), m.stride(0), m.stride(2), _ptr(bias), _ptr(rgb),
+        hh, ww, rgb.stride(0), rgb.stride(1), rgb.stride(2), _ptr(projection), _ptr(rgb_projection), g, _stream(f)), "scene_accumulate_group"),
+        bytes=4 * (n_v * (c * h * w + group.cm * h * w + 3 * hh * ww)) + 2 * n * (s0.k1_sum.numel() + s0.k2_sum.numel()) * 4, kind="hbm")
+    for s in scenes:
+        group.states[s].n_views += k
+
+
+def _group_finish_args(group: SceneGroupState, scenes):
+    scenes = group.listed(scenes)
+    empty = [s for s in scenes if group.states[s].n_views == 0]
+    if empty:
+        raise ValueError(f"scenes {empty} have no views yet")
+    return scenes, group.block(), group.sel(scenes)
+
+
+def density_finish_group(group: SceneGroupState, bias: Tensor, scenes=None) -> Tensor:
+    """:func:`density_finish` for the listed scenes in one launch: ``(len(scenes) * N, 2*(3+cm))`` rows, listed scene i's voxel v in row
+    ``i N + v``, each scene finished over its own view total; bit for bit :func:`density_finish`'s rows per scene.  No state is changed."""
+    _need_gpu(bias)
+    scenes, blk, sel = _group_finish_args(group, scenes)
+    bias = _f32c(bias)
+    assert bias.numel() == group.cm
+    s0 = group.states[0]
+    out = torch.empty((len(scenes) * s0.n_voxels, 2 * (3 + group.cm)), dtype=torch.float32, device=s0.k1_sum.device)
+    trace.span("k_density_finish_group", lambda: check(_lib.load().ndet_scene_density_finish_group(
+        ctypes.byref(blk), ctypes.byref(sel), _ptr(bias), _ptr(out), _stream(out)), "scene_density_finish_group"),
+        bytes=4 * (len(scenes) * s0.k2_sum.numel() + out.numel()), kind="hbm")
+    return out
+
+
+def volume_finish_group(group: SceneGroupState, alpha: Optional[Tensor] = None, scenes=None) -> Tuple[Tensor, Tensor]:
+    """:func:`volume_finish` for the listed scenes in one launch: ``(volume (n,C,X,Y,Z) with (n,X,Y,Z,C) memory, count (n,1,X,Y,Z) int64)``;
+    ``alpha`` None or ``n * N`` values indexed as :func:`density_finish_group`'s rows.  Bit for bit :func:`volume_finish`'s outputs per scene;
+    no state is changed."""
+    _need_gpu(alpha)
+    scenes, blk, sel = _group_finish_args(group, scenes)
+    n, s0 = len(scenes), group.states[0]
+    dev = s0.k1_sum.device
+    if alpha is not None:
+        alpha = _f32c(alpha).reshape(-1)
+        assert alpha.numel() == n * s0.n_voxels
+    gx, gy, gz = group.grid
+    buf = torch.empty((n, gx, gy, gz, group.c), dtype=torch.float32, device=dev)
+    count = torch.empty((n, 1, gx, gy, gz), dtype=torch.int64, device=dev)
+    trace.span("k_volume_finish_group", lambda: check(_lib.load().ndet_scene_volume_finish_group(
+        ctypes.byref(blk), ctypes.byref(sel), _ptr(alpha), _ptr(buf), _ptr(count), _stream(buf)), "scene_volume_finish_group"),
+        bytes=n * (8 * s0.k1_sum.numel() + 12 * s0.n_voxels), kind="hbm")
+    return buf.permute(0, 4, 1, 2, 3), count
+
+
+# --------------------------------------------------------------------------------------------
 # A6 pieces
 # --------------------------------------------------------------------------------------------
 def sigma_to_alpha(raw_sigma: Tensor) -> Tensor:

@@ -22,6 +22,13 @@ views through a device table of pointers, oldest first, so the summation order i
 render is the one-shot packed sampler's bits over the same maps; beyond, the one-pass variance differs from the generic kernel's two-pass
 one by rounding.  In a window a chunk's bank segment leaves with its state.  Renders and evictions go out on one stream (rays.ViewBank).
 
+``nerfdet.begin_scenes([img_meta_0, ...])`` returns a :class:`SceneGroup`: up to 64 scenes with a state each, fed and finished together -- one
+backbone pass, one guard read and one grouped accumulate per ``add_views`` call over one chunk per listed scene (ops.scene_accumulate_group),
+one grouped density finish, one sigma-MLP call and one grouped volume finish per ``detect`` (ops.density_finish_group / volume_finish_group), then
+neck_3d and the tails scene by scene, all queued before the host waits.  Each scene's state holds the bits
+``ops.scene_accumulate`` leaves for that scene alone; a group of one scene is a ``SceneStream`` bit for bit.  Groups are unwindowed and keep no
+view bank.
+
 Inference only: no training / autograd, no hipGraph replay, one scene per stream; whole chunks are dropped, not single views out of one.
 Without ``keep_views`` there is no ray branch (rendering needs every view's map).
 """
@@ -37,6 +44,19 @@ from . import conv3d, ops
 from .volume import map_features_2d, map_features_2d_hip
 
 Tensor = torch.Tensor
+
+
+def check_chunk_meta(scene_meta: dict, img_meta: dict, k: int) -> None:
+    """A chunk's meta against its scene's: same intrinsic, origin, img_shape and ori_shape, and k extrinsics (else ValueError)."""
+    a, b = scene_meta, img_meta
+    for key in ("intrinsic", "origin"):
+        if not np.array_equal(np.asarray(a["lidar2img"][key], dtype=np.float64), np.asarray(b["lidar2img"][key], dtype=np.float64)):
+            raise ValueError(f"add_views: the chunk's lidar2img.{key} differs from the scene's")
+    for key in ("img_shape", "ori_shape"):
+        if tuple(a[key]) != tuple(b[key]):
+            raise ValueError(f"add_views: the chunk's {key} {tuple(b[key])} differs from the scene's {tuple(a[key])}")
+    if len(b["lidar2img"]["extrinsic"]) != k:
+        raise ValueError(f"add_views: {len(b['lidar2img']['extrinsic'])} extrinsics for {k} views")
 
 
 class SceneStream:
@@ -137,15 +157,7 @@ class SceneStream:
             self.bank.push(banked)
 
     def _check_meta(self, img_meta: dict, k: int) -> None:
-        a, b = self.meta, img_meta
-        for key in ("intrinsic", "origin"):
-            if not np.array_equal(np.asarray(a["lidar2img"][key], dtype=np.float64), np.asarray(b["lidar2img"][key], dtype=np.float64)):
-                raise ValueError(f"add_views: the chunk's lidar2img.{key} differs from the scene's")
-        for key in ("img_shape", "ori_shape"):
-            if tuple(a[key]) != tuple(b[key]):
-                raise ValueError(f"add_views: the chunk's {key} {tuple(b[key])} differs from the scene's {tuple(a[key])}")
-        if len(b["lidar2img"]["extrinsic"]) != k:
-            raise ValueError(f"add_views: {len(b['lidar2img']['extrinsic'])} extrinsics for {k} views")
+        check_chunk_meta(self.meta, img_meta, k)
 
     def _features(self, img: Tensor):
         x, _, stride = self.det.extract_2d(img)
@@ -292,5 +304,206 @@ class SceneStream:
             with torch.no_grad():
                 x = self.det.neck_3d(vol.unsqueeze(0))
                 return self.det._detect_tail(x, valid.unsqueeze(0), metas, False, False, vol.device, None)
+        finally:
+            conv3d.set_arithmetic(prev)
+
+
+_TRIPPED = object()     # a deferred tail's answer when the range-guard word came back set (SceneGroup.detect)
+
+
+class SceneGroup:
+    """S scenes (1 .. ops.GROUP_MAX) of one detector streamed together: ``det.begin_scenes([img_meta_0, ..., img_meta_{S-1}])``.  Every scene
+    has its own ``lidar2img.intrinsic``, ``lidar2img.origin`` and extrinsics and its own state; ``img_shape``, ``ori_shape``, the voxel grid and
+    the detector are the group's.  One :meth:`add_views` call runs the backbone once over one chunk of k views (1 .. ops.GROUP_VIEWS_MAX) per
+    listed scene and folds every chunk into its scene's state with one grouped accumulate (ops.scene_accumulate_group); one :meth:`detect`
+    finishes the listed scenes with one grouped density finish, one sigma-MLP call, one grouped volume finish and one neck_3d call over the
+    batch (which neck_3d walks scene by scene), queues every scene's tail and then waits once.  ``scenes``: None (all scenes, in order) or a list of distinct scene indices -- cameras do not
+    tick together, so a call may serve a subset.
+
+    What is exact: a scene's state after a grouped accumulate is bit-equal to ops.scene_accumulate on that scene alone (sums and counts),
+    whatever the other scenes, the subset or its order, and the grouped finishes give the single-state finishes' rows, volume and counts bit
+    for bit.  A group of one scene gives :class:`SceneStream`'s detections bit for bit (hence a single chunk gives ``simple_test``'s).  With
+    more than one scene the backbone's per-tensor fp16-pair scales are shared by the scenes of a call (neck_3d and the head still run scene by
+    scene, on scales of their own): detections agree with separate streams within the chunking contract -- same labels in the same order,
+    scores and boxes to 1e-4.
+
+    Unwindowed, and no view bank: ``window=`` and ``keep_views=`` for groups are out of scope, as are scenes of different image sizes or
+    grids in one group, training, and the graphed path."""
+
+    def __init__(self, det, img_metas):
+        metas = list(img_metas)
+        if not 1 <= len(metas) <= ops.GROUP_MAX:
+            raise ValueError(f"begin_scenes takes 1 to {ops.GROUP_MAX} scenes, got {len(metas)}")
+        self._check_shapes(metas[0], metas)
+        if det.training:
+            raise RuntimeError("SceneGroup is inference only: call det.eval() first")
+        if det.render_testing:
+            raise NotImplementedError("SceneGroup does not render rays (render_testing needs every view's feature map)")
+        self.det = det
+        self.metas = metas
+        self.device = next(det.parameters()).device
+        lin = det.mapping[0]
+        self._lin = lin
+        points = [ops.get_points(det.n_voxels, det.voxel_size, m["lidar2img"]["origin"], self.device) for m in metas]
+        self.group = ops.SceneGroupState(det.n_voxels, lin.in_features, lin.out_features, points, self.device)
+
+    @staticmethod
+    def _check_shapes(first: dict, metas) -> None:
+        for i, m in enumerate(metas):
+            for key in ("img_shape", "ori_shape"):
+                if tuple(m[key]) != tuple(first[key]):
+                    raise ValueError(f"scene {i}'s {key} {tuple(m[key])} differs from the group's {tuple(first[key])}")
+
+    @property
+    def n_scenes(self) -> int:
+        return len(self.metas)
+
+    @property
+    def n_views(self) -> List[int]:
+        """View counts of the S scenes."""
+        return self.group.n_views
+
+    def reset(self, scenes=None) -> None:
+        """Forget every view of the listed scenes: they start empty again; the others keep theirs."""
+        for s in ops.listed_scenes(self.n_scenes, scenes):
+            self.group.states[s].reset()
+
+    def _check_call(self, img: Tensor, denorm_images: Tensor, metas, scenes, depth):
+        """Everything add_views refuses, before anything is launched: ``(listed scenes, k)``."""
+        scenes = ops.listed_scenes(self.n_scenes, scenes)
+        n = len(scenes)
+        if img.dim() != 5 or img.shape[0] != n:
+            raise ValueError(f"add_views takes one chunk per listed scene, ({n}, k, 3, H, W); got {tuple(img.shape)}")
+        k = img.shape[1]
+        if not 1 <= k <= ops.GROUP_VIEWS_MAX:
+            raise ValueError(f"add_views: k={k} views per scene, must be 1 .. {ops.GROUP_VIEWS_MAX}")
+        if denorm_images.dim() != 5 or denorm_images.shape[:2] != img.shape[:2]:
+            raise ValueError(f"add_views: img {tuple(img.shape)} and denorm_images {tuple(denorm_images.shape)} must hold the same scenes and views")
+        if depth is not None and (depth.dim() != 4 or depth.shape[:2] != img.shape[:2]):
+            raise ValueError(f"add_views: depth must be ({n}, k, Hd, Wd), got {tuple(depth.shape)}")
+        metas = list(metas)
+        if len(metas) != n:
+            raise ValueError(f"add_views: {len(metas)} chunk metas for {n} listed scenes")
+        for s, m in zip(scenes, metas):
+            check_chunk_meta(self.metas[s], m, k)
+        if self.det.training:
+            raise RuntimeError("SceneGroup is inference only: call det.eval() first")
+        return scenes, k
+
+    def _features(self, img: Tensor):
+        x, _, stride = self.det.extract_2d(img)
+        return x, getattr(x, "_ndet_feature_2d", None), stride
+
+    def add_views(self, img: Tensor, denorm_images: Tensor, metas, scenes=None, depth: Optional[Tensor] = None) -> None:
+        """Fold k views into each listed scene.  ``img``, ``denorm_images`` (len(scenes), k, 3, H, W), one row per listed scene; ``metas`` one
+        chunk meta per row (its ``extrinsic`` list has k entries; the rest must equal its scene's, else ValueError); ``depth`` None or
+        (len(scenes), k, Hd, Wd) float32 / float64: it gates every scene of the call or none (nerfdet.py:404-411).
+
+        One pass for the whole call: the guard word is cleared, the backbone runs on all the chunks, the word is read back once (one
+        synchronisation per call, not per scene), and one grouped accumulate folds every scene's rows into its own state.  A tripped call's
+        backbone is redone on bf16x3 before any state is touched (``conv3d.guard_trips`` counts it once).  A call that is refused leaves
+        every state as it was -- also one the backbone refuses: the ``len(scenes) * k`` views share its launches, whose operands address
+        at most 2 GB each (200 views of 240 x 320 are too many)."""
+        scenes, k = self._check_call(img, denorm_images, metas, scenes, depth)
+        n = len(scenes)
+        metas = list(metas)
+        with torch.no_grad():
+            guarded = conv3d.ARITHMETIC == "f16x2" and img.is_cuda
+            if guarded:
+                conv3d.guard_begin(img.device)
+            x, f2d, stride = self._features(img)
+            if guarded and conv3d.guard_tripped(img.device):
+                conv3d.guard_trips += 1
+                prev = conv3d.set_arithmetic("bf16x3")
+                try:
+                    x, f2d, stride = self._features(img)
+                finally:
+                    conv3d.set_arithmetic(prev)
+            first = self.metas[0]
+            hh, ww = first["img_shape"][0], first["img_shape"][1]
+            h, w = hh // stride, ww // stride
+            feat = ops.to_channels_last(x)[:, :, :h, :w]
+            lin = self._lin
+            if f2d is not None:
+                mapped = f2d[:, :, :h, :w]
+            elif lin.in_features % 32 == 0:
+                mapped = map_features_2d_hip(feat, lin)
+            else:
+                mapped = map_features_2d(feat, lin.weight, lin.bias)
+            rgb = denorm_images.reshape([-1] + list(denorm_images.shape)[2:])[:, :, :hh, :ww]
+            gate = None
+            if depth is not None:
+                d = depth.reshape([-1] + list(depth.shape)[2:]).to(self.device, non_blocking=True)
+                gate = ops.depth_gate(d, self.det.voxel_size, (h, w), (hh, ww))
+            proj = ops.compute_projection_group(metas, (stride, 1), self.device)     # the n k projections at both strides: one upload
+            ops.scene_accumulate_group(self.group, scenes, feat, mapped, lin.bias, rgb, proj[0], proj[1], depth_gate=gate)
+
+    def _need_views(self, scenes) -> List[int]:
+        scenes = ops.listed_scenes(self.n_scenes, scenes)
+        empty = [s for s in scenes if self.group.states[s].n_views == 0]
+        if empty:
+            raise ValueError(f"scenes {empty} have no views yet: call add_views first")
+        return scenes
+
+    def _volumes(self, scenes: List[int]):
+        """``(volume (n,C,X,Y,Z), valid (n,1,X,Y,Z) int64)`` of the listed scenes: grouped K2-finish -> one sigma-MLP call over all their
+        rows -> grouped K1-finish (channels-last memory)."""
+        pts = torch.cat([self.group.points[s].reshape(3, -1) for s in scenes], dim=1) if len(scenes) > 1 else self.group.points[scenes[0]]
+        glob = ops.density_finish_group(self.group, self._lin.bias, scenes)
+        mlp = self.det.nerf_mlp
+        if hasattr(mlp, "hip_trunk_ok") and mlp.hip_trunk_ok():
+            alpha = mlp.alpha_from_points(pts, glob)
+        else:
+            alpha = ops.sigma_to_alpha(mlp.raw_sigma_from_rows(ops.posenc_concat(pts, glob)))
+        return ops.volume_finish_group(self.group, alpha, scenes)
+
+    def volume(self, scenes=None):
+        """Per listed scene ``(volume (C,X,Y,Z), valid (1,X,Y,Z) int64)`` of its views so far, as :meth:`SceneStream.volume` returns them."""
+        scenes = self._need_views(scenes)
+        with torch.no_grad():
+            vol, valid = self._volumes(scenes)
+        return [(vol[i], valid[i]) for i in range(len(scenes))]
+
+    def detect(self, scenes=None):
+        """Detections of the listed scenes over their views so far: a list with, per scene, what ``SceneStream.detect()[0]`` returns
+        (``dict(boxes_3d, scores_3d, labels_3d)``).  No state is changed.  neck_3d runs once on the scenes' volumes as one batch; every scene's
+        tail is queued before the first result is collected, so the host waits once for the queue, not once per scene.  neck_3d and the
+        tails are still launches per scene (neck_3d walks its batch scene by scene), so the fp16-pair scales of the 3D part are each
+        scene's own.  The listed scenes share the stream's range-guard word: when it comes back set with any scene's picks, the whole
+        call is repeated on bf16x3 from the finished volumes (``conv3d.guard_trips`` counts it once), so no f16x2 result of a tripped
+        launch gets out."""
+        scenes = self._need_views(scenes)
+        n = len(scenes)
+        det = self.det
+        with torch.no_grad():
+            vol, valid = self._volumes(scenes)
+            dev = vol.device
+            guarded = conv3d.ARITHMETIC == "f16x2" and vol.is_cuda
+            if guarded:
+                conv3d.guard_begin(dev)
+            x = det.neck_3d(vol)
+            metas = [[dict(self.metas[s])] for s in scenes]
+            pending, word_rides = [], True
+            for i in range(n):
+                xi = x if n == 1 else [lvl[i:i + 1] for lvl in x]
+                word_rides = word_rides and hasattr(det.bbox_head, "can_fuse") and det.bbox_head.can_fuse(xi)
+                pending.append(det._detect_tail(xi, valid[i:i + 1], metas[i], True, guarded, dev, lambda: _TRIPPED))
+            # a tail that is not the fused one does not carry the guard word with its picks: read the word once for all of them
+            tripped = guarded and not word_rides and conv3d.guard_tripped(dev)
+            results = [finish() for finish in pending]
+            if tripped or any(r is _TRIPPED for r in results):
+                results = self._repeat_tails(vol, valid, metas)
+        return [r[0] for r in results]
+
+    def _repeat_tails(self, vol: Tensor, valid: Tensor, metas):
+        """The call's neck_3d and tails once more on bf16x3, from the finished volumes, for every listed scene: the scenes of a call share
+        the stream's guard word, so a set word says that some launch of the call tripped, not which scene's."""
+        conv3d.guard_trips += 1
+        prev = conv3d.set_arithmetic("bf16x3")
+        try:
+            n = vol.shape[0]
+            x = self.det.neck_3d(vol)
+            return [self.det._detect_tail(x if n == 1 else [lvl[i:i + 1] for lvl in x], valid[i:i + 1], metas[i], False, False, vol.device, None)
+                    for i in range(n)]
         finally:
             conv3d.set_arithmetic(prev)

@@ -14,6 +14,11 @@ the scene's 50 views and 8192 x 64 sample points, for the bank held as 1, 10 and
 the generic sampler over a concatenated copy; scene.render of one target view next to rays.render_rays(render_testing=True) over the same
 maps; and the bank's bytes per view.  The calls of a comparison alternate inside one loop.
     python tools/time_streaming.py --render [--reps 20 --warmup 3]
+With --group 1,4,8,16 it times scene groups (det.begin_scenes): for every S, group.add_views of S x 1 and S x 5 views against S separate
+SceneStream.add_views calls of the same chunks, and group.detect() against S separate detect() calls (one after the other, and all queued
+with defer=True before the first is collected) with every scene holding the workload's 50 views -- the compared calls alternating inside
+one loop -- plus the group's state size and the peak allocation of building a group, adding 5 views per scene and detecting once.
+    python tools/time_streaming.py --group 1,4,8,16 [--reps 20 --warmup 3]
 """
 import argparse
 import importlib.util
@@ -103,6 +108,70 @@ def window_mode(bench, det, img, dn, meta, sizes, reps, warmup, dev):
             res[f"window_S{S}_{k}_gbs"] = b / (med[k.replace("_full", "") + "_ms"] * 1e-3) / 1e9
         res[f"window_S{S}_state_mb"] = S * sum(t.numel() * t.element_size() for t in (
             win._segs[0].k1_sum, win._segs[0].k1_count, win._segs[0].k2_sum, win._segs[0].k2_count)) / 2 ** 20
+    return res
+
+
+def group_mode(det, img, dn, meta, sizes, reps, warmup, dev):
+    import numpy as np
+    res = {}
+    n_v = img.shape[1]
+    for S in sizes:
+        # S scenes on the workload's rig: scene i has its own origin (its own points) and starts its chunks at another view
+        metas = []
+        for i in range(S):
+            m = dict(meta)
+            m["lidar2img"] = dict(meta["lidar2img"], origin=np.asarray(meta["lidar2img"]["origin"], dtype=np.float32) + np.float32([0.05 * i, -0.03 * i, 0.0]))
+            metas.append(m)
+        group = det.begin_scenes([dict(m) for m in metas])
+        streams = [det.begin_scene(dict(m)) for m in metas]
+        for k in (1, 5):
+            starts = [(i * k) % (n_v - k + 1) for i in range(S)]
+            gimg = torch.cat([img[:, v:v + k] for v in starts]).contiguous()
+            gdn = torch.cat([dn[:, v:v + k] for v in starts]).contiguous()
+            cmetas = [chunk_meta(m, v, v + k) for m, v in zip(metas, starts)]
+
+            def separate():
+                for i, st in enumerate(streams):
+                    st.add_views(gimg[i:i + 1], gdn[i:i + 1], cmetas[i])
+
+            fns = {f"group_add_views_{S}x{k}_ms": lambda: group.add_views(gimg, gdn, cmetas), f"separate_add_views_{S}x{k}_ms": separate}
+            med, span = timed_alternating(fns, reps, warmup)
+            for name in fns:
+                res[name], res[name + "_min_max"] = med[name], span[name]
+            res[f"add_views_{S}x{k}_separate_over_group"] = med[f"separate_add_views_{S}x{k}_ms"] / med[f"group_add_views_{S}x{k}_ms"]
+        group.reset()
+        for st in streams:
+            st.reset()
+        for v0 in range(0, n_v, 5):     # every scene takes the workload's views, 5 per call: S x 5 views share a backbone pass
+            group.add_views(img[:, v0:v0 + 5].expand(S, -1, -1, -1, -1).contiguous(), dn[:, v0:v0 + 5].expand(S, -1, -1, -1, -1).contiguous(),
+                            [chunk_meta(m, v0, v0 + 5) for m in metas])
+            for st, m in zip(streams, metas):
+                st.add_views(img[:, v0:v0 + 5], dn[:, v0:v0 + 5], chunk_meta(m, v0, v0 + 5))
+        assert group.n_views == [n_v] * S
+
+        def deferred():
+            pending = [st.detect(defer=True) for st in streams]
+            return [f() for f in pending]
+
+        fns = {f"group_detect_S{S}_ms": group.detect, f"separate_detect_S{S}_ms": lambda: [st.detect() for st in streams],
+               f"separate_deferred_detect_S{S}_ms": deferred}
+        med, span = timed_alternating(fns, reps, warmup)
+        for name in fns:
+            res[name], res[name + "_min_max"] = med[name], span[name]
+        res[f"detect_S{S}_separate_over_group"] = med[f"separate_detect_S{S}_ms"] / med[f"group_detect_S{S}_ms"]
+        res[f"detect_S{S}_deferred_over_group"] = med[f"separate_deferred_detect_S{S}_ms"] / med[f"group_detect_S{S}_ms"]
+        res[f"group_S{S}_state_mb"] = sum(t.numel() * t.element_size() for st in group.group.states
+                                          for t in (st.k1_sum, st.k1_count, st.k2_sum, st.k2_count)) / 2 ** 20
+        del group, streams
+        gimg, gdn = torch.cat([img[:, :5]] * S).contiguous(), torch.cat([dn[:, :5]] * S).contiguous()
+
+        def once():
+            g = det.begin_scenes([dict(m) for m in metas])
+            g.add_views(gimg, gdn, [chunk_meta(m, 0, 5) for m in metas])
+            return g.detect()
+
+        res[f"group_S{S}_peak_mb"] = peak_mb(once)
+        del gimg, gdn
     return res
 
 
@@ -211,6 +280,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--window", type=str, default=None, help="comma-separated window sizes in chunks of 5 views, e.g. 1,4,8")
     ap.add_argument("--render", action="store_true", help="time rendering from a streamed scene (the view-bank sampler)")
+    ap.add_argument("--group", type=str, default=None, help="comma-separated scene-group sizes, e.g. 1,4,8,16")
     args = ap.parse_args()
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
@@ -226,6 +296,13 @@ def main():
     if args.render:
         with torch.no_grad():
             res = render_mode(det, img, dn, meta, rb, args.reps, args.warmup, dev)
+        for k, v in res.items():
+            print(f"{k:>44}: " + (f"{v:.3f}" if isinstance(v, float) else str(v)))
+        print(json.dumps(res))
+        return
+    if args.group:
+        with torch.no_grad():
+            res = group_mode(det, img, dn, meta, [int(v) for v in args.group.split(",")], args.reps, args.warmup, dev)
         for k, v in res.items():
             print(f"{k:>44}: " + (f"{v:.3f}" if isinstance(v, float) else str(v)))
         print(json.dumps(res))
