@@ -299,6 +299,50 @@ int ndet_scene_density_finish_group(const NdetSceneGroup* g, const NdetGroupSel*
 int ndet_scene_volume_finish_group(const NdetSceneGroup* g, const NdetGroupSel* sel, const float* alpha, float* out, int64_t* count,
                                    void* stream);
 
+/* Windowed groups: every scene of a group keeps a sliding window of chunks, one state per chunk (nerf-det_amd/streaming.py,
+ * SceneGroup(window=S)), and the listed scenes' windows are finished by one launch, grid.y = listed scene, each scene over its own
+ * number of segments.  The accumulate side is ndet_scene_accumulate_group, unchanged: a call's chunks go into empty states listed by a
+ * per-call table of n rows.
+ *
+ * The states of all the scenes form a pool: one NdetSceneSlot row per state in a DEVICE table (a row carries its scene's points), described
+ * by an NdetSceneGroup block with n_slots in 1 .. NDET_GROUP_POOL_MAX (up to NDET_RING_MAX + 1 states for each of NDET_GROUP_MAX scenes: a
+ * sliding window of S chunks owns S + 1 states).  The block's other fields are checked as ndet_scene_group_check checks them; the four
+ * entry points above keep refusing n_slots > NDET_GROUP_MAX.
+ * NdetGroupRingSel: the scenes one ring finish serves, a HOST block (size = sizeof(NdetGroupRingSel)) that rides by value in the kernel
+ * arguments:
+ *   n          listed scenes, 1 .. NDET_GROUP_MAX; grid.y of the launch.
+ *   n_segs[i]  segments of listed scene i, 1 .. NDET_RING_MAX.
+ *   n_views[i] the scene's view total over its segments (>= 0; the divisor-side n_views of nerfdet.py:234-253).
+ * The segment lists: (n, NDET_RING_MAX) int32 pool rows, row i listed scene i's segments oldest first; entries beyond n_segs[i] are never
+ * read.  Up to 16 KiB, too large for the kernel arguments, so the list is passed twice: segs_host (HOST memory, read by the checks only) and
+ * segs_dev (DEVICE memory holding the same values, read by the kernel; the caller uploads it on the call's stream).  No pool row may be
+ * listed twice in one call.  The entry points copy nothing and do not wait for the device.
+ * Per voxel a scene's segments are added in list order starting from the oldest segment's values, as ndet_scene_*_finish_ring add them:
+ * listed scene i's outputs are bit for bit those functions' outputs over its segments' states (so one segment gives the single-state
+ * finish's).  The states are only read. */
+#define NDET_GROUP_POOL_MAX (NDET_GROUP_MAX * (NDET_RING_MAX + 1))
+typedef struct NdetGroupRingSel {
+    int32_t size;
+    int32_t n;
+    int32_t n_segs[NDET_GROUP_MAX];
+    int32_t n_views[NDET_GROUP_MAX];
+} NdetGroupRingSel;
+
+/* The host-side checks both grouped ring finishes make before they launch anything, on their own (nerfdet.py:164-176, 234-253 are what
+ * the blocks feed): the pool block, the selection, every listed pool row inside the table and listed once.  NDET_OK, NDET_E_INVALID or NDET_E_UNSUPPORTED (message set); nothing is launched
+ * and no device memory is read. */
+int ndet_scene_group_ring_check(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_host);
+
+/* ndet_scene_density_finish_ring for the listed scenes in one launch (nerfdet.py:234-253): global_feat (n N, 2 (3 + cm)), listed scene
+ * i's voxel v in row i N + v, finished over sel->n_views[i] views. */
+int ndet_scene_density_finish_group_ring(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_host,
+                                         const int32_t* segs_dev, const float* bias, float* global_feat, void* stream);
+
+/* ndet_scene_volume_finish_ring for the listed scenes in one launch (nerfdet.py:175-176, 259-261): out (n, N, C) channels-last, count
+ * (n, N) int64, alpha NULL or (n N) indexed as global_feat's rows. */
+int ndet_scene_volume_finish_group_ring(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_host,
+                                        const int32_t* segs_dev, const float* alpha, float* out, int64_t* count, void* stream);
+
 /* A6 (gating only, unfused form). volume = (1-exp(-density)) * mean, 0 where count==0; nerfdet.py:257-261.
  * mean/out in `layout` with C channels. */
 int ndet_alpha_gate(const float* mean, const float* density, const int64_t* count, float* out,

@@ -59,7 +59,17 @@ class NdetGroupSel(ctypes.Structure):    # the scenes one grouped call serves: i
                 ("n_views", ctypes.c_int32 * NDET_GROUP_MAX)]
 
 
+NDET_RING_MAX = 64
+NDET_GROUP_POOL_MAX = NDET_GROUP_MAX * (NDET_RING_MAX + 1)   # states a windowed group's pool table may hold
+
+
+class NdetGroupRingSel(ctypes.Structure):  # the scenes one grouped ring finish serves: include/nerfdet_hip.h::NdetGroupRingSel, 520 bytes
+    _fields_ = [("size", ctypes.c_int32), ("n", ctypes.c_int32), ("n_segs", ctypes.c_int32 * NDET_GROUP_MAX),
+                ("n_views", ctypes.c_int32 * NDET_GROUP_MAX)]
+
+
 _G = ctypes.POINTER(NdetDepthGate)
+_GR = ctypes.POINTER(NdetGroupRingSel)
 _S = ctypes.POINTER(NdetSceneAccum)
 _SG = ctypes.POINTER(NdetSceneGroup)
 _GS = ctypes.POINTER(NdetGroupSel)
@@ -97,6 +107,9 @@ SIGNATURES = {
                                      c_int64, _P, _P, _G, _P], c_int),
     "ndet_scene_density_finish_group": ([_SG, _GS, _P, _P, _P], c_int),
     "ndet_scene_volume_finish_group": ([_SG, _GS, _P, _P, _P, _P], c_int),
+    "ndet_scene_group_ring_check": ([_SG, _GR, _P], c_int),
+    "ndet_scene_density_finish_group_ring": ([_SG, _GR, _P, _P, _P, _P, _P], c_int),
+    "ndet_scene_volume_finish_group_ring": ([_SG, _GR, _P, _P, _P, _P, _P, _P], c_int),
     "ndet_alpha_gate": ([_P, _P, _P, _P, c_int, c_int, c_int, _P], c_int),
     "ndet_sigma_to_alpha": ([_P, _P, c_int, _P], c_int),
     "ndet_posenc_concat": ([_P, _P, c_int, c_int, c_int, _P, _P], c_int),

@@ -562,6 +562,109 @@ __global__ __launch_bounds__(256) void k_density_finish_group(const NdetSceneSlo
     *reinterpret_cast<float2*>(out + ((int64_t)y * N + n) * 2 * nc + 2 * c) = make_float2(mean, expf(-var));
 }
 
+// k_density_finish_ring (its own copy, expression for expression) for the listed scenes of a windowed group (include/nerfdet_hip.h,
+// ndet_scene_density_finish_group_ring), grid.y = listed scene: the scene's segments are rows segs[y][0 .. n_segs - 1] of the pool table.
+// Threads 0 .. n_segs - 1 resolve them into LDS once (block-uniform pointers, 64 x 16 bytes), one barrier, then the ring walk with the
+// pool's pitch; threads past N nq stay for the barrier and skip the body.  Output row y N + n, finished over the scene's own view total.
+__global__ __launch_bounds__(256) void k_density_finish_group_ring(const NdetSceneSlot* __restrict__ table, NdetGroupRingSel sel,
+                                                                   const int32_t* __restrict__ segs, int pitch,
+                                                                   const float* __restrict__ bias, int cm, int N, float* __restrict__ out) {
+    constexpr int U = NDET_RING_BATCH;
+    __shared__ const float* s_sum[NDET_RING_MAX];
+    __shared__ const int* s_count[NDET_RING_MAX];
+    const int y = blockIdx.y;
+    const int n_segs = sel.n_segs[y];
+    const int n_views = sel.n_views[y];
+    if ((int)threadIdx.x < n_segs) {
+        const NdetSceneSlot& sl = table[segs[y * NDET_RING_MAX + threadIdx.x]];
+        s_sum[threadIdx.x] = sl.k2_sum;
+        s_count[threadIdx.x] = sl.k2_count;
+    }
+    __syncthreads();
+    const int nq = (cm >> 2) + 1;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (int64_t)N * nq) {
+        const int n = (int)(i / nq), qd = (int)(i % nq);
+        const bool is_rgb = qd == 0;
+        const int seg = cm + 4;
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+        auto counts = [&](int sj, int& c_f, int& c_mine) {
+            const int2 c = *reinterpret_cast<const int2*>(s_count[sj] + 2 * n);
+            c_f = c.x;
+            c_mine = is_rgb ? c.y : c.x;
+        };
+        int cnt, n_mine;
+        counts(0, cnt, n_mine);
+        float4 a = zero, qq = zero, ss = zero;
+        if (n_mine != 0) {
+            const float* row = s_sum[0] + (int64_t)n * pitch + 4 * qd;
+            a = *reinterpret_cast<const float4*>(row);
+            qq = *reinterpret_cast<const float4*>(row + seg);
+            ss = *reinterpret_cast<const float4*>(row + 2 * seg);
+        }
+        for (int s0 = 1; s0 < n_segs; s0 += U) {
+            int cc[U], mm[U];
+            float4 va[U], vq[U], vs[U];
+#pragma unroll
+            for (int j = 0; j < U; ++j) {      // unconditional loads (past the end: the last segment's counts again, dropped), so all U are in flight
+                const bool in = s0 + j < n_segs;
+                counts(min(s0 + j, n_segs - 1), cc[j], mm[j]);
+                cc[j] = in ? cc[j] : 0;
+                mm[j] = in ? mm[j] : 0;
+            }
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                va[j] = zero; vq[j] = zero; vs[j] = zero;
+                if (mm[j] != 0) {      // implies s0 + j < n_segs
+                    const float* row = s_sum[s0 + j] + (int64_t)n * pitch + 4 * qd;
+                    va[j] = *reinterpret_cast<const float4*>(row);
+                    vq[j] = *reinterpret_cast<const float4*>(row + seg);
+                    vs[j] = *reinterpret_cast<const float4*>(row + 2 * seg);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                a = ndet_add4(a, va[j]);
+                qq = ndet_add4(qq, vq[j]);
+                ss = ndet_add4(ss, vs[j]);
+                cnt += cc[j];
+                n_mine += mm[j];
+            }
+        }
+        const float denom = (float)cnt + 1e-8f;
+        const float nu = (float)(n_views - n_mine), nv = (float)n_views;
+        auto finish = [&](float a1, float q1, float s1, float fl) -> float2 {
+            const float sm = a1 + nu * fl;
+            const float mean = sm / denom;                        // NOT zeroed at cnt == 0 (nerfdet.py:241)
+            const float dm = mean - fl;
+            float s = q1 - 2.0f * dm * s1 + nv * (dm * dm);
+            s = fmaxf(s, 0.0f);                                   // a sum of squares: rounding may leave -1 ulp
+            float var = s / denom;
+            if (cnt == 0) var = 1e6f;                             // nerfdet.py:249
+            return make_float2(mean, expf(-var));
+        };
+        float2* o = reinterpret_cast<float2*>(out + ((int64_t)y * N + n) * 2 * (3 + cm));
+        if (is_rgb) {
+            o[0] = finish(a.x, qq.x, ss.x, 0.0f);
+            o[1] = finish(a.y, qq.y, ss.y, 0.0f);
+            o[2] = finish(a.z, qq.z, ss.z, 0.0f);
+        } else {
+            const int c = 4 * (qd - 1);                           // first mapped channel of the quad
+            o[3 + c] = finish(a.x, qq.x, ss.x, bias[c]);
+            o[4 + c] = finish(a.y, qq.y, ss.y, bias[c + 1]);
+            o[5 + c] = finish(a.z, qq.z, ss.z, bias[c + 2]);
+            o[6 + c] = finish(a.w, qq.w, ss.w, bias[c + 3]);
+        }
+    }
+}
+
+void ndet_scene_k2_finish_group_ring_launch(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_dev, const float* bias,
+                                            float* global_feat, hipStream_t stream) {
+    const int64_t total = (int64_t)pool->N * (pool->cm / 4 + 1);
+    hipLaunchKernelGGL(k_density_finish_group_ring, dim3((unsigned)((total + 255) / 256), sel->n), dim3(256), 0, stream, pool->table, *sel,
+                       segs_dev, (int)pool->k2_pitch, bias, pool->cm, pool->N, global_feat);
+}
+
 void ndet_scene_k2_accumulate_group_launch(const NdetSceneGroup* g, const NdetGroupSel* sel, int k, const float* mapped, int h, int w,
                                            int mview_pitch, int mrow_pitch, const float* bias, const float* rgb, int H, int W, int rsv, int rsc,
                                            int rsy, const float* proj, const float* rgb_proj, bool gated, const NdetGateMap& gf,

@@ -148,6 +148,11 @@ void ndet_scene_k2_accumulate_group_launch(const NdetSceneGroup* g, const NdetGr
 void ndet_scene_k2_finish_group_launch(const NdetSceneGroup* g, const NdetGroupSel* sel, const float* bias, float* global_feat,
                                        hipStream_t stream);
 
+// Windowed groups (include/nerfdet_hip.h, ndet_scene_*_finish_group_ring): launcher of K2's grouped ring finish (density_kernels.hip);
+// segs_dev is the DEVICE copy of the (n, NDET_RING_MAX) segment lists, the host copy having been checked by the entry point.
+void ndet_scene_k2_finish_group_ring_launch(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_dev, const float* bias,
+                                            float* global_feat, hipStream_t stream);
+
 // Gradient scatter of the backward kernels.  Default: float atomics (global_atomic_add_f32) -- fast, but the ORDER of the adds, and with it the last
 // bits of every sum, changes from run to run.  Deterministic mode (tests: ndet_measurement_knob("deterministic_scatter", 1); the caller then hands
 // a zeroed buffer of int64 in place of the float buffer): every contribution is rounded to a multiple of 2^-40 and added as a 64-bit INTEGER --

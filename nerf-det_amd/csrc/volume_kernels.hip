@@ -1132,6 +1132,161 @@ extern "C" int ndet_scene_volume_finish_group(const NdetSceneGroup* g, const Nde
 }
 
 // ------------------------------------------------------------------------------------------
+// Windowed groups (include/nerfdet_hip.h, NdetGroupRingSel): the listed scenes' windows finished by one launch, grid.y = listed scene.
+//
+// k_volume_finish_group_ring is k_volume_finish_ring (its own copy, expression for expression) with the segments found through memory:
+// segs[y][j] is a row of the pool table, the row holds the state's pointers.  That chain is block-uniform, so threads 0 .. n_segs - 1
+// resolve it once into LDS (64 x 16 bytes) and the walk reads its pointers from there after one barrier; the threads past N c4 stay for
+// the barrier and skip the body.  The state pitch is the pool's.  Output row y N + n, alpha indexed the same way.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_volume_finish_group_ring(const NdetSceneSlot* __restrict__ table, NdetGroupRingSel sel,
+                                                                  const int32_t* __restrict__ segs, int pitch,
+                                                                  const float* __restrict__ alpha, int C, int N, float* __restrict__ out,
+                                                                  int64_t* __restrict__ out_count) {
+    constexpr int U = NDET_RING_BATCH;
+    __shared__ const float* s_sum[NDET_RING_MAX];
+    __shared__ const int* s_count[NDET_RING_MAX];
+    const int y = blockIdx.y;
+    const int n_segs = sel.n_segs[y];
+    if ((int)threadIdx.x < n_segs) {
+        const NdetSceneSlot& sl = table[segs[y * NDET_RING_MAX + threadIdx.x]];
+        s_sum[threadIdx.x] = sl.k1_sum;
+        s_count[threadIdx.x] = sl.k1_count;
+    }
+    __syncthreads();
+    const int c4 = C >> 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (int64_t)N * c4) {
+        const int n = (int)(i / c4), q = (int)(i % c4);
+        const int64_t row = (int64_t)y * N + n;
+        int cnt = s_count[0][n];
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (cnt != 0) s = *reinterpret_cast<const float4*>(s_sum[0] + (int64_t)n * pitch + q * 4);
+        for (int s0 = 1; s0 < n_segs; s0 += U) {
+            int cc[U];
+            float4 vv[U];
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                const int sj = min(s0 + j, n_segs - 1);     // past the end: the last segment's slot, not read (cc = 0)
+                cc[j] = (s0 + j < n_segs) ? s_count[sj][n] : 0;
+            }
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                const int sj = min(s0 + j, n_segs - 1);
+                vv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (cc[j] != 0) vv[j] = *reinterpret_cast<const float4*>(s_sum[sj] + (int64_t)n * pitch + q * 4);
+            }
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                s.x = s.x + vv[j].x;
+                s.y = s.y + vv[j].y;
+                s.z = s.z + vv[j].z;
+                s.w = s.w + vv[j].w;
+                cnt += cc[j];
+            }
+        }
+        const float denom = (float)cnt + 1e-8f;
+        float4 mean;
+        mean.x = s.x / denom;
+        mean.y = s.y / denom;
+        mean.z = s.z / denom;
+        mean.w = s.w / denom;
+        if (alpha) {
+            const float a = alpha[row];
+            mean.x = a * mean.x;
+            mean.y = a * mean.y;
+            mean.z = a * mean.z;
+            mean.w = a * mean.w;
+        }
+        if (cnt == 0) mean = make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(out + row * C + q * 4) = mean;
+        if (q == 0) out_count[row] = (int64_t)cnt;
+    }
+}
+
+// The pool's block, checked as group_check checks a group's apart from the bound on n_slots (a pool holds up to NDET_RING_MAX + 1 states
+// per scene).
+static int pool_check(const NdetSceneGroup* g, const char* fn) {
+    NDET_REQUIRE(g, NDET_E_INVALID, "%s: null state pool", fn);
+    NDET_REQUIRE(g->size == (int32_t)sizeof(NdetSceneGroup), NDET_E_INVALID, "%s: NdetSceneGroup.size %d != %d (caller built against another layout)",
+                 fn, g->size, (int)sizeof(NdetSceneGroup));
+    NDET_REQUIRE(g->table, NDET_E_INVALID, "%s: null pool table", fn);
+    NDET_REQUIRE(((uintptr_t)g->table & 15) == 0, NDET_E_UNSUPPORTED, "%s: the pool table must be 16-byte aligned", fn);
+    NDET_REQUIRE(g->n_slots >= 1 && g->n_slots <= NDET_GROUP_POOL_MAX, NDET_E_INVALID, "%s: n_slots=%d must be 1 .. %d", fn, g->n_slots,
+                 NDET_GROUP_POOL_MAX);
+    NDET_REQUIRE(g->N > 0 && g->C > 0 && g->cm > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
+    NDET_REQUIRE(g->C % 4 == 0 && g->C <= 1024, NDET_E_UNSUPPORTED, "%s: C=%d must be a multiple of 4 and <= 1024", fn, g->C);
+    NDET_REQUIRE(g->cm % 4 == 0 && g->cm <= 128, NDET_E_UNSUPPORTED, "%s: cm=%d must be a multiple of 4 and <= 128", fn, g->cm);
+    NDET_REQUIRE(g->k1_pitch >= g->C && g->k2_pitch >= 3 * (g->cm + 4), NDET_E_INVALID, "%s: state pitches smaller than a row", fn);
+    NDET_REQUIRE(g->k1_pitch < ((int64_t)1 << 31) && g->k2_pitch < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: state pitches exceed int32", fn);
+    NDET_REQUIRE(g->k1_pitch % 4 == 0 && g->k2_pitch % 4 == 0, NDET_E_UNSUPPORTED, "%s: state rows must be 16-byte aligned", fn);
+    return NDET_OK;
+}
+
+// The pool, a call's selection and its segment lists (the HOST copy), checked before any launch.
+static int group_ring_check(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_host, const char* fn) {
+    const int rc = pool_check(pool, fn);
+    if (rc != NDET_OK) return rc;
+    NDET_REQUIRE(sel, NDET_E_INVALID, "%s: null selection", fn);
+    NDET_REQUIRE(sel->size == (int32_t)sizeof(NdetGroupRingSel), NDET_E_INVALID,
+                 "%s: NdetGroupRingSel.size %d != %d (caller built against another layout)", fn, sel->size, (int)sizeof(NdetGroupRingSel));
+    NDET_REQUIRE(sel->n >= 1 && sel->n <= NDET_GROUP_MAX, NDET_E_INVALID, "%s: %d listed scenes, must be 1 .. %d", fn, sel->n, NDET_GROUP_MAX);
+    NDET_REQUIRE(segs_host, NDET_E_INVALID, "%s: null segs_host", fn);
+    uint64_t used[(NDET_GROUP_POOL_MAX + 63) / 64] = {};
+    for (int i = 0; i < sel->n; ++i) {
+        NDET_REQUIRE(sel->n_segs[i] >= 1 && sel->n_segs[i] <= NDET_RING_MAX, NDET_E_INVALID, "%s: n_segs[%d]=%d must be 1 .. %d", fn, i,
+                     sel->n_segs[i], NDET_RING_MAX);
+        NDET_REQUIRE(sel->n_views[i] >= 0, NDET_E_INVALID, "%s: n_views[%d]=%d", fn, i, sel->n_views[i]);
+        for (int j = 0; j < sel->n_segs[i]; ++j) {
+            const int s = segs_host[i * NDET_RING_MAX + j];
+            NDET_REQUIRE(s >= 0 && s < pool->n_slots, NDET_E_INVALID, "%s: segs[%d][%d]=%d outside the pool's %d rows", fn, i, j, s, pool->n_slots);
+            NDET_REQUIRE(!((used[s >> 6] >> (s & 63)) & 1ull), NDET_E_INVALID, "%s: segs[%d][%d]=%d is listed twice", fn, i, j, s);
+            used[s >> 6] |= 1ull << (s & 63);
+        }
+    }
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_group_ring_check(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_host) {
+    return group_ring_check(pool, sel, segs_host, "ndet_scene_group_ring_check");
+}
+
+extern "C" int ndet_scene_density_finish_group_ring(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_host,
+                                                    const int32_t* segs_dev, const float* bias, float* global_feat, void* stream) {
+    const char* fn = "ndet_scene_density_finish_group_ring";
+    const int rc = group_ring_check(pool, sel, segs_host, fn);
+    if (rc != NDET_OK) return rc;
+    NDET_REQUIRE(segs_dev, NDET_E_INVALID, "%s: null segs_dev", fn);
+    NDET_REQUIRE(((uintptr_t)segs_dev & 3) == 0, NDET_E_UNSUPPORTED, "%s: segs_dev must be 4-byte aligned", fn);
+    NDET_REQUIRE(bias, NDET_E_INVALID, "%s: null bias", fn);
+    NDET_REQUIRE(global_feat, NDET_E_INVALID, "%s: null global_feat", fn);
+    NDET_REQUIRE(((uintptr_t)global_feat & 7) == 0, NDET_E_UNSUPPORTED, "%s: global_feat must be 8-byte aligned", fn);
+    NDET_REQUIRE(((int64_t)pool->N * (pool->cm / 4 + 1) + 255) / 256 < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
+    ndet_scene_k2_finish_group_ring_launch(pool, sel, segs_dev, bias, global_feat, (hipStream_t)stream);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_volume_finish_group_ring(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_host,
+                                                   const int32_t* segs_dev, const float* alpha, float* out, int64_t* count, void* stream) {
+    const char* fn = "ndet_scene_volume_finish_group_ring";
+    const int rc = group_ring_check(pool, sel, segs_host, fn);
+    if (rc != NDET_OK) return rc;
+    NDET_REQUIRE(segs_dev, NDET_E_INVALID, "%s: null segs_dev", fn);
+    NDET_REQUIRE(((uintptr_t)segs_dev & 3) == 0, NDET_E_UNSUPPORTED, "%s: segs_dev must be 4-byte aligned", fn);
+    NDET_REQUIRE(out, NDET_E_INVALID, "%s: null out", fn);
+    NDET_REQUIRE(count, NDET_E_INVALID, "%s: null count", fn);
+    NDET_REQUIRE(((uintptr_t)out & 15) == 0, NDET_E_UNSUPPORTED, "%s: out must be 16-byte aligned", fn);
+    NDET_REQUIRE(((uintptr_t)count & 7) == 0, NDET_E_UNSUPPORTED, "%s: count must be 8-byte aligned", fn);
+    const int64_t blocks = ((int64_t)pool->N * (pool->C / 4) + 255) / 256;
+    NDET_REQUIRE(blocks < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
+    hipLaunchKernelGGL(k_volume_finish_group_ring, dim3((unsigned)blocks, sel->n), dim3(256), 0, (hipStream_t)stream, pool->table, *sel, segs_dev,
+                       (int)pool->k1_pitch, alpha, pool->C, pool->N, out, count);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // K2  density conditioning features   A5
 //
 // One wavefront per voxel, lanes over the 3 + cm channels (35 of 64 lanes at cm = 32): lanes 0-2

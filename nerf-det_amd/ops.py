@@ -666,6 +666,290 @@ def volume_finish_group(group: SceneGroupState, alpha: Optional[Tensor] = None, 
 
 
 # --------------------------------------------------------------------------------------------
+# Windowed groups: every scene of a group keeps a sliding window of chunks, one state per chunk, all the states behind one pool table
+# (include/nerfdet_hip.h, NdetGroupRingSel)
+# --------------------------------------------------------------------------------------------
+GROUP_POOL_MAX = GROUP_MAX * (RING_MAX + 1)    # states one pool table may hold (include/nerfdet_hip.h, NDET_GROUP_POOL_MAX)
+
+
+def check_window(window) -> int:
+    """``window`` of a windowed stream or group: an int in 1 .. RING_MAX (else ValueError)."""
+    if isinstance(window, bool) or not isinstance(window, int) or not 1 <= window <= RING_MAX:
+        raise ValueError(f"window must be None or an int in 1 .. {RING_MAX}, got {window!r}")
+    return window
+
+
+class SceneGroupRingState:
+    """The windows of S scenes (1 .. 64) that share grid, C and cm: per scene the states of the chunks held, oldest first (``segs[s]``), and
+    its zeroed states waiting for chunks to come (``spare[s]``) -- at most ``window + 1`` states per scene, allocated when first needed (a
+    sliding window owns S + 1: the chunk that leaves hands its state to the chunk after the next).  Every state is a row of one pool
+    table on the device (64-byte NdetSceneSlot rows, each with its scene's points), uploaded again only when a state is first allocated;
+    the table has room for every state the pool can come to own, so its address changes with an upload but not its size.  The pool owns
+    every tensor the table points to: states are zeroed in place, never replaced.  Uploads are ordered on the stream that is current
+    when they are made: use the pool on one stream."""
+
+    def __init__(self, n_voxels, c: int, cm: int, points: Sequence[Tensor], window: int, device):
+        self.window = check_window(window)
+        points = list(points)
+        if not 1 <= len(points) <= GROUP_MAX:
+            raise ValueError(f"a scene group holds 1 to {GROUP_MAX} scenes, got {len(points)}")
+        self.grid = tuple(int(v) for v in n_voxels)
+        assert c % 4 == 0 and cm % 4 == 0, f"streaming needs C and cm in multiples of 4 (got {c}, {cm})"
+        self.c, self.cm, self.device = int(c), int(cm), torch.device(device)
+        self.points = []
+        for p in points:
+            if self.device.type == "cuda":
+                _need_gpu(p)
+            assert tuple(p.shape[-3:]) == self.grid and p.shape[0] == 3, f"points {tuple(p.shape)} for a {self.grid} state"
+            self.points.append(_f32c(p))
+        self.segs = [[] for _ in points]
+        self.spare = [[] for _ in points]
+        self.states = []            # every state of the pool; a state's pool row is its index here (``state.row``)
+        self.owner = []             # the scene of every pool row
+        self._table = None          # the device table, or None when a state has been allocated since the last upload
+        self._version = 0           # bumped whenever a window changes: the finishes' selection is built once per version and scene list
+        self._sel = None
+
+    def __len__(self) -> int:
+        return len(self.segs)
+
+    @property
+    def n_voxels(self) -> int:
+        return self.grid[0] * self.grid[1] * self.grid[2]
+
+    @property
+    def chunk_views(self):
+        """Per scene the view counts of the chunks held, oldest first."""
+        return [[st.n_views for st in segs] for segs in self.segs]
+
+    @property
+    def n_chunks(self):
+        return [len(segs) for segs in self.segs]
+
+    @property
+    def n_views(self):
+        return [sum(st.n_views for st in segs) for segs in self.segs]
+
+    def listed(self, scenes) -> list:
+        return listed_scenes(len(self.segs), scenes)
+
+    def owned(self, s: int) -> int:
+        """States scene ``s`` owns, held or spare."""
+        return len(self.segs[s]) + len(self.spare[s])
+
+    def _new_state(self, s: int) -> SceneState:
+        assert sum(1 for o in self.owner if o == s) <= self.window, f"scene {s} already owns {self.window + 1} states"
+        st = SceneState(self.grid, self.c, self.cm, self.device)
+        st.row = len(self.states)
+        self.states.append(st)
+        self.owner.append(s)
+        self._table = None
+        return st
+
+    def take(self, scenes) -> list:
+        """One empty state per listed scene, from its spares or freshly allocated; they belong to no window until :meth:`push`."""
+        return [self.spare[s].pop() if self.spare[s] else self._new_state(s) for s in scenes]
+
+    def give_back(self, scenes, states) -> None:
+        """States taken for a call that failed go back to their scenes' spares, zeroed."""
+        for s, st in zip(scenes, states):
+            st.reset()
+            self.spare[s].append(st)
+
+    def push(self, scenes, states) -> None:
+        """The filled states join their scenes' windows; the oldest chunk leaves each listed scene whose window was full."""
+        for s, st in zip(scenes, states):
+            if len(self.segs[s]) == self.window:
+                self._drop(s, 1)
+            self.segs[s].append(st)
+        self._version += 1
+
+    def _drop(self, s: int, k: int) -> None:
+        for st in self.segs[s][:k]:
+            st.reset()
+            self.spare[s].append(st)
+        del self.segs[s][:k]
+
+    def drop_oldest(self, k: int = 1, scenes=None) -> None:
+        """Forget the k oldest chunks of every listed scene; refused whole (ValueError) when a listed scene holds fewer than k."""
+        scenes = self.listed(scenes)
+        if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+            raise ValueError(f"drop_oldest: k={k!r}")
+        short = [s for s in scenes if len(self.segs[s]) < k]
+        if short:
+            raise ValueError(f"drop_oldest: k={k!r} for {[len(self.segs[s]) for s in short]} chunks held by scenes {short}")
+        for s in scenes:
+            self._drop(s, k)
+        self._version += 1
+
+    def accumulate(self, scenes, fill) -> None:
+        """One chunk per listed scene: ``fill(states)`` fills one empty state per listed scene; only when it has succeeded do the states
+        join the windows and the oldest chunks leave the full ones.  When it raises, every window stays as it was and the states go back
+        zeroed."""
+        states = self.take(scenes)
+        try:
+            fill(states)
+        except BaseException:
+            self.give_back(scenes, states)
+            raise
+        self.push(scenes, states)
+
+    def _upload(self, rows) -> Tensor:
+        host = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8)
+        return _upload_async(host, self.device) if self.device.type == "cuda" else host.clone()
+
+    def _slot(self, row, st: SceneState, p: Tensor) -> None:
+        assert (st.k1_sum.data_ptr() | st.k2_sum.data_ptr()) % 16 == 0 and st.k1_count.data_ptr() % 4 == 0 and st.k2_count.data_ptr() % 8 == 0 \
+            and p.data_ptr() % 4 == 0, "state rows must be 16-byte aligned"
+        row.k1_sum, row.k1_count, row.k2_sum, row.k2_count = st.k1_sum.data_ptr(), st.k1_count.data_ptr(), st.k2_sum.data_ptr(), st.k2_count.data_ptr()
+        row.points = p.data_ptr()
+
+    def table(self) -> Tensor:
+        """The pool table on the device, uploaded when a state has been allocated since the last call; rows beyond the states allocated
+        are null and beyond ``n_slots``."""
+        if self._table is None:
+            rows = (_lib.NdetSceneSlot * (len(self.segs) * (self.window + 1)))()
+            for st, s in zip(self.states, self.owner):
+                self._slot(rows[st.row], st, self.points[s])
+            self._table = self._upload(rows)
+        return self._table
+
+    def _block(self, n_slots: int, table: Tensor) -> "_lib.NdetSceneGroup":
+        g = _lib.NdetSceneGroup()
+        g.size = ctypes.sizeof(_lib.NdetSceneGroup)
+        g.n_slots, g.N, g.C, g.cm = n_slots, self.n_voxels, self.c, self.cm
+        g.k1_pitch, g.k2_pitch, g.table = self.c, 3 * (self.cm + 4), table.data_ptr()
+        return g
+
+    def block(self):
+        """``(NdetSceneGroup block of the pool, the table tensor it points to)``."""
+        table = self.table()
+        return self._block(len(self.states), table), table
+
+    def front(self, scenes, states):
+        """A call's front table -- one row per listed scene, pointing at the state it fills and its scene's points -- with the block and the
+        selection ndet_scene_accumulate_group takes for it: ``(block, sel, table tensor)``."""
+        rows = (_lib.NdetSceneSlot * len(scenes))()
+        sel = _lib.NdetGroupSel()
+        sel.size, sel.n = ctypes.sizeof(_lib.NdetGroupSel), len(scenes)
+        for i, (s, st) in enumerate(zip(scenes, states)):
+            assert st.n_views == 0, "a front state must be empty"
+            self._slot(rows[i], st, self.points[s])
+            sel.slot[i], sel.n_views[i] = i, 0
+        table = self._upload(rows)
+        return self._block(len(scenes), table), sel, table
+
+    def ring_sel(self, scenes):
+        """The grouped ring finishes' arguments for the (checked) scene list: ``(NdetGroupRingSel, segment lists on the host, on the
+        device)``, (n, RING_MAX) int32 pool rows, oldest first; built and uploaded once per scene list and window change."""
+        key = (tuple(scenes), self._version)
+        if self._sel is None or self._sel[0] != key:
+            sel = _lib.NdetGroupRingSel()
+            sel.size, sel.n = ctypes.sizeof(_lib.NdetGroupRingSel), len(scenes)
+            host = torch.zeros((len(scenes), RING_MAX), dtype=torch.int32)
+            for i, s in enumerate(scenes):
+                segs = self.segs[s]
+                sel.n_segs[i], sel.n_views[i] = len(segs), sum(st.n_views for st in segs)
+                host[i, :len(segs)] = torch.tensor([st.row for st in segs], dtype=torch.int32)
+            dev = _upload_async(host, self.device) if self.device.type == "cuda" else host.clone()
+            self._sel = (key, sel, host, dev)
+        return self._sel[1:]
+
+
+def scene_accumulate_group_ring(pool: SceneGroupRingState, scenes, features: Tensor, mapped: Tensor, bias: Tensor, denorm_images: Tensor,
+                                projection: Tensor, rgb_projection: Tensor, depth_gate: Optional[DepthGate] = None, states=None) -> None:
+    """:func:`scene_accumulate_group` for a windowed group: one chunk of k views per listed scene, each into an empty state of its own that
+    then joins its scene's window (the oldest chunk leaving a full one); arguments as :func:`scene_accumulate_group`'s.  The grouped
+    accumulate runs unchanged over a per-call table of the n states it fills, so each holds the bits :func:`scene_accumulate` leaves in an
+    empty state for that chunk -- what a windowed SceneStream's segment holds.  A call that raises leaves every window as it was.
+    ``states``: None, or the empty states to fill (one per listed scene, from ``pool.take``); the caller then does the pool's bookkeeping
+    (``pool.accumulate`` is that bookkeeping, and what this function does with ``states=None``)."""
+    scenes = pool.listed(scenes)
+    if states is None:
+        pool.accumulate(scenes, lambda front: scene_accumulate_group_ring(pool, scenes, features, mapped, bias, denorm_images, projection,
+                                                                          rgb_projection, depth_gate=depth_gate, states=front))
+        return
+    _need_gpu(features, mapped, bias, denorm_images, projection, rgb_projection)
+    n = len(scenes)
+    assert len(states) == n
+    f = to_channels_last(features)
+    m = to_channels_last(mapped)
+    n_v, c, h, w = f.shape
+    if n_v % n or not 1 <= n_v // n <= GROUP_VIEWS_MAX:
+        raise ValueError(f"{n_v} views for {n} scenes: every listed scene brings the same 1 .. {GROUP_VIEWS_MAX} views")
+    k = n_v // n
+    assert m.shape[0] == n_v and m.shape[2:] == f.shape[2:], f"mapped map {tuple(m.shape)} for features {tuple(f.shape)}"
+    assert (c, m.shape[1]) == (pool.c, pool.cm), f"group for C={pool.c}, cm={pool.cm}; chunk has {c}, {m.shape[1]}"
+    if not density_packed_ok(0, pool.cm, m):       # the packed walk's channel quads need 16-byte aligned rows
+        m = to_channels_last(m.contiguous())
+    rgb = denorm_images if denorm_images.dtype == torch.float32 else denorm_images.float()
+    assert rgb.shape[0] == n_v and rgb.shape[1] == 3
+    if rgb.stride(3) != 1:
+        rgb = rgb.contiguous()
+    hh, ww = rgb.shape[2:]
+    projection, rgb_projection, bias = _f32c(projection), _f32c(rgb_projection), _f32c(bias)
+    assert projection.shape == (n_v, 3, 4) and rgb_projection.shape == (n_v, 3, 4)
+    g = None if depth_gate is None else _gate_arg(depth_gate, n_v, (h, w), (hh, ww))
+    blk, sel, table = pool.front(scenes, states)
+    s0 = states[0]
+    trace.span("k_scene_accumulate_group", lambda: check(_lib.load().ndet_scene_accumulate_group(
+        ctypes.byref(blk), ctypes.byref(sel), k, _ptr(f), h, w, f.stride(0), f.stride(2), _ptr(m), m.stride(0), m.stride(2), _ptr(bias), _ptr(rgb),
+        hh, ww, rgb.stride(0), rgb.stride(1), rgb.stride(2), _ptr(projection), _ptr(rgb_projection), g, _stream(f)), "scene_accumulate_group"),
+        bytes=4 * (n_v * (c * h * w + pool.cm * h * w + 3 * hh * ww)) + 2 * n * (s0.k1_sum.numel() + s0.k2_sum.numel()) * 4, kind="hbm")
+    del table       # held until the launches were queued
+    for st in states:
+        st.n_views = k
+
+
+def _group_ring_finish_args(pool: SceneGroupRingState, scenes):
+    scenes = pool.listed(scenes)
+    empty = [s for s in scenes if sum(st.n_views for st in pool.segs[s]) == 0]
+    if empty:
+        raise ValueError(f"scenes {empty} have no views yet")
+    blk, table = pool.block()
+    return (scenes, blk, table) + tuple(pool.ring_sel(scenes))
+
+
+def density_finish_group_ring(pool: SceneGroupRingState, bias: Tensor, scenes=None) -> Tensor:
+    """:func:`density_finish_ring` for the listed scenes' windows in one launch: ``(len(scenes) * N, 2*(3+cm))`` rows as
+    :func:`density_finish_group` returns them, listed scene i finished over its own segments and view total; bit for bit
+    :func:`density_finish_ring`'s rows over that scene's states.  No state is changed.  The span's bytes count every segment in full, an
+    upper bound as in :func:`density_finish_ring`."""
+    _need_gpu(bias)
+    scenes, blk, table, sel, segs_host, segs_dev = _group_ring_finish_args(pool, scenes)
+    bias = _f32c(bias)
+    assert bias.numel() == pool.cm
+    n_vox = pool.n_voxels
+    out = torch.empty((len(scenes) * n_vox, 2 * (3 + pool.cm)), dtype=torch.float32, device=pool.device)
+    read = sum(st.k2_sum.numel() + st.k2_count.numel() for s in scenes for st in pool.segs[s])
+    trace.span("k_density_finish_group_ring", lambda: check(_lib.load().ndet_scene_density_finish_group_ring(
+        ctypes.byref(blk), ctypes.byref(sel), segs_host.data_ptr(), _ptr(segs_dev), _ptr(bias), _ptr(out), _stream(out)),
+        "scene_density_finish_group_ring"), bytes=4 * (read + out.numel()), kind="hbm")
+    return out
+
+
+def volume_finish_group_ring(pool: SceneGroupRingState, alpha: Optional[Tensor] = None, scenes=None) -> Tuple[Tensor, Tensor]:
+    """:func:`volume_finish_ring` for the listed scenes' windows in one launch: ``(volume (n,C,X,Y,Z) with (n,X,Y,Z,C) memory, count
+    (n,1,X,Y,Z) int64)`` as :func:`volume_finish_group` returns them; ``alpha`` None or ``n * N`` values indexed as
+    :func:`density_finish_group_ring`'s rows.  Bit for bit :func:`volume_finish_ring`'s outputs over each scene's states; no state is
+    changed.  The span's bytes count every segment in full, an upper bound."""
+    _need_gpu(alpha)
+    scenes, blk, table, sel, segs_host, segs_dev = _group_ring_finish_args(pool, scenes)
+    n, n_vox = len(scenes), pool.n_voxels
+    if alpha is not None:
+        alpha = _f32c(alpha).reshape(-1)
+        assert alpha.numel() == n * n_vox
+    gx, gy, gz = pool.grid
+    buf = torch.empty((n, gx, gy, gz, pool.c), dtype=torch.float32, device=pool.device)
+    count = torch.empty((n, 1, gx, gy, gz), dtype=torch.int64, device=pool.device)
+    read = sum(st.k1_sum.numel() + st.k1_count.numel() for s in scenes for st in pool.segs[s])
+    trace.span("k_volume_finish_group_ring", lambda: check(_lib.load().ndet_scene_volume_finish_group_ring(
+        ctypes.byref(blk), ctypes.byref(sel), segs_host.data_ptr(), _ptr(segs_dev), _ptr(alpha), _ptr(buf), _ptr(count), _stream(buf)),
+        "scene_volume_finish_group_ring"), bytes=4 * (read + buf.numel()) + (12 if alpha is not None else 8) * n * n_vox, kind="hbm")
+    return buf.permute(0, 4, 1, 2, 3), count
+
+
+# --------------------------------------------------------------------------------------------
 # A6 pieces
 # --------------------------------------------------------------------------------------------
 def sigma_to_alpha(raw_sigma: Tensor) -> Tensor:

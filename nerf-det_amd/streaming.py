@@ -26,8 +26,12 @@ one by rounding.  In a window a chunk's bank segment leaves with its state.  Ren
 backbone pass, one guard read and one grouped accumulate per ``add_views`` call over one chunk per listed scene (ops.scene_accumulate_group),
 one grouped density finish, one sigma-MLP call and one grouped volume finish per ``detect`` (ops.density_finish_group / volume_finish_group), then
 neck_3d and the tails scene by scene, all queued before the host waits.  Each scene's state holds the bits
-``ops.scene_accumulate`` leaves for that scene alone; a group of one scene is a ``SceneStream`` bit for bit.  Groups are unwindowed and keep no
-view bank.
+``ops.scene_accumulate`` leaves for that scene alone; a group of one scene is a ``SceneStream`` bit for bit.  Groups keep no view bank.
+
+``nerfdet.begin_scenes(metas, window=S)`` gives every scene of the group a sliding window of S chunks: each listed scene's chunk fills a
+state of its own through the same grouped accumulate (ops.scene_accumulate_group_ring), scenes evict independently, and ``detect`` finishes
+the listed scenes' windows with one grouped density ring finish, one sigma-MLP call and one grouped volume ring finish
+(ops.density_finish_group_ring / volume_finish_group_ring), whose outputs are the single-scene ring finishes' bit for bit.
 
 Inference only: no training / autograd, no hipGraph replay, one scene per stream; whole chunks are dropped, not single views out of one.
 Without ``keep_views`` there is no ray branch (rendering needs every view's map).
@@ -327,10 +331,24 @@ class SceneGroup:
     scene, on scales of their own): detections agree with separate streams within the chunking contract -- same labels in the same order,
     scores and boxes to 1e-4.
 
-    Unwindowed, and no view bank: ``window=`` and ``keep_views=`` for groups are out of scope, as are scenes of different image sizes or
-    grids in one group, training, and the graphed path."""
+    ``window``: None, or the number of chunks every scene keeps (1 .. ops.RING_MAX).  A windowed group holds one state per chunk and scene
+    (ops.SceneGroupRingState: at most ``window + 1`` states per scene, allocated when first needed).  Every listed scene's chunk of an
+    :meth:`add_views` call fills a state of its own through the same grouped accumulate; only when it has succeeded do the states join
+    their scenes' windows and the oldest chunk leaves each listed scene whose window was full -- scenes evict independently, and a call
+    that raises leaves every window as it was.  :meth:`detect` finishes the listed windows with one grouped density ring finish, one
+    sigma-MLP call and one grouped volume ring finish, whose outputs are ops.density_finish_ring / volume_finish_ring's per scene bit
+    for bit: a windowed group of one scene is a windowed :class:`SceneStream` bit for bit, and a dropped chunk leaves no trace.
 
-    def __init__(self, det, img_metas):
+    No view bank: ``keep_views=`` / rendering for groups is out of scope, as are scenes of different image sizes or grids in one group,
+    training, and the graphed path."""
+
+    window = None       # None, or the chunks every scene keeps
+    pool = None         # ops.SceneGroupRingState of a windowed group
+    group = None        # ops.SceneGroupState of an unwindowed one
+
+    def __init__(self, det, img_metas, window: Optional[int] = None):
+        if window is not None:
+            ops.check_window(window)
         metas = list(img_metas)
         if not 1 <= len(metas) <= ops.GROUP_MAX:
             raise ValueError(f"begin_scenes takes 1 to {ops.GROUP_MAX} scenes, got {len(metas)}")
@@ -345,7 +363,11 @@ class SceneGroup:
         lin = det.mapping[0]
         self._lin = lin
         points = [ops.get_points(det.n_voxels, det.voxel_size, m["lidar2img"]["origin"], self.device) for m in metas]
-        self.group = ops.SceneGroupState(det.n_voxels, lin.in_features, lin.out_features, points, self.device)
+        self.window = window
+        if window is None:
+            self.group = ops.SceneGroupState(det.n_voxels, lin.in_features, lin.out_features, points, self.device)
+        else:
+            self.pool = ops.SceneGroupRingState(det.n_voxels, lin.in_features, lin.out_features, points, window, self.device)
 
     @staticmethod
     def _check_shapes(first: dict, metas) -> None:
@@ -360,13 +382,44 @@ class SceneGroup:
 
     @property
     def n_views(self) -> List[int]:
-        """View counts of the S scenes."""
-        return self.group.n_views
+        """View counts of the S scenes (of a windowed group: over the chunks held)."""
+        return self.group.n_views if self.window is None else self.pool.n_views
+
+    @property
+    def chunk_views(self) -> List[List[int]]:
+        """Per scene the view counts of the chunks held, oldest first (an unwindowed scene holds its views as one)."""
+        if self.window is None:
+            return [[v] if v else [] for v in self.group.n_views]
+        return self.pool.chunk_views
+
+    @property
+    def n_chunks(self) -> List[int]:
+        return [len(c) for c in self.chunk_views]
 
     def reset(self, scenes=None) -> None:
         """Forget every view of the listed scenes: they start empty again; the others keep theirs."""
-        for s in ops.listed_scenes(self.n_scenes, scenes):
-            self.group.states[s].reset()
+        scenes = ops.listed_scenes(self.n_scenes, scenes)
+        for s in scenes:
+            if self.window is None:
+                self.group.states[s].reset()
+            else:
+                self.pool.drop_oldest(len(self.pool.segs[s]), [s])
+
+    def drop_oldest(self, k: int = 1, scenes=None) -> None:
+        """Forget the k oldest chunks of every listed scene of a windowed group (their states are zeroed and kept for the chunks to come).
+        The call is refused whole (ValueError) when any listed scene holds fewer than k chunks; ``k = 0`` is allowed."""
+        if self.window is None:
+            raise ValueError("drop_oldest needs a windowed group: begin_scenes(img_metas, window=S)")
+        self.pool.drop_oldest(k, ops.listed_scenes(self.n_scenes, scenes))
+
+    def _accumulate(self, scenes, *chunk, depth_gate=None) -> None:
+        """Fold one chunk per listed scene into the scenes' states, or in a windowed group into empty states that join the scenes' windows
+        once the grouped accumulate has succeeded (ops.SceneGroupRingState.accumulate): a call that fails leaves every window as it was."""
+        if self.window is None:
+            ops.scene_accumulate_group(self.group, scenes, *chunk, depth_gate=depth_gate)
+            return
+        self.pool.accumulate(scenes, lambda states: ops.scene_accumulate_group_ring(self.pool, scenes, *chunk, depth_gate=depth_gate,
+                                                                                   states=states))
 
     def _check_call(self, img: Tensor, denorm_images: Tensor, metas, scenes, depth):
         """Everything add_views refuses, before anything is launched: ``(listed scenes, k)``."""
@@ -400,9 +453,10 @@ class SceneGroup:
         (len(scenes), k, Hd, Wd) float32 / float64: it gates every scene of the call or none (nerfdet.py:404-411).
 
         One pass for the whole call: the guard word is cleared, the backbone runs on all the chunks, the word is read back once (one
-        synchronisation per call, not per scene), and one grouped accumulate folds every scene's rows into its own state.  A tripped call's
-        backbone is redone on bf16x3 before any state is touched (``conv3d.guard_trips`` counts it once).  A call that is refused leaves
-        every state as it was -- also one the backbone refuses: the ``len(scenes) * k`` views share its launches, whose operands address
+        synchronisation per call, not per scene), and one grouped accumulate folds every scene's rows into its own state (in a windowed
+        group: into a state of its own per listed scene, which then joins that scene's window).  A tripped call's backbone is redone on
+        bf16x3 before any state or window is touched (``conv3d.guard_trips`` counts it once).  A call that is refused leaves every state
+        and window as it was -- also one the backbone refuses: the ``len(scenes) * k`` views share its launches, whose operands address
         at most 2 GB each (200 views of 240 x 320 are too many)."""
         scenes, k = self._check_call(img, denorm_images, metas, scenes, depth)
         n = len(scenes)
@@ -436,26 +490,32 @@ class SceneGroup:
                 d = depth.reshape([-1] + list(depth.shape)[2:]).to(self.device, non_blocking=True)
                 gate = ops.depth_gate(d, self.det.voxel_size, (h, w), (hh, ww))
             proj = ops.compute_projection_group(metas, (stride, 1), self.device)     # the n k projections at both strides: one upload
-            ops.scene_accumulate_group(self.group, scenes, feat, mapped, lin.bias, rgb, proj[0], proj[1], depth_gate=gate)
+            self._accumulate(scenes, feat, mapped, lin.bias, rgb, proj[0], proj[1], depth_gate=gate)
 
     def _need_views(self, scenes) -> List[int]:
         scenes = ops.listed_scenes(self.n_scenes, scenes)
-        empty = [s for s in scenes if self.group.states[s].n_views == 0]
+        held = self.n_views
+        empty = [s for s in scenes if held[s] == 0]
         if empty:
             raise ValueError(f"scenes {empty} have no views yet: call add_views first")
         return scenes
 
     def _volumes(self, scenes: List[int]):
         """``(volume (n,C,X,Y,Z), valid (n,1,X,Y,Z) int64)`` of the listed scenes: grouped K2-finish -> one sigma-MLP call over all their
-        rows -> grouped K1-finish (channels-last memory)."""
-        pts = torch.cat([self.group.points[s].reshape(3, -1) for s in scenes], dim=1) if len(scenes) > 1 else self.group.points[scenes[0]]
-        glob = ops.density_finish_group(self.group, self._lin.bias, scenes)
+        rows -> grouped K1-finish (channels-last memory); in a windowed group the two finishes are the grouped ring finishes."""
+        ring = self.window is not None
+        points = self.pool.points if ring else self.group.points
+        pts = torch.cat([points[s].reshape(3, -1) for s in scenes], dim=1) if len(scenes) > 1 else points[scenes[0]]
+        if ring:
+            glob = ops.density_finish_group_ring(self.pool, self._lin.bias, scenes)
+        else:
+            glob = ops.density_finish_group(self.group, self._lin.bias, scenes)
         mlp = self.det.nerf_mlp
         if hasattr(mlp, "hip_trunk_ok") and mlp.hip_trunk_ok():
             alpha = mlp.alpha_from_points(pts, glob)
         else:
             alpha = ops.sigma_to_alpha(mlp.raw_sigma_from_rows(ops.posenc_concat(pts, glob)))
-        return ops.volume_finish_group(self.group, alpha, scenes)
+        return ops.volume_finish_group_ring(self.pool, alpha, scenes) if ring else ops.volume_finish_group(self.group, alpha, scenes)
 
     def volume(self, scenes=None):
         """Per listed scene ``(volume (C,X,Y,Z), valid (1,X,Y,Z) int64)`` of its views so far, as :meth:`SceneStream.volume` returns them."""

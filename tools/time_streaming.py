@@ -19,6 +19,13 @@ SceneStream.add_views calls of the same chunks, and group.detect() against S sep
 with defer=True before the first is collected) with every scene holding the workload's 50 views -- the compared calls alternating inside
 one loop -- plus the group's state size and the peak allocation of building a group, adding 5 views per scene and detecting once.
     python tools/time_streaming.py --group 1,4,8,16 [--reps 20 --warmup 3]
+With --group-window S:W[,S:W...] it times windowed groups (det.begin_scenes(metas, window=W)): for every configuration S scenes with full
+windows of W single-view chunks -- group.add_views of S x 1 views against S windowed SceneStream.add_views calls and against the
+unwindowed group's; group.detect() against the S windowed streams' detect(defer=True) calls, all queued before the first is collected, and
+against the unwindowed group's; the two grouped ring finishes alone against S calls of each single-scene ring finish -- the compared calls
+alternating inside one loop -- plus the finish and sigma-MLP spans of one detect(), the pool's size and the peak allocations of
+sliding a window once and detecting.
+    python tools/time_streaming.py --group-window 8:4,8:8 [--reps 20 --warmup 3]
 """
 import argparse
 import importlib.util
@@ -175,6 +182,100 @@ def group_mode(det, img, dn, meta, sizes, reps, warmup, dev):
     return res
 
 
+def group_window_mode(det, img, dn, meta, configs, reps, warmup, dev):
+    import numpy as np
+    from nerfdet_amd import ops, trace
+    res = {}
+    n_v = img.shape[1]
+    for S, W in configs:
+        tag = f"S{S}_W{W}"
+        metas = []
+        for i in range(S):
+            m = dict(meta)
+            m["lidar2img"] = dict(meta["lidar2img"], origin=np.asarray(meta["lidar2img"]["origin"], dtype=np.float32) + np.float32([0.05 * i, -0.03 * i, 0.0]))
+            metas.append(m)
+
+        def frames(r):
+            """Round r's call: one view per scene, scene i on view (r + 3 i) of the workload's rig."""
+            starts = [(r + 3 * i) % n_v for i in range(S)]
+            return (torch.cat([img[:, v:v + 1] for v in starts]).contiguous(), torch.cat([dn[:, v:v + 1] for v in starts]).contiguous(),
+                    [chunk_meta(m, v, v + 1) for m, v in zip(metas, starts)])
+
+        wgroup = det.begin_scenes([dict(m) for m in metas], window=W)
+        ugroup = det.begin_scenes([dict(m) for m in metas])
+        streams = [det.begin_scene(dict(m), window=W) for m in metas]
+
+        def stream_add(call):
+            for i, st in enumerate(streams):
+                st.add_views(call[0][i:i + 1], call[1][i:i + 1], call[2][i])
+
+        for r in range(W + 1):        # full windows that have slid once: from here on nothing is allocated
+            call = frames(r)
+            wgroup.add_views(*call)
+            ugroup.add_views(*call)
+            stream_add(call)
+        assert wgroup.n_chunks == [W] * S and all(st.n_chunks == W for st in streams)
+        call = frames(W + 1)
+        fns = {"window_group_add_views_ms": lambda: wgroup.add_views(*call), "window_streams_add_views_ms": lambda: stream_add(call),
+               "unwindowed_group_add_views_ms": lambda: ugroup.add_views(*call)}
+        med, span = timed_alternating(fns, reps, warmup)
+
+        def deferred():
+            pending = [st.detect(defer=True) for st in streams]
+            return [f() for f in pending]
+
+        bias = wgroup._lin.bias
+        alpha = torch.rand(S * wgroup.pool.n_voxels, device=dev)
+        a1 = alpha[:wgroup.pool.n_voxels]
+        fns2 = {"window_group_detect_ms": wgroup.detect, "window_streams_deferred_detect_ms": deferred, "unwindowed_group_detect_ms": ugroup.detect,
+                "density_finish_group_ring_ms": lambda: ops.density_finish_group_ring(wgroup.pool, bias),
+                "density_finish_ring_x_S_ms": lambda: [ops.density_finish_ring(st._segs, bias) for st in streams],
+                "volume_finish_group_ring_ms": lambda: ops.volume_finish_group_ring(wgroup.pool, alpha),
+                "volume_finish_ring_x_S_ms": lambda: [ops.volume_finish_ring(st._segs, a1) for st in streams]}
+        med2, span2 = timed_alternating(fns2, reps, warmup)
+        med.update(med2)
+        span.update(span2)
+        for k in med:
+            res[f"{tag}_{k}"], res[f"{tag}_{k}_min_max"] = med[k], span[k]
+        res[f"{tag}_add_views_streams_over_window_group"] = med["window_streams_add_views_ms"] / med["window_group_add_views_ms"]
+        res[f"{tag}_detect_streams_over_window_group"] = med["window_streams_deferred_detect_ms"] / med["window_group_detect_ms"]
+        res[f"{tag}_density_finish_separate_over_group"] = med["density_finish_ring_x_S_ms"] / med["density_finish_group_ring_ms"]
+        res[f"{tag}_volume_finish_separate_over_group"] = med["volume_finish_ring_x_S_ms"] / med["volume_finish_group_ring_ms"]
+        # the launches of one windowed-group detect(): spans of the finishes and of the sigma-MLP
+        prev, trace.recorder = trace.recorder, trace.Recorder()
+        try:
+            wgroup.detect()
+            names = [sp[0] for sp in trace.recorder.spans]
+        finally:
+            trace.recorder = prev
+        res[f"{tag}_detect_spans"] = {n: names.count(n) for n in sorted(set(names)) if "finish" in n or "point_mlp" in n or "sigma" in n}
+        pool = wgroup.pool
+        res[f"{tag}_pool_states"] = len(pool.states)
+        res[f"{tag}_pool_mb"] = sum(t.numel() * t.element_size() for st in pool.states for t in (st.k1_sum, st.k1_count, st.k2_sum, st.k2_count)) / 2 ** 20
+        del wgroup, ugroup, streams, pool
+        calls = [frames(r) for r in range(W + 1)]
+
+        def slide_group(window):
+            g = det.begin_scenes([dict(m) for m in metas], window=window)
+            for c in calls:
+                g.add_views(*c)
+            return g.detect()
+
+        def slide_streams():
+            sts = [det.begin_scene(dict(m), window=W) for m in metas]
+            for c in calls:
+                for i, st in enumerate(sts):
+                    st.add_views(c[0][i:i + 1], c[1][i:i + 1], c[2][i])
+            pending = [st.detect(defer=True) for st in sts]
+            return [f() for f in pending]
+
+        res[f"{tag}_window_group_peak_mb"] = peak_mb(lambda: slide_group(W))
+        res[f"{tag}_window_streams_peak_mb"] = peak_mb(slide_streams)
+        res[f"{tag}_unwindowed_group_peak_mb"] = peak_mb(lambda: slide_group(None))
+        del calls
+    return res
+
+
 def render_mode(det, img, dn, meta, rb, reps, warmup, dev):
     from nerfdet_amd import rays, synth
     res = {}
@@ -281,6 +382,7 @@ def main():
     ap.add_argument("--window", type=str, default=None, help="comma-separated window sizes in chunks of 5 views, e.g. 1,4,8")
     ap.add_argument("--render", action="store_true", help="time rendering from a streamed scene (the view-bank sampler)")
     ap.add_argument("--group", type=str, default=None, help="comma-separated scene-group sizes, e.g. 1,4,8,16")
+    ap.add_argument("--group-window", type=str, default=None, help="comma-separated scenes:window configurations of windowed groups, e.g. 8:4,8:8")
     args = ap.parse_args()
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
@@ -298,6 +400,14 @@ def main():
             res = render_mode(det, img, dn, meta, rb, args.reps, args.warmup, dev)
         for k, v in res.items():
             print(f"{k:>44}: " + (f"{v:.3f}" if isinstance(v, float) else str(v)))
+        print(json.dumps(res))
+        return
+    if args.group_window:
+        configs = [tuple(int(x) for x in c.split(":")) for c in args.group_window.split(",")]
+        with torch.no_grad():
+            res = group_window_mode(det, img, dn, meta, configs, args.reps, args.warmup, dev)
+        for k, v in res.items():
+            print(f"{k:>52}: " + (f"{v:.3f}" if isinstance(v, float) else str(v)))
         print(json.dumps(res))
         return
     if args.group:
