@@ -651,6 +651,23 @@ typedef struct NdetConvArgs {
 } NdetConvArgs;
 int ndet_conv_split(const NdetConvArgs* a, void* stream);
 
+/* ndet_conv_split over a BATCH of volumes in one launch: in (batch, D, H, W, Cin) -> out (batch, OD, OH, OW, Cout), both contiguous; a->D / H / W are
+ * ONE volume's extents.  The GEMM has batch * OD * OH * OW rows; a row's taps are bounded by its own volume (nothing is read across a volume's
+ * first or last slice), the weights, the affine, the residual (same shape as out), split-K (workspace: splits * batch * M * Cout floats), in_amax /
+ * out_amax (one slot each for the whole batch: the fp16-pair scale is shared by its volumes) and the guard work on the rows of all volumes as they
+ * do on one volume's.  The layers of mmdet3d/models/necks/imvoxelnet.py:36-67,233-260 and dense_heads/imvoxel_head_v2.py:45-49 for several scenes
+ * at once (the reference runs them on a batch axis of nn.Conv3d).  Every tile but the persistent ones (129256 / 129257 / 129064) has a batched
+ * instantiation of its kernel beside the plain one.  batch == 1 is ndet_conv_split, launch for launch.  Refused before any HIP call: batch < 1
+ * (NDET_E_INVALID); batch > 1 with w_amax, keep_partials, residual_up2, map_* or a persistent tile, batch * OD * OH * OW >= 2^31, and the tile
+ * families' operand limits taken over the whole batch (NDET_E_UNSUPPORTED). */
+int ndet_conv_split_batch(const NdetConvArgs* a, int batch, void* stream);
+
+/* TEST SUPPORT, not part of the drop-in surface (no caller in the package).  What a halo tile (3128 / 3256 / 3257 / 3258) would launch on a stride-1 same-padded convolution over one D x H x W volume (a batch tiles every
+ * volume this way): patch[3] = the 128-voxel output patch (TD, TH, TW) its launcher picks, *looped = 1 when the depth taps are looped outside the
+ * staged halo image, 0 when they lie inside it.  No HIP call: for tests that must know which of the two forms a shape exercises.  Part of the
+ * launcher of the convolutions of mmdet3d/models/necks/imvoxelnet.py:36-67; the reference has no counterpart.  NDET_E_INVALID for another tile. */
+int ndet_conv_halo_patch(int tile, int D, int H, int W, const int* kernel, int* patch, int* looped);
+
 #define NDET_TILE_DIRECT 1    /* epilogue straight from the accumulators: final values only */
 #define NDET_TILE_OWNS_ROWS 2 /* one tile holds all 256 channels of its rows: the chained projection (map_out) is allowed */
 #define NDET_TILE_ORDER2 4    /* may be dealt in the activation-stationary workgroup order */

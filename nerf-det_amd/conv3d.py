@@ -396,14 +396,17 @@ def layer_arithmetic(k_iters: int) -> str:
 
 
 def _conv_split(x, pk, out, dims, kernel, stride, pad, transposed, residual, residual_up2, relu, splits, tile, m, k_iters, flops, want_amax=True, chain=None,
-                keep_partials=False):
+                keep_partials=False, batch=1):
     """One ndet_conv_split launch.  ``keep_partials`` (the weight-gradient GEMM of conv_train.weight_grad): returns ``(out, partials)``, ``partials`` =
-    ``(workspace, splits)`` when the launch split K and left its partial sums for ndet_wgrad_to_torch to add (``out`` is then unwritten), else None."""
+    ``(workspace, splits)`` when the launch split K and left its partial sums for ndet_wgrad_to_torch to add (``out`` is then unwritten), else None.
+    ``batch`` > 1: ``x`` / ``out`` hold that many volumes of ``dims``, ``m`` counts the rows of all of them, and the launch is one
+    ndet_conv_split_batch (the tile and splits are the tables' for ``m`` rows; no chain, no keep_partials, no upsampled residual)."""
+    assert batch == 1 or (chain is None and not keep_partials and not residual_up2 and pk.w_amax is None)
     halo_ok = (not transposed and all(s == 1 for s in stride) and all(k % 2 == 1 and q == k // 2 for k, q in zip(kernel, pad))
                and kernel[0] * kernel[1] * kernel[2] > 1)
     tile, splits = choose_tiling_split(m, pk.cout, k_iters, tile, 1 if (transposed or residual_up2) else splits, transposed, halo_ok)
     tile, splits = conv_tiles.resolve(tile, splits, m=m, cout=pk.cout, cin=pk.cin, taps=kernel[0] * kernel[1] * kernel[2], transposed=transposed,
-                                      halo_ok=halo_ok, direct_epilogue=DIRECT_EPILOGUE)
+                                      halo_ok=halo_ok, direct_epilogue=DIRECT_EPILOGUE, batch=batch)
     ws = torch.empty((m * pk.cout * splits * 4,), dtype=torch.uint8, device=x.device) if splits > 1 else None
     st = c_void_p(raw_stream(x.device))
     lib = _lib.load()
@@ -451,7 +454,11 @@ def _conv_split(x, pk, out, dims, kernel, stride, pad, transposed, residual, res
             nbytes += 4 * mapped.numel()
     out_amax = AMAX.take(x.device) if want_amax else None
     a.out_amax = _addr(out_amax)
-    _launch(flops, lambda: check(lib.ndet_conv_split(a, st), "conv_split"), arith, tile, nbytes)
+    if batch == 1:
+        _launch(flops, lambda: check(lib.ndet_conv_split(a, st), "conv_split"), arith, tile, nbytes)
+    else:
+        _launch(flops, lambda: check(lib.ndet_conv_split_batch(a, batch, st), "conv_split_batch"), arith, tile, nbytes,
+                name=KERNEL_NAMES.get((arith, tile), f"{arith}:{tile}") + "/batch")
     if want_amax:
         _tag_amax(out, out_amax)
     if keep_partials:
@@ -565,9 +572,12 @@ def linear_rows(x: torch.Tensor, pk: ConvPack, relu: int = 0) -> torch.Tensor:
 def conv3d_ndhwc(x: torch.Tensor, pk: ConvPack, residual: Optional[torch.Tensor] = None, relu: int = 0, splits: int = 0, tile: int = 0,
                  amax: bool = True):
     """x (D,H,W,Cin) contiguous fp32 on the GPU -> (OD,OH,OW,Cout).  relu: 0 none, 1 after the residual add, 2 before it.  amax (fp16-pair
-    mode): leave max |out| behind for a following convolution -- False for outputs no convolution reads (identity branches, final heads)."""
+    mode): leave max |out| behind for a following convolution -- False for outputs no convolution reads (identity branches, final heads).
+    A 5-D x (N,D,H,W,Cin) is a batch of volumes -> (N,OD,OH,OW,Cout) in one launch (split-family arithmetics; _conv3d_batch)."""
     if not x.is_cuda:
         raise RuntimeError("nerfdet_amd.conv3d: tensors must live on the GPU (no CPU fallback)")
+    if x.dim() == 5:
+        return _conv3d_batch(x, pk, residual, relu, splits, tile, amax)
     assert x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32
     d, h, w, cin = x.shape
     assert cin == pk.cin, (cin, pk.cin)
@@ -600,6 +610,33 @@ def conv3d_ndhwc(x: torch.Tensor, pk: ConvPack, residual: Optional[torch.Tensor]
                                                        _ptr(pk.shift), _ptr(residual), relu, splits, tile, _ptr(ws), st), "conv3d_ndhwc"), "f32", tile,
             4 * (x.numel() + pk.w.numel() + out.numel() + (0 if residual is None else residual.numel())))
     return out
+
+
+def _conv3d_batch(x, pk, residual, relu, splits, tile, amax):
+    """conv3d_ndhwc on a batch: x (N,D,H,W,Cin) contiguous fp32 -> (N,OD,OH,OW,Cout), every volume convolved on its own, in ONE launch
+    (ndet_conv_split_batch).  Tile and splits are chosen for the N * OD*OH*OW rows of the whole batch; in the fp16-pair arithmetic the volumes
+    share the input's scale (one amax slot for the batch) and the output carries the launch's slot.  Split-family arithmetics only."""
+    if ARITHMETIC not in SPLIT_FAMILY:
+        raise ValueError(f"conv3d_ndhwc: a 5-D (batched) input needs a split-family arithmetic {SPLIT_FAMILY}, not {ARITHMETIC!r}: "
+                         "the fp32-MFMA family has no batch axis (run the volumes one by one)")
+    assert x.is_contiguous() and x.dtype == torch.float32 and pk.ndim == 3
+    n, d, h, w, cin = x.shape
+    assert cin == pk.cin, (cin, pk.cin)
+    k, s, tr, cout = pk.kernel[0], pk.strides[0], pk.transposed, pk.cout
+    if tr:
+        od, oh, ow = 2 * d, 2 * h, 2 * w
+        kk, ss, pp = (2, 2, 2), (2, 2, 2), (0, 0, 0)
+    else:
+        pad = int(pk.pads[0])
+        od, oh, ow = ((v + 2 * pad - k) // s + 1 for v in (d, h, w))
+        kk, ss, pp = (k,) * 3, (s,) * 3, (pad,) * 3
+    out = torch.empty((n, od, oh, ow, cout), dtype=torch.float32, device=x.device)
+    if residual is not None:
+        assert residual.shape == out.shape and residual.is_contiguous()
+    m = n * (d * h * w if tr else od * oh * ow)
+    flops = 2 * m * cout * cin * (1 if tr else k ** 3) * (8 if tr else 1)
+    return _conv_split(x, pk, out, (d, h, w), kk, ss, pp, tr, residual, False, relu, splits, tile, m, (cin // 32) * (1 if tr else k ** 3), flops, amax,
+                       batch=n)
 
 
 def conv2d_nhwc(x: torch.Tensor, pk: ConvPack, residual: Optional[torch.Tensor] = None, relu: int = 0, splits: int = 0, tile: int = 0,

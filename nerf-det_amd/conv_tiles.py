@@ -51,10 +51,12 @@ def owns_rows(tile: int) -> bool:
     return tile in TILES and bool(TILES[tile].flags & OWNS_ROWS)
 
 
-def resolve(tile: int, splits: int, *, m: int, cout: int, cin: int, taps: int, transposed: bool, halo_ok: bool, direct_epilogue: bool = True):
+def resolve(tile: int, splits: int, *, m: int, cout: int, cin: int, taps: int, transposed: bool, halo_ok: bool, direct_epilogue: bool = True,
+            batch: int = 1):
     """(tile, splits) the layer runs when the tables / the caller name ``tile``: what a family does not take goes to the nearest tile that does (the
     library itself rejects such a request: the NDET_REQUIREs of each split_launch_*).  ``halo_ok``: stride 1, odd same-padded kernel, more than one
-    tap.  An id outside the table is left for the library to reject."""
+    tap.  ``batch``: volumes in the launch (ndet_conv_split_batch; ``m`` counts the rows of all of them).  An id outside the table is left for the
+    library to reject."""
     row = TILES.get(tile)
     if row is None:
         return tile, splits
@@ -63,8 +65,8 @@ def resolve(tile: int, splits: int, *, m: int, cout: int, cin: int, taps: int, t
             tile = 128256 if cout > 128 else 128
         else:
             splits = min(splits, cin // 32)
-    elif row.family == "wsp" and (transposed or cout % 16 or taps > 32):
-        tile = 128256               # the persistent form takes plain convolutions with Cout % 16 == 0
+    elif row.family == "wsp" and (transposed or cout % 16 or taps > 32 or batch > 1):
+        tile = 128256               # the persistent form takes plain convolutions with Cout % 16 == 0, one volume per launch
     row = TILES[tile]
     if row.family == "unified":
         # unified tiles that write final values: the epilogue straight from the MFMA's C layout (no LDS staging, no barriers)

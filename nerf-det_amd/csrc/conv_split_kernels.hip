@@ -29,7 +29,11 @@
 
 // K walk of the unified tiles: fills acc (per-wave 32x32 MFMA tiles) for GEMM rows m0.. and channels n0..; returns the transposed-conv tap
 // (blockIdx.z) in ztap.  Ends behind a barrier: the LDS operand planes are free for the epilogue.
-template <int BM, int BN, int WGM, int WGN, int SCH>
+// BATCH: the rows are N volumes of p.OD x p.OH x p.OW stacked along depth (M = N OD OH OW; input N x p.D x p.H x p.W): a row's depth index is
+// taken inside its own volume -- the taps' depth bound is the volume's p.D -- and the volume enters the input address as n p.D slices.  Setup
+// only: the K walk, the weights and the epilogues work on linear rows.  (k2 s2 transposed: the rows are input voxels, decoded the same way for
+// load_tile's depth test; the output row 2 (n D + d) + kd = n OD + 2 d + kd needs nothing.)
+template <int BM, int BN, int WGM, int WGN, int SCH, bool BATCH = false>
 __device__ __forceinline__ void conv_split_mainloop(const Conv3dParams& p, const uint16_t* __restrict__ wsplit, uint16_t* lds16,
                                                     f32x16 (&acc)[BM / WGM / 32][BN / WGN / 32], int& ztap) {
     constexpr int NTHR = 64 * WGM * WGN;
@@ -100,6 +104,17 @@ __device__ __forceinline__ void conv_split_mainloop(const Conv3dParams& p, const
     const float* rowbase[AR];
 #pragma unroll
     for (int i = 0; i < AR; ++i) {
+        if constexpr (BATCH) {
+            const int rd = p.transposed ? p.D : p.OD;      // depth extent of one volume's rows
+            const int n = vd[i] / rd;
+            vd[i] -= n * rd;
+            const int vol = n * p.D;                       // first input slice of the row's volume
+            bd[i] = p.transposed ? vd[i] : vd[i] * p.sd - p.pd;
+            bh[i] = p.transposed ? vh[i] : vh[i] * p.sh - p.ph;
+            bw[i] = p.transposed ? vw[i] : vw[i] * p.sw - p.pw;
+            rowbase[i] = p.in + (((int64_t)(vol + bd[i]) * p.H + bh[i]) * p.W + bw[i]) * p.Cin + akq * 4;
+            continue;
+        }
         bd[i] = p.transposed ? vd[i] : vd[i] * p.sd - p.pd;
         bh[i] = p.transposed ? vh[i] : vh[i] * p.sh - p.ph;
         bw[i] = p.transposed ? vw[i] : vw[i] * p.sw - p.pw;
@@ -205,8 +220,13 @@ __device__ __forceinline__ void conv_split_mainloop(const Conv3dParams& p, const
                              // conv3 layers, which now take two rounds), but at 128 registers the kernel spills 316 bytes per lane (162 needed): three
 #endif
 template <int BM, int BN, int SCH> constexpr int uni_min_wgs() { return (SCH == 1 && BM == 128 && BN == 128) ? UNI128_F16_WGS : 2; }
-template <int BM, int BN, int WGM, int WGN, int SCH = 0>
-__global__ __launch_bounds__(64 * WGM * WGN, (uni_min_wgs<BM, BN, SCH>())) void k_conv_split(const Conv3dParams p, const uint16_t* __restrict__ wsplit) {
+// The batched form of a tile kernel (BATCH of conv_split_mainloop) is an instantiation of its own beside the plain one: its scheme argument is
+// SCH + SPL_BATCH, so the plain kernels keep their symbols and are compiled exactly as before.
+#define SPL_BATCH 4
+template <int BM, int BN, int WGM, int WGN, int SCHB = 0>
+__global__ __launch_bounds__(64 * WGM * WGN, (uni_min_wgs<BM, BN, (SCHB & 3)>())) void k_conv_split(const Conv3dParams p, const uint16_t* __restrict__ wsplit) {
+    constexpr int SCH = SCHB & 3;
+    constexpr bool BATCH = (SCHB & SPL_BATCH) != 0;
     constexpr int NTHR = 64 * WGM * WGN;
     constexpr int WM = BM / WGM, WN = BN / WGN, MT = WM / 32, NT = WN / 32;
     extern __shared__ __attribute__((aligned(16))) uint16_t lds16[];
@@ -219,7 +239,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (uni_min_wgs<BM, BN, SCH>())) void 
     int ztap;
     const float amax_in = conv_amax_in(p);
     conv_guard_check(p, amax_in);
-    conv_split_mainloop<BM, BN, WGM, WGN, SCH>(p, wsplit, lds16, acc, ztap);
+    conv_split_mainloop<BM, BN, WGM, WGN, SCH, BATCH>(p, wsplit, lds16, acc, ztap);
     const float osc = conv_oscale_of(p, amax_in);
 
     // C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
@@ -750,9 +770,11 @@ __device__ __forceinline__ void spl_dma16(__amdgpu_buffer_rsrc_t rsrc, uint16_t*
 #define WS_DEPTH 2
 #define WS_OOB 0x80000000u
 
-// SCH: the arithmetic scheme (Spl above).
-template <int SCH>
+// SCHB: the arithmetic scheme (Spl above), + SPL_BATCH: rows of N stacked volumes, as in conv_split_mainloop.
+template <int SCHB>
 __global__ __launch_bounds__(512, 1) void k_conv_split_ws(const Conv3dParams p, const uint16_t* __restrict__ wsplit) {
+    constexpr int SCH = SCHB & 3;
+    constexpr bool BATCH = (SCHB & SPL_BATCH) != 0;
     constexpr int APL = WS_BM * CBK, BPL = WS_BN * CBK;   // one plane, in bf16 elements
     constexpr int NPL = Spl<SCH>::NPL, WPL = Spl<SCH>::WPL;
     constexpr int STAGE = NPL * (APL + BPL);
@@ -807,9 +829,12 @@ __global__ __launch_bounds__(512, 1) void k_conv_split_ws(const Conv3dParams p, 
             const bool vok = m < p.M;
             const int mm = vok ? m : 0;
             const int ow_ = p.transposed ? p.W : p.OW, oh_ = p.transposed ? p.H : p.OH;
-            const int vw = mm % ow_, vh = (mm / ow_) % oh_, vd = mm / (ow_ * oh_);
+            const int vw = mm % ow_, vh = (mm / ow_) % oh_, vdg = mm / (ow_ * oh_);
+            const int vol = (BATCH && !p.transposed) ? vdg / p.OD : 0;      // the row's volume; vd: its depth inside that volume
+            const int vd = BATCH ? vdg - vol * p.OD : vdg;
             const int sd = p.transposed ? 1 : p.sd, sh = p.transposed ? 1 : p.sh, sw = p.transposed ? 1 : p.sw;
-            avoff[i] = (unsigned)(((((int64_t)vd * sd) * p.H + vh * sh) * p.W + vw * sw) * p.Cin * 4 + akq * 16);
+            if constexpr (BATCH) avoff[i] = (unsigned)(((((int64_t)vd * sd + vol * p.D) * p.H + vh * sh) * p.W + vw * sw) * p.Cin * 4 + akq * 16);
+            else avoff[i] = (unsigned)(((((int64_t)vd * sd) * p.H + vh * sh) * p.W + vw * sw) * p.Cin * 4 + akq * 16);
             unsigned msk = 0;
             if (vok) {
                 if (p.transposed) {
@@ -998,10 +1023,14 @@ static inline int with_scheme(int sch, F&& f) {
     return sch == 2 ? f(std::integral_constant<int, 2>{}) : (sch == 1 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{}));
 }
 
-static int split_launch_ws(const Conv3dParams& p, hipStream_t st, const char* fn) {
+// BATCH (here and in the launchers below): `batch` volumes of p.D x p.H x p.W in one launch of the kernel's batched instantiation, p.M their rows
+// in all; the plain form never looks at `batch`
+template <bool BATCH>
+static int split_launch_ws_n(const Conv3dParams& p, int batch, hipStream_t st, const char* fn) {
     const int taps = p.transposed ? 1 : p.kd * p.kh * p.kw;
+    const int64_t nvol = BATCH ? batch : 1;
     NDET_REQUIRE(taps <= 32, NDET_E_UNSUPPORTED, "%s: the 128x256 tile supports at most 32 taps", fn);
-    NDET_REQUIRE((int64_t)p.D * p.H * p.W * p.Cin * 4 < ((int64_t)1 << 31) && (int64_t)(p.transposed ? 8 : taps) * p.Cin * p.Cout * 6 < ((int64_t)1 << 31),
+    NDET_REQUIRE(nvol * p.D * p.H * p.W * p.Cin * 4 < ((int64_t)1 << 31) && (int64_t)(p.transposed ? 8 : taps) * p.Cin * p.Cout * 6 < ((int64_t)1 << 31),
                  NDET_E_UNSUPPORTED, "%s: the 128x256 tile addresses at most 2 GB per operand", fn);
     const int zdim = p.transposed ? 8 : p.splits;
     dim3 grid((p.M + WS_BM - 1) / WS_BM, (p.Cout + WS_BN - 1) / WS_BN, zdim);
@@ -1010,12 +1039,14 @@ static int split_launch_ws(const Conv3dParams& p, hipStream_t st, const char* fn
     const size_t cs = (size_t)64 * (WS_BN + 4) * sizeof(float);   // the epilogue's C staging
     if (cs > lds) lds = cs;
     return with_scheme(sch, [&](auto s) -> int {
-        const auto kernel = k_conv_split_ws<decltype(s)::value>;
+        const auto kernel = k_conv_split_ws<decltype(s)::value + (BATCH ? SPL_BATCH : 0)>;
         NDET_RAISE_LDS(kernel, lds);
         hipLaunchKernelGGL(kernel, grid, dim3(512), lds, st, p, (const uint16_t*)p.w);
         return NDET_OK;
     });
 }
+static int split_launch_ws(const Conv3dParams& p, hipStream_t st, const char* fn) { return split_launch_ws_n<false>(p, 1, st, fn); }
+static int split_launch_ws_batch(const Conv3dParams& p, int batch, hipStream_t st, const char* fn) { return split_launch_ws_n<true>(p, batch, st, fn); }
 
 
 // ------------------------------------------------------------------------------------------------
@@ -1374,6 +1405,15 @@ struct HaloRowMap {
         return (od < OD && oh < OH && ow < OW) ? (od * OH + oh) * OW + ow : -1;
     }
 };
+// the same inside one volume of a batch: the volumes' rows follow each other
+struct HaloRowMapBatch {
+    HaloRowMap in_volume;
+    int vol_first;         // volume index * OD * OH * OW
+    __device__ __forceinline__ int operator()(int row) const {
+        const int m = in_volume(row);
+        return m < 0 ? m : vol_first + m;
+    }
+};
 
 // NT16: 16x16 tiles per consumer wave along N; WGN: consumer waves along N (2 along M).  <4,2>: 128 channels, <8,2>: 256 channels with
 // one consumer wave per SIMD, <4,4>: 256 channels with two consumer waves per SIMD (each covers the other's LDS latency).
@@ -1381,8 +1421,13 @@ struct HaloRowMap {
 // SCH 2: the leading bf16 plane only, one product (bf16 autocast arithmetic); the weights keep their three-plane layout.
 // NPROD: producer waves (4, or 8: an LDS-DMA piece holds its wave at the issue stage for ~250 cycles beside the MFMA stream, so the weight tile of a
 // 256-column step -- 32 pieces on two planes -- costs four producer waves 2 000 cycles where the step's MFMAs need 1 536; eight waves issue it in half)
-template <int NT16, int WGN, int SCH, int NPROD = 4>
+// SCHB = SCH + SPL_BATCH: N volumes of p.D x p.H x p.W, each tiled by patches of its own (grid x = N npd nph npw, the volume from the patch index).
+// The patch origin d0 stays inside the volume, so the halo's depth bound and the looped depth taps' mask are the volume's; the volume enters the
+// activation offsets and the output row only.
+template <int NT16, int WGN, int SCHB, int NPROD = 4>
 __global__ __launch_bounds__(64 * (2 * WGN + NPROD), 1) void k_conv_split_halo(const Conv3dParams p, const uint16_t* __restrict__ wsplit, const HaloGeom g) {
+    constexpr int SCH = SCHB & 3;
+    constexpr bool BATCH = (SCHB & SPL_BATCH) != 0;
     constexpr int BN = 16 * NT16 * WGN;
     constexpr int NCONS = 2 * WGN, NTHR = 64 * (NCONS + NPROD);
     constexpr int PT = 64 * NPROD;                          // producer threads
@@ -1410,7 +1455,9 @@ __global__ __launch_bounds__(64 * (2 * WGN + NPROD), 1) void k_conv_split_halo(c
     int pb = blk.x;
     const int pwi = pb % g.npw; pb /= g.npw;
     const int phi = pb % g.nph;
-    const int pdi = pb / g.nph;
+    const int pdv = pb / g.nph;
+    const int vol = BATCH ? pdv / g.npd : 0;      // the patch's volume
+    const int pdi = BATCH ? pdv - vol * g.npd : pdv;
     const int d0 = pdi << g.ltd, h0 = phi << g.lth, w0 = pwi << g.ltw;
     const float amax_in = conv_amax_in(p);
     conv_guard_check(p, amax_in);
@@ -1450,7 +1497,8 @@ __global__ __launch_bounds__(64 * (2 * WGN + NPROD), 1) void k_conv_split_halo(c
             const int hw = row % g.HW, hh = (row / g.HW) % g.HH, hd = row / (g.HW * g.HH);
             const int vd = d0 + hd - (dloop ? 0 : p.pd), vh = h0 - p.ph + hh, vw = w0 - p.pw + hw;
             const bool ok = row < g.NH && (unsigned)vd < (unsigned)p.D && (unsigned)vh < (unsigned)p.H && (unsigned)vw < (unsigned)p.W;
-            avoff[i] = ok ? (unsigned)((((int64_t)vd * p.H + vh) * p.W + vw) * p.Cin * 4 + q * 16) : WS_OOB;
+            if constexpr (BATCH) avoff[i] = ok ? (unsigned)((((int64_t)(vol * p.D + vd) * p.H + vh) * p.W + vw) * p.Cin * 4 + q * 16) : WS_OOB;
+            else avoff[i] = ok ? (unsigned)((((int64_t)vd * p.H + vh) * p.W + vw) * p.Cin * 4 + q * 16) : WS_OOB;
             unsigned msk = 0;
             if (dloop)
                 for (int k = 0; k < g.KDL; ++k)
@@ -1620,7 +1668,8 @@ __global__ __launch_bounds__(64 * (2 * WGN + NPROD), 1) void k_conv_split_halo(c
         float* Wl = Cs + 64 * CLDC;                     // (BN, 32) floats behind the staged rows (the launcher checked the room)
         if (p.map_out && h == 0)                        // every wave has left the K walk (the barrier above): the operand stages are free
             for (int i = tid; i < BN * 8; i += NTHR) reinterpret_cast<float4*>(Wl)[i] = reinterpret_cast<const float4*>(p.map_w)[i];
-        conv_store_rows_mapped<BN, NTHR>(p, Cs, CLDC, 64, n0, tid, 0, blk.z, rmap, mx, osc);
+        if constexpr (BATCH) conv_store_rows_mapped<BN, NTHR>(p, Cs, CLDC, 64, n0, tid, 0, blk.z, HaloRowMapBatch{rmap, vol * p.OD * p.OH * p.OW}, mx, osc);
+        else conv_store_rows_mapped<BN, NTHR>(p, Cs, CLDC, 64, n0, tid, 0, blk.z, rmap, mx, osc);
         __syncthreads();                                // (and Wl is in place)
         if (p.map_out) conv_map_rows<BN, NTHR>(p, Cs, CLDC, tid, rmap, osc, Wl);      // (uniform branch; barriers inside)
     }
@@ -1653,19 +1702,20 @@ static bool halo_geometry(const Conv3dParams& p, int halo_max, HaloGeom& g) {
     return best < 1e29;
 }
 
-template <int NT16, int WGN, int SCH = 0, int NPROD = 4>
-static int split_launch_halo(const Conv3dParams& p, hipStream_t st, const char* fn) {
+template <int NT16, int WGN, int SCH, int NPROD, bool BATCH>
+static int split_launch_halo(const Conv3dParams& p, int batch, hipStream_t st, const char* fn) {
     constexpr int NPL = SCH == 1 ? 2 : (SCH == 2 ? 1 : 3);
     constexpr int BN = 16 * NT16 * WGN, HALO_MAX = (BN == 128) ? 400 : 224, NSTAGE = (BN == 128) ? 3 : 2;
     NDET_REQUIRE(!p.transposed && p.sd == 1 && p.sh == 1 && p.sw == 1 && (p.kd & 1) && (p.kh & 1) && (p.kw & 1) && p.pd == p.kd / 2 &&
                      p.ph == p.kh / 2 && p.pw == p.kw / 2,
                  NDET_E_UNSUPPORTED, "%s: the halo tile needs a stride-1 same-padded convolution with odd kernel extents", fn);
-    NDET_REQUIRE((int64_t)p.D * p.H * p.W * p.Cin * 4 < ((int64_t)1 << 31) && (int64_t)p.kd * p.kh * p.kw * p.Cin * p.Cout * 6 < ((int64_t)1 << 31),
+    const int64_t nvol = BATCH ? batch : 1;
+    NDET_REQUIRE(nvol * p.D * p.H * p.W * p.Cin * 4 < ((int64_t)1 << 31) && (int64_t)p.kd * p.kh * p.kw * p.Cin * p.Cout * 6 < ((int64_t)1 << 31),
                  NDET_E_UNSUPPORTED, "%s: the halo tile addresses at most 2 GB per operand", fn);
     NDET_REQUIRE(p.splits <= p.Cin / CBK, NDET_E_INVALID, "%s: the halo tile splits K over the %d channel chunks only", fn, p.Cin / CBK);
     HaloGeom g;
     NDET_REQUIRE(halo_geometry(p, HALO_MAX, g), NDET_E_UNSUPPORTED, "%s: no patch shape fits the halo tile", fn);
-    dim3 grid(g.npd * g.nph * g.npw, (p.Cout + BN - 1) / BN, p.splits);
+    dim3 grid((unsigned)(nvol * g.npd * g.nph * g.npw), (p.Cout + BN - 1) / BN, p.splits);      // every volume is tiled by patches of its own
     size_t lds = (size_t)(NPL * HALO_MAX * CBK + NSTAGE * NPL * BN * CBK) * sizeof(uint16_t);
     const size_t cs = (size_t)64 * (BN + 4) * sizeof(float);
     if (cs > lds) lds = cs;
@@ -1676,35 +1726,51 @@ static int split_launch_halo(const Conv3dParams& p, hipStream_t st, const char* 
                      "%s: the chained projection needs a tile that owns all %d output channels of its rows, no split-K / residual / ReLU", fn, p.Cout);
         lds = lds_cap;
     }
-    NDET_RAISE_LDS((k_conv_split_halo<NT16, WGN, SCH, NPROD>), lds_cap);
-    hipLaunchKernelGGL((k_conv_split_halo<NT16, WGN, SCH, NPROD>), grid, dim3(64 * (2 * WGN + NPROD)), lds, st, p, (const uint16_t*)p.w, g);
+    const auto kernel = k_conv_split_halo<NT16, WGN, SCH + (BATCH ? SPL_BATCH : 0), NPROD>;
+    NDET_RAISE_LDS(kernel, lds_cap);
+    hipLaunchKernelGGL(kernel, grid, dim3(64 * (2 * WGN + NPROD)), lds, st, p, (const uint16_t*)p.w, g);
     return NDET_OK;
 }
 
-template <int BM, int BN, int WGM, int WGN, int SCH>
+template <int BM, int BN, int WGM, int WGN, int SCH, bool BATCH>
 static int split_launch_tile_sch(const Conv3dParams& p, hipStream_t st, const char* fn) {
     const int zdim = p.transposed ? 8 : p.splits;
     dim3 grid((p.M + BM - 1) / BM, (p.Cout + BN - 1) / BN, zdim);
     size_t lds = (size_t)Spl<SCH>::NPL * (BM + BN) * SPL_RS * sizeof(uint16_t);
     const size_t cs = (size_t)(BM / WGM) * (BN + 4) * sizeof(float);
     if (cs > lds) lds = cs;
-    if (lds > 64 * 1024) NDET_RAISE_LDS((k_conv_split<BM, BN, WGM, WGN, SCH>), lds);
-    hipLaunchKernelGGL((k_conv_split<BM, BN, WGM, WGN, SCH>), grid, dim3(64 * WGM * WGN), lds, st, p, (const uint16_t*)p.w);
+    const auto kernel = k_conv_split<BM, BN, WGM, WGN, SCH + (BATCH ? SPL_BATCH : 0)>;
+    if (lds > 64 * 1024) NDET_RAISE_LDS(kernel, lds);
+    hipLaunchKernelGGL(kernel, grid, dim3(64 * WGM * WGN), lds, st, p, (const uint16_t*)p.w);
     return NDET_OK;
 }
 template <int BM, int BN, int WGM, int WGN>
 static int split_launch_tile(const Conv3dParams& p, hipStream_t st, const char* fn) {
-    return with_scheme(conv_scheme(p), [&](auto s) { return split_launch_tile_sch<BM, BN, WGM, WGN, decltype(s)::value>(p, st, fn); });
+    return with_scheme(conv_scheme(p), [&](auto s) { return split_launch_tile_sch<BM, BN, WGM, WGN, decltype(s)::value, false>(p, st, fn); });
+}
+template <int BM, int BN, int WGM, int WGN>
+static int split_launch_tile_batch(const Conv3dParams& p, int, hipStream_t st, const char* fn) {      // (the rows carry the batch: p.M)
+    return with_scheme(conv_scheme(p), [&](auto s) { return split_launch_tile_sch<BM, BN, WGM, WGN, decltype(s)::value, true>(p, st, fn); });
 }
 template <int NT16, int WGN>
 static int split_launch_halo_any(const Conv3dParams& p, hipStream_t st, const char* fn) {
-    return with_scheme(conv_scheme(p), [&](auto s) { return split_launch_halo<NT16, WGN, decltype(s)::value>(p, st, fn); });
+    return with_scheme(conv_scheme(p), [&](auto s) { return split_launch_halo<NT16, WGN, decltype(s)::value, 4, false>(p, 1, st, fn); });
+}
+template <int NT16, int WGN>
+static int split_launch_halo_any_batch(const Conv3dParams& p, int batch, hipStream_t st, const char* fn) {
+    return with_scheme(conv_scheme(p), [&](auto s) { return split_launch_halo<NT16, WGN, decltype(s)::value, 4, true>(p, batch, st, fn); });
 }
 // tile 3258: <4,4> with eight producer waves (16 waves: 128 registers each -- the three-plane form does not fit and keeps four)
 static int split_launch_halo_p8(const Conv3dParams& p, hipStream_t st, const char* fn) {
     return with_scheme(conv_scheme(p), [&](auto s) {
         constexpr int SCH = decltype(s)::value;
-        return split_launch_halo<4, 4, SCH, SCH == 0 ? 4 : 8>(p, st, fn);
+        return split_launch_halo<4, 4, SCH, SCH == 0 ? 4 : 8, false>(p, 1, st, fn);
+    });
+}
+static int split_launch_halo_p8_batch(const Conv3dParams& p, int batch, hipStream_t st, const char* fn) {
+    return with_scheme(conv_scheme(p), [&](auto s) {
+        constexpr int SCH = decltype(s)::value;
+        return split_launch_halo<4, 4, SCH, SCH == 0 ? 4 : 8, true>(p, batch, st, fn);
     });
 }
 
@@ -1740,25 +1806,26 @@ extern "C" int ndet_amax_slot_floats(void) { return NDET_AMAX_SUB * NDET_AMAX_ST
 struct ConvTile {
     int id, rows, cols, flags;
     int (*launch)(const Conv3dParams&, hipStream_t, const char*);
+    int (*launch_batch)(const Conv3dParams&, int batch, hipStream_t, const char*);      // null: the tile takes one volume (ndet_conv_split_batch)
 };
 static const ConvTile CONV_TILES[] = {
     // the unified tiles: LDS-staged epilogue, and the same tiles storing straight from the accumulators
-    {64, 64, 64, NDET_TILE_ORDER2, split_launch_tile<64, 64, 2, 2>},
-    {128, 128, 128, NDET_TILE_ORDER2, split_launch_tile<128, 128, 2, 2>},
-    {12864, 128, 64, NDET_TILE_ORDER2, split_launch_tile<128, 64, 2, 2>},
-    {100064, 64, 64, NDET_TILE_ORDER2 | NDET_TILE_DIRECT, split_launch_tile<64, 64, 2, 2>},
-    {100128, 128, 128, NDET_TILE_ORDER2 | NDET_TILE_DIRECT, split_launch_tile<128, 128, 2, 2>},
-    {112864, 128, 64, NDET_TILE_ORDER2 | NDET_TILE_DIRECT, split_launch_tile<128, 64, 2, 2>},
+    {64, 64, 64, NDET_TILE_ORDER2, split_launch_tile<64, 64, 2, 2>, split_launch_tile_batch<64, 64, 2, 2>},
+    {128, 128, 128, NDET_TILE_ORDER2, split_launch_tile<128, 128, 2, 2>, split_launch_tile_batch<128, 128, 2, 2>},
+    {12864, 128, 64, NDET_TILE_ORDER2, split_launch_tile<128, 64, 2, 2>, split_launch_tile_batch<128, 64, 2, 2>},
+    {100064, 64, 64, NDET_TILE_ORDER2 | NDET_TILE_DIRECT, split_launch_tile<64, 64, 2, 2>, split_launch_tile_batch<64, 64, 2, 2>},
+    {100128, 128, 128, NDET_TILE_ORDER2 | NDET_TILE_DIRECT, split_launch_tile<128, 128, 2, 2>, split_launch_tile_batch<128, 128, 2, 2>},
+    {112864, 128, 64, NDET_TILE_ORDER2 | NDET_TILE_DIRECT, split_launch_tile<128, 64, 2, 2>, split_launch_tile_batch<128, 64, 2, 2>},
     // wave-specialised 128 x 256, and its persistent forms: eight consumer waves (two per SIMD, 64 x 64 each); 64-row tiles
-    {128256, 128, 256, NDET_TILE_ORDER2, split_launch_ws},
-    {129256, 128, 256, 0, split_launch_wsp<128, 4>},
-    {129257, 128, 256, 0, split_launch_wsp<128, 8>},
-    {129064, 64, 256, 0, split_launch_wsp<64, 4>},
+    {128256, 128, 256, NDET_TILE_ORDER2, split_launch_ws, split_launch_ws_batch},
+    {129256, 128, 256, 0, split_launch_wsp<128, 4>, nullptr},
+    {129257, 128, 256, 0, split_launch_wsp<128, 8>, nullptr},
+    {129064, 64, 256, 0, split_launch_wsp<64, 4>, nullptr},
     // halo-stationary 128-voxel patch; the 256-column ones own whole rows of a 256-channel layer
-    {3128, 128, 128, 0, split_launch_halo_any<4, 2>},
-    {3256, 128, 256, NDET_TILE_OWNS_ROWS, split_launch_halo_any<8, 2>},
-    {3257, 128, 256, NDET_TILE_OWNS_ROWS, split_launch_halo_any<4, 4>},
-    {3258, 128, 256, NDET_TILE_OWNS_ROWS, split_launch_halo_p8},
+    {3128, 128, 128, 0, split_launch_halo_any<4, 2>, split_launch_halo_any_batch<4, 2>},
+    {3256, 128, 256, NDET_TILE_OWNS_ROWS, split_launch_halo_any<8, 2>, split_launch_halo_any_batch<8, 2>},
+    {3257, 128, 256, NDET_TILE_OWNS_ROWS, split_launch_halo_any<4, 4>, split_launch_halo_any_batch<4, 4>},
+    {3258, 128, 256, NDET_TILE_OWNS_ROWS, split_launch_halo_p8, split_launch_halo_p8_batch},
 };
 static const ConvTile* conv_tile(int id) {
     for (const ConvTile& t : CONV_TILES)
@@ -1775,14 +1842,31 @@ extern "C" int ndet_conv_tile_info(int tile, int* rows, int* cols, int* flags) {
     return NDET_OK;
 }
 
+extern "C" int ndet_conv_halo_patch(int tile, int D, int H, int W, const int* kernel, int* patch, int* looped) {
+    const char* fn = "ndet_conv_halo_patch";
+    NDET_REQUIRE(kernel && patch && looped, NDET_E_INVALID, "%s: null pointer", fn);
+    const ConvTile* t = conv_tile(tile);
+    NDET_REQUIRE(t && (tile == 3128 || (t->flags & NDET_TILE_OWNS_ROWS)), NDET_E_INVALID, "%s: tile %d is not a halo tile", fn, tile);
+    NDET_REQUIRE(D > 0 && H > 0 && W > 0 && kernel[0] >= 1 && kernel[1] >= 1 && kernel[2] >= 1, NDET_E_INVALID, "%s: sizes must be positive", fn);
+    Conv3dParams p{};
+    p.OD = D; p.OH = H; p.OW = W; p.kd = kernel[0]; p.kh = kernel[1]; p.kw = kernel[2];
+    HaloGeom g;
+    NDET_REQUIRE(halo_geometry(p, t->cols == 128 ? 400 : 224, g), NDET_E_UNSUPPORTED, "%s: no patch shape fits the halo tile", fn);
+    patch[0] = 1 << g.ltd; patch[1] = 1 << g.lth; patch[2] = 1 << g.ltw;
+    *looped = g.KDL > 1 ? 1 : 0;
+    return NDET_OK;
+}
+
 // keep_partials (weight-gradient GEMMs): a split-K launch leaves its partial sums in the workspace and ndet_wgrad_to_torch adds them up (same fixed
 // order) on its way to torch's layout -- one launch and one pass over dW fewer per layer
-int conv_split_launch(Conv3dParams& p, int tile, bool keep_partials, hipStream_t st, const char* fn) {
+// batch > 1 (ndet_conv_split_batch): p.M holds the rows of all `batch` volumes, p.D / p.OD one volume's extents; the tile's batch launcher runs
+static int conv_split_launch_n(Conv3dParams& p, int tile, bool keep_partials, int batch, hipStream_t st, const char* fn) {
     p.nt = (p.splits <= 1 || p.transposed) && (int64_t)p.M * p.Cout * 4 * (p.transposed ? 8 : 1) >= conv_nt_bytes() ? 1 : 0;
     const int64_t big_tiles = (int64_t)((p.M + 127) / 128) * ((p.Cout + 127) / 128);
     if (tile == 0) tile = (big_tiles >= 192 && p.Cout >= 128) ? 128 : 64;
     const ConvTile* t = conv_tile(tile);
     NDET_REQUIRE(t, NDET_E_INVALID, "%s: unknown tile %d", fn, tile);
+    NDET_REQUIRE(batch == 1 || t->launch_batch, NDET_E_UNSUPPORTED, "%s: tile %d takes one volume per launch", fn, tile);
     p.direct = (t->flags & NDET_TILE_DIRECT) ? 1 : 0;
     NDET_REQUIRE(!p.direct || (!p.transposed && p.splits == 1 && p.Cout % 32 == 0 && ((int64_t)p.M + 128) * p.Cout * 4 < ((int64_t)1 << 32)),
                  NDET_E_UNSUPPORTED, "%s: the direct epilogue needs splits == 1, no transposition, Cout %% 32 == 0 and an output below 4 GB", fn);
@@ -1801,11 +1885,14 @@ int conv_split_launch(Conv3dParams& p, int tile, bool keep_partials, hipStream_t
                 (t->flags & NDET_TILE_ORDER2)) p.order = 2;
         }
     }
-    const int rc = t->launch(p, st, fn);
+    const int rc = batch == 1 ? t->launch(p, st, fn) : t->launch_batch(p, batch, st, fn);
     if (rc != NDET_OK) return rc;
     NDET_CHECK_LAUNCH(fn);
     if (keep_partials && p.splits > 1) return NDET_OK;
     return conv_splitk_reduce_launch(p, st, fn);
+}
+int conv_split_launch(Conv3dParams& p, int tile, bool keep_partials, hipStream_t st, const char* fn) {
+    return conv_split_launch_n(p, tile, keep_partials, 1, st, fn);
 }
 
 // packed fp32 weights (taps, Cout, Cin) -> three bf16 planes tiled per K step, (taps, Cin/32, 3, Cout, 32):
@@ -2066,8 +2153,8 @@ static int conv_geometry(Conv3dParams& p, const int* kernel, const int* stride, 
 // arith (0 bf16x3, 1 fp16 pair, 2 bf16) -> Conv3dParams::max_order; the kernels' SCH template argument is numbered as arith (conv_scheme)
 static int max_order_of(int arith) { return arith == 0 ? 2 : (arith == 1 ? 1 : 0); }
 
-extern "C" int ndet_conv_split(const NdetConvArgs* a, void* stream) {
-    const char* fn = "ndet_conv_split";
+// ndet_conv_split (batch 1) and ndet_conv_split_batch
+static int conv_split_entry(const NdetConvArgs* a, int batch, void* stream, const char* fn) {
     NDET_REQUIRE(a && a->size == (int32_t)sizeof(NdetConvArgs), NDET_E_INVALID, "%s: the argument block must be set up with size = %d", fn,
                  (int)sizeof(NdetConvArgs));
     NDET_REQUIRE(a->arith >= 0 && a->arith <= 2, NDET_E_INVALID, "%s: arith must be 0 (bf16x3), 1 (fp16 pair) or 2 (bf16)", fn);
@@ -2093,6 +2180,13 @@ extern "C" int ndet_conv_split(const NdetConvArgs* a, void* stream) {
         NDET_REQUIRE(a->splits <= 1 && !a->residual && !a->relu && !a->transposed, NDET_E_UNSUPPORTED,
                      "%s: the chained projection takes no split-K, residual, ReLU or transposition", fn);
     }
+    if (batch != 1) {
+        NDET_REQUIRE(batch >= 1, NDET_E_INVALID, "%s: batch=%d must be at least 1", fn, batch);
+        NDET_REQUIRE(!a->w_amax && !a->keep_partials && !a->residual_up2 && !a->map_w && !a->map_b && !a->map_out, NDET_E_UNSUPPORTED,
+                     "%s: a batch takes no w_amax, keep_partials, upsampled residual or chained projection", fn);
+        const ConvTile* t = conv_tile(a->tile);
+        NDET_REQUIRE(!t || t->launch_batch, NDET_E_UNSUPPORTED, "%s: tile %d (persistent) takes one volume per launch", fn, a->tile);
+    }
     NDET_REQUIRE(a->in && a->w_planes && a->out, NDET_E_INVALID, "%s: null pointer", fn);
     NDET_REQUIRE(a->D > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
     NDET_REQUIRE((a->scale == nullptr) == (a->shift == nullptr), NDET_E_INVALID, "%s: scale and shift go together", fn);
@@ -2113,14 +2207,17 @@ extern "C" int ndet_conv_split(const NdetConvArgs* a, void* stream) {
         p.transposed = 1;
         p.kd = p.kh = p.kw = 2; p.sd = p.sh = p.sw = 2; p.pd = p.ph = p.pw = 0;
         p.OD = 2 * p.D; p.OH = 2 * p.H; p.OW = 2 * p.W;
-        NDET_REQUIRE((int64_t)p.OD * p.OH * p.OW < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: tensor too large", fn);
-        p.M = p.D * p.H * p.W;
+        NDET_REQUIRE((int64_t)batch * p.OD * p.OH * p.OW < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: tensor too large", fn);
+        p.M = batch * p.D * p.H * p.W;
         p.splits = 1; p.partial = nullptr;
         p.res_up2 = 0; p.RH = p.RW = 0;
-        return conv_split_launch(p, a->tile, false, (hipStream_t)stream, fn);
+        return conv_split_launch_n(p, a->tile, false, batch, (hipStream_t)stream, fn);
     }
     const int rc = conv_geometry(p, a->kernel, a->stride, a->pad, fn);
     if (rc != NDET_OK) return rc;
+    NDET_REQUIRE((int64_t)batch * p.M < ((int64_t)1 << 31) && (int64_t)batch * p.D * p.H * p.W * p.Cin < ((int64_t)1 << 40), NDET_E_UNSUPPORTED,
+                 "%s: the %d volumes of the batch are too large together", fn, batch);
+    p.M *= batch;      // rows of the whole batch; p.D / p.OD stay one volume's
     p.splits = a->splits < 1 ? 1 : a->splits;
     p.res_up2 = (a->residual && a->residual_up2) ? 1 : 0;
     p.RH = (p.OH + 1) / 2; p.RW = (p.OW + 1) / 2;
@@ -2128,8 +2225,10 @@ extern "C" int ndet_conv_split(const NdetConvArgs* a, void* stream) {
     const int iters = p.kd * p.kh * p.kw * (p.Cin / CBK);
     NDET_REQUIRE(p.splits <= iters, NDET_E_INVALID, "%s: splits=%d exceeds the %d K steps", fn, p.splits, iters);
     NDET_REQUIRE(p.splits == 1 || a->workspace != nullptr, NDET_E_INVALID, "%s: split-K needs a workspace", fn);
-    return conv_split_launch(p, a->tile, a->keep_partials != 0, (hipStream_t)stream, fn);
+    return conv_split_launch_n(p, a->tile, a->keep_partials != 0, batch, (hipStream_t)stream, fn);
 }
+extern "C" int ndet_conv_split(const NdetConvArgs* a, void* stream) { return conv_split_entry(a, 1, stream, "ndet_conv_split"); }
+extern "C" int ndet_conv_split_batch(const NdetConvArgs* a, int batch, void* stream) { return conv_split_entry(a, batch, stream, "ndet_conv_split_batch"); }
 
 template <int MID, int SCH>
 static int chain_launch(const Conv3dParams& p, const ConvChain& c, hipStream_t st, const char* fn) {

@@ -237,16 +237,19 @@ class nerfdet(BaseDetector):
         return self._detect_tail(x, valids, img_metas, defer, guarded, img.device,
                                  lambda: self._repeat_exact(img, img_metas, depth, ray_batch, evaluate_nerf))
 
-    def _detect_tail(self, x, valids, img_metas, defer, guarded, device, repeat):
+    def _detect_tail(self, x, valids, img_metas, defer, guarded, device, repeat, raws=None):
         """neck_3d outputs -> detections (nerfdet.py:292-311), shared by simple_test and streaming.SceneStream.detect: the fused head with its
-        single device-to-host copy where it applies.  ``guarded``: a set range-guard word calls ``repeat()`` for the answer instead."""
+        single device-to-host copy where it applies.  ``guarded``: a set range-guard word calls ``repeat()`` for the answer instead.  ``raws``: the
+        scene's head convolutions when a batched launch has computed them already (streaming.SceneGroup.detect(batched=True)); the tail then
+        starts behind them."""
         from . import conv3d
         for m in img_metas:
             m.setdefault("box_type_3d", DepthInstance3DBoxes)
         if hasattr(self.bbox_head, "can_fuse") and self.bbox_head.can_fuse(x) and len(img_metas) == 1:
-            bbox_list = self.bbox_head.simple_test_fused(x, valids.float(), img_metas, defer=defer)
+            bbox_list = self.bbox_head.simple_test_fused(x, valids.float(), img_metas, defer=defer, raws=raws)
         else:
-            bbox_list = self.bbox_head.get_bboxes(*self.bbox_head(x), valids.float(), img_metas)
+            outs = self.bbox_head(x) if raws is None else self.bbox_head.outputs_from_raws(raws)
+            bbox_list = self.bbox_head.get_bboxes(*outs, valids.float(), img_metas)
             if defer:
                 ready = bbox_list
                 bbox_list = lambda: ready

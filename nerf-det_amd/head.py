@@ -95,6 +95,26 @@ class ScanNetImVoxelHeadV2(nn.Module):
         o = outs[0].unsqueeze(0) if len(outs) == 1 else torch.stack(outs)
         return o[:, :1], torch.exp(scale(o[:, 1:1 + n_reg])), o[:, 1 + n_reg:]
 
+    def raws_batched(self, x):
+        """Per level the fused ``centerness | reg | cls`` convolution of :meth:`forward_single_hip` over the WHOLE batch in one launch:
+        x[l] (B,C,X,Y,Z), a view of channels-last memory -> (B,X,Y,Z,1 + n_reg + n_classes).  Scene b's contiguous slice ``raw[b]`` is what
+        :meth:`simple_test_fused` (``raws=``) and :meth:`outputs_from_raws` take."""
+        pk = packed([self.centerness_conv, self.reg_conv, self.cls_conv])
+        raws = []
+        for f in x:
+            t = f.float().permute(0, 2, 3, 4, 1)
+            raws.append(conv3d_ndhwc(carry_amax(f, t if t.is_contiguous() else t.contiguous()), pk, amax=False))
+        return raws
+
+    def outputs_from_raws(self, raws):
+        """What :meth:`forward` returns for one scene, from that scene's precomputed per-level raws (X,Y,Z,1 + n_reg + n_classes)."""
+        n_reg = self.reg_conv.out_channels
+        outs = []
+        for raw, scale in zip(raws, self.scales):
+            o = raw.permute(3, 0, 1, 2).unsqueeze(0)
+            outs.append((o[:, :1], torch.exp(scale(o[:, 1:1 + n_reg])), o[:, 1 + n_reg:]))
+        return tuple(map(list, zip(*outs)))
+
     def forward(self, x):
         outs = [self.forward_single(f, s) for f, s in zip(x, self.scales)]
         return tuple(map(list, zip(*outs)))
@@ -164,8 +184,11 @@ class ScanNetImVoxelHeadV2(nn.Module):
         return (x[0].is_cuda and not self.training and not torch.is_grad_enabled() and x[0].shape[1] % 32 == 0
                 and x[0].shape[0] == 1 and self.reg_conv.out_channels == 6)
 
-    def simple_test_fused(self, x, valid, img_metas, defer=False):
-        """``defer=True``: everything is enqueued, the picks travel to a pinned host buffer asynchronously, and a ``finish()`` callable is
+    def simple_test_fused(self, x, valid, img_metas, defer=False, raws=None):
+        """``raws``: the scene's per-level fused head convolutions (X,Y,Z,25) when the caller has run them already (:meth:`raws_batched`: one
+        launch per level for several scenes); everything from the decode onward is this scene's as usual.
+
+        ``defer=True``: everything is enqueued, the picks travel to a pinned host buffer asynchronously, and a ``finish()`` callable is
         returned that waits for that copy and builds the detections -- a server keeps a second scene's launches queued (on another
         stream) while this one drains.  Default: the detections themselves.
 
@@ -187,7 +210,8 @@ class ScanNetImVoxelHeadV2(nn.Module):
         gx0, gy0, gz0 = valid.shape[-3:]
         v0 = valid.reshape(gx0, gy0, gz0).float().contiguous()
         bests, labels, boxes = [], [], []
-        raws = [conv3d_ndhwc(to_ndhwc(carry_amax(f, f[0]) if f.dtype == torch.float32 else f[0].float()), pk, amax=False) for f in x]  # (X,Y,Z,25) each
+        if raws is None:
+            raws = [conv3d_ndhwc(to_ndhwc(carry_amax(f, f[0]) if f.dtype == torch.float32 else f[0].float()), pk, amax=False) for f in x]  # (X,Y,Z,25) each
         grids = [tuple(r.shape[:3]) for r in raws]
         facs = [gx0 // g[0] for g in grids]
         org = np.float32(np.asarray(meta["lidar2img"]["origin"]))

@@ -36,7 +36,8 @@ class BasicBlock3dV2(nn.Module):
         return _bn(self.norm2, conv_forward(self.conv2, out), relu=True, residual=idt)       # relu(norm2(.) + identity), imvoxelnet.py:60-66
 
     def forward_ndhwc(self, x):
-        """x (D,H,W,C) -> (D',H',W',C'); eval-mode BN folded, ``relu(bn2(conv2(.)) + identity)`` in one epilogue."""
+        """x (D,H,W,C) -> (D',H',W',C'), or a batch (B,D,H,W,C) -> (B,D',H',W',C') with one launch per layer; eval-mode BN folded,
+        ``relu(bn2(conv2(.)) + identity)`` in one epilogue."""
         y = conv3d_ndhwc(x, packed([self.conv1], self.norm1), relu=1)
         idt = x if self.stride == 1 else conv3d_ndhwc(x, packed([self.downsample[0]], self.downsample[1]), amax=False)
         return conv3d_ndhwc(y, packed([self.conv2], self.norm2), residual=idt, relu=1)
@@ -149,6 +150,31 @@ class FastIndoorImVoxelNeck(nn.Module):
                 per_level[i].append(carry_amax(o, o.permute(3, 0, 1, 2)))
         # (one scene: the views keep the maximum the convolution left behind, so the head's first launch needs no pass of its own)
         return [carry_amax(lv[0], lv[0].unsqueeze(0)) if len(lv) == 1 else torch.stack(lv) for lv in per_level]
+
+    def forward_batched(self, x):
+        """:meth:`forward_hip` with ONE launch per layer for the whole batch (conv3d_ndhwc on (B,X,Y,Z,C): ndet_conv_split_batch), nothing
+        stacked: (B,C,X,Y,Z) -> 3 x (B,128,X_i,Y_i,Z_i), logical NCDHW views of channels-last results that keep the maximum their launch left
+        behind.  In the fp16-pair arithmetic the scenes of the batch share every layer's per-tensor scale."""
+        t = x.float().permute(0, 2, 3, 4, 1)
+        outs = self._levels_ndhwc(carry_amax(x, t if t.is_contiguous() else t.contiguous()))
+        return [carry_amax(o, o.permute(0, 4, 1, 2, 3)) for o in outs]
+
+    def _levels_ndhwc(self, t):
+        """The network on channels-last memory, one volume (X,Y,Z,C) or a batch (B,X,Y,Z,C): the per-level outputs (..., X_i,Y_i,Z_i, 128),
+        finest first.  The layer sequence is the one :meth:`forward_hip` walks per scene."""
+        downs, outs = [], [None] * self.n_scales
+        for i in range(self.n_scales):
+            for blk in getattr(self, f"down_layer_{i}"):
+                t = blk.forward_ndhwc(t)
+            downs.append(t)
+        for i in range(self.n_scales - 1, -1, -1):
+            if i < self.n_scales - 1:
+                up = getattr(self, f"up_block_{i + 1}")
+                t = conv3d_ndhwc(t, packed([up[0]], up[1]), relu=1)
+                t = conv3d_ndhwc(t, packed([up[3]], up[4]), residual=downs[i], relu=2)      # x = down_outs[i] + up(x): ReLU first, then the skip add
+            ob = getattr(self, f"out_block_{i}")
+            outs[i] = conv3d_ndhwc(t, packed([ob[0]], ob[1]), relu=1)
+        return outs
 
     def forward_library(self, x):
         downs = []

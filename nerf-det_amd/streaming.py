@@ -321,7 +321,8 @@ class SceneGroup:
     the detector are the group's.  One :meth:`add_views` call runs the backbone once over one chunk of k views (1 .. ops.GROUP_VIEWS_MAX) per
     listed scene and folds every chunk into its scene's state with one grouped accumulate (ops.scene_accumulate_group); one :meth:`detect`
     finishes the listed scenes with one grouped density finish, one sigma-MLP call, one grouped volume finish and one neck_3d call over the
-    batch (which neck_3d walks scene by scene), queues every scene's tail and then waits once.  ``scenes``: None (all scenes, in order) or a list of distinct scene indices -- cameras do not
+    batch (which neck_3d walks scene by scene; ``detect(batched=True)``: one launch per neck layer and head level for all the listed scenes, which
+    then share the 3D part's fp16-pair scales), queues every scene's tail and then waits once.  ``scenes``: None (all scenes, in order) or a list of distinct scene indices -- cameras do not
     tick together, so a call may serve a subset.
 
     What is exact: a scene's state after a grouped accumulate is bit-equal to ops.scene_accumulate on that scene alone (sums and counts),
@@ -524,14 +525,31 @@ class SceneGroup:
             vol, valid = self._volumes(scenes)
         return [(vol[i], valid[i]) for i in range(len(scenes))]
 
-    def detect(self, scenes=None):
+    def _can_batch(self, vol: Tensor) -> bool:
+        """Would neck_3d and the head take their HIP inference paths on ``vol`` in an arithmetic that has batched launches?"""
+        det = self.det
+        neck, head = det.neck_3d, det.bbox_head
+        return (conv3d.ARITHMETIC in conv3d.SPLIT_FAMILY and hasattr(neck, "forward_batched") and hasattr(head, "raws_batched")
+                and vol.is_cuda and not neck.training and not head.training and not torch.is_grad_enabled() and vol.shape[1] % 32 == 0
+                and head.centerness_conv.in_channels % 32 == 0)
+
+    def detect(self, scenes=None, batched: bool = False):
         """Detections of the listed scenes over their views so far: a list with, per scene, what ``SceneStream.detect()[0]`` returns
         (``dict(boxes_3d, scores_3d, labels_3d)``).  No state is changed.  neck_3d runs once on the scenes' volumes as one batch; every scene's
-        tail is queued before the first result is collected, so the host waits once for the queue, not once per scene.  neck_3d and the
-        tails are still launches per scene (neck_3d walks its batch scene by scene), so the fp16-pair scales of the 3D part are each
+        tail is queued before the first result is collected, so the host waits once for the queue, not once per scene.  By default neck_3d and
+        the tails are still launches per scene (neck_3d walks its batch scene by scene), so the fp16-pair scales of the 3D part are each
         scene's own.  The listed scenes share the stream's range-guard word: when it comes back set with any scene's picks, the whole
         call is repeated on bf16x3 from the finished volumes (``conv3d.guard_trips`` counts it once), so no f16x2 result of a tripped
-        launch gets out."""
+        launch gets out.
+
+        ``batched=True`` with more than one listed scene: the finished volumes go through neck_3d and the head's convolutions as ONE batch --
+        one launch per layer and level for all the scenes (``neck_3d.forward_batched``, ``bbox_head.raws_batched``: ndet_conv_split_batch), one
+        amax pass for the volume batch; every scene's tail (decode, selection, NMS) then takes its scene's slice, queued before the host waits
+        as above.  The scenes of such a call SHARE the fp16-pair scales of neck_3d and the head, so a scene's detections depend (within the
+        chunking contract: same labels in the same order, scores and boxes to 1e-4) on the scenes it is listed with; the volumes and states
+        stay bit-equal.  A set guard word repeats the call exactly as the unbatched call is repeated (per scene, on bf16x3): a tripped
+        batched call returns a tripped unbatched call's results.  One listed scene, the "f32" arithmetic, or a neck / head that would not
+        take its HIP inference path: the unbatched path, bit for bit."""
         scenes = self._need_views(scenes)
         n = len(scenes)
         det = self.det
@@ -541,13 +559,16 @@ class SceneGroup:
             guarded = conv3d.ARITHMETIC == "f16x2" and vol.is_cuda
             if guarded:
                 conv3d.guard_begin(dev)
-            x = det.neck_3d(vol)
+            batched = bool(batched) and n > 1 and self._can_batch(vol)
+            x = det.neck_3d.forward_batched(vol) if batched else det.neck_3d(vol)
+            raws = det.bbox_head.raws_batched(x) if batched else None
             metas = [[dict(self.metas[s])] for s in scenes]
             pending, word_rides = [], True
             for i in range(n):
                 xi = x if n == 1 else [lvl[i:i + 1] for lvl in x]
                 word_rides = word_rides and hasattr(det.bbox_head, "can_fuse") and det.bbox_head.can_fuse(xi)
-                pending.append(det._detect_tail(xi, valid[i:i + 1], metas[i], True, guarded, dev, lambda: _TRIPPED))
+                pending.append(det._detect_tail(xi, valid[i:i + 1], metas[i], True, guarded, dev, lambda: _TRIPPED,
+                                                raws=[r[i] for r in raws] if batched else None))
             # a tail that is not the fused one does not carry the guard word with its picks: read the word once for all of them
             tripped = guarded and not word_rides and conv3d.guard_tripped(dev)
             results = [finish() for finish in pending]

@@ -15,13 +15,13 @@ the generic sampler over a concatenated copy; scene.render of one target view ne
 maps; and the bank's bytes per view.  The calls of a comparison alternate inside one loop.
     python tools/time_streaming.py --render [--reps 20 --warmup 3]
 With --group 1,4,8,16 it times scene groups (det.begin_scenes): for every S, group.add_views of S x 1 and S x 5 views against S separate
-SceneStream.add_views calls of the same chunks, and group.detect() against S separate detect() calls (one after the other, and all queued
+SceneStream.add_views calls of the same chunks, and group.detect() against group.detect(batched=True) and S separate detect() calls (one after the other, and all queued
 with defer=True before the first is collected) with every scene holding the workload's 50 views -- the compared calls alternating inside
 one loop -- plus the group's state size and the peak allocation of building a group, adding 5 views per scene and detecting once.
     python tools/time_streaming.py --group 1,4,8,16 [--reps 20 --warmup 3]
 With --group-window S:W[,S:W...] it times windowed groups (det.begin_scenes(metas, window=W)): for every configuration S scenes with full
 windows of W single-view chunks -- group.add_views of S x 1 views against S windowed SceneStream.add_views calls and against the
-unwindowed group's; group.detect() against the S windowed streams' detect(defer=True) calls, all queued before the first is collected, and
+unwindowed group's; group.detect() against group.detect(batched=True), the S windowed streams' detect(defer=True) calls, all queued before the first is collected, and
 against the unwindowed group's; the two grouped ring finishes alone against S calls of each single-scene ring finish -- the compared calls
 alternating inside one loop -- plus the finish and sigma-MLP spans of one detect(), the pool's size and the peak allocations of
 sliding a window once and detecting.
@@ -160,11 +160,12 @@ def group_mode(det, img, dn, meta, sizes, reps, warmup, dev):
             pending = [st.detect(defer=True) for st in streams]
             return [f() for f in pending]
 
-        fns = {f"group_detect_S{S}_ms": group.detect, f"separate_detect_S{S}_ms": lambda: [st.detect() for st in streams],
-               f"separate_deferred_detect_S{S}_ms": deferred}
+        fns = {f"group_detect_S{S}_ms": group.detect, f"group_detect_batched_S{S}_ms": lambda: group.detect(batched=True),
+               f"separate_detect_S{S}_ms": lambda: [st.detect() for st in streams], f"separate_deferred_detect_S{S}_ms": deferred}
         med, span = timed_alternating(fns, reps, warmup)
         for name in fns:
             res[name], res[name + "_min_max"] = med[name], span[name]
+        res[f"detect_S{S}_group_over_batched"] = med[f"group_detect_S{S}_ms"] / med[f"group_detect_batched_S{S}_ms"]
         res[f"detect_S{S}_separate_over_group"] = med[f"separate_detect_S{S}_ms"] / med[f"group_detect_S{S}_ms"]
         res[f"detect_S{S}_deferred_over_group"] = med[f"separate_deferred_detect_S{S}_ms"] / med[f"group_detect_S{S}_ms"]
         res[f"group_S{S}_state_mb"] = sum(t.numel() * t.element_size() for st in group.group.states
@@ -227,7 +228,8 @@ def group_window_mode(det, img, dn, meta, configs, reps, warmup, dev):
         bias = wgroup._lin.bias
         alpha = torch.rand(S * wgroup.pool.n_voxels, device=dev)
         a1 = alpha[:wgroup.pool.n_voxels]
-        fns2 = {"window_group_detect_ms": wgroup.detect, "window_streams_deferred_detect_ms": deferred, "unwindowed_group_detect_ms": ugroup.detect,
+        fns2 = {"window_group_detect_ms": wgroup.detect, "window_group_detect_batched_ms": lambda: wgroup.detect(batched=True),
+                "window_streams_deferred_detect_ms": deferred, "unwindowed_group_detect_ms": ugroup.detect,
                 "density_finish_group_ring_ms": lambda: ops.density_finish_group_ring(wgroup.pool, bias),
                 "density_finish_ring_x_S_ms": lambda: [ops.density_finish_ring(st._segs, bias) for st in streams],
                 "volume_finish_group_ring_ms": lambda: ops.volume_finish_group_ring(wgroup.pool, alpha),
@@ -239,6 +241,7 @@ def group_window_mode(det, img, dn, meta, configs, reps, warmup, dev):
             res[f"{tag}_{k}"], res[f"{tag}_{k}_min_max"] = med[k], span[k]
         res[f"{tag}_add_views_streams_over_window_group"] = med["window_streams_add_views_ms"] / med["window_group_add_views_ms"]
         res[f"{tag}_detect_streams_over_window_group"] = med["window_streams_deferred_detect_ms"] / med["window_group_detect_ms"]
+        res[f"{tag}_detect_window_group_over_batched"] = med["window_group_detect_ms"] / med["window_group_detect_batched_ms"]
         res[f"{tag}_density_finish_separate_over_group"] = med["density_finish_ring_x_S_ms"] / med["density_finish_group_ring_ms"]
         res[f"{tag}_volume_finish_separate_over_group"] = med["volume_finish_ring_x_S_ms"] / med["volume_finish_group_ring_ms"]
         # the launches of one windowed-group detect(): spans of the finishes and of the sigma-MLP
