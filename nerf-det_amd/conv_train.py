@@ -196,6 +196,23 @@ def _to_torch_layout(dw_rows: Tensor, taps: int, cin: int, cout: int, kernel, sp
     return out
 
 
+def implicit_plan(taps: int, cin: int, cout: int, lo: int, f16: bool) -> tuple:
+    """``(bm, bn, splits, keep)`` of the implicit weight-gradient launch (csrc/conv_split_kernels.hip::k_wgrad_split) for a layer of ``taps`` taps,
+    ``cin`` -> ``cout`` channels over ``lo`` output voxels: the GEMM tile (rows = (tap, input channel), columns = output channels), the split-K factor
+    and whether the partials go straight to ndet_wgrad_to_torch.  ``f16``: the fp16-pair arithmetic.  Pure arithmetic: no tensor, no GPU."""
+    bm = 128 if cin % 128 == 0 else 64
+    bn = 256 if (f16 and bm == 128 and cout % 256 == 0 and taps * (cin // 128) >= 32) else (128 if cout > 64 else 64)      # (the library's own choice: ndet_wgrad_split)
+    tiles = (taps * cin // bm) * ((cout + bn - 1) // bn)
+    ksteps = (lo + 31) // 32                                # the kernel steps the contraction by 32 voxels
+    # ~1 000 workgroups of the 128 x 128 tile (768 left the FPN's 36-tile layer at 24 splits: 1 505 us against 1 260 at 32), ~800 of the 128 x 256
+    # tile (the neck's 54-tile layers: 16 splits 439 us, 24 splits 477 us) -- tools/diag/wgrad_ab.py
+    splits = max(1, min(32, ksteps // 8, -(-(768 if bn == 256 else 1024) // tiles)))
+    if splits >= 6:
+        splits = min(32, (splits + 7) // 8 * 8)           # a multiple of 8: one K split per XCD at a time (k_wgrad_split: the tiles of a split share its slice of x and dy in that L2)
+    keep = f16 and splits > 1 and taps <= 27       # the partials go straight to ndet_wgrad_to_torch: no reduction pass, no (m, cout) intermediate
+    return bm, bn, splits, keep
+
+
 def weight_grad(x: Tensor, g: Tensor, kernel: Sequence[int], stride: int = 1, pads=None, implicit=None) -> Tensor:
     """dW of a convolution of uniform stride (same-padded unless ``pads`` says otherwise).  x (D,H,W,Cin), g (OD,OH,OW,Cout) contiguous fp32
     channels-last (2D: D = batch, kernel (kh,kw)) -> (Cout, Cin, *kernel) in torch's layout."""
@@ -235,18 +252,9 @@ def weight_grad(x: Tensor, g: Tensor, kernel: Sequence[int], stride: int = 1, pa
         # form writes and re-reads taps x the input (707 MB for a 3x3x3 layer at 40x40x16x256); on small grids and 1x1 layers the staged
         # GEMM runs on the faster tiles and wins (tools/bench_wgrad.py)
         planes = pk.planes_f16[0] if f16 else C.split_planes(pk)
-        bm = 128 if cin % 128 == 0 else 64
-        bn = 256 if (f16 and bm == 128 and cout % 256 == 0 and taps * (cin // 128) >= 32) else (128 if cout > 64 else 64)      # (the library's own choice: ndet_wgrad_split)
-        tiles = (taps * cin // bm) * ((cout + bn - 1) // bn)
-        ksteps = lrow // 32
-        # ~1 000 workgroups of the 128 x 128 tile (768 left the FPN's 36-tile layer at 24 splits: 1 505 us against 1 260 at 32), ~800 of the 128 x 256
-        # tile (the neck's 54-tile layers: 16 splits 439 us, 24 splits 477 us) -- tools/diag/wgrad_ab.py
-        splits = max(1, min(32, ksteps // 8, -(-(768 if bn == 256 else 1024) // tiles)))
-        if splits >= 6:
-            splits = min(32, (splits + 7) // 8 * 8)           # a multiple of 8: one K split per XCD at a time (k_wgrad_split: the tiles of a split share its slice of x and dy in that L2)
+        _, _, splits, keep = implicit_plan(taps, cin, cout, lo, f16)       # (the tile is the library's to launch; it makes the same choice)
         m = taps * cin
         ws = torch.empty((splits * m * cout,), dtype=torch.float32, device=x.device) if splits > 1 else None
-        keep = f16 and splits > 1 and taps <= 27       # the partials go straight to ndet_wgrad_to_torch: no reduction pass, no (m, cout) intermediate
         dw = None if keep else torch.empty((m, cout), dtype=torch.float32, device=x.device)
         _lib.check(_lib.load().ndet_wgrad_split(_ptr(x), d, h, w, cin, i3(*k3), i3(*s3), i3(*pads), _ptr(planes), cout, lrow, splits, C.ARITH_ID[arith],
                                                 _ptr(x_slot), _ptr(dy_slot), _ptr(ws), _ptr(ws if keep else dw), int(keep), st), "wgrad_split")
