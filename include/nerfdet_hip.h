@@ -478,6 +478,29 @@ typedef struct NdetBankView {
 int ndet_ray_view_stats_bank(const float* pts, int n_points, const NdetBankView* views_dev, int n_views, float img_h, float img_w, int H,
                              int W, int d, int hf, int wf, float* global_feat, uint8_t* pixel_mask, int* view_count, void* stream);
 
+/* The view banks one grouped sampler call serves, a HOST block (size = sizeof(NdetBankGroupSel)) that rides by value in the kernel
+ * arguments (1032 bytes; with the library's prefix over n_points 1288 of the 4096 a launch may carry):
+ *   n          listed scenes, 1 .. NDET_GROUP_MAX; grid.y of the launch.
+ *   views[i]   listed scene i's DEVICE table of NdetBankView rows, oldest view first, 8-byte aligned.
+ *   n_views[i] its rows, >= 1.
+ *   n_points[i] its sample points, >= 1: rows [sum_{j<i} n_points[j], + n_points[i]) of the call's point array and of every output. */
+typedef struct NdetBankGroupSel {
+    int32_t size;
+    int32_t n;
+    const NdetBankView* views[NDET_GROUP_MAX];
+    int32_t n_views[NDET_GROUP_MAX];
+    int32_t n_points[NDET_GROUP_MAX];
+} NdetBankGroupSel;
+
+/* ndet_ray_view_stats_bank for several view banks in one launch -- Projector.compute() (model_utils/projection.py:91-151) +
+ * compute_mask_points() (render_ray.py:71-93) + the concat / pixel mask of render_ray.py:299-303 per listed scene.  pts
+ * (sum n_points, 3), global_feat (sum n_points, 2*(3+d)), pixel_mask and view_count (sum n_points; view_count may be NULL): listed scene
+ * i's rows follow scene i-1's.  The map, image and camera sizes are the call's, shared by every scene; d % 4 == 0, d <= 128; fewer than
+ * 2^31 points in all.  Every check runs on the host before the launch and reads no device memory.  Listed scene i's output rows are
+ * ndet_ray_view_stats_bank's over views[i] and its points bit for bit, whatever the other scenes, the subset or its order. */
+int ndet_ray_view_stats_bank_group(const float* pts, const NdetBankGroupSel* sel, float img_h, float img_w, int H, int W, int d, int hf,
+                                   int wf, float* global_feat, uint8_t* pixel_mask, int* view_count, void* stream);
+
 /* A7 exact API form. Replaces Projector.compute(), projection.py:91-151: rgb_feat (P, n_views, 3+d) and
  * mask (P, n_views) fp32 0/1, materialised like the reference. Same inputs as ndet_ray_view_stats. */
 int ndet_project_sample(const float* pts, int n_points, const float* KE, int n_views, float img_h, float img_w,

@@ -68,6 +68,11 @@ class NdetGroupRingSel(ctypes.Structure):  # the scenes one grouped ring finish 
                 ("n_views", ctypes.c_int32 * NDET_GROUP_MAX)]
 
 
+class NdetBankGroupSel(ctypes.Structure):  # the view banks one grouped sampler call serves: include/nerfdet_hip.h::NdetBankGroupSel, 1032 bytes
+    _fields_ = [("size", ctypes.c_int32), ("n", ctypes.c_int32), ("views", _P * NDET_GROUP_MAX), ("n_views", ctypes.c_int32 * NDET_GROUP_MAX),
+                ("n_points", ctypes.c_int32 * NDET_GROUP_MAX)]
+
+
 _G = ctypes.POINTER(NdetDepthGate)
 _GR = ctypes.POINTER(NdetGroupRingSel)
 _S = ctypes.POINTER(NdetSceneAccum)
@@ -125,6 +130,7 @@ SIGNATURES = {
     "ndet_ray_view_stats_packed": ([_P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int64, c_int64,
                                     _P, _P, _P, _P], c_int),
     "ndet_ray_view_stats_bank": ([_P, c_int, _P, c_int, c_float, c_float, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P], c_int),
+    "ndet_ray_view_stats_bank_group": ([_P, ctypes.POINTER(NdetBankGroupSel), c_float, c_float, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P], c_int),
     "ndet_ray_view_stats_packed_bwd": ([_P, _P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, c_int, c_int64, c_int64, _P, _P], c_int),
     "ndet_project_sample": ([_P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, c_int64, c_int64, c_int64,
                              _P, c_int, c_int, c_int, c_int64, c_int64, _P, _P, _P], c_int),

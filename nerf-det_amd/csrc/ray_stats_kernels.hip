@@ -14,7 +14,8 @@
 //   * the variance is accumulated in the same walk with the first gathered value as pivot:
 //         sum_near (v - mean)^2 = sum (v - c)^2 - 2 (mean - c) sum (v - c) + n_near (mean - c)^2,   + n_far mean^2
 //     (shifted-data form: conditioned like the two-pass sum when the pivot lies inside the data, no second gather).
-// k_ray_stats_bank (below) runs the same expressions over a view bank: any number of views, each behind its own pointers.
+// k_ray_stats_bank (below) runs the same expressions over a view bank: any number of views, each behind its own pointers;
+// k_ray_stats_bank_group runs that walk for the banks of several scenes in one launch (grid.y = scene).
 // Compiled with -ffp-contract=off.
 #include "ndet_common.hpp"
 
@@ -537,6 +538,178 @@ extern "C" int ndet_ray_view_stats_bank(const float* pts, int n_points, const Nd
     NDET_REQUIRE(blocks * 4 * G < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many points", fn);
     hipLaunchKernelGGL(k_ray_stats_bank, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pts, n_points, views_dev, n_views, img_h,
                        img_w, H, W, d, hf, wf, G, global_feat, pixel_mask, view_count);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// view banks of a scene group: k_ray_stats_bank's walk for several banks in one launch.  grid.y = listed scene, grid.x = the largest
+// per-scene block count; a block past its scene's count leaves before it touches LDS or a barrier.  A block serves ONE scene: its
+// points tile by 4 G from that scene's own row 0, so the view count, the rounds, the count pass and both barrier positions are uniform
+// within a block and differ between the blocks of a launch -- the whole difference from k_ray_stats_bank, whose walk is copied here
+// (not shared as a template: that kernel's register figures stay what they were).  The selection rides by value in the kernel
+// arguments with the host's prefix over n_points (the scene's first row of the concatenated points and outputs).
+// ------------------------------------------------------------------------------------------------
+struct RbGroupFirst {
+    int32_t row[NDET_GROUP_MAX];
+};
+
+__global__ __launch_bounds__(256) void k_ray_stats_bank_group(const float* __restrict__ pts_all, NdetBankGroupSel sel, RbGroupFirst first,
+                                                              float img_h, float img_w, int H, int W, int d, int hf, int wf, int G,
+                                                              float* __restrict__ glob_all, uint8_t* __restrict__ pixel_mask_all,
+                                                              int* __restrict__ view_count_all) {
+    extern __shared__ float2 s_bank[];
+    const int sc = blockIdx.y;                         // listed scene: block-uniform (scalar loads from the kernel arguments)
+    const int n_points = sel.n_points[sc];
+    if ((int64_t)blockIdx.x * 4 * G >= (int64_t)n_points) return;   // grid.x padding: the whole block leaves, before LDS and barriers
+    const int n_views = sel.n_views[sc];
+    const NdetBankView* __restrict__ views = sel.views[sc];
+    const int64_t row0 = first.row[sc];
+    const int nch = 3 + d;
+    const float* __restrict__ pts = pts_all + row0 * 3;
+    float* __restrict__ glob = glob_all + row0 * 2 * nch;
+    uint8_t* __restrict__ pixel_mask = pixel_mask_all + row0;
+    int* __restrict__ view_count = view_count_all ? view_count_all + row0 : nullptr;
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lps = (d >> 2) + 1;                      // lanes per sample: [image quad | d/4 feature quads]
+    const int g = lane / lps, sub = lane - g * lps;
+    const int p_base = (blockIdx.x * 4 + wave) * G;
+    float2* rec = s_bank + (size_t)wave * G * RB_VIEWS;
+    const float** s_ptr = reinterpret_cast<const float**>(s_bank + (size_t)4 * G * RB_VIEWS);   // [0,64) feature maps, [64,128) images
+    const int rounds = (n_views + RB_VIEWS - 1) / RB_VIEWS;
+
+    // ---- count pass (more than one round): valid and near views of every sample over all the scene's views ----
+    int cnt = 0, n_near = 0;
+    unsigned long long my_valid = 0ull, my_near = 0ull;
+    if (rounds > 1) {
+        for (int r = 0; r < rounds; ++r) {
+            rb_project_round<false>(pts, n_points, p_base, G, g, lane, views, r * RB_VIEWS + lane, n_views, img_h, img_w, H, W, hf, wf, rec,
+                                    my_valid, my_near);
+            cnt += __popcll(my_valid);
+            n_near += __popcll(my_near);
+        }
+    }
+
+    const int my_p = p_base + g;
+    const bool on = g < G && my_p < n_points;
+    const bool is_rgb = sub == 0;
+    const int fq = sub - 1;                                   // feature quad of this lane
+    const int Hs = is_rgb ? H : hf, Ws = is_rgb ? W : wf;
+    const int rpitch = is_rgb ? W * 4 : wf * d, pix = is_rgb ? 4 : d;
+    const int poff = is_rgb ? 0 : 4 * fq;
+    const float** my_ptr = s_ptr + (is_rgb ? RB_VIEWS : 0);
+    const float2* myrec = rec + (on ? g : 0) * RB_VIEWS;
+    float denom = (float)cnt + 1e-8f;
+    float wgt = 1.0f / denom;                                 // mask / (sum(mask) + 1e-8), render_ray.py:83
+    RsAcc a;
+    a.acc = a.q = a.s1 = a.piv = make_float4(0.f, 0.f, 0.f, 0.f);
+    a.have = false;
+
+    // ---- walk pass: round by round, lanes over views, then lanes over (sample, channel quad); rounds is the block's ----
+    for (int r = 0; r < rounds; ++r) {
+        if (r > 0) __syncthreads();                           // the round before has read its records and pointers
+        const int v = r * RB_VIEWS + lane;
+        rb_project_round<true>(pts, n_points, p_base, G, g, lane, views, v, n_views, img_h, img_w, H, W, hf, wf, rec, my_valid, my_near);
+        if (wave < 2) s_ptr[wave * RB_VIEWS + lane] = v < n_views ? (wave == 0 ? views[v].feat : views[v].rgb4) : nullptr;
+        if (rounds == 1) {                                    // a single round: its own ballots are the counts
+            cnt = __popcll(my_valid);
+            n_near = __popcll(my_near);
+            denom = (float)cnt + 1e-8f;
+            wgt = 1.0f / denom;
+        }
+        __syncthreads();
+        unsigned long long m = on ? my_near : 0ull;
+        const unsigned long long vm = my_valid;
+        while (__ballot(m != 0ull) != 0ull) {                 // until every sample of the wave has walked its near views
+            const bool h0 = m != 0ull;
+            const int b0 = h0 ? __builtin_ctzll(m) : 0;
+            m = h0 ? (m & (m - 1ull)) : 0ull;
+            const bool h1 = m != 0ull;
+            const int b1 = h1 ? __builtin_ctzll(m) : 0;
+            m = h1 ? (m & (m - 1ull)) : 0ull;
+            const float2 r0 = h0 ? myrec[b0] : make_float2(0.f, 0.f);
+            const float2 r1 = h1 ? myrec[b1] : make_float2(0.f, 0.f);
+            const float* v0 = h0 ? my_ptr[b0] + poff : nullptr;
+            const float* v1 = h1 ? my_ptr[b1] + poff : nullptr;
+            const RsTaps t0 = rs_taps(r0.x, r0.y, Hs, Ws, rpitch, pix), t1 = rs_taps(r1.x, r1.y, Hs, Ws, rpitch, pix);
+            float4 a00 = make_float4(0.f, 0.f, 0.f, 0.f), a01 = a00, a10 = a00, a11 = a00, c00 = a00, c01 = a00, c10 = a00, c11 = a00;
+            if (h0) {
+                a00 = *reinterpret_cast<const float4*>(v0 + t0.o00);
+                a01 = *reinterpret_cast<const float4*>(v0 + t0.o01);
+                a10 = *reinterpret_cast<const float4*>(v0 + t0.o10);
+                a11 = *reinterpret_cast<const float4*>(v0 + t0.o11);
+            }
+            if (h1) {
+                c00 = *reinterpret_cast<const float4*>(v1 + t1.o00);
+                c01 = *reinterpret_cast<const float4*>(v1 + t1.o01);
+                c10 = *reinterpret_cast<const float4*>(v1 + t1.o10);
+                c11 = *reinterpret_cast<const float4*>(v1 + t1.o11);
+            }
+            if (h0) rs_take(a, rs_blend(a00, a01, a10, a11, t0), (vm >> b0) & 1ull, wgt);
+            if (h1) rs_take(a, rs_blend(c00, c01, c10, c11, t1), (vm >> b1) & 1ull, wgt);
+        }
+    }
+    if (!on) return;
+    const float nn = (float)n_near, nf = (float)(n_views - n_near);
+    const float4 mean = a.acc;
+    float4 ev;
+    ev.x = expf(-(rs_var_sum(a.q.x, a.s1.x, a.piv.x, mean.x, nn, nf) / denom));
+    ev.y = expf(-(rs_var_sum(a.q.y, a.s1.y, a.piv.y, mean.y, nn, nf) / denom));
+    ev.z = expf(-(rs_var_sum(a.q.z, a.s1.z, a.piv.z, mean.z, nn, nf) / denom));
+    ev.w = expf(-(rs_var_sum(a.q.w, a.s1.w, a.piv.w, mean.w, nn, nf) / denom));
+    float* row = glob + (int64_t)my_p * 2 * nch;              // cat([mean, exp(-var)], dim=-1), render_ray.py:303
+    if (is_rgb) {
+        row[0] = mean.x; row[1] = mean.y; row[2] = mean.z;
+        row[nch + 0] = ev.x; row[nch + 1] = ev.y; row[nch + 2] = ev.z;
+        pixel_mask[my_p] = cnt > 1 ? 1 : 0;                   // render_ray.py:301
+        if (view_count) view_count[my_p] = cnt;
+    } else {
+        const int c = 3 + 4 * fq;
+        row[c + 0] = mean.x; row[c + 1] = mean.y; row[c + 2] = mean.z; row[c + 3] = mean.w;
+        row[nch + c + 0] = ev.x; row[nch + c + 1] = ev.y; row[nch + c + 2] = ev.z; row[nch + c + 3] = ev.w;
+    }
+}
+
+extern "C" int ndet_ray_view_stats_bank_group(const float* pts, const NdetBankGroupSel* sel, float img_h, float img_w, int H, int W, int d,
+                                              int hf, int wf, float* global_feat, uint8_t* pixel_mask, int* view_count, void* stream) {
+    const char* fn = "ndet_ray_view_stats_bank_group";
+    static_assert(sizeof(NdetBankGroupSel) == 8 + 16 * NDET_GROUP_MAX, "NdetBankGroupSel is 1032 bytes");
+    static_assert(sizeof(NdetBankGroupSel) + sizeof(RbGroupFirst) + 128 <= 4096, "the kernel arguments stay under 4 KiB");
+    NDET_REQUIRE(pts && sel && global_feat && pixel_mask, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(sel->size == (int32_t)sizeof(NdetBankGroupSel), NDET_E_INVALID,
+                 "%s: NdetBankGroupSel.size %d != %d (caller built against another layout)", fn, sel->size, (int)sizeof(NdetBankGroupSel));
+    NDET_REQUIRE(sel->n >= 1 && sel->n <= NDET_GROUP_MAX, NDET_E_INVALID, "%s: %d listed scenes, must be 1 .. %d", fn, sel->n, NDET_GROUP_MAX);
+    NDET_REQUIRE(H > 1 && W > 1 && hf > 1 && wf > 1 && d > 0, NDET_E_INVALID, "%s: bad sizes", fn);
+    for (int i = 0; i < sel->n; ++i) {
+        NDET_REQUIRE(sel->views[i], NDET_E_INVALID, "%s: null pointer (view table of listed scene %d)", fn, i);
+        NDET_REQUIRE(sel->n_views[i] >= 1 && sel->n_points[i] >= 1, NDET_E_INVALID, "%s: bad sizes (listed scene %d: %d views, %d points)", fn, i,
+                     sel->n_views[i], sel->n_points[i]);
+    }
+    NDET_REQUIRE(d % 4 == 0 && d <= 128, NDET_E_UNSUPPORTED, "%s: d=%d must be a multiple of 4, at most 128", fn, d);
+    for (int i = 0; i < sel->n; ++i)
+        NDET_REQUIRE(((uintptr_t)sel->views[i] & 7) == 0, NDET_E_UNSUPPORTED, "%s: the view table of listed scene %d must be 8-byte aligned", fn, i);
+    NDET_REQUIRE(((uintptr_t)global_feat & 3) == 0, NDET_E_UNSUPPORTED, "%s: global_feat must be 4-byte aligned", fn);
+    NDET_REQUIRE((int64_t)hf * wf * d < ((int64_t)1 << 31) && (int64_t)H * W * 4 < ((int64_t)1 << 31), NDET_E_UNSUPPORTED,
+                 "%s: a source view exceeds 2^31 floats", fn);
+    const int lps = d / 4 + 1;
+    int G = 64 / lps;
+    const int ptr_bytes = 2 * RB_VIEWS * (int)sizeof(const float*);
+    while (G > 1 && 4 * G * RB_VIEWS * (int)sizeof(float2) + ptr_bytes > 64 * 1024) --G;
+    const int lds = 4 * G * RB_VIEWS * (int)sizeof(float2) + ptr_bytes;
+    RbGroupFirst first;
+    int64_t total = 0, max_blocks = 0;
+    for (int i = 0; i < NDET_GROUP_MAX; ++i) first.row[i] = 0;
+    for (int i = 0; i < sel->n; ++i) {
+        first.row[i] = (int32_t)total;
+        const int64_t blocks = ((int64_t)sel->n_points[i] + 4 * G - 1) / (4 * G);
+        NDET_REQUIRE(blocks * 4 * G < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many points (listed scene %d)", fn, i);
+        total += sel->n_points[i];
+        NDET_REQUIRE(total < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many points (%lld in all)", fn, (long long)total);
+        if (blocks > max_blocks) max_blocks = blocks;
+    }
+    hipLaunchKernelGGL(k_ray_stats_bank_group, dim3((unsigned)max_blocks, (unsigned)sel->n), dim3(256), lds, (hipStream_t)stream, pts, *sel, first,
+                       img_h, img_w, H, W, d, hf, wf, G, global_feat, pixel_mask, view_count);
     NDET_CHECK_LAUNCH(fn);
     return NDET_OK;
 }

@@ -276,17 +276,19 @@ class nerfdet(BaseDetector):
         from .streaming import SceneStream
         return SceneStream(self, img_meta, window=window, keep_views=keep_views)
 
-    def begin_scenes(self, img_metas, window=None):
+    def begin_scenes(self, img_metas, window=None, keep_views=False):
         """A :class:`~nerfdet_amd.streaming.SceneGroup` for 1 .. 64 scenes streamed together, each with its own intrinsic, origin and extrinsics
         (``img_shape``, ``ori_shape``, the voxel grid and the detector are shared): ``group.add_views(img, denorm, metas, scenes=None)`` runs the
         backbone once over one chunk of k views per listed scene and folds them into the scenes' states with one grouped accumulate;
         ``group.detect(scenes=None)`` returns, per listed scene, what ``begin_scene(...).detect()[0]`` returns.  ``window=S`` (1 .. 64) gives
         every scene a sliding window of its last S chunks, as ``begin_scene(img_meta, window=S)`` gives one scene: each listed scene's chunk
         fills a state of its own, scenes evict independently (``group.drop_oldest(k, scenes)`` forgets chunks explicitly), and ``detect``
-        finishes the listed windows with two grouped ring finishes.  No view bank (``keep_views=`` / rendering), one image size and grid
-        per group, inference only, not graphed."""
+        finishes the listed windows with two grouped ring finishes.  ``keep_views=True`` gives every scene a view bank that follows its
+        states (``group.banks``): ``group.render_rays(ray_o, ray_d, scenes=None, batched=False)`` / ``group.render(ray_batches, ...)`` then
+        render novel views of the listed scenes with one grouped sampler launch per pass, each scene bit for bit what
+        ``begin_scene(..., keep_views=True)`` renders from the same maps.  One image size and grid per group, inference only, not graphed."""
         from .streaming import SceneGroup
-        return SceneGroup(self, img_metas, window=window)
+        return SceneGroup(self, img_metas, window=window, keep_views=keep_views)
 
     def forward_test_async(self, img, img_metas, **kwargs):
         """Serving form of :meth:`forward_test`: every launch of the scene is queued on the current stream and a ``finish()`` callable is

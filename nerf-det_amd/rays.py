@@ -4,6 +4,7 @@
 csrc/ray_kernels.hip.  The fused path (:func:`ray_view_stats`) never builds the (R,S,n_views,35) tensor."""
 from __future__ import annotations
 
+import ctypes
 from collections import OrderedDict
 from ctypes import c_void_p
 from typing import List, Optional, Tuple
@@ -265,6 +266,66 @@ def ray_view_stats_bank(xyz: Tensor, bank: ViewBank):
         _lib.load().ndet_ray_view_stats_bank(_ptr(pts), n, _ptr(table), n_v, h, w, H, W, d, hf, wf, _ptr(glob), _ptr(pm), _ptr(vc), _stream(xyz)),
         "ray_view_stats_bank"), bytes=nbytes, kind="hbm")
     return glob.view(*shape, -1), pm.view(*shape), vc.view(*shape)
+
+
+def ray_view_stats_bank_group(xyz_list, banks):
+    """:func:`ray_view_stats_bank` for several banks in ONE launch (k_ray_stats_bank_group): ``xyz_list[i]`` (..., 3) are the sample points
+    of ``banks[i]``; returns a list of ``(globalfeat, pixel_mask, view_count)``, one per bank, each shaped as :func:`ray_view_stats_bank`
+    shapes it and a view into the call's concatenated buffers.  The banks share map, image and camera sizes and the device (else
+    ValueError); 1 .. 64 banks, a single one goes through the same entry point.  Every bank's outputs are :func:`ray_view_stats_bank`'s
+    over that bank and its points bit for bit, whatever the other banks or their order.  No bank is changed; as with one bank, the call
+    and the banks' evictions belong on one stream (:class:`ViewBank`)."""
+    xyz_list = list(xyz_list)
+    glob, pm, vc, _ = bank_group_stats(xyz_list, banks)
+    out, at = [], 0
+    for x in xyz_list:
+        shape, c = x.shape[:-1], x.numel() // 3
+        out.append((glob[at:at + c].view(*shape, -1), pm[at:at + c].view(*shape), vc[at:at + c].view(*shape)))
+        at += c
+    return out
+
+
+def bank_group_stats(xyz_list, banks):
+    """The launch of :func:`ray_view_stats_bank_group` with its buffers whole: ``(globalfeat (P, 2*(3+d)), pixel_mask (P,), view_count (P,),
+    points (P, 3))`` over the ``P = sum of points`` rows, bank i's rows after bank i-1's."""
+    xyz_list, banks = list(xyz_list), list(banks)
+    n = len(banks)
+    if len(xyz_list) != n or not 1 <= n <= _lib.NDET_GROUP_MAX:
+        raise ValueError(f"ray_view_stats_bank_group: {len(xyz_list)} point sets for {n} banks (1 .. {_lib.NDET_GROUP_MAX})")
+    for x in xyz_list:
+        if not x.is_cuda:
+            raise RuntimeError("nerfdet_amd.rays: tensors must live on the GPU (no CPU fallback)")
+    tables = [b.table() for b in banks]          # RuntimeError for an empty bank
+    s0 = banks[0].segments[0]
+    dev = s0.feat.device
+    for i, (x, b) in enumerate(zip(xyz_list, banks)):
+        s = b.segments[0]
+        if s.feat.shape[1:] != s0.feat.shape[1:] or s.rgb4.shape[1:] != s0.rgb4.shape[1:] or s.img_hw != s0.img_hw:
+            raise ValueError(f"ray_view_stats_bank_group: bank {i}'s map, image or camera size differs from bank 0's")
+        if s.feat.device != dev or x.device != dev:
+            raise ValueError(f"ray_view_stats_bank_group: bank {i} or its points live on another device than bank 0")
+        if x.shape[-1] != 3 or x.numel() == 0:
+            raise ValueError(f"ray_view_stats_bank_group: points {tuple(x.shape)} of bank {i} must be (..., 3) with at least one point")
+    _, hf, wf, d = s0.feat.shape
+    H, W = s0.rgb4.shape[1], s0.rgb4.shape[2]
+    h, w = s0.img_hw
+    flat = [x.to(torch.float32).reshape(-1, 3) for x in xyz_list]
+    counts = [f.shape[0] for f in flat]
+    pts = flat[0].contiguous() if n == 1 else torch.cat(flat, dim=0)
+    total = pts.shape[0]
+    sel = _lib.NdetBankGroupSel()
+    sel.size, sel.n = ctypes.sizeof(_lib.NdetBankGroupSel), n
+    for i, ((table, n_v), c) in enumerate(zip(tables, counts)):
+        sel.views[i], sel.n_views[i], sel.n_points[i] = table.data_ptr(), n_v, c
+    glob = torch.empty((total, 2 * (3 + d)), dtype=torch.float32, device=dev)
+    pm = torch.empty((total,), dtype=torch.bool, device=dev)
+    vc = torch.empty((total,), dtype=torch.int32, device=dev)
+    n_v_all = sum(t[1] for t in tables)
+    nbytes = 4 * (n_v_all * 4 * H * W + n_v_all * d * hf * wf + 2 * (3 + d) * total)
+    trace.span("k_ray_stats_bank_group", lambda: check(
+        _lib.load().ndet_ray_view_stats_bank_group(_ptr(pts), ctypes.byref(sel), h, w, H, W, d, hf, wf, _ptr(glob), _ptr(pm), _ptr(vc),
+                                                   _stream(pts)), "ray_view_stats_bank_group"), bytes=nbytes, kind="hbm")
+    return glob, pm, vc, pts
 
 
 class Projector:

@@ -26,7 +26,14 @@ one by rounding.  In a window a chunk's bank segment leaves with its state.  Ren
 backbone pass, one guard read and one grouped accumulate per ``add_views`` call over one chunk per listed scene (ops.scene_accumulate_group),
 one grouped density finish, one sigma-MLP call and one grouped volume finish per ``detect`` (ops.density_finish_group / volume_finish_group), then
 neck_3d and the tails scene by scene, all queued before the host waits.  Each scene's state holds the bits
-``ops.scene_accumulate`` leaves for that scene alone; a group of one scene is a ``SceneStream`` bit for bit.  Groups keep no view bank.
+``ops.scene_accumulate`` leaves for that scene alone; a group of one scene is a ``SceneStream`` bit for bit.
+
+``nerfdet.begin_scenes(metas, keep_views=True)`` (windowed or not) gives every scene of the group a view bank that follows its states
+(``group.banks``): ``group.render_rays(ray_o, ray_d, scenes=None, batched=False)`` and ``group.render(ray_batches, ...)`` render the listed
+scenes with ONE sampler launch per pass over all their banks (rays.ray_view_stats_bank_group), every scene bit for bit what a
+``SceneStream`` holding the same maps renders; ``batched=True`` also runs the NeRF MLP and the compositing once per pass (shared fp16-pair
+scales: masks bit-equal, rgb to 1e-4, depth to 1e-4 x far).  4 (hf wf cm + 4 H W) + 64 bytes a view held and scene; one stream for
+renders and evictions (rays.ViewBank).
 
 ``nerfdet.begin_scenes(metas, window=S)`` gives every scene of the group a sliding window of S chunks: each listed scene's chunk fills a
 state of its own through the same grouped accumulate (ops.scene_accumulate_group_ring), scenes evict independently, and ``detect`` finishes
@@ -340,14 +347,26 @@ class SceneGroup:
     sigma-MLP call and one grouped volume ring finish, whose outputs are ops.density_finish_ring / volume_finish_ring's per scene bit
     for bit: a windowed group of one scene is a windowed :class:`SceneStream` bit for bit, and a dropped chunk leaves no trace.
 
-    No view bank: ``keep_views=`` / rendering for groups is out of scope, as are scenes of different image sizes or grids in one group,
-    training, and the graphed path."""
+    ``keep_views``: also keep every scene's views in a view bank of its own (``banks[s]``, a rays.ViewBank; None without it) so that
+    :meth:`render_rays` / :meth:`render` work; a detector with ``render_testing=True`` is accepted only then.  :meth:`add_views` makes
+    every listed scene's segment from its rows of the mapped map and of ``denorm_images`` before the grouped accumulate
+    (``make_segment`` changes nothing) and pushes them only once it has succeeded; in a windowed group a scene's oldest segment leaves
+    with its oldest state (a full window, :meth:`drop_oldest`), :meth:`reset` clears the listed banks, and a call that raises anywhere
+    leaves every state, window and bank as it was.  After every call a scene's bank holds exactly the chunks its states hold
+    (windowed: ``[seg.n_views for seg in banks[s].segments] == chunk_views[s]``; an unwindowed scene reports its views as one chunk,
+    its bank keeps a segment per call, the totals agree).  4 (hf wf cm + 4 H W) + 64 bytes a view held.  As with one bank, renders and
+    evictions must be issued on ONE stream (rays.ViewBank).
+
+    Out of scope: scenes of different image sizes or grids in one group, training or autograd through the banks, and the graphed path."""
 
     window = None       # None, or the chunks every scene keeps
     pool = None         # ops.SceneGroupRingState of a windowed group
     group = None        # ops.SceneGroupState of an unwindowed one
+    banks = None        # with keep_views one rays.ViewBank per scene, else None
 
-    def __init__(self, det, img_metas, window: Optional[int] = None):
+    def __init__(self, det, img_metas, window: Optional[int] = None, keep_views: bool = False):
+        if not isinstance(keep_views, bool):
+            raise ValueError(f"keep_views must be a bool, got {keep_views!r}")
         if window is not None:
             ops.check_window(window)
         metas = list(img_metas)
@@ -356,8 +375,9 @@ class SceneGroup:
         self._check_shapes(metas[0], metas)
         if det.training:
             raise RuntimeError("SceneGroup is inference only: call det.eval() first")
-        if det.render_testing:
-            raise NotImplementedError("SceneGroup does not render rays (render_testing needs every view's feature map)")
+        if det.render_testing and not keep_views:
+            raise NotImplementedError("SceneGroup does not render rays (render_testing needs every view's feature map): "
+                                      "begin_scenes(img_metas, keep_views=True) keeps them")
         self.det = det
         self.metas = metas
         self.device = next(det.parameters()).device
@@ -369,6 +389,9 @@ class SceneGroup:
             self.group = ops.SceneGroupState(det.n_voxels, lin.in_features, lin.out_features, points, self.device)
         else:
             self.pool = ops.SceneGroupRingState(det.n_voxels, lin.in_features, lin.out_features, points, window, self.device)
+        if keep_views:
+            from .rays import ViewBank
+            self.banks = [ViewBank() for _ in metas]
 
     @staticmethod
     def _check_shapes(first: dict, metas) -> None:
@@ -405,22 +428,39 @@ class SceneGroup:
                 self.group.states[s].reset()
             else:
                 self.pool.drop_oldest(len(self.pool.segs[s]), [s])
+            if self.banks is not None:
+                self.banks[s].clear()
 
     def drop_oldest(self, k: int = 1, scenes=None) -> None:
         """Forget the k oldest chunks of every listed scene of a windowed group (their states are zeroed and kept for the chunks to come).
         The call is refused whole (ValueError) when any listed scene holds fewer than k chunks; ``k = 0`` is allowed."""
         if self.window is None:
             raise ValueError("drop_oldest needs a windowed group: begin_scenes(img_metas, window=S)")
-        self.pool.drop_oldest(k, ops.listed_scenes(self.n_scenes, scenes))
+        scenes = ops.listed_scenes(self.n_scenes, scenes)
+        self.pool.drop_oldest(k, scenes)            # refused whole before any window or bank changes
+        if self.banks is not None:
+            for s in scenes:
+                self.banks[s].drop_oldest(k)
 
-    def _accumulate(self, scenes, *chunk, depth_gate=None) -> None:
+    def _accumulate(self, scenes, *chunk, depth_gate=None, banked=None) -> None:
         """Fold one chunk per listed scene into the scenes' states, or in a windowed group into empty states that join the scenes' windows
-        once the grouped accumulate has succeeded (ops.SceneGroupRingState.accumulate): a call that fails leaves every window as it was."""
+        once the grouped accumulate has succeeded (ops.SceneGroupRingState.accumulate): a call that fails leaves every window as it was.
+        ``banked``: the listed scenes' view-bank segments, made by the caller (rays.ViewBank.make_segment changes nothing); they join
+        their banks only once the states have taken the chunks, and a scene's oldest segment leaves with the oldest state of its full
+        window, so states and banks hold the same chunks."""
         if self.window is None:
             ops.scene_accumulate_group(self.group, scenes, *chunk, depth_gate=depth_gate)
-            return
-        self.pool.accumulate(scenes, lambda states: ops.scene_accumulate_group_ring(self.pool, scenes, *chunk, depth_gate=depth_gate,
-                                                                                   states=states))
+        else:
+            full = [len(self.pool.segs[s]) == self.window for s in scenes]
+            self.pool.accumulate(scenes, lambda states: ops.scene_accumulate_group_ring(self.pool, scenes, *chunk, depth_gate=depth_gate,
+                                                                                       states=states))
+            if banked is not None:
+                for s, was_full in zip(scenes, full):
+                    if was_full:
+                        self.banks[s].drop_oldest(1)
+        if banked is not None:
+            for s, seg in zip(scenes, banked):
+                self.banks[s].push(seg)
 
     def _check_call(self, img: Tensor, denorm_images: Tensor, metas, scenes, depth):
         """Everything add_views refuses, before anything is launched: ``(listed scenes, k)``."""
@@ -456,8 +496,9 @@ class SceneGroup:
         One pass for the whole call: the guard word is cleared, the backbone runs on all the chunks, the word is read back once (one
         synchronisation per call, not per scene), and one grouped accumulate folds every scene's rows into its own state (in a windowed
         group: into a state of its own per listed scene, which then joins that scene's window).  A tripped call's backbone is redone on
-        bf16x3 before any state or window is touched (``conv3d.guard_trips`` counts it once).  A call that is refused leaves every state
-        and window as it was -- also one the backbone refuses: the ``len(scenes) * k`` views share its launches, whose operands address
+        bf16x3 before any state or window is touched (``conv3d.guard_trips`` counts it once).  With ``keep_views`` every listed scene's
+        bank segment is made before the accumulate and joins its bank after it.  A call that is refused leaves every state, window
+        and bank as it was -- also one the backbone refuses: the ``len(scenes) * k`` views share its launches, whose operands address
         at most 2 GB each (200 views of 240 x 320 are too many)."""
         scenes, k = self._check_call(img, denorm_images, metas, scenes, depth)
         n = len(scenes)
@@ -491,7 +532,12 @@ class SceneGroup:
                 d = depth.reshape([-1] + list(depth.shape)[2:]).to(self.device, non_blocking=True)
                 gate = ops.depth_gate(d, self.det.voxel_size, (h, w), (hh, ww))
             proj = ops.compute_projection_group(metas, (stride, 1), self.device)     # the n k projections at both strides: one upload
-            self._accumulate(scenes, feat, mapped, lin.bias, rgb, proj[0], proj[1], depth_gate=gate)
+            # every bank takes its scene's rows of the mapped map as they are accumulated and of the images as extract_feat hands them to
+            # render_rays (uncropped); all the segments are made before any state, window or bank changes
+            banked = None
+            if self.banks is not None:
+                banked = [self.banks[s].make_segment(mapped[i * k:(i + 1) * k], denorm_images[i], metas[i]) for i, s in enumerate(scenes)]
+            self._accumulate(scenes, feat, mapped, lin.bias, rgb, proj[0], proj[1], depth_gate=gate, banked=banked)
 
     def _need_views(self, scenes) -> List[int]:
         scenes = ops.listed_scenes(self.n_scenes, scenes)
@@ -500,6 +546,129 @@ class SceneGroup:
         if empty:
             raise ValueError(f"scenes {empty} have no views yet: call add_views first")
         return scenes
+
+    def _need_banks(self, what: str, scenes) -> List[int]:
+        if self.banks is None:
+            raise RuntimeError(f"{what} needs the scenes' views: begin_scenes(img_metas, keep_views=True)")
+        scenes = ops.listed_scenes(self.n_scenes, scenes)
+        empty = [s for s in scenes if self.banks[s].n_views == 0]
+        if empty:
+            raise RuntimeError(f"scenes {empty} have no views yet: call add_views first")
+        return scenes
+
+    def _render(self, ray_os, ray_ds, scenes: List[int], step: int, batched: bool):
+        """render_ray.py:250-327 (``det=True``, mode 'image') over the listed scenes' banks, at most ``step`` rays per scene and pass:
+        per listed scene ``(rgb, depth, mask)``.  A pass samples every scene that still has rays, runs ONE grouped sampler launch over
+        their banks (rays.ray_view_stats_bank_group) and then the MLP and the compositing per scene, or with ``batched`` once over all
+        the pass's samples."""
+        from . import rays
+        det = self.det
+        n = len(scenes)
+        banks = [self.banks[s] for s in scenes]
+        batched = bool(batched) and n > 1 and conv3d.ARITHMETIC != "f32"
+        outs = [([], [], []) for _ in range(n)]
+        with torch.no_grad():
+            for i0 in range(0, max(o.shape[0] for o in ray_os), step):
+                live = [i for i in range(n) if ray_os[i].shape[0] > i0]
+                dirs, pts, zs = [], [], []
+                for i in live:
+                    o, d = ray_os[i][i0:i0 + step], ray_ds[i][i0:i0 + step]
+                    p, z = rays.sample_along_camera_ray(o, d, det.near_far_range, det.N_samples, det=True)
+                    dirs.append(d)
+                    pts.append(p)
+                    zs.append(z)
+                glob, pm, _, all_pts = rays.bank_group_stats(pts, [banks[i] for i in live])
+                counts = [p.shape[0] for p in pts]
+                if batched and len(live) > 1:
+                    # one MLP call and one compositing call over the pass: the scenes share linear_rows' per-tensor fp16-pair scales
+                    rr, ss = sum(counts), det.N_samples
+                    rgb_pts, density_pts = det.nerf_mlp(all_pts.view(rr, ss, 3), torch.cat(dirs, dim=0), glob.view(rr, ss, -1))
+                    out = rays.raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), torch.cat(zs, dim=0), pm.view(rr, ss))
+                    at = 0
+                    for i, c in zip(live, counts):
+                        for acc, key in zip(outs[i], ("rgb", "depth", "mask")):
+                            acc.append(out[key][at:at + c])
+                        at += c
+                    continue
+                at = 0
+                for i, c, d, p, z in zip(live, counts, dirs, pts, zs):
+                    rows = slice(at * det.N_samples, (at + c) * det.N_samples)
+                    rgb_pts, density_pts = det.nerf_mlp(p, d, glob[rows].view(c, det.N_samples, -1))
+                    out = rays.raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), z, pm[rows].view(c, det.N_samples))
+                    for acc, key in zip(outs[i], ("rgb", "depth", "mask")):
+                        acc.append(out[key])
+                    at += c
+        return [tuple(a[0] if len(a) == 1 else torch.cat(a, dim=0) for a in acc) for acc in outs]
+
+    def render_rays(self, ray_o, ray_d, scenes=None, batched: bool = False):
+        """Render rays against the views the listed scenes hold: ``ray_o``, ``ray_d`` are lists of (R_s, 3) tensors, one pair per listed
+        scene (the counts may differ, each at least 1); returns per listed scene ``dict(rgb (R_s,3), depth (R_s,), mask (R_s,) bool)`` as
+        :meth:`SceneStream.render_rays` does.  Passes of at most ``rays.RENDER_TESTING_RAYS`` rays per scene: every scene that still has
+        rays is sampled (``rays.sample_along_camera_ray(det=True)``), ONE grouped sampler launch serves all of them
+        (rays.ray_view_stats_bank_group, k_ray_stats_bank_group), then ``nerf_mlp`` and ``rays.raw2outputs`` run per scene.  Every
+        scene's result is bit for bit what ``rays.render_rays_func(det=True)`` gives, pass by pass, over the concatenation of that
+        scene's own bank segments -- what a :class:`SceneStream` holding the same maps renders, whatever the other scenes; a group of
+        one scene is ``SceneStream(keep_views=True).render_rays`` bit for bit.
+
+        ``batched=True`` with more than one listed scene: one ``nerf_mlp`` call and one ``raw2outputs`` call over all the scenes'
+        samples of a pass.  The ``linear_rows`` layers of the MLP take a per-tensor fp16-pair scale, which the scenes of a call then
+        share (the fused trunk's scales are per row and do not change): masks stay bit-equal, ``rgb`` agrees with ``batched=False`` to
+        1e-4 absolute and ``depth`` to 1e-4 x ``near_far_range[1]``.  One listed scene, or the "f32" arithmetic: the ``batched=False``
+        path bit for bit.
+
+        Needs ``keep_views=True`` and at least one view in every listed scene (else RuntimeError); wrong list lengths or shapes are a
+        ValueError; everything is refused before anything is launched.  No bank or state is changed.  Renders and evictions
+        (``add_views`` at a full window, ``drop_oldest``, ``reset``) must be issued on ONE stream (rays.ViewBank)."""
+        from . import rays
+        scenes = self._need_banks("render_rays", scenes)
+        ray_o, ray_d = self._check_rays(ray_o, ray_d, len(scenes))
+        res = self._render(ray_o, ray_d, scenes, rays.RENDER_TESTING_RAYS, batched)
+        return [OrderedDict([("rgb", rgb), ("depth", depth), ("mask", mask)]) for rgb, depth, mask in res]
+
+    @staticmethod
+    def _check_rays(ray_o, ray_d, n: int):
+        if isinstance(ray_o, Tensor) or isinstance(ray_d, Tensor):
+            raise ValueError("render_rays takes LISTS of (R,3) origins and directions, one pair per listed scene")
+        ray_o, ray_d = list(ray_o), list(ray_d)
+        if len(ray_o) != n or len(ray_d) != n:
+            raise ValueError(f"render_rays: {len(ray_o)} origin and {len(ray_d)} direction tensors for {n} listed scenes")
+        for i, (o, d) in enumerate(zip(ray_o, ray_d)):
+            if o.dim() != 2 or o.shape[1] != 3 or o.shape[0] < 1 or d.shape != o.shape:
+                raise ValueError(f"render_rays takes (R,3) origins and directions with R >= 1, got {tuple(o.shape)} and {tuple(d.shape)} "
+                                 f"for listed scene {i}")
+        return ray_o, ray_d
+
+    def render(self, ray_batches, scenes=None, batched: bool = False):
+        """Every ray of the target views of one ray batch per listed scene: per scene what :meth:`SceneStream.render` returns
+        (``outputs_coarse.rgb`` (T,h,w,3), ``outputs_coarse.depth`` (T,h,w,1), ``gt_rgb``, ``gt_depth`` -- ``rays.rendering_metrics``
+        applies), through the passes of :meth:`render_rays` with SceneStream.render's pass size,
+        ``N_rand * max(1, RENDER_TESTING_RAYS // N_rand)``; ``batched`` as in :meth:`render_rays`.  One stream, as there."""
+        from . import rays
+        scenes = self._need_banks("render", scenes)
+        ray_batches = list(ray_batches)
+        if len(ray_batches) != len(scenes):
+            raise ValueError(f"render: {len(ray_batches)} ray batches for {len(scenes)} listed scenes")
+        os_, ds_, shapes, gts = [], [], [], []
+        for rb in ray_batches:
+            ray_o, ray_d, gt_rgb, gt_depth = rb["ray_o"], rb["ray_d"], rb["gt_rgb"], rb["gt_depth"]
+            nerf_size = rb["nerf_sizes"][0]
+            view_num = ray_o.shape[1]
+            hh, ww = int(nerf_size[0][0]), int(nerf_size[0][1])
+            ray_o, ray_d, gt_rgb = ray_o.view(-1, 3), ray_d.view(-1, 3), gt_rgb.view(-1, 3)
+            gt_depth = gt_depth.view(-1, 1) if len(gt_depth) != 0 else None
+            assert view_num * hh * ww == ray_o.shape[0]  # render_ray.py:468
+            os_.append(ray_o)
+            ds_.append(ray_d)
+            shapes.append((view_num, hh, ww))
+            gts.append((gt_rgb, gt_depth))
+        os_, ds_ = self._check_rays(os_, ds_, len(scenes))
+        n_rand = self.det.N_rand
+        step = n_rand * max(1, rays.RENDER_TESTING_RAYS // n_rand)       # the passes of rays.render_rays
+        res = self._render(os_, ds_, scenes, step, batched)
+        return [{"outputs_coarse": {"rgb": rgb.view(t, hh, ww, 3), "depth": depth.view(t, hh, ww, 1)},
+                 "gt_rgb": gt_rgb.view(t, hh, ww, 3),
+                 "gt_depth": gt_depth.view(t, hh, ww, 1) if gt_depth is not None else None}
+                for (rgb, depth, _), (t, hh, ww), (gt_rgb, gt_depth) in zip(res, shapes, gts)]
 
     def _volumes(self, scenes: List[int]):
         """``(volume (n,C,X,Y,Z), valid (n,1,X,Y,Z) int64)`` of the listed scenes: grouped K2-finish -> one sigma-MLP call over all their

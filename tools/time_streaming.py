@@ -26,6 +26,11 @@ against the unwindowed group's; the two grouped ring finishes alone against S ca
 alternating inside one loop -- plus the finish and sigma-MLP spans of one detect(), the pool's size and the peak allocations of
 sliding a window once and detecting.
     python tools/time_streaming.py --group-window 8:4,8:8 [--reps 20 --warmup 3]
+With --group S[,S...] --render it times rendering for scene groups (det.begin_scenes(metas, keep_views=True)), every scene holding the
+workload's 50 views in chunks of 5: the grouped bank sampler (one launch for S banks) against S single-bank sampler calls at 2048 and 8192
+rays x 64 samples per scene, checked torch.equal first; group.render_rays of 2048 rays per scene with batched=False and batched=True
+against S SceneStream.render_rays calls; and the banks' bytes per view.  The compared calls alternate inside one loop.
+    python tools/time_streaming.py --group 4,8 --render [--reps 20 --warmup 3]
 """
 import argparse
 import importlib.util
@@ -363,6 +368,67 @@ def render_mode(det, img, dn, meta, rb, reps, warmup, dev):
     return res
 
 
+def group_render_mode(det, img, dn, meta, sizes, reps, warmup, dev):
+    import numpy as np
+    from nerfdet_amd import rays, synth
+    res = {}
+    n_v = img.shape[1]
+    target = synth.batch_to(synth.train_scene(1, tuple(img.shape[-2:]), t_views=1, n_boxes=1, seed=1), dev)
+    rb = det._ray_batch({k: v for k, v in target.items() if k not in ("img", "img_metas")})
+    all_o, all_d = rb["ray_o"].reshape(-1, 3), rb["ray_d"].reshape(-1, 3)
+    for S in sizes:
+        metas = []
+        for i in range(S):
+            m = dict(meta)
+            m["lidar2img"] = dict(meta["lidar2img"], origin=np.asarray(meta["lidar2img"]["origin"], dtype=np.float32) + np.float32([0.05 * i, -0.03 * i, 0.0]))
+            metas.append(m)
+        group = det.begin_scenes([dict(m) for m in metas], keep_views=True)
+        streams = [det.begin_scene(dict(m), keep_views=True) for m in metas]
+        for v0 in range(0, n_v, 5):
+            group.add_views(img[:, v0:v0 + 5].expand(S, -1, -1, -1, -1).contiguous(), dn[:, v0:v0 + 5].expand(S, -1, -1, -1, -1).contiguous(),
+                            [chunk_meta(m, v0, v0 + 5) for m in metas])
+            for st, m in zip(streams, metas):
+                st.add_views(img[:, v0:v0 + 5], dn[:, v0:v0 + 5], chunk_meta(m, v0, v0 + 5))
+        banks = group.banks
+        assert [b.n_views for b in banks] == [n_v] * S and all(len(b.segments) == n_v // 5 for b in banks)
+        res[f"S{S}_bank_bytes_per_view"] = banks[0].nbytes() / banks[0].n_views
+        res[f"S{S}_banks_mb"] = sum(b.nbytes() for b in banks) / 2 ** 20
+        # 1. the sampler alone: one grouped launch against S single-bank launches, every scene with rays of its own
+        for n_rays in (2048, 8192):
+            pts = []
+            for i in range(S):
+                o, d = all_o.roll(-977 * i, 0)[:n_rays], all_d.roll(-977 * i, 0)[:n_rays]
+                pts.append(rays.sample_along_camera_ray(o, d, det.near_far_range, 64, det=True)[0])
+            fns = {"group_ms": lambda: rays.ray_view_stats_bank_group(pts, banks),
+                   "singles_ms": lambda: [rays.ray_view_stats_bank(p, b) for p, b in zip(pts, banks)]}
+            for got, want in zip(fns["group_ms"](), fns["singles_ms"]()):
+                assert all(torch.equal(a, c) for a, c in zip(got, want)), "the grouped sampler differs from the single-bank sampler"
+            med, span = timed_alternating(fns, reps, warmup)
+            for k in fns:
+                res[f"S{S}_stats_{n_rays}r_{k}"], res[f"S{S}_stats_{n_rays}r_{k}_min_max"] = med[k], span[k]
+            res[f"S{S}_stats_{n_rays}r_singles_over_group"] = med["singles_ms"] / med["group_ms"]
+            del pts
+        # 2. a preview per scene: 2048 rays each
+        os_ = [all_o.roll(-977 * i, 0)[:2048].contiguous() for i in range(S)]
+        ds_ = [all_d.roll(-977 * i, 0)[:2048].contiguous() for i in range(S)]
+        fns = {"group_render_rays_ms": lambda: group.render_rays(os_, ds_), "group_render_rays_batched_ms": lambda: group.render_rays(os_, ds_, batched=True),
+               "streams_render_rays_ms": lambda: [st.render_rays(o, d) for st, o, d in zip(streams, os_, ds_)]}
+        plain, bat = fns["group_render_rays_ms"](), fns["group_render_rays_batched_ms"]()
+        for i in range(S):
+            alone = group.render_rays(os_[i:i + 1], ds_[i:i + 1], scenes=[i])[0]
+            assert all(torch.equal(plain[i][k], alone[k]) for k in ("rgb", "depth", "mask")), "a scene's render depends on its neighbours"
+            assert torch.equal(plain[i]["mask"], bat[i]["mask"])
+        res[f"S{S}_batched_max_abs_rgb"] = max(float((a["rgb"] - b["rgb"]).abs().max()) for a, b in zip(plain, bat))
+        res[f"S{S}_batched_max_abs_depth"] = max(float((a["depth"] - b["depth"]).abs().max()) for a, b in zip(plain, bat))
+        med, span = timed_alternating(fns, max(5, reps // 2), warmup)
+        for k in fns:
+            res[f"S{S}_{k}"], res[f"S{S}_{k}_min_max"] = med[k], span[k]
+        res[f"S{S}_render_rays_streams_over_group"] = med["streams_render_rays_ms"] / med["group_render_rays_ms"]
+        res[f"S{S}_render_rays_streams_over_batched"] = med["streams_render_rays_ms"] / med["group_render_rays_batched_ms"]
+        del group, streams, banks
+    return res
+
+
 def peak_mb(fn):
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
@@ -398,6 +464,13 @@ def main():
     rb = det._ray_batch({k: v for k, v in batch.items() if k not in ("img", "img_metas")})
     n_v = img.shape[1]
     res = {}
+    if args.render and args.group:
+        with torch.no_grad():
+            res = group_render_mode(det, img, dn, meta, [int(v) for v in args.group.split(",")], args.reps, args.warmup, dev)
+        for k, v in res.items():
+            print(f"{k:>52}: " + (f"{v:.3e}" if isinstance(v, float) and "max_abs" in k else f"{v:.3f}" if isinstance(v, float) else str(v)))
+        print(json.dumps(res))
+        return
     if args.render:
         with torch.no_grad():
             res = render_mode(det, img, dn, meta, rb, args.reps, args.warmup, dev)
