@@ -822,8 +822,10 @@ int ndet_split_weights_train(const float* w_torch, int taps, int Cout, int Cin, 
  * nn.BatchNorm3d): y = relu?((x - mean) / sqrt(var + eps) * gamma + beta (+ residual)), mean / biased var over the N rows; running_mean /
  * running_var (may be null) updated with `momentum` (unbiased variance), save_mean / save_invstd kept for the backward.  y_amax (may be null): a
  * zeroed amax slot that receives max |y|.  workspace: ndet_bn_workspace_floats(N, C) floats.  Three launches (partial sums, finish, apply); the
- * partial sums are added in a fixed order.  The backward: dx = gamma invstd (g - mean(g) - xhat mean(g xhat)) with g = dy [y > 0] when relu (y = the
- * forward's output), d_residual (may be null) = g, dgamma = sum g xhat, dbeta = sum g; dx_amax as y_amax. */
+ * variance is one pass of sums about a pivot per workgroup (the median of three rows of its slice: no single row decides the conditioning),
+ * left as the slice's (mean, M2) and joined by the pairwise (n, mean, M2) formula; every sum is added in a fixed order.  The backward:
+ * dx = gamma invstd (g - mean(g) - xhat mean(g xhat)) with g = dy [y > 0] when relu (y = the forward's output), d_residual (may be null) = g,
+ * dgamma = sum g xhat, dbeta = sum g; dx_amax as y_amax. */
 int64_t ndet_bn_workspace_floats(int64_t N, int C);
 int ndet_bn_train_forward(const float* x, int64_t N, int C, const float* gamma, const float* beta, float* running_mean, float* running_var,
                           float momentum, float eps, const float* residual, int relu, float* y, float* save_mean, float* save_invstd, float* y_amax,

@@ -3,46 +3,70 @@
 // up / out blocks) folded into the same passes.  The training step of the 3D neck has 15 such layers; through ATen each is a statistics kernel at
 // ~0.6 TB/s, a normalise pass, a separate ReLU, (a separate add,) and the same again backwards -- 1.8 ms + 0.4 ms of ReLU passes per step (profiles/r04_c_train_profile_cfg3_f16x2.txt).
 //
-//   forward   k_bn_stats      per-workgroup partial sums of (x - s) and (x - s)^2 per channel, s = the tensor's first row (a shift that keeps the
-//                             one-pass variance well conditioned); fixed-order partials: deterministic
-//             k_bn_finish     partials -> mean, 1 / sqrt(var + eps) (biased variance, as F.batch_norm), running statistics (unbiased variance)
+//   forward   k_bn_stats      per workgroup g and channel: the sums of (x - s_g) and (x - s_g)^2 over its rows, added in a fixed order (deterministic)
+//                             and left as mean_g and M2_g = sum (x - mean_g)^2.  s_g = the per-channel MEDIAN of three rows of the workgroup's own
+//                             slice (first, middle, last).
+//             k_bn_finish     the workgroups' (n_g, mean_g, M2_g) joined by the pairwise (Chan) formula's n-ary form in a fixed order -> mean,
+//                             1 / sqrt(var + eps) (biased variance, as F.batch_norm), running statistics (unbiased variance)
 //             k_bn_apply      y = relu?((x - mean) invstd gamma + beta (+ residual)); leaves max |y| in an amax slot for the next convolution
 //   backward  k_bn_bwd_stats  partial sums of g and g xhat, g = dy [y > 0]
 //             k_bn_bwd_finish partials -> dgamma, dbeta and the two means of the input gradient
 //             k_bn_bwd_apply  dx = gamma invstd (g - mean(g) - xhat mean(g xhat)); d_residual = g
+//
+// The pivot.  The one-pass variance sum (x - s)^2 / n - (mean - s)^2 cancels by (mean - s)^2 / var, so s must lie inside the channel's bulk.  One
+// pivot for the whole tensor taken from one row (the first row was used: in the neck the corner voxel, which sees 8 of 27 taps) lets that row decide
+// the conditioning of every channel: a first row 8 sigma off costs 3e-5 of the variance, 100 sigma 1e-3.  Here no single row does: a median of
+// three rows is an outlier only if two of the three are, a workgroup's pivot touches only its own slice's sums (a bad one costs that slice's
+// share of the variance, <= 1 / n_wg of the rows), and M2_g = s2_g - s1_g^2 / n_g is exact in the pivot, whatever it is.  The slices' (n_g, mean_g,
+// M2_g) then meet through mean = sum n_g mean_g / N, M2 = sum (M2_g + n_g (mean_g - mean)^2), which adds non-negative terms only.  No further pass
+// over x (three rows per workgroup are read twice), the same three launches, the same workspace, and every sum in an order that depends on (N, C)
+// alone.
 #include "conv_common.hpp"
 
 #define BN_THREADS 1024      // row kernels: 16 waves per workgroup, C / 4 lanes per row
-#define BN_MAX_WG 256        // partial sums per channel (the finish kernels add them in a fixed order: 8 lanes x <= 32 each)
-#define BN_FIN_THREADS 256   // finish kernels: 32 channels x 8 partial lanes
+#define BN_MAX_WG 256        // partial sums per channel (the finish kernels add them in a fixed order: 8 lanes x <= 32 each backward, 32 x <= 8 forward)
+#define BN_FIN_THREADS 256   // the backward's finish kernel: 32 channels x 8 partial lanes
 
 struct BnGeom { int64_t N; int C, CQ, RL; int64_t rows_per_wg; };      // CQ = C / 4 channel quads, RL = 1024 / CQ rows side by side in a workgroup
 
 __device__ __forceinline__ float4 bn_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
-// two per-channel sums over a workgroup's rows -> partial[(g * 2 + k) * C + c]
-__device__ __forceinline__ void bn_reduce_rows(float4 a, float4 b, const BnGeom& G, float* __restrict__ partial) {
+// two per-channel sums over a workgroup's rows, left in a and b of the threads it returns true to (row 0's).  The RL rows side by side (a power of
+// two) meet pairwise, row rl with row rl + RL / 2, then + RL / 4, ...: a fixed order, and log2 RL roundings on a sum instead of the RL of a chain
+// (C = 4 has RL = 1024: the chain's rounding, ~ sqrt(RL) 2^-24, times the one-pass formula's cancellation reached 7e-6 of the variance).
+__device__ __forceinline__ bool bn_reduce_rows(float4& a, float4& b, const BnGeom& G) {
     __shared__ float4 red[2][BN_THREADS];
-    const int t = threadIdx.x, q = t % G.CQ, rl = t / G.CQ;
+    const int t = threadIdx.x, rl = t / G.CQ;
     red[0][t] = a; red[1][t] = b;
     __syncthreads();
-    if (rl == 0 && t < G.CQ) {
-        for (int r = 1; r < G.RL; ++r) {                       // fixed order
-            const float4 u = red[0][r * G.CQ + q], v = red[1][r * G.CQ + q];
+    for (int h = G.RL >> 1; h >= 1; h >>= 1) {
+        if (rl < h) {                                            // reads rows [h, 2h), writes rows [0, h): no row is read and written in one step
+            const float4 u = red[0][t + h * G.CQ], v = red[1][t + h * G.CQ];
             a.x += u.x; a.y += u.y; a.z += u.z; a.w += u.w;
             b.x += v.x; b.y += v.y; b.z += v.z; b.w += v.w;
+            red[0][t] = a; red[1][t] = b;
         }
-        *reinterpret_cast<float4*>(partial + ((int64_t)blockIdx.x * 2 + 0) * G.C + 4 * q) = a;
-        *reinterpret_cast<float4*>(partial + ((int64_t)blockIdx.x * 2 + 1) * G.C + 4 * q) = b;
+        __syncthreads();
     }
+    return rl == 0;
 }
+
+// -> partial[(g * 2 + k) * C + c], g = the workgroup
+__device__ __forceinline__ void bn_store_partials(const float4& a, const float4& b, const BnGeom& G, float* __restrict__ partial) {
+    const int q = threadIdx.x % G.CQ;
+    *reinterpret_cast<float4*>(partial + ((int64_t)blockIdx.x * 2 + 0) * G.C + 4 * q) = a;
+    *reinterpret_cast<float4*>(partial + ((int64_t)blockIdx.x * 2 + 1) * G.C + 4 * q) = b;
+}
+
+__device__ __forceinline__ float bn_med3(float a, float b, float c) { return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c)); }
 
 __global__ __launch_bounds__(BN_THREADS) void k_bn_stats(const float* __restrict__ x, BnGeom G, float* __restrict__ partial) {
     const int t = threadIdx.x, q = t % G.CQ, rl = t / G.CQ;
     const int64_t lo = (int64_t)blockIdx.x * G.rows_per_wg, hi = lo + G.rows_per_wg < G.N ? lo + G.rows_per_wg : G.N;
-    float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+    float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1, sh = s1;
     if (rl < G.RL) {
-        const float4 sh = bn_ld4(x + 4 * q);
+        const float4 a = bn_ld4(x + lo * G.C + 4 * q), b = bn_ld4(x + (lo + (hi - lo) / 2) * G.C + 4 * q), c = bn_ld4(x + (hi - 1) * G.C + 4 * q);
+        sh = make_float4(bn_med3(a.x, b.x, c.x), bn_med3(a.y, b.y, c.y), bn_med3(a.z, b.z, c.z), bn_med3(a.w, b.w, c.w));
         for (int64_t r = lo + rl; r < hi; r += G.RL) {
             const float4 v = bn_ld4(x + r * G.C + 4 * q);
             const float dx = v.x - sh.x, dy = v.y - sh.y, dz = v.z - sh.z, dw = v.w - sh.w;
@@ -50,7 +74,14 @@ __global__ __launch_bounds__(BN_THREADS) void k_bn_stats(const float* __restrict
             s2.x += dx * dx; s2.y += dy * dy; s2.z += dz * dz; s2.w += dw * dw;
         }
     }
-    bn_reduce_rows(s1, s2, G, partial);
+    if (!bn_reduce_rows(s1, s2, G)) return;
+    // (s1, s2) about the pivot -> (mean_g, M2_g): exact in the pivot, whatever it is; rounding may leave M2_g -1 ulp of s2.  mean_g is stored
+    // rounded to fp32: half an ulp of |mean|, which enters the finish's n_g (mean_g - mean)^2 -- 2e-6 of the variance at |mean| = 1000 sigma, where
+    // x itself is known to 8e-5 sigma (a third array for the pivots avoided it and cost the finish half as many loads again).
+    const float inv_n = 1.0f / (float)(hi - lo);
+    const float4 d = make_float4(s1.x * inv_n, s1.y * inv_n, s1.z * inv_n, s1.w * inv_n);        // mean_g - s_g
+    const float4 m2 = make_float4(fmaxf(s2.x - s1.x * d.x, 0.f), fmaxf(s2.y - s1.y * d.y, 0.f), fmaxf(s2.z - s1.z * d.z, 0.f), fmaxf(s2.w - s1.w * d.w, 0.f));
+    bn_store_partials(make_float4(sh.x + d.x, sh.y + d.y, sh.z + d.z, sh.w + d.w), m2, G, partial);
 }
 
 // partial[(g * 2 + k) * C + c], g < n_wg -> the two sums of channel c.  32 channels x 8 lanes per workgroup: lane p adds the partials p, p + 8, ...
@@ -77,18 +108,54 @@ __device__ __forceinline__ void bn_sum_partials(const float* __restrict__ partia
     for (int k = 0; k < 8; ++k) { o1 += lane_sum[0][k][threadIdx.x & 31]; o2 += lane_sum[1][k][threadIdx.x & 31]; }
 }
 
-__global__ __launch_bounds__(BN_FIN_THREADS) void k_bn_finish(const float* __restrict__ x, const float* __restrict__ partial, int n_wg, int64_t N, int C, float eps,
-                                                              float momentum, float* __restrict__ running_mean, float* __restrict__ running_var,
-                                                              float* __restrict__ mean, float* __restrict__ invstd) {
-    const int c = blockIdx.x * 32 + (threadIdx.x & 31), p = threadIdx.x >> 5;
-    float s1, s2;
-    bn_sum_partials(partial, n_wg, C, c, p, s1, s2);
-    if (c >= C || p != 0) return;
-    const float inv_n = 1.0f / (float)N;
-    const float d = s1 * inv_n;                    // mean - shift
-    float var = s2 * inv_n - d * d;
-    var = var > 0.f ? var : 0.f;
-    const float m = x[c] + d;
+// partial[(g * 2 + 0) * C + c] = mean_g, partial[(g * 2 + 1) * C + c] = M2_g of workgroup g's rows -> mean and variance of channel c, by the n-ary
+// form of the pairwise (Chan, Golub, LeVeque) update,
+//     mean = sum n_g mean_g / N,   M2 = sum (M2_g + n_g (mean_g - mean)^2)       (every term of M2 is >= 0: nothing cancels).
+// The means are summed as offsets from workgroup 0's, so their roundings are ulps of the spread between the slices, not of the mean's magnitude.
+// 32 channels x 32 lanes per workgroup: lane p holds the workgroups p, p + 32, ... (all of them in registers: BN_MAX_WG / 32 = 8) and adds them in
+// index order, the 32 lane sums are added in lane order -- once for the mean, once for M2.  (Eight lanes of 32 workgroups each, as the backward's
+// finish has them, leave one wave per SIMD with a long dependent chain: 2 us more than this.)
+#define BN_FWD_FIN_LANES 32
+__global__ __launch_bounds__(32 * BN_FWD_FIN_LANES) void k_bn_finish(const float* __restrict__ partial, int n_wg, int64_t N, int64_t rows_per_wg, int C, float eps,
+                                                                     float momentum, float* __restrict__ running_mean, float* __restrict__ running_var,
+                                                                     float* __restrict__ mean, float* __restrict__ invstd) {
+    constexpr int SLOTS = BN_MAX_WG / BN_FWD_FIN_LANES;
+    __shared__ float lane_sum[BN_FWD_FIN_LANES][32];
+    const int cl = threadIdx.x & 31, c = blockIdx.x * 32 + cl, p = threadIdx.x >> 5;
+    const bool on = c < C;
+    const float ref = on ? partial[c] : 0.f;
+    const float n_full = (float)rows_per_wg, n_last = (float)(N - (int64_t)(n_wg - 1) * rows_per_wg);
+    float ng[SLOTS], mg[SLOTS], m2g[SLOTS];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k) {
+        const int g = p + BN_FWD_FIN_LANES * k;
+        const bool in = on && g < n_wg;
+        ng[k] = in ? (g == n_wg - 1 ? n_last : n_full) : 0.f;
+        mg[k] = (in ? partial[((int64_t)g * 2 + 0) * C + c] : ref) - ref;
+        m2g[k] = in ? partial[((int64_t)g * 2 + 1) * C + c] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k) s += ng[k] * mg[k];
+    lane_sum[p][cl] = s;
+    __syncthreads();
+    float tot = 0.f;
+    for (int k = 0; k < BN_FWD_FIN_LANES; ++k) tot += lane_sum[k][cl];
+    const float mo = tot / (float)N;                          // mean - ref
+    __syncthreads();
+    float qs = 0.f;
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k) {
+        const float d = mg[k] - mo;
+        qs += m2g[k] + ng[k] * (d * d);
+    }
+    lane_sum[p][cl] = qs;
+    __syncthreads();
+    if (!on || p != 0) return;
+    float m2 = 0.f;
+    for (int k = 0; k < BN_FWD_FIN_LANES; ++k) m2 += lane_sum[k][cl];
+    const float var = m2 / (float)N;
+    const float m = ref + mo;
     mean[c] = m;
     invstd[c] = 1.0f / sqrtf(var + eps);
     if (running_mean) running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * m;
@@ -132,7 +199,7 @@ __global__ __launch_bounds__(BN_THREADS) void k_bn_bwd_stats(const float* __rest
             s2.x += g.x * ((v.x - m.x) * is.x); s2.y += g.y * ((v.y - m.y) * is.y); s2.z += g.z * ((v.z - m.z) * is.z); s2.w += g.w * ((v.w - m.w) * is.w);
         }
     }
-    bn_reduce_rows(s1, s2, G, partial);
+    if (bn_reduce_rows(s1, s2, G)) bn_store_partials(s1, s2, G, partial);
 }
 
 __global__ __launch_bounds__(BN_FIN_THREADS) void k_bn_bwd_finish(const float* __restrict__ partial, int n_wg, int C, float* __restrict__ dgamma, float* __restrict__ dbeta) {
@@ -202,7 +269,7 @@ extern "C" int ndet_bn_train_forward(const float* x, int64_t N, int C, const flo
     if (rc != NDET_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_bn_stats, dim3(n_wg), dim3(BN_THREADS), 0, st, x, G, workspace);
-    hipLaunchKernelGGL(k_bn_finish, dim3((C + 31) / 32), dim3(BN_FIN_THREADS), 0, st, x, (const float*)workspace, n_wg, N, C, eps, momentum, running_mean,
+    hipLaunchKernelGGL(k_bn_finish, dim3((C + 31) / 32), dim3(32 * BN_FWD_FIN_LANES), 0, st, (const float*)workspace, n_wg, N, G.rows_per_wg, C, eps, momentum, running_mean,
                        running_var, save_mean, save_invstd);
     hipLaunchKernelGGL(k_bn_apply, dim3(n_wg), dim3(BN_THREADS), 0, st, x, G, (const float*)save_mean, (const float*)save_invstd, gamma, beta, residual, relu ? 1 : 0, y, y_amax);
     NDET_CHECK_LAUNCH(fn);
