@@ -516,6 +516,29 @@ int ndet_composite(const float* raw, const float* z_vals, const uint8_t* pixel_m
                    const float* zminmax, float* rgb_map, float* depth_map, float* weights, uint8_t* ray_mask,
                    float* alpha, float* transparency, void* stream);
 
+/* Hierarchical sampling, exact API form.  Replaces sample_pdf(), mmdet3d/models/model_utils/render_ray.py:96-142, with the uniforms
+ * supplied: bins (R, M+1), weights (R, M; NOT modified -- the reference adds 1e-5 in place), u: n_out values per ray at rows
+ * u_row_stride floats apart -- n_out, or 0 when every ray shares one row (det=True: torch.linspace(0, 1, n_out); else the
+ * torch.rand draw) -- samples (R, n_out).  Per ray, every operation rounded on its own: w = weights + 1e-5, pdf = w / sum(w),
+ * cdf = [0, cumsum(pdf)], above = #{i < M : u >= cdf[i]}, below = max(above - 1, 0), denom = cdf[above] - cdf[below] (1 where
+ * < 1e-5), sample = bins[below] + (u - cdf[below]) / denom * (bins[above] - bins[below]), then kept inside [bins[0], bins[M]]: the
+ * reference's float32 result overshoots bins[M] at u = 1.0 when its rounded cdf ends below 1.  The order of the sum and of the running
+ * sum is the kernel's own (csrc/importance_kernels.hip), fixed; results repeat bit for bit, torch's differ in the last bits of the cdf.
+ * Refused on the host before any launch, reading no device memory: a null pointer, R < 1, M < 1, n_out < 1, u_row_stride neither 0
+ * nor n_out (NDET_E_INVALID); M > 254, n_out > 256, R * (M + 1 + n_out) >= 2^31 (NDET_E_UNSUPPORTED). */
+int ndet_sample_pdf(const float* bins, const float* weights, int R, int M, const float* u, int u_row_stride, int n_out, float* samples,
+                    void* stream);
+
+/* Hierarchical sampling, fused: the fine pass's sample set of render_ray.py:343-356 (inv_uniform=False) in one launch.  z_vals and
+ * weights (R, S) of the coarse pass, ray_o and ray_d (R, 3), u as ndet_sample_pdf takes it (n_imp values a ray).  Per ray: bins =
+ * .5 * (z[1:] + z[:-1]), the weights weights[:, 1:-1] (M = S - 2), the draw of ndet_sample_pdf (same device code, same bits) ->
+ * z_samples_out (R, n_imp; may be NULL); z_out (R, S + n_imp) ascending, as a multiset sort(cat(z_vals, samples)) (equal depths in
+ * any order, no NaN); pts_out (R, S + n_imp, 3) = z * ray_d + ray_o, a multiply then an add.
+ * Refused on the host before any launch, reading no device memory: a null pointer (z_samples_out excepted), R < 1, S < 3, n_imp < 1,
+ * u_row_stride neither 0 nor n_imp (NDET_E_INVALID); S > 256, n_imp > 256, R * (S + n_imp) >= 2^31 (NDET_E_UNSUPPORTED). */
+int ndet_importance_merge(const float* z_vals, const float* weights, const float* ray_o, const float* ray_d, int R, int S, const float* u,
+                          int u_row_stride, int n_imp, float* z_out, float* pts_out, float* z_samples_out, void* stream);
+
 /* A13/A14. 3D convolution, channels-last, fp32 on the matrix cores, fused epilogue.  Replaces nn.Conv3d /
  * nn.ConvTranspose3d(2,2) + BatchNorm3d(eval) + ReLU (+ residual add) of mmdet3d/models/necks/imvoxelnet.py:8-67,
  * 233-260 and the head convs of mmdet3d/models/dense_heads/imvoxel_head_v2.py:45-49,442-449.

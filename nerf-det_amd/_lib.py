@@ -135,6 +135,8 @@ SIGNATURES = {
     "ndet_project_sample": ([_P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, c_int64, c_int64, c_int64,
                              _P, c_int, c_int, c_int, c_int64, c_int64, _P, _P, _P], c_int),
     "ndet_composite": ([_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P], c_int),
+    "ndet_sample_pdf": ([_P, _P, c_int, c_int, _P, c_int, c_int, _P, _P], c_int),
+    "ndet_importance_merge": ([_P, _P, _P, _P, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P], c_int),
     "ndet_backproject_aggregate_bwd": ([_P, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, c_int, _P, _P, _P], c_int),
     "ndet_density_features_bwd": ([_P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, _P, c_int, _P, _P, _P, _P], c_int),
     "ndet_ray_view_stats_bwd": ([_P, _P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, c_int, c_int64, c_int64, _P, _P], c_int),

@@ -1,7 +1,8 @@
 """Host mirror of the NeRF ray branch (A7-A12): ``Projector`` (mmdet3d/models/model_utils/projection.py:20-151),
 ``compute_mask_points`` / ``sample_along_camera_ray`` / ``raw2outputs`` / ``render_rays_func`` / ``render_rays``
 (model_utils/render_ray.py:48-93,145-327,371-520), same signatures, bodies on the HIP kernels of
-csrc/ray_kernels.hip.  The fused path (:func:`ray_view_stats`) never builds the (R,S,n_views,35) tensor."""
+csrc/ray_kernels.hip.  The fused path (:func:`ray_view_stats`) never builds the (R,S,n_views,35) tensor.  Hierarchical sampling
+(``sample_pdf``, render_ray.py:96-142, and the fine pass of ``render_rays_func``) runs on csrc/importance_kernels.hip."""
 from __future__ import annotations
 
 import ctypes
@@ -390,6 +391,95 @@ def sample_along_camera_ray(ray_o, ray_d, depth_range, N_samples, inv_uniform=Fa
 
 
 # ------------------------------------------------------------------------------------------------------
+# hierarchical sampling (render_ray.py:96-142, 343-356)
+# ------------------------------------------------------------------------------------------------------
+def _uniforms(u: Optional[Tensor], det: bool, r: int, n: int, device) -> Tuple[Tensor, int]:
+    """The ``u`` of sample_pdf (render_ray.py:113-117) as the C ABI takes it: ``(tensor, row stride)``.  ``det``: torch's own
+    ``linspace(0, 1, n)`` as ONE row every ray shares (stride 0); else the caller's ``u`` -- (R, n), or (n,) / (1, n) shared -- or a
+    ``torch.rand`` draw."""
+    if det:
+        return torch.linspace(0., 1., n, device=device), 0
+    if u is None:
+        return torch.rand((r, n), dtype=torch.float32, device=device), n
+    if not u.is_cuda:
+        raise RuntimeError("nerfdet_amd.rays: tensors must live on the GPU (no CPU fallback)")
+    u = u.to(torch.float32).contiguous()
+    if tuple(u.shape) in ((n,), (1, n)):
+        return u, 0
+    if tuple(u.shape) != (r, n):
+        raise ValueError(f"u {tuple(u.shape)} must be ({r}, {n}), or ({n},) shared by every ray")
+    return u, n
+
+
+def sample_pdf(bins, weights, N_samples, det=False, u: Optional[Tensor] = None):
+    """render_ray.py:96-142: ``bins`` (R, M+1), ``weights`` (R, M) -> (R, N_samples) depths drawn from the piecewise-constant pdf the
+    weights give over the bins.  ``u`` (R, N_samples) replaces the reference's ``torch.rand`` draw when given (``det`` wins, as in
+    :func:`sample_along_camera_ray`).  ``weights`` is NOT modified: the reference adds 1e-5 to it in place and is only ever handed a
+    clone.  The sums run in the kernel's order (csrc/importance_kernels.hip), so the depths agree with torch's to rounding in CDF
+    space, not bit for bit.  M <= 254, N_samples <= 256."""
+    if not (bins.is_cuda and weights.is_cuda):
+        raise RuntimeError("nerfdet_amd.rays: tensors must live on the GPU (no CPU fallback)")
+    r, m = weights.shape
+    if tuple(bins.shape) != (r, m + 1):
+        raise ValueError(f"sample_pdf: bins {tuple(bins.shape)} for weights {tuple(weights.shape)}")
+    b = bins.detach().to(torch.float32).contiguous()
+    w = weights.detach().to(torch.float32).contiguous()
+    n = int(N_samples)
+    uu, stride = _uniforms(u, det, r, n, b.device)
+    out = torch.empty((r, n), dtype=torch.float32, device=b.device)
+    trace.span("k_sample_pdf", lambda: check(
+        _lib.load().ndet_sample_pdf(_ptr(b), _ptr(w), r, m, _ptr(uu), stride, n, _ptr(out), _stream(b)), "sample_pdf"))
+    return out
+
+
+def importance_merge(z_vals, weights, ray_o, ray_d, N_importance, det, u: Optional[Tensor] = None):
+    """The fine pass's samples (render_ray.py:343-356, ``inv_uniform=False``) in ONE launch (k_importance_merge): ``z_vals``,
+    ``weights`` (R, S) of the coarse pass -> ``(pts (R, S+k, 3), z_vals (R, S+k), z_samples (R, k))`` with ``z_samples =
+    sample_pdf(.5 * (z[1:] + z[:-1]), weights[:, 1:-1], k, det, u)`` bit for bit, the merged depths ``sort(cat(z_vals, z_samples))``
+    and ``pts = z * ray_d + ray_o``.  3 <= S <= 256, 1 <= k <= 256.  Nothing is differentiable here (the reference detaches the
+    weights, render_ray.py:332)."""
+    if not (z_vals.is_cuda and weights.is_cuda and ray_o.is_cuda and ray_d.is_cuda):
+        raise RuntimeError("nerfdet_amd.rays: tensors must live on the GPU (no CPU fallback)")
+    r, s = z_vals.shape
+    k = int(N_importance)
+    if tuple(weights.shape) != (r, s) or tuple(ray_o.shape) != (r, 3) or tuple(ray_d.shape) != (r, 3):
+        raise ValueError(f"importance_merge: z_vals {tuple(z_vals.shape)}, weights {tuple(weights.shape)}, ray_o {tuple(ray_o.shape)}, "
+                         f"ray_d {tuple(ray_d.shape)}")
+    z = z_vals.detach().to(torch.float32).contiguous()
+    w = weights.detach().to(torch.float32).contiguous()
+    o = ray_o.detach().to(torch.float32).contiguous()
+    d = ray_d.detach().to(torch.float32).contiguous()
+    uu, stride = _uniforms(u, det, r, k, z.device)
+    tot = s + max(k, 0)
+    z_out = torch.empty((r, tot), dtype=torch.float32, device=z.device)
+    pts = torch.empty((r, tot, 3), dtype=torch.float32, device=z.device)
+    z_samples = torch.empty((r, max(k, 0)), dtype=torch.float32, device=z.device)
+    trace.span("k_importance_merge", lambda: check(
+        _lib.load().ndet_importance_merge(_ptr(z), _ptr(w), _ptr(o), _ptr(d), r, s, _ptr(uu), stride, k, _ptr(z_out), _ptr(pts),
+                                          _ptr(z_samples), _stream(z)), "importance_merge"),
+        bytes=4 * r * (2 * s + 5 * tot), kind="hbm")
+    return pts, z_out, z_samples
+
+
+FINE_MLP_ROWS = 8192 * 64     # sample rows per nerf_mlp call of a fine pass: what a coarse pass of RENDER_TESTING_RAYS rays x 64 samples hands it
+
+
+def fine_mlp(nerf_mlp, pts, ray_d, globalfeat):
+    """``nerf_mlp(pts, ray_d, globalfeat)`` over the (R, S + k, .) samples of a fine pass, as ``(rgb, sigma)``: in one call up to
+    FINE_MLP_ROWS sample rows, beyond that in the fewest calls of whole rays, equal in size to within one ray, that stay under it.  The
+    row MLP's 1x1-convolution kernels address at most 2 GB per operand, which 8192 rays x 128 samples of the cfg2 widths exceed.  The
+    split is a function of (R, S + k) alone, so every renderer's fine pass makes the same calls over the same rays -- the ``linear_rows``
+    layers take a per-tensor scale, the calls are part of the result's bits."""
+    r, s = pts.shape[:2]
+    most = max(1, FINE_MLP_ROWS // s)          # rays a call may take
+    if r <= most:
+        return nerf_mlp(pts, ray_d, globalfeat)
+    step = -(-r // -(-r // most))
+    outs = [nerf_mlp(pts[i:i + step], ray_d[i:i + step], globalfeat[i:i + step]) for i in range(0, r, step)]
+    return torch.cat([o[0] for o in outs], dim=0), torch.cat([o[1] for o in outs], dim=0)
+
+
+# ------------------------------------------------------------------------------------------------------
 # A11
 # ------------------------------------------------------------------------------------------------------
 def raw2outputs(raw, z_vals, mask, white_bkgd=False):
@@ -430,13 +520,23 @@ def _raw2outputs_impl(raw, z_vals, mask, white_bkgd=False):
 def render_rays_func(ray_o, ray_d, mean_volume, cov_volume, features_2D, img, aabb, near_far_range, N_samples, N_rand=4096,
                      nerf_mlp=None, img_meta=None, projector=None, mode="volume", nerf_sample_view=3, inv_uniform=False,
                      N_importance=0, det=False, is_train=True, white_bkgd=False, gt_rgb=None, gt_depth=None, t_rand=None):
-    """render_ray.py:250-369, ``mode='image'``, ``N_importance=0`` (the only reachable branch)."""
+    """render_ray.py:250-369, ``mode='image'``.  ``N_importance=0`` is the only branch the reference can reach.
+
+    ``N_importance=k > 0`` is THIS PROJECT'S definition of the fine pass: the reference's branch (render_ray.py:329-367) names
+    ``model``, ``ray_batch`` and ``featmaps``, which do not exist there, and cannot run.  Here the coarse weights (detached,
+    render_ray.py:332) go through :func:`importance_merge` (render_ray.py:343-356), and the merged ``N_samples + k`` samples through the
+    same sampler, the same ``nerf_mlp`` -- NeRF-Det has one MLP, there is no separate fine network -- and :func:`raw2outputs`;
+    the result is ``ret['outputs_fine']``, ``outputs_coarse`` and ``sigma`` are the coarse pass's, unchanged.  The fine pass is
+    inference only: with autograd on and ``features_2D.requires_grad`` it raises ValueError.  ``inv_uniform`` stays refused."""
     assert mode == "image", "nerf_mode='volume' is not used by any nerfdet config"
-    assert N_importance == 0, "the N_importance>0 branch references undefined names in the reference (render_ray.py:329-367)"
+    assert N_importance >= 0
+    training = torch.is_grad_enabled() and features_2D.requires_grad
+    if N_importance > 0 and training:
+        raise ValueError("render_rays_func: N_importance > 0 has no backward (the fine pass is inference only)")
     ret = {"outputs_coarse": None, "outputs_fine": None, "gt_rgb": gt_rgb, "gt_depth": gt_depth}
     pts, z_vals = sample_along_camera_ray(ray_o, ray_d, near_far_range, N_samples, inv_uniform=inv_uniform, det=det, t_rand=t_rand)
     cams = _compute_projection(img_meta)
-    if torch.is_grad_enabled() and features_2D.requires_grad:
+    if training:
         from .autograd import RayViewStats
         globalfeat, pixel_mask, _ = RayViewStats.apply(features_2D, pts, img, cams)
     else:
@@ -444,6 +544,12 @@ def render_rays_func(ray_o, ray_d, mean_volume, cov_volume, features_2D, img, aa
     rgb_pts, density_pts = nerf_mlp(pts, ray_d, globalfeat)
     ret["sigma"] = density_pts
     ret["outputs_coarse"] = raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), z_vals, pixel_mask, white_bkgd=white_bkgd)
+    if N_importance > 0:
+        weights = ret["outputs_coarse"]["weights"].detach()                                  # render_ray.py:332
+        pts_f, z_f, _ = importance_merge(z_vals, weights, ray_o, ray_d, N_importance, det)   # render_ray.py:343-356
+        globalfeat_f, pixel_mask_f, _ = ray_view_stats(pts_f, img, cams, features_2D)
+        rgb_f, density_f = fine_mlp(nerf_mlp, pts_f, ray_d, globalfeat_f)
+        ret["outputs_fine"] = raw2outputs(torch.cat([rgb_f, density_f], dim=-1), z_f, pixel_mask_f, white_bkgd=white_bkgd)
     return ret
 
 
@@ -540,7 +646,7 @@ def render_rays(ray_batch, mean_volume, cov_volume, features_2D, img, aabb, near
         ray_o, ray_d, gt_rgb = ray_o.view(-1, 3), ray_d.view(-1, 3), gt_rgb.view(-1, 3)
         gt_depth = gt_depth.view(-1, 1) if len(gt_depth) != 0 else None
         assert view_num * hh * ww == ray_o.shape[0]  # render_ray.py:468
-        rgbs, depths = [], []
+        rgbs, depths, rgbs_f, depths_f = [], [], [], []
         # the reference walks the rays N_rand at a time (render_ray.py:470); a ray's result does not depend on its chunk mates (deterministic
         # sampling, row-wise MLP), so on the GPU several of its chunks go through one pass: fewer, larger GEMMs
         step = N_rand * max(1, RENDER_TESTING_RAYS // N_rand) if ray_o.is_cuda else N_rand
@@ -550,10 +656,17 @@ def render_rays(ray_batch, mean_volume, cov_volume, features_2D, img, aabb, near
                                    inv_uniform, N_importance, True, is_train, white_bkgd, gt_rgb, gt_depth)
             rgbs.append(ret["outputs_coarse"]["rgb"])
             depths.append(ret["outputs_coarse"]["depth"])
-        return {"outputs_coarse": {"rgb": torch.cat(rgbs, dim=0).view(view_num, hh, ww, 3),
-                                   "depth": torch.cat(depths, dim=0).view(view_num, hh, ww, 1)},
-                "gt_rgb": gt_rgb.view(view_num, hh, ww, 3),
-                "gt_depth": gt_depth.view(view_num, hh, ww, 1) if gt_depth is not None else None}
+            if N_importance > 0:
+                rgbs_f.append(ret["outputs_fine"]["rgb"])
+                depths_f.append(ret["outputs_fine"]["depth"])
+        out = {"outputs_coarse": {"rgb": torch.cat(rgbs, dim=0).view(view_num, hh, ww, 3),
+                                  "depth": torch.cat(depths, dim=0).view(view_num, hh, ww, 1)},
+               "gt_rgb": gt_rgb.view(view_num, hh, ww, 3),
+               "gt_depth": gt_depth.view(view_num, hh, ww, 1) if gt_depth is not None else None}
+        if N_importance > 0:             # this project's fine pass (render_rays_func), stacked like the coarse one
+            out["outputs_fine"] = {"rgb": torch.cat(rgbs_f, dim=0).view(view_num, hh, ww, 3),
+                                   "depth": torch.cat(depths_f, dim=0).view(view_num, hh, ww, 1)}
+        return out
     return None
 
 
@@ -581,12 +694,13 @@ def compute_ssim(pred: Tensor, target: Tensor) -> Tensor:
     return s.mean(dim=(2, 3)).mean()
 
 
-def rendering_metrics(rendered: dict):
+def rendering_metrics(rendered: dict, which: str = "outputs_coarse"):
     """What ``save_rendered_img`` returns (model_utils/save_rendered_img.py:38-78) for one ``render_rays(render_testing=True)`` result,
     without its PNG dump: mean PSNR and mean SSIM over the target views (device scalars) and the mean squared depth error MAP
-    (H,W,1) the reference calls rmse (None without depth maps)."""
-    rgb, gt = rendered["outputs_coarse"]["rgb"], rendered["gt_rgb"]
-    depth, gt_depth = rendered["outputs_coarse"]["depth"], rendered["gt_depth"]
+    (H,W,1) the reference calls rmse (None without depth maps).  ``which``: ``'outputs_coarse'`` (the reference's) or
+    ``'outputs_fine'`` of a render with ``N_importance > 0``."""
+    rgb, gt = rendered[which]["rgb"], rendered["gt_rgb"]
+    depth, gt_depth = rendered[which]["depth"], rendered["gt_depth"]
     n = gt.shape[0]
     psnr = torch.stack([compute_psnr(rgb[v], gt[v]) for v in range(n)]).mean()
     ssim = torch.stack([compute_ssim(rgb[v], gt[v]) for v in range(n)]).mean()

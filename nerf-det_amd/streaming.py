@@ -70,6 +70,34 @@ def check_chunk_meta(scene_meta: dict, img_meta: dict, k: int) -> None:
         raise ValueError(f"add_views: {len(b['lidar2img']['extrinsic'])} extrinsics for {k} views")
 
 
+def _check_n_importance(n_importance) -> int:
+    """The fine samples per ray of a render call: an int in 0 .. 256 (k_importance_merge's limit), else ValueError."""
+    if isinstance(n_importance, bool) or not isinstance(n_importance, int) or not 0 <= n_importance <= 256:
+        raise ValueError(f"n_importance={n_importance!r} must be an int in 0 .. 256")
+    return n_importance
+
+
+def _render_dict(coarse, fine):
+    """``render_rays``'s result of one scene: ``(rgb, depth, mask)`` of the coarse pass and of the fine pass (None without one)."""
+    keys = ("rgb", "depth", "mask")
+    if fine is None:
+        return OrderedDict(zip(keys, coarse))
+    out = OrderedDict(zip(keys, fine))
+    out["coarse"] = OrderedDict(zip(keys, coarse))
+    return out
+
+
+def _render_views(coarse, fine, shape, gt_rgb, gt_depth):
+    """``render``'s result of one scene (render_ray.py:452-517), ``outputs_fine`` beside ``outputs_coarse`` when there was a fine pass."""
+    t, hh, ww = shape
+    out = {"outputs_coarse": {"rgb": coarse[0].view(t, hh, ww, 3), "depth": coarse[1].view(t, hh, ww, 1)},
+           "gt_rgb": gt_rgb.view(t, hh, ww, 3),
+           "gt_depth": gt_depth.view(t, hh, ww, 1) if gt_depth is not None else None}
+    if fine is not None:
+        out["outputs_fine"] = {"rgb": fine[0].view(t, hh, ww, 3), "depth": fine[1].view(t, hh, ww, 1)}
+    return out
+
+
 class SceneStream:
     """One scene of a :class:`~nerfdet_amd.detector.nerfdet` detector, filled chunk by chunk (:meth:`add_views`) and detected at any time
     (:meth:`detect`).  ``img_meta`` fixes the scene: ``lidar2img.intrinsic``, ``lidar2img.origin``, ``img_shape`` and ``ori_shape``; its
@@ -232,12 +260,13 @@ class SceneStream:
             raise RuntimeError("the scene has no views yet: call add_views first")
         return bank
 
-    def _render(self, ray_o: Tensor, ray_d: Tensor, step: int):
-        """render_ray.py:250-327 (``det=True``, mode 'image') over the bank, ``step`` rays per pass."""
+    def _render(self, ray_o: Tensor, ray_d: Tensor, step: int, n_importance: int = 0):
+        """render_ray.py:250-327 (``det=True``, mode 'image') over the bank, ``step`` rays per pass: ``(rgb, depth, mask)`` of the coarse
+        pass and, with ``n_importance > 0``, of the fine pass of ``rays.render_rays_func`` (else None)."""
         from . import rays
         bank = self._need_bank("rendering")
         det = self.det
-        rgbs, depths, masks = [], [], []
+        coarse, fine = ([], [], []), ([], [], [])
         with torch.no_grad():
             for i in range(0, ray_o.shape[0], step):
                 o, d = ray_o[i:i + step], ray_d[i:i + step]
@@ -245,27 +274,42 @@ class SceneStream:
                 globalfeat, pixel_mask, _ = rays.ray_view_stats_bank(pts, bank)
                 rgb_pts, density_pts = det.nerf_mlp(pts, d, globalfeat)
                 out = rays.raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), z_vals, pixel_mask)
-                rgbs.append(out["rgb"])
-                depths.append(out["depth"])
-                masks.append(out["mask"])
-        return torch.cat(rgbs, dim=0), torch.cat(depths, dim=0), torch.cat(masks, dim=0)
+                for acc, key in zip(coarse, ("rgb", "depth", "mask")):
+                    acc.append(out[key])
+                if n_importance > 0:
+                    pts, z_vals, _ = rays.importance_merge(z_vals, out["weights"], o, d, n_importance, True)
+                    globalfeat, pixel_mask, _ = rays.ray_view_stats_bank(pts, bank)
+                    rgb_pts, density_pts = rays.fine_mlp(det.nerf_mlp, pts, d, globalfeat)
+                    out = rays.raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), z_vals, pixel_mask)
+                    for acc, key in zip(fine, ("rgb", "depth", "mask")):
+                        acc.append(out[key])
+        coarse = tuple(torch.cat(a, dim=0) for a in coarse)
+        return coarse, (tuple(torch.cat(a, dim=0) for a in fine) if n_importance > 0 else None)
 
-    def render_rays(self, ray_o: Tensor, ray_d: Tensor):
+    def render_rays(self, ray_o: Tensor, ray_d: Tensor, n_importance: int = 0):
         """Render rays ``ray_o``, ``ray_d`` (R,3) against the views held: ``dict(rgb (R,3), depth (R,), mask (R,) bool)``, what
         ``rays.render_rays_func(det=True)`` composites (render_ray.py:250-327) with the detector's ``near_far_range`` and ``N_samples``,
-        ``rays.RENDER_TESTING_RAYS`` rays per pass.  Needs ``keep_views=True`` and at least one view (else RuntimeError)."""
+        ``rays.RENDER_TESTING_RAYS`` rays per pass.  Needs ``keep_views=True`` and at least one view (else RuntimeError).
+
+        ``n_importance=k > 0`` adds the fine pass of ``rays.render_rays_func(N_importance=k)``: k further depths per ray drawn from the
+        coarse weights (one k_importance_merge launch a pass), then the sampler, the MLP and the compositing again over the
+        ``N_samples + k`` depths.  ``rgb``, ``depth`` and ``mask`` are then the fine pass's, and the dict gains ``'coarse'``:
+        ``dict(rgb, depth, mask)`` of the coarse pass, which is what ``n_importance=0`` returns."""
         from . import rays
         self._need_bank("render_rays")
+        n_importance = _check_n_importance(n_importance)
         if ray_o.dim() != 2 or ray_o.shape[1] != 3 or ray_d.shape != ray_o.shape:
             raise ValueError(f"render_rays takes (R,3) origins and directions, got {tuple(ray_o.shape)} and {tuple(ray_d.shape)}")
-        rgb, depth, mask = self._render(ray_o, ray_d, rays.RENDER_TESTING_RAYS)
-        return OrderedDict([("rgb", rgb), ("depth", depth), ("mask", mask)])
+        coarse, fine = self._render(ray_o, ray_d, rays.RENDER_TESTING_RAYS, n_importance)
+        return _render_dict(coarse, fine)
 
-    def render(self, ray_batch: dict):
+    def render(self, ray_batch: dict, n_importance: int = 0):
         """Every ray of the ray batch's target views, as ``rays.render_rays(render_testing=True)`` returns them (render_ray.py:452-517):
-        ``outputs_coarse.rgb`` (T,h,w,3), ``outputs_coarse.depth`` (T,h,w,1), ``gt_rgb``, ``gt_depth`` -- ``rays.rendering_metrics`` applies."""
+        ``outputs_coarse.rgb`` (T,h,w,3), ``outputs_coarse.depth`` (T,h,w,1), ``gt_rgb``, ``gt_depth`` -- ``rays.rendering_metrics`` applies.
+        ``n_importance=k > 0`` adds ``outputs_fine`` (same shapes), as ``rays.render_rays(render_testing=True, N_importance=k)`` does."""
         from . import rays
         self._need_bank("render")
+        n_importance = _check_n_importance(n_importance)
         ray_o, ray_d, gt_rgb, gt_depth = ray_batch["ray_o"], ray_batch["ray_d"], ray_batch["gt_rgb"], ray_batch["gt_depth"]
         nerf_size = ray_batch["nerf_sizes"][0]
         view_num = ray_o.shape[1]
@@ -275,10 +319,8 @@ class SceneStream:
         assert view_num * hh * ww == ray_o.shape[0]  # render_ray.py:468
         n_rand = self.det.N_rand
         step = n_rand * max(1, rays.RENDER_TESTING_RAYS // n_rand)       # the passes of rays.render_rays
-        rgb, depth, _ = self._render(ray_o, ray_d, step)
-        return {"outputs_coarse": {"rgb": rgb.view(view_num, hh, ww, 3), "depth": depth.view(view_num, hh, ww, 1)},
-                "gt_rgb": gt_rgb.view(view_num, hh, ww, 3),
-                "gt_depth": gt_depth.view(view_num, hh, ww, 1) if gt_depth is not None else None}
+        coarse, fine = self._render(ray_o, ray_d, step, n_importance)
+        return _render_views(coarse, fine, (view_num, hh, ww), gt_rgb, gt_depth)
 
     def volume(self):
         """``(volume (C,X,Y,Z), valid (1,X,Y,Z) int64)`` of the views so far: K2-finish -> sigma-MLP -> K1-finish, what ``extract_volume``
@@ -556,51 +598,71 @@ class SceneGroup:
             raise RuntimeError(f"scenes {empty} have no views yet: call add_views first")
         return scenes
 
-    def _render(self, ray_os, ray_ds, scenes: List[int], step: int, batched: bool):
+    def _render(self, ray_os, ray_ds, scenes: List[int], step: int, batched: bool, n_importance: int = 0):
         """render_ray.py:250-327 (``det=True``, mode 'image') over the listed scenes' banks, at most ``step`` rays per scene and pass:
-        per listed scene ``(rgb, depth, mask)``.  A pass samples every scene that still has rays, runs ONE grouped sampler launch over
-        their banks (rays.ray_view_stats_bank_group) and then the MLP and the compositing per scene, or with ``batched`` once over all
-        the pass's samples."""
+        per listed scene ``((rgb, depth, mask) of the coarse pass, the same of the fine pass or None)``.  A pass samples every scene
+        that still has rays, runs ONE grouped sampler launch over their banks (rays.ray_view_stats_bank_group) and then the MLP and the
+        compositing per scene, or with ``batched`` once over all the pass's samples.  With ``n_importance > 0`` ONE k_importance_merge
+        launch over all the pass's rays then gives the fine samples (the kernel is per ray), and the same three steps run over them."""
         from . import rays
         det = self.det
         n = len(scenes)
         banks = [self.banks[s] for s in scenes]
         batched = bool(batched) and n > 1 and conv3d.ARITHMETIC != "f32"
         outs = [([], [], []) for _ in range(n)]
+        fines = [([], [], []) for _ in range(n)]
+
+        def shade(live, accs, dirs, pts, zs, ss, want_weights):
+            """Sampler, MLP and compositing of one pass over ``ss`` samples a ray; appends to ``accs``, returns the rays' weights (R, ss)."""
+            mlp = det.nerf_mlp if ss == det.N_samples else (lambda p, d, g: rays.fine_mlp(det.nerf_mlp, p, d, g))
+            glob, pm, _, all_pts = rays.bank_group_stats(pts, [banks[i] for i in live])
+            counts = [p.shape[0] for p in pts]
+            if batched and len(live) > 1:
+                # one MLP call and one compositing call over the pass: the scenes share linear_rows' per-tensor fp16-pair scales
+                rr = sum(counts)
+                rgb_pts, density_pts = mlp(all_pts.view(rr, ss, 3), torch.cat(dirs, dim=0), glob.view(rr, ss, -1))
+                out = rays.raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), torch.cat(zs, dim=0), pm.view(rr, ss))
+                at = 0
+                for i, c in zip(live, counts):
+                    for acc, key in zip(accs[i], ("rgb", "depth", "mask")):
+                        acc.append(out[key][at:at + c])
+                    at += c
+                return out["weights"]
+            at, wts = 0, []
+            for i, c, d, p, z in zip(live, counts, dirs, pts, zs):
+                rows = slice(at * ss, (at + c) * ss)
+                rgb_pts, density_pts = mlp(p, d, glob[rows].view(c, ss, -1))
+                out = rays.raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), z, pm[rows].view(c, ss))
+                for acc, key in zip(accs[i], ("rgb", "depth", "mask")):
+                    acc.append(out[key])
+                wts.append(out["weights"])
+                at += c
+            return (wts[0] if len(wts) == 1 else torch.cat(wts, dim=0)) if want_weights else None
+
         with torch.no_grad():
             for i0 in range(0, max(o.shape[0] for o in ray_os), step):
                 live = [i for i in range(n) if ray_os[i].shape[0] > i0]
-                dirs, pts, zs = [], [], []
+                origins, dirs, pts, zs = [], [], [], []
                 for i in live:
                     o, d = ray_os[i][i0:i0 + step], ray_ds[i][i0:i0 + step]
                     p, z = rays.sample_along_camera_ray(o, d, det.near_far_range, det.N_samples, det=True)
+                    origins.append(o)
                     dirs.append(d)
                     pts.append(p)
                     zs.append(z)
-                glob, pm, _, all_pts = rays.bank_group_stats(pts, [banks[i] for i in live])
-                counts = [p.shape[0] for p in pts]
-                if batched and len(live) > 1:
-                    # one MLP call and one compositing call over the pass: the scenes share linear_rows' per-tensor fp16-pair scales
-                    rr, ss = sum(counts), det.N_samples
-                    rgb_pts, density_pts = det.nerf_mlp(all_pts.view(rr, ss, 3), torch.cat(dirs, dim=0), glob.view(rr, ss, -1))
-                    out = rays.raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), torch.cat(zs, dim=0), pm.view(rr, ss))
-                    at = 0
-                    for i, c in zip(live, counts):
-                        for acc, key in zip(outs[i], ("rgb", "depth", "mask")):
-                            acc.append(out[key][at:at + c])
-                        at += c
-                    continue
-                at = 0
-                for i, c, d, p, z in zip(live, counts, dirs, pts, zs):
-                    rows = slice(at * det.N_samples, (at + c) * det.N_samples)
-                    rgb_pts, density_pts = det.nerf_mlp(p, d, glob[rows].view(c, det.N_samples, -1))
-                    out = rays.raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), z, pm[rows].view(c, det.N_samples))
-                    for acc, key in zip(outs[i], ("rgb", "depth", "mask")):
-                        acc.append(out[key])
-                    at += c
-        return [tuple(a[0] if len(a) == 1 else torch.cat(a, dim=0) for a in acc) for acc in outs]
+                weights = shade(live, outs, dirs, pts, zs, det.N_samples, n_importance > 0)
+                if n_importance > 0:
+                    one = len(live) == 1
+                    pts_f, z_f, _ = rays.importance_merge(zs[0] if one else torch.cat(zs, dim=0), weights,
+                                                          origins[0] if one else torch.cat(origins, dim=0),
+                                                          dirs[0] if one else torch.cat(dirs, dim=0), n_importance, True)
+                    counts = [p.shape[0] for p in pts]
+                    shade(live, fines, dirs, list(torch.split(pts_f, counts, dim=0)), list(torch.split(z_f, counts, dim=0)),
+                          det.N_samples + n_importance, False)
+        cat = lambda acc: tuple(a[0] if len(a) == 1 else torch.cat(a, dim=0) for a in acc)
+        return [(cat(c), cat(f) if n_importance > 0 else None) for c, f in zip(outs, fines)]
 
-    def render_rays(self, ray_o, ray_d, scenes=None, batched: bool = False):
+    def render_rays(self, ray_o, ray_d, scenes=None, batched: bool = False, n_importance: int = 0):
         """Render rays against the views the listed scenes hold: ``ray_o``, ``ray_d`` are lists of (R_s, 3) tensors, one pair per listed
         scene (the counts may differ, each at least 1); returns per listed scene ``dict(rgb (R_s,3), depth (R_s,), mask (R_s,) bool)`` as
         :meth:`SceneStream.render_rays` does.  Passes of at most ``rays.RENDER_TESTING_RAYS`` rays per scene: every scene that still has
@@ -616,14 +678,21 @@ class SceneGroup:
         1e-4 absolute and ``depth`` to 1e-4 x ``near_far_range[1]``.  One listed scene, or the "f32" arithmetic: the ``batched=False``
         path bit for bit.
 
+        ``n_importance=k > 0`` adds the fine pass of ``rays.render_rays_func(N_importance=k)`` to every pass: after the coarse
+        compositing ONE k_importance_merge launch over all the listed scenes' rays of the pass (rays.importance_merge), a second grouped
+        sampler launch over the ``N_samples + k`` depths, then the MLP and the compositing again, per scene or ``batched``.  Each
+        dict's ``rgb``, ``depth`` and ``mask`` are then the fine pass's and it gains ``'coarse'``, as :meth:`SceneStream.render_rays`
+        returns them -- with ``batched=False`` bit for bit, with ``batched=True`` to the bounds above.
+
         Needs ``keep_views=True`` and at least one view in every listed scene (else RuntimeError); wrong list lengths or shapes are a
         ValueError; everything is refused before anything is launched.  No bank or state is changed.  Renders and evictions
         (``add_views`` at a full window, ``drop_oldest``, ``reset``) must be issued on ONE stream (rays.ViewBank)."""
         from . import rays
         scenes = self._need_banks("render_rays", scenes)
+        n_importance = _check_n_importance(n_importance)
         ray_o, ray_d = self._check_rays(ray_o, ray_d, len(scenes))
-        res = self._render(ray_o, ray_d, scenes, rays.RENDER_TESTING_RAYS, batched)
-        return [OrderedDict([("rgb", rgb), ("depth", depth), ("mask", mask)]) for rgb, depth, mask in res]
+        res = self._render(ray_o, ray_d, scenes, rays.RENDER_TESTING_RAYS, batched, n_importance)
+        return [_render_dict(coarse, fine) for coarse, fine in res]
 
     @staticmethod
     def _check_rays(ray_o, ray_d, n: int):
@@ -638,13 +707,15 @@ class SceneGroup:
                                  f"for listed scene {i}")
         return ray_o, ray_d
 
-    def render(self, ray_batches, scenes=None, batched: bool = False):
+    def render(self, ray_batches, scenes=None, batched: bool = False, n_importance: int = 0):
         """Every ray of the target views of one ray batch per listed scene: per scene what :meth:`SceneStream.render` returns
         (``outputs_coarse.rgb`` (T,h,w,3), ``outputs_coarse.depth`` (T,h,w,1), ``gt_rgb``, ``gt_depth`` -- ``rays.rendering_metrics``
         applies), through the passes of :meth:`render_rays` with SceneStream.render's pass size,
-        ``N_rand * max(1, RENDER_TESTING_RAYS // N_rand)``; ``batched`` as in :meth:`render_rays`.  One stream, as there."""
+        ``N_rand * max(1, RENDER_TESTING_RAYS // N_rand)``; ``batched`` and ``n_importance`` (which adds ``outputs_fine``) as in
+        :meth:`render_rays`.  One stream, as there."""
         from . import rays
         scenes = self._need_banks("render", scenes)
+        n_importance = _check_n_importance(n_importance)
         ray_batches = list(ray_batches)
         if len(ray_batches) != len(scenes):
             raise ValueError(f"render: {len(ray_batches)} ray batches for {len(scenes)} listed scenes")
@@ -664,11 +735,8 @@ class SceneGroup:
         os_, ds_ = self._check_rays(os_, ds_, len(scenes))
         n_rand = self.det.N_rand
         step = n_rand * max(1, rays.RENDER_TESTING_RAYS // n_rand)       # the passes of rays.render_rays
-        res = self._render(os_, ds_, scenes, step, batched)
-        return [{"outputs_coarse": {"rgb": rgb.view(t, hh, ww, 3), "depth": depth.view(t, hh, ww, 1)},
-                 "gt_rgb": gt_rgb.view(t, hh, ww, 3),
-                 "gt_depth": gt_depth.view(t, hh, ww, 1) if gt_depth is not None else None}
-                for (rgb, depth, _), (t, hh, ww), (gt_rgb, gt_depth) in zip(res, shapes, gts)]
+        res = self._render(os_, ds_, scenes, step, batched, n_importance)
+        return [_render_views(coarse, fine, shape, gt_rgb, gt_depth) for (coarse, fine), shape, (gt_rgb, gt_depth) in zip(res, shapes, gts)]
 
     def _volumes(self, scenes: List[int]):
         """``(volume (n,C,X,Y,Z), valid (n,1,X,Y,Z) int64)`` of the listed scenes: grouped K2-finish -> one sigma-MLP call over all their

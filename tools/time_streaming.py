@@ -14,6 +14,9 @@ the scene's 50 views and 8192 x 64 sample points, for the bank held as 1, 10 and
 the generic sampler over a concatenated copy; scene.render of one target view next to rays.render_rays(render_testing=True) over the same
 maps; and the bank's bytes per view.  The calls of a comparison alternate inside one loop.
     python tools/time_streaming.py --render [--reps 20 --warmup 3]
+Both --render modes end with the hierarchical-sampling table: the target view (scene.render) and the groups' previews (group.render_rays, per
+scene and batched) with n_importance = 0 / 64 / 128 fine samples a ray, each against n_importance=0 in the same alternating loop;
+--importance-only times nothing else.
 With --group 1,4,8,16 it times scene groups (det.begin_scenes): for every S, group.add_views of S x 1 and S x 5 views against S separate
 SceneStream.add_views calls of the same chunks, and group.detect() against group.detect(batched=True) and S separate detect() calls (one after the other, and all queued
 with defer=True before the first is collected) with every scene holding the workload's 50 views -- the compared calls alternating inside
@@ -284,7 +287,22 @@ def group_window_mode(det, img, dn, meta, configs, reps, warmup, dev):
     return res
 
 
-def render_mode(det, img, dn, meta, rb, reps, warmup, dev):
+N_IMPORTANCE = (0, 64, 128)     # fine samples per ray of the hierarchical-sampling table (0 = the coarse render it is measured against)
+
+
+def importance_table(res, prefix, call, reps, warmup):
+    """``call(k)`` with k fine samples per ray for every k of N_IMPORTANCE, alternating inside one loop; each figure also as a multiple of
+    the k = 0 render of the same loop, next to the (2S + k) / S that compositing S + k samples after S would cost at equal cost a sample."""
+    fns = {f"n_importance_{k}_ms": (lambda k=k: call(k)) for k in N_IMPORTANCE}
+    med, span = timed_alternating(fns, reps, warmup)
+    for k in N_IMPORTANCE:
+        key = f"n_importance_{k}_ms"
+        res[f"{prefix}_{key}"], res[f"{prefix}_{key}_min_max"] = med[key], span[key]
+        res[f"{prefix}_n_importance_{k}_over_0"] = med[key] / med["n_importance_0_ms"]
+        res[f"{prefix}_n_importance_{k}_samples_ratio"] = (2 * 64 + k) / 64 if k else 1.0
+
+
+def render_mode(det, img, dn, meta, rb, reps, warmup, dev, importance_only=False):
     from nerfdet_amd import rays, synth
     res = {}
     n_v = img.shape[1]
@@ -303,6 +321,13 @@ def render_mode(det, img, dn, meta, rb, reps, warmup, dev):
     cams = rays._compute_projection(meta)
     ray_o, ray_d = rb["ray_o"].reshape(-1, 3)[:8192], rb["ray_d"].reshape(-1, 3)[:8192]
     pts, _ = rays.sample_along_camera_ray(ray_o, ray_d, det.near_far_range, 64, det=True)
+    if importance_only:
+        assert det.N_samples == 64
+        fine = scene.render(rb, n_importance=64)
+        assert torch.equal(fine["outputs_coarse"]["rgb"], scene.render(rb)["outputs_coarse"]["rgb"]) and bool(torch.isfinite(fine["outputs_fine"]["rgb"]).all())
+        importance_table(res, "render_1view", lambda k: scene.render(rb, n_importance=k), max(3, reps // 4), 1)
+        res["render_1view_rays"] = int(rb["ray_o"].reshape(-1, 3).shape[0])
+        return res
 
     def regroup(sizes):
         b, v = rays.ViewBank(), 0
@@ -365,10 +390,12 @@ def render_mode(det, img, dn, meta, rb, reps, warmup, dev):
     for k in fns:
         res[f"render_1view_{k}"], res[f"render_1view_{k}_min_max"] = med[k], span[k]
     res["render_1view_rays"] = int(one["ray_o"].reshape(-1, 3).shape[0])
+    # 4. hierarchical sampling: the same target view with 0 / 64 / 128 fine samples a ray
+    importance_table(res, "render_1view", lambda k: scene.render(one, n_importance=k), max(3, reps // 4), 1)
     return res
 
 
-def group_render_mode(det, img, dn, meta, sizes, reps, warmup, dev):
+def group_render_mode(det, img, dn, meta, sizes, reps, warmup, dev, importance_only=False):
     import numpy as np
     from nerfdet_amd import rays, synth
     res = {}
@@ -387,14 +414,14 @@ def group_render_mode(det, img, dn, meta, sizes, reps, warmup, dev):
         for v0 in range(0, n_v, 5):
             group.add_views(img[:, v0:v0 + 5].expand(S, -1, -1, -1, -1).contiguous(), dn[:, v0:v0 + 5].expand(S, -1, -1, -1, -1).contiguous(),
                             [chunk_meta(m, v0, v0 + 5) for m in metas])
-            for st, m in zip(streams, metas):
+            for st, m in zip(streams, metas) if not importance_only else ():
                 st.add_views(img[:, v0:v0 + 5], dn[:, v0:v0 + 5], chunk_meta(m, v0, v0 + 5))
         banks = group.banks
         assert [b.n_views for b in banks] == [n_v] * S and all(len(b.segments) == n_v // 5 for b in banks)
         res[f"S{S}_bank_bytes_per_view"] = banks[0].nbytes() / banks[0].n_views
         res[f"S{S}_banks_mb"] = sum(b.nbytes() for b in banks) / 2 ** 20
         # 1. the sampler alone: one grouped launch against S single-bank launches, every scene with rays of its own
-        for n_rays in (2048, 8192):
+        for n_rays in (2048, 8192) if not importance_only else ():
             pts = []
             for i in range(S):
                 o, d = all_o.roll(-977 * i, 0)[:n_rays], all_d.roll(-977 * i, 0)[:n_rays]
@@ -411,6 +438,13 @@ def group_render_mode(det, img, dn, meta, sizes, reps, warmup, dev):
         # 2. a preview per scene: 2048 rays each
         os_ = [all_o.roll(-977 * i, 0)[:2048].contiguous() for i in range(S)]
         ds_ = [all_d.roll(-977 * i, 0)[:2048].contiguous() for i in range(S)]
+        # 3. hierarchical sampling: the same previews with 0 / 64 / 128 fine samples a ray
+        for batched in (False, True):
+            importance_table(res, f"S{S}_render_rays" + ("_batched" if batched else ""),
+                             lambda k: group.render_rays(os_, ds_, batched=batched, n_importance=k), max(5, reps // 2), warmup)
+        if importance_only:
+            del group, streams, banks
+            continue
         fns = {"group_render_rays_ms": lambda: group.render_rays(os_, ds_), "group_render_rays_batched_ms": lambda: group.render_rays(os_, ds_, batched=True),
                "streams_render_rays_ms": lambda: [st.render_rays(o, d) for st, o, d in zip(streams, os_, ds_)]}
         plain, bat = fns["group_render_rays_ms"](), fns["group_render_rays_batched_ms"]()
@@ -451,6 +485,7 @@ def main():
     ap.add_argument("--window", type=str, default=None, help="comma-separated window sizes in chunks of 5 views, e.g. 1,4,8")
     ap.add_argument("--render", action="store_true", help="time rendering from a streamed scene (the view-bank sampler)")
     ap.add_argument("--group", type=str, default=None, help="comma-separated scene-group sizes, e.g. 1,4,8,16")
+    ap.add_argument("--importance-only", action="store_true", help="with --render: only the n_importance 0 / 64 / 128 table")
     ap.add_argument("--group-window", type=str, default=None, help="comma-separated scenes:window configurations of windowed groups, e.g. 8:4,8:8")
     args = ap.parse_args()
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
@@ -466,14 +501,14 @@ def main():
     res = {}
     if args.render and args.group:
         with torch.no_grad():
-            res = group_render_mode(det, img, dn, meta, [int(v) for v in args.group.split(",")], args.reps, args.warmup, dev)
+            res = group_render_mode(det, img, dn, meta, [int(v) for v in args.group.split(",")], args.reps, args.warmup, dev, args.importance_only)
         for k, v in res.items():
             print(f"{k:>52}: " + (f"{v:.3e}" if isinstance(v, float) and "max_abs" in k else f"{v:.3f}" if isinstance(v, float) else str(v)))
         print(json.dumps(res))
         return
     if args.render:
         with torch.no_grad():
-            res = render_mode(det, img, dn, meta, rb, args.reps, args.warmup, dev)
+            res = render_mode(det, img, dn, meta, rb, args.reps, args.warmup, dev, args.importance_only)
         for k, v in res.items():
             print(f"{k:>44}: " + (f"{v:.3f}" if isinstance(v, float) else str(v)))
         print(json.dumps(res))
