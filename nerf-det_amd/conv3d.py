@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import struct
 from ctypes import c_void_p
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -197,6 +198,13 @@ def carry_amax(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
 def amax_value(slot: torch.Tensor) -> float:
     """Host read-back of a slot (tests / diagnostics; synchronises)."""
     return float(slot.view(-1, 32)[:, 0].max())
+
+
+def tilemin_value(slot: torch.Tensor) -> float:
+    """Host read-back of word 1 of a slot: the smallest non-zero tile maximum its producer recorded (what conv_tilemin_read hands the range guard),
+    0.0 when nothing was recorded (tests / diagnostics; synchronises)."""
+    v = int(slot.view(torch.int32).view(-1, 32)[:, 1].max())
+    return 0.0 if v == 0 else struct.unpack("<f", struct.pack("<I", 0x7f800000 - v))[0]
 
 
 _slot_width_checked = False

@@ -130,6 +130,27 @@ __device__ __forceinline__ void conv_amax_commit(float* slot, float mx) {
     }
 }
 
+// The same for a PERSISTENT workgroup that wrote several tiles (k_stem_conv_pool, k_conv_split_wsp): word 0 takes the maximum over all of its tiles,
+// word 1 the smallest non-zero maximum of ONE tile -- folding the tiles of a workgroup into one value would hide a dim tile behind the bright ones the
+// same workgroup happened to be dealt, and the next layer's guard would never see it.  `mx`: this thread's running max |v| over every tile;
+// `tmin`: the smallest non-zero tile maximum this thread knows of, +inf for none (the callers keep it workgroup-uniform; any thread's value counts).
+// The atomics and the sub-slot addressing are conv_amax_commit's.  Every thread of the workgroup must arrive (there is a barrier inside).
+__device__ __forceinline__ void conv_amax_commit_tiles(float* slot, float mx, float tmin) {
+    __shared__ float wg_tmax[16], wg_tmin[16];
+#pragma unroll
+    for (int o = 32; o; o >>= 1) { mx = fmaxf(mx, __shfl_xor(mx, o)); tmin = fminf(tmin, __shfl_xor(tmin, o)); }
+    const int nw = ((int)blockDim.x + 63) >> 6;
+    if ((threadIdx.x & 63) == 0) { wg_tmax[threadIdx.x >> 6] = mx; wg_tmin[threadIdx.x >> 6] = tmin; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < nw; ++i) { mx = fmaxf(mx, wg_tmax[i]); tmin = fminf(tmin, wg_tmin[i]); }
+        const unsigned bits = __float_as_uint(mx), tbits = __float_as_uint(tmin);
+        unsigned* sub = reinterpret_cast<unsigned*>(slot) + conv_xcc_id() * NDET_AMAX_STRIDE;
+        if (bits) atomicMax(sub, bits);
+        if (tbits && tbits < 0x7f800000u) atomicMax(sub + 1, 0x7f800000u - tbits);
+    }
+}
+
 // The smallest non-zero maximum any workgroup committed for the tensor behind `slot` (0: none recorded).  Every lane of the calling wave must be
 // active (shuffles).
 __device__ __forceinline__ float conv_tilemin_read(const float* slot) {
@@ -145,7 +166,10 @@ __device__ __forceinline__ float conv_tilemin_read(const float* slot) {
 //   (2) some part of the input really lives below the fp16-pair window: the smallest workgroup-tile maximum recorded for it is below 2^-16 of the
 //       tensor's maximum.  Where every region of a tensor is within 2^-16 of its maximum, outputs of that region carry an fp32-class error of
 //       ~2^-22 |w||a| >= the floor anyway (a uniformly large tensor -- a deep un-normalised network's activations of 1e6 -- loses nothing to the
-//       per-tensor scale; without (2) the ResNet-101 workload tripped on every scene).  Tile granularity: 64 - 128 rows x the tile's channels.
+//       per-tensor scale; without (2) the ResNet-101 workload tripped on every scene).  Granularity: the region ONE workgroup writes in one go, never
+//       more than its tile -- 64 - 128 rows x the tile's channels for the convolutions (the persistent tiles record every tile of their walk, not
+//       their walk), 3 x 8 pooled pixels x 64 channels of one image for the stem, one contiguous range of rows for the elementwise passes.  Structure
+//       smaller than that is not seen (tests/test_guard_tilemin_gpu.py pins both).
 // Every thread of workgroup 0 must call (the slot reads shuffle).
 __device__ __forceinline__ void conv_guard_check(const Conv3dParams& p, float amax_in) {
     if (!p.guard || blockIdx.x != 0 || blockIdx.y != 0 || blockIdx.z != 0) return;

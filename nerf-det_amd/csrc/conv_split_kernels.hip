@@ -1096,7 +1096,20 @@ __global__ __launch_bounds__(64 * (NCONS + 4), 1) void k_conv_split_wsp(const Co
     const float xs = SCH == 1 ? conv_xscale(p.amax_in) : 1.0f;
     const float osc = conv_oscale(p);
     if (SCH == 1) conv_guard_check(p, conv_amax_in(p));
-    float mx = 0.0f;
+    // The slot's two words (conv_amax_commit_tiles): mx = max |out| over every tile of this workgroup's walk; tmin = the smallest non-zero maximum of ONE
+    // BM x 256 tile of the table (not of a wave's part of it: the consumer waves' maxima of a tile meet in s_tmax behind the barrier that opens the
+    // next tile's K walk -- no barrier and no atomic of its own).  Two buffers: tile k's maxima are read behind the first barrier of tile k + 1 and
+    // written again in the epilogue of tile k + 2, which lies behind that tile's first barrier.
+    __shared__ float s_tmax[2][NCONS];
+    const bool track = p.amax_out != nullptr && p.splits == 1;
+    float mx = 0.0f, tmin = INFINITY;
+    int kt = 0;                                           // tiles this workgroup has finished
+    auto fold_tile = [&](int k) {
+        float m = s_tmax[k & 1][0];
+#pragma unroll
+        for (int i = 1; i < NCONS; ++i) m = fmaxf(m, s_tmax[k & 1][i]);
+        if (m > 0.0f) tmin = fminf(tmin, m);              // (an all-zero tile is exact in any arithmetic: not recorded)
+    };
     const int wm = (wave % NCONS) / CW, wn = (wave % NCONS) % CW;
 
     const int cin_steps = p.Cin / CBK;
@@ -1108,7 +1121,7 @@ __global__ __launch_bounds__(64 * (NCONS + 4), 1) void k_conv_split_wsp(const Co
     const int G = gridDim.x;
     const int vb = (G & 7) == 0 ? (int)(blockIdx.x & 7) * (G >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
 
-    for (int tile = vb; tile < n_tiles; tile += G) {
+    for (int tile = vb; tile < n_tiles; tile += G, ++kt) {
         const int nt = tile % n_nt, mt = (tile / n_nt) % n_mt, zs = tile / (n_nt * n_mt);
         const int m0 = mt * BM, n0 = nt * WS_BN;
         int it_begin = 0, it_end = n_iters_all;
@@ -1254,6 +1267,8 @@ __global__ __launch_bounds__(64 * (NCONS + 4), 1) void k_conv_split_wsp(const Co
             const int aoff = (wm * 64 + frow) * CBK + kc;
             const int boff = NPL * APL + (wn * WNC + frow) * CBK + kc;
             __syncthreads();
+            if (track && kt > 0) fold_tile(kt - 1);       // the previous tile's maximum, all consumer waves' parts of it
+            float tmx = 0.0f;                             // this thread's part of this tile's
             for (int j = 0; j < n_round; ++j) {
                 if (j < n_it) {
                     const uint16_t* st = lds16 + (j & 1) * STAGE;
@@ -1335,14 +1350,24 @@ __global__ __launch_bounds__(64 * (NCONS + 4), 1) void k_conv_split_wsp(const Co
                             if (p.relu == 2) v = fmaxf(v, 0.f);
                             if (has_res) v = v + rr[ta][r];
                             if (p.relu == 1) v = fmaxf(v, 0.f);
-                            if (rowl + 16 * ta + r < p.M) mx = fmaxf(mx, fabsf(v));
+                            if (rowl + 16 * ta + r < p.M) tmx = fmaxf(tmx, fabsf(v));
                         }
                         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rout, vo, so, 0);
                     }
             }
+            if (track) {
+                mx = fmaxf(mx, tmx);
+#pragma unroll
+                for (int o = 32; o; o >>= 1) tmx = fmaxf(tmx, __shfl_xor(tmx, o));
+                if (lane == 0) s_tmax[kt & 1][wave] = tmx;
+            }
         }
     }
-    if (p.amax_out && p.splits == 1) conv_amax_commit(p.amax_out, mx);
+    if (track) {
+        __syncthreads();                                  // the last tile's maxima
+        if (kt > 0) fold_tile(kt - 1);
+        conv_amax_commit_tiles(p.amax_out, mx, tmin);
+    }
 }
 
 template <int BM, int NCONS>

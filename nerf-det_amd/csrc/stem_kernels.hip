@@ -60,6 +60,8 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv_pool(const StemParams p) {
     __shared__ __attribute__((aligned(16))) uint16_t P[NPL * 3 * ST_IY * ST_PITCH];   // [plane][c][iy][pitch]
     __shared__ __attribute__((aligned(16))) float Cs[128 * ST_CLD];
     __shared__ float s_pmax[4];
+    __shared__ __attribute__((aligned(16))) float s_tmax[4];            // the waves' maxima of the tile pooled last (written at the top of the next
+                                                                        // iteration, read behind its first barrier)
     constexpr int PPL = 3 * ST_IY * ST_PITCH;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -106,7 +108,18 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv_pool(const StemParams p) {
             ra[i] = ok ? base[c * p.sc + y * p.sy + x * p.sx] : 0.0f;
         }
     };
-    float omax = 0.0f;
+    // max |out| over all of this workgroup's tiles (word 0 of the slot) and the smallest non-zero maximum of ONE of its tiles (word 1: the range
+    // guard's tile minimum -- the tiles of a persistent workgroup lie 512 apart, in different images: one value for all of them hides a dim image)
+    // A tile's maximum crosses the workgroup on what the NEXT iteration does anyway: the waves reduce it beside the patch maximum (one shuffle chain
+    // for both), and the barrier behind it publishes it -- no barrier and no atomic of its own inside the loop; the last tile's follows the loop.
+    float omax = 0.0f, tmin = INFINITY;
+    float tprev = 0.0f;                                                  // this thread's part of the maximum of the tile pooled last (0: none yet)
+    const bool track = p.amax_out != nullptr;
+    auto fold_tile = [&]() {
+        const float4 w = *reinterpret_cast<const float4*>(s_tmax);
+        const float m = fmaxf(fmaxf(w.x, w.y), fmaxf(w.z, w.w));
+        if (m > 0.0f) tmin = fminf(tmin, m);                             // (an all-zero tile is exact in any arithmetic: not recorded)
+    };
     __syncthreads();
     int t = blockIdx.x;
     if (t < p.tiles) load_patch(t);
@@ -118,12 +131,21 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv_pool(const StemParams p) {
 #pragma unroll
             for (int i = 0; i < ST_EPT; ++i) m = fmaxf(m, fabsf(ra[i]));
 #pragma unroll
-            for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-            if (lane == 0) s_pmax[wave] = m;
+            for (int o = 32; o; o >>= 1) {
+                m = fmaxf(m, __shfl_xor(m, o));
+                tprev = fmaxf(tprev, __shfl_xor(tprev, o));              // (with or without a slot: a branch here would put the two chains in a row)
+            }
+            if (lane == 0) { s_pmax[wave] = m; s_tmax[wave] = tprev; }
             __syncthreads();                                             // (also: the previous tile's MFMA reads of P are done -- all waves passed (B))
             m = fmaxf(fmaxf(s_pmax[0], s_pmax[1]), fmaxf(s_pmax[2], s_pmax[3]));
             xs = conv_xscale_of(m);
             xinv = conv_xinv_of(m) * p.winv;
+            if (track) fold_tile();                                      // (s_tmax is rewritten behind (A) and (B): every read here is done by then; zeros
+                                                                         // in the first iteration: nothing recorded)
+        } else if (track) {                                              // (the six-product form has no patch maximum to ride on: a chain of its own)
+#pragma unroll
+            for (int o = 32; o; o >>= 1) tprev = fmaxf(tprev, __shfl_xor(tprev, o));
+            if (lane == 0) s_tmax[wave] = tprev;
         }
 #pragma unroll
         for (int i = 0; i < ST_EPT; ++i)
@@ -143,6 +165,7 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv_pool(const StemParams p) {
                 }
             }
         __syncthreads();                                             // (A) patch complete; the previous tile's pooling has read Cs
+        if (SCH != 1 && track) fold_tile();                          // (the six-product form: the waves' parts of the last tile's maximum meet here)
         const int tn = t + gridDim.x;
         if (tn < p.tiles) load_patch(tn);                            // the next patch travels during the multiplication
 
@@ -191,6 +214,7 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv_pool(const StemParams p) {
         {
             const int tx = t % p.tiles_x, ty = (t / p.tiles_x) % p.tiles_y, n = t / (p.tiles_x * p.tiles_y);
             const int cy0 = 2 * ty * ST_TPY - 1, cx0 = 2 * tx * ST_TPX - 1;
+            float tmax = 0.0f;
             for (int w = tid; w < ST_TPY * ST_TPX * 16; w += 256) {
                 const int q = w & 15, pp = w >> 4, ppy = pp / ST_TPX, ppx = pp - ppy * ST_TPX;
                 const int py = ty * ST_TPY + ppy, px = tx * ST_TPX + ppx;
@@ -207,13 +231,22 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv_pool(const StemParams p) {
                         }
                     }
                 *reinterpret_cast<float4*>(p.out + (((int64_t)n * p.PH + py) * p.PW + px) * 64 + q * 4) = m;
-                omax = fmaxf(fmaxf(omax, fmaxf(m.x, m.y)), fmaxf(m.z, m.w));       // (post-ReLU: non-negative)
+                tmax = fmaxf(fmaxf(tmax, fmaxf(m.x, m.y)), fmaxf(m.z, m.w));       // (post-ReLU: non-negative)
             }
+            omax = fmaxf(omax, tmax);
+            tprev = tmax;                                                // this tile's maximum crosses the workgroup in the next iteration
         }
         // the next iteration's patch stores touch P only; its barrier (A) orders them against this tile's MFMA reads (all waves passed (B))
         // and orders the next Cs writes against this pooling
     }
-    if (p.amax_out) conv_amax_commit(p.amax_out, omax);                  // once per persistent workgroup
+    if (track) {                                                         // once per persistent workgroup: both words
+#pragma unroll
+        for (int o = 32; o; o >>= 1) tprev = fmaxf(tprev, __shfl_xor(tprev, o));
+        if (lane == 0) s_tmax[wave] = tprev;                             // the last tile's maximum (the reads behind its (A) are done: all waves passed (B))
+        __syncthreads();
+        fold_tile();
+        conv_amax_commit_tiles(p.amax_out, omax, tmin);
+    }
 }
 
 // stem weight (64, 3, 7, 7) fp32 -> (3 planes, 64, 176) bf16 with k = (ky * 3 + c) * 8 + kx; kx = 7 and k >= 168 are zero
