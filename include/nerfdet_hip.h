@@ -797,6 +797,21 @@ int ndet_target_rays(const uint8_t* frames_bgr, const int* target_ids, int n_tar
                      const float* intrinsic_rows, const float* camrotc2w, const float* cam_lightpos, const double* mean_rgb,
                      const double* std_rgb, float* raydirs, float* lightpos, float* gt_images, void* stream);
 
+/* ndet_resize_normalize_views: the same contract from frames at CAPTURE resolution, frames_bgr (n_frames,Hs,Ws,3) uint8 BGR -- the
+ * configs' Resize(keep_ratio) -> Normalize -> Pad (configs/nerfdet/nerfdet_res101_2x_low_res.py:95-97, applied per view by
+ * mmdet3d/datasets/pipelines/multi_view.py:90-110) in one launch.  For each selected frame ids[v] (ids == NULL: frames 0 .. n_sel-1):
+ *   content [0,Hr) x [0,Wr) of the H x W outputs: the byte of nerfdet_amd.datasets.imresize_linear(frame, (Wr, Hr)) bit for bit
+ *     (cv2.INTER_LINEAR: two taps per axis at float32(float64((d + 0.5) * (src / dst) - 0.5)), clamped at the borders, 11-bit
+ *     fixed-point weights, two-stage rounding; Hr == Hs && Wr == Ws is a copy; upscaling is allowed), then ndet_normalize_views'
+ *     float32 arithmetic on that byte: img RGB planes, denorm BGR planes;
+ *   pad, the rest: img = 0.0f (Pad follows Normalize), denorm = (float)(unsigned char)(int)mean_c / 255.0f, resized_bgr = 0.
+ * img, denorm (n_sel,3,H,W); resized_bgr NULL or (n_sel,H,W,3) uint8.  Every element of every output is written.  Frame offsets are
+ * 64-bit.  Refused before any device work: a null pointer other than ids / resized_bgr, a non-positive size, std <= 0, Hr > H or
+ * Wr > W (NDET_E_INVALID); Hs * Ws * 3 >= 2^31 or H * W * 3 >= 2^31 (NDET_E_UNSUPPORTED). */
+int ndet_resize_normalize_views(const uint8_t* frames_bgr, const int* ids, int n_sel, int Hs, int Ws, int Hr, int Wr, int H, int W,
+                                const double* mean_rgb, const double* std_rgb, float* img, float* denorm, uint8_t* resized_bgr,
+                                void* stream);
+
 /* Weight-gradient staging for the training-time convolutions (autograd of nn.Conv3d / nn.Conv2d in
  * mmdet3d/models/necks/imvoxelnet.py:22-67,233-260 and of the third-party ResNet/FPN layers): channels-last x (D,H,W,C) -> rows
  * out[t - t0][c][j] = x[stride * o(j) + tap(t) - pad][c] over the flattened OUTPUT grid of the (kernel, stride, pad) convolution, taps

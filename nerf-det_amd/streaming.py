@@ -40,6 +40,11 @@ state of its own through the same grouped accumulate (ops.scene_accumulate_group
 the listed scenes' windows with one grouped density ring finish, one sigma-MLP call and one grouped volume ring finish
 (ops.density_finish_group_ring / volume_finish_group_ring), whose outputs are the single-scene ring finishes' bit for bit.
 
+``scene.add_frames(frames, img_meta)`` / ``group.add_frames(frames, metas, scenes=None)`` take frames at CAPTURE resolution, uint8 BGR
+(1 or len(scenes), k, Hs, Ws, 3) on the device, instead of prepared tensors: the frames are checked against the scene's meta (``ori_shape``,
+``img_shape``, ``pad_shape``: pipeline.frame_meta), resized, normalised and padded in ONE launch for the whole call (pipeline.prepare_frames,
+ndet_resize_normalize_views; ``mean`` / ``std`` are ``begin_scene(s)`` keywords) and handed to ``add_views``, which does the rest.
+
 Inference only: no training / autograd, no hipGraph replay, one scene per stream; whole chunks are dropped, not single views out of one.
 Without ``keep_views`` there is no ray branch (rendering needs every view's map).
 """
@@ -52,9 +57,18 @@ import numpy as np
 import torch
 
 from . import conv3d, ops
+from .pipeline import IMG_MEAN, IMG_STD, prepare_frames, rescale_size
 from .volume import map_features_2d, map_features_2d_hip
 
 Tensor = torch.Tensor
+
+
+def _norm_cfg(mean, std):
+    """``begin_scene(s)``'s img-norm ``mean`` / ``std`` (RGB) as tuples of three floats, ``std`` positive; else ValueError."""
+    mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+    if len(mean) != 3 or len(std) != 3 or min(std) <= 0.0:
+        raise ValueError(f"mean and std must hold three values each, std positive; got {mean} and {std}")
+    return mean, std
 
 
 def check_chunk_meta(scene_meta: dict, img_meta: dict, k: int) -> None:
@@ -68,6 +82,29 @@ def check_chunk_meta(scene_meta: dict, img_meta: dict, k: int) -> None:
             raise ValueError(f"add_views: the chunk's {key} {tuple(b[key])} differs from the scene's {tuple(a[key])}")
     if len(b["lidar2img"]["extrinsic"]) != k:
         raise ValueError(f"add_views: {len(b['lidar2img']['extrinsic'])} extrinsics for {k} views")
+
+
+def check_frames_meta(scene_meta: dict, frames: Tensor, n: int):
+    """``add_frames``'s own checks, before any device work: ``frames`` is (n, k, Hs, Ws, 3) uint8 with ``(Hs, Ws)`` the scene's
+    ``ori_shape``, and the scene's ``img_shape`` is what ``Resize(keep_ratio=True)`` into the ``pad_shape`` box makes of such a frame
+    (pipeline.rescale_size; a meta without ``pad_shape`` is unpadded: ``pad_shape = img_shape``).  Returns ``(img_scale, pad_size)`` as
+    pipeline.prepare_frames takes them, else ValueError."""
+    if frames.dim() != 5 or frames.shape[0] != n or frames.shape[1] < 1 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
+        raise ValueError(f"add_frames takes raw uint8 BGR frames ({n}, k, Hs, Ws, 3); got {tuple(frames.shape)} {frames.dtype}")
+    hs, ws = int(frames.shape[2]), int(frames.shape[3])
+    if (hs, ws) != tuple(scene_meta["ori_shape"][:2]):
+        raise ValueError(f"add_frames: frames of {(hs, ws)} differ from the scene's ori_shape {tuple(scene_meta['ori_shape'])}")
+    img_shape = tuple(scene_meta["img_shape"][:2])
+    h, w = tuple(scene_meta.get("pad_shape", scene_meta["img_shape"])[:2])
+    if rescale_size((hs, ws), (w, h)) != img_shape:
+        raise ValueError(f"add_frames: a {(hs, ws)} frame rescales to {rescale_size((hs, ws), (w, h))} inside pad_shape {(h, w)}, "
+                         f"not to the scene's img_shape {img_shape}")
+    return (w, h), (h, w)
+
+
+def _check_pad_shape(scene_meta: dict, img_meta: dict) -> None:
+    if "pad_shape" in img_meta and tuple(img_meta["pad_shape"]) != tuple(scene_meta.get("pad_shape", scene_meta["img_shape"])):
+        raise ValueError(f"add_frames: the chunk's pad_shape {tuple(img_meta['pad_shape'])} differs from the scene's")
 
 
 def _check_n_importance(n_importance) -> int:
@@ -106,8 +143,10 @@ class SceneStream:
     keep the views' mapped maps, images and cameras (``bank``, a rays.ViewBank) so that :meth:`render_rays` / :meth:`render` work."""
 
     bank = None     # rays.ViewBank with keep_views, else None
+    mean, std = IMG_MEAN, IMG_STD     # img_norm_cfg of add_frames (RGB)
 
-    def __init__(self, det, img_meta: dict, window: Optional[int] = None, keep_views: bool = False):
+    def __init__(self, det, img_meta: dict, window: Optional[int] = None, keep_views: bool = False, mean=IMG_MEAN, std=IMG_STD):
+        self.mean, self.std = _norm_cfg(mean, std)
         if not isinstance(keep_views, bool):
             raise ValueError(f"keep_views must be a bool, got {keep_views!r}")
         if window is not None and (isinstance(window, bool) or not isinstance(window, int) or not 1 <= window <= ops.RING_MAX):
@@ -202,14 +241,8 @@ class SceneStream:
         x, _, stride = self.det.extract_2d(img)
         return x, getattr(x, "_ndet_feature_2d", None), stride
 
-    def add_views(self, img: Tensor, denorm_images: Tensor, img_meta: dict, depth: Optional[Tensor] = None) -> None:
-        """Fold k >= 1 views into the scene.  ``img``, ``denorm_images`` (1, k, 3, H, W); ``img_meta`` the chunk's (its ``extrinsic`` list has
-        k entries; the rest must equal the scene's, else ValueError); ``depth`` None or (1, k, Hd, Wd) float32 / float64: the chunk's views are
-        depth-gated as by ``simple_test(depth=)`` (nerfdet.py:404-411).
-
-        Range guard of the fp16-pair arithmetic: the guard word is cleared before the chunk's backbone and read back before the chunk enters
-        the state -- one 4-byte device-to-host read (a synchronisation) per chunk.  A tripped chunk is redone on bf16x3 first
-        (``conv3d.guard_trips`` counts it), so no tripped chunk reaches the state."""
+    def _check_chunk(self, img: Tensor, denorm_images: Tensor, img_meta: dict, depth) -> None:
+        """Everything add_views refuses, before anything is launched (only shapes are read)."""
         if img.dim() != 5 or img.shape[0] != 1:
             raise ValueError(f"add_views takes one scene's chunk, (1, k, 3, H, W); got {tuple(img.shape)}")
         k = img.shape[1]
@@ -220,6 +253,33 @@ class SceneStream:
         self._check_meta(img_meta, k)
         if self.det.training:
             raise RuntimeError("SceneStream is inference only: call det.eval() first")
+
+    def add_frames(self, frames: Tensor, img_meta: dict, depth: Optional[Tensor] = None) -> None:
+        """:meth:`add_views` for k >= 1 frames at CAPTURE resolution: ``frames`` (1, k, Hs, Ws, 3) uint8 BGR on the device, as a decode
+        engine leaves them.  The scene's meta says what becomes of them (pipeline.frame_meta makes such a meta): ``(Hs, Ws)`` must be its
+        ``ori_shape``, its ``img_shape`` what ``Resize(keep_ratio=True)`` into the ``pad_shape`` box gives (pipeline.rescale_size;
+        ``pad_shape`` absent: ``img_shape``), else ValueError -- raised, like everything :meth:`add_views` refuses, before any device
+        work.  One ndet_resize_normalize_views launch then makes the chunk's ``img`` and ``denorm_images`` (1, k, 3, H, W) at the padded
+        size -- ``datasets.imresize_linear``'s bytes, normalised with ``mean`` / ``std`` of ``begin_scene`` as ndet_normalize_views does, then
+        padded, as the configs' Resize -> Normalize -> Pad -- and :meth:`add_views` takes them: guard, window, bank and the promise that a call that raises changes nothing are its own.  ``depth`` passes through
+        (ops.depth_gate resizes it to ``img_shape``)."""
+        img_scale, pad_size = check_frames_meta(self.meta, frames, 1)
+        _check_pad_shape(self.meta, img_meta)
+        k = frames.shape[1]
+        shape = torch.empty((1, k, 3) + pad_size, device="meta")
+        self._check_chunk(shape, shape, img_meta, depth)
+        img, denorm = prepare_frames(frames[0], img_scale, pad_size, self.mean, self.std)
+        self.add_views(img.unsqueeze(0), denorm.unsqueeze(0), img_meta, depth=depth)
+
+    def add_views(self, img: Tensor, denorm_images: Tensor, img_meta: dict, depth: Optional[Tensor] = None) -> None:
+        """Fold k >= 1 views into the scene.  ``img``, ``denorm_images`` (1, k, 3, H, W); ``img_meta`` the chunk's (its ``extrinsic`` list has
+        k entries; the rest must equal the scene's, else ValueError); ``depth`` None or (1, k, Hd, Wd) float32 / float64: the chunk's views are
+        depth-gated as by ``simple_test(depth=)`` (nerfdet.py:404-411).
+
+        Range guard of the fp16-pair arithmetic: the guard word is cleared before the chunk's backbone and read back before the chunk enters
+        the state -- one 4-byte device-to-host read (a synchronisation) per chunk.  A tripped chunk is redone on bf16x3 first
+        (``conv3d.guard_trips`` counts it), so no tripped chunk reaches the state."""
+        self._check_chunk(img, denorm_images, img_meta, depth)
         with torch.no_grad():
             guarded = conv3d.ARITHMETIC == "f16x2" and img.is_cuda
             if guarded:
@@ -405,8 +465,10 @@ class SceneGroup:
     pool = None         # ops.SceneGroupRingState of a windowed group
     group = None        # ops.SceneGroupState of an unwindowed one
     banks = None        # with keep_views one rays.ViewBank per scene, else None
+    mean, std = IMG_MEAN, IMG_STD     # img_norm_cfg of add_frames (RGB)
 
-    def __init__(self, det, img_metas, window: Optional[int] = None, keep_views: bool = False):
+    def __init__(self, det, img_metas, window: Optional[int] = None, keep_views: bool = False, mean=IMG_MEAN, std=IMG_STD):
+        self.mean, self.std = _norm_cfg(mean, std)
         if not isinstance(keep_views, bool):
             raise ValueError(f"keep_views must be a bool, got {keep_views!r}")
         if window is not None:
@@ -529,6 +591,24 @@ class SceneGroup:
     def _features(self, img: Tensor):
         x, _, stride = self.det.extract_2d(img)
         return x, getattr(x, "_ndet_feature_2d", None), stride
+
+    def add_frames(self, frames: Tensor, metas, scenes=None, depth: Optional[Tensor] = None) -> None:
+        """:meth:`add_views` for frames at CAPTURE resolution: ``frames`` (len(scenes), k, Hs, Ws, 3) uint8 BGR on the device, one row of k
+        frames per listed scene.  The group's meta says what becomes of them, as in :meth:`SceneStream.add_frames`: ``(Hs, Ws)`` must be
+        its ``ori_shape`` and its ``img_shape`` what ``Resize(keep_ratio=True)`` into the ``pad_shape`` box gives, else ValueError --
+        raised, like everything :meth:`add_views` refuses, before any device work.  ONE ndet_resize_normalize_views launch over all the
+        ``len(scenes) * k`` frames makes ``img`` and ``denorm_images`` (with ``mean`` / ``std`` of ``begin_scenes``), and :meth:`add_views` takes them: guard, windows, banks and the promise that a call that raises changes
+        nothing are its own.  ``depth`` passes through."""
+        n = len(ops.listed_scenes(self.n_scenes, scenes))
+        img_scale, pad_size = check_frames_meta(self.metas[0], frames, n)
+        metas = list(metas)
+        for m in metas:
+            _check_pad_shape(self.metas[0], m)
+        k = frames.shape[1]
+        shape = torch.empty((n, k, 3) + pad_size, device="meta")
+        self._check_call(shape, shape, metas, scenes, depth)
+        img, denorm = prepare_frames(frames.reshape((n * k,) + tuple(frames.shape[2:])), img_scale, pad_size, self.mean, self.std)
+        self.add_views(img.view((n, k) + tuple(img.shape[1:])), denorm.view((n, k) + tuple(denorm.shape[1:])), metas, scenes=scenes, depth=depth)
 
     def add_views(self, img: Tensor, denorm_images: Tensor, metas, scenes=None, depth: Optional[Tensor] = None) -> None:
         """Fold k views into each listed scene.  ``img``, ``denorm_images`` (len(scenes), k, 3, H, W), one row per listed scene; ``metas`` one
