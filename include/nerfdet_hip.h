@@ -812,6 +812,35 @@ int ndet_resize_normalize_views(const uint8_t* frames_bgr, const int* ids, int n
                                 const double* mean_rgb, const double* std_rgb, float* img, float* denorm, uint8_t* resized_bgr,
                                 void* stream);
 
+/* ---- depth frames: the loader's `depth`, `gt_depths` and `depth_rays` from the sensor's frames, frames_mm (n_frames,Hd,Wd) uint16
+ * millimetres resident on the device.
+ *
+ * ndet_depth_frames: for each selected frame ids[v] (ids == NULL: frames 0 .. n_sel-1) the map
+ * nerfdet_amd.datasets.imresize_linear(frame / 1000, (w, h)) in float64, bit for bit -- mmcv.imresize of the float64 metres, as
+ * mmdet3d/datasets/pipelines/multi_view.py:98-105 resizes a selected view's depth to the meta's img_shape and multi_view.py:156-166 a
+ * target view's to gt_rgb_shape, the PADDED image size -- of which only the crop [margin, h-margin) x [margin, w-margin) is computed
+ * and stored: out (n_sel, h-2*margin, w-2*margin) float64, every element written.  Each tap is double(u16) / 1000.0; positions
+ * float32(float64((d + 0.5) * (src / dst) - 0.5)), floor, both border clamps; weight f float32 widened to float64, 1 - f formed in
+ * float64; a * (1 - fx) + b * fx per source row, then h0 * (1 - fy) + h1 * fy; every product and sum rounded on its own (no FMA);
+ * h == Hd && w == Wd is the copy frame / 1000.  Frame offsets are 64-bit, offsets inside a frame or a map 32-bit.  Refused before any
+ * device work: a null pointer other than ids, a non-positive size, margin < 0 or a margin that leaves no pixel (NDET_E_INVALID);
+ * Hd * Wd >= 2^31 or (h-2*margin) * (w-2*margin) >= 2^31 (NDET_E_UNSUPPORTED). */
+int ndet_depth_frames(const uint16_t* frames_mm, const int* ids, int n_sel, int Hd, int Wd, int h, int w, int margin, double* out,
+                      void* stream);
+
+/* ndet_positive_indices: the rays WITH depth of the training-time ray draw, render_ray.py:386-404 (torch.nonzero(gt_depth > 0)) and
+ * nerfdet_amd/datasets.py:293 (np.flatnonzero on the loader's side): indices[0 .. K) = the i with x[i] > 0 in ascending order, int64,
+ * and count[0] = K, for x (n) float64 on the device; NaN, zeros of either sign and negative values are left out; indices[K .. n) is
+ * not written.  ONE kernel launch behind a memset node that zeroes the workspace (ndet_positive_indices_workspace_bytes(n) bytes
+ * of device memory, 16-byte aligned, contents irrelevant on entry): a single-pass scan over tiles of 256 elements; no atomic decides
+ * where an index goes, so two calls on the same x write the same bytes.  Waits inside the kernel are bounded: should one run out,
+ * count[0] = -1 and indices is unspecified.  indices holds n elements; count is a device int64.  Refused before any device work: a
+ * null pointer, n <= 0, a misaligned workspace (NDET_E_INVALID); n >= 2^31 (NDET_E_UNSUPPORTED). */
+int ndet_positive_indices(const double* x, int64_t n, int64_t* indices, int64_t* count, void* workspace, void* stream);
+
+/* Workspace of ndet_positive_indices for n elements (render_ray.py:386-404), in bytes; 0 for an n the entry point refuses. */
+int64_t ndet_positive_indices_workspace_bytes(int64_t n);
+
 /* Weight-gradient staging for the training-time convolutions (autograd of nn.Conv3d / nn.Conv2d in
  * mmdet3d/models/necks/imvoxelnet.py:22-67,233-260 and of the third-party ResNet/FPN layers): channels-last x (D,H,W,C) -> rows
  * out[t - t0][c][j] = x[stride * o(j) + tap(t) - pad][c] over the flattened OUTPUT grid of the (kernel, stride, pad) convolution, taps

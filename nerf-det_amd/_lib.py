@@ -163,6 +163,9 @@ SIGNATURES = {
     "ndet_normalize_views": ([_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P], c_int),
     "ndet_target_rays": ([_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P], c_int),
     "ndet_resize_normalize_views": ([_P, _P] + [c_int] * 7 + [_P] * 6, c_int),
+    "ndet_depth_frames": ([_P, _P] + [c_int] * 6 + [_P, _P], c_int),
+    "ndet_positive_indices": ([_P, c_int64, _P, _P, _P, _P], c_int),
+    "ndet_positive_indices_workspace_bytes": ([c_int64], c_int64),
     "ndet_stem_pack_weights": ([_P, _P, _P], c_int),
     "ndet_stem_conv_bn_relu_maxpool": ([_P, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, _P, c_float, _P, _P, _P, _P, _P], c_int),
     "ndet_stem_pack_weights_f16x2": ([_P, c_float, _P, _P], c_int),

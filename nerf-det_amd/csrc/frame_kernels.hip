@@ -12,6 +12,7 @@
 //   (2048, 0) on both axes, and ((2048 * (2048 * p >> 4) >> 16) + 2) >> 2 == p: the copy the host function makes.  Every intermediate
 //   fits int32: 2049 * ((255 * 2049) >> 4) < 2^26.
 #include "ndet_common.hpp"
+#include "frame_tap.hpp"
 
 struct FrameTap {
     int s0, s1;   // source index of the two taps
@@ -19,16 +20,12 @@ struct FrameTap {
 };
 
 __device__ __forceinline__ FrameTap frame_tap(int d, double scale /* n_src / n_dst */, int n_src) {
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f = f - (float)s;
-    if (s < 0) { f = 0.0f; s = 0; }
-    if (s >= n_src - 1) { f = 0.0f; s = n_src - 1; }
+    const FramePos p = frame_pos(d, scale, n_src);
     FrameTap t;
-    t.s0 = s;
-    t.s1 = s + 1 < n_src ? s + 1 : n_src - 1;
-    t.a1 = (int)rintf(f * 2048.0f);
-    t.a0 = (int)rintf((1.0f - f) * 2048.0f);
+    t.s0 = p.s0;
+    t.s1 = p.s1;
+    t.a1 = (int)rintf(p.f * 2048.0f);
+    t.a0 = (int)rintf((1.0f - p.f) * 2048.0f);
     return t;
 }
 

@@ -9,6 +9,10 @@ rays -- two kernel launches instead of 50-100 per-frame numpy passes on the sing
 config:134), or at CAPTURE resolution: :func:`prepare_frames` / ``MultiViewPipeline(img_scale=, pad_size=)`` then run the configs'
 ``Resize(keep_ratio) -> Normalize -> Pad`` in one launch (ndet_resize_normalize_views), the resize being
 ``datasets.imresize_linear`` bit for bit, and report ``img_shape`` / ``pad_shape`` as that chain leaves them.
+
+The sensor's depth frames (uint16 millimetres on the device) go the same way: :func:`prepare_depth_frames` is the loader's
+``imresize_linear(frame / 1000, ...)`` in float64 (ndet_depth_frames), :func:`positive_indices` its ``flatnonzero(gt_depths > 0)``
+(ndet_positive_indices), and ``MultiViewPipeline(...)(..., depth_frames=)`` adds ``depth``, ``gt_depths`` and ``depth_rays`` to the batch.
 """
 from __future__ import annotations
 
@@ -111,6 +115,60 @@ def prepare_frames(frames: torch.Tensor, img_scale, pad_size, mean: Sequence[flo
     return (img, denorm, u8) if want_u8 else (img, denorm)
 
 
+def _check_depth_frames(depth_frames, what: str, n_frames=None):
+    """ValueError for anything but contiguous (n, Hd, Wd) uint16 on the GPU (``n_frames`` given: with that n); only the descriptor is read."""
+    if (not isinstance(depth_frames, torch.Tensor) or depth_frames.dtype != torch.uint16 or depth_frames.dim() != 3 or 0 in depth_frames.shape
+            or not depth_frames.is_contiguous() or not depth_frames.is_cuda):
+        got = f"{tuple(depth_frames.shape)} {depth_frames.dtype} on {depth_frames.device}" if isinstance(depth_frames, torch.Tensor) else type(depth_frames).__name__
+        raise ValueError(f"{what} takes contiguous (n, Hd, Wd) torch.uint16 depth frames (millimetres) on the GPU, got {got}")
+    if n_frames is not None and depth_frames.shape[0] != n_frames:
+        raise ValueError(f"{what}: {depth_frames.shape[0]} depth frames for {n_frames} colour frames")
+
+
+def prepare_depth_frames(depth_frames: torch.Tensor, size_hw, ids=None, margin: int = 0) -> torch.Tensor:
+    """The loader's depth maps from the sensor's frames, in one launch (ndet_depth_frames): ``depth_frames`` (n, Hd, Wd) uint16
+    millimetres on the device -> ``datasets.imresize_linear(frame / 1000, (w, h))`` in float64 metres, bit for bit (what
+    ``datasets.MultiViewPipeline._depth`` makes of the PNG), cropped to ``[margin, h - margin) x [margin, w - margin)``:
+    ``(n_sel, h - 2 * margin, w - 2 * margin)`` float64.  ``size_hw = (h, w)``; ``ids``: a sequence of frame indices, None for every frame in
+    order.  ValueError for anything but contiguous (n, Hd, Wd) ``torch.uint16`` on the GPU, for bad ``ids`` and for a margin that leaves
+    no pixel."""
+    _check_depth_frames(depth_frames, "prepare_depth_frames")
+    n, hd, wd = depth_frames.shape
+    h, w, m = int(size_hw[0]), int(size_hw[1]), int(margin)
+    if h < 1 or w < 1 or m < 0 or 2 * m >= h or 2 * m >= w:
+        raise ValueError(f"prepare_depth_frames: margin {m} leaves no pixel of a {(h, w)} map")
+    dev = depth_frames.device
+    ids_d = None
+    if ids is not None:
+        ids = [int(i) for i in ids]
+        if not ids or min(ids) < 0 or max(ids) >= n:
+            raise ValueError(f"prepare_depth_frames: ids must be a non-empty list of frame indices below {n}")
+        ids_d = torch.tensor(ids, dtype=torch.int32, device=dev)
+    n_sel = n if ids is None else len(ids)
+    out = torch.empty((n_sel, h - 2 * m, w - 2 * m), dtype=torch.float64, device=dev)
+    check(_lib.load().ndet_depth_frames(_ptr(depth_frames), _ptr(ids_d), n_sel, hd, wd, h, w, m, _ptr(out), c_void_p(_lib.raw_stream(dev))),
+          "depth_frames")
+    return out
+
+
+def positive_indices(x: torch.Tensor) -> torch.Tensor:
+    """``flatnonzero(x > 0)`` of a float64 tensor on the device, as the loader leaves ``depth_rays`` (datasets.DefaultFormatBundle3D): (K,)
+    int64, ascending, from one launch (ndet_positive_indices) and one 8-byte read of the count -- the only synchronisation."""
+    if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f"positive_indices takes a contiguous, non-empty float64 tensor on the GPU, got {tuple(x.shape)} {x.dtype}")
+    lib, dev, n = _lib.load(), x.device, x.numel()
+    if n >= 2 ** 31:
+        raise ValueError(f"positive_indices: {n} elements, 2^31 or more")
+    idx = torch.empty(n, dtype=torch.int64, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = torch.empty(lib.ndet_positive_indices_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    check(lib.ndet_positive_indices(_ptr(x), n, _ptr(idx), _ptr(count), _ptr(ws), c_void_p(_lib.raw_stream(dev))), "positive_indices")
+    k = int(count.item())
+    if k < 0:
+        raise _lib.NdetError("positive_indices: a wait inside the scan ran out of polls")
+    return idx[:k]
+
+
 def frame_meta(cams_or_lidar2img: dict, size_hw, img_scale, pad_size) -> dict:
     """The ``img_meta`` of capture-size frames as the ``datasets`` chain leaves it: ``lidar2img{intrinsic, extrinsic[], origin}`` of the
     cameras (``scene_cameras``'s dict or a ``lidar2img``), ``ori_shape = (Hs, Ws, 3)``, ``img_shape = (Hr, Wr, 3)`` -- what
@@ -133,7 +191,15 @@ class MultiViewPipeline:
     ``img`` / ``denorm_images`` from one ndet_resize_normalize_views launch over the selected and the target views, ``img_metas`` as
     :func:`frame_meta` gives (``ori_shape`` is the frames' own; the argument must be None or equal to it), target intrinsics scaled by
     ``Hs / Hr``, the ray grid over the padded H x W (multi_view.py takes ``imgs[0].shape``) and ``gt_images`` the margin crop of the
-    target views' de-normalised planes, so a pad pixel is ``trunc(mean) / 255``.  Both None: frames at network resolution, as above."""
+    target views' de-normalised planes, so a pad pixel is ``trunc(mean) / 255``.  Both None: frames at network resolution, as above.
+
+    ``depth_frames=`` (n_frames, Hd, Wd) uint16 millimetres on the device, one per colour frame, of any size of their own: the batch gains
+    what the ``*_depth_sp`` configs' loader adds (multi_view.py:98-105, 156-166; formating.py) -- ``depth`` (1, n_v, Hr, Wr) float64 metres,
+    the selected views' maps at the meta's ``img_shape``, for ``simple_test(depth=)``; and with target views ``gt_depths``
+    (1, T, H - 2m, W - 2m) float64, the margin crop of the targets' maps at the PADDED size (the reference resizes them to ``gt_rgb_shape``:
+    240 x 320 where the image content is 239 x 320), and ``depth_rays`` (1, K) int64, ``flatnonzero(gt_depths > 0)`` -- each
+    ``datasets.imresize_linear(frame / 1000, ...)`` bit for bit (:func:`prepare_depth_frames`).  Three launches and one 8-byte read (the
+    count K) on top of the call's own; without ``depth_frames`` nothing changes and ``gt_depths`` stays ``[]``."""
 
     def __init__(self, n_images: int, mean: Sequence[float] = IMG_MEAN, std: Sequence[float] = IMG_STD, margin: int = 10,
                  depth_range=(0.5, 5.5), loading: str = "random", nerf_target_views: int = 0, sample_freq: int = 3, img_scale=None,
@@ -147,7 +213,15 @@ class MultiViewPipeline:
         self.img_scale = None if img_scale is None else tuple(img_scale)
         self.pad_size = None if pad_size is None else tuple(pad_size)
 
-    def _raw(self, frames: torch.Tensor, cams: dict, ori_shape, ids, target_ids) -> dict:
+    def _depth(self, depth_frames: torch.Tensor, ids, target_ids, view_hw, pad_hw) -> dict:
+        """The depth keys of a batch: the selected views at ``view_hw``, the targets' margin crop at ``pad_hw`` and its positive rays."""
+        out = dict(depth=prepare_depth_frames(depth_frames, view_hw, ids=ids).unsqueeze(0))
+        if target_ids:
+            gt = prepare_depth_frames(depth_frames, pad_hw, ids=target_ids, margin=self.margin)
+            out.update(gt_depths=gt.unsqueeze(0), depth_rays=positive_indices(gt).reshape(1, -1))
+        return out
+
+    def _raw(self, frames: torch.Tensor, cams: dict, ori_shape, ids, target_ids, depth_frames=None) -> dict:
         """``__call__`` for frames at capture resolution."""
         n_frames, hs, ws, _ = frames.shape
         if ori_shape is not None and tuple(ori_shape)[:2] != (hs, ws):
@@ -182,18 +256,22 @@ class MultiViewPipeline:
                          gt_images=gt.unsqueeze(0), gt_depths=[], nerf_sizes=[size.clone() for _ in target_ids],
                          depth_range=torch.tensor([[self.depth_range]], dtype=torch.float32, device=dev),
                          c2w=[cams["c2w"][i] for i in target_ids])
+        if depth_frames is not None:
+            batch.update(self._depth(depth_frames, ids, target_ids, (hr, wr), (h, w)))
         return batch
 
-    def __call__(self, frames: torch.Tensor, cams: dict, ori_shape=None, ids=None, target_ids=None) -> dict:
+    def __call__(self, frames: torch.Tensor, cams: dict, ori_shape=None, ids=None, target_ids=None, depth_frames=None) -> dict:
         if not frames.is_cuda:
             raise RuntimeError("nerfdet_amd.pipeline: frames must live on the GPU (no CPU fallback)")
         assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[-1] == 3 and frames.is_contiguous()
         n_frames, h, w, _ = frames.shape
+        if depth_frames is not None:
+            _check_depth_frames(depth_frames, "MultiViewPipeline", n_frames)
         if ids is None:
             ids, target_ids = select_views(n_frames, self.n_images, self.nerf_target_views, self.loading, self.sample_freq)
         target_ids = list(target_ids or [])
         if self.img_scale is not None:
-            return self._raw(frames, cams, ori_shape, ids, target_ids)
+            return self._raw(frames, cams, ori_shape, ids, target_ids, depth_frames)
         dev = frames.device
         lib = _lib.load()
         st = c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -224,4 +302,6 @@ class MultiViewPipeline:
                          gt_images=gt.unsqueeze(0), gt_depths=[], nerf_sizes=[size.clone() for _ in target_ids],
                          depth_range=torch.tensor([[self.depth_range]], dtype=torch.float32, device=dev),
                          c2w=[cams["c2w"][i] for i in target_ids])
+        if depth_frames is not None:
+            batch.update(self._depth(depth_frames, ids, target_ids, (h, w), (h, w)))
         return batch

@@ -57,7 +57,7 @@ import numpy as np
 import torch
 
 from . import conv3d, ops
-from .pipeline import IMG_MEAN, IMG_STD, prepare_frames, rescale_size
+from .pipeline import IMG_MEAN, IMG_STD, prepare_depth_frames, prepare_frames, rescale_size
 from .volume import map_features_2d, map_features_2d_hip
 
 Tensor = torch.Tensor
@@ -100,6 +100,19 @@ def check_frames_meta(scene_meta: dict, frames: Tensor, n: int):
         raise ValueError(f"add_frames: a {(hs, ws)} frame rescales to {rescale_size((hs, ws), (w, h))} inside pad_shape {(h, w)}, "
                          f"not to the scene's img_shape {img_shape}")
     return (w, h), (h, w)
+
+
+def check_depth_frames(depth_frames, depth, n: int, k: int) -> None:
+    """``add_frames(depth_frames=)``'s own checks, on the descriptor only: None, or contiguous (n, k, Hd, Wd) uint16 on the GPU and no
+    ``depth`` beside it, else ValueError."""
+    if depth_frames is None:
+        return
+    if depth is not None:
+        raise ValueError("add_frames: depth_frames and depth exclude each other (depth_frames is resized into the call's depth)")
+    if (depth_frames.dim() != 4 or depth_frames.dtype != torch.uint16 or tuple(depth_frames.shape[:2]) != (n, k) or 0 in depth_frames.shape
+            or not depth_frames.is_contiguous() or not depth_frames.is_cuda):
+        raise ValueError(f"add_frames takes depth_frames as contiguous uint16 millimetres ({n}, {k}, Hd, Wd) on the GPU; got "
+                         f"{tuple(depth_frames.shape)} {depth_frames.dtype} on {depth_frames.device}")
 
 
 def _check_pad_shape(scene_meta: dict, img_meta: dict) -> None:
@@ -254,7 +267,7 @@ class SceneStream:
         if self.det.training:
             raise RuntimeError("SceneStream is inference only: call det.eval() first")
 
-    def add_frames(self, frames: Tensor, img_meta: dict, depth: Optional[Tensor] = None) -> None:
+    def add_frames(self, frames: Tensor, img_meta: dict, depth: Optional[Tensor] = None, depth_frames: Optional[Tensor] = None) -> None:
         """:meth:`add_views` for k >= 1 frames at CAPTURE resolution: ``frames`` (1, k, Hs, Ws, 3) uint8 BGR on the device, as a decode
         engine leaves them.  The scene's meta says what becomes of them (pipeline.frame_meta makes such a meta): ``(Hs, Ws)`` must be its
         ``ori_shape``, its ``img_shape`` what ``Resize(keep_ratio=True)`` into the ``pad_shape`` box gives (pipeline.rescale_size;
@@ -262,13 +275,19 @@ class SceneStream:
         work.  One ndet_resize_normalize_views launch then makes the chunk's ``img`` and ``denorm_images`` (1, k, 3, H, W) at the padded
         size -- ``datasets.imresize_linear``'s bytes, normalised with ``mean`` / ``std`` of ``begin_scene`` as ndet_normalize_views does, then
         padded, as the configs' Resize -> Normalize -> Pad -- and :meth:`add_views` takes them: guard, window, bank and the promise that a call that raises changes nothing are its own.  ``depth`` passes through
-        (ops.depth_gate resizes it to ``img_shape``)."""
+        (ops.depth_gate resizes it to ``img_shape``).  ``depth_frames`` instead of ``depth``: the sensor's frames (1, k, Hd, Wd) uint16
+        millimetres on the device, of any size of their own; one ndet_depth_frames launch makes the float64 metres at the scene's
+        ``img_shape`` (pipeline.prepare_depth_frames: ``datasets.imresize_linear(frame / 1000, ...)`` bit for bit), which go to
+        :meth:`add_views` as its ``depth``.  Both given, a wrong dtype or another k: ValueError, before any device work."""
         img_scale, pad_size = check_frames_meta(self.meta, frames, 1)
         _check_pad_shape(self.meta, img_meta)
         k = frames.shape[1]
+        check_depth_frames(depth_frames, depth, 1, k)
         shape = torch.empty((1, k, 3) + pad_size, device="meta")
         self._check_chunk(shape, shape, img_meta, depth)
         img, denorm = prepare_frames(frames[0], img_scale, pad_size, self.mean, self.std)
+        if depth_frames is not None:
+            depth = prepare_depth_frames(depth_frames[0], self.meta["img_shape"][:2]).unsqueeze(0)
         self.add_views(img.unsqueeze(0), denorm.unsqueeze(0), img_meta, depth=depth)
 
     def add_views(self, img: Tensor, denorm_images: Tensor, img_meta: dict, depth: Optional[Tensor] = None) -> None:
@@ -592,21 +611,27 @@ class SceneGroup:
         x, _, stride = self.det.extract_2d(img)
         return x, getattr(x, "_ndet_feature_2d", None), stride
 
-    def add_frames(self, frames: Tensor, metas, scenes=None, depth: Optional[Tensor] = None) -> None:
+    def add_frames(self, frames: Tensor, metas, scenes=None, depth: Optional[Tensor] = None, depth_frames: Optional[Tensor] = None) -> None:
         """:meth:`add_views` for frames at CAPTURE resolution: ``frames`` (len(scenes), k, Hs, Ws, 3) uint8 BGR on the device, one row of k
         frames per listed scene.  The group's meta says what becomes of them, as in :meth:`SceneStream.add_frames`: ``(Hs, Ws)`` must be
         its ``ori_shape`` and its ``img_shape`` what ``Resize(keep_ratio=True)`` into the ``pad_shape`` box gives, else ValueError --
         raised, like everything :meth:`add_views` refuses, before any device work.  ONE ndet_resize_normalize_views launch over all the
         ``len(scenes) * k`` frames makes ``img`` and ``denorm_images`` (with ``mean`` / ``std`` of ``begin_scenes``), and :meth:`add_views` takes them: guard, windows, banks and the promise that a call that raises changes
-        nothing are its own.  ``depth`` passes through."""
+        nothing are its own.  ``depth`` passes through.  ``depth_frames`` instead of ``depth``: the sensor's frames (len(scenes), k, Hd, Wd)
+        uint16 millimetres on the device; ONE ndet_depth_frames launch over all of them makes the float64 metres at the group's
+        ``img_shape``, as in :meth:`SceneStream.add_frames`.  Both given, a wrong dtype or another k: ValueError, before any device work."""
         n = len(ops.listed_scenes(self.n_scenes, scenes))
         img_scale, pad_size = check_frames_meta(self.metas[0], frames, n)
         metas = list(metas)
         for m in metas:
             _check_pad_shape(self.metas[0], m)
         k = frames.shape[1]
+        check_depth_frames(depth_frames, depth, n, k)
         shape = torch.empty((n, k, 3) + pad_size, device="meta")
         self._check_call(shape, shape, metas, scenes, depth)
+        if depth_frames is not None:
+            d = prepare_depth_frames(depth_frames.reshape((n * k,) + tuple(depth_frames.shape[2:])), self.metas[0]["img_shape"][:2])
+            depth = d.view((n, k) + tuple(d.shape[1:]))
         img, denorm = prepare_frames(frames.reshape((n * k,) + tuple(frames.shape[2:])), img_scale, pad_size, self.mean, self.std)
         self.add_views(img.view((n, k) + tuple(img.shape[1:])), denorm.view((n, k) + tuple(denorm.shape[1:])), metas, scenes=scenes, depth=depth)
 
