@@ -221,6 +221,12 @@ extern "C" int ndet_density_features_packed_gated(const float* mapped_nhwc, int 
 // (sum_seen v for the mean, the shifted sums about the fill for the variance) and the two counts the finish needs.  Views that do not see a
 // voxel add nothing; they enter only through n_views in the finish.  K2-finish is the packed kernel's finish over the state, expression for
 // expression: a state filled by one launch gives its rows bit for bit (0 + x = x).  The state is only read.
+//
+// The kernels for one state, a ring of states, the listed scenes of a group and the listed scenes' rings share one text of everything
+// but their set-up: the walk (k2_packed_sums), the add to the state (k2_state_add), the finish of one value (k2_finish_value), of one
+// channel (k2_finish_channel) and of one quad (k2_finish_quad), and the sum over a ring's segments (k2_ring_sums).  Not shared, on
+// purpose: k_density_features_packed above keeps its own walk and finish, as k_backproject_aggregate does, whose C = 512 instantiation
+// spilled once routed through an inlined helper ("Streaming scenes"); neither one-shot kernel's code object may move.
 // ------------------------------------------------------------------------------------------
 // What a finishing lane (group 0) of a packed K2 wave holds after the walk over the launch's views and the groups' meeting in LDS.
 struct K2Sums {
@@ -352,18 +358,9 @@ __device__ __forceinline__ bool k2_packed_sums(int2* s_off, const float* __restr
     return true;
 }
 
-template <bool DG>
-__global__ __launch_bounds__(256) void k_density_accumulate_packed(const float* __restrict__ mapped, int n_views, int cm, int h, int w,
-                                                                   int mview_pitch, int mrow_pitch, const float* __restrict__ bias,
-                                                                   const float* __restrict__ rgb, int H, int W, int rsv, int rsc, int rsy,
-                                                                   const float* __restrict__ points, int N, const float* __restrict__ proj,
-                                                                   const float* __restrict__ rgb_proj, float* __restrict__ sum, int pitch,
-                                                                   int* __restrict__ count, int n_blocks, int nvp, NdetGateMap gf, NdetGateMap gr) {
-    extern __shared__ int2 s_off[];
-    K2Sums r;
-    if (!k2_packed_sums<DG>(s_off, mapped, n_views, cm, h, w, mview_pitch, mrow_pitch, bias, rgb, H, W, rsv, rsc, rsy, points, N, proj, rgb_proj,
-                            n_blocks, nvp, gf, gr, r))
-        return;
+// The accumulate kernels' epilogue: a finishing lane adds its three sums to its quad of the voxel's state row, the colour lane the two
+// counts as well.
+__device__ __forceinline__ void k2_state_add(const K2Sums& r, float* __restrict__ sum, int pitch, int* __restrict__ count, int cm) {
     const int seg = cm + 4;   // [r g b 0 | cm mapped channels] per sum
     float4* row = reinterpret_cast<float4*>(sum + (int64_t)r.n * pitch + (r.is_rgb ? 0 : 4 + 4 * r.fq));
     row[0] = ndet_add4(row[0], r.acc);
@@ -376,13 +373,25 @@ __global__ __launch_bounds__(256) void k_density_accumulate_packed(const float* 
     }
 }
 
-// One thread per (voxel, channel): k_density_features_packed's finish over the state.
-__global__ __launch_bounds__(256) void k_density_finish(const float* __restrict__ sum, int pitch, const int* __restrict__ count,
-                                                        const float* __restrict__ bias, int cm, int N, int n_views, float* __restrict__ out) {
-    const int nc = 3 + cm;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)N * nc) return;
-    const int n = (int)(i / nc), c = (int)(i % nc);
+// k_density_features_packed's finish of one channel, expression for expression: [mean, cov] from the channel's three sums a, q, s about
+// its fill, the voxel's count in the stride-4 map (cnt) and in the channel's own map (n_mine), and the scene's view total.
+__device__ __forceinline__ float2 k2_finish_value(float a, float q, float s, float fill, int cnt, int n_mine, int n_views) {
+    const float denom = (float)cnt + 1e-8f;
+    const float nu = (float)(n_views - n_mine), nv = (float)n_views;
+    const float sm = a + nu * fill;
+    const float mean = sm / denom;                        // NOT zeroed at cnt == 0 (nerfdet.py:241)
+    const float dm = mean - fill;
+    float sq = q - 2.0f * dm * s + nv * (dm * dm);
+    sq = fmaxf(sq, 0.0f);                                 // a sum of squares: rounding may leave -1 ulp
+    float var = sq / denom;
+    if (cnt == 0) var = 1e6f;                             // nerfdet.py:249
+    return make_float2(mean, expf(-var));
+}
+
+// Channel c (0 .. 2 colour, 3 .. the mapped ones) of voxel n, from a state to the voxel's output row.
+__device__ __forceinline__ void k2_finish_channel(const float* __restrict__ sum, int pitch, const int* __restrict__ count,
+                                                  const float* __restrict__ bias, int cm, int n, int c, int n_views,
+                                                  float* __restrict__ out_row) {
     const bool is_rgb = c < 3;
     const int k = is_rgb ? c : c + 1;          // column inside a segment
     const int seg = cm + 4;
@@ -390,43 +399,29 @@ __global__ __launch_bounds__(256) void k_density_finish(const float* __restrict_
     const float a = row[k], qq = row[seg + k], ss = row[2 * seg + k];
     const float fl = is_rgb ? 0.0f : bias[c - 3];
     const int cnt = count[2 * n], n_mine = is_rgb ? count[2 * n + 1] : cnt;
-    const float denom = (float)cnt + 1e-8f;
-    const float nu = (float)(n_views - n_mine), nv = (float)n_views;
-    const float sm = a + nu * fl;
-    const float mean = sm / denom;                        // NOT zeroed at cnt == 0 (nerfdet.py:241)
-    const float dm = mean - fl;
-    float s = qq - 2.0f * dm * ss + nv * (dm * dm);
-    s = fmaxf(s, 0.0f);                                   // a sum of squares: rounding may leave -1 ulp
-    float var = s / denom;
-    if (cnt == 0) var = 1e6f;                             // nerfdet.py:249
-    *reinterpret_cast<float2*>(out + (int64_t)n * 2 * nc + 2 * c) = make_float2(mean, expf(-var));
+    *reinterpret_cast<float2*>(out_row + 2 * c) = k2_finish_value(a, qq, ss, fl, cnt, n_mine, n_views);
 }
 
-// k_density_finish over a ring of states (include/nerfdet_hip.h, ndet_scene_density_finish_ring), its own copy of the finish: one thread
-// per (voxel, channel quad) -- quad 0 the colour lane [r g b 0], quads 1 .. cm / 4 the mapped channels -- with 16-byte loads of the three
-// sums.  The sums and counts start from the oldest segment's values and take the others in array order, NDET_RING_BATCH segments at a
-// time: counts first, then the rows of the segments that see the voxel in the quad's own map (the others hold zeros there), then the adds.
-// Every component then goes through k_density_finish's expressions, so one segment gives its rows bit for bit.
-__global__ __launch_bounds__(256) void k_density_finish_ring(NdetRingArgs r, int n_segs, const float* __restrict__ bias, int cm, int N,
-                                                             int n_views, float* __restrict__ out) {
+// Quad qd of voxel n -- quad 0 the colour lane [r g b 0], quads 1 .. cm / 4 the mapped channels -- summed over a ring's segments (Segs:
+// NdetRingArgSegs or NdetRingLdsSegs, ndet_common.hpp) with 16-byte loads of the three sums, and the voxel's two counts.  The sums and
+// counts start from the oldest segment's values and take the others in array order, NDET_RING_BATCH segments at a time: counts first,
+// then the rows of the segments that see the voxel in the quad's own map (the others hold zeros there), then the adds.
+template <class Segs>
+__device__ __forceinline__ void k2_ring_sums(const Segs& g, int n_segs, int cm, int n, int qd, float4& a, float4& qq, float4& ss, int& cnt,
+                                             int& n_mine) {
     constexpr int U = NDET_RING_BATCH;
-    const int nq = (cm >> 2) + 1;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)N * nq) return;
-    const int n = (int)(i / nq), qd = (int)(i % nq);
     const bool is_rgb = qd == 0;
     const int seg = cm + 4;
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     auto counts = [&](int sj, int& c_f, int& c_mine) {
-        const int2 c = *reinterpret_cast<const int2*>(r.count[sj] + 2 * n);
+        const int2 c = *reinterpret_cast<const int2*>(g.count(sj) + 2 * n);
         c_f = c.x;
         c_mine = is_rgb ? c.y : c.x;
     };
-    int cnt, n_mine;
     counts(0, cnt, n_mine);
-    float4 a = zero, qq = zero, ss = zero;
+    a = zero; qq = zero; ss = zero;
     if (n_mine != 0) {
-        const float* row = r.sum[0] + (int64_t)n * r.pitch[0] + 4 * qd;
+        const float* row = g.sum(0) + (int64_t)n * g.pitch(0) + 4 * qd;
         a = *reinterpret_cast<const float4*>(row);
         qq = *reinterpret_cast<const float4*>(row + seg);
         ss = *reinterpret_cast<const float4*>(row + 2 * seg);
@@ -445,7 +440,7 @@ __global__ __launch_bounds__(256) void k_density_finish_ring(NdetRingArgs r, int
         for (int j = 0; j < U; ++j) {
             va[j] = zero; vq[j] = zero; vs[j] = zero;
             if (mm[j] != 0) {      // implies s0 + j < n_segs
-                const float* row = r.sum[s0 + j] + (int64_t)n * r.pitch[s0 + j] + 4 * qd;
+                const float* row = g.sum(s0 + j) + (int64_t)n * g.pitch(s0 + j) + 4 * qd;
                 va[j] = *reinterpret_cast<const float4*>(row);
                 vq[j] = *reinterpret_cast<const float4*>(row + seg);
                 vs[j] = *reinterpret_cast<const float4*>(row + 2 * seg);
@@ -460,36 +455,43 @@ __global__ __launch_bounds__(256) void k_density_finish_ring(NdetRingArgs r, int
             n_mine += mm[j];
         }
     }
-    const float denom = (float)cnt + 1e-8f;
-    const float nu = (float)(n_views - n_mine), nv = (float)n_views;
-    auto finish = [&](float a1, float q1, float s1, float fl) -> float2 {
-        const float sm = a1 + nu * fl;
-        const float mean = sm / denom;                        // NOT zeroed at cnt == 0 (nerfdet.py:241)
-        const float dm = mean - fl;
-        float s = q1 - 2.0f * dm * s1 + nv * (dm * dm);
-        s = fmaxf(s, 0.0f);                                   // a sum of squares: rounding may leave -1 ulp
-        float var = s / denom;
-        if (cnt == 0) var = 1e6f;                             // nerfdet.py:249
-        return make_float2(mean, expf(-var));
-    };
-    float2* o = reinterpret_cast<float2*>(out + (int64_t)n * 2 * (3 + cm));
-    if (is_rgb) {
-        o[0] = finish(a.x, qq.x, ss.x, 0.0f);
-        o[1] = finish(a.y, qq.y, ss.y, 0.0f);
-        o[2] = finish(a.z, qq.z, ss.z, 0.0f);
-    } else {
-        const int c = 4 * (qd - 1);                           // first mapped channel of the quad
-        o[3 + c] = finish(a.x, qq.x, ss.x, bias[c]);
-        o[4 + c] = finish(a.y, qq.y, ss.y, bias[c + 1]);
-        o[5 + c] = finish(a.z, qq.z, ss.z, bias[c + 2]);
-        o[6 + c] = finish(a.w, qq.w, ss.w, bias[c + 3]);
-    }
 }
 
-// k_density_accumulate_packed for the listed scenes of a group (include/nerfdet_hip.h, ndet_scene_accumulate_group), grid.y = listed scene:
-// the block takes its scene's state and points from the device table, moves the mapped maps, images, projections and gate maps on by y * k
-// views and runs the packed walk over the scene's k views.  Its own copy of the parent's epilogue; the offsets the walk records stay inside
-// the scene's k views (k * mview_pitch and k * rsv below 2^31, checked on the host).
+// Every component of quad qd through k2_finish_value, to the voxel's output row: one segment gives k_density_finish's rows bit for bit.
+// One sequence for both kinds of quad -- the colour quad's fill is 0 and it has no fourth value -- because written as a branch each the
+// ring kernels came out up to 7 % longer than with the expressions in place ("One body per streaming kernel family").
+__device__ __forceinline__ void k2_finish_quad(float4 a, float4 qq, float4 ss, int cnt, int n_mine, int n_views, const float* __restrict__ bias,
+                                               int qd, float* __restrict__ out_row) {
+    const bool is_rgb = qd == 0;
+    const int c = 4 * (qd - 1);                               // first mapped channel of the quad
+    float4 fl = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!is_rgb) fl = make_float4(bias[c], bias[c + 1], bias[c + 2], bias[c + 3]);
+    float2* o = reinterpret_cast<float2*>(out_row) + (is_rgb ? 0 : 3 + c);
+    o[0] = k2_finish_value(a.x, qq.x, ss.x, fl.x, cnt, n_mine, n_views);
+    o[1] = k2_finish_value(a.y, qq.y, ss.y, fl.y, cnt, n_mine, n_views);
+    o[2] = k2_finish_value(a.z, qq.z, ss.z, fl.z, cnt, n_mine, n_views);
+    if (!is_rgb) o[3] = k2_finish_value(a.w, qq.w, ss.w, fl.w, cnt, n_mine, n_views);
+}
+
+template <bool DG>
+__global__ __launch_bounds__(256) void k_density_accumulate_packed(const float* __restrict__ mapped, int n_views, int cm, int h, int w,
+                                                                   int mview_pitch, int mrow_pitch, const float* __restrict__ bias,
+                                                                   const float* __restrict__ rgb, int H, int W, int rsv, int rsc, int rsy,
+                                                                   const float* __restrict__ points, int N, const float* __restrict__ proj,
+                                                                   const float* __restrict__ rgb_proj, float* __restrict__ sum, int pitch,
+                                                                   int* __restrict__ count, int n_blocks, int nvp, NdetGateMap gf, NdetGateMap gr) {
+    extern __shared__ int2 s_off[];
+    K2Sums r;
+    if (!k2_packed_sums<DG>(s_off, mapped, n_views, cm, h, w, mview_pitch, mrow_pitch, bias, rgb, H, W, rsv, rsc, rsy, points, N, proj, rgb_proj,
+                            n_blocks, nvp, gf, gr, r))
+        return;
+    k2_state_add(r, sum, pitch, count, cm);
+}
+
+// The listed scenes of a group (include/nerfdet_hip.h, ndet_scene_accumulate_group), grid.y = listed scene: the block takes its scene's
+// state and points from the device table, moves the mapped maps, images, projections and gate maps on by y * k views and runs the packed
+// walk over the scene's k views; the offsets the walk records stay inside those (k * mview_pitch and k * rsv below 2^31, checked on the
+// host).
 template <bool DG>
 __global__ __launch_bounds__(256) void k_density_accumulate_group(const NdetSceneSlot* __restrict__ table, NdetGroupSel sel, int k,
                                                                   const float* __restrict__ mapped_all, int cm, int h, int w, int mview_pitch,
@@ -500,38 +502,25 @@ __global__ __launch_bounds__(256) void k_density_accumulate_group(const NdetScen
     extern __shared__ int2 s_off[];
     const int y = blockIdx.y;
     const NdetSceneSlot& sl = table[sel.slot[y]];
-    const float* __restrict__ points = sl.points;
-    float* __restrict__ sum = sl.k2_sum;
-    int* __restrict__ count = sl.k2_count;
     const int64_t v0 = (int64_t)y * k;                         // the scene's first view of the call
-    const float* __restrict__ mapped = mapped_all + v0 * mview_pitch;
-    const float* __restrict__ rgb = rgb_all + v0 * rsv;
-    const float* __restrict__ proj = proj_all + v0 * 12;
-    const float* __restrict__ rgb_proj = rgb_proj_all + v0 * 12;
-    NdetGateMap gf = gf_all, gr = gr_all;
-    if (DG) {
-        const size_t es = gf_all.f64 ? sizeof(double) : sizeof(float);
-        gf.map = static_cast<const char*>(gf_all.map) + (size_t)v0 * gf_all.view_pitch * es;
-        gr.map = static_cast<const char*>(gr_all.map) + (size_t)v0 * gr_all.view_pitch * es;
-    }
     K2Sums r;
-    if (!k2_packed_sums<DG>(s_off, mapped, k, cm, h, w, mview_pitch, mrow_pitch, bias, rgb, H, W, rsv, rsc, rsy, points, N, proj, rgb_proj,
-                            n_blocks, nvp, gf, gr, r))
+    if (!k2_packed_sums<DG>(s_off, mapped_all + v0 * mview_pitch, k, cm, h, w, mview_pitch, mrow_pitch, bias, rgb_all + v0 * rsv, H, W, rsv, rsc,
+                            rsy, sl.points, N, proj_all + v0 * 12, rgb_proj_all + v0 * 12, n_blocks, nvp,
+                            DG ? ndet_gate_from_view(gf_all, v0) : gf_all, DG ? ndet_gate_from_view(gr_all, v0) : gr_all, r))
         return;
-    const int seg = cm + 4;   // [r g b 0 | cm mapped channels] per sum
-    float4* row = reinterpret_cast<float4*>(sum + (int64_t)r.n * pitch + (r.is_rgb ? 0 : 4 + 4 * r.fq));
-    row[0] = ndet_add4(row[0], r.acc);
-    row[seg / 4] = ndet_add4(row[seg / 4], r.q);
-    row[2 * seg / 4] = ndet_add4(row[2 * seg / 4], r.s1);
-    if (r.is_rgb) {
-        int2* c = reinterpret_cast<int2*>(count) + r.n;
-        const int2 c0 = *c;
-        *c = make_int2(c0.x + r.cnt, c0.y + r.n_mine);
-    }
+    k2_state_add(r, sl.k2_sum, pitch, sl.k2_count, cm);
 }
 
-// k_density_finish (its own copy, expression for expression) for the listed scenes of a group: output row y N + n, finished over the
-// scene's own view total.
+// One thread per (voxel, channel); the grouped kernel writes output row y N + n and finishes over the scene's own view total.
+__global__ __launch_bounds__(256) void k_density_finish(const float* __restrict__ sum, int pitch, const int* __restrict__ count,
+                                                        const float* __restrict__ bias, int cm, int N, int n_views, float* __restrict__ out) {
+    const int nc = 3 + cm;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)N * nc) return;
+    const int n = (int)(i / nc), c = (int)(i % nc);
+    k2_finish_channel(sum, pitch, count, bias, cm, n, c, n_views, out + (int64_t)n * 2 * nc);
+}
+
 __global__ __launch_bounds__(256) void k_density_finish_group(const NdetSceneSlot* __restrict__ table, NdetGroupSel sel, int pitch,
                                                               const float* __restrict__ bias, int cm, int N, float* __restrict__ out) {
     const int nc = 3 + cm;
@@ -539,37 +528,30 @@ __global__ __launch_bounds__(256) void k_density_finish_group(const NdetSceneSlo
     if (i >= (int64_t)N * nc) return;
     const int y = blockIdx.y;
     const NdetSceneSlot& sl = table[sel.slot[y]];
-    const float* __restrict__ sum = sl.k2_sum;
-    const int* __restrict__ count = sl.k2_count;
-    const int n_views = sel.n_views[y];
     const int n = (int)(i / nc), c = (int)(i % nc);
-    const bool is_rgb = c < 3;
-    const int k = is_rgb ? c : c + 1;          // column inside a segment
-    const int seg = cm + 4;
-    const float* row = sum + (int64_t)n * pitch;
-    const float a = row[k], qq = row[seg + k], ss = row[2 * seg + k];
-    const float fl = is_rgb ? 0.0f : bias[c - 3];
-    const int cnt = count[2 * n], n_mine = is_rgb ? count[2 * n + 1] : cnt;
-    const float denom = (float)cnt + 1e-8f;
-    const float nu = (float)(n_views - n_mine), nv = (float)n_views;
-    const float sm = a + nu * fl;
-    const float mean = sm / denom;                        // NOT zeroed at cnt == 0 (nerfdet.py:241)
-    const float dm = mean - fl;
-    float s = qq - 2.0f * dm * ss + nv * (dm * dm);
-    s = fmaxf(s, 0.0f);                                   // a sum of squares: rounding may leave -1 ulp
-    float var = s / denom;
-    if (cnt == 0) var = 1e6f;                             // nerfdet.py:249
-    *reinterpret_cast<float2*>(out + ((int64_t)y * N + n) * 2 * nc + 2 * c) = make_float2(mean, expf(-var));
+    k2_finish_channel(sl.k2_sum, pitch, sl.k2_count, bias, cm, n, c, sel.n_views[y], out + ((int64_t)y * N + n) * 2 * nc);
 }
 
-// k_density_finish_ring (its own copy, expression for expression) for the listed scenes of a windowed group (include/nerfdet_hip.h,
-// ndet_scene_density_finish_group_ring), grid.y = listed scene: the scene's segments are rows segs[y][0 .. n_segs - 1] of the pool table.
-// Threads 0 .. n_segs - 1 resolve them into LDS once (block-uniform pointers, 64 x 16 bytes), one barrier, then the ring walk with the
-// pool's pitch; threads past N nq stay for the barrier and skip the body.  Output row y N + n, finished over the scene's own view total.
+// One thread per (voxel, channel quad) over a ring of states (include/nerfdet_hip.h, ndet_scene_density_finish_ring).
+__global__ __launch_bounds__(256) void k_density_finish_ring(NdetRingArgs r, int n_segs, const float* __restrict__ bias, int cm, int N,
+                                                             int n_views, float* __restrict__ out) {
+    const int nq = (cm >> 2) + 1;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)N * nq) return;
+    const int n = (int)(i / nq), qd = (int)(i % nq);
+    float4 a, qq, ss;
+    int cnt, n_mine;
+    k2_ring_sums(NdetRingArgSegs{r}, n_segs, cm, n, qd, a, qq, ss, cnt, n_mine);
+    k2_finish_quad(a, qq, ss, cnt, n_mine, n_views, bias, qd, out + (int64_t)n * 2 * (3 + cm));
+}
+
+// The listed scenes of a windowed group (include/nerfdet_hip.h, ndet_scene_density_finish_group_ring), grid.y = listed scene: the scene's
+// segments are rows segs[y][0 .. n_segs - 1] of the pool table.  Threads 0 .. n_segs - 1 resolve them into LDS once (block-uniform
+// pointers, 64 x 16 bytes), one barrier, then the ring walk with the pool's pitch; threads past N nq stay for the barrier and do nothing
+// after it.  Output row y N + n, finished over the scene's own view total.
 __global__ __launch_bounds__(256) void k_density_finish_group_ring(const NdetSceneSlot* __restrict__ table, NdetGroupRingSel sel,
                                                                    const int32_t* __restrict__ segs, int pitch,
                                                                    const float* __restrict__ bias, int cm, int N, float* __restrict__ out) {
-    constexpr int U = NDET_RING_BATCH;
     __shared__ const float* s_sum[NDET_RING_MAX];
     __shared__ const int* s_count[NDET_RING_MAX];
     const int y = blockIdx.y;
@@ -585,84 +567,26 @@ __global__ __launch_bounds__(256) void k_density_finish_group_ring(const NdetSce
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < (int64_t)N * nq) {
         const int n = (int)(i / nq), qd = (int)(i % nq);
-        const bool is_rgb = qd == 0;
-        const int seg = cm + 4;
-        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-        auto counts = [&](int sj, int& c_f, int& c_mine) {
-            const int2 c = *reinterpret_cast<const int2*>(s_count[sj] + 2 * n);
-            c_f = c.x;
-            c_mine = is_rgb ? c.y : c.x;
-        };
+        float4 a, qq, ss;
         int cnt, n_mine;
-        counts(0, cnt, n_mine);
-        float4 a = zero, qq = zero, ss = zero;
-        if (n_mine != 0) {
-            const float* row = s_sum[0] + (int64_t)n * pitch + 4 * qd;
-            a = *reinterpret_cast<const float4*>(row);
-            qq = *reinterpret_cast<const float4*>(row + seg);
-            ss = *reinterpret_cast<const float4*>(row + 2 * seg);
-        }
-        for (int s0 = 1; s0 < n_segs; s0 += U) {
-            int cc[U], mm[U];
-            float4 va[U], vq[U], vs[U];
-#pragma unroll
-            for (int j = 0; j < U; ++j) {      // unconditional loads (past the end: the last segment's counts again, dropped), so all U are in flight
-                const bool in = s0 + j < n_segs;
-                counts(min(s0 + j, n_segs - 1), cc[j], mm[j]);
-                cc[j] = in ? cc[j] : 0;
-                mm[j] = in ? mm[j] : 0;
-            }
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                va[j] = zero; vq[j] = zero; vs[j] = zero;
-                if (mm[j] != 0) {      // implies s0 + j < n_segs
-                    const float* row = s_sum[s0 + j] + (int64_t)n * pitch + 4 * qd;
-                    va[j] = *reinterpret_cast<const float4*>(row);
-                    vq[j] = *reinterpret_cast<const float4*>(row + seg);
-                    vs[j] = *reinterpret_cast<const float4*>(row + 2 * seg);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                a = ndet_add4(a, va[j]);
-                qq = ndet_add4(qq, vq[j]);
-                ss = ndet_add4(ss, vs[j]);
-                cnt += cc[j];
-                n_mine += mm[j];
-            }
-        }
-        const float denom = (float)cnt + 1e-8f;
-        const float nu = (float)(n_views - n_mine), nv = (float)n_views;
-        auto finish = [&](float a1, float q1, float s1, float fl) -> float2 {
-            const float sm = a1 + nu * fl;
-            const float mean = sm / denom;                        // NOT zeroed at cnt == 0 (nerfdet.py:241)
-            const float dm = mean - fl;
-            float s = q1 - 2.0f * dm * s1 + nv * (dm * dm);
-            s = fmaxf(s, 0.0f);                                   // a sum of squares: rounding may leave -1 ulp
-            float var = s / denom;
-            if (cnt == 0) var = 1e6f;                             // nerfdet.py:249
-            return make_float2(mean, expf(-var));
-        };
-        float2* o = reinterpret_cast<float2*>(out + ((int64_t)y * N + n) * 2 * (3 + cm));
-        if (is_rgb) {
-            o[0] = finish(a.x, qq.x, ss.x, 0.0f);
-            o[1] = finish(a.y, qq.y, ss.y, 0.0f);
-            o[2] = finish(a.z, qq.z, ss.z, 0.0f);
-        } else {
-            const int c = 4 * (qd - 1);                           // first mapped channel of the quad
-            o[3 + c] = finish(a.x, qq.x, ss.x, bias[c]);
-            o[4 + c] = finish(a.y, qq.y, ss.y, bias[c + 1]);
-            o[5 + c] = finish(a.z, qq.z, ss.z, bias[c + 2]);
-            o[6 + c] = finish(a.w, qq.w, ss.w, bias[c + 3]);
-        }
+        k2_ring_sums(NdetRingLdsSegs{s_sum, s_count, pitch}, n_segs, cm, n, qd, a, qq, ss, cnt, n_mine);
+        k2_finish_quad(a, qq, ss, cnt, n_mine, n_views, bias, qd, out + ((int64_t)y * N + n) * 2 * (3 + cm));
     }
 }
 
-void ndet_scene_k2_finish_group_ring_launch(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_dev, const float* bias,
-                                            float* global_feat, hipStream_t stream) {
-    const int64_t total = (int64_t)pool->N * (pool->cm / 4 + 1);
-    hipLaunchKernelGGL(k_density_finish_group_ring, dim3((unsigned)((total + 255) / 256), sel->n), dim3(256), 0, stream, pool->table, *sel,
-                       segs_dev, (int)pool->k2_pitch, bias, pool->cm, pool->N, global_feat);
+// ---- launchers (ndet_common.hpp), called by the entry points in volume_kernels.hip once every argument has been checked ----
+void ndet_scene_k2_accumulate_launch(const NdetSceneAccum* s, const float* mapped, int n_views, int h, int w, int mview_pitch, int mrow_pitch,
+                                     const float* bias, const float* rgb, int H, int W, int rsv, int rsc, int rsy, const float* points,
+                                     const float* proj, const float* rgb_proj, bool gated, const NdetGateMap& gf, const NdetGateMap& gr,
+                                     hipStream_t stream) {
+    const int nvp = ((n_views + 63) / 64) * 64;
+    const int lds = 4 * nvp * (int)sizeof(int2) + 4 * 64 * 3 * (int)sizeof(float4);
+    const int blocks = (s->N + 3) / 4;
+    ndet_by_flag(gated, [&](auto dg) {
+        hipLaunchKernelGGL((k_density_accumulate_packed<decltype(dg)::value>), dim3((unsigned)blocks), dim3(256), lds, stream, mapped, n_views,
+                           s->cm, h, w, mview_pitch, mrow_pitch, bias, rgb, H, W, rsv, rsc, rsy, points, s->N, proj, rgb_proj, s->k2_sum,
+                           (int)s->k2_pitch, s->k2_count, blocks, nvp, gf, gr);
+    });
 }
 
 void ndet_scene_k2_accumulate_group_launch(const NdetSceneGroup* g, const NdetGroupSel* sel, int k, const float* mapped, int h, int w,
@@ -672,13 +596,17 @@ void ndet_scene_k2_accumulate_group_launch(const NdetSceneGroup* g, const NdetGr
     const int nvp = ((k + 63) / 64) * 64;
     const int lds = 4 * nvp * (int)sizeof(int2) + 4 * 64 * 3 * (int)sizeof(float4);
     const int blocks = (g->N + 3) / 4;
-#define K2G_LAUNCH(DG)                                                                                                                          \
-    hipLaunchKernelGGL((k_density_accumulate_group<DG>), dim3((unsigned)blocks, sel->n), dim3(256), lds, stream, g->table, *sel, k, mapped,    \
-                       g->cm, h, w, mview_pitch, mrow_pitch, bias, rgb, H, W, rsv, rsc, rsy, g->N, proj, rgb_proj, (int)g->k2_pitch, blocks, \
-                       nvp, gf, gr)
-    if (gated) K2G_LAUNCH(true);
-    else K2G_LAUNCH(false);
-#undef K2G_LAUNCH
+    ndet_by_flag(gated, [&](auto dg) {
+        hipLaunchKernelGGL((k_density_accumulate_group<decltype(dg)::value>), dim3((unsigned)blocks, sel->n), dim3(256), lds, stream, g->table,
+                           *sel, k, mapped, g->cm, h, w, mview_pitch, mrow_pitch, bias, rgb, H, W, rsv, rsc, rsy, g->N, proj, rgb_proj,
+                           (int)g->k2_pitch, blocks, nvp, gf, gr);
+    });
+}
+
+void ndet_scene_k2_finish_launch(const NdetSceneAccum* s, const float* bias, float* global_feat, hipStream_t stream) {
+    const int64_t total = (int64_t)s->N * (3 + s->cm);
+    hipLaunchKernelGGL(k_density_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, s->k2_sum, (int)s->k2_pitch, s->k2_count,
+                       bias, s->cm, s->N, s->n_views, global_feat);
 }
 
 void ndet_scene_k2_finish_group_launch(const NdetSceneGroup* g, const NdetGroupSel* sel, const float* bias, float* global_feat,
@@ -686,28 +614,6 @@ void ndet_scene_k2_finish_group_launch(const NdetSceneGroup* g, const NdetGroupS
     const int64_t total = (int64_t)g->N * (3 + g->cm);
     hipLaunchKernelGGL(k_density_finish_group, dim3((unsigned)((total + 255) / 256), sel->n), dim3(256), 0, stream, g->table, *sel,
                        (int)g->k2_pitch, bias, g->cm, g->N, global_feat);
-}
-
-void ndet_scene_k2_accumulate_launch(const NdetSceneAccum* s, const float* mapped, int n_views, int h, int w, int mview_pitch, int mrow_pitch,
-                                     const float* bias, const float* rgb, int H, int W, int rsv, int rsc, int rsy, const float* points,
-                                     const float* proj, const float* rgb_proj, bool gated, const NdetGateMap& gf, const NdetGateMap& gr,
-                                     hipStream_t stream) {
-    const int nvp = ((n_views + 63) / 64) * 64;
-    const int lds = 4 * nvp * (int)sizeof(int2) + 4 * 64 * 3 * (int)sizeof(float4);
-    const int blocks = (s->N + 3) / 4;
-#define K2A_LAUNCH(DG)                                                                                                                       \
-    hipLaunchKernelGGL((k_density_accumulate_packed<DG>), dim3((unsigned)blocks), dim3(256), lds, stream, mapped, n_views, s->cm, h, w,     \
-                       mview_pitch, mrow_pitch, bias, rgb, H, W, rsv, rsc, rsy, points, s->N, proj, rgb_proj, s->k2_sum, (int)s->k2_pitch, \
-                       s->k2_count, blocks, nvp, gf, gr)
-    if (gated) K2A_LAUNCH(true);
-    else K2A_LAUNCH(false);
-#undef K2A_LAUNCH
-}
-
-void ndet_scene_k2_finish_launch(const NdetSceneAccum* s, const float* bias, float* global_feat, hipStream_t stream) {
-    const int64_t total = (int64_t)s->N * (3 + s->cm);
-    hipLaunchKernelGGL(k_density_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, s->k2_sum, (int)s->k2_pitch, s->k2_count,
-                       bias, s->cm, s->N, s->n_views, global_feat);
 }
 
 void ndet_scene_k2_finish_ring_launch(const NdetSceneAccum* segs, int n_segs, int n_views, const float* bias, float* global_feat,
@@ -721,4 +627,11 @@ void ndet_scene_k2_finish_ring_launch(const NdetSceneAccum* segs, int n_segs, in
     const int64_t total = (int64_t)segs[0].N * (segs[0].cm / 4 + 1);
     hipLaunchKernelGGL(k_density_finish_ring, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, r, n_segs, bias, segs[0].cm,
                        segs[0].N, n_views, global_feat);
+}
+
+void ndet_scene_k2_finish_group_ring_launch(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_dev, const float* bias,
+                                            float* global_feat, hipStream_t stream) {
+    const int64_t total = (int64_t)pool->N * (pool->cm / 4 + 1);
+    hipLaunchKernelGGL(k_density_finish_group_ring, dim3((unsigned)((total + 255) / 256), sel->n), dim3(256), 0, stream, pool->table, *sel,
+                       segs_dev, (int)pool->k2_pitch, bias, pool->cm, pool->N, global_feat);
 }

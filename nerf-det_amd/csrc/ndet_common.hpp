@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/nerfdet_hip.h"
 
 #define NDET_WAVE 64
@@ -18,6 +20,13 @@ void ndet_set_error(const char* fmt, ...);
             ndet_set_error(__VA_ARGS__); \
             return (code);             \
         }                              \
+    } while (0)
+
+// ... and for a check that has set the message itself: its error code is the caller's
+#define NDET_TRY(call)                    \
+    do {                                  \
+        const int rc__ = (call);          \
+        if (rc__ != NDET_OK) return rc__; \
     } while (0)
 
 #define NDET_CHECK_LAUNCH(name)                                                      \
@@ -120,6 +129,20 @@ __device__ __forceinline__ bool ndet_depth_band(const NdetGateMap& g, int v, int
 int ndet_gate_prepare(const NdetDepthGate* g, const char* fn, int n_views, int h, int w, int H, int W, bool need_r,
                       NdetGateMap* gf, NdetGateMap* gr);
 
+// The gate with its map moved on by v0 views: what a launch (or a group kernel's block) over views v0 .. of the call indexes from 0.
+__host__ __device__ __forceinline__ NdetGateMap ndet_gate_from_view(const NdetGateMap& g, int64_t v0) {
+    NdetGateMap o = g;
+    o.map = static_cast<const char*>(g.map) + (size_t)v0 * g.view_pitch * (g.f64 ? sizeof(double) : sizeof(float));
+    return o;
+}
+
+// Host side: launch(std::true_type / std::false_type) by a run-time flag, for kernels that take the flag as a template argument.
+template <class F>
+static inline void ndet_by_flag(bool flag, F&& launch) {
+    if (flag) launch(std::true_type{});
+    else launch(std::false_type{});
+}
+
 // Streaming scenes (include/nerfdet_hip.h, NdetSceneAccum): launchers of K2's accumulate (<= 128 views) and finish kernels
 // (density_kernels.hip), called by the entry points in volume_kernels.hip once every argument has been checked.
 void ndet_scene_k2_accumulate_launch(const NdetSceneAccum* s, const float* mapped, int n_views, int h, int w, int mview_pitch, int mrow_pitch,
@@ -136,6 +159,23 @@ struct NdetRingArgs {
     int pitch[NDET_RING_MAX];
 };
 #define NDET_RING_BATCH 4   // segments whose loads a thread issues before it adds them (in array order)
+
+// Where a ring walk (k1_ring_sum in volume_kernels.hip, k2_ring_sums in density_kernels.hip) finds segment j: in the kernel-argument
+// block, or -- the grouped ring finishes -- in the workgroup's LDS arrays of resolved pointers, every state at the pool's pitch.
+struct NdetRingArgSegs {
+    const NdetRingArgs& r;
+    __device__ __forceinline__ const float* sum(int j) const { return r.sum[j]; }
+    __device__ __forceinline__ const int* count(int j) const { return r.count[j]; }
+    __device__ __forceinline__ int pitch(int j) const { return r.pitch[j]; }
+};
+struct NdetRingLdsSegs {
+    const float* const (&s_sum)[NDET_RING_MAX];
+    const int* const (&s_count)[NDET_RING_MAX];
+    int pool_pitch;
+    __device__ __forceinline__ const float* sum(int j) const { return s_sum[j]; }
+    __device__ __forceinline__ const int* count(int j) const { return s_count[j]; }
+    __device__ __forceinline__ int pitch(int) const { return pool_pitch; }
+};
 void ndet_scene_k2_finish_ring_launch(const NdetSceneAccum* segs, int n_segs, int n_views, const float* bias, float* global_feat,
                                       hipStream_t stream);
 

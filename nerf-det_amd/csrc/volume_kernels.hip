@@ -321,9 +321,9 @@ extern "C" int ndet_backproject_gated(const float* features, int n_views, int C,
 // writes = (C + 2) * N * 4 bytes.
 // ------------------------------------------------------------------------------------------
 // K1's view walk for the wave's voxels, phases A and B of k_backproject_aggregate below: adds the feature row of every view that sees a voxel
-// to acc, in ascending view order, and the number of those views to cnt.  Used by the streaming accumulate kernel (k_backproject_accumulate),
-// which starts from the scene's running sums instead of zero.  The one-shot kernel keeps its own copy of the walk: inlined through this
-// helper it compiles to other register allocations (more spills at NCHUNK = 2).
+// to acc, in ascending view order, and the number of those views to cnt.  Used by the streaming accumulate kernels (k1_accumulate_body),
+// which start from the scene's running sums instead of zero.  The one-shot kernel keeps its own copy of the walk: inlined through this
+// helper it compiles to other register allocations (at NCHUNK = 2, 114 spilled VGPRs instead of 24).
 constexpr int K1_VPW = VOX_PER_TILE / 4;  // voxels per wave, processed together
 template <int NCHUNK, bool DG>
 __device__ __forceinline__ void k1_walk(const float* __restrict__ feat, int n_views, int C, int h, int w, int64_t view_pitch, int row_pitch,
@@ -613,17 +613,27 @@ extern "C" int ndet_backproject_aggregate_gated(const float* features_nhwc, int 
 }
 
 // ------------------------------------------------------------------------------------------
-// Streaming scenes (include/nerfdet_hip.h, NdetSceneAccum): K1 split at its division.
+// Streaming scenes (include/nerfdet_hip.h): K1 split at its division, for one state (NdetSceneAccum), a ring of states
+// (ndet_scene_*_finish_ring), the listed scenes of a group (NdetSceneGroup, grid.y = listed scene) and the listed scenes' rings
+// (NdetGroupRingSel).
 //
 // K1-accumulate is k_backproject_aggregate's walk started from the scene's running sums (channels-last fp32) and count instead of zero,
 // stored back without the division.  The walk adds rows in ascending view order, so a scene fed in chunks holds the very sums one launch
 // over all its views forms.  K1-finish is K1's epilogue over the state; the state is only read.
+//
+// What the four families share is written once: the accumulate body (k1_accumulate_body around k1_walk), the sum over a ring's segments
+// (k1_ring_sum) and the finish of one (voxel, channel quad) (k1_finish_quad).  The kernels are what differs: where the state, the points
+// and the output row come from.  Not shared, on purpose: k_backproject_aggregate keeps its own walk and epilogue, because routed through
+// an inlined helper its C = 512 instantiation spilled 114 VGPRs instead of 24 ("Streaming scenes").  That was measured for
+// the one-shot kernel alone; the kernels below keep their LDS, scratch and occupancy with the helpers (DESIGN.md has the table).
 // ------------------------------------------------------------------------------------------
+// The accumulate kernels from the tile remap on: the tile's points, counts and running sums in, k1_walk over the n_views views at feat /
+// proj / dgate, sums and counts out.
 template <int NCHUNK, bool DG>
-__global__ __launch_bounds__(256, DG ? K1_MIN_WAVES - 1 : K1_MIN_WAVES) void k_backproject_accumulate(
-    const float* __restrict__ feat, int n_views, int C, int h, int w, int64_t view_pitch, int row_pitch,
-    const float* __restrict__ points, int N, const float* __restrict__ proj, float* __restrict__ sum, int pitch,
-    int* __restrict__ count, int n_tiles, NdetGateMap dgate) {
+__device__ __forceinline__ void k1_accumulate_body(const float* __restrict__ feat, int n_views, int C, int h, int w, int64_t view_pitch,
+                                                   int row_pitch, const float* __restrict__ points, int N, const float* __restrict__ proj,
+                                                   float* __restrict__ sum, int pitch, int* __restrict__ count, int n_tiles,
+                                                   const NdetGateMap& dgate) {
     constexpr int VPW = K1_VPW;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -663,172 +673,51 @@ __global__ __launch_bounds__(256, DG ? K1_MIN_WAVES - 1 : K1_MIN_WAVES) void k_b
     }
 }
 
-// One thread per (voxel, channel quad): K1's epilogue, expression for expression (k_backproject_aggregate above).
-__global__ __launch_bounds__(256) void k_volume_finish(const float* __restrict__ sum, int pitch, const int* __restrict__ count,
-                                                       const float* __restrict__ alpha, int C, int N, float* __restrict__ out,
-                                                       int64_t* __restrict__ out_count) {
-    const int c4 = C >> 2;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)N * c4) return;
-    const int n = (int)(i / c4), q = (int)(i % c4);
-    const int cnt = count[n];
+// K1's epilogue for channel quad q of one voxel, expression for expression (k_backproject_aggregate above): s and cnt are the voxel's
+// summed rows and view count, `row` its row of alpha, out and out_count.
+__device__ __forceinline__ void k1_finish_quad(float4 s, int cnt, const float* __restrict__ alpha, int64_t row, int C, int q,
+                                               float* __restrict__ out, int64_t* __restrict__ out_count) {
     const float denom = (float)cnt + 1e-8f;
-    const float4 s = *reinterpret_cast<const float4*>(sum + (int64_t)n * pitch + q * 4);
     float4 mean;
     mean.x = s.x / denom;
     mean.y = s.y / denom;
     mean.z = s.z / denom;
     mean.w = s.w / denom;
     if (alpha) {
-        const float a = alpha[n];
+        const float a = alpha[row];
         mean.x = a * mean.x;
         mean.y = a * mean.y;
         mean.z = a * mean.z;
         mean.w = a * mean.w;
     }
     if (cnt == 0) mean = make_float4(0.f, 0.f, 0.f, 0.f);
-    *reinterpret_cast<float4*>(out + (int64_t)n * C + q * 4) = mean;
-    if (q == 0) out_count[n] = (int64_t)cnt;
+    *reinterpret_cast<float4*>(out + row * C + q * 4) = mean;
+    if (q == 0) out_count[row] = (int64_t)cnt;
 }
 
-// The block's own fields (pointers, sizes, pitches, alignment), checked before any launch.
-static int scene_check(const NdetSceneAccum* s, const char* fn) {
-    NDET_REQUIRE(s, NDET_E_INVALID, "%s: null scene state", fn);
-    NDET_REQUIRE(s->size == (int32_t)sizeof(NdetSceneAccum), NDET_E_INVALID, "%s: NdetSceneAccum.size %d != %d (caller built against another layout)",
-                 fn, s->size, (int)sizeof(NdetSceneAccum));
-    NDET_REQUIRE(s->k1_sum && s->k1_count && s->k2_sum && s->k2_count, NDET_E_INVALID, "%s: null pointer in the scene state", fn);
-    NDET_REQUIRE(s->N > 0 && s->C > 0 && s->cm > 0 && s->n_views >= 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
-    NDET_REQUIRE(s->C % 4 == 0 && s->C <= 1024, NDET_E_UNSUPPORTED, "%s: C=%d must be a multiple of 4 and <= 1024", fn, s->C);
-    NDET_REQUIRE(s->cm % 4 == 0 && s->cm <= 128, NDET_E_UNSUPPORTED, "%s: cm=%d must be a multiple of 4 and <= 128", fn, s->cm);
-    NDET_REQUIRE(s->k1_pitch >= s->C && s->k2_pitch >= 3 * (s->cm + 4), NDET_E_INVALID, "%s: state pitches smaller than a row", fn);
-    NDET_REQUIRE(s->k1_pitch < ((int64_t)1 << 31) && s->k2_pitch < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: state pitches exceed int32", fn);
-    NDET_REQUIRE(s->k1_pitch % 4 == 0 && s->k2_pitch % 4 == 0 && (((uintptr_t)s->k1_sum | (uintptr_t)s->k2_sum) & 15) == 0 &&
-                     (((uintptr_t)s->k1_count & 3) | ((uintptr_t)s->k2_count & 7)) == 0,
-                 NDET_E_UNSUPPORTED, "%s: state rows must be 16-byte aligned", fn);
-    return NDET_OK;
-}
-
-extern "C" int ndet_scene_accumulate(const NdetSceneAccum* s, const float* features_nhwc, int n_views, int h, int w,
-                                     int64_t view_pitch, int64_t row_pitch, const float* mapped_nhwc, int64_t mview_pitch,
-                                     int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv, int64_t rsc,
-                                     int64_t rsy, const float* points, const float* projection, const float* rgb_projection,
-                                     const NdetDepthGate* gate, void* stream) {
-    const char* fn = "ndet_scene_accumulate";
-    int rc = scene_check(s, fn);
-    if (rc != NDET_OK) return rc;
-    const int N = s->N, C = s->C, cm = s->cm;
-    NDET_REQUIRE(features_nhwc && mapped_nhwc && bias && rgb && points && projection && rgb_projection, NDET_E_INVALID, "%s: null pointer", fn);
-    NDET_REQUIRE(n_views > 0 && h > 0 && w > 0 && H > 0 && W > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
-    NDET_REQUIRE(s->n_views <= 0x7fffffff - n_views, NDET_E_UNSUPPORTED, "%s: view count overflows int32", fn);
-    // K1's inputs (backproject_aggregate_impl)
-    NDET_REQUIRE(row_pitch >= (int64_t)w * C && view_pitch >= (int64_t)h * row_pitch, NDET_E_INVALID, "%s: feature pitches smaller than the map", fn);
-    NDET_REQUIRE(row_pitch % 4 == 0 && view_pitch % 4 == 0 && ((uintptr_t)features_nhwc & 15) == 0, NDET_E_UNSUPPORTED,
-                 "%s: feature rows must be 16-byte aligned", fn);
-    NDET_REQUIRE((int64_t)h * row_pitch < (int64_t)1 << 31, NDET_E_UNSUPPORTED, "%s: one view exceeds 2^31 floats", fn);
-    // K2's inputs (density_features_packed_impl), per launch of at most 128 views
-    const int per = n_views < 128 ? n_views : 128;
-    NDET_REQUIRE(mrow_pitch >= (int64_t)w * cm && mview_pitch >= (int64_t)h * mrow_pitch && rsy >= W && rsc >= 0 && rsv >= 0, NDET_E_INVALID,
-                 "%s: mapped / image pitches smaller than the maps", fn);
-    NDET_REQUIRE((int64_t)per * mview_pitch < ((int64_t)1 << 31) && (int64_t)per * rsv + 3 * rsc < ((int64_t)1 << 31), NDET_E_UNSUPPORTED,
-                 "%s: a launch's source tensor exceeds 2^31 floats", fn);
-    NDET_REQUIRE(mview_pitch % 4 == 0 && mrow_pitch % 4 == 0 && (((uintptr_t)mapped_nhwc | (uintptr_t)bias) & 15) == 0, NDET_E_UNSUPPORTED,
-                 "%s: mapped features / bias must keep channel quads 16-byte aligned", fn);
-    NdetGateMap gf = {}, gr = {};
-    if (gate) {
-        rc = ndet_gate_prepare(gate, fn, n_views, h, w, H, W, true, &gf, &gr);
-        if (rc != NDET_OK) return rc;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int n_tiles = (N + VOX_PER_TILE - 1) / VOX_PER_TILE;
-    const int rp = (int)row_pitch, k1p = (int)s->k1_pitch;
-#define K1A_LAUNCH(NC, DG)                                                                                                                \
-    hipLaunchKernelGGL((k_backproject_accumulate<NC, DG>), dim3(n_tiles), dim3(256), 0, st, features_nhwc, n_views, C, h, w, view_pitch, rp, \
-                       points, N, projection, s->k1_sum, k1p, s->k1_count, n_tiles, gf)
-#define K1A_CHUNKS(DG)                \
-    if (C <= 256) K1A_LAUNCH(1, DG);  \
-    else if (C <= 512) K1A_LAUNCH(2, DG); \
-    else K1A_LAUNCH(4, DG)
-    if (gate) {
-        K1A_CHUNKS(true);
-    } else {
-        K1A_CHUNKS(false);
-    }
-#undef K1A_CHUNKS
-#undef K1A_LAUNCH
-    NDET_CHECK_LAUNCH(fn);
-    for (int v0 = 0; v0 < n_views; v0 += 128) {
-        const int nv = n_views - v0 < 128 ? n_views - v0 : 128;
-        NdetGateMap gf1 = gf, gr1 = gr;
-        if (gate) {
-            const size_t es = gf.f64 ? sizeof(double) : sizeof(float);
-            gf1.map = (const char*)gf.map + (size_t)v0 * gf.view_pitch * es;
-            gr1.map = (const char*)gr.map + (size_t)v0 * gr.view_pitch * es;
-        }
-        ndet_scene_k2_accumulate_launch(s, mapped_nhwc + (int64_t)v0 * mview_pitch, nv, h, w, (int)mview_pitch, (int)mrow_pitch, bias,
-                                        rgb + (int64_t)v0 * rsv, H, W, (int)rsv, (int)rsc, (int)rsy, points, projection + (int64_t)v0 * 12,
-                                        rgb_projection + (int64_t)v0 * 12, gate != nullptr, gf1, gr1, st);
-        NDET_CHECK_LAUNCH(fn);
-    }
-    return NDET_OK;
-}
-
-extern "C" int ndet_scene_density_finish(const NdetSceneAccum* s, const float* bias, float* global_feat, void* stream) {
-    const char* fn = "ndet_scene_density_finish";
-    const int rc = scene_check(s, fn);
-    if (rc != NDET_OK) return rc;
-    NDET_REQUIRE(bias && global_feat, NDET_E_INVALID, "%s: null pointer", fn);
-    NDET_REQUIRE(((uintptr_t)global_feat & 7) == 0, NDET_E_UNSUPPORTED, "%s: global_feat must be 8-byte aligned", fn);
-    NDET_REQUIRE(((int64_t)s->N * (s->cm + 3) + 255) / 256 < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
-    ndet_scene_k2_finish_launch(s, bias, global_feat, (hipStream_t)stream);
-    NDET_CHECK_LAUNCH(fn);
-    return NDET_OK;
-}
-
-extern "C" int ndet_scene_volume_finish(const NdetSceneAccum* s, const float* alpha, float* out, int64_t* count, void* stream) {
-    const char* fn = "ndet_scene_volume_finish";
-    const int rc = scene_check(s, fn);
-    if (rc != NDET_OK) return rc;
-    NDET_REQUIRE(out && count, NDET_E_INVALID, "%s: null pointer", fn);
-    NDET_REQUIRE(((uintptr_t)out & 15) == 0, NDET_E_UNSUPPORTED, "%s: out must be 16-byte aligned", fn);
-    const int64_t blocks = ((int64_t)s->N * (s->C / 4) + 255) / 256;
-    NDET_REQUIRE(blocks < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
-    hipLaunchKernelGGL(k_volume_finish, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, s->k1_sum, (int)s->k1_pitch, s->k1_count,
-                       alpha, s->C, s->N, out, count);
-    NDET_CHECK_LAUNCH(fn);
-    return NDET_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// Sliding windows (include/nerfdet_hip.h, ndet_scene_*_finish_ring): one state per chunk, finished over a list of states.
-//
-// k_volume_finish_ring is k_volume_finish (its own copy) with the row sum and count formed over the segments first: the accumulator starts
-// from the oldest segment's values, the others are added in array order, NDET_RING_BATCH segments at a time -- their counts are loaded
-// first, then the rows of those that see the voxel (a segment that does not holds an all-zero row: adding +0 instead changes at most the
-// sign of a zero), then the adds.  With one segment the loop does not run and the expressions are k_volume_finish's.
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_volume_finish_ring(NdetRingArgs r, int n_segs, const float* __restrict__ alpha, int C, int N,
-                                                            float* __restrict__ out, int64_t* __restrict__ out_count) {
+// Channel quad q of voxel n summed over a ring's segments (Segs: NdetRingArgSegs or NdetRingLdsSegs, ndet_common.hpp), and the voxel's
+// view count.  The accumulator starts from the oldest segment's values, the others are added in array order, NDET_RING_BATCH segments at
+// a time -- their counts are loaded first, then the rows of those that see the voxel (a segment that does not holds an all-zero row: adding
+// +0 instead changes at most the sign of a zero), then the adds.  With one segment the loop does not run and s, cnt are the state's own.
+template <class Segs>
+__device__ __forceinline__ void k1_ring_sum(const Segs& g, int n_segs, int n, int q, float4& s, int& cnt) {
     constexpr int U = NDET_RING_BATCH;
-    const int c4 = C >> 2;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)N * c4) return;
-    const int n = (int)(i / c4), q = (int)(i % c4);
-    int cnt = r.count[0][n];
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (cnt != 0) s = *reinterpret_cast<const float4*>(r.sum[0] + (int64_t)n * r.pitch[0] + q * 4);
+    cnt = g.count(0)[n];
+    s = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (cnt != 0) s = *reinterpret_cast<const float4*>(g.sum(0) + (int64_t)n * g.pitch(0) + q * 4);
     for (int s0 = 1; s0 < n_segs; s0 += U) {
         int cc[U];
         float4 vv[U];
 #pragma unroll
         for (int j = 0; j < U; ++j) {
             const int sj = min(s0 + j, n_segs - 1);     // past the end: the last segment's slot, not read (cc = 0)
-            cc[j] = (s0 + j < n_segs) ? r.count[sj][n] : 0;
+            cc[j] = (s0 + j < n_segs) ? g.count(sj)[n] : 0;
         }
 #pragma unroll
         for (int j = 0; j < U; ++j) {
             const int sj = min(s0 + j, n_segs - 1);
             vv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (cc[j] != 0) vv[j] = *reinterpret_cast<const float4*>(r.sum[sj] + (int64_t)n * r.pitch[sj] + q * 4);
+            if (cc[j] != 0) vv[j] = *reinterpret_cast<const float4*>(g.sum(sj) + (int64_t)n * g.pitch(sj) + q * 4);
         }
 #pragma unroll
         for (int j = 0; j < U; ++j) {
@@ -839,26 +728,126 @@ __global__ __launch_bounds__(256) void k_volume_finish_ring(NdetRingArgs r, int 
             cnt += cc[j];
         }
     }
-    const float denom = (float)cnt + 1e-8f;
-    float4 mean;
-    mean.x = s.x / denom;
-    mean.y = s.y / denom;
-    mean.z = s.z / denom;
-    mean.w = s.w / denom;
-    if (alpha) {
-        const float a = alpha[n];
-        mean.x = a * mean.x;
-        mean.y = a * mean.y;
-        mean.z = a * mean.z;
-        mean.w = a * mean.w;
-    }
-    if (cnt == 0) mean = make_float4(0.f, 0.f, 0.f, 0.f);
-    *reinterpret_cast<float4*>(out + (int64_t)n * C + q * 4) = mean;
-    if (q == 0) out_count[n] = (int64_t)cnt;
 }
 
-// The segment list of a ring finish, checked before any launch: every block as scene_check checks it (the message names the segment),
-// equal N / C / cm, a view total within int32.
+// The depth-gated instantiations run one wave fewer per SIMD, as k_backproject_aggregate's do.
+template <int NCHUNK, bool DG>
+__global__ __launch_bounds__(256, DG ? K1_MIN_WAVES - 1 : K1_MIN_WAVES) void k_backproject_accumulate(
+    const float* __restrict__ feat, int n_views, int C, int h, int w, int64_t view_pitch, int row_pitch,
+    const float* __restrict__ points, int N, const float* __restrict__ proj, float* __restrict__ sum, int pitch,
+    int* __restrict__ count, int n_tiles, NdetGateMap dgate) {
+    k1_accumulate_body<NCHUNK, DG>(feat, n_views, C, h, w, view_pitch, row_pitch, points, N, proj, sum, pitch, count, n_tiles, dgate);
+}
+
+// The listed scenes' chunks in one launch.  A block reads its scene's row of the device table, moves the view-indexed inputs on by y * k
+// views -- as the host loop of ndet_scene_accumulate moves them on per 128-view launch -- and runs the body on that scene's state and
+// points; no block reads or writes another scene's state.  The XCD remap stays on blockIdx.x: a scene's neighbouring tiles still share an
+// L2, which XCD a slab lands on differs from row to row when the tile count is no multiple of 8 (locality only).
+template <int NCHUNK, bool DG>
+__global__ __launch_bounds__(256, DG ? K1_MIN_WAVES - 1 : K1_MIN_WAVES) void k_backproject_accumulate_group(
+    const NdetSceneSlot* __restrict__ table, NdetGroupSel sel, int k, const float* __restrict__ feat_all, int C, int h, int w,
+    int64_t view_pitch, int row_pitch, int N, const float* __restrict__ proj_all, int pitch, int n_tiles, NdetGateMap dgate_all) {
+    const int y = blockIdx.y;                                  // listed scene: block-uniform, the row comes in through scalar loads
+    const NdetSceneSlot& sl = table[sel.slot[y]];
+    const int64_t v0 = (int64_t)y * k;                         // the scene's first view of the call
+    k1_accumulate_body<NCHUNK, DG>(feat_all + v0 * view_pitch, k, C, h, w, view_pitch, row_pitch, sl.points, N, proj_all + v0 * 12, sl.k1_sum,
+                                   pitch, sl.k1_count, n_tiles, DG ? ndet_gate_from_view(dgate_all, v0) : dgate_all);
+}
+
+// One thread per (voxel, channel quad) in all four finishes; the grouped ones write output row y N + n and index alpha the same way.
+__global__ __launch_bounds__(256) void k_volume_finish(const float* __restrict__ sum, int pitch, const int* __restrict__ count,
+                                                       const float* __restrict__ alpha, int C, int N, float* __restrict__ out,
+                                                       int64_t* __restrict__ out_count) {
+    const int c4 = C >> 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)N * c4) return;
+    const int n = (int)(i / c4), q = (int)(i % c4);
+    const int cnt = count[n];
+    k1_finish_quad(*reinterpret_cast<const float4*>(sum + (int64_t)n * pitch + q * 4), cnt, alpha, n, C, q, out, out_count);
+}
+
+__global__ __launch_bounds__(256) void k_volume_finish_ring(NdetRingArgs r, int n_segs, const float* __restrict__ alpha, int C, int N,
+                                                            float* __restrict__ out, int64_t* __restrict__ out_count) {
+    const int c4 = C >> 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)N * c4) return;
+    const int n = (int)(i / c4), q = (int)(i % c4);
+    float4 s;
+    int cnt;
+    k1_ring_sum(NdetRingArgSegs{r}, n_segs, n, q, s, cnt);
+    k1_finish_quad(s, cnt, alpha, n, C, q, out, out_count);
+}
+
+__global__ __launch_bounds__(256) void k_volume_finish_group(const NdetSceneSlot* __restrict__ table, NdetGroupSel sel, int pitch,
+                                                             const float* __restrict__ alpha, int C, int N, float* __restrict__ out,
+                                                             int64_t* __restrict__ out_count) {
+    const int c4 = C >> 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)N * c4) return;
+    const int y = blockIdx.y;
+    const NdetSceneSlot& sl = table[sel.slot[y]];
+    const int n = (int)(i / c4), q = (int)(i % c4);
+    const int cnt = sl.k1_count[n];
+    k1_finish_quad(*reinterpret_cast<const float4*>(sl.k1_sum + (int64_t)n * pitch + q * 4), cnt, alpha, (int64_t)y * N + n, C, q, out,
+                   out_count);
+}
+
+// The segments are found through memory: segs[y][j] is a row of the pool table, the row holds the state's pointers.  That chain is
+// block-uniform, so threads 0 .. n_segs - 1 resolve it once into LDS (64 x 16 bytes) and the walk reads its pointers from there after one
+// barrier; the threads past N c4 stay for the barrier and do nothing after it.  The state pitch is the pool's.
+__global__ __launch_bounds__(256) void k_volume_finish_group_ring(const NdetSceneSlot* __restrict__ table, NdetGroupRingSel sel,
+                                                                  const int32_t* __restrict__ segs, int pitch,
+                                                                  const float* __restrict__ alpha, int C, int N, float* __restrict__ out,
+                                                                  int64_t* __restrict__ out_count) {
+    __shared__ const float* s_sum[NDET_RING_MAX];
+    __shared__ const int* s_count[NDET_RING_MAX];
+    const int y = blockIdx.y;
+    const int n_segs = sel.n_segs[y];
+    if ((int)threadIdx.x < n_segs) {
+        const NdetSceneSlot& sl = table[segs[y * NDET_RING_MAX + threadIdx.x]];
+        s_sum[threadIdx.x] = sl.k1_sum;
+        s_count[threadIdx.x] = sl.k1_count;
+    }
+    __syncthreads();
+    const int c4 = C >> 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (int64_t)N * c4) {
+        const int n = (int)(i / c4), q = (int)(i % c4);
+        float4 s;
+        int cnt;
+        k1_ring_sum(NdetRingLdsSegs{s_sum, s_count, pitch}, n_segs, n, q, s, cnt);
+        k1_finish_quad(s, cnt, alpha, (int64_t)y * N + n, C, q, out, out_count);
+    }
+}
+
+// ---- host checks, all before any launch ----
+// A state's sizes and pitches: the same for a single state's block, a group's and a pool's.
+static int state_dims_check(const char* fn, int N, int C, int cm, int64_t k1_pitch, int64_t k2_pitch) {
+    NDET_REQUIRE(N > 0 && C > 0 && cm > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
+    NDET_REQUIRE(C % 4 == 0 && C <= 1024, NDET_E_UNSUPPORTED, "%s: C=%d must be a multiple of 4 and <= 1024", fn, C);
+    NDET_REQUIRE(cm % 4 == 0 && cm <= 128, NDET_E_UNSUPPORTED, "%s: cm=%d must be a multiple of 4 and <= 128", fn, cm);
+    NDET_REQUIRE(k1_pitch >= C && k2_pitch >= 3 * (cm + 4), NDET_E_INVALID, "%s: state pitches smaller than a row", fn);
+    NDET_REQUIRE(k1_pitch < ((int64_t)1 << 31) && k2_pitch < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: state pitches exceed int32", fn);
+    NDET_REQUIRE(k1_pitch % 4 == 0 && k2_pitch % 4 == 0, NDET_E_UNSUPPORTED, "%s: state rows must be 16-byte aligned", fn);
+    return NDET_OK;
+}
+
+// A single state's block (pointers, sizes, pitches, alignment).
+static int scene_check(const NdetSceneAccum* s, const char* fn) {
+    NDET_REQUIRE(s, NDET_E_INVALID, "%s: null scene state", fn);
+    NDET_REQUIRE(s->size == (int32_t)sizeof(NdetSceneAccum), NDET_E_INVALID, "%s: NdetSceneAccum.size %d != %d (caller built against another layout)",
+                 fn, s->size, (int)sizeof(NdetSceneAccum));
+    NDET_REQUIRE(s->k1_sum && s->k1_count && s->k2_sum && s->k2_count, NDET_E_INVALID, "%s: null pointer in the scene state", fn);
+    NDET_REQUIRE(s->n_views >= 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
+    const int rc = state_dims_check(fn, s->N, s->C, s->cm, s->k1_pitch, s->k2_pitch);
+    if (rc != NDET_OK) return rc;
+    NDET_REQUIRE((((uintptr_t)s->k1_sum | (uintptr_t)s->k2_sum) & 15) == 0 && (((uintptr_t)s->k1_count & 3) | ((uintptr_t)s->k2_count & 7)) == 0,
+                 NDET_E_UNSUPPORTED, "%s: state rows must be 16-byte aligned", fn);
+    return NDET_OK;
+}
+
+// The segment list of a ring finish: every block as scene_check checks it (the message names the segment), equal N / C / cm, a view
+// total within int32.
 static int ring_check(const NdetSceneAccum* segs, int n_segs, const char* fn, int* total_views) {
     NDET_REQUIRE(segs, NDET_E_INVALID, "%s: null segs", fn);
     NDET_REQUIRE(n_segs >= 1 && n_segs <= NDET_RING_MAX, NDET_E_INVALID, "%s: n_segs=%d must be 1 .. %d", fn, n_segs, NDET_RING_MAX);
@@ -881,152 +870,22 @@ static int ring_check(const NdetSceneAccum* segs, int n_segs, const char* fn, in
     return NDET_OK;
 }
 
-extern "C" int ndet_scene_density_finish_ring(const NdetSceneAccum* segs, int n_segs, const float* bias, float* global_feat, void* stream) {
-    const char* fn = "ndet_scene_density_finish_ring";
-    int n_views = 0;
-    const int rc = ring_check(segs, n_segs, fn, &n_views);
-    if (rc != NDET_OK) return rc;
-    NDET_REQUIRE(bias, NDET_E_INVALID, "%s: null bias", fn);
-    NDET_REQUIRE(global_feat, NDET_E_INVALID, "%s: null global_feat", fn);
-    NDET_REQUIRE(((uintptr_t)global_feat & 7) == 0, NDET_E_UNSUPPORTED, "%s: global_feat must be 8-byte aligned", fn);
-    NDET_REQUIRE(((int64_t)segs[0].N * (segs[0].cm / 4 + 1) + 255) / 256 < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
-    ndet_scene_k2_finish_ring_launch(segs, n_segs, n_views, bias, global_feat, (hipStream_t)stream);
-    NDET_CHECK_LAUNCH(fn);
-    return NDET_OK;
-}
-
-extern "C" int ndet_scene_volume_finish_ring(const NdetSceneAccum* segs, int n_segs, const float* alpha, float* out, int64_t* count,
-                                             void* stream) {
-    const char* fn = "ndet_scene_volume_finish_ring";
-    int n_views = 0;
-    const int rc = ring_check(segs, n_segs, fn, &n_views);
-    if (rc != NDET_OK) return rc;
-    NDET_REQUIRE(out, NDET_E_INVALID, "%s: null out", fn);
-    NDET_REQUIRE(count, NDET_E_INVALID, "%s: null count", fn);
-    NDET_REQUIRE(((uintptr_t)out & 15) == 0, NDET_E_UNSUPPORTED, "%s: out must be 16-byte aligned", fn);
-    NDET_REQUIRE(((uintptr_t)count & 7) == 0, NDET_E_UNSUPPORTED, "%s: count must be 8-byte aligned", fn);
-    const int64_t blocks = ((int64_t)segs[0].N * (segs[0].C / 4) + 255) / 256;
-    NDET_REQUIRE(blocks < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
-    NdetRingArgs r = {};
-    for (int i = 0; i < n_segs; ++i) {
-        r.sum[i] = segs[i].k1_sum;
-        r.count[i] = segs[i].k1_count;
-        r.pitch[i] = (int)segs[i].k1_pitch;
-    }
-    hipLaunchKernelGGL(k_volume_finish_ring, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, r, n_segs, alpha, segs[0].C, segs[0].N,
-                       out, count);
-    NDET_CHECK_LAUNCH(fn);
-    return NDET_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// Scene groups (include/nerfdet_hip.h, NdetSceneSlot / NdetSceneGroup / NdetGroupSel): many scenes' chunks in one launch, grid.y = listed
-// scene.  A block reads its scene's row of the device table, moves the view-indexed inputs on by y * k views -- as the host loop of
-// ndet_scene_accumulate moves them on per 128-view launch -- and runs the single-scene walk on that scene's state and points.  The kernels
-// are copies of their parents' bodies around the shared walks (k1_walk, k2_packed_sums); no block reads or writes another scene's state.
-// The XCD remap stays on blockIdx.x: a scene's neighbouring tiles still share an L2, which XCD a slab lands on differs from row to row
-// when the tile count is no multiple of 8 (locality only).
-// ------------------------------------------------------------------------------------------
-template <int NCHUNK, bool DG>
-__global__ __launch_bounds__(256, DG ? K1_MIN_WAVES - 1 : K1_MIN_WAVES) void k_backproject_accumulate_group(
-    const NdetSceneSlot* __restrict__ table, NdetGroupSel sel, int k, const float* __restrict__ feat_all, int C, int h, int w,
-    int64_t view_pitch, int row_pitch, int N, const float* __restrict__ proj_all, int pitch, int n_tiles, NdetGateMap dgate_all) {
-    constexpr int VPW = K1_VPW;
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int y = blockIdx.y;                                  // listed scene: block-uniform, the row comes in through scalar loads
-    const NdetSceneSlot& sl = table[sel.slot[y]];
-    const float* __restrict__ points = sl.points;
-    float* __restrict__ sum = sl.k1_sum;
-    int* __restrict__ count = sl.k1_count;
-    const int64_t v0 = (int64_t)y * k;                         // the scene's first view of the call
-    const float* __restrict__ feat = feat_all + v0 * view_pitch;
-    const float* __restrict__ proj = proj_all + v0 * 12;
-    NdetGateMap dgate = dgate_all;
-    if (DG) dgate.map = static_cast<const char*>(dgate_all.map) + (size_t)v0 * dgate_all.view_pitch * (dgate_all.f64 ? sizeof(double) : sizeof(float));
-    const int tile = ndet_xcd_remap(blockIdx.x, n_tiles);
-    const int n0 = tile * VOX_PER_TILE;
-    const int c4 = C >> 2;
-    float px[VPW], py[VPW], pz[VPW];
-    bool live[VPW];
-    float4 acc[VPW][NCHUNK];
-    int cnt[VPW];
-#pragma unroll
-    for (int j = 0; j < VPW; ++j) {
-        const int n = n0 + j * 4 + wave;
-        live[j] = n < N;  // wave-uniform
-        const int nn = live[j] ? n : 0;
-        px[j] = points[nn];
-        py[j] = points[N + nn];
-        pz[j] = points[2 * N + nn];
-        cnt[j] = live[j] ? count[nn] : 0;
-#pragma unroll
-        for (int q = 0; q < NCHUNK; ++q) {
-            const int ci = lane + q * 64;
-            acc[j][q] = (live[j] && ci < c4) ? *reinterpret_cast<const float4*>(sum + (int64_t)nn * pitch + ci * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-    k1_walk<NCHUNK, DG>(feat, k, C, h, w, view_pitch, row_pitch, proj, px, py, pz, live, acc, cnt, dgate, lane);
-#pragma unroll
-    for (int j = 0; j < VPW; ++j) {
-        if (!live[j]) continue;
-        const int n = n0 + j * 4 + wave;
-#pragma unroll
-        for (int q = 0; q < NCHUNK; ++q) {
-            const int ci = lane + q * 64;
-            if (ci < c4) *reinterpret_cast<float4*>(sum + (int64_t)n * pitch + ci * 4) = acc[j][q];
-        }
-        if (lane == 0) count[n] = cnt[j];
-    }
-}
-
-// k_volume_finish (its own copy, expression for expression) for the listed scenes: output row y N + n, alpha indexed the same way.
-__global__ __launch_bounds__(256) void k_volume_finish_group(const NdetSceneSlot* __restrict__ table, NdetGroupSel sel, int pitch,
-                                                             const float* __restrict__ alpha, int C, int N, float* __restrict__ out,
-                                                             int64_t* __restrict__ out_count) {
-    const int c4 = C >> 2;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)N * c4) return;
-    const int y = blockIdx.y;
-    const NdetSceneSlot& sl = table[sel.slot[y]];
-    const float* __restrict__ sum = sl.k1_sum;
-    const int* __restrict__ count = sl.k1_count;
-    const int n = (int)(i / c4), q = (int)(i % c4);
-    const int64_t row = (int64_t)y * N + n;
-    const int cnt = count[n];
-    const float denom = (float)cnt + 1e-8f;
-    const float4 s = *reinterpret_cast<const float4*>(sum + (int64_t)n * pitch + q * 4);
-    float4 mean;
-    mean.x = s.x / denom;
-    mean.y = s.y / denom;
-    mean.z = s.z / denom;
-    mean.w = s.w / denom;
-    if (alpha) {
-        const float a = alpha[row];
-        mean.x = a * mean.x;
-        mean.y = a * mean.y;
-        mean.z = a * mean.z;
-        mean.w = a * mean.w;
-    }
-    if (cnt == 0) mean = make_float4(0.f, 0.f, 0.f, 0.f);
-    *reinterpret_cast<float4*>(out + row * C + q * 4) = mean;
-    if (q == 0) out_count[row] = (int64_t)cnt;
-}
-
-// The group's block and a call's selection, checked before any launch (the table itself is device memory: its rows are the caller's).
-static int group_check(const NdetSceneGroup* g, const NdetGroupSel* sel, int k, const char* fn) {
-    NDET_REQUIRE(g, NDET_E_INVALID, "%s: null scene group", fn);
+// A table block (the table itself is device memory: its rows are the caller's): a `what` = "scene group" of up to NDET_GROUP_MAX rows,
+// or a "state pool" of up to NDET_GROUP_POOL_MAX (NDET_RING_MAX + 1 states per scene).
+static int table_check(const NdetSceneGroup* g, const char* fn, const char* what, const char* table, int max_slots) {
+    NDET_REQUIRE(g, NDET_E_INVALID, "%s: null %s", fn, what);
     NDET_REQUIRE(g->size == (int32_t)sizeof(NdetSceneGroup), NDET_E_INVALID, "%s: NdetSceneGroup.size %d != %d (caller built against another layout)",
                  fn, g->size, (int)sizeof(NdetSceneGroup));
-    NDET_REQUIRE(g->table, NDET_E_INVALID, "%s: null scene table", fn);
-    NDET_REQUIRE(((uintptr_t)g->table & 15) == 0, NDET_E_UNSUPPORTED, "%s: the scene table must be 16-byte aligned", fn);
-    NDET_REQUIRE(g->n_slots >= 1 && g->n_slots <= NDET_GROUP_MAX, NDET_E_INVALID, "%s: n_slots=%d must be 1 .. %d", fn, g->n_slots, NDET_GROUP_MAX);
-    NDET_REQUIRE(g->N > 0 && g->C > 0 && g->cm > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
-    NDET_REQUIRE(g->C % 4 == 0 && g->C <= 1024, NDET_E_UNSUPPORTED, "%s: C=%d must be a multiple of 4 and <= 1024", fn, g->C);
-    NDET_REQUIRE(g->cm % 4 == 0 && g->cm <= 128, NDET_E_UNSUPPORTED, "%s: cm=%d must be a multiple of 4 and <= 128", fn, g->cm);
-    NDET_REQUIRE(g->k1_pitch >= g->C && g->k2_pitch >= 3 * (g->cm + 4), NDET_E_INVALID, "%s: state pitches smaller than a row", fn);
-    NDET_REQUIRE(g->k1_pitch < ((int64_t)1 << 31) && g->k2_pitch < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: state pitches exceed int32", fn);
-    NDET_REQUIRE(g->k1_pitch % 4 == 0 && g->k2_pitch % 4 == 0, NDET_E_UNSUPPORTED, "%s: state rows must be 16-byte aligned", fn);
+    NDET_REQUIRE(g->table, NDET_E_INVALID, "%s: null %s table", fn, table);
+    NDET_REQUIRE(((uintptr_t)g->table & 15) == 0, NDET_E_UNSUPPORTED, "%s: the %s table must be 16-byte aligned", fn, table);
+    NDET_REQUIRE(g->n_slots >= 1 && g->n_slots <= max_slots, NDET_E_INVALID, "%s: n_slots=%d must be 1 .. %d", fn, g->n_slots, max_slots);
+    return state_dims_check(fn, g->N, g->C, g->cm, g->k1_pitch, g->k2_pitch);
+}
+
+// A group's block and a call's selection.
+static int group_check(const NdetSceneGroup* g, const NdetGroupSel* sel, int k, const char* fn) {
+    const int rc = table_check(g, fn, "scene group", "scene", NDET_GROUP_MAX);
+    if (rc != NDET_OK) return rc;
     NDET_REQUIRE(sel, NDET_E_INVALID, "%s: null selection", fn);
     NDET_REQUIRE(sel->size == (int32_t)sizeof(NdetGroupSel), NDET_E_INVALID, "%s: NdetGroupSel.size %d != %d (caller built against another layout)",
                  fn, sel->size, (int)sizeof(NdetGroupSel));
@@ -1044,188 +903,9 @@ static int group_check(const NdetSceneGroup* g, const NdetGroupSel* sel, int k, 
     return NDET_OK;
 }
 
-extern "C" int ndet_scene_group_check(const NdetSceneGroup* g, const NdetGroupSel* sel, int k) {
-    return group_check(g, sel, k, "ndet_scene_group_check");
-}
-
-extern "C" int ndet_scene_accumulate_group(const NdetSceneGroup* g, const NdetGroupSel* sel, int k, const float* features_nhwc, int h, int w,
-                                           int64_t view_pitch, int64_t row_pitch, const float* mapped_nhwc, int64_t mview_pitch,
-                                           int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv, int64_t rsc,
-                                           int64_t rsy, const float* projection, const float* rgb_projection, const NdetDepthGate* gate,
-                                           void* stream) {
-    const char* fn = "ndet_scene_accumulate_group";
-    NDET_REQUIRE(k >= 1 && k <= 128, NDET_E_UNSUPPORTED, "%s: k=%d views per scene, must be 1 .. 128", fn, k);
-    int rc = group_check(g, sel, k, fn);
-    if (rc != NDET_OK) return rc;
-    const int N = g->N, C = g->C, cm = g->cm, n = sel->n;
-    NDET_REQUIRE(features_nhwc && mapped_nhwc && bias && rgb && projection && rgb_projection, NDET_E_INVALID, "%s: null pointer", fn);
-    NDET_REQUIRE(h > 0 && w > 0 && H > 0 && W > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
-    // K1's inputs (ndet_scene_accumulate)
-    NDET_REQUIRE(row_pitch >= (int64_t)w * C && view_pitch >= (int64_t)h * row_pitch, NDET_E_INVALID, "%s: feature pitches smaller than the map", fn);
-    NDET_REQUIRE(row_pitch % 4 == 0 && view_pitch % 4 == 0 && ((uintptr_t)features_nhwc & 15) == 0, NDET_E_UNSUPPORTED,
-                 "%s: feature rows must be 16-byte aligned", fn);
-    NDET_REQUIRE((int64_t)h * row_pitch < (int64_t)1 << 31, NDET_E_UNSUPPORTED, "%s: one view exceeds 2^31 floats", fn);
-    // K2's inputs: a scene's k views are one packed launch's
-    NDET_REQUIRE(mrow_pitch >= (int64_t)w * cm && mview_pitch >= (int64_t)h * mrow_pitch && rsy >= W && rsc >= 0 && rsv >= 0, NDET_E_INVALID,
-                 "%s: mapped / image pitches smaller than the maps", fn);
-    NDET_REQUIRE((int64_t)k * mview_pitch < ((int64_t)1 << 31) && (int64_t)k * rsv + 3 * rsc < ((int64_t)1 << 31), NDET_E_UNSUPPORTED,
-                 "%s: a scene's source tensor exceeds 2^31 floats", fn);
-    NDET_REQUIRE(mview_pitch % 4 == 0 && mrow_pitch % 4 == 0 && (((uintptr_t)mapped_nhwc | (uintptr_t)bias) & 15) == 0, NDET_E_UNSUPPORTED,
-                 "%s: mapped features / bias must keep channel quads 16-byte aligned", fn);
-    NdetGateMap gf = {}, gr = {};
-    if (gate) {
-        rc = ndet_gate_prepare(gate, fn, n * k, h, w, H, W, true, &gf, &gr);
-        if (rc != NDET_OK) return rc;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int n_tiles = (N + VOX_PER_TILE - 1) / VOX_PER_TILE;
-    const int rp = (int)row_pitch, k1p = (int)g->k1_pitch;
-    const dim3 grid(n_tiles, n);
-#define K1G_LAUNCH(NC, DG)                                                                                                                  \
-    hipLaunchKernelGGL((k_backproject_accumulate_group<NC, DG>), grid, dim3(256), 0, st, g->table, *sel, k, features_nhwc, C, h, w, view_pitch, \
-                       rp, N, projection, k1p, n_tiles, gf)
-#define K1G_CHUNKS(DG)                \
-    if (C <= 256) K1G_LAUNCH(1, DG);  \
-    else if (C <= 512) K1G_LAUNCH(2, DG); \
-    else K1G_LAUNCH(4, DG)
-    if (gate) {
-        K1G_CHUNKS(true);
-    } else {
-        K1G_CHUNKS(false);
-    }
-#undef K1G_CHUNKS
-#undef K1G_LAUNCH
-    NDET_CHECK_LAUNCH(fn);
-    ndet_scene_k2_accumulate_group_launch(g, sel, k, mapped_nhwc, h, w, (int)mview_pitch, (int)mrow_pitch, bias, rgb, H, W, (int)rsv, (int)rsc,
-                                          (int)rsy, projection, rgb_projection, gate != nullptr, gf, gr, st);
-    NDET_CHECK_LAUNCH(fn);
-    return NDET_OK;
-}
-
-extern "C" int ndet_scene_density_finish_group(const NdetSceneGroup* g, const NdetGroupSel* sel, const float* bias, float* global_feat,
-                                               void* stream) {
-    const char* fn = "ndet_scene_density_finish_group";
-    const int rc = group_check(g, sel, 0, fn);
-    if (rc != NDET_OK) return rc;
-    NDET_REQUIRE(bias && global_feat, NDET_E_INVALID, "%s: null pointer", fn);
-    NDET_REQUIRE(((uintptr_t)global_feat & 7) == 0, NDET_E_UNSUPPORTED, "%s: global_feat must be 8-byte aligned", fn);
-    NDET_REQUIRE(((int64_t)g->N * (g->cm + 3) + 255) / 256 < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
-    ndet_scene_k2_finish_group_launch(g, sel, bias, global_feat, (hipStream_t)stream);
-    NDET_CHECK_LAUNCH(fn);
-    return NDET_OK;
-}
-
-extern "C" int ndet_scene_volume_finish_group(const NdetSceneGroup* g, const NdetGroupSel* sel, const float* alpha, float* out, int64_t* count,
-                                              void* stream) {
-    const char* fn = "ndet_scene_volume_finish_group";
-    const int rc = group_check(g, sel, 0, fn);
-    if (rc != NDET_OK) return rc;
-    NDET_REQUIRE(out && count, NDET_E_INVALID, "%s: null pointer", fn);
-    NDET_REQUIRE(((uintptr_t)out & 15) == 0, NDET_E_UNSUPPORTED, "%s: out must be 16-byte aligned", fn);
-    NDET_REQUIRE(((uintptr_t)count & 7) == 0, NDET_E_UNSUPPORTED, "%s: count must be 8-byte aligned", fn);
-    const int64_t blocks = ((int64_t)g->N * (g->C / 4) + 255) / 256;
-    NDET_REQUIRE(blocks < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
-    hipLaunchKernelGGL(k_volume_finish_group, dim3((unsigned)blocks, sel->n), dim3(256), 0, (hipStream_t)stream, g->table, *sel,
-                       (int)g->k1_pitch, alpha, g->C, g->N, out, count);
-    NDET_CHECK_LAUNCH(fn);
-    return NDET_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// Windowed groups (include/nerfdet_hip.h, NdetGroupRingSel): the listed scenes' windows finished by one launch, grid.y = listed scene.
-//
-// k_volume_finish_group_ring is k_volume_finish_ring (its own copy, expression for expression) with the segments found through memory:
-// segs[y][j] is a row of the pool table, the row holds the state's pointers.  That chain is block-uniform, so threads 0 .. n_segs - 1
-// resolve it once into LDS (64 x 16 bytes) and the walk reads its pointers from there after one barrier; the threads past N c4 stay for
-// the barrier and skip the body.  The state pitch is the pool's.  Output row y N + n, alpha indexed the same way.
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_volume_finish_group_ring(const NdetSceneSlot* __restrict__ table, NdetGroupRingSel sel,
-                                                                  const int32_t* __restrict__ segs, int pitch,
-                                                                  const float* __restrict__ alpha, int C, int N, float* __restrict__ out,
-                                                                  int64_t* __restrict__ out_count) {
-    constexpr int U = NDET_RING_BATCH;
-    __shared__ const float* s_sum[NDET_RING_MAX];
-    __shared__ const int* s_count[NDET_RING_MAX];
-    const int y = blockIdx.y;
-    const int n_segs = sel.n_segs[y];
-    if ((int)threadIdx.x < n_segs) {
-        const NdetSceneSlot& sl = table[segs[y * NDET_RING_MAX + threadIdx.x]];
-        s_sum[threadIdx.x] = sl.k1_sum;
-        s_count[threadIdx.x] = sl.k1_count;
-    }
-    __syncthreads();
-    const int c4 = C >> 2;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (int64_t)N * c4) {
-        const int n = (int)(i / c4), q = (int)(i % c4);
-        const int64_t row = (int64_t)y * N + n;
-        int cnt = s_count[0][n];
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (cnt != 0) s = *reinterpret_cast<const float4*>(s_sum[0] + (int64_t)n * pitch + q * 4);
-        for (int s0 = 1; s0 < n_segs; s0 += U) {
-            int cc[U];
-            float4 vv[U];
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                const int sj = min(s0 + j, n_segs - 1);     // past the end: the last segment's slot, not read (cc = 0)
-                cc[j] = (s0 + j < n_segs) ? s_count[sj][n] : 0;
-            }
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                const int sj = min(s0 + j, n_segs - 1);
-                vv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (cc[j] != 0) vv[j] = *reinterpret_cast<const float4*>(s_sum[sj] + (int64_t)n * pitch + q * 4);
-            }
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                s.x = s.x + vv[j].x;
-                s.y = s.y + vv[j].y;
-                s.z = s.z + vv[j].z;
-                s.w = s.w + vv[j].w;
-                cnt += cc[j];
-            }
-        }
-        const float denom = (float)cnt + 1e-8f;
-        float4 mean;
-        mean.x = s.x / denom;
-        mean.y = s.y / denom;
-        mean.z = s.z / denom;
-        mean.w = s.w / denom;
-        if (alpha) {
-            const float a = alpha[row];
-            mean.x = a * mean.x;
-            mean.y = a * mean.y;
-            mean.z = a * mean.z;
-            mean.w = a * mean.w;
-        }
-        if (cnt == 0) mean = make_float4(0.f, 0.f, 0.f, 0.f);
-        *reinterpret_cast<float4*>(out + row * C + q * 4) = mean;
-        if (q == 0) out_count[row] = (int64_t)cnt;
-    }
-}
-
-// The pool's block, checked as group_check checks a group's apart from the bound on n_slots (a pool holds up to NDET_RING_MAX + 1 states
-// per scene).
-static int pool_check(const NdetSceneGroup* g, const char* fn) {
-    NDET_REQUIRE(g, NDET_E_INVALID, "%s: null state pool", fn);
-    NDET_REQUIRE(g->size == (int32_t)sizeof(NdetSceneGroup), NDET_E_INVALID, "%s: NdetSceneGroup.size %d != %d (caller built against another layout)",
-                 fn, g->size, (int)sizeof(NdetSceneGroup));
-    NDET_REQUIRE(g->table, NDET_E_INVALID, "%s: null pool table", fn);
-    NDET_REQUIRE(((uintptr_t)g->table & 15) == 0, NDET_E_UNSUPPORTED, "%s: the pool table must be 16-byte aligned", fn);
-    NDET_REQUIRE(g->n_slots >= 1 && g->n_slots <= NDET_GROUP_POOL_MAX, NDET_E_INVALID, "%s: n_slots=%d must be 1 .. %d", fn, g->n_slots,
-                 NDET_GROUP_POOL_MAX);
-    NDET_REQUIRE(g->N > 0 && g->C > 0 && g->cm > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
-    NDET_REQUIRE(g->C % 4 == 0 && g->C <= 1024, NDET_E_UNSUPPORTED, "%s: C=%d must be a multiple of 4 and <= 1024", fn, g->C);
-    NDET_REQUIRE(g->cm % 4 == 0 && g->cm <= 128, NDET_E_UNSUPPORTED, "%s: cm=%d must be a multiple of 4 and <= 128", fn, g->cm);
-    NDET_REQUIRE(g->k1_pitch >= g->C && g->k2_pitch >= 3 * (g->cm + 4), NDET_E_INVALID, "%s: state pitches smaller than a row", fn);
-    NDET_REQUIRE(g->k1_pitch < ((int64_t)1 << 31) && g->k2_pitch < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: state pitches exceed int32", fn);
-    NDET_REQUIRE(g->k1_pitch % 4 == 0 && g->k2_pitch % 4 == 0, NDET_E_UNSUPPORTED, "%s: state rows must be 16-byte aligned", fn);
-    return NDET_OK;
-}
-
-// The pool, a call's selection and its segment lists (the HOST copy), checked before any launch.
+// A pool's block, a call's selection and its segment lists (the HOST copy).
 static int group_ring_check(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_host, const char* fn) {
-    const int rc = pool_check(pool, fn);
+    const int rc = table_check(pool, fn, "state pool", "pool", NDET_GROUP_POOL_MAX);
     if (rc != NDET_OK) return rc;
     NDET_REQUIRE(sel, NDET_E_INVALID, "%s: null selection", fn);
     NDET_REQUIRE(sel->size == (int32_t)sizeof(NdetGroupRingSel), NDET_E_INVALID,
@@ -1247,6 +927,197 @@ static int group_ring_check(const NdetSceneGroup* pool, const NdetGroupRingSel* 
     return NDET_OK;
 }
 
+// The device copy of a grouped ring finish's segment lists.
+static int segs_dev_check(const int32_t* segs_dev, const char* fn) {
+    NDET_REQUIRE(segs_dev, NDET_E_INVALID, "%s: null segs_dev", fn);
+    NDET_REQUIRE(((uintptr_t)segs_dev & 3) == 0, NDET_E_UNSUPPORTED, "%s: segs_dev must be 4-byte aligned", fn);
+    return NDET_OK;
+}
+
+// A chunk's feature maps (K1's input, as backproject_aggregate_impl checks them), mapped maps and images (K2's, as
+// density_features_packed_impl does); `per` = the most views one K2 launch covers.
+static int accumulate_inputs_check(const char* fn, int C, int cm, int per, int h, int w, const float* features_nhwc, int64_t view_pitch,
+                                   int64_t row_pitch, const float* mapped_nhwc, int64_t mview_pitch, int64_t mrow_pitch, const float* bias,
+                                   int W, int64_t rsv, int64_t rsc, int64_t rsy) {
+    NDET_REQUIRE(row_pitch >= (int64_t)w * C && view_pitch >= (int64_t)h * row_pitch, NDET_E_INVALID, "%s: feature pitches smaller than the map", fn);
+    NDET_REQUIRE(row_pitch % 4 == 0 && view_pitch % 4 == 0 && ((uintptr_t)features_nhwc & 15) == 0, NDET_E_UNSUPPORTED,
+                 "%s: feature rows must be 16-byte aligned", fn);
+    NDET_REQUIRE((int64_t)h * row_pitch < (int64_t)1 << 31, NDET_E_UNSUPPORTED, "%s: one view exceeds 2^31 floats", fn);
+    NDET_REQUIRE(mrow_pitch >= (int64_t)w * cm && mview_pitch >= (int64_t)h * mrow_pitch && rsy >= W && rsc >= 0 && rsv >= 0, NDET_E_INVALID,
+                 "%s: mapped / image pitches smaller than the maps", fn);
+    NDET_REQUIRE((int64_t)per * mview_pitch < ((int64_t)1 << 31) && (int64_t)per * rsv + 3 * rsc < ((int64_t)1 << 31), NDET_E_UNSUPPORTED,
+                 "%s: a launch's source tensor exceeds 2^31 floats", fn);
+    NDET_REQUIRE(mview_pitch % 4 == 0 && mrow_pitch % 4 == 0 && (((uintptr_t)mapped_nhwc | (uintptr_t)bias) & 15) == 0, NDET_E_UNSUPPORTED,
+                 "%s: mapped features / bias must keep channel quads 16-byte aligned", fn);
+    return NDET_OK;
+}
+
+// A finish's outputs: `name` = "global_feat" (8-byte rows, no count) or "out" (16-byte rows, and the int64 count); `threads` = the
+// launch's threads per listed scene.
+static int finish_out_check(const char* fn, const char* name, const void* out, int align, bool counted, const int64_t* count,
+                            int64_t threads) {
+    NDET_REQUIRE(out, NDET_E_INVALID, "%s: null %s", fn, name);
+    if (counted) NDET_REQUIRE(count, NDET_E_INVALID, "%s: null count", fn);
+    NDET_REQUIRE(((uintptr_t)out & (align - 1)) == 0, NDET_E_UNSUPPORTED, "%s: %s must be %d-byte aligned", fn, name, align);
+    if (counted) NDET_REQUIRE(((uintptr_t)count & 7) == 0, NDET_E_UNSUPPORTED, "%s: count must be 8-byte aligned", fn);
+    NDET_REQUIRE((threads + 255) / 256 < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
+    return NDET_OK;
+}
+
+// launch(integral_constant NCHUNK, true_type / false_type DG) for the accumulate kernels' instantiation at C channels
+template <class F>
+static void k1_accumulate_dispatch(int C, bool gated, F&& launch) {
+    ndet_by_flag(gated, [&](auto dg) {
+        if (C <= 256) launch(std::integral_constant<int, 1>{}, dg);
+        else if (C <= 512) launch(std::integral_constant<int, 2>{}, dg);
+        else launch(std::integral_constant<int, 4>{}, dg);
+    });
+}
+
+// ---- entry points: one state ----
+extern "C" int ndet_scene_accumulate(const NdetSceneAccum* s, const float* features_nhwc, int n_views, int h, int w,
+                                     int64_t view_pitch, int64_t row_pitch, const float* mapped_nhwc, int64_t mview_pitch,
+                                     int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv, int64_t rsc,
+                                     int64_t rsy, const float* points, const float* projection, const float* rgb_projection,
+                                     const NdetDepthGate* gate, void* stream) {
+    const char* fn = "ndet_scene_accumulate";
+    NDET_TRY(scene_check(s, fn));
+    const int N = s->N, C = s->C;
+    NDET_REQUIRE(features_nhwc && mapped_nhwc && bias && rgb && points && projection && rgb_projection, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(n_views > 0 && h > 0 && w > 0 && H > 0 && W > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
+    NDET_REQUIRE(s->n_views <= 0x7fffffff - n_views, NDET_E_UNSUPPORTED, "%s: view count overflows int32", fn);
+    NDET_TRY(accumulate_inputs_check(fn, C, s->cm, n_views < 128 ? n_views : 128, h, w, features_nhwc, view_pitch, row_pitch, mapped_nhwc,
+                                     mview_pitch, mrow_pitch, bias, W, rsv, rsc, rsy));
+    NdetGateMap gf = {}, gr = {};
+    if (gate) NDET_TRY(ndet_gate_prepare(gate, fn, n_views, h, w, H, W, true, &gf, &gr));
+    hipStream_t st = (hipStream_t)stream;
+    const int n_tiles = (N + VOX_PER_TILE - 1) / VOX_PER_TILE;
+    k1_accumulate_dispatch(C, gate != nullptr, [&](auto nc, auto dg) {
+        hipLaunchKernelGGL((k_backproject_accumulate<decltype(nc)::value, decltype(dg)::value>), dim3(n_tiles), dim3(256), 0, st, features_nhwc,
+                           n_views, C, h, w, view_pitch, (int)row_pitch, points, N, projection, s->k1_sum, (int)s->k1_pitch, s->k1_count, n_tiles, gf);
+    });
+    NDET_CHECK_LAUNCH(fn);
+    for (int v0 = 0; v0 < n_views; v0 += 128) {   // K2: launches of at most 128 views
+        const int nv = n_views - v0 < 128 ? n_views - v0 : 128;
+        ndet_scene_k2_accumulate_launch(s, mapped_nhwc + (int64_t)v0 * mview_pitch, nv, h, w, (int)mview_pitch, (int)mrow_pitch, bias,
+                                        rgb + (int64_t)v0 * rsv, H, W, (int)rsv, (int)rsc, (int)rsy, points, projection + (int64_t)v0 * 12,
+                                        rgb_projection + (int64_t)v0 * 12, gate != nullptr, gate ? ndet_gate_from_view(gf, v0) : gf,
+                                        gate ? ndet_gate_from_view(gr, v0) : gr, st);
+        NDET_CHECK_LAUNCH(fn);
+    }
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_density_finish(const NdetSceneAccum* s, const float* bias, float* global_feat, void* stream) {
+    const char* fn = "ndet_scene_density_finish";
+    NDET_TRY(scene_check(s, fn));
+    NDET_REQUIRE(bias, NDET_E_INVALID, "%s: null bias", fn);
+    NDET_TRY(finish_out_check(fn, "global_feat", global_feat, 8, false, nullptr, (int64_t)s->N * (s->cm + 3)));
+    ndet_scene_k2_finish_launch(s, bias, global_feat, (hipStream_t)stream);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_volume_finish(const NdetSceneAccum* s, const float* alpha, float* out, int64_t* count, void* stream) {
+    const char* fn = "ndet_scene_volume_finish";
+    NDET_TRY(scene_check(s, fn));
+    const int64_t threads = (int64_t)s->N * (s->C / 4);
+    NDET_TRY(finish_out_check(fn, "out", out, 16, true, count, threads));
+    hipLaunchKernelGGL(k_volume_finish, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s->k1_sum, (int)s->k1_pitch,
+                       s->k1_count, alpha, s->C, s->N, out, count);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+// ---- entry points: a ring of states ----
+extern "C" int ndet_scene_density_finish_ring(const NdetSceneAccum* segs, int n_segs, const float* bias, float* global_feat, void* stream) {
+    const char* fn = "ndet_scene_density_finish_ring";
+    int n_views = 0;
+    NDET_TRY(ring_check(segs, n_segs, fn, &n_views));
+    NDET_REQUIRE(bias, NDET_E_INVALID, "%s: null bias", fn);
+    NDET_TRY(finish_out_check(fn, "global_feat", global_feat, 8, false, nullptr, (int64_t)segs[0].N * (segs[0].cm / 4 + 1)));
+    ndet_scene_k2_finish_ring_launch(segs, n_segs, n_views, bias, global_feat, (hipStream_t)stream);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_volume_finish_ring(const NdetSceneAccum* segs, int n_segs, const float* alpha, float* out, int64_t* count,
+                                             void* stream) {
+    const char* fn = "ndet_scene_volume_finish_ring";
+    int n_views = 0;
+    NDET_TRY(ring_check(segs, n_segs, fn, &n_views));
+    const int64_t threads = (int64_t)segs[0].N * (segs[0].C / 4);
+    NDET_TRY(finish_out_check(fn, "out", out, 16, true, count, threads));
+    NdetRingArgs r = {};
+    for (int i = 0; i < n_segs; ++i) {
+        r.sum[i] = segs[i].k1_sum;
+        r.count[i] = segs[i].k1_count;
+        r.pitch[i] = (int)segs[i].k1_pitch;
+    }
+    hipLaunchKernelGGL(k_volume_finish_ring, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, r, n_segs, alpha,
+                       segs[0].C, segs[0].N, out, count);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+// ---- entry points: scene groups ----
+extern "C" int ndet_scene_group_check(const NdetSceneGroup* g, const NdetGroupSel* sel, int k) {
+    return group_check(g, sel, k, "ndet_scene_group_check");
+}
+
+extern "C" int ndet_scene_accumulate_group(const NdetSceneGroup* g, const NdetGroupSel* sel, int k, const float* features_nhwc, int h, int w,
+                                           int64_t view_pitch, int64_t row_pitch, const float* mapped_nhwc, int64_t mview_pitch,
+                                           int64_t mrow_pitch, const float* bias, const float* rgb, int H, int W, int64_t rsv, int64_t rsc,
+                                           int64_t rsy, const float* projection, const float* rgb_projection, const NdetDepthGate* gate,
+                                           void* stream) {
+    const char* fn = "ndet_scene_accumulate_group";
+    NDET_REQUIRE(k >= 1 && k <= 128, NDET_E_UNSUPPORTED, "%s: k=%d views per scene, must be 1 .. 128", fn, k);
+    NDET_TRY(group_check(g, sel, k, fn));
+    const int N = g->N, C = g->C, n = sel->n;
+    NDET_REQUIRE(features_nhwc && mapped_nhwc && bias && rgb && projection && rgb_projection, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(h > 0 && w > 0 && H > 0 && W > 0, NDET_E_INVALID, "%s: sizes must be positive", fn);
+    // a scene's k views are one packed K2 launch's
+    NDET_TRY(accumulate_inputs_check(fn, C, g->cm, k, h, w, features_nhwc, view_pitch, row_pitch, mapped_nhwc, mview_pitch, mrow_pitch, bias, W,
+                                     rsv, rsc, rsy));
+    NdetGateMap gf = {}, gr = {};
+    if (gate) NDET_TRY(ndet_gate_prepare(gate, fn, n * k, h, w, H, W, true, &gf, &gr));
+    hipStream_t st = (hipStream_t)stream;
+    const int n_tiles = (N + VOX_PER_TILE - 1) / VOX_PER_TILE;
+    k1_accumulate_dispatch(C, gate != nullptr, [&](auto nc, auto dg) {
+        hipLaunchKernelGGL((k_backproject_accumulate_group<decltype(nc)::value, decltype(dg)::value>), dim3(n_tiles, n), dim3(256), 0, st, g->table,
+                           *sel, k, features_nhwc, C, h, w, view_pitch, (int)row_pitch, N, projection, (int)g->k1_pitch, n_tiles, gf);
+    });
+    NDET_CHECK_LAUNCH(fn);
+    ndet_scene_k2_accumulate_group_launch(g, sel, k, mapped_nhwc, h, w, (int)mview_pitch, (int)mrow_pitch, bias, rgb, H, W, (int)rsv, (int)rsc,
+                                          (int)rsy, projection, rgb_projection, gate != nullptr, gf, gr, st);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_density_finish_group(const NdetSceneGroup* g, const NdetGroupSel* sel, const float* bias, float* global_feat,
+                                               void* stream) {
+    const char* fn = "ndet_scene_density_finish_group";
+    NDET_TRY(group_check(g, sel, 0, fn));
+    NDET_REQUIRE(bias, NDET_E_INVALID, "%s: null bias", fn);
+    NDET_TRY(finish_out_check(fn, "global_feat", global_feat, 8, false, nullptr, (int64_t)g->N * (g->cm + 3)));
+    ndet_scene_k2_finish_group_launch(g, sel, bias, global_feat, (hipStream_t)stream);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+extern "C" int ndet_scene_volume_finish_group(const NdetSceneGroup* g, const NdetGroupSel* sel, const float* alpha, float* out, int64_t* count,
+                                              void* stream) {
+    const char* fn = "ndet_scene_volume_finish_group";
+    NDET_TRY(group_check(g, sel, 0, fn));
+    const int64_t threads = (int64_t)g->N * (g->C / 4);
+    NDET_TRY(finish_out_check(fn, "out", out, 16, true, count, threads));
+    hipLaunchKernelGGL(k_volume_finish_group, dim3((unsigned)((threads + 255) / 256), sel->n), dim3(256), 0, (hipStream_t)stream, g->table, *sel,
+                       (int)g->k1_pitch, alpha, g->C, g->N, out, count);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+// ---- entry points: windowed groups ----
 extern "C" int ndet_scene_group_ring_check(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_host) {
     return group_ring_check(pool, sel, segs_host, "ndet_scene_group_ring_check");
 }
@@ -1254,14 +1125,10 @@ extern "C" int ndet_scene_group_ring_check(const NdetSceneGroup* pool, const Nde
 extern "C" int ndet_scene_density_finish_group_ring(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_host,
                                                     const int32_t* segs_dev, const float* bias, float* global_feat, void* stream) {
     const char* fn = "ndet_scene_density_finish_group_ring";
-    const int rc = group_ring_check(pool, sel, segs_host, fn);
-    if (rc != NDET_OK) return rc;
-    NDET_REQUIRE(segs_dev, NDET_E_INVALID, "%s: null segs_dev", fn);
-    NDET_REQUIRE(((uintptr_t)segs_dev & 3) == 0, NDET_E_UNSUPPORTED, "%s: segs_dev must be 4-byte aligned", fn);
+    NDET_TRY(group_ring_check(pool, sel, segs_host, fn));
+    NDET_TRY(segs_dev_check(segs_dev, fn));
     NDET_REQUIRE(bias, NDET_E_INVALID, "%s: null bias", fn);
-    NDET_REQUIRE(global_feat, NDET_E_INVALID, "%s: null global_feat", fn);
-    NDET_REQUIRE(((uintptr_t)global_feat & 7) == 0, NDET_E_UNSUPPORTED, "%s: global_feat must be 8-byte aligned", fn);
-    NDET_REQUIRE(((int64_t)pool->N * (pool->cm / 4 + 1) + 255) / 256 < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
+    NDET_TRY(finish_out_check(fn, "global_feat", global_feat, 8, false, nullptr, (int64_t)pool->N * (pool->cm / 4 + 1)));
     ndet_scene_k2_finish_group_ring_launch(pool, sel, segs_dev, bias, global_feat, (hipStream_t)stream);
     NDET_CHECK_LAUNCH(fn);
     return NDET_OK;
@@ -1270,18 +1137,12 @@ extern "C" int ndet_scene_density_finish_group_ring(const NdetSceneGroup* pool, 
 extern "C" int ndet_scene_volume_finish_group_ring(const NdetSceneGroup* pool, const NdetGroupRingSel* sel, const int32_t* segs_host,
                                                    const int32_t* segs_dev, const float* alpha, float* out, int64_t* count, void* stream) {
     const char* fn = "ndet_scene_volume_finish_group_ring";
-    const int rc = group_ring_check(pool, sel, segs_host, fn);
-    if (rc != NDET_OK) return rc;
-    NDET_REQUIRE(segs_dev, NDET_E_INVALID, "%s: null segs_dev", fn);
-    NDET_REQUIRE(((uintptr_t)segs_dev & 3) == 0, NDET_E_UNSUPPORTED, "%s: segs_dev must be 4-byte aligned", fn);
-    NDET_REQUIRE(out, NDET_E_INVALID, "%s: null out", fn);
-    NDET_REQUIRE(count, NDET_E_INVALID, "%s: null count", fn);
-    NDET_REQUIRE(((uintptr_t)out & 15) == 0, NDET_E_UNSUPPORTED, "%s: out must be 16-byte aligned", fn);
-    NDET_REQUIRE(((uintptr_t)count & 7) == 0, NDET_E_UNSUPPORTED, "%s: count must be 8-byte aligned", fn);
-    const int64_t blocks = ((int64_t)pool->N * (pool->C / 4) + 255) / 256;
-    NDET_REQUIRE(blocks < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many voxels", fn);
-    hipLaunchKernelGGL(k_volume_finish_group_ring, dim3((unsigned)blocks, sel->n), dim3(256), 0, (hipStream_t)stream, pool->table, *sel, segs_dev,
-                       (int)pool->k1_pitch, alpha, pool->C, pool->N, out, count);
+    NDET_TRY(group_ring_check(pool, sel, segs_host, fn));
+    NDET_TRY(segs_dev_check(segs_dev, fn));
+    const int64_t threads = (int64_t)pool->N * (pool->C / 4);
+    NDET_TRY(finish_out_check(fn, "out", out, 16, true, count, threads));
+    hipLaunchKernelGGL(k_volume_finish_group_ring, dim3((unsigned)((threads + 255) / 256), sel->n), dim3(256), 0, (hipStream_t)stream, pool->table,
+                       *sel, segs_dev, (int)pool->k1_pitch, alpha, pool->C, pool->N, out, count);
     NDET_CHECK_LAUNCH(fn);
     return NDET_OK;
 }

@@ -11,6 +11,7 @@ pytestmark = pytest.mark.gpu
 
 ORIGINS = [(-0.4, 0.0, 0.5), (0.0, 0.3, 0.6), (0.4, 0.6, 0.7)]        # every scene sees part of its grid only (checked below)
 FAR_ORIGINS = [(0.4, 0.6, 0.7), (-0.6, 0.5, 0.8)]                      # the same for the 70-view ring at 32 x 48
+SIDE_ORIGINS = [(1.2, 0.0, 1.5), (-1.2, 0.0, 0.5)]                     # a 3 x 3 x 2 grid beside a 24 x 32 ring: 3 views see part of it
 TENSORS = ("k1_sum", "k1_count", "k2_sum", "k2_count")
 
 
@@ -133,6 +134,54 @@ def test_group_accumulate_two_view_rounds(device):
     for s, ref in enumerate(refs):
         seen = int((ref.k1_count != 0).sum())
         assert 0 < seen < ref.n_voxels and int(ref.k1_count.max()) > 64, f"scene {s}: {seen} voxels seen, at most {int(ref.k1_count.max())} views"
+
+
+@pytest.mark.parametrize("gated", [False, True])
+def test_four_channel_chunks(device, gated):
+    """C = 516 takes the accumulate kernels' NCHUNK = 4 (C > 512): c4 = 129 is the first quad of the third 64-lane chunk, so the ``ci < c4``
+    guard cuts inside a chunk.  N = 18: one full 16-voxel K1 tile and one with 2 live voxels.  Two scenes, 3 views each as chunks of 2 and
+    1: the single states against one launch over the 3 views, the group's states against the single states, and the four volume finishes
+    against each other over one-segment rings."""
+    from nerfdet_amd import ops
+    ds = _scenes(device, 3, SIDE_ORIGINS, seed0=51, hw=(24, 32), grid=(3, 3, 2), c=516)
+    d0 = ds[0]
+    assert d0["feats"].shape[1:] == (516, 6, 8)
+    group, refs = _new_group(ds), _new_refs(ds)
+    _feed(group, refs, ds, None, 0, 2, gated)
+    _feed(group, refs, ds, None, 2, 3, gated)
+    _assert_states(group, refs, "chunks of 2 and 1")
+    # a windowed pool holding each scene's 3 views as one chunk: K1's sums do not depend on the chunking, so its states are one-segment
+    # rings over the same sums
+    pool = ops.SceneGroupRingState(d0["grid"], 516, d0["mapped"].shape[1], [d["points"] for d in ds], 2, device)
+    cat = lambda key: torch.cat([_views(d, key, 0, 3) for d in ds])
+    ops.scene_accumulate_group_ring(pool, None, cat("feats"), cat("mapped"), d0["bias"], cat("rgb"), cat("proj"), cat("rgb_proj"),
+                                    depth_gate=ops.depth_gate(cat("depth"), d0["vs"], (d0["h"], d0["w"]), d0["hw"]) if gated else None)
+    assert pool.n_chunks == [1, 1]
+    n_vox = refs[0].n_voxels
+    assert n_vox == 18
+    for alpha in (None, torch.rand(2 * n_vox, generator=torch.Generator().manual_seed(3)).to(device)):
+        group_mean, group_cnt = ops.volume_finish_group(group, alpha)
+        pool_mean, pool_cnt = ops.volume_finish_group_ring(pool, alpha)
+        for s, (d, ref) in enumerate(zip(ds, refs)):
+            a = None if alpha is None else alpha[s * n_vox:(s + 1) * n_vox]
+            seg, = pool.segs[s]
+            assert torch.equal(seg.k1_sum, ref.k1_sum) and torch.equal(seg.k1_count, ref.k1_count), f"scene {s}: one chunk of 3 against 2 + 1"
+            want_mean, want_cnt = ops.backproject_aggregate(_views(d, "feats", 0, 3), d["points"], _views(d, "proj", 0, 3), alpha=a,
+                                                            depth_gate=_gate(d, d["shift"], d["shift"] + 3, gated))
+            mean, cnt = ops.volume_finish(ref, a)
+            assert torch.equal(cnt, want_cnt) and torch.equal(mean, want_mean), f"scene {s}: K1 sums differ from one launch over the 3 views"
+            ring_mean, ring_cnt = ops.volume_finish_ring([ref], a)
+            assert torch.equal(ring_mean, mean) and torch.equal(ring_cnt, cnt), f"scene {s}: ring of one state"
+            assert torch.equal(group_mean[s], mean) and torch.equal(group_cnt[s], cnt), f"scene {s}: group finish"
+            assert torch.equal(pool_mean[s], mean) and torch.equal(pool_cnt[s], cnt), f"scene {s}: group ring finish"
+    for s, ref in enumerate(refs):
+        seen = int((ref.k1_count != 0).sum())
+        assert 0 < seen < n_vox, f"scene {s}: {seen} of {n_vox} voxels seen -- the case needs seen and unseen voxels"
+    assert int(refs[1].k1_count[16:].min()) > 0, "no view sees the 2 voxels of the ragged tile"
+    if gated:
+        ungated = _new_refs(ds)
+        _feed(_new_group(ds), ungated, ds, None, 0, 3, False)
+        assert all(int(a.k1_count.sum()) < int(b.k1_count.sum()) for a, b in zip(refs, ungated)), "the gate dropped nothing"
 
 
 def test_group_ops_refuse_bad_calls(device):
