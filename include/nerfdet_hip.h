@@ -838,6 +838,38 @@ int ndet_depth_frames(const uint16_t* frames_mm, const int* ids, int n_sel, int 
  * null pointer, n <= 0, a misaligned workspace (NDET_E_INVALID); n >= 2^31 (NDET_E_UNSUPPORTED). */
 int ndet_positive_indices(const double* x, int64_t n, int64_t* indices, int64_t* count, void* workspace, void* stream);
 
+/* ---- frames out: a pose in, uint8 BGR and uint16 millimetre frames out, and a render compared with a held-out frame on the device.
+ * Every entry point checks its arguments on the host before any HIP call: a null pointer (other than the optional ones named below) or
+ * a non-positive size is NDET_E_INVALID, 2^31 elements or more and a misaligned pointer are NDET_E_UNSUPPORTED.
+ *
+ * ndet_camera_rays: get_dtu_raydir (mmdet3d/datasets/pipelines/data_augment_utils.py:410-424, un-normalised, as multi_view.py:117-155
+ * calls it) for n_cams cameras that share intrinsic_rows, a device (2,3) array (rows 0,1 of the intrinsics at the image grid's scale),
+ * with camrotc2w (n_cams,3,3) and cam_lightpos (n_cams,3) on the device.  Output pixel (i, j) of camera c looks through image pixel
+ * px = x0 + j * stride, py = y0 + i * stride: x = ((float)px + 0.5f - k[2]) / k[0], y = ((float)py + 0.5f - k[5]) / k[4],
+ * ray_d[c][i * w + j][r] = fmaf(y, R[r][1], x * R[r][0]) + R[r][2] -- ndet_target_rays' arithmetic in its operation order, bit for bit --
+ * and ray_o the camera centre repeated (formating.py:70-75); both (n_cams, h * w, 3) float32.  No frame and no image bound: a pose may
+ * look anywhere.  stride >= 1, x0, y0 >= 0, n_cams, h, w >= 1 (else NDET_E_INVALID); n_cams * h * w * 3 >= 2^31 or a pixel coordinate
+ * of 2^31 or more: NDET_E_UNSUPPORTED. */
+int ndet_camera_rays(const float* intrinsic_rows, const float* camrotc2w, const float* cam_lightpos, int n_cams, int x0, int y0, int stride,
+                     int h, int w, float* ray_o, float* ray_d, void* stream);
+
+/* ndet_pack_frames: a render as the formats the input side takes (the reference writes np.uint8(img * 255.0),
+ * mmdet3d/models/model_utils/save_rendered_img.py:68).  rgb (R,3) float32, depth (R) float32 metres, mask (R) bool or NULL (all true) ->
+ * bgr_u8 (R,3) uint8, depth_mm (R) uint16.  Byte, in float32: v = x * 255.0f; NaN and v < 0 give 0, v > 255 gives 255, else
+ * (uint8)(int)(v + 0.5f).  The channel order is kept: composited from a view bank the three columns are B, G, R already.  Depth:
+ * d = depth * 1000.0f; NaN and d < 0 give 0, d > 65535 gives 65535, else (uint16)(int)(d + 0.5f); 0 where mask is false -- a depth of 0
+ * is a hole, as in the sensor's frames.  R * 3 >= 2^31: NDET_E_UNSUPPORTED. */
+int ndet_pack_frames(const float* rgb, const float* depth, const uint8_t* mask, int64_t R, uint8_t* bgr_u8, uint16_t* depth_mm, void* stream);
+
+/* ndet_frame_errors: frames a against frames b, as integer sums per frame (the reference's compute_psnr and depth error,
+ * mmdet3d/models/model_utils/save_rendered_img.py:10-19,55, on the bytes).  a, b (n, px, 3) uint8; da, db (n, px) uint16 millimetres, db may
+ * be NULL; out (n,4) int64 on the device: sse = sum (a - b)^2 over the three bytes of every pixel with da != 0; n_px, the number of those
+ * pixels; sad_mm = sum |da - db| over the pixels with da != 0 && db != 0; n_depth, their number (both 0 without db).  A memset node in
+ * front of the launch zeroes out; a wave reduction and one 64-bit vector atomic add per workgroup and sum follow -- integers, so exact and the
+ * same bytes in any order.  n * px * 3 >= 2^31: NDET_E_UNSUPPORTED. */
+int ndet_frame_errors(const uint8_t* a, const uint8_t* b, const uint16_t* da, const uint16_t* db, int n, int64_t px, int64_t* out,
+                      void* stream);
+
 /* Workspace of ndet_positive_indices for n elements (render_ray.py:386-404), in bytes; 0 for an n the entry point refuses. */
 int64_t ndet_positive_indices_workspace_bytes(int64_t n);
 

@@ -166,6 +166,9 @@ SIGNATURES = {
     "ndet_depth_frames": ([_P, _P] + [c_int] * 6 + [_P, _P], c_int),
     "ndet_positive_indices": ([_P, c_int64, _P, _P, _P, _P], c_int),
     "ndet_positive_indices_workspace_bytes": ([c_int64], c_int64),
+    "ndet_camera_rays": ([_P, _P, _P] + [c_int] * 6 + [_P, _P, _P], c_int),
+    "ndet_pack_frames": ([_P, _P, _P, c_int64, _P, _P, _P], c_int),
+    "ndet_frame_errors": ([_P, _P, _P, _P, c_int, c_int64, _P, _P], c_int),
     "ndet_stem_pack_weights": ([_P, _P, _P], c_int),
     "ndet_stem_conv_bn_relu_maxpool": ([_P, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, _P, c_float, _P, _P, _P, _P, _P], c_int),
     "ndet_stem_pack_weights_f16x2": ([_P, c_float, _P, _P], c_int),

@@ -13,6 +13,11 @@ config:134), or at CAPTURE resolution: :func:`prepare_frames` / ``MultiViewPipel
 The sensor's depth frames (uint16 millimetres on the device) go the same way: :func:`prepare_depth_frames` is the loader's
 ``imresize_linear(frame / 1000, ...)`` in float64 (ndet_depth_frames), :func:`positive_indices` its ``flatnonzero(gt_depths > 0)``
 (ndet_positive_indices), and ``MultiViewPipeline(...)(..., depth_frames=)`` adds ``depth``, ``gt_depths`` and ``depth_rays`` to the batch.
+
+The output side speaks the same formats: :func:`camera_rays` makes the rays of any camera pose without a frame (ndet_camera_rays:
+ndet_target_rays' arithmetic), :func:`pack_frames` turns a render into uint8 BGR and uint16 millimetre frames (ndet_pack_frames), and
+:func:`frame_errors` compares two such frames on the device with exact integer sums (ndet_frame_errors) -- what
+``SceneStream / SceneGroup.render_frames`` and ``score_frames`` stand on.
 """
 from __future__ import annotations
 
@@ -167,6 +172,134 @@ def positive_indices(x: torch.Tensor) -> torch.Tensor:
     if k < 0:
         raise _lib.NdetError("positive_indices: a wait inside the scan ran out of polls")
     return idx[:k]
+
+
+def check_window(window, stride) -> tuple:
+    """``(y0, x0, h, w), stride`` of a ray grid as ints: offsets >= 0, an h x w output of at least one pixel, stride >= 1; else ValueError."""
+    ok = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    if not ok(stride) or stride < 1:
+        raise ValueError(f"stride={stride!r} must be an int of at least 1")
+    if not isinstance(window, (tuple, list)) or len(window) != 4 or not all(ok(v) for v in window):
+        raise ValueError(f"window={window!r} must be (y0, x0, h, w), four ints")
+    y0, x0, h, w = (int(v) for v in window)
+    if y0 < 0 or x0 < 0 or h < 1 or w < 1:
+        raise ValueError(f"window {(y0, x0, h, w)} is empty or starts before pixel 0")
+    return (y0, x0, h, w), int(stride)
+
+
+def _host_matrices(mats, what: str) -> np.ndarray:
+    """``n >= 1`` matrices of 4 x 4 (a list of numpy arrays or tensors, or one (n,4,4) array or tensor) as one float64-exact numpy array."""
+    if isinstance(mats, torch.Tensor):
+        mats = mats.detach().cpu().numpy()
+    elif not isinstance(mats, np.ndarray):
+        mats = [m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m) for m in mats]
+        if not mats or any(m.shape != (4, 4) for m in mats):
+            raise ValueError(f"{what} must hold at least one 4 x 4 matrix")
+        mats = np.stack(mats)
+    if mats.ndim != 3 or mats.shape[0] < 1 or mats.shape[1:] != (4, 4):
+        raise ValueError(f"{what} must be n >= 1 matrices of 4 x 4, got {mats.shape}")
+    return mats
+
+
+def camera_rays(intrinsic, c2w, window, stride: int = 1, device=None):
+    """The rays of n camera poses that need no frame: ``(ray_o, ray_d)``, each (n, h * w, 3) float32 on the device, from one launch
+    (ndet_camera_rays).  ``intrinsic``: the 3 x 3 or 4 x 4 intrinsics already scaled to the image grid; ``c2w``: n camera-to-world matrices
+    of 4 x 4, numpy or tensors, as in ``scene_cameras(info)["c2w"]``; ``window = (y0, x0, h, w)``: output pixel (i, j) looks through image
+    pixel ``(y0 + i * stride, x0 + j * stride)`` -- the image has no bound here, a pose may look anywhere.  ``ray_d`` is ``get_dtu_raydir``
+    in ndet_target_rays' float32 operation order (bit for bit its ``raydirs`` for the same pixels), ``ray_o`` the camera centre repeated.
+    ``device``: the GPU to work on (default: the current one).  ValueError for wrong shapes, RuntimeError without a GPU (no CPU fallback)."""
+    (y0, x0, h, w), stride = check_window(window, stride)
+    k = intrinsic.detach().cpu().numpy() if isinstance(intrinsic, torch.Tensor) else np.asarray(intrinsic)
+    if k.shape not in ((3, 3), (4, 4)):
+        raise ValueError(f"camera_rays takes 3 x 3 or 4 x 4 intrinsics, got {k.shape}")
+    m = _host_matrices(c2w, "camera_rays: c2w").astype(np.float32)
+    n = m.shape[0]
+    if n * h * w * 3 >= 2 ** 31:
+        raise ValueError(f"camera_rays: {n} cameras of {h} x {w} rays hold 2^31 elements or more")
+    if device is None and isinstance(c2w, torch.Tensor) and c2w.is_cuda:
+        device = c2w.device
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("nerfdet_amd.pipeline: camera rays are made on the GPU (no CPU fallback)")
+    # one upload: 6 intrinsic floats, then the n rotations, then the n centres
+    host = np.concatenate([np.ascontiguousarray(k[:2, :3], dtype=np.float32).reshape(-1), m[:, :3, :3].reshape(-1), m[:, :3, 3].reshape(-1)])
+    buf = torch.from_numpy(host).to(dev)
+    ray_o = torch.empty((n, h * w, 3), dtype=torch.float32, device=dev)
+    ray_d = torch.empty_like(ray_o)
+    check(_lib.load().ndet_camera_rays(_ptr(buf), _ptr(buf[6:]), _ptr(buf[6 + 9 * n:]), n, x0, y0, stride, h, w, _ptr(ray_o), _ptr(ray_d),
+                                       c_void_p(_lib.raw_stream(dev))), "camera_rays")
+    return ray_o, ray_d
+
+
+def pack_frames(rgb: torch.Tensor, depth: torch.Tensor, mask, shape):
+    """A render as the formats ``add_frames`` takes: ``(frames (n,h,w,3) uint8, depth_frames (n,h,w) uint16 millimetres)`` from one launch
+    (ndet_pack_frames).  ``rgb`` float32 with ``n * h * w`` rows of 3, ``depth`` float32 metres and ``mask`` bool (or None: all true) with
+    as many elements, ``shape = (n, h, w)``.  Bytes are ``x * 255`` rounded half up and saturated (NaN: 0), in the channel order given --
+    a view bank's images are BGR planes, so a render from one is BGR already; millimetres are ``depth * 1000`` rounded half up, saturated at
+    65535, and 0 -- the sensor's hole -- where ``mask`` is false.  ValueError for wrong shapes or dtypes, RuntimeError for CPU tensors."""
+    if len(tuple(shape)) != 3 or min(int(v) for v in shape) < 1:
+        raise ValueError(f"pack_frames: shape {tuple(shape)} must be (n, h, w), all positive")
+    n, h, w = (int(v) for v in shape)
+    rows = n * h * w
+    for t, name, dtype, numel in ((rgb, "rgb", torch.float32, rows * 3), (depth, "depth", torch.float32, rows), (mask, "mask", torch.bool, rows)):
+        if t is None and name == "mask":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != numel or not t.is_contiguous():
+            got = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"pack_frames takes {name} as a contiguous {dtype} tensor of {numel} elements for frames {(n, h, w)}, got {got}")
+    if rgb.shape[-1] != 3:
+        raise ValueError(f"pack_frames takes rgb as rows of 3, got {tuple(rgb.shape)}")
+    if rows * 3 >= 2 ** 31:
+        raise ValueError(f"pack_frames: {rows} pixels, 2^31 colour elements or more")
+    if not rgb.is_cuda or depth.device != rgb.device or (mask is not None and mask.device != rgb.device):
+        raise RuntimeError("nerfdet_amd.pipeline: renders must live on the GPU (no CPU fallback)")
+    dev = rgb.device
+    frames = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    depth_frames = torch.empty((n, h, w), dtype=torch.uint16, device=dev)
+    check(_lib.load().ndet_pack_frames(_ptr(rgb), _ptr(depth), _ptr(mask), rows, _ptr(frames), _ptr(depth_frames), c_void_p(_lib.raw_stream(dev))),
+          "pack_frames")
+    return frames, depth_frames
+
+
+def frame_errors(frames_a: torch.Tensor, frames_b: torch.Tensor, depth_a: torch.Tensor, depth_b=None) -> dict:
+    """Frames a (a render) against frames b (held-out camera frames) on the device: ``frames_*`` (n, h, w, 3) uint8, ``depth_*`` (n, h, w)
+    uint16 millimetres, ``depth_b`` optional.  One launch behind a memset node (ndet_frame_errors) gives, per frame and as (n,) int64
+    device tensors, ``sse`` = sum (a - b)^2 over the bytes of the pixels where a has depth (``depth_a != 0``), ``n_px`` their number,
+    ``depth_sad_mm`` = sum |depth_a - depth_b| over the pixels where both have depth and ``n_depth`` their number (both 0 without
+    ``depth_b``) -- integer sums, the same bytes on every call -- and ``psnr`` (n,) float64 = 10 log10(255^2 * 3 * n_px / sse), by torch on
+    the device: inf where ``sse == 0``, nan where ``n_px == 0``.  ValueError for wrong shapes or dtypes, RuntimeError for CPU tensors."""
+    a, b = frames_a, frames_b
+    if (not isinstance(a, torch.Tensor) or not isinstance(b, torch.Tensor) or a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.dim() != 4
+            or a.shape[-1] != 3 or 0 in a.shape or b.shape != a.shape or not a.is_contiguous() or not b.is_contiguous()):
+        raise ValueError(f"frame_errors takes two contiguous (n, h, w, 3) uint8 tensors of one shape, got "
+                         f"{tuple(getattr(a, 'shape', ()))} {getattr(a, 'dtype', None)} and {tuple(getattr(b, 'shape', ()))} {getattr(b, 'dtype', None)}")
+    for d, name in ((depth_a, "depth_a"), (depth_b, "depth_b")):
+        if d is None and name == "depth_b":
+            continue
+        if not isinstance(d, torch.Tensor) or d.dtype != torch.uint16 or d.shape != a.shape[:3] or not d.is_contiguous():
+            got = f"{tuple(d.shape)} {d.dtype}" if isinstance(d, torch.Tensor) else type(d).__name__
+            raise ValueError(f"frame_errors takes {name} as a contiguous {tuple(a.shape[:3])} uint16 tensor (millimetres), got {got}")
+    n, px = int(a.shape[0]), int(a.shape[1]) * int(a.shape[2])
+    if n * px * 3 >= 2 ** 31:
+        raise ValueError(f"frame_errors: {n} frames of {px} pixels hold 2^31 elements or more")
+    if not a.is_cuda or any(t is not None and t.device != a.device for t in (b, depth_a, depth_b)):
+        raise RuntimeError("nerfdet_amd.pipeline: frames must live on the GPU (no CPU fallback)")
+    dev = a.device
+    out = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    check(_lib.load().ndet_frame_errors(_ptr(a), _ptr(b), _ptr(depth_a), _ptr(depth_b), n, px, _ptr(out), c_void_p(_lib.raw_stream(dev))),
+          "frame_errors")
+    sse, n_px = out[:, 0], out[:, 1]
+    psnr = 10.0 * torch.log10(255.0 ** 2 * 3.0 * n_px.to(torch.float64) / sse.to(torch.float64))
+    return dict(sse=sse, n_px=n_px, depth_sad_mm=out[:, 2], n_depth=out[:, 3], psnr=psnr)
+
+
+def depth_to_mm(depth: torch.Tensor) -> torch.Tensor:
+    """Metres -> uint16 millimetres by :func:`pack_frames`' own rule, with torch: in float32 ``d = depth * 1000``; NaN and d < 0 give 0,
+    d > 65535 gives 65535, else trunc(d + 0.5).  For the held-out depth maps of ``score_frames``."""
+    d = depth.to(torch.float32) * 1000.0
+    q = torch.where(d > 65535.0, torch.full_like(d, 65535.0), d + 0.5)
+    q = torch.where(d >= 0.0, q, torch.zeros_like(d))          # NaN compares false
+    return q.to(torch.int32).to(torch.uint16)
 
 
 def frame_meta(cams_or_lidar2img: dict, size_hw, img_scale, pad_size) -> dict:

@@ -45,6 +45,12 @@ the listed scenes' windows with one grouped density ring finish, one sigma-MLP c
 ``img_shape``, ``pad_shape``: pipeline.frame_meta), resized, normalised and padded in ONE launch for the whole call (pipeline.prepare_frames,
 ndet_resize_normalize_views; ``mean`` / ``std`` are ``begin_scene(s)`` keywords) and handed to ``add_views``, which does the rest.
 
+``scene.render_frames(c2w= | extrinsic=)`` / ``group.render_frames(...)`` are the output side in the same formats: the rays of k camera poses
+come from one launch (pipeline.camera_rays, ndet_camera_rays -- a pose needs no frame), go through ``render_rays``' passes, and one launch
+packs the result into (k, h, w, 3) uint8 BGR and (k, h, w) uint16 millimetre frames beside the float outputs (pipeline.pack_frames; depth 0
+is a hole); ``window`` crops, ``stride`` makes a thumbnail.  ``score_frames(frames, meta, depth_frames=)`` compares such a render with
+held-out capture-resolution frames on the device (pipeline.frame_errors: integer sums per frame and their PSNR) and adds nothing to the scene.
+
 Inference only: no training / autograd, no hipGraph replay, one scene per stream; whole chunks are dropped, not single views out of one.
 Without ``keep_views`` there is no ray branch (rendering needs every view's map).
 """
@@ -57,7 +63,8 @@ import numpy as np
 import torch
 
 from . import conv3d, ops
-from .pipeline import IMG_MEAN, IMG_STD, prepare_depth_frames, prepare_frames, rescale_size
+from .pipeline import (IMG_MEAN, IMG_STD, _host_matrices, camera_rays, check_window, depth_to_mm, frame_errors, pack_frames, prepare_depth_frames,
+                       prepare_frames, rescale_size)
 from .volume import map_features_2d, map_features_2d_hip
 
 Tensor = torch.Tensor
@@ -135,6 +142,67 @@ def _render_dict(coarse, fine):
     out = OrderedDict(zip(keys, fine))
     out["coarse"] = OrderedDict(zip(keys, coarse))
     return out
+
+
+def _camera_poses(c2w, extrinsic, what: str) -> np.ndarray:
+    """The k >= 1 poses of a ``render_frames`` call as (k,4,4) float32 camera-to-world matrices: exactly one of ``c2w`` (taken as given) and
+    ``extrinsic`` (world-to-camera, as a chunk meta carries them: inverted on the host in float64, then rounded to float32); else ValueError."""
+    if (c2w is None) == (extrinsic is None):
+        raise ValueError(f"{what} takes exactly one of c2w (camera-to-world) and extrinsic (world-to-camera)")
+    if c2w is not None:
+        return _host_matrices(c2w, f"{what}: c2w").astype(np.float32)
+    return np.linalg.inv(_host_matrices(extrinsic, f"{what}: extrinsic").astype(np.float64)).astype(np.float32)
+
+
+def _scene_intrinsic(meta: dict) -> np.ndarray:
+    """The scene meta's intrinsics at the scale of its ``img_shape``: rows 0 and 1 divided by ``ori_shape[0] / img_shape[0]`` in float32, as
+    pipeline.MultiViewPipeline forms the target views' ``krows`` (multi_view.py:113-114)."""
+    k = np.array(meta["lidar2img"]["intrinsic"], dtype=np.float32)
+    k[:2] = k[:2] / (meta["ori_shape"][0] / meta["img_shape"][0])
+    return k
+
+
+def _frame_grid(meta: dict, window, stride):
+    """``((y0, x0, h, w), stride)`` of a ``render_frames`` call.  ``window=None``: the content region of the meta's ``img_shape`` -- with
+    ``stride=s`` the pixels ``s // 2, s // 2 + s, ...`` inside it on both axes (a thumbnail).  ValueError for anything that leaves no pixel."""
+    if window is None:
+        _, stride = check_window((0, 0, 1, 1), stride)
+        hr, wr = int(meta["img_shape"][0]), int(meta["img_shape"][1])
+        o = stride // 2
+        if o >= hr or o >= wr:
+            raise ValueError(f"stride={stride} leaves no pixel of the {(hr, wr)} content region")
+        window = (o, o, (hr - o + stride - 1) // stride, (wr - o + stride - 1) // stride)
+    return check_window(window, stride)
+
+
+def _frames_dict(coarse, fine, shape):
+    """``render_frames``'s result of one scene: per pass ``frames``, ``depth_frames`` (pipeline.pack_frames) and the float ``rgb`` (k,h,w,3),
+    ``depth``, ``mask`` (k,h,w) they were packed from -- of the fine pass, with the coarse pass's under ``'coarse'``, when there was one."""
+    k, h, w = shape
+
+    def one(rgb, depth, mask):
+        frames, depth_frames = pack_frames(rgb, depth, mask, shape)
+        return OrderedDict(frames=frames, depth_frames=depth_frames, rgb=rgb.view(k, h, w, 3), depth=depth.view(k, h, w), mask=mask.view(k, h, w))
+
+    if fine is None:
+        return one(*coarse)
+    out = one(*fine)
+    out["coarse"] = one(*coarse)
+    return out
+
+
+def _held_out(frames: Tensor, depth_frames, meta: dict, img_scale, pad_size, mean, std, grid):
+    """The held-out side of ``score_frames``: ``frames`` (n, Hs, Ws, 3) through pipeline.prepare_frames' resized bytes, cropped to the content
+    region and strided like the render -- (n, h, w, 3) uint8 -- and ``depth_frames`` (n, Hd, Wd) or None through
+    pipeline.prepare_depth_frames at the content size, strided the same way and quantised by pipeline.depth_to_mm -- (n, h, w) uint16."""
+    (y0, x0, h, w), s = grid
+    hr, wr = int(meta["img_shape"][0]), int(meta["img_shape"][1])
+    u8 = prepare_frames(frames, img_scale, pad_size, mean, std, want_u8=True)[2]
+    held = u8[:, y0:hr:s, x0:wr:s].contiguous()
+    assert tuple(held.shape[1:3]) == (h, w)
+    if depth_frames is None:
+        return held, None
+    return held, depth_to_mm(prepare_depth_frames(depth_frames, (hr, wr))[:, y0::s, x0::s].contiguous())
 
 
 def _render_views(coarse, fine, shape, gt_rgb, gt_depth):
@@ -400,6 +468,51 @@ class SceneStream:
         step = n_rand * max(1, rays.RENDER_TESTING_RAYS // n_rand)       # the passes of rays.render_rays
         coarse, fine = self._render(ray_o, ray_d, step, n_importance)
         return _render_views(coarse, fine, (view_num, hh, ww), gt_rgb, gt_depth)
+
+    def render_frames(self, c2w=None, extrinsic=None, window=None, stride: int = 1, n_importance: int = 0):
+        """Camera frames of k >= 1 poses against the views held -- pose in, BGR and depth out, in the formats :meth:`add_frames` takes.
+        Exactly one of ``c2w`` (k camera-to-world 4 x 4, as ``pipeline.scene_cameras(info)["c2w"]``) and ``extrinsic`` (k world-to-camera
+        4 x 4, as a chunk meta carries them: inverted on the host in float64, rounded to float32).  The intrinsics are the scene meta's,
+        scaled by ``ori_shape[0] / img_shape[0]`` as pipeline.MultiViewPipeline scales the target views'.  ``window = (y0, x0, h, w)``: the
+        h x w output looks through image pixels ``(y0 + i * stride, x0 + j * stride)``; None: the content region of ``img_shape``, with
+        ``stride=s`` its pixels ``s // 2, s // 2 + s, ...`` (a thumbnail).  One ndet_camera_rays launch makes all the rays
+        (pipeline.camera_rays), which go through :meth:`render_rays`' passes of ``rays.RENDER_TESTING_RAYS``; one ndet_pack_frames launch
+        per pass kind makes the frames (pipeline.pack_frames).
+
+        Returns ``dict(frames (k,h,w,3) uint8 BGR, depth_frames (k,h,w) uint16 millimetres, rgb (k,h,w,3), depth (k,h,w), mask (k,h,w))``;
+        with ``n_importance > 0`` these are the fine pass's and ``'coarse'`` holds the same five keys for the coarse pass.  The float
+        outputs are bit for bit ``self.render_rays(*camera_rays(...))`` on the concatenated rays, reshaped; the frames are
+        ``pack_frames`` of them: depth 0 is a hole (``mask`` false), as in the sensor's frames.  Needs ``keep_views=True`` and at least one
+        view (else RuntimeError); bad arguments are a ValueError before any launch.  No state and no bank is changed."""
+        from . import rays
+        self._need_bank("render_frames")
+        n_importance = _check_n_importance(n_importance)
+        poses = _camera_poses(c2w, extrinsic, "render_frames")
+        win, stride = _frame_grid(self.meta, window, stride)
+        ray_o, ray_d = camera_rays(_scene_intrinsic(self.meta), poses, win, stride, device=self.device)
+        coarse, fine = self._render(ray_o.view(-1, 3), ray_d.view(-1, 3), rays.RENDER_TESTING_RAYS, n_importance)
+        return _frames_dict(coarse, fine, (poses.shape[0], win[2], win[3]))
+
+    def score_frames(self, frames: Tensor, meta: dict, depth_frames: Optional[Tensor] = None, stride: int = 1, n_importance: int = 0) -> dict:
+        """Held-out camera frames against the scene's render of their poses, on the device: ``frames`` (1, k, Hs, Ws, 3) uint8 BGR at capture
+        resolution, checked against the scene as :meth:`add_frames` checks them; ``meta`` a chunk meta with the k extrinsics; ``depth_frames``
+        optionally the sensor's (1, k, Hd, Wd) uint16 millimetres.  The held-out bytes are pipeline.prepare_frames' resized bytes cropped to
+        the content region and strided like the render (``stride=s``: pixels ``s // 2, s // 2 + s, ...``), the held-out depth
+        pipeline.prepare_depth_frames at the content size, strided the same way and quantised by pack_frames' rule (pipeline.depth_to_mm);
+        the render is :meth:`render_frames` of the extrinsics.  Returns ``pipeline.frame_errors(render, held_out, render_depth,
+        held_out_depth)``: per frame ``sse``, ``n_px``, ``depth_sad_mm``, ``n_depth`` (int64) and ``psnr`` (float64) over the pixels the
+        render has a depth for.  Nothing is added to the scene."""
+        self._need_bank("score_frames")
+        img_scale, pad_size = check_frames_meta(self.meta, frames, 1)
+        k = frames.shape[1]
+        check_chunk_meta(self.meta, meta, k)
+        check_depth_frames(depth_frames, None, 1, k)
+        n_importance = _check_n_importance(n_importance)
+        grid = _frame_grid(self.meta, None, stride)
+        held, held_depth = _held_out(frames[0], None if depth_frames is None else depth_frames[0], self.meta, img_scale, pad_size, self.mean,
+                                     self.std, grid)
+        out = self.render_frames(extrinsic=meta["lidar2img"]["extrinsic"], stride=stride, n_importance=n_importance)
+        return frame_errors(out["frames"], held, out["depth_frames"], held_depth)
 
     def volume(self):
         """``(volume (C,X,Y,Z), valid (1,X,Y,Z) int64)`` of the views so far: K2-finish -> sigma-MLP -> K1-finish, what ``extract_volume``
@@ -842,6 +955,72 @@ class SceneGroup:
         step = n_rand * max(1, rays.RENDER_TESTING_RAYS // n_rand)       # the passes of rays.render_rays
         res = self._render(os_, ds_, scenes, step, batched, n_importance)
         return [_render_views(coarse, fine, shape, gt_rgb, gt_depth) for (coarse, fine), shape, (gt_rgb, gt_depth) in zip(res, shapes, gts)]
+
+    def render_frames(self, c2w=None, extrinsic=None, scenes=None, batched: bool = False, window=None, stride: int = 1, n_importance: int = 0):
+        """:meth:`SceneStream.render_frames` for the listed scenes at once: exactly one of ``c2w`` and ``extrinsic``, a list with one list of
+        4 x 4 matrices per listed scene (the counts may differ, each at least 1).  Every scene uses its own intrinsics, scaled as in
+        :meth:`SceneStream.render_frames`; ``window`` and ``stride`` are the call's (the group shares ``img_shape``).  ONE
+        ndet_camera_rays launch per distinct intrinsics makes the rays of all the scenes that share them (scenes of one camera model: one
+        launch for the call), rendering goes through :meth:`render_rays`' grouped passes (``batched`` and ``n_importance`` as there), and
+        every scene's frames are packed by one ndet_pack_frames launch per pass kind.  Returns a list of dicts as
+        :meth:`SceneStream.render_frames` returns them: per scene bit for bit ``group.render_rays`` on the generated rays (with
+        ``batched=True`` to :meth:`render_rays`' documented bounds), and a group of one scene is ``SceneStream.render_frames`` bit for bit.
+        RuntimeError without ``keep_views`` or for a listed scene without views; bad arguments are a ValueError before any launch."""
+        from . import rays
+        scenes = self._need_banks("render_frames", scenes)
+        n_importance = _check_n_importance(n_importance)
+        if (c2w is None) == (extrinsic is None):
+            raise ValueError("render_frames takes exactly one of c2w (camera-to-world) and extrinsic (world-to-camera)")
+        given = c2w if c2w is not None else extrinsic
+        if isinstance(given, (Tensor, np.ndarray)) and given.ndim != 4:
+            raise ValueError("render_frames takes one LIST of 4 x 4 matrices per listed scene")
+        given = list(given)
+        if len(given) != len(scenes):
+            raise ValueError(f"render_frames: {len(given)} camera lists for {len(scenes)} listed scenes")
+        poses = [_camera_poses(g, None, "render_frames") if c2w is not None else _camera_poses(None, g, "render_frames") for g in given]
+        win, stride = _frame_grid(self.metas[0], window, stride)
+        ks = [_scene_intrinsic(self.metas[s]) for s in scenes]
+        shared = OrderedDict()                      # listed scenes by the bytes of their intrinsic rows: one launch each
+        for i, k in enumerate(ks):
+            shared.setdefault(k[:2, :3].tobytes(), []).append(i)
+        ray_os, ray_ds = [None] * len(scenes), [None] * len(scenes)
+        for idx in shared.values():
+            o, d = camera_rays(ks[idx[0]], np.concatenate([poses[i] for i in idx]), win, stride, device=self.device)
+            at = 0
+            for i in idx:
+                c = poses[i].shape[0]
+                ray_os[i], ray_ds[i] = o[at:at + c].view(-1, 3), d[at:at + c].view(-1, 3)
+                at += c
+        res = self._render(ray_os, ray_ds, scenes, rays.RENDER_TESTING_RAYS, batched, n_importance)
+        return [_frames_dict(coarse, fine, (p.shape[0], win[2], win[3])) for (coarse, fine), p in zip(res, poses)]
+
+    def score_frames(self, frames: Tensor, metas, scenes=None, depth_frames: Optional[Tensor] = None, batched: bool = False, stride: int = 1,
+                     n_importance: int = 0):
+        """:meth:`SceneStream.score_frames` for the listed scenes at once: ``frames`` (len(scenes), k, Hs, Ws, 3) uint8 BGR, one row of k
+        held-out frames per listed scene, checked as :meth:`add_frames` checks them; ``metas`` one chunk meta per row with its k extrinsics;
+        ``depth_frames`` optionally (len(scenes), k, Hd, Wd) uint16 millimetres.  One ndet_resize_normalize_views launch (and one
+        ndet_depth_frames launch) makes all the held-out frames, :meth:`render_frames` all the renders, and one ndet_frame_errors launch
+        per scene compares them.  Returns a list of ``pipeline.frame_errors`` dicts; nothing is added to any scene."""
+        scenes = self._need_banks("score_frames", scenes)
+        n = len(scenes)
+        first = self.metas[0]
+        img_scale, pad_size = check_frames_meta(first, frames, n)
+        metas = list(metas)
+        if len(metas) != n:
+            raise ValueError(f"score_frames: {len(metas)} chunk metas for {n} listed scenes")
+        k = frames.shape[1]
+        for s, m in zip(scenes, metas):
+            check_chunk_meta(self.metas[s], m, k)
+        check_depth_frames(depth_frames, None, n, k)
+        n_importance = _check_n_importance(n_importance)
+        grid = _frame_grid(first, None, stride)
+        held, held_depth = _held_out(frames.reshape((n * k,) + tuple(frames.shape[2:])),
+                                     None if depth_frames is None else depth_frames.reshape((n * k,) + tuple(depth_frames.shape[2:])), first,
+                                     img_scale, pad_size, self.mean, self.std, grid)
+        outs = self.render_frames(extrinsic=[m["lidar2img"]["extrinsic"] for m in metas], scenes=scenes, batched=batched, stride=stride,
+                                  n_importance=n_importance)
+        return [frame_errors(out["frames"], held[i * k:(i + 1) * k], out["depth_frames"], None if held_depth is None else held_depth[i * k:(i + 1) * k])
+                for i, out in enumerate(outs)]
 
     def _volumes(self, scenes: List[int]):
         """``(volume (n,C,X,Y,Z), valid (n,1,X,Y,Z) int64)`` of the listed scenes: grouped K2-finish -> one sigma-MLP call over all their
