@@ -870,6 +870,54 @@ int ndet_pack_frames(const float* rgb, const float* depth, const uint8_t* mask, 
 int ndet_frame_errors(const uint8_t* a, const uint8_t* b, const uint16_t* da, const uint16_t* db, int n, int64_t px, int64_t* out,
                       void* stream);
 
+/* ---- detections out: the 3D boxes of a detection result in a camera's image -- projected, drawn onto a frame, matched to a depth frame.
+ * Every entry point checks its arguments on the host before any HIP call: a null pointer, a non-positive size, stride < 1, a negative
+ * offset, near <= 0 and a thickness other than 1, 3, 5 are NDET_E_INVALID; 2^31 elements or more, a misaligned pointer and more boxes than
+ * an int16 label holds are NDET_E_UNSUPPORTED.  Plain vector stores, no global atomics; nothing is read back.
+ *
+ * ndet_project_boxes: the corners of n boxes, (n,8,3) float32 in the order of DepthInstance3DBoxes.corners
+ * (mmdet3d/core/bbox/structures/depth_box3d.py:46-84), through k world-to-camera matrices world2cam (k,3,4) and the intrinsic rows (2,3) of
+ * ndet_camera_rays (the skew entry is ignored, as there) onto ndet_camera_rays' grid: output pixel (i, j) is image pixel
+ * (y0 + i * stride, x0 + j * stride), an image pixel px covers [px, px + 1) and has its centre at px + 0.5.  One thread per (pose, box),
+ * float32 in this statement order (the library is built with -ffp-contract=off, every fused step is an fmaf):
+ *   camera point   q_r = fmaf(E[r][2], Z, fmaf(E[r][1], Y, E[r][0] * X)) + E[r][3]  for the rows r = 0, 1, 2 of the pose's matrix E;
+ *   the 12 edges   (0,1) (1,2) (2,3) (3,0), (4,5) (5,6) (6,7) (7,4), (0,4) (1,5) (2,6) (3,7) as corner pairs.  An end survives iff
+ *       z >= near (a NaN fails).  An edge whose ends both fail is dropped; if exactly one fails it moves to the near plane: with a the
+ *       surviving and b the failing end t = (near - z_a) / (z_b - z_a), x = fmaf(t, x_b - x_a, x_a), y likewise, z = near;
+ *   pixel          u = fmaf(k[0], x / z, k[2]), v = fmaf(k[4], y / z, k[5]); xo = (u - ((float)x0 + 0.5f)) / (float)stride + 0.5f, yo likewise
+ *       with y0.  A NaN in any of an edge's four coordinates drops the edge; else each is clamped to [-2^20, 2^20] (which only keeps
+ *       ndet_draw_boxes' integers in range: a line that leaves that square is bent at its border) and (int)floorf is taken.
+ * Outputs: edges (k,n,12,4) int32 = x_a, y_a, x_b, y_b per edge in the edge's own corner order, zeros for a dropped edge; edge_mask (k,n)
+ * int32, bit e set iff edge e survives; rect (k,n,4) int32 = inclusive xmin, ymin, xmax, ymax of the surviving edges' ends intersected with
+ * [0,w) x [0,h), four -1 when nothing survives or nothing is left; zrange (k,n,2) float32 = the least and the largest camera z of the eight
+ * unclipped corners (a NaN z is passed over unless all are).  edges and rect must be 16-byte aligned. */
+int ndet_project_boxes(const float* intrinsic_rows, const float* world2cam, const float* corners, int k, int n, int x0, int y0, int stride, int h,
+                       int w, float near_m, int32_t* edges, int32_t* edge_mask, int32_t* rect, float* zrange, void* stream);
+
+/* ndet_draw_boxes: the wireframes of ndet_project_boxes' edges onto frames -- the reference draws its results nowhere; the boxes are the
+ * result's, mmdet3d/models/dense_heads/imvoxel_head_v2.py:544.  frames_in (k,h,w,3) uint8 is only read; frames_out, a buffer that does
+ * not overlap it, gets every pixel: the input bytes, or -- where an edge covers the pixel -- colours[b] (n,3) uint8 of the HIGHEST box index
+ * b with a covering edge (hand the boxes over by ascending score and the best detection wins).  A gather per pixel: one workgroup per
+ * 16 x 16 tile scans the frame's 12 n edges in batches of 256, keeps in LDS those that can reach the tile, and each thread tests its pixel.
+ * Coverage is integer-exact, thickness t in {1, 3, 5}, r = (t - 1) / 2; for an edge with a = x_b - x_a, b = y_b - y_a:
+ *   x-major, |a| >= |b| and a != 0: with the ends swapped so that a > 0, for x_a <= x <= x_b the line passes
+ *       yl = y_a + floor((2 b (x - x_a) + a) / (2 a))  (floor division in int64) and covers (x, y) iff |y - yl| <= r;
+ *   y-major, |b| > |a|: the same with x and y exchanged;  a = b = 0: the pixels x = x_a, |y - y_a| <= r.
+ * Edges whose bit in edge_mask (k,n) is clear paint nothing. */
+int ndet_draw_boxes(const uint8_t* frames_in, const int32_t* edges, const int32_t* edge_mask, const uint8_t* colours, int k, int h, int w, int n,
+                    int thickness, uint8_t* frames_out, void* stream);
+
+/* ndet_label_frames: which detection each pixel of a depth frame belongs to.  depth_mm (k,h,w) uint16 millimetres (0: a hole) on
+ * ndet_camera_rays' grid x0, y0, stride with its intrinsic_rows (2,3), camrotc2w (k,3,3) and cam_lightpos (k,3); box_frames (n,8) float32 =
+ * centre (3), half extents (3), cos yaw, sin yaw, n <= 32767.  A pixel with mm != 0 looks along d, ndet_camera_rays' expression statement
+ * for statement (get_dtu_raydir, mmdet3d/datasets/pipelines/data_augment_utils.py:410-424); its point is z = (float)mm / 1000.0f,
+ * p_j = fmaf(z, d_j, lpos_j); in a box's frame, with (dx, dy, dz) = p - centre, lx = fmaf(dx, cos, -(dy * sin)), ly = fmaf(dx, sin, dy * cos)
+ * -- the inverse of the corners' yaw; the box holds the point iff |lx| <= hx && |ly| <= hy && |dz| <= hz.  labels (k,h,w) int16: the
+ * highest index among the boxes that hold the point, -1 for none and for mm = 0.  One thread per pixel, the boxes staged through LDS 256 at
+ * a time. */
+int ndet_label_frames(const uint16_t* depth_mm, const float* intrinsic_rows, const float* camrotc2w, const float* cam_lightpos,
+                      const float* box_frames, int k, int h, int w, int n, int x0, int y0, int stride, int16_t* labels, void* stream);
+
 /* Workspace of ndet_positive_indices for n elements (render_ray.py:386-404), in bytes; 0 for an n the entry point refuses. */
 int64_t ndet_positive_indices_workspace_bytes(int64_t n);
 

@@ -169,6 +169,9 @@ SIGNATURES = {
     "ndet_camera_rays": ([_P, _P, _P] + [c_int] * 6 + [_P, _P, _P], c_int),
     "ndet_pack_frames": ([_P, _P, _P, c_int64, _P, _P, _P], c_int),
     "ndet_frame_errors": ([_P, _P, _P, _P, c_int, c_int64, _P, _P], c_int),
+    "ndet_project_boxes": ([_P, _P, _P] + [c_int] * 7 + [c_float, _P, _P, _P, _P, _P], c_int),
+    "ndet_draw_boxes": ([_P, _P, _P, _P] + [c_int] * 5 + [_P, _P], c_int),
+    "ndet_label_frames": ([_P] * 5 + [c_int] * 7 + [_P, _P], c_int),
     "ndet_stem_pack_weights": ([_P, _P, _P], c_int),
     "ndet_stem_conv_bn_relu_maxpool": ([_P, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, _P, c_float, _P, _P, _P, _P, _P], c_int),
     "ndet_stem_pack_weights_f16x2": ([_P, c_float, _P, _P], c_int),

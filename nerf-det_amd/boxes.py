@@ -4,6 +4,7 @@ get_targets :457-470).  Semantics of mmdet3d/core/bbox/structures/base_box3d.py:
 (x, y, z_bottom, dx, dy, dz, yaw); a (N,6) input gets a zero yaw; ``origin`` re-bases the centre."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 
@@ -57,3 +58,55 @@ def bbox3d2result(bboxes, scores, labels):
         out.tensor, out.box_dim, out.with_yaw = packed[:, :c].contiguous(), bboxes.box_dim, bboxes.with_yaw
         return dict(boxes_3d=out, scores_3d=packed[:, c].contiguous(), labels_3d=packed[:, c + 1].to(torch.int64))
     return dict(boxes_3d=bboxes.to("cpu"), scores_3d=scores.cpu(), labels_3d=labels.cpu())
+
+
+# DepthInstance3DBoxes.corners' order (mmdet3d/core/bbox/structures/depth_box3d.py:72-78): unit offsets about the origin (0.5, 0.5, 0)
+CORNER_OFFSETS = ((0, 0, 0), (0, 0, 1), (0, 1, 1), (0, 1, 0), (1, 0, 0), (1, 0, 1), (1, 1, 1), (1, 1, 0))
+# the 12 edges as corner pairs: the x = 0 face loop, the x = 1 face loop, the four connectors (csrc/detections_out_kernels.hip)
+BOX_EDGES = ((0, 1), (1, 2), (2, 3), (3, 0), (4, 5), (5, 6), (6, 7), (7, 4), (0, 4), (1, 5), (2, 6), (3, 7))
+
+
+def _boxes_f64(tensor) -> np.ndarray:
+    """(n, 7) boxes, numpy or a CPU tensor, as float64; ValueError for another shape."""
+    t = tensor.detach().numpy() if isinstance(tensor, torch.Tensor) else np.asarray(tensor)
+    if t.ndim != 2 or t.shape[1] != 7:
+        raise ValueError(f"boxes must be (n, 7) = (x, y, z_bottom, dx, dy, dz, yaw), got {t.shape}")
+    return t.astype(np.float64)
+
+
+def box_corners(tensor) -> np.ndarray:
+    """The corners of (n, 7) boxes ``(x, y, z_bottom, dx, dy, dz, yaw)``, numpy or a CPU tensor, as (n, 8, 3) float32: what
+    ``DepthInstance3DBoxes.corners`` returns (depth_box3d.py:46-84), in its order, with the yaw sign of ``rotation_3d_in_axis(axis=2)``
+    (structures/utils.py:21-61: x' = x cos + y sin, y' = -x sin + y cos) -- computed in float64 and rounded once to float32."""
+    t = _boxes_f64(tensor)
+    norm = np.asarray(CORNER_OFFSETS, dtype=np.float64) - np.array([0.5, 0.5, 0.0])
+    c = t[:, None, 3:6] * norm[None]
+    cos, sin = np.cos(t[:, 6])[:, None], np.sin(t[:, 6])[:, None]
+    out = np.empty_like(c)
+    out[..., 0] = c[..., 0] * cos + c[..., 1] * sin
+    out[..., 1] = c[..., 0] * -sin + c[..., 1] * cos
+    out[..., 2] = c[..., 2]
+    return (out + t[:, None, :3]).astype(np.float32)
+
+
+def box_frames(tensor) -> np.ndarray:
+    """(n, 8) float32 for ndet_label_frames: the gravity centre (3), the half extents (3), cos yaw, sin yaw of (n, 7) boxes -- computed in
+    float64 and rounded once.  A point p lies in the box's frame at lx = dx cos - dy sin, ly = dx sin + dy cos, (dx, dy) = p - centre: the
+    inverse of :func:`box_corners`' rotation."""
+    t = _boxes_f64(tensor)
+    out = np.empty((t.shape[0], 8), dtype=np.float64)
+    out[:, :2] = t[:, :2]
+    out[:, 2] = t[:, 2] + t[:, 5] * 0.5
+    out[:, 3:6] = t[:, 3:6] * 0.5
+    out[:, 6], out[:, 7] = np.cos(t[:, 6]), np.sin(t[:, 6])
+    return out.astype(np.float32)
+
+
+def drawing_order(scores, score_thr: float = 0.0) -> np.ndarray:
+    """The indices of the detections with ``score >= score_thr`` in drawing order, int64: by ascending score, the sort stable -- of equal
+    scores the one later in the result comes last.  The best detection gets the highest position and wins every pixel it shares."""
+    s = scores.detach().cpu().numpy() if isinstance(scores, torch.Tensor) else np.asarray(scores)
+    if s.ndim != 1:
+        raise ValueError(f"scores must be (n,), got {s.shape}")
+    keep = np.flatnonzero(s >= score_thr)
+    return keep[np.argsort(s[keep], kind="stable")].astype(np.int64)

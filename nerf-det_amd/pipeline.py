@@ -18,6 +18,10 @@ The output side speaks the same formats: :func:`camera_rays` makes the rays of a
 ndet_target_rays' arithmetic), :func:`pack_frames` turns a render into uint8 BGR and uint16 millimetre frames (ndet_pack_frames), and
 :func:`frame_errors` compares two such frames on the device with exact integer sums (ndet_frame_errors) -- what
 ``SceneStream / SceneGroup.render_frames`` and ``score_frames`` stand on.
+
+A detection result goes the same way into the camera's image: :func:`project_boxes` says where boxes fall in the frames of given poses
+(ndet_project_boxes), :func:`draw_boxes` puts their wireframes onto frames in device memory (ndet_draw_boxes) and :func:`label_frames` says
+which box each pixel of a depth frame belongs to (ndet_label_frames) -- what ``draw_detections`` and ``label_detections`` stand on.
 """
 from __future__ import annotations
 
@@ -291,6 +295,149 @@ def frame_errors(frames_a: torch.Tensor, frames_b: torch.Tensor, depth_a: torch.
     sse, n_px = out[:, 0], out[:, 1]
     psnr = 10.0 * torch.log10(255.0 ** 2 * 3.0 * n_px.to(torch.float64) / sse.to(torch.float64))
     return dict(sse=sse, n_px=n_px, depth_sad_mm=out[:, 2], n_depth=out[:, 3], psnr=psnr)
+
+
+# BGR, one colour a class, repeated beyond the table (the 18 ScanNet classes get 18 distinct colours)
+PALETTE_BGR = ((75, 25, 230), (75, 180, 60), (25, 225, 255), (200, 130, 0), (48, 130, 245), (180, 30, 145), (240, 240, 70), (230, 50, 240),
+               (60, 245, 210), (212, 190, 250), (128, 128, 0), (255, 190, 220), (40, 110, 170), (200, 250, 255), (0, 0, 128), (195, 255, 170),
+               (0, 128, 128), (180, 215, 255))
+
+
+def class_palette(n: int) -> np.ndarray:
+    """``(n, 3)`` uint8 BGR colours, one a class: the fixed table ``PALETTE_BGR`` repeated."""
+    if not isinstance(n, (int, np.integer)) or isinstance(n, bool) or n < 1:
+        raise ValueError(f"class_palette takes a positive int, got {n!r}")
+    table = np.asarray(PALETTE_BGR, dtype=np.uint8)
+    return table[np.arange(int(n)) % len(table)]
+
+
+def _gpu(device, given=None) -> torch.device:
+    """The GPU a wrapper works on: ``device``, else ``given``'s when that is a device tensor, else the current one; RuntimeError without one."""
+    if device is None and isinstance(given, torch.Tensor) and given.is_cuda:
+        device = given.device
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("nerfdet_amd.pipeline: detections are projected, drawn and labelled on the GPU (no CPU fallback)")
+    return dev
+
+
+def _intrinsic_rows(intrinsic, what: str) -> np.ndarray:
+    k = intrinsic.detach().cpu().numpy() if isinstance(intrinsic, torch.Tensor) else np.asarray(intrinsic)
+    if k.shape not in ((3, 3), (4, 4)):
+        raise ValueError(f"{what} takes 3 x 3 or 4 x 4 intrinsics, got {k.shape}")
+    return np.ascontiguousarray(k[:2, :3], dtype=np.float32).reshape(-1)
+
+
+def _host_f32(a, shape_tail: tuple, what: str) -> np.ndarray:
+    """``a`` (numpy or tensor) as a float32 numpy array of shape (n >= 1,) + shape_tail; else ValueError."""
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if a.ndim != 1 + len(shape_tail) or a.shape[0] < 1 or tuple(a.shape[1:]) != shape_tail or a.dtype.kind != "f":
+        raise ValueError(f"{what} must be a float array of shape (n >= 1,) + {shape_tail}, got {a.shape} {a.dtype}")
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def project_boxes(intrinsic, corners, window, stride: int = 1, c2w=None, extrinsic=None, near: float = 0.1, device=None) -> dict:
+    """Where n boxes fall in the frames of k camera poses: one launch (ndet_project_boxes), one small upload, nothing read back.
+    ``intrinsic``: 3 x 3 or 4 x 4, scaled to the image grid; ``corners`` (n, 8, 3) float, as ``boxes.box_corners`` makes them;
+    ``window = (y0, x0, h, w)`` and ``stride`` as in :func:`camera_rays`; exactly one of ``c2w`` (k camera-to-world 4 x 4, inverted on the host
+    in float64 and rounded to float32) and ``extrinsic`` (k world-to-camera 4 x 4, taken as given); ``near`` > 0 in metres, the plane edges are
+    clipped at.  Returns ``dict(edges (k,n,12,4) int32, edge_mask (k,n) int32, rect (k,n,4) int32, zrange (k,n,2) float32, window, stride)``
+    on the device, as include/nerfdet_hip.h defines them.  ValueError for wrong shapes, RuntimeError without a GPU (no CPU fallback)."""
+    (y0, x0, h, w), stride = check_window(window, stride)
+    krows = _intrinsic_rows(intrinsic, "project_boxes")
+    pts = _host_f32(corners, (8, 3), "project_boxes: corners")
+    if (c2w is None) == (extrinsic is None):
+        raise ValueError("project_boxes takes exactly one of c2w (camera-to-world) and extrinsic (world-to-camera)")
+    if c2w is not None:
+        w2c = np.linalg.inv(_host_matrices(c2w, "project_boxes: c2w").astype(np.float64)).astype(np.float32)
+    else:
+        w2c = _host_matrices(extrinsic, "project_boxes: extrinsic").astype(np.float32)
+    if not isinstance(near, (int, float, np.floating, np.integer)) or isinstance(near, bool) or not near > 0:
+        raise ValueError(f"project_boxes: near={near!r} must be a positive number of metres")
+    k, n = w2c.shape[0], pts.shape[0]
+    if k * n * 48 >= 2 ** 31:
+        raise ValueError(f"project_boxes: {k} poses of {n} boxes hold 2^31 edge elements or more")
+    dev = _gpu(device, c2w if c2w is not None else extrinsic)
+    # one upload: 6 intrinsic floats, then the k matrices' three rows, then the corners
+    buf = torch.from_numpy(np.concatenate([krows, w2c[:, :3, :].reshape(-1), pts.reshape(-1)])).to(dev)
+    edges = torch.empty((k, n, 12, 4), dtype=torch.int32, device=dev)
+    edge_mask = torch.empty((k, n), dtype=torch.int32, device=dev)
+    rect = torch.empty((k, n, 4), dtype=torch.int32, device=dev)
+    zrange = torch.empty((k, n, 2), dtype=torch.float32, device=dev)
+    check(_lib.load().ndet_project_boxes(_ptr(buf), _ptr(buf[6:]), _ptr(buf[6 + 12 * k:]), k, n, x0, y0, stride, h, w, float(near), _ptr(edges),
+                                         _ptr(edge_mask), _ptr(rect), _ptr(zrange), c_void_p(_lib.raw_stream(dev))), "project_boxes")
+    return dict(edges=edges, edge_mask=edge_mask, rect=rect, zrange=zrange, window=(y0, x0, h, w), stride=stride)
+
+
+def draw_boxes(frames: torch.Tensor, projected: dict, colours, thickness: int = 1) -> torch.Tensor:
+    """The wireframes of :func:`project_boxes`' boxes on frames that lie in device memory: one launch (ndet_draw_boxes) writes NEW frames,
+    ``frames`` (k, h, w, 3) uint8 is only read.  ``projected``: project_boxes' dict for the same k and an h x w window; ``colours`` (n, 3)
+    uint8, numpy or tensor (a device tensor is used as it is); ``thickness`` 1, 3 or 5 pixels across the line's major axis.  Where the edges
+    of several boxes cover a pixel the HIGHEST box index wins, so hand the boxes over by ascending score (``boxes.drawing_order``).
+    ValueError for wrong shapes or dtypes before any launch, RuntimeError for CPU tensors."""
+    if thickness not in (1, 3, 5) or isinstance(thickness, bool):
+        raise ValueError(f"draw_boxes: thickness={thickness!r} must be 1, 3 or 5")
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3 or 0 in frames.shape \
+            or not frames.is_contiguous():
+        got = f"{tuple(frames.shape)} {frames.dtype}" if isinstance(frames, torch.Tensor) else type(frames).__name__
+        raise ValueError(f"draw_boxes takes frames as a contiguous (k, h, w, 3) uint8 tensor, got {got}")
+    k, h, w = (int(v) for v in frames.shape[:3])
+    if not isinstance(projected, dict):
+        raise ValueError(f"draw_boxes takes project_boxes' dict, got {type(projected).__name__}")
+    edges, edge_mask = projected.get("edges"), projected.get("edge_mask")
+    if (not isinstance(edges, torch.Tensor) or not isinstance(edge_mask, torch.Tensor) or edges.dtype != torch.int32 or edge_mask.dtype != torch.int32
+            or edges.dim() != 4 or edges.shape[0] != k or edges.shape[1] < 1 or tuple(edges.shape[2:]) != (12, 4)
+            or edge_mask.shape != edges.shape[:2] or not edges.is_contiguous() or not edge_mask.is_contiguous()):
+        raise ValueError(f"draw_boxes takes project_boxes' edges ({k}, n, 12, 4) and edge_mask ({k}, n) as contiguous int32 tensors")
+    if "window" in projected and tuple(projected["window"][2:]) != (h, w):
+        raise ValueError(f"draw_boxes: the boxes were projected onto a {tuple(projected['window'][2:])} grid, the frames are {(h, w)}")
+    n = int(edges.shape[1])
+    col = colours if isinstance(colours, torch.Tensor) else np.asarray(colours)
+    if tuple(col.shape) != (n, 3) or col.dtype != (torch.uint8 if isinstance(col, torch.Tensor) else np.uint8):
+        raise ValueError(f"draw_boxes takes colours as ({n}, 3) uint8, got {tuple(col.shape)} {col.dtype}")
+    if k * h * w * 3 >= 2 ** 31:
+        raise ValueError(f"draw_boxes: {k} frames of {h} x {w} pixels hold 2^31 elements or more")
+    if not frames.is_cuda or edges.device != frames.device or edge_mask.device != frames.device:
+        raise RuntimeError("nerfdet_amd.pipeline: frames and projected boxes must live on the GPU (no CPU fallback)")
+    dev = frames.device
+    col = col.to(dev).contiguous() if isinstance(col, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(col)).to(dev)
+    out = torch.empty_like(frames)
+    check(_lib.load().ndet_draw_boxes(_ptr(frames), _ptr(edges), _ptr(edge_mask), _ptr(col), k, h, w, n, int(thickness), _ptr(out),
+                                      c_void_p(_lib.raw_stream(dev))), "draw_boxes")
+    return out
+
+
+def label_frames(depth_frames: torch.Tensor, intrinsic, c2w, box_frames, window, stride: int = 1) -> torch.Tensor:
+    """Which box each pixel of a depth frame belongs to: ``(k, h, w)`` int16 from one launch (ndet_label_frames) -- the highest index among
+    the boxes that hold the pixel's point, -1 for none and for a hole (0 millimetres).  ``depth_frames`` (k, h, w) uint16 millimetres on the
+    device, on the grid ``window = (y0, x0, h, w)``, ``stride`` of :func:`camera_rays` with its ``intrinsic`` and ``c2w`` (k camera-to-world
+    4 x 4); ``box_frames`` (n, 8) float as ``boxes.box_frames`` makes them, n <= 32767.  The point of a pixel is the camera centre plus
+    ``mm / 1000`` times :func:`camera_rays`' direction.  ValueError for wrong shapes or dtypes before any launch, RuntimeError for CPU tensors."""
+    (y0, x0, h, w), stride = check_window(window, stride)
+    krows = _intrinsic_rows(intrinsic, "label_frames")
+    d = depth_frames
+    if not isinstance(d, torch.Tensor) or d.dtype != torch.uint16 or d.dim() != 3 or d.shape[0] < 1 or tuple(d.shape[1:]) != (h, w) or not d.is_contiguous():
+        got = f"{tuple(d.shape)} {d.dtype}" if isinstance(d, torch.Tensor) else type(d).__name__
+        raise ValueError(f"label_frames takes depth_frames as a contiguous (k, {h}, {w}) uint16 tensor (millimetres), got {got}")
+    k = int(d.shape[0])
+    m = _host_matrices(c2w, "label_frames: c2w").astype(np.float32)
+    if m.shape[0] != k:
+        raise ValueError(f"label_frames: {m.shape[0]} poses for {k} depth frames")
+    bf = _host_f32(box_frames, (8,), "label_frames: box_frames")
+    n = bf.shape[0]
+    if n > 32767:
+        raise ValueError(f"label_frames: {n} boxes do not fit an int16 label")
+    if k * h * w >= 2 ** 31:
+        raise ValueError(f"label_frames: {k} frames of {h} x {w} pixels hold 2^31 elements or more")
+    if not d.is_cuda:
+        raise RuntimeError("nerfdet_amd.pipeline: depth frames must live on the GPU (no CPU fallback)")
+    dev = d.device
+    # one upload: 6 intrinsic floats, the k rotations, the k centres, the boxes
+    buf = torch.from_numpy(np.concatenate([krows, m[:, :3, :3].reshape(-1), m[:, :3, 3].reshape(-1), bf.reshape(-1)])).to(dev)
+    labels = torch.empty((k, h, w), dtype=torch.int16, device=dev)
+    check(_lib.load().ndet_label_frames(_ptr(d), _ptr(buf), _ptr(buf[6:]), _ptr(buf[6 + 9 * k:]), _ptr(buf[6 + 12 * k:]), k, h, w, n, x0, y0, stride,
+                                        _ptr(labels), c_void_p(_lib.raw_stream(dev))), "label_frames")
+    return labels
 
 
 def depth_to_mm(depth: torch.Tensor) -> torch.Tensor:

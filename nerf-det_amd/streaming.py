@@ -51,6 +51,12 @@ packs the result into (k, h, w, 3) uint8 BGR and (k, h, w) uint16 millimetre fra
 is a hole); ``window`` crops, ``stride`` makes a thumbnail.  ``score_frames(frames, meta, depth_frames=)`` compares such a render with
 held-out capture-resolution frames on the device (pipeline.frame_errors: integer sums per frame and their PSNR) and adds nothing to the scene.
 
+``scene.draw_detections(frames, result, c2w= | extrinsic=)`` / ``label_detections(depth_frames, result, ...)`` (and the group's, with one
+list per listed scene) put a detection result into the camera's image: the kept boxes' corners go up in one upload, one launch projects
+them (pipeline.project_boxes, ndet_project_boxes), one draws their wireframes onto frames that lie in device memory (pipeline.draw_boxes,
+ndet_draw_boxes: new frames, the best detection on top) or says which detection each pixel of a depth frame belongs to
+(pipeline.label_frames, ndet_label_frames).  They use the scene's meta only and need no ``keep_views``.
+
 Inference only: no training / autograd, no hipGraph replay, one scene per stream; whole chunks are dropped, not single views out of one.
 Without ``keep_views`` there is no ray branch (rendering needs every view's map).
 """
@@ -63,8 +69,8 @@ import numpy as np
 import torch
 
 from . import conv3d, ops
-from .pipeline import (IMG_MEAN, IMG_STD, _host_matrices, camera_rays, check_window, depth_to_mm, frame_errors, pack_frames, prepare_depth_frames,
-                       prepare_frames, rescale_size)
+from .pipeline import (IMG_MEAN, IMG_STD, _host_matrices, camera_rays, check_window, class_palette, depth_to_mm, draw_boxes, frame_errors,
+                       label_frames, pack_frames, prepare_depth_frames, prepare_frames, project_boxes, rescale_size)
 from .volume import map_features_2d, map_features_2d_hip
 
 Tensor = torch.Tensor
@@ -203,6 +209,98 @@ def _held_out(frames: Tensor, depth_frames, meta: dict, img_scale, pad_size, mea
     if depth_frames is None:
         return held, None
     return held, depth_to_mm(prepare_depth_frames(depth_frames, (hr, wr))[:, y0::s, x0::s].contiguous())
+
+
+def _kept_detections(result, score_thr, palette, what: str):
+    """What of one scene's detection result (``detect()[0]``: ``boxes_3d``, ``scores_3d``, ``labels_3d`` on the host) goes to the device:
+    ``(kept (m,) int64 indices in boxes.drawing_order, their boxes (m,7) float32, their colours (m,3) uint8)`` -- the colour of a box is its
+    label's row of ``palette`` ((c,3) uint8; None: pipeline.class_palette).  ValueError for anything else."""
+    from .boxes import drawing_order
+    if not isinstance(result, dict) or not all(key in result for key in ("boxes_3d", "scores_3d", "labels_3d")):
+        raise ValueError(f"{what} takes one scene's result as detect() returns it: dict(boxes_3d, scores_3d, labels_3d)")
+    boxes = getattr(result["boxes_3d"], "tensor", result["boxes_3d"])
+    boxes = boxes.detach().cpu().numpy() if isinstance(boxes, Tensor) else np.asarray(boxes)
+    scores, labels = (t.detach().cpu().numpy() if isinstance(t, Tensor) else np.asarray(t) for t in (result["scores_3d"], result["labels_3d"]))
+    if boxes.ndim != 2 or boxes.shape[1] != 7 or scores.shape != (boxes.shape[0],) or labels.shape != scores.shape or labels.dtype.kind not in "iu":
+        raise ValueError(f"{what}: a result holds (n,7) boxes, (n,) scores and (n,) integer labels, got {boxes.shape}, {scores.shape}, "
+                         f"{labels.shape} {labels.dtype}")
+    if not isinstance(score_thr, (int, float, np.floating, np.integer)) or isinstance(score_thr, bool) or score_thr != score_thr:
+        raise ValueError(f"{what}: score_thr={score_thr!r} must be a number")
+    if palette is not None:
+        palette = palette.detach().cpu().numpy() if isinstance(palette, Tensor) else np.asarray(palette)
+        if palette.ndim != 2 or palette.shape[0] < 1 or palette.shape[1] != 3 or palette.dtype != np.uint8:
+            raise ValueError(f"{what}: palette must be (c, 3) uint8 BGR, got {palette.shape} {palette.dtype}")
+    kept = drawing_order(scores, score_thr)
+    lab = labels[kept].astype(np.int64)
+    if len(lab) and (lab.min() < 0 or (palette is not None and lab.max() >= palette.shape[0])):
+        raise ValueError(f"{what}: labels {int(lab.min())} .. {int(lab.max())} do not index the palette")
+    if palette is None:
+        palette = class_palette(int(lab.max()) + 1 if len(lab) else 1)
+    return kept, np.ascontiguousarray(boxes[kept], dtype=np.float32), np.ascontiguousarray(palette[lab])
+
+
+def _detection_grid(meta: dict, window, stride, capture, what: str):
+    """``(intrinsic, (y0, x0, h, w), stride)`` of a ``draw_detections`` / ``label_detections`` call: the render grid of ``render_frames``
+    (:func:`_frame_grid`, :func:`_scene_intrinsic`), or with ``capture=True`` the whole frame at ``ori_shape`` with the meta's intrinsics
+    unscaled -- a window or a stride is refused there."""
+    if not isinstance(capture, bool):
+        raise ValueError(f"{what}: capture must be a bool, got {capture!r}")
+    if not capture:
+        return (_scene_intrinsic(meta),) + _frame_grid(meta, window, stride)
+    if window is not None or isinstance(stride, bool) or stride != 1:
+        raise ValueError(f"{what}: capture=True takes whole frames at ori_shape {tuple(meta['ori_shape'][:2])}: no window, stride 1")
+    return np.array(meta["lidar2img"]["intrinsic"], dtype=np.float32), (0, 0, int(meta["ori_shape"][0]), int(meta["ori_shape"][1])), 1
+
+
+def _plan_detections(det, meta: dict, frames, trailing: tuple, dtype, result, c2w, extrinsic, window, stride, capture, score_thr, palette, what: str):
+    """Every check of one scene's ``draw_detections`` / ``label_detections`` call, before any launch: the frames' shape and dtype against
+    the grid and the poses, the result, the grid.  Returns what the launches need."""
+    if det.training:
+        raise RuntimeError(f"{what} is inference only: call det.eval() first")
+    intrinsic, win, stride = _detection_grid(meta, window, stride, capture, what)
+    poses = _camera_poses(c2w, extrinsic, what)                # validates the pair; camera-to-world
+    shape = (poses.shape[0], win[2], win[3]) + trailing
+    if not isinstance(frames, Tensor) or frames.dtype != dtype or tuple(frames.shape) != shape or not frames.is_contiguous():
+        got = f"{tuple(frames.shape)} {frames.dtype}" if isinstance(frames, Tensor) else type(frames).__name__
+        raise ValueError(f"{what} takes {poses.shape[0]} frames as a contiguous {shape} {dtype} tensor for this grid, got {got}")
+    kept, boxes, colours = _kept_detections(result, score_thr, palette, what)
+    if len(kept) > 32767:
+        raise ValueError(f"{what}: {len(kept)} detections kept; an int16 label holds 32767")
+    return dict(frames=frames, intrinsic=intrinsic, window=win, stride=stride, poses=poses, c2w=c2w, extrinsic=extrinsic, kept=kept, boxes=boxes,
+                colours=colours)
+
+
+def _need_device_frames(plans, what: str) -> None:
+    if any(not p["frames"].is_cuda for p in plans):
+        raise RuntimeError(f"{what}: the frames must live on the GPU (no CPU fallback)")
+
+
+def _draw_plan(p: dict, thickness: int) -> dict:
+    """One scene's ``draw_detections`` from its checked plan: one ndet_project_boxes and one ndet_draw_boxes launch, or none when no
+    detection is kept."""
+    from .boxes import box_corners
+    frames, k = p["frames"], p["poses"].shape[0]
+    kept = torch.from_numpy(p["kept"])
+    if len(p["kept"]) == 0:
+        return OrderedDict(frames=frames.clone(), rect=torch.empty((k, 0, 4), dtype=torch.int32, device=frames.device),
+                           zrange=torch.empty((k, 0, 2), dtype=torch.float32, device=frames.device), kept=kept)
+    proj = project_boxes(p["intrinsic"], box_corners(p["boxes"]), p["window"], p["stride"], c2w=p["c2w"], extrinsic=p["extrinsic"],
+                         device=frames.device)
+    return OrderedDict(frames=draw_boxes(frames, proj, p["colours"], thickness), rect=proj["rect"], zrange=proj["zrange"], kept=kept)
+
+
+def _label_plan(p: dict) -> Tensor:
+    """One scene's ``label_detections`` from its checked plan: one ndet_label_frames launch, or a frame of -1 when no detection is kept."""
+    from .boxes import box_frames
+    if len(p["kept"]) == 0:
+        return torch.full(p["frames"].shape, -1, dtype=torch.int16, device=p["frames"].device)
+    return label_frames(p["frames"], p["intrinsic"], p["poses"], box_frames(p["boxes"]), p["window"], p["stride"])
+
+
+def _check_thickness(thickness, what: str) -> int:
+    if isinstance(thickness, bool) or thickness not in (1, 3, 5):
+        raise ValueError(f"{what}: thickness={thickness!r} must be 1, 3 or 5")
+    return int(thickness)
 
 
 def _render_views(coarse, fine, shape, gt_rgb, gt_depth):
@@ -513,6 +611,35 @@ class SceneStream:
                                      self.std, grid)
         out = self.render_frames(extrinsic=meta["lidar2img"]["extrinsic"], stride=stride, n_importance=n_importance)
         return frame_errors(out["frames"], held, out["depth_frames"], held_depth)
+
+    def draw_detections(self, frames: Tensor, result: dict, c2w=None, extrinsic=None, window=None, stride: int = 1, capture: bool = False,
+                        score_thr: float = 0.0, thickness: int = 1, palette=None) -> dict:
+        """The wireframes of one detection result on k camera frames that lie in device memory.  ``result``: what ``detect()[0]`` returns;
+        the detections with ``score >= score_thr`` are kept, handed over by ascending score (boxes.drawing_order: the best one wins every
+        pixel it shares) and coloured by label (``palette`` (c,3) uint8 BGR; None: pipeline.class_palette).  Exactly one of ``c2w`` and
+        ``extrinsic``, the k poses as :meth:`render_frames` takes them.  ``capture=False``: ``frames`` (k,h,w,3) uint8 on the grid
+        ``window`` / ``stride`` of :meth:`render_frames` -- its ``frames`` output fits -- with the scene meta's scaled intrinsics;
+        ``capture=True``: ``frames`` (k,Hs,Ws,3) at ``ori_shape`` with the meta's intrinsics unscaled (no window, no stride).  One
+        ndet_project_boxes and one ndet_draw_boxes launch (pipeline.project_boxes, pipeline.draw_boxes), none when nothing is kept.
+        Returns ``dict(frames`` -- new frames, the input is only read -- ``, rect (k,m,4) int32, zrange (k,m,2) float32, kept (m,) int64``:
+        the result's indices in drawing order, which is the numbering of ``rect`` and ``zrange``).  Uses the scene's meta only: no
+        ``keep_views``, no state and no bank is changed.  Bad arguments are a ValueError before any launch, CPU frames a RuntimeError."""
+        thickness = _check_thickness(thickness, "draw_detections")
+        plan = _plan_detections(self.det, self.meta, frames, (3,), torch.uint8, result, c2w, extrinsic, window, stride, capture, score_thr, palette,
+                                "draw_detections")
+        _need_device_frames([plan], "draw_detections")
+        return _draw_plan(plan, thickness)
+
+    def label_detections(self, depth_frames: Tensor, result: dict, c2w=None, extrinsic=None, window=None, stride: int = 1, capture: bool = False,
+                         score_thr: float = 0.0) -> Tensor:
+        """Which kept detection each pixel of k depth frames belongs to: ``(k,h,w)`` int16 in the numbering of :meth:`draw_detections`'
+        ``kept`` (the best detection that holds the pixel's point wins), -1 for none and for a hole.  ``depth_frames`` (k,h,w) uint16
+        millimetres at the grid's size -- :meth:`render_frames`' ``depth_frames``, or with ``capture=True`` a sensor frame whose size is
+        ``ori_shape``'s; the other arguments as in :meth:`draw_detections`.  One ndet_label_frames launch (pipeline.label_frames)."""
+        plan = _plan_detections(self.det, self.meta, depth_frames, (), torch.uint16, result, c2w, extrinsic, window, stride, capture, score_thr, None,
+                                "label_detections")
+        _need_device_frames([plan], "label_detections")
+        return _label_plan(plan)
 
     def volume(self):
         """``(volume (C,X,Y,Z), valid (1,X,Y,Z) int64)`` of the views so far: K2-finish -> sigma-MLP -> K1-finish, what ``extract_volume``
@@ -1021,6 +1148,45 @@ class SceneGroup:
                                   n_importance=n_importance)
         return [frame_errors(out["frames"], held[i * k:(i + 1) * k], out["depth_frames"], None if held_depth is None else held_depth[i * k:(i + 1) * k])
                 for i, out in enumerate(outs)]
+
+    def _plan_detections(self, frames, results, c2w, extrinsic, scenes, trailing, dtype, window, stride, capture, score_thr, palette, what: str):
+        """The checked plans of a grouped ``draw_detections`` / ``label_detections`` call, one per listed scene; nothing is launched."""
+        scenes = ops.listed_scenes(self.n_scenes, scenes)
+        if (c2w is None) == (extrinsic is None):
+            raise ValueError(f"{what} takes exactly one of c2w (camera-to-world) and extrinsic (world-to-camera)")
+        given = c2w if c2w is not None else extrinsic
+        if isinstance(given, (Tensor, np.ndarray)) and given.ndim != 4:
+            raise ValueError(f"{what} takes one LIST of 4 x 4 matrices per listed scene")
+        given = list(given)
+        if isinstance(frames, Tensor) or isinstance(results, dict):
+            raise ValueError(f"{what} takes one frames tensor and one result per listed scene, as lists")
+        frames, results = list(frames), list(results)
+        if not len(frames) == len(results) == len(given) == len(scenes):
+            raise ValueError(f"{what}: {len(frames)} frame tensors, {len(results)} results and {len(given)} camera lists for {len(scenes)} listed scenes")
+        plans = [_plan_detections(self.det, self.metas[s], f, trailing, dtype, r, g if c2w is not None else None, g if c2w is None else None,
+                                  window, stride, capture, score_thr, palette, what) for s, f, r, g in zip(scenes, frames, results, given)]
+        _need_device_frames(plans, what)
+        return plans
+
+    def draw_detections(self, frames, results, c2w=None, extrinsic=None, scenes=None, window=None, stride: int = 1, capture: bool = False,
+                        score_thr: float = 0.0, thickness: int = 1, palette=None):
+        """:meth:`SceneStream.draw_detections` for the listed scenes: ``frames``, ``results`` and exactly one of ``c2w`` / ``extrinsic`` are
+        lists with one entry per listed scene (a frames tensor, a ``detect()`` entry, a list of poses; the counts may differ).  Every scene
+        uses its own meta; the other arguments are the call's.  One ndet_project_boxes and one ndet_draw_boxes launch per scene, as
+        ``pack_frames`` and ``frame_errors`` are per scene.  Returns a list of dicts as the stream's method returns them; a group of one scene
+        is the stream bit for bit.  Bad arguments are refused whole, before any launch."""
+        thickness = _check_thickness(thickness, "draw_detections")
+        plans = self._plan_detections(frames, results, c2w, extrinsic, scenes, (3,), torch.uint8, window, stride, capture, score_thr, palette,
+                                      "draw_detections")
+        return [_draw_plan(p, thickness) for p in plans]
+
+    def label_detections(self, depth_frames, results, c2w=None, extrinsic=None, scenes=None, window=None, stride: int = 1, capture: bool = False,
+                         score_thr: float = 0.0):
+        """:meth:`SceneStream.label_detections` for the listed scenes, the lists as in :meth:`draw_detections`: a list of (k,h,w) int16
+        tensors, one ndet_label_frames launch per scene."""
+        plans = self._plan_detections(depth_frames, results, c2w, extrinsic, scenes, (), torch.uint16, window, stride, capture, score_thr, None,
+                                      "label_detections")
+        return [_label_plan(p) for p in plans]
 
     def _volumes(self, scenes: List[int]):
         """``(volume (n,C,X,Y,Z), valid (n,1,X,Y,Z) int64)`` of the listed scenes: grouped K2-finish -> one sigma-MLP call over all their
