@@ -359,35 +359,65 @@ class SceneState:
         return b
 
 
-def scene_accumulate(state: SceneState, features: Tensor, mapped: Tensor, bias: Tensor, denorm_images: Tensor, points: Tensor,
-                     projection: Tensor, rgb_projection: Tensor, depth_gate: Optional[DepthGate] = None) -> None:
-    """Add one chunk of k views to ``state``: K1's view sum and count of nerfdet.py:164-176 and K2's sums of nerfdet.py:234-253, both without
-    their finish.  Arguments as :func:`backproject_aggregate` (``features`` (k,C,h,w)) and :func:`density_features` (``mapped`` (k,cm,h,w),
-    ``bias``, ``denorm_images`` (k,3,H,W)) for the chunk's views; ``depth_gate`` for the chunk's views (nerfdet.py:404-411).  K1's sums hold
-    the same bits whatever the chunking; K2 runs in launches of at most 128 views."""
-    _need_gpu(features, mapped, bias, denorm_images, points, projection, rgb_projection)
+def _chunk_args(features: Tensor, mapped: Tensor, bias: Tensor, denorm_images: Tensor, projection: Tensor, rgb_projection: Tensor,
+                depth_gate: Optional[DepthGate], c: int, cm: int):
+    """A chunk's arguments as the accumulate entry points take them, for a state of ``c`` and ``cm`` channels: ``(features, mapped`` (both
+    channels-last), ``bias, images`` (float32, unit pixel stride), ``projection, rgb_projection`` (float32, contiguous), ``n_v, h, w, H, W,``
+    the gate block or None, the bytes the launch reads of the chunk)``."""
+    _need_gpu(features, mapped, bias, denorm_images, projection, rgb_projection)
     f = to_channels_last(features)
     m = to_channels_last(mapped)
-    n_v, c, h, w = f.shape
+    n_v, h, w = f.shape[0], f.shape[2], f.shape[3]
     assert m.shape[0] == n_v and m.shape[2:] == f.shape[2:], f"mapped map {tuple(m.shape)} for features {tuple(f.shape)}"
-    assert (c, m.shape[1]) == (state.c, state.cm), f"state for C={state.c}, cm={state.cm}; chunk has {c}, {m.shape[1]}"
-    if not density_packed_ok(0, state.cm, m):       # the packed walk's channel quads need 16-byte aligned rows
+    assert (f.shape[1], m.shape[1]) == (c, cm), f"state for C={c}, cm={cm}; chunk has {f.shape[1]}, {m.shape[1]}"
+    if not density_packed_ok(0, cm, m):       # the packed walk's channel quads need 16-byte aligned rows
         m = to_channels_last(m.contiguous())
     rgb = denorm_images if denorm_images.dtype == torch.float32 else denorm_images.float()
     assert rgb.shape[0] == n_v and rgb.shape[1] == 3
     if rgb.stride(3) != 1:
         rgb = rgb.contiguous()
     hh, ww = rgb.shape[2:]
-    assert points.shape[-3:] == state.grid, f"points {tuple(points.shape)} for a {state.grid} state"
-    points, projection, rgb_projection, bias = _f32c(points), _f32c(projection), _f32c(rgb_projection), _f32c(bias)
+    projection, rgb_projection, bias = _f32c(projection), _f32c(rgb_projection), _f32c(bias)
     assert projection.shape == (n_v, 3, 4) and rgb_projection.shape == (n_v, 3, 4)
-    g = None if depth_gate is None else _gate_arg(depth_gate, n_v, (h, w), (hh, ww))
+    g = _gate_arg(depth_gate, n_v, (h, w), (hh, ww))
+    return f, m, bias, rgb, projection, rgb_projection, n_v, h, w, hh, ww, g, 4 * (n_v * (c * h * w + cm * h * w + 3 * hh * ww))
+
+
+def scene_accumulate(state: SceneState, features: Tensor, mapped: Tensor, bias: Tensor, denorm_images: Tensor, points: Tensor,
+                     projection: Tensor, rgb_projection: Tensor, depth_gate: Optional[DepthGate] = None) -> None:
+    """Add one chunk of k views to ``state``: K1's view sum and count of nerfdet.py:164-176 and K2's sums of nerfdet.py:234-253, both without
+    their finish.  Arguments as :func:`backproject_aggregate` (``features`` (k,C,h,w)) and :func:`density_features` (``mapped`` (k,cm,h,w),
+    ``bias``, ``denorm_images`` (k,3,H,W)) for the chunk's views; ``depth_gate`` for the chunk's views (nerfdet.py:404-411).  K1's sums hold
+    the same bits whatever the chunking; K2 runs in launches of at most 128 views."""
+    _need_gpu(points)
+    f, m, bias, rgb, projection, rgb_projection, n_v, h, w, hh, ww, g, read = _chunk_args(
+        features, mapped, bias, denorm_images, projection, rgb_projection, depth_gate, state.c, state.cm)
+    assert points.shape[-3:] == state.grid, f"points {tuple(points.shape)} for a {state.grid} state"
+    points = _f32c(points)
     blk = state.block()
     trace.span("k_scene_accumulate", lambda: check(_lib.load().ndet_scene_accumulate(
         ctypes.byref(blk), _ptr(f), n_v, h, w, f.stride(0), f.stride(2), _ptr(m), m.stride(0), m.stride(2), _ptr(bias), _ptr(rgb), hh, ww,
         rgb.stride(0), rgb.stride(1), rgb.stride(2), _ptr(points), _ptr(projection), _ptr(rgb_projection), g, _stream(f)), "scene_accumulate"),
-        bytes=4 * (n_v * (c * h * w + state.cm * h * w + 3 * hh * ww)) + 2 * (state.k1_sum.numel() + state.k2_sum.numel()) * 4, kind="hbm")
+        bytes=read + 2 * (state.k1_sum.numel() + state.k2_sum.numel()) * 4, kind="hbm")
     state.n_views += n_v
+
+
+def _density_out(bias: Tensor, cm: int, rows: int, device):
+    """What every density finish starts from: the bias checked against ``cm`` and the ``(rows, 2*(3+cm))`` output."""
+    bias = _f32c(bias)
+    assert bias.numel() == cm
+    return bias, torch.empty((rows, 2 * (3 + cm)), dtype=torch.float32, device=device)
+
+
+def _volume_out(alpha: Optional[Tensor], n: int, grid, c: int, device):
+    """What every volume finish starts from, for n scenes: ``alpha`` flattened and checked (or None), the ``(n,X,Y,Z,C)`` volume buffer and
+    the ``(n,1,X,Y,Z)`` int64 count.  A single-scene finish returns their row 0."""
+    gx, gy, gz = grid
+    if alpha is not None:
+        alpha = _f32c(alpha).reshape(-1)
+        assert alpha.numel() == n * gx * gy * gz
+    return (alpha, torch.empty((n, gx, gy, gz, c), dtype=torch.float32, device=device),
+            torch.empty((n, 1, gx, gy, gz), dtype=torch.int64, device=device))
 
 
 def density_finish(state: SceneState, bias: Tensor) -> Tensor:
@@ -395,9 +425,7 @@ def density_finish(state: SceneState, bias: Tensor) -> Tensor:
     A state filled by one chunk of at most 128 views gives :func:`density_features`'s rows bit for bit."""
     _need_gpu(bias)
     assert state.n_views > 0, "the scene has no views yet"
-    bias = _f32c(bias)
-    assert bias.numel() == state.cm
-    out = torch.empty((state.n_voxels, 2 * (3 + state.cm)), dtype=torch.float32, device=state.k1_sum.device)
+    bias, out = _density_out(bias, state.cm, state.n_voxels, state.k1_sum.device)
     blk = state.block()
     trace.span("k_density_finish", lambda: check(_lib.load().ndet_scene_density_finish(ctypes.byref(blk), _ptr(bias), _ptr(out), _stream(out)),
                                                  "scene_density_finish"), bytes=4 * (state.k2_sum.numel() + out.numel()), kind="hbm")
@@ -408,18 +436,12 @@ def volume_finish(state: SceneState, alpha: Optional[Tensor] = None) -> Tuple[Te
     """K1's epilogue over ``state`` (nerfdet.py:175-176 and, with ``alpha``, 259-261): ``(volume (C,X,Y,Z) with (X,Y,Z,C) memory, count
     (1,X,Y,Z) int64)``, bit for bit what :func:`backproject_aggregate` returns over all the state's views; ``state`` is not changed."""
     _need_gpu(alpha)
-    dev = state.k1_sum.device
-    if alpha is not None:
-        alpha = _f32c(alpha).reshape(-1)
-        assert alpha.numel() == state.n_voxels
-    gx, gy, gz = state.grid
-    buf = torch.empty((gx, gy, gz, state.c), dtype=torch.float32, device=dev)
-    count = torch.empty((1, gx, gy, gz), dtype=torch.int64, device=dev)
+    alpha, buf, count = _volume_out(alpha, 1, state.grid, state.c, state.k1_sum.device)
     blk = state.block()
     trace.span("k_volume_finish", lambda: check(_lib.load().ndet_scene_volume_finish(ctypes.byref(blk), _ptr(alpha), _ptr(buf), _ptr(count),
                                                                                      _stream(buf)), "scene_volume_finish"),
                bytes=8 * state.k1_sum.numel() + 12 * state.n_voxels, kind="hbm")
-    return buf.permute(3, 0, 1, 2), count
+    return buf[0].permute(3, 0, 1, 2), count[0]
 
 
 RING_MAX = 64   # segments one ring finish reads (include/nerfdet_hip.h)
@@ -448,9 +470,7 @@ def density_finish_ring(states: Sequence[SceneState], bias: Tensor) -> Tensor:
     _need_gpu(bias)
     states, arr = _ring_blocks(states)
     s0 = states[0]
-    bias = _f32c(bias)
-    assert bias.numel() == s0.cm
-    out = torch.empty((s0.n_voxels, 2 * (3 + s0.cm)), dtype=torch.float32, device=s0.k1_sum.device)
+    bias, out = _density_out(bias, s0.cm, s0.n_voxels, s0.k1_sum.device)
     read = sum(s.k2_sum.numel() + s.k2_count.numel() for s in states)
     trace.span("k_density_finish_ring", lambda: check(_lib.load().ndet_scene_density_finish_ring(arr, len(states), _ptr(bias), _ptr(out),
                                                                                                 _stream(out)), "scene_density_finish_ring"),
@@ -465,19 +485,13 @@ def volume_finish_ring(states: Sequence[SceneState], alpha: Optional[Tensor] = N
     _need_gpu(alpha)
     states, arr = _ring_blocks(states)
     s0 = states[0]
-    dev = s0.k1_sum.device
-    if alpha is not None:
-        alpha = _f32c(alpha).reshape(-1)
-        assert alpha.numel() == s0.n_voxels
-    gx, gy, gz = s0.grid
-    buf = torch.empty((gx, gy, gz, s0.c), dtype=torch.float32, device=dev)
-    count = torch.empty((1, gx, gy, gz), dtype=torch.int64, device=dev)
+    alpha, buf, count = _volume_out(alpha, 1, s0.grid, s0.c, s0.k1_sum.device)
     read = sum(s.k1_sum.numel() + s.k1_count.numel() for s in states)
     trace.span("k_volume_finish_ring", lambda: check(_lib.load().ndet_scene_volume_finish_ring(arr, len(states), _ptr(alpha), _ptr(buf),
                                                                                               _ptr(count), _stream(buf)),
                                                     "scene_volume_finish_ring"),
                bytes=4 * (read + buf.numel()) + (12 if alpha is not None else 8) * s0.n_voxels, kind="hbm")
-    return buf.permute(3, 0, 1, 2), count
+    return buf[0].permute(3, 0, 1, 2), count[0]
 
 
 # --------------------------------------------------------------------------------------------
@@ -520,6 +534,60 @@ def compute_projection_group(img_metas, strides, device=None) -> Tensor:
     return _upload_async(proj, device) if torch.device(device).type == "cuda" else proj.to(device)
 
 
+def _group_points(points: Sequence[Tensor], grid, on_gpu: bool) -> list:
+    """The ``(3,X,Y,Z)`` point lattices of a group's 1 .. GROUP_MAX scenes, checked against ``grid``, as contiguous float32."""
+    points = list(points)
+    if not 1 <= len(points) <= GROUP_MAX:
+        raise ValueError(f"a scene group holds 1 to {GROUP_MAX} scenes, got {len(points)}")
+    for p in points:
+        if on_gpu:
+            _need_gpu(p)
+        assert tuple(p.shape[-3:]) == grid and p.shape[0] == 3, f"points {tuple(p.shape)} for a {grid} state"
+    return [_f32c(p) for p in points]
+
+
+def _fill_slot(row, st: SceneState, p: Tensor) -> None:
+    """One NdetSceneSlot row: the state's four tensors and its scene's points.  The grouped kernels take the pitches from the group's block
+    (:func:`_group_block`) and walk the rows in quads."""
+    assert (st.k1_sum.stride(0), st.k2_sum.stride(0)) == (st.c, 3 * (st.cm + 4))
+    assert (st.k1_sum.data_ptr() | st.k2_sum.data_ptr()) % 16 == 0 and st.k1_count.data_ptr() % 4 == 0 and st.k2_count.data_ptr() % 8 == 0 \
+        and p.data_ptr() % 4 == 0, "state rows must be 16-byte aligned"
+    row.k1_sum, row.k1_count, row.k2_sum, row.k2_count = st.k1_sum.data_ptr(), st.k1_count.data_ptr(), st.k2_sum.data_ptr(), st.k2_count.data_ptr()
+    row.points = p.data_ptr()
+
+
+def _upload_table(rows, device) -> Tensor:
+    """A host array of table rows as bytes on ``device``, uploaded asynchronously on the current stream."""
+    host = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8)
+    return _upload_async(host, device) if device.type == "cuda" else host.clone()
+
+
+def _group_block(n_slots: int, n_voxels: int, c: int, cm: int, table: Tensor) -> "_lib.NdetSceneGroup":
+    """The C ABI's NdetSceneGroup for a table of ``n_slots`` states of ``c`` and ``cm`` channels."""
+    g = _lib.NdetSceneGroup()
+    g.size = ctypes.sizeof(_lib.NdetSceneGroup)
+    g.n_slots, g.N, g.C, g.cm = n_slots, n_voxels, c, cm
+    g.k1_pitch, g.k2_pitch, g.table = c, 3 * (cm + 4), table.data_ptr()
+    return g
+
+
+def _accumulate_group(front, n: int, s0: SceneState, features: Tensor, mapped: Tensor, bias: Tensor, denorm_images: Tensor,
+                      projection: Tensor, rgb_projection: Tensor, depth_gate: Optional[DepthGate]) -> int:
+    """The launch of ndet_scene_accumulate_group for n listed scenes whose states are like ``s0``: the chunk is checked, then ``front()``
+    gives ``(block, selection, table tensor or None)`` -- the table is held until the launches are queued.  Returns k, the views a scene."""
+    f, m, bias, rgb, projection, rgb_projection, n_v, h, w, hh, ww, g, read = _chunk_args(
+        features, mapped, bias, denorm_images, projection, rgb_projection, depth_gate, s0.c, s0.cm)
+    if n_v % n or not 1 <= n_v // n <= GROUP_VIEWS_MAX:
+        raise ValueError(f"{n_v} views for {n} scenes: every listed scene brings the same 1 .. {GROUP_VIEWS_MAX} views")
+    k = n_v // n
+    blk, sel, table = front()
+    trace.span("k_scene_accumulate_group", lambda: check(_lib.load().ndet_scene_accumulate_group(
+        ctypes.byref(blk), ctypes.byref(sel), k, _ptr(f), h, w, f.stride(0), f.stride(2), _ptr(m), m.stride(0), m.stride(2), _ptr(bias), _ptr(rgb),
+        hh, ww, rgb.stride(0), rgb.stride(1), rgb.stride(2), _ptr(projection), _ptr(rgb_projection), g, _stream(f)), "scene_accumulate_group"),
+        bytes=read + 2 * n * (s0.k1_sum.numel() + s0.k2_sum.numel()) * 4, kind="hbm")
+    return k
+
+
 class SceneGroupState:
     """The states of S scenes (1 .. 64) that share grid, C and cm, one :class:`SceneState` and one ``(3,X,Y,Z)`` point lattice per scene, and
     the device table the grouped kernels find them through: one 64-byte NdetSceneSlot per scene, built on the host once and uploaded
@@ -528,28 +596,14 @@ class SceneGroupState:
     make the other stream wait for it first."""
 
     def __init__(self, n_voxels, c: int, cm: int, points: Sequence[Tensor], device):
-        points = list(points)
-        if not 1 <= len(points) <= GROUP_MAX:
-            raise ValueError(f"a scene group holds 1 to {GROUP_MAX} scenes, got {len(points)}")
-        self.states = [SceneState(n_voxels, c, cm, device) for _ in points]
-        s0 = self.states[0]
-        self.grid, self.c, self.cm = s0.grid, s0.c, s0.cm
-        self.points = []
-        for p in points:
-            _need_gpu(p)
-            assert tuple(p.shape[-3:]) == self.grid and p.shape[0] == 3, f"points {tuple(p.shape)} for a {self.grid} state"
-            self.points.append(_f32c(p))
-        rows = (_lib.NdetSceneSlot * len(points))()
+        self.grid = tuple(int(v) for v in n_voxels)
+        self.points = _group_points(points, self.grid, True)
+        self.states = [SceneState(n_voxels, c, cm, device) for _ in self.points]
+        self.c, self.cm, self.device = self.states[0].c, self.states[0].cm, torch.device(device)
+        rows = (_lib.NdetSceneSlot * len(self.points))()
         for row, st, p in zip(rows, self.states, self.points):
-            assert (st.k1_sum.stride(0), st.k2_sum.stride(0)) == (s0.k1_sum.stride(0), s0.k2_sum.stride(0))
-            assert (st.k1_sum.data_ptr() | st.k2_sum.data_ptr()) % 16 == 0 and st.k1_count.data_ptr() % 4 == 0 and st.k2_count.data_ptr() % 8 == 0 \
-                and p.data_ptr() % 4 == 0, "state rows must be 16-byte aligned"
-            row.k1_sum, row.k1_count, row.k2_sum, row.k2_count = st.k1_sum.data_ptr(), st.k1_count.data_ptr(), st.k2_sum.data_ptr(), st.k2_count.data_ptr()
-            row.points = p.data_ptr()
-        host = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8)
-        dev = torch.device(device)
-        self.table = _upload_async(host, dev) if dev.type == "cuda" else host.clone()
-        self.device = dev
+            _fill_slot(row, st, p)
+        self.table = _upload_table(rows, self.device)
 
     def __len__(self) -> int:
         return len(self.states)
@@ -567,12 +621,7 @@ class SceneGroupState:
         return listed_scenes(len(self.states), scenes)
 
     def block(self) -> "_lib.NdetSceneGroup":
-        s0 = self.states[0]
-        g = _lib.NdetSceneGroup()
-        g.size = ctypes.sizeof(_lib.NdetSceneGroup)
-        g.n_slots, g.N, g.C, g.cm = len(self.states), s0.n_voxels, s0.c, s0.cm
-        g.k1_pitch, g.k2_pitch, g.table = s0.k1_sum.stride(0), s0.k2_sum.stride(0), self.table.data_ptr()
-        return g
+        return _group_block(len(self.states), self.n_voxels, self.c, self.cm, self.table)
 
     def sel(self, scenes) -> "_lib.NdetGroupSel":
         """The C ABI's selection block for the (checked) scene list, with the scenes' view totals."""
@@ -593,31 +642,8 @@ def scene_accumulate_group(group: SceneGroupState, scenes, features: Tensor, map
     other scenes, the subset or its order."""
     _need_gpu(features, mapped, bias, denorm_images, projection, rgb_projection)
     scenes = group.listed(scenes)
-    n = len(scenes)
-    f = to_channels_last(features)
-    m = to_channels_last(mapped)
-    n_v, c, h, w = f.shape
-    if n_v % n or not 1 <= n_v // n <= GROUP_VIEWS_MAX:
-        raise ValueError(f"{n_v} views for {n} scenes: every listed scene brings the same 1 .. {GROUP_VIEWS_MAX} views")
-    k = n_v // n
-    assert m.shape[0] == n_v and m.shape[2:] == f.shape[2:], f"mapped map {tuple(m.shape)} for features {tuple(f.shape)}"
-    assert (c, m.shape[1]) == (group.c, group.cm), f"group for C={group.c}, cm={group.cm}; chunk has {c}, {m.shape[1]}"
-    if not density_packed_ok(0, group.cm, m):       # the packed walk's channel quads need 16-byte aligned rows
-        m = to_channels_last(m.contiguous())
-    rgb = denorm_images if denorm_images.dtype == torch.float32 else denorm_images.float()
-    assert rgb.shape[0] == n_v and rgb.shape[1] == 3
-    if rgb.stride(3) != 1:
-        rgb = rgb.contiguous()
-    hh, ww = rgb.shape[2:]
-    projection, rgb_projection, bias = _f32c(projection), _f32c(rgb_projection), _f32c(bias)
-    assert projection.shape == (n_v, 3, 4) and rgb_projection.shape == (n_v, 3, 4)
-    g = None if depth_gate is None else _gate_arg(depth_gate, n_v, (h, w), (hh, ww))
-    blk, sel = group.block(), group.sel(scenes)
-    s0 = group.states[0]
-    trace.span("k_scene_accumulate_group", lambda: check(_lib.load().ndet_scene_accumulate_group(
-        ctypes.byref(blk), ctypes.byref(sel), k, _ptr(f), h, w, f.stride(0), f.stride(2), _ptr(m), m.stride(0), m.stride(2), _ptr(bias), _ptr(rgb),
-        hh, ww, rgb.stride(0), rgb.stride(1), rgb.stride(2), _ptr(projection), _ptr(rgb_projection), g, _stream(f)), "scene_accumulate_group"),
-        bytes=4 * (n_v * (c * h * w + group.cm * h * w + 3 * hh * ww)) + 2 * n * (s0.k1_sum.numel() + s0.k2_sum.numel()) * 4, kind="hbm")
+    k = _accumulate_group(lambda: (group.block(), group.sel(scenes), None), len(scenes), group.states[0], features, mapped, bias, denorm_images,
+                          projection, rgb_projection, depth_gate)
     for s in scenes:
         group.states[s].n_views += k
 
@@ -635,10 +661,8 @@ def density_finish_group(group: SceneGroupState, bias: Tensor, scenes=None) -> T
     ``i N + v``, each scene finished over its own view total; bit for bit :func:`density_finish`'s rows per scene.  No state is changed."""
     _need_gpu(bias)
     scenes, blk, sel = _group_finish_args(group, scenes)
-    bias = _f32c(bias)
-    assert bias.numel() == group.cm
     s0 = group.states[0]
-    out = torch.empty((len(scenes) * s0.n_voxels, 2 * (3 + group.cm)), dtype=torch.float32, device=s0.k1_sum.device)
+    bias, out = _density_out(bias, group.cm, len(scenes) * s0.n_voxels, s0.k1_sum.device)
     trace.span("k_density_finish_group", lambda: check(_lib.load().ndet_scene_density_finish_group(
         ctypes.byref(blk), ctypes.byref(sel), _ptr(bias), _ptr(out), _stream(out)), "scene_density_finish_group"),
         bytes=4 * (len(scenes) * s0.k2_sum.numel() + out.numel()), kind="hbm")
@@ -652,13 +676,7 @@ def volume_finish_group(group: SceneGroupState, alpha: Optional[Tensor] = None, 
     _need_gpu(alpha)
     scenes, blk, sel = _group_finish_args(group, scenes)
     n, s0 = len(scenes), group.states[0]
-    dev = s0.k1_sum.device
-    if alpha is not None:
-        alpha = _f32c(alpha).reshape(-1)
-        assert alpha.numel() == n * s0.n_voxels
-    gx, gy, gz = group.grid
-    buf = torch.empty((n, gx, gy, gz, group.c), dtype=torch.float32, device=dev)
-    count = torch.empty((n, 1, gx, gy, gz), dtype=torch.int64, device=dev)
+    alpha, buf, count = _volume_out(alpha, n, group.grid, group.c, s0.k1_sum.device)
     trace.span("k_volume_finish_group", lambda: check(_lib.load().ndet_scene_volume_finish_group(
         ctypes.byref(blk), ctypes.byref(sel), _ptr(alpha), _ptr(buf), _ptr(count), _stream(buf)), "scene_volume_finish_group"),
         bytes=n * (8 * s0.k1_sum.numel() + 12 * s0.n_voxels), kind="hbm")
@@ -690,20 +708,12 @@ class SceneGroupRingState:
 
     def __init__(self, n_voxels, c: int, cm: int, points: Sequence[Tensor], window: int, device):
         self.window = check_window(window)
-        points = list(points)
-        if not 1 <= len(points) <= GROUP_MAX:
-            raise ValueError(f"a scene group holds 1 to {GROUP_MAX} scenes, got {len(points)}")
-        self.grid = tuple(int(v) for v in n_voxels)
+        self.grid, self.device = tuple(int(v) for v in n_voxels), torch.device(device)
+        self.points = _group_points(points, self.grid, self.device.type == "cuda")
         assert c % 4 == 0 and cm % 4 == 0, f"streaming needs C and cm in multiples of 4 (got {c}, {cm})"
-        self.c, self.cm, self.device = int(c), int(cm), torch.device(device)
-        self.points = []
-        for p in points:
-            if self.device.type == "cuda":
-                _need_gpu(p)
-            assert tuple(p.shape[-3:]) == self.grid and p.shape[0] == 3, f"points {tuple(p.shape)} for a {self.grid} state"
-            self.points.append(_f32c(p))
-        self.segs = [[] for _ in points]
-        self.spare = [[] for _ in points]
+        self.c, self.cm = int(c), int(cm)
+        self.segs = [[] for _ in self.points]
+        self.spare = [[] for _ in self.points]
         self.states = []            # every state of the pool; a state's pool row is its index here (``state.row``)
         self.owner = []             # the scene of every pool row
         self._table = None          # the device table, or None when a state has been allocated since the last upload
@@ -794,37 +804,20 @@ class SceneGroupRingState:
             raise
         self.push(scenes, states)
 
-    def _upload(self, rows) -> Tensor:
-        host = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8)
-        return _upload_async(host, self.device) if self.device.type == "cuda" else host.clone()
-
-    def _slot(self, row, st: SceneState, p: Tensor) -> None:
-        assert (st.k1_sum.data_ptr() | st.k2_sum.data_ptr()) % 16 == 0 and st.k1_count.data_ptr() % 4 == 0 and st.k2_count.data_ptr() % 8 == 0 \
-            and p.data_ptr() % 4 == 0, "state rows must be 16-byte aligned"
-        row.k1_sum, row.k1_count, row.k2_sum, row.k2_count = st.k1_sum.data_ptr(), st.k1_count.data_ptr(), st.k2_sum.data_ptr(), st.k2_count.data_ptr()
-        row.points = p.data_ptr()
-
     def table(self) -> Tensor:
         """The pool table on the device, uploaded when a state has been allocated since the last call; rows beyond the states allocated
         are null and beyond ``n_slots``."""
         if self._table is None:
             rows = (_lib.NdetSceneSlot * (len(self.segs) * (self.window + 1)))()
             for st, s in zip(self.states, self.owner):
-                self._slot(rows[st.row], st, self.points[s])
-            self._table = self._upload(rows)
+                _fill_slot(rows[st.row], st, self.points[s])
+            self._table = _upload_table(rows, self.device)
         return self._table
-
-    def _block(self, n_slots: int, table: Tensor) -> "_lib.NdetSceneGroup":
-        g = _lib.NdetSceneGroup()
-        g.size = ctypes.sizeof(_lib.NdetSceneGroup)
-        g.n_slots, g.N, g.C, g.cm = n_slots, self.n_voxels, self.c, self.cm
-        g.k1_pitch, g.k2_pitch, g.table = self.c, 3 * (self.cm + 4), table.data_ptr()
-        return g
 
     def block(self):
         """``(NdetSceneGroup block of the pool, the table tensor it points to)``."""
         table = self.table()
-        return self._block(len(self.states), table), table
+        return _group_block(len(self.states), self.n_voxels, self.c, self.cm, table), table
 
     def front(self, scenes, states):
         """A call's front table -- one row per listed scene, pointing at the state it fills and its scene's points -- with the block and the
@@ -834,10 +827,10 @@ class SceneGroupRingState:
         sel.size, sel.n = ctypes.sizeof(_lib.NdetGroupSel), len(scenes)
         for i, (s, st) in enumerate(zip(scenes, states)):
             assert st.n_views == 0, "a front state must be empty"
-            self._slot(rows[i], st, self.points[s])
+            _fill_slot(rows[i], st, self.points[s])
             sel.slot[i], sel.n_views[i] = i, 0
-        table = self._upload(rows)
-        return self._block(len(scenes), table), sel, table
+        table = _upload_table(rows, self.device)
+        return _group_block(len(scenes), self.n_voxels, self.c, self.cm, table), sel, table
 
     def ring_sel(self, scenes):
         """The grouped ring finishes' arguments for the (checked) scene list: ``(NdetGroupRingSel, segment lists on the host, on the
@@ -870,33 +863,9 @@ def scene_accumulate_group_ring(pool: SceneGroupRingState, scenes, features: Ten
                                                                           rgb_projection, depth_gate=depth_gate, states=front))
         return
     _need_gpu(features, mapped, bias, denorm_images, projection, rgb_projection)
-    n = len(scenes)
-    assert len(states) == n
-    f = to_channels_last(features)
-    m = to_channels_last(mapped)
-    n_v, c, h, w = f.shape
-    if n_v % n or not 1 <= n_v // n <= GROUP_VIEWS_MAX:
-        raise ValueError(f"{n_v} views for {n} scenes: every listed scene brings the same 1 .. {GROUP_VIEWS_MAX} views")
-    k = n_v // n
-    assert m.shape[0] == n_v and m.shape[2:] == f.shape[2:], f"mapped map {tuple(m.shape)} for features {tuple(f.shape)}"
-    assert (c, m.shape[1]) == (pool.c, pool.cm), f"group for C={pool.c}, cm={pool.cm}; chunk has {c}, {m.shape[1]}"
-    if not density_packed_ok(0, pool.cm, m):       # the packed walk's channel quads need 16-byte aligned rows
-        m = to_channels_last(m.contiguous())
-    rgb = denorm_images if denorm_images.dtype == torch.float32 else denorm_images.float()
-    assert rgb.shape[0] == n_v and rgb.shape[1] == 3
-    if rgb.stride(3) != 1:
-        rgb = rgb.contiguous()
-    hh, ww = rgb.shape[2:]
-    projection, rgb_projection, bias = _f32c(projection), _f32c(rgb_projection), _f32c(bias)
-    assert projection.shape == (n_v, 3, 4) and rgb_projection.shape == (n_v, 3, 4)
-    g = None if depth_gate is None else _gate_arg(depth_gate, n_v, (h, w), (hh, ww))
-    blk, sel, table = pool.front(scenes, states)
-    s0 = states[0]
-    trace.span("k_scene_accumulate_group", lambda: check(_lib.load().ndet_scene_accumulate_group(
-        ctypes.byref(blk), ctypes.byref(sel), k, _ptr(f), h, w, f.stride(0), f.stride(2), _ptr(m), m.stride(0), m.stride(2), _ptr(bias), _ptr(rgb),
-        hh, ww, rgb.stride(0), rgb.stride(1), rgb.stride(2), _ptr(projection), _ptr(rgb_projection), g, _stream(f)), "scene_accumulate_group"),
-        bytes=4 * (n_v * (c * h * w + pool.cm * h * w + 3 * hh * ww)) + 2 * n * (s0.k1_sum.numel() + s0.k2_sum.numel()) * 4, kind="hbm")
-    del table       # held until the launches were queued
+    assert len(states) == len(scenes)
+    k = _accumulate_group(lambda: pool.front(scenes, states), len(scenes), states[0], features, mapped, bias, denorm_images, projection,
+                          rgb_projection, depth_gate)
     for st in states:
         st.n_views = k
 
@@ -917,10 +886,7 @@ def density_finish_group_ring(pool: SceneGroupRingState, bias: Tensor, scenes=No
     upper bound as in :func:`density_finish_ring`."""
     _need_gpu(bias)
     scenes, blk, table, sel, segs_host, segs_dev = _group_ring_finish_args(pool, scenes)
-    bias = _f32c(bias)
-    assert bias.numel() == pool.cm
-    n_vox = pool.n_voxels
-    out = torch.empty((len(scenes) * n_vox, 2 * (3 + pool.cm)), dtype=torch.float32, device=pool.device)
+    bias, out = _density_out(bias, pool.cm, len(scenes) * pool.n_voxels, pool.device)
     read = sum(st.k2_sum.numel() + st.k2_count.numel() for s in scenes for st in pool.segs[s])
     trace.span("k_density_finish_group_ring", lambda: check(_lib.load().ndet_scene_density_finish_group_ring(
         ctypes.byref(blk), ctypes.byref(sel), segs_host.data_ptr(), _ptr(segs_dev), _ptr(bias), _ptr(out), _stream(out)),
@@ -936,12 +902,7 @@ def volume_finish_group_ring(pool: SceneGroupRingState, alpha: Optional[Tensor] 
     _need_gpu(alpha)
     scenes, blk, table, sel, segs_host, segs_dev = _group_ring_finish_args(pool, scenes)
     n, n_vox = len(scenes), pool.n_voxels
-    if alpha is not None:
-        alpha = _f32c(alpha).reshape(-1)
-        assert alpha.numel() == n * n_vox
-    gx, gy, gz = pool.grid
-    buf = torch.empty((n, gx, gy, gz, pool.c), dtype=torch.float32, device=pool.device)
-    count = torch.empty((n, 1, gx, gy, gz), dtype=torch.int64, device=pool.device)
+    alpha, buf, count = _volume_out(alpha, n, pool.grid, pool.c, pool.device)
     read = sum(st.k1_sum.numel() + st.k1_count.numel() for s in scenes for st in pool.segs[s])
     trace.span("k_volume_finish_group_ring", lambda: check(_lib.load().ndet_scene_volume_finish_group_ring(
         ctypes.byref(blk), ctypes.byref(sel), segs_host.data_ptr(), _ptr(segs_dev), _ptr(alpha), _ptr(buf), _ptr(count), _stream(buf)),

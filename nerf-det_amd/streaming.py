@@ -314,6 +314,192 @@ def _render_views(coarse, fine, shape, gt_rgb, gt_depth):
     return out
 
 
+# ---- what SceneStream and SceneGroup share: a stream is a group of one scene bit for bit because both run these bodies ----
+def _chunk_features(det, lin, img: Tensor, img_shape):
+    """The backbone and FPN on a call's views under the range guard of the fp16-pair arithmetic: the guard word is cleared, read back once
+    after the backbone (a synchronisation), and a tripped call is redone on bf16x3 (``conv3d.guard_trips`` counts it).  Returns ``(feat,
+    mapped, stride)``: the feature map and its ``lin`` image (the FPN's own when it made one), channels-last, cropped to ``img_shape // stride``."""
+    def features():
+        x, _, stride = det.extract_2d(img)
+        return x, getattr(x, "_ndet_feature_2d", None), stride
+
+    guarded = conv3d.ARITHMETIC == "f16x2" and img.is_cuda
+    if guarded:
+        conv3d.guard_begin(img.device)
+    x, f2d, stride = features()
+    if guarded and conv3d.guard_tripped(img.device):
+        conv3d.guard_trips += 1
+        prev = conv3d.set_arithmetic("bf16x3")
+        try:
+            x, f2d, stride = features()
+        finally:
+            conv3d.set_arithmetic(prev)
+    h, w = img_shape[0] // stride, img_shape[1] // stride
+    feat = ops.to_channels_last(x)[:, :, :h, :w]
+    if f2d is not None:
+        mapped = f2d[:, :, :h, :w]
+    elif lin.in_features % 32 == 0:
+        mapped = map_features_2d_hip(feat, lin)
+    else:
+        mapped = map_features_2d(feat, lin.weight, lin.bias)
+    return feat, mapped, stride
+
+
+def _prepared_frames(frames: Tensor, depth_frames, depth, img_shape, img_scale, pad_size, mean, std):
+    """``add_frames``' device work for the (n, k) frames of a call: ONE ndet_resize_normalize_views launch over all of them and, with
+    ``depth_frames`` (n, k, Hd, Wd), ONE ndet_depth_frames launch.  Returns ``(img, denorm_images, depth)`` shaped (n, k, ...) as
+    ``add_views`` takes them; without ``depth_frames`` the call's ``depth`` passes through."""
+    rows = lambda t: t.reshape((-1,) + tuple(t.shape[2:]))
+    chunks = lambda t: t.view(tuple(frames.shape[:2]) + tuple(t.shape[1:]))
+    img, denorm = prepare_frames(rows(frames), img_scale, pad_size, mean, std)
+    if depth_frames is not None:
+        depth = chunks(prepare_depth_frames(rows(depth_frames), img_shape[:2]))
+    return chunks(img), chunks(denorm), depth
+
+
+def _score_held_out(first: dict, scene_metas, frames: Tensor, chunk_metas, depth_frames, stride, n_importance, mean, std):
+    """Everything ``score_frames`` checks of its own arguments, before any launch, and then its held-out side (:func:`_held_out`) for the
+    n listed scenes' rows of k frames at once: ``(held (n k, h, w, 3), held depth (n k, h, w) or None, k, n_importance)``.  ``first``: the
+    meta that says what becomes of a frame (a group's scenes share it)."""
+    n = len(scene_metas)
+    img_scale, pad_size = check_frames_meta(first, frames, n)
+    if len(chunk_metas) != n:
+        raise ValueError(f"score_frames: {len(chunk_metas)} chunk metas for {n} listed scenes")
+    k = frames.shape[1]
+    for scene_meta, m in zip(scene_metas, chunk_metas):
+        check_chunk_meta(scene_meta, m, k)
+    check_depth_frames(depth_frames, None, n, k)
+    n_importance = _check_n_importance(n_importance)
+    grid = _frame_grid(first, None, stride)
+    rows = lambda t: t.reshape((n * k,) + tuple(t.shape[2:]))
+    held, held_depth = _held_out(rows(frames), None if depth_frames is None else rows(depth_frames), first, img_scale, pad_size, mean, std, grid)
+    return held, held_depth, k, n_importance
+
+
+def _camera_lists(c2w, extrinsic, what: str) -> list:
+    """The cameras of a grouped call: exactly one of ``c2w`` and ``extrinsic``, one list of 4 x 4 matrices per listed scene (else ValueError);
+    returns the one given, as a list."""
+    if (c2w is None) == (extrinsic is None):
+        raise ValueError(f"{what} takes exactly one of c2w (camera-to-world) and extrinsic (world-to-camera)")
+    given = c2w if c2w is not None else extrinsic
+    if isinstance(given, (Tensor, np.ndarray)) and given.ndim != 4:
+        raise ValueError(f"{what} takes one LIST of 4 x 4 matrices per listed scene")
+    return list(given)
+
+
+def _unpack_ray_batch(ray_batch: dict):
+    """A ray batch's target views as flat rays (render_ray.py:452-468): ``(ray_o (R,3), ray_d (R,3), (T, h, w), gt_rgb (R,3), gt_depth (R,1)
+    or None)``."""
+    ray_o, ray_d, gt_rgb, gt_depth = ray_batch["ray_o"], ray_batch["ray_d"], ray_batch["gt_rgb"], ray_batch["gt_depth"]
+    nerf_size = ray_batch["nerf_sizes"][0]
+    view_num = ray_o.shape[1]
+    hh, ww = int(nerf_size[0][0]), int(nerf_size[0][1])
+    ray_o, ray_d, gt_rgb = ray_o.view(-1, 3), ray_d.view(-1, 3), gt_rgb.view(-1, 3)
+    gt_depth = gt_depth.view(-1, 1) if len(gt_depth) != 0 else None
+    assert view_num * hh * ww == ray_o.shape[0]  # render_ray.py:468
+    return ray_o, ray_d, (view_num, hh, ww), gt_rgb, gt_depth
+
+
+def _render_step(det) -> int:
+    """The rays per pass of ``render``: the passes of rays.render_rays."""
+    from . import rays
+    return det.N_rand * max(1, rays.RENDER_TESTING_RAYS // det.N_rand)
+
+
+def _one_bank_stats(xyz_list, banks):
+    """rays.bank_group_stats for ONE bank through the single-bank sampler (k_ray_stats_bank): the same flat ``(globalfeat, pixel_mask,
+    view_count, points)``, all views of its outputs and of the points -- nothing is copied."""
+    from . import rays
+    (xyz,), (bank,) = xyz_list, banks
+    glob, pm, vc = rays.ray_view_stats_bank(xyz, bank)
+    return glob.view(-1, glob.shape[-1]), pm.view(-1), vc.view(-1), xyz.reshape(-1, 3)
+
+
+def _render_passes(det, banks, ray_os, ray_ds, step: int, batched: bool, n_importance: int, sampler):
+    """render_ray.py:250-327 (``det=True``, mode 'image') over one bank per scene, at most ``step`` rays per scene and pass: per scene
+    ``((rgb, depth, mask) of the coarse pass, the same of the fine pass or None)``.  A pass samples every scene that still has rays, runs
+    ONE ``sampler`` launch over their banks (rays.bank_group_stats, or :func:`_one_bank_stats` for a stream's one bank) and then the MLP
+    and the compositing per scene, or with ``batched`` once over all the pass's samples.  With ``n_importance > 0`` ONE k_importance_merge
+    launch over all the pass's rays then gives the fine samples (the kernel is per ray), and the same three steps run over them."""
+    from . import rays
+    n = len(banks)
+    batched = bool(batched) and n > 1 and conv3d.ARITHMETIC != "f32"
+    outs = [([], [], []) for _ in range(n)]
+    fines = [([], [], []) for _ in range(n)]
+
+    def shade(live, accs, dirs, pts, zs, ss, want_weights):
+        """Sampler, MLP and compositing of one pass over ``ss`` samples a ray; appends to ``accs``, returns the rays' weights (R, ss)."""
+        mlp = det.nerf_mlp if ss == det.N_samples else (lambda p, d, g: rays.fine_mlp(det.nerf_mlp, p, d, g))
+        glob, pm, _, all_pts = sampler(pts, [banks[i] for i in live])
+        counts = [p.shape[0] for p in pts]
+        if batched and len(live) > 1:
+            # one MLP call and one compositing call over the pass: the scenes share linear_rows' per-tensor fp16-pair scales
+            rr = sum(counts)
+            rgb_pts, density_pts = mlp(all_pts.view(rr, ss, 3), torch.cat(dirs, dim=0), glob.view(rr, ss, -1))
+            out = rays.raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), torch.cat(zs, dim=0), pm.view(rr, ss))
+            at = 0
+            for i, c in zip(live, counts):
+                for acc, key in zip(accs[i], ("rgb", "depth", "mask")):
+                    acc.append(out[key][at:at + c])
+                at += c
+            return out["weights"]
+        at, wts = 0, []
+        for i, c, d, p, z in zip(live, counts, dirs, pts, zs):
+            rows = slice(at * ss, (at + c) * ss)
+            rgb_pts, density_pts = mlp(p, d, glob[rows].view(c, ss, -1))
+            out = rays.raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), z, pm[rows].view(c, ss))
+            for acc, key in zip(accs[i], ("rgb", "depth", "mask")):
+                acc.append(out[key])
+            wts.append(out["weights"])
+            at += c
+        return (wts[0] if len(wts) == 1 else torch.cat(wts, dim=0)) if want_weights else None
+
+    with torch.no_grad():
+        for i0 in range(0, max(o.shape[0] for o in ray_os), step):
+            live = [i for i in range(n) if ray_os[i].shape[0] > i0]
+            origins, dirs, pts, zs = [], [], [], []
+            for i in live:
+                o, d = ray_os[i][i0:i0 + step], ray_ds[i][i0:i0 + step]
+                p, z = rays.sample_along_camera_ray(o, d, det.near_far_range, det.N_samples, det=True)
+                origins.append(o)
+                dirs.append(d)
+                pts.append(p)
+                zs.append(z)
+            weights = shade(live, outs, dirs, pts, zs, det.N_samples, n_importance > 0)
+            if n_importance > 0:
+                one = len(live) == 1
+                pts_f, z_f, _ = rays.importance_merge(zs[0] if one else torch.cat(zs, dim=0), weights,
+                                                      origins[0] if one else torch.cat(origins, dim=0),
+                                                      dirs[0] if one else torch.cat(dirs, dim=0), n_importance, True)
+                counts = [p.shape[0] for p in pts]
+                shade(live, fines, dirs, list(torch.split(pts_f, counts, dim=0)), list(torch.split(z_f, counts, dim=0)),
+                      det.N_samples + n_importance, False)
+    cat = lambda acc: tuple(a[0] if len(a) == 1 else torch.cat(a, dim=0) for a in acc)
+    return [(cat(c), cat(f) if n_importance > 0 else None) for c, f in zip(outs, fines)]
+
+
+def _finished_alpha(mlp, points: Tensor, glob: Tensor) -> Tensor:
+    """The sigma-MLP over the density finish's rows and their alpha: the fused trunk where the MLP has one."""
+    if hasattr(mlp, "hip_trunk_ok") and mlp.hip_trunk_ok():
+        return mlp.alpha_from_points(points, glob)
+    return ops.sigma_to_alpha(mlp.raw_sigma_from_rows(ops.posenc_concat(points, glob)))
+
+
+def _repeat_tails(det, vol: Tensor, valid: Tensor, metas):
+    """neck_3d and the tails of a call's scenes once more on bf16x3, from the finished volumes (n,C,X,Y,Z): the scenes of a call share the
+    stream's guard word, so a set word says that some launch of the call tripped, not which scene's."""
+    conv3d.guard_trips += 1
+    prev = conv3d.set_arithmetic("bf16x3")
+    try:
+        with torch.no_grad():
+            n = vol.shape[0]
+            x = det.neck_3d(vol)
+            return [det._detect_tail(x if n == 1 else [lvl[i:i + 1] for lvl in x], valid[i:i + 1], metas[i], False, False, vol.device, None)
+                    for i in range(n)]
+    finally:
+        conv3d.set_arithmetic(prev)
+
+
 class SceneStream:
     """One scene of a :class:`~nerfdet_amd.detector.nerfdet` detector, filled chunk by chunk (:meth:`add_views`) and detected at any time
     (:meth:`detect`).  ``img_meta`` fixes the scene: ``lidar2img.intrinsic``, ``lidar2img.origin``, ``img_shape`` and ``ori_shape``; its
@@ -328,8 +514,8 @@ class SceneStream:
         self.mean, self.std = _norm_cfg(mean, std)
         if not isinstance(keep_views, bool):
             raise ValueError(f"keep_views must be a bool, got {keep_views!r}")
-        if window is not None and (isinstance(window, bool) or not isinstance(window, int) or not 1 <= window <= ops.RING_MAX):
-            raise ValueError(f"window must be None or an int in 1 .. {ops.RING_MAX}, got {window!r}")
+        if window is not None:
+            ops.check_window(window)
         if det.training:
             raise RuntimeError("SceneStream is inference only: call det.eval() first")
         if det.render_testing and not keep_views:
@@ -416,10 +602,6 @@ class SceneStream:
     def _check_meta(self, img_meta: dict, k: int) -> None:
         check_chunk_meta(self.meta, img_meta, k)
 
-    def _features(self, img: Tensor):
-        x, _, stride = self.det.extract_2d(img)
-        return x, getattr(x, "_ndet_feature_2d", None), stride
-
     def _check_chunk(self, img: Tensor, denorm_images: Tensor, img_meta: dict, depth) -> None:
         """Everything add_views refuses, before anything is launched (only shapes are read)."""
         if img.dim() != 5 or img.shape[0] != 1:
@@ -451,10 +633,8 @@ class SceneStream:
         check_depth_frames(depth_frames, depth, 1, k)
         shape = torch.empty((1, k, 3) + pad_size, device="meta")
         self._check_chunk(shape, shape, img_meta, depth)
-        img, denorm = prepare_frames(frames[0], img_scale, pad_size, self.mean, self.std)
-        if depth_frames is not None:
-            depth = prepare_depth_frames(depth_frames[0], self.meta["img_shape"][:2]).unsqueeze(0)
-        self.add_views(img.unsqueeze(0), denorm.unsqueeze(0), img_meta, depth=depth)
+        img, denorm, depth = _prepared_frames(frames, depth_frames, depth, self.meta["img_shape"], img_scale, pad_size, self.mean, self.std)
+        self.add_views(img, denorm, img_meta, depth=depth)
 
     def add_views(self, img: Tensor, denorm_images: Tensor, img_meta: dict, depth: Optional[Tensor] = None) -> None:
         """Fold k >= 1 views into the scene.  ``img``, ``denorm_images`` (1, k, 3, H, W); ``img_meta`` the chunk's (its ``extrinsic`` list has
@@ -466,31 +646,13 @@ class SceneStream:
         (``conv3d.guard_trips`` counts it), so no tripped chunk reaches the state."""
         self._check_chunk(img, denorm_images, img_meta, depth)
         with torch.no_grad():
-            guarded = conv3d.ARITHMETIC == "f16x2" and img.is_cuda
-            if guarded:
-                conv3d.guard_begin(img.device)
-            x, f2d, stride = self._features(img)
-            if guarded and conv3d.guard_tripped(img.device):
-                conv3d.guard_trips += 1
-                prev = conv3d.set_arithmetic("bf16x3")
-                try:
-                    x, f2d, stride = self._features(img)
-                finally:
-                    conv3d.set_arithmetic(prev)
-            hh, ww = self.meta["img_shape"][0], self.meta["img_shape"][1]
-            h, w = hh // stride, ww // stride
-            feat = ops.to_channels_last(x)[:, :, :h, :w]
             lin = self._lin
-            if f2d is not None:
-                mapped = f2d[:, :, :h, :w]
-            elif lin.in_features % 32 == 0:
-                mapped = map_features_2d_hip(feat, lin)
-            else:
-                mapped = map_features_2d(feat, lin.weight, lin.bias)
+            hh, ww = self.meta["img_shape"][0], self.meta["img_shape"][1]
+            feat, mapped, stride = _chunk_features(self.det, lin, img, (hh, ww))
             rgb = denorm_images[0][:, :, :hh, :ww]
             gate = None
             if depth is not None:
-                gate = ops.depth_gate(depth[0].to(self.device, non_blocking=True), self.det.voxel_size, (h, w), (hh, ww))
+                gate = ops.depth_gate(depth[0].to(self.device, non_blocking=True), self.det.voxel_size, (hh // stride, ww // stride), (hh, ww))
             proj = ops.compute_projection(img_meta, stride, self.device)
             rgb_proj = ops.compute_projection(img_meta, 1, self.device)
             # the bank takes the mapped map as it is accumulated and the images as extract_feat hands them to render_rays (uncropped)
@@ -508,28 +670,8 @@ class SceneStream:
     def _render(self, ray_o: Tensor, ray_d: Tensor, step: int, n_importance: int = 0):
         """render_ray.py:250-327 (``det=True``, mode 'image') over the bank, ``step`` rays per pass: ``(rgb, depth, mask)`` of the coarse
         pass and, with ``n_importance > 0``, of the fine pass of ``rays.render_rays_func`` (else None)."""
-        from . import rays
         bank = self._need_bank("rendering")
-        det = self.det
-        coarse, fine = ([], [], []), ([], [], [])
-        with torch.no_grad():
-            for i in range(0, ray_o.shape[0], step):
-                o, d = ray_o[i:i + step], ray_d[i:i + step]
-                pts, z_vals = rays.sample_along_camera_ray(o, d, det.near_far_range, det.N_samples, det=True)
-                globalfeat, pixel_mask, _ = rays.ray_view_stats_bank(pts, bank)
-                rgb_pts, density_pts = det.nerf_mlp(pts, d, globalfeat)
-                out = rays.raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), z_vals, pixel_mask)
-                for acc, key in zip(coarse, ("rgb", "depth", "mask")):
-                    acc.append(out[key])
-                if n_importance > 0:
-                    pts, z_vals, _ = rays.importance_merge(z_vals, out["weights"], o, d, n_importance, True)
-                    globalfeat, pixel_mask, _ = rays.ray_view_stats_bank(pts, bank)
-                    rgb_pts, density_pts = rays.fine_mlp(det.nerf_mlp, pts, d, globalfeat)
-                    out = rays.raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), z_vals, pixel_mask)
-                    for acc, key in zip(fine, ("rgb", "depth", "mask")):
-                        acc.append(out[key])
-        coarse = tuple(torch.cat(a, dim=0) for a in coarse)
-        return coarse, (tuple(torch.cat(a, dim=0) for a in fine) if n_importance > 0 else None)
+        return _render_passes(self.det, [bank], [ray_o], [ray_d], step, False, n_importance, _one_bank_stats)[0]
 
     def render_rays(self, ray_o: Tensor, ray_d: Tensor, n_importance: int = 0):
         """Render rays ``ray_o``, ``ray_d`` (R,3) against the views held: ``dict(rgb (R,3), depth (R,), mask (R,) bool)``, what
@@ -552,20 +694,11 @@ class SceneStream:
         """Every ray of the ray batch's target views, as ``rays.render_rays(render_testing=True)`` returns them (render_ray.py:452-517):
         ``outputs_coarse.rgb`` (T,h,w,3), ``outputs_coarse.depth`` (T,h,w,1), ``gt_rgb``, ``gt_depth`` -- ``rays.rendering_metrics`` applies.
         ``n_importance=k > 0`` adds ``outputs_fine`` (same shapes), as ``rays.render_rays(render_testing=True, N_importance=k)`` does."""
-        from . import rays
         self._need_bank("render")
         n_importance = _check_n_importance(n_importance)
-        ray_o, ray_d, gt_rgb, gt_depth = ray_batch["ray_o"], ray_batch["ray_d"], ray_batch["gt_rgb"], ray_batch["gt_depth"]
-        nerf_size = ray_batch["nerf_sizes"][0]
-        view_num = ray_o.shape[1]
-        hh, ww = int(nerf_size[0][0]), int(nerf_size[0][1])
-        ray_o, ray_d, gt_rgb = ray_o.view(-1, 3), ray_d.view(-1, 3), gt_rgb.view(-1, 3)
-        gt_depth = gt_depth.view(-1, 1) if len(gt_depth) != 0 else None
-        assert view_num * hh * ww == ray_o.shape[0]  # render_ray.py:468
-        n_rand = self.det.N_rand
-        step = n_rand * max(1, rays.RENDER_TESTING_RAYS // n_rand)       # the passes of rays.render_rays
-        coarse, fine = self._render(ray_o, ray_d, step, n_importance)
-        return _render_views(coarse, fine, (view_num, hh, ww), gt_rgb, gt_depth)
+        ray_o, ray_d, shape, gt_rgb, gt_depth = _unpack_ray_batch(ray_batch)
+        coarse, fine = self._render(ray_o, ray_d, _render_step(self.det), n_importance)
+        return _render_views(coarse, fine, shape, gt_rgb, gt_depth)
 
     def render_frames(self, c2w=None, extrinsic=None, window=None, stride: int = 1, n_importance: int = 0):
         """Camera frames of k >= 1 poses against the views held -- pose in, BGR and depth out, in the formats :meth:`add_frames` takes.
@@ -601,14 +734,7 @@ class SceneStream:
         held_out_depth)``: per frame ``sse``, ``n_px``, ``depth_sad_mm``, ``n_depth`` (int64) and ``psnr`` (float64) over the pixels the
         render has a depth for.  Nothing is added to the scene."""
         self._need_bank("score_frames")
-        img_scale, pad_size = check_frames_meta(self.meta, frames, 1)
-        k = frames.shape[1]
-        check_chunk_meta(self.meta, meta, k)
-        check_depth_frames(depth_frames, None, 1, k)
-        n_importance = _check_n_importance(n_importance)
-        grid = _frame_grid(self.meta, None, stride)
-        held, held_depth = _held_out(frames[0], None if depth_frames is None else depth_frames[0], self.meta, img_scale, pad_size, self.mean,
-                                     self.std, grid)
+        held, held_depth, _, n_importance = _score_held_out(self.meta, [self.meta], frames, [meta], depth_frames, stride, n_importance, self.mean, self.std)
         out = self.render_frames(extrinsic=meta["lidar2img"]["extrinsic"], stride=stride, n_importance=n_importance)
         return frame_errors(out["frames"], held, out["depth_frames"], held_depth)
 
@@ -649,11 +775,7 @@ class SceneStream:
         ring = self.window is not None
         with torch.no_grad():
             glob = ops.density_finish_ring(self._segs, self._lin.bias) if ring else ops.density_finish(self.state, self._lin.bias)
-            mlp = self.det.nerf_mlp
-            if hasattr(mlp, "hip_trunk_ok") and mlp.hip_trunk_ok():
-                alpha = mlp.alpha_from_points(self.points, glob)
-            else:
-                alpha = ops.sigma_to_alpha(mlp.raw_sigma_from_rows(ops.posenc_concat(self.points, glob)))
+            alpha = _finished_alpha(self.det.nerf_mlp, self.points, glob)
             return ops.volume_finish_ring(self._segs, alpha) if ring else ops.volume_finish(self.state, alpha)
 
     def detect(self, defer: bool = False):
@@ -670,14 +792,7 @@ class SceneStream:
             return self.det._detect_tail(x, valid.unsqueeze(0), metas, defer, guarded, vol.device, lambda: self._repeat_tail(vol, valid, metas))
 
     def _repeat_tail(self, vol: Tensor, valid: Tensor, metas):
-        conv3d.guard_trips += 1
-        prev = conv3d.set_arithmetic("bf16x3")
-        try:
-            with torch.no_grad():
-                x = self.det.neck_3d(vol.unsqueeze(0))
-                return self.det._detect_tail(x, valid.unsqueeze(0), metas, False, False, vol.device, None)
-        finally:
-            conv3d.set_arithmetic(prev)
+        return _repeat_tails(self.det, vol.unsqueeze(0), valid.unsqueeze(0), [metas])[0]
 
 
 _TRIPPED = object()     # a deferred tail's answer when the range-guard word came back set (SceneGroup.detect)
@@ -847,10 +962,6 @@ class SceneGroup:
             raise RuntimeError("SceneGroup is inference only: call det.eval() first")
         return scenes, k
 
-    def _features(self, img: Tensor):
-        x, _, stride = self.det.extract_2d(img)
-        return x, getattr(x, "_ndet_feature_2d", None), stride
-
     def add_frames(self, frames: Tensor, metas, scenes=None, depth: Optional[Tensor] = None, depth_frames: Optional[Tensor] = None) -> None:
         """:meth:`add_views` for frames at CAPTURE resolution: ``frames`` (len(scenes), k, Hs, Ws, 3) uint8 BGR on the device, one row of k
         frames per listed scene.  The group's meta says what becomes of them, as in :meth:`SceneStream.add_frames`: ``(Hs, Ws)`` must be
@@ -869,11 +980,8 @@ class SceneGroup:
         check_depth_frames(depth_frames, depth, n, k)
         shape = torch.empty((n, k, 3) + pad_size, device="meta")
         self._check_call(shape, shape, metas, scenes, depth)
-        if depth_frames is not None:
-            d = prepare_depth_frames(depth_frames.reshape((n * k,) + tuple(depth_frames.shape[2:])), self.metas[0]["img_shape"][:2])
-            depth = d.view((n, k) + tuple(d.shape[1:]))
-        img, denorm = prepare_frames(frames.reshape((n * k,) + tuple(frames.shape[2:])), img_scale, pad_size, self.mean, self.std)
-        self.add_views(img.view((n, k) + tuple(img.shape[1:])), denorm.view((n, k) + tuple(denorm.shape[1:])), metas, scenes=scenes, depth=depth)
+        img, denorm, depth = _prepared_frames(frames, depth_frames, depth, self.metas[0]["img_shape"], img_scale, pad_size, self.mean, self.std)
+        self.add_views(img, denorm, metas, scenes=scenes, depth=depth)
 
     def add_views(self, img: Tensor, denorm_images: Tensor, metas, scenes=None, depth: Optional[Tensor] = None) -> None:
         """Fold k views into each listed scene.  ``img``, ``denorm_images`` (len(scenes), k, 3, H, W), one row per listed scene; ``metas`` one
@@ -891,33 +999,14 @@ class SceneGroup:
         n = len(scenes)
         metas = list(metas)
         with torch.no_grad():
-            guarded = conv3d.ARITHMETIC == "f16x2" and img.is_cuda
-            if guarded:
-                conv3d.guard_begin(img.device)
-            x, f2d, stride = self._features(img)
-            if guarded and conv3d.guard_tripped(img.device):
-                conv3d.guard_trips += 1
-                prev = conv3d.set_arithmetic("bf16x3")
-                try:
-                    x, f2d, stride = self._features(img)
-                finally:
-                    conv3d.set_arithmetic(prev)
-            first = self.metas[0]
-            hh, ww = first["img_shape"][0], first["img_shape"][1]
-            h, w = hh // stride, ww // stride
-            feat = ops.to_channels_last(x)[:, :, :h, :w]
             lin = self._lin
-            if f2d is not None:
-                mapped = f2d[:, :, :h, :w]
-            elif lin.in_features % 32 == 0:
-                mapped = map_features_2d_hip(feat, lin)
-            else:
-                mapped = map_features_2d(feat, lin.weight, lin.bias)
+            hh, ww = self.metas[0]["img_shape"][0], self.metas[0]["img_shape"][1]
+            feat, mapped, stride = _chunk_features(self.det, lin, img, (hh, ww))
             rgb = denorm_images.reshape([-1] + list(denorm_images.shape)[2:])[:, :, :hh, :ww]
             gate = None
             if depth is not None:
                 d = depth.reshape([-1] + list(depth.shape)[2:]).to(self.device, non_blocking=True)
-                gate = ops.depth_gate(d, self.det.voxel_size, (h, w), (hh, ww))
+                gate = ops.depth_gate(d, self.det.voxel_size, (hh // stride, ww // stride), (hh, ww))
             proj = ops.compute_projection_group(metas, (stride, 1), self.device)     # the n k projections at both strides: one upload
             # every bank takes its scene's rows of the mapped map as they are accumulated and of the images as extract_feat hands them to
             # render_rays (uncropped); all the segments are made before any state, window or bank changes
@@ -944,68 +1033,10 @@ class SceneGroup:
         return scenes
 
     def _render(self, ray_os, ray_ds, scenes: List[int], step: int, batched: bool, n_importance: int = 0):
-        """render_ray.py:250-327 (``det=True``, mode 'image') over the listed scenes' banks, at most ``step`` rays per scene and pass:
-        per listed scene ``((rgb, depth, mask) of the coarse pass, the same of the fine pass or None)``.  A pass samples every scene
-        that still has rays, runs ONE grouped sampler launch over their banks (rays.ray_view_stats_bank_group) and then the MLP and the
-        compositing per scene, or with ``batched`` once over all the pass's samples.  With ``n_importance > 0`` ONE k_importance_merge
-        launch over all the pass's rays then gives the fine samples (the kernel is per ray), and the same three steps run over them."""
+        """:func:`_render_passes` over the listed scenes' banks with ONE grouped sampler launch per pass (rays.bank_group_stats,
+        k_ray_stats_bank_group): per listed scene ``((rgb, depth, mask) of the coarse pass, the same of the fine pass or None)``."""
         from . import rays
-        det = self.det
-        n = len(scenes)
-        banks = [self.banks[s] for s in scenes]
-        batched = bool(batched) and n > 1 and conv3d.ARITHMETIC != "f32"
-        outs = [([], [], []) for _ in range(n)]
-        fines = [([], [], []) for _ in range(n)]
-
-        def shade(live, accs, dirs, pts, zs, ss, want_weights):
-            """Sampler, MLP and compositing of one pass over ``ss`` samples a ray; appends to ``accs``, returns the rays' weights (R, ss)."""
-            mlp = det.nerf_mlp if ss == det.N_samples else (lambda p, d, g: rays.fine_mlp(det.nerf_mlp, p, d, g))
-            glob, pm, _, all_pts = rays.bank_group_stats(pts, [banks[i] for i in live])
-            counts = [p.shape[0] for p in pts]
-            if batched and len(live) > 1:
-                # one MLP call and one compositing call over the pass: the scenes share linear_rows' per-tensor fp16-pair scales
-                rr = sum(counts)
-                rgb_pts, density_pts = mlp(all_pts.view(rr, ss, 3), torch.cat(dirs, dim=0), glob.view(rr, ss, -1))
-                out = rays.raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), torch.cat(zs, dim=0), pm.view(rr, ss))
-                at = 0
-                for i, c in zip(live, counts):
-                    for acc, key in zip(accs[i], ("rgb", "depth", "mask")):
-                        acc.append(out[key][at:at + c])
-                    at += c
-                return out["weights"]
-            at, wts = 0, []
-            for i, c, d, p, z in zip(live, counts, dirs, pts, zs):
-                rows = slice(at * ss, (at + c) * ss)
-                rgb_pts, density_pts = mlp(p, d, glob[rows].view(c, ss, -1))
-                out = rays.raw2outputs(torch.cat([rgb_pts, density_pts], dim=-1), z, pm[rows].view(c, ss))
-                for acc, key in zip(accs[i], ("rgb", "depth", "mask")):
-                    acc.append(out[key])
-                wts.append(out["weights"])
-                at += c
-            return (wts[0] if len(wts) == 1 else torch.cat(wts, dim=0)) if want_weights else None
-
-        with torch.no_grad():
-            for i0 in range(0, max(o.shape[0] for o in ray_os), step):
-                live = [i for i in range(n) if ray_os[i].shape[0] > i0]
-                origins, dirs, pts, zs = [], [], [], []
-                for i in live:
-                    o, d = ray_os[i][i0:i0 + step], ray_ds[i][i0:i0 + step]
-                    p, z = rays.sample_along_camera_ray(o, d, det.near_far_range, det.N_samples, det=True)
-                    origins.append(o)
-                    dirs.append(d)
-                    pts.append(p)
-                    zs.append(z)
-                weights = shade(live, outs, dirs, pts, zs, det.N_samples, n_importance > 0)
-                if n_importance > 0:
-                    one = len(live) == 1
-                    pts_f, z_f, _ = rays.importance_merge(zs[0] if one else torch.cat(zs, dim=0), weights,
-                                                          origins[0] if one else torch.cat(origins, dim=0),
-                                                          dirs[0] if one else torch.cat(dirs, dim=0), n_importance, True)
-                    counts = [p.shape[0] for p in pts]
-                    shade(live, fines, dirs, list(torch.split(pts_f, counts, dim=0)), list(torch.split(z_f, counts, dim=0)),
-                          det.N_samples + n_importance, False)
-        cat = lambda acc: tuple(a[0] if len(a) == 1 else torch.cat(a, dim=0) for a in acc)
-        return [(cat(c), cat(f) if n_importance > 0 else None) for c, f in zip(outs, fines)]
+        return _render_passes(self.det, [self.banks[s] for s in scenes], ray_os, ray_ds, step, batched, n_importance, rays.bank_group_stats)
 
     def render_rays(self, ray_o, ray_d, scenes=None, batched: bool = False, n_importance: int = 0):
         """Render rays against the views the listed scenes hold: ``ray_o``, ``ray_d`` are lists of (R_s, 3) tensors, one pair per listed
@@ -1058,30 +1089,15 @@ class SceneGroup:
         applies), through the passes of :meth:`render_rays` with SceneStream.render's pass size,
         ``N_rand * max(1, RENDER_TESTING_RAYS // N_rand)``; ``batched`` and ``n_importance`` (which adds ``outputs_fine``) as in
         :meth:`render_rays`.  One stream, as there."""
-        from . import rays
         scenes = self._need_banks("render", scenes)
         n_importance = _check_n_importance(n_importance)
         ray_batches = list(ray_batches)
         if len(ray_batches) != len(scenes):
             raise ValueError(f"render: {len(ray_batches)} ray batches for {len(scenes)} listed scenes")
-        os_, ds_, shapes, gts = [], [], [], []
-        for rb in ray_batches:
-            ray_o, ray_d, gt_rgb, gt_depth = rb["ray_o"], rb["ray_d"], rb["gt_rgb"], rb["gt_depth"]
-            nerf_size = rb["nerf_sizes"][0]
-            view_num = ray_o.shape[1]
-            hh, ww = int(nerf_size[0][0]), int(nerf_size[0][1])
-            ray_o, ray_d, gt_rgb = ray_o.view(-1, 3), ray_d.view(-1, 3), gt_rgb.view(-1, 3)
-            gt_depth = gt_depth.view(-1, 1) if len(gt_depth) != 0 else None
-            assert view_num * hh * ww == ray_o.shape[0]  # render_ray.py:468
-            os_.append(ray_o)
-            ds_.append(ray_d)
-            shapes.append((view_num, hh, ww))
-            gts.append((gt_rgb, gt_depth))
-        os_, ds_ = self._check_rays(os_, ds_, len(scenes))
-        n_rand = self.det.N_rand
-        step = n_rand * max(1, rays.RENDER_TESTING_RAYS // n_rand)       # the passes of rays.render_rays
-        res = self._render(os_, ds_, scenes, step, batched, n_importance)
-        return [_render_views(coarse, fine, shape, gt_rgb, gt_depth) for (coarse, fine), shape, (gt_rgb, gt_depth) in zip(res, shapes, gts)]
+        unpacked = [_unpack_ray_batch(rb) for rb in ray_batches]
+        os_, ds_ = self._check_rays([u[0] for u in unpacked], [u[1] for u in unpacked], len(scenes))
+        res = self._render(os_, ds_, scenes, _render_step(self.det), batched, n_importance)
+        return [_render_views(coarse, fine, shape, gt_rgb, gt_depth) for (coarse, fine), (_, _, shape, gt_rgb, gt_depth) in zip(res, unpacked)]
 
     def render_frames(self, c2w=None, extrinsic=None, scenes=None, batched: bool = False, window=None, stride: int = 1, n_importance: int = 0):
         """:meth:`SceneStream.render_frames` for the listed scenes at once: exactly one of ``c2w`` and ``extrinsic``, a list with one list of
@@ -1096,12 +1112,7 @@ class SceneGroup:
         from . import rays
         scenes = self._need_banks("render_frames", scenes)
         n_importance = _check_n_importance(n_importance)
-        if (c2w is None) == (extrinsic is None):
-            raise ValueError("render_frames takes exactly one of c2w (camera-to-world) and extrinsic (world-to-camera)")
-        given = c2w if c2w is not None else extrinsic
-        if isinstance(given, (Tensor, np.ndarray)) and given.ndim != 4:
-            raise ValueError("render_frames takes one LIST of 4 x 4 matrices per listed scene")
-        given = list(given)
+        given = _camera_lists(c2w, extrinsic, "render_frames")
         if len(given) != len(scenes):
             raise ValueError(f"render_frames: {len(given)} camera lists for {len(scenes)} listed scenes")
         poses = [_camera_poses(g, None, "render_frames") if c2w is not None else _camera_poses(None, g, "render_frames") for g in given]
@@ -1129,21 +1140,9 @@ class SceneGroup:
         ndet_depth_frames launch) makes all the held-out frames, :meth:`render_frames` all the renders, and one ndet_frame_errors launch
         per scene compares them.  Returns a list of ``pipeline.frame_errors`` dicts; nothing is added to any scene."""
         scenes = self._need_banks("score_frames", scenes)
-        n = len(scenes)
-        first = self.metas[0]
-        img_scale, pad_size = check_frames_meta(first, frames, n)
         metas = list(metas)
-        if len(metas) != n:
-            raise ValueError(f"score_frames: {len(metas)} chunk metas for {n} listed scenes")
-        k = frames.shape[1]
-        for s, m in zip(scenes, metas):
-            check_chunk_meta(self.metas[s], m, k)
-        check_depth_frames(depth_frames, None, n, k)
-        n_importance = _check_n_importance(n_importance)
-        grid = _frame_grid(first, None, stride)
-        held, held_depth = _held_out(frames.reshape((n * k,) + tuple(frames.shape[2:])),
-                                     None if depth_frames is None else depth_frames.reshape((n * k,) + tuple(depth_frames.shape[2:])), first,
-                                     img_scale, pad_size, self.mean, self.std, grid)
+        held, held_depth, k, n_importance = _score_held_out(self.metas[0], [self.metas[s] for s in scenes], frames, metas, depth_frames, stride, n_importance,
+                                                            self.mean, self.std)
         outs = self.render_frames(extrinsic=[m["lidar2img"]["extrinsic"] for m in metas], scenes=scenes, batched=batched, stride=stride,
                                   n_importance=n_importance)
         return [frame_errors(out["frames"], held[i * k:(i + 1) * k], out["depth_frames"], None if held_depth is None else held_depth[i * k:(i + 1) * k])
@@ -1152,12 +1151,7 @@ class SceneGroup:
     def _plan_detections(self, frames, results, c2w, extrinsic, scenes, trailing, dtype, window, stride, capture, score_thr, palette, what: str):
         """The checked plans of a grouped ``draw_detections`` / ``label_detections`` call, one per listed scene; nothing is launched."""
         scenes = ops.listed_scenes(self.n_scenes, scenes)
-        if (c2w is None) == (extrinsic is None):
-            raise ValueError(f"{what} takes exactly one of c2w (camera-to-world) and extrinsic (world-to-camera)")
-        given = c2w if c2w is not None else extrinsic
-        if isinstance(given, (Tensor, np.ndarray)) and given.ndim != 4:
-            raise ValueError(f"{what} takes one LIST of 4 x 4 matrices per listed scene")
-        given = list(given)
+        given = _camera_lists(c2w, extrinsic, what)
         if isinstance(frames, Tensor) or isinstance(results, dict):
             raise ValueError(f"{what} takes one frames tensor and one result per listed scene, as lists")
         frames, results = list(frames), list(results)
@@ -1198,11 +1192,7 @@ class SceneGroup:
             glob = ops.density_finish_group_ring(self.pool, self._lin.bias, scenes)
         else:
             glob = ops.density_finish_group(self.group, self._lin.bias, scenes)
-        mlp = self.det.nerf_mlp
-        if hasattr(mlp, "hip_trunk_ok") and mlp.hip_trunk_ok():
-            alpha = mlp.alpha_from_points(pts, glob)
-        else:
-            alpha = ops.sigma_to_alpha(mlp.raw_sigma_from_rows(ops.posenc_concat(pts, glob)))
+        alpha = _finished_alpha(self.det.nerf_mlp, pts, glob)
         return ops.volume_finish_group_ring(self.pool, alpha, scenes) if ring else ops.volume_finish_group(self.group, alpha, scenes)
 
     def volume(self, scenes=None):
@@ -1260,18 +1250,5 @@ class SceneGroup:
             tripped = guarded and not word_rides and conv3d.guard_tripped(dev)
             results = [finish() for finish in pending]
             if tripped or any(r is _TRIPPED for r in results):
-                results = self._repeat_tails(vol, valid, metas)
+                results = _repeat_tails(det, vol, valid, metas)
         return [r[0] for r in results]
-
-    def _repeat_tails(self, vol: Tensor, valid: Tensor, metas):
-        """The call's neck_3d and tails once more on bf16x3, from the finished volumes, for every listed scene: the scenes of a call share
-        the stream's guard word, so a set word says that some launch of the call tripped, not which scene's."""
-        conv3d.guard_trips += 1
-        prev = conv3d.set_arithmetic("bf16x3")
-        try:
-            n = vol.shape[0]
-            x = self.det.neck_3d(vol)
-            return [self.det._detect_tail(x if n == 1 else [lvl[i:i + 1] for lvl in x], valid[i:i + 1], metas[i], False, False, vol.device, None)
-                    for i in range(n)]
-        finally:
-            conv3d.set_arithmetic(prev)
