@@ -468,8 +468,10 @@ def fine_mlp(nerf_mlp, pts, ray_d, globalfeat):
     """``nerf_mlp(pts, ray_d, globalfeat)`` over the (R, S + k, .) samples of a fine pass, as ``(rgb, sigma)``: in one call up to
     FINE_MLP_ROWS sample rows, beyond that in the fewest calls of whole rays, equal in size to within one ray, that stay under it.  The
     row MLP's 1x1-convolution kernels address at most 2 GB per operand, which 8192 rays x 128 samples of the cfg2 widths exceed.  The
-    split is a function of (R, S + k) alone, so every renderer's fine pass makes the same calls over the same rays -- the ``linear_rows``
-    layers take a per-tensor scale, the calls are part of the result's bits."""
+    split is a function of (R, S + k) alone, so every renderer's fine pass makes the same calls over the same rays.  No scale is shared
+    across a call's rows: the fused trunk scales per row, and the ``linear_rows`` layers are pinned to bf16x3 (conv3d.packed_linear),
+    which splits the operands exactly and has no per-tensor scale
+    (tests/test_ray_forward_gpu.py::test_radiance_mlp_at_inference_against_float64 asserts the arithmetic of every launch)."""
     r, s = pts.shape[:2]
     most = max(1, FINE_MLP_ROWS // s)          # rays a call may take
     if r <= most:
