@@ -238,23 +238,8 @@ extern "C" int ndet_density_features_bwd_gated(const float* grad_global_feat, co
 // K4 backward: d(mapped features) from d(globalfeat) of the ray sampler.
 //   val_v = bilinear(feat_v), mean = sum_v mask_v wgt val_v, var = sum_v (val_v-mean)^2 / den, ev = exp(-var)
 //   dL/dval_v = gm mask_v wgt + (-ge ev/den) (2 (val_v-mean) - 2 mask_v wgt sum_u (val_u - mean))
-// then spread over the 4 taps with the bilinear weights.  Lanes over the d feature channels.
+// then spread over the 4 taps with the bilinear weights.  Lanes over the d feature channels.  The projection is ndet_ray_project.
 // ------------------------------------------------------------------------------------------------
-struct RayHit { float nx, ny; bool mask; };
-
-__device__ __forceinline__ RayHit bwd_ray_project(const float* __restrict__ KE, float x, float y, float z, float h, float w) {
-    float q0 = KE[0] * x; q0 = fmaf(KE[1], y, q0); q0 = fmaf(KE[2], z, q0); q0 = q0 + KE[3];
-    float q1 = KE[4] * x; q1 = fmaf(KE[5], y, q1); q1 = fmaf(KE[6], z, q1); q1 = q1 + KE[7];
-    float q2 = KE[8] * x; q2 = fmaf(KE[9], y, q2); q2 = fmaf(KE[10], z, q2); q2 = q2 + KE[11];
-    const float den = fmaxf(q2, 1e-8f);
-    float px = fminf(fmaxf(q0 / den, -1e6f), 1e6f), py = fminf(fmaxf(q1 / den, -1e6f), 1e6f);
-    RayHit r;
-    r.mask = (px <= w - 1.0f) && (px >= 0.0f) && (py <= h - 1.0f) && (py >= 0.0f) && (q2 > 0.0f);
-    r.nx = (2.0f * px) / (w - 1.0f) - 1.0f;
-    r.ny = (2.0f * py) / (h - 1.0f) - 1.0f;
-    return r;
-}
-
 struct Taps { int o00, o01, o10, o11; float w00, w01, w10, w11; };  // offsets < 0: tap outside the map
 
 __device__ __forceinline__ Taps bilinear_taps(float nx, float ny, int Hs, int Ws, int row_pitch, int d) {
@@ -289,7 +274,7 @@ __global__ __launch_bounds__(256) void k_ray_view_stats_bwd(const float* __restr
     int cnt = 0;
     for (int r0 = 0; r0 < n_views; r0 += 64) {
         const int v = r0 + lane;
-        const bool m = v < n_views && bwd_ray_project(KE + v * 12, x, y, z, img_h, img_w).mask;
+        const bool m = v < n_views && ndet_ray_project(KE + v * 12, x, y, z, img_h, img_w).mask;
         cnt += __popcll(__ballot(m));
     }
     const float den = (float)cnt + 1e-8f, wgt = 1.0f / den;
@@ -301,8 +286,8 @@ __global__ __launch_bounds__(256) void k_ray_view_stats_bwd(const float* __restr
         float acc = 0.0f, acc2 = 0.0f;
         for (int r0 = 0; r0 < n_views; r0 += 64) {
             const int v = r0 + lane;
-            RayHit hit; hit.nx = 0.f; hit.ny = 0.f; hit.mask = false;
-            if (v < n_views) hit = bwd_ray_project(KE + v * 12, x, y, z, img_h, img_w);
+            NdetRayHit hit; hit.nx = 0.f; hit.ny = 0.f; hit.mask = false;
+            if (v < n_views) hit = ndet_ray_project(KE + v * 12, x, y, z, img_h, img_w);
             const unsigned long long mbits = __ballot(hit.mask);
             const int nv_here = min(64, n_views - r0);
             for (int b = 0; b < nv_here; ++b) {

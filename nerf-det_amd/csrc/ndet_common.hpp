@@ -99,6 +99,38 @@ __device__ __forceinline__ bool ndet_project(const float* __restrict__ P, float 
     return ndet_project_z(P, px, py, pz, w, h, xi, yi, z);
 }
 
+// One sample point -> one source view of the ray branch (projection.py:42-64 + :37-40 + :24-35), for the forward samplers
+// (ray_kernels.hip, ray_stats_kernels.hip) and the sampler's backward (backward_kernels.hip).  KE = rows 0..2 of K @ E, in memory or
+// in registers; the same k-ordered FMA chain as ndet_project_z.
+struct NdetRayHit {
+    float nx, ny;  // normalised coordinates in [-1, 1] (projection.py:37-40)
+    bool mask;     // in-image and in front (projection.py:149-150)
+};
+
+__device__ __forceinline__ NdetRayHit ndet_ray_project(const float* KE, float x, float y, float z, float h, float w) {
+    float q0 = KE[0] * x;
+    q0 = fmaf(KE[1], y, q0);
+    q0 = fmaf(KE[2], z, q0);
+    q0 = q0 + KE[3];
+    float q1 = KE[4] * x;
+    q1 = fmaf(KE[5], y, q1);
+    q1 = fmaf(KE[6], z, q1);
+    q1 = q1 + KE[7];
+    float q2 = KE[8] * x;
+    q2 = fmaf(KE[9], y, q2);
+    q2 = fmaf(KE[10], z, q2);
+    q2 = q2 + KE[11];
+    const float den = fmaxf(q2, 1e-8f);                       // torch.clamp(min=1e-8)
+    float px = q0 / den, py = q1 / den;
+    px = fminf(fmaxf(px, -1e6f), 1e6f);                       // torch.clamp(-1e6, 1e6)
+    py = fminf(fmaxf(py, -1e6f), 1e6f);
+    NdetRayHit r;
+    r.mask = (px <= w - 1.0f) && (px >= 0.0f) && (py <= h - 1.0f) && (py >= 0.0f) && (q2 > 0.0f);
+    r.nx = (2.0f * px) / (w - 1.0f) - 1.0f;
+    r.ny = (2.0f * py) / (h - 1.0f) - 1.0f;
+    return r;
+}
+
 // Depth gate of nerfdet.py:404-411 (include/nerfdet_hip.h, NdetDepthGate): one resized map, kernel-argument form.  The kernels
 // take it under a compile-time flag; their ungated instantiations never read it.
 struct NdetGateMap {

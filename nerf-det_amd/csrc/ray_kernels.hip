@@ -47,38 +47,8 @@ extern "C" int ndet_sample_along_rays(const float* ray_o, const float* ray_d, in
 }
 
 // ------------------------------------------------------------------------------------------------
-// shared device pieces of A7
+// shared device pieces of A7 (the projection is ndet_ray_project, ndet_common.hpp)
 // ------------------------------------------------------------------------------------------------
-struct ViewHit {
-    float nx, ny;  // normalised coordinates in [-1, 1] (projection.py:37-40)
-    bool mask;     // in-image and in front (projection.py:149-150)
-};
-
-// projection.py:42-64 + :37-40 + :24-35.  KE = (K @ E) rows 0..2, the same k-ordered FMA chain as K1.
-__device__ __forceinline__ ViewHit ray_project(const float* __restrict__ KE, float x, float y, float z, float h, float w) {
-    float q0 = KE[0] * x;
-    q0 = fmaf(KE[1], y, q0);
-    q0 = fmaf(KE[2], z, q0);
-    q0 = q0 + KE[3];
-    float q1 = KE[4] * x;
-    q1 = fmaf(KE[5], y, q1);
-    q1 = fmaf(KE[6], z, q1);
-    q1 = q1 + KE[7];
-    float q2 = KE[8] * x;
-    q2 = fmaf(KE[9], y, q2);
-    q2 = fmaf(KE[10], z, q2);
-    q2 = q2 + KE[11];
-    const float den = fmaxf(q2, 1e-8f);                       // torch.clamp(min=1e-8)
-    float px = q0 / den, py = q1 / den;
-    px = fminf(fmaxf(px, -1e6f), 1e6f);                       // torch.clamp(-1e6, 1e6)
-    py = fminf(fmaxf(py, -1e6f), 1e6f);
-    ViewHit r;
-    r.mask = (px <= w - 1.0f) && (px >= 0.0f) && (py <= h - 1.0f) && (py >= 0.0f) && (q2 > 0.0f);
-    r.nx = (2.0f * px) / (w - 1.0f) - 1.0f;
-    r.ny = (2.0f * py) / (h - 1.0f) - 1.0f;
-    return r;
-}
-
 // F.grid_sample(bilinear, zeros, align_corners=True) of ONE channel at normalised (nx, ny).
 // `at(yy, xx)` must return the element's address.
 template <typename At>
@@ -142,7 +112,7 @@ __global__ __launch_bounds__(256) void k_ray_view_stats(const float* __restrict_
         for (int r0 = 0; r0 < n_views; r0 += 64) {
             const int v = r0 + lane;
             bool m = false;
-            if (v < n_views) m = ray_project(KE + v * 12, x, y, z, img_h, img_w).mask;
+            if (v < n_views) m = ndet_ray_project(KE + v * 12, x, y, z, img_h, img_w).mask;
             cnt += __popcll(__ballot(m));
         }
         const float denom = (float)cnt + 1e-8f;
@@ -153,9 +123,9 @@ __global__ __launch_bounds__(256) void k_ray_view_stats(const float* __restrict_
             float acc = 0.0f;
             for (int r0 = 0; r0 < n_views; r0 += 64) {
                 const int v = r0 + lane;
-                ViewHit hit;
+                NdetRayHit hit;
                 hit.nx = 0.f; hit.ny = 0.f; hit.mask = false;
-                if (v < n_views) hit = ray_project(KE + v * 12, x, y, z, img_h, img_w);
+                if (v < n_views) hit = ndet_ray_project(KE + v * 12, x, y, z, img_h, img_w);
                 const unsigned long long mbits = __ballot(hit.mask);
                 const int nv_here = min(64, n_views - r0);
                 for (int b = 0; b < nv_here; ++b) {
@@ -231,7 +201,7 @@ __global__ __launch_bounds__(256) void k_project_sample(const float* __restrict_
     const int c = (int)(i % nch);
     const int v = (int)((i / nch) % n_views);
     const int64_t p = i / ((int64_t)nch * n_views);
-    const ViewHit hit = ray_project(KE + v * 12, pts[p * 3], pts[p * 3 + 1], pts[p * 3 + 2], img_h, img_w);
+    const NdetRayHit hit = ndet_ray_project(KE + v * 12, pts[p * 3], pts[p * 3 + 1], pts[p * 3 + 2], img_h, img_w);
     float val;
     if (c < 3) {
         const float* base = rgb + (int64_t)v * rsv + (int64_t)c * rsc;

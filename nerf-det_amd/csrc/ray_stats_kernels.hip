@@ -50,38 +50,8 @@ extern "C" int ndet_pack_rgb_nhwc4(const float* rgb, int n_views, int H, int W, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// device pieces
+// device pieces (the projection is ndet_ray_project, called with the camera row in registers)
 // ------------------------------------------------------------------------------------------------
-struct RsHit {
-    float nx, ny;
-    bool mask;
-};
-
-// projection.py:42-64,37-40,24-35 with the camera row in registers; same k-ordered FMA chain as ray_project / K1
-__device__ __forceinline__ RsHit rs_project(const float (&k)[12], float x, float y, float z, float h, float w) {
-    float q0 = k[0] * x;
-    q0 = fmaf(k[1], y, q0);
-    q0 = fmaf(k[2], z, q0);
-    q0 = q0 + k[3];
-    float q1 = k[4] * x;
-    q1 = fmaf(k[5], y, q1);
-    q1 = fmaf(k[6], z, q1);
-    q1 = q1 + k[7];
-    float q2 = k[8] * x;
-    q2 = fmaf(k[9], y, q2);
-    q2 = fmaf(k[10], z, q2);
-    q2 = q2 + k[11];
-    const float den = fmaxf(q2, 1e-8f);
-    float px = q0 / den, py = q1 / den;
-    px = fminf(fmaxf(px, -1e6f), 1e6f);
-    py = fminf(fmaxf(py, -1e6f), 1e6f);
-    RsHit r;
-    r.mask = (px <= w - 1.0f) && (px >= 0.0f) && (py <= h - 1.0f) && (py >= 0.0f) && (q2 > 0.0f);
-    r.nx = (2.0f * px) / (w - 1.0f) - 1.0f;
-    r.ny = (2.0f * py) / (h - 1.0f) - 1.0f;
-    return r;
-}
-
 // F.grid_sample(align_corners=True) source coordinate; a tap can only be inside the map for -1 < i < size (NaN: never)
 __device__ __forceinline__ bool rs_near(float nx, float ny, int Hs, int Ws) {
     const float ix = ((nx + 1.0f) / 2.0f) * (float)(Ws - 1);
@@ -148,6 +118,34 @@ __device__ __forceinline__ float rs_var_sum(float q, float s1, float piv, float 
     return s + n_far * (mean * mean);   // views with no tap inside a map sample exactly 0
 }
 
+// exp(-var) of a lane's four channels; a.acc is the masked mean
+__device__ __forceinline__ float4 rs_exp_var(const RsAcc& a, float n_near, float n_far, float denom) {
+    float4 ev;
+    ev.x = expf(-(rs_var_sum(a.q.x, a.s1.x, a.piv.x, a.acc.x, n_near, n_far) / denom));
+    ev.y = expf(-(rs_var_sum(a.q.y, a.s1.y, a.piv.y, a.acc.y, n_near, n_far) / denom));
+    ev.z = expf(-(rs_var_sum(a.q.z, a.s1.z, a.piv.z, a.acc.z, n_near, n_far) / denom));
+    ev.w = expf(-(rs_var_sum(a.q.w, a.s1.w, a.piv.w, a.acc.w, n_near, n_far) / denom));
+    return ev;
+}
+
+// A forward lane's part of sample p's row cat([mean, exp(-var)], dim=-1) (render_ray.py:303): the image lane writes the three colour
+// channels and the sample's masks, feature lane fq its channel quad
+__device__ __forceinline__ void rs_write_row(float* __restrict__ glob, uint8_t* __restrict__ pixel_mask, int* __restrict__ view_count, int p,
+                                             int d, bool is_rgb, int fq, const float4& mean, const float4& ev, int cnt) {
+    const int nch = 3 + d;
+    float* row = glob + (int64_t)p * 2 * nch;
+    if (is_rgb) {
+        row[0] = mean.x; row[1] = mean.y; row[2] = mean.z;
+        row[nch + 0] = ev.x; row[nch + 1] = ev.y; row[nch + 2] = ev.z;
+        pixel_mask[p] = cnt > 1 ? 1 : 0;                      // render_ray.py:301
+        if (view_count) view_count[p] = cnt;
+    } else {
+        const int c = 3 + 4 * fq;
+        row[c + 0] = mean.x; row[c + 1] = mean.y; row[c + 2] = mean.z; row[c + 3] = mean.w;
+        row[nch + c + 0] = ev.x; row[nch + c + 1] = ev.y; row[nch + c + 2] = ev.z; row[nch + c + 3] = ev.w;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // the kernel.  FWD: lanes of a sample = [image quad | d/4 feature quads]; BWD: d/4 feature quads only (images carry no gradient)
 // ------------------------------------------------------------------------------------------------
@@ -187,7 +185,7 @@ __global__ __launch_bounds__(256) void k_ray_stats_packed(const float* __restric
                 const int v = r * 64 + lane;
                 bool m = false, nr = false;
                 if (v < n_views) {
-                    const RsHit hit = rs_project(cam[r], x, y, z, img_h, img_w);
+                    const NdetRayHit hit = ndet_ray_project(cam[r], x, y, z, img_h, img_w);
                     m = hit.mask;
                     nr = rs_near(hit.nx, hit.ny, hf, wf) || (!BWD && rs_near(hit.nx, hit.ny, H, W));
                     rec[gg * nvp + v] = make_float2(hit.nx, hit.ny);
@@ -253,28 +251,12 @@ __global__ __launch_bounds__(256) void k_ray_stats_packed(const float* __restric
     const float nn = (float)n_near, nf = (float)(n_views - n_near);
     const float4 mean = a.acc;
     float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (on) {
-        ev.x = expf(-(rs_var_sum(a.q.x, a.s1.x, a.piv.x, mean.x, nn, nf) / denom));
-        ev.y = expf(-(rs_var_sum(a.q.y, a.s1.y, a.piv.y, mean.y, nn, nf) / denom));
-        ev.z = expf(-(rs_var_sum(a.q.z, a.s1.z, a.piv.z, mean.z, nn, nf) / denom));
-        ev.w = expf(-(rs_var_sum(a.q.w, a.s1.w, a.piv.w, mean.w, nn, nf) / denom));
-    }
-    const int nch = 3 + d;
+    if (on) ev = rs_exp_var(a, nn, nf, denom);
     if (!BWD) {
-        if (!on) return;
-        float* row = glob + (int64_t)my_p * 2 * nch;          // cat([mean, exp(-var)], dim=-1), render_ray.py:303
-        if (is_rgb) {
-            row[0] = mean.x; row[1] = mean.y; row[2] = mean.z;
-            row[nch + 0] = ev.x; row[nch + 1] = ev.y; row[nch + 2] = ev.z;
-            pixel_mask[my_p] = cnt > 1 ? 1 : 0;               // render_ray.py:301
-            if (view_count) view_count[my_p] = cnt;
-        } else {
-            const int c = 3 + 4 * fq;
-            row[c + 0] = mean.x; row[c + 1] = mean.y; row[c + 2] = mean.z; row[c + 3] = mean.w;
-            row[nch + c + 0] = ev.x; row[nch + c + 1] = ev.y; row[nch + c + 2] = ev.z; row[nch + c + 3] = ev.w;
-        }
+        if (on) rs_write_row(glob, pixel_mask, view_count, my_p, d, is_rgb, fq, mean, ev, cnt);
         return;
     }
+    const int nch = 3 + d;
     // ---- backward: dL/dval_v = gm mask_v wgt + k2 (2 (val_v - mean) - 2 mask_v wgt sum_u (val_u - mean)),  k2 = -ge ev / den;
     // views without a tap inside the map have no pixel to receive anything.
     // The scatter runs with ONE channel per lane: a (sample, view, tap) then is one atomic instruction over d consecutive floats
@@ -402,7 +384,7 @@ __device__ __forceinline__ void rb_project_round(const float* __restrict__ pts, 
         const float x = pts[(int64_t)p * 3 + 0], y = pts[(int64_t)p * 3 + 1], z = pts[(int64_t)p * 3 + 2];
         bool m = false, nr = false;
         if (v < n_views) {
-            const RsHit hit = rs_project(cam, x, y, z, img_h, img_w);
+            const NdetRayHit hit = ndet_ray_project(cam, x, y, z, img_h, img_w);
             m = hit.mask;
             nr = rs_near(hit.nx, hit.ny, hf, wf) || rs_near(hit.nx, hit.ny, H, W);
             if (STORE) rec[gg * RB_VIEWS + lane] = make_float2(hit.nx, hit.ny);
@@ -412,9 +394,13 @@ __device__ __forceinline__ void rb_project_round(const float* __restrict__ pts, 
     }
 }
 
-__global__ __launch_bounds__(256) void k_ray_stats_bank(const float* __restrict__ pts, int n_points, const NdetBankView* __restrict__ views,
-                                                        int n_views, float img_h, float img_w, int H, int W, int d, int hf, int wf, int G,
-                                                        float* __restrict__ glob, uint8_t* __restrict__ pixel_mask, int* __restrict__ view_count) {
+// The body of both bank kernels: one bank's views over one block's 4 G of its points (blockIdx.x tiles the points from row 0 of `pts`).
+// Every argument is block-uniform.  The two-views-per-trip walk below is k_ray_stats_packed's written out a second time (records and
+// base pointers come from elsewhere): moved into one helper taking both as lambdas it cost every kernel VGPRs at gfx950 -- bank and
+// group 118 -> 130, 4 -> 3 waves per SIMD; packed forward 104 -> 116, packed backward 112 -> 120 -- so it stays in two places.
+__device__ __forceinline__ void rb_walk(const float* __restrict__ pts, int n_points, const NdetBankView* __restrict__ views, int n_views,
+                                        float img_h, float img_w, int H, int W, int d, int hf, int wf, int G, float* __restrict__ glob,
+                                        uint8_t* __restrict__ pixel_mask, int* __restrict__ view_count) {
     extern __shared__ float2 s_bank[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lps = (d >> 2) + 1;                      // lanes per sample: [image quad | d/4 feature quads]
@@ -496,59 +482,23 @@ __global__ __launch_bounds__(256) void k_ray_stats_bank(const float* __restrict_
         }
     }
     if (!on) return;
-    const float nn = (float)n_near, nf = (float)(n_views - n_near);
-    const float4 mean = a.acc;
-    float4 ev;
-    ev.x = expf(-(rs_var_sum(a.q.x, a.s1.x, a.piv.x, mean.x, nn, nf) / denom));
-    ev.y = expf(-(rs_var_sum(a.q.y, a.s1.y, a.piv.y, mean.y, nn, nf) / denom));
-    ev.z = expf(-(rs_var_sum(a.q.z, a.s1.z, a.piv.z, mean.z, nn, nf) / denom));
-    ev.w = expf(-(rs_var_sum(a.q.w, a.s1.w, a.piv.w, mean.w, nn, nf) / denom));
-    const int nch = 3 + d;
-    float* row = glob + (int64_t)my_p * 2 * nch;              // cat([mean, exp(-var)], dim=-1), render_ray.py:303
-    if (is_rgb) {
-        row[0] = mean.x; row[1] = mean.y; row[2] = mean.z;
-        row[nch + 0] = ev.x; row[nch + 1] = ev.y; row[nch + 2] = ev.z;
-        pixel_mask[my_p] = cnt > 1 ? 1 : 0;                   // render_ray.py:301
-        if (view_count) view_count[my_p] = cnt;
-    } else {
-        const int c = 3 + 4 * fq;
-        row[c + 0] = mean.x; row[c + 1] = mean.y; row[c + 2] = mean.z; row[c + 3] = mean.w;
-        row[nch + c + 0] = ev.x; row[nch + c + 1] = ev.y; row[nch + c + 2] = ev.z; row[nch + c + 3] = ev.w;
-    }
+    const float4 ev = rs_exp_var(a, (float)n_near, (float)(n_views - n_near), denom);
+    rs_write_row(glob, pixel_mask, view_count, my_p, d, is_rgb, fq, a.acc, ev, cnt);
 }
 
-extern "C" int ndet_ray_view_stats_bank(const float* pts, int n_points, const NdetBankView* views_dev, int n_views, float img_h, float img_w,
-                                        int H, int W, int d, int hf, int wf, float* global_feat, uint8_t* pixel_mask, int* view_count,
-                                        void* stream) {
-    const char* fn = "ndet_ray_view_stats_bank";
-    static_assert(sizeof(NdetBankView) == 64, "NdetBankView is 64 bytes");
-    NDET_REQUIRE(pts && views_dev && global_feat && pixel_mask, NDET_E_INVALID, "%s: null pointer", fn);
-    NDET_REQUIRE(n_points > 0 && n_views > 0 && H > 1 && W > 1 && hf > 1 && wf > 1 && d > 0, NDET_E_INVALID, "%s: bad sizes", fn);
-    NDET_REQUIRE(d % 4 == 0 && d <= 128, NDET_E_UNSUPPORTED, "%s: d=%d must be a multiple of 4, at most 128", fn, d);
-    NDET_REQUIRE(((uintptr_t)views_dev & 7) == 0, NDET_E_UNSUPPORTED, "%s: the view table must be 8-byte aligned", fn);
-    NDET_REQUIRE(((uintptr_t)global_feat & 3) == 0, NDET_E_UNSUPPORTED, "%s: global_feat must be 4-byte aligned", fn);
-    NDET_REQUIRE((int64_t)hf * wf * d < ((int64_t)1 << 31) && (int64_t)H * W * 4 < ((int64_t)1 << 31), NDET_E_UNSUPPORTED,
-                 "%s: a source view exceeds 2^31 floats", fn);
-    const int lps = d / 4 + 1;
-    int G = 64 / lps;
-    const int ptr_bytes = 2 * RB_VIEWS * (int)sizeof(const float*);
-    while (G > 1 && 4 * G * RB_VIEWS * (int)sizeof(float2) + ptr_bytes > 64 * 1024) --G;
-    const int lds = 4 * G * RB_VIEWS * (int)sizeof(float2) + ptr_bytes;
-    const int64_t blocks = ((int64_t)n_points + 4 * G - 1) / (4 * G);
-    NDET_REQUIRE(blocks * 4 * G < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many points", fn);
-    hipLaunchKernelGGL(k_ray_stats_bank, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pts, n_points, views_dev, n_views, img_h,
-                       img_w, H, W, d, hf, wf, G, global_feat, pixel_mask, view_count);
-    NDET_CHECK_LAUNCH(fn);
-    return NDET_OK;
+__global__ __launch_bounds__(256) void k_ray_stats_bank(const float* __restrict__ pts, int n_points, const NdetBankView* __restrict__ views,
+                                                        int n_views, float img_h, float img_w, int H, int W, int d, int hf, int wf, int G,
+                                                        float* __restrict__ glob, uint8_t* __restrict__ pixel_mask, int* __restrict__ view_count) {
+    rb_walk(pts, n_points, views, n_views, img_h, img_w, H, W, d, hf, wf, G, glob, pixel_mask, view_count);
 }
 
 // ------------------------------------------------------------------------------------------------
-// view banks of a scene group: k_ray_stats_bank's walk for several banks in one launch.  grid.y = listed scene, grid.x = the largest
-// per-scene block count; a block past its scene's count leaves before it touches LDS or a barrier.  A block serves ONE scene: its
-// points tile by 4 G from that scene's own row 0, so the view count, the rounds, the count pass and both barrier positions are uniform
-// within a block and differ between the blocks of a launch -- the whole difference from k_ray_stats_bank, whose walk is copied here
-// (not shared as a template: that kernel's register figures stay what they were).  The selection rides by value in the kernel
-// arguments with the host's prefix over n_points (the scene's first row of the concatenated points and outputs).
+// view banks of a scene group: rb_walk for several banks in one launch.  grid.y = listed scene, grid.x = the largest per-scene block
+// count; a block past its scene's count leaves before it touches LDS or a barrier.  A block serves ONE scene: its points tile by 4 G
+// from that scene's own row 0, so the view count, the rounds, the count pass and both barrier positions are uniform within a block and
+// differ between the blocks of a launch.  Picking the scene's table, counts and first row out of the kernel arguments is the whole
+// difference from k_ray_stats_bank: the selection rides there by value with the host's prefix over n_points (the scene's first row of
+// the concatenated points and outputs).
 // ------------------------------------------------------------------------------------------------
 struct RbGroupFirst {
     int32_t row[NDET_GROUP_MAX];
@@ -558,117 +508,53 @@ __global__ __launch_bounds__(256) void k_ray_stats_bank_group(const float* __res
                                                               float img_h, float img_w, int H, int W, int d, int hf, int wf, int G,
                                                               float* __restrict__ glob_all, uint8_t* __restrict__ pixel_mask_all,
                                                               int* __restrict__ view_count_all) {
-    extern __shared__ float2 s_bank[];
     const int sc = blockIdx.y;                         // listed scene: block-uniform (scalar loads from the kernel arguments)
     const int n_points = sel.n_points[sc];
     if ((int64_t)blockIdx.x * 4 * G >= (int64_t)n_points) return;   // grid.x padding: the whole block leaves, before LDS and barriers
-    const int n_views = sel.n_views[sc];
-    const NdetBankView* __restrict__ views = sel.views[sc];
     const int64_t row0 = first.row[sc];
-    const int nch = 3 + d;
-    const float* __restrict__ pts = pts_all + row0 * 3;
-    float* __restrict__ glob = glob_all + row0 * 2 * nch;
-    uint8_t* __restrict__ pixel_mask = pixel_mask_all + row0;
-    int* __restrict__ view_count = view_count_all ? view_count_all + row0 : nullptr;
+    rb_walk(pts_all + row0 * 3, n_points, sel.views[sc], sel.n_views[sc], img_h, img_w, H, W, d, hf, wf, G, glob_all + row0 * 2 * (3 + d),
+            pixel_mask_all + row0, view_count_all ? view_count_all + row0 : nullptr);
+}
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lps = (d >> 2) + 1;                      // lanes per sample: [image quad | d/4 feature quads]
-    const int g = lane / lps, sub = lane - g * lps;
-    const int p_base = (blockIdx.x * 4 + wave) * G;
-    float2* rec = s_bank + (size_t)wave * G * RB_VIEWS;
-    const float** s_ptr = reinterpret_cast<const float**>(s_bank + (size_t)4 * G * RB_VIEWS);   // [0,64) feature maps, [64,128) images
-    const int rounds = (n_views + RB_VIEWS - 1) / RB_VIEWS;
-
-    // ---- count pass (more than one round): valid and near views of every sample over all the scene's views ----
-    int cnt = 0, n_near = 0;
-    unsigned long long my_valid = 0ull, my_near = 0ull;
-    if (rounds > 1) {
-        for (int r = 0; r < rounds; ++r) {
-            rb_project_round<false>(pts, n_points, p_base, G, g, lane, views, r * RB_VIEWS + lane, n_views, img_h, img_w, H, W, hf, wf, rec,
-                                    my_valid, my_near);
-            cnt += __popcll(my_valid);
-            n_near += __popcll(my_near);
-        }
+// What both bank entry points ask of the call's shapes and buffers once their own sizes are in order, in the order they report it: d,
+// the view tables' alignment (`listed`: the message names the listed scene), the outputs, the 2^31 limit; then G, the samples per wave
+// (at most 64 / lanes per sample, fewer where 64 KB of LDS ask for it: 31 at d = 4), and the launch's LDS bytes.  Reads no device memory.
+static int rb_check(const char* fn, const NdetBankView* const* tables, int n_tables, bool listed, int H, int W, int d, int hf, int wf,
+                    const float* global_feat, int* G_out, int* lds_out) {
+    NDET_REQUIRE(d % 4 == 0 && d <= 128, NDET_E_UNSUPPORTED, "%s: d=%d must be a multiple of 4, at most 128", fn, d);
+    for (int i = 0; i < n_tables; ++i) {
+        if (((uintptr_t)tables[i] & 7) == 0) continue;
+        if (listed) ndet_set_error("%s: the view table of listed scene %d must be 8-byte aligned", fn, i);
+        else ndet_set_error("%s: the view table must be 8-byte aligned", fn);
+        return NDET_E_UNSUPPORTED;
     }
+    NDET_REQUIRE(((uintptr_t)global_feat & 3) == 0, NDET_E_UNSUPPORTED, "%s: global_feat must be 4-byte aligned", fn);
+    NDET_REQUIRE((int64_t)hf * wf * d < ((int64_t)1 << 31) && (int64_t)H * W * 4 < ((int64_t)1 << 31), NDET_E_UNSUPPORTED,
+                 "%s: a source view exceeds 2^31 floats", fn);
+    const int lps = d / 4 + 1;
+    int G = 64 / lps;
+    const int ptr_bytes = 2 * RB_VIEWS * (int)sizeof(const float*);
+    while (G > 1 && 4 * G * RB_VIEWS * (int)sizeof(float2) + ptr_bytes > 64 * 1024) --G;
+    *G_out = G;
+    *lds_out = 4 * G * RB_VIEWS * (int)sizeof(float2) + ptr_bytes;
+    return NDET_OK;
+}
 
-    const int my_p = p_base + g;
-    const bool on = g < G && my_p < n_points;
-    const bool is_rgb = sub == 0;
-    const int fq = sub - 1;                                   // feature quad of this lane
-    const int Hs = is_rgb ? H : hf, Ws = is_rgb ? W : wf;
-    const int rpitch = is_rgb ? W * 4 : wf * d, pix = is_rgb ? 4 : d;
-    const int poff = is_rgb ? 0 : 4 * fq;
-    const float** my_ptr = s_ptr + (is_rgb ? RB_VIEWS : 0);
-    const float2* myrec = rec + (on ? g : 0) * RB_VIEWS;
-    float denom = (float)cnt + 1e-8f;
-    float wgt = 1.0f / denom;                                 // mask / (sum(mask) + 1e-8), render_ray.py:83
-    RsAcc a;
-    a.acc = a.q = a.s1 = a.piv = make_float4(0.f, 0.f, 0.f, 0.f);
-    a.have = false;
-
-    // ---- walk pass: round by round, lanes over views, then lanes over (sample, channel quad); rounds is the block's ----
-    for (int r = 0; r < rounds; ++r) {
-        if (r > 0) __syncthreads();                           // the round before has read its records and pointers
-        const int v = r * RB_VIEWS + lane;
-        rb_project_round<true>(pts, n_points, p_base, G, g, lane, views, v, n_views, img_h, img_w, H, W, hf, wf, rec, my_valid, my_near);
-        if (wave < 2) s_ptr[wave * RB_VIEWS + lane] = v < n_views ? (wave == 0 ? views[v].feat : views[v].rgb4) : nullptr;
-        if (rounds == 1) {                                    // a single round: its own ballots are the counts
-            cnt = __popcll(my_valid);
-            n_near = __popcll(my_near);
-            denom = (float)cnt + 1e-8f;
-            wgt = 1.0f / denom;
-        }
-        __syncthreads();
-        unsigned long long m = on ? my_near : 0ull;
-        const unsigned long long vm = my_valid;
-        while (__ballot(m != 0ull) != 0ull) {                 // until every sample of the wave has walked its near views
-            const bool h0 = m != 0ull;
-            const int b0 = h0 ? __builtin_ctzll(m) : 0;
-            m = h0 ? (m & (m - 1ull)) : 0ull;
-            const bool h1 = m != 0ull;
-            const int b1 = h1 ? __builtin_ctzll(m) : 0;
-            m = h1 ? (m & (m - 1ull)) : 0ull;
-            const float2 r0 = h0 ? myrec[b0] : make_float2(0.f, 0.f);
-            const float2 r1 = h1 ? myrec[b1] : make_float2(0.f, 0.f);
-            const float* v0 = h0 ? my_ptr[b0] + poff : nullptr;
-            const float* v1 = h1 ? my_ptr[b1] + poff : nullptr;
-            const RsTaps t0 = rs_taps(r0.x, r0.y, Hs, Ws, rpitch, pix), t1 = rs_taps(r1.x, r1.y, Hs, Ws, rpitch, pix);
-            float4 a00 = make_float4(0.f, 0.f, 0.f, 0.f), a01 = a00, a10 = a00, a11 = a00, c00 = a00, c01 = a00, c10 = a00, c11 = a00;
-            if (h0) {
-                a00 = *reinterpret_cast<const float4*>(v0 + t0.o00);
-                a01 = *reinterpret_cast<const float4*>(v0 + t0.o01);
-                a10 = *reinterpret_cast<const float4*>(v0 + t0.o10);
-                a11 = *reinterpret_cast<const float4*>(v0 + t0.o11);
-            }
-            if (h1) {
-                c00 = *reinterpret_cast<const float4*>(v1 + t1.o00);
-                c01 = *reinterpret_cast<const float4*>(v1 + t1.o01);
-                c10 = *reinterpret_cast<const float4*>(v1 + t1.o10);
-                c11 = *reinterpret_cast<const float4*>(v1 + t1.o11);
-            }
-            if (h0) rs_take(a, rs_blend(a00, a01, a10, a11, t0), (vm >> b0) & 1ull, wgt);
-            if (h1) rs_take(a, rs_blend(c00, c01, c10, c11, t1), (vm >> b1) & 1ull, wgt);
-        }
-    }
-    if (!on) return;
-    const float nn = (float)n_near, nf = (float)(n_views - n_near);
-    const float4 mean = a.acc;
-    float4 ev;
-    ev.x = expf(-(rs_var_sum(a.q.x, a.s1.x, a.piv.x, mean.x, nn, nf) / denom));
-    ev.y = expf(-(rs_var_sum(a.q.y, a.s1.y, a.piv.y, mean.y, nn, nf) / denom));
-    ev.z = expf(-(rs_var_sum(a.q.z, a.s1.z, a.piv.z, mean.z, nn, nf) / denom));
-    ev.w = expf(-(rs_var_sum(a.q.w, a.s1.w, a.piv.w, mean.w, nn, nf) / denom));
-    float* row = glob + (int64_t)my_p * 2 * nch;              // cat([mean, exp(-var)], dim=-1), render_ray.py:303
-    if (is_rgb) {
-        row[0] = mean.x; row[1] = mean.y; row[2] = mean.z;
-        row[nch + 0] = ev.x; row[nch + 1] = ev.y; row[nch + 2] = ev.z;
-        pixel_mask[my_p] = cnt > 1 ? 1 : 0;                   // render_ray.py:301
-        if (view_count) view_count[my_p] = cnt;
-    } else {
-        const int c = 3 + 4 * fq;
-        row[c + 0] = mean.x; row[c + 1] = mean.y; row[c + 2] = mean.z; row[c + 3] = mean.w;
-        row[nch + c + 0] = ev.x; row[nch + c + 1] = ev.y; row[nch + c + 2] = ev.z; row[nch + c + 3] = ev.w;
-    }
+extern "C" int ndet_ray_view_stats_bank(const float* pts, int n_points, const NdetBankView* views_dev, int n_views, float img_h, float img_w,
+                                        int H, int W, int d, int hf, int wf, float* global_feat, uint8_t* pixel_mask, int* view_count,
+                                        void* stream) {
+    const char* fn = "ndet_ray_view_stats_bank";
+    static_assert(sizeof(NdetBankView) == 64, "NdetBankView is 64 bytes");
+    NDET_REQUIRE(pts && views_dev && global_feat && pixel_mask, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(n_points > 0 && n_views > 0 && H > 1 && W > 1 && hf > 1 && wf > 1 && d > 0, NDET_E_INVALID, "%s: bad sizes", fn);
+    int G = 0, lds = 0;
+    NDET_TRY(rb_check(fn, &views_dev, 1, false, H, W, d, hf, wf, global_feat, &G, &lds));
+    const int64_t blocks = ((int64_t)n_points + 4 * G - 1) / (4 * G);
+    NDET_REQUIRE(blocks * 4 * G < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: too many points", fn);
+    hipLaunchKernelGGL(k_ray_stats_bank, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pts, n_points, views_dev, n_views, img_h,
+                       img_w, H, W, d, hf, wf, G, global_feat, pixel_mask, view_count);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
 }
 
 extern "C" int ndet_ray_view_stats_bank_group(const float* pts, const NdetBankGroupSel* sel, float img_h, float img_w, int H, int W, int d,
@@ -686,17 +572,8 @@ extern "C" int ndet_ray_view_stats_bank_group(const float* pts, const NdetBankGr
         NDET_REQUIRE(sel->n_views[i] >= 1 && sel->n_points[i] >= 1, NDET_E_INVALID, "%s: bad sizes (listed scene %d: %d views, %d points)", fn, i,
                      sel->n_views[i], sel->n_points[i]);
     }
-    NDET_REQUIRE(d % 4 == 0 && d <= 128, NDET_E_UNSUPPORTED, "%s: d=%d must be a multiple of 4, at most 128", fn, d);
-    for (int i = 0; i < sel->n; ++i)
-        NDET_REQUIRE(((uintptr_t)sel->views[i] & 7) == 0, NDET_E_UNSUPPORTED, "%s: the view table of listed scene %d must be 8-byte aligned", fn, i);
-    NDET_REQUIRE(((uintptr_t)global_feat & 3) == 0, NDET_E_UNSUPPORTED, "%s: global_feat must be 4-byte aligned", fn);
-    NDET_REQUIRE((int64_t)hf * wf * d < ((int64_t)1 << 31) && (int64_t)H * W * 4 < ((int64_t)1 << 31), NDET_E_UNSUPPORTED,
-                 "%s: a source view exceeds 2^31 floats", fn);
-    const int lps = d / 4 + 1;
-    int G = 64 / lps;
-    const int ptr_bytes = 2 * RB_VIEWS * (int)sizeof(const float*);
-    while (G > 1 && 4 * G * RB_VIEWS * (int)sizeof(float2) + ptr_bytes > 64 * 1024) --G;
-    const int lds = 4 * G * RB_VIEWS * (int)sizeof(float2) + ptr_bytes;
+    int G = 0, lds = 0;
+    NDET_TRY(rb_check(fn, sel->views, sel->n, true, H, W, d, hf, wf, global_feat, &G, &lds));
     RbGroupFirst first;
     int64_t total = 0, max_blocks = 0;
     for (int i = 0; i < NDET_GROUP_MAX; ++i) first.row[i] = 0;

@@ -101,6 +101,12 @@ def packed_ok(n_views: int, d: int, backward: bool = False) -> bool:
     return 4 * g * nvp * 8 <= 64 * 1024
 
 
+def _stats_buffers(n: int, d: int, device):
+    """The samplers' outputs for n sample points: ``globalfeat`` (n, 2*(3+d)), ``pixel_mask`` (n,) bool, ``view_count`` (n,) int32."""
+    return (torch.empty((n, 2 * (3 + d)), dtype=torch.float32, device=device), torch.empty((n,), dtype=torch.bool, device=device),
+            torch.empty((n,), dtype=torch.int32, device=device))
+
+
 def ray_view_stats(xyz: Tensor, train_imgs: Tensor, train_cameras: Tensor, featmaps: Tensor):
     """Fused A7+A8: sample points (R,S,3) -> ``globalfeat`` (R,S,2*(3+d)), ``pixel_mask`` (R,S) bool,
     ``view_count`` (R,S) int32.  Equals Projector.compute + compute_mask_points + cat + ``mask.sum(2) > 1``
@@ -116,9 +122,7 @@ def ray_view_stats(xyz: Tensor, train_imgs: Tensor, train_cameras: Tensor, featm
     shape = xyz.shape[:-1]
     pts = xyz.to(torch.float32).reshape(-1, 3).contiguous()
     n = pts.shape[0]
-    glob = torch.empty((n, 2 * (3 + d)), dtype=torch.float32, device=xyz.device)
-    pm = torch.empty((n,), dtype=torch.bool, device=xyz.device)
-    vc = torch.empty((n,), dtype=torch.int32, device=xyz.device)
+    glob, pm, vc = _stats_buffers(n, d, xyz.device)
     nbytes = 4 * (n_v * 3 * rgb.shape[2] * rgb.shape[3] + n_v * d * hf * wf + 2 * (3 + d) * n)
     if packed_ok(n_v, d) and f.stride(0) % 4 == 0 and f.stride(2) % 4 == 0 and f.data_ptr() % 16 == 0:
         rgb4 = packed_rgb(rgb)
@@ -243,6 +247,16 @@ class ViewBank:
         return self._table
 
 
+def _bank_call(bank: ViewBank, n_views: int, n: int):
+    """What a bank sampler's launch over ``n_views`` views and ``n`` sample points takes from the bank's sizes (its oldest segment's, which
+    every segment shares): the entry points' ``(img_h, img_w, H, W, d, hf, wf)``, the outputs on the bank's device, the bytes for the trace."""
+    s0 = bank.segments[0]
+    _, hf, wf, d = s0.feat.shape
+    H, W = s0.rgb4.shape[1], s0.rgb4.shape[2]
+    nbytes = 4 * (n_views * 4 * H * W + n_views * d * hf * wf + 2 * (3 + d) * n)
+    return (*s0.img_hw, H, W, d, hf, wf), _stats_buffers(n, d, s0.feat.device), nbytes
+
+
 def ray_view_stats_bank(xyz: Tensor, bank: ViewBank):
     """:func:`ray_view_stats` over a :class:`ViewBank`: sample points (R,S,3) -> ``globalfeat`` (R,S,2*(3+d)), ``pixel_mask`` (R,S) bool,
     ``view_count`` (R,S) int32 (projection.py:91-151 + render_ray.py:71-93, 299-303), for any number of views in any number of segments.
@@ -253,18 +267,12 @@ def ray_view_stats_bank(xyz: Tensor, bank: ViewBank):
     s0 = bank.segments[0]
     if xyz.device != s0.feat.device:
         raise ValueError("ray_view_stats_bank: the points and the bank live on different devices")
-    _, hf, wf, d = s0.feat.shape
-    H, W = s0.rgb4.shape[1], s0.rgb4.shape[2]
-    h, w = s0.img_hw
     shape = xyz.shape[:-1]
     pts = xyz.to(torch.float32).reshape(-1, 3).contiguous()
     n = pts.shape[0]
-    glob = torch.empty((n, 2 * (3 + d)), dtype=torch.float32, device=xyz.device)
-    pm = torch.empty((n,), dtype=torch.bool, device=xyz.device)
-    vc = torch.empty((n,), dtype=torch.int32, device=xyz.device)
-    nbytes = 4 * (n_v * 4 * H * W + n_v * d * hf * wf + 2 * (3 + d) * n)
+    geom, (glob, pm, vc), nbytes = _bank_call(bank, n_v, n)
     trace.span("k_ray_stats_bank", lambda: check(
-        _lib.load().ndet_ray_view_stats_bank(_ptr(pts), n, _ptr(table), n_v, h, w, H, W, d, hf, wf, _ptr(glob), _ptr(pm), _ptr(vc), _stream(xyz)),
+        _lib.load().ndet_ray_view_stats_bank(_ptr(pts), n, _ptr(table), n_v, *geom, _ptr(glob), _ptr(pm), _ptr(vc), _stream(xyz)),
         "ray_view_stats_bank"), bytes=nbytes, kind="hbm")
     return glob.view(*shape, -1), pm.view(*shape), vc.view(*shape)
 
@@ -307,25 +315,17 @@ def bank_group_stats(xyz_list, banks):
             raise ValueError(f"ray_view_stats_bank_group: bank {i} or its points live on another device than bank 0")
         if x.shape[-1] != 3 or x.numel() == 0:
             raise ValueError(f"ray_view_stats_bank_group: points {tuple(x.shape)} of bank {i} must be (..., 3) with at least one point")
-    _, hf, wf, d = s0.feat.shape
-    H, W = s0.rgb4.shape[1], s0.rgb4.shape[2]
-    h, w = s0.img_hw
     flat = [x.to(torch.float32).reshape(-1, 3) for x in xyz_list]
     counts = [f.shape[0] for f in flat]
     pts = flat[0].contiguous() if n == 1 else torch.cat(flat, dim=0)
-    total = pts.shape[0]
     sel = _lib.NdetBankGroupSel()
     sel.size, sel.n = ctypes.sizeof(_lib.NdetBankGroupSel), n
     for i, ((table, n_v), c) in enumerate(zip(tables, counts)):
         sel.views[i], sel.n_views[i], sel.n_points[i] = table.data_ptr(), n_v, c
-    glob = torch.empty((total, 2 * (3 + d)), dtype=torch.float32, device=dev)
-    pm = torch.empty((total,), dtype=torch.bool, device=dev)
-    vc = torch.empty((total,), dtype=torch.int32, device=dev)
-    n_v_all = sum(t[1] for t in tables)
-    nbytes = 4 * (n_v_all * 4 * H * W + n_v_all * d * hf * wf + 2 * (3 + d) * total)
+    geom, (glob, pm, vc), nbytes = _bank_call(banks[0], sum(t[1] for t in tables), pts.shape[0])
     trace.span("k_ray_stats_bank_group", lambda: check(
-        _lib.load().ndet_ray_view_stats_bank_group(_ptr(pts), ctypes.byref(sel), h, w, H, W, d, hf, wf, _ptr(glob), _ptr(pm), _ptr(vc),
-                                                   _stream(pts)), "ray_view_stats_bank_group"), bytes=nbytes, kind="hbm")
+        _lib.load().ndet_ray_view_stats_bank_group(_ptr(pts), ctypes.byref(sel), *geom, _ptr(glob), _ptr(pm), _ptr(vc), _stream(pts)),
+        "ray_view_stats_bank_group"), bytes=nbytes, kind="hbm")
     return glob, pm, vc, pts
 
 

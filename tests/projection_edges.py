@@ -1,7 +1,7 @@
 """Exact scenes for the projecting kernels: every decision a kernel takes about a (point, view) pair is put ON its edge, not near it.
 
 Both projection rules of the project -- nearest pixel (ndet_project_z: round-half-even, 0 <= x < w, d > 0, strict depth band) and bilinear
-(ray_project / rs_project / bwd_ray_project: denominator clamped at 1e-8, pixel clamped to +-1e6, 0 <= px <= w-1 inclusive, q2 > 0, zero
+(ndet_ray_project: denominator clamped at 1e-8, pixel clamped to +-1e6, 0 <= px <= w-1 inclusive, q2 > 0, zero
 padded align_corners=True taps) -- are fed cameras whose matrices hold small dyadic numbers only (focal length 16, integer principal
 point, axis-aligned rotations, dyadic translations) and points with dyadic coordinates.  u, v, d and the quotients are then exactly
 representable: the float32 chain of the kernels and a float64 evaluation agree bit for bit on every decision, so masks and counts can be
@@ -373,7 +373,7 @@ def nearest_rule(points, projection, h, w, slip=None, depth=None):
 
 
 def bilinear_rule(points, ke, h, w, hf, wf, slip=None):
-    """ray_project / rs_project / bwd_ray_project and the tap rule of rs_taps with ``slip``: (mask (n, n_v), tap (n, n_v): some tap of the
+    """ndet_ray_project and the tap rule of rs_taps with ``slip``: (mask (n, n_v), tap (n, n_v): some tap of the
     view lies inside the hf x wf map with a nonzero weight)."""
     hom = torch.cat([points.t(), torch.ones(1, points.shape[0])]).numpy()[None]
     q = torch.from_numpy(O.fma_chain_matmul(ke.numpy(), hom))

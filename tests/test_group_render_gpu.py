@@ -1,5 +1,6 @@
 """GPU checks of view banks and rendering for scene groups: the grouped bank sampler (csrc/ray_stats_kernels.hip: k_ray_stats_bank_group,
-rays.ray_view_stats_bank_group) against the single-bank sampler run per scene on the same banks, and SceneGroup(keep_views=True)
+rays.ray_view_stats_bank_group) against the single-bank sampler run per scene on the same banks -- the two kernels share one body, so
+once against the packed and the generic kernels, which do not -- and SceneGroup(keep_views=True)
 (nerf-det_amd/streaming.py): banks that follow the states, render_rays / render against the one-shot ray branch and SceneStream."""
 import numpy as np
 import pytest
@@ -9,6 +10,7 @@ from oracle import nerfdet_oracle as O
 
 pytestmark = pytest.mark.gpu
 
+ATOL = 2e-5      # tests/test_stream_render_gpu.py: the one-pass statistics against the generic (two-pass) kernel on identical fp32 coordinates
 R, S = 257, 19   # 4883 samples: not a multiple of any samples-per-block
 
 _CACHE = {}
@@ -179,6 +181,45 @@ def test_repeated_calls_leave_tables_and_banks_unchanged(device):
         for s, (f, i, k, fp, ip) in zip(bank.segments, segs):
             assert torch.equal(s.feat, f) and torch.equal(s.rgb4, i) and torch.equal(s.ke, k) and (s.feat.data_ptr(), s.rgb4.data_ptr()) == (fp, ip)
     _equal(rays.ray_view_stats_bank(pts[0], banks[0]), a[0], "the single-bank sampler after the grouped calls")
+
+
+# ---- K-f: against kernels that do not share the bank samplers' body ----
+@pytest.mark.parametrize("d,hw,spb", [(8, (60, 80), 84), (32, (64, 96), 28)])
+def test_grouped_sampler_equals_the_packed_and_generic_kernels(device, d, hw, spb):
+    """One launch over banks of 9, 40, 64, 100 and 130 views, with 1, 4G - 1 or 4G + 1 points each, every scene against rays.ray_view_stats
+    over the concatenated segments.  Where that call takes k_ray_stats_packed the scene is its bits: 9, 40 and 64 views (no count pass, one
+    round, a round of exactly 64) and, at d = 32, 100 views (count pass, two rounds).  Where it takes the generic kernel -- 130 views, and 100
+    views at d = 8, whose records for two rounds of 21 samples a wave exceed the packed kernel's 64 KB of LDS -- the masks and counts are
+    equal and the statistics within ATOL (tests/test_stream_render_gpu.py::test_more_than_128_views_match_generic_kernel).  Neither
+    reference runs rb_walk."""
+    from nerfdet_amd import rays, trace
+    assert _samples_per_block(d) == spb
+    segs = [[4, 5], [40], [63, 1], [63, 2, 35], [64, 2, 64]]
+    counts = [spb + 1, 1, spb - 1, spb + 1, spb - 1]
+    inps = [_inputs(device, sum(s), d, hw, seed=30 + i) for i, s in enumerate(segs)]
+    banks = [_bank(inp, s) for inp, s in zip(inps, segs)]
+    pts = [inp["pts"].reshape(-1, 3)[R * S // 2 - c // 2:][:c] for inp, c in zip(inps, counts)]
+    assert [p.shape[0] for p in pts] == counts and [b.n_views for b in banks] == [9, 40, 64, 100, 130]
+    prev, trace.recorder = trace.recorder, trace.Recorder()
+    try:
+        got = rays.ray_view_stats_bank_group(pts, banks)
+        want = [rays.ray_view_stats(p, inp["img"], rays._compute_projection(inp["meta"]), inp["feat"]) for p, inp in zip(pts, inps)]
+        names = [sp[0] for sp in trace.recorder.spans]
+    finally:
+        trace.recorder = prev
+    packed = [rays.packed_ok(b.n_views, d) for b in banks]
+    assert packed == [True, True, True, d == 32, False]
+    assert names == ["k_ray_stats_bank_group"] + ["k_ray_stats_packed" if p else "k_ray_view_stats" for p in packed], names
+    for i, (g, w) in enumerate(zip(got, want)):
+        what = f"d={d}: {banks[i].n_views} views, {counts[i]} points"
+        assert g[0].shape == w[0].shape == (counts[i], 2 * (3 + d))
+        if packed[i]:
+            _equal(g, w, what + " against the packed kernel")
+            continue
+        print(f"{what}: max |group - generic| = {float((g[0] - w[0]).abs().max()):.3e} (bound {ATOL:.0e})")
+        assert torch.equal(g[1], w[1]) and torch.equal(g[2], w[2]), what + " against the generic kernel: masks or counts differ"
+        torch.testing.assert_close(g[0], w[0], rtol=0, atol=ATOL)
+    assert any(bool(g[1].any()) for g in got), "no sample of the call is seen by more than one view"
 
 
 # ---- detector level ----
