@@ -870,6 +870,25 @@ int ndet_pack_frames(const float* rgb, const float* depth, const uint8_t* mask, 
 int ndet_frame_errors(const uint8_t* a, const uint8_t* b, const uint16_t* da, const uint16_t* db, int n, int64_t px, int64_t* out,
                       void* stream);
 
+/* ndet_frame_ssim: the structural similarity of frames a (a render) and b (held-out frames), as integer sums per frame and channel (the
+ * reference's compute_ssim, mmdet3d/models/model_utils/save_rendered_img.py:21-36,51-78 -> skimage.metrics.structural_similarity of
+ * scikit-image 0.18.1 with multichannel=True: 7 x 7 uniform window, sample covariance, K1 = 0.01, K2 = 0.03, data range 2 on float images,
+ * the mean over the window-valid interior).  a, b (n, h, w, 3) contiguous, uint8 (kind 0) or float32 (kind 1); depth_a (n, h, w) uint16 or
+ * NULL; out (n,4) int64 on the device: Q_0, Q_1, Q_2, n_w.  Per frame and channel the windows are the (h-6)(w-6) valid 7 x 7 windows; a
+ * window COUNTS iff all its 49 pixels have depth_a != 0 (every window without depth_a).  For a counting window, with Sx, Sy, Sxx, Syy, Sxy
+ * the sums over its 49 pixels of one channel (kind 0: exact integers of the bytes),
+ *     C1 = (0.01*2*255)^2 * 49^2, C2 = (0.03*2*255)^2 * 49*48      (kind 1: without the 255 factors), float64
+ *     A1 = (double)(2 Sx Sy) + C1                A2 = (double)(2 (49 Sxy - Sx Sy)) + C2
+ *     B1 = (double)(Sx^2 + Sy^2) + C1            B2 = (double)(49 Sxx - Sx^2 + 49 Syy - Sy^2) + C2
+ *     s = (A1 A2) / (B1 B2)  in IEEE float64, one rounding per operation;    q = llrint(s * 2^40), ties to even
+ * and Q_c = sum of q over the counting windows of channel c, n_w their number: SSIM_c = Q_c / (2^40 n_w).  Integer sums, so kind 0 gives
+ * the same bytes for any tile shape and atomic order.  Kind 1 forms every window's sums in float64 in one fixed order (each row's 7 terms
+ * left to right, then the 7 row sums top to bottom; a product of two float32 is exact): the same bytes call to call and at any place in
+ * the batch.  A memset node in front of the launch zeroes out.  n < 1, h or w below 7, a kind other than 0 and 1: NDET_E_INVALID;
+ * (h-6)(w-6) >= 2^22 (keeps |Q_c| < 2^62), n * h * w * 3 >= 2^31, a misaligned depth_a or out, misaligned float32 frames:
+ * NDET_E_UNSUPPORTED. */
+int ndet_frame_ssim(const void* a, const void* b, const uint16_t* depth_a, int kind, int n, int h, int w, int64_t* out, void* stream);
+
 /* ---- detections out: the 3D boxes of a detection result in a camera's image -- projected, drawn onto a frame, matched to a depth frame.
  * Every entry point checks its arguments on the host before any HIP call: a null pointer, a non-positive size, stride < 1, a negative
  * offset, near <= 0 and a thickness other than 1, 3, 5 are NDET_E_INVALID; 2^31 elements or more, a misaligned pointer and more boxes than

@@ -169,6 +169,7 @@ SIGNATURES = {
     "ndet_camera_rays": ([_P, _P, _P] + [c_int] * 6 + [_P, _P, _P], c_int),
     "ndet_pack_frames": ([_P, _P, _P, c_int64, _P, _P, _P], c_int),
     "ndet_frame_errors": ([_P, _P, _P, _P, c_int, c_int64, _P, _P], c_int),
+    "ndet_frame_ssim": ([_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P], c_int),
     "ndet_project_boxes": ([_P, _P, _P] + [c_int] * 7 + [c_float, _P, _P, _P, _P, _P], c_int),
     "ndet_draw_boxes": ([_P, _P, _P, _P] + [c_int] * 5 + [_P, _P], c_int),
     "ndet_label_frames": ([_P] * 5 + [c_int] * 7 + [_P, _P], c_int),

@@ -17,7 +17,8 @@ The sensor's depth frames (uint16 millimetres on the device) go the same way: :f
 The output side speaks the same formats: :func:`camera_rays` makes the rays of any camera pose without a frame (ndet_camera_rays:
 ndet_target_rays' arithmetic), :func:`pack_frames` turns a render into uint8 BGR and uint16 millimetre frames (ndet_pack_frames), and
 :func:`frame_errors` compares two such frames on the device with exact integer sums (ndet_frame_errors) -- what
-``SceneStream / SceneGroup.render_frames`` and ``score_frames`` stand on.
+``SceneStream / SceneGroup.render_frames`` and ``score_frames`` stand on.  :func:`frame_ssim` is the reference's second metric for the
+same frames, and for float renders: one fused 7 x 7 window kernel with integer sums per frame and channel (ndet_frame_ssim).
 
 A detection result goes the same way into the camera's image: :func:`project_boxes` says where boxes fall in the frames of given poses
 (ndet_project_boxes), :func:`draw_boxes` puts their wireframes onto frames in device memory (ndet_draw_boxes) and :func:`label_frames` says
@@ -295,6 +296,49 @@ def frame_errors(frames_a: torch.Tensor, frames_b: torch.Tensor, depth_a: torch.
     sse, n_px = out[:, 0], out[:, 1]
     psnr = 10.0 * torch.log10(255.0 ** 2 * 3.0 * n_px.to(torch.float64) / sse.to(torch.float64))
     return dict(sse=sse, n_px=n_px, depth_sad_mm=out[:, 2], n_depth=out[:, 3], psnr=psnr)
+
+
+SSIM_TILE = (16, 32)     # window rows and columns a workgroup of k_frame_ssim owns (SSIM_TH, SSIM_TW in csrc/frame_ssim_kernels.hip)
+SSIM_WINDOW = 7
+
+
+def frame_ssim(frames_a: torch.Tensor, frames_b: torch.Tensor, depth_a=None) -> dict:
+    """The structural similarity of frames a (a render) and frames b (held-out frames) on the device, the reference's second render metric
+    (save_rendered_img.py:21-36: scikit-image 0.18.1's ``structural_similarity(multichannel=True)`` -- 7 x 7 uniform window, sample
+    covariance, K1 = 0.01, K2 = 0.03, data range 2, the window-valid interior).  ``frames_*`` (n, h, w, 3), both uint8 (bytes, scored as
+    x / 255) or both float32; ``depth_a`` optionally (n, h, w) uint16: a window counts only if all its 49 pixels have ``depth_a != 0``.  One
+    launch behind a memset node (ndet_frame_ssim, which states the arithmetic) gives ``ssim_sum`` (n, 3) int64 -- per channel the sum over
+    the counting windows of ``llrint(s * 2^40)`` -- and ``n_windows`` (n,) int64; for bytes every box sum is an exact integer and the sums
+    are the same bytes on every call, whatever the tiling.  By torch on the device, in float64: ``ssim_channels`` (n, 3) =
+    ``ssim_sum / (2^40 n_windows)`` and ``ssim`` (n,) their mean, nan where ``n_windows == 0``.  ValueError for wrong shapes or dtypes and
+    for h or w below 7, RuntimeError for CPU tensors."""
+    a, b = frames_a, frames_b
+    if (not isinstance(a, torch.Tensor) or not isinstance(b, torch.Tensor) or a.dtype not in (torch.uint8, torch.float32) or b.dtype != a.dtype
+            or a.dim() != 4 or a.shape[-1] != 3 or 0 in a.shape or b.shape != a.shape or not a.is_contiguous() or not b.is_contiguous()):
+        raise ValueError(f"frame_ssim takes two contiguous (n, h, w, 3) tensors of one shape, both uint8 or both float32, got "
+                         f"{tuple(getattr(a, 'shape', ()))} {getattr(a, 'dtype', None)} and {tuple(getattr(b, 'shape', ()))} {getattr(b, 'dtype', None)}")
+    if depth_a is not None and (not isinstance(depth_a, torch.Tensor) or depth_a.dtype != torch.uint16 or depth_a.shape != a.shape[:3]
+                                or not depth_a.is_contiguous()):
+        got = f"{tuple(depth_a.shape)} {depth_a.dtype}" if isinstance(depth_a, torch.Tensor) else type(depth_a).__name__
+        raise ValueError(f"frame_ssim takes depth_a as a contiguous {tuple(a.shape[:3])} uint16 tensor (millimetres), got {got}")
+    n, h, w = (int(v) for v in a.shape[:3])
+    if h < SSIM_WINDOW or w < SSIM_WINDOW:
+        raise ValueError(f"frame_ssim: frames of {h} x {w} pixels hold no {SSIM_WINDOW} x {SSIM_WINDOW} window")
+    if (h - SSIM_WINDOW + 1) * (w - SSIM_WINDOW + 1) >= 2 ** 22:
+        raise ValueError(f"frame_ssim: frames of {h} x {w} pixels hold 2^22 windows or more")
+    if n * h * w * 3 >= 2 ** 31:
+        raise ValueError(f"frame_ssim: {n} frames of {h} x {w} pixels hold 2^31 elements or more")
+    if not a.is_cuda or b.device != a.device or (depth_a is not None and depth_a.device != a.device):
+        raise RuntimeError("nerfdet_amd.pipeline: frames must live on the GPU (no CPU fallback)")
+    dev = a.device
+    out = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    check(_lib.load().ndet_frame_ssim(_ptr(a), _ptr(b), _ptr(depth_a), 0 if a.dtype == torch.uint8 else 1, n, h, w, _ptr(out),
+                                      c_void_p(_lib.raw_stream(dev))), "frame_ssim")
+    ssim_sum, n_windows = out[:, :3], out[:, 3]
+    ssim_channels = ssim_sum.to(torch.float64) / (float(2 ** 40) * n_windows.to(torch.float64)).unsqueeze(1)
+    # elementwise, one rounding per operation, in this order; a tensor divisor, for torch multiplies by the reciprocal of a scalar one
+    ssim = (ssim_channels[:, 0] + ssim_channels[:, 1] + ssim_channels[:, 2]) / torch.full_like(n_windows, 3, dtype=torch.float64)
+    return dict(ssim_sum=ssim_sum, n_windows=n_windows, ssim_channels=ssim_channels, ssim=ssim)
 
 
 # BGR, one colour a class, repeated beyond the table (the 18 ScanNet classes get 18 distinct colours)

@@ -696,16 +696,30 @@ def compute_ssim(pred: Tensor, target: Tensor) -> Tensor:
     return s.mean(dim=(2, 3)).mean()
 
 
-def rendering_metrics(rendered: dict, which: str = "outputs_coarse"):
+def ssim_views(pred: Tensor, target: Tensor) -> Tensor:
+    """:func:`compute_ssim` of n views at once: ``pred``, ``target`` (n,H,W,3) float32 on the device -> (n,) float64, from ONE launch of the
+    fused window kernel (pipeline.frame_ssim's float form: float64 box sums in a fixed order, the per-window values summed as integers
+    of 2^-40, so the same bytes on every call).  Agrees with :func:`compute_ssim` per view to 1e-10."""
+    from .pipeline import frame_ssim
+    if not isinstance(pred, Tensor) or not isinstance(target, Tensor) or pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError("ssim_views takes two float32 (n, H, W, 3) tensors")
+    return frame_ssim(pred.contiguous(), target.contiguous())["ssim"]
+
+
+def rendering_metrics(rendered: dict, which: str = "outputs_coarse", fused: bool = False):
     """What ``save_rendered_img`` returns (model_utils/save_rendered_img.py:38-78) for one ``render_rays(render_testing=True)`` result,
     without its PNG dump: mean PSNR and mean SSIM over the target views (device scalars) and the mean squared depth error MAP
     (H,W,1) the reference calls rmse (None without depth maps).  ``which``: ``'outputs_coarse'`` (the reference's) or
-    ``'outputs_fine'`` of a render with ``N_importance > 0``."""
+    ``'outputs_fine'`` of a render with ``N_importance > 0``.  ``fused=True``: the SSIM of all the views from one :func:`ssim_views`
+    launch in place of :func:`compute_ssim` view by view (within 1e-10 of it); PSNR and the depth error are the same code either way."""
     rgb, gt = rendered[which]["rgb"], rendered["gt_rgb"]
     depth, gt_depth = rendered[which]["depth"], rendered["gt_depth"]
     n = gt.shape[0]
     psnr = torch.stack([compute_psnr(rgb[v], gt[v]) for v in range(n)]).mean()
-    ssim = torch.stack([compute_ssim(rgb[v], gt[v]) for v in range(n)]).mean()
+    if fused:
+        ssim = ssim_views(rgb, gt).mean()
+    else:
+        ssim = torch.stack([compute_ssim(rgb[v], gt[v]) for v in range(n)]).mean()
     err = None if gt_depth is None else ((depth - gt_depth) ** 2).mean(dim=0)
     return psnr, ssim, err
 

@@ -49,7 +49,8 @@ ndet_resize_normalize_views; ``mean`` / ``std`` are ``begin_scene(s)`` keywords)
 come from one launch (pipeline.camera_rays, ndet_camera_rays -- a pose needs no frame), go through ``render_rays``' passes, and one launch
 packs the result into (k, h, w, 3) uint8 BGR and (k, h, w) uint16 millimetre frames beside the float outputs (pipeline.pack_frames; depth 0
 is a hole); ``window`` crops, ``stride`` makes a thumbnail.  ``score_frames(frames, meta, depth_frames=)`` compares such a render with
-held-out capture-resolution frames on the device (pipeline.frame_errors: integer sums per frame and their PSNR) and adds nothing to the scene.
+held-out capture-resolution frames on the device (pipeline.frame_errors: integer sums per frame and their PSNR; with ``ssim=True`` also
+pipeline.frame_ssim: the SSIM per frame from one fused window kernel) and adds nothing to the scene.
 
 ``scene.draw_detections(frames, result, c2w= | extrinsic=)`` / ``label_detections(depth_frames, result, ...)`` (and the group's, with one
 list per listed scene) put a detection result into the camera's image: the kept boxes' corners go up in one upload, one launch projects
@@ -70,7 +71,7 @@ import torch
 
 from . import conv3d, ops
 from .pipeline import (IMG_MEAN, IMG_STD, _host_matrices, camera_rays, check_window, class_palette, depth_to_mm, draw_boxes, frame_errors,
-                       label_frames, pack_frames, prepare_depth_frames, prepare_frames, project_boxes, rescale_size)
+                       SSIM_WINDOW, frame_ssim, label_frames, pack_frames, prepare_depth_frames, prepare_frames, project_boxes, rescale_size)
 from .volume import map_features_2d, map_features_2d_hip
 
 Tensor = torch.Tensor
@@ -357,10 +358,11 @@ def _prepared_frames(frames: Tensor, depth_frames, depth, img_shape, img_scale, 
     return chunks(img), chunks(denorm), depth
 
 
-def _score_held_out(first: dict, scene_metas, frames: Tensor, chunk_metas, depth_frames, stride, n_importance, mean, std):
+def _score_held_out(first: dict, scene_metas, frames: Tensor, chunk_metas, depth_frames, stride, n_importance, mean, std, ssim=False):
     """Everything ``score_frames`` checks of its own arguments, before any launch, and then its held-out side (:func:`_held_out`) for the
     n listed scenes' rows of k frames at once: ``(held (n k, h, w, 3), held depth (n k, h, w) or None, k, n_importance)``.  ``first``: the
-    meta that says what becomes of a frame (a group's scenes share it)."""
+    meta that says what becomes of a frame (a group's scenes share it).  ``ssim``: the call also wants pipeline.frame_ssim, which needs a
+    strided content region of at least 7 x 7 pixels."""
     n = len(scene_metas)
     img_scale, pad_size = check_frames_meta(first, frames, n)
     if len(chunk_metas) != n:
@@ -371,9 +373,24 @@ def _score_held_out(first: dict, scene_metas, frames: Tensor, chunk_metas, depth
     check_depth_frames(depth_frames, None, n, k)
     n_importance = _check_n_importance(n_importance)
     grid = _frame_grid(first, None, stride)
+    if not isinstance(ssim, bool):
+        raise ValueError(f"score_frames: ssim must be a bool, got {ssim!r}")
+    if ssim and min(grid[0][2], grid[0][3]) < SSIM_WINDOW:
+        raise ValueError(f"score_frames: ssim=True needs frames of at least {SSIM_WINDOW} x {SSIM_WINDOW} pixels, stride {grid[1]} leaves "
+                         f"{grid[0][2]} x {grid[0][3]}")
     rows = lambda t: t.reshape((n * k,) + tuple(t.shape[2:]))
     held, held_depth = _held_out(rows(frames), None if depth_frames is None else rows(depth_frames), first, img_scale, pad_size, mean, std, grid)
     return held, held_depth, k, n_importance
+
+
+def _frame_scores(out: dict, held: Tensor, held_depth, ssim: bool) -> dict:
+    """What ``score_frames`` returns for one scene: pipeline.frame_errors of the render ``out`` against the held-out frames and, with
+    ``ssim``, pipeline.frame_ssim's ``ssim``, ``ssim_channels`` and ``n_windows`` beside it."""
+    scores = frame_errors(out["frames"], held, out["depth_frames"], held_depth)
+    if ssim:
+        s = frame_ssim(out["frames"], held, out["depth_frames"])
+        scores.update(ssim=s["ssim"], ssim_channels=s["ssim_channels"], n_windows=s["n_windows"])
+    return scores
 
 
 def _camera_lists(c2w, extrinsic, what: str) -> list:
@@ -724,7 +741,8 @@ class SceneStream:
         coarse, fine = self._render(ray_o.view(-1, 3), ray_d.view(-1, 3), rays.RENDER_TESTING_RAYS, n_importance)
         return _frames_dict(coarse, fine, (poses.shape[0], win[2], win[3]))
 
-    def score_frames(self, frames: Tensor, meta: dict, depth_frames: Optional[Tensor] = None, stride: int = 1, n_importance: int = 0) -> dict:
+    def score_frames(self, frames: Tensor, meta: dict, depth_frames: Optional[Tensor] = None, stride: int = 1, n_importance: int = 0,
+                     ssim: bool = False) -> dict:
         """Held-out camera frames against the scene's render of their poses, on the device: ``frames`` (1, k, Hs, Ws, 3) uint8 BGR at capture
         resolution, checked against the scene as :meth:`add_frames` checks them; ``meta`` a chunk meta with the k extrinsics; ``depth_frames``
         optionally the sensor's (1, k, Hd, Wd) uint16 millimetres.  The held-out bytes are pipeline.prepare_frames' resized bytes cropped to
@@ -732,11 +750,15 @@ class SceneStream:
         pipeline.prepare_depth_frames at the content size, strided the same way and quantised by pack_frames' rule (pipeline.depth_to_mm);
         the render is :meth:`render_frames` of the extrinsics.  Returns ``pipeline.frame_errors(render, held_out, render_depth,
         held_out_depth)``: per frame ``sse``, ``n_px``, ``depth_sad_mm``, ``n_depth`` (int64) and ``psnr`` (float64) over the pixels the
-        render has a depth for.  Nothing is added to the scene."""
+        render has a depth for.  With ``ssim=True`` one more launch (``pipeline.frame_ssim(render, held_out, render_depth)``) adds the
+        reference's second metric over the 7 x 7 windows the render has a depth for throughout: ``ssim``, ``ssim_channels`` (float64) and
+        ``n_windows`` (int64) per frame, on the strided frames as they are; a strided content region below 7 x 7 pixels is then a
+        ValueError before any launch.  Nothing is added to the scene."""
         self._need_bank("score_frames")
-        held, held_depth, _, n_importance = _score_held_out(self.meta, [self.meta], frames, [meta], depth_frames, stride, n_importance, self.mean, self.std)
+        held, held_depth, _, n_importance = _score_held_out(self.meta, [self.meta], frames, [meta], depth_frames, stride, n_importance, self.mean, self.std,
+                                                            ssim)
         out = self.render_frames(extrinsic=meta["lidar2img"]["extrinsic"], stride=stride, n_importance=n_importance)
-        return frame_errors(out["frames"], held, out["depth_frames"], held_depth)
+        return _frame_scores(out, held, held_depth, ssim)
 
     def draw_detections(self, frames: Tensor, result: dict, c2w=None, extrinsic=None, window=None, stride: int = 1, capture: bool = False,
                         score_thr: float = 0.0, thickness: int = 1, palette=None) -> dict:
@@ -1133,19 +1155,21 @@ class SceneGroup:
         return [_frames_dict(coarse, fine, (p.shape[0], win[2], win[3])) for (coarse, fine), p in zip(res, poses)]
 
     def score_frames(self, frames: Tensor, metas, scenes=None, depth_frames: Optional[Tensor] = None, batched: bool = False, stride: int = 1,
-                     n_importance: int = 0):
+                     n_importance: int = 0, ssim: bool = False):
         """:meth:`SceneStream.score_frames` for the listed scenes at once: ``frames`` (len(scenes), k, Hs, Ws, 3) uint8 BGR, one row of k
         held-out frames per listed scene, checked as :meth:`add_frames` checks them; ``metas`` one chunk meta per row with its k extrinsics;
         ``depth_frames`` optionally (len(scenes), k, Hd, Wd) uint16 millimetres.  One ndet_resize_normalize_views launch (and one
         ndet_depth_frames launch) makes all the held-out frames, :meth:`render_frames` all the renders, and one ndet_frame_errors launch
-        per scene compares them.  Returns a list of ``pipeline.frame_errors`` dicts; nothing is added to any scene."""
+        per scene compares them -- with ``ssim=True`` one ndet_frame_ssim launch per scene beside it, which adds ``ssim``, ``ssim_channels``
+        and ``n_windows`` as in :meth:`SceneStream.score_frames`.  Returns a list of ``pipeline.frame_errors`` dicts; nothing is added to
+        any scene."""
         scenes = self._need_banks("score_frames", scenes)
         metas = list(metas)
         held, held_depth, k, n_importance = _score_held_out(self.metas[0], [self.metas[s] for s in scenes], frames, metas, depth_frames, stride, n_importance,
-                                                            self.mean, self.std)
+                                                            self.mean, self.std, ssim)
         outs = self.render_frames(extrinsic=[m["lidar2img"]["extrinsic"] for m in metas], scenes=scenes, batched=batched, stride=stride,
                                   n_importance=n_importance)
-        return [frame_errors(out["frames"], held[i * k:(i + 1) * k], out["depth_frames"], None if held_depth is None else held_depth[i * k:(i + 1) * k])
+        return [_frame_scores(out, held[i * k:(i + 1) * k], None if held_depth is None else held_depth[i * k:(i + 1) * k], ssim)
                 for i, out in enumerate(outs)]
 
     def _plan_detections(self, frames, results, c2w, extrinsic, scenes, trailing, dtype, window, stride, capture, score_thr, palette, what: str):
