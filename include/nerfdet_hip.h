@@ -501,6 +501,47 @@ typedef struct NdetBankGroupSel {
 int ndet_ray_view_stats_bank_group(const float* pts, const NdetBankGroupSel* sel, float img_h, float img_w, int H, int W, int d, int hf,
                                    int wf, float* global_feat, uint8_t* pixel_mask, int* view_count, void* stream);
 
+/* ---- empty-space skipping for renders from a streamed scene (nerf-det_amd/streaming.py, skip_empty=; the reference renders every sample).
+ * Every entry point checks its arguments on the host before any HIP call: a null pointer, a non-positive size, dilate outside 0 .. 2, a
+ * non-finite threshold or lattice origin, a voxel size that is not positive and finite and an unknown `outside` are NDET_E_INVALID; 2^31
+ * points or voxels or more, a misaligned pointer and more than 2^24 workgroups are NDET_E_UNSUPPORTED.  Plain vector stores, no global
+ * atomics: every output is the same bytes on every call.
+ *
+ * ndet_occupancy_bits: the alpha of the voxel lattice (1 - exp(-relu(sigma)), nerfdet.py:255-257 -- the density volume a detect() computes;
+ * k_composite applies the same expression to a sample, render_ray.py:196-247) as a dilated bit grid.  alpha (N) float32 and count (N)
+ * int64 (the `valid` of ndet_scene_volume_finish) in the lattice's flat order n = (ix ny + iy) nz + iz, N = nx ny nz.  Voxel n is SOLID iff
+ * !(alpha[n] <= threshold) || count[n] == 0: a NaN alpha is solid, and so is a voxel no view saw.  Bit n (word n >> 5, bit n & 31 of
+ * uint32 bits[(N + 31) / 32]; the last word's spare bits are 0) is set iff any voxel within Chebyshev distance `dilate` of n, inside the
+ * grid, is solid.  One thread per voxel, a wave's ballot is two whole words. */
+int ndet_occupancy_bits(const float* alpha, const int64_t* count, int nx, int ny, int nz, float threshold, int dilate, uint32_t* bits,
+                        void* stream);
+
+#define NDET_OUTSIDE_KEEP 0 /* a point outside the lattice is kept */
+#define NDET_OUTSIDE_CULL 1 /* ... is culled */
+
+/* Ordered compaction of n_points sample points (n_points, 3) against the bits of ndet_occupancy_bits (sample_along_camera_ray's points,
+ * render_ray.py:145-189).  The lattice: n_voxels[3], p0[3] its first point, vs[3] the voxel size, HOST arrays.  Per axis, in float32 and
+ * this statement order,   q = (x - p0) / vs;   i = (int)floorf(q + 0.5f)   -- the nearest lattice point.  A point is INSIDE iff all
+ * three i lie in [0, n_voxels) and its three coordinates are finite; an inside point is kept iff its bit is set, any other point iff
+ * outside == NDET_OUTSIDE_KEEP.  The points go in blocks of 512 consecutive points, a wave each:
+ *   ndet_cull_blocks  the number of blocks of n_points points (0 for n_points <= 0);
+ *   ndet_cull_count   block_count[b] = kept points of block b (ndet_cull_blocks(n_points) ints);
+ *   ndet_cull_write   with block_first the EXCLUSIVE prefix sum of block_count: idx (M) int32, the kept flat point indices in ascending
+ *                     order, and pts_kept (M, 3) their points; M = the sum of block_count, which the caller reads back (one read).
+ * The bits are staged in LDS when they fit 64 KiB, else read from global memory.  Order inside a block comes from wave ballots and prefix
+ * popcounts. */
+int64_t ndet_cull_blocks(int64_t n_points);
+int ndet_cull_count(const float* pts, int64_t n_points, const uint32_t* bits, const int* n_voxels, const float* p0, const float* vs,
+                    int outside, int* block_count, void* stream);
+int ndet_cull_write(const float* pts, int64_t n_points, const uint32_t* bits, const int* n_voxels, const float* p0, const float* vs,
+                    int outside, const int* block_first, int* idx, float* pts_kept, void* stream);
+
+/* The count pass of ndet_ray_view_stats_bank alone: pixel_mask (n_points) = view_count > 1 and view_count (n_points) int32, the number of
+ * views of the bank whose image holds the sample (Projector.compute()'s mask, model_utils/projection.py:91-151, summed as in
+ * render_ray.py:299-303) -- ndet_ray_view_stats_bank's two outputs bit for bit, through the same projection, with no gathers. */
+int ndet_ray_view_count_bank(const float* pts, int64_t n_points, const NdetBankView* views_dev, int n_views, float img_h, float img_w,
+                             uint8_t* pixel_mask, int* view_count, void* stream);
+
 /* A7 exact API form. Replaces Projector.compute(), projection.py:91-151: rgb_feat (P, n_views, 3+d) and
  * mask (P, n_views) fp32 0/1, materialised like the reference. Same inputs as ndet_ray_view_stats. */
 int ndet_project_sample(const float* pts, int n_points, const float* KE, int n_views, float img_h, float img_w,

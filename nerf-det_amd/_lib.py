@@ -43,6 +43,7 @@ class NdetBankView(ctypes.Structure):    # one source view of a view bank (a DEV
 
 
 NDET_GROUP_MAX = 64
+NDET_OUTSIDE = {"keep": 0, "cull": 1}   # ndet_cull_*'s `outside`: include/nerfdet_hip.h::NDET_OUTSIDE_KEEP / NDET_OUTSIDE_CULL
 
 
 class NdetSceneSlot(ctypes.Structure):   # one scene of a scene group (a DEVICE table of these): include/nerfdet_hip.h::NdetSceneSlot, 64 bytes
@@ -131,6 +132,11 @@ SIGNATURES = {
                                     _P, _P, _P, _P], c_int),
     "ndet_ray_view_stats_bank": ([_P, c_int, _P, c_int, c_float, c_float, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P], c_int),
     "ndet_ray_view_stats_bank_group": ([_P, ctypes.POINTER(NdetBankGroupSel), c_float, c_float, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P], c_int),
+    "ndet_occupancy_bits": ([_P, _P, c_int, c_int, c_int, c_float, c_int, _P, _P], c_int),
+    "ndet_cull_blocks": ([c_int64], c_int64),
+    "ndet_cull_count": ([_P, c_int64, _P, ctypes.POINTER(c_int), _F3, _F3, c_int, _P, _P], c_int),
+    "ndet_cull_write": ([_P, c_int64, _P, ctypes.POINTER(c_int), _F3, _F3, c_int, _P, _P, _P, _P], c_int),
+    "ndet_ray_view_count_bank": ([_P, c_int64, _P, c_int, c_float, c_float, _P, _P, _P], c_int),
     "ndet_ray_view_stats_packed_bwd": ([_P, _P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, c_int, c_int64, c_int64, _P, _P], c_int),
     "ndet_project_sample": ([_P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, c_int64, c_int64, c_int64,
                              _P, c_int, c_int, c_int, c_int64, c_int64, _P, _P, _P], c_int),

@@ -1,0 +1,244 @@
+// Empty-space skipping for renders from a streamed scene (nerf-det_amd/streaming.py, skip_empty=), for gfx950:
+//   * ndet_occupancy_bits       the alpha a detect() computes at the voxel lattice (1 - exp(-relu(sigma)), nerfdet.py:255-257) -> a
+//                               dilated bit grid, bit n of word n >> 5 for voxel n = (ix ny + iy) nz + iz;
+//   * ndet_cull_count / _write  ordered compaction of sample points against that grid: the kept flat indices ascending, and their
+//                               points, the same bytes on every call (wave ballots and prefix popcounts, no atomics);
+//   * ndet_ray_view_count_bank  the view-bank sampler's count pass alone (ray_stats_kernels.hip, rb_project_round<false>): the valid
+//                               views of every sample through ndet_ray_project, lanes over views, no gathers.
+// A sample whose raw row is zero is an exact no-op in k_composite (ray_kernels.hip: a = 1 - expf(-0) = 0, wgt = 0, T (1 - 0 + 1e-10f) =
+// T), so "skipped" means "sigma = 0".  Plain vector stores only.  Compiled with -ffp-contract=off.
+#include "ndet_common.hpp"
+
+#include <cmath>
+
+// ------------------------------------------------------------------------------------------------
+// alpha -> bits.  One thread per voxel; a wave's ballot is two whole words (64 consecutive voxels, 256 per workgroup).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool se_solid(const float* __restrict__ alpha, const int64_t* __restrict__ count, int n, float threshold) {
+    return !(alpha[n] <= threshold) || count[n] == 0;       // NaN: solid; a voxel no view saw: solid (nothing is known about it)
+}
+
+__global__ __launch_bounds__(256) void k_occupancy_bits(const float* __restrict__ alpha, const int64_t* __restrict__ count, int nx, int ny, int nz,
+                                                        int n_total, float threshold, int dilate, uint32_t* __restrict__ bits, int n_words) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool set = false;
+    if (t < n_total) {
+        const int n = (int)t;
+        const int iz = n % nz, iy = (n / nz) % ny, ix = n / (nz * ny);
+        const int x0 = max(ix - dilate, 0), x1 = min(ix + dilate, nx - 1);
+        const int y0 = max(iy - dilate, 0), y1 = min(iy + dilate, ny - 1);
+        const int z0 = max(iz - dilate, 0), z1 = min(iz + dilate, nz - 1);
+        for (int x = x0; x <= x1; ++x)
+            for (int y = y0; y <= y1; ++y)
+                for (int z = z0; z <= z1; ++z) set = set || se_solid(alpha, count, (x * ny + y) * nz + z, threshold);
+    }
+    const unsigned long long b = __ballot(set);
+    const int64_t w = (t >> 6) * 2;                            // the wave's first word (t - lane is a multiple of 64)
+    const int lane = threadIdx.x & 63;
+    if (lane == 0 && w < n_words) bits[w] = (uint32_t)b;
+    if (lane == 32 && w + 1 < n_words) bits[w + 1] = (uint32_t)(b >> 32);
+}
+
+extern "C" int ndet_occupancy_bits(const float* alpha, const int64_t* count, int nx, int ny, int nz, float threshold, int dilate,
+                                   uint32_t* bits, void* stream) {
+    const char* fn = "ndet_occupancy_bits";
+    NDET_REQUIRE(alpha && count && bits, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(nx > 0 && ny > 0 && nz > 0, NDET_E_INVALID, "%s: bad sizes", fn);
+    NDET_REQUIRE(dilate >= 0 && dilate <= 2, NDET_E_INVALID, "%s: dilate=%d must be 0, 1 or 2", fn, dilate);
+    NDET_REQUIRE(std::isfinite(threshold), NDET_E_INVALID, "%s: threshold must be finite", fn);
+    const int64_t total = (int64_t)nx * ny * nz;
+    NDET_REQUIRE(total < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: %lld voxels, must be fewer than 2^31", fn, (long long)total);
+    NDET_REQUIRE(((uintptr_t)alpha & 3) == 0 && ((uintptr_t)count & 7) == 0 && ((uintptr_t)bits & 3) == 0, NDET_E_UNSUPPORTED,
+                 "%s: misaligned pointer", fn);
+    const int64_t blocks = (total + 255) / 256;
+    NDET_REQUIRE(blocks <= ((int64_t)1 << 24), NDET_E_UNSUPPORTED, "%s: more than 2^24 workgroups", fn);
+    hipLaunchKernelGGL(k_occupancy_bits, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, alpha, count, nx, ny, nz, (int)total,
+                       threshold, dilate, bits, (int)((total + 31) / 32));
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// points against the bits.  A wave owns SE_WAVE_POINTS consecutive points (one "block of points": one kept count) and walks them 64 at
+// a time in ascending order, so no wave needs another's counts: the 64 KiB of LDS are the bits' alone.
+// ------------------------------------------------------------------------------------------------
+#define SE_WAVE_POINTS 512
+#define SE_LDS_BYTES (64 * 1024)
+
+struct SeLattice {
+    float p0[3], vs[3];
+    int n[3];
+};
+
+// nearest lattice point per axis, in this fp32 statement order: q = (x - p0) / vs; i = (int)floorf(q + 0.5f)
+__device__ __forceinline__ bool se_keep(const float* __restrict__ pts, int64_t p, const SeLattice& g, const uint32_t* bits, bool keep_outside,
+                                        float& x, float& y, float& z) {
+    x = pts[p * 3 + 0];
+    y = pts[p * 3 + 1];
+    z = pts[p * 3 + 2];
+    const float qx = (x - g.p0[0]) / g.vs[0], qy = (y - g.p0[1]) / g.vs[1], qz = (z - g.p0[2]) / g.vs[2];
+    const float fx = floorf(qx + 0.5f), fy = floorf(qy + 0.5f), fz = floorf(qz + 0.5f);
+    // the range test runs on the floats (equal to the test on the ints wherever the cast is defined; NaN and +-inf fail it)
+    const bool inside = isfinite(x) && isfinite(y) && isfinite(z) && fx >= 0.0f && fx < (float)g.n[0] && fy >= 0.0f && fy < (float)g.n[1] &&
+                        fz >= 0.0f && fz < (float)g.n[2];
+    if (!inside) return keep_outside;
+    const int n = ((int)fx * g.n[1] + (int)fy) * g.n[2] + (int)fz;
+    return (bits[n >> 5] >> (n & 31)) & 1u;
+}
+
+template <bool LDS>
+__device__ __forceinline__ const uint32_t* se_stage_bits(const uint32_t* __restrict__ bits, int n_words) {
+    extern __shared__ uint32_t s_bits[];
+    if (!LDS) return bits;
+    for (int i = threadIdx.x; i < n_words; i += 256) s_bits[i] = bits[i];
+    __syncthreads();
+    return s_bits;
+}
+
+template <bool LDS, bool WRITE>
+__global__ __launch_bounds__(256) void k_cull(const float* __restrict__ pts, int64_t n_points, const uint32_t* __restrict__ bits, int n_words,
+                                              SeLattice g, int keep_outside, int* __restrict__ block_count,
+                                              const int* __restrict__ block_first, int* __restrict__ idx, float* __restrict__ pts_kept) {
+    const uint32_t* b = se_stage_bits<LDS>(bits, n_words);
+    const int lane = threadIdx.x & 63;
+    const int64_t wb = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // this wave's block of points
+    const int64_t p0 = wb * SE_WAVE_POINTS;
+    if (p0 >= n_points) return;                                           // wave-uniform, after the only barrier
+    int64_t at = WRITE ? block_first[wb] : 0;
+    int kept = 0;
+    for (int i = 0; i < SE_WAVE_POINTS; i += 64) {
+        const int64_t p = p0 + i + lane;
+        float x = 0.0f, y = 0.0f, z = 0.0f;
+        const bool k = p < n_points && se_keep(pts, p, g, b, keep_outside != 0, x, y, z);
+        const unsigned long long m = __ballot(k);
+        if (WRITE && k) {
+            const int64_t o = at + __popcll(m & ((1ull << lane) - 1ull));
+            idx[o] = (int)p;
+            pts_kept[o * 3 + 0] = x;
+            pts_kept[o * 3 + 1] = y;
+            pts_kept[o * 3 + 2] = z;
+        }
+        at += __popcll(m);
+        kept += __popcll(m);
+    }
+    if (!WRITE && lane == 0) block_count[wb] = kept;
+}
+
+static int se_cull_check(const char* fn, const float* pts, int64_t n_points, const uint32_t* bits, const int* n_voxels, const float* p0,
+                         const float* vs, int outside, SeLattice* g, int* n_words, int64_t* blocks) {
+    NDET_REQUIRE(pts && bits && n_voxels && p0 && vs, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(n_points > 0 && n_voxels[0] > 0 && n_voxels[1] > 0 && n_voxels[2] > 0, NDET_E_INVALID, "%s: bad sizes", fn);
+    for (int k = 0; k < 3; ++k) {
+        NDET_REQUIRE(std::isfinite(vs[k]) && vs[k] > 0.0f, NDET_E_INVALID, "%s: voxel size %d must be positive and finite", fn, k);
+        NDET_REQUIRE(std::isfinite(p0[k]), NDET_E_INVALID, "%s: lattice origin %d must be finite", fn, k);
+    }
+    NDET_REQUIRE(outside == NDET_OUTSIDE_KEEP || outside == NDET_OUTSIDE_CULL, NDET_E_INVALID, "%s: outside=%d is neither keep nor cull", fn,
+                 outside);
+    NDET_REQUIRE(n_points < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: %lld points, must be fewer than 2^31", fn, (long long)n_points);
+    const int64_t total = (int64_t)n_voxels[0] * n_voxels[1] * n_voxels[2];
+    NDET_REQUIRE(total < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: %lld voxels, must be fewer than 2^31", fn, (long long)total);
+    NDET_REQUIRE(((uintptr_t)pts & 3) == 0 && ((uintptr_t)bits & 3) == 0, NDET_E_UNSUPPORTED, "%s: misaligned pointer", fn);
+    for (int k = 0; k < 3; ++k) {
+        g->p0[k] = p0[k];
+        g->vs[k] = vs[k];
+        g->n[k] = n_voxels[k];
+    }
+    *n_words = (int)((total + 31) / 32);
+    *blocks = (ndet_cull_blocks(n_points) + 3) / 4;
+    NDET_REQUIRE(*blocks <= ((int64_t)1 << 24), NDET_E_UNSUPPORTED, "%s: more than 2^24 workgroups", fn);
+    return NDET_OK;
+}
+
+template <bool WRITE>
+static void se_cull_launch(int64_t blocks, int n_words, hipStream_t stream, const float* pts, int64_t n_points, const uint32_t* bits,
+                           const SeLattice& g, int outside, int* block_count, const int* block_first, int* idx, float* pts_kept) {
+    const size_t lds = (size_t)n_words * sizeof(uint32_t);
+    if (lds <= SE_LDS_BYTES)
+        hipLaunchKernelGGL((k_cull<true, WRITE>), dim3((unsigned)blocks), dim3(256), lds, stream, pts, n_points, bits, n_words, g,
+                           outside == NDET_OUTSIDE_KEEP, block_count, block_first, idx, pts_kept);
+    else
+        hipLaunchKernelGGL((k_cull<false, WRITE>), dim3((unsigned)blocks), dim3(256), 0, stream, pts, n_points, bits, n_words, g,
+                           outside == NDET_OUTSIDE_KEEP, block_count, block_first, idx, pts_kept);
+}
+
+extern "C" int64_t ndet_cull_blocks(int64_t n_points) { return n_points > 0 ? (n_points + SE_WAVE_POINTS - 1) / SE_WAVE_POINTS : 0; }
+
+extern "C" int ndet_cull_count(const float* pts, int64_t n_points, const uint32_t* bits, const int* n_voxels, const float* p0, const float* vs,
+                               int outside, int* block_count, void* stream) {
+    const char* fn = "ndet_cull_count";
+    SeLattice g;
+    int n_words = 0;
+    int64_t blocks = 0;
+    NDET_TRY(se_cull_check(fn, pts, n_points, bits, n_voxels, p0, vs, outside, &g, &n_words, &blocks));
+    NDET_REQUIRE(block_count, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(((uintptr_t)block_count & 3) == 0, NDET_E_UNSUPPORTED, "%s: misaligned pointer", fn);
+    se_cull_launch<false>(blocks, n_words, (hipStream_t)stream, pts, n_points, bits, g, outside, block_count, nullptr, nullptr, nullptr);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+extern "C" int ndet_cull_write(const float* pts, int64_t n_points, const uint32_t* bits, const int* n_voxels, const float* p0, const float* vs,
+                               int outside, const int* block_first, int* idx, float* pts_kept, void* stream) {
+    const char* fn = "ndet_cull_write";
+    SeLattice g;
+    int n_words = 0;
+    int64_t blocks = 0;
+    NDET_TRY(se_cull_check(fn, pts, n_points, bits, n_voxels, p0, vs, outside, &g, &n_words, &blocks));
+    NDET_REQUIRE(block_first && idx && pts_kept, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(((uintptr_t)block_first & 3) == 0 && ((uintptr_t)idx & 3) == 0 && ((uintptr_t)pts_kept & 3) == 0, NDET_E_UNSUPPORTED,
+                 "%s: misaligned pointer", fn);
+    se_cull_launch<true>(blocks, n_words, (hipStream_t)stream, pts, n_points, bits, g, outside, nullptr, block_first, idx, pts_kept);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the bank sampler's count pass alone.  Lanes over views in rounds of 64, the camera row in registers, as rb_project_round holds it
+// (ray_stats_kernels.hip); a wave owns 64 consecutive samples, lane g keeps sample g's count and loads its point once (the sampler's
+// wave-uniform loads read the same floats).  A sample's count is the popcount of the ballot of ndet_ray_project's mask over the views.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ray_count_bank(const float* __restrict__ pts, int64_t n_points, const NdetBankView* __restrict__ views,
+                                                        int n_views, float img_h, float img_w, uint8_t* __restrict__ pixel_mask,
+                                                        int* __restrict__ view_count) {
+    const int lane = threadIdx.x & 63;
+    const int64_t p_base = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;
+    if (p_base >= n_points) return;                            // wave-uniform
+    const int64_t my_p = p_base + lane;
+    const bool on = my_p < n_points;
+    const float mx = on ? pts[my_p * 3 + 0] : 0.0f, my = on ? pts[my_p * 3 + 1] : 0.0f, mz = on ? pts[my_p * 3 + 2] : 0.0f;
+    const int live = (int)min((int64_t)64, n_points - p_base);
+    int cnt = 0;
+    for (int v0 = 0; v0 < n_views; v0 += 64) {
+        const int v = v0 + lane;
+        float cam[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) cam[k] = v < n_views ? views[v].ke[k] : 0.0f;
+        for (int gg = 0; gg < live; ++gg) {
+            const float x = __shfl(mx, gg), y = __shfl(my, gg), z = __shfl(mz, gg);
+            bool m = false;
+            if (v < n_views) m = ndet_ray_project(cam, x, y, z, img_h, img_w).mask;
+            const unsigned long long vb = __ballot(m);
+            if (lane == gg) cnt += __popcll(vb);
+        }
+    }
+    if (on) {
+        pixel_mask[my_p] = cnt > 1 ? 1 : 0;                    // render_ray.py:301
+        view_count[my_p] = cnt;
+    }
+}
+
+extern "C" int ndet_ray_view_count_bank(const float* pts, int64_t n_points, const NdetBankView* views_dev, int n_views, float img_h, float img_w,
+                                        uint8_t* pixel_mask, int* view_count, void* stream) {
+    const char* fn = "ndet_ray_view_count_bank";
+    NDET_REQUIRE(pts && views_dev && pixel_mask && view_count, NDET_E_INVALID, "%s: null pointer", fn);
+    NDET_REQUIRE(n_points > 0 && n_views > 0, NDET_E_INVALID, "%s: bad sizes", fn);
+    NDET_REQUIRE(n_points < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: %lld points, must be fewer than 2^31", fn, (long long)n_points);
+    NDET_REQUIRE(((uintptr_t)views_dev & 7) == 0, NDET_E_UNSUPPORTED, "%s: the view table must be 8-byte aligned", fn);
+    NDET_REQUIRE(((uintptr_t)pts & 3) == 0 && ((uintptr_t)view_count & 3) == 0, NDET_E_UNSUPPORTED, "%s: misaligned pointer", fn);
+    const int64_t blocks = (n_points + 255) / 256;
+    NDET_REQUIRE(blocks <= ((int64_t)1 << 24), NDET_E_UNSUPPORTED, "%s: more than 2^24 workgroups", fn);
+    hipLaunchKernelGGL(k_ray_count_bank, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, pts, n_points, views_dev, n_views, img_h,
+                       img_w, pixel_mask, view_count);
+    NDET_CHECK_LAUNCH(fn);
+    return NDET_OK;
+}

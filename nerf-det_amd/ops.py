@@ -922,6 +922,23 @@ def sigma_to_alpha(raw_sigma: Tensor) -> Tensor:
     return out
 
 
+def occupancy_bits(alpha: Tensor, count: Tensor, n_voxels, threshold: float, dilate: int) -> Tensor:
+    """The lattice's alpha (N,) and view count (N,) int64, flat as :func:`get_points` orders the voxels, as a dilated occupancy bit grid:
+    ``((N + 31) // 32,)`` int32 words, bit ``n & 31`` of word ``n >> 5`` set iff a voxel within Chebyshev distance ``dilate`` (0, 1, 2) of
+    voxel n is solid -- ``not (alpha <= threshold)`` (a NaN is solid) or seen by no view (k_occupancy_bits; the same bytes on every call)."""
+    _need_gpu(alpha, count)
+    nv = [int(v) for v in (n_voxels.tolist() if isinstance(n_voxels, Tensor) else n_voxels)]
+    a = _f32c(alpha).reshape(-1)
+    c = count.to(torch.int64).contiguous().reshape(-1)
+    n = nv[0] * nv[1] * nv[2]
+    assert len(nv) == 3 and a.numel() == n and c.numel() == n, f"alpha {tuple(alpha.shape)} and count {tuple(count.shape)} for a {nv} lattice"
+    bits = torch.empty(((n + 31) // 32,), dtype=torch.int32, device=a.device)
+    trace.span("k_occupancy_bits", lambda: check(_lib.load().ndet_occupancy_bits(_ptr(a), _ptr(c), nv[0], nv[1], nv[2], float(threshold), int(dilate),
+                                                                                _ptr(bits), _stream(a)), "occupancy_bits"),
+               bytes=12 * n + 4 * bits.numel(), kind="hbm")
+    return bits
+
+
 def alpha_gate(mean: Tensor, density: Tensor, count: Tensor) -> Tensor:
     """Unfused gating of nerfdet.py:257-261: ``(1-exp(-density)) * mean`` zeroed where count == 0.
     ``mean`` (C,X,Y,Z) contiguous or channels-last (as produced by :func:`backproject_aggregate`)."""

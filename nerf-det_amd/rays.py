@@ -329,6 +329,84 @@ def bank_group_stats(xyz_list, banks):
     return glob, pm, vc, pts
 
 
+# ------------------------------------------------------------------------------------------------------
+# empty-space skipping (csrc/skip_empty_kernels.hip): the bank sampler's count pass alone, and an ordered cull against an occupancy grid
+# ------------------------------------------------------------------------------------------------------
+def ray_view_count_bank(xyz: Tensor, bank: ViewBank):
+    """The count pass of :func:`ray_view_stats_bank` alone (k_ray_count_bank): sample points (..., 3) -> ``(pixel_mask (...) bool,
+    view_count (...) int32)``, that function's second and third output bit for bit, with no gathers.  The bank is not changed."""
+    if not xyz.is_cuda:
+        raise RuntimeError("nerfdet_amd.rays: tensors must live on the GPU (no CPU fallback)")
+    table, n_v = bank.table()
+    s0 = bank.segments[0]
+    if xyz.device != s0.feat.device:
+        raise ValueError("ray_view_count_bank: the points and the bank live on different devices")
+    shape = xyz.shape[:-1]
+    pts = xyz.to(torch.float32).reshape(-1, 3).contiguous()
+    n = pts.shape[0]
+    pm = torch.empty((n,), dtype=torch.bool, device=pts.device)
+    vc = torch.empty((n,), dtype=torch.int32, device=pts.device)
+    trace.span("k_ray_count_bank", lambda: check(
+        _lib.load().ndet_ray_view_count_bank(_ptr(pts), n, _ptr(table), n_v, *s0.img_hw, _ptr(pm), _ptr(vc), _stream(xyz)),
+        "ray_view_count_bank"), bytes=17 * n + 64 * n_v, kind="hbm")
+    return pm.view(*shape), vc.view(*shape)
+
+
+class OccupancyGrid:
+    """Where a streamed scene may hold matter: ``bits`` (ops.occupancy_bits' words, on the device) over the detection lattice of
+    ``n_voxels`` voxels whose first point is ``p0`` and whose pitch is ``voxel_size`` (three float32 each, on the host), and ``outside``:
+    'keep' or 'cull', what becomes of a sample outside the lattice.  ``threshold`` and ``dilate`` record how it was made (None when
+    unknown).  :func:`cull_points` reads it; ``SceneStream.occupancy`` makes it."""
+    __slots__ = ("bits", "n_voxels", "p0", "voxel_size", "outside", "threshold", "dilate")
+
+    def __init__(self, bits: Tensor, n_voxels, p0, voxel_size, outside: str = "keep", threshold=None, dilate=None):
+        nv = tuple(int(v) for v in (n_voxels.tolist() if isinstance(n_voxels, Tensor) else n_voxels))
+        p0 = tuple(float(np.float32(v)) for v in (p0.tolist() if isinstance(p0, (Tensor, np.ndarray)) else p0))
+        vs = tuple(float(np.float32(v)) for v in (voxel_size.tolist() if isinstance(voxel_size, (Tensor, np.ndarray)) else voxel_size))
+        if len(nv) != 3 or len(p0) != 3 or len(vs) != 3 or min(nv) < 1:
+            raise ValueError(f"OccupancyGrid: n_voxels {nv}, p0 {p0} and voxel_size {vs} must hold three values each, n_voxels positive")
+        if not all(np.isfinite(p0)) or not all(np.isfinite(vs)) or min(vs) <= 0.0:
+            raise ValueError(f"OccupancyGrid: p0 {p0} must be finite and voxel_size {vs} positive and finite")
+        if outside not in _lib.NDET_OUTSIDE:
+            raise ValueError(f"OccupancyGrid: outside={outside!r} must be 'keep' or 'cull'")
+        words = (nv[0] * nv[1] * nv[2] + 31) // 32
+        if not isinstance(bits, Tensor) or bits.dtype != torch.int32 or tuple(bits.shape) != (words,) or not bits.is_contiguous():
+            raise ValueError(f"OccupancyGrid: bits must be a contiguous ({words},) int32 tensor for {nv} voxels")
+        self.bits, self.n_voxels, self.p0, self.voxel_size, self.outside = bits, nv, p0, vs, outside
+        self.threshold, self.dilate = threshold, dilate
+
+
+def cull_points(pts: Tensor, occ: OccupancyGrid):
+    """Ordered compaction of ``pts`` (..., 3) against ``occ``: ``(idx (M,) int32, pts_kept (M, 3))``, the flat indices of the kept points
+    in ascending order and those points.  Per axis, in float32, ``i = int(floor((x - p0) / voxel_size + 0.5))`` is the nearest lattice
+    point; a point with all three in range and finite coordinates is kept iff its bit is set, any other iff ``occ.outside == 'keep'``.
+    Two launches (k_cull_count, k_cull_write) around one prefix sum; M reaches the host in ONE device-to-host read, the call's only
+    synchronisation; ``M = 0`` skips the second launch.  The same bytes on every call."""
+    if not (pts.is_cuda and occ.bits.is_cuda):
+        raise RuntimeError("nerfdet_amd.rays: tensors must live on the GPU (no CPU fallback)")
+    if pts.device != occ.bits.device:
+        raise ValueError("cull_points: the points and the grid live on different devices")
+    p = pts.to(torch.float32).reshape(-1, 3).contiguous()
+    n = p.shape[0]
+    if n < 1:
+        raise ValueError(f"cull_points: points {tuple(pts.shape)} must be (..., 3) with at least one point")
+    lib = _lib.load()
+    geom = ((ctypes.c_int * 3)(*occ.n_voxels), _lib.float3(occ.p0), _lib.float3(occ.voxel_size), _lib.NDET_OUTSIDE[occ.outside])
+    counts = torch.empty((int(lib.ndet_cull_blocks(n)),), dtype=torch.int32, device=p.device)
+    trace.span("k_cull_count", lambda: check(lib.ndet_cull_count(_ptr(p), n, _ptr(occ.bits), *geom, _ptr(counts), _stream(p)), "cull_count"),
+               bytes=12 * n + 4 * counts.numel(), kind="hbm")
+    last = torch.cumsum(counts, 0, dtype=torch.int32)
+    first = last - counts
+    m = int(last[-1])                                          # the one read
+    idx = torch.empty((m,), dtype=torch.int32, device=p.device)
+    kept = torch.empty((m, 3), dtype=torch.float32, device=p.device)
+    if m:
+        trace.span("k_cull_write", lambda: check(lib.ndet_cull_write(_ptr(p), n, _ptr(occ.bits), *geom, _ptr(first), _ptr(idx), _ptr(kept),
+                                                                     _stream(p)), "cull_write"),
+                   bytes=12 * n + 16 * m, kind="hbm")
+    return idx, kept
+
+
 class Projector:
     """projection.py:20-151.  ``compute`` keeps the reference's signature and materialised outputs."""
 

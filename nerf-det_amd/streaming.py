@@ -58,6 +58,13 @@ them (pipeline.project_boxes, ndet_project_boxes), one draws their wireframes on
 ndet_draw_boxes: new frames, the best detection on top) or says which detection each pixel of a depth frame belongs to
 (pipeline.label_frames, ndet_label_frames).  They use the scene's meta only and need no ``keep_views``.
 
+``scene.occupancy(threshold, dilate, outside)`` / ``group.occupancy(..., scenes=)`` make an occupancy grid (rays.OccupancyGrid) from the
+finishes ``volume()`` runs -- the sigma-MLP's alpha at the lattice is the expression compositing applies to a sample -- and
+``skip_empty=`` on ``render_rays``, ``render``, ``render_frames`` and ``score_frames`` leaves out the samples the grid calls empty: per pass
+one count launch over all samples for the ray mask (rays.ray_view_count_bank), one ordered cull (rays.cull_points, one read), sampler and
+MLP over the kept rows only, and the compositing over the same ray ranges with the culled samples at sigma = 0, an exact no-op.  The
+default ``skip_empty=None`` makes the launches and the bits it made without the keyword.
+
 Inference only: no training / autograd, no hipGraph replay, one scene per stream; whole chunks are dropped, not single views out of one.
 Without ``keep_views`` there is no ray branch (rendering needs every view's map).
 """
@@ -495,6 +502,123 @@ def _render_passes(det, banks, ray_os, ray_ds, step: int, batched: bool, n_impor
     return [(cat(c), cat(f) if n_importance > 0 else None) for c, f in zip(outs, fines)]
 
 
+# ---- skip_empty=: renders that leave out the samples an occupancy grid calls empty ----
+SKIP_EMPTY_DEFAULTS = dict(threshold=1e-3, dilate=1, outside="keep")
+
+
+def _check_occupancy_knobs(threshold, dilate, outside):
+    """``occupancy``'s three knobs as ``(float threshold, int dilate, outside)``: a finite number, 0 .. 2, 'keep' or 'cull'; else ValueError."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.floating, np.integer)) or not np.isfinite(threshold):
+        raise ValueError(f"occupancy: threshold={threshold!r} must be a finite number")
+    if isinstance(dilate, bool) or not isinstance(dilate, (int, np.integer)) or not 0 <= dilate <= 2:
+        raise ValueError(f"occupancy: dilate={dilate!r} must be 0, 1 or 2")
+    if outside not in ("keep", "cull"):
+        raise ValueError(f"occupancy: outside={outside!r} must be 'keep' or 'cull'")
+    return float(threshold), int(dilate), outside
+
+
+def _skip_knobs(skip_empty, det, device, what: str):
+    """What a ``skip_empty=`` argument asks for, checked before any launch: None (no culling: None or False), a dict of ``occupancy``'s
+    keywords (True: the defaults), or the caller's rays.OccupancyGrid, whose lattice must be the detector's.  Else ValueError."""
+    if skip_empty is None or skip_empty is False:
+        return None
+    from .rays import OccupancyGrid
+    if skip_empty is True:
+        return dict(SKIP_EMPTY_DEFAULTS)
+    if isinstance(skip_empty, OccupancyGrid):
+        n_voxels = tuple(int(v) for v in det.n_voxels)
+        if tuple(skip_empty.n_voxels) != n_voxels:
+            raise ValueError(f"{what}: the grid's n_voxels {tuple(skip_empty.n_voxels)} differ from the scene's {n_voxels}")
+        if not skip_empty.bits.is_cuda or skip_empty.bits.device != device:
+            raise RuntimeError(f"{what}: the grid's bits must live on the scene's GPU (no CPU fallback)")
+        return skip_empty
+    if isinstance(skip_empty, dict):
+        if not set(skip_empty) <= set(SKIP_EMPTY_DEFAULTS):
+            raise ValueError(f"{what}: skip_empty takes the keys {sorted(SKIP_EMPTY_DEFAULTS)}, got {sorted(skip_empty)}")
+        knobs = dict(SKIP_EMPTY_DEFAULTS, **skip_empty)
+        knobs["threshold"], knobs["dilate"], knobs["outside"] = _check_occupancy_knobs(knobs["threshold"], knobs["dilate"], knobs["outside"])
+        return knobs
+    raise ValueError(f"{what}: skip_empty={skip_empty!r} must be None, True, a dict of occupancy()'s keywords or a rays.OccupancyGrid")
+
+
+def _check_culled_call(det, what: str, *tensors) -> None:
+    """What a culled render refuses beyond its unculled twin: a training detector and CPU tensors (RuntimeError), before any launch."""
+    if det.training:
+        raise RuntimeError(f"{what}(skip_empty=) is inference only: call det.eval() first")
+    if any(not t.is_cuda for t in tensors):
+        raise RuntimeError(f"{what}(skip_empty=): the rays must live on the GPU (no CPU fallback)")
+
+
+def _make_occupancy(alpha: Tensor, valid: Tensor, points: Tensor, n_voxels, voxel_size, threshold: float, dilate: int, outside: str):
+    """A scene's rays.OccupancyGrid from its finished alpha (N,), its ``valid`` (1,X,Y,Z) and its lattice ``points`` (3,X,Y,Z): one
+    k_occupancy_bits launch and one 12-byte read of the lattice's first point."""
+    from .rays import OccupancyGrid
+    bits = ops.occupancy_bits(alpha, valid, n_voxels, threshold, dilate)
+    return OccupancyGrid(bits, n_voxels, points[:, 0, 0, 0].cpu(), np.float32([float(v) for v in voxel_size]), outside, threshold, dilate)
+
+
+def _culled_shade(det, bank, occ, dirs: Tensor, pts: Tensor, z: Tensor):
+    """Sampler, MLP and compositing of one pass of one scene over the samples ``occ`` keeps: ``pts`` (c, ss, 3), ``z`` (c, ss), ``dirs``
+    (c, 3) -> ``(rays.raw2outputs' dict, kept rows)``.  The ray mask comes from the sampler's count pass over ALL the samples
+    (rays.ray_view_count_bank: ``seen > 8`` counts them all); the kept rows alone go through the sampler (at most
+    ``RENDER_TESTING_RAYS * N_samples`` rows a launch) and ``nerf_mlp`` (at most ``rays.FINE_MLP_ROWS`` rows a call) and are scattered
+    into a zero-filled raw -- a zero row is an exact no-op in k_composite -- which is composited over the pass's rays as ever (the depth
+    clamp's ``zminmax`` is per pass).  One device-to-host read (rays.cull_points); no kept row: neither sampler nor MLP is launched."""
+    from . import rays
+    c, ss = pts.shape[:2]
+    flat = pts.view(-1, 3)
+    pm, _ = rays.ray_view_count_bank(flat, bank)
+    idx, kept = rays.cull_points(flat, occ)
+    m = idx.shape[0]
+    raw = torch.zeros((c * ss, 4), dtype=torch.float32, device=pts.device)
+    if m:
+        idx = idx.to(torch.int64)
+        kdirs = dirs.to(torch.float32)[idx // ss]
+        rows = rays.RENDER_TESTING_RAYS * det.N_samples
+        for a in range(0, m, rows):
+            glob = rays.ray_view_stats_bank(kept[a:a + rows], bank)[0]
+            for b in range(0, glob.shape[0], rays.FINE_MLP_ROWS):
+                sl = slice(a + b, a + min(b + rays.FINE_MLP_ROWS, glob.shape[0]))
+                rgb, sigma = det.nerf_mlp(kept[sl], kdirs[sl], glob[b:b + rays.FINE_MLP_ROWS])
+                raw.index_copy_(0, idx[sl], torch.cat([rgb, sigma], dim=-1))
+    return rays.raw2outputs(raw.view(c, ss, 4), z, pm.view(c, ss)), m
+
+
+def _render_passes_culled(det, bank, occ, ray_o: Tensor, ray_d: Tensor, step: int, n_importance: int):
+    """:func:`_render_passes` for ONE scene with the samples ``occ`` calls empty left out (:func:`_culled_shade`), over the same ray ranges
+    pass by pass: ``((rgb, depth, mask) of the coarse pass, the same of the fine pass or None, kept rows, sample rows)``, the last two
+    host ints over every cull of the call.  With ``n_importance > 0`` the coarse weights are the culled coarse pass's (dense, zero where
+    culled), rays.importance_merge runs over them and the merged samples are culled, sampled, shaded and composited the same way."""
+    from . import rays
+    out, fine = ([], [], []), ([], [], [])
+    n_kept = n_samples = 0
+    with torch.no_grad():
+        for i0 in range(0, ray_o.shape[0], step):
+            o, d = ray_o[i0:i0 + step], ray_d[i0:i0 + step]
+            pts, z = rays.sample_along_camera_ray(o, d, det.near_far_range, det.N_samples, det=True)
+            res, m = _culled_shade(det, bank, occ, d, pts, z)
+            n_kept, n_samples = n_kept + m, n_samples + z.numel()
+            for acc, key in zip(out, ("rgb", "depth", "mask")):
+                acc.append(res[key])
+            if n_importance > 0:
+                pts_f, z_f, _ = rays.importance_merge(z, res["weights"], o, d, n_importance, True)
+                res, m = _culled_shade(det, bank, occ, d, pts_f, z_f)
+                n_kept, n_samples = n_kept + m, n_samples + z_f.numel()
+                for acc, key in zip(fine, ("rgb", "depth", "mask")):
+                    acc.append(res[key])
+    cat = lambda acc: tuple(a[0] if len(a) == 1 else torch.cat(a, dim=0) for a in acc)
+    return cat(out), cat(fine) if n_importance > 0 else None, n_kept, n_samples
+
+
+def _with_counts(out: dict, counts) -> dict:
+    """A render's result with what its culls counted: the unculled call's dict as it is (``counts`` None), else with the host ints
+    ``n_kept`` and ``n_samples`` -- sample rows that went through sampler and MLP, and all sample rows, over every cull of the call (the
+    fine pass's included)."""
+    if counts is not None:
+        out["n_kept"], out["n_samples"] = int(counts[0]), int(counts[1])
+    return out
+
+
 def _finished_alpha(mlp, points: Tensor, glob: Tensor) -> Tensor:
     """The sigma-MLP over the density finish's rows and their alpha: the fused trunk where the MLP has one."""
     if hasattr(mlp, "hip_trunk_ok") and mlp.hip_trunk_ok():
@@ -525,6 +649,7 @@ class SceneStream:
     keep the views' mapped maps, images and cameras (``bank``, a rays.ViewBank) so that :meth:`render_rays` / :meth:`render` work."""
 
     bank = None     # rays.ViewBank with keep_views, else None
+    _occ = None     # (threshold, dilate, outside) -> rays.OccupancyGrid of the views held now, made by occupancy(); dropped by _drop_grids()
     mean, std = IMG_MEAN, IMG_STD     # img_norm_cfg of add_frames (RGB)
 
     def __init__(self, det, img_meta: dict, window: Optional[int] = None, keep_views: bool = False, mean=IMG_MEAN, std=IMG_STD):
@@ -569,8 +694,13 @@ class SceneStream:
     def n_views(self) -> int:
         return sum(self.chunk_views)
 
+    def _drop_grids(self) -> None:
+        """Whatever changes the views held drops the cached occupancy grids."""
+        self._occ = None
+
     def reset(self) -> None:
         """Forget every view: the scene starts empty again."""
+        self._drop_grids()
         if self.window is None:
             self.state.reset()
             if self.bank is not None:
@@ -584,6 +714,7 @@ class SceneStream:
             raise ValueError("drop_oldest needs a windowed stream: begin_scene(img_meta, window=S)")
         if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= len(self._segs):
             raise ValueError(f"drop_oldest: k={k!r} for {len(self._segs)} chunks held")
+        self._drop_grids()
         for st in self._segs[:k]:
             st.reset()
             self._spare.append(st)
@@ -596,6 +727,7 @@ class SceneStream:
         the oldest chunk leave a full window.  A chunk that fails leaves the window as it was (its state goes back, zeroed).  ``banked``:
         the chunk's view-bank segment, made by the caller (rays.ViewBank.make_segment changes nothing); it joins the bank once the
         states have taken the chunk, so states and bank hold the same chunks."""
+        self._drop_grids()
         if self.window is None:
             ops.scene_accumulate(self.state, *chunk, depth_gate=depth_gate)
             if banked is not None:
@@ -690,7 +822,15 @@ class SceneStream:
         bank = self._need_bank("rendering")
         return _render_passes(self.det, [bank], [ray_o], [ray_d], step, False, n_importance, _one_bank_stats)[0]
 
-    def render_rays(self, ray_o: Tensor, ray_d: Tensor, n_importance: int = 0):
+    def _render_counted(self, ray_o: Tensor, ray_d: Tensor, step: int, n_importance: int, occ):
+        """``((coarse, fine), counts)``: :meth:`_render` and None without a grid, else the culled passes (:func:`_render_passes_culled`)
+        and their ``(n_kept, n_samples)``."""
+        if occ is None:
+            return self._render(ray_o, ray_d, step, n_importance), None
+        coarse, fine, n_kept, n_samples = _render_passes_culled(self.det, self._need_bank("rendering"), occ, ray_o, ray_d, step, n_importance)
+        return (coarse, fine), (n_kept, n_samples)
+
+    def render_rays(self, ray_o: Tensor, ray_d: Tensor, n_importance: int = 0, skip_empty=None):
         """Render rays ``ray_o``, ``ray_d`` (R,3) against the views held: ``dict(rgb (R,3), depth (R,), mask (R,) bool)``, what
         ``rays.render_rays_func(det=True)`` composites (render_ray.py:250-327) with the detector's ``near_far_range`` and ``N_samples``,
         ``rays.RENDER_TESTING_RAYS`` rays per pass.  Needs ``keep_views=True`` and at least one view (else RuntimeError).
@@ -698,26 +838,41 @@ class SceneStream:
         ``n_importance=k > 0`` adds the fine pass of ``rays.render_rays_func(N_importance=k)``: k further depths per ray drawn from the
         coarse weights (one k_importance_merge launch a pass), then the sampler, the MLP and the compositing again over the
         ``N_samples + k`` depths.  ``rgb``, ``depth`` and ``mask`` are then the fine pass's, and the dict gains ``'coarse'``:
-        ``dict(rgb, depth, mask)`` of the coarse pass, which is what ``n_importance=0`` returns."""
+        ``dict(rgb, depth, mask)`` of the coarse pass, which is what ``n_importance=0`` returns.
+
+        ``skip_empty``: None (the default: every launch and every bit as without the keyword), True (:meth:`occupancy`'s defaults), a
+        dict of :meth:`occupancy`'s keywords, or a rays.OccupancyGrid over the scene's lattice.  The samples the grid calls empty are
+        then left out: per pass one count launch over all samples keeps the ray mask exact (rays.ray_view_count_bank), one cull
+        (rays.cull_points: its read of the kept count is the one synchronisation a pass adds) picks the kept rows, which alone go
+        through the sampler and ``nerf_mlp``; the others composite as ``sigma = 0``, an exact no-op in k_composite, over the same ray
+        ranges as the unculled passes.  ``mask`` is the unculled call's bit for bit; ``rgb`` and ``depth`` are those of the unculled
+        samples with the culled ones' sigma set to 0 -- bit for bit as measured (the MLP's launches scale per row or not at all, so
+        regrouping its rows across calls changes nothing).  With ``n_importance > 0`` the fine samples are drawn from the culled coarse weights and culled the
+        same way.  The dict gains the host ints ``n_kept`` and ``n_samples``.  Many culled samples each just under the threshold can
+        add up along a ray: compare with the plain render (or :meth:`score_frames`) on your own data.  Inference only, not graphed:
+        a training detector or CPU rays are a RuntimeError, bad knobs or another lattice's grid a ValueError, before any launch."""
         from . import rays
         self._need_bank("render_rays")
         n_importance = _check_n_importance(n_importance)
         if ray_o.dim() != 2 or ray_o.shape[1] != 3 or ray_d.shape != ray_o.shape:
             raise ValueError(f"render_rays takes (R,3) origins and directions, got {tuple(ray_o.shape)} and {tuple(ray_d.shape)}")
-        coarse, fine = self._render(ray_o, ray_d, rays.RENDER_TESTING_RAYS, n_importance)
-        return _render_dict(coarse, fine)
+        occ = self._skip_grid(skip_empty, "render_rays", ray_o, ray_d)
+        (coarse, fine), counts = self._render_counted(ray_o, ray_d, rays.RENDER_TESTING_RAYS, n_importance, occ)
+        return _with_counts(_render_dict(coarse, fine), counts)
 
-    def render(self, ray_batch: dict, n_importance: int = 0):
+    def render(self, ray_batch: dict, n_importance: int = 0, skip_empty=None):
         """Every ray of the ray batch's target views, as ``rays.render_rays(render_testing=True)`` returns them (render_ray.py:452-517):
         ``outputs_coarse.rgb`` (T,h,w,3), ``outputs_coarse.depth`` (T,h,w,1), ``gt_rgb``, ``gt_depth`` -- ``rays.rendering_metrics`` applies.
-        ``n_importance=k > 0`` adds ``outputs_fine`` (same shapes), as ``rays.render_rays(render_testing=True, N_importance=k)`` does."""
+        ``n_importance=k > 0`` adds ``outputs_fine`` (same shapes), as ``rays.render_rays(render_testing=True, N_importance=k)`` does.
+        ``skip_empty`` as in :meth:`render_rays` (the dict gains ``n_kept`` and ``n_samples``)."""
         self._need_bank("render")
         n_importance = _check_n_importance(n_importance)
         ray_o, ray_d, shape, gt_rgb, gt_depth = _unpack_ray_batch(ray_batch)
-        coarse, fine = self._render(ray_o, ray_d, _render_step(self.det), n_importance)
-        return _render_views(coarse, fine, shape, gt_rgb, gt_depth)
+        occ = self._skip_grid(skip_empty, "render", ray_o, ray_d)
+        (coarse, fine), counts = self._render_counted(ray_o, ray_d, _render_step(self.det), n_importance, occ)
+        return _with_counts(_render_views(coarse, fine, shape, gt_rgb, gt_depth), counts)
 
-    def render_frames(self, c2w=None, extrinsic=None, window=None, stride: int = 1, n_importance: int = 0):
+    def render_frames(self, c2w=None, extrinsic=None, window=None, stride: int = 1, n_importance: int = 0, skip_empty=None):
         """Camera frames of k >= 1 poses against the views held -- pose in, BGR and depth out, in the formats :meth:`add_frames` takes.
         Exactly one of ``c2w`` (k camera-to-world 4 x 4, as ``pipeline.scene_cameras(info)["c2w"]``) and ``extrinsic`` (k world-to-camera
         4 x 4, as a chunk meta carries them: inverted on the host in float64, rounded to float32).  The intrinsics are the scene meta's,
@@ -731,18 +886,24 @@ class SceneStream:
         with ``n_importance > 0`` these are the fine pass's and ``'coarse'`` holds the same five keys for the coarse pass.  The float
         outputs are bit for bit ``self.render_rays(*camera_rays(...))`` on the concatenated rays, reshaped; the frames are
         ``pack_frames`` of them: depth 0 is a hole (``mask`` false), as in the sensor's frames.  Needs ``keep_views=True`` and at least one
-        view (else RuntimeError); bad arguments are a ValueError before any launch.  No state and no bank is changed."""
+        view (else RuntimeError); bad arguments are a ValueError before any launch.  No state and no bank is changed.
+        ``skip_empty`` as in :meth:`render_rays`: the frames are ``pack_frames`` of the culled float outputs, and the dict gains
+        ``n_kept`` and ``n_samples``."""
         from . import rays
         self._need_bank("render_frames")
         n_importance = _check_n_importance(n_importance)
         poses = _camera_poses(c2w, extrinsic, "render_frames")
         win, stride = _frame_grid(self.meta, window, stride)
+        knobs = _skip_knobs(skip_empty, self.det, self.device, "render_frames")        # refused before the ray launch
+        if knobs is not None:
+            _check_culled_call(self.det, "render_frames")
         ray_o, ray_d = camera_rays(_scene_intrinsic(self.meta), poses, win, stride, device=self.device)
-        coarse, fine = self._render(ray_o.view(-1, 3), ray_d.view(-1, 3), rays.RENDER_TESTING_RAYS, n_importance)
-        return _frames_dict(coarse, fine, (poses.shape[0], win[2], win[3]))
+        occ = self._skip_grid(knobs, "render_frames")
+        (coarse, fine), counts = self._render_counted(ray_o.view(-1, 3), ray_d.view(-1, 3), rays.RENDER_TESTING_RAYS, n_importance, occ)
+        return _with_counts(_frames_dict(coarse, fine, (poses.shape[0], win[2], win[3])), counts)
 
     def score_frames(self, frames: Tensor, meta: dict, depth_frames: Optional[Tensor] = None, stride: int = 1, n_importance: int = 0,
-                     ssim: bool = False) -> dict:
+                     ssim: bool = False, skip_empty=None) -> dict:
         """Held-out camera frames against the scene's render of their poses, on the device: ``frames`` (1, k, Hs, Ws, 3) uint8 BGR at capture
         resolution, checked against the scene as :meth:`add_frames` checks them; ``meta`` a chunk meta with the k extrinsics; ``depth_frames``
         optionally the sensor's (1, k, Hd, Wd) uint16 millimetres.  The held-out bytes are pipeline.prepare_frames' resized bytes cropped to
@@ -753,12 +914,16 @@ class SceneStream:
         render has a depth for.  With ``ssim=True`` one more launch (``pipeline.frame_ssim(render, held_out, render_depth)``) adds the
         reference's second metric over the 7 x 7 windows the render has a depth for throughout: ``ssim``, ``ssim_channels`` (float64) and
         ``n_windows`` (int64) per frame, on the strided frames as they are; a strided content region below 7 x 7 pixels is then a
-        ValueError before any launch.  Nothing is added to the scene."""
+        ValueError before any launch.  Nothing is added to the scene.  ``skip_empty`` as in :meth:`render_rays`: the culled render is
+        scored, and the dict gains ``n_kept`` and ``n_samples`` -- scoring with and without it says what a threshold costs."""
         self._need_bank("score_frames")
+        knobs = _skip_knobs(skip_empty, self.det, self.device, "score_frames")
+        if knobs is not None:
+            _check_culled_call(self.det, "score_frames", frames)
         held, held_depth, _, n_importance = _score_held_out(self.meta, [self.meta], frames, [meta], depth_frames, stride, n_importance, self.mean, self.std,
                                                             ssim)
-        out = self.render_frames(extrinsic=meta["lidar2img"]["extrinsic"], stride=stride, n_importance=n_importance)
-        return _frame_scores(out, held, held_depth, ssim)
+        out = self.render_frames(extrinsic=meta["lidar2img"]["extrinsic"], stride=stride, n_importance=n_importance, skip_empty=knobs)
+        return _with_counts(_frame_scores(out, held, held_depth, ssim), None if knobs is None else (out["n_kept"], out["n_samples"]))
 
     def draw_detections(self, frames: Tensor, result: dict, c2w=None, extrinsic=None, window=None, stride: int = 1, capture: bool = False,
                         score_thr: float = 0.0, thickness: int = 1, palette=None) -> dict:
@@ -792,13 +957,45 @@ class SceneStream:
     def volume(self):
         """``(volume (C,X,Y,Z), valid (1,X,Y,Z) int64)`` of the views so far: K2-finish -> sigma-MLP -> K1-finish, what ``extract_volume``
         returns for them (channels-last memory)."""
+        return self._finish()[1:]
+
+    def _finish(self):
+        """The finishes :meth:`volume` and :meth:`occupancy` share, ring or not: ``(alpha (N,), volume, valid)``."""
         if self.n_views == 0:
             raise RuntimeError("the scene has no views yet: call add_views first")
         ring = self.window is not None
         with torch.no_grad():
             glob = ops.density_finish_ring(self._segs, self._lin.bias) if ring else ops.density_finish(self.state, self._lin.bias)
             alpha = _finished_alpha(self.det.nerf_mlp, self.points, glob)
-            return ops.volume_finish_ring(self._segs, alpha) if ring else ops.volume_finish(self.state, alpha)
+            return (alpha,) + (ops.volume_finish_ring(self._segs, alpha) if ring else ops.volume_finish(self.state, alpha))
+
+    def occupancy(self, threshold: float = 1e-3, dilate: int = 1, outside: str = "keep"):
+        """The scene's occupancy grid (rays.OccupancyGrid) over the views held now, from the stream's own finishes -- density finish, the
+        sigma-MLP's alpha, ``volume_finish``'s ``valid``: exactly what :meth:`volume` runs -- and one k_occupancy_bits launch.  A voxel is
+        solid iff ``not (alpha <= threshold)`` or no view saw it; a bit is set iff a voxel within Chebyshev distance ``dilate`` (0, 1, 2)
+        is solid; ``outside``: 'keep' or 'cull', what a culled render does with a sample outside the lattice.  The alpha is the same
+        ``1 - exp(-relu(sigma))`` of the same ``nerf_mlp`` that compositing applies to a sample, so the two compare directly.  The
+        default threshold is a GUESS: nobody has judged it on a trained checkpoint.  The grid is as coarse as the detection lattice.
+
+        Cached per ``(threshold, dilate, outside)`` and dropped by whatever changes the views held (``add_views``, ``add_frames``, an
+        eviction, ``drop_oldest``, ``reset``).  No views held: RuntimeError; bad knobs: ValueError, before any launch."""
+        key = _check_occupancy_knobs(threshold, dilate, outside)
+        if self.n_views == 0:
+            raise RuntimeError("the scene has no views yet: call add_views first")
+        if self._occ is None:
+            self._occ = {}
+        if key not in self._occ:
+            alpha, _, valid = self._finish()
+            self._occ[key] = _make_occupancy(alpha, valid, self.points, self.det.n_voxels, self.det.voxel_size, *key)
+        return self._occ[key]
+
+    def _skip_grid(self, skip_empty, what: str, *tensors):
+        """The grid of a ``skip_empty=`` render (None: no culling) once everything the call refuses has been checked."""
+        knobs = _skip_knobs(skip_empty, self.det, self.device, what)
+        if knobs is None:
+            return None
+        _check_culled_call(self.det, what, *tensors)
+        return self.occupancy(**knobs) if isinstance(knobs, dict) else knobs
 
     def detect(self, defer: bool = False):
         """Detections over the views so far: what ``simple_test`` returns, ``[dict(boxes_3d, scores_3d, labels_3d)]``; with ``defer`` a
@@ -861,6 +1058,7 @@ class SceneGroup:
     pool = None         # ops.SceneGroupRingState of a windowed group
     group = None        # ops.SceneGroupState of an unwindowed one
     banks = None        # with keep_views one rays.ViewBank per scene, else None
+    _occ = None         # per scene (threshold, dilate, outside) -> rays.OccupancyGrid of the views it holds now, made by occupancy()
     mean, std = IMG_MEAN, IMG_STD     # img_norm_cfg of add_frames (RGB)
 
     def __init__(self, det, img_metas, window: Optional[int] = None, keep_views: bool = False, mean=IMG_MEAN, std=IMG_STD):
@@ -920,9 +1118,16 @@ class SceneGroup:
     def n_chunks(self) -> List[int]:
         return [len(c) for c in self.chunk_views]
 
+    def _drop_grids(self, scenes) -> None:
+        """Whatever changes the views a scene holds drops that scene's cached occupancy grids."""
+        if self._occ is not None:
+            for s in scenes:
+                self._occ[s].clear()
+
     def reset(self, scenes=None) -> None:
         """Forget every view of the listed scenes: they start empty again; the others keep theirs."""
         scenes = ops.listed_scenes(self.n_scenes, scenes)
+        self._drop_grids(scenes)
         for s in scenes:
             if self.window is None:
                 self.group.states[s].reset()
@@ -938,6 +1143,7 @@ class SceneGroup:
             raise ValueError("drop_oldest needs a windowed group: begin_scenes(img_metas, window=S)")
         scenes = ops.listed_scenes(self.n_scenes, scenes)
         self.pool.drop_oldest(k, scenes)            # refused whole before any window or bank changes
+        self._drop_grids(scenes)
         if self.banks is not None:
             for s in scenes:
                 self.banks[s].drop_oldest(k)
@@ -948,6 +1154,7 @@ class SceneGroup:
         ``banked``: the listed scenes' view-bank segments, made by the caller (rays.ViewBank.make_segment changes nothing); they join
         their banks only once the states have taken the chunks, and a scene's oldest segment leaves with the oldest state of its full
         window, so states and banks hold the same chunks."""
+        self._drop_grids(scenes)
         if self.window is None:
             ops.scene_accumulate_group(self.group, scenes, *chunk, depth_gate=depth_gate)
         else:
@@ -1060,7 +1267,17 @@ class SceneGroup:
         from . import rays
         return _render_passes(self.det, [self.banks[s] for s in scenes], ray_os, ray_ds, step, batched, n_importance, rays.bank_group_stats)
 
-    def render_rays(self, ray_o, ray_d, scenes=None, batched: bool = False, n_importance: int = 0):
+    def _render_counted(self, ray_os, ray_ds, scenes: List[int], step: int, batched: bool, n_importance: int, occs):
+        """``(per listed scene (coarse, fine), per listed scene (n_kept, n_samples))``: :meth:`_render` and Nones without grids, else every
+        listed scene's culled passes on their own (:func:`_render_passes_culled`, the body of ``SceneStream``'s culled render): the kept
+        counts differ from scene to scene and are known only after each scene's read, so a scene's launches follow its own cull --
+        per scene and pass one count launch, one cull, one sampler launch and the MLP's calls, nothing grouped."""
+        if occs is None:
+            return self._render(ray_os, ray_ds, scenes, step, batched, n_importance), [None] * len(scenes)
+        res = [_render_passes_culled(self.det, self.banks[s], occ, o, d, step, n_importance) for s, occ, o, d in zip(scenes, occs, ray_os, ray_ds)]
+        return [r[:2] for r in res], [r[2:] for r in res]
+
+    def render_rays(self, ray_o, ray_d, scenes=None, batched: bool = False, n_importance: int = 0, skip_empty=None):
         """Render rays against the views the listed scenes hold: ``ray_o``, ``ray_d`` are lists of (R_s, 3) tensors, one pair per listed
         scene (the counts may differ, each at least 1); returns per listed scene ``dict(rgb (R_s,3), depth (R_s,), mask (R_s,) bool)`` as
         :meth:`SceneStream.render_rays` does.  Passes of at most ``rays.RENDER_TESTING_RAYS`` rays per scene: every scene that still has
@@ -1084,13 +1301,19 @@ class SceneGroup:
 
         Needs ``keep_views=True`` and at least one view in every listed scene (else RuntimeError); wrong list lengths or shapes are a
         ValueError; everything is refused before anything is launched.  No bank or state is changed.  Renders and evictions
-        (``add_views`` at a full window, ``drop_oldest``, ``reset``) must be issued on ONE stream (rays.ViewBank)."""
+        (``add_views`` at a full window, ``drop_oldest``, ``reset``) must be issued on ONE stream (rays.ViewBank).
+
+        ``skip_empty`` as in :meth:`SceneStream.render_rays` -- None, True, a dict of :meth:`occupancy`'s keywords (each scene then uses
+        its own grid) or one rays.OccupancyGrid for every listed scene: each listed scene's dict, ``n_kept`` and ``n_samples``
+        included, is what a :class:`SceneStream` holding the same chunks returns with the same ``skip_empty``.  The culled passes run
+        scene by scene (one count launch, one cull, one sampler launch per scene and pass).  With ``batched=True``: ValueError."""
         from . import rays
         scenes = self._need_banks("render_rays", scenes)
         n_importance = _check_n_importance(n_importance)
         ray_o, ray_d = self._check_rays(ray_o, ray_d, len(scenes))
-        res = self._render(ray_o, ray_d, scenes, rays.RENDER_TESTING_RAYS, batched, n_importance)
-        return [_render_dict(coarse, fine) for coarse, fine in res]
+        occs = self._skip_grids(skip_empty, scenes, batched, "render_rays", *ray_o, *ray_d)
+        res, counts = self._render_counted(ray_o, ray_d, scenes, rays.RENDER_TESTING_RAYS, batched, n_importance, occs)
+        return [_with_counts(_render_dict(coarse, fine), c) for (coarse, fine), c in zip(res, counts)]
 
     @staticmethod
     def _check_rays(ray_o, ray_d, n: int):
@@ -1105,12 +1328,12 @@ class SceneGroup:
                                  f"for listed scene {i}")
         return ray_o, ray_d
 
-    def render(self, ray_batches, scenes=None, batched: bool = False, n_importance: int = 0):
+    def render(self, ray_batches, scenes=None, batched: bool = False, n_importance: int = 0, skip_empty=None):
         """Every ray of the target views of one ray batch per listed scene: per scene what :meth:`SceneStream.render` returns
         (``outputs_coarse.rgb`` (T,h,w,3), ``outputs_coarse.depth`` (T,h,w,1), ``gt_rgb``, ``gt_depth`` -- ``rays.rendering_metrics``
         applies), through the passes of :meth:`render_rays` with SceneStream.render's pass size,
         ``N_rand * max(1, RENDER_TESTING_RAYS // N_rand)``; ``batched`` and ``n_importance`` (which adds ``outputs_fine``) as in
-        :meth:`render_rays`.  One stream, as there."""
+        :meth:`render_rays`.  One stream, as there.  ``skip_empty`` as in :meth:`render_rays`."""
         scenes = self._need_banks("render", scenes)
         n_importance = _check_n_importance(n_importance)
         ray_batches = list(ray_batches)
@@ -1118,10 +1341,13 @@ class SceneGroup:
             raise ValueError(f"render: {len(ray_batches)} ray batches for {len(scenes)} listed scenes")
         unpacked = [_unpack_ray_batch(rb) for rb in ray_batches]
         os_, ds_ = self._check_rays([u[0] for u in unpacked], [u[1] for u in unpacked], len(scenes))
-        res = self._render(os_, ds_, scenes, _render_step(self.det), batched, n_importance)
-        return [_render_views(coarse, fine, shape, gt_rgb, gt_depth) for (coarse, fine), (_, _, shape, gt_rgb, gt_depth) in zip(res, unpacked)]
+        occs = self._skip_grids(skip_empty, scenes, batched, "render", *os_, *ds_)
+        res, counts = self._render_counted(os_, ds_, scenes, _render_step(self.det), batched, n_importance, occs)
+        return [_with_counts(_render_views(coarse, fine, shape, gt_rgb, gt_depth), c)
+                for (coarse, fine), (_, _, shape, gt_rgb, gt_depth), c in zip(res, unpacked, counts)]
 
-    def render_frames(self, c2w=None, extrinsic=None, scenes=None, batched: bool = False, window=None, stride: int = 1, n_importance: int = 0):
+    def render_frames(self, c2w=None, extrinsic=None, scenes=None, batched: bool = False, window=None, stride: int = 1, n_importance: int = 0,
+                      skip_empty=None):
         """:meth:`SceneStream.render_frames` for the listed scenes at once: exactly one of ``c2w`` and ``extrinsic``, a list with one list of
         4 x 4 matrices per listed scene (the counts may differ, each at least 1).  Every scene uses its own intrinsics, scaled as in
         :meth:`SceneStream.render_frames`; ``window`` and ``stride`` are the call's (the group shares ``img_shape``).  ONE
@@ -1130,7 +1356,8 @@ class SceneGroup:
         every scene's frames are packed by one ndet_pack_frames launch per pass kind.  Returns a list of dicts as
         :meth:`SceneStream.render_frames` returns them: per scene bit for bit ``group.render_rays`` on the generated rays (with
         ``batched=True`` to :meth:`render_rays`' documented bounds), and a group of one scene is ``SceneStream.render_frames`` bit for bit.
-        RuntimeError without ``keep_views`` or for a listed scene without views; bad arguments are a ValueError before any launch."""
+        RuntimeError without ``keep_views`` or for a listed scene without views; bad arguments are a ValueError before any launch.
+        ``skip_empty`` as in :meth:`render_rays`."""
         from . import rays
         scenes = self._need_banks("render_frames", scenes)
         n_importance = _check_n_importance(n_importance)
@@ -1140,6 +1367,11 @@ class SceneGroup:
         poses = [_camera_poses(g, None, "render_frames") if c2w is not None else _camera_poses(None, g, "render_frames") for g in given]
         win, stride = _frame_grid(self.metas[0], window, stride)
         ks = [_scene_intrinsic(self.metas[s]) for s in scenes]
+        knobs = _skip_knobs(skip_empty, self.det, self.device, "render_frames")        # refused before the ray launches
+        if knobs is not None:
+            if batched:
+                raise ValueError("render_frames: batched=True and skip_empty exclude each other for now")
+            _check_culled_call(self.det, "render_frames")
         shared = OrderedDict()                      # listed scenes by the bytes of their intrinsic rows: one launch each
         for i, k in enumerate(ks):
             shared.setdefault(k[:2, :3].tobytes(), []).append(i)
@@ -1151,26 +1383,32 @@ class SceneGroup:
                 c = poses[i].shape[0]
                 ray_os[i], ray_ds[i] = o[at:at + c].view(-1, 3), d[at:at + c].view(-1, 3)
                 at += c
-        res = self._render(ray_os, ray_ds, scenes, rays.RENDER_TESTING_RAYS, batched, n_importance)
-        return [_frames_dict(coarse, fine, (p.shape[0], win[2], win[3])) for (coarse, fine), p in zip(res, poses)]
+        occs = self._skip_grids(knobs, scenes, batched, "render_frames")
+        res, counts = self._render_counted(ray_os, ray_ds, scenes, rays.RENDER_TESTING_RAYS, batched, n_importance, occs)
+        return [_with_counts(_frames_dict(coarse, fine, (p.shape[0], win[2], win[3])), c) for (coarse, fine), p, c in zip(res, poses, counts)]
 
     def score_frames(self, frames: Tensor, metas, scenes=None, depth_frames: Optional[Tensor] = None, batched: bool = False, stride: int = 1,
-                     n_importance: int = 0, ssim: bool = False):
+                     n_importance: int = 0, ssim: bool = False, skip_empty=None):
         """:meth:`SceneStream.score_frames` for the listed scenes at once: ``frames`` (len(scenes), k, Hs, Ws, 3) uint8 BGR, one row of k
         held-out frames per listed scene, checked as :meth:`add_frames` checks them; ``metas`` one chunk meta per row with its k extrinsics;
         ``depth_frames`` optionally (len(scenes), k, Hd, Wd) uint16 millimetres.  One ndet_resize_normalize_views launch (and one
         ndet_depth_frames launch) makes all the held-out frames, :meth:`render_frames` all the renders, and one ndet_frame_errors launch
         per scene compares them -- with ``ssim=True`` one ndet_frame_ssim launch per scene beside it, which adds ``ssim``, ``ssim_channels``
         and ``n_windows`` as in :meth:`SceneStream.score_frames`.  Returns a list of ``pipeline.frame_errors`` dicts; nothing is added to
-        any scene."""
+        any scene.  ``skip_empty`` as in :meth:`render_rays`: the culled renders are scored, every dict gains ``n_kept`` and ``n_samples``."""
         scenes = self._need_banks("score_frames", scenes)
+        knobs = _skip_knobs(skip_empty, self.det, self.device, "score_frames")
+        if knobs is not None:
+            if batched:
+                raise ValueError("score_frames: batched=True and skip_empty exclude each other for now")
+            _check_culled_call(self.det, "score_frames", frames)
         metas = list(metas)
         held, held_depth, k, n_importance = _score_held_out(self.metas[0], [self.metas[s] for s in scenes], frames, metas, depth_frames, stride, n_importance,
                                                             self.mean, self.std, ssim)
         outs = self.render_frames(extrinsic=[m["lidar2img"]["extrinsic"] for m in metas], scenes=scenes, batched=batched, stride=stride,
-                                  n_importance=n_importance)
-        return [_frame_scores(out, held[i * k:(i + 1) * k], None if held_depth is None else held_depth[i * k:(i + 1) * k], ssim)
-                for i, out in enumerate(outs)]
+                                  n_importance=n_importance, skip_empty=knobs)
+        return [_with_counts(_frame_scores(out, held[i * k:(i + 1) * k], None if held_depth is None else held_depth[i * k:(i + 1) * k], ssim),
+                             None if knobs is None else (out["n_kept"], out["n_samples"])) for i, out in enumerate(outs)]
 
     def _plan_detections(self, frames, results, c2w, extrinsic, scenes, trailing, dtype, window, stride, capture, score_thr, palette, what: str):
         """The checked plans of a grouped ``draw_detections`` / ``label_detections`` call, one per listed scene; nothing is launched."""
@@ -1209,6 +1447,11 @@ class SceneGroup:
     def _volumes(self, scenes: List[int]):
         """``(volume (n,C,X,Y,Z), valid (n,1,X,Y,Z) int64)`` of the listed scenes: grouped K2-finish -> one sigma-MLP call over all their
         rows -> grouped K1-finish (channels-last memory); in a windowed group the two finishes are the grouped ring finishes."""
+        return self._finishes(scenes)[1:]
+
+    def _finishes(self, scenes: List[int]):
+        """The finishes :meth:`_volumes` and :meth:`occupancy` share: ``(alpha (n N,), volume, valid)``, listed scene i's alpha in rows
+        ``[i N, (i + 1) N)``."""
         ring = self.window is not None
         points = self.pool.points if ring else self.group.points
         pts = torch.cat([points[s].reshape(3, -1) for s in scenes], dim=1) if len(scenes) > 1 else points[scenes[0]]
@@ -1217,7 +1460,38 @@ class SceneGroup:
         else:
             glob = ops.density_finish_group(self.group, self._lin.bias, scenes)
         alpha = _finished_alpha(self.det.nerf_mlp, pts, glob)
-        return ops.volume_finish_group_ring(self.pool, alpha, scenes) if ring else ops.volume_finish_group(self.group, alpha, scenes)
+        return (alpha,) + (ops.volume_finish_group_ring(self.pool, alpha, scenes) if ring else ops.volume_finish_group(self.group, alpha, scenes))
+
+    def occupancy(self, threshold: float = 1e-3, dilate: int = 1, outside: str = "keep", scenes=None):
+        """:meth:`SceneStream.occupancy` for the listed scenes: a list of rays.OccupancyGrid, each scene's own, from ONE run of the grouped
+        finishes :meth:`volume` runs over the listed scenes that have no cached grid for these knobs, and one k_occupancy_bits launch
+        each.  A scene's grid is cached per ``(threshold, dilate, outside)`` until ``add_views`` / ``add_frames``, an eviction,
+        ``drop_oldest`` or ``reset`` lists the scene.  ValueError for bad knobs or a listed scene without views, before any launch."""
+        key = _check_occupancy_knobs(threshold, dilate, outside)
+        scenes = self._need_views(scenes)
+        if self._occ is None:
+            self._occ = [{} for _ in self.metas]
+        todo = [s for s in scenes if key not in self._occ[s]]
+        if todo:
+            points = self.pool.points if self.window is not None else self.group.points
+            with torch.no_grad():
+                alpha, _, valid = self._finishes(todo)
+            n = alpha.numel() // len(todo)
+            for i, s in enumerate(todo):
+                self._occ[s][key] = _make_occupancy(alpha[i * n:(i + 1) * n], valid[i], points[s].view(3, *[int(v) for v in self.det.n_voxels]),
+                                                    self.det.n_voxels, self.det.voxel_size, *key)
+        return [self._occ[s][key] for s in scenes]
+
+    def _skip_grids(self, skip_empty, scenes: List[int], batched: bool, what: str, *tensors):
+        """The listed scenes' grids of a ``skip_empty=`` render (None: no culling) once everything the call refuses has been checked: a
+        rays.OccupancyGrid serves every listed scene (the group shares the lattice's size; each scene's first point is its own)."""
+        knobs = _skip_knobs(skip_empty, self.det, self.device, what)
+        if knobs is None:
+            return None
+        if batched:
+            raise ValueError(f"{what}: batched=True and skip_empty exclude each other for now")
+        _check_culled_call(self.det, what, *tensors)
+        return self.occupancy(scenes=scenes, **knobs) if isinstance(knobs, dict) else [knobs] * len(scenes)
 
     def volume(self, scenes=None):
         """Per listed scene ``(volume (C,X,Y,Z), valid (1,X,Y,Z) int64)`` of its views so far, as :meth:`SceneStream.volume` returns them."""
