@@ -542,6 +542,40 @@ int ndet_cull_write(const float* pts, int64_t n_points, const uint32_t* bits, co
 int ndet_ray_view_count_bank(const float* pts, int64_t n_points, const NdetBankView* views_dev, int n_views, float img_h, float img_w,
                              uint8_t* pixel_mask, int* view_count, void* stream);
 
+/* ---- early ray termination for renders from a streamed scene (nerf-det_amd/streaming.py, early_stop=; the reference composites every
+ * sample).  A pass of R rays x S samples is walked front to back in segments of consecutive columns [s0, s1); a ray whose transmittance
+ * at a segment's first column is below eps is left out from there on, its raw rows stay zero, and a zero row is an exact no-op in
+ * ndet_composite.  Every entry point checks its arguments on the host before any HIP call: a null pointer, a non-positive R or S,
+ * s0 < 0, s1 > S, s1 < s0 (s1 <= s0 for the front pair), an eps that is NaN or outside [0, 1) and the lattice's knobs as
+ * ndet_cull_count rejects them are NDET_E_INVALID; a segment of more than 32 columns, R S of 2^31 or more, 2^31 voxels or more, a
+ * misaligned pointer (raw: 16 bytes, the rest 4) and more than 2^24 workgroups are NDET_E_UNSUPPORTED.  Plain vector stores, no atomics:
+ * every output is the same bytes on every call.
+ *
+ * ndet_ray_advance: T[r] <- T[r] * prod_{s = s0}^{s1 - 1} ((1.0f - a_s) + 1e-10f), a_s = 1.0f - expf(-raw[r, s, 3]), s ascending, in
+ * ndet_composite's statements (raw2outputs' cumprod(1 - alpha + 1e-10), render_ray.py:196-247): advanced from 1 over columns [0, b),
+ * T[r] is ndet_composite's transparency[r, b] bit for bit.  raw (R S, 4), T (R) updated in place; one lane per ray, one store per ray;
+ * s0 == s1 launches nothing. */
+int ndet_ray_advance(const float* raw, float* T, int R, int S, int s0, int s1, void* stream);
+
+/* Ordered compaction of the LIVE rays' samples of the segment [s0, s1), 1 <= w = s1 - s0 <= 32, of pts (R S, 3), optionally through the
+ * occupancy grid of ndet_occupancy_bits in the same launch (the samples whose weights raw2outputs would compute, render_ray.py:196-247).
+ * The virtual point n = r w + c stands for the flat sample f = r S + s0 + c.  It is KEPT iff !(T[r] < eps) -- a float32 compare: a NaN
+ * transmittance keeps the ray -- and, if bits is not NULL, ndet_cull_count would keep pts[f] (the same float32 statements: nearest
+ * lattice point, finite test, `outside` rule).  With bits == NULL the arguments n_voxels, p0, vs and outside are ignored and may be NULL.
+ * The nominal width of a segment is the least of 4, 8, 16, 32 that holds w; a wave step covers 64 / nominal consecutive rays, lanes over
+ * (ray, column), and a wave owns one block of 512 / nominal consecutive rays:
+ *   ndet_front_blocks  the number of blocks of R rays at width w (0 for R <= 0 or w outside 1 .. 32);
+ *   ndet_front_count   block_count[b] = kept virtual points of block b (ndet_front_blocks(R, w) ints);
+ *   ndet_front_write   with block_first the EXCLUSIVE prefix sum of block_count: idx (M) int32, the kept f in ascending order, and
+ *                      pts_kept (M, 3) their points; M = the sum of block_count, which the caller reads back (one read).
+ * The bits are staged in LDS when they fit 64 KiB, else read from global memory.  Order inside a block comes from wave ballots and prefix
+ * popcounts; T must not change between the two launches. */
+int64_t ndet_front_blocks(int64_t R, int w);
+int ndet_front_count(const float* pts, int R, int S, int s0, int s1, const float* T, float eps, const uint32_t* bits, const int* n_voxels,
+                     const float* p0, const float* vs, int outside, int* block_count, void* stream);
+int ndet_front_write(const float* pts, int R, int S, int s0, int s1, const float* T, float eps, const uint32_t* bits, const int* n_voxels,
+                     const float* p0, const float* vs, int outside, const int* block_first, int* idx, float* pts_kept, void* stream);
+
 /* A7 exact API form. Replaces Projector.compute(), projection.py:91-151: rgb_feat (P, n_views, 3+d) and
  * mask (P, n_views) fp32 0/1, materialised like the reference. Same inputs as ndet_ray_view_stats. */
 int ndet_project_sample(const float* pts, int n_points, const float* KE, int n_views, float img_h, float img_w,

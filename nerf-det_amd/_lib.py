@@ -137,6 +137,10 @@ SIGNATURES = {
     "ndet_cull_count": ([_P, c_int64, _P, ctypes.POINTER(c_int), _F3, _F3, c_int, _P, _P], c_int),
     "ndet_cull_write": ([_P, c_int64, _P, ctypes.POINTER(c_int), _F3, _F3, c_int, _P, _P, _P, _P], c_int),
     "ndet_ray_view_count_bank": ([_P, c_int64, _P, c_int, c_float, c_float, _P, _P, _P], c_int),
+    "ndet_ray_advance": ([_P, _P, c_int, c_int, c_int, c_int, _P], c_int),
+    "ndet_front_blocks": ([c_int64, c_int], c_int64),
+    "ndet_front_count": ([_P, c_int, c_int, c_int, c_int, _P, c_float, _P, ctypes.POINTER(c_int), _F3, _F3, c_int, _P, _P], c_int),
+    "ndet_front_write": ([_P, c_int, c_int, c_int, c_int, _P, c_float, _P, ctypes.POINTER(c_int), _F3, _F3, c_int, _P, _P, _P, _P], c_int),
     "ndet_ray_view_stats_packed_bwd": ([_P, _P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, c_int, c_int64, c_int64, _P, _P], c_int),
     "ndet_project_sample": ([_P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, c_int64, c_int64, c_int64,
                              _P, c_int, c_int, c_int, c_int64, c_int64, _P, _P, _P], c_int),

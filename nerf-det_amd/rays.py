@@ -407,6 +407,74 @@ def cull_points(pts: Tensor, occ: OccupancyGrid):
     return idx, kept
 
 
+# ------------------------------------------------------------------------------------------------------
+# early ray termination (csrc/early_stop_kernels.hip): a transmittance state per ray, and the live rays' samples of one depth segment
+# ------------------------------------------------------------------------------------------------------
+def advance_transmittance(raw: Tensor, T: Tensor, s0: int, s1: int) -> Tensor:
+    """``T[r] *= prod over columns s0 <= s < s1 of ((1 - a) + 1e-10)``, ``a = 1 - exp(-raw[r, s, 3])``, s ascending, in k_composite's
+    float32 statements (k_ray_advance): advanced from 1 over columns ``[0, b)``, ``T`` is ``raw2outputs(raw, ...)['transparency'][:, b]``
+    bit for bit.  ``raw`` (R, S, 4) and ``T`` (R,) contiguous float32; ``T`` is updated in place and returned.  ``s0 == s1`` launches
+    nothing."""
+    if not (raw.is_cuda and T.is_cuda):
+        raise RuntimeError("nerfdet_amd.rays: tensors must live on the GPU (no CPU fallback)")
+    if raw.dim() != 3 or raw.shape[2] != 4 or tuple(T.shape) != (raw.shape[0],) or raw.dtype != torch.float32 or T.dtype != torch.float32 \
+            or not raw.is_contiguous() or not T.is_contiguous() or raw.device != T.device:
+        raise ValueError(f"advance_transmittance: raw {tuple(raw.shape)} must be contiguous float32 (R, S, 4) and T {tuple(T.shape)} (R,) beside it")
+    r, s = raw.shape[:2]
+    call = lambda: check(_lib.load().ndet_ray_advance(_ptr(raw), _ptr(T), r, s, int(s0), int(s1), _stream(raw)), "advance_transmittance")
+    if s0 == s1:
+        call()                                                 # the host checks alone
+    else:
+        trace.span("k_ray_advance", call, bytes=16 * r * (s1 - s0) + 8 * r, kind="hbm")
+    return T
+
+
+def front_segment(pts: Tensor, T: Tensor, s0: int, s1: int, eps: float, occ: Optional[OccupancyGrid] = None, all_live: bool = False):
+    """Ordered compaction of the live rays' samples of the segment ``[s0, s1)`` (at most 32 columns) of ``pts`` (R, S, 3):
+    ``(idx (M,) int32, pts_kept (M, 3))``, the flat indices ``f = r S + s`` of the kept samples in ascending order and those points.  A
+    sample is kept iff ``not (T[r] < eps)`` in float32 (a NaN transmittance keeps its ray) and, with ``occ``, :func:`cull_points` would
+    keep it -- in the same launch.  Two launches (k_front_count, k_front_write) around one prefix sum; M reaches the host in ONE
+    device-to-host read, the call's only synchronisation; ``M = 0`` skips the second launch.  ``all_live=True`` (no ``occ``) is the
+    caller's word that no ray has stopped: ``M = R (s1 - s0)`` is then known on the host, and neither the count launch nor the read
+    happens.  The same bytes on every call."""
+    if not (pts.is_cuda and T.is_cuda and (occ is None or occ.bits.is_cuda)):
+        raise RuntimeError("nerfdet_amd.rays: tensors must live on the GPU (no CPU fallback)")
+    if pts.dim() != 3 or pts.shape[2] != 3 or tuple(T.shape) != (pts.shape[0],) or T.dtype != torch.float32 or not T.is_contiguous():
+        raise ValueError(f"front_segment: pts {tuple(pts.shape)} must be (R, S, 3) and T {tuple(T.shape)} contiguous float32 (R,)")
+    if pts.device != T.device or (occ is not None and occ.bits.device != pts.device):
+        raise ValueError("front_segment: the points, the transmittance and the grid live on different devices")
+    if all_live and occ is not None:
+        raise ValueError("front_segment: all_live says nothing about what a grid culls")
+    p = pts.to(torch.float32).contiguous()
+    r, s = p.shape[:2]
+    s0, s1, eps = int(s0), int(s1), float(eps)
+    w = s1 - s0
+    lib = _lib.load()
+    if occ is None:
+        geom = (None, None, None, None, 0)
+    else:
+        geom = (_ptr(occ.bits), (ctypes.c_int * 3)(*occ.n_voxels), _lib.float3(occ.p0), _lib.float3(occ.voxel_size), _lib.NDET_OUTSIDE[occ.outside])
+    blocks = int(lib.ndet_front_blocks(r, w))
+    if all_live and blocks:
+        per = 512 >> max(2, (w - 1).bit_length())              # rays of a block: 512 / the nominal width (include/nerfdet_hip.h)
+        first = torch.arange(blocks, dtype=torch.int32, device=p.device) * (per * w)
+        m = r * w
+    else:
+        counts = torch.empty((blocks,), dtype=torch.int32, device=p.device)
+        trace.span("k_front_count", lambda: check(lib.ndet_front_count(_ptr(p), r, s, s0, s1, _ptr(T), eps, *geom, _ptr(counts), _stream(p)),
+                                                  "front_count"), bytes=4 * r + (12 * r * w if occ is not None else 0) + 4 * blocks, kind="hbm")
+        last = torch.cumsum(counts, 0, dtype=torch.int32)
+        first = last - counts
+        m = int(last[-1])                                      # the one read
+    idx = torch.empty((m,), dtype=torch.int32, device=p.device)
+    kept = torch.empty((m, 3), dtype=torch.float32, device=p.device)
+    if m:
+        trace.span("k_front_write", lambda: check(lib.ndet_front_write(_ptr(p), r, s, s0, s1, _ptr(T), eps, *geom, _ptr(first), _ptr(idx),
+                                                                       _ptr(kept), _stream(p)), "front_write"),
+                   bytes=4 * r + 12 * r * w + 16 * m, kind="hbm")
+    return idx, kept
+
+
 class Projector:
     """projection.py:20-151.  ``compute`` keeps the reference's signature and materialised outputs."""
 
@@ -540,6 +608,26 @@ def importance_merge(z_vals, weights, ray_o, ray_d, N_importance, det, u: Option
 
 
 FINE_MLP_ROWS = 8192 * 64     # sample rows per nerf_mlp call of a fine pass: what a coarse pass of RENDER_TESTING_RAYS rays x 64 samples hands it
+
+
+MLP_STABLE_ROWS = 24576       # sample rows from which on a nerf_mlp call's launches no longer depend on its row count (mlp_rows_padded)
+
+
+def mlp_rows_padded(nerf_mlp, pts, ray_d, globalfeat, floor: int):
+    """``nerf_mlp`` over flat sample rows -- ``pts`` (n, 3), ``ray_d`` (n, 3), ``globalfeat`` (n, F) -- as ``(rgb, sigma)``, the call
+    padded with copies of its first row up to ``floor`` rows.  No scale is shared across a call's rows (:func:`fine_mlp`), but WHICH
+    launches a call makes depends on its row count: below 192 tiles of 128 rows the bottleneck layer leaves the 128 x 256 tile
+    (conv3d.choose_tiling_split), and below some 16 384 rows ATen's 128 -> 3 GEMM of the colour head picks another kernel; both sum in
+    another order, and ``rgb`` moves in its last bit (2.4e-7 measured; sigma does not move).  From MLP_STABLE_ROWS rows on a row's
+    result was the same in every call measured (24 575 .. 262 143 rows).  A caller whose row counts fall below that, and who owes the
+    bits of a larger call, pads up to ``min(MLP_STABLE_ROWS, rows of the larger call)``: at that size the call makes the larger call's
+    launches or is the larger call's size."""
+    n = pts.shape[0]
+    if n >= floor:
+        return nerf_mlp(pts, ray_d, globalfeat)
+    pad = lambda t: torch.cat([t, t[:1].expand(floor - n, *t.shape[1:])], dim=0)
+    rgb, sigma = nerf_mlp(pad(pts), pad(ray_d), pad(globalfeat))
+    return rgb[:n], sigma[:n]
 
 
 def fine_mlp(nerf_mlp, pts, ray_d, globalfeat):

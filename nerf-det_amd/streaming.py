@@ -65,6 +65,12 @@ one count launch over all samples for the ray mask (rays.ray_view_count_bank), o
 MLP over the kept rows only, and the compositing over the same ray ranges with the culled samples at sigma = 0, an exact no-op.  The
 default ``skip_empty=None`` makes the launches and the bits it made without the keyword.
 
+``early_stop=`` on the same four calls, alone or with ``skip_empty``, walks every pass front to back in segments of a few samples and
+stops a ray once its transmittance is below ``eps``: a transmittance per ray advanced over each finished segment
+(rays.advance_transmittance), the live rays' samples of the next one compacted in order (rays.front_segment, through the grid in the same
+launch; one read), sampler and MLP over those rows only.  What lies behind the first opaque surface composites as sigma = 0; the result
+is the plain pieces' with those rows zeroed, within ``eps`` of the plain render.  The default ``early_stop=None`` changes nothing.
+
 Inference only: no training / autograd, no hipGraph replay, one scene per stream; whole chunks are dropped, not single views out of one.
 Without ``keep_views`` there is no ray branch (rendering needs every view's map).
 """
@@ -541,12 +547,13 @@ def _skip_knobs(skip_empty, det, device, what: str):
     raise ValueError(f"{what}: skip_empty={skip_empty!r} must be None, True, a dict of occupancy()'s keywords or a rays.OccupancyGrid")
 
 
-def _check_culled_call(det, what: str, *tensors) -> None:
-    """What a culled render refuses beyond its unculled twin: a training detector and CPU tensors (RuntimeError), before any launch."""
+def _check_culled_call(det, what: str, *tensors, keyword: str = "skip_empty") -> None:
+    """What a culled (or, ``keyword='early_stop'``, a stopped) render refuses beyond its plain twin: a training detector and CPU tensors
+    (RuntimeError), before any launch."""
     if det.training:
-        raise RuntimeError(f"{what}(skip_empty=) is inference only: call det.eval() first")
+        raise RuntimeError(f"{what}({keyword}=) is inference only: call det.eval() first")
     if any(not t.is_cuda for t in tensors):
-        raise RuntimeError(f"{what}(skip_empty=): the rays must live on the GPU (no CPU fallback)")
+        raise RuntimeError(f"{what}({keyword}=): the rays must live on the GPU (no CPU fallback)")
 
 
 def _make_occupancy(alpha: Tensor, valid: Tensor, points: Tensor, n_voxels, voxel_size, threshold: float, dilate: int, outside: str):
@@ -571,43 +578,133 @@ def _culled_shade(det, bank, occ, dirs: Tensor, pts: Tensor, z: Tensor):
     idx, kept = rays.cull_points(flat, occ)
     m = idx.shape[0]
     raw = torch.zeros((c * ss, 4), dtype=torch.float32, device=pts.device)
-    if m:
-        idx = idx.to(torch.int64)
-        kdirs = dirs.to(torch.float32)[idx // ss]
-        rows = rays.RENDER_TESTING_RAYS * det.N_samples
-        for a in range(0, m, rows):
-            glob = rays.ray_view_stats_bank(kept[a:a + rows], bank)[0]
-            for b in range(0, glob.shape[0], rays.FINE_MLP_ROWS):
-                sl = slice(a + b, a + min(b + rays.FINE_MLP_ROWS, glob.shape[0]))
-                rgb, sigma = det.nerf_mlp(kept[sl], kdirs[sl], glob[b:b + rays.FINE_MLP_ROWS])
-                raw.index_copy_(0, idx[sl], torch.cat([rgb, sigma], dim=-1))
+    _shade_rows(det, bank, dirs, ss, idx, kept, raw)
     return rays.raw2outputs(raw.view(c, ss, 4), z, pm.view(c, ss)), m
 
 
-def _render_passes_culled(det, bank, occ, ray_o: Tensor, ray_d: Tensor, step: int, n_importance: int):
+def _shade_rows(det, bank, dirs: Tensor, ss: int, idx: Tensor, kept: Tensor, raw: Tensor, floor: int = 0) -> None:
+    """The kept sample rows ``idx`` (M,) with their points ``kept`` (M, 3) through the bank sampler (at most ``RENDER_TESTING_RAYS *
+    N_samples`` rows a launch) and ``nerf_mlp`` (at most ``rays.FINE_MLP_ROWS`` rows a call), with the direction of row f's ray
+    ``f // ss``, into the rows ``idx`` of ``raw`` (c ss, 4).  No kept row: nothing is launched.  ``floor``: an MLP call of fewer rows is
+    padded up to it (rays.mlp_rows_padded), for callers whose calls can be small."""
+    from . import rays
+    m = idx.shape[0]
+    if not m:
+        return
+    idx = idx.to(torch.int64)
+    kdirs = dirs.to(torch.float32)[idx // ss]
+    rows = rays.RENDER_TESTING_RAYS * det.N_samples
+    for a in range(0, m, rows):
+        glob = rays.ray_view_stats_bank(kept[a:a + rows], bank)[0]
+        for b in range(0, glob.shape[0], rays.FINE_MLP_ROWS):
+            sl = slice(a + b, a + min(b + rays.FINE_MLP_ROWS, glob.shape[0]))
+            rgb, sigma = rays.mlp_rows_padded(det.nerf_mlp, kept[sl], kdirs[sl], glob[b:b + rays.FINE_MLP_ROWS], floor)
+            raw.index_copy_(0, idx[sl], torch.cat([rgb, sigma], dim=-1))
+
+
+def _render_passes_culled(det, bank, occ, ray_o: Tensor, ray_d: Tensor, step: int, n_importance: int, shade=None):
     """:func:`_render_passes` for ONE scene with the samples ``occ`` calls empty left out (:func:`_culled_shade`), over the same ray ranges
     pass by pass: ``((rgb, depth, mask) of the coarse pass, the same of the fine pass or None, kept rows, sample rows)``, the last two
     host ints over every cull of the call.  With ``n_importance > 0`` the coarse weights are the culled coarse pass's (dense, zero where
-    culled), rays.importance_merge runs over them and the merged samples are culled, sampled, shaded and composited the same way."""
+    culled), rays.importance_merge runs over them and the merged samples are culled, sampled, shaded and composited the same way.
+    ``shade(dirs, pts, z)`` replaces :func:`_culled_shade` (:func:`_render_passes_stopped`)."""
     from . import rays
+    if shade is None:
+        shade = lambda d, pts, z: _culled_shade(det, bank, occ, d, pts, z)
     out, fine = ([], [], []), ([], [], [])
     n_kept = n_samples = 0
     with torch.no_grad():
         for i0 in range(0, ray_o.shape[0], step):
             o, d = ray_o[i0:i0 + step], ray_d[i0:i0 + step]
             pts, z = rays.sample_along_camera_ray(o, d, det.near_far_range, det.N_samples, det=True)
-            res, m = _culled_shade(det, bank, occ, d, pts, z)
+            res, m = shade(d, pts, z)
             n_kept, n_samples = n_kept + m, n_samples + z.numel()
             for acc, key in zip(out, ("rgb", "depth", "mask")):
                 acc.append(res[key])
             if n_importance > 0:
                 pts_f, z_f, _ = rays.importance_merge(z, res["weights"], o, d, n_importance, True)
-                res, m = _culled_shade(det, bank, occ, d, pts_f, z_f)
+                res, m = shade(d, pts_f, z_f)
                 n_kept, n_samples = n_kept + m, n_samples + z_f.numel()
                 for acc, key in zip(fine, ("rgb", "depth", "mask")):
                     acc.append(res[key])
     cat = lambda acc: tuple(a[0] if len(a) == 1 else torch.cat(a, dim=0) for a in acc)
     return cat(out), cat(fine) if n_importance > 0 else None, n_kept, n_samples
+
+
+# ---- early_stop=: renders that walk every ray front to back and leave out what lies behind an opaque surface ----
+EARLY_STOP_SEGMENTS = (4, 8, 16, 32)
+EARLY_STOP_DEFAULTS = dict(eps=1e-3, segment=8)      # segment: the fastest of 8, 16, 32 at the cfg2 frame (DESIGN.md 17)
+
+
+def _stop_knobs(early_stop, what: str):
+    """What an ``early_stop=`` argument asks for, checked before any launch: None (no stopping: None or False) or ``dict(eps, segment)``
+    (True: the defaults; a dict: those of its two keys it names).  ``eps``: a number in [0, 1); ``segment``: 4, 8, 16 or 32.  Else
+    ValueError."""
+    if early_stop is None or early_stop is False:
+        return None
+    if early_stop is True:
+        return dict(EARLY_STOP_DEFAULTS)
+    if not isinstance(early_stop, dict):
+        raise ValueError(f"{what}: early_stop={early_stop!r} must be None, True or a dict of the keys {sorted(EARLY_STOP_DEFAULTS)}")
+    if not set(early_stop) <= set(EARLY_STOP_DEFAULTS):
+        raise ValueError(f"{what}: early_stop takes the keys {sorted(EARLY_STOP_DEFAULTS)}, got {sorted(early_stop)}")
+    knobs = dict(EARLY_STOP_DEFAULTS, **early_stop)
+    eps, segment = knobs["eps"], knobs["segment"]
+    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.floating, np.integer)) or not 0.0 <= float(np.float32(eps)) < 1.0:
+        raise ValueError(f"{what}: early_stop's eps={eps!r} must be a number in [0, 1) as a float32")
+    if isinstance(segment, bool) or not isinstance(segment, (int, np.integer)) or segment not in EARLY_STOP_SEGMENTS:
+        raise ValueError(f"{what}: early_stop's segment={segment!r} must be one of {EARLY_STOP_SEGMENTS}")
+    return dict(eps=float(eps), segment=int(segment))
+
+
+def _stop_checked(det, early_stop, what: str, *tensors, batched: bool = False):
+    """The ``dict(eps, segment)`` of an ``early_stop=`` render (None: no stopping) once everything the call refuses has been checked, before
+    any launch: bad knobs and ``batched=True`` are a ValueError, a training detector and CPU tensors a RuntimeError."""
+    stop = _stop_knobs(early_stop, what)
+    if stop is not None:
+        if batched:
+            raise ValueError(f"{what}: batched=True and early_stop exclude each other for now")
+        _check_culled_call(det, what, *tensors, keyword="early_stop")
+    return stop
+
+
+def _front_shade(det, bank, occ, stop: dict, dirs: Tensor, pts: Tensor, z: Tensor):
+    """:func:`_culled_shade` walked front to back: ``pts`` (c, ss, 3), ``z`` (c, ss), ``dirs`` (c, 3) -> ``(rays.raw2outputs' dict, kept
+    rows)``.  The samples of a ray go in segments of ``stop['segment']`` columns (the last may be shorter).  ``T`` (c,) starts at 1 and is
+    advanced over each finished segment (rays.advance_transmittance: k_composite's own exclusive product of the raw built so far); at a
+    segment's first column b > 0 a ray with ``T < stop['eps']`` is stopped: its rows from b on are never computed and stay zero, which
+    leaves ``T`` where it is, so the ray stays stopped.  rays.front_segment picks the live rays' samples of the segment -- through ``occ``
+    as well when there is a grid (None: no culling) -- and they alone go through sampler and MLP (:func:`_shade_rows`).  The ray mask
+    comes from the count pass over ALL samples, and the compositing runs over the pass's rays as ever.  One device-to-host read per
+    segment; without a grid none for the first (every ray is live), and no live ray ends the walk.  A late segment has few live rows,
+    and a ``nerf_mlp`` call of few rows makes other launches than the pass-sized call of the plain render, whose ``rgb`` differs in the
+    last bit: such a call is padded to ``min(rays.MLP_STABLE_ROWS, c ss)`` rows (rays.mlp_rows_padded), which keeps the result the
+    plain pieces' bit for bit at the price of an MLP call of that size per late segment."""
+    from . import rays
+    c, ss = pts.shape[:2]
+    seg, eps = stop["segment"], stop["eps"]
+    pts = pts.to(torch.float32).contiguous()
+    pm, _ = rays.ray_view_count_bank(pts.view(-1, 3), bank)
+    raw = torch.zeros((c * ss, 4), dtype=torch.float32, device=pts.device)
+    T = torch.ones((c,), dtype=torch.float32, device=pts.device)
+    kept_rows, floor = 0, min(rays.MLP_STABLE_ROWS, c * ss)
+    for s0 in range(0, ss, seg):
+        if s0:
+            rays.advance_transmittance(raw.view(c, ss, 4), T, s0 - seg, s0)
+        idx, kept = rays.front_segment(pts, T, s0, min(s0 + seg, ss), eps, occ, all_live=occ is None and s0 == 0)
+        if occ is None and not idx.shape[0]:
+            break                                              # every ray has stopped
+        _shade_rows(det, bank, dirs, ss, idx, kept, raw, floor)
+        kept_rows += idx.shape[0]
+    return rays.raw2outputs(raw.view(c, ss, 4), z, pm.view(c, ss)), kept_rows
+
+
+def _render_passes_stopped(det, bank, occ, stop: dict, ray_o: Tensor, ray_d: Tensor, step: int, n_importance: int):
+    """:func:`_render_passes_culled` with every pass shaded front to back (:func:`_front_shade`; ``occ`` None: no grid).  With
+    ``n_importance > 0`` the coarse weights are dense, zero where stopped or culled; rays.importance_merge runs over them and the merged
+    ``N_samples + k`` samples are segmented again from ``T = 1``."""
+    return _render_passes_culled(det, bank, occ, ray_o, ray_d, step, n_importance,
+                                 shade=lambda d, pts, z: _front_shade(det, bank, occ, stop, d, pts, z))
 
 
 def _with_counts(out: dict, counts) -> dict:
@@ -822,15 +919,20 @@ class SceneStream:
         bank = self._need_bank("rendering")
         return _render_passes(self.det, [bank], [ray_o], [ray_d], step, False, n_importance, _one_bank_stats)[0]
 
-    def _render_counted(self, ray_o: Tensor, ray_d: Tensor, step: int, n_importance: int, occ):
-        """``((coarse, fine), counts)``: :meth:`_render` and None without a grid, else the culled passes (:func:`_render_passes_culled`)
-        and their ``(n_kept, n_samples)``."""
-        if occ is None:
+    def _render_counted(self, ray_o: Tensor, ray_d: Tensor, step: int, n_importance: int, occ, stop=None):
+        """``((coarse, fine), counts)``: :meth:`_render` and None without a grid and without ``stop``, else the culled passes
+        (:func:`_render_passes_culled`) or, with ``stop``, the front-to-back ones (:func:`_render_passes_stopped`) and their ``(n_kept,
+        n_samples)``."""
+        if occ is None and stop is None:
             return self._render(ray_o, ray_d, step, n_importance), None
-        coarse, fine, n_kept, n_samples = _render_passes_culled(self.det, self._need_bank("rendering"), occ, ray_o, ray_d, step, n_importance)
+        bank = self._need_bank("rendering")
+        if stop is None:
+            coarse, fine, n_kept, n_samples = _render_passes_culled(self.det, bank, occ, ray_o, ray_d, step, n_importance)
+        else:
+            coarse, fine, n_kept, n_samples = _render_passes_stopped(self.det, bank, occ, stop, ray_o, ray_d, step, n_importance)
         return (coarse, fine), (n_kept, n_samples)
 
-    def render_rays(self, ray_o: Tensor, ray_d: Tensor, n_importance: int = 0, skip_empty=None):
+    def render_rays(self, ray_o: Tensor, ray_d: Tensor, n_importance: int = 0, skip_empty=None, early_stop=None):
         """Render rays ``ray_o``, ``ray_d`` (R,3) against the views held: ``dict(rgb (R,3), depth (R,), mask (R,) bool)``, what
         ``rays.render_rays_func(det=True)`` composites (render_ray.py:250-327) with the detector's ``near_far_range`` and ``N_samples``,
         ``rays.RENDER_TESTING_RAYS`` rays per pass.  Needs ``keep_views=True`` and at least one view (else RuntimeError).
@@ -850,29 +952,42 @@ class SceneStream:
         regrouping its rows across calls changes nothing).  With ``n_importance > 0`` the fine samples are drawn from the culled coarse weights and culled the
         same way.  The dict gains the host ints ``n_kept`` and ``n_samples``.  Many culled samples each just under the threshold can
         add up along a ray: compare with the plain render (or :meth:`score_frames`) on your own data.  Inference only, not graphed:
-        a training detector or CPU rays are a RuntimeError, bad knobs or another lattice's grid a ValueError, before any launch."""
+        a training detector or CPU rays are a RuntimeError, bad knobs or another lattice's grid a ValueError, before any launch.
+
+        ``early_stop``: None or False (the default: every launch and every bit as without the keyword), True (``eps=1e-3`` and the
+        default ``segment``) or ``dict(eps=, segment=)`` with ``0 <= eps < 1`` and ``segment`` 4, 8, 16 or 32; alone or with
+        ``skip_empty``.  Every pass is then walked front to back in segments of ``segment`` samples (:func:`_front_shade`): a ray whose
+        transmittance -- k_composite's own exclusive product -- is below ``eps`` at a segment's first sample is stopped, and its
+        samples from there on are never computed: they composite as ``sigma = 0``.  The result is bit for bit that of the plain
+        pieces with those rows (and the grid's) zeroed; ``mask`` is the plain render's.  Against the plain render a stopped ray's
+        ``rgb`` moves by less than ``eps`` per channel and its ``depth`` by at most ``eps far / (1 - eps)``; ``eps=0`` stops
+        nothing.  The default ``eps`` rests on that bound (a frame byte moves by at most one level), not on a measurement on trained
+        weights.  Each segment costs one device-to-host read.  The dict gains ``n_kept`` and ``n_samples``.  Refusals as for
+        ``skip_empty``."""
         from . import rays
         self._need_bank("render_rays")
         n_importance = _check_n_importance(n_importance)
         if ray_o.dim() != 2 or ray_o.shape[1] != 3 or ray_d.shape != ray_o.shape:
             raise ValueError(f"render_rays takes (R,3) origins and directions, got {tuple(ray_o.shape)} and {tuple(ray_d.shape)}")
+        stop = _stop_checked(self.det, early_stop, "render_rays", ray_o, ray_d)
         occ = self._skip_grid(skip_empty, "render_rays", ray_o, ray_d)
-        (coarse, fine), counts = self._render_counted(ray_o, ray_d, rays.RENDER_TESTING_RAYS, n_importance, occ)
+        (coarse, fine), counts = self._render_counted(ray_o, ray_d, rays.RENDER_TESTING_RAYS, n_importance, occ, stop)
         return _with_counts(_render_dict(coarse, fine), counts)
 
-    def render(self, ray_batch: dict, n_importance: int = 0, skip_empty=None):
+    def render(self, ray_batch: dict, n_importance: int = 0, skip_empty=None, early_stop=None):
         """Every ray of the ray batch's target views, as ``rays.render_rays(render_testing=True)`` returns them (render_ray.py:452-517):
         ``outputs_coarse.rgb`` (T,h,w,3), ``outputs_coarse.depth`` (T,h,w,1), ``gt_rgb``, ``gt_depth`` -- ``rays.rendering_metrics`` applies.
         ``n_importance=k > 0`` adds ``outputs_fine`` (same shapes), as ``rays.render_rays(render_testing=True, N_importance=k)`` does.
-        ``skip_empty`` as in :meth:`render_rays` (the dict gains ``n_kept`` and ``n_samples``)."""
+        ``skip_empty`` and ``early_stop`` as in :meth:`render_rays` (the dict gains ``n_kept`` and ``n_samples``)."""
         self._need_bank("render")
         n_importance = _check_n_importance(n_importance)
         ray_o, ray_d, shape, gt_rgb, gt_depth = _unpack_ray_batch(ray_batch)
+        stop = _stop_checked(self.det, early_stop, "render", ray_o, ray_d)
         occ = self._skip_grid(skip_empty, "render", ray_o, ray_d)
-        (coarse, fine), counts = self._render_counted(ray_o, ray_d, _render_step(self.det), n_importance, occ)
+        (coarse, fine), counts = self._render_counted(ray_o, ray_d, _render_step(self.det), n_importance, occ, stop)
         return _with_counts(_render_views(coarse, fine, shape, gt_rgb, gt_depth), counts)
 
-    def render_frames(self, c2w=None, extrinsic=None, window=None, stride: int = 1, n_importance: int = 0, skip_empty=None):
+    def render_frames(self, c2w=None, extrinsic=None, window=None, stride: int = 1, n_importance: int = 0, skip_empty=None, early_stop=None):
         """Camera frames of k >= 1 poses against the views held -- pose in, BGR and depth out, in the formats :meth:`add_frames` takes.
         Exactly one of ``c2w`` (k camera-to-world 4 x 4, as ``pipeline.scene_cameras(info)["c2w"]``) and ``extrinsic`` (k world-to-camera
         4 x 4, as a chunk meta carries them: inverted on the host in float64, rounded to float32).  The intrinsics are the scene meta's,
@@ -887,8 +1002,8 @@ class SceneStream:
         outputs are bit for bit ``self.render_rays(*camera_rays(...))`` on the concatenated rays, reshaped; the frames are
         ``pack_frames`` of them: depth 0 is a hole (``mask`` false), as in the sensor's frames.  Needs ``keep_views=True`` and at least one
         view (else RuntimeError); bad arguments are a ValueError before any launch.  No state and no bank is changed.
-        ``skip_empty`` as in :meth:`render_rays`: the frames are ``pack_frames`` of the culled float outputs, and the dict gains
-        ``n_kept`` and ``n_samples``."""
+        ``skip_empty`` and ``early_stop`` as in :meth:`render_rays`: the frames are ``pack_frames`` of the culled or stopped float
+        outputs, and the dict gains ``n_kept`` and ``n_samples``."""
         from . import rays
         self._need_bank("render_frames")
         n_importance = _check_n_importance(n_importance)
@@ -897,13 +1012,14 @@ class SceneStream:
         knobs = _skip_knobs(skip_empty, self.det, self.device, "render_frames")        # refused before the ray launch
         if knobs is not None:
             _check_culled_call(self.det, "render_frames")
+        stop = _stop_checked(self.det, early_stop, "render_frames")
         ray_o, ray_d = camera_rays(_scene_intrinsic(self.meta), poses, win, stride, device=self.device)
         occ = self._skip_grid(knobs, "render_frames")
-        (coarse, fine), counts = self._render_counted(ray_o.view(-1, 3), ray_d.view(-1, 3), rays.RENDER_TESTING_RAYS, n_importance, occ)
+        (coarse, fine), counts = self._render_counted(ray_o.view(-1, 3), ray_d.view(-1, 3), rays.RENDER_TESTING_RAYS, n_importance, occ, stop)
         return _with_counts(_frames_dict(coarse, fine, (poses.shape[0], win[2], win[3])), counts)
 
     def score_frames(self, frames: Tensor, meta: dict, depth_frames: Optional[Tensor] = None, stride: int = 1, n_importance: int = 0,
-                     ssim: bool = False, skip_empty=None) -> dict:
+                     ssim: bool = False, skip_empty=None, early_stop=None) -> dict:
         """Held-out camera frames against the scene's render of their poses, on the device: ``frames`` (1, k, Hs, Ws, 3) uint8 BGR at capture
         resolution, checked against the scene as :meth:`add_frames` checks them; ``meta`` a chunk meta with the k extrinsics; ``depth_frames``
         optionally the sensor's (1, k, Hd, Wd) uint16 millimetres.  The held-out bytes are pipeline.prepare_frames' resized bytes cropped to
@@ -915,15 +1031,18 @@ class SceneStream:
         reference's second metric over the 7 x 7 windows the render has a depth for throughout: ``ssim``, ``ssim_channels`` (float64) and
         ``n_windows`` (int64) per frame, on the strided frames as they are; a strided content region below 7 x 7 pixels is then a
         ValueError before any launch.  Nothing is added to the scene.  ``skip_empty`` as in :meth:`render_rays`: the culled render is
-        scored, and the dict gains ``n_kept`` and ``n_samples`` -- scoring with and without it says what a threshold costs."""
+        scored, and the dict gains ``n_kept`` and ``n_samples`` -- scoring with and without it says what a threshold costs.
+        ``early_stop`` as in :meth:`render_rays`, in the same way."""
         self._need_bank("score_frames")
         knobs = _skip_knobs(skip_empty, self.det, self.device, "score_frames")
         if knobs is not None:
             _check_culled_call(self.det, "score_frames", frames)
+        stop = _stop_checked(self.det, early_stop, "score_frames", frames)
         held, held_depth, _, n_importance = _score_held_out(self.meta, [self.meta], frames, [meta], depth_frames, stride, n_importance, self.mean, self.std,
                                                             ssim)
-        out = self.render_frames(extrinsic=meta["lidar2img"]["extrinsic"], stride=stride, n_importance=n_importance, skip_empty=knobs)
-        return _with_counts(_frame_scores(out, held, held_depth, ssim), None if knobs is None else (out["n_kept"], out["n_samples"]))
+        out = self.render_frames(extrinsic=meta["lidar2img"]["extrinsic"], stride=stride, n_importance=n_importance, skip_empty=knobs,
+                                 early_stop=stop)
+        return _with_counts(_frame_scores(out, held, held_depth, ssim), (out["n_kept"], out["n_samples"]) if "n_kept" in out else None)
 
     def draw_detections(self, frames: Tensor, result: dict, c2w=None, extrinsic=None, window=None, stride: int = 1, capture: bool = False,
                         score_thr: float = 0.0, thickness: int = 1, palette=None) -> dict:
@@ -1267,17 +1386,22 @@ class SceneGroup:
         from . import rays
         return _render_passes(self.det, [self.banks[s] for s in scenes], ray_os, ray_ds, step, batched, n_importance, rays.bank_group_stats)
 
-    def _render_counted(self, ray_os, ray_ds, scenes: List[int], step: int, batched: bool, n_importance: int, occs):
+    def _render_counted(self, ray_os, ray_ds, scenes: List[int], step: int, batched: bool, n_importance: int, occs, stop=None):
         """``(per listed scene (coarse, fine), per listed scene (n_kept, n_samples))``: :meth:`_render` and Nones without grids, else every
         listed scene's culled passes on their own (:func:`_render_passes_culled`, the body of ``SceneStream``'s culled render): the kept
         counts differ from scene to scene and are known only after each scene's read, so a scene's launches follow its own cull --
         per scene and pass one count launch, one cull, one sampler launch and the MLP's calls, nothing grouped."""
-        if occs is None:
+        if occs is None and stop is None:
             return self._render(ray_os, ray_ds, scenes, step, batched, n_importance), [None] * len(scenes)
-        res = [_render_passes_culled(self.det, self.banks[s], occ, o, d, step, n_importance) for s, occ, o, d in zip(scenes, occs, ray_os, ray_ds)]
+        occs = [None] * len(scenes) if occs is None else occs
+        if stop is None:
+            res = [_render_passes_culled(self.det, self.banks[s], occ, o, d, step, n_importance) for s, occ, o, d in zip(scenes, occs, ray_os, ray_ds)]
+        else:          # front to back (early_stop=), scene by scene for the same reason
+            res = [_render_passes_stopped(self.det, self.banks[s], occ, stop, o, d, step, n_importance)
+                   for s, occ, o, d in zip(scenes, occs, ray_os, ray_ds)]
         return [r[:2] for r in res], [r[2:] for r in res]
 
-    def render_rays(self, ray_o, ray_d, scenes=None, batched: bool = False, n_importance: int = 0, skip_empty=None):
+    def render_rays(self, ray_o, ray_d, scenes=None, batched: bool = False, n_importance: int = 0, skip_empty=None, early_stop=None):
         """Render rays against the views the listed scenes hold: ``ray_o``, ``ray_d`` are lists of (R_s, 3) tensors, one pair per listed
         scene (the counts may differ, each at least 1); returns per listed scene ``dict(rgb (R_s,3), depth (R_s,), mask (R_s,) bool)`` as
         :meth:`SceneStream.render_rays` does.  Passes of at most ``rays.RENDER_TESTING_RAYS`` rays per scene: every scene that still has
@@ -1306,13 +1430,16 @@ class SceneGroup:
         ``skip_empty`` as in :meth:`SceneStream.render_rays` -- None, True, a dict of :meth:`occupancy`'s keywords (each scene then uses
         its own grid) or one rays.OccupancyGrid for every listed scene: each listed scene's dict, ``n_kept`` and ``n_samples``
         included, is what a :class:`SceneStream` holding the same chunks returns with the same ``skip_empty``.  The culled passes run
-        scene by scene (one count launch, one cull, one sampler launch per scene and pass).  With ``batched=True``: ValueError."""
+        scene by scene (one count launch, one cull, one sampler launch per scene and pass).  With ``batched=True``: ValueError.
+        ``early_stop`` as in :meth:`SceneStream.render_rays`, alone or with ``skip_empty``: each listed scene's dict is the stream's with
+        the same ``early_stop``; the passes run scene by scene, and ``batched=True`` is a ValueError."""
         from . import rays
         scenes = self._need_banks("render_rays", scenes)
         n_importance = _check_n_importance(n_importance)
         ray_o, ray_d = self._check_rays(ray_o, ray_d, len(scenes))
+        stop = _stop_checked(self.det, early_stop, "render_rays", *ray_o, *ray_d, batched=batched)
         occs = self._skip_grids(skip_empty, scenes, batched, "render_rays", *ray_o, *ray_d)
-        res, counts = self._render_counted(ray_o, ray_d, scenes, rays.RENDER_TESTING_RAYS, batched, n_importance, occs)
+        res, counts = self._render_counted(ray_o, ray_d, scenes, rays.RENDER_TESTING_RAYS, batched, n_importance, occs, stop)
         return [_with_counts(_render_dict(coarse, fine), c) for (coarse, fine), c in zip(res, counts)]
 
     @staticmethod
@@ -1328,12 +1455,12 @@ class SceneGroup:
                                  f"for listed scene {i}")
         return ray_o, ray_d
 
-    def render(self, ray_batches, scenes=None, batched: bool = False, n_importance: int = 0, skip_empty=None):
+    def render(self, ray_batches, scenes=None, batched: bool = False, n_importance: int = 0, skip_empty=None, early_stop=None):
         """Every ray of the target views of one ray batch per listed scene: per scene what :meth:`SceneStream.render` returns
         (``outputs_coarse.rgb`` (T,h,w,3), ``outputs_coarse.depth`` (T,h,w,1), ``gt_rgb``, ``gt_depth`` -- ``rays.rendering_metrics``
         applies), through the passes of :meth:`render_rays` with SceneStream.render's pass size,
         ``N_rand * max(1, RENDER_TESTING_RAYS // N_rand)``; ``batched`` and ``n_importance`` (which adds ``outputs_fine``) as in
-        :meth:`render_rays`.  One stream, as there.  ``skip_empty`` as in :meth:`render_rays`."""
+        :meth:`render_rays`.  One stream, as there.  ``skip_empty`` and ``early_stop`` as in :meth:`render_rays`."""
         scenes = self._need_banks("render", scenes)
         n_importance = _check_n_importance(n_importance)
         ray_batches = list(ray_batches)
@@ -1341,13 +1468,14 @@ class SceneGroup:
             raise ValueError(f"render: {len(ray_batches)} ray batches for {len(scenes)} listed scenes")
         unpacked = [_unpack_ray_batch(rb) for rb in ray_batches]
         os_, ds_ = self._check_rays([u[0] for u in unpacked], [u[1] for u in unpacked], len(scenes))
+        stop = _stop_checked(self.det, early_stop, "render", *os_, *ds_, batched=batched)
         occs = self._skip_grids(skip_empty, scenes, batched, "render", *os_, *ds_)
-        res, counts = self._render_counted(os_, ds_, scenes, _render_step(self.det), batched, n_importance, occs)
+        res, counts = self._render_counted(os_, ds_, scenes, _render_step(self.det), batched, n_importance, occs, stop)
         return [_with_counts(_render_views(coarse, fine, shape, gt_rgb, gt_depth), c)
                 for (coarse, fine), (_, _, shape, gt_rgb, gt_depth), c in zip(res, unpacked, counts)]
 
     def render_frames(self, c2w=None, extrinsic=None, scenes=None, batched: bool = False, window=None, stride: int = 1, n_importance: int = 0,
-                      skip_empty=None):
+                      skip_empty=None, early_stop=None):
         """:meth:`SceneStream.render_frames` for the listed scenes at once: exactly one of ``c2w`` and ``extrinsic``, a list with one list of
         4 x 4 matrices per listed scene (the counts may differ, each at least 1).  Every scene uses its own intrinsics, scaled as in
         :meth:`SceneStream.render_frames`; ``window`` and ``stride`` are the call's (the group shares ``img_shape``).  ONE
@@ -1357,7 +1485,7 @@ class SceneGroup:
         :meth:`SceneStream.render_frames` returns them: per scene bit for bit ``group.render_rays`` on the generated rays (with
         ``batched=True`` to :meth:`render_rays`' documented bounds), and a group of one scene is ``SceneStream.render_frames`` bit for bit.
         RuntimeError without ``keep_views`` or for a listed scene without views; bad arguments are a ValueError before any launch.
-        ``skip_empty`` as in :meth:`render_rays`."""
+        ``skip_empty`` and ``early_stop`` as in :meth:`render_rays`."""
         from . import rays
         scenes = self._need_banks("render_frames", scenes)
         n_importance = _check_n_importance(n_importance)
@@ -1372,6 +1500,7 @@ class SceneGroup:
             if batched:
                 raise ValueError("render_frames: batched=True and skip_empty exclude each other for now")
             _check_culled_call(self.det, "render_frames")
+        stop = _stop_checked(self.det, early_stop, "render_frames", batched=batched)
         shared = OrderedDict()                      # listed scenes by the bytes of their intrinsic rows: one launch each
         for i, k in enumerate(ks):
             shared.setdefault(k[:2, :3].tobytes(), []).append(i)
@@ -1384,31 +1513,33 @@ class SceneGroup:
                 ray_os[i], ray_ds[i] = o[at:at + c].view(-1, 3), d[at:at + c].view(-1, 3)
                 at += c
         occs = self._skip_grids(knobs, scenes, batched, "render_frames")
-        res, counts = self._render_counted(ray_os, ray_ds, scenes, rays.RENDER_TESTING_RAYS, batched, n_importance, occs)
+        res, counts = self._render_counted(ray_os, ray_ds, scenes, rays.RENDER_TESTING_RAYS, batched, n_importance, occs, stop)
         return [_with_counts(_frames_dict(coarse, fine, (p.shape[0], win[2], win[3])), c) for (coarse, fine), p, c in zip(res, poses, counts)]
 
     def score_frames(self, frames: Tensor, metas, scenes=None, depth_frames: Optional[Tensor] = None, batched: bool = False, stride: int = 1,
-                     n_importance: int = 0, ssim: bool = False, skip_empty=None):
+                     n_importance: int = 0, ssim: bool = False, skip_empty=None, early_stop=None):
         """:meth:`SceneStream.score_frames` for the listed scenes at once: ``frames`` (len(scenes), k, Hs, Ws, 3) uint8 BGR, one row of k
         held-out frames per listed scene, checked as :meth:`add_frames` checks them; ``metas`` one chunk meta per row with its k extrinsics;
         ``depth_frames`` optionally (len(scenes), k, Hd, Wd) uint16 millimetres.  One ndet_resize_normalize_views launch (and one
         ndet_depth_frames launch) makes all the held-out frames, :meth:`render_frames` all the renders, and one ndet_frame_errors launch
         per scene compares them -- with ``ssim=True`` one ndet_frame_ssim launch per scene beside it, which adds ``ssim``, ``ssim_channels``
         and ``n_windows`` as in :meth:`SceneStream.score_frames`.  Returns a list of ``pipeline.frame_errors`` dicts; nothing is added to
-        any scene.  ``skip_empty`` as in :meth:`render_rays`: the culled renders are scored, every dict gains ``n_kept`` and ``n_samples``."""
+        any scene.  ``skip_empty`` as in :meth:`render_rays`: the culled renders are scored, every dict gains ``n_kept`` and ``n_samples``.
+        ``early_stop`` as in :meth:`render_rays`, in the same way."""
         scenes = self._need_banks("score_frames", scenes)
         knobs = _skip_knobs(skip_empty, self.det, self.device, "score_frames")
         if knobs is not None:
             if batched:
                 raise ValueError("score_frames: batched=True and skip_empty exclude each other for now")
             _check_culled_call(self.det, "score_frames", frames)
+        stop = _stop_checked(self.det, early_stop, "score_frames", frames, batched=batched)
         metas = list(metas)
         held, held_depth, k, n_importance = _score_held_out(self.metas[0], [self.metas[s] for s in scenes], frames, metas, depth_frames, stride, n_importance,
                                                             self.mean, self.std, ssim)
         outs = self.render_frames(extrinsic=[m["lidar2img"]["extrinsic"] for m in metas], scenes=scenes, batched=batched, stride=stride,
-                                  n_importance=n_importance, skip_empty=knobs)
+                                  n_importance=n_importance, skip_empty=knobs, early_stop=stop)
         return [_with_counts(_frame_scores(out, held[i * k:(i + 1) * k], None if held_depth is None else held_depth[i * k:(i + 1) * k], ssim),
-                             None if knobs is None else (out["n_kept"], out["n_samples"])) for i, out in enumerate(outs)]
+                             (out["n_kept"], out["n_samples"]) if "n_kept" in out else None) for i, out in enumerate(outs)]
 
     def _plan_detections(self, frames, results, c2w, extrinsic, scenes, trailing, dtype, window, stride, capture, score_thr, palette, what: str):
         """The checked plans of a grouped ``draw_detections`` / ``label_detections`` call, one per listed scene; nothing is launched."""
