@@ -80,7 +80,7 @@ __global__ __launch_bounds__(BN_THREADS) void k_bn_stats(const float* __restrict
     // x itself is known to 8e-5 sigma (a third array for the pivots avoided it and cost the finish half as many loads again).
     const float inv_n = 1.0f / (float)(hi - lo);
     const float4 d = make_float4(s1.x * inv_n, s1.y * inv_n, s1.z * inv_n, s1.w * inv_n);        // mean_g - s_g
-    const float4 m2 = make_float4(fmaxf(s2.x - s1.x * d.x, 0.f), fmaxf(s2.y - s1.y * d.y, 0.f), fmaxf(s2.z - s1.z * d.z, 0.f), fmaxf(s2.w - s1.w * d.w, 0.f));
+    const float4 m2 = ndet_relu4(make_float4(s2.x - s1.x * d.x, s2.y - s1.y * d.y, s2.z - s1.z * d.z, s2.w - s1.w * d.w));   // (a NaN stays: running_var must show it)
     bn_store_partials(make_float4(sh.x + d.x, sh.y + d.y, sh.z + d.z, sh.w + d.w), m2, G, partial);
 }
 
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(BN_THREADS) void k_bn_apply(const float* __restrict
             const float4 v = bn_ld4(x + o);
             float4 w = make_float4((v.x - m.x) * is.x * ga.x + be.x, (v.y - m.y) * is.y * ga.y + be.y, (v.z - m.z) * is.z * ga.z + be.z, (v.w - m.w) * is.w * ga.w + be.w);
             if (res) { const float4 u = bn_ld4(res + o); w.x += u.x; w.y += u.y; w.z += u.z; w.w += u.w; }
-            if (relu) { w.x = fmaxf(w.x, 0.f); w.y = fmaxf(w.y, 0.f); w.z = fmaxf(w.z, 0.f); w.w = fmaxf(w.w, 0.f); }
+            if (relu) w = ndet_relu4(w);
             *reinterpret_cast<float4*>(y + o) = w;
             mx = fmaxf(fmaxf(mx, fmaxf(fabsf(w.x), fabsf(w.y))), fmaxf(fabsf(w.z), fabsf(w.w)));
         }
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(BN_THREADS) void k_bn_bwd_stats(const float* __rest
         for (int64_t r = lo + rl; r < hi; r += G.RL) {
             const int64_t o = r * G.C + 4 * q;
             float4 g = bn_ld4(dy + o);
-            if (relu) { const float4 u = bn_ld4(y + o); g.x = u.x > 0.f ? g.x : 0.f; g.y = u.y > 0.f ? g.y : 0.f; g.z = u.z > 0.f ? g.z : 0.f; g.w = u.w > 0.f ? g.w : 0.f; }
+            if (relu) g = ndet_relu_mask4(bn_ld4(y + o), g);
             const float4 v = bn_ld4(x + o);
             s1.x += g.x; s1.y += g.y; s1.z += g.z; s1.w += g.w;
             s2.x += g.x * ((v.x - m.x) * is.x); s2.y += g.y * ((v.y - m.y) * is.y); s2.z += g.z * ((v.z - m.z) * is.z); s2.w += g.w * ((v.w - m.w) * is.w);
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(BN_THREADS) void k_bn_bwd_apply(const float* __rest
         for (int64_t r = lo + rl; r < hi; r += G.RL) {
             const int64_t o = r * G.C + 4 * q;
             float4 g = bn_ld4(dy + o);
-            if (relu) { const float4 u = bn_ld4(y + o); g.x = u.x > 0.f ? g.x : 0.f; g.y = u.y > 0.f ? g.y : 0.f; g.z = u.z > 0.f ? g.z : 0.f; g.w = u.w > 0.f ? g.w : 0.f; }
+            if (relu) g = ndet_relu_mask4(bn_ld4(y + o), g);
             if (dres) *reinterpret_cast<float4*>(dres + o) = g;
             const float4 v = bn_ld4(x + o);
             const float4 w = make_float4(a.x * (g.x - b.x - (v.x - m.x) * is.x * cc.x), a.y * (g.y - b.y - (v.y - m.y) * is.y * cc.y),

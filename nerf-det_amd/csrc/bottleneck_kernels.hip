@@ -231,10 +231,10 @@ __global__ __launch_bounds__(256, 2) void k_bottleneck_f16x2(const BottleneckPar
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                float v = fmaxf((acc1[a][r] * osc1) * sc + sh, 0.f);
+                float v = ndet_relu((acc1[a][r] * osc1) * sc + sh);
                 v = rowok[row] ? v : 0.0f;
                 acc1[a][r] = v;
-                m = fmaxf(m, v);
+                m = fmaxf(m, v);         // (fmaxf: the scale's maximum is over the values that are not NaN)
             }
         ymax1 = wg_maximum(m);
         const float ys1 = conv_xscale_of(ymax1);
@@ -349,7 +349,7 @@ __global__ __launch_bounds__(256, 2) void k_bottleneck_f16x2(const BottleneckPar
         float m = 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float v = fmaxf((acc2[0][r] * osc2) * sc + sh, 0.f);
+            const float v = ndet_relu((acc2[0][r] * osc2) * sc + sh);
             acc2[0][r] = v;
             m = fmaxf(m, v);
         }
@@ -412,7 +412,7 @@ __global__ __launch_bounds__(256, 2) void k_bottleneck_f16x2(const BottleneckPar
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) vv[rt][r] = fmaxf(((c2[c][rt][r] * osc3) * sc3 + sh3) + rr[rt][r], 0.f);
+                for (int r = 0; r < 16; ++r) vv[rt][r] = ndet_relu(((c2[c][rt][r] * osc3) * sc3 + sh3) + rr[rt][r]);
             if constexpr (c + 1 < NCB) { if (!DS) load_identity(c + 1); }      // (rr is consumed: the next slice's identity rows travel under these stores)
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt)

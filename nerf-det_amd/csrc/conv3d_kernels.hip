@@ -221,12 +221,12 @@ __global__ __launch_bounds__(256) void k_conv3d_splitk_reduce(const float* __res
                 const float4 sc = *reinterpret_cast<const float4*>(scale + co), sh = *reinterpret_cast<const float4*>(shift + co);
                 v.x = v.x * sc.x + sh.x; v.y = v.y * sc.y + sh.y; v.z = v.z * sc.z + sh.z; v.w = v.w * sc.w + sh.w;
             }
-            if (relu == 2) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+            if (relu == 2) v = ndet_relu4(v);
             if (res) {
                 const float4 rr = *reinterpret_cast<const float4*>(res + i);
                 v.x = v.x + rr.x; v.y = v.y + rr.y; v.z = v.z + rr.z; v.w = v.w + rr.w;
             }
-            if (relu == 1) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+            if (relu == 1) v = ndet_relu4(v);
             *reinterpret_cast<float4*>(out + i) = v;
             mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
         } else {
@@ -234,9 +234,9 @@ __global__ __launch_bounds__(256) void k_conv3d_splitk_reduce(const float* __res
             for (int s = 1; s < splits; ++s) v = v + partial[(int64_t)s * MN + i];
             const int co = (int)(i % Cout);
             if (scale) v = v * scale[co] + shift[co];
-            if (relu == 2) v = fmaxf(v, 0.0f);
+            if (relu == 2) v = ndet_relu(v);
             if (res) v = v + res[i];
-            if (relu == 1) v = fmaxf(v, 0.0f);
+            if (relu == 1) v = ndet_relu(v);
             out[i] = v;
             mx = fmaxf(mx, fabsf(v));
         }
@@ -375,10 +375,10 @@ __global__ __launch_bounds__(256) void k_bn_relu_maxpool(const float* __restrict
             const int xx = 2 * ow + dx;
             if (xx < 0 || xx >= W) continue;
             const float4 v = *reinterpret_cast<const float4*>(x + (((int64_t)n * H + y) * W + xx) * C + c4 * 4);
-            m.x = fmaxf(m.x, v.x * sc.x + sh.x);
-            m.y = fmaxf(m.y, v.y * sc.y + sh.y);
-            m.z = fmaxf(m.z, v.z * sc.z + sh.z);
-            m.w = fmaxf(m.w, v.w * sc.w + sh.w);
+            m.x = ndet_max(m.x, v.x * sc.x + sh.x);
+            m.y = ndet_max(m.y, v.y * sc.y + sh.y);
+            m.z = ndet_max(m.z, v.z * sc.z + sh.z);
+            m.w = ndet_max(m.w, v.w * sc.w + sh.w);
         }
     }
     *reinterpret_cast<float4*>(out + i * 4) = m;

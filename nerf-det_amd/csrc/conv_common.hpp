@@ -256,13 +256,13 @@ __device__ __forceinline__ void conv_store_rows_mapped(const Conv3dParams& p, co
                     const float4 sc = *reinterpret_cast<const float4*>(p.scale + co), sh = *reinterpret_cast<const float4*>(p.shift + co);
                     v.x = v.x * sc.x + sh.x; v.y = v.y * sc.y + sh.y; v.z = v.z * sc.z + sh.z; v.w = v.w * sc.w + sh.w;
                 }
-                if (p.relu == 2) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                if (p.relu == 2) v = ndet_relu4(v);
                 if (p.res) {
                     const int64_t rrow = walk ? ((int64_t)ud * p.RH + (uh >> 1)) * p.RW + (uw >> 1) : res_row(m, orow);
                     const float4 rr = *reinterpret_cast<const float4*>(p.res + rrow * p.Cout + co);
                     v.x = v.x + rr.x; v.y = v.y + rr.y; v.z = v.z + rr.z; v.w = v.w + rr.w;
                 }
-                if (p.relu == 1) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                if (p.relu == 1) v = ndet_relu4(v);
                 mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
             }
             if (p.nt) {
@@ -280,9 +280,9 @@ __device__ __forceinline__ void conv_store_rows_mapped(const Conv3dParams& p, co
             float v = Cs[row * cld + c] * osc;
             if (!raw) {
                 if (p.scale) v = v * p.scale[co] + p.shift[co];
-                if (p.relu == 2) v = fmaxf(v, 0.0f);
+                if (p.relu == 2) v = ndet_relu(v);
                 if (p.res) v = v + p.res[res_row(m, orow) * p.Cout + co];
-                if (p.relu == 1) v = fmaxf(v, 0.0f);
+                if (p.relu == 1) v = ndet_relu(v);
                 mx = fmaxf(mx, fabsf(v));
             }
             dst[orow * p.Cout + co] = v;

@@ -288,9 +288,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, (uni_min_wgs<BM, BN, (SCHB & 3)>())
                 for (int r = 0; r < 16; ++r) {
                     const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)(((r & 3) + 8 * (r >> 2)) * p.Cout * 4));
                     float v = (acc[ta][tb][r] * osc) * sc + sh;
-                    if (p.relu == 2) v = fmaxf(v, 0.f);
+                    if (p.relu == 2) v = ndet_relu(v);
                     v += rr[r];
-                    if (p.relu == 1) v = fmaxf(v, 0.f);
+                    if (p.relu == 1) v = ndet_relu(v);
                     if (p.nt) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rout, vo, so, 2);
                     else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rout, vo, so, 0);
                     if (mrow + (r & 3) + 8 * (r >> 2) < p.M) mx = fmaxf(mx, fabsf(v));      // rows past M: dropped stores of values that are not the layer's
@@ -387,7 +387,7 @@ __global__ __launch_bounds__(256, MID == 64 ? (SCH == 1 ? CHAIN64_F16_WGS : 3) :
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     float a = (acc[ta][tb][r] * osc1) * sc + sh;
-                    if (p.relu) a = fmaxf(a, 0.f);
+                    if (p.relu) a = ndet_relu(a);
                     acc[ta][tb][r] = a;
                     ymax = fmaxf(ymax, fabsf(a));
                 }
@@ -425,7 +425,7 @@ __global__ __launch_bounds__(256, MID == 64 ? (SCH == 1 ? CHAIN64_F16_WGS : 3) :
                         float a = acc[ta][tb][r], b = acc[ta][tb][r + 1];   // rows r and r + 1 of this lane's column
                         if (SCH != 1) {                                      // (fp16 pair: BN + ReLU were applied in place above)
                             a = a * sc + sh; b = b * sc + sh;
-                            if (p.relu) { a = fmaxf(a, 0.f); b = fmaxf(b, 0.f); }
+                            if (p.relu) { a = ndet_relu(a); b = ndet_relu(b); }
                         }
                         const int row = (HALVES == 1 ? wm * WM : 0) + ta * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                         uint16_t* da = Y + row * YRS + ((((col >> 3) ^ (row & 7)) << 3) | (col & 7));
@@ -490,9 +490,9 @@ __global__ __launch_bounds__(256, MID == 64 ? (SCH == 1 ? CHAIN64_F16_WGS : 3) :
                 for (int r = 0; r < 16; ++r) {
                     const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)((rt * 32 + (r & 3) + 8 * (r >> 2)) * c.Cout3 * 4));
                     float v = (cc[r] * osc3) * sc3 + sh3;
-                    if (c.relu3 == 2) v = fmaxf(v, 0.f);
+                    if (c.relu3 == 2) v = ndet_relu(v);
                     v += rr[r];
-                    if (c.relu3 == 1) v = fmaxf(v, 0.f);
+                    if (c.relu3 == 1) v = ndet_relu(v);
                     if (p.nt) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rout, vo, so, 2);
                     else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rout, vo, so, 0);
                     if (m0 + h * RH + 4 * (lane >> 5) + rt * 32 + (r & 3) + 8 * (r >> 2) < p.M) omax = fmaxf(omax, fabsf(v));
@@ -1347,9 +1347,9 @@ __global__ __launch_bounds__(64 * (NCONS + 4), 1) void k_conv_split_wsp(const Co
                         float v = acc[ta][tb][r] * osc;
                         if (!raw) {
                             if (p.scale) v = v * sc + sh;
-                            if (p.relu == 2) v = fmaxf(v, 0.f);
+                            if (p.relu == 2) v = ndet_relu(v);
                             if (has_res) v = v + rr[ta][r];
-                            if (p.relu == 1) v = fmaxf(v, 0.f);
+                            if (p.relu == 1) v = ndet_relu(v);
                             if (rowl + 16 * ta + r < p.M) tmx = fmaxf(tmx, fabsf(v));
                         }
                         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rout, vo, so, 0);

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void k_density_features_packed(const float* __
         mean = sum / denom;                                   // NOT zeroed at cnt == 0 (nerfdet.py:241)
         const float dm = mean - fl;
         float s = qq - 2.0f * dm * ss + nv * (dm * dm);
-        s = fmaxf(s, 0.0f);                                   // a sum of squares: rounding may leave -1 ulp
+        s = ndet_max(s, 0.0f);                                // a sum of squares: rounding may leave -1 ulp (a NaN stays NaN)
         float var = s / denom;
         if (cnt == 0) var = 1e6f;                             // nerfdet.py:249
         cov = expf(-var);
@@ -382,7 +382,7 @@ __device__ __forceinline__ float2 k2_finish_value(float a, float q, float s, flo
     const float mean = sm / denom;                        // NOT zeroed at cnt == 0 (nerfdet.py:241)
     const float dm = mean - fill;
     float sq = q - 2.0f * dm * s + nv * (dm * dm);
-    sq = fmaxf(sq, 0.0f);                                 // a sum of squares: rounding may leave -1 ulp
+    sq = ndet_max(sq, 0.0f);                              // a sum of squares: rounding may leave -1 ulp (a NaN stays NaN)
     float var = sq / denom;
     if (cnt == 0) var = 1e6f;                             // nerfdet.py:249
     return make_float2(mean, expf(-var));

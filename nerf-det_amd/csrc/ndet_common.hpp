@@ -52,6 +52,20 @@ hipError_t ndet_lds_limit(const void* kernel, size_t bytes);
 
 // ---- device helpers ----------------------------------------------------------------------
 
+// Maximum / minimum / ReLU that carry a NaN, as torch.relu, max_pool, clamp and threshold_backward do ("Non-finite values"):
+// IEEE 754-2019 maximum / minimum, one v_maximum3_f32 / v_minimum3_f32 each; for operands that are not NaN the bits of fmaxf / fminf
+// (-0 < +0 included).  fmaxf / fminf return the operand that is NOT a NaN: they stay where a max |x| is built, which is by contract
+// the maximum over the elements that are not NaN, and nowhere else on a value the reference passes through a maximum.
+__device__ __forceinline__ float ndet_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float ndet_min(float a, float b) { return __builtin_elementwise_minimum(a, b); }
+__device__ __forceinline__ float ndet_relu(float v) { return __builtin_elementwise_maximum(v, 0.0f); }
+__device__ __forceinline__ float4 ndet_relu4(float4 v) { return make_float4(ndet_relu(v.x), ndet_relu(v.y), ndet_relu(v.z), ndet_relu(v.w)); }
+// threshold_backward: the gradient passes unless y <= 0, so it passes where y is NaN
+__device__ __forceinline__ float ndet_relu_mask(float y, float g) { return !(y <= 0.0f) ? g : 0.0f; }
+__device__ __forceinline__ float4 ndet_relu_mask4(float4 y, float4 g) {
+    return make_float4(ndet_relu_mask(y.x, g.x), ndet_relu_mask(y.y, g.y), ndet_relu_mask(y.z, g.z), ndet_relu_mask(y.w, g.w));
+}
+
 // Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share one).  Give each XCD a
 // contiguous slab of tiles so neighbouring voxel tiles (which hit the same feature pixels)
 // share an L2.  Bijective for any n (cdna guide, "XCD swizzle must be bijective").  Speed only.

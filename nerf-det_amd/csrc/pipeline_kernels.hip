@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void k_relu_affine_bwd(const float4* __restric
         float4 v = g[i];
         if (relu) {
             const float4 t = y[i];
-            v.x = t.x > 0.f ? v.x : 0.f; v.y = t.y > 0.f ? v.y : 0.f; v.z = t.z > 0.f ? v.z : 0.f; v.w = t.w > 0.f ? v.w : 0.f;
+            v = ndet_relu_mask4(t, v);
         }
         if (gm) gm[i] = v;
         const float4 s = scale[i % c4];

@@ -220,9 +220,9 @@ __global__ __launch_bounds__(256, 2) void k_point_mlp(const PointMlpParams p) {
                     const float bv[4] = {bb.x, bb.y, bb.z, bb.w};
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const float v = fmaxf(acc[mt][nt][4 * g + j] * osc + bv[j], 0.0f);
+                        const float v = ndet_relu(acc[mt][nt][4 * g + j] * osc + bv[j]);
                         acc[mt][nt][4 * g + j] = v;
-                        m = fmaxf(m, v);
+                        m = fmaxf(m, v);     // (fmaxf: the row's scale comes from its values that are not NaN)
                     }
                 }
             m = fmaxf(m, __shfl_xor(m, 32));
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(256, 2) void k_point_mlp(const PointMlpParams p) {
         if (n < p.N) {
             const float sg = (((sigp[tid] + sigp[PM_BM + tid]) + sigp[2 * PM_BM + tid]) + sigp[3 * PM_BM + tid]) + xdot[tid] + p.bsig[0];
             if (p.raw) p.raw[n] = sg;
-            p.alpha[n] = 1.0f - expf(-fmaxf(sg, 0.0f));     // F.relu (nerf_mlp.py:227), 1 - exp(-density) (nerfdet.py:257)
+            p.alpha[n] = 1.0f - expf(-ndet_relu(sg));     // F.relu (nerf_mlp.py:227), 1 - exp(-density) (nerfdet.py:257)
         }
     }
 }

@@ -265,7 +265,7 @@ __global__ __launch_bounds__(64) void k_composite(const float* __restrict__ raw,
     rgb_map[r * 3 + 1] = c1;
     rgb_map[r * 3 + 2] = c2;
     float dep = wz / (wsum + 1e-8f);
-    dep = fminf(fmaxf(dep, zminmax[0]), zminmax[1]);  // clamp to the GLOBAL z range (render_ray.py:236)
+    dep = ndet_min(ndet_max(dep, zminmax[0]), zminmax[1]);  // torch.clamp: a NaN depth stays NaN; clamp to the GLOBAL z range (render_ray.py:236)
     depth_map[r] = dep;
     if (ray_mask) ray_mask[r] = seen > 8 ? 1 : 0;      // render_ray.py:230
 }

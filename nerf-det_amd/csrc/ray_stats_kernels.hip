@@ -114,7 +114,7 @@ __device__ __forceinline__ void rs_take(RsAcc& a, const float4& v, bool valid, f
 __device__ __forceinline__ float rs_var_sum(float q, float s1, float piv, float mean, float n_near, float n_far) {
     const float dm = mean - piv;
     float s = q - 2.0f * dm * s1 + n_near * (dm * dm);
-    s = fmaxf(s, 0.0f);                 // a sum of squares: rounding may leave -1 ulp
+    s = ndet_max(s, 0.0f);              // a sum of squares: rounding may leave -1 ulp (a NaN stays NaN)
     return s + n_far * (mean * mean);   // views with no tap inside a map sample exactly 0
 }
 

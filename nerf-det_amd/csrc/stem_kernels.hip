@@ -129,7 +129,10 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv_pool(const StemParams p) {
         if constexpr (SCH == 1) {                                        // the patch's own maximum -> its power-of-two scale
             float m = 0.0f;
 #pragma unroll
-            for (int i = 0; i < ST_EPT; ++i) m = fmaxf(m, fabsf(ra[i]));
+            for (int i = 0; i < ST_EPT; ++i) {                       // over the FINITE pixels: fmaxf drops a NaN, and an Inf must not take the scale
+                const float a = fabsf(ra[i]);                            // (2^-114 would flush every other pixel of the patch, and this kernel's input has
+                m = fmaxf(m, a < INFINITY ? a : 0.0f);                   // no range guard to say so); the Inf itself stays Inf under any power of two
+            }
 #pragma unroll
             for (int o = 32; o; o >>= 1) {
                 m = fmaxf(m, __shfl_xor(m, o));
@@ -181,14 +184,18 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv_pool(const StemParams p) {
 #pragma unroll
             for (int ks = 0; ks < ST_KS; ++ks) {
                 int g = 2 * ks + fh;                                     // (ky, c) group of this lane's 8 k
-                if (g > 20) g = 20;                                      // padding slice: zero weights, any finite operand
+                // padding slice (k 168 .. 175): zero weights on group 20 read a second time.  A non-finite pixel there does give 0 x NaN = NaN,
+                // but kx 0 .. 6 of (ky 6, c 2) lie inside this output's own 7 x 7 window, whose real weights poison it anyway
+                if (g > 20) g = 20;
                 const int ky = g / 3, c = g - 3 * ky;
                 const int goff = (c * ST_IY + ky) * ST_PITCH;
                 bf16x8 fa[NPL];
 #pragma unroll
                 for (int pl = 0; pl < NPL; ++pl) {
                     const uint32_t* q = reinterpret_cast<const uint32_t*>(P + pl * PPL + goff + ao);   // 4-byte aligned: the offsets are even
-                    const u32x4 v = {q[0], q[1], q[2], q[3]};
+                    // k 7 of the group (kx = 7: the pixel right of the window) meets a zero weight, but 0 x NaN / Inf is a NaN: a +0 in its place
+                    // keeps a non-finite pixel inside its 7 x 7 windows (finite pixels: the product was a zero before, the same bits)
+                    const u32x4 v = {q[0], q[1], q[2], q[3] & 0xffffu};
                     fa[pl] = __builtin_bit_cast(bf16x8, v);
                 }
                 if constexpr (SCH == 1) {                                // smallest terms first: hi lo, lo hi, hi hi
@@ -206,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv_pool(const StemParams p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = wm * 64 + rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                Cs[row * ST_CLD + wn * 32 + frow] = fmaxf((SCH == 1 ? acc[r] * xinv : acc[r]) * sc + sh, 0.0f);
+                Cs[row * ST_CLD + wn * 32 + frow] = ndet_relu((SCH == 1 ? acc[r] * xinv : acc[r]) * sc + sh);
             }
         }
         __syncthreads();                                             // (B)
@@ -227,11 +234,11 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv_pool(const StemParams p) {
                         const int ly = 2 * ppy + dy, lx = 2 * ppx + dx;
                         if ((unsigned)(cy0 + ly) < (unsigned)p.CH && (unsigned)(cx0 + lx) < (unsigned)p.CW) {
                             const float4 v = *reinterpret_cast<const float4*>(Cs + (ly * ST_CX + lx) * ST_CLD + q * 4);
-                            m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+                            m.x = ndet_max(m.x, v.x); m.y = ndet_max(m.y, v.y); m.z = ndet_max(m.z, v.z); m.w = ndet_max(m.w, v.w);
                         }
                     }
                 *reinterpret_cast<float4*>(p.out + (((int64_t)n * p.PH + py) * p.PW + px) * 64 + q * 4) = m;
-                tmax = fmaxf(fmaxf(tmax, fmaxf(m.x, m.y)), fmaxf(m.z, m.w));       // (post-ReLU: non-negative)
+                tmax = fmaxf(fmaxf(tmax, fmaxf(m.x, m.y)), fmaxf(m.z, m.w));       // (post-ReLU: non-negative; fmaxf: a NaN stays out of the slot)
             }
             omax = fmaxf(omax, tmax);
             tprev = tmax;                                                // this tile's maximum crosses the workgroup in the next iteration

@@ -1405,7 +1405,7 @@ extern "C" int ndet_density_features_gated(const float* mapped_nhwc, int n_views
 __global__ __launch_bounds__(256) void k_sigma_to_alpha(const float* __restrict__ raw, float* __restrict__ alpha, int N) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
-    const float s = fmaxf(raw[n], 0.0f);  // F.relu, nerf_mlp.py:227
+    const float s = ndet_relu(raw[n]);    // F.relu, nerf_mlp.py:227
     alpha[n] = 1.0f - expf(-s);            // nerfdet.py:257
 }
 
@@ -1494,7 +1494,7 @@ __global__ __launch_bounds__(256) void k_sigma_head(const float* __restrict__ h,
     if (lane == 0) {
         const float sg = acc + bias[0];
         if (raw_sigma) raw_sigma[n] = sg;
-        alpha[n] = 1.0f - expf(-fmaxf(sg, 0.0f));
+        alpha[n] = 1.0f - expf(-ndet_relu(sg));
     }
 }
 
