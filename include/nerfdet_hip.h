@@ -887,6 +887,38 @@ int ndet_resize_normalize_views(const uint8_t* frames_bgr, const int* ids, int n
                                 const double* mean_rgb, const double* std_rgb, float* img, float* denorm, uint8_t* resized_bgr,
                                 void* stream);
 
+/* ---- NV12 surfaces: what a hardware video decoder leaves in device memory and a hardware encoder takes.  A surface batch is
+ * surfaces (n, rows, pitch) uint8: the Y plane in rows [0,Hs), the interleaved U,V plane (U first) in rows [uv_row, uv_row + Hs/2),
+ * columns [0,Ws) of each row used; tight: pitch = Ws, uv_row = Hs, rows = Hs * 3 / 2.  The colour definition is
+ * nerfdet_amd.datasets.nv12_to_bgr / bgr_to_nv12 (BT.601 limited range in 20-bit fixed point, nearest chroma on ingest, the rounded
+ * 2 x 2 mean on egress), bit for bit.
+ *
+ * ndet_resize_normalize_views_nv12: ndet_resize_normalize_views' contract -- the configs' Resize(keep_ratio) -> Normalize -> Pad
+ * (configs/nerfdet/nerfdet_res101_2x_low_res.py:95-97, applied per view by mmdet3d/datasets/pipelines/multi_view.py:90-110) -- reading
+ * surfaces: img, denorm and resized_bgr are what ndet_resize_normalize_views writes for nv12_to_bgr of each selected surface, bit for
+ * bit; ids, the pad and mean / std as there.  Each of the four taps converts its own source pixel, Y at (y, x) and the UV pair at
+ * (y >> 1, x >> 1), before the 2^11 fixed-point blend.  Frame offsets are 64-bit, offsets inside a surface 32-bit.  Refused before any
+ * device work: a null pointer other than ids / resized_bgr, a non-positive size, std <= 0, Hr > H or Wr > W, odd Hs or Ws, pitch < Ws,
+ * uv_row < Hs, rows < uv_row + Hs/2 (NDET_E_INVALID); rows * pitch >= 2^31, H * W * 3 >= 2^31, 2^31 workgroups or more, an odd pitch
+ * or an odd base address -- the UV pair is one 16-bit load -- (NDET_E_UNSUPPORTED). */
+int ndet_resize_normalize_views_nv12(const uint8_t* surfaces, const int* ids, int n_sel, int Hs, int Ws, int pitch, int uv_row, int rows,
+                                     int Hr, int Wr, int H, int W, const double* mean_rgb, const double* std_rgb, float* img, float* denorm,
+                                     uint8_t* resized_bgr, void* stream);
+
+/* ndet_nv12_to_bgr: frames_bgr (n_sel,Hs,Ws,3) uint8 = nv12_to_bgr of each selected surface ids[v] (ids == NULL: 0 .. n_sel-1) at full
+ * size, for what needs capture-size BGR (drawing onto camera frames; the frames are those the configs' LoadImageFromFile hands to
+ * mmdet3d/datasets/pipelines/multi_view.py:90).  One thread per 2 x 2 block; every output byte is written.  Refusals as above, and
+ * Hs * Ws * 3 >= 2^31 (NDET_E_UNSUPPORTED). */
+int ndet_nv12_to_bgr(const uint8_t* surfaces, const int* ids, int n_sel, int Hs, int Ws, int pitch, int uv_row, int rows,
+                     uint8_t* frames_bgr, void* stream);
+
+/* ndet_bgr_to_nv12: tight surfaces (n, He * 3 / 2, We) = bgr_to_nv12 of frames_bgr (n,H,W,3) of ANY size: He = H + H % 2,
+ * We = W + W % 2, surface pixel (r, c) reads frame[min(r, H-1), min(c, W-1)] -- the inverse direction of the same contract
+ * (multi_view.py:107-110 keeps BGR bytes; an encoder takes NV12).  One thread per 2 x 2 block writes four Y bytes and one UV pair; every
+ * output byte is written.  Refused before any device work: a null pointer, a non-positive size (NDET_E_INVALID); H * W * 3 >= 2^31
+ * (NDET_E_UNSUPPORTED). */
+int ndet_bgr_to_nv12(const uint8_t* frames_bgr, int n, int H, int W, uint8_t* surfaces, void* stream);
+
 /* ---- depth frames: the loader's `depth`, `gt_depths` and `depth_rays` from the sensor's frames, frames_mm (n_frames,Hd,Wd) uint16
  * millimetres resident on the device.
  *

@@ -173,6 +173,9 @@ SIGNATURES = {
     "ndet_normalize_views": ([_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P], c_int),
     "ndet_target_rays": ([_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P], c_int),
     "ndet_resize_normalize_views": ([_P, _P] + [c_int] * 7 + [_P] * 6, c_int),
+    "ndet_resize_normalize_views_nv12": ([_P, _P] + [c_int] * 10 + [_P] * 6, c_int),
+    "ndet_nv12_to_bgr": ([_P, _P] + [c_int] * 6 + [_P, _P], c_int),
+    "ndet_bgr_to_nv12": ([_P] + [c_int] * 3 + [_P, _P], c_int),
     "ndet_depth_frames": ([_P, _P] + [c_int] * 6 + [_P, _P], c_int),
     "ndet_positive_indices": ([_P, c_int64, _P, _P, _P, _P], c_int),
     "ndet_positive_indices_workspace_bytes": ([c_int64], c_int64),

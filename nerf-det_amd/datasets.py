@@ -110,6 +110,49 @@ def imresize_linear(img: np.ndarray, size_wh) -> np.ndarray:
     return out.reshape((nh, nw) + img.shape[2:])
 
 
+def nv12_to_bgr(y: np.ndarray, uv: np.ndarray) -> np.ndarray:
+    """An NV12 surface as a hardware video decoder leaves it -> (Hs, Ws, 3) uint8 BGR: the project's DEFINITION of that conversion, which
+    ndet_resize_normalize_views_nv12 and ndet_nv12_to_bgr reproduce bit for bit.  ``y`` (Hs, Ws) uint8, ``uv`` (Hs / 2, Ws / 2, 2) uint8
+    with U first, Hs and Ws even.  Pixel (r, c) takes ``uv[r >> 1, c >> 1]``: nearest chroma, no chroma interpolation.  BT.601 limited
+    range in 20-bit fixed point with the constants OpenCV uses for ``COLOR_YUV2BGR_NV12``: ``Y' = max(0, Y - 16) * 1220542``,
+    ``u = U - 128``, ``v = V - 128``, ``h = 1 << 19``; ``R = (Y' + h + 1673527 v) >> 20``, ``G = (Y' + h - 852492 v - 409993 u) >> 20``,
+    ``B = (Y' + h + 2116026 u) >> 20`` with an arithmetic (floor) shift, each clipped to [0, 255].  Every intermediate fits int32
+    (``|Y' + h + 2116026 u| < 5.7e8``).  cv2 is absent from the image: restated from the published constants, bit parity with cv2 unpinned."""
+    y, uv = np.asarray(y), np.asarray(uv)
+    if y.dtype != np.uint8 or uv.dtype != np.uint8 or y.ndim != 2 or y.shape[0] % 2 or y.shape[1] % 2 or 0 in y.shape \
+            or uv.shape != (y.shape[0] // 2, y.shape[1] // 2, 2):
+        raise ValueError(f"nv12_to_bgr takes y (Hs, Ws) and uv (Hs/2, Ws/2, 2) uint8 with even Hs, Ws; got {y.shape} {y.dtype}, {uv.shape} {uv.dtype}")
+    yy = np.maximum(y.astype(np.int32) - 16, 0) * np.int32(1220542) + np.int32(1 << 19)
+    c = uv.astype(np.int32).repeat(2, axis=0).repeat(2, axis=1) - 128
+    u, v = c[..., 0], c[..., 1]
+    r = (yy + 1673527 * v) >> 20
+    g = (yy - 852492 * v - 409993 * u) >> 20
+    b = (yy + 2116026 * u) >> 20
+    return np.clip(np.stack((b, g, r), axis=-1), 0, 255).astype(np.uint8)
+
+
+def bgr_to_nv12(frame: np.ndarray):
+    """(H, W, 3) uint8 BGR of ANY size -> ``(y (He, We), uv (He / 2, We / 2, 2))`` uint8, the NV12 surface a hardware encoder takes: the
+    project's DEFINITION, which ndet_bgr_to_nv12 reproduces bit for bit.  ``He = H + H % 2``, ``We = W + W % 2``; surface pixel (r, c)
+    reads ``frame[min(r, H - 1), min(c, W - 1)]`` -- the last row / column replicated, for both planes.  BT.601 limited range in 20-bit
+    fixed point (OpenCV's constants): ``Y = (269484 R + 528482 G + 102760 B + (16 << 20) + (1 << 19)) >> 20``; chroma from the rounded
+    mean ``(a + b + c + d + 2) >> 2`` of each 2 x 2 block per channel: ``U = (-155188 R - 305135 G + 460324 B + (128 << 20) + (1 << 19))
+    >> 20``, ``V = (460324 R - 385875 G - 74448 B + (128 << 20) + (1 << 19)) >> 20``, both clipped to [0, 255].  The 2 x 2 mean is this
+    project's own choice, NOT cv2's; bit parity with cv2 is not claimed."""
+    frame = np.asarray(frame)
+    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3 or 0 in frame.shape:
+        raise ValueError(f"bgr_to_nv12 takes an (H, W, 3) uint8 BGR frame, got {frame.shape} {frame.dtype}")
+    h, w = frame.shape[:2]
+    f = np.pad(frame, ((0, h % 2), (0, w % 2), (0, 0)), mode="edge").astype(np.int32)
+    b, g, r = f[..., 0], f[..., 1], f[..., 2]
+    y = (269484 * r + 528482 * g + 102760 * b + (16 << 20) + (1 << 19)) >> 20
+    m = (f[0::2, 0::2] + f[0::2, 1::2] + f[1::2, 0::2] + f[1::2, 1::2] + 2) >> 2
+    b, g, r = m[..., 0], m[..., 1], m[..., 2]
+    u = (-155188 * r - 305135 * g + 460324 * b + (128 << 20) + (1 << 19)) >> 20
+    v = (460324 * r - 385875 * g - 74448 * b + (128 << 20) + (1 << 19)) >> 20
+    return y.astype(np.uint8), np.clip(np.stack((u, v), axis=-1), 0, 255).astype(np.uint8)
+
+
 @PIPELINES.register_module()
 class Resize:
     """``Resize(img_scale=(w, h), keep_ratio=True)``: the largest rescale that fits the long edge into max(img_scale) and the short

@@ -10,6 +10,12 @@ config:134), or at CAPTURE resolution: :func:`prepare_frames` / ``MultiViewPipel
 ``Resize(keep_ratio) -> Normalize -> Pad`` in one launch (ndet_resize_normalize_views), the resize being
 ``datasets.imresize_linear`` bit for bit, and report ``img_shape`` / ``pad_shape`` as that chain leaves them.
 
+What a hardware video decoder hands over is not BGR but NV12 surfaces (a Y plane and a half-size plane of interleaved U,V bytes, with a
+row pitch and a chroma-plane row of its own choosing): ``prepare_frames(format="nv12")`` / ``MultiViewPipeline(frame_format="nv12")``
+take those at capture resolution and convert inside the resize taps (ndet_resize_normalize_views_nv12) -- the BGR call's outputs on
+``datasets.nv12_to_bgr`` of each surface bit for bit; :func:`nv12_to_bgr` and :func:`bgr_to_nv12` are the two conversions alone
+(ndet_nv12_to_bgr, ndet_bgr_to_nv12), the second for an encoder.
+
 The sensor's depth frames (uint16 millimetres on the device) go the same way: :func:`prepare_depth_frames` is the loader's
 ``imresize_linear(frame / 1000, ...)`` in float64 (ndet_depth_frames), :func:`positive_indices` its ``flatnonzero(gt_depths > 0)``
 (ndet_positive_indices), and ``MultiViewPipeline(...)(..., depth_frames=)`` adds ``depth``, ``gt_depths`` and ``depth_rays`` to the batch.
@@ -93,36 +99,133 @@ def _frame_sizes(size_hw, img_scale, pad_size):
     return (hr, wr), (h, w)
 
 
+FRAME_FORMATS = ("bgr", "nv12")
+
+
+def _check_format(format, what: str) -> str:
+    if format not in FRAME_FORMATS:
+        raise ValueError(f"{what}: format={format!r} must be one of {FRAME_FORMATS}")
+    return format
+
+
+def surface_layout(rows: int, pitch: int, size, uv_row, what: str):
+    """The checked description ``(Hs, Ws, uv_row)`` of NV12 surfaces of ``rows`` rows of ``pitch`` bytes: the Y plane ``size = (Hs, Ws)``,
+    both even, in rows [0, Hs), the interleaved U,V plane in rows [uv_row, uv_row + Hs / 2) (``uv_row=None``: Hs, the tight layout).
+    ValueError for a layout the surfaces cannot hold and for an odd pitch (ndet_resize_normalize_views_nv12 loads a UV pair at once);
+    only integers are read."""
+    if size is None or len(size) < 2:
+        raise ValueError(f"{what}: NV12 surfaces need size=(Hs, Ws), the size of their Y plane")
+    hs, ws = int(size[0]), int(size[1])
+    if hs < 2 or ws < 2 or hs % 2 or ws % 2:
+        raise ValueError(f"{what}: an NV12 surface has even sizes, got {(hs, ws)}")
+    uv = hs if uv_row is None else int(uv_row)
+    if pitch < ws:
+        raise ValueError(f"{what}: surfaces of pitch {pitch} do not hold rows of {ws} pixels")
+    if uv < hs:
+        raise ValueError(f"{what}: uv_row={uv} lies inside the Y plane of {hs} rows")
+    if rows < uv + hs // 2:
+        raise ValueError(f"{what}: surfaces of {rows} rows do not hold a {hs}-row Y plane and its {hs // 2} UV rows at row {uv}")
+    if pitch % 2:
+        raise ValueError(f"{what}: an odd pitch ({pitch}) is not supported")
+    if rows * pitch >= 1 << 31:
+        raise ValueError(f"{what}: a surface of {rows} rows x {pitch} bytes holds 2^31 bytes or more")
+    return hs, ws, uv
+
+
+def _check_surfaces(frames, size, uv_row, what: str):
+    """ValueError for anything but contiguous (n, rows, pitch) uint8 surfaces that hold the described planes: ``(n, rows, pitch, Hs, Ws, uv_row)``."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 3 or 0 in frames.shape or not frames.is_contiguous():
+        got = f"{tuple(frames.shape)} {frames.dtype}" if isinstance(frames, torch.Tensor) else type(frames).__name__
+        raise ValueError(f"{what} takes contiguous (n, rows, pitch) uint8 NV12 surfaces, got {got}")
+    n, rows, pitch = (int(v) for v in frames.shape)
+    return (n, rows, pitch) + surface_layout(rows, pitch, size, uv_row, what)
+
+
+def _device_ids(ids, n: int, dev, what: str):
+    """``(ids on the device or None, n_sel)`` of a call that selects frames."""
+    if ids is None:
+        return None, n
+    ids = [int(i) for i in ids]
+    if not ids or min(ids) < 0 or max(ids) >= n:
+        raise ValueError(f"{what}: ids must be a non-empty list of frame indices below {n}")
+    return torch.tensor(ids, dtype=torch.int32, device=dev), len(ids)
+
+
 def prepare_frames(frames: torch.Tensor, img_scale, pad_size, mean: Sequence[float] = IMG_MEAN, std: Sequence[float] = IMG_STD, ids=None,
-                   want_u8: bool = False):
+                   want_u8: bool = False, format: str = "bgr", size=None, uv_row=None):
     """The configs' ``Resize(img_scale, keep_ratio=True) -> Normalize(mean, std, to_rgb=True) -> Pad(size=pad_size)`` and the reference's
     de-normalised copy for frames at capture resolution, in one launch: ``frames`` (n, Hs, Ws, 3) uint8 BGR on the device ->
     ``(img, denorm)``, both (n_sel, 3, H, W) float32 (``ids``: a sequence of frame indices, None for every frame in order), and with
     ``want_u8`` also the resized, zero-padded bytes (n_sel, H, W, 3).  The content region holds ``datasets.imresize_linear``'s bytes
     normalised as ``ndet_normalize_views`` does; the pad is 0 in ``img`` and ``trunc(mean) / 255`` in ``denorm``.  ValueError when the
-    rescaled frame does not fit ``pad_size`` (a portrait frame into a landscape pad)."""
-    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
-        raise ValueError(f"prepare_frames takes contiguous (n, Hs, Ws, 3) uint8 frames, got {tuple(frames.shape)} {frames.dtype}")
-    n, hs, ws, _ = frames.shape
+    rescaled frame does not fit ``pad_size`` (a portrait frame into a landscape pad).
+
+    ``format="nv12"``: ``frames`` are a video decoder's surfaces, (n, rows, pitch) uint8 with the Y plane ``size = (Hs, Ws)`` in rows
+    [0, Hs) and the interleaved U,V plane from row ``uv_row`` (None: Hs, the tight layout; :func:`surface_layout`).  One
+    ndet_resize_normalize_views_nv12 launch converts inside the resize taps: the outputs are the BGR call's on
+    ``datasets.nv12_to_bgr`` of each surface, bit for bit, and no BGR frame at capture size is ever written."""
+    what = "prepare_frames"
+    if _check_format(format, what) == "nv12":
+        n, rows, pitch, hs, ws, uv = _check_surfaces(frames, size, uv_row, what)
+    else:
+        if size is not None or uv_row is not None:
+            raise ValueError("prepare_frames: size= and uv_row= describe NV12 surfaces (format='nv12')")
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
+            raise ValueError(f"prepare_frames takes contiguous (n, Hs, Ws, 3) uint8 frames, got {tuple(frames.shape)} {frames.dtype}")
+        n, hs, ws, _ = frames.shape
     (hr, wr), (h, w) = _frame_sizes((hs, ws), img_scale, pad_size)
     if not frames.is_cuda:
         raise RuntimeError("nerfdet_amd.pipeline: frames must live on the GPU (no CPU fallback)")
     dev = frames.device
-    ids_d = None
-    if ids is not None:
-        ids = [int(i) for i in ids]
-        if not ids or min(ids) < 0 or max(ids) >= n:
-            raise ValueError(f"prepare_frames: ids must be a non-empty list of frame indices below {n}")
-        ids_d = torch.tensor(ids, dtype=torch.int32, device=dev)
-    n_sel = n if ids is None else len(ids)
+    ids_d, n_sel = _device_ids(ids, n, dev, what)
     mean, std = np.asarray(mean, dtype=np.float64), np.asarray(std, dtype=np.float64)
     img = torch.empty((n_sel, 3, h, w), dtype=torch.float32, device=dev)
     denorm = torch.empty_like(img)
     u8 = torch.empty((n_sel, h, w, 3), dtype=torch.uint8, device=dev) if want_u8 else None
-    check(_lib.load().ndet_resize_normalize_views(_ptr(frames), _ptr(ids_d), n_sel, hs, ws, hr, wr, h, w, mean.ctypes.data_as(c_void_p),
-                                                  std.ctypes.data_as(c_void_p), _ptr(img), _ptr(denorm), _ptr(u8),
-                                                  c_void_p(_lib.raw_stream(dev))), "resize_normalize_views")
+    tail = (hr, wr, h, w, mean.ctypes.data_as(c_void_p), std.ctypes.data_as(c_void_p), _ptr(img), _ptr(denorm), _ptr(u8), c_void_p(_lib.raw_stream(dev)))
+    if format == "nv12":
+        check(_lib.load().ndet_resize_normalize_views_nv12(_ptr(frames), _ptr(ids_d), n_sel, hs, ws, pitch, uv, rows, *tail), "resize_normalize_views_nv12")
+    else:
+        check(_lib.load().ndet_resize_normalize_views(_ptr(frames), _ptr(ids_d), n_sel, hs, ws, *tail), "resize_normalize_views")
     return (img, denorm, u8) if want_u8 else (img, denorm)
+
+
+def nv12_to_bgr(frames: torch.Tensor, size, uv_row=None, ids=None) -> torch.Tensor:
+    """NV12 surfaces as BGR frames at full size, in one launch (ndet_nv12_to_bgr): ``frames`` (n, rows, pitch) uint8 on the device,
+    described by ``size = (Hs, Ws)`` and ``uv_row`` as :func:`prepare_frames` takes them -> (n_sel, Hs, Ws, 3) uint8,
+    ``datasets.nv12_to_bgr`` of each selected surface bit for bit.  For what needs capture-size BGR, ``draw_detections(capture=True)``
+    for one; the ingest road does not (``prepare_frames(format="nv12")`` converts inside the resize)."""
+    what = "nv12_to_bgr"
+    n, rows, pitch, hs, ws, uv = _check_surfaces(frames, size, uv_row, what)
+    if hs * ws * 3 >= 1 << 31:
+        raise ValueError(f"{what}: a frame of {hs} x {ws} x 3 holds 2^31 elements or more")
+    if not frames.is_cuda:
+        raise RuntimeError("nerfdet_amd.pipeline: frames must live on the GPU (no CPU fallback)")
+    dev = frames.device
+    ids_d, n_sel = _device_ids(ids, n, dev, what)
+    out = torch.empty((n_sel, hs, ws, 3), dtype=torch.uint8, device=dev)
+    check(_lib.load().ndet_nv12_to_bgr(_ptr(frames), _ptr(ids_d), n_sel, hs, ws, pitch, uv, rows, _ptr(out), c_void_p(_lib.raw_stream(dev))), what)
+    return out
+
+
+def bgr_to_nv12(frames: torch.Tensor):
+    """BGR frames as the NV12 surfaces a hardware encoder takes, in one launch (ndet_bgr_to_nv12): ``frames`` (n, H, W, 3) uint8 on the
+    device, of ANY size -- ``render_frames``' and ``draw_detections``' outputs fit -- -> ``(surfaces (n, He * 3 / 2, We) uint8, (He, We))``
+    in the tight layout, ``He = H + H % 2``, ``We = W + W % 2`` (the last row / column replicated): ``datasets.bgr_to_nv12`` of each
+    frame bit for bit, Y in rows [0, He), interleaved U,V from row He."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3 or 0 in frames.shape \
+            or not frames.is_contiguous():
+        got = f"{tuple(frames.shape)} {frames.dtype}" if isinstance(frames, torch.Tensor) else type(frames).__name__
+        raise ValueError(f"bgr_to_nv12 takes contiguous (n, H, W, 3) uint8 frames, got {got}")
+    n, h, w = (int(v) for v in frames.shape[:3])
+    if h * w * 3 >= 1 << 31:
+        raise ValueError(f"bgr_to_nv12: a frame of {h} x {w} x 3 holds 2^31 elements or more")
+    if not frames.is_cuda:
+        raise RuntimeError("nerfdet_amd.pipeline: frames must live on the GPU (no CPU fallback)")
+    he, we = h + h % 2, w + w % 2
+    out = torch.empty((n, he // 2 * 3, we), dtype=torch.uint8, device=frames.device)
+    check(_lib.load().ndet_bgr_to_nv12(_ptr(frames), n, h, w, _ptr(out), c_void_p(_lib.raw_stream(frames.device))), "bgr_to_nv12")
+    return out, (he, we)
 
 
 def _check_depth_frames(depth_frames, what: str, n_frames=None):
@@ -517,6 +620,11 @@ class MultiViewPipeline:
     ``Hs / Hr``, the ray grid over the padded H x W (multi_view.py takes ``imgs[0].shape``) and ``gt_images`` the margin crop of the
     target views' de-normalised planes, so a pad pixel is ``trunc(mean) / 255``.  Both None: frames at network resolution, as above.
 
+    ``frame_format="nv12"`` (raw mode only): ``frames`` are a video decoder's NV12 surfaces (n, rows, pitch) uint8, ``ori_shape=(Hs, Ws[, 3])``
+    says the size of their Y plane and ``uv_row=`` where the U,V plane starts (None: Hs; :func:`surface_layout`).  The one launch is
+    ndet_resize_normalize_views_nv12 and the batch is the BGR raw mode's on ``datasets.nv12_to_bgr`` of the surfaces bit for bit; everything
+    after the resize is the same code.
+
     ``depth_frames=`` (n_frames, Hd, Wd) uint16 millimetres on the device, one per colour frame, of any size of their own: the batch gains
     what the ``*_depth_sp`` configs' loader adds (multi_view.py:98-105, 156-166; formating.py) -- ``depth`` (1, n_v, Hr, Wr) float64 metres,
     the selected views' maps at the meta's ``img_shape``, for ``simple_test(depth=)``; and with target views ``gt_depths``
@@ -527,8 +635,11 @@ class MultiViewPipeline:
 
     def __init__(self, n_images: int, mean: Sequence[float] = IMG_MEAN, std: Sequence[float] = IMG_STD, margin: int = 10,
                  depth_range=(0.5, 5.5), loading: str = "random", nerf_target_views: int = 0, sample_freq: int = 3, img_scale=None,
-                 pad_size=None):
+                 pad_size=None, frame_format: str = "bgr"):
         self.n_images, self.margin, self.depth_range = n_images, margin, list(depth_range)
+        self.frame_format = _check_format(frame_format, "MultiViewPipeline")
+        if frame_format == "nv12" and img_scale is None:
+            raise ValueError("MultiViewPipeline: frame_format='nv12' takes surfaces at capture resolution: give img_scale and pad_size")
         self.loading, self.nerf_target_views, self.sample_freq = loading, nerf_target_views, sample_freq
         self.mean = np.asarray(mean, dtype=np.float64)
         self.std = np.asarray(std, dtype=np.float64)
@@ -545,16 +656,20 @@ class MultiViewPipeline:
             out.update(gt_depths=gt.unsqueeze(0), depth_rays=positive_indices(gt).reshape(1, -1))
         return out
 
-    def _raw(self, frames: torch.Tensor, cams: dict, ori_shape, ids, target_ids, depth_frames=None) -> dict:
+    def _raw(self, frames: torch.Tensor, cams: dict, ori_shape, ids, target_ids, depth_frames=None, uv_row=None) -> dict:
         """``__call__`` for frames at capture resolution."""
-        n_frames, hs, ws, _ = frames.shape
-        if ori_shape is not None and tuple(ori_shape)[:2] != (hs, ws):
-            raise ValueError(f"MultiViewPipeline: ori_shape {tuple(ori_shape)} differs from the raw frames' {(hs, ws, 3)}")
+        if self.frame_format == "nv12":
+            (hs, ws), surf = (int(ori_shape[0]), int(ori_shape[1])), dict(format="nv12", size=ori_shape[:2], uv_row=uv_row)
+        else:
+            n_frames, hs, ws, _ = frames.shape
+            surf = {}
+            if ori_shape is not None and tuple(ori_shape)[:2] != (hs, ws):
+                raise ValueError(f"MultiViewPipeline: ori_shape {tuple(ori_shape)} differs from the raw frames' {(hs, ws, 3)}")
         (hr, wr), (h, w) = _frame_sizes((hs, ws), self.img_scale, self.pad_size)
         dev = frames.device
         n, m = len(ids), self.margin
         # one launch over the selected and the target views; only the targets' rays need the resized bytes
-        out = prepare_frames(frames, self.img_scale, self.pad_size, self.mean, self.std, ids=list(ids) + target_ids, want_u8=bool(target_ids))
+        out = prepare_frames(frames, self.img_scale, self.pad_size, self.mean, self.std, ids=list(ids) + target_ids, want_u8=bool(target_ids), **surf)
         img, denorm = out[0], out[1]
         meta = frame_meta(dict(cams, extrinsic=[cams["extrinsic"][i] for i in ids]), (hs, ws), self.img_scale, self.pad_size)
         batch = dict(img=img[:n].unsqueeze(0), img_metas=[meta])
@@ -584,18 +699,27 @@ class MultiViewPipeline:
             batch.update(self._depth(depth_frames, ids, target_ids, (hr, wr), (h, w)))
         return batch
 
-    def __call__(self, frames: torch.Tensor, cams: dict, ori_shape=None, ids=None, target_ids=None, depth_frames=None) -> dict:
+    def __call__(self, frames: torch.Tensor, cams: dict, ori_shape=None, ids=None, target_ids=None, depth_frames=None, uv_row=None) -> dict:
+        if self.frame_format == "nv12":
+            if ori_shape is None:
+                raise ValueError("MultiViewPipeline: NV12 surfaces need ori_shape=(Hs, Ws[, 3]), the size of their Y plane")
+            n_frames = _check_surfaces(frames, ori_shape, uv_row, "MultiViewPipeline")[0]
+        elif uv_row is not None:
+            raise ValueError("MultiViewPipeline: uv_row= describes NV12 surfaces (frame_format='nv12')")
         if not frames.is_cuda:
             raise RuntimeError("nerfdet_amd.pipeline: frames must live on the GPU (no CPU fallback)")
-        assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[-1] == 3 and frames.is_contiguous()
-        n_frames, h, w, _ = frames.shape
+        if self.frame_format == "nv12":
+            h = w = None
+        else:
+            assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[-1] == 3 and frames.is_contiguous()
+            n_frames, h, w, _ = frames.shape
         if depth_frames is not None:
             _check_depth_frames(depth_frames, "MultiViewPipeline", n_frames)
         if ids is None:
             ids, target_ids = select_views(n_frames, self.n_images, self.nerf_target_views, self.loading, self.sample_freq)
         target_ids = list(target_ids or [])
         if self.img_scale is not None:
-            return self._raw(frames, cams, ori_shape, ids, target_ids, depth_frames)
+            return self._raw(frames, cams, ori_shape, ids, target_ids, depth_frames, uv_row)
         dev = frames.device
         lib = _lib.load()
         st = c_void_p(torch.cuda.current_stream(dev).cuda_stream)

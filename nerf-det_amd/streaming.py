@@ -44,6 +44,9 @@ the listed scenes' windows with one grouped density ring finish, one sigma-MLP c
 (1 or len(scenes), k, Hs, Ws, 3) on the device, instead of prepared tensors: the frames are checked against the scene's meta (``ori_shape``,
 ``img_shape``, ``pad_shape``: pipeline.frame_meta), resized, normalised and padded in ONE launch for the whole call (pipeline.prepare_frames,
 ndet_resize_normalize_views; ``mean`` / ``std`` are ``begin_scene(s)`` keywords) and handed to ``add_views``, which does the rest.
+``format="nv12"`` (an explicit keyword, never inferred from the rank) on ``add_frames`` and ``score_frames`` takes a hardware video
+decoder's NV12 surfaces (1 or len(scenes), k, rows, pitch) instead, with ``uv_row=`` the row where the U,V plane starts: the same one
+launch converts inside the resize taps (ndet_resize_normalize_views_nv12), bit-equal to ``datasets.nv12_to_bgr`` followed by the BGR road.
 
 ``scene.render_frames(c2w= | extrinsic=)`` / ``group.render_frames(...)`` are the output side in the same formats: the rays of k camera poses
 come from one launch (pipeline.camera_rays, ndet_camera_rays -- a pose needs no frame), go through ``render_rays``' passes, and one launch
@@ -83,8 +86,9 @@ import numpy as np
 import torch
 
 from . import conv3d, ops
-from .pipeline import (IMG_MEAN, IMG_STD, _host_matrices, camera_rays, check_window, class_palette, depth_to_mm, draw_boxes, frame_errors,
-                       SSIM_WINDOW, frame_ssim, label_frames, pack_frames, prepare_depth_frames, prepare_frames, project_boxes, rescale_size)
+from .pipeline import (FRAME_FORMATS, IMG_MEAN, IMG_STD, _host_matrices, camera_rays, check_window, class_palette, depth_to_mm, draw_boxes, frame_errors,
+                       SSIM_WINDOW, frame_ssim, label_frames, pack_frames, prepare_depth_frames, prepare_frames, project_boxes, rescale_size,
+                       surface_layout)
 from .volume import map_features_2d, map_features_2d_hip
 
 Tensor = torch.Tensor
@@ -111,22 +115,41 @@ def check_chunk_meta(scene_meta: dict, img_meta: dict, k: int) -> None:
         raise ValueError(f"add_views: {len(b['lidar2img']['extrinsic'])} extrinsics for {k} views")
 
 
-def check_frames_meta(scene_meta: dict, frames: Tensor, n: int):
+def check_frames_meta(scene_meta: dict, frames: Tensor, n: int, format: str = "bgr", uv_row=None):
     """``add_frames``'s own checks, before any device work: ``frames`` is (n, k, Hs, Ws, 3) uint8 with ``(Hs, Ws)`` the scene's
     ``ori_shape``, and the scene's ``img_shape`` is what ``Resize(keep_ratio=True)`` into the ``pad_shape`` box makes of such a frame
-    (pipeline.rescale_size; a meta without ``pad_shape`` is unpadded: ``pad_shape = img_shape``).  Returns ``(img_scale, pad_size)`` as
-    pipeline.prepare_frames takes them, else ValueError."""
-    if frames.dim() != 5 or frames.shape[0] != n or frames.shape[1] < 1 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
-        raise ValueError(f"add_frames takes raw uint8 BGR frames ({n}, k, Hs, Ws, 3); got {tuple(frames.shape)} {frames.dtype}")
-    hs, ws = int(frames.shape[2]), int(frames.shape[3])
-    if (hs, ws) != tuple(scene_meta["ori_shape"][:2]):
-        raise ValueError(f"add_frames: frames of {(hs, ws)} differ from the scene's ori_shape {tuple(scene_meta['ori_shape'])}")
+    (pipeline.rescale_size; a meta without ``pad_shape`` is unpadded: ``pad_shape = img_shape``).  ``format="nv12"``: ``frames`` is
+    (n, k, rows, pitch) uint8, a video decoder's surfaces whose Y plane is the scene's ``ori_shape`` -- which must be even -- and whose
+    U,V plane starts at row ``uv_row`` (None: Hs); rows and pitch must hold both planes (pipeline.surface_layout).  Returns
+    ``(img_scale, pad_size)`` as pipeline.prepare_frames takes them, else ValueError."""
+    if format not in FRAME_FORMATS:
+        raise ValueError(f"add_frames: format={format!r} must be one of {FRAME_FORMATS}")
+    if format == "nv12":
+        if frames.dim() != 4 or frames.shape[0] != n or 0 in frames.shape or frames.dtype != torch.uint8:
+            raise ValueError(f"add_frames takes NV12 surfaces as uint8 ({n}, k, rows, pitch); got {tuple(frames.shape)} {frames.dtype}")
+        hs, ws = (int(v) for v in scene_meta["ori_shape"][:2])
+        if hs % 2 or ws % 2:
+            raise ValueError(f"add_frames: NV12 surfaces have even sizes, the scene's ori_shape is {tuple(scene_meta['ori_shape'])}")
+        surface_layout(int(frames.shape[2]), int(frames.shape[3]), (hs, ws), uv_row, "add_frames")
+    else:
+        if uv_row is not None:
+            raise ValueError("add_frames: uv_row= describes NV12 surfaces (format='nv12')")
+        if frames.dim() != 5 or frames.shape[0] != n or frames.shape[1] < 1 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
+            raise ValueError(f"add_frames takes raw uint8 BGR frames ({n}, k, Hs, Ws, 3); got {tuple(frames.shape)} {frames.dtype}")
+        hs, ws = int(frames.shape[2]), int(frames.shape[3])
+        if (hs, ws) != tuple(scene_meta["ori_shape"][:2]):
+            raise ValueError(f"add_frames: frames of {(hs, ws)} differ from the scene's ori_shape {tuple(scene_meta['ori_shape'])}")
     img_shape = tuple(scene_meta["img_shape"][:2])
     h, w = tuple(scene_meta.get("pad_shape", scene_meta["img_shape"])[:2])
     if rescale_size((hs, ws), (w, h)) != img_shape:
         raise ValueError(f"add_frames: a {(hs, ws)} frame rescales to {rescale_size((hs, ws), (w, h))} inside pad_shape {(h, w)}, "
                          f"not to the scene's img_shape {img_shape}")
     return (w, h), (h, w)
+
+
+def _surface_kwargs(scene_meta: dict, format: str, uv_row) -> dict:
+    """What pipeline.prepare_frames needs beyond the frames of a checked call: nothing for BGR frames, the surfaces' description for NV12."""
+    return {} if format == "bgr" else dict(format=format, size=tuple(scene_meta["ori_shape"][:2]), uv_row=uv_row)
 
 
 def check_depth_frames(depth_frames, depth, n: int, k: int) -> None:
@@ -211,13 +234,14 @@ def _frames_dict(coarse, fine, shape):
     return out
 
 
-def _held_out(frames: Tensor, depth_frames, meta: dict, img_scale, pad_size, mean, std, grid):
-    """The held-out side of ``score_frames``: ``frames`` (n, Hs, Ws, 3) through pipeline.prepare_frames' resized bytes, cropped to the content
+def _held_out(frames: Tensor, depth_frames, meta: dict, img_scale, pad_size, mean, std, grid, surf: dict = {}):
+    """The held-out side of ``score_frames``: ``frames`` (n, Hs, Ws, 3) -- or NV12 surfaces (n, rows, pitch) described by ``surf``
+    (:func:`_surface_kwargs`) -- through pipeline.prepare_frames' resized bytes, cropped to the content
     region and strided like the render -- (n, h, w, 3) uint8 -- and ``depth_frames`` (n, Hd, Wd) or None through
     pipeline.prepare_depth_frames at the content size, strided the same way and quantised by pipeline.depth_to_mm -- (n, h, w) uint16."""
     (y0, x0, h, w), s = grid
     hr, wr = int(meta["img_shape"][0]), int(meta["img_shape"][1])
-    u8 = prepare_frames(frames, img_scale, pad_size, mean, std, want_u8=True)[2]
+    u8 = prepare_frames(frames, img_scale, pad_size, mean, std, want_u8=True, **surf)[2]
     held = u8[:, y0:hr:s, x0:wr:s].contiguous()
     assert tuple(held.shape[1:3]) == (h, w)
     if depth_frames is None:
@@ -359,25 +383,27 @@ def _chunk_features(det, lin, img: Tensor, img_shape):
     return feat, mapped, stride
 
 
-def _prepared_frames(frames: Tensor, depth_frames, depth, img_shape, img_scale, pad_size, mean, std):
-    """``add_frames``' device work for the (n, k) frames of a call: ONE ndet_resize_normalize_views launch over all of them and, with
+def _prepared_frames(frames: Tensor, depth_frames, depth, img_shape, img_scale, pad_size, mean, std, surf: dict = {}):
+    """``add_frames``' device work for the (n, k) frames of a call: ONE ndet_resize_normalize_views launch over all of them (NV12
+    surfaces described by ``surf``, :func:`_surface_kwargs`: ONE ndet_resize_normalize_views_nv12 launch) and, with
     ``depth_frames`` (n, k, Hd, Wd), ONE ndet_depth_frames launch.  Returns ``(img, denorm_images, depth)`` shaped (n, k, ...) as
     ``add_views`` takes them; without ``depth_frames`` the call's ``depth`` passes through."""
     rows = lambda t: t.reshape((-1,) + tuple(t.shape[2:]))
     chunks = lambda t: t.view(tuple(frames.shape[:2]) + tuple(t.shape[1:]))
-    img, denorm = prepare_frames(rows(frames), img_scale, pad_size, mean, std)
+    img, denorm = prepare_frames(rows(frames), img_scale, pad_size, mean, std, **surf)
     if depth_frames is not None:
         depth = chunks(prepare_depth_frames(rows(depth_frames), img_shape[:2]))
     return chunks(img), chunks(denorm), depth
 
 
-def _score_held_out(first: dict, scene_metas, frames: Tensor, chunk_metas, depth_frames, stride, n_importance, mean, std, ssim=False):
+def _score_held_out(first: dict, scene_metas, frames: Tensor, chunk_metas, depth_frames, stride, n_importance, mean, std, ssim=False,
+                    format: str = "bgr", uv_row=None):
     """Everything ``score_frames`` checks of its own arguments, before any launch, and then its held-out side (:func:`_held_out`) for the
     n listed scenes' rows of k frames at once: ``(held (n k, h, w, 3), held depth (n k, h, w) or None, k, n_importance)``.  ``first``: the
     meta that says what becomes of a frame (a group's scenes share it).  ``ssim``: the call also wants pipeline.frame_ssim, which needs a
     strided content region of at least 7 x 7 pixels."""
     n = len(scene_metas)
-    img_scale, pad_size = check_frames_meta(first, frames, n)
+    img_scale, pad_size = check_frames_meta(first, frames, n, format, uv_row)
     if len(chunk_metas) != n:
         raise ValueError(f"score_frames: {len(chunk_metas)} chunk metas for {n} listed scenes")
     k = frames.shape[1]
@@ -392,7 +418,8 @@ def _score_held_out(first: dict, scene_metas, frames: Tensor, chunk_metas, depth
         raise ValueError(f"score_frames: ssim=True needs frames of at least {SSIM_WINDOW} x {SSIM_WINDOW} pixels, stride {grid[1]} leaves "
                          f"{grid[0][2]} x {grid[0][3]}")
     rows = lambda t: t.reshape((n * k,) + tuple(t.shape[2:]))
-    held, held_depth = _held_out(rows(frames), None if depth_frames is None else rows(depth_frames), first, img_scale, pad_size, mean, std, grid)
+    held, held_depth = _held_out(rows(frames), None if depth_frames is None else rows(depth_frames), first, img_scale, pad_size, mean, std, grid,
+                                 _surface_kwargs(first, format, uv_row))
     return held, held_depth, k, n_importance
 
 
@@ -861,9 +888,13 @@ class SceneStream:
         if self.det.training:
             raise RuntimeError("SceneStream is inference only: call det.eval() first")
 
-    def add_frames(self, frames: Tensor, img_meta: dict, depth: Optional[Tensor] = None, depth_frames: Optional[Tensor] = None) -> None:
-        """:meth:`add_views` for k >= 1 frames at CAPTURE resolution: ``frames`` (1, k, Hs, Ws, 3) uint8 BGR on the device, as a decode
-        engine leaves them.  The scene's meta says what becomes of them (pipeline.frame_meta makes such a meta): ``(Hs, Ws)`` must be its
+    def add_frames(self, frames: Tensor, img_meta: dict, depth: Optional[Tensor] = None, depth_frames: Optional[Tensor] = None,
+                   format: str = "bgr", uv_row=None) -> None:
+        """:meth:`add_views` for k >= 1 frames at CAPTURE resolution: ``frames`` (1, k, Hs, Ws, 3) uint8 BGR on the device -- or, with
+        ``format="nv12"``, the NV12 surfaces (1, k, rows, pitch) uint8 a hardware video decoder leaves there: their Y plane is the
+        scene's ``ori_shape``, which must be even, their U,V plane starts at row ``uv_row`` (None: Hs, the tight layout), and ONE
+        ndet_resize_normalize_views_nv12 launch converts inside the resize taps, which leaves the scene what ``datasets.nv12_to_bgr`` of
+        the surfaces would, bit for bit.  The format is never inferred from the rank.  The scene's meta says what becomes of them (pipeline.frame_meta makes such a meta): ``(Hs, Ws)`` must be its
         ``ori_shape``, its ``img_shape`` what ``Resize(keep_ratio=True)`` into the ``pad_shape`` box gives (pipeline.rescale_size;
         ``pad_shape`` absent: ``img_shape``), else ValueError -- raised, like everything :meth:`add_views` refuses, before any device
         work.  One ndet_resize_normalize_views launch then makes the chunk's ``img`` and ``denorm_images`` (1, k, 3, H, W) at the padded
@@ -873,13 +904,14 @@ class SceneStream:
         millimetres on the device, of any size of their own; one ndet_depth_frames launch makes the float64 metres at the scene's
         ``img_shape`` (pipeline.prepare_depth_frames: ``datasets.imresize_linear(frame / 1000, ...)`` bit for bit), which go to
         :meth:`add_views` as its ``depth``.  Both given, a wrong dtype or another k: ValueError, before any device work."""
-        img_scale, pad_size = check_frames_meta(self.meta, frames, 1)
+        img_scale, pad_size = check_frames_meta(self.meta, frames, 1, format, uv_row)
         _check_pad_shape(self.meta, img_meta)
         k = frames.shape[1]
         check_depth_frames(depth_frames, depth, 1, k)
         shape = torch.empty((1, k, 3) + pad_size, device="meta")
         self._check_chunk(shape, shape, img_meta, depth)
-        img, denorm, depth = _prepared_frames(frames, depth_frames, depth, self.meta["img_shape"], img_scale, pad_size, self.mean, self.std)
+        img, denorm, depth = _prepared_frames(frames, depth_frames, depth, self.meta["img_shape"], img_scale, pad_size, self.mean, self.std,
+                                              _surface_kwargs(self.meta, format, uv_row))
         self.add_views(img, denorm, img_meta, depth=depth)
 
     def add_views(self, img: Tensor, denorm_images: Tensor, img_meta: dict, depth: Optional[Tensor] = None) -> None:
@@ -1019,9 +1051,10 @@ class SceneStream:
         return _with_counts(_frames_dict(coarse, fine, (poses.shape[0], win[2], win[3])), counts)
 
     def score_frames(self, frames: Tensor, meta: dict, depth_frames: Optional[Tensor] = None, stride: int = 1, n_importance: int = 0,
-                     ssim: bool = False, skip_empty=None, early_stop=None) -> dict:
+                     ssim: bool = False, skip_empty=None, early_stop=None, format: str = "bgr", uv_row=None) -> dict:
         """Held-out camera frames against the scene's render of their poses, on the device: ``frames`` (1, k, Hs, Ws, 3) uint8 BGR at capture
-        resolution, checked against the scene as :meth:`add_frames` checks them; ``meta`` a chunk meta with the k extrinsics; ``depth_frames``
+        resolution -- ``format="nv12"``: NV12 surfaces (1, k, rows, pitch) with ``uv_row``, scored as ``datasets.nv12_to_bgr`` of them would
+        be, exactly -- checked against the scene as :meth:`add_frames` checks them; ``meta`` a chunk meta with the k extrinsics; ``depth_frames``
         optionally the sensor's (1, k, Hd, Wd) uint16 millimetres.  The held-out bytes are pipeline.prepare_frames' resized bytes cropped to
         the content region and strided like the render (``stride=s``: pixels ``s // 2, s // 2 + s, ...``), the held-out depth
         pipeline.prepare_depth_frames at the content size, strided the same way and quantised by pack_frames' rule (pipeline.depth_to_mm);
@@ -1039,7 +1072,7 @@ class SceneStream:
             _check_culled_call(self.det, "score_frames", frames)
         stop = _stop_checked(self.det, early_stop, "score_frames", frames)
         held, held_depth, _, n_importance = _score_held_out(self.meta, [self.meta], frames, [meta], depth_frames, stride, n_importance, self.mean, self.std,
-                                                            ssim)
+                                                            ssim, format, uv_row)
         out = self.render_frames(extrinsic=meta["lidar2img"]["extrinsic"], stride=stride, n_importance=n_importance, skip_empty=knobs,
                                  early_stop=stop)
         return _with_counts(_frame_scores(out, held, held_depth, ssim), (out["n_kept"], out["n_samples"]) if "n_kept" in out else None)
@@ -1310,9 +1343,11 @@ class SceneGroup:
             raise RuntimeError("SceneGroup is inference only: call det.eval() first")
         return scenes, k
 
-    def add_frames(self, frames: Tensor, metas, scenes=None, depth: Optional[Tensor] = None, depth_frames: Optional[Tensor] = None) -> None:
+    def add_frames(self, frames: Tensor, metas, scenes=None, depth: Optional[Tensor] = None, depth_frames: Optional[Tensor] = None,
+                   format: str = "bgr", uv_row=None) -> None:
         """:meth:`add_views` for frames at CAPTURE resolution: ``frames`` (len(scenes), k, Hs, Ws, 3) uint8 BGR on the device, one row of k
-        frames per listed scene.  The group's meta says what becomes of them, as in :meth:`SceneStream.add_frames`: ``(Hs, Ws)`` must be
+        frames per listed scene -- or, with ``format="nv12"``, a video decoder's NV12 surfaces (len(scenes), k, rows, pitch) uint8 with
+        ``uv_row`` as in :meth:`SceneStream.add_frames`, still ONE launch (ndet_resize_normalize_views_nv12) for the whole call.  The group's meta says what becomes of them, as in :meth:`SceneStream.add_frames`: ``(Hs, Ws)`` must be
         its ``ori_shape`` and its ``img_shape`` what ``Resize(keep_ratio=True)`` into the ``pad_shape`` box gives, else ValueError --
         raised, like everything :meth:`add_views` refuses, before any device work.  ONE ndet_resize_normalize_views launch over all the
         ``len(scenes) * k`` frames makes ``img`` and ``denorm_images`` (with ``mean`` / ``std`` of ``begin_scenes``), and :meth:`add_views` takes them: guard, windows, banks and the promise that a call that raises changes
@@ -1320,7 +1355,7 @@ class SceneGroup:
         uint16 millimetres on the device; ONE ndet_depth_frames launch over all of them makes the float64 metres at the group's
         ``img_shape``, as in :meth:`SceneStream.add_frames`.  Both given, a wrong dtype or another k: ValueError, before any device work."""
         n = len(ops.listed_scenes(self.n_scenes, scenes))
-        img_scale, pad_size = check_frames_meta(self.metas[0], frames, n)
+        img_scale, pad_size = check_frames_meta(self.metas[0], frames, n, format, uv_row)
         metas = list(metas)
         for m in metas:
             _check_pad_shape(self.metas[0], m)
@@ -1328,7 +1363,8 @@ class SceneGroup:
         check_depth_frames(depth_frames, depth, n, k)
         shape = torch.empty((n, k, 3) + pad_size, device="meta")
         self._check_call(shape, shape, metas, scenes, depth)
-        img, denorm, depth = _prepared_frames(frames, depth_frames, depth, self.metas[0]["img_shape"], img_scale, pad_size, self.mean, self.std)
+        img, denorm, depth = _prepared_frames(frames, depth_frames, depth, self.metas[0]["img_shape"], img_scale, pad_size, self.mean, self.std,
+                                              _surface_kwargs(self.metas[0], format, uv_row))
         self.add_views(img, denorm, metas, scenes=scenes, depth=depth)
 
     def add_views(self, img: Tensor, denorm_images: Tensor, metas, scenes=None, depth: Optional[Tensor] = None) -> None:
@@ -1517,9 +1553,9 @@ class SceneGroup:
         return [_with_counts(_frames_dict(coarse, fine, (p.shape[0], win[2], win[3])), c) for (coarse, fine), p, c in zip(res, poses, counts)]
 
     def score_frames(self, frames: Tensor, metas, scenes=None, depth_frames: Optional[Tensor] = None, batched: bool = False, stride: int = 1,
-                     n_importance: int = 0, ssim: bool = False, skip_empty=None, early_stop=None):
+                     n_importance: int = 0, ssim: bool = False, skip_empty=None, early_stop=None, format: str = "bgr", uv_row=None):
         """:meth:`SceneStream.score_frames` for the listed scenes at once: ``frames`` (len(scenes), k, Hs, Ws, 3) uint8 BGR, one row of k
-        held-out frames per listed scene, checked as :meth:`add_frames` checks them; ``metas`` one chunk meta per row with its k extrinsics;
+        held-out frames per listed scene (``format="nv12"``: NV12 surfaces (len(scenes), k, rows, pitch) with ``uv_row``), checked as :meth:`add_frames` checks them; ``metas`` one chunk meta per row with its k extrinsics;
         ``depth_frames`` optionally (len(scenes), k, Hd, Wd) uint16 millimetres.  One ndet_resize_normalize_views launch (and one
         ndet_depth_frames launch) makes all the held-out frames, :meth:`render_frames` all the renders, and one ndet_frame_errors launch
         per scene compares them -- with ``ssim=True`` one ndet_frame_ssim launch per scene beside it, which adds ``ssim``, ``ssim_channels``
@@ -1535,7 +1571,7 @@ class SceneGroup:
         stop = _stop_checked(self.det, early_stop, "score_frames", frames, batched=batched)
         metas = list(metas)
         held, held_depth, k, n_importance = _score_held_out(self.metas[0], [self.metas[s] for s in scenes], frames, metas, depth_frames, stride, n_importance,
-                                                            self.mean, self.std, ssim)
+                                                            self.mean, self.std, ssim, format, uv_row)
         outs = self.render_frames(extrinsic=[m["lidar2img"]["extrinsic"] for m in metas], scenes=scenes, batched=batched, stride=stride,
                                   n_importance=n_importance, skip_empty=knobs, early_stop=stop)
         return [_with_counts(_frame_scores(out, held[i * k:(i + 1) * k], None if held_depth is None else held_depth[i * k:(i + 1) * k], ssim),

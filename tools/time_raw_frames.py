@@ -8,6 +8,7 @@
 The two launches: median of --reps event-timed launches after --warmup; the host chain: median of --host-reps runs.  One line per figure,
 then one JSON line.
     python tools/time_raw_frames.py [--reps 50 --warmup 10 --threads 16 --host-reps 3]
+    python tools/time_raw_frames.py --format nv12       # the NV12 ingest instead: fused launch, two-launch chain, BGR launch (nv12_figures)
 """
 import argparse
 import json
@@ -39,6 +40,65 @@ def timed(fn, reps, warmup):
     return statistics.median(ts)
 
 
+def nv12_figures(args):
+    """--format nv12: 50 tight NV12 surfaces of 968 x 1296 -> 239 x 320 in 240 x 320.
+      nv12_fused_ms      ndet_resize_normalize_views_nv12 on the surfaces
+      nv12_chain_ms      ndet_nv12_to_bgr to capture-size BGR frames, then ndet_resize_normalize_views on those: the two launches the fused
+                         one replaces
+      bgr_ms             ndet_resize_normalize_views on BGR frames of the same size, for the same session's comparison
+    each on one source buffer and (``*_rotating_ms``) over --rotate copies in turn, so that the source comes from HBM."""
+    from nerfdet_amd import _lib, pipeline as P
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    n, (hs, ws), scale, (h, w) = 50, (968, 1296), (320, 240), (240, 320)
+    hr, wr = P.rescale_size((hs, ws), scale)
+    rows = hs * 3 // 2
+    rng = np.random.RandomState(0)
+    surfaces = torch.from_numpy(rng.randint(0, 256, (n, rows, ws)).astype(np.uint8)).to(dev)
+    frames = torch.from_numpy(rng.randint(0, 256, (n, hs, ws, 3)).astype(np.uint8)).to(dev)
+    bgr = torch.empty((n, hs, ws, 3), dtype=torch.uint8, device=dev)
+    img = torch.empty((n, 3, h, w), device=dev)
+    dn = torch.empty_like(img)
+    u8 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev) if args.u8 else None
+    mean, std = np.asarray(P.IMG_MEAN, np.float64), np.asarray(P.IMG_STD, np.float64)
+    mp, sp = mean.ctypes.data_as(c_void_p), std.ctypes.data_as(c_void_p)
+    st = c_void_p(_lib.raw_stream(dev))
+    ptr = _lib._ptr
+
+    def fused(s):
+        _lib.check(lib.ndet_resize_normalize_views_nv12(ptr(s), None, n, hs, ws, ws, hs, rows, hr, wr, h, w, mp, sp, ptr(img), ptr(dn), ptr(u8), st),
+                   "resize_normalize_views_nv12")
+
+    def from_bgr(f):
+        _lib.check(lib.ndet_resize_normalize_views(ptr(f), None, n, hs, ws, hr, wr, h, w, mp, sp, ptr(img), ptr(dn), ptr(u8), st), "resize_normalize_views")
+
+    def chain(s):
+        _lib.check(lib.ndet_nv12_to_bgr(ptr(s), None, n, hs, ws, ws, hs, rows, ptr(bgr), st), "nv12_to_bgr")
+        from_bgr(bgr)
+
+    res = dict(format="nv12", frames=n, capture=[hs, ws], resized=[hr, wr], pad=[h, w])
+    for name, fn, src in (("nv12_fused", fused, surfaces), ("nv12_chain", chain, surfaces), ("bgr", from_bgr, frames)):
+        res[f"{name}_ms"] = timed(lambda: fn(src), args.reps, args.warmup)
+        copies = [src] + [src.clone() for _ in range(max(0, args.rotate - 1))]
+        turn = [0]
+
+        def rotating():
+            turn[0] = (turn[0] + 1) % len(copies)
+            fn(copies[turn[0]])
+
+        res[f"{name}_rotating_ms"] = timed(rotating, args.reps, args.warmup)
+        del copies
+    # the fused launch writes what the chain writes
+    fused(surfaces)
+    a = (img.clone(), dn.clone())
+    chain(surfaces)
+    torch.cuda.synchronize()
+    res["fused_equals_chain"] = bool(torch.equal(a[0], img) and torch.equal(a[1], dn))
+    for k, v in res.items():
+        print(f"{k:>24}: {v:.4f}" if isinstance(v, float) else f"{k:>24}: {v}")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
@@ -47,7 +107,10 @@ def main():
     ap.add_argument("--host-reps", type=int, default=3)
     ap.add_argument("--u8", action="store_true", help="also write the resized bytes")
     ap.add_argument("--rotate", type=int, default=4, help="copies of the raw frames the rotating figure walks")
+    ap.add_argument("--format", choices=("bgr", "nv12"), default="bgr", help="nv12: the NV12 ingest figures instead (see nv12_figures)")
     args = ap.parse_args()
+    if args.format == "nv12":
+        return nv12_figures(args)
     threads = max(1, min(16, args.threads))
     from nerfdet_amd import _lib, pipeline as P
     from nerfdet_amd.datasets import Normalize, Pad, Resize
