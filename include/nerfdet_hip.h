@@ -789,6 +789,16 @@ int ndet_conv_split_batch(const NdetConvArgs* a, int batch, void* stream);
  * launcher of the convolutions of mmdet3d/models/necks/imvoxelnet.py:36-67; the reference has no counterpart.  NDET_E_INVALID for another tile. */
 int ndet_conv_halo_patch(int tile, int D, int H, int W, const int* kernel, int* patch, int* looped);
 
+/* TEST SUPPORT, not part of the drop-in surface (no caller in the package).  Taps per barrier interval of the halo tiles' K walk: tile 3128 in
+ * arith 1 / 2 multiplies the three taps of a group between two barriers when the staged image's taps come in threes (3x3, 3x3x3 in both depth
+ * forms, 3x1x3); every other launch, one.  mode: 1 = every later launch of this process takes the one-tap walk (the same build's reference for
+ * the three-tap one: the two are bit-identical by construction), 0 = automatic again (the default), -1 = leave the switch as it is.  With taps or
+ * lds_bytes non-null, also what a launch of `tile` in `arith` (as NdetConvArgs::arith) over an image of `taps_per_image` taps would take under the
+ * switch as it then stands: *taps = 3 or 1, *lds_bytes = the dynamic LDS of its K walk (split image + weight stages).  No HIP call.  Part of the
+ * launcher of the convolutions of mmdet3d/models/necks/imvoxelnet.py:36-67; the reference has no counterpart.  NDET_E_INVALID for a mode outside
+ * -1 .. 1 and, when a query is asked, for a tile that is not a halo tile, arith outside 0 .. 2 or taps_per_image < 1 (the switch is then left). */
+int ndet_conv_halo_taps(int mode, int tile, int arith, int taps_per_image, int* taps, int* lds_bytes);
+
 #define NDET_TILE_DIRECT 1    /* epilogue straight from the accumulators: final values only */
 #define NDET_TILE_OWNS_ROWS 2 /* one tile holds all 256 channels of its rows: the chained projection (map_out) is allowed */
 #define NDET_TILE_ORDER2 4    /* may be dealt in the activation-stationary workgroup order */

@@ -156,6 +156,7 @@ SIGNATURES = {
     "ndet_conv_split": ([ctypes.POINTER(NdetConvArgs), _P], c_int),
     "ndet_conv_split_batch": ([ctypes.POINTER(NdetConvArgs), c_int, _P], c_int),
     "ndet_conv_halo_patch": ([c_int] * 4 + [ctypes.POINTER(c_int)] * 3, c_int),
+    "ndet_conv_halo_taps": ([c_int] * 4 + [ctypes.POINTER(c_int)] * 2, c_int),
     "ndet_conv_tile_info": ([c_int] + [ctypes.POINTER(c_int)] * 3, c_int),
     "ndet_conv_chain": ([_P, _P] + [c_int] * 5 + [_P] * 6 + [c_int, _P, _P, _P, c_int, _P, c_int, _P, c_float, c_float, _P, c_float, c_float, c_float, _P, _P], c_int),
     "ndet_bottleneck_f16x2": ([_P, c_int, c_int, c_int, c_int, c_int, _P, c_float, _P, _P, _P, c_float, _P, _P, _P, c_float, _P, _P, _P, c_float, _P, _P, _P, _P, _P,

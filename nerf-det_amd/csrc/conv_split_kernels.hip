@@ -1409,6 +1409,8 @@ static int split_launch_wsp(const Conv3dParams& p, hipStream_t st, const char* f
 // image -- a tap is a constant row offset in the halo grid.  Per tap step the producers only move the weight tile:
 // LDS-DMA (buffer_load ... lds, no registers, no ds_write), 2 - 3 stages deep, waited with counted vmcnt.
 // Consumers: 4 waves (2 x 2), 16x16x32 MFMAs, wave tile 64 x (16 NT16).
+// The 128-column tile in the two- and one-plane schemes takes three taps per barrier interval (SPL_TPS3 below) where the image's taps come in
+// threes: measured (profiles/r05_a_halo3128_kstep_stamps.txt) 1 850 -> 1 510 ticks per tap on l3.conv2, 1 716 -> 1 422 on the neck's out0.
 // ------------------------------------------------------------------------------------------------
 struct HaloGeom {
     int ltd, lth, ltw;     // log2 of the patch extents (TD TH TW = 128)
@@ -1449,15 +1451,38 @@ struct HaloRowMapBatch {
 // SCHB = SCH + SPL_BATCH: N volumes of p.D x p.H x p.W, each tiled by patches of its own (grid x = N npd nph npw, the volume from the patch index).
 // The patch origin d0 stays inside the volume, so the halo's depth bound and the looped depth taps' mask are the volume's; the volume enters the
 // activation offsets and the output row only.
+// SCHB + SPL_TPS3 (the 128-column tile, SCH 1 / 2, Tin % 3 == 0): THREE taps per barrier interval.  A 128-column step is 48 MFMAs per SIMD
+// (768 cycles) and pays the same barrier, fragment-read latency and DMA issue as a 256-column one; this tile's LDS has room (100 of 160 KB),
+// so a weight stage holds the 3 tap tiles of a group (two stages: 51 200 B image + 2 x 49 152 B in fp16-pair mode = 149 504 B).  The
+// producers issue group i + 1 into the free stage and drain their queue (vmcnt(0)) before P1; the consumers multiply group i tap-major
+// between two P1 barriers, every product and tile in the one-tap loop's order (each accumulator sees the same MFMA sequence: the result is
+// bit-identical), and read tap t + 1's fragments while tap t multiplies.  The image is constant over a phase's Tin taps, so a group never
+// straddles a P2 restage.  The same barriers P0 / P1 / P2, a third as many P1.
+#define SPL_TPS3 8
+#ifdef HALO_STAMPS    // diagnostic builds (tools/diag/halo_stamps.py): every wave of workgroup (0, 0, 0) sums the shader clock over the parts of its K walk
+__device__ unsigned long long* g_halo_stamps = nullptr;
+extern "C" int ndet_halo_set_stamps(unsigned long long* buf) { return hipMemcpyToSymbol(HIP_SYMBOL(g_halo_stamps), &buf, sizeof(buf)) == hipSuccess ? 0 : -3; }
+#define HSTAMP_BEGIN() unsigned long long hs_acc[4] = {0, 0, 0, 0}, hs_t = __builtin_amdgcn_s_memtime()
+#define HSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long hs_n = __builtin_amdgcn_s_memtime(); hs_acc[i] += hs_n - hs_t; hs_t = hs_n; __builtin_amdgcn_sched_barrier(0); } while (0)
+#define HSTAMP_READS() do { if (HALO_STAMPS > 1) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); HSTAMP(0); } } while (0)   // (serialises reads and MFMAs)
+#define HSTAMP_END() do { if (g_halo_stamps && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && lane == 0) for (int i = 0; i < 4; ++i) g_halo_stamps[wave * 4 + i] = hs_acc[i]; } while (0)
+#else
+#define HSTAMP_BEGIN()
+#define HSTAMP(i)
+#define HSTAMP_READS()
+#define HSTAMP_END()
+#endif
 template <int NT16, int WGN, int SCHB, int NPROD = 4>
 __global__ __launch_bounds__(64 * (2 * WGN + NPROD), 1) void k_conv_split_halo(const Conv3dParams p, const uint16_t* __restrict__ wsplit, const HaloGeom g) {
     constexpr int SCH = SCHB & 3;
     constexpr bool BATCH = (SCHB & SPL_BATCH) != 0;
+    constexpr int TPS = (SCHB & SPL_TPS3) ? 3 : 1;           // taps per barrier interval
     constexpr int BN = 16 * NT16 * WGN;
     constexpr int NCONS = 2 * WGN, NTHR = 64 * (NCONS + NPROD);
     constexpr int PT = 64 * NPROD;                          // producer threads
     constexpr int HALO_MAX = (BN == 128) ? 400 : 224;
-    constexpr int NSTAGE = (BN == 128) ? 3 : 2;
+    constexpr int NSTAGE = (BN == 128 && TPS == 1) ? 3 : 2;  // weight stages, of TPS tap tiles each
+    static_assert(TPS == 1 || (BN == 128 && SCH != 0), "three taps per interval: the 128-column tile in the two- and one-plane schemes");
     constexpr int NPIECE = (HALO_MAX * 8 + PT - 1) / PT;
     constexpr int APL = HALO_MAX * CBK, BPL = BN * CBK;   // one plane, elements
     constexpr int NPL = SCH == 1 ? 2 : (SCH == 2 ? 1 : 3);   // operand planes staged and multiplied
@@ -1466,6 +1491,7 @@ __global__ __launch_bounds__(64 * (2 * WGN + NPROD), 1) void k_conv_split_halo(c
     constexpr int BR = BN / (16 * NPROD);                  // weight rows per producer thread and plane
     static_assert(BR >= 1 && BN % (16 * NPROD) == 0, "every producer wave stages 16 rows of each row group");
     constexpr int NB = NPL * BR;                             // LDS-DMA instructions per producer thread and K step
+    static_assert((size_t)(NPL * APL + NSTAGE * TPS * BSTAGE) * sizeof(uint16_t) <= 160 * 1024, "image + weight stages exceed a CU's LDS");
     extern __shared__ __attribute__((aligned(16))) uint16_t lds16[];
     uint16_t* Bs = lds16 + NPL * APL;
 
@@ -1542,9 +1568,9 @@ __global__ __launch_bounds__(64 * (2 * WGN + NPROD), 1) void k_conv_split_halo(c
         }
         const unsigned wtile_b = (unsigned)p.Cout * CBK * 2;
         int dt = 0, dc = 0;   // tap and chunk (relative to cb) of the next weight tile to fetch
-        auto dma_b = [&](int u) {   // tile u -> stage u % NSTAGE
+        auto dma_b = [&](int u) {   // tile u -> stage u % NSTAGE (TPS 3: u is the tile slot itself, stage * TPS + tap of the group)
             const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)(((int64_t)dt * nch_all + cb + dc) * WPL) * wtile_b);
-            uint16_t* stage = Bs + (u % NSTAGE) * BSTAGE;
+            uint16_t* stage = Bs + (TPS == 1 ? u % NSTAGE : u) * BSTAGE;
 #pragma unroll
             for (int i = 0; i < BR; ++i)
 #pragma unroll
@@ -1580,41 +1606,67 @@ __global__ __launch_bounds__(64 * (2 * WGN + NPROD), 1) void k_conv_split_halo(c
 
         __builtin_amdgcn_s_setprio(3);
         load_a(0);
+        if constexpr (TPS == 1) {
 #pragma unroll
-        for (int u = 0; u < NSTAGE - 1; ++u)
-            if (u < S) dma_b(u);
+            for (int u = 0; u < NSTAGE - 1; ++u)
+                if (u < S) dma_b(u);
+        } else {
+#pragma unroll
+            for (int j = 0; j < TPS; ++j) dma_b(j);          // group 0 (S >= Tin >= TPS)
+        }
         split_store_a();
         if (nphase > 1) load_a(1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // weight tile 0 (and whatever else) has landed
         __syncthreads();                                     // P0
+        HSTAMP_BEGIN();
         int s = 0;
         for (int ci = 0; ci < nphase; ++ci) {
-            for (int t = 0; t < Tin; ++t, ++s) {
-                if (s + NSTAGE - 1 < S) {
-                    dma_b(s + NSTAGE - 1);
-                    // tile s + 1 must have landed before the barrier; the NSTAGE - 2 younger tiles may stay in flight
-                    // (completion is in order: right after a chunk boundary the next chunk's activation loads are younger
-                    // than tile s + 1 and may stay in flight too)
-                    if (NSTAGE == 3) {
-                        // exactly the NB pieces just issued may stay in flight.  (Right after a chunk boundary the next chunk's
-                        // NPIECE activation loads are younger than tile s + 1 too and could be allowed to fly as well -- vmcnt(NB +
-                        // NPIECE) -- but that count is only right on the path through P2, which tools/audit_vmcnt.py cannot tell
-                        // from the loop's back edge in the compiled control flow: the provable wait is kept.)
-                        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB) : "memory");
+            if constexpr (TPS == 1) {
+                for (int t = 0; t < Tin; ++t, ++s) {
+                    if (s + NSTAGE - 1 < S) {
+                        dma_b(s + NSTAGE - 1);
+                        // tile s + 1 must have landed before the barrier; the NSTAGE - 2 younger tiles may stay in flight
+                        // (completion is in order: right after a chunk boundary the next chunk's activation loads are younger
+                        // than tile s + 1 and may stay in flight too)
+                        if (NSTAGE == 3) {
+                            // exactly the NB pieces just issued may stay in flight.  (Right after a chunk boundary the next chunk's
+                            // NPIECE activation loads are younger than tile s + 1 too and could be allowed to fly as well -- vmcnt(NB +
+                            // NPIECE) -- but that count is only right on the path through P2, which tools/audit_vmcnt.py cannot tell
+                            // from the loop's back edge in the compiled control flow: the provable wait is kept.)
+                            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB) : "memory");
+                        } else {
+                            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        }
                     } else {
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     }
-                } else {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    HSTAMP(0);
+                    __syncthreads();                             // P1
+                    HSTAMP(1);
                 }
-                __syncthreads();                             // P1
+            } else {
+                // s counts groups of TPS taps: group s multiplies out of stage s & 1 while group s + 1 lands in the other one, which the
+                // consumers left at the previous P1.  The queue is drained before every P1: no count to prove.
+                for (int t = 0; t < Tin; t += TPS, ++s) {
+                    if ((s + 1) * TPS < S) {
+#pragma unroll
+                        for (int j = 0; j < TPS; ++j) dma_b(((s + 1) & 1) * TPS + j);
+                    }
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    HSTAMP(0);
+                    __syncthreads();                             // P1
+                    HSTAMP(1);
+                }
             }
             if (ci + 1 < nphase) {
                 split_store_a();                             // image ci + 1 (loaded during image ci); the consumers wait at P2
+                HSTAMP(2);
                 __syncthreads();                             // P2
                 if (ci + 2 < nphase) load_a(ci + 2);
+                HSTAMP(3);
             }
         }
+        HSTAMP_END();
     } else {
         // ---------------- consumers ----------------
         const int frow = lane & 15, fc = lane >> 4;
@@ -1628,9 +1680,11 @@ __global__ __launch_bounds__(64 * (2 * WGN + NPROD), 1) void k_conv_split_halo(c
         const int boff = (wn * (16 * NT16) + frow) * CBK + ((fc ^ ws_swz(frow)) * 8);
         const int wkh = p.kh, wkw = p.kw;
         __syncthreads();                                     // P0
+        HSTAMP_BEGIN();
         int s = 0;
         for (int ci = 0; ci < nphase; ++ci) {
             int kd = 0, kh = 0, kw = 0;   // tap inside the staged image (kd stays 0 when the depth taps are looped outside)
+            if constexpr (TPS == 1) {
             for (int t = 0; t < Tin; ++t, ++s) {
                 const int tapoff = (kd * g.HH + kh) * g.HW + kw;
                 const uint16_t* bst = Bs + (s % NSTAGE) * BSTAGE + boff;
@@ -1649,6 +1703,7 @@ __global__ __launch_bounds__(64 * (2 * WGN + NPROD), 1) void k_conv_split_halo(c
 #pragma unroll
                     for (int tb = 0; tb < NT16; ++tb) fb[pq][tb] = *reinterpret_cast<const bf16x8*>(bst + pq * BPL + tb * 16 * CBK);
                 }
+                HSTAMP_READS();
 #pragma unroll
                 for (int order = NPL - 1; order >= 0; --order)
                     if (order <= p.max_order)
@@ -1666,10 +1721,67 @@ __global__ __launch_bounds__(64 * (2 * WGN + NPROD), 1) void k_conv_split_halo(c
                     kw = 0;
                     if (++kh == wkh) { kh = 0; ++kd; }
                 }
+                HSTAMP(1);
                 __syncthreads();                             // P1
+                HSTAMP(2);
             }
-            if (ci + 1 < nphase) __syncthreads();            // P2
+            } else {
+                // s counts groups: stage s & 1 holds the TPS tap tiles of group s.  Tap-major, and inside a tap the planes, products and tiles
+                // of the loop above in its order; fragment set tt & 1 multiplies while set (tt + 1) & 1 is read.
+                const uint16_t* ap[4];
+                auto read_frags = [&](bf16x8 (&fa)[NPL][4], bf16x8 (&fb)[NPL][NT16], const uint16_t* bst) {
+                    const int tapoff = (kd * g.HH + kh) * g.HW + kw;
+#pragma unroll
+                    for (int ta = 0; ta < 4; ++ta) {
+                        const int hr = hr0[ta] + tapoff;
+                        ap[ta] = lds16 + hr * CBK + ((fc ^ ws_swz(hr)) * 8);
+                    }
+#pragma unroll
+                    for (int pl = 0; pl < NPL; ++pl) {
+                        const int pq = NPL - 1 - pl;
+#pragma unroll
+                        for (int ta = 0; ta < 4; ++ta) fa[pl][ta] = *reinterpret_cast<const bf16x8*>(ap[ta] + pl * APL);
+#pragma unroll
+                        for (int tb = 0; tb < NT16; ++tb) fb[pq][tb] = *reinterpret_cast<const bf16x8*>(bst + pq * BPL + tb * 16 * CBK);
+                    }
+                    if (++kw == wkw) {                           // (kd kh kw: the tap whose fragments are read next)
+                        kw = 0;
+                        if (++kh == wkh) { kh = 0; ++kd; }
+                    }
+                };
+                for (int t = 0; t < Tin; t += TPS, ++s) {
+                    const uint16_t* bst = Bs + (s & 1) * (TPS * BSTAGE) + boff;
+                    bf16x8 fa[2][NPL][4], fb[2][NPL][NT16];
+                    read_frags(fa[0], fb[0], bst);
+                    HSTAMP_READS();
+#pragma unroll
+                    for (int tt = 0; tt < TPS; ++tt) {
+                        if (tt + 1 < TPS) read_frags(fa[(tt + 1) & 1], fb[(tt + 1) & 1], bst + (tt + 1) * BSTAGE);
+#pragma unroll
+                        for (int order = NPL - 1; order >= 0; --order)
+                            if (order <= p.max_order)
+#pragma unroll
+                            for (int pa = 0; pa <= order; ++pa) {
+                                const int pbb = order - pa;
+#pragma unroll
+                                for (int ta = 0; ta < 4; ++ta)
+#pragma unroll
+                                    for (int tb = 0; tb < NT16; ++tb) {
+                                        acc[ta][tb] = spl_mfma16<SCH>(fa[tt & 1][pa][ta], fb[tt & 1][pbb][tb], acc[ta][tb]);
+                                    }
+                            }
+                    }
+                    HSTAMP(1);
+                    __syncthreads();                             // P1
+                    HSTAMP(2);
+                }
+            }
+            if (ci + 1 < nphase) {
+                __syncthreads();                                 // P2
+                HSTAMP(3);
+            }
         }
+        HSTAMP_END();
     }
     __builtin_amdgcn_s_setprio(0);
 
@@ -1727,10 +1839,21 @@ static bool halo_geometry(const Conv3dParams& p, int halo_max, HaloGeom& g) {
     return best < 1e29;
 }
 
+// Taps per barrier interval of a halo launch: 3 where the instantiation exists (the 128-column tile with four producer waves, SCH 1 / 2) and the
+// staged image's taps come in threes, else 1.  g_halo_tps1 (ndet_conv_halo_taps, test support) forces 1.
+static bool g_halo_tps1 = false;
+static constexpr bool halo_has_tps3(int cols, int sch, int nprod) { return cols == 128 && nprod == 4 && (sch == 1 || sch == 2); }
+static int halo_tps(int cols, int sch, int nprod, int tin) { return halo_has_tps3(cols, sch, nprod) && tin % 3 == 0 && !g_halo_tps1 ? 3 : 1; }
+// dynamic LDS of the K walk: the split image + the weight stages (3 one-tap stages at 128 columns, 2 at 256; 2 three-tap stages at TPS 3)
+static constexpr size_t halo_walk_lds(int cols, int sch, int tps) {
+    const int npl = sch == 1 ? 2 : (sch == 2 ? 1 : 3);
+    const int halo_max = cols == 128 ? 400 : 224, nstage = (cols == 128 && tps == 1) ? 3 : 2;
+    return (size_t)(npl * halo_max * CBK + nstage * tps * npl * cols * CBK) * sizeof(uint16_t);
+}
+
 template <int NT16, int WGN, int SCH, int NPROD, bool BATCH>
 static int split_launch_halo(const Conv3dParams& p, int batch, hipStream_t st, const char* fn) {
-    constexpr int NPL = SCH == 1 ? 2 : (SCH == 2 ? 1 : 3);
-    constexpr int BN = 16 * NT16 * WGN, HALO_MAX = (BN == 128) ? 400 : 224, NSTAGE = (BN == 128) ? 3 : 2;
+    constexpr int BN = 16 * NT16 * WGN, HALO_MAX = (BN == 128) ? 400 : 224;
     NDET_REQUIRE(!p.transposed && p.sd == 1 && p.sh == 1 && p.sw == 1 && (p.kd & 1) && (p.kh & 1) && (p.kw & 1) && p.pd == p.kd / 2 &&
                      p.ph == p.kh / 2 && p.pw == p.kw / 2,
                  NDET_E_UNSUPPORTED, "%s: the halo tile needs a stride-1 same-padded convolution with odd kernel extents", fn);
@@ -1741,7 +1864,8 @@ static int split_launch_halo(const Conv3dParams& p, int batch, hipStream_t st, c
     HaloGeom g;
     NDET_REQUIRE(halo_geometry(p, HALO_MAX, g), NDET_E_UNSUPPORTED, "%s: no patch shape fits the halo tile", fn);
     dim3 grid((unsigned)(nvol * g.npd * g.nph * g.npw), (p.Cout + BN - 1) / BN, p.splits);      // every volume is tiled by patches of its own
-    size_t lds = (size_t)(NPL * HALO_MAX * CBK + NSTAGE * NPL * BN * CBK) * sizeof(uint16_t);
+    const int tps = halo_tps(BN, SCH, NPROD, g.Tin);
+    size_t lds = halo_walk_lds(BN, SCH, tps);
     const size_t cs = (size_t)64 * (BN + 4) * sizeof(float);
     if (cs > lds) lds = cs;
     const size_t lds_map = cs + (size_t)BN * 32 * sizeof(float);     // the staged rows + the chained projection's (BN, 32) weight
@@ -1750,6 +1874,15 @@ static int split_launch_halo(const Conv3dParams& p, int batch, hipStream_t st, c
         NDET_REQUIRE(p.Cout == BN && p.splits == 1 && !p.res && p.relu == 0, NDET_E_UNSUPPORTED,
                      "%s: the chained projection needs a tile that owns all %d output channels of its rows, no split-K / residual / ReLU", fn, p.Cout);
         lds = lds_cap;
+    }
+    if constexpr (halo_has_tps3(BN, SCH, NPROD)) {
+        static_assert(halo_walk_lds(BN, SCH, 3) <= 160 * 1024, "image + two three-tap weight stages exceed a CU's LDS");
+        if (tps == 3) {
+            const auto kernel3 = k_conv_split_halo<NT16, WGN, SCH + (BATCH ? SPL_BATCH : 0) + SPL_TPS3, NPROD>;
+            NDET_RAISE_LDS(kernel3, lds_cap);
+            hipLaunchKernelGGL(kernel3, grid, dim3(64 * (2 * WGN + NPROD)), lds, st, p, (const uint16_t*)p.w, g);
+            return NDET_OK;
+        }
     }
     const auto kernel = k_conv_split_halo<NT16, WGN, SCH + (BATCH ? SPL_BATCH : 0), NPROD>;
     NDET_RAISE_LDS(kernel, lds_cap);
@@ -1879,6 +2012,24 @@ extern "C" int ndet_conv_halo_patch(int tile, int D, int H, int W, const int* ke
     NDET_REQUIRE(halo_geometry(p, t->cols == 128 ? 400 : 224, g), NDET_E_UNSUPPORTED, "%s: no patch shape fits the halo tile", fn);
     patch[0] = 1 << g.ltd; patch[1] = 1 << g.lth; patch[2] = 1 << g.ltw;
     *looped = g.KDL > 1 ? 1 : 0;
+    return NDET_OK;
+}
+
+extern "C" int ndet_conv_halo_taps(int mode, int tile, int arith, int taps_per_image, int* taps, int* lds_bytes) {
+    const char* fn = "ndet_conv_halo_taps";
+    NDET_REQUIRE(mode >= -1 && mode <= 1, NDET_E_INVALID, "%s: mode is -1 (leave), 0 (automatic) or 1 (one tap per interval)", fn);
+    if (taps || lds_bytes) {
+        const ConvTile* t = conv_tile(tile);
+        NDET_REQUIRE(t && (tile == 3128 || (t->flags & NDET_TILE_OWNS_ROWS)), NDET_E_INVALID, "%s: tile %d is not a halo tile", fn, tile);
+        NDET_REQUIRE(arith >= 0 && arith <= 2 && taps_per_image >= 1, NDET_E_INVALID, "%s: arith is 0 / 1 / 2, taps_per_image >= 1", fn);
+    }
+    if (mode >= 0) g_halo_tps1 = mode == 1;
+    if (taps || lds_bytes) {
+        const int nprod = tile == 3258 && arith != 0 ? 8 : 4;
+        const int tps = halo_tps(conv_tile(tile)->cols, arith, nprod, taps_per_image);
+        if (taps) *taps = tps;
+        if (lds_bytes) *lds_bytes = (int)halo_walk_lds(conv_tile(tile)->cols, arith, tps);
+    }
     return NDET_OK;
 }
 
