@@ -1043,6 +1043,43 @@ int ndet_project_boxes(const float* intrinsic_rows, const float* world2cam, cons
 int ndet_draw_boxes(const uint8_t* frames_in, const int32_t* edges, const int32_t* edge_mask, const uint8_t* colours, int k, int h, int w, int n,
                     int thickness, uint8_t* frames_out, void* stream);
 
+/* ndet_project_boxes_w: ndet_project_boxes -- the same arguments, checks and statement order, its four outputs bit for bit (the corners
+ * are DepthInstance3DBoxes.corners, mmdet3d/core/bbox/structures/depth_box3d.py:46-84) -- plus edge_w (k,n,12,2) float32 for
+ * ndet_draw_overlay's depth test: for a surviving edge, in the edge's own corner order, 1.0f / z of either end AFTER the near clip (a
+ * clipped end has z = near); two zeros for a dropped edge.  edge_w must be 8-byte aligned (NDET_E_UNSUPPORTED), a null edge_w is
+ * NDET_E_INVALID. */
+int ndet_project_boxes_w(const float* intrinsic_rows, const float* world2cam, const float* corners, int k, int n, int x0, int y0, int stride, int h,
+                         int w, float near_m, int32_t* edges, int32_t* edge_mask, int32_t* rect, float* zrange, float* edge_w, void* stream);
+
+/* ndet_draw_overlay: ndet_draw_boxes with an optional depth test of the edges and optional text plates, one launch, new frames (the
+ * boxes are the result's, mmdet3d/models/dense_heads/imvoxel_head_v2.py:544; the reference draws nothing).  frames_in, edges, edge_mask,
+ * colours, thickness and frames_out are ndet_draw_boxes', with its line rule.  Two optional argument groups, each whole or all null:
+ * depth_mm (k,h,w) uint16 millimetres + edge_w (k,n,12,2) of ndet_project_boxes_w;  rect (k,n,4) of ndet_project_boxes + text (n,32) uint8
+ * codes + text_len (n) int32 + font (96,7) uint8.  With both groups null the output is ndet_draw_boxes' bit for bit.
+ *   Edge depth at a covered pixel: where the line rule swaps an edge's ends, their w swap with them.  With P the pixel's major-axis
+ *       coordinate, p0 and p1 the ends' and a = p1 - p0 > 0:  s = (float)(P - p0) / (float)a,  w_p = fmaf(s, w_1 - w_0, w_0);  a = 0 (a
+ *       point edge): w_p = w_0, the first end in corner order;  e_mm = (1.0f / w_p) * 1000.0f.  Every pixel a thick line covers uses
+ *       its own P and its own millimetres.  1/z is linear on the screen, but s comes from integer cells: it is off by up to a pixel's
+ *       worth along the edge, and more at an end bent by ndet_project_boxes' 2^20 clamp -- bias_mm is there to absorb that.
+ *   Hidden: a covered pixel of an edge is hidden iff mm != 0 && (float)mm + bias_mm < e_mm.  A hole hides nothing; 65535 is a value
+ *       like any other.  Without depth_mm nothing is hidden.
+ *   Winner without a plate: bv = the highest box index with a visible covering edge, bh = the highest with a hidden one.  bv >= 0: the
+ *       pixel is colours[bv] (a visible edge beats a hidden one of any index); else occluded == 1 (dim) and bh >= 0: each channel is
+ *       (3 * in + colours[bh][c] + 2) >> 2; else the input byte (occluded == 0: hide).
+ *   Plates: box b of pose p has one iff rect[p][b].x >= 0 and len = clamp(text_len[b], 0, 32) > 0.  With S = text_scale in {1, 2, 3}:
+ *       pw = S (6 len + 1), ph = 9 S, px0 = min(xmin, max(w - pw, 0)), py0 = max(ymin - ph, 0), clipped to the frame.  For a pixel inside
+ *       u = (x - px0) / S, v = (y - py0) / S, c = u - 1, r = v - 1, g = c / 6, gc = c - 6 g; it is ink iff c >= 0 && 0 <= r <= 6 &&
+ *       gc < 5 && g < len and bit (4 - gc) of font[glyph][r] is set, glyph = code - 32 for 32 <= code <= 127 (code = text[b][g]), else 95.
+ *       A pixel under any plate takes the plate of the HIGHEST box index, ahead of every edge and never depth-tested: colours[b], or
+ *       for ink black where (29 B + 150 G + 77 R + 128) >> 8 >= 128 of that colour, else white.
+ * One workgroup per 16 x 16 tile; plates and edges are staged through LDS 256 at a time, the font once.  On the host, before any HIP call:
+ * ndet_draw_boxes' refusals, an incomplete group, occluded not 0 or 1, bias_mm negative, NaN or infinite, text_scale outside 1..3 with
+ * plates: NDET_E_INVALID; 2^31 elements, 2^24 workgroups, a misaligned edge_w (8 bytes), rect (16), depth_mm (2), text_len (4):
+ * NDET_E_UNSUPPORTED. */
+int ndet_draw_overlay(const uint8_t* frames_in, const int32_t* edges, const int32_t* edge_mask, const uint8_t* colours, const uint16_t* depth_mm,
+                      const float* edge_w, float bias_mm, int occluded, const int32_t* rect, const uint8_t* text, const int32_t* text_len,
+                      const uint8_t* font, int text_scale, int k, int h, int w, int n, int thickness, uint8_t* frames_out, void* stream);
+
 /* ndet_label_frames: which detection each pixel of a depth frame belongs to.  depth_mm (k,h,w) uint16 millimetres (0: a hole) on
  * ndet_camera_rays' grid x0, y0, stride with its intrinsic_rows (2,3), camrotc2w (k,3,3) and cam_lightpos (k,3); box_frames (n,8) float32 =
  * centre (3), half extents (3), cos yaw, sin yaw, n <= 32767.  A pixel with mm != 0 looks along d, ndet_camera_rays' expression statement

@@ -186,6 +186,8 @@ SIGNATURES = {
     "ndet_frame_ssim": ([_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P], c_int),
     "ndet_project_boxes": ([_P, _P, _P] + [c_int] * 7 + [c_float, _P, _P, _P, _P, _P], c_int),
     "ndet_draw_boxes": ([_P, _P, _P, _P] + [c_int] * 5 + [_P, _P], c_int),
+    "ndet_project_boxes_w": ([_P, _P, _P] + [c_int] * 7 + [c_float, _P, _P, _P, _P, _P, _P], c_int),
+    "ndet_draw_overlay": ([_P] * 6 + [c_float, c_int] + [_P] * 4 + [c_int] * 6 + [_P, _P], c_int),
     "ndet_label_frames": ([_P] * 5 + [c_int] * 7 + [_P, _P], c_int),
     "ndet_stem_pack_weights": ([_P, _P, _P], c_int),
     "ndet_stem_conv_bn_relu_maxpool": ([_P, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, _P, c_float, _P, _P, _P, _P, _P], c_int),

@@ -29,6 +29,9 @@ same frames, and for float renders: one fused 7 x 7 window kernel with integer s
 A detection result goes the same way into the camera's image: :func:`project_boxes` says where boxes fall in the frames of given poses
 (ndet_project_boxes), :func:`draw_boxes` puts their wireframes onto frames in device memory (ndet_draw_boxes) and :func:`label_frames` says
 which box each pixel of a depth frame belongs to (ndet_label_frames) -- what ``draw_detections`` and ``label_detections`` stand on.
+:func:`draw_overlay` is :func:`draw_boxes` with the edges depth-tested against a millimetre depth frame and with the class and the score
+written on a plate above each box (ndet_draw_overlay; ``project_boxes(depths=True)``, ndet_project_boxes_w, gives the edges' depths;
+:data:`FONT_5X7` and :func:`encode_texts` the glyphs and the codes).
 """
 from __future__ import annotations
 
@@ -483,13 +486,17 @@ def _host_f32(a, shape_tail: tuple, what: str) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-def project_boxes(intrinsic, corners, window, stride: int = 1, c2w=None, extrinsic=None, near: float = 0.1, device=None) -> dict:
+def project_boxes(intrinsic, corners, window, stride: int = 1, c2w=None, extrinsic=None, near: float = 0.1, device=None, depths: bool = False) -> dict:
     """Where n boxes fall in the frames of k camera poses: one launch (ndet_project_boxes), one small upload, nothing read back.
     ``intrinsic``: 3 x 3 or 4 x 4, scaled to the image grid; ``corners`` (n, 8, 3) float, as ``boxes.box_corners`` makes them;
     ``window = (y0, x0, h, w)`` and ``stride`` as in :func:`camera_rays`; exactly one of ``c2w`` (k camera-to-world 4 x 4, inverted on the host
     in float64 and rounded to float32) and ``extrinsic`` (k world-to-camera 4 x 4, taken as given); ``near`` > 0 in metres, the plane edges are
     clipped at.  Returns ``dict(edges (k,n,12,4) int32, edge_mask (k,n) int32, rect (k,n,4) int32, zrange (k,n,2) float32, window, stride)``
-    on the device, as include/nerfdet_hip.h defines them.  ValueError for wrong shapes, RuntimeError without a GPU (no CPU fallback)."""
+    on the device, as include/nerfdet_hip.h defines them.  ``depths=True`` makes the launch ndet_project_boxes_w: the same tables bit for
+    bit and ``edge_w (k,n,12,2) float32``, the reciprocal camera z of every surviving edge's ends after the near clip, which
+    :func:`draw_overlay`'s depth test needs.  ValueError for wrong shapes, RuntimeError without a GPU (no CPU fallback)."""
+    if not isinstance(depths, bool):
+        raise ValueError(f"project_boxes: depths must be a bool, got {depths!r}")
     (y0, x0, h, w), stride = check_window(window, stride)
     krows = _intrinsic_rows(intrinsic, "project_boxes")
     pts = _host_f32(corners, (8, 3), "project_boxes: corners")
@@ -511,9 +518,15 @@ def project_boxes(intrinsic, corners, window, stride: int = 1, c2w=None, extrins
     edge_mask = torch.empty((k, n), dtype=torch.int32, device=dev)
     rect = torch.empty((k, n, 4), dtype=torch.int32, device=dev)
     zrange = torch.empty((k, n, 2), dtype=torch.float32, device=dev)
-    check(_lib.load().ndet_project_boxes(_ptr(buf), _ptr(buf[6:]), _ptr(buf[6 + 12 * k:]), k, n, x0, y0, stride, h, w, float(near), _ptr(edges),
-                                         _ptr(edge_mask), _ptr(rect), _ptr(zrange), c_void_p(_lib.raw_stream(dev))), "project_boxes")
-    return dict(edges=edges, edge_mask=edge_mask, rect=rect, zrange=zrange, window=(y0, x0, h, w), stride=stride)
+    out = dict(edges=edges, edge_mask=edge_mask, rect=rect, zrange=zrange, window=(y0, x0, h, w), stride=stride)
+    args = (_ptr(buf), _ptr(buf[6:]), _ptr(buf[6 + 12 * k:]), k, n, x0, y0, stride, h, w, float(near), _ptr(edges), _ptr(edge_mask), _ptr(rect),
+            _ptr(zrange))
+    if depths:
+        out["edge_w"] = torch.empty((k, n, 12, 2), dtype=torch.float32, device=dev)
+        check(_lib.load().ndet_project_boxes_w(*args, _ptr(out["edge_w"]), c_void_p(_lib.raw_stream(dev))), "project_boxes")
+    else:
+        check(_lib.load().ndet_project_boxes(*args, c_void_p(_lib.raw_stream(dev))), "project_boxes")
+    return out
 
 
 def draw_boxes(frames: torch.Tensor, projected: dict, colours, thickness: int = 1) -> torch.Tensor:
@@ -522,35 +535,166 @@ def draw_boxes(frames: torch.Tensor, projected: dict, colours, thickness: int = 
     uint8, numpy or tensor (a device tensor is used as it is); ``thickness`` 1, 3 or 5 pixels across the line's major axis.  Where the edges
     of several boxes cover a pixel the HIGHEST box index wins, so hand the boxes over by ascending score (``boxes.drawing_order``).
     ValueError for wrong shapes or dtypes before any launch, RuntimeError for CPU tensors."""
+    (k, h, w, n), edges, edge_mask, col = _check_drawing(frames, projected, colours, thickness, "draw_boxes")
+    _need_gpu_drawing(frames, edges, edge_mask)
+    dev = frames.device
+    col = _device_colours(col, dev)
+    out = torch.empty_like(frames)
+    check(_lib.load().ndet_draw_boxes(_ptr(frames), _ptr(edges), _ptr(edge_mask), _ptr(col), k, h, w, n, int(thickness), _ptr(out),
+                                      c_void_p(_lib.raw_stream(dev))), "draw_boxes")
+    return out
+
+
+def _check_drawing(frames, projected, colours, thickness, what: str):
+    """The shape and dtype checks :func:`draw_boxes` and :func:`draw_overlay` share: ``((k, h, w, n), edges, edge_mask, colours)``, the
+    colours a tensor or a numpy array as given; ValueError for anything else."""
     if thickness not in (1, 3, 5) or isinstance(thickness, bool):
-        raise ValueError(f"draw_boxes: thickness={thickness!r} must be 1, 3 or 5")
+        raise ValueError(f"{what}: thickness={thickness!r} must be 1, 3 or 5")
     if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3 or 0 in frames.shape \
             or not frames.is_contiguous():
         got = f"{tuple(frames.shape)} {frames.dtype}" if isinstance(frames, torch.Tensor) else type(frames).__name__
-        raise ValueError(f"draw_boxes takes frames as a contiguous (k, h, w, 3) uint8 tensor, got {got}")
+        raise ValueError(f"{what} takes frames as a contiguous (k, h, w, 3) uint8 tensor, got {got}")
     k, h, w = (int(v) for v in frames.shape[:3])
     if not isinstance(projected, dict):
-        raise ValueError(f"draw_boxes takes project_boxes' dict, got {type(projected).__name__}")
+        raise ValueError(f"{what} takes project_boxes' dict, got {type(projected).__name__}")
     edges, edge_mask = projected.get("edges"), projected.get("edge_mask")
     if (not isinstance(edges, torch.Tensor) or not isinstance(edge_mask, torch.Tensor) or edges.dtype != torch.int32 or edge_mask.dtype != torch.int32
             or edges.dim() != 4 or edges.shape[0] != k or edges.shape[1] < 1 or tuple(edges.shape[2:]) != (12, 4)
             or edge_mask.shape != edges.shape[:2] or not edges.is_contiguous() or not edge_mask.is_contiguous()):
-        raise ValueError(f"draw_boxes takes project_boxes' edges ({k}, n, 12, 4) and edge_mask ({k}, n) as contiguous int32 tensors")
+        raise ValueError(f"{what} takes project_boxes' edges ({k}, n, 12, 4) and edge_mask ({k}, n) as contiguous int32 tensors")
     if "window" in projected and tuple(projected["window"][2:]) != (h, w):
-        raise ValueError(f"draw_boxes: the boxes were projected onto a {tuple(projected['window'][2:])} grid, the frames are {(h, w)}")
+        raise ValueError(f"{what}: the boxes were projected onto a {tuple(projected['window'][2:])} grid, the frames are {(h, w)}")
     n = int(edges.shape[1])
     col = colours if isinstance(colours, torch.Tensor) else np.asarray(colours)
     if tuple(col.shape) != (n, 3) or col.dtype != (torch.uint8 if isinstance(col, torch.Tensor) else np.uint8):
-        raise ValueError(f"draw_boxes takes colours as ({n}, 3) uint8, got {tuple(col.shape)} {col.dtype}")
+        raise ValueError(f"{what} takes colours as ({n}, 3) uint8, got {tuple(col.shape)} {col.dtype}")
     if k * h * w * 3 >= 2 ** 31:
-        raise ValueError(f"draw_boxes: {k} frames of {h} x {w} pixels hold 2^31 elements or more")
-    if not frames.is_cuda or edges.device != frames.device or edge_mask.device != frames.device:
+        raise ValueError(f"{what}: {k} frames of {h} x {w} pixels hold 2^31 elements or more")
+    return (k, h, w, n), edges, edge_mask, col
+
+
+def _need_gpu_drawing(frames, *others) -> None:
+    if not frames.is_cuda or any(t.device != frames.device for t in others):
         raise RuntimeError("nerfdet_amd.pipeline: frames and projected boxes must live on the GPU (no CPU fallback)")
+
+
+def _device_colours(col, dev) -> torch.Tensor:
+    return col.to(dev).contiguous() if isinstance(col, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(col)).to(dev)
+
+
+def _glyphs(rows: str) -> list:
+    return [int(v, 16) for v in rows.split()]
+
+
+# 5 x 7 bitmaps of the codes 32..126 in the low five bits of a byte a row, bit 4 leftmost, top row first; index 95 (code 127, and every
+# code the table does not hold) is a full block.  Drawn for this project; the one source of the glyphs: draw_overlay uploads it.
+FONT_5X7 = np.array([_glyphs(g) for g in (
+    "00 00 00 00 00 00 00", "04 04 04 04 04 00 04", "0A 0A 0A 00 00 00 00", "0A 0A 1F 0A 1F 0A 0A",     # space ! " #
+    "04 0F 14 0E 05 1E 04", "18 19 02 04 08 13 03", "0C 12 14 08 15 12 0D", "0C 04 08 00 00 00 00",     # $ % & '
+    "02 04 08 08 08 04 02", "08 04 02 02 02 04 08", "00 04 15 0E 15 04 00", "00 04 04 1F 04 04 00",     # ( ) * +
+    "00 00 00 00 0C 04 08", "00 00 00 1F 00 00 00", "00 00 00 00 00 0C 0C", "00 01 02 04 08 10 00",     # , - . /
+    "0E 11 13 15 19 11 0E", "04 0C 04 04 04 04 0E", "0E 11 01 02 04 08 1F", "1F 02 04 02 01 11 0E",     # 0 1 2 3
+    "02 06 0A 12 1F 02 02", "1F 10 1E 01 01 11 0E", "06 08 10 1E 11 11 0E", "1F 01 02 04 08 08 08",     # 4 5 6 7
+    "0E 11 11 0E 11 11 0E", "0E 11 11 0F 01 02 0C", "00 0C 0C 00 0C 0C 00", "00 0C 0C 00 0C 04 08",     # 8 9 : ;
+    "02 04 08 10 08 04 02", "00 00 1F 00 1F 00 00", "08 04 02 01 02 04 08", "0E 11 01 02 04 00 04",     # < = > ?
+    "0E 11 01 0D 15 15 0E", "0E 11 11 11 1F 11 11", "1E 11 11 1E 11 11 1E", "0E 11 10 10 10 11 0E",     # @ A B C
+    "1C 12 11 11 11 12 1C", "1F 10 10 1E 10 10 1F", "1F 10 10 1E 10 10 10", "0E 11 10 17 11 11 0F",     # D E F G
+    "11 11 11 1F 11 11 11", "0E 04 04 04 04 04 0E", "07 02 02 02 02 12 0C", "11 12 14 18 14 12 11",     # H I J K
+    "10 10 10 10 10 10 1F", "11 1B 15 15 11 11 11", "11 11 19 15 13 11 11", "0E 11 11 11 11 11 0E",     # L M N O
+    "1E 11 11 1E 10 10 10", "0E 11 11 11 15 12 0D", "1E 11 11 1E 14 12 11", "0F 10 10 0E 01 01 1E",     # P Q R S
+    "1F 04 04 04 04 04 04", "11 11 11 11 11 11 0E", "11 11 11 11 11 0A 04", "11 11 11 15 15 15 0A",     # T U V W
+    "11 11 0A 04 0A 11 11", "11 11 11 0A 04 04 04", "1F 01 02 04 08 10 1F", "0E 08 08 08 08 08 0E",     # X Y Z [
+    "00 10 08 04 02 01 00", "0E 02 02 02 02 02 0E", "04 0A 11 00 00 00 00", "00 00 00 00 00 00 1F",     # \ ] ^ _
+    "08 04 02 00 00 00 00", "00 00 0E 01 0F 11 0F", "10 10 16 19 11 11 1E", "00 00 0E 10 10 11 0E",     # ` a b c
+    "01 01 0D 13 11 11 0F", "00 00 0E 11 1F 10 0E", "06 09 08 1C 08 08 08", "00 0F 11 11 0F 01 0E",     # d e f g
+    "10 10 16 19 11 11 11", "04 00 0C 04 04 04 0E", "02 00 06 02 02 12 0C", "10 10 12 14 18 14 12",     # h i j k
+    "0C 04 04 04 04 04 0E", "00 00 1A 15 15 11 11", "00 00 16 19 11 11 11", "00 00 0E 11 11 11 0E",     # l m n o
+    "00 00 1E 11 1E 10 10", "00 00 0D 13 0F 01 01", "00 00 16 19 10 10 10", "00 00 0E 10 0E 01 1E",     # p q r s
+    "08 08 1C 08 08 09 06", "00 00 11 11 11 13 0D", "00 00 11 11 11 0A 04", "00 00 11 11 15 15 0A",     # t u v w
+    "00 00 11 0A 04 0A 11", "00 00 11 11 0F 01 0E", "00 00 1F 02 04 08 1F", "02 04 04 08 04 04 02",     # x y z {
+    "04 04 04 04 04 04 04", "08 04 04 02 04 04 08", "00 00 08 15 02 00 00", "1F 1F 1F 1F 1F 1F 1F",     # | } ~ block
+)], dtype=np.uint8)
+TEXT_MAX = 32      # codes a plate holds
+
+
+def encode_texts(strings) -> tuple:
+    """``(codes (n, 32) uint8, lens (n,) int32)`` of n strings for :func:`draw_overlay`: a string is cut at 32 characters, a character
+    outside 32..126 becomes code 127 (the block glyph); rows are padded with zeros."""
+    if isinstance(strings, (str, bytes)) or not all(isinstance(s, str) for s in strings):
+        raise ValueError("encode_texts takes a sequence of str")
+    strings = list(strings)
+    codes = np.zeros((len(strings), TEXT_MAX), dtype=np.uint8)
+    lens = np.zeros(len(strings), dtype=np.int32)
+    for i, s in enumerate(strings):
+        s = s[:TEXT_MAX]
+        lens[i] = len(s)
+        codes[i, :len(s)] = [ord(c) if 32 <= ord(c) <= 126 else 127 for c in s]
+    return codes, lens
+
+
+OCCLUDED = {"hide": 0, "dim": 1}
+
+
+def check_overlay_options(occluded, depth_bias, text_scale, what: str) -> tuple:
+    """``(ndet_draw_overlay's occluded, bias_mm as np.float32, text_scale)`` of a call's options; ValueError for anything else."""
+    if not isinstance(occluded, str) or occluded not in OCCLUDED:
+        raise ValueError(f"{what}: occluded={occluded!r} must be 'hide' or 'dim'")
+    if not isinstance(depth_bias, (int, float, np.floating, np.integer)) or isinstance(depth_bias, bool) or not 0 <= depth_bias < float("inf"):
+        raise ValueError(f"{what}: depth_bias={depth_bias!r} must be a finite number of metres, not negative")
+    with np.errstate(over="ignore"):
+        bias_mm = np.float32(depth_bias * 1000.0)
+    if not np.isfinite(bias_mm):
+        raise ValueError(f"{what}: depth_bias={depth_bias!r} does not fit float32 millimetres")
+    if isinstance(text_scale, bool) or text_scale not in (1, 2, 3):
+        raise ValueError(f"{what}: text_scale={text_scale!r} must be 1, 2 or 3")
+    return OCCLUDED[occluded], bias_mm, int(text_scale)
+
+
+def draw_overlay(frames: torch.Tensor, projected: dict, colours, thickness: int = 1, depth_frames=None, occluded: str = "hide",
+                 depth_bias: float = 0.05, texts=None, text_scale: int = 1) -> torch.Tensor:
+    """:func:`draw_boxes` with a depth test of the edges and text plates: one launch (ndet_draw_overlay) writes NEW frames.  ``frames``,
+    ``projected``, ``colours`` and ``thickness`` as in :func:`draw_boxes`; with ``depth_frames`` and ``texts`` both None the bytes are its.
+    ``depth_frames`` (k, h, w) uint16 millimetres on the frames' device (0: a hole, which hides nothing) needs ``projected["edge_w"]``
+    (``project_boxes(..., depths=True)``): a covered pixel of an edge is hidden where the depth frame lies more than ``depth_bias`` metres
+    in front of the edge there (``bias_mm = np.float32(depth_bias * 1000.0)``); ``occluded="hide"`` leaves a pixel whose edges are all
+    hidden as it was, ``"dim"`` blends a quarter of the colour in; a visible edge beats a hidden one of any index.  The edge's depth is
+    interpolated from integer cells, so it is off by up to a pixel's worth: the default ``depth_bias`` of 0.05 m is a choice, not a
+    measurement, made to cover that and sensor noise at indoor range.  ``texts``: n strings (:func:`encode_texts`: 32 characters at most);
+    box b gets a filled plate in its colour above its ``projected["rect"]`` carrying its string in :data:`FONT_5X7` at ``text_scale``
+    1, 2 or 3 -- ahead of every edge, the highest box index on top, never depth-tested; no plate for an empty string or a box outside the
+    frame.  One upload for texts, lengths and font.  ValueError for wrong shapes or dtypes before any launch, RuntimeError for CPU tensors."""
+    (k, h, w, n), edges, edge_mask, col = _check_drawing(frames, projected, colours, thickness, "draw_overlay")
+    mode, bias_mm, text_scale = check_overlay_options(occluded, depth_bias, text_scale, "draw_overlay")
+    device_side = [edges, edge_mask]
+    edge_w = rect = None
+    if depth_frames is not None:
+        d, edge_w = depth_frames, projected.get("edge_w")
+        if not isinstance(d, torch.Tensor) or d.dtype != torch.uint16 or tuple(d.shape) != (k, h, w) or not d.is_contiguous():
+            got = f"{tuple(d.shape)} {d.dtype}" if isinstance(d, torch.Tensor) else type(d).__name__
+            raise ValueError(f"draw_overlay takes depth_frames as a contiguous ({k}, {h}, {w}) uint16 tensor (millimetres), got {got}")
+        if not isinstance(edge_w, torch.Tensor) or edge_w.dtype != torch.float32 or tuple(edge_w.shape) != (k, n, 12, 2) or not edge_w.is_contiguous():
+            raise ValueError(f"draw_overlay: a depth test needs project_boxes(..., depths=True)'s edge_w ({k}, {n}, 12, 2) float32")
+        device_side += [d, edge_w]
+    if texts is not None:
+        rect = projected.get("rect")
+        if not isinstance(rect, torch.Tensor) or rect.dtype != torch.int32 or tuple(rect.shape) != (k, n, 4) or not rect.is_contiguous():
+            raise ValueError(f"draw_overlay: text plates need project_boxes' rect ({k}, {n}, 4) int32")
+        codes, lens = encode_texts(texts)
+        if len(lens) != n:
+            raise ValueError(f"draw_overlay: {len(lens)} texts for {n} boxes")
+        device_side.append(rect)
+    _need_gpu_drawing(frames, *device_side)
     dev = frames.device
-    col = col.to(dev).contiguous() if isinstance(col, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(col)).to(dev)
+    col = _device_colours(col, dev)
+    text = text_len = font = None
+    if texts is not None:
+        # one upload: the n lengths (int32), then the n x 32 codes, then the font's 672 bytes
+        buf = torch.from_numpy(np.concatenate([lens.view(np.uint8), codes.reshape(-1), FONT_5X7.reshape(-1)])).to(dev)
+        text_len, text, font = buf, buf[4 * n:], buf[36 * n:]
     out = torch.empty_like(frames)
-    check(_lib.load().ndet_draw_boxes(_ptr(frames), _ptr(edges), _ptr(edge_mask), _ptr(col), k, h, w, n, int(thickness), _ptr(out),
-                                      c_void_p(_lib.raw_stream(dev))), "draw_boxes")
+    check(_lib.load().ndet_draw_overlay(_ptr(frames), _ptr(edges), _ptr(edge_mask), _ptr(col), _ptr(depth_frames), _ptr(edge_w), float(bias_mm), mode,
+                                        _ptr(rect), _ptr(text), _ptr(text_len), _ptr(font), text_scale, k, h, w, n, int(thickness), _ptr(out),
+                                        c_void_p(_lib.raw_stream(dev))), "draw_overlay")
     return out
 
 

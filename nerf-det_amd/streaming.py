@@ -59,7 +59,9 @@ pipeline.frame_ssim: the SSIM per frame from one fused window kernel) and adds n
 list per listed scene) put a detection result into the camera's image: the kept boxes' corners go up in one upload, one launch projects
 them (pipeline.project_boxes, ndet_project_boxes), one draws their wireframes onto frames that lie in device memory (pipeline.draw_boxes,
 ndet_draw_boxes: new frames, the best detection on top) or says which detection each pixel of a depth frame belongs to
-(pipeline.label_frames, ndet_label_frames).  They use the scene's meta only and need no ``keep_views``.
+(pipeline.label_frames, ndet_label_frames).  They use the scene's meta only and need no ``keep_views``.  ``draw_detections(...,
+depth_frames=, occluded=, depth_bias=, text=, text_scale=)`` depth-tests the edges against millimetre depth frames and writes class and
+score on a plate above each box: one ndet_project_boxes_w and one ndet_draw_overlay (pipeline.draw_overlay) in place of the two launches.
 
 ``scene.occupancy(threshold, dilate, outside)`` / ``group.occupancy(..., scenes=)`` make an occupancy grid (rays.OccupancyGrid) from the
 finishes ``volume()`` runs -- the sigma-MLP's alpha at the lattice is the expression compositing applies to a sample -- and
@@ -85,7 +87,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from . import conv3d, ops
+from . import conv3d, ops, pipeline
 from .pipeline import (FRAME_FORMATS, IMG_MEAN, IMG_STD, _host_matrices, camera_rays, check_window, class_palette, depth_to_mm, draw_boxes, frame_errors,
                        SSIM_WINDOW, frame_ssim, label_frames, pack_frames, prepare_depth_frames, prepare_frames, project_boxes, rescale_size,
                        surface_layout)
@@ -313,18 +315,52 @@ def _need_device_frames(plans, what: str) -> None:
         raise RuntimeError(f"{what}: the frames must live on the GPU (no CPU fallback)")
 
 
+def _plan_overlay(p: dict, result, depth_frames, occluded, depth_bias, text, text_scale, what: str) -> None:
+    """The checks of ``draw_detections``' depth test and text plates for one scene's checked plan, before any launch; ``p["overlay"]``
+    becomes None (both absent: the two launches of old) or ``pipeline.draw_overlay``'s keywords, the texts in drawing order."""
+    pipeline.check_overlay_options(occluded, depth_bias, text_scale, what)
+    shape = tuple(p["frames"].shape[:3])
+    d = depth_frames
+    if d is not None and (not isinstance(d, Tensor) or d.dtype != torch.uint16 or tuple(d.shape) != shape or not d.is_contiguous()):
+        got = f"{tuple(d.shape)} {d.dtype}" if isinstance(d, Tensor) else type(d).__name__
+        raise ValueError(f"{what} takes depth_frames on the frames' own grid, a contiguous {shape} uint16 tensor (millimetres), got {got}")
+    texts = None
+    if text is not None:
+        names = None if text is True else text
+        if text is False or (names is not None and (isinstance(names, str) or not isinstance(names, (list, tuple))
+                                                    or not all(isinstance(s, str) for s in names))):
+            raise ValueError(f"{what}: text must be None, True (the label's number) or a list of class names, got {text!r}")
+        kept = p["kept"]
+        scores, labels = (np.asarray(t.detach().cpu() if isinstance(t, Tensor) else t)[kept] for t in (result["scores_3d"], result["labels_3d"]))
+        if names is not None and len(labels) and int(labels.max()) >= len(names):
+            raise ValueError(f"{what}: label {int(labels.max())} has no name among the {len(names)} given")
+        texts = [f"{int(lab) if names is None else names[int(lab)]} {float(s):.2f}" for lab, s in zip(labels, scores)]
+    p["overlay"] = None if d is None and text is None else dict(depth_frames=d, occluded=occluded, depth_bias=depth_bias, texts=texts,
+                                                                  text_scale=text_scale)
+
+
+def _need_device_depth(plans, what: str) -> None:
+    for p in plans:
+        d = p["overlay"]["depth_frames"] if p["overlay"] else None
+        if d is not None and (not d.is_cuda or d.device != p["frames"].device):
+            raise RuntimeError(f"{what}: the depth frames must live on the frames' GPU (no CPU fallback)")
+
+
 def _draw_plan(p: dict, thickness: int) -> dict:
-    """One scene's ``draw_detections`` from its checked plan: one ndet_project_boxes and one ndet_draw_boxes launch, or none when no
-    detection is kept."""
+    """One scene's ``draw_detections`` from its checked plan: one ndet_project_boxes and one ndet_draw_boxes launch -- with a depth test or
+    text plates one ndet_project_boxes_w (ndet_project_boxes without depth frames) and one ndet_draw_overlay -- or none when no detection
+    is kept."""
     from .boxes import box_corners
     frames, k = p["frames"], p["poses"].shape[0]
     kept = torch.from_numpy(p["kept"])
     if len(p["kept"]) == 0:
         return OrderedDict(frames=frames.clone(), rect=torch.empty((k, 0, 4), dtype=torch.int32, device=frames.device),
                            zrange=torch.empty((k, 0, 2), dtype=torch.float32, device=frames.device), kept=kept)
+    over = p.get("overlay")
     proj = project_boxes(p["intrinsic"], box_corners(p["boxes"]), p["window"], p["stride"], c2w=p["c2w"], extrinsic=p["extrinsic"],
-                         device=frames.device)
-    return OrderedDict(frames=draw_boxes(frames, proj, p["colours"], thickness), rect=proj["rect"], zrange=proj["zrange"], kept=kept)
+                         device=frames.device, depths=over is not None and over["depth_frames"] is not None)
+    drawn = draw_boxes(frames, proj, p["colours"], thickness) if over is None else pipeline.draw_overlay(frames, proj, p["colours"], thickness, **over)
+    return OrderedDict(frames=drawn, rect=proj["rect"], zrange=proj["zrange"], kept=kept)
 
 
 def _label_plan(p: dict) -> Tensor:
@@ -1078,7 +1114,8 @@ class SceneStream:
         return _with_counts(_frame_scores(out, held, held_depth, ssim), (out["n_kept"], out["n_samples"]) if "n_kept" in out else None)
 
     def draw_detections(self, frames: Tensor, result: dict, c2w=None, extrinsic=None, window=None, stride: int = 1, capture: bool = False,
-                        score_thr: float = 0.0, thickness: int = 1, palette=None) -> dict:
+                        score_thr: float = 0.0, thickness: int = 1, palette=None, depth_frames=None, occluded: str = "hide",
+                        depth_bias: float = 0.05, text=None, text_scale: int = 1) -> dict:
         """The wireframes of one detection result on k camera frames that lie in device memory.  ``result``: what ``detect()[0]`` returns;
         the detections with ``score >= score_thr`` are kept, handed over by ascending score (boxes.drawing_order: the best one wins every
         pixel it shares) and coloured by label (``palette`` (c,3) uint8 BGR; None: pipeline.class_palette).  Exactly one of ``c2w`` and
@@ -1088,11 +1125,24 @@ class SceneStream:
         ndet_project_boxes and one ndet_draw_boxes launch (pipeline.project_boxes, pipeline.draw_boxes), none when nothing is kept.
         Returns ``dict(frames`` -- new frames, the input is only read -- ``, rect (k,m,4) int32, zrange (k,m,2) float32, kept (m,) int64``:
         the result's indices in drawing order, which is the numbering of ``rect`` and ``zrange``).  Uses the scene's meta only: no
-        ``keep_views``, no state and no bank is changed.  Bad arguments are a ValueError before any launch, CPU frames a RuntimeError."""
+        ``keep_views``, no state and no bank is changed.  Bad arguments are a ValueError before any launch, CPU frames a RuntimeError.
+
+        ``depth_frames`` (k,h,w) uint16 millimetres on the frames' own grid (``capture=True`` included; :meth:`render_frames`'
+        ``depth_frames`` fits, a sensor frame of another size is the caller's to bring there:
+        ``depth_to_mm(prepare_depth_frames(...))``) depth-tests the edges: a covered pixel is hidden where the depth frame lies more than
+        ``depth_bias`` metres in front of the edge (a hole hides nothing); ``occluded="hide"`` leaves hidden pixels as they were,
+        ``"dim"`` blends a quarter of the colour in.  The default ``depth_bias`` of 0.05 m is a choice, not a measurement: it covers the
+        one-pixel error of the edge's interpolated depth and sensor noise at indoor range.  ``text=True`` writes ``f"{label} {score:.2f}"``
+        on a plate in the box's colour above its rectangle, a sequence of class names ``f"{names[label]} {score:.2f}"`` (a label outside
+        it is a ValueError), at ``text_scale`` 1, 2 or 3 (pipeline.FONT_5X7).  With ``depth_frames`` and ``text`` both None the call is
+        the two launches above; otherwise one ndet_project_boxes_w (ndet_project_boxes without depth frames) and one ndet_draw_overlay
+        (pipeline.draw_overlay).  The returned dict is the same."""
         thickness = _check_thickness(thickness, "draw_detections")
         plan = _plan_detections(self.det, self.meta, frames, (3,), torch.uint8, result, c2w, extrinsic, window, stride, capture, score_thr, palette,
                                 "draw_detections")
+        _plan_overlay(plan, result, depth_frames, occluded, depth_bias, text, text_scale, "draw_detections")
         _need_device_frames([plan], "draw_detections")
+        _need_device_depth([plan], "draw_detections")
         return _draw_plan(plan, thickness)
 
     def label_detections(self, depth_frames: Tensor, result: dict, c2w=None, extrinsic=None, window=None, stride: int = 1, capture: bool = False,
@@ -1578,7 +1628,8 @@ class SceneGroup:
                              (out["n_kept"], out["n_samples"]) if "n_kept" in out else None) for i, out in enumerate(outs)]
 
     def _plan_detections(self, frames, results, c2w, extrinsic, scenes, trailing, dtype, window, stride, capture, score_thr, palette, what: str):
-        """The checked plans of a grouped ``draw_detections`` / ``label_detections`` call, one per listed scene; nothing is launched."""
+        """The checked plans of a grouped ``draw_detections`` / ``label_detections`` call, one per listed scene; nothing is launched, and
+        where the tensors live is the caller's to check after its own arguments (``_need_device_frames``)."""
         scenes = ops.listed_scenes(self.n_scenes, scenes)
         given = _camera_lists(c2w, extrinsic, what)
         if isinstance(frames, Tensor) or isinstance(results, dict):
@@ -1588,19 +1639,29 @@ class SceneGroup:
             raise ValueError(f"{what}: {len(frames)} frame tensors, {len(results)} results and {len(given)} camera lists for {len(scenes)} listed scenes")
         plans = [_plan_detections(self.det, self.metas[s], f, trailing, dtype, r, g if c2w is not None else None, g if c2w is None else None,
                                   window, stride, capture, score_thr, palette, what) for s, f, r, g in zip(scenes, frames, results, given)]
-        _need_device_frames(plans, what)
         return plans
 
     def draw_detections(self, frames, results, c2w=None, extrinsic=None, scenes=None, window=None, stride: int = 1, capture: bool = False,
-                        score_thr: float = 0.0, thickness: int = 1, palette=None):
+                        score_thr: float = 0.0, thickness: int = 1, palette=None, depth_frames=None, occluded: str = "hide",
+                        depth_bias: float = 0.05, text=None, text_scale: int = 1):
         """:meth:`SceneStream.draw_detections` for the listed scenes: ``frames``, ``results`` and exactly one of ``c2w`` / ``extrinsic`` are
-        lists with one entry per listed scene (a frames tensor, a ``detect()`` entry, a list of poses; the counts may differ).  Every scene
-        uses its own meta; the other arguments are the call's.  One ndet_project_boxes and one ndet_draw_boxes launch per scene, as
-        ``pack_frames`` and ``frame_errors`` are per scene.  Returns a list of dicts as the stream's method returns them; a group of one scene
-        is the stream bit for bit.  Bad arguments are refused whole, before any launch."""
-        thickness = _check_thickness(thickness, "draw_detections")
-        plans = self._plan_detections(frames, results, c2w, extrinsic, scenes, (3,), torch.uint8, window, stride, capture, score_thr, palette,
-                                      "draw_detections")
+        lists with one entry per listed scene (a frames tensor, a ``detect()`` entry, a list of poses; the counts may differ), and so is
+        ``depth_frames`` when given.  Every scene uses its own meta; the other arguments are the call's.  One ndet_project_boxes and one
+        ndet_draw_boxes launch per scene (with depth frames or text the stream's other two), as ``pack_frames`` and ``frame_errors`` are
+        per scene.  Returns a list of dicts as the stream's method returns them; a group of one scene is the stream bit for bit.  Bad
+        arguments are refused whole, before any launch."""
+        what = "draw_detections"
+        thickness = _check_thickness(thickness, what)
+        if depth_frames is not None and not isinstance(depth_frames, (list, tuple)):
+            raise ValueError(f"{what} takes depth_frames as a list, one tensor per listed scene")
+        plans = self._plan_detections(frames, results, c2w, extrinsic, scenes, (3,), torch.uint8, window, stride, capture, score_thr, palette, what)
+        depths = [None] * len(plans) if depth_frames is None else list(depth_frames)
+        if len(depths) != len(plans):
+            raise ValueError(f"{what}: {len(depths)} depth frame tensors for {len(plans)} listed scenes")
+        for p, r, d in zip(plans, list(results), depths):
+            _plan_overlay(p, r, d, occluded, depth_bias, text, text_scale, what)
+        _need_device_frames(plans, what)
+        _need_device_depth(plans, what)
         return [_draw_plan(p, thickness) for p in plans]
 
     def label_detections(self, depth_frames, results, c2w=None, extrinsic=None, scenes=None, window=None, stride: int = 1, capture: bool = False,
@@ -1609,6 +1670,7 @@ class SceneGroup:
         tensors, one ndet_label_frames launch per scene."""
         plans = self._plan_detections(depth_frames, results, c2w, extrinsic, scenes, (), torch.uint16, window, stride, capture, score_thr, None,
                                       "label_detections")
+        _need_device_frames(plans, "label_detections")
         return [_label_plan(p) for p in plans]
 
     def _volumes(self, scenes: List[int]):
