@@ -576,6 +576,40 @@ int ndet_front_count(const float* pts, int R, int S, int s0, int s1, const float
 int ndet_front_write(const float* pts, int R, int S, int s0, int s1, const float* T, float eps, const uint32_t* bits, const int* n_voxels,
                      const float* p0, const float* vs, int outside, const int* block_first, int* idx, float* pts_kept, void* stream);
 
+/* ---- space carving from depth frames (nerf-det_amd/streaming.py, begin_scene(carve=); the reference has no counterpart).
+ * A FINE lattice of (nx, ny, nz) voxels, n = (ix ny + iy) nz + iz, refines the detection lattice by refine = 1, 2 or 4 per axis (the same
+ * box, the same centre).  Every entry point checks its arguments on the host before any HIP call: a null pointer, a non-positive size,
+ * min_free < 1, dilate outside 0 .. 2, a band that is not finite and positive, a depth dtype other than 0 / 1, pitches smaller than the
+ * map, refine other than 1 / 2 / 4 (with coarse_bits: fine sizes that are no multiples of it) and fewer than 1 or more than
+ * NDET_RING_MAX segments are NDET_E_INVALID; 2^31 voxels or more, more than 2^24 workgroups and a misaligned pointer are
+ * NDET_E_UNSUPPORTED.  Plain vector stores, no atomics: the same bytes on every call.
+ *
+ * ndet_carve_accumulate: adds the evidence of a chunk's k >= 1 views to counts (N) uint32, one word per fine voxel: the FREE count in bits
+ * 0-15, the HIT count in bits 16-31, each saturating at 65535 (integer adds: any chunking of the same views leaves the same bytes).
+ * points (3, nx, ny, nz) the fine lattice (ndet_get_points), proj (k, 3, 4) the chunk's stride-1 projections (DEVICE), depth the chunk's
+ * image-resolution depth maps, element (v, y, x) at v view_pitch + y row_pitch + x, dtype 0 = float32 / 1 = float64, H x W the image.
+ * View v and voxel n: the point goes through the projection of ndet_density_features' RGB gather (k-ordered FMA chain, round-half-even
+ * pixel, in-image and z > 0); a rejected point is no evidence.  Else d = depth[v, y, x]; !(d > 0) -- a hole, a negative, a NaN -- is no
+ * evidence.  Else, in the map's dtype (z widened exactly for float64; band rounded to float32 for float32):
+ *     FREE  iff !(z > d - band)               in front of the surface by at least the band;
+ *     HIT   iff  z > d - band && z < d + band the depth gate's own test (NdetDepthGate, nerfdet.py:404-411);
+ *     else behind the surface: no evidence.
+ * One thread per voxel, the views' loop inside it, one read-modify-write of the voxel's word per launch. */
+int ndet_carve_accumulate(const float* points, int nx, int ny, int nz, const float* proj, int k, const void* depth, int dtype,
+                          int64_t view_pitch, int64_t row_pitch, int H, int W, double band, uint32_t* counts, void* stream);
+
+/* ndet_carve_bits: n_segs (1 .. NDET_RING_MAX) counter buffers, a HOST array of device pointers, -> bits[(N + 31) / 32] in
+ * ndet_occupancy_bits' format (the last word's spare bits are 0), for ndet_cull_* and ndet_front_* to leave samples out of a render
+ * (the reference composites every sample, render_ray.py:196-247).  Per fine voxel free and hit are summed over the segments in 32 bits.
+ * The voxel is EMPTY iff free >= min_free && hit == 0, else SOLID (unseen, behind a surface or on one).  With coarse_bits -- an UNDILATED
+ * grid of ndet_occupancy_bits on the parent lattice (nx, ny, nz) / refine -- a voxel is solid iff it is carve-solid AND bit
+ * ((ix / refine) (ny / refine) + iy / refine) (nz / refine) + iz / refine is set.  Bit n is set iff a voxel within Chebyshev distance
+ * dilate of n, inside the grid, is solid.  scratch: NULL, or (N + 31) / 32 words of the caller's; with scratch and dilate > 0 a first
+ * launch writes the undilated grid there and a second dilates from those bits (the segments are read once a voxel), else every thread
+ * sums the segments over its whole neighbourhood.  Both forms give the same bytes. */
+int ndet_carve_bits(const uint32_t* const* segments, int n_segs, int min_free, int dilate, int nx, int ny, int nz,
+                    const uint32_t* coarse_bits, int refine, uint32_t* scratch, uint32_t* bits, void* stream);
+
 /* A7 exact API form. Replaces Projector.compute(), projection.py:91-151: rgb_feat (P, n_views, 3+d) and
  * mask (P, n_views) fp32 0/1, materialised like the reference. Same inputs as ndet_ray_view_stats. */
 int ndet_project_sample(const float* pts, int n_points, const float* KE, int n_views, float img_h, float img_w,

@@ -141,6 +141,8 @@ SIGNATURES = {
     "ndet_front_blocks": ([c_int64, c_int], c_int64),
     "ndet_front_count": ([_P, c_int, c_int, c_int, c_int, _P, c_float, _P, ctypes.POINTER(c_int), _F3, _F3, c_int, _P, _P], c_int),
     "ndet_front_write": ([_P, c_int, c_int, c_int, c_int, _P, c_float, _P, ctypes.POINTER(c_int), _F3, _F3, c_int, _P, _P, _P, _P], c_int),
+    "ndet_carve_accumulate": ([_P, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int64, c_int64, c_int, c_int, ctypes.c_double, _P, _P], c_int),
+    "ndet_carve_bits": ([ctypes.POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P], c_int),
     "ndet_ray_view_stats_packed_bwd": ([_P, _P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, c_int, c_int64, c_int64, _P, _P], c_int),
     "ndet_project_sample": ([_P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, c_int64, c_int64, c_int64,
                              _P, c_int, c_int, c_int, c_int64, c_int64, _P, _P, _P], c_int),

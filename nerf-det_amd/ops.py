@@ -939,6 +939,99 @@ def occupancy_bits(alpha: Tensor, count: Tensor, n_voxels, threshold: float, dil
     return bits
 
 
+# --------------------------------------------------------------------------------------------
+# space carving from depth frames (csrc/carve_kernels.hip)
+# --------------------------------------------------------------------------------------------
+CARVE_REFINES = (1, 2, 4)
+
+
+def carve_lattice(n_voxels, voxel_size, refine: int):
+    """``(n_voxels_fine, voxel_size_fine)`` of the fine lattice that refines the detection lattice by ``refine`` (1, 2, 4) per axis:
+    ``get_points(r n_voxels, voxel_size / r, origin)``, the same box and centre; ``voxel_size / r`` is taken in float32, where a division
+    by a power of two is exact."""
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or int(refine) not in CARVE_REFINES:
+        raise ValueError(f"carve: refine={refine!r} must be 1, 2 or 4")
+    r = int(refine)
+    nv = [int(v) for v in (n_voxels.tolist() if isinstance(n_voxels, Tensor) else n_voxels)]
+    vs = [float(v) for v in (voxel_size.tolist() if isinstance(voxel_size, Tensor) else voxel_size)]
+    return tuple(r * v for v in nv), tuple(float(np.float32(v) / np.float32(r)) for v in vs)
+
+
+def carve_accumulate(counts: Tensor, points: Tensor, projection: Tensor, gate: DepthGate) -> Tensor:
+    """Add the evidence of a chunk's k views to ``counts`` (N,) int32, one word per voxel of the fine lattice ``points`` (3,X,Y,Z): the
+    free count in bits 0-15, the hit count in bits 16-31, each saturating at 65535.  ``projection`` (k,3,4) the chunk's stride-1
+    projections; ``gate`` the chunk's :class:`DepthGate`, whose image-resolution map ``depth_r`` (k,H,W) and ``band`` are read.  View by
+    view, a voxel the projection accepts at a pixel of depth ``d > 0`` is FREE iff ``not (z > d - band)`` and a HIT iff the gate's own
+    band test holds (include/nerfdet_hip.h).  In place, one k_carve_accumulate launch; returns ``counts``."""
+    _need_gpu(counts, points, projection)
+    d = gate.depth_r
+    assert d is not None, "carve_accumulate: the depth gate has no map at the image's size (ops.depth_gate(..., img_hw=))"
+    assert points.dim() == 4 and points.shape[0] == 3 and points.dtype == torch.float32 and points.is_contiguous(), \
+        f"points must be a contiguous float32 (3,X,Y,Z) lattice, got {tuple(points.shape)}"
+    nx, ny, nz = points.shape[1:]
+    n = nx * ny * nz
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == n, \
+        f"counts must be a contiguous int32 tensor of {n} words, got {tuple(counts.shape)} {counts.dtype}"
+    proj = _f32c(projection)
+    k = proj.shape[0]
+    assert tuple(proj.shape) == (k, 3, 4) and k >= 1 and d.shape[0] == k, f"projection {tuple(projection.shape)} for a {tuple(d.shape)} map"
+    if d.stride(2) != 1:
+        d = d.contiguous()
+    h, w = d.shape[1], d.shape[2]
+    trace.span("k_carve_accumulate", lambda: check(
+        _lib.load().ndet_carve_accumulate(_ptr(points), nx, ny, nz, _ptr(proj), k, _ptr(d), _DEPTH_DTYPES[d.dtype], d.stride(0), d.stride(1), h, w,
+                                          float(gate.band), _ptr(counts), _stream(counts)), "carve_accumulate"),
+        bytes=20 * n + 48 * k + d.element_size() * k * h * w, kind="hbm")
+    return counts
+
+
+CARVE_TWO_PASS = True   # carve_bits with dilate > 0: undilated bits first, then a dilation from the bits (DESIGN.md 21 has the timings)
+
+
+def carve_bits(segments: Sequence[Tensor], n_voxels_fine, min_free: int, dilate: int, coarse_bits: Optional[Tensor] = None, refine: int = 1,
+               two_pass: Optional[bool] = None) -> Tensor:
+    """1 .. 64 counter segments of :func:`carve_accumulate` over one fine lattice -> its dilated occupancy bit grid, ``((N + 31) // 32,)``
+    int32 words in :func:`occupancy_bits`' format.  Free and hit are summed over the segments; a voxel is empty iff ``free >= min_free
+    and hit == 0`` and solid otherwise; with ``coarse_bits`` (an undilated :func:`occupancy_bits` grid of the parent lattice
+    ``n_voxels_fine / refine``) it is solid iff it is carve-solid and its parent's bit is set; a bit is set iff a voxel within Chebyshev
+    distance ``dilate`` is solid.  ``two_pass``: None (``CARVE_TWO_PASS``), or which of the kernel's two forms runs; the bytes are the
+    same.  The same bytes on every call."""
+    segments = list(segments)
+    _need_gpu(*segments, coarse_bits)
+    nv = [int(v) for v in (n_voxels_fine.tolist() if isinstance(n_voxels_fine, Tensor) else n_voxels_fine)]
+    n = nv[0] * nv[1] * nv[2]
+    assert 1 <= len(segments) <= RING_MAX, f"carve_bits takes 1 to {RING_MAX} segments, got {len(segments)}"
+    for s in segments:
+        assert s.dtype == torch.int32 and s.is_contiguous() and s.numel() == n and s.device == segments[0].device, \
+            f"every segment must be a contiguous int32 tensor of {n} words on one device"
+    words = (n + 31) // 32
+    if coarse_bits is not None:
+        r = int(refine)
+        assert r in CARVE_REFINES and all(v % r == 0 for v in nv), f"refine={refine!r} for a {nv} lattice"
+        cw = (n // r ** 3 + 31) // 32
+        assert coarse_bits.dtype == torch.int32 and coarse_bits.is_contiguous() and tuple(coarse_bits.shape) == (cw,), \
+            f"coarse_bits must be a contiguous ({cw},) int32 tensor"
+    dev = segments[0].device
+    bits = torch.empty((words,), dtype=torch.int32, device=dev)
+    two = (CARVE_TWO_PASS if two_pass is None else bool(two_pass)) and int(dilate) > 0
+    scratch = torch.empty((words,), dtype=torch.int32, device=dev) if two else None
+    ptrs = (ctypes.c_void_p * len(segments))(*[s.data_ptr() for s in segments])
+    reads = len(segments) * (1 if two or not dilate else (2 * int(dilate) + 1) ** 3)
+    trace.span("k_carve_bits", lambda: check(
+        _lib.load().ndet_carve_bits(ptrs, len(segments), int(min_free), int(dilate), nv[0], nv[1], nv[2], _ptr(coarse_bits), int(refine),
+                                    _ptr(scratch), _ptr(bits), _stream(bits)), "carve_bits"),
+        bytes=4 * n * reads + 4 * words * (3 if two else 1), kind="hbm")
+    return bits
+
+
+def carve_counts(segments: Sequence[Tensor], n_voxels_fine) -> Tuple[Tensor, Tensor]:
+    """``(free, hit)`` int32 (X,Y,Z) tensors: the segments' counts summed (torch arithmetic; for inspection, not on a hot path)."""
+    nv = [int(v) for v in n_voxels_fine]
+    free = sum((s & 0xffff) for s in segments)
+    hit = sum(((s >> 16) & 0xffff) for s in segments)
+    return free.view(*nv).to(torch.int32), hit.view(*nv).to(torch.int32)
+
+
 def alpha_gate(mean: Tensor, density: Tensor, count: Tensor) -> Tensor:
     """Unfused gating of nerfdet.py:257-261: ``(1-exp(-density)) * mean`` zeroed where count == 0.
     ``mean`` (C,X,Y,Z) contiguous or channels-last (as produced by :func:`backproject_aggregate`)."""

@@ -376,6 +376,60 @@ class OccupancyGrid:
         self.threshold, self.dilate = threshold, dilate
 
 
+class CarveStore:
+    """A carved scene's counter segments (ops.carve_accumulate's words over one fine lattice of ``n`` voxels), oldest first, following the
+    scene's states as a :class:`ViewBank` follows them: :meth:`push`, :meth:`drop_oldest`, :meth:`clear`.  Unwindowed: ONE segment, into
+    which every chunk accumulates.  Windowed: one segment per chunk held.  :meth:`target` hands out the buffer the next chunk's counts
+    go into -- the held segment of an unwindowed store, else a zeroed spare that belongs to no window until it is pushed; a dropped
+    segment is zeroed and kept, so a sliding window allocates nothing once it has slid.  A chunk without depth pushes its target as it
+    is: all zero, no evidence.  4 n bytes a segment."""
+
+    def __init__(self, n: int, device, windowed: bool):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"CarveStore: n={n!r} voxels")
+        self.n, self.device, self.windowed = int(n), device, bool(windowed)
+        self.segments: List[Tensor] = []
+        self._spare: List[Tensor] = []
+
+    def nbytes(self) -> int:
+        """Device bytes owned: the segments held and the spares."""
+        return 4 * self.n * (len(self.segments) + len(self._spare))
+
+    def target(self) -> Tensor:
+        """The (n,) int32 buffer the next chunk's counts are added into; the store is not changed."""
+        if not self.windowed and self.segments:
+            return self.segments[0]
+        return self._spare.pop() if self._spare else torch.zeros((self.n,), dtype=torch.int32, device=self.device)
+
+    def give_back(self, seg: Tensor) -> None:
+        """A target whose chunk failed: zeroed and spare again (an unwindowed store's held segment is never given back)."""
+        if any(seg is s for s in self.segments):
+            raise ValueError("CarveStore.give_back: the segment is held")
+        seg.zero_()
+        self._spare.append(seg)
+
+    def push(self, seg: Tensor) -> None:
+        """The chunk's target joins the store as its newest segment (unwindowed: it is, or becomes, the one segment)."""
+        if seg.dtype != torch.int32 or tuple(seg.shape) != (self.n,):
+            raise ValueError(f"CarveStore.push: a segment is an ({self.n},) int32 tensor, got {tuple(seg.shape)} {seg.dtype}")
+        if not self.windowed and self.segments:
+            if seg is not self.segments[0]:
+                raise ValueError("CarveStore.push: an unwindowed store accumulates into its one segment (target())")
+            return
+        self.segments.append(seg)
+
+    def drop_oldest(self, k_segments: int = 1) -> None:
+        if isinstance(k_segments, bool) or not isinstance(k_segments, int) or not 0 <= k_segments <= len(self.segments):
+            raise ValueError(f"CarveStore.drop_oldest: k={k_segments!r} for {len(self.segments)} segments held")
+        for seg in self.segments[:k_segments]:
+            seg.zero_()
+            self._spare.append(seg)
+        del self.segments[:k_segments]
+
+    def clear(self) -> None:
+        self.drop_oldest(len(self.segments))
+
+
 def cull_points(pts: Tensor, occ: OccupancyGrid):
     """Ordered compaction of ``pts`` (..., 3) against ``occ``: ``(idx (M,) int32, pts_kept (M, 3))``, the flat indices of the kept points
     in ascending order and those points.  Per axis, in float32, ``i = int(floor((x - p0) / voxel_size + 0.5))`` is the nearest lattice
@@ -619,7 +673,8 @@ def mlp_rows_padded(nerf_mlp, pts, ray_d, globalfeat, floor: int):
     launches a call makes depends on its row count: below 192 tiles of 128 rows the bottleneck layer leaves the 128 x 256 tile
     (conv3d.choose_tiling_split), and below some 16 384 rows ATen's 128 -> 3 GEMM of the colour head picks another kernel; both sum in
     another order, and ``rgb`` moves in its last bit (2.4e-7 measured; sigma does not move).  From MLP_STABLE_ROWS rows on a row's
-    result was the same in every call measured (24 575 .. 262 143 rows).  A caller whose row counts fall below that, and who owes the
+    result was the same in every call measured then (24 575 .. 262 143 rows) -- sizes measured, not a guarantee: a later call of exactly
+    132 292 rows moved ``rgb``'s last bit (1.8e-7) against calls of 131 072, 147 456 and 262 144 rows over the same rows.  A caller whose row counts fall below that, and who owes the
     bits of a larger call, pads up to ``min(MLP_STABLE_ROWS, rows of the larger call)``: at that size the call makes the larger call's
     launches or is the larger call's size."""
     n = pts.shape[0]

@@ -586,9 +586,89 @@ def _check_occupancy_knobs(threshold, dilate, outside):
     return float(threshold), int(dilate), outside
 
 
+OCCUPANCY_SOURCES = ("alpha", "depth", "both")
+CARVE_DEFAULTS = dict(refine=2, band=None)
+
+
+def _check_source_knobs(source, min_free):
+    """``occupancy``'s ``source`` and ``min_free`` as ``(source, int min_free)``: 'alpha', 'depth' or 'both', an int from 1 to 65535; else
+    ValueError."""
+    if source not in OCCUPANCY_SOURCES:
+        raise ValueError(f"occupancy: source={source!r} must be 'alpha', 'depth' or 'both'")
+    if isinstance(min_free, bool) or not isinstance(min_free, (int, np.integer)) or not 1 <= min_free <= 65535:
+        raise ValueError(f"occupancy: min_free={min_free!r} must be an int from 1 to 65535")
+    return source, int(min_free)
+
+
+def _carve_knobs(carve, det):
+    """What a ``carve=`` argument of ``begin_scene`` / ``begin_scenes`` asks for, checked before any device work: None (None or False: no
+    carving), or ``(refine, band)`` -- True: ``refine=2`` and the reference gate's band ``voxel_size[2]``; a dict of ``refine`` (1, 2, 4)
+    and ``band`` (None, or a finite positive number of metres).  Else ValueError.  ``det.voxel_size`` is read only when a carve is asked for."""
+    if carve is None or carve is False:
+        return None
+    if carve is True:
+        carve = {}
+    if not isinstance(carve, dict) or not set(carve) <= set(CARVE_DEFAULTS):
+        raise ValueError(f"carve={carve!r} must be None, True or a dict with the keys {sorted(CARVE_DEFAULTS)}")
+    knobs = dict(CARVE_DEFAULTS, **carve)
+    refine, band = knobs["refine"], knobs["band"]
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or int(refine) not in ops.CARVE_REFINES:
+        raise ValueError(f"carve: refine={refine!r} must be 1, 2 or 4")
+    if band is None:
+        band = float(det.voxel_size[2])
+    if isinstance(band, bool) or not isinstance(band, (int, float, np.floating, np.integer)) or not np.isfinite(band) or not band > 0:
+        raise ValueError(f"carve: band={band!r} must be None or a finite positive number")
+    return int(refine), float(band)
+
+
+class SceneCarve:
+    """One scene's carve (``begin_scene(carve=)``): the fine lattice -- ``ops.get_points(r n_voxels, voxel_size / r, origin)`` -- the band, fixed
+    for the scene's life because the counters depend on it, and the rays.CarveStore that follows the scene's states."""
+
+    def __init__(self, det, origin, device, knobs, windowed: bool):
+        from .rays import CarveStore
+        self.refine, self.band = knobs
+        self.n_voxels, self.voxel_size = ops.carve_lattice(det.n_voxels, det.voxel_size, self.refine)
+        self.points = ops.get_points(self.n_voxels, self.voxel_size, origin, device)
+        self.store = CarveStore(self.n_voxels[0] * self.n_voxels[1] * self.n_voxels[2], device, windowed)
+
+    def chunk(self, gate, rgb_proj: Tensor) -> Tensor:
+        """The store's target with a chunk's evidence added: one k_carve_accumulate launch over the chunk's depth gate (its ``depth_r``)
+        and stride-1 projections; without a gate nothing is launched (no evidence).  The store itself is not changed."""
+        seg = self.store.target()
+        if gate is not None:
+            try:
+                ops.carve_accumulate(seg, self.points, rgb_proj, ops.DepthGate(gate.depth_f, gate.depth_r, self.band))
+            except BaseException:
+                if not any(seg is s for s in self.store.segments):
+                    self.store.give_back(seg)
+                raise
+        return seg
+
+    def grid(self, min_free: int, dilate: int, outside: str, coarse_bits=None):
+        """The rays.OccupancyGrid over the fine lattice of the segments held now: one k_carve_bits call."""
+        from .rays import OccupancyGrid
+        bits = ops.carve_bits(self.store.segments, self.n_voxels, min_free, dilate, coarse_bits, self.refine)
+        return OccupancyGrid(bits, self.n_voxels, self.points[:, 0, 0, 0].cpu(), np.float32(self.voxel_size), outside, None, dilate)
+
+
+def _need_carve(carve, source: str, what: str):
+    if source != "alpha" and carve is None:
+        raise ValueError(f"{what}: source={source!r} needs a carved scene: begin_scene(img_meta, carve=True)")
+
+
+def _grid_refine(grid_n_voxels, n_voxels):
+    """r in (1, 2, 4) with ``grid_n_voxels == r * n_voxels`` on all three axes, or None."""
+    for r in ops.CARVE_REFINES:
+        if tuple(grid_n_voxels) == tuple(r * v for v in n_voxels):
+            return r
+    return None
+
+
 def _skip_knobs(skip_empty, det, device, what: str):
     """What a ``skip_empty=`` argument asks for, checked before any launch: None (no culling: None or False), a dict of ``occupancy``'s
-    keywords (True: the defaults), or the caller's rays.OccupancyGrid, whose lattice must be the detector's.  Else ValueError."""
+    keywords (True: the defaults; ``source`` and ``min_free`` are carried only when given), or the caller's rays.OccupancyGrid, whose
+    lattice must be the detector's or refine it by 2 or 4 on all three axes.  Else ValueError."""
     if skip_empty is None or skip_empty is False:
         return None
     from .rays import OccupancyGrid
@@ -596,16 +676,19 @@ def _skip_knobs(skip_empty, det, device, what: str):
         return dict(SKIP_EMPTY_DEFAULTS)
     if isinstance(skip_empty, OccupancyGrid):
         n_voxels = tuple(int(v) for v in det.n_voxels)
-        if tuple(skip_empty.n_voxels) != n_voxels:
-            raise ValueError(f"{what}: the grid's n_voxels {tuple(skip_empty.n_voxels)} differ from the scene's {n_voxels}")
+        if _grid_refine(skip_empty.n_voxels, n_voxels) is None:
+            raise ValueError(f"{what}: the grid's n_voxels {tuple(skip_empty.n_voxels)} are not 1, 2 or 4 times the scene's {n_voxels}")
         if not skip_empty.bits.is_cuda or skip_empty.bits.device != device:
             raise RuntimeError(f"{what}: the grid's bits must live on the scene's GPU (no CPU fallback)")
         return skip_empty
     if isinstance(skip_empty, dict):
-        if not set(skip_empty) <= set(SKIP_EMPTY_DEFAULTS):
-            raise ValueError(f"{what}: skip_empty takes the keys {sorted(SKIP_EMPTY_DEFAULTS)}, got {sorted(skip_empty)}")
+        if not set(skip_empty) <= set(SKIP_EMPTY_DEFAULTS) | {"source", "min_free"}:
+            raise ValueError(f"{what}: skip_empty takes the keys {sorted(SKIP_EMPTY_DEFAULTS) + ['min_free', 'source']}, got {sorted(skip_empty)}")
         knobs = dict(SKIP_EMPTY_DEFAULTS, **skip_empty)
         knobs["threshold"], knobs["dilate"], knobs["outside"] = _check_occupancy_knobs(knobs["threshold"], knobs["dilate"], knobs["outside"])
+        if "source" in knobs or "min_free" in knobs:
+            source, min_free = _check_source_knobs(knobs.get("source", "alpha"), knobs.get("min_free", 2))
+            knobs.update({k: v for k, v in (("source", source), ("min_free", min_free)) if k in knobs})
         return knobs
     raise ValueError(f"{what}: skip_empty={skip_empty!r} must be None, True, a dict of occupancy()'s keywords or a rays.OccupancyGrid")
 
@@ -809,15 +892,17 @@ class SceneStream:
     keep the views' mapped maps, images and cameras (``bank``, a rays.ViewBank) so that :meth:`render_rays` / :meth:`render` work."""
 
     bank = None     # rays.ViewBank with keep_views, else None
-    _occ = None     # (threshold, dilate, outside) -> rays.OccupancyGrid of the views held now, made by occupancy(); dropped by _drop_grids()
+    _occ = None     # (threshold, dilate, outside[, source, min_free]) -> rays.OccupancyGrid of the views held now, made by occupancy(); dropped by _drop_grids()
+    carve = None    # SceneCarve with begin_scene(carve=), else None
     mean, std = IMG_MEAN, IMG_STD     # img_norm_cfg of add_frames (RGB)
 
-    def __init__(self, det, img_meta: dict, window: Optional[int] = None, keep_views: bool = False, mean=IMG_MEAN, std=IMG_STD):
+    def __init__(self, det, img_meta: dict, window: Optional[int] = None, keep_views: bool = False, mean=IMG_MEAN, std=IMG_STD, carve=None):
         self.mean, self.std = _norm_cfg(mean, std)
         if not isinstance(keep_views, bool):
             raise ValueError(f"keep_views must be a bool, got {keep_views!r}")
         if window is not None:
             ops.check_window(window)
+        carve = _carve_knobs(carve, det)
         if det.training:
             raise RuntimeError("SceneStream is inference only: call det.eval() first")
         if det.render_testing and not keep_views:
@@ -838,6 +923,8 @@ class SceneStream:
         if keep_views:
             from .rays import ViewBank
             self.bank = ViewBank()
+        if carve is not None:
+            self.carve = SceneCarve(det, img_meta["lidar2img"]["origin"], self.device, carve, window is not None)
 
     @property
     def chunk_views(self) -> List[int]:
@@ -865,6 +952,8 @@ class SceneStream:
             self.state.reset()
             if self.bank is not None:
                 self.bank.clear()
+            if self.carve is not None:
+                self.carve.store.clear()
         else:
             self.drop_oldest(len(self._segs))
 
@@ -881,23 +970,34 @@ class SceneStream:
         del self._segs[:k]
         if self.bank is not None:
             self.bank.drop_oldest(k)
+        if self.carve is not None:
+            self.carve.store.drop_oldest(k)
 
     def _accumulate(self, *chunk, depth_gate=None, banked=None) -> None:
         """Fold a chunk into the scene's state, or in a window into an empty state that joins the window once it is filled; only then does
         the oldest chunk leave a full window.  A chunk that fails leaves the window as it was (its state goes back, zeroed).  ``banked``:
         the chunk's view-bank segment, made by the caller (rays.ViewBank.make_segment changes nothing); it joins the bank once the
-        states have taken the chunk, so states and bank hold the same chunks."""
+        states have taken the chunk, so states and bank hold the same chunks.  A carved scene's counters (SceneCarve.chunk: the chunk's
+        depth gate and stride-1 projection, the last of ``chunk``) follow the same rule: a windowed scene's are made in a spare segment
+        beside the state and join the store with it; an unwindowed scene's are added to its one segment once the state has taken the
+        chunk."""
         self._drop_grids()
+        carve = self.carve
         if self.window is None:
             ops.scene_accumulate(self.state, *chunk, depth_gate=depth_gate)
             if banked is not None:
                 self.bank.push(banked)
+            if carve is not None:
+                carve.store.push(carve.chunk(depth_gate, chunk[-1]))
             return
         lin = self._lin
         # a sliding window therefore owns S + 1 states: the chunk that leaves hands its (zeroed) state to the chunk after the next
         st = self._spare.pop() if self._spare else ops.SceneState(self.det.n_voxels, lin.in_features, lin.out_features, self.device)
+        cseg = None
         try:
             ops.scene_accumulate(st, *chunk, depth_gate=depth_gate)
+            if carve is not None:
+                cseg = carve.chunk(depth_gate, chunk[-1])
         except BaseException:
             st.reset()
             self._spare.append(st)
@@ -907,6 +1007,8 @@ class SceneStream:
         self._segs.append(st)
         if banked is not None:
             self.bank.push(banked)
+        if cseg is not None:
+            carve.store.push(cseg)
 
     def _check_meta(self, img_meta: dict, k: int) -> None:
         check_chunk_meta(self.meta, img_meta, k)
@@ -1171,7 +1273,15 @@ class SceneStream:
             alpha = _finished_alpha(self.det.nerf_mlp, self.points, glob)
             return (alpha,) + (ops.volume_finish_ring(self._segs, alpha) if ring else ops.volume_finish(self.state, alpha))
 
-    def occupancy(self, threshold: float = 1e-3, dilate: int = 1, outside: str = "keep"):
+    def carve_counts(self):
+        """``(free, hit)`` int32 (X,Y,Z) tensors over the carve's fine lattice: the counts of the chunks held now, for inspection.  Needs
+        ``begin_scene(carve=)`` (else ValueError); no chunk held: zeros."""
+        if self.carve is None:
+            raise ValueError("carve_counts needs a carved scene: begin_scene(img_meta, carve=True)")
+        segs = self.carve.store.segments or [torch.zeros((self.carve.store.n,), dtype=torch.int32, device=self.device)]
+        return ops.carve_counts(segs, self.carve.n_voxels)
+
+    def occupancy(self, threshold: float = 1e-3, dilate: int = 1, outside: str = "keep", *, source: str = "alpha", min_free: int = 2):
         """The scene's occupancy grid (rays.OccupancyGrid) over the views held now, from the stream's own finishes -- density finish, the
         sigma-MLP's alpha, ``volume_finish``'s ``valid``: exactly what :meth:`volume` runs -- and one k_occupancy_bits launch.  A voxel is
         solid iff ``not (alpha <= threshold)`` or no view saw it; a bit is set iff a voxel within Chebyshev distance ``dilate`` (0, 1, 2)
@@ -1179,16 +1289,34 @@ class SceneStream:
         ``1 - exp(-relu(sigma))`` of the same ``nerf_mlp`` that compositing applies to a sample, so the two compare directly.  The
         default threshold is a GUESS: nobody has judged it on a trained checkpoint.  The grid is as coarse as the detection lattice.
 
-        Cached per ``(threshold, dilate, outside)`` and dropped by whatever changes the views held (``add_views``, ``add_frames``, an
-        eviction, ``drop_oldest``, ``reset``).  No views held: RuntimeError; bad knobs: ValueError, before any launch."""
+        ``source``: 'alpha' (the above), 'depth' or 'both'; the last two need ``begin_scene(carve=)`` (else ValueError).  'depth': the grid
+        carved from the depth frames of the chunks held, over the carve's FINE lattice -- a fine voxel is empty iff at least
+        ``min_free`` views saw it in front of their surface by the band or more and none saw it on a surface, and solid otherwise (unseen,
+        behind a surface, on one); ``dilate`` counts fine voxels; one k_carve_bits call, no MLP, ``threshold`` is not used.  'both': solid
+        iff carve-solid AND the parent detection voxel is solid in the undilated alpha grid; dilation follows on the fine lattice.  Whether
+        a carved grid helps on a real scene is yours to judge: :meth:`score_frames` with and without it.
+
+        Cached per ``(threshold, dilate, outside)`` and, for the other sources, ``source`` and ``min_free``; dropped by whatever changes
+        the views held (``add_views``, ``add_frames``, an eviction, ``drop_oldest``, ``reset``).  No views held: RuntimeError; bad knobs:
+        ValueError, before any launch."""
         key = _check_occupancy_knobs(threshold, dilate, outside)
+        source, min_free = _check_source_knobs(source, min_free)
+        _need_carve(self.carve, source, "occupancy")
         if self.n_views == 0:
             raise RuntimeError("the scene has no views yet: call add_views first")
         if self._occ is None:
             self._occ = {}
+        if source != "alpha":
+            key = key + (source, min_free)
         if key not in self._occ:
-            alpha, _, valid = self._finish()
-            self._occ[key] = _make_occupancy(alpha, valid, self.points, self.det.n_voxels, self.det.voxel_size, *key)
+            if source == "depth":
+                self._occ[key] = self.carve.grid(min_free, key[1], key[2])
+            else:
+                alpha, _, valid = self._finish()
+                if source == "alpha":
+                    self._occ[key] = _make_occupancy(alpha, valid, self.points, self.det.n_voxels, self.det.voxel_size, *key)
+                else:
+                    self._occ[key] = self.carve.grid(min_free, key[1], key[2], ops.occupancy_bits(alpha, valid, self.det.n_voxels, key[0], 0))
         return self._occ[key]
 
     def _skip_grid(self, skip_empty, what: str, *tensors):
@@ -1260,15 +1388,17 @@ class SceneGroup:
     pool = None         # ops.SceneGroupRingState of a windowed group
     group = None        # ops.SceneGroupState of an unwindowed one
     banks = None        # with keep_views one rays.ViewBank per scene, else None
-    _occ = None         # per scene (threshold, dilate, outside) -> rays.OccupancyGrid of the views it holds now, made by occupancy()
+    _occ = None         # per scene (threshold, dilate, outside[, source, min_free]) -> rays.OccupancyGrid of the views it holds now, made by occupancy()
+    carves = None       # with begin_scenes(carve=) one SceneCarve per scene (one refine and band for the group), else None
     mean, std = IMG_MEAN, IMG_STD     # img_norm_cfg of add_frames (RGB)
 
-    def __init__(self, det, img_metas, window: Optional[int] = None, keep_views: bool = False, mean=IMG_MEAN, std=IMG_STD):
+    def __init__(self, det, img_metas, window: Optional[int] = None, keep_views: bool = False, mean=IMG_MEAN, std=IMG_STD, carve=None):
         self.mean, self.std = _norm_cfg(mean, std)
         if not isinstance(keep_views, bool):
             raise ValueError(f"keep_views must be a bool, got {keep_views!r}")
         if window is not None:
             ops.check_window(window)
+        carve = _carve_knobs(carve, det)
         metas = list(img_metas)
         if not 1 <= len(metas) <= ops.GROUP_MAX:
             raise ValueError(f"begin_scenes takes 1 to {ops.GROUP_MAX} scenes, got {len(metas)}")
@@ -1292,6 +1422,8 @@ class SceneGroup:
         if keep_views:
             from .rays import ViewBank
             self.banks = [ViewBank() for _ in metas]
+        if carve is not None:
+            self.carves = [SceneCarve(det, m["lidar2img"]["origin"], self.device, carve, window is not None) for m in metas]
 
     @staticmethod
     def _check_shapes(first: dict, metas) -> None:
@@ -1337,6 +1469,8 @@ class SceneGroup:
                 self.pool.drop_oldest(len(self.pool.segs[s]), [s])
             if self.banks is not None:
                 self.banks[s].clear()
+            if self.carves is not None:
+                self.carves[s].store.clear()
 
     def drop_oldest(self, k: int = 1, scenes=None) -> None:
         """Forget the k oldest chunks of every listed scene of a windowed group (their states are zeroed and kept for the chunks to come).
@@ -1349,27 +1483,64 @@ class SceneGroup:
         if self.banks is not None:
             for s in scenes:
                 self.banks[s].drop_oldest(k)
+        if self.carves is not None:
+            for s in scenes:
+                self.carves[s].store.drop_oldest(k)
+
+    def _carve_chunks(self, scenes, depth_gate, rgb_proj: Tensor) -> list:
+        """Every listed scene's carve target with its chunk's evidence added (SceneCarve.chunk over the scene's k views of the call's gate
+        and stride-1 projections: one k_carve_accumulate launch a scene); no store is changed.  When a scene's launch is refused, the
+        targets made so far go back."""
+        k = rgb_proj.shape[0] // len(scenes)
+        segs = []
+        try:
+            for i, s in enumerate(scenes):
+                sl = slice(i * k, (i + 1) * k)
+                g = None if depth_gate is None else ops.DepthGate(depth_gate.depth_f[sl], depth_gate.depth_r[sl], depth_gate.band)
+                segs.append(self.carves[s].chunk(g, rgb_proj[sl]))
+        except BaseException:
+            if self.window is not None:
+                for s, seg in zip(scenes, segs):
+                    self.carves[s].store.give_back(seg)
+            raise
+        return segs
 
     def _accumulate(self, scenes, *chunk, depth_gate=None, banked=None) -> None:
         """Fold one chunk per listed scene into the scenes' states, or in a windowed group into empty states that join the scenes' windows
         once the grouped accumulate has succeeded (ops.SceneGroupRingState.accumulate): a call that fails leaves every window as it was.
         ``banked``: the listed scenes' view-bank segments, made by the caller (rays.ViewBank.make_segment changes nothing); they join
         their banks only once the states have taken the chunks, and a scene's oldest segment leaves with the oldest state of its full
-        window, so states and banks hold the same chunks."""
+        window, so states and banks hold the same chunks.  Carved scenes' counter segments (:meth:`_carve_chunks`) follow the same rule:
+        in a windowed group they are made inside the grouped accumulate's transaction and join their stores with the states; in an
+        unwindowed one they are added to the scenes' segments once the states have taken the chunks."""
         self._drop_grids(scenes)
+        carved = None
         if self.window is None:
             ops.scene_accumulate_group(self.group, scenes, *chunk, depth_gate=depth_gate)
+            if self.carves is not None:
+                carved = self._carve_chunks(scenes, depth_gate, chunk[-1])
         else:
             full = [len(self.pool.segs[s]) == self.window for s in scenes]
-            self.pool.accumulate(scenes, lambda states: ops.scene_accumulate_group_ring(self.pool, scenes, *chunk, depth_gate=depth_gate,
-                                                                                       states=states))
-            if banked is not None:
-                for s, was_full in zip(scenes, full):
-                    if was_full:
+
+            def fill(states):
+                nonlocal carved
+                ops.scene_accumulate_group_ring(self.pool, scenes, *chunk, depth_gate=depth_gate, states=states)
+                if self.carves is not None:
+                    carved = self._carve_chunks(scenes, depth_gate, chunk[-1])
+
+            self.pool.accumulate(scenes, fill)
+            for s, was_full in zip(scenes, full):
+                if was_full:
+                    if banked is not None:
                         self.banks[s].drop_oldest(1)
+                    if carved is not None:
+                        self.carves[s].store.drop_oldest(1)
         if banked is not None:
             for s, seg in zip(scenes, banked):
                 self.banks[s].push(seg)
+        if carved is not None:
+            for s, seg in zip(scenes, carved):
+                self.carves[s].store.push(seg)
 
     def _check_call(self, img: Tensor, denorm_images: Tensor, metas, scenes, depth):
         """Everything add_views refuses, before anything is launched: ``(listed scenes, k)``."""
@@ -1691,24 +1862,50 @@ class SceneGroup:
         alpha = _finished_alpha(self.det.nerf_mlp, pts, glob)
         return (alpha,) + (ops.volume_finish_group_ring(self.pool, alpha, scenes) if ring else ops.volume_finish_group(self.group, alpha, scenes))
 
-    def occupancy(self, threshold: float = 1e-3, dilate: int = 1, outside: str = "keep", scenes=None):
+    def carve_counts(self, scenes=None):
+        """Per listed scene :meth:`SceneStream.carve_counts`' ``(free, hit)``.  Needs ``begin_scenes(carve=)`` (else ValueError)."""
+        if self.carves is None:
+            raise ValueError("carve_counts needs carved scenes: begin_scenes(img_metas, carve=True)")
+        out = []
+        for s in ops.listed_scenes(self.n_scenes, scenes):
+            c = self.carves[s]
+            out.append(ops.carve_counts(c.store.segments or [torch.zeros((c.store.n,), dtype=torch.int32, device=self.device)], c.n_voxels))
+        return out
+
+    def occupancy(self, threshold: float = 1e-3, dilate: int = 1, outside: str = "keep", scenes=None, *, source: str = "alpha",
+                  min_free: int = 2):
         """:meth:`SceneStream.occupancy` for the listed scenes: a list of rays.OccupancyGrid, each scene's own, from ONE run of the grouped
         finishes :meth:`volume` runs over the listed scenes that have no cached grid for these knobs, and one k_occupancy_bits launch
-        each.  A scene's grid is cached per ``(threshold, dilate, outside)`` until ``add_views`` / ``add_frames``, an eviction,
-        ``drop_oldest`` or ``reset`` lists the scene.  ValueError for bad knobs or a listed scene without views, before any launch."""
+        each.  ``source='depth'`` runs no finish and no MLP: one k_carve_bits call per listed scene over its own counter segments;
+        ``'both'`` runs the finishes and ANDs each scene's carve with its undilated alpha grid.  Both need ``begin_scenes(carve=)``.  A
+        scene's grid is cached per ``(threshold, dilate, outside)`` -- and ``source``, ``min_free`` for the carved ones -- until
+        ``add_views`` / ``add_frames``, an eviction, ``drop_oldest`` or ``reset`` lists the scene.  ValueError for bad knobs or a listed
+        scene without views, before any launch."""
         key = _check_occupancy_knobs(threshold, dilate, outside)
+        source, min_free = _check_source_knobs(source, min_free)
+        _need_carve(self.carves, source, "occupancy")
         scenes = self._need_views(scenes)
         if self._occ is None:
             self._occ = [{} for _ in self.metas]
+        thr, dil, out = key
+        if source != "alpha":
+            key = key + (source, min_free)
         todo = [s for s in scenes if key not in self._occ[s]]
-        if todo:
+        if todo and source == "depth":
+            for s in todo:
+                self._occ[s][key] = self.carves[s].grid(min_free, dil, out)
+        elif todo:
             points = self.pool.points if self.window is not None else self.group.points
             with torch.no_grad():
                 alpha, _, valid = self._finishes(todo)
             n = alpha.numel() // len(todo)
             for i, s in enumerate(todo):
-                self._occ[s][key] = _make_occupancy(alpha[i * n:(i + 1) * n], valid[i], points[s].view(3, *[int(v) for v in self.det.n_voxels]),
-                                                    self.det.n_voxels, self.det.voxel_size, *key)
+                if source == "alpha":
+                    self._occ[s][key] = _make_occupancy(alpha[i * n:(i + 1) * n], valid[i], points[s].view(3, *[int(v) for v in self.det.n_voxels]),
+                                                        self.det.n_voxels, self.det.voxel_size, *key)
+                else:
+                    coarse = ops.occupancy_bits(alpha[i * n:(i + 1) * n], valid[i], self.det.n_voxels, thr, 0)
+                    self._occ[s][key] = self.carves[s].grid(min_free, dil, out, coarse)
         return [self._occ[s][key] for s in scenes]
 
     def _skip_grids(self, skip_empty, scenes: List[int], batched: bool, what: str, *tensors):
