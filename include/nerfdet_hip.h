@@ -610,6 +610,53 @@ int ndet_carve_accumulate(const float* points, int nx, int ny, int nz, const flo
 int ndet_carve_bits(const uint32_t* const* segments, int n_segs, int min_free, int dilate, int nx, int ny, int nz,
                     const uint32_t* coarse_bits, int refine, uint32_t* scratch, uint32_t* bits, void* stream);
 
+/* ---- points out: a voxel-downsampled point cloud of a streamed RGB-D scene (nerf-det_amd/streaming.py, begin_scene(cloud=); DESIGN.md
+ * 22; the reference has no counterpart).  The FINE lattice is the carve's: (nx, ny, nz) voxels, n = (ix ny + iy) nz + iz, first point p0,
+ * voxel size vs (HOST float[3] each).  A voxel's record is 8 uint32 words, 32 bytes: n, sum qx, sum qy, sum qz, sum b, sum g, sum r and
+ * one spare word that is never written.  Every entry point checks its arguments on the host before any HIP call: a null pointer, a
+ * non-positive size, a depth dtype other than 0 / 1, pitches smaller than the map or the planes, a voxel size that is not finite and
+ * positive, an origin that is not finite, a NaN max_depth, min_points < 1 and fewer than 1 or more than NDET_RING_MAX segments are
+ * NDET_E_INVALID; 2^31 voxels or points or more, 2^24 workgroups or more, k H W >= 2^24 pixels in one launch, a misaligned pointer and
+ * more than 32767 boxes are NDET_E_UNSUPPORTED.
+ *
+ * ndet_cloud_accumulate: adds the k >= 1 views of a chunk to sums (N, 8).  depth: the chunk's image-resolution maps, element (v, y, x) at
+ * v view_pitch + y row_pitch + x, dtype 0 = float32 / 1 = float64; rgb: the B, G, R float planes in [0, 1], element (v, c, y, x) at
+ * v rgb_view_pitch + c rgb_plane_pitch + y rgb_row_pitch + x; intrinsic_rows (2,3), camrotc2w (k,3,3), cam_lightpos (k,3) DEVICE, as
+ * ndet_camera_rays takes them.  Pixel (v, xi, yi), d = (float) the map's value, contributes iff d > 0, d is finite and (max_depth <= 0 or
+ * d <= max_depth).  Its point is the camera centre plus d times ndet_camera_rays' direction of the pixel (get_dtu_raydir,
+ * mmdet3d/datasets/pipelines/data_augment_utils.py:410-424; the reference itself uses a depth map only in the gate of
+ * nerfdet.py:404-411), in ndet_label_frames' float32
+ * statements (pt_j = fmaf(d, dir_j, centre_j)).  Per axis, in float32, t = (x - p0) / vs + 0.5f, i = floorf(t), frac = t - i -- the
+ * voxel whose bit ndet_cull_* reads for the point; a point with an index out of range or a coordinate that is not finite is dropped;
+ * q = min((int)(frac * 256.0f), 255).  A colour byte is ndet_pack_frames' (x 255 rounded half up, saturated, NaN -> 0).  The voxel's
+ * record takes n += 1, the three q and the three bytes, by integer atomics: any chunking and any arrival order leave the same bytes; a
+ * sum of bytes stays exact below 2^24 contributions, which the caller keeps track of.  One thread per pixel.  merge != 0: a wave sums
+ * the values of its lanes that share a voxel before it touches memory; merge == 0: every lane adds its own.  The same bytes. */
+int ndet_cloud_accumulate(const void* depth, int dtype, int64_t view_pitch, int64_t row_pitch, const float* rgb, int64_t rgb_view_pitch,
+                          int64_t rgb_plane_pitch, int64_t rgb_row_pitch, const float* intrinsic_rows, const float* camrotc2w,
+                          const float* cam_lightpos, int k, int H, int W, const float* p0, const float* vs, int nx, int ny, int nz,
+                          float max_depth, int merge, uint32_t* sums, void* stream);
+
+/* ndet_cloud_count / ndet_cloud_write: ordered compaction of n_segs (1 .. NDET_RING_MAX) record buffers, a HOST array of device pointers,
+ * over the fine lattice (ndet_get_points' of nerfdet.py:380-390, refined; the reference's only 3-D output is its list of boxes).
+ * Per fine voxel every field is summed over the segments in 64 bits; the voxel is emitted iff n >= min_points.  ndet_cloud_count writes
+ * block_count[ndet_cloud_blocks(N)], the emitted voxels of every 512 consecutive ones; the caller turns them into exclusive prefix sums
+ * (block_first) and M, their total.  ndet_cloud_write then writes, for the emitted voxels in ascending flat index:
+ *     xyz (M,3)   per axis (float)((double)p0 + (double)vs * ((double)i - 0.5 + ((double)sum_q + 0.5 n) / (256.0 n)));
+ *     bgr (M,3)   per channel (2 sum_c + n) / (2 n) in integers;
+ *     count (M)   n, saturated to int32;  voxel (M)  the flat index.
+ * No atomics: the same bytes on every call. */
+int64_t ndet_cloud_blocks(int64_t n_voxels);
+int ndet_cloud_count(const uint32_t* const* segments, int n_segs, int nx, int ny, int nz, const float* p0, const float* vs, int min_points,
+                     int* block_count, void* stream);
+int ndet_cloud_write(const uint32_t* const* segments, int n_segs, int nx, int ny, int nz, const float* p0, const float* vs, int min_points,
+                     const int* block_first, float* xyz, uint8_t* bgr, int* count, int* voxel, void* stream);
+
+/* ndet_label_points: labels[p] = the highest index among the n <= 32767 box_frames rows (centre, half extents, cos yaw, sin yaw) that hold
+ * point p of points (n_points, 3), -1 for none: ndet_label_frames' test -- the inverse of the corners' yaw,
+ * mmdet3d/core/bbox/structures/depth_box3d.py:46-84 -- on a point that the caller has already. */
+int ndet_label_points(const float* points, int64_t n_points, const float* box_frames, int n, int16_t* labels, void* stream);
+
 /* A7 exact API form. Replaces Projector.compute(), projection.py:91-151: rgb_feat (P, n_views, 3+d) and
  * mask (P, n_views) fp32 0/1, materialised like the reference. Same inputs as ndet_ray_view_stats. */
 int ndet_project_sample(const float* pts, int n_points, const float* KE, int n_views, float img_h, float img_w,

@@ -143,6 +143,12 @@ SIGNATURES = {
     "ndet_front_write": ([_P, c_int, c_int, c_int, c_int, _P, c_float, _P, ctypes.POINTER(c_int), _F3, _F3, c_int, _P, _P, _P, _P], c_int),
     "ndet_carve_accumulate": ([_P, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int64, c_int64, c_int, c_int, ctypes.c_double, _P, _P], c_int),
     "ndet_carve_bits": ([ctypes.POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P], c_int),
+    "ndet_cloud_accumulate": ([_P, c_int, c_int64, c_int64, _P, c_int64, c_int64, c_int64, _P, _P, _P, c_int, c_int, c_int, _F3, _F3, c_int, c_int,
+                               c_int, c_float, c_int, _P, _P], c_int),
+    "ndet_cloud_blocks": ([c_int64], c_int64),
+    "ndet_cloud_count": ([ctypes.POINTER(_P), c_int, c_int, c_int, c_int, _F3, _F3, c_int, _P, _P], c_int),
+    "ndet_cloud_write": ([ctypes.POINTER(_P), c_int, c_int, c_int, c_int, _F3, _F3, c_int, _P, _P, _P, _P, _P, _P], c_int),
+    "ndet_label_points": ([_P, c_int64, _P, c_int, _P, _P], c_int),
     "ndet_ray_view_stats_packed_bwd": ([_P, _P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, c_int, c_int64, c_int64, _P, _P], c_int),
     "ndet_project_sample": ([_P, c_int, _P, c_int, c_float, c_float, _P, c_int, c_int, c_int64, c_int64, c_int64,
                              _P, c_int, c_int, c_int, c_int64, c_int64, _P, _P, _P], c_int),

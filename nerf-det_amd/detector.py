@@ -269,7 +269,7 @@ class nerfdet(BaseDetector):
         trace.mark("head_nms")
         return res
 
-    def begin_scene(self, img_meta, window=None, keep_views=False, mean=IMG_MEAN, std=IMG_STD, carve=None):
+    def begin_scene(self, img_meta, window=None, keep_views=False, mean=IMG_MEAN, std=IMG_STD, carve=None, cloud=None):
         """A :class:`~nerfdet_amd.streaming.SceneStream` for one scene whose views arrive in chunks: ``add_views`` runs the backbone on a
         chunk and folds it into the scene's running sums, ``detect`` returns what :meth:`simple_test` returns for the views so far.  ``window=S`` keeps
         the last S chunks only (a sliding window; ``drop_oldest`` forgets chunks explicitly).  ``keep_views=True`` also keeps the views' mapped maps,
@@ -279,12 +279,16 @@ class nerfdet(BaseDetector):
         ``carve``: None (the default: every launch and every bit as without the keyword), True or ``dict(refine=2, band=None)``: the scene
         also counts, per voxel of a lattice ``refine`` (1, 2, 4) times finer than the detection one, how many of the depth frames it is
         given saw the voxel free and how many saw it on a surface (``band``: None = ``voxel_size[2]``, fixed for the scene's life), so that
-        ``scene.occupancy(source="depth")`` and ``skip_empty=dict(source="depth")`` carve free space from the sensor.  Bad
-        knobs: ValueError, before any device work."""
+        ``scene.occupancy(source="depth")`` and ``skip_empty=dict(source="depth")`` carve free space from the sensor.
+        ``cloud``: None (the default: every launch and every bit as without the keyword), True or ``dict(refine=2, max_depth=None)``: the
+        scene also keeps, per voxel of such a fine lattice, integer sums of the depth pixels that fell into it (those with
+        ``0 < d <= max_depth`` metres), so that ``scene.points()`` returns a coloured, voxel-downsampled point cloud of the chunks held and
+        labels it with a ``detect()`` result.  Independent of ``carve`` and of ``keep_views``.  Bad knobs: ValueError,
+        before any device work."""
         from .streaming import SceneStream
-        return SceneStream(self, img_meta, window=window, keep_views=keep_views, mean=mean, std=std, carve=carve)
+        return SceneStream(self, img_meta, window=window, keep_views=keep_views, mean=mean, std=std, carve=carve, cloud=cloud)
 
-    def begin_scenes(self, img_metas, window=None, keep_views=False, mean=IMG_MEAN, std=IMG_STD, carve=None):
+    def begin_scenes(self, img_metas, window=None, keep_views=False, mean=IMG_MEAN, std=IMG_STD, carve=None, cloud=None):
         """A :class:`~nerfdet_amd.streaming.SceneGroup` for 1 .. 64 scenes streamed together, each with its own intrinsic, origin and extrinsics
         (``img_shape``, ``ori_shape``, the voxel grid and the detector are shared): ``group.add_views(img, denorm, metas, scenes=None)`` runs the
         backbone once over one chunk of k views per listed scene and folds them into the scenes' states with one grouped accumulate;
@@ -297,9 +301,11 @@ class nerfdet(BaseDetector):
         ``begin_scene(..., keep_views=True)`` renders from the same maps.  ``group.add_frames(frames, metas, scenes=None)`` takes capture-resolution
         frames (len(scenes), k, Hs, Ws, 3) instead and prepares all of them in one launch with ``mean`` / ``std``, as ``begin_scene`` describes.
         ``carve`` as in :meth:`begin_scene`, one ``refine`` and ``band`` for the group: every scene gets counter segments of its own that follow
-        its states (one k_carve_accumulate launch per listed scene and call).  One image size and grid per group, inference only, not graphed."""
+        its states (one k_carve_accumulate launch per listed scene and call).  ``cloud`` as in :meth:`begin_scene`, one ``refine`` and
+        ``max_depth`` for the group: every scene gets record segments of its own (one k_cloud_accumulate launch per listed scene and call),
+        read by ``group.points(scenes=)``.  One image size and grid per group, inference only, not graphed."""
         from .streaming import SceneGroup
-        return SceneGroup(self, img_metas, window=window, keep_views=keep_views, mean=mean, std=std, carve=carve)
+        return SceneGroup(self, img_metas, window=window, keep_views=keep_views, mean=mean, std=std, carve=carve, cloud=cloud)
 
     def forward_test_async(self, img, img_metas, **kwargs):
         """Serving form of :meth:`forward_test`: every launch of the scene is queued on the current stream and a ``finish()`` callable is

@@ -1032,6 +1032,138 @@ def carve_counts(segments: Sequence[Tensor], n_voxels_fine) -> Tuple[Tensor, Ten
     return free.view(*nv).to(torch.int32), hit.view(*nv).to(torch.int32)
 
 
+# --------------------------------------------------------------------------------------------
+# points out: a voxel-downsampled point cloud of a streamed RGB-D scene (csrc/cloud_kernels.hip)
+# --------------------------------------------------------------------------------------------
+CLOUD_WORDS = 8                 # uint32 words of a fine voxel's record: n, sum qx, qy, qz, sum b, g, r, one spare word (32 bytes)
+CLOUD_FIELDS = ("n", "qx", "qy", "qz", "b", "g", "r")
+CLOUD_PIXELS_MAX = 2 ** 24      # pixels of one launch, and contributions a segment may hold, stay below this: a sum of bytes stays exact
+CLOUD_WAVE_MERGE = True         # k_cloud_accumulate sums the lanes of a wave that share a voxel before it touches memory
+
+
+def _cloud_lattice(n_voxels_fine, p0, vs):
+    nv = [int(v) for v in (n_voxels_fine.tolist() if isinstance(n_voxels_fine, Tensor) else n_voxels_fine)]
+    p0 = [float(v) for v in (p0.tolist() if isinstance(p0, (Tensor, np.ndarray)) else p0)]
+    vs = [float(v) for v in (vs.tolist() if isinstance(vs, (Tensor, np.ndarray)) else vs)]
+    if len(nv) != 3 or len(p0) != 3 or len(vs) != 3 or min(nv) < 1:
+        raise ValueError(f"cloud: a lattice is three positive voxel counts, a first point and a voxel size, got {nv}, {p0}, {vs}")
+    if not all(np.isfinite(v) and v > 0 for v in vs) or not all(np.isfinite(v) for v in p0):
+        raise ValueError(f"cloud: the voxel size {vs} must be positive and finite, the first point {p0} finite")
+    if nv[0] * nv[1] * nv[2] >= 2 ** 31:
+        raise ValueError(f"cloud: {nv} holds 2^31 voxels or more")
+    return nv, p0, vs
+
+
+def _cloud_segments(segments, n: int, what: str) -> list:
+    segments = list(segments)
+    if not 1 <= len(segments) <= RING_MAX:
+        raise ValueError(f"{what} takes 1 to {RING_MAX} segments, got {len(segments)}")
+    for s in segments:
+        if not isinstance(s, Tensor) or s.dtype != torch.int32 or tuple(s.shape) != (n, CLOUD_WORDS) or not s.is_contiguous() \
+                or s.device != segments[0].device:
+            raise ValueError(f"{what}: every segment must be a contiguous ({n}, {CLOUD_WORDS}) int32 tensor on one device")
+    return segments
+
+
+def check_cloud_max_depth(max_depth):
+    """``max_depth`` of a cloud as the float32 value the kernel compares with (0.0: none): None or a finite positive number; else ValueError."""
+    if max_depth is None:
+        return 0.0
+    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, float, np.floating, np.integer)) or not np.isfinite(max_depth) \
+            or not float(np.float32(max_depth)) > 0:
+        raise ValueError(f"cloud: max_depth={max_depth!r} must be None or a finite positive number of metres")
+    return float(np.float32(max_depth))
+
+
+def cloud_accumulate(sums: Tensor, n_voxels_fine, p0, vs, depth_r: Tensor, rgb: Tensor, intrinsic, c2w, max_depth=None,
+                     merge: Optional[bool] = None) -> Tensor:
+    """Add a chunk's k views to ``sums`` (N, 8) int32, the records of the fine lattice ``n_voxels_fine`` with first point ``p0`` and voxel
+    size ``vs`` (:func:`carve_lattice` over :func:`get_points`).  ``depth_r`` (k, H, W) float32 / float64 metres at the image's size (a
+    :class:`DepthGate`'s ``depth_r``), ``rgb`` (k, 3, H, W) float32 B, G, R planes in [0, 1]; both may be pitched views with a unit last
+    stride.  ``intrinsic`` 3 x 3 or 4 x 4 at the image's scale and ``c2w`` k camera-to-world 4 x 4, as pipeline.camera_rays takes them.
+    A pixel with ``d > 0``, finite and ``d <= max_depth`` (None: no limit) adds its point -- the camera centre plus d times camera_rays'
+    direction -- to the voxel ``floor((x - p0) / vs + 0.5)`` (include/nerfdet_hip.h).  ``merge``: None (``CLOUD_WAVE_MERGE``), or which of
+    the kernel's two forms runs; the bytes are the same.  In place, one k_cloud_accumulate launch; returns ``sums``.  ValueError for wrong
+    shapes or dtypes before the launch, RuntimeError for CPU tensors."""
+    nv, p0, vs = _cloud_lattice(n_voxels_fine, p0, vs)
+    n = nv[0] * nv[1] * nv[2]
+    md = check_cloud_max_depth(max_depth)
+    if not isinstance(sums, Tensor) or sums.dtype != torch.int32 or tuple(sums.shape) != (n, CLOUD_WORDS) or not sums.is_contiguous():
+        raise ValueError(f"cloud_accumulate: sums must be a contiguous ({n}, {CLOUD_WORDS}) int32 tensor")
+    d = depth_r
+    if not isinstance(d, Tensor) or d.dim() != 3 or d.dtype not in _DEPTH_DTYPES or min(d.shape) < 1:
+        raise ValueError("cloud_accumulate: depth_r must be a (k, H, W) float32 or float64 tensor")
+    k, h, w = (int(v) for v in d.shape)
+    if not isinstance(rgb, Tensor) or rgb.dtype != torch.float32 or tuple(rgb.shape) != (k, 3, h, w):
+        raise ValueError(f"cloud_accumulate: rgb must be a ({k}, 3, {h}, {w}) float32 tensor beside depth_r {tuple(d.shape)}")
+    if k * h * w >= CLOUD_PIXELS_MAX:
+        raise ValueError(f"cloud_accumulate: {k} views of {h} x {w} hold 2^24 pixels or more; add them in smaller chunks")
+    kk = intrinsic.detach().cpu().numpy() if isinstance(intrinsic, Tensor) else np.asarray(intrinsic)
+    if kk.shape not in ((3, 3), (4, 4)):
+        raise ValueError(f"cloud_accumulate takes 3 x 3 or 4 x 4 intrinsics, got {kk.shape}")
+    m = c2w.detach().cpu().numpy() if isinstance(c2w, Tensor) else np.asarray(c2w)
+    if m.shape != (k, 4, 4):
+        raise ValueError(f"cloud_accumulate: c2w must be ({k}, 4, 4) camera-to-world matrices, got {m.shape}")
+    _need_gpu(sums, d, rgb)
+    if d.device != sums.device or rgb.device != sums.device:
+        raise ValueError("cloud_accumulate: sums, depth_r and rgb live on different devices")
+    if d.stride(2) != 1 or d.stride(1) < w or d.stride(0) < h * d.stride(1):
+        d = d.contiguous()
+    if rgb.stride(3) != 1 or rgb.stride(2) < w or rgb.stride(1) < h * rgb.stride(2) or rgb.stride(0) < 3 * rgb.stride(1):
+        rgb = rgb.contiguous()
+    m = m.astype(np.float32)
+    # one upload: 6 intrinsic floats, then the k rotations, then the k centres (pipeline.camera_rays' layout)
+    host = np.concatenate([np.ascontiguousarray(kk[:2, :3], dtype=np.float32).reshape(-1), m[:, :3, :3].reshape(-1), m[:, :3, 3].reshape(-1)])
+    buf = _upload_async(torch.from_numpy(host), sums.device)
+    merge = CLOUD_WAVE_MERGE if merge is None else bool(merge)
+    trace.span("k_cloud_accumulate", lambda: check(
+        _lib.load().ndet_cloud_accumulate(_ptr(d), _DEPTH_DTYPES[d.dtype], d.stride(0), d.stride(1), _ptr(rgb), rgb.stride(0), rgb.stride(1),
+                                          rgb.stride(2), _ptr(buf), _ptr(buf[6:]), _ptr(buf[6 + 9 * k:]), k, h, w, float3(p0), float3(vs),
+                                          nv[0], nv[1], nv[2], md, int(merge), _ptr(sums), _stream(sums)), "cloud_accumulate"),
+        bytes=k * h * w * (d.element_size() + 12), kind="hbm")
+    return sums
+
+
+def cloud_points(segments: Sequence[Tensor], n_voxels_fine, p0, vs, min_points: int = 1) -> dict:
+    """1 .. 64 segments of :func:`cloud_accumulate` records over one fine lattice -> ``dict(xyz (M,3) float32, bgr (M,3) uint8, count (M,)
+    int32, voxel (M,) int32)``: one point per fine voxel whose count, summed over the segments, is ``min_points`` or more, in ascending
+    flat index -- the mean position, the mean colour (rounded half up), the count and the index (include/nerfdet_hip.h).  Two launches
+    (k_cloud_count, k_cloud_write) around one prefix sum; M reaches the host in ONE device-to-host read, the call's only synchronisation;
+    ``M = 0`` skips the second launch.  The same bytes on every call."""
+    nv, p0, vs = _cloud_lattice(n_voxels_fine, p0, vs)
+    n = nv[0] * nv[1] * nv[2]
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or not 1 <= min_points < 2 ** 31:
+        raise ValueError(f"cloud_points: min_points={min_points!r} must be an int of at least 1")
+    segments = _cloud_segments(segments, n, "cloud_points")
+    _need_gpu(*segments)
+    lib, dev = _lib.load(), segments[0].device
+    ptrs = (ctypes.c_void_p * len(segments))(*[s.data_ptr() for s in segments])
+    geom = (nv[0], nv[1], nv[2], float3(p0), float3(vs), int(min_points))
+    counts = torch.empty((int(lib.ndet_cloud_blocks(n)),), dtype=torch.int32, device=dev)
+    trace.span("k_cloud_count", lambda: check(lib.ndet_cloud_count(ptrs, len(segments), *geom, _ptr(counts), _stream(counts)), "cloud_count"),
+               bytes=32 * n * len(segments) + 4 * counts.numel(), kind="hbm")
+    last = torch.cumsum(counts, 0, dtype=torch.int32)
+    first = last - counts
+    m = int(last[-1])                                          # the one read
+    out = dict(xyz=torch.empty((m, 3), dtype=torch.float32, device=dev), bgr=torch.empty((m, 3), dtype=torch.uint8, device=dev),
+               count=torch.empty((m,), dtype=torch.int32, device=dev), voxel=torch.empty((m,), dtype=torch.int32, device=dev))
+    if m:
+        trace.span("k_cloud_write", lambda: check(
+            lib.ndet_cloud_write(ptrs, len(segments), *geom, _ptr(first), _ptr(out["xyz"]), _ptr(out["bgr"]), _ptr(out["count"]),
+                                 _ptr(out["voxel"]), _stream(counts)), "cloud_write"),
+            bytes=32 * n * len(segments) + 23 * m, kind="hbm")
+    return out
+
+
+def cloud_sums(segments: Sequence[Tensor], n_voxels_fine) -> dict:
+    """``dict(n, qx, qy, qz, b, g, r)`` of int64 (X,Y,Z) tensors: the segments' records summed field by field (torch arithmetic; for
+    inspection, not on a hot path)."""
+    nv = [int(v) for v in n_voxels_fine]
+    segments = _cloud_segments(segments, nv[0] * nv[1] * nv[2], "cloud_sums")
+    total = sum((s.to(torch.int64) & 0xffffffff) for s in segments)
+    return {f: total[:, i].reshape(*nv).contiguous() for i, f in enumerate(CLOUD_FIELDS)}
+
+
 def alpha_gate(mean: Tensor, density: Tensor, count: Tensor) -> Tensor:
     """Unfused gating of nerfdet.py:257-261: ``(1-exp(-density)) * mean`` zeroed where count == 0.
     ``mean`` (C,X,Y,Z) contiguous or channels-last (as produced by :func:`backproject_aggregate`)."""

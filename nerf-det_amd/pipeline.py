@@ -731,6 +731,64 @@ def label_frames(depth_frames: torch.Tensor, intrinsic, c2w, box_frames, window,
     return labels
 
 
+def label_points(xyz: torch.Tensor, box_frames) -> torch.Tensor:
+    """Which box each point belongs to: ``(M,)`` int16 from one launch (ndet_label_points) -- :func:`label_frames`' rule on points the
+    caller has already (a scene's ``points()["xyz"]``): the highest index among the boxes that hold the point, -1 for none.  ``xyz`` (M, 3)
+    float32 on the device; ``box_frames`` (n, 8) float as ``boxes.box_frames`` makes them, n <= 32767 -- no box at all, (0, 8), or no point
+    launches nothing.  ValueError for wrong shapes or dtypes before any launch, RuntimeError for CPU tensors."""
+    if not isinstance(xyz, torch.Tensor) or xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3 or not xyz.is_contiguous():
+        got = f"{tuple(xyz.shape)} {xyz.dtype}" if isinstance(xyz, torch.Tensor) else type(xyz).__name__
+        raise ValueError(f"label_points takes xyz as a contiguous (M, 3) float32 tensor, got {got}")
+    bf = box_frames.detach().cpu().numpy() if isinstance(box_frames, torch.Tensor) else np.asarray(box_frames)
+    if bf.ndim != 2 or bf.shape[1] != 8 or (bf.shape[0] and bf.dtype.kind != "f"):
+        raise ValueError(f"label_points: box_frames must be a float array of shape (n, 8), got {bf.shape} {bf.dtype}")
+    n, m = bf.shape[0], xyz.shape[0]
+    if n > 32767:
+        raise ValueError(f"label_points: {n} boxes do not fit an int16 label")
+    if m >= 2 ** 31:
+        raise ValueError(f"label_points: {m} points, 2^31 or more")
+    if not xyz.is_cuda:
+        raise RuntimeError("nerfdet_amd.pipeline: points must live on the GPU (no CPU fallback)")
+    dev = xyz.device
+    if n == 0 or m == 0:
+        return torch.full((m,), -1, dtype=torch.int16, device=dev)
+    buf = torch.from_numpy(np.ascontiguousarray(bf, dtype=np.float32).reshape(-1)).to(dev)
+    labels = torch.empty((m,), dtype=torch.int16, device=dev)
+    check(_lib.load().ndet_label_points(_ptr(xyz), m, _ptr(buf), n, _ptr(labels), c_void_p(_lib.raw_stream(dev))), "label_points")
+    return labels
+
+
+def write_ply(path, xyz, bgr, labels=None) -> None:
+    """A point cloud as a binary little-endian PLY file, on the host: per vertex ``x y z`` float32 and ``red green blue`` uchar -- ``bgr``'s
+    columns swapped -- and with ``labels`` a ``label`` short.  ``xyz`` (M, 3) float, ``bgr`` (M, 3) uint8, ``labels`` None or (M,) int16;
+    tensors (of any device) or arrays.  ValueError for wrong shapes or dtypes, before the file is opened."""
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    xyz, bgr = host(xyz), host(bgr)
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or xyz.dtype.kind != "f":
+        raise ValueError(f"write_ply: xyz must be a float array of shape (M, 3), got {xyz.shape} {xyz.dtype}")
+    m = xyz.shape[0]
+    if bgr.shape != (m, 3) or bgr.dtype != np.uint8:
+        raise ValueError(f"write_ply: bgr must be a uint8 array of shape ({m}, 3), got {bgr.shape} {bgr.dtype}")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    if labels is not None:
+        labels = host(labels)
+        if labels.shape != (m,) or labels.dtype != np.int16:
+            raise ValueError(f"write_ply: labels must be an int16 array of shape ({m},), got {labels.shape} {labels.dtype}")
+        fields.append(("label", "<i2"))
+    rows = np.empty((m,), dtype=np.dtype(fields))
+    for j, name in enumerate("xyz"):
+        rows[name] = xyz[:, j]
+    for j, name in enumerate(("blue", "green", "red")):
+        rows[name] = bgr[:, j]
+    if labels is not None:
+        rows["label"] = labels
+    names = {"<f4": "float", "u1": "uchar", "<i2": "short"}
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {m}"] + [f"property {names[t]} {f}" for f, t in fields] + ["end_header"]
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode("ascii"))
+        out.write(rows.tobytes())
+
+
 def depth_to_mm(depth: torch.Tensor) -> torch.Tensor:
     """Metres -> uint16 millimetres by :func:`pack_frames`' own rule, with torch: in float32 ``d = depth * 1000``; NaN and d < 0 give 0,
     d > 65535 gives 65535, else trunc(d + 0.5).  For the held-out depth maps of ``score_frames``."""

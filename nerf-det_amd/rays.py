@@ -430,6 +430,62 @@ class CarveStore:
         self.drop_oldest(len(self.segments))
 
 
+class CloudStore(CarveStore):
+    """A cloud scene's record segments (ops.cloud_accumulate's (n, 8) int32 sums over one fine lattice), oldest first, following the scene's
+    states as a :class:`CarveStore` does, with ``pixels[j]``, the pixels of the chunks segment j has taken -- an upper bound of what any of
+    its voxels holds.  A sum of 8-bit values is exact below 2^24 contributions, so no segment may pass ``budget`` (default 2^24 - 1)
+    pixels: a chunk of more is refused; an unwindowed store, which accumulates into its newest segment, opens a further one when the
+    next chunk would take that past the budget, and is refused, whole, once it holds :data:`ops.RING_MAX` segments.  Every refusal is a
+    ValueError of :meth:`target`, which changes nothing.  Windowed: one segment per chunk held.  32 n bytes a segment."""
+
+    def __init__(self, n: int, device, windowed: bool, budget: int = 2 ** 24 - 1):
+        super().__init__(n, device, windowed)
+        if isinstance(budget, bool) or not isinstance(budget, (int, np.integer)) or not 1 <= budget < 2 ** 24:
+            raise ValueError(f"CloudStore: budget={budget!r} must be an int from 1 to 2^24 - 1")
+        self.budget = int(budget)
+        self.pixels: List[int] = []
+
+    def nbytes(self) -> int:
+        return 4 * ops.CLOUD_WORDS * self.n * (len(self.segments) + len(self._spare))
+
+    def _joins(self, pixels: int) -> bool:
+        return not self.windowed and bool(self.segments) and self.pixels[-1] + pixels <= self.budget
+
+    def check(self, pixels: int = 0) -> None:
+        """What :meth:`target` refuses for a next chunk of ``pixels`` pixels (ValueError), with no device work."""
+        if isinstance(pixels, bool) or not isinstance(pixels, (int, np.integer)) or pixels < 0:
+            raise ValueError(f"CloudStore: pixels={pixels!r}")
+        if pixels > self.budget:
+            raise ValueError(f"CloudStore: a chunk of {pixels} pixels is more than a segment may hold ({self.budget}); add fewer views at a time")
+        if not self.windowed and not self._joins(pixels) and len(self.segments) >= ops.RING_MAX:
+            raise ValueError(f"CloudStore: {ops.RING_MAX} segments of {self.budget} pixels are full; reset the scene or stream it through a window")
+
+    def target(self, pixels: int = 0) -> Tensor:
+        """The (n, 8) int32 buffer a next chunk of ``pixels`` pixels is added into; the store is not changed."""
+        self.check(pixels)
+        if self._joins(pixels):
+            return self.segments[-1]
+        return self._spare.pop() if self._spare else torch.zeros((self.n, ops.CLOUD_WORDS), dtype=torch.int32, device=self.device)
+
+    def push(self, seg: Tensor, pixels: int = 0) -> None:
+        """The chunk's target joins the store (unwindowed: it is the newest segment, or becomes it) with its ``pixels``."""
+        if seg.dtype != torch.int32 or tuple(seg.shape) != (self.n, ops.CLOUD_WORDS):
+            raise ValueError(f"CloudStore.push: a segment is an ({self.n}, {ops.CLOUD_WORDS}) int32 tensor, got {tuple(seg.shape)} {seg.dtype}")
+        if self.segments and seg is self.segments[-1]:
+            if not self._joins(pixels):
+                raise ValueError("CloudStore.push: the newest segment cannot take this chunk (target())")
+            self.pixels[-1] += int(pixels)
+            return
+        if any(seg is s for s in self.segments) or self._joins(pixels) or len(self.segments) >= ops.RING_MAX or pixels > self.budget:
+            raise ValueError("CloudStore.push: not the segment target() hands out for this chunk")
+        self.segments.append(seg)
+        self.pixels.append(int(pixels))
+
+    def drop_oldest(self, k_segments: int = 1) -> None:
+        super().drop_oldest(k_segments)
+        del self.pixels[:k_segments]
+
+
 def cull_points(pts: Tensor, occ: OccupancyGrid):
     """Ordered compaction of ``pts`` (..., 3) against ``occ``: ``(idx (M,) int32, pts_kept (M, 3))``, the flat indices of the kept points
     in ascending order and those points.  Per axis, in float32, ``i = int(floor((x - p0) / voxel_size + 0.5))`` is the nearest lattice

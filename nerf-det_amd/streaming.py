@@ -81,6 +81,7 @@ Without ``keep_views`` there is no ray branch (rendering needs every view's map)
 """
 from __future__ import annotations
 
+import functools
 from collections import OrderedDict
 from typing import List, Optional
 
@@ -652,6 +653,104 @@ class SceneCarve:
         return OccupancyGrid(bits, self.n_voxels, self.points[:, 0, 0, 0].cpu(), np.float32(self.voxel_size), outside, None, dilate)
 
 
+CLOUD_DEFAULTS = dict(refine=2, max_depth=None)
+
+
+def _cloud_knobs(cloud):
+    """What a ``cloud=`` argument of ``begin_scene`` / ``begin_scenes`` asks for, checked before any device work: None (None or False: no
+    cloud), or ``(refine, max_depth)`` -- True: ``refine=2`` and no depth limit; a dict of ``refine`` (1, 2, 4) and ``max_depth`` (None, or
+    a finite positive number of metres).  Else ValueError."""
+    if cloud is None or cloud is False:
+        return None
+    if cloud is True:
+        cloud = {}
+    if not isinstance(cloud, dict) or not set(cloud) <= set(CLOUD_DEFAULTS):
+        raise ValueError(f"cloud={cloud!r} must be None, True or a dict with the keys {sorted(CLOUD_DEFAULTS)}")
+    knobs = dict(CLOUD_DEFAULTS, **cloud)
+    refine, max_depth = knobs["refine"], knobs["max_depth"]
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or int(refine) not in ops.CARVE_REFINES:
+        raise ValueError(f"cloud: refine={refine!r} must be 1, 2 or 4")
+    ops.check_cloud_max_depth(max_depth)
+    return int(refine), (None if max_depth is None else float(max_depth))
+
+
+def _check_min_points(min_points) -> int:
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or not 1 <= min_points < 2 ** 31:
+        raise ValueError(f"points: min_points={min_points!r} must be an int of at least 1")
+    return int(min_points)
+
+
+class SceneCloud:
+    """One scene's point cloud (``begin_scene(cloud=)``): the carve's fine lattice -- ``ops.get_points(r n_voxels, voxel_size / r,
+    origin)``, of which the first point ``p0`` and the voxel size ``vs`` are kept on the host -- the depth limit, the intrinsics at the scale
+    of ``img_shape`` (what ``render_frames`` hands to ``camera_rays``) and the rays.CloudStore that follows the scene's states."""
+
+    def __init__(self, det, meta: dict, device, knobs, windowed: bool):
+        from .rays import CloudStore
+        self.refine, self.max_depth = knobs
+        self.n_voxels, self.voxel_size = ops.carve_lattice(det.n_voxels, det.voxel_size, self.refine)
+        self.p0 = tuple(float(v) for v in ops.get_points(self.n_voxels, self.voxel_size, meta["lidar2img"]["origin"], device)[:, 0, 0, 0].cpu())
+        self.vs = tuple(float(np.float32(v)) for v in self.voxel_size)
+        self.intrinsic = _scene_intrinsic(meta)
+        self.pixels = int(meta["img_shape"][0]) * int(meta["img_shape"][1])      # of one view
+        self.device = device
+        self.store = CloudStore(self.n_voxels[0] * self.n_voxels[1] * self.n_voxels[2], device, windowed)
+
+    def check(self, k: int, with_depth: bool) -> None:
+        """What the store refuses for a next chunk of k views (ValueError: 2^24 pixels or more, 64 full segments); no device work."""
+        self.store.check(k * self.pixels if with_depth else 0)
+
+    def chunk(self, gate, rgb: Tensor, c2w: np.ndarray) -> tuple:
+        """``(segment, pixels)``: the store's target with a chunk's pixels added -- one k_cloud_accumulate launch over the chunk's depth gate
+        (its ``depth_r``), its B, G, R planes and its camera-to-world matrices; without a gate nothing is launched.  The store itself is
+        not changed."""
+        pixels = 0 if gate is None else rgb.shape[0] * self.pixels
+        seg = self.store.target(pixels)
+        if gate is not None:
+            try:
+                ops.cloud_accumulate(seg, self.n_voxels, self.p0, self.vs, gate.depth_r, rgb, self.intrinsic, c2w, self.max_depth)
+            except BaseException:
+                if not any(seg is s for s in self.store.segments):
+                    self.store.give_back(seg)
+                raise
+        return seg, pixels
+
+    def sums(self) -> dict:
+        segs = self.store.segments or [torch.zeros((self.store.n, ops.CLOUD_WORDS), dtype=torch.int32, device=self.device)]
+        return ops.cloud_sums(segs, self.n_voxels)
+
+    def points(self, min_points, result, score_thr) -> dict:
+        """``scene.points``: every check before any launch; ops.cloud_points over the segments held (none held: M = 0 and no launch), and
+        with a result one ndet_label_points launch."""
+        min_points = _check_min_points(min_points)
+        kept = None
+        if result is not None:
+            kept, boxes, _ = _kept_detections(result, score_thr, None, "points")
+            if len(kept) > 32767:
+                raise ValueError(f"points: {len(kept)} detections kept; an int16 label holds 32767")
+        if self.store.segments:
+            out = ops.cloud_points(self.store.segments, self.n_voxels, self.p0, self.vs, min_points)
+        else:
+            out = dict(xyz=torch.empty((0, 3), dtype=torch.float32, device=self.device), bgr=torch.empty((0, 3), dtype=torch.uint8, device=self.device),
+                       count=torch.empty((0,), dtype=torch.int32, device=self.device), voxel=torch.empty((0,), dtype=torch.int32, device=self.device))
+        if kept is not None:
+            from .boxes import box_frames
+            out["ids"] = pipeline.label_points(out["xyz"], box_frames(boxes) if len(kept) else np.zeros((0, 8), dtype=np.float32))
+            out["kept"] = torch.from_numpy(kept)
+        return out
+
+
+def _chunk_c2w(img_meta: dict) -> np.ndarray:
+    """A chunk meta's extrinsics as (k,4,4) float32 camera-to-world matrices: inverted on the host in float64, then rounded, as
+    pipeline.project_boxes does."""
+    return _camera_poses(None, img_meta["lidar2img"]["extrinsic"], "cloud")
+
+
+def _need_cloud(cloud, what: str, call: str = "begin_scene(img_meta, cloud=True)"):
+    if cloud is None:
+        raise ValueError(f"{what} needs a scene with a point cloud: {call}")
+
+
 def _need_carve(carve, source: str, what: str):
     if source != "alpha" and carve is None:
         raise ValueError(f"{what}: source={source!r} needs a carved scene: begin_scene(img_meta, carve=True)")
@@ -884,6 +983,17 @@ def _repeat_tails(det, vol: Tensor, valid: Tensor, metas):
         conv3d.set_arithmetic(prev)
 
 
+class _LatticePoints(Tensor):
+    """``SceneStream.points`` of one scene: the lattice tensor (3,X,Y,Z) that the attribute has always been -- indexing, ``.cpu()`` and
+    every torch function see that tensor and return plain tensors -- which, called, is :meth:`SceneStream.points`, the scene's point
+    cloud.  The stream itself works on ``lattice``, the plain tensor that shares its memory."""
+
+    __torch_function__ = torch._C._disabled_torch_function_impl
+
+    def __call__(self, *args, **kwargs):
+        return self._cloud_call(*args, **kwargs)
+
+
 class SceneStream:
     """One scene of a :class:`~nerfdet_amd.detector.nerfdet` detector, filled chunk by chunk (:meth:`add_views`) and detected at any time
     (:meth:`detect`).  ``img_meta`` fixes the scene: ``lidar2img.intrinsic``, ``lidar2img.origin``, ``img_shape`` and ``ori_shape``; its
@@ -894,15 +1004,18 @@ class SceneStream:
     bank = None     # rays.ViewBank with keep_views, else None
     _occ = None     # (threshold, dilate, outside[, source, min_free]) -> rays.OccupancyGrid of the views held now, made by occupancy(); dropped by _drop_grids()
     carve = None    # SceneCarve with begin_scene(carve=), else None
+    cloud = None    # SceneCloud with begin_scene(cloud=), else None
     mean, std = IMG_MEAN, IMG_STD     # img_norm_cfg of add_frames (RGB)
 
-    def __init__(self, det, img_meta: dict, window: Optional[int] = None, keep_views: bool = False, mean=IMG_MEAN, std=IMG_STD, carve=None):
+    def __init__(self, det, img_meta: dict, window: Optional[int] = None, keep_views: bool = False, mean=IMG_MEAN, std=IMG_STD, carve=None,
+                 cloud=None):
         self.mean, self.std = _norm_cfg(mean, std)
         if not isinstance(keep_views, bool):
             raise ValueError(f"keep_views must be a bool, got {keep_views!r}")
         if window is not None:
             ops.check_window(window)
         carve = _carve_knobs(carve, det)
+        cloud = _cloud_knobs(cloud)
         if det.training:
             raise RuntimeError("SceneStream is inference only: call det.eval() first")
         if det.render_testing and not keep_views:
@@ -919,12 +1032,16 @@ class SceneStream:
         self.state = ops.SceneState(det.n_voxels, lin.in_features, lin.out_features, self.device) if window is None else None
         self._segs: List[ops.SceneState] = []
         self._spare: List[ops.SceneState] = []
-        self.points = ops.get_points(det.n_voxels, det.voxel_size, img_meta["lidar2img"]["origin"], self.device)
+        self.lattice = ops.get_points(det.n_voxels, det.voxel_size, img_meta["lidar2img"]["origin"], self.device)
+        self.points = self.lattice.as_subclass(_LatticePoints)      # the tensor it has always been; called, the method below
+        self.points._cloud_call = functools.partial(SceneStream.points, self)
         if keep_views:
             from .rays import ViewBank
             self.bank = ViewBank()
         if carve is not None:
             self.carve = SceneCarve(det, img_meta["lidar2img"]["origin"], self.device, carve, window is not None)
+        if cloud is not None:
+            self.cloud = SceneCloud(det, self.meta, self.device, cloud, window is not None)
 
     @property
     def chunk_views(self) -> List[int]:
@@ -954,6 +1071,8 @@ class SceneStream:
                 self.bank.clear()
             if self.carve is not None:
                 self.carve.store.clear()
+            if self.cloud is not None:
+                self.cloud.store.clear()
         else:
             self.drop_oldest(len(self._segs))
 
@@ -972,35 +1091,44 @@ class SceneStream:
             self.bank.drop_oldest(k)
         if self.carve is not None:
             self.carve.store.drop_oldest(k)
+        if self.cloud is not None:
+            self.cloud.store.drop_oldest(k)
 
-    def _accumulate(self, *chunk, depth_gate=None, banked=None) -> None:
+    def _accumulate(self, *chunk, depth_gate=None, banked=None, cloud_c2w=None) -> None:
         """Fold a chunk into the scene's state, or in a window into an empty state that joins the window once it is filled; only then does
         the oldest chunk leave a full window.  A chunk that fails leaves the window as it was (its state goes back, zeroed).  ``banked``:
         the chunk's view-bank segment, made by the caller (rays.ViewBank.make_segment changes nothing); it joins the bank once the
         states have taken the chunk, so states and bank hold the same chunks.  A carved scene's counters (SceneCarve.chunk: the chunk's
         depth gate and stride-1 projection, the last of ``chunk``) follow the same rule: a windowed scene's are made in a spare segment
         beside the state and join the store with it; an unwindowed scene's are added to its one segment once the state has taken the
-        chunk."""
+        chunk.  So do a cloud scene's records (SceneCloud.chunk: the gate's ``depth_r``, the chunk's B, G, R planes -- ``chunk[3]`` -- and
+        ``cloud_c2w``, its camera-to-world matrices)."""
         self._drop_grids()
-        carve = self.carve
+        carve, cloud = self.carve, self.cloud
         if self.window is None:
             ops.scene_accumulate(self.state, *chunk, depth_gate=depth_gate)
             if banked is not None:
                 self.bank.push(banked)
             if carve is not None:
                 carve.store.push(carve.chunk(depth_gate, chunk[-1]))
+            if cloud is not None:
+                cloud.store.push(*cloud.chunk(depth_gate, chunk[3], cloud_c2w))
             return
         lin = self._lin
         # a sliding window therefore owns S + 1 states: the chunk that leaves hands its (zeroed) state to the chunk after the next
         st = self._spare.pop() if self._spare else ops.SceneState(self.det.n_voxels, lin.in_features, lin.out_features, self.device)
-        cseg = None
+        cseg = pseg = None
         try:
             ops.scene_accumulate(st, *chunk, depth_gate=depth_gate)
             if carve is not None:
                 cseg = carve.chunk(depth_gate, chunk[-1])
+            if cloud is not None:
+                pseg = cloud.chunk(depth_gate, chunk[3], cloud_c2w)
         except BaseException:
             st.reset()
             self._spare.append(st)
+            if cseg is not None:
+                carve.store.give_back(cseg)
             raise
         if len(self._segs) == self.window:
             self.drop_oldest(1)
@@ -1009,6 +1137,8 @@ class SceneStream:
             self.bank.push(banked)
         if cseg is not None:
             carve.store.push(cseg)
+        if pseg is not None:
+            cloud.store.push(*pseg)
 
     def _check_meta(self, img_meta: dict, k: int) -> None:
         check_chunk_meta(self.meta, img_meta, k)
@@ -1048,6 +1178,8 @@ class SceneStream:
         check_depth_frames(depth_frames, depth, 1, k)
         shape = torch.empty((1, k, 3) + pad_size, device="meta")
         self._check_chunk(shape, shape, img_meta, depth)
+        if self.cloud is not None:
+            self.cloud.check(k, depth is not None or depth_frames is not None)
         img, denorm, depth = _prepared_frames(frames, depth_frames, depth, self.meta["img_shape"], img_scale, pad_size, self.mean, self.std,
                                               _surface_kwargs(self.meta, format, uv_row))
         self.add_views(img, denorm, img_meta, depth=depth)
@@ -1061,6 +1193,10 @@ class SceneStream:
         the state -- one 4-byte device-to-host read (a synchronisation) per chunk.  A tripped chunk is redone on bf16x3 first
         (``conv3d.guard_trips`` counts it), so no tripped chunk reaches the state."""
         self._check_chunk(img, denorm_images, img_meta, depth)
+        cloud_c2w = None
+        if self.cloud is not None:
+            self.cloud.check(img.shape[1], depth is not None)
+            cloud_c2w = _chunk_c2w(img_meta)
         with torch.no_grad():
             lin = self._lin
             hh, ww = self.meta["img_shape"][0], self.meta["img_shape"][1]
@@ -1073,7 +1209,7 @@ class SceneStream:
             rgb_proj = ops.compute_projection(img_meta, 1, self.device)
             # the bank takes the mapped map as it is accumulated and the images as extract_feat hands them to render_rays (uncropped)
             banked = None if self.bank is None else self.bank.make_segment(mapped, denorm_images[0], img_meta)
-            self._accumulate(feat, mapped, lin.bias, rgb, self.points, proj, rgb_proj, depth_gate=gate, banked=banked)
+            self._accumulate(feat, mapped, lin.bias, rgb, self.lattice, proj, rgb_proj, depth_gate=gate, banked=banked, cloud_c2w=cloud_c2w)
 
     def _need_bank(self, what: str):
         bank = self.bank
@@ -1270,7 +1406,7 @@ class SceneStream:
         ring = self.window is not None
         with torch.no_grad():
             glob = ops.density_finish_ring(self._segs, self._lin.bias) if ring else ops.density_finish(self.state, self._lin.bias)
-            alpha = _finished_alpha(self.det.nerf_mlp, self.points, glob)
+            alpha = _finished_alpha(self.det.nerf_mlp, self.lattice, glob)
             return (alpha,) + (ops.volume_finish_ring(self._segs, alpha) if ring else ops.volume_finish(self.state, alpha))
 
     def carve_counts(self):
@@ -1280,6 +1416,24 @@ class SceneStream:
             raise ValueError("carve_counts needs a carved scene: begin_scene(img_meta, carve=True)")
         segs = self.carve.store.segments or [torch.zeros((self.carve.store.n,), dtype=torch.int32, device=self.device)]
         return ops.carve_counts(segs, self.carve.n_voxels)
+
+    def points(self, min_points: int = 1, result=None, score_thr: float = 0.0):
+        """The scene's point cloud from the depth frames of the chunks held now: ``dict(xyz (M,3) float32, bgr (M,3) uint8,
+        count (M,) int32, voxel (M,) int32)`` on the device -- one point per voxel of the cloud's fine lattice that ``min_points`` (an int of
+        at least 1) or more depth pixels fell into, in ascending flat index: their mean position, their mean colour, their number and the
+        voxel's index (ops.cloud_points: two launches, one device-to-host read).  ``result``: one scene's ``detect()[0]``; the dict then
+        also holds ``ids (M,)`` int16, for every point the index INTO ``kept`` of the box that holds it (the last such in drawing
+        order; -1: none), and ``kept``, the result's indices with ``scores_3d >= score_thr`` by ascending score, as
+        :meth:`label_detections` defines them.  ``pipeline.write_ply`` writes such a cloud to a file.  ``detect()`` does not use the
+        cloud.  Needs ``begin_scene(cloud=)`` (else ValueError); no chunk held: M = 0."""
+        _need_cloud(self.cloud, "points")
+        return self.cloud.points(min_points, result, score_thr)
+
+    def cloud_sums(self):
+        """``dict(n, qx, qy, qz, b, g, r)`` of int64 (X,Y,Z) tensors over the cloud's fine lattice: the sums of the chunks held now, for
+        inspection.  Needs ``begin_scene(cloud=)`` (else ValueError); no chunk held: zeros."""
+        _need_cloud(self.cloud, "cloud_sums")
+        return self.cloud.sums()
 
     def occupancy(self, threshold: float = 1e-3, dilate: int = 1, outside: str = "keep", *, source: str = "alpha", min_free: int = 2):
         """The scene's occupancy grid (rays.OccupancyGrid) over the views held now, from the stream's own finishes -- density finish, the
@@ -1314,7 +1468,7 @@ class SceneStream:
             else:
                 alpha, _, valid = self._finish()
                 if source == "alpha":
-                    self._occ[key] = _make_occupancy(alpha, valid, self.points, self.det.n_voxels, self.det.voxel_size, *key)
+                    self._occ[key] = _make_occupancy(alpha, valid, self.lattice, self.det.n_voxels, self.det.voxel_size, *key)
                 else:
                     self._occ[key] = self.carve.grid(min_free, key[1], key[2], ops.occupancy_bits(alpha, valid, self.det.n_voxels, key[0], 0))
         return self._occ[key]
@@ -1390,15 +1544,18 @@ class SceneGroup:
     banks = None        # with keep_views one rays.ViewBank per scene, else None
     _occ = None         # per scene (threshold, dilate, outside[, source, min_free]) -> rays.OccupancyGrid of the views it holds now, made by occupancy()
     carves = None       # with begin_scenes(carve=) one SceneCarve per scene (one refine and band for the group), else None
+    clouds = None       # with begin_scenes(cloud=) one SceneCloud per scene (one refine and max_depth for the group), else None
     mean, std = IMG_MEAN, IMG_STD     # img_norm_cfg of add_frames (RGB)
 
-    def __init__(self, det, img_metas, window: Optional[int] = None, keep_views: bool = False, mean=IMG_MEAN, std=IMG_STD, carve=None):
+    def __init__(self, det, img_metas, window: Optional[int] = None, keep_views: bool = False, mean=IMG_MEAN, std=IMG_STD, carve=None,
+                 cloud=None):
         self.mean, self.std = _norm_cfg(mean, std)
         if not isinstance(keep_views, bool):
             raise ValueError(f"keep_views must be a bool, got {keep_views!r}")
         if window is not None:
             ops.check_window(window)
         carve = _carve_knobs(carve, det)
+        cloud = _cloud_knobs(cloud)
         metas = list(img_metas)
         if not 1 <= len(metas) <= ops.GROUP_MAX:
             raise ValueError(f"begin_scenes takes 1 to {ops.GROUP_MAX} scenes, got {len(metas)}")
@@ -1424,6 +1581,8 @@ class SceneGroup:
             self.banks = [ViewBank() for _ in metas]
         if carve is not None:
             self.carves = [SceneCarve(det, m["lidar2img"]["origin"], self.device, carve, window is not None) for m in metas]
+        if cloud is not None:
+            self.clouds = [SceneCloud(det, m, self.device, cloud, window is not None) for m in metas]
 
     @staticmethod
     def _check_shapes(first: dict, metas) -> None:
@@ -1471,6 +1630,8 @@ class SceneGroup:
                 self.banks[s].clear()
             if self.carves is not None:
                 self.carves[s].store.clear()
+            if self.clouds is not None:
+                self.clouds[s].store.clear()
 
     def drop_oldest(self, k: int = 1, scenes=None) -> None:
         """Forget the k oldest chunks of every listed scene of a windowed group (their states are zeroed and kept for the chunks to come).
@@ -1486,6 +1647,9 @@ class SceneGroup:
         if self.carves is not None:
             for s in scenes:
                 self.carves[s].store.drop_oldest(k)
+        if self.clouds is not None:
+            for s in scenes:
+                self.clouds[s].store.drop_oldest(k)
 
     def _carve_chunks(self, scenes, depth_gate, rgb_proj: Tensor) -> list:
         """Every listed scene's carve target with its chunk's evidence added (SceneCarve.chunk over the scene's k views of the call's gate
@@ -1505,7 +1669,25 @@ class SceneGroup:
             raise
         return segs
 
-    def _accumulate(self, scenes, *chunk, depth_gate=None, banked=None) -> None:
+    def _cloud_chunks(self, scenes, depth_gate, rgb: Tensor, c2ws) -> list:
+        """Every listed scene's cloud target with its chunk's pixels added, and their number (SceneCloud.chunk over the scene's k views of
+        the call's gate, B, G, R planes and camera-to-world matrices: one k_cloud_accumulate launch a scene); no store is changed.  When a
+        scene's launch is refused, the targets made so far go back."""
+        k = rgb.shape[0] // len(scenes)
+        segs = []
+        try:
+            for i, s in enumerate(scenes):
+                sl = slice(i * k, (i + 1) * k)
+                g = None if depth_gate is None else ops.DepthGate(depth_gate.depth_f[sl], depth_gate.depth_r[sl], depth_gate.band)
+                segs.append(self.clouds[s].chunk(g, rgb[sl], c2ws[i]))
+        except BaseException:
+            if self.window is not None:
+                for s, (seg, _) in zip(scenes, segs):
+                    self.clouds[s].store.give_back(seg)
+            raise
+        return segs
+
+    def _accumulate(self, scenes, *chunk, depth_gate=None, banked=None, cloud_c2w=None) -> None:
         """Fold one chunk per listed scene into the scenes' states, or in a windowed group into empty states that join the scenes' windows
         once the grouped accumulate has succeeded (ops.SceneGroupRingState.accumulate): a call that fails leaves every window as it was.
         ``banked``: the listed scenes' view-bank segments, made by the caller (rays.ViewBank.make_segment changes nothing); they join
@@ -1514,19 +1696,29 @@ class SceneGroup:
         in a windowed group they are made inside the grouped accumulate's transaction and join their stores with the states; in an
         unwindowed one they are added to the scenes' segments once the states have taken the chunks."""
         self._drop_grids(scenes)
-        carved = None
+        carved = clouded = None
         if self.window is None:
             ops.scene_accumulate_group(self.group, scenes, *chunk, depth_gate=depth_gate)
             if self.carves is not None:
                 carved = self._carve_chunks(scenes, depth_gate, chunk[-1])
+            if self.clouds is not None:
+                clouded = self._cloud_chunks(scenes, depth_gate, chunk[3], cloud_c2w)
         else:
             full = [len(self.pool.segs[s]) == self.window for s in scenes]
 
             def fill(states):
-                nonlocal carved
+                nonlocal carved, clouded
                 ops.scene_accumulate_group_ring(self.pool, scenes, *chunk, depth_gate=depth_gate, states=states)
                 if self.carves is not None:
                     carved = self._carve_chunks(scenes, depth_gate, chunk[-1])
+                if self.clouds is not None:
+                    try:
+                        clouded = self._cloud_chunks(scenes, depth_gate, chunk[3], cloud_c2w)
+                    except BaseException:
+                        if carved is not None:
+                            for s, seg in zip(scenes, carved):
+                                self.carves[s].store.give_back(seg)
+                        raise
 
             self.pool.accumulate(scenes, fill)
             for s, was_full in zip(scenes, full):
@@ -1535,12 +1727,17 @@ class SceneGroup:
                         self.banks[s].drop_oldest(1)
                     if carved is not None:
                         self.carves[s].store.drop_oldest(1)
+                    if clouded is not None:
+                        self.clouds[s].store.drop_oldest(1)
         if banked is not None:
             for s, seg in zip(scenes, banked):
                 self.banks[s].push(seg)
         if carved is not None:
             for s, seg in zip(scenes, carved):
                 self.carves[s].store.push(seg)
+        if clouded is not None:
+            for s, seg in zip(scenes, clouded):
+                self.clouds[s].store.push(*seg)
 
     def _check_call(self, img: Tensor, denorm_images: Tensor, metas, scenes, depth):
         """Everything add_views refuses, before anything is launched: ``(listed scenes, k)``."""
@@ -1575,7 +1772,8 @@ class SceneGroup:
         nothing are its own.  ``depth`` passes through.  ``depth_frames`` instead of ``depth``: the sensor's frames (len(scenes), k, Hd, Wd)
         uint16 millimetres on the device; ONE ndet_depth_frames launch over all of them makes the float64 metres at the group's
         ``img_shape``, as in :meth:`SceneStream.add_frames`.  Both given, a wrong dtype or another k: ValueError, before any device work."""
-        n = len(ops.listed_scenes(self.n_scenes, scenes))
+        listed = ops.listed_scenes(self.n_scenes, scenes)
+        n = len(listed)
         img_scale, pad_size = check_frames_meta(self.metas[0], frames, n, format, uv_row)
         metas = list(metas)
         for m in metas:
@@ -1584,6 +1782,9 @@ class SceneGroup:
         check_depth_frames(depth_frames, depth, n, k)
         shape = torch.empty((n, k, 3) + pad_size, device="meta")
         self._check_call(shape, shape, metas, scenes, depth)
+        if self.clouds is not None:
+            for s in listed:
+                self.clouds[s].check(k, depth is not None or depth_frames is not None)
         img, denorm, depth = _prepared_frames(frames, depth_frames, depth, self.metas[0]["img_shape"], img_scale, pad_size, self.mean, self.std,
                                               _surface_kwargs(self.metas[0], format, uv_row))
         self.add_views(img, denorm, metas, scenes=scenes, depth=depth)
@@ -1603,6 +1804,11 @@ class SceneGroup:
         scenes, k = self._check_call(img, denorm_images, metas, scenes, depth)
         n = len(scenes)
         metas = list(metas)
+        cloud_c2w = None
+        if self.clouds is not None:
+            for s in scenes:
+                self.clouds[s].check(k, depth is not None)
+            cloud_c2w = [_chunk_c2w(m) for m in metas]
         with torch.no_grad():
             lin = self._lin
             hh, ww = self.metas[0]["img_shape"][0], self.metas[0]["img_shape"][1]
@@ -1618,7 +1824,7 @@ class SceneGroup:
             banked = None
             if self.banks is not None:
                 banked = [self.banks[s].make_segment(mapped[i * k:(i + 1) * k], denorm_images[i], metas[i]) for i, s in enumerate(scenes)]
-            self._accumulate(scenes, feat, mapped, lin.bias, rgb, proj[0], proj[1], depth_gate=gate, banked=banked)
+            self._accumulate(scenes, feat, mapped, lin.bias, rgb, proj[0], proj[1], depth_gate=gate, banked=banked, cloud_c2w=cloud_c2w)
 
     def _need_views(self, scenes) -> List[int]:
         scenes = ops.listed_scenes(self.n_scenes, scenes)
@@ -1871,6 +2077,25 @@ class SceneGroup:
             c = self.carves[s]
             out.append(ops.carve_counts(c.store.segments or [torch.zeros((c.store.n,), dtype=torch.int32, device=self.device)], c.n_voxels))
         return out
+
+    def points(self, min_points: int = 1, results=None, score_thr: float = 0.0, scenes=None):
+        """Per listed scene :meth:`SceneStream.points`: a list of dicts.  ``results``: None, or one ``detect()`` result per listed scene.
+        Needs ``begin_scenes(cloud=)`` (else ValueError); every check comes before any launch."""
+        _need_cloud(self.clouds, "points", "begin_scenes(img_metas, cloud=True)")
+        scenes = ops.listed_scenes(self.n_scenes, scenes)
+        results = [None] * len(scenes) if results is None else list(results)
+        if len(results) != len(scenes):
+            raise ValueError(f"points: {len(results)} results for {len(scenes)} listed scenes")
+        _check_min_points(min_points)
+        for r in results:
+            if r is not None:
+                _kept_detections(r, score_thr, None, "points")
+        return [self.clouds[s].points(min_points, r, score_thr) for s, r in zip(scenes, results)]
+
+    def cloud_sums(self, scenes=None):
+        """Per listed scene :meth:`SceneStream.cloud_sums`' dict.  Needs ``begin_scenes(cloud=)`` (else ValueError)."""
+        _need_cloud(self.clouds, "cloud_sums", "begin_scenes(img_metas, cloud=True)")
+        return [self.clouds[s].sums() for s in ops.listed_scenes(self.n_scenes, scenes)]
 
     def occupancy(self, threshold: float = 1e-3, dilate: int = 1, outside: str = "keep", scenes=None, *, source: str = "alpha",
                   min_free: int = 2):
