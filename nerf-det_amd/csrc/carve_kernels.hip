@@ -6,9 +6,7 @@
 // The evidence of a view for a voxel is ndet_project_z (K2's stride-1 RGB projection) and the depth gate's own band test on the
 // image-resolution map (ndet_depth_band): free | hit | behind partition the camera depths with no gap.  Integer counts: any chunking of
 // the same views leaves the same bytes.  Plain vector stores, no atomics.  Compiled with -ffp-contract=off.
-#include "ndet_common.hpp"
-
-#include <cmath>
+#include "grid_common.hpp"
 
 #define CARVE_SAT 65535u
 
@@ -91,24 +89,18 @@ extern "C" int ndet_carve_accumulate(const float* points, int nx, int ny, int nz
 }
 
 // ------------------------------------------------------------------------------------------------
-// counts -> bits.  One thread per fine voxel; a wave's ballot is two whole words, as k_occupancy_bits writes them.  The segment
-// pointers ride in the kernel-argument block (512 bytes), entries beyond n_segs are null and never read.
+// counts -> bits.  One thread per fine voxel; the bit grid and the segment table are grid_common.hpp's.
 //   one pass    every thread sums the segments at each voxel of its (2 dilate + 1)^3 neighbourhood;
 //   two passes  (scratch given, dilate > 0) the first launch writes the UNDILATED grid into scratch, the second dilates from those
 //               bits: the segments are read once a voxel, the neighbourhood costs bit reads from a grid 1/32 the size of a segment.
 // ------------------------------------------------------------------------------------------------
-struct CarveSegs {
-    const uint32_t* seg[NDET_RING_MAX];
-};
-
 struct CarveGrid {
     int nx, ny, nz;
     int refine;                 // the parent lattice is (nx, ny, nz) / refine
     const uint32_t* coarse;     // undilated alpha bits on the parent lattice, or null
 };
 
-__device__ __forceinline__ bool carve_solid(const CarveSegs& s, int n_segs, uint32_t min_free, const CarveGrid& g, int x, int y, int z) {
-    const int n = (x * g.ny + y) * g.nz + z;
+__device__ __forceinline__ bool carve_solid(const NdetSegs& s, int n_segs, uint32_t min_free, const CarveGrid& g, int x, int y, int z, int n) {
     uint32_t free_ = 0, hit = 0;
     for (int j = 0; j < n_segs; ++j) {
         const uint32_t w = s.seg[j][n];
@@ -119,78 +111,46 @@ __device__ __forceinline__ bool carve_solid(const CarveSegs& s, int n_segs, uint
     if (g.coarse) {
         const int r = g.refine;
         const int p = ((x / r) * (g.ny / r) + y / r) * (g.nz / r) + z / r;
-        solid = solid && ((g.coarse[p >> 5] >> (p & 31)) & 1u);
+        solid = solid && ndet_bit(g.coarse, p);
     }
     return solid;
 }
 
-__device__ __forceinline__ void carve_ballot_store(bool set, int64_t t, uint32_t* __restrict__ bits, int n_words) {
-    const unsigned long long b = __ballot(set);
-    const int64_t w = (t >> 6) * 2;                            // the wave's first word (t - lane is a multiple of 64)
-    const int lane = threadIdx.x & 63;
-    if (lane == 0 && w < n_words) bits[w] = (uint32_t)b;
-    if (lane == 32 && w + 1 < n_words) bits[w + 1] = (uint32_t)(b >> 32);
-}
-
-__global__ __launch_bounds__(256) void k_carve_bits(CarveSegs s, int n_segs, uint32_t min_free, int dilate, CarveGrid g, int n_total,
+__global__ __launch_bounds__(256) void k_carve_bits(NdetSegs s, int n_segs, uint32_t min_free, int dilate, CarveGrid g, int n_total,
                                                     uint32_t* __restrict__ bits, int n_words) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    bool set = false;
-    if (t < n_total) {
-        const int n = (int)t;
-        const int iz = n % g.nz, iy = (n / g.nz) % g.ny, ix = n / (g.nz * g.ny);
-        const int x0 = max(ix - dilate, 0), x1 = min(ix + dilate, g.nx - 1);
-        const int y0 = max(iy - dilate, 0), y1 = min(iy + dilate, g.ny - 1);
-        const int z0 = max(iz - dilate, 0), z1 = min(iz + dilate, g.nz - 1);
-        for (int x = x0; x <= x1 && !set; ++x)
-            for (int y = y0; y <= y1 && !set; ++y)
-                for (int z = z0; z <= z1 && !set; ++z) set = carve_solid(s, n_segs, min_free, g, x, y, z);
-    }
-    carve_ballot_store(set, t, bits, n_words);
+    const bool set = t < n_total && ndet_any_neighbour((int)t, g.nx, g.ny, g.nz, dilate, [&](int x, int y, int z, int m) {
+                         return carve_solid(s, n_segs, min_free, g, x, y, z, m);
+                     });
+    ndet_ballot_store_words(set, t, bits, n_words);
 }
 
 __global__ __launch_bounds__(256) void k_carve_dilate(const uint32_t* __restrict__ solid, int nx, int ny, int nz, int n_total, int dilate,
                                                       uint32_t* __restrict__ bits, int n_words) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    bool set = false;
-    if (t < n_total) {
-        const int n = (int)t;
-        const int iz = n % nz, iy = (n / nz) % ny, ix = n / (nz * ny);
-        const int x0 = max(ix - dilate, 0), x1 = min(ix + dilate, nx - 1);
-        const int y0 = max(iy - dilate, 0), y1 = min(iy + dilate, ny - 1);
-        const int z0 = max(iz - dilate, 0), z1 = min(iz + dilate, nz - 1);
-        for (int x = x0; x <= x1; ++x)
-            for (int y = y0; y <= y1; ++y)
-                for (int z = z0; z <= z1; ++z) {
-                    const int m = (x * ny + y) * nz + z;
-                    set = set || ((solid[m >> 5] >> (m & 31)) & 1u);
-                }
-    }
-    carve_ballot_store(set, t, bits, n_words);
+    const bool set = t < n_total && ndet_any_neighbour((int)t, nx, ny, nz, dilate, [&](int, int, int, int m) { return ndet_bit(solid, m); });
+    ndet_ballot_store_words(set, t, bits, n_words);
 }
 
 extern "C" int ndet_carve_bits(const uint32_t* const* segments, int n_segs, int min_free, int dilate, int nx, int ny, int nz,
                                const uint32_t* coarse_bits, int refine, uint32_t* scratch, uint32_t* bits, void* stream) {
     const char* fn = "ndet_carve_bits";
-    NDET_REQUIRE(segments && bits, NDET_E_INVALID, "%s: null pointer", fn);
-    NDET_REQUIRE(n_segs >= 1 && n_segs <= NDET_RING_MAX, NDET_E_INVALID, "%s: %d segments, must be 1 .. %d", fn, n_segs, NDET_RING_MAX);
-    for (int j = 0; j < n_segs; ++j) NDET_REQUIRE(segments[j], NDET_E_INVALID, "%s: null pointer (segment %d)", fn, j);
+    NDET_REQUIRE(bits, NDET_E_INVALID, "%s: null pointer", fn);
     NDET_REQUIRE(nx > 0 && ny > 0 && nz > 0, NDET_E_INVALID, "%s: bad sizes", fn);
     NDET_REQUIRE(min_free >= 1, NDET_E_INVALID, "%s: min_free=%d must be at least 1", fn, min_free);
     NDET_REQUIRE(dilate >= 0 && dilate <= 2, NDET_E_INVALID, "%s: dilate=%d must be 0, 1 or 2", fn, dilate);
     NDET_REQUIRE(refine == 1 || refine == 2 || refine == 4, NDET_E_INVALID, "%s: refine=%d must be 1, 2 or 4", fn, refine);
     NDET_REQUIRE(!coarse_bits || (nx % refine == 0 && ny % refine == 0 && nz % refine == 0), NDET_E_INVALID,
                  "%s: the fine sizes (%d, %d, %d) must be multiples of refine=%d", fn, nx, ny, nz, refine);
+    NdetSegs s;
+    NDET_TRY(ndet_segs_fill(fn, segments, n_segs, &s));
     const int64_t total = (int64_t)nx * ny * nz;
     NDET_REQUIRE(total < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: %lld voxels, must be fewer than 2^31", fn, (long long)total);
     const int64_t blocks = (total + 255) / 256;
     NDET_REQUIRE(blocks <= ((int64_t)1 << 24), NDET_E_UNSUPPORTED, "%s: more than 2^24 workgroups", fn);
-    bool aligned = ((uintptr_t)bits & 3) == 0 && ((uintptr_t)coarse_bits & 3) == 0 && ((uintptr_t)scratch & 3) == 0;
-    for (int j = 0; j < n_segs; ++j) aligned = aligned && ((uintptr_t)segments[j] & 3) == 0;
-    NDET_REQUIRE(aligned, NDET_E_UNSUPPORTED, "%s: misaligned pointer", fn);
+    NDET_REQUIRE(((uintptr_t)bits & 3) == 0 && ((uintptr_t)coarse_bits & 3) == 0 && ((uintptr_t)scratch & 3) == 0, NDET_E_UNSUPPORTED,
+                 "%s: misaligned pointer", fn);
     NDET_REQUIRE(scratch != bits, NDET_E_INVALID, "%s: scratch and bits must differ", fn);
-    CarveSegs s = {};
-    for (int j = 0; j < n_segs; ++j) s.seg[j] = segments[j];
     const CarveGrid g = {nx, ny, nz, refine, coarse_bits};
     const int n_words = (int)((total + 31) / 32);
     const bool two = scratch && dilate > 0;

@@ -6,13 +6,11 @@
 //   * ndet_cloud_count / _write  ordered compaction of 1 .. 64 segments of such records: the voxels that hold min_points pixels or more in
 //                                ascending flat index, with mean position, mean colour and count (wave ballots and prefix popcounts,
 //                                no atomics: the same bytes on every call);
-//   * ndet_label_points          which box a point belongs to, by k_label_frames' own test (detections_out_kernels.hip).
-// A pixel's point is the camera centre plus d times k_camera_rays' direction, in k_label_frames' float32 statements; its voxel is
-// k_cull's nearest lattice point (skip_empty_kernels.hip).  Plain vector stores and integer vector atomics only.  Compiled with
+//   * ndet_label_points          which box a point belongs to, by k_label_frames' test (ndet_box_of_point).
+// A pixel's point is the camera centre plus d times k_camera_rays' direction (ndet_pixel_dir, ndet_ray_point); its voxel is the nearest
+// lattice point, as k_cull finds it (grid_common.hpp).  Plain vector stores and integer vector atomics only.  Compiled with
 // -ffp-contract=off.
-#include "ndet_common.hpp"
-
-#include <cmath>
+#include "grid_common.hpp"
 
 #define CLOUD_WORDS 8            // a voxel's record: n, sum qx, sum qy, sum qz, sum b, sum g, sum r, one spare word -- 32 bytes, one sector
 #define CLOUD_PIXELS_MAX ((int64_t)1 << 24)
@@ -26,11 +24,6 @@ struct CloudMap {
 struct CloudPlanes {
     const float* p;
     int64_t view_pitch, plane_pitch, row_pitch;
-};
-
-struct CloudLattice {
-    float p0[3], vs[3];
-    int n[3];
 };
 
 // pack_frames' byte (frames_out_kernels.hip, fo_quantise): x * 255 rounded half up, saturated, NaN -> 0
@@ -51,7 +44,7 @@ __device__ __forceinline__ uint32_t cloud_byte(float x) {
 template <bool MERGE>
 __global__ __launch_bounds__(256) void k_cloud_accumulate(CloudMap dm, CloudPlanes cp, const float* __restrict__ kn /* (2,3) */,
                                                           const float* __restrict__ rot /* (k,3,3) */, const float* __restrict__ lpos /* (k,3) */,
-                                                          int total, int px, int w, CloudLattice g, float max_depth,
+                                                          int total, int px, int w, NdetLattice g, float max_depth,
                                                           uint32_t* __restrict__ sums) {
     const int t = blockIdx.x * 256 + threadIdx.x;           // total < 2^24
     int key = -1;
@@ -62,27 +55,13 @@ __global__ __launch_bounds__(256) void k_cloud_accumulate(CloudMap dm, CloudPlan
         const int64_t o = (int64_t)v * dm.view_pitch + (int64_t)yi * dm.row_pitch + xi;
         const float d = dm.f64 ? (float)static_cast<const double*>(dm.map)[o] : static_cast<const float*>(dm.map)[o];
         if (d > 0.0f && isfinite(d) && (!(max_depth > 0.0f) || d <= max_depth)) {
-            const float xc = ((float)xi + 0.5f - kn[2]) / kn[0];
-            const float yc = ((float)yi + 0.5f - kn[5]) / kn[4];
-            const float* R = rot + (int64_t)v * 9;
-            bool inside = true;
-            int idx[3];
+            float dir[3], pt[3], tt[3], fi[3];
+            ndet_pixel_dir(kn, rot + (int64_t)v * 9, xi, yi, dir);
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                float dir = xc * R[j * 3 + 0];
-                dir = fmaf(yc, R[j * 3 + 1], dir);
-                dir = dir + R[j * 3 + 2];
-                const float x = fmaf(d, dir, lpos[(int64_t)v * 3 + j]);
-                const float tt = (x - g.p0[j]) / g.vs[j] + 0.5f;
-                const float fi = floorf(tt);
-                const float frac = tt - fi;
-                // the range test runs on the floats, as k_cull's does: NaN and +-inf fail it
-                inside = inside && isfinite(x) && fi >= 0.0f && fi < (float)g.n[j];
-                idx[j] = inside ? (int)fi : 0;
-                q[j] = (uint32_t)min((int)(frac * 256.0f), 255);
-            }
-            if (inside) {
-                key = (idx[0] * g.n[1] + idx[1]) * g.n[2] + idx[2];
+            for (int j = 0; j < 3; ++j) pt[j] = ndet_ray_point(d, dir[j], lpos[(int64_t)v * 3 + j]);
+            if (ndet_lattice_index(pt, g, &key, tt, fi)) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) q[j] = (uint32_t)min((int)((tt[j] - fi[j]) * 256.0f), 255);
                 const int64_t co = (int64_t)v * cp.view_pitch + (int64_t)yi * cp.row_pitch + xi;
 #pragma unroll
                 for (int j = 0; j < 3; ++j) c[j] = cloud_byte(cp.p[co + j * cp.plane_pitch]);
@@ -126,34 +105,21 @@ __global__ __launch_bounds__(256) void k_cloud_accumulate(CloudMap dm, CloudPlan
     }
 }
 
-static bool cloud_lattice(const float* p0, const float* vs, int nx, int ny, int nz, CloudLattice* g) {
-    const int n[3] = {nx, ny, nz};
-    bool ok = true;
-    for (int j = 0; j < 3; ++j) {
-        ok = ok && std::isfinite(vs[j]) && vs[j] > 0.0f && std::isfinite(p0[j]);
-        g->p0[j] = p0[j];
-        g->vs[j] = vs[j];
-        g->n[j] = n[j];
-    }
-    return ok;
-}
-
 extern "C" int ndet_cloud_accumulate(const void* depth, int dtype, int64_t view_pitch, int64_t row_pitch, const float* rgb,
                                      int64_t rgb_view_pitch, int64_t rgb_plane_pitch, int64_t rgb_row_pitch, const float* intrinsic_rows,
                                      const float* camrotc2w, const float* cam_lightpos, int k, int H, int W, const float* p0, const float* vs,
                                      int nx, int ny, int nz, float max_depth, int merge, uint32_t* sums, void* stream) {
     const char* fn = "ndet_cloud_accumulate";
     NDET_REQUIRE(depth && rgb && intrinsic_rows && camrotc2w && cam_lightpos && p0 && vs && sums, NDET_E_INVALID, "%s: null pointer", fn);
-    NDET_REQUIRE(nx > 0 && ny > 0 && nz > 0 && k > 0 && H > 0 && W > 0, NDET_E_INVALID, "%s: bad sizes", fn);
+    NDET_REQUIRE(k > 0 && H > 0 && W > 0, NDET_E_INVALID, "%s: bad sizes", fn);
     NDET_REQUIRE(dtype == 0 || dtype == 1, NDET_E_INVALID, "%s: depth dtype %d (0 = float32, 1 = float64)", fn, dtype);
     NDET_REQUIRE(row_pitch >= W && view_pitch >= (int64_t)H * row_pitch, NDET_E_INVALID, "%s: depth pitches smaller than the map", fn);
     NDET_REQUIRE(rgb_row_pitch >= W && rgb_plane_pitch >= (int64_t)H * rgb_row_pitch && rgb_view_pitch >= 3 * rgb_plane_pitch, NDET_E_INVALID,
                  "%s: colour pitches smaller than the planes", fn);
-    CloudLattice g;
-    NDET_REQUIRE(cloud_lattice(p0, vs, nx, ny, nz, &g), NDET_E_INVALID, "%s: the voxel sizes must be positive and finite, the origin finite", fn);
     NDET_REQUIRE(max_depth == max_depth, NDET_E_INVALID, "%s: max_depth is NaN (0 or negative: none)", fn);
-    const int64_t voxels = (int64_t)nx * ny * nz;
-    NDET_REQUIRE(voxels < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: %lld voxels, must be fewer than 2^31", fn, (long long)voxels);
+    NdetLattice g;
+    int64_t voxels = 0;
+    NDET_TRY(ndet_lattice_fill(fn, nx, ny, nz, p0, vs, &g, &voxels));
     const int64_t total = (int64_t)k * H * W;
     NDET_REQUIRE(total < CLOUD_PIXELS_MAX, NDET_E_UNSUPPORTED, "%s: %lld pixels in one launch, must be fewer than 2^24 (a sum of bytes stays exact)",
                  fn, (long long)total);
@@ -175,18 +141,13 @@ extern "C" int ndet_cloud_accumulate(const void* depth, int dtype, int64_t view_
 }
 
 // ------------------------------------------------------------------------------------------------
-// sums -> points.  A wave owns CLOUD_WAVE_VOXELS consecutive fine voxels (one kept count) and walks them 64 at a time in ascending
-// order, as k_cull walks its points; the segment pointers ride in the kernel-argument block (512 bytes), entries beyond n_segs are null
-// and never read.  Every field is summed over the segments in 64 bits.
+// sums -> points.  Ordered compaction (grid_common.hpp): a wave owns CLOUD_WAVE_VOXELS consecutive fine voxels.  Every field is summed
+// over the segments in 64 bits.
 // ------------------------------------------------------------------------------------------------
 #define CLOUD_WAVE_VOXELS 512
 
-struct CloudSegs {
-    const uint32_t* seg[NDET_RING_MAX];
-};
-
 template <bool WRITE>
-__global__ __launch_bounds__(256) void k_cloud_emit(CloudSegs s, int n_segs, int n_total, unsigned long long min_points, CloudLattice g,
+__global__ __launch_bounds__(256) void k_cloud_emit(NdetSegs s, int n_segs, int n_total, unsigned long long min_points, NdetLattice g,
                                                     int* __restrict__ block_count, const int* __restrict__ block_first,
                                                     float* __restrict__ xyz, uint8_t* __restrict__ bgr, int* __restrict__ count,
                                                     int* __restrict__ voxel) {
@@ -194,15 +155,14 @@ __global__ __launch_bounds__(256) void k_cloud_emit(CloudSegs s, int n_segs, int
     const int64_t wb = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // this wave's block of voxels
     const int64_t v0 = wb * CLOUD_WAVE_VOXELS;
     if (v0 >= n_total) return;                                            // wave-uniform
-    int64_t at = WRITE ? block_first[wb] : 0;
-    int kept = 0;
+    NdetCompact c = ndet_compact_begin<WRITE>(block_first, wb);
     for (int i = 0; i < CLOUD_WAVE_VOXELS; i += 64) {
         const int64_t vx = v0 + i + lane;
         unsigned long long n = 0;
         if (vx < n_total)
             for (int j = 0; j < n_segs; ++j) n += s.seg[j][vx * CLOUD_WORDS];
         const bool k = vx < n_total && n >= min_points;
-        const unsigned long long m = __ballot(k);
+        const int64_t o = ndet_compact_step(c, k);
         if (WRITE && k) {
             unsigned long long f[6] = {0, 0, 0, 0, 0, 0};
             for (int j = 0; j < n_segs; ++j) {
@@ -210,7 +170,6 @@ __global__ __launch_bounds__(256) void k_cloud_emit(CloudSegs s, int n_segs, int
 #pragma unroll
                 for (int e = 0; e < 6; ++e) f[e] += rec[1 + e];
             }
-            const int64_t o = at + __popcll(m & ((1ull << lane) - 1ull));
             const int nv = (int)vx;
             const int iz = nv % g.n[2], iy = (nv / g.n[2]) % g.n[1], ix = nv / (g.n[2] * g.n[1]);
             const int idx[3] = {ix, iy, iz};
@@ -225,29 +184,19 @@ __global__ __launch_bounds__(256) void k_cloud_emit(CloudSegs s, int n_segs, int
             count[o] = n > 2147483647ull ? 2147483647 : (int)n;
             voxel[o] = nv;
         }
-        at += __popcll(m);
-        kept += __popcll(m);
     }
-    if (!WRITE && lane == 0) block_count[wb] = kept;
+    ndet_compact_end<WRITE>(c, block_count, wb);
 }
 
 static int cloud_emit_check(const char* fn, const uint32_t* const* segments, int n_segs, int nx, int ny, int nz, const float* p0, const float* vs,
-                            int min_points, CloudSegs* s, CloudLattice* g, int64_t* blocks) {
-    NDET_REQUIRE(segments && p0 && vs, NDET_E_INVALID, "%s: null pointer", fn);
-    NDET_REQUIRE(n_segs >= 1 && n_segs <= NDET_RING_MAX, NDET_E_INVALID, "%s: %d segments, must be 1 .. %d", fn, n_segs, NDET_RING_MAX);
-    for (int j = 0; j < n_segs; ++j) NDET_REQUIRE(segments[j], NDET_E_INVALID, "%s: null pointer (segment %d)", fn, j);
-    NDET_REQUIRE(nx > 0 && ny > 0 && nz > 0, NDET_E_INVALID, "%s: bad sizes", fn);
-    NDET_REQUIRE(cloud_lattice(p0, vs, nx, ny, nz, g), NDET_E_INVALID, "%s: the voxel sizes must be positive and finite, the origin finite", fn);
+                            int min_points, NdetSegs* s, NdetLattice* g, int64_t* blocks) {
+    NDET_REQUIRE(p0 && vs, NDET_E_INVALID, "%s: null pointer", fn);
     NDET_REQUIRE(min_points >= 1, NDET_E_INVALID, "%s: min_points=%d must be at least 1", fn, min_points);
-    const int64_t total = (int64_t)nx * ny * nz;
-    NDET_REQUIRE(total < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: %lld voxels, must be fewer than 2^31", fn, (long long)total);
+    int64_t total = 0;
+    NDET_TRY(ndet_lattice_fill(fn, nx, ny, nz, p0, vs, g, &total));
+    NDET_TRY(ndet_segs_fill(fn, segments, n_segs, s));
     *blocks = (ndet_cloud_blocks(total) + 3) / 4;
     NDET_REQUIRE(*blocks < ((int64_t)1 << 24), NDET_E_UNSUPPORTED, "%s: 2^24 workgroups or more", fn);
-    *s = CloudSegs{};
-    for (int j = 0; j < n_segs; ++j) {
-        NDET_REQUIRE(((uintptr_t)segments[j] & 3) == 0, NDET_E_UNSUPPORTED, "%s: misaligned pointer", fn);
-        s->seg[j] = segments[j];
-    }
     return NDET_OK;
 }
 
@@ -256,8 +205,8 @@ extern "C" int64_t ndet_cloud_blocks(int64_t n_voxels) { return n_voxels > 0 ? (
 extern "C" int ndet_cloud_count(const uint32_t* const* segments, int n_segs, int nx, int ny, int nz, const float* p0, const float* vs,
                                 int min_points, int* block_count, void* stream) {
     const char* fn = "ndet_cloud_count";
-    CloudSegs s;
-    CloudLattice g;
+    NdetSegs s;
+    NdetLattice g;
     int64_t blocks = 0;
     NDET_TRY(cloud_emit_check(fn, segments, n_segs, nx, ny, nz, p0, vs, min_points, &s, &g, &blocks));
     NDET_REQUIRE(block_count, NDET_E_INVALID, "%s: null pointer", fn);
@@ -271,8 +220,8 @@ extern "C" int ndet_cloud_count(const uint32_t* const* segments, int n_segs, int
 extern "C" int ndet_cloud_write(const uint32_t* const* segments, int n_segs, int nx, int ny, int nz, const float* p0, const float* vs,
                                 int min_points, const int* block_first, float* xyz, uint8_t* bgr, int* count, int* voxel, void* stream) {
     const char* fn = "ndet_cloud_write";
-    CloudSegs s;
-    CloudLattice g;
+    NdetSegs s;
+    NdetLattice g;
     int64_t blocks = 0;
     NDET_TRY(cloud_emit_check(fn, segments, n_segs, nx, ny, nz, p0, vs, min_points, &s, &g, &blocks));
     NDET_REQUIRE(block_first && xyz && bgr && count && voxel, NDET_E_INVALID, "%s: null pointer", fn);
@@ -285,33 +234,14 @@ extern "C" int ndet_cloud_write(const uint32_t* const* segments, int n_segs, int
 }
 
 // ------------------------------------------------------------------------------------------------
-// points -> labels.  One thread per point; the boxes pass through LDS in batches, as in k_label_frames, whose test this restates: the
-// highest index among the boxes (centre, half extents, cos yaw, sin yaw) that hold the point, -1 for none (a NaN fails every test).
+// points -> labels.  One thread per point, k_label_frames' test (ndet_box_of_point).
 // ------------------------------------------------------------------------------------------------
-#define CLOUD_BOX_BATCH 256
-
 __global__ __launch_bounds__(256) void k_label_points(const float* __restrict__ pts, int m, const float* __restrict__ boxes /* (n,8) */, int n,
                                                       int16_t* __restrict__ labels) {
-    __shared__ float s_box[CLOUD_BOX_BATCH * 8];
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool on = p < m;
     const float x = on ? pts[p * 3 + 0] : 0.0f, y = on ? pts[p * 3 + 1] : 0.0f, z = on ? pts[p * 3 + 2] : 0.0f;
-    int best = -1;
-    for (int base = 0; base < n; base += CLOUD_BOX_BATCH) {
-        const int here = min(CLOUD_BOX_BATCH, n - base);
-        __syncthreads();
-        for (int j = threadIdx.x; j < here * 8; j += 256) s_box[j] = boxes[(int64_t)base * 8 + j];
-        __syncthreads();
-        if (on) {
-            for (int j = 0; j < here; ++j) {
-                const float* B = s_box + j * 8;
-                const float dx = x - B[0], dy = y - B[1], dz = z - B[2];
-                const float lx = fmaf(dx, B[6], -(dy * B[7]));
-                const float ly = fmaf(dx, B[7], dy * B[6]);
-                if (fabsf(lx) <= B[3] && fabsf(ly) <= B[4] && fabsf(dz) <= B[5]) best = base + j;
-            }
-        }
-    }
+    const int best = ndet_box_of_point(boxes, n, on, x, y, z);
     if (on) labels[p] = (int16_t)best;
 }
 

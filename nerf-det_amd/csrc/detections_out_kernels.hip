@@ -336,7 +336,6 @@ __global__ __launch_bounds__(256) void k_label_frames(const uint16_t* __restrict
                                                       const float* __restrict__ rot /* (k,3,3) */, const float* __restrict__ lpos /* (k,3) */,
                                                       const float* __restrict__ boxes /* (n,8) */, int px, int w, int n, int x0, int y0, int stride,
                                                       int blocks_per_frame, int16_t* __restrict__ labels) {
-    __shared__ float s_box[DO_BATCH * 8];
     const int f = blockIdx.x / blocks_per_frame;
     const int p = (blockIdx.x - f * blocks_per_frame) * 256 + threadIdx.x;
     const int64_t at = (int64_t)f * px + p;
@@ -344,35 +343,13 @@ __global__ __launch_bounds__(256) void k_label_frames(const uint16_t* __restrict
     float pt[3] = {0.0f, 0.0f, 0.0f};
     if (mm != 0) {
         const int row = p / w, col = p - row * w;
-        const int ix = x0 + col * stride, iy = y0 + row * stride;
-        const float xc = ((float)ix + 0.5f - kn[2]) / kn[0];
-        const float yc = ((float)iy + 0.5f - kn[5]) / kn[4];
         const float z = (float)mm / 1000.0f;
-        const float* R = rot + (int64_t)f * 9;
+        float d[3];
+        ndet_pixel_dir(kn, rot + (int64_t)f * 9, x0 + col * stride, y0 + row * stride, d);
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            float d = xc * R[j * 3 + 0];
-            d = fmaf(yc, R[j * 3 + 1], d);
-            d = d + R[j * 3 + 2];
-            pt[j] = fmaf(z, d, lpos[(int64_t)f * 3 + j]);
-        }
+        for (int j = 0; j < 3; ++j) pt[j] = ndet_ray_point(z, d[j], lpos[(int64_t)f * 3 + j]);
     }
-    int best = -1;
-    for (int base = 0; base < n; base += DO_BATCH) {
-        const int here = min(DO_BATCH, n - base);
-        __syncthreads();
-        for (int j = threadIdx.x; j < here * 8; j += 256) s_box[j] = boxes[(int64_t)base * 8 + j];
-        __syncthreads();
-        if (mm != 0) {
-            for (int j = 0; j < here; ++j) {
-                const float* B = s_box + j * 8;                 // centre, half extents, cos yaw, sin yaw
-                const float dx = pt[0] - B[0], dy = pt[1] - B[1], dz = pt[2] - B[2];
-                const float lx = fmaf(dx, B[6], -(dy * B[7]));
-                const float ly = fmaf(dx, B[7], dy * B[6]);
-                if (fabsf(lx) <= B[3] && fabsf(ly) <= B[4] && fabsf(dz) <= B[5]) best = base + j;
-            }
-        }
-    }
+    const int best = ndet_box_of_point(boxes, n, mm != 0, pt[0], pt[1], pt[2]);
     if (p < px) labels[at] = (int16_t)best;
 }
 

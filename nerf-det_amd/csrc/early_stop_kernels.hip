@@ -7,9 +7,7 @@
 //                                 same bytes on every call (wave ballots and prefix popcounts, no atomics).
 // A sample whose raw row stays zero is an exact no-op in k_composite (a = 0, wgt = 0, T (1 - 0 + 1e-10f) = T), so a stopped ray's T no
 // longer moves and the ray stays stopped.  Plain vector stores only.  Compiled with -ffp-contract=off.
-#include "ndet_common.hpp"
-
-#include <cmath>
+#include "grid_common.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // T over one segment.  One lane per ray, the columns in ascending order, one store per ray.
@@ -54,45 +52,20 @@ extern "C" int ndet_ray_advance(const float* raw, float* T, int R, int S, int s0
 #define FS_LDS_BYTES (64 * 1024)
 enum { FS_NO_GRID = 0, FS_GRID_LDS = 1, FS_GRID_GLOBAL = 2 };
 
-struct FsLattice {
-    float p0[3], vs[3];
-    int n[3];
-};
-
-// skip_empty_kernels.hip's se_keep, statement for statement (copied, so that file's kernels stay as they are): the nearest lattice point
-// per axis in fp32,   q = (x - p0) / vs; i = (int)floorf(q + 0.5f)
-__device__ __forceinline__ bool fs_grid_keep(float x, float y, float z, const FsLattice& g, const uint32_t* bits, bool keep_outside) {
-    const float qx = (x - g.p0[0]) / g.vs[0], qy = (y - g.p0[1]) / g.vs[1], qz = (z - g.p0[2]) / g.vs[2];
-    const float fx = floorf(qx + 0.5f), fy = floorf(qy + 0.5f), fz = floorf(qz + 0.5f);
-    // the range test runs on the floats (equal to the test on the ints wherever the cast is defined; NaN and +-inf fail it)
-    const bool inside = isfinite(x) && isfinite(y) && isfinite(z) && fx >= 0.0f && fx < (float)g.n[0] && fy >= 0.0f && fy < (float)g.n[1] &&
-                        fz >= 0.0f && fz < (float)g.n[2];
-    if (!inside) return keep_outside;
-    const int n = ((int)fx * g.n[1] + (int)fy) * g.n[2] + (int)fz;
-    return (bits[n >> 5] >> (n & 31)) & 1u;
-}
-
 static inline int fs_shift(int w) { return w <= 4 ? 2 : w <= 8 ? 3 : w <= 16 ? 4 : 5; }      // log2 of the nominal width, 1 <= w <= 32
 
 template <int GRID, bool WRITE>
 __global__ __launch_bounds__(256) void k_front(const float* __restrict__ pts, int R, int S, int s0, int w, int shift, const float* __restrict__ T,
-                                               float eps, const uint32_t* __restrict__ bits, int n_words, FsLattice g, int keep_outside,
+                                               float eps, const uint32_t* __restrict__ bits, int n_words, NdetLattice g, int keep_outside,
                                                int* __restrict__ block_count, const int* __restrict__ block_first, int* __restrict__ idx,
                                                float* __restrict__ pts_kept) {
-    extern __shared__ uint32_t s_bits[];
-    const uint32_t* b = bits;
-    if (GRID == FS_GRID_LDS) {
-        for (int i = threadIdx.x; i < n_words; i += 256) s_bits[i] = bits[i];
-        __syncthreads();
-        b = s_bits;
-    }
+    const uint32_t* b = ndet_stage_bits<GRID == FS_GRID_LDS>(bits, n_words);
     const int lane = threadIdx.x & 63;
     const int64_t wb = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // this wave's block of rays
     const int64_t r0 = wb * (FS_WAVE_LANES >> shift);
     if (r0 >= R) return;                                                  // wave-uniform, after the only barrier
     const int col = lane & ((1 << shift) - 1);
-    int64_t at = WRITE ? block_first[wb] : 0;
-    int kept = 0;
+    NdetCompact c = ndet_compact_begin<WRITE>(block_first, wb);
     for (int i = 0; i < FS_WAVE_LANES; i += 64) {
         const int64_t r = r0 + ((i + lane) >> shift);
         const int64_t f = r * S + s0 + col;                               // below 2^31 wherever it is used (the host checks R S)
@@ -104,19 +77,16 @@ __global__ __launch_bounds__(256) void k_front(const float* __restrict__ pts, in
             y = pts[f * 3 + 1];
             z = pts[f * 3 + 2];
         }
-        if (GRID != FS_NO_GRID && k) k = fs_grid_keep(x, y, z, g, b, keep_outside != 0);
-        const unsigned long long m = __ballot(k);
+        if (GRID != FS_NO_GRID && k) k = ndet_grid_keep(x, y, z, g, b, keep_outside != 0);
+        const int64_t o = ndet_compact_step(c, k);
         if (WRITE && k) {
-            const int64_t o = at + __popcll(m & ((1ull << lane) - 1ull));
             idx[o] = (int)f;
             pts_kept[o * 3 + 0] = x;
             pts_kept[o * 3 + 1] = y;
             pts_kept[o * 3 + 2] = z;
         }
-        at += __popcll(m);
-        kept += __popcll(m);
     }
-    if (!WRITE && lane == 0) block_count[wb] = kept;
+    ndet_compact_end<WRITE>(c, block_count, wb);
 }
 
 extern "C" int64_t ndet_front_blocks(int64_t R, int w) {
@@ -126,7 +96,7 @@ extern "C" int64_t ndet_front_blocks(int64_t R, int w) {
 }
 
 static int fs_check(const char* fn, const float* pts, int R, int S, int s0, int s1, const float* T, float eps, const uint32_t* bits,
-                    const int* n_voxels, const float* p0, const float* vs, int outside, FsLattice* g, int* n_words, int64_t* blocks) {
+                    const int* n_voxels, const float* p0, const float* vs, int outside, NdetLattice* g, int* n_words, int64_t* blocks) {
     NDET_REQUIRE(pts && T, NDET_E_INVALID, "%s: null pointer", fn);
     NDET_REQUIRE(R > 0 && S > 0, NDET_E_INVALID, "%s: bad sizes", fn);
     NDET_REQUIRE(s0 >= 0 && s1 <= S && s1 > s0, NDET_E_INVALID, "%s: columns [%d, %d) of %d", fn, s0, s1, S);
@@ -135,27 +105,15 @@ static int fs_check(const char* fn, const float* pts, int R, int S, int s0, int 
     memset(g, 0, sizeof(*g));
     if (bits) {
         NDET_REQUIRE(n_voxels && p0 && vs, NDET_E_INVALID, "%s: null pointer", fn);
-        NDET_REQUIRE(n_voxels[0] > 0 && n_voxels[1] > 0 && n_voxels[2] > 0, NDET_E_INVALID, "%s: bad sizes", fn);
-        for (int k = 0; k < 3; ++k) {
-            NDET_REQUIRE(std::isfinite(vs[k]) && vs[k] > 0.0f, NDET_E_INVALID, "%s: voxel size %d must be positive and finite", fn, k);
-            NDET_REQUIRE(std::isfinite(p0[k]), NDET_E_INVALID, "%s: lattice origin %d must be finite", fn, k);
-        }
         NDET_REQUIRE(outside == NDET_OUTSIDE_KEEP || outside == NDET_OUTSIDE_CULL, NDET_E_INVALID, "%s: outside=%d is neither keep nor cull", fn,
                      outside);
+        int64_t total = 0;
+        NDET_TRY(ndet_lattice_fill(fn, n_voxels[0], n_voxels[1], n_voxels[2], p0, vs, g, &total));
+        *n_words = (int)((total + 31) / 32);
     }
     NDET_REQUIRE(s1 - s0 <= 32, NDET_E_UNSUPPORTED, "%s: a segment of %d columns, at most 32", fn, s1 - s0);
     NDET_REQUIRE((int64_t)R * S < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: %lld samples, must be fewer than 2^31", fn,
                  (long long)((int64_t)R * S));
-    if (bits) {
-        const int64_t total = (int64_t)n_voxels[0] * n_voxels[1] * n_voxels[2];
-        NDET_REQUIRE(total < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: %lld voxels, must be fewer than 2^31", fn, (long long)total);
-        for (int k = 0; k < 3; ++k) {
-            g->p0[k] = p0[k];
-            g->vs[k] = vs[k];
-            g->n[k] = n_voxels[k];
-        }
-        *n_words = (int)((total + 31) / 32);
-    }
     NDET_REQUIRE(((uintptr_t)pts & 3) == 0 && ((uintptr_t)T & 3) == 0 && ((uintptr_t)bits & 3) == 0, NDET_E_UNSUPPORTED, "%s: misaligned pointer",
                  fn);
     *blocks = (ndet_front_blocks(R, s1 - s0) + 3) / 4;
@@ -165,7 +123,7 @@ static int fs_check(const char* fn, const float* pts, int R, int S, int s0, int 
 
 template <bool WRITE>
 static void fs_launch(int64_t blocks, int n_words, hipStream_t stream, const float* pts, int R, int S, int s0, int s1, const float* T, float eps,
-                      const uint32_t* bits, const FsLattice& g, int outside, int* block_count, const int* block_first, int* idx,
+                      const uint32_t* bits, const NdetLattice& g, int outside, int* block_count, const int* block_first, int* idx,
                       float* pts_kept) {
     const int w = s1 - s0, shift = fs_shift(w), keep = outside == NDET_OUTSIDE_KEEP;
     const size_t lds = (size_t)n_words * sizeof(uint32_t);
@@ -184,7 +142,7 @@ static void fs_launch(int64_t blocks, int n_words, hipStream_t stream, const flo
 extern "C" int ndet_front_count(const float* pts, int R, int S, int s0, int s1, const float* T, float eps, const uint32_t* bits,
                                 const int* n_voxels, const float* p0, const float* vs, int outside, int* block_count, void* stream) {
     const char* fn = "ndet_front_count";
-    FsLattice g;
+    NdetLattice g;
     int n_words = 0;
     int64_t blocks = 0;
     NDET_REQUIRE(block_count, NDET_E_INVALID, "%s: null pointer", fn);
@@ -199,7 +157,7 @@ extern "C" int ndet_front_write(const float* pts, int R, int S, int s0, int s1, 
                                 const int* n_voxels, const float* p0, const float* vs, int outside, const int* block_first, int* idx,
                                 float* pts_kept, void* stream) {
     const char* fn = "ndet_front_write";
-    FsLattice g;
+    NdetLattice g;
     int n_words = 0;
     int64_t blocks = 0;
     NDET_REQUIRE(block_first && idx && pts_kept, NDET_E_INVALID, "%s: null pointer", fn);

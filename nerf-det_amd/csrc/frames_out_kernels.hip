@@ -3,8 +3,8 @@
 // mmdet3d/models/model_utils/save_rendered_img.py:10-19,55,68).  Three memory-bound kernels, one element per thread, plain vector stores.
 //
 //   k_camera_rays   get_dtu_raydir (data_augment_utils.py:410-424, un-normalised) for the pixels px = x0 + j * stride, py = y0 + i * stride of
-//       n cameras that share one pair of intrinsic rows: k_target_rays' arithmetic in k_target_rays' operation order (pipeline_kernels.hip)
-//       without its frame -- x = ((float)px + 0.5f - k[2]) / k[0], y likewise, d_j = fmaf(y, R[j][1], x * R[j][0]) + R[j][2] -- and the
+//       n cameras that share one pair of intrinsic rows: k_target_rays' directions (pipeline_kernels.hip) without its frame, both through
+//       ndet_pixel_dir -- x = ((float)px + 0.5f - k[2]) / k[0], y likewise, d_j = fmaf(y, R[j][1], x * R[j][0]) + R[j][2] -- and the
 //       camera centre repeated per ray.  No image bound: a pose may look anywhere.
 //   k_pack_frames   float rgb in [0, 1] -> bytes, float metres -> uint16 millimetres, both round-half-up with saturation; NaN gives 0;
 //       a ray whose mask is false gets depth 0, the sensor's hole.  Channel order is kept (the bank's images are BGR planes already).
@@ -23,15 +23,11 @@ __global__ __launch_bounds__(256) void k_camera_rays(const float* __restrict__ k
     const int r = (int)(i - c * per);                 // one camera holds fewer than 2^31 rays
     const int row = r / w, col = r - row * w;
     const int px = x0 + col * stride, py = y0 + row * stride;
-    const float x = ((float)px + 0.5f - kn[2]) / kn[0];
-    const float y = ((float)py + 0.5f - kn[5]) / kn[4];
-    const float* R = rot + (int64_t)c * 9;
+    float d[3];
+    ndet_pixel_dir(kn, rot + (int64_t)c * 9, px, py, d);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        float d = x * R[j * 3 + 0];
-        d = fmaf(y, R[j * 3 + 1], d);
-        d = d + R[j * 3 + 2];
-        ray_d[i * 3 + j] = d;
+        ray_d[i * 3 + j] = d[j];
         ray_o[i * 3 + j] = lpos[(int64_t)c * 3 + j];
     }
 }

@@ -145,6 +145,47 @@ __device__ __forceinline__ NdetRayHit ndet_ray_project(const float* KE, float x,
     return r;
 }
 
+// Pixel (px, py) of a camera -> its ray direction, get_dtu_raydir un-normalised (data_augment_utils.py:410-424): kn = rows 0, 1 of the
+// intrinsics (2,3), R = the camera-to-world rotation (3,3).  One operation order for every kernel that casts a ray or lifts a pixel.
+__device__ __forceinline__ void ndet_pixel_dir(const float* __restrict__ kn, const float* __restrict__ R, int px, int py, float (&dir)[3]) {
+    const float x = ((float)px + 0.5f - kn[2]) / kn[0];
+    const float y = ((float)py + 0.5f - kn[5]) / kn[4];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        float d = x * R[j * 3 + 0];
+        d = fmaf(y, R[j * 3 + 1], d);
+        d = d + R[j * 3 + 2];
+        dir[j] = d;
+    }
+}
+
+// ... and one axis of the world point at depth z along it
+__device__ __forceinline__ float ndet_ray_point(float z, float dir, float centre) { return fmaf(z, dir, centre); }
+
+// Which box holds a point: the highest index among the n boxes (centre, half extents, cos yaw, sin yaw: 8 floats) that hold (x, y, z),
+// -1 for none; a NaN fails every test.  The boxes pass through LDS in batches, so all 256 threads of the workgroup call, `on` or not.
+#define NDET_BOX_BATCH 256
+__device__ __forceinline__ int ndet_box_of_point(const float* __restrict__ boxes, int n, bool on, float x, float y, float z) {
+    __shared__ float s_box[NDET_BOX_BATCH * 8];
+    int best = -1;
+    for (int base = 0; base < n; base += NDET_BOX_BATCH) {
+        const int here = min(NDET_BOX_BATCH, n - base);
+        __syncthreads();
+        for (int j = threadIdx.x; j < here * 8; j += 256) s_box[j] = boxes[(int64_t)base * 8 + j];
+        __syncthreads();
+        if (on) {
+            for (int j = 0; j < here; ++j) {
+                const float* B = s_box + j * 8;
+                const float dx = x - B[0], dy = y - B[1], dz = z - B[2];
+                const float lx = fmaf(dx, B[6], -(dy * B[7]));
+                const float ly = fmaf(dx, B[7], dy * B[6]);
+                if (fabsf(lx) <= B[3] && fabsf(ly) <= B[4] && fabsf(dz) <= B[5]) best = base + j;
+            }
+        }
+    }
+    return best;
+}
+
 // Depth gate of nerfdet.py:404-411 (include/nerfdet_hip.h, NdetDepthGate): one resized map, kernel-argument form.  The kernels
 // take it under a compile-time flag; their ungated instantiations never read it.
 struct NdetGateMap {

@@ -44,15 +44,11 @@ __global__ __launch_bounds__(256) void k_target_rays(const uint8_t* __restrict__
     const int r = (int)(i - t * per);
     const int px = margin + r % rw, py = margin + r / rw;
     const int f = tids[t];
-    const float x = ((float)px + 0.5f - kn[2]) / kn[0];
-    const float y = ((float)py + 0.5f - kn[5]) / kn[4];
-    const float* R = rot + (int64_t)f * 9;
+    float d[3];
+    ndet_pixel_dir(kn, rot + (int64_t)f * 9, px, py, d);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        float d = x * R[j * 3 + 0];
-        d = fmaf(y, R[j * 3 + 1], d);
-        d = d + R[j * 3 + 2];
-        raydirs[i * 3 + j] = d;
+        raydirs[i * 3 + j] = d[j];
         lightpos[i * 3 + j] = lpos[(int64_t)f * 3 + j];
     }
     const uint8_t* src = frames + (((int64_t)f * H + py) * W + px) * 3;

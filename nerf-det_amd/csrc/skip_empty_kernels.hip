@@ -1,15 +1,13 @@
 // Empty-space skipping for renders from a streamed scene (nerf-det_amd/streaming.py, skip_empty=), for gfx950:
 //   * ndet_occupancy_bits       the alpha a detect() computes at the voxel lattice (1 - exp(-relu(sigma)), nerfdet.py:255-257) -> a
-//                               dilated bit grid, bit n of word n >> 5 for voxel n = (ix ny + iy) nz + iz;
+//                               dilated bit grid (grid_common.hpp);
 //   * ndet_cull_count / _write  ordered compaction of sample points against that grid: the kept flat indices ascending, and their
 //                               points, the same bytes on every call (wave ballots and prefix popcounts, no atomics);
 //   * ndet_ray_view_count_bank  the view-bank sampler's count pass alone (ray_stats_kernels.hip, rb_project_round<false>): the valid
 //                               views of every sample through ndet_ray_project, lanes over views, no gathers.
 // A sample whose raw row is zero is an exact no-op in k_composite (ray_kernels.hip: a = 1 - expf(-0) = 0, wgt = 0, T (1 - 0 + 1e-10f) =
 // T), so "skipped" means "sigma = 0".  Plain vector stores only.  Compiled with -ffp-contract=off.
-#include "ndet_common.hpp"
-
-#include <cmath>
+#include "grid_common.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // alpha -> bits.  One thread per voxel; a wave's ballot is two whole words (64 consecutive voxels, 256 per workgroup).
@@ -21,22 +19,9 @@ __device__ __forceinline__ bool se_solid(const float* __restrict__ alpha, const 
 __global__ __launch_bounds__(256) void k_occupancy_bits(const float* __restrict__ alpha, const int64_t* __restrict__ count, int nx, int ny, int nz,
                                                         int n_total, float threshold, int dilate, uint32_t* __restrict__ bits, int n_words) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    bool set = false;
-    if (t < n_total) {
-        const int n = (int)t;
-        const int iz = n % nz, iy = (n / nz) % ny, ix = n / (nz * ny);
-        const int x0 = max(ix - dilate, 0), x1 = min(ix + dilate, nx - 1);
-        const int y0 = max(iy - dilate, 0), y1 = min(iy + dilate, ny - 1);
-        const int z0 = max(iz - dilate, 0), z1 = min(iz + dilate, nz - 1);
-        for (int x = x0; x <= x1; ++x)
-            for (int y = y0; y <= y1; ++y)
-                for (int z = z0; z <= z1; ++z) set = set || se_solid(alpha, count, (x * ny + y) * nz + z, threshold);
-    }
-    const unsigned long long b = __ballot(set);
-    const int64_t w = (t >> 6) * 2;                            // the wave's first word (t - lane is a multiple of 64)
-    const int lane = threadIdx.x & 63;
-    if (lane == 0 && w < n_words) bits[w] = (uint32_t)b;
-    if (lane == 32 && w + 1 < n_words) bits[w + 1] = (uint32_t)(b >> 32);
+    const bool set = t < n_total && ndet_any_neighbour((int)t, nx, ny, nz, dilate,
+                                                       [&](int, int, int, int m) { return se_solid(alpha, count, m, threshold); });
+    ndet_ballot_store_words(set, t, bits, n_words);
 }
 
 extern "C" int ndet_occupancy_bits(const float* alpha, const int64_t* count, int nx, int ny, int nz, float threshold, int dilate,
@@ -65,84 +50,47 @@ extern "C" int ndet_occupancy_bits(const float* alpha, const int64_t* count, int
 #define SE_WAVE_POINTS 512
 #define SE_LDS_BYTES (64 * 1024)
 
-struct SeLattice {
-    float p0[3], vs[3];
-    int n[3];
-};
-
-// nearest lattice point per axis, in this fp32 statement order: q = (x - p0) / vs; i = (int)floorf(q + 0.5f)
-__device__ __forceinline__ bool se_keep(const float* __restrict__ pts, int64_t p, const SeLattice& g, const uint32_t* bits, bool keep_outside,
-                                        float& x, float& y, float& z) {
-    x = pts[p * 3 + 0];
-    y = pts[p * 3 + 1];
-    z = pts[p * 3 + 2];
-    const float qx = (x - g.p0[0]) / g.vs[0], qy = (y - g.p0[1]) / g.vs[1], qz = (z - g.p0[2]) / g.vs[2];
-    const float fx = floorf(qx + 0.5f), fy = floorf(qy + 0.5f), fz = floorf(qz + 0.5f);
-    // the range test runs on the floats (equal to the test on the ints wherever the cast is defined; NaN and +-inf fail it)
-    const bool inside = isfinite(x) && isfinite(y) && isfinite(z) && fx >= 0.0f && fx < (float)g.n[0] && fy >= 0.0f && fy < (float)g.n[1] &&
-                        fz >= 0.0f && fz < (float)g.n[2];
-    if (!inside) return keep_outside;
-    const int n = ((int)fx * g.n[1] + (int)fy) * g.n[2] + (int)fz;
-    return (bits[n >> 5] >> (n & 31)) & 1u;
-}
-
-template <bool LDS>
-__device__ __forceinline__ const uint32_t* se_stage_bits(const uint32_t* __restrict__ bits, int n_words) {
-    extern __shared__ uint32_t s_bits[];
-    if (!LDS) return bits;
-    for (int i = threadIdx.x; i < n_words; i += 256) s_bits[i] = bits[i];
-    __syncthreads();
-    return s_bits;
-}
-
 template <bool LDS, bool WRITE>
 __global__ __launch_bounds__(256) void k_cull(const float* __restrict__ pts, int64_t n_points, const uint32_t* __restrict__ bits, int n_words,
-                                              SeLattice g, int keep_outside, int* __restrict__ block_count,
+                                              NdetLattice g, int keep_outside, int* __restrict__ block_count,
                                               const int* __restrict__ block_first, int* __restrict__ idx, float* __restrict__ pts_kept) {
-    const uint32_t* b = se_stage_bits<LDS>(bits, n_words);
+    const uint32_t* b = ndet_stage_bits<LDS>(bits, n_words);
     const int lane = threadIdx.x & 63;
     const int64_t wb = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // this wave's block of points
     const int64_t p0 = wb * SE_WAVE_POINTS;
     if (p0 >= n_points) return;                                           // wave-uniform, after the only barrier
-    int64_t at = WRITE ? block_first[wb] : 0;
-    int kept = 0;
+    NdetCompact c = ndet_compact_begin<WRITE>(block_first, wb);
     for (int i = 0; i < SE_WAVE_POINTS; i += 64) {
         const int64_t p = p0 + i + lane;
         float x = 0.0f, y = 0.0f, z = 0.0f;
-        const bool k = p < n_points && se_keep(pts, p, g, b, keep_outside != 0, x, y, z);
-        const unsigned long long m = __ballot(k);
+        bool k = p < n_points;
+        if (k) {
+            x = pts[p * 3 + 0];
+            y = pts[p * 3 + 1];
+            z = pts[p * 3 + 2];
+            k = ndet_grid_keep(x, y, z, g, b, keep_outside != 0);
+        }
+        const int64_t o = ndet_compact_step(c, k);
         if (WRITE && k) {
-            const int64_t o = at + __popcll(m & ((1ull << lane) - 1ull));
             idx[o] = (int)p;
             pts_kept[o * 3 + 0] = x;
             pts_kept[o * 3 + 1] = y;
             pts_kept[o * 3 + 2] = z;
         }
-        at += __popcll(m);
-        kept += __popcll(m);
     }
-    if (!WRITE && lane == 0) block_count[wb] = kept;
+    ndet_compact_end<WRITE>(c, block_count, wb);
 }
 
 static int se_cull_check(const char* fn, const float* pts, int64_t n_points, const uint32_t* bits, const int* n_voxels, const float* p0,
-                         const float* vs, int outside, SeLattice* g, int* n_words, int64_t* blocks) {
+                         const float* vs, int outside, NdetLattice* g, int* n_words, int64_t* blocks) {
     NDET_REQUIRE(pts && bits && n_voxels && p0 && vs, NDET_E_INVALID, "%s: null pointer", fn);
-    NDET_REQUIRE(n_points > 0 && n_voxels[0] > 0 && n_voxels[1] > 0 && n_voxels[2] > 0, NDET_E_INVALID, "%s: bad sizes", fn);
-    for (int k = 0; k < 3; ++k) {
-        NDET_REQUIRE(std::isfinite(vs[k]) && vs[k] > 0.0f, NDET_E_INVALID, "%s: voxel size %d must be positive and finite", fn, k);
-        NDET_REQUIRE(std::isfinite(p0[k]), NDET_E_INVALID, "%s: lattice origin %d must be finite", fn, k);
-    }
+    NDET_REQUIRE(n_points > 0, NDET_E_INVALID, "%s: bad sizes", fn);
     NDET_REQUIRE(outside == NDET_OUTSIDE_KEEP || outside == NDET_OUTSIDE_CULL, NDET_E_INVALID, "%s: outside=%d is neither keep nor cull", fn,
                  outside);
+    int64_t total = 0;
+    NDET_TRY(ndet_lattice_fill(fn, n_voxels[0], n_voxels[1], n_voxels[2], p0, vs, g, &total));
     NDET_REQUIRE(n_points < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: %lld points, must be fewer than 2^31", fn, (long long)n_points);
-    const int64_t total = (int64_t)n_voxels[0] * n_voxels[1] * n_voxels[2];
-    NDET_REQUIRE(total < ((int64_t)1 << 31), NDET_E_UNSUPPORTED, "%s: %lld voxels, must be fewer than 2^31", fn, (long long)total);
     NDET_REQUIRE(((uintptr_t)pts & 3) == 0 && ((uintptr_t)bits & 3) == 0, NDET_E_UNSUPPORTED, "%s: misaligned pointer", fn);
-    for (int k = 0; k < 3; ++k) {
-        g->p0[k] = p0[k];
-        g->vs[k] = vs[k];
-        g->n[k] = n_voxels[k];
-    }
     *n_words = (int)((total + 31) / 32);
     *blocks = (ndet_cull_blocks(n_points) + 3) / 4;
     NDET_REQUIRE(*blocks <= ((int64_t)1 << 24), NDET_E_UNSUPPORTED, "%s: more than 2^24 workgroups", fn);
@@ -151,7 +99,7 @@ static int se_cull_check(const char* fn, const float* pts, int64_t n_points, con
 
 template <bool WRITE>
 static void se_cull_launch(int64_t blocks, int n_words, hipStream_t stream, const float* pts, int64_t n_points, const uint32_t* bits,
-                           const SeLattice& g, int outside, int* block_count, const int* block_first, int* idx, float* pts_kept) {
+                           const NdetLattice& g, int outside, int* block_count, const int* block_first, int* idx, float* pts_kept) {
     const size_t lds = (size_t)n_words * sizeof(uint32_t);
     if (lds <= SE_LDS_BYTES)
         hipLaunchKernelGGL((k_cull<true, WRITE>), dim3((unsigned)blocks), dim3(256), lds, stream, pts, n_points, bits, n_words, g,
@@ -166,7 +114,7 @@ extern "C" int64_t ndet_cull_blocks(int64_t n_points) { return n_points > 0 ? (n
 extern "C" int ndet_cull_count(const float* pts, int64_t n_points, const uint32_t* bits, const int* n_voxels, const float* p0, const float* vs,
                                int outside, int* block_count, void* stream) {
     const char* fn = "ndet_cull_count";
-    SeLattice g;
+    NdetLattice g;
     int n_words = 0;
     int64_t blocks = 0;
     NDET_TRY(se_cull_check(fn, pts, n_points, bits, n_voxels, p0, vs, outside, &g, &n_words, &blocks));
@@ -180,7 +128,7 @@ extern "C" int ndet_cull_count(const float* pts, int64_t n_points, const uint32_
 extern "C" int ndet_cull_write(const float* pts, int64_t n_points, const uint32_t* bits, const int* n_voxels, const float* p0, const float* vs,
                                int outside, const int* block_first, int* idx, float* pts_kept, void* stream) {
     const char* fn = "ndet_cull_write";
-    SeLattice g;
+    NdetLattice g;
     int n_words = 0;
     int64_t blocks = 0;
     NDET_TRY(se_cull_check(fn, pts, n_points, bits, n_voxels, p0, vs, outside, &g, &n_words, &blocks));

@@ -1124,6 +1124,14 @@ def cloud_accumulate(sums: Tensor, n_voxels_fine, p0, vs, depth_r: Tensor, rgb: 
     return sums
 
 
+def compaction_offsets(counts: Tensor):
+    """Between the two launches of an ordered compaction (csrc/grid_common.hpp): the count pass' ``counts`` (blocks,) int32 -> ``(first,
+    M)``, the exclusive prefix sum that the write pass reads and the number of kept elements.  M reaches the host in ONE device-to-host
+    read, the compaction's only synchronisation; the caller skips the write launch when ``M = 0``."""
+    last = torch.cumsum(counts, 0, dtype=torch.int32)
+    return last - counts, int(last[-1])                        # the one read
+
+
 def cloud_points(segments: Sequence[Tensor], n_voxels_fine, p0, vs, min_points: int = 1) -> dict:
     """1 .. 64 segments of :func:`cloud_accumulate` records over one fine lattice -> ``dict(xyz (M,3) float32, bgr (M,3) uint8, count (M,)
     int32, voxel (M,) int32)``: one point per fine voxel whose count, summed over the segments, is ``min_points`` or more, in ascending
@@ -1142,9 +1150,7 @@ def cloud_points(segments: Sequence[Tensor], n_voxels_fine, p0, vs, min_points: 
     counts = torch.empty((int(lib.ndet_cloud_blocks(n)),), dtype=torch.int32, device=dev)
     trace.span("k_cloud_count", lambda: check(lib.ndet_cloud_count(ptrs, len(segments), *geom, _ptr(counts), _stream(counts)), "cloud_count"),
                bytes=32 * n * len(segments) + 4 * counts.numel(), kind="hbm")
-    last = torch.cumsum(counts, 0, dtype=torch.int32)
-    first = last - counts
-    m = int(last[-1])                                          # the one read
+    first, m = compaction_offsets(counts)
     out = dict(xyz=torch.empty((m, 3), dtype=torch.float32, device=dev), bgr=torch.empty((m, 3), dtype=torch.uint8, device=dev),
                count=torch.empty((m,), dtype=torch.int32, device=dev), voxel=torch.empty((m,), dtype=torch.int32, device=dev))
     if m:

@@ -486,6 +486,11 @@ class CloudStore(CarveStore):
         del self.pixels[:k_segments]
 
 
+def _kept_points(m: int, device):
+    """What a compaction of points returns: ``(idx (M,) int32, pts_kept (M, 3) float32)``, to be written."""
+    return torch.empty((m,), dtype=torch.int32, device=device), torch.empty((m, 3), dtype=torch.float32, device=device)
+
+
 def cull_points(pts: Tensor, occ: OccupancyGrid):
     """Ordered compaction of ``pts`` (..., 3) against ``occ``: ``(idx (M,) int32, pts_kept (M, 3))``, the flat indices of the kept points
     in ascending order and those points.  Per axis, in float32, ``i = int(floor((x - p0) / voxel_size + 0.5))`` is the nearest lattice
@@ -505,11 +510,8 @@ def cull_points(pts: Tensor, occ: OccupancyGrid):
     counts = torch.empty((int(lib.ndet_cull_blocks(n)),), dtype=torch.int32, device=p.device)
     trace.span("k_cull_count", lambda: check(lib.ndet_cull_count(_ptr(p), n, _ptr(occ.bits), *geom, _ptr(counts), _stream(p)), "cull_count"),
                bytes=12 * n + 4 * counts.numel(), kind="hbm")
-    last = torch.cumsum(counts, 0, dtype=torch.int32)
-    first = last - counts
-    m = int(last[-1])                                          # the one read
-    idx = torch.empty((m,), dtype=torch.int32, device=p.device)
-    kept = torch.empty((m, 3), dtype=torch.float32, device=p.device)
+    first, m = ops.compaction_offsets(counts)
+    idx, kept = _kept_points(m, p.device)
     if m:
         trace.span("k_cull_write", lambda: check(lib.ndet_cull_write(_ptr(p), n, _ptr(occ.bits), *geom, _ptr(first), _ptr(idx), _ptr(kept),
                                                                      _stream(p)), "cull_write"),
@@ -573,11 +575,8 @@ def front_segment(pts: Tensor, T: Tensor, s0: int, s1: int, eps: float, occ: Opt
         counts = torch.empty((blocks,), dtype=torch.int32, device=p.device)
         trace.span("k_front_count", lambda: check(lib.ndet_front_count(_ptr(p), r, s, s0, s1, _ptr(T), eps, *geom, _ptr(counts), _stream(p)),
                                                   "front_count"), bytes=4 * r + (12 * r * w if occ is not None else 0) + 4 * blocks, kind="hbm")
-        last = torch.cumsum(counts, 0, dtype=torch.int32)
-        first = last - counts
-        m = int(last[-1])                                      # the one read
-    idx = torch.empty((m,), dtype=torch.int32, device=p.device)
-    kept = torch.empty((m, 3), dtype=torch.float32, device=p.device)
+        first, m = ops.compaction_offsets(counts)
+    idx, kept = _kept_points(m, p.device)
     if m:
         trace.span("k_front_write", lambda: check(lib.ndet_front_write(_ptr(p), r, s, s0, s1, _ptr(T), eps, *geom, _ptr(first), _ptr(idx),
                                                                        _ptr(kept), _stream(p)), "front_write"),
