@@ -169,7 +169,8 @@ def _dx_slots_are_exact(outs, arith, n=1):
 
 def _poison(device, *sizes):
     """NaN into what the launch is about to take with torch.empty / new_zeros -- the padded dy, the upsample buffer, the split-K workspace, the result:
-    the caching allocator hands a freed block to the next request of its size (tests/test_wgrad_shapes_gpu.py::_poison)."""
+    the caching allocator hands a freed block to the next request of its size (tests/test_wgrad_shapes_gpu.py::_poison).
+    That is the allocator's habit, not a guarantee: tests/redzone.py carves every such allocation and fills it itself (tests/test_redzone_train_gpu.py)."""
     blocks = [torch.full((int(n),), float("nan"), device=device) for n in sizes if n]
     del blocks
 

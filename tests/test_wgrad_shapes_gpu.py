@@ -194,7 +194,8 @@ def _expect_plan(name, arith, wide=True):
 def _poison(device, taps, cin, cout, splits):
     """NaN into what weight_grad is about to take with torch.empty -- the split-K workspace, the GEMM rows, the result: the caching allocator hands a
     freed block to the next request of its size, and a tile or a split the kernel never writes would otherwise read what an earlier case of the same
-    shape left there (seen with a broken remap: the stale partials of the previous case were the right answer)."""
+    shape left there (seen with a broken remap: the stale partials of the previous case were the right answer).
+    That is the allocator's habit, not a guarantee: tests/redzone.py carves every such allocation and fills it itself (tests/test_redzone_train_gpu.py)."""
     blocks = [torch.full((n,), float("nan"), device=device) for n in (splits * taps * cin * cout, taps * cin * cout, cout * cin * taps)]
     del blocks
 
